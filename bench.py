@@ -9,7 +9,13 @@
 One rank per GPU; albums/questions are sharded over ranks (weak scaling: 64 QA
 pairs per GPU), the only collective is the all-reduce of the flat gradient
 buffer.  Inputs (synthetic, seeded) are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line.  `roofline` is for the DOMINANT kernel of the step
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and
+prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`
+and the timed region's own per-step figures); `--dump-outputs DIR` first writes what
+the last timed step computed as DIR/<name>.npy.
+
+Everything else needs runs of its own and comes with `--full` only:
+`roofline` is for the DOMINANT kernel of the step
 (largest `kernel_ms_per_step` entry; today the bi-LSTM backward step), every other
 bracketed kernel has its own `roofline_<name>` object.  Kernel durations come from
 HIP events recorded on the launch stream inside the library (fvta_profile_*), live,
@@ -102,8 +108,18 @@ def parse(argv=None):
                     help="freeze: gc.collect(); gc.freeze(); gc.disable() once the model and the batch are built, as a training "
                          "loop that owns its process does (a generation-2 pass over torch's and numpy's heaps is a pause of tens of "
                          "milliseconds on the host); default: CPython's collector left alone (diagnosis)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the HBM probe, the bracketed kernel pass (rooflines, kernel_ms_per_step), the "
+                         "`also` cases and the CPU baseline (--also / --no-cpu-baseline trim a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, yp, logits; the train step also "
+                         "the updated weights and their gradients, in the reference's shapes) as DIR/<name>.npy, float32, "
+                         "at most 64 MB in all (larger arrays: a fixed seeded sample of their elements)")
     ap.add_argument("--also-helper", action="store_true", help=argparse.SUPPRESS)   # internal: the `also` orchestrator (no GPU)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.also == "on" and not args.full:
+        ap.error("--also on needs --full")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ self-launch --
@@ -205,6 +221,37 @@ def cpu_baseline(spec_kw, sample_n, forward_only, threads, literal_n=1):
     except Exception:
         pass
     return out
+
+
+# ------------------------------------------------------------------------------------------------ output dump --
+DUMP_BYTES = 63 * 1000 * 1000      # 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(dirname, model, trained):
+    """--dump-outputs: what the last timed step computed, as a caller of that path receives it -- the loss, the answer
+    probabilities `yp` and the logits, and after a train step the updated weights and their gradients under the reference's
+    variable names ('/' -> '.').  float32 .npy files.  When they would exceed DUMP_BYTES, every array of more than 4096
+    elements is cut to a seeded sample of its elements (flattened; the same indices for the same name and size)."""
+    import zlib
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in (("loss", model.loss), ("yp", model.yp), ("logits", model.logits))
+              if v is not None}
+    if trained:
+        for kind, grad in (("weight", False), ("grad", True)):
+            for name, v in model.get_weights(grad=grad).items():
+                arrays["%s.%s" % (kind, name.replace("/", "."))] = np.asarray(v, dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        big = sum(a.nbytes for a in arrays.values() if a.size > 4096)
+        keep = (DUMP_BYTES - (total - big)) / big
+        for k, a in arrays.items():
+            if a.size > 4096:
+                idx = np.random.default_rng(zlib.crc32(k.encode())).choice(a.size, max(4096, int(a.size * keep)), replace=False)
+                arrays[k] = a.reshape(-1)[np.sort(idx)]
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    log("outputs of the last timed step: %d arrays, %.1f MB in %s" % (len(arrays), sum(a.nbytes for a in arrays.values()) / 1e6, dirname))
 
 
 # --------------------------------------------------------------------------------------------------- one case --
@@ -342,25 +389,30 @@ def run_case(args, lib, ws, rank, local, probe_gbs=None):
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
     log('timed region done: %.3f s for %d steps (per-step HIP events: median %.3f ms)'
         % (elapsed, args.steps, statistics.median(step_ms)))
-    # ---- a second pass of the same steps with the library's HIP-event brackets around the kernels the rooflines
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, trained=not args.forward_only)
+    # ---- (--full) a second pass of the same steps with the library's HIP-event brackets around the kernels the rooflines
     # are quoted for (events on the launch streams); kept out of the headline
-    lib.fvta_profile_enable(1)
-    lib.fvta_lstm_bwd_kernel_counts((ctypes.c_int64 * 3)())      # (reading resets the counters)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    lib.fvta_profile_enable(0)
-    dist.barrier()
+    prof = {name: (0.0, 0) for name, _ in PROF_IDS}
+    bwd_counts = {}
+    if args.full:
+        lib.fvta_profile_enable(1)
+        lib.fvta_lstm_bwd_kernel_counts((ctypes.c_int64 * 3)())      # (reading resets the counters)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        lib.fvta_profile_enable(0)
+        dist.barrier()
 
-    def collect(pid):
-        ms, n = ctypes.c_double(0), ctypes.c_int64(0)
-        lib.fvta_profile_collect(pid, ctypes.byref(ms), ctypes.byref(n))
-        return ms.value, n.value
+        def collect(pid):
+            ms, n = ctypes.c_double(0), ctypes.c_int64(0)
+            lib.fvta_profile_collect(pid, ctypes.byref(ms), ctypes.byref(n))
+            return ms.value, n.value
 
-    prof = {name: collect(pid) for name, pid in PROF_IDS}
-    bwd_counts = (ctypes.c_int64 * 3)()
-    lib.fvta_lstm_bwd_kernel_counts(bwd_counts)     # text-cell backward-step launches by kernel since the bracketed pass began
-    bwd_counts = dict(zip(("lstm_bwd_fused_bf16", "lstm_bwd_ring_bf16", "lstm_bwd_wreg_bf16"), (int(v) for v in bwd_counts)))
+        prof = {name: collect(pid) for name, pid in PROF_IDS}
+        bwd_counts = (ctypes.c_int64 * 3)()
+        lib.fvta_lstm_bwd_kernel_counts(bwd_counts)     # text-cell backward-step launches by kernel since the bracketed pass began
+        bwd_counts = dict(zip(("lstm_bwd_fused_bf16", "lstm_bwd_ring_bf16", "lstm_bwd_wreg_bf16"), (int(v) for v in bwd_counts)))
     if rank != 0:
         return None, kw
     total_qa = spec.N * ws * args.steps
@@ -479,7 +531,7 @@ def run_case(args, lib, ws, rank, local, probe_gbs=None):
             hbm_roof("attention_bwd", "attn_bwd_main", "attn_bwd_main", valid_rows * model.wp * (row_b + 4.0),
                      traffic=("r06_attention_pmc.json", "attn_bwd_main<256, 1, 32, false, false, true>" if shadow else "attn_bwd_main<256, 1, 32, false, false, false>"))
     # the DOMINANT kernel of the step (largest bracketed time per step) is `roofline`; the rest are roofline_<name>
-    kms = {k: round(v[0] / args.steps, 4) for k, v in prof.items()}
+    kms = {k: round(v[0] / args.steps, 4) for k, v in prof.items()} if args.full else {}
     order = sorted(roofs, key=lambda k: -roofs[k]["ms_per_step"])
     for r in roofs.values():         # the line stays short enough for the driver's record: the notes live in DESIGN.md section 5
         r.pop("note", None)
@@ -561,7 +613,7 @@ def also_helper():
         if only and name not in only:
             continue
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm),
-               "--also", "off", "--no-cpu-baseline", "--gc", os.environ.get("FVTA_BENCH_GC", "freeze")] + over
+               "--full", "--also", "off", "--no-cpu-baseline", "--gc", os.environ.get("FVTA_BENCH_GC", "freeze")] + over
         t0 = time.perf_counter()
         try:
             pr = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True, timeout=900,
@@ -593,7 +645,7 @@ def main():
                         and args.graph == "fvta" and not args.front_end and not args.batch and args.scaling == "weak"
                         and not args.time_warp)
     helper = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and (args.also == "on" or (args.also == "auto" and default_headline)):
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and (args.also == "on" or (args.also == "auto" and default_headline)):
         # the `also` orchestrator must exist before this process initialises the GPU; it sleeps until told to go
         helper = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--also-helper"], stdin=subprocess.PIPE,
                                   stdout=subprocess.PIPE, text=True, env=dict(os.environ, FVTA_BENCH_GC=args.gc))
@@ -615,7 +667,7 @@ def main():
 
     # achievable HBM read rate on THIS device: one coalesced read-only pass over 1.5 GiB, median of 5
     probe_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             pbuf = torch.empty(3 << 28, dtype=torch.float32, device=dev).zero_()       # 1.5 GiB, about the context tensor
             sink = torch.zeros(16, dtype=torch.float32, device=dev)
@@ -651,8 +703,8 @@ def main():
             out["also"] = json.loads(line)
         except Exception as exc:
             out["also"] = dict(error=repr(exc))
-        out["also_note"] = "each case: a fresh `python bench.py <args> --also off` process right after the headline; rooflines = [frac of HBM (lstm_dw: of MFMA), avg_launch_ms]; step_ms = [min, median, max]"
-    if ws == 1 and not args.no_cpu_baseline and args.graph == "fvta":
+        out["also_note"] = "each case: a fresh `python bench.py <args> --full --also off` process right after the headline; rooflines = [frac of HBM (lstm_dw: of MFMA), avg_launch_ms]; step_ms = [min, median, max]"
+    if args.full and ws == 1 and not args.no_cpu_baseline and args.graph == "fvta":
         log('timing the CPU oracle (%d threads of %d host CPUs)' % (args.cpu_threads, host_cores()))
         out["cpu_baseline"] = cpu_baseline(kw, args.cpu_sample, args.forward_only, args.cpu_threads)
     else:

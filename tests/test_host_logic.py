@@ -189,6 +189,39 @@ def test_bench_also_helper_exits_quietly_without_go():
     assert r.returncode == 0 and r.stdout.strip() == ""
 
 
+def test_bench_plain_run_options_and_output_dump(tmp_path):
+    """bench.py: a plain run keeps the side measurements off (`--also on` needs `--full`); `--dump-outputs` writes float32
+    .npy files of at most 64 MB in all, an oversized array cut to a seeded sample that is the same run to run."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 2, False, None)
+    with pytest.raises(SystemExit):
+        bench.parse(["--also", "on"])
+    assert bench.parse(["--full", "--also", "on", "--dump-outputs", "d"]).dump_outputs == "d"
+
+    class Stub:
+        loss, yp, logits = torch.tensor([1.5]), torch.rand(4, 4, dtype=torch.float64), torch.randn(4, 4)
+
+        def get_weights(self, grad=False):
+            g = torch.Generator().manual_seed(int(grad))
+            return {"reader/text/kernel": torch.randn(6000, 4000, generator=g).numpy(), "output/b": np.ones(1, np.float32)}
+
+    bench.dump_outputs(str(tmp_path / "a"), Stub(), trained=True)
+    bench.dump_outputs(str(tmp_path / "b"), Stub(), trained=False)
+    bench.dump_outputs(str(tmp_path / "c"), Stub(), trained=True)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grad.output.b.npy", "grad.reader.text.kernel.npy", "logits.npy", "loss.npy", "weight.output.b.npy",
+                     "weight.reader.text.kernel.npy", "yp.npy"]
+    assert sorted(os.listdir(tmp_path / "b")) == ["logits.npy", "loss.npy", "yp.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "c" / f)
+        assert x.dtype == np.float32 and np.array_equal(x, y), f
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "yp.npy"), Stub.yp.float().numpy())
+    w = np.load(tmp_path / "a" / "weight.reader.text.kernel.npy")
+    assert 4096 < w.size < 6000 * 4000 and np.isin(w[:100], Stub().get_weights()["reader/text/kernel"]).all()
+
+
 def test_trainer_owns_and_releases_the_collector():
     """Trainer.own_host (called by the first step_device under config gc_freeze, default on): CPython's collector frozen and
     off while a trainer steps, back on when it releases the host or goes away; gc_freeze=False never touches it."""

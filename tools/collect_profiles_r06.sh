@@ -10,12 +10,12 @@ out=gpurun_out/$tag
 mkdir -p "$out"
 export TMPDIR=/tmp
 cp tools/.collect_head "$out/head.txt" 2>/dev/null || echo "unknown" > "$out/head.txt"
-timeout 1200 python3 bench.py > $out/bench_metric.json 2> $out/bench_metric.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks -o ks -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --also off > $out/ks_bench.json 2> $out/ks.err
+timeout 1200 python3 bench.py --full > $out/bench_metric.json 2> $out/bench_metric.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks -o ks -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --also off > $out/ks_bench.json 2> $out/ks.err
 cp "$(find $out/ks -name "*kernel_stats.csv" | head -1)" $out/kernel_stats.csv 2>/dev/null
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks_ragged -o ks -- python3 bench.py --variant ragged --steps 5 --warmup 2 --no-cpu-baseline --also off > $out/ks_ragged_bench.json 2> $out/ks_ragged.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks_ragged -o ks -- python3 bench.py --full --variant ragged --steps 5 --warmup 2 --no-cpu-baseline --also off > $out/ks_ragged_bench.json 2> $out/ks_ragged.err
 cp "$(find $out/ks_ragged -name "*kernel_stats.csv" | head -1)" $out/kernel_stats_ragged.csv 2>/dev/null
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks_x3 -o ks -- python3 bench.py --precision bf16x3 --steps 3 --warmup 2 --no-cpu-baseline --also off > $out/ks_x3_bench.json 2> $out/ks_x3.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks_x3 -o ks -- python3 bench.py --full --precision bf16x3 --steps 3 --warmup 2 --no-cpu-baseline --also off > $out/ks_x3_bench.json 2> $out/ks_x3.err
 cp "$(find $out/ks_x3 -name "*kernel_stats.csv" | head -1)" $out/kernel_stats_bf16x3.csv 2>/dev/null
 pmc() {  # pmc <dir> <script and args...>
   d=$1; shift; mkdir -p $d
@@ -40,7 +40,7 @@ if [ "${2:-}" = "full" ]; then
   pmc $out/pmc_attn tools/bench_attn_shadow.py;   cp $out/pmc_attn/summary.json $out/attention_pmc.json   # fp32-row and shadow-row kernels
   pmc $out/pmc_attn_wide tools/bench_attn_wide.py; cp $out/pmc_attn_wide/summary.json $out/attention_wide_pmc.json
   # one rank through the launcher: the collective path (RCCL communicator, flat-gradient all-reduce) on the one GPU there is
-  FVTA_DIST_FORCE=1 timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --also off > $out/bench_rccl_one_rank.json 2>/dev/null
-  timeout 600 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --also off > $out/bench_plain_same_box.json 2>/dev/null
+  FVTA_DIST_FORCE=1 timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --also off > $out/bench_rccl_one_rank.json 2>/dev/null
+  timeout 600 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --also off > $out/bench_plain_same_box.json 2>/dev/null
 fi
 head -30 $out/kernel_stats.csv | cut -c1-150

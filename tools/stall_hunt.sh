@@ -3,12 +3,12 @@
 # event median).  Fresh box: the FIRST process is the driver's own command; then fresh processes of the three cases
 # that showed it, five each, collector left alone / frozen.
 out=gpurun_out/stall; mkdir -p $out
-python bench.py --gpus 1 --steps 20 --warmup 5 --gc default > $out/first_default.json 2> $out/first_default.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --gc default > $out/first_default.json 2> $out/first_default.err
 for mode in default freeze; do
   for i in 1 2 3 4 5; do
-    python bench.py --steps 20 --warmup 5 --also off --no-cpu-baseline --gc $mode > $out/head_${mode}_$i.json 2>/dev/null
-    python bench.py --steps 10 --warmup 3 --also off --no-cpu-baseline --gc $mode --variant ragged > $out/ragged_${mode}_$i.json 2>/dev/null
-    python bench.py --steps 5 --warmup 2 --also off --no-cpu-baseline --gc $mode --time-warp 5 > $out/tw_${mode}_$i.json 2>/dev/null
+    python bench.py --full --steps 20 --warmup 5 --also off --no-cpu-baseline --gc $mode > $out/head_${mode}_$i.json 2>/dev/null
+    python bench.py --full --steps 10 --warmup 3 --also off --no-cpu-baseline --gc $mode --variant ragged > $out/ragged_${mode}_$i.json 2>/dev/null
+    python bench.py --full --steps 5 --warmup 2 --also off --no-cpu-baseline --gc $mode --time-warp 5 > $out/tw_${mode}_$i.json 2>/dev/null
   done
 done
 python - <<'PY'

@@ -5,8 +5,8 @@ out=gpurun_out/stall2; mkdir -p $out
 ls /sys/class/drm/ > $out/drm.txt 2>&1; which rocm-smi amd-smi >> $out/drm.txt 2>&1
 run_set() {   # $1 = tag
   for i in 1 2 3; do
-    python bench.py --steps 20 --warmup 5 --also off --no-cpu-baseline > $out/head_$1_$i.json 2>/dev/null
-    python bench.py --steps 10 --warmup 3 --also off --no-cpu-baseline --variant ragged > $out/ragged_$1_$i.json 2>/dev/null
+    python bench.py --full --steps 20 --warmup 5 --also off --no-cpu-baseline > $out/head_$1_$i.json 2>/dev/null
+    python bench.py --full --steps 10 --warmup 3 --also off --no-cpu-baseline --variant ragged > $out/ragged_$1_$i.json 2>/dev/null
   done
 }
 run_set none

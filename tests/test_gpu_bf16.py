@@ -4,18 +4,55 @@ The fragment maps are checked EXACTLY (operands pre-rounded to bf16, so only fp3
 order differs).  The LSTM / whole-model results are compared with the fp64 oracle at a bf16
 tolerance (operands carry 8 significant bits): 3e-2 absolute on activations in [-1,1],
 and the fp32 engine remains the 1e-4 parity path."""
+import math
+import os
+
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-F32, BF16 = 0, 1
+F32, BF16, BF16X3 = 0, 1, 2
 
 
 def _close(a, b, rtol, atol, msg=""):
     a = a.detach().cpu().double().numpy()
     b = b.detach().cpu().double().numpy()
     np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
+
+
+def _dx_row_error(dx, ref):
+    """max over (b, t) of |dx[b,t] - ref[b,t]| / (|ref[b,t]| + 0.1 x the rms row norm): one row the kernel got wrong or
+    never wrote scores about 1, however many rows the tensor has -- whole-tensor relative L2 dilutes it by sqrt(rows)"""
+    a, b = dx.detach().cpu().double(), ref.detach().cpu().double()
+    rn = b.norm(dim=-1)
+    live = rn > 0
+    rms = float(rn[live].pow(2).mean().sqrt()) if bool(live.any()) else 1.0
+    return float(((a - b).norm(dim=-1) / (rn + 0.1 * rms)).max())
+
+
+def _split_bwd_tiles(B, d, hint=None):
+    """The split engine's backward step tile for each step, restating launch_bwd_fused_xm (csrc/lstm_bf16.hip:471-516;
+    launch_bwd_wreg never takes XM = 2, lstm_wreg_bwd.hip:612).  hint: the host's active rows per step (None: unknown,
+    the launcher sizes by B).  -> one of "photo", "w1m1", "w1m2", "t224" (<2,4,2,64,2,56>), "t256" (<2,4,2,64,2>),
+    "t1x4" (<1,4,2,64,2>) per step -- so that a change of the heuristics moves no case silently onto another kernel."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rpw_on = not os.environ.get("FVTA_BWD_RPW", "").startswith("64")
+    tiles = []
+    for h in (hint if hint is not None else [None]):
+        if B <= 64 and d % 128 == 0:
+            tiles.append("photo")
+        elif B <= 64:
+            tiles.append("w1m1")
+        elif B <= 128:
+            tiles.append("w1m2")
+        elif d % 256 == 0 and not (h is not None and h >= 0 and 4 * math.ceil(h / 256) <= 160):
+            rows, percol = (h if h is not None and h >= 0 else B), 2 * (d // 256)
+            t256, tr = math.ceil(rows / 256) * percol, math.ceil(rows / 224) * percol
+            tiles.append("t224" if rpw_on and t256 <= cus and tr <= cus and tr > t256 else "t256")
+        else:
+            tiles.append("t1x4")
+    return tiles
 
 
 @pytest.mark.parametrize("layout", [1, 2])
@@ -103,11 +140,16 @@ def test_bilstm_bf16_forward_backward(B, J, din, d, dense, share):
         err = (a - b).norm() / (b.norm() + 1e-30)
         assert err < tol, "%s: relative L2 error %.4f" % (name, err)
 
+    # per row: one wrong or skipped 56-row wave tile is ~4.5 % of dx's whole-tensor norm at 9000 x 3, but ~1 here
+    # (measured: at most 0.0097 over these cases)
+    row = _dx_row_error(dx, leaves[0].grad)
+    print("bf16 engine B=%d J=%d din=%d d=%d: dx per-row error %.4g" % (B, J, din, d, row))
     rel(dx, leaves[0].grad, "dx")
     rel(dkf, leaves[1].grad, "dkernel_fw")
     rel(dbf, leaves[2].grad, "dbias_fw")
     if not share:
         rel(dkb, leaves[3].grad, "dkernel_bw")
+    assert row < 0.03, "dx: per-row error %.4f" % row
 
 
 def test_model_bf16_matches_oracle_loosely_and_fp32_engine_closely():
@@ -167,14 +209,17 @@ def test_bilstm_bf16_backward_overlapped_equals_serial(B, J, din, d, dense):
         _close(cur[0], ref[0], rtol=1e-5, atol=1e-6, msg="dx")
 
 
-def test_backward_with_host_lengths_hint_is_bitwise_the_same(monkeypatch):
+@pytest.mark.parametrize("precision,B,J,din,d", [(BF16, 700, 9, 16, 256), (BF16X3, 700, 9, 16, 256),
+                                                 # split engine at the text cell's width: the hint moves steps 1-5 from
+                                                 # the 224-row tile to <1,4,2,64,2>; the wrong hints put every step on one
+                                                 (BF16X3, 13000, 6, 200, 512)],
+                         ids=["bf16", "bf16x3", "bf16x3-d512-13000"])
+def test_backward_with_host_lengths_hint_is_bitwise_the_same(precision, B, J, din, d):
     """fvta_bilstm_bwd_hint: the host's knowledge of the lengths only picks each step's block tile (few active rows: the
     small one) -- gradients are bitwise those of the unhinted call, also under a WRONG hint (costs time, never
     correctness)."""
     from fvta_memexqa_amd import ops
-    from fvta_memexqa_amd._lib import BF16
     g = torch.Generator().manual_seed(31)
-    B, J, din, d = 700, 9, 16, 256
     x = torch.randn(B, J, din, generator=g).cuda()
     lens = torch.randint(0, J + 1, (B,), generator=g)
     lim = (6.0 / (din + d + 4 * d)) ** 0.5
@@ -182,7 +227,12 @@ def test_backward_with_host_lengths_hint_is_bitwise_the_same(monkeypatch):
     b = (torch.randn(4 * d, generator=g) * 0.1).cuda()
     mask = (torch.arange(J)[None, :] < lens[:, None])
     g_out = (torch.randn(B, J, 2 * d, generator=g) * mask[:, :, None]).cuda()
-    out, last, op = ops.bilstm_simple(x, lens, k, b, None, None, training=True, precision=BF16)
+    if d == 512:
+        nact = [int((lens > t).sum()) for t in range(J)]
+        assert _split_bwd_tiles(B, d) == ["t224"] and _split_bwd_tiles(B, d, [B] * J) == ["t224"] * J
+        assert _split_bwd_tiles(B, d, nact) == ["t224"] + ["t1x4"] * (J - 1), nact
+        assert _split_bwd_tiles(B, d, [0] * J) == ["t1x4"] * J
+    out, last, op = ops.bilstm_simple(x, lens, k, b, None, None, training=True, precision=precision)
 
     def grads(hint):
         op.set_active_hint(hint)
@@ -213,8 +263,35 @@ def test_bilstm_bf16x3_meets_the_fp32_tolerances(B, J, din, d, dense, share):
     fp32 saved gates -- the bi-LSTM forward and every gradient against autograd of the fp64 oracle at north_star's
     tolerance, 1e-4 relative (rtol 1e-4 plus 3e-5 x max|ref| absolute: a two-term bf16 split carries 16-17 significant
     bits per operand, so a sum of K products is good to ~2e-5 of its scale -- the exact-fp32 engine's tests hold 1e-5)."""
+    _bf16x3_vs_oracle(B, J, din, d, dense, share)
+
+
+# the sizes bench.py times (train_bf16x3: ~12,900 active rows per step in the text cell) and the launcher branches around
+# them, 256 CUs assumed (each case asserts its backward tiles per step, _split_bwd_tiles).  Forward: lstm_fwd_wreg_bf16
+# <WregCfg<14, 32, 1, true>> (din 200) / <8, 32, 1, true> (din 100) over hundreds of 32-row tiles; dx: both directions in
+# one wide launch (din 200) / the narrow lstm_dx_bf16<1, 64, 2, ..., 2> (din 100, B > 64)
+@pytest.mark.parametrize("B,J,din,d,dense,share,hint,tiles", [
+    # the timed size: 58 tiles of 224 rows, the last one 138 rows (wave 2 partial, wave 3 empty); lstm_dw_x2 with 6
+    # slabs padded to 8 XCD slots
+    (12906, 3, 200, 512, True, True, False, {"t224"}),
+    # last 224-row tile 84 rows (wave 1 partial), tiles above each step's active rows idle; J = 17: the weight
+    # gradient's last step group holds one step, 18 slabs
+    (2100, 17, 200, 512, False, False, False, {"t224"}),
+    # the host's lengths: step 0 (> 10,240 active rows) on the 224-row tile, the later steps on <1,4,2,64,2>
+    (13000, 6, 200, 512, False, True, True, {"t224", "t1x4"}),
+    (200, 4, 200, 512, True, True, False, {"t256"}),         # t256 == tr: the plain 256-row tile
+    (16500, 2, 200, 512, True, True, False, {"t256"}),       # t256 > CUs: the 256-row tile at scale
+    (3000, 4, 100, 512, False, True, False, {"t224"}),       # narrow input: WregCfg<8,32,1,true>, narrow dx
+], ids=["timed-12906x3-t224", "ragged-2100x17-t224-sep", "hint-13000x6-t224-t1x4", "dense-200x4-t256",
+        "dense-16500x2-t256", "narrow-3000x4-din100"])
+def test_bilstm_bf16x3_at_the_timed_sizes_meets_the_fp32_tolerances(B, J, din, d, dense, share, hint, tiles):
+    """The split engine at the sizes its benchmark runs, one case per backward-tile branch: every output and gradient
+    against the fp64 oracle at the same 1e-4 tolerances as the small cases above, dx also per row."""
+    _bf16x3_vs_oracle(B, J, din, d, dense, share, hint=hint, tiles=tiles)
+
+
+def _bf16x3_vs_oracle(B, J, din, d, dense, share, hint=False, tiles=None):
     from fvta_memexqa_amd import ops
-    from fvta_memexqa_amd._lib import BF16X3
     from oracle import fvta_fused as F
     g = torch.Generator().manual_seed(B + J + d + 1)
     x = torch.randn(B, J, din, generator=g)
@@ -233,11 +310,20 @@ def test_bilstm_bf16x3_meets_the_fp32_tolerances(B, J, din, d, dense, share):
     ((ref_out * g_out.double()).sum() + (ref_last * g_last.double()).sum()).backward()
     cu = lambda t: None if t is None else t.cuda().contiguous()
     xc, kf, bf, kb, bb = cu(x), cu(k_fw), cu(b_fw), cu(k_bw), cu(b_bw)
+    nact = [int((lens > t).sum()) for t in range(J)]
+    if tiles is not None:
+        got = set(_split_bwd_tiles(B, d, nact if hint else None))
+        assert got == tiles, "backward tiles %r, the case is meant for %r (active rows per step %r)" % (got, tiles, nact)
     out, last, op = ops.bilstm_simple(xc, lens, kf, bf, kb, bb, training=True, precision=BF16X3)
+    if hint:
+        op.set_active_hint(lens.numpy())
+    used = {}
 
     def close(a, b, msg, rtol=1e-4, atol=3e-5):
         a, b = a.detach().cpu().double().numpy(), b.detach().cpu().double().numpy()
-        np.testing.assert_allclose(a, b, rtol=rtol, atol=atol * max(1.0, float(np.abs(b).max())), err_msg=msg)
+        at = atol * max(1.0, float(np.abs(b).max()))
+        used[msg] = float((np.abs(a - b) / (at + rtol * np.abs(b))).max())    # fraction of the tolerance taken
+        np.testing.assert_allclose(a, b, rtol=rtol, atol=at, err_msg=msg)
 
     close(out, ref_out, "out")
     close(last, ref_last, "last")
@@ -247,12 +333,17 @@ def test_bilstm_bf16x3_meets_the_fp32_tolerances(B, J, din, d, dense, share):
     dkf, dbf = torch.zeros_like(kf), torch.zeros_like(bf)
     dkb, dbb = (None, None) if share else (torch.zeros_like(kb), torch.zeros_like(bb))
     op.backward(xc, out, d_out, kf, kb, dx, dkf, dbf, dkb, dbb)
+    row = _dx_row_error(dx, leaves[0].grad)
+    print("bf16x3 B=%d J=%d din=%d d=%d: dx per-row error %.3g" % (B, J, din, d, row))
     close(dx, leaves[0].grad, "dx")
     close(dkf, leaves[1].grad, "dkernel_fw")
     close(dbf, leaves[2].grad, "dbias_fw")
     if not share:
         close(dkb, leaves[3].grad, "dkernel_bw")
         close(dbb, leaves[4].grad, "dbias_bw")
+    print("bf16x3 B=%d J=%d din=%d d=%d: fraction of the tolerance taken: %s" % (
+        B, J, din, d, " ".join("%s %.3f" % kv for kv in used.items())))
+    assert row < 1e-3, "dx: per-row error %.3g" % row
 
 
 def test_model_bf16x3_train_step_at_the_metric_shape_meets_the_fp32_tolerances():

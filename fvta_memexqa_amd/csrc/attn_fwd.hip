@@ -689,7 +689,8 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void attn_fwd_rows16(Attn
   constexpr int NM = NB / 2;         // MFMAs along K per wave
   constexpr int NPART = NW * 4;      // row-term partials per row
   __shared__ __attribute__((aligned(16))) float s_part[NW][512];  // [jt][r][lane] partial scores
-  __shared__ __attribute__((aligned(16))) float s_vec[2][NW * NB * 16];
+  constexpr int WCH = NW * NB * 16;  // channels of a row (= w)
+  __shared__ __attribute__((aligned(16))) float s_vec[2][WCH];    // Rh, R2
   __shared__ uint16_t s_idx[R16_CAP];
   __shared__ int s_tnk[R16_MAXT];
   __shared__ uint8_t s_titem[R16_MAXT], s_iallm[R16_MAXI];
@@ -710,9 +711,8 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void attn_fwd_rows16(Attn
   const int nitems = s.N * s.K * s.nsplit;
   // XCD-contiguous workgroup order (see attn_fwd_main): the workgroups of one n share an L2
   const int nwg = (nitems + a.ipw - 1) / a.ipw;
-  const int per = (nwg + 7) / 8;
-  const int wg = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-  if (wg >= nwg || (int)(blockIdx.x >> 3) >= per) return;
+  int wg;
+  if (!attn_wg_index(nwg, wg)) return;
   const int item_lo = wg * a.ipw;
   const int nit = min(nitems, item_lo + a.ipw) - item_lo;
   const unsigned long long t_entry = __builtin_readcyclecounter();
@@ -729,12 +729,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void attn_fwd_rows16(Attn
     s_it0[tid] = t0;
     s_int[tid] = max(0, t1 - t0);
     s_iallm[tid] = a.sv.allmasked[nk] != 0;
-    if (t1 <= t0) {  // empty split
-      float* part = a.part + (size_t)item * (w + 4);
-      part[0] = -INFINITY;
-      part[1] = 0.f;
-      part[2] = -INFINITY;
-    }
+    if (t1 <= t0) store_empty_partial(a.part + (size_t)item * (w + 4));  // empty split
   }
   for (int c = tid; c < w; c += NT) {
     if (RMODE != 2) s_vec[0][c] = a.sv.vecs[VEC_RH * w + c];
@@ -856,14 +851,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void attn_fwd_rows16(Attn
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           const int c0 = 16 * (NB * wave + 2 * m + q) + 4 * kq;
-          const f32x4 h = frag[2 * m + q];
-          if (RMODE == 1) {
-            rt4 += h * *reinterpret_cast<const f32x4*>(&s_vec[0][c0]);
-          } else if (RMODE == 2) {
-            rt4 += (h * h) * *reinterpret_cast<const f32x4*>(&s_vec[1][c0]);
-          } else {
-            rt4 += h * (*reinterpret_cast<const f32x4*>(&s_vec[0][c0]) + *reinterpret_cast<const f32x4*>(&s_vec[1][c0]) * h);
-          }
+          row_term<RMODE>(rt4, frag[2 * m + q], &s_vec[0][0], c0, WCH + c0);  // (s_vec[1][c0]: the rows are contiguous)
         }
         half8 hi, lo;
         split_f16x8(frag[2 * m], frag[2 * m + 1], hi, lo);
@@ -943,15 +931,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void attn_fwd_rows16(Attn
         }
       }
     }
-    const float m_new = fmaxf(m_run, row16_max(am));
-    const float scale = expf(m_run - m_new);
-    const float pr = expf(am - m_new);
-    l_run = l_run * scale + row16_sum(pr);
-    m_run = m_new;
-    if (scale != 1.f) {  // workgroup-uniform; the running max rarely moves after the first tiles of an item
-#pragma unroll
-      for (int i = 0; i < NB; ++i) uacc[i] *= scale;
-    }
+    const float pr = softmax_step(am, m_run, l_run, uacc);
 #pragma unroll
     for (int i = 0; i < NB; ++i) uacc[i] += frag[i] * pr;
     FVTA_STAMP(7);
@@ -965,11 +945,7 @@ __global__ __launch_bounds__(NW * 64, NW >= 8 ? 1 : 2) void attn_fwd_rows16(Attn
         for (int e = 0; e < 4; ++e) u[e] = row16_sum(u[e]);
         if (l15 == 0) *reinterpret_cast<f32x4*>(part + 4 + 16 * (NB * wave + i) + 4 * kq) = u;
       }
-      if (tid == 0) {
-        part[0] = m_run;
-        part[1] = l_run;
-        part[2] = m_run;  // no time_warp_att in this kernel: the softmax logits are amax itself
-      }
+      if (tid == 0) store_partial_head(part, m_run, l_run);
     }
   };
 
@@ -1014,9 +990,8 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_wave16(AttnFwdArgs a, int G) 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int l15 = lane & 15, kq = lane >> 4;
   const int T = s.T, w = s.w, JP = s.JP;
-  const int nwg = s.N * G, per = (nwg + 7) / 8;
-  const int wg = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-  if (wg >= nwg || (int)(blockIdx.x >> 3) >= per) return;
+  int wg;
+  if (!attn_wg_index(s.N * G, wg)) return;
   const int n = wg / G, g0 = wg % G;
 
   // ---- the question operand of n, in MFMA B lane order: step ks, j tile jt, lane (col l15, k group kq) holds channels
@@ -1054,11 +1029,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_wave16(AttnFwdArgs a, int G) 
     const int t0 = split * tiles_per, t1 = min(tiles_total, t0 + tiles_per);
     float* part = a.part + ((size_t)nk * s.nsplit + split) * (w + 4);
     if (t1 <= t0) {  // empty split
-      if (lane == 0) {
-        part[0] = -INFINITY;
-        part[1] = 0.f;
-        part[2] = -INFINITY;
-      }
+      if (lane == 0) store_empty_partial(part);
       continue;
     }
     const float* hbase = a.hinfo + (size_t)nk * a.hstride;
@@ -1099,13 +1070,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_wave16(AttnFwdArgs a, int G) 
 #pragma unroll
           for (int q = 0; q < 2; ++q) {
             const int c0 = 16 * (2 * ks + q) + 4 * kq;
-            const f32x4 hv = h[2 * ks + q];
-            if (RMODE == 1)
-              rt4 += hv * *reinterpret_cast<const f32x4*>(&s_vec[c0]);
-            else if (RMODE == 2)
-              rt4 += (hv * hv) * *reinterpret_cast<const f32x4*>(&s_vec[w + c0]);
-            else
-              rt4 += hv * (*reinterpret_cast<const f32x4*>(&s_vec[c0]) + *reinterpret_cast<const f32x4*>(&s_vec[w + c0]) * hv);
+            row_term<RMODE>(rt4, h[2 * ks + q], s_vec, c0, w + c0);
           }
           half8 hi, lo;
           split_f16x8(h[2 * ks], h[2 * ks + 1], hi, lo);
@@ -1122,62 +1087,23 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_wave16(AttnFwdArgs a, int G) 
         float rtp = (rt4[0] + rt4[1]) + (rt4[2] + rt4[3]);
         rtp += __shfl_xor(rtp, 16, 64);
         rtp += __shfl_xor(rtp, 32, 64);
-        // D layout of 16x16xK: lane -> column j = l15 (+ 16 jt), rows 4 kq + i.  Per row: max / first arg-max over j.
-        float amr[4];
-        int jmr[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float rti = __shfl(rtp, 4 * kq + i, 64);
-          float best = -INFINITY;
-          int bestj = 0;
-#pragma unroll
-          for (int jt = 0; jt < 2; ++jt) {
-            const int j = l15 + 16 * jt;
-            const float x = ahh[jt][i] + axx[jt][i] * (1.f / 2048.f) + rti + s_ct[j];
-            if (((qvalid >> j) & 1ull) && x > best) {
-              best = x;
-              bestj = j;
-            }
-          }
-          row16_argmax(best, bestj);
-          amr[i] = best;
-          jmr[i] = bestj;
-        }
-        // row l15's result sits in the lane group l15 >> 2 as its entry l15 & 3
-        const int src = ((l15 >> 2) << 4) | l15;
-        float bestv = 0.f;
-        int bestj = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float v = __shfl(amr[i], src, 64);
-          const int jj = __shfl(jmr[i], src, 64);
-          if ((l15 & 3) == i) {
-            bestv = v;
-            bestj = jj;
-          }
-        }
+        float bestv;
+        int bestj;
+        finish_scores([&](int jt, int i) { return ahh[jt][i] + axx[jt][i] * (1.f / 2048.f); },
+                      [&](int i) { return __shfl(rtp, 4 * kq + i, 64); }, s_ct, qvalid, l15, bestv, bestj);
         am = rvalid ? (s.add_tanh ? fvta_tanh(bestv) : bestv) : -INFINITY;
         if (kq == 0 && rvalid) {
           a.sv.amax[(size_t)nk * T + t] = am;
           a.sv.jmax[(size_t)nk * T + t] = (uint8_t)bestj;
         }
       }
-      // online softmax over t (softsel inner, model_v2.py:278); every lane of a DPP row holds its own row l15
-      const float m_new = fmaxf(m_run, row16_max(am));
-      const float scale = expf(m_run - m_new);
-      const float pr = expf(am - m_new);
-      l_run = l_run * scale + row16_sum(pr);
-      m_run = m_new;
+      const float pr = softmax_step(am, m_run, l_run, u);
       // weighted sum u[c] = u[c] * scale + sum_r p_r h[r, c]: every block summed over the 16 row lanes by DPP row sums
       // (an all-reduce), kept by lane b & 15.  Measured alternatives, all slower with one wave per SIMD: a reduce-scatter
       // over the row lanes (60 instead of 256 values per 16 blocks, but two selects per value and one long dependent
       // chain: 0.48 vs 0.45 ms); a transposition through a wave-private LDS scratch (a sixth of the VALU work, but two
       // exposed LDS round trips per 64 channels: 0.49); two blocks per butterfly step to cover the DPP read hazard
       // (fewer s_nop, but the compiler spills: 0.50).
-      if (scale != 1.f) {
-#pragma unroll
-        for (int i = 0; i < NU; ++i) u[i] *= scale;
-      }
       if (has_next) {
 #pragma unroll
         for (int b = 0; b < NBLK; ++b) {
@@ -1200,11 +1126,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_wave16(AttnFwdArgs a, int G) 
     // the item's partial (m, l, u): lane (l15, kq) holds channels 16 (16 i + l15) + 4 kq + (0..3)
 #pragma unroll
     for (int i = 0; i < NU; ++i) *reinterpret_cast<f32x4*>(part + 4 + 16 * (16 * i + l15) + 4 * kq) = u[i];
-    if (lane == 0) {
-      part[0] = m_run;
-      part[1] = l_run;
-      part[2] = m_run;
-    }
+    if (lane == 0) store_partial_head(part, m_run, l_run);
   }
 }
 
@@ -1248,19 +1170,8 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pair16(AttnFwdArgs a, int G_a
   const int pair = wave >> 1, hv = wave & 1;
   const int l15 = lane & 15, kq = lane >> 4;
   const int T = s.T, w = s.w, JP = s.JP;
-  const int nwg = s.N * G_all, per = (nwg + 7) / 8;
-  const int wg = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-  if (wg >= nwg || (int)(blockIdx.x >> 3) >= per) return;
-  // the n this workgroup serves, its index among that n's workgroups and their number: uniform (G_all each), or dealt in
-  // proportion to the n's valid tiles (masked batches: albums differ in rows)
-  int n = wg / G_all, g0 = wg % G_all, G = G_all;
-  if (a.wgtab) {
-    const uint32_t e = a.wgtab[wg];
-    if (e == 0xffffffffu) return;
-    n = (int)(e & 0xffffu);
-    g0 = (int)((e >> 16) & 0xffu);
-    G = (int)(e >> 24);
-  }
+  int wg, n, g0, G;
+  if (!attn_wg_index(s.N * G_all, wg) || !attn_wg_album(a.wgtab, wg, G_all, n, g0, G)) return;
   // -DFVTA_PAIR_ABL=bits: compile-time ablations (timing only, results are wrong; a run-time switch makes the compiler
   // spill): 1 no tile loads after an item's first, 2 no score MFMA loop, 4 no weighted sum (refill only), 8 no pair
   // hand-shake -- tools/r02_v.sh
@@ -1273,192 +1184,26 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pair16(AttnFwdArgs a, int G_a
   const bool pstamp = (a.dbg & 16) && wg == 0 && wave == ((a.dbg >> 8) & 7) && lane == 0;
   const unsigned long long t_entry = __builtin_readcyclecounter();
 #endif
-  {
-    const int W4c = w / 4;
-    const uint16_t* qh = a.sv.Qh + (size_t)n * 2 * W4c * 32 * 4;
-    // every load of the staging is issued before the first LDS write: as a rolled loop (two loads, wait, write) the
-    // 128 KB took 16 dependent round trips per thread, 35-50 k cycles before the first tile was even requested
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    constexpr int QIT = 2 * 2 * NKS * 2 * 64 / 512;
-    u32x2 x0[QIT], x1[QIT];
-#pragma unroll
-    for (int it = 0; it < QIT; ++it) {
-      const int e = tid + 512 * it;
-      const int ln = e & 63, jt = (e >> 6) & 1, ks = (e >> 7) % (2 * NKS), pc = (e >> 7) / (2 * NKS);
-      const int j = (ln & 15) + 16 * jt, q4 = ln >> 4;
-      x0[it] = *reinterpret_cast<const u32x2*>(qh + (((size_t)pc * W4c + 8 * ks + q4) * 32 + j) * 4);
-      x1[it] = *reinterpret_cast<const u32x2*>(qh + (((size_t)pc * W4c + 8 * ks + 4 + q4) * 32 + j) * 4);
-    }
-    float v0[2], v1[2];  // w <= 1024: at most two channels of each row-term vector per thread
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int c = tid + 512 * it;
-      v0[it] = c < w ? a.sv.vecs[VEC_RH * w + c] : 0.f;
-      v1[it] = c < w ? a.sv.vecs[VEC_R2 * w + c] : 0.f;
-    }
-    const float ctv = tid < 32 ? a.sv.ct[(size_t)n * JP + tid] : 0.f;
-#pragma unroll
-    for (int it = 0; it < QIT; ++it) {
-      const int e = tid + 512 * it;
-      const int ln = e & 63, jt = (e >> 6) & 1, ks = (e >> 7) % (2 * NKS), pc = (e >> 7) / (2 * NKS);
-      const u32x4 xx = __builtin_shufflevector(x0[it], x1[it], 0, 1, 2, 3);
-      (pc == 0 ? s_qhi : s_qlo)[ks][jt][ln] = __builtin_bit_cast(half8, xx);
-    }
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int c = tid + 512 * it;
-      if (c < w) {
-        s_vec[c] = v0[it];
-        s_vec[w + c] = v1[it];
-      }
-    }
-    if (tid < 32) s_ct[tid] = ctv;
-  }
+  stage_question<2 * NKS, 1, 4>(a.sv, n, w, JP, tid, s_qhi, s_qlo, s_vec, s_ct);
   const uint64_t qvalid = a.sv.qvalid[(size_t)n * 2];
-  const int nitems_n = s.K * s.nsplit;
-  const int P = 4 * G, pg = 4 * g0 + pair;  // pairs that share this n, this pair's index among them
-  // ---- the streams of this n: valid rows, first tile (in the n's flat tile order), fully-masked flag
-  if (tid == 64) {
-    int acc = 0;
-    for (int k = 0; k < s.K; ++k) {
-      const int c = a.sv.cnt[n * s.K + k];
-      s_kcnt[k] = c;
-      s_kall[k] = a.sv.allmasked[n * s.K + k];
-      s_kstart[k] = acc;
-      acc += (c + 15) >> 4;
-    }
-    s_kstart[s.K] = acc;
-    // FLAT dealing: the n's tiles, in (k, tile) order, are cut into P equal runs, one per pair (a run crosses stream
-    // boundaries; pair p's piece of stream k is that stream's partial number p - (first pair that touches k)).  Only if
-    // no stream is cut into more pieces than it has partial slots (nsplit); otherwise the (k, split) items are dealt
-    // round-robin as in the other kernels (pieces of ceil(tiles / nsplit) tiles: unequal sums per pair).
-    int ok = acc > 0;
-    for (int k = 0; k < s.K && ok; ++k) {
-      const int st = s_kstart[k], en = s_kstart[k + 1];
-      if (en > st && ((en * P - 1) / acc) - (((st + 1) * P - 1) / acc) + 1 > s.nsplit) ok = 0;
-    }
-    s_flat = ok;
-  }
+  // ---- the streams of this n and how its tiles are dealt to the pairs that share it (attn_fwd_shared.h)
+  if (tid == 64) deal_streams<16>(a.sv, n, s.K, s.nsplit, 4 * G, s_kstart, s_kcnt, s_kall, &s_flat);
   if (tid < 8) {
     s_pub[tid] = 0;
     s_done[tid] = 0;
   }
   __syncthreads();
-  const bool flat = s_flat != 0;
-  const int tot = s_kstart[s.K];
-  const int lo = flat ? tot * pg / P : 0, hi = flat ? tot * (pg + 1) / P : 0;  // this pair's run (flat dealing)
-  auto empty_partial = [&](int nk, int split) {
-    float* pp = a.part + ((size_t)nk * s.nsplit + split) * (w + 4);
-    pp[0] = -INFINITY;
-    pp[1] = 0.f;
-    pp[2] = -INFINITY;
-  };
-  if (flat && g0 == 0) {  // the partial slots no pair fills
-    for (int e = tid; e < nitems_n; e += 512) {
-      const int k = e / s.nsplit, sp = e % s.nsplit;
-      const int st = s_kstart[k], en = s_kstart[k + 1];
-      bool filled = false;  // slot sp belongs to pair (first pair that touches k) + sp, if that pair's run meets k at all
-      if (en > st) {
-        const int px = ((st + 1) * P - 1) / tot + sp;
-        filled = px < P && max(tot * px / P, st) < min(tot * (px + 1) / P, en);
-      }
-      if (!filled) empty_partial(n * s.K + k, sp);
-    }
-  }
-  // ---- the pair's pieces ("segments": consecutive tiles [t0, t1) of one stream, summed into one partial)
-  struct Seg {
-    int nk, t0, t1, slot, cnt, allm;
-  };
-  auto item_seg = [&](int il, Seg& sg) {  // round-robin dealing: item il = (k, split)
-    const int k = il / s.nsplit, split = il % s.nsplit;
-    const int c = s_kcnt[k];
-    const int tiles_total = (c + 15) >> 4;
-    const int tiles_per = (tiles_total + s.nsplit - 1) / s.nsplit;
-    sg.nk = n * s.K + k;
-    sg.t0 = split * tiles_per;
-    sg.t1 = min(tiles_total, sg.t0 + tiles_per);
-    sg.slot = split;
-    sg.cnt = c;
-    sg.allm = s_kall[k];
-    return sg.t1 > sg.t0;
-  };
-  int it_k = 0, it_il = g0 + G * pair - 4 * G;
-  auto next_seg = [&](Seg& sg) {  // false: none left
-    if (flat) {
-      while (it_k < s.K) {
-        const int k = it_k++;
-        const int st = s_kstart[k], en = s_kstart[k + 1];
-        if (st >= hi) break;
-        const int x0 = max(lo, st), x1 = min(hi, en);
-        if (x0 < x1) {
-          sg.nk = n * s.K + k;
-          sg.t0 = x0 - st;
-          sg.t1 = x1 - st;
-          sg.slot = pg - ((st + 1) * P - 1) / tot;
-          sg.cnt = s_kcnt[k];
-          sg.allm = s_kall[k];
-          return true;
-        }
-      }
-      it_k = s.K;
-      return false;
-    }
-    for (;;) {
-      it_il += 4 * G;
-      if (it_il >= nitems_n) return false;
-      if (item_seg(it_il, sg)) return true;
-      if (hv == 0 && lane == 0) empty_partial(sg.nk, sg.slot);  // empty split
-    }
-  };
-  int myrounds = hi - lo;
-  if (!flat) {
-    myrounds = 0;
-    Seg sg;
-    for (int il = g0 + G * pair; il < nitems_n; il += 4 * G)
-      if (item_seg(il, sg)) myrounds += sg.t1 - sg.t0;
-  }
+  const bool writer = hv == 0 && lane == 0;  // the pair's lane for partial heads and empty partials
+  AttnDeal dl = deal_init<4>(s_kstart, s_kcnt, s_kall, s_flat, a, n, g0, G, pair, writer);
+  deal_fill_unowned<512>(dl, tid);
+  const int myrounds = deal_rounds<16>(dl);
   int rounds = myrounds;
   if (!FLAGS) {  // the barrier version runs every pair for the longest pair's number of rounds
-    if (hv == 0 && lane == 0) s_tiles[pair] = myrounds;
+    if (writer) s_tiles[pair] = myrounds;
     __syncthreads();
     rounds = max(max(s_tiles[0], s_tiles[1]), max(s_tiles[2], s_tiles[3]));
   }
   const int pwv = wave ^ 1;
-  // (the flags are accessed through LDS-address-space pointers: through a generic pointer the compiler emits FLAT
-  //  loads/stores, whose s_waitcnt vmcnt(0) would also wait for every outstanding load of the next tile)
-  typedef __attribute__((address_space(3))) int lds_int;
-  auto wait_flag = [&](int* flag, int want) {  // bounded poll of an LDS word
-    volatile lds_int* f = (volatile lds_int*)flag;
-    bool arrived = false;
-    // (the partner wave is resident in this very workgroup: it can only be DELAYED -- counter collection serialising waves,
-    //  pre-emption, a debugger -- so the bound is generous: 2^28 polls of s_sleep 2, tens of seconds)
-    for (int spin = 0; spin < (1 << 28); ++spin) {
-      if (*f >= want) {
-        arrived = true;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(2);
-    }
-    // a partner that never arrives is a bug (a wedged wave).  The trap aborts the queue -- on ROCm that usually ends the
-    // process, it is NOT a recoverable launch error -- which is still better than folding stale partials into amax /
-    // jmax / h_a and training on them
-    if (!arrived) {
-      if (a.fault) {  // (host-mapped: visible to the host once the system-scope fence has drained)
-        __hip_atomic_store(a.fault, (int)ATTN_FAULT_PAIR_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __threadfence_system();
-      }
-      __builtin_trap();
-    }
-    // acquire: the partner's published area (plain LDS loads below) is read only after the poll has matched; workgroup
-    // scope lowers to s_waitcnt lgkmcnt(0) and, unlike an empty asm, is a compiler fence for __shared__ accesses too
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  };
-  auto post_flag = [&](int* flag, int v) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // my partials are written before the flag says so
-    *(volatile lds_int*)flag = v;
-  };
-
   // ---- the pair's tile stream: the CURRENT tile is in h[], the NEXT tile's identity and row numbers are known one
   // round ahead (its rows replace the current tile's registers during the weighted sum, also across a stream boundary)
   Seg cs = {0, 0, 0, 0, 0, 0}, ns = {0, 0, 0, 0, 0, 0};
@@ -1478,26 +1223,14 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pair16(AttnFwdArgs a, int G_a
     v = lr < sg.cnt;
     t = a.sv.idx[(size_t)sg.nk * T + max(min(lr, sg.cnt - 1), 0)];
   };
-  auto tile_after = [&](const Seg& from, int ftl, Seg& to, int& ttl) {
-    if (ftl + 1 < from.t1) {
-      to = from;
-      ttl = ftl + 1;
-      return true;
-    }
-    if (next_seg(to)) {
-      ttl = to.t0;
-      return true;
-    }
-    return false;
-  };
-  bool active = next_seg(cs), has_n = false;
+  bool active = next_seg<16>(dl, cs), has_n = false;
   if (active) {
     ctl = cs.t0;
     rows_of(cs, ctl, t_cur, v_cur);
     const float* rowp = a.hinfo + (size_t)cs.nk * a.hstride + (size_t)t_cur * w + coff;
 #pragma unroll
     for (int b = 0; b < NBH; ++b) h[b] = *reinterpret_cast<const f32x4*>(rowp + 16 * b);
-    has_n = tile_after(cs, ctl, ns, ntl);
+    has_n = tile_after<16>(dl, cs, ctl, ns, ntl);
     if (!has_n) {
       ns = cs;
       ntl = ctl;
@@ -1524,13 +1257,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pair16(AttnFwdArgs a, int G_a
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           const int c0 = coff + 16 * (2 * ks + q);
-          const f32x4 hv4 = h[2 * ks + q];
-          if (RMODE == 1)
-            rt4 += hv4 * *reinterpret_cast<const f32x4*>(&s_vec[c0]);
-          else if (RMODE == 2)
-            rt4 += (hv4 * hv4) * *reinterpret_cast<const f32x4*>(&s_vec[w + c0]);
-          else
-            rt4 += hv4 * (*reinterpret_cast<const f32x4*>(&s_vec[c0]) + *reinterpret_cast<const f32x4*>(&s_vec[w + c0]) * hv4);
+          row_term<RMODE>(rt4, h[2 * ks + q], s_vec, c0, w + c0);
         }
         half8 hi8, lo8;
         split_f16x8(h[2 * ks], h[2 * ks + 1], hi8, lo8);
@@ -1549,7 +1276,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pair16(AttnFwdArgs a, int G_a
       float rtp = (rt4[0] + rt4[1]) + (rt4[2] + rt4[3]);
       rtp += __shfl_xor(rtp, 16, 64);
       rtp += __shfl_xor(rtp, 32, 64);
-      if (FLAGS && !(abl & 8)) wait_flag(&s_done[pwv], g);  // the partner has read my partials of round g - 1 (rounds are numbered from 1)
+      if (FLAGS && !(abl & 8)) wait_flag(&s_done[pwv], g, a.fault);  // the partner has read my partials of round g - 1 (rounds are numbered from 1)
       if (kq == 0) s_rt[wave][l15] = rtp;
 #pragma unroll
       for (int jt = 0; jt < 2; ++jt)
@@ -1566,7 +1293,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pair16(AttnFwdArgs a, int G_a
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // my partials are in LDS (a wave's LDS operations complete in order)
       if (lane == 0) post_flag(&s_pub[wave], g + 1);
       FVTA_PSTAMP(3);
-      if (!(abl & 8)) wait_flag(&s_pub[pwv], g + 1);
+      if (!(abl & 8)) wait_flag(&s_pub[pwv], g + 1, a.fault);
     } else {
       lds_barrier();  // both halves of every tile are published
     }
@@ -1574,41 +1301,11 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pair16(AttnFwdArgs a, int G_a
     if (active) {
       float am = rvalid ? FVTA_NEG : -INFINITY;
       if (!allm) {
-        const int pw = wave ^ 1;
-        float amr[4];
-        int jmr[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float rti = s_rt[wave][4 * kq + i] + s_rt[pw][4 * kq + i];
-          float best = -INFINITY;
-          int bestj = 0;
-#pragma unroll
-          for (int jt = 0; jt < 2; ++jt) {
-            const int j = l15 + 16 * jt;
-            const int pi = (jt * 4 + i) * 64 + lane;
-            // (own + partner: floating-point addition commutes, so both waves of the pair get bit-identical sums)
-            const float x = (xown[jt * 4 + i] + s_x[pw][pi]) + rti + s_ct[j];
-            if (((qvalid >> j) & 1ull) && x > best) {
-              best = x;
-              bestj = j;
-            }
-          }
-          row16_argmax(best, bestj);
-          amr[i] = best;
-          jmr[i] = bestj;
-        }
-        const int src = ((l15 >> 2) << 4) | l15;
-        float bestv = 0.f;
-        int bestj = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float v = __shfl(amr[i], src, 64);
-          const int jj = __shfl(jmr[i], src, 64);
-          if ((l15 & 3) == i) {
-            bestv = v;
-            bestj = jj;
-          }
-        }
+        float bestv;
+        int bestj;
+        // (own + partner: floating-point addition commutes, so both waves of the pair get bit-identical sums)
+        finish_scores([&](int jt, int i) { return xown[jt * 4 + i] + s_x[pwv][(jt * 4 + i) * 64 + lane]; },
+                      [&](int i) { return s_rt[wave][4 * kq + i] + s_rt[pwv][4 * kq + i]; }, s_ct, qvalid, l15, bestv, bestj);
         am = rvalid ? (s.add_tanh ? fvta_tanh(bestv) : bestv) : -INFINITY;
         if (hv == 0 && kq == 0 && rvalid) {
           a.sv.amax[(size_t)cs.nk * T + t] = am;
@@ -1619,15 +1316,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pair16(AttnFwdArgs a, int G_a
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the partner's partials are in my registers
         if (lane == 0) post_flag(&s_done[wave], g + 1);
       }
-      const float m_new = fmaxf(m_run, row16_max(am));
-      const float scale = expf(m_run - m_new);
-      const float pr = expf(am - m_new);
-      l_run = l_run * scale + row16_sum(pr);
-      m_run = m_new;
-      if (scale != 1.f) {
-#pragma unroll
-        for (int i = 0; i < NU; ++i) u[i] *= scale;
-      }
+      const float pr = softmax_step(am, m_run, l_run, u);
       FVTA_PSTAMP(5);
       if (has_n) {
         const float* rowp_next = a.hinfo + (size_t)ns.nk * a.hstride + (size_t)t_nxt * w + coff;
@@ -1667,11 +1356,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pair16(AttnFwdArgs a, int G_a
           *reinterpret_cast<f32x4*>(part + 4 + coff + 16 * (16 * i + l15)) = u[i];
           u[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        if (hv == 0 && lane == 0) {
-          part[0] = m_run;
-          part[1] = l_run;
-          part[2] = m_run;
-        }
+        if (writer) store_partial_head(part, m_run, l_run);
         m_run = -INFINITY;
         l_run = 0.f;
       }
@@ -1682,7 +1367,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_pair16(AttnFwdArgs a, int G_a
         ctl = ntl;
         t_cur = t_nxt;
         v_cur = v_nxt;
-        has_n = tile_after(cs, ctl, ns, ntl);
+        has_n = tile_after<16>(dl, cs, ctl, ns, ntl);
         if (!has_n) {
           ns = cs;
           ntl = ctl;
@@ -1961,6 +1646,10 @@ extern "C" size_t fvta_attn_saved_bytes(const fvta_attn_desc* d) {
 
 size_t fvta_attn_bwd_workspace_bytes(const AttnShape& s);  // attn_bwd.hip
 
+// the split partials of the forward (+ one per (n,k) for the masked rows' share under time_warp_att): the head of the workspace
+static size_t attn_part_bytes(const AttnShape& s) {
+  return fvta_align_up((size_t)s.N * s.K * (s.nsplit + 1) * (s.w + 4) * sizeof(float), 256);
+}
 constexpr size_t ATTN_WGTAB_BYTES = 4096 * sizeof(uint32_t);  // the pair kernel's workgroup table, behind the partials
 
 extern "C" size_t fvta_attn_workspace_bytes(const fvta_attn_desc* d) {
@@ -1968,7 +1657,7 @@ extern "C" size_t fvta_attn_workspace_bytes(const fvta_attn_desc* d) {
   const AttnShape s = attn_shape(d, true);
   // forward: the split partials, then one more partial per (n,k) for the masked rows' share under time_warp_att
   // (+ the shadow forward's compacted row addresses: two words per row)
-  const size_t fwd = fvta_align_up((size_t)s.N * s.K * (s.nsplit + 1) * (s.w + 4) * sizeof(float), 256) + ATTN_WGTAB_BYTES +
+  const size_t fwd = attn_part_bytes(s) + ATTN_WGTAB_BYTES +
                      (size_t)2 * s.N * s.K * s.T * sizeof(uint64_t);
   const size_t bwd = fvta_attn_bwd_workspace_bytes(s);
   return fwd > bwd ? fwd : bwd;
@@ -2002,6 +1691,44 @@ extern "C" int fvta_attn_fwd_shadow(const fvta_attn_desc* d, const uint64_t* tab
   return attn_fwd_impl(d, nullptr, table, hq, hmask, qmask, W, b, nullptr, h_a, nullptr, saved, workspace, stream_);
 }
 
+// workgroups per album of the kernels that deal an album's tiles: about 256 in all, at most maxg per album
+static int attn_wg_per_album(const AttnShape& s, int maxg) {
+  int G = (256 + s.N - 1) / s.N;
+  if (G > maxg) G = maxg;
+  if (G < 1) G = 1;
+  return G;
+}
+// ragged albums (a masked batch): workgroups in proportion to the rows -- attn_balance_kernel fills the table behind the partials.
+// NOTE on rounding: with the table an album's workgroup count -- hence the split points of its partial sums, hence
+// the fp32 rounding of its h_a (nothing else: arg-max positions and logits do not move) -- depends on the OTHER albums
+// of the batch.  The same batch always gives the same bits; an album moved into another batch may differ in the last
+// bits (tests/test_gpu_forward.py::test_attention_pair_kernel_balance_on_skewed_batches).
+static void attn_balance_if_ragged(AttnFwdArgs& a, bool use_mask, int G, int maxg, void* workspace, int run_cap, hipStream_t stream) {
+  const AttnShape& s = a.s;
+  const int nwg = s.N * G;
+  if (use_mask && s.N <= 64 && s.N > 1 && nwg <= 4096 && maxg <= 255) {
+    uint32_t* tab = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + attn_part_bytes(s));
+    hipLaunchKernelGGL(attn_balance_kernel, dim3(1), dim3(64), 0, stream, s, a.sv, nwg, maxg, tab, run_cap);
+    a.wgtab = tab;
+  }
+}
+template <int NBH, int RMODE, bool FLAGS>
+static void launch_pair16(const AttnFwdArgs& a, int G, hipStream_t stream) {
+  const size_t lds = attn_question_lds(NBH, a.s.w);
+  (void)hipFuncSetAttribute((const void*)attn_fwd_pair16<NBH, RMODE, FLAGS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((attn_fwd_pair16<NBH, RMODE, FLAGS>), attn_xcd_grid(a.s.N * G), dim3(512), lds, stream, a, G);
+}
+template <int NBLK, int RMODE>
+static void launch_wave16(const AttnFwdArgs& a, int G, hipStream_t stream) {
+  const size_t lds = attn_question_lds(NBLK / 2, a.s.w);
+  (void)hipFuncSetAttribute((const void*)attn_fwd_wave16<NBLK, RMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((attn_fwd_wave16<NBLK, RMODE>), attn_xcd_grid(a.s.N * G), dim3(256), lds, stream, a, G);
+}
+template <int NB, int NW, int RMODE>
+static void launch_rows16(const AttnFwdArgs& a, int nwg, hipStream_t stream) {
+  hipLaunchKernelGGL((attn_fwd_rows16<NB, NW, RMODE>), attn_xcd_grid(nwg), dim3(NW * 64), 0, stream, a);
+}
+
 static int attn_fwd_impl(const fvta_attn_desc* d, const float* hinfo, const uint64_t* table, const float* hq, const uint8_t* hmask,
                          const uint8_t* qmask, const float* W, const float* b, const float* tscale, float* h_a,
                          float* a_logits, void* saved, void* workspace, fvta_stream_t stream_) {
@@ -2019,9 +1746,7 @@ static int attn_fwd_impl(const fvta_attn_desc* d, const float* hinfo, const uint
   // wide rows (w = 2048: BASELINE.json configs[4]): the rows-stationary, question-streaming kernel of attn_fwd_wide.hip
   const bool exact_kernel = attn_exact_mode() != 0;
   const int wave16_mode = attn_wave16_mode();
-  int wideG = (256 + s.N - 1) / s.N;
-  if (wideG > s.K * s.nsplit) wideG = s.K * s.nsplit;
-  if (wideG < 1) wideG = 1;
+  const int wideG = attn_wg_per_album(s, s.K * s.nsplit);
   const bool use_wide = !table && !exact_kernel && wave16_mode != 0 && !a_logits && !tscale && !d->hinfo_stride && wide_covers(s, wideG);
   FVTA_CHECK_ARG(!table || (shadow_covers(s) && !d->hinfo_stride),
                  "attn_fwd_shadow: needs JQ <= 32, w = 512 or 1024, simiMatrix 1-3, no hinfo_stride (JQ=%d w=%d simi=%d)", d->JQ, d->w, d->simi);
@@ -2056,96 +1781,35 @@ static int attn_fwd_impl(const fvta_attn_desc* d, const float* hinfo, const uint
                       !exact_kernel;
   // FVTA_ATTN_WAVE16: the one-wave-per-tile kernel for the shapes it covers (measurement switch)
   if (table) {
-    int G = (256 + s.N - 1) / s.N;
-    const int maxg = (s.K * s.nsplit + 3) / 4;
-    if (G > maxg) G = maxg;
-    if (G < 1) G = 1;
-    const int nwg = s.N * G;
-    const size_t part_bytes = fvta_align_up((size_t)s.N * s.K * (s.nsplit + 1) * (s.w + 4) * sizeof(float), 256);
-    if (use_mask && s.N <= 64 && s.N > 1 && nwg <= 4096 && maxg <= 255) {
-      uint32_t* tab = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + part_bytes);
-      hipLaunchKernelGGL(attn_balance_kernel, dim3(1), dim3(64), 0, stream, s, sv, nwg, maxg, tab, 0);
-      a.wgtab = tab;
-    }
-    uint64_t* rowptr = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + part_bytes + ATTN_WGTAB_BYTES);
+    const int maxg = (s.K * s.nsplit + 3) / 4, G = attn_wg_per_album(s, maxg);
+    attn_balance_if_ragged(a, use_mask, G, maxg, workspace, 0, stream);
+    uint64_t* rowptr = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(workspace) + attn_part_bytes(s) + ATTN_WGTAB_BYTES);
     launch_attn_shadow_compact(s, sv, table, rowptr, stream);
     launch_attn_fwd_pair16h(a, G, rowptr, stream);
   } else if (use_wide) {
-    const int nwg = s.N * wideG, maxg = s.K * s.nsplit;
-    if (use_mask && s.N <= 64 && s.N > 1 && nwg <= 4096 && maxg <= 255) {  // ragged albums: workgroups in proportion to the rows
-      uint32_t* tab = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) +
-                                                 fvta_align_up((size_t)s.N * s.K * (s.nsplit + 1) * (s.w + 4) * sizeof(float), 256));
-      hipLaunchKernelGGL(attn_balance_kernel, dim3(1), dim3(64), 0, stream, s, sv, nwg, maxg, tab, wide_max_run());
-      a.wgtab = tab;
-    }
+    attn_balance_if_ragged(a, use_mask, wideG, s.K * s.nsplit, workspace, wide_max_run(), stream);
     launch_attn_fwd_wide(a, wideG, stream);
   } else if (rows16 && (wave16_mode == 2 || wave16_mode == 3) && s.simi != 4 && s.w >= 512) {  // two waves per tile (attn_fwd_pair16)
     const bool flags = wave16_mode == 3;
-    int G = (256 + s.N - 1) / s.N;
-    const int maxg = (s.K * s.nsplit + 3) / 4;
-    if (G > maxg) G = maxg;
-    if (G < 1) G = 1;
-    const int nwg = s.N * G;
-    const dim3 grid(((nwg + 7) / 8) * 8);
-    const int rmode = s.simi == 1 ? 1 : (s.simi == 3 ? 3 : 2);
-    // NOTE on rounding: with the table an album's workgroup count -- hence the split points of its partial sums, hence
-    // the fp32 rounding of its h_a (nothing else: arg-max positions and logits do not move) -- depends on the OTHER albums
-    // of the batch.  The same batch always gives the same bits; an album moved into another batch may differ in the last
-    // bits (tests/test_gpu_forward.py::test_attention_pair_kernel_balance_on_skewed_batches).
-    if (use_mask && s.N <= 64 && s.N > 1 && nwg <= 4096 && maxg <= 255) {  // ragged albums: workgroups in proportion to the rows
-      uint32_t* tab = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) +
-                                                 fvta_align_up((size_t)s.N * s.K * (s.nsplit + 1) * (s.w + 4) * sizeof(float), 256));
-      hipLaunchKernelGGL(attn_balance_kernel, dim3(1), dim3(64), 0, stream, s, sv, nwg, maxg, tab, 0);
-      a.wgtab = tab;
-    }
-#define FVTA_P16K(NBH, RM, FL)                                                                                          \
-  do {                                                                                                                   \
-    (void)hipFuncSetAttribute((const void*)attn_fwd_pair16<NBH, RM, FL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((attn_fwd_pair16<NBH, RM, FL>), grid, dim3(512), lds, stream, a, G);                             \
-  } while (0)
-#define FVTA_P16(NBH)                                                                                                    \
-  do {                                                                                                                   \
-    const size_t lds = (size_t)2 * 2 * (NBH / 2) * 2 * 64 * 16 + (size_t)2 * s.w * sizeof(float);                        \
-    if (flags) {                                                                                                         \
-      if (rmode == 1) FVTA_P16K(NBH, 1, true); else if (rmode == 2) FVTA_P16K(NBH, 2, true); else FVTA_P16K(NBH, 3, true); \
-    } else {                                                                                                             \
-      if (rmode == 1) FVTA_P16K(NBH, 1, false); else if (rmode == 2) FVTA_P16K(NBH, 2, false); else FVTA_P16K(NBH, 3, false); \
-    }                                                                                                                    \
-  } while (0)
-    switch (s.w) {
-      case 512: FVTA_P16(16); break;
-      case 1024: FVTA_P16(32); break;
-    }
-#undef FVTA_P16K
-#undef FVTA_P16
+    const int maxg = (s.K * s.nsplit + 3) / 4, G = attn_wg_per_album(s, maxg);
+    attn_balance_if_ragged(a, use_mask, G, maxg, workspace, 0, stream);
+    attn_with_rmode(s.simi, [&](auto rm) {
+      constexpr int RM = decltype(rm)::value;
+      switch (s.w) {
+        case 512: flags ? launch_pair16<16, RM, true>(a, G, stream) : launch_pair16<16, RM, false>(a, G, stream); break;
+        case 1024: flags ? launch_pair16<32, RM, true>(a, G, stream) : launch_pair16<32, RM, false>(a, G, stream); break;
+      }
+    });
   } else if (rows16 && wave16_mode && s.simi != 4 && s.w >= 256) {
-    int G = (256 + s.N - 1) / s.N;
-    const int maxg = (s.K * s.nsplit + 3) / 4;
-    if (G > maxg) G = maxg;
-    if (G < 1) G = 1;
-    const int nwg = s.N * G;
-    const dim3 grid(((nwg + 7) / 8) * 8);
-    const int rmode = s.simi == 1 ? 1 : (s.simi == 3 ? 3 : 2);
-#define FVTA_W16(NBLK)                                                                                                   \
-  do {                                                                                                                   \
-    const size_t lds = (size_t)2 * (NBLK / 2) * 2 * 64 * 16 + (size_t)2 * s.w * sizeof(float);                           \
-    if (rmode == 1) {                                                                                                    \
-      (void)hipFuncSetAttribute((const void*)attn_fwd_wave16<NBLK, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      hipLaunchKernelGGL((attn_fwd_wave16<NBLK, 1>), grid, dim3(256), lds, stream, a, G);                               \
-    } else if (rmode == 2) {                                                                                             \
-      (void)hipFuncSetAttribute((const void*)attn_fwd_wave16<NBLK, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      hipLaunchKernelGGL((attn_fwd_wave16<NBLK, 2>), grid, dim3(256), lds, stream, a, G);                               \
-    } else {                                                                                                             \
-      (void)hipFuncSetAttribute((const void*)attn_fwd_wave16<NBLK, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-      hipLaunchKernelGGL((attn_fwd_wave16<NBLK, 3>), grid, dim3(256), lds, stream, a, G);                               \
-    }                                                                                                                    \
-  } while (0)
-    switch (s.w) {
-      case 256: FVTA_W16(16); break;
-      case 512: FVTA_W16(32); break;
-      case 1024: FVTA_W16(64); break;
-    }
-#undef FVTA_W16
+    const int G = attn_wg_per_album(s, (s.K * s.nsplit + 3) / 4);
+    attn_with_rmode(s.simi, [&](auto rm) {
+      constexpr int RM = decltype(rm)::value;
+      switch (s.w) {
+        case 256: launch_wave16<16, RM>(a, G, stream); break;
+        case 512: launch_wave16<32, RM>(a, G, stream); break;
+        case 1024: launch_wave16<64, RM>(a, G, stream); break;
+      }
+    });
   } else if (rows16) {
     // a workgroup streams `ipw` consecutive items: about one workgroup per CU, bounded by its LDS row list
     const int nitems = s.nsplit * s.N * s.K;
@@ -2161,21 +1825,15 @@ static int attn_fwd_impl(const fvta_attn_desc* d, const float* hinfo, const uint
     if (ipw < 1) ipw = 1;
     a.ipw = ipw;
     const int nwg = (nitems + ipw - 1) / ipw;
-    const dim3 grid(((nwg + 7) / 8) * 8);
-    const int rmode = s.simi == 1 ? 1 : (s.simi == 3 ? 3 : 2);
-#define FVTA_R16(NB, NW)                                                                                          \
-  do {                                                                                                            \
-    if (rmode == 1) hipLaunchKernelGGL((attn_fwd_rows16<NB, NW, 1>), grid, dim3(NW * 64), 0, stream, a);          \
-    else if (rmode == 2) hipLaunchKernelGGL((attn_fwd_rows16<NB, NW, 2>), grid, dim3(NW * 64), 0, stream, a);     \
-    else hipLaunchKernelGGL((attn_fwd_rows16<NB, NW, 3>), grid, dim3(NW * 64), 0, stream, a);                     \
-  } while (0)
-    switch (s.w) {
-      case 128: FVTA_R16(2, 4); break;
-      case 256: FVTA_R16(4, 4); break;
-      case 512: FVTA_R16(4, 8); break;
-      case 1024: FVTA_R16(8, 8); break;
-    }
-#undef FVTA_R16
+    attn_with_rmode(s.simi, [&](auto rm) {
+      constexpr int RM = decltype(rm)::value;
+      switch (s.w) {
+        case 128: launch_rows16<2, 4, RM>(a, nwg, stream); break;
+        case 256: launch_rows16<4, 4, RM>(a, nwg, stream); break;
+        case 512: launch_rows16<4, 8, RM>(a, nwg, stream); break;
+        case 1024: launch_rows16<8, 8, RM>(a, nwg, stream); break;
+      }
+    });
   } else
   switch (s.w) {
     case 64: launch_main<4, 1, 4, 1, 1, 4>(a, stream); break;

@@ -66,9 +66,10 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_wide(AttnFwdArgs a, int G_all
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int l15 = lane & 15, kq = lane >> 4;
   const int T = s.T, w = s.w, JP = s.JP;
-  const int nwg = s.N * G_all, per = (nwg + 7) / 8;
-  const int wg = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-  if (wg >= nwg || (int)(blockIdx.x >> 3) >= per) return;
+  int wg;
+  if (!attn_wg_index(s.N * G_all, wg)) return;
+  // (the album decode is attn_wg_album's, spelled out: through the helper, and with the unowned slots filled before the
+  //  round count below, the <8,1,*> instantiations' tile loop came out with 8 + 8 more register copies and ~1 % slower)
   int n = wg / G_all, g0 = wg % G_all, G = G_all;
   if (a.wgtab) {
     const uint32_t e = a.wgtab[wg];
@@ -84,109 +85,23 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_wide(AttnFwdArgs a, int G_all
   if (tid < 64) s_ct[tid] = tid < JP ? a.sv.ct[(size_t)n * JP + tid] : 0.f;
   const uint64_t qvalid = a.sv.qvalid[(size_t)n * 2];
   asm volatile("" ::"s"(qvalid));
-  const int nitems_n = s.K * s.nsplit;
-  const int P = G, pg = g0;
-  if (tid == 64) {
-    int acc = 0;
-    for (int k = 0; k < s.K; ++k) {
-      const int c = a.sv.cnt[n * s.K + k];
-      s_kcnt[k] = c;
-      s_kall[k] = a.sv.allmasked[n * s.K + k];
-      s_kstart[k] = acc;
-      acc += (c + 31) >> 5;
-    }
-    s_kstart[s.K] = acc;
-    int ok = acc > 0;  // FLAT dealing if no stream is cut into more pieces than it has partial slots
-    for (int k = 0; k < s.K && ok; ++k) {
-      const int st = s_kstart[k], en = s_kstart[k + 1];
-      if (en > st && ((en * P - 1) / acc) - (((st + 1) * P - 1) / acc) + 1 > s.nsplit) ok = 0;
-    }
-    s_flat = ok;
-  }
+  // the album's 32-row tiles, dealt to the workgroups that share it (attn_fwd_shared.h: one dealer per workgroup)
+  if (tid == 64) deal_streams<32>(a.sv, n, s.K, s.nsplit, G, s_kstart, s_kcnt, s_kall, &s_flat);
   __syncthreads();
-  const bool flat = s_flat != 0;
-  const int tot = s_kstart[s.K];
-  const int lo = flat ? tot * pg / P : 0, hi = flat ? tot * (pg + 1) / P : 0;
-  auto empty_partial = [&](int nk, int split) {
-    float* pp = a.part + ((size_t)nk * s.nsplit + split) * (w + 4);
-    pp[0] = -INFINITY;
-    pp[1] = 0.f;
-    pp[2] = -INFINITY;
-  };
-  if (flat && g0 == 0) {  // the partial slots no run fills
-    for (int e = tid; e < nitems_n; e += 512) {
-      const int k = e / s.nsplit, sp = e % s.nsplit;
-      const int st = s_kstart[k], en = s_kstart[k + 1];
-      bool filled = false;
-      if (en > st) {
-        const int px = ((st + 1) * P - 1) / tot + sp;
-        filled = px < P && max(tot * px / P, st) < min(tot * (px + 1) / P, en);
-      }
-      if (!filled) empty_partial(n * s.K + k, sp);
-    }
-  }
-  struct Seg {
-    int nk, t0, t1, slot, cnt, allm;
-  };
-  auto item_seg = [&](int il, Seg& sg) {
-    const int k = il / s.nsplit, split = il % s.nsplit;
-    const int c = s_kcnt[k];
-    const int tiles_total = (c + 31) >> 5;
-    const int tiles_per = (tiles_total + s.nsplit - 1) / s.nsplit;
-    sg.nk = n * s.K + k;
-    sg.t0 = split * tiles_per;
-    sg.t1 = min(tiles_total, sg.t0 + tiles_per);
-    sg.slot = split;
-    sg.cnt = c;
-    sg.allm = s_kall[k];
-    return sg.t1 > sg.t0;
-  };
-  int it_k = 0, it_il = g0 - G;
-  auto next_seg = [&](Seg& sg) {  // (thread 0 only)
-    if (flat) {
-      while (it_k < s.K) {
-        const int k = it_k++;
-        const int st = s_kstart[k], en = s_kstart[k + 1];
-        if (st >= hi) break;
-        const int x0 = max(lo, st), x1 = min(hi, en);
-        if (x0 < x1) {
-          sg.nk = n * s.K + k;
-          sg.t0 = x0 - st;
-          sg.t1 = x1 - st;
-          sg.slot = pg - ((st + 1) * P - 1) / tot;
-          sg.cnt = s_kcnt[k];
-          sg.allm = s_kall[k];
-          return true;
-        }
-      }
-      it_k = s.K;
-      return false;
-    }
-    for (;;) {
-      it_il += G;
-      if (it_il >= nitems_n) return false;
-      if (item_seg(it_il, sg)) return true;
-      empty_partial(sg.nk, sg.slot);  // empty split
-    }
-  };
-  int rounds = hi - lo;
-  if (!flat) {
-    rounds = 0;
-    Seg sg;
-    for (int il = g0; il < nitems_n; il += G)
-      if (item_seg(il, sg)) rounds += sg.t1 - sg.t0;
-  }
+  AttnDeal dl = deal_init<1>(s_kstart, s_kcnt, s_kall, s_flat, a, n, g0, G, 0, true);
+  const int rounds = deal_rounds<32>(dl);
+  deal_fill_unowned<512>(dl, tid);
   if (rounds > WIDE_MAXR) __builtin_trap();  // (ruled out by the host's bound, wide_covers, and by attn_balance_kernel's run_cap)
   typedef int i32x4 __attribute__((ext_vector_type(4)));
   if (tid == 0) {  // the run's tiles, listed once
     Seg sg = {0, 0, 0, 0, 0, 0};
     int i = 0;
-    while (i < rounds && next_seg(sg))
+    while (i < rounds && next_seg<32>(dl, sg))
       for (int tl = sg.t0; tl < sg.t1 && i < rounds; ++tl, ++i)
         *reinterpret_cast<i32x4*>(s_tiles[i]) = i32x4{sg.nk, tl, sg.cnt, sg.slot | (sg.allm ? 256 : 0) | (tl + 1 == sg.t1 ? 512 : 0)};
-    if (!flat) {
+    if (!dl.flat) {  // (the empty partials of the items behind the run's last tile)
       Seg rest;
-      while (next_seg(rest)) {
+      while (next_seg<32>(dl, rest)) {
       }
     }
   }
@@ -270,13 +185,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_wide(AttnFwdArgs a, int G_all
             const f32x4 h0 = h[sb][2 * ks], h1 = h[sb][2 * ks + 1];
             if (hj == 0) {
               const float* vp = s_vec + coff + 32 * ks;
-              if (RMODE == 1)
-                rt4[sb] += h0 * *reinterpret_cast<const f32x4*>(vp) + h1 * *reinterpret_cast<const f32x4*>(vp + 16);
-              else if (RMODE == 2)
-                rt4[sb] += (h0 * h0) * *reinterpret_cast<const f32x4*>(vp + w) + (h1 * h1) * *reinterpret_cast<const f32x4*>(vp + w + 16);
-              else
-                rt4[sb] += h0 * (*reinterpret_cast<const f32x4*>(vp) + *reinterpret_cast<const f32x4*>(vp + w) * h0) +
-                           h1 * (*reinterpret_cast<const f32x4*>(vp + 16) + *reinterpret_cast<const f32x4*>(vp + w + 16) * h1);
+              row_term2<RMODE, 16>(rt4[sb], h0, h1, vp, 0, w);
             }
             // (the split is redone in every pass: left to itself the compiler keeps the first pass's 16 x 2 fragments -- 128
             //  registers -- alive for the second and spills rows; the empty asm makes this pass's inputs new values)
@@ -395,11 +304,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_wide(AttnFwdArgs a, int G_all
       float* part = a.part + ((size_t)cur.nk * s.nsplit + (cur.flags & 255)) * (w + 4);
       *reinterpret_cast<f32x4*>(part + 4 + CW * wave + 16 * l15 + 4 * kq) = u;
       u = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (tid == 0) {
-        part[0] = m_run;
-        part[1] = l_run;
-        part[2] = m_run;
-      }
+      if (tid == 0) store_partial_head(part, m_run, l_run);
       m_run = -INFINITY;
       l_run = 0.f;
     }
@@ -414,6 +319,7 @@ __global__ __launch_bounds__(512, 1) void attn_fwd_wide(AttnFwdArgs a, int G_all
 
 // host side: shapes covered, LDS, instantiation
 int wide_max_run() { return WIDE_MAXR; }
+// (the longest run a workgroup can be dealt, flat or round-robin: the dealing rule is written down in attn_fwd_shared.h)
 bool wide_covers(const AttnShape& s, int G) {
   if (!(s.w == 2048 && s.JT <= 2 && s.simi != 4)) return false;
   const int t32 = (s.T + 31) / 32;
@@ -422,28 +328,22 @@ bool wide_covers(const AttnShape& s, int G) {
   return (flat_max > rr_max ? flat_max : rr_max) <= WIDE_MAXR;
 }
 
+template <int NH, int RMODE>
+static void launch_wide(const AttnFwdArgs& a, int G, hipStream_t stream) {
+  const size_t lds = (size_t)8 * WIDE_NSTG * 4096 + (size_t)8 * 32 * 36 * sizeof(float) + (size_t)2 * a.s.w * 4;
+  (void)hipFuncSetAttribute((const void*)attn_fwd_wide<8, NH, RMODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((attn_fwd_wide<8, NH, RMODE>), attn_xcd_grid(a.s.N * G), dim3(512), lds, stream, a, G);
+}
+
 bool launch_attn_fwd_wide(const AttnFwdArgs& a, int G, hipStream_t stream) {
   const AttnShape& s = a.s;
   if (!wide_covers(s, G)) return false;
-  const int nwg = s.N * G;
-  const dim3 grid(((nwg + 7) / 8) * 8);
-  const int rmode = s.simi == 1 ? 1 : (s.simi == 3 ? 3 : 2);
-#define FVTA_WD(NH, RM)                                                                                                  \
-  do {                                                                                                                   \
-    const size_t lds = (size_t)8 * WIDE_NSTG * 4096 + (size_t)8 * 32 * 36 * sizeof(float) + (size_t)2 * s.w * 4; \
-    (void)hipFuncSetAttribute((const void*)attn_fwd_wide<8, NH, RM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((attn_fwd_wide<8, NH, RM>), grid, dim3(512), lds, stream, a, G);                                  \
-  } while (0)
-#define FVTA_WDH(NH)                                                                                                     \
-  do {                                                                                                                   \
-    if (rmode == 1) FVTA_WD(NH, 1); else if (rmode == 2) FVTA_WD(NH, 2); else FVTA_WD(NH, 3);                            \
-  } while (0)
-  if (s.JT == 2)
-    FVTA_WDH(2);
-  else
-    FVTA_WDH(1);
-#undef FVTA_WDH
-#undef FVTA_WD
+  attn_with_rmode(s.simi, [&](auto rm) {
+    if (s.JT == 2)
+      launch_wide<2, decltype(rm)::value>(a, G, stream);
+    else
+      launch_wide<1, decltype(rm)::value>(a, G, stream);
+  });
   return true;
 }
 

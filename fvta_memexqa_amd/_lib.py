@@ -52,6 +52,7 @@ _SIGS = {
     "fvta_abi_struct_bytes": (c_int64, [c_int32]),
     "fvta_attn_workspace_bytes": (c_size_t, [POINTER(AttnDesc)]),
     "fvta_attn_saved_bytes": (c_size_t, [POINTER(AttnDesc)]),
+    "fvta_attn_plan": (c_int, [POINTER(AttnDesc), c_int32, POINTER(c_int32)]),
     "fvta_attn_fwd": (c_int, [POINTER(AttnDesc), P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_attn_bwd": (c_int, [POINTER(AttnDesc), P, P, P, P, P, P, P, P, P, P, P, P, c_int, P, P]),
     "fvta_attn_fwd_shadow": (c_int, [POINTER(AttnDesc), P, P, P, P, P, P, P, P, P, P]),

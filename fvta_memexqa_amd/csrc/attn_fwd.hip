@@ -1663,6 +1663,19 @@ extern "C" size_t fvta_attn_workspace_bytes(const fvta_attn_desc* d) {
   return fwd > bwd ? fwd : bwd;
 }
 
+// How attn_shape() splits the work of this descriptor (host only, nothing is launched): tests assert the regime they
+// mean to exercise, so that a retuned threshold cannot silently move a shape out of it.
+extern "C" int fvta_attn_plan(const fvta_attn_desc* d, int32_t use_mask, int32_t out[4]) {
+  if (int e = fvta_attn_check_desc(d)) return e;
+  FVTA_CHECK_ARG(out != nullptr, "attn_plan: null pointer");
+  const AttnShape s = attn_shape(d, use_mask != 0);
+  out[0] = s.nsplit;
+  out[1] = s.bsplit;
+  out[2] = s.gk;
+  out[3] = s.ng;
+  return FVTA_OK;
+}
+
 extern "C" int fvta_attn_fwd(const fvta_attn_desc* d, const float* hinfo, const float* hq, const uint8_t* hmask,
                              const uint8_t* qmask, const float* W, const float* b, float* h_a, float* a_logits,
                              void* saved, void* workspace, fvta_stream_t stream_) {

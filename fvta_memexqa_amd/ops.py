@@ -225,6 +225,12 @@ class FocalAttention:
         self.work = _bytes(self.lib.fvta_attn_workspace_bytes(r), self.dev)
         self.N, self.K, self.T, self.JQ, self.w = N, K, T, JQ, w
 
+    def plan(self, use_mask=True):
+        """{nsplit, bsplit, gk, ng}: how the kernels split this shape's work (fvta_attn_plan; host only)"""
+        out = (ctypes.c_int32 * 4)()
+        check(self.lib.fvta_attn_plan(ctypes.byref(self.desc), int(bool(use_mask)), out), "fvta_attn_plan")
+        return dict(zip(("nsplit", "bsplit", "gk", "ng"), (int(v) for v in out)))
+
     def forward(self, hinfo, hq, hmask, qmask, W, b, want_logits=False, tscale=None):
         """tscale [N,T] (time_warp_att, model_v2.py:269-275): the softmax over t runs on amax * tscale."""
         h_a = torch.empty(self.N, self.w, device=self.dev, dtype=torch.float32)

@@ -76,6 +76,11 @@ typedef struct fvta_attn_desc {
 
 size_t fvta_attn_workspace_bytes(const fvta_attn_desc* d);
 size_t fvta_attn_saved_bytes(const fvta_attn_desc* d);
+/* How the kernels split this descriptor's work (host only, launches nothing; use_mask = both masks given):
+ * out = {nsplit, bsplit, gk, ng} -- workgroups per (n,k) of the forward main kernel and of the backward main kernel,
+ * consecutive k of one n that share a backward workgroup (> 1 only with bsplit == 1), and ceil(K / gk) groups per n.
+ * For tests and tools that must know which regime a shape runs in. */
+int fvta_attn_plan(const fvta_attn_desc* d, int32_t use_mask, int32_t out[4]);
 
 int fvta_attn_fwd(const fvta_attn_desc* d, const float* hinfo, const float* hq, const uint8_t* hmask,
                   const uint8_t* qmask, const float* W, const float* b, float* h_a, float* a_logits,

@@ -46,6 +46,14 @@ def test_size_queries_and_error_reporting(lib):
     bad5 = _lib.AttnDesc(1, 1, 8, 4, 64, 5, 0, 0)                 # model_v2.py:255-257
     assert lib.fvta_attn_saved_bytes(ctypes.byref(bad5)) == 0
     assert b"similarity matrix not implemented" in lib.fvta_last_error()
+    # fvta_attn_plan: attn_shape()'s split of the work, without a GPU -- the metric shape (long streams: split, never grouped),
+    # a batch past N*K = 1024 of short streams (the grouped backward tests/test_gpu_attention_batch.py is there for), errors
+    plan = (ctypes.c_int32 * 4)()
+    assert lib.fvta_attn_plan(ctypes.byref(d), 1, plan) == 0 and plan[0] > 1 and plan[1] > 1 and tuple(plan[2:]) == (1, 6)
+    dg = _lib.AttnDesc(320, 5, 16, 6, 128, 3, 0, 1)
+    assert lib.fvta_attn_plan(ctypes.byref(dg), 1, plan) == 0 and tuple(plan) == (1, 1, 3, 2)
+    assert lib.fvta_attn_plan(ctypes.byref(bad), 1, plan) == -1 and b"unsupported" in lib.fvta_last_error()
+    assert lib.fvta_attn_plan(ctypes.byref(d), 1, None) == -1
     ld = _lib.LstmDesc(12800, 30, 200, 512, 1, 0, 1, 0)
     assert lib.fvta_lstm_plan_bytes(ctypes.byref(ld)) > 2 * 2 * 30 * 12800 * 8
     assert lib.fvta_lstm_saved_bytes(ctypes.byref(ld)) >= 2 * 30 * 12800 * 5 * 512 * 4

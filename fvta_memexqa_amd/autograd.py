@@ -1,0 +1,321 @@
+"""torch.autograd over the C ABI: one `torch.autograd.Function` per op of the functional surface and of the encoders.
+
+Forward and backward are each one (or a few) calls into libfvta_hip.so; no arithmetic happens in Python.  Every Function
+is `once_differentiable` (no double backward).  Rules that hold for all of them:
+
+  * tensors are contiguous fp32 CUDA tensors with the channel widths the kernels accept -- zero padding and un-padding
+    stay OUTSIDE, as ordinary differentiable torch ops (functional.py, nn.py);
+  * a Function may be applied several times before one `backward()` (the reference runs one text cell over five
+    streams): whatever the forward leaves for the backward (`saved`, plans) belongs to that call alone;
+  * when no input requires grad the same kernels run, nothing is kept, the outputs are bit-identical;
+  * parameter gradients are accumulated by the kernels into fresh zero buffers, autograd sums them across calls.
+
+Deviations from TensorFlow's gradients that carry over from the model's backward kernels, on the
+`h_a` path of the focal attention only: an exact tie in the max over the question goes to the FIRST arg-max (TF splits
+it), and a fully masked (n,k) row list sends no gradient into its logits.  The `a_logits` path (fvta_attn_cube_bwd) is the
+plain dense gradient; the additive mask lets it through to masked entries, as in TF.
+"""
+import ctypes
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _lib, ops
+from ._lib import BF16, BF16X3, F32, check, ptr, stream_ptr
+
+_PRECISIONS = {"f32": F32, "bf16": BF16, "bf16x3": BF16X3, F32: F32, BF16: BF16, BF16X3: BF16X3}
+
+
+def _c(t):
+    return None if t is None else t.contiguous()
+
+
+# ------------------------------------------------------------------ small ops
+class _Softmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits):
+        out = torch.empty_like(logits)
+        J = logits.shape[-1]
+        check(_lib.load().fvta_softmax_fwd(ptr(logits), ptr(out), logits.numel() // J, J, stream_ptr()), "fvta_softmax_fwd")
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        p, = ctx.saved_tensors
+        dx = torch.empty_like(p)
+        ops.softmax_bwd(p, _c(g), dx, p.numel() // p.shape[-1], p.shape[-1])
+        return dx
+
+
+class _Softsel(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, target, logits):
+        J, d = target.shape[-2], target.shape[-1]
+        out = torch.empty(*target.shape[:-2], d, dtype=torch.float32, device=target.device)
+        check(_lib.load().fvta_softsel_fwd(ptr(target), ptr(logits), ptr(out), logits.numel() // J, J, d, stream_ptr()),
+              "fvta_softsel_fwd")
+        ctx.save_for_backward(target, logits)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        target, logits = ctx.saved_tensors
+        J, d = target.shape[-2], target.shape[-1]
+        dt = torch.empty_like(target) if ctx.needs_input_grad[0] else None
+        dl = torch.empty_like(logits) if ctx.needs_input_grad[1] else None
+        check(_lib.load().fvta_softsel_bwd(ptr(target), ptr(logits), ptr(_c(g)), ptr(dt), ptr(dl), logits.numel() // J, J, d,
+                                           stream_ptr()), "fvta_softsel_bwd")
+        return dt, dl
+
+
+class _ExpMask(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, val, mask_u8):
+        out = torch.empty_like(val)
+        check(_lib.load().fvta_exp_mask(ptr(val), ptr(mask_u8), ptr(out), val.numel(), stream_ptr()), "fvta_exp_mask")
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return g, None          # the mask is additive (utils.py:210-213)
+
+
+class _Linear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, W, b, add_tanh):
+        din, dout = W.shape
+        y = torch.empty(*x.shape[:-1], dout, dtype=torch.float32, device=x.device)
+        check(_lib.load().fvta_linear_fwd(ptr(x), ptr(W), ptr(b), ptr(y), x.numel() // din, din, dout, int(add_tanh),
+                                          stream_ptr()), "fvta_linear_fwd")
+        ctx.add_tanh = bool(add_tanh)
+        ctx.has_b = b is not None
+        ctx.save_for_backward(x, W, y)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, W, y = ctx.saved_tensors
+        din, dout = W.shape
+        need_x, need_W, need_b = ctx.needs_input_grad[:3]
+        dx = torch.empty_like(x) if need_x else None
+        dW = torch.zeros_like(W) if (need_W or need_b) else None
+        db = torch.zeros(dout, dtype=torch.float32, device=x.device) if (ctx.has_b and dW is not None) else None
+        ops.linear_bwd(x, W, y, _c(g), dx, dW, db, x.numel() // din, din, dout, add_tanh=ctx.add_tanh)
+        return dx, (dW if need_W else None), (db if need_b else None), None
+
+
+class _Wsum(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, target, weights):
+        rows, J, d = target.shape
+        out = torch.empty(rows, d, dtype=torch.float32, device=target.device)
+        check(_lib.load().fvta_wsum_fwd(ptr(target), ptr(weights), ptr(out), rows, J, d, stream_ptr()), "fvta_wsum_fwd")
+        ctx.save_for_backward(target, weights)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        target, weights = ctx.saved_tensors
+        rows, J, d = target.shape
+        dt = torch.zeros_like(target) if ctx.needs_input_grad[0] else None       # fvta_wsum_bwd adds into d_target
+        dw = torch.empty_like(weights) if ctx.needs_input_grad[1] else None
+        ops.wsum_bwd(target, weights, _c(g), dw, dt, rows, J, d)
+        return dt, dw
+
+
+def softmax(logits):
+    return _Softmax.apply(logits)
+
+
+def softsel(target, logits):
+    return _Softsel.apply(target, logits)
+
+
+def exp_mask(val, mask_u8):
+    return _ExpMask.apply(val, mask_u8)
+
+
+def linear(x, W, b, add_tanh=False):
+    """x [..., in] (contiguous), W [in, out], b [out] or None"""
+    return _Linear.apply(x, W, b, bool(add_tanh))
+
+
+def wsum(target, weights):
+    return _Wsum.apply(target, weights)
+
+
+# ------------------------------------------------------------ focal attention
+class _FocalAttention(torch.autograd.Function):
+    """(hinfo [N,K,T,w], hq [N,JQ,w], W [F*w] | None, b [1] | None, tscale [N,T] | None; masks u8 | None) ->
+    (h_a [N,w], a_logits [N,K,T,JQ]).  Each call owns its handle and with it the `saved` buffer."""
+
+    @staticmethod
+    def forward(ctx, hinfo, hq, W, b, tscale, hmask, qmask, simi, add_tanh, feat_order):
+        N, K, T, w = hinfo.shape
+        op = ops.FocalAttention(N, K, T, hq.shape[1], w, simi, add_tanh, feat_order=feat_order)
+        h_a, a = op.forward(hinfo, hq, hmask, qmask, W, b, want_logits=True, tscale=tscale)
+        ctx.set_materialize_grads(False)
+        ctx.op = op
+        ctx.masks = (hmask, qmask)
+        ctx.save_for_backward(hinfo, hq, W, b, tscale)
+        return h_a, a
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ha, g_a):
+        none = (None,) * 10
+        if g_ha is None and g_a is None:
+            return none
+        hinfo, hq, W, b, tscale = ctx.saved_tensors
+        hmask, qmask = ctx.masks
+        op = ctx.op
+        if g_a is not None and op.desc.simi == 4:
+            raise NotImplementedError("attention: no gradient of a_logits under simiMatrix 4 (the cosine cube has no "
+                                      "backward kernel); the h_a gradient is available")
+        dh, dq = torch.empty_like(hinfo), torch.empty_like(hq)
+        dW = torch.zeros_like(W) if W is not None else None
+        db = torch.zeros_like(b) if b is not None else None
+        dts = torch.zeros_like(tscale) if tscale is not None else None
+        if g_ha is not None:
+            op.backward(hinfo, hq, hmask, qmask, W, b, _c(g_ha), dh, dq, dW, db, 0, tscale=tscale, d_tscale=dts)
+        if g_a is not None:
+            r = ctypes.byref(op.desc)
+            work = ops._bytes(op.lib.fvta_attn_cube_bwd_workspace_bytes(r), op.dev)
+            check(op.lib.fvta_attn_cube_bwd(r, ptr(hinfo), ptr(hq), ptr(W), ptr(b), ptr(_c(g_a)), ptr(dh), ptr(dq), ptr(dW),
+                                            ptr(db), 0 if g_ha is None else 1, ptr(work), stream_ptr()), "fvta_attn_cube_bwd")
+        need = ctx.needs_input_grad
+        return (dh if need[0] else None, dq if need[1] else None, dW if need[2] else None, db if need[3] else None,
+                dts if need[4] else None) + (None,) * 5
+
+
+def focal_attention(hinfo, hq, W, b, hmask=None, qmask=None, simi=1, add_tanh=False, feat_order=0, tscale=None):
+    return _FocalAttention.apply(hinfo, hq, W, b, tscale, hmask, qmask, int(simi), bool(add_tanh), int(feat_order))
+
+
+class _AttnQSide(torch.autograd.Function):
+    """q_a [R,w] = mean_v softsel(hq[r], a_logits[r,v,:]) (the `bidirect` half, model_v2.py:184-188).  Forward: the three
+    launches functional._bidirect_q_a has always made (softmax over JQ, the mean over V of the weights, the weighted sum of
+    the question), so results do not depend on whether a gradient is wanted; backward: fvta_attn_qside_bwd (JQ <= 64,
+    V * JQ <= 8192).  The logit gradient it returns reaches hinfo, hq, W, b through fvta_attn_cube_bwd."""
+
+    @staticmethod
+    def forward(ctx, a_logits, hq):
+        R, V, JQ = a_logits.shape
+        p = _Softmax.apply(a_logits)
+        pbar = _Wsum.apply(p, torch.full((R, V), 1.0 / V, dtype=torch.float32, device=p.device))
+        ctx.save_for_backward(a_logits, hq)
+        return _Wsum.apply(hq, pbar)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        a_logits, hq = ctx.saved_tensors
+        R, V, JQ = a_logits.shape
+        dA = torch.empty_like(a_logits)
+        dq = torch.zeros_like(hq)                       # fvta_attn_qside_bwd adds into d_hq
+        ops.attn_qside_bwd(a_logits, hq, _c(g), dA, dq, R, V, JQ, hq.shape[-1])
+        return (dA if ctx.needs_input_grad[0] else None), (dq if ctx.needs_input_grad[1] else None)
+
+
+def attn_qside(a_logits, hq):
+    return _AttnQSide.apply(a_logits, hq)
+
+
+# -------------------------------------------------------------------- bi-LSTM
+class _BiLstm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, lens, kernel_fw, bias_fw, kernel_bw, bias_bw, precision):
+        B, J, din = x.shape
+        d = kernel_fw.shape[1] // 4
+        train = any(ctx.needs_input_grad)               # the descriptor keeps gate activations only when a gradient is needed
+        ar = torch.arange(B, dtype=torch.int64)
+        op = ops.BiLstm(B, J, din, d, ar * J * din, ar * J * 2 * d, torch.full((B,), J, dtype=torch.int32), 2 * d,
+                        share_fw_bw=kernel_bw is None, precision=precision, training=train)
+        op.make_plan(lens)
+        out = torch.empty(B, J, 2 * d, device=x.device, dtype=torch.float32)
+        op.forward(x, out, kernel_fw, bias_fw, kernel_bw, bias_bw)
+        last = torch.empty(B, 2 * d, device=x.device, dtype=torch.float32)
+        op.last_state(out, 0, B, last)
+        ctx.set_materialize_grads(False)
+        if train:
+            ctx.op = op
+            ctx.save_for_backward(x, out, kernel_fw, kernel_bw)
+        return out, last
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_last):
+        none = (None,) * 7
+        if g_out is None and g_last is None:
+            return none
+        x, out, kernel_fw, kernel_bw = ctx.saved_tensors
+        op = ctx.op
+        d_out = g_out.contiguous().clone() if g_out is not None else torch.zeros_like(out)
+        if g_last is not None:
+            op.last_state_bwd(_c(g_last), 0, op.B, d_out)
+        need = ctx.needs_input_grad
+        dx = torch.zeros_like(x) if need[0] else None
+        dk_fw = torch.zeros_like(kernel_fw)
+        db_fw = torch.zeros(kernel_fw.shape[1], dtype=torch.float32, device=x.device)
+        dk_bw = torch.zeros_like(kernel_bw) if kernel_bw is not None else None
+        db_bw = torch.zeros_like(db_fw) if kernel_bw is not None else None
+        op.backward(x, out, d_out, kernel_fw, kernel_bw, dx, dk_fw, db_fw, dk_bw, db_bw)
+        return (dx, None, dk_fw if need[2] else None, db_fw if need[3] else None,
+                dk_bw if kernel_bw is not None and need[4] else None, db_bw if kernel_bw is not None and need[5] else None, None)
+
+
+def bilstm(x, lens, kernel_fw, bias_fw, kernel_bw=None, bias_bw=None, precision="f32"):
+    """model_v2.py:652-661, 694-823: x [B,J,in] dense, lens [B] -> (out [B,J,2d] with rows t >= len zeroed, last [B,2d] =
+    concat(fw h at len-1, bw h at 0)).  kernel [in+d, 4d] gate order i,j,f,o, bias [4d]; in % 4 == 0, d % 32 == 0
+    (nn.BiLSTMEncoder pads any size).  Without kernel_bw both directions share the cell.  Either output's gradient may be
+    absent."""
+    if precision not in _PRECISIONS:
+        raise ValueError("bilstm: precision %r (f32 | bf16 | bf16x3)" % (precision,))
+    ops.require_gpu()
+    f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+    return _BiLstm.apply(f(x), lens.to(torch.int32), f(kernel_fw), f(bias_fw), f(kernel_bw), f(bias_bw),
+                         _PRECISIONS[precision])
+
+
+# --------------------------------------------------------------------- scorer
+class _ScorerCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, gq, g1, gch, W, b, y, use_eu_output, add_tanh, tf_xent_grad):
+        logits, yp, loss = ops.scorer_ce_fwd(gq, g1, gch, W, b, y, use_eu_output=use_eu_output, add_tanh=add_tanh)
+        ctx.flags = (use_eu_output, add_tanh, tf_xent_grad)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(logits, yp)
+        ctx.save_for_backward(gq, g1, gch, W, b, y, logits, yp)
+        return loss.reshape(()), logits, yp
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss, _g_logits, _g_yp):
+        if g_loss is None:
+            return (None,) * 9
+        gq, g1, gch, W, b, y, logits, yp = ctx.saved_tensors
+        eu, tanh, tfg = ctx.flags
+        dW, db = torch.zeros_like(W), torch.zeros_like(b)
+        dgq, dg1, dgch = ops.scorer_ce_bwd(gq, g1, gch, W, b, y, logits, yp, 1.0, dW, db, use_eu_output=eu, add_tanh=tanh,
+                                           tf_xent_grad=tfg)
+        # d loss arrives as a device scalar; fvta_scorer_ce_bwd takes its scale from the host, so the kernel runs at 1 and
+        # the five results are scaled here (no host sync)
+        need = ctx.needs_input_grad
+        outs = [t * g_loss if n else None for t, n in zip((dgq, dg1, dgch, dW, db), need[:5])]
+        return tuple(outs) + (None,) * 4
+
+
+def scorer_ce(gq, g1, gch, W, b, y, use_eu_output=False, add_tanh=False, tf_xent_grad=True):
+    """model_v2.py:1053-1096: gq, g1 [N,w], gch [N,C,w], W [5w] (7w with use_eu_output), b [1], y [N,C] labels ->
+    (loss scalar, logits [N,C], yp [N,C]); only `loss` is differentiable.  tf_xent_grad: TF-1's cross-entropy gradient
+    (softmax - labels on every row, all-False label rows included); False: the gradient of the loss as a function."""
+    ops.require_gpu()
+    f = lambda t: t.to(torch.float32).contiguous()
+    return _ScorerCE.apply(f(gq), f(g1), f(gch), f(W).reshape(-1), f(b), ops.as_mask_u8(y), bool(use_eu_output),
+                           bool(add_tanh), bool(tf_xent_grad))

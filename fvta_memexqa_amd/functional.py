@@ -12,8 +12,13 @@
                         bidirect=False, scope=None) -> h_a [N,M,w]                   model.py:247-314
     attention_tgif(hinfo, lq, hinfo_mask=None, wd=None, mlp_dim=512, scope=None)     model.py:210-244
 
-Tensors are torch CUDA tensors; every op is one call into libfvta_hip.so (forward only -- training goes through
-`Model`, whose backward kernels own the gradients).  Where the reference creates TF variables (`linear`'s W / b, the
+Tensors are torch CUDA tensors; every op is one call into libfvta_hip.so, wrapped in a `torch.autograd.Function`
+(autograd.py): a tensor that requires grad gets its gradient through the library's backward kernels, and when nothing
+requires grad the same forward kernels run and nothing is kept.  `attention_keeprank1` alone is forward only.  The
+variable store keeps plain tensors; `variables[name].requires_grad_()` makes one a leaf that receives its gradient.
+On the focal attentions' `h_a` path two deviations of the model's backward kernels carry over: an
+exact tie in the max over the question sends its gradient to the FIRST arg-max (TensorFlow splits it), and a fully
+masked (n,k) row list sends no gradient into its logits.  Where the reference creates TF variables (`linear`'s W / b, the
 `att_logits` linear inside the attentions) the variable lives in a module-level store under the same scoped name
 (`variable_scope("attention")` + `scope="all"` -> "attention/all/att_logits/W"), initialised like the reference
 (truncated normal 0.1 / zeros) and reused on the next call, which is what `tf.get_variable` under reuse does.
@@ -25,7 +30,7 @@ import zlib
 
 import torch
 
-from . import _lib, ops
+from . import _lib, autograd, ops
 from ._lib import check, ptr, stream_ptr
 from .model_v2 import SUPPORTED_W
 
@@ -88,11 +93,7 @@ def _f32(t):
 
 
 def softmax(logits, scope=None):
-    logits = _f32(logits)
-    out = torch.empty_like(logits)
-    J = logits.shape[-1]
-    check(_lib.load().fvta_softmax_fwd(ptr(logits), ptr(out), logits.numel() // J, J, stream_ptr()), "fvta_softmax_fwd")
-    return out
+    return autograd.softmax(_f32(logits))
 
 
 def softsel(target, logits, hard=False, hardK=None, scope=None):
@@ -101,28 +102,18 @@ def softsel(target, logits, hard=False, hardK=None, scope=None):
     J, d = target.shape[-2], target.shape[-1]
     if tuple(logits.shape) != tuple(target.shape[:-1]):
         raise ValueError("softsel: logits %s do not match target %s" % (tuple(logits.shape), tuple(target.shape)))
-    out = torch.empty(*target.shape[:-2], d, dtype=torch.float32, device=target.device)
-    check(_lib.load().fvta_softsel_fwd(ptr(target), ptr(logits), ptr(out), logits.numel() // J, J, d, stream_ptr()),
-          "fvta_softsel_fwd")
-    return out
+    return autograd.softsel(target, logits)
 
 
 def exp_mask(val, mask):
     val = _f32(val)
     m = ops.as_mask_u8(mask.expand_as(val) if tuple(mask.shape) != tuple(val.shape) else mask)
-    out = torch.empty_like(val)
-    check(_lib.load().fvta_exp_mask(ptr(val), ptr(m), ptr(out), val.numel(), stream_ptr()), "fvta_exp_mask")
-    return out
+    return autograd.exp_mask(val, m)
 
 
 def linear_raw(x, W, b, add_tanh=False):
     """flatten(x, 1) . W [in, out] + b through fvta_linear_fwd with explicit weights (no variable scope)"""
-    x = _f32(x)
-    din, dout = x.shape[-1], W.shape[1]
-    y = torch.empty(*x.shape[:-1], dout, dtype=torch.float32, device=x.device)
-    check(_lib.load().fvta_linear_fwd(ptr(x), ptr(_f32(W)), ptr(b), ptr(y), x.numel() // din, din, dout, int(add_tanh),
-                                      stream_ptr()), "fvta_linear_fwd")
-    return y
+    return autograd.linear(_f32(x), _f32(W), None if b is None else _f32(b), add_tanh)
 
 
 def linear(x, output_size, scope, add_tanh=False, wd=None):
@@ -133,50 +124,57 @@ def linear(x, output_size, scope, add_tanh=False, wd=None):
         W = get_variable(wn, (din, int(output_size)))
         b = get_variable(bn, (int(output_size),), init="zeros")
         _add_wd([wn, bn], wd)
-    y = torch.empty(*x.shape[:-1], int(output_size), dtype=torch.float32, device=x.device)
-    check(_lib.load().fvta_linear_fwd(ptr(x), ptr(W), ptr(b), ptr(y), x.numel() // din, din, int(output_size), int(add_tanh),
-                                      stream_ptr()), "fvta_linear_fwd")
-    return y
+    return autograd.linear(x, W, b, add_tanh)
 
 
 def _pad_channels(t, wp):
     w = t.shape[-1]
     if w == wp:
         return t.contiguous()
-    out = torch.zeros(*t.shape[:-1], wp, dtype=torch.float32, device=t.device)
-    out[..., :w] = t
-    return out
+    return torch.nn.functional.pad(t, (0, wp - w))      # (differentiable: the gradient of the padding is dropped)
 
 
-def _attention(hinfo, hq, hinfo_mask, hq_mask, simiMatrix, wd, add_tanh, scope, feat_order, tscale=None):
-    """hinfo [N,K,T,w] -> (h_a [N,w], a_logits [N,K,T,JQ]) through fvta_attn_fwd; w is zero padded to a kernel width
-    (exact: a zero channel adds nothing to any feature of any similarity), W block-wise with it."""
+def attention_raw(hinfo, hq, W, b, hinfo_mask=None, hq_mask=None, simiMatrix=1, add_tanh=False, feat_order=0, tscale=None):
+    """The focal attention with explicit weights: hinfo [N,K,T,w], hq [N,JQ,w], W [F*w, 1] (any shape with F*w elements;
+    None for simiMatrix 4), b [1] -> (h_a [N,w], a_logits [N,K,T,JQ]).  w is zero padded to a kernel width (exact: a zero
+    channel adds nothing to any feature of any similarity), W block-wise with it; both outputs are differentiable
+    (h_a: fvta_attn_bwd_tw, a_logits: fvta_attn_cube_bwd)."""
     if simiMatrix not in (1, 2, 3, 4):
         raise ValueError("similarity matrix not implemented")              # model_v2.py:255-257 (sys.exit there)
     hinfo, hq = _f32(hinfo), _f32(hq)
     N, K, T, w = hinfo.shape
-    JQ = hq.shape[1]
     wp = next((c for c in SUPPORTED_W if w <= c), None)
     if wp is None:
         raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
+    F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
+    if F:
+        W = _pad_channels(_f32(W).reshape(F, w), wp).reshape(-1)
+        b = _f32(b)
+    else:
+        W = b = None
+    ops.require_gpu()
+    both = hinfo_mask is not None and hq_mask is not None                  # model_v2.py:146 / 233: only when BOTH are given
+    hm = ops.as_mask_u8(hinfo_mask.reshape(N, K, T)) if both else None
+    qm = ops.as_mask_u8(hq_mask) if both else None
+    h_a, a = autograd.focal_attention(_pad_channels(hinfo, wp), _pad_channels(hq, wp), W, b, hm, qm, simiMatrix, add_tanh,
+                                      feat_order, tscale)
+    return h_a[:, :w].contiguous(), a
+
+
+def _attention(hinfo, hq, hinfo_mask, hq_mask, simiMatrix, wd, add_tanh, scope, feat_order, tscale=None):
+    """attention_raw with the `att_logits` variables of the scope (linear(..., output_size=1, scope="att_logits"))"""
+    if simiMatrix not in (1, 2, 3, 4):
+        raise ValueError("similarity matrix not implemented")
+    w = hinfo.shape[-1]
     F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
     W = b = None
     with variable_scope(scope):
         if F:
             wn, bn = _name("att_logits", "W"), _name("att_logits", "b")
-            Wv = get_variable(wn, (F * w, 1))                              # linear(..., output_size=1, scope="att_logits")
+            W = get_variable(wn, (F * w, 1))
             b = get_variable(bn, (1,), init="zeros")
-            W = Wv.reshape(F, w)
-            if wp != w:
-                W = _pad_channels(W, wp)
-            W = W.reshape(-1).contiguous()
             _add_wd([wn, bn], wd)
-    op = ops.FocalAttention(N, K, T, JQ, wp, simiMatrix, add_tanh, feat_order=feat_order)
-    both = hinfo_mask is not None and hq_mask is not None                  # model_v2.py:146 / 233: only when BOTH are given
-    hm = ops.as_mask_u8(hinfo_mask.reshape(N, K, T)) if both else None
-    qm = ops.as_mask_u8(hq_mask) if both else None
-    h_a, a = op.forward(_pad_channels(hinfo, wp), _pad_channels(hq, wp), hm, qm, W, b, want_logits=True, tscale=tscale)
-    return h_a[:, :w].contiguous(), a
+    return attention_raw(hinfo, hq, W, b, hinfo_mask, hq_mask, simiMatrix, add_tanh, feat_order, tscale)
 
 
 def attention_3d(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, add_tanh=False, time_warp_att=False,
@@ -200,11 +198,7 @@ def attention_3d(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None
 
 def _wsum(target, weights):
     """sum_j weights[r,j] * target[r,j,:] -> [rows, d] (fvta_wsum_fwd)"""
-    target, weights = _f32(target), _f32(weights)
-    rows, J, d = target.shape
-    out = torch.empty(rows, d, dtype=torch.float32, device=target.device)
-    check(_lib.load().fvta_wsum_fwd(ptr(target), ptr(weights), ptr(out), rows, J, d, stream_ptr()), "fvta_wsum_fwd")
-    return out
+    return autograd.wsum(_f32(target), _f32(weights))
 
 
 def _bidirect_q_a(a_logits, hq, lead):
@@ -226,6 +220,15 @@ def _bidirect_q_a(a_logits, hq, lead):
     return _wsum(q, pbar).reshape(*lead, q.shape[-1])
 
 
+def bidirect_q_a(a_logits, hq):
+    """_bidirect_q_a for the 1-D attention (a_logits [N,V,JQ] -> q_a [N,w]): the same three launches; where
+    fvta_attn_qside_bwd covers the shape (JQ <= 64, V * JQ <= 8192) it is their backward, otherwise each launch's own."""
+    N, V, JQ = a_logits.shape
+    if JQ <= 64 and V * JQ <= 8192:
+        return autograd.attn_qside(a_logits.contiguous(), _f32(hq))
+    return _bidirect_q_a(a_logits, hq, (N,))
+
+
 def attention(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, add_tanh=False, bidirect=False, scope=None):
     """hinfo [N,...,w] flattened to [N,V,w] (model_v2.py:133) -> (h_a [N,w], a_logits [N,V,JQ]); with `bidirect`
     h_a is [N,2w] = concat([h_a, q_a]) (model_v2.py:184-192)."""
@@ -235,15 +238,18 @@ def attention(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, a
     h_a, a = _attention(h, hq, hm, hq_mask, simiMatrix, wd, add_tanh, scope or "attention_2vector", 0)
     a = a.reshape(N, h.shape[2], hq.shape[1])
     if bidirect:
-        h_a = torch.cat([h_a, _bidirect_q_a(a, hq, (N,))], 1)              # tf.concat: memory layout, no arithmetic
+        h_a = torch.cat([h_a, bidirect_q_a(a, hq)], 1)                      # tf.concat: memory layout, no arithmetic
     return h_a, a
 
 
+@torch.no_grad()
 def attention_keeprank1(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, bidirect=False, scope=None):
     """model.py:247-314: hinfo [N,M,...,w] -> h_a [N,M,w] ([N,M,2w] with `bidirect`), each album attended on its own (softsel over the rows of
     (n, m) with the max-over-question logits; no softmax over m).  That is the inner stage of attention_3d with K = M:
     one fvta_attn_fwd, then the per-(n,k) result is read back out of the saved state.  model.py's feature order for
-    simiMatrix 2 is [(h-q)^2, h*q] (feat_order 1); no tanh on the logits."""
+    simiMatrix 2 is [(h-q)^2, h*q] (feat_order 1); no tanh on the logits.
+    FORWARD ONLY (runs under torch.no_grad): the per-(n,k) read-out has no backward kernel, so the result carries no
+    grad_fn even when an input requires grad (the other helpers of this module are differentiable)."""
     if simiMatrix not in (1, 2, 3):
         raise ValueError("similarity matrix not implemented")              # model.py:283-285 (sys.exit there)
     hinfo, hq = _f32(hinfo), _f32(hq)
@@ -290,8 +296,7 @@ def attention_tgif(hinfo, lq, hinfo_mask=None, wd=None, mlp_dim=512, scope=None)
         att = softmax(score)
         if hinfo_mask is not None:
             att = exp_mask(att, hinfo_mask.reshape(N, V))
-        attended = torch.empty(N, w, dtype=torch.float32, device=h.device)
-        check(_lib.load().fvta_wsum_fwd(ptr(h), ptr(att), ptr(attended), N, V, w, stream_ptr()), "fvta_wsum_fwd")
+        attended = _wsum(h, att)
         final = linear(attended, 2 * mlp_dim, scope="final", add_tanh=True)
         if wd is not None:                                                    # add_wd over the whole scope (:241-242)
             _add_wd([n for n in variables if n.startswith(_name("") )], wd)

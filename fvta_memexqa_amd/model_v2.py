@@ -51,6 +51,24 @@ def padded_hidden(d):
     raise ValueError("hidden_size %d too large (max %d)" % (d, SUPPORTED_W[-1] // 2))
 
 
+def pad_lstm_kernel(k, din, dinp, d, dp):
+    """reference [din+d, 4d] -> padded [dinp+dp, 4dp] (input rows, zero rows, hidden rows; gate blocks
+    i,j,f,o kept apart).  Plain slicing on k's device: differentiable when k requires grad."""
+    out = torch.zeros(dinp + dp, 4 * dp, dtype=torch.float32, device=k.device)
+    for g in range(4):
+        out[:din, g * dp:g * dp + d] = k[:din, g * d:(g + 1) * d]
+        out[dinp:dinp + d, g * dp:g * dp + d] = k[din:, g * d:(g + 1) * d]
+    return out
+
+
+def pad_blocks(v, nblk, blk, blkp):
+    """[nblk * blk] -> [nblk * blkp]: every block zero padded at its end (LSTM bias gates, feature vectors)."""
+    out = torch.zeros(nblk * blkp, dtype=torch.float32, device=v.device)
+    for g in range(nblk):
+        out[g * blkp:g * blkp + blk] = v[g * blk:(g + 1) * blk]
+    return out
+
+
 class ParamStore:
     """All trainables in ONE flat fp32 device buffer (+ one flat gradient buffer):
     a single RCCL all-reduce bucket and a single optimiser launch per step."""
@@ -267,14 +285,7 @@ class Model:
 
     # ------------------------------------------------------------ parameters
     def _pad_kernel(self, k, din, dinp):
-        """reference [din+d, 4d] -> padded [dinp+dp, 4dp] (input rows, zero rows, hidden rows; gate blocks
-        i,j,f,o kept apart)."""
-        d, dp = self.d, self.dp
-        out = torch.zeros(dinp + dp, 4 * dp, dtype=torch.float32)
-        for g in range(4):
-            out[:din, g * dp:g * dp + d] = k[:din, g * d:(g + 1) * d]
-            out[dinp:dinp + d, g * dp:g * dp + d] = k[din:, g * d:(g + 1) * d]
-        return out
+        return pad_lstm_kernel(k, din, dinp, self.d, self.dp)
 
     def _unpad_kernel(self, kp, din, dinp):
         d, dp = self.d, self.dp
@@ -288,10 +299,7 @@ class Model:
         return (self.text_in, self.text_in_p) if "utext" in name else (self.img_in, self.img_in_p)
 
     def _pad_blocks(self, v, nblk, blk, blkp):
-        out = torch.zeros(nblk * blkp, dtype=torch.float32)
-        for g in range(nblk):
-            out[g * blkp:g * blkp + blk] = v[g * blk:(g + 1) * blk]
-        return out
+        return pad_blocks(v, nblk, blk, blkp)
 
     def _pad_feat(self, v):
         """[F*w] feature vectors (att W, scorer W): each w-block = [fw d | bw d] -> [fw dp | bw dp]."""

@@ -414,8 +414,8 @@ int fvta_adam_step(float* var, const float* grad, float* m, float* v, int64_t n,
 int fvta_weight_decay(const float* var, float* grad, int64_t n, float coef, float* loss, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
- * Stand-alone forms of the reference's small graph helpers (SURVEY 8b "functional ops"), forward only.  Inside the
- * model they are folded into the attention / scorer / embedding kernels.
+ * Stand-alone forms of the reference's small graph helpers (SURVEY 8b "functional ops"); their backwards follow below.
+ * Inside the model they are folded into the attention / scorer / embedding kernels.
  *   fvta_softmax_fwd : softmax(logits) over the last axis, model_v2.py:23-28 (logits viewed as [rows, J])
  *   fvta_softsel_fwd : softsel(target [rows,J,d], logits [rows,J]) -> [rows,d], model_v2.py:39-48
  *   fvta_exp_mask    : val + (1 - mask) * -1e30, utils.py:210-213
@@ -491,6 +491,22 @@ int fvta_attn_qside_bwd(const float* a_logits, const float* hq, const float* d_q
 size_t fvta_attn_logits_bwd_workspace_bytes(const fvta_attn_desc* d);
 int fvta_attn_logits_bwd(const fvta_attn_desc* d, const float* hinfo, const float* hq, const float* W, const float* dA,
                          float* d_hinfo, float* d_hq, float* dW, float* db, void* workspace, fvta_stream_t stream);
+/* The dense gradient of the focal logits CUBE: dA [N,K,T,JQ], the gradient of the value fvta_attn_fwd writes to a_logits
+ * (model_v2.py:210-298's second result; tester.py:34-36 reads it, a loss on the evidence photos supervises it), at any K,
+ * any T, with add_tanh, simiMatrix 1-3, both feat_orders, JQ <= 64, w in {64 .. 2048}; hinfo_stride as in
+ * fvta_attn_logits_bwd.  The mask is additive (exp_mask), so dA reaches masked entries too and the call takes no masks;
+ * under add_tanh the pre-activation is recomputed (a masked a_logits entry is exactly -1e30).  accumulate = 0: d_hinfo
+ * [N,K,T,w] and d_hq [N,JQ,w] (summed over k) are overwritten, nothing of them is read; 1: both are added to.  dW, db are
+ * always accumulated into.  Exact fp32, fixed summation order (per-workgroup slabs in `workspace`, no atomics). */
+size_t fvta_attn_cube_bwd_workspace_bytes(const fvta_attn_desc* d);
+int fvta_attn_cube_bwd(const fvta_attn_desc* d, const float* hinfo, const float* hq, const float* W, const float* b,
+                       const float* dA, float* d_hinfo, float* d_hq, float* dW, float* db, int accumulate, void* workspace,
+                       fvta_stream_t stream);
+/* Backward of fvta_softsel_fwd from d_out [rows,d]: p = softmax(logits) is recomputed (an all -1e30 row is uniform, as in
+ * the forward); d_target [rows,J,d] = p (x) d_out, d_logits [rows,J] = p (g - sum_j p g) with g[j] = d_out . target[j].
+ * Both are overwritten; either may be NULL. */
+int fvta_softsel_bwd(const float* target, const float* logits, const float* d_out, float* d_target, float* d_logits,
+                     int64_t rows, int32_t J, int32_t d, fvta_stream_t stream);
 /* attention_keeprank1 (model.py:247-314) = the per-(n,k) inner softsel of attention_3d without the softmax over k:
  * after fvta_attn_fwd(desc with K = M) this copies that result, u[N,K,w], out of the saved state. */
 int fvta_attn_read_u(const fvta_attn_desc* d, const void* saved, float* u_out, fvta_stream_t stream);

@@ -120,6 +120,8 @@ _SIGS = {
     "fvta_rows_reduce": (c_int, [P, P, c_int64, c_int32, c_int32, c_int64, c_float, c_int32, P]),
     "fvta_rows_broadcast": (c_int, [P, P, c_int64, c_int32, c_int32, c_int64, c_float, c_int32, P]),
     "fvta_attn_read_u": (c_int, [POINTER(AttnDesc), P, P, P]),
+    "fvta_attn_bwd_u_workspace_bytes": (c_size_t, [POINTER(AttnDesc)]),
+    "fvta_attn_bwd_u": (c_int, [POINTER(AttnDesc), P, P, P, P, P, P, P, P, P, P, P, P, c_int, P, P]),
     "fvta_test_gemm": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, P, P, P, P]),
     "fvta_profile_enable": (c_int, [c_int32]),
     "fvta_lstm_kernel_select": (c_int, [c_int32]),

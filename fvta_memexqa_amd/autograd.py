@@ -11,9 +11,10 @@ is `once_differentiable` (no double backward).  Rules that hold for all of them:
   * parameter gradients are accumulated by the kernels into fresh zero buffers, autograd sums them across calls.
 
 Deviations from TensorFlow's gradients that carry over from the model's backward kernels, on the
-`h_a` path of the focal attention only: an exact tie in the max over the question goes to the FIRST arg-max (TF splits
-it), and a fully masked (n,k) row list sends no gradient into its logits.  The `a_logits` path (fvta_attn_cube_bwd) is the
-plain dense gradient; the additive mask lets it through to masked entries, as in TF.
+`h_a` path of the focal attention and on attention_keeprank1's per-(n,m) vectors (fvta_attn_bwd_u, the same kernels): an
+exact tie in the max over the question goes to the FIRST arg-max (TF splits it), and a fully masked (n,k) row list sends
+no gradient into its logits.  The `a_logits` path (fvta_attn_cube_bwd) is the plain dense gradient; the additive mask
+lets it through to masked entries, as in TF.
 """
 import ctypes
 
@@ -196,6 +197,58 @@ class _FocalAttention(torch.autograd.Function):
 
 def focal_attention(hinfo, hq, W, b, hmask=None, qmask=None, simi=1, add_tanh=False, feat_order=0, tscale=None):
     return _FocalAttention.apply(hinfo, hq, W, b, tscale, hmask, qmask, int(simi), bool(add_tanh), int(feat_order))
+
+
+class _KeepRank1(torch.autograd.Function):
+    """attention_keeprank1 (model.py:247-314): (hinfo [N,M,V,w], hq [N,JQ,w], W [F*w], b [1]; masks u8 | None) ->
+    (u [N,M,w], a_logits [N,M,V,JQ] | None).  Forward: fvta_attn_fwd at K = M in model.py's feature order, then the
+    per-(n,m) softsel result read out of `saved` (fvta_attn_read_u); the logits cube only when `want_logits` (the bidirect
+    branch) -- asking for it selects the general forward kernel, so the flag keeps `u` what it has always been.
+    Backward: fvta_attn_bwd_u for g_u, fvta_attn_cube_bwd at K = M for g_a (on top when both are present).
+    fvta_attn_bwd_u takes N * M <= 65535 (a larger batch that requires grad is refused in the forward) and its workspace,
+    allocated in backward(), holds one dQs slab set per (n,m): N M bsplit (256 / min(w/4, 256)) 32 ceil(JQ/32) w floats
+    (136 MB at N M = 1040, w = 64)."""
+
+    @staticmethod
+    def forward(ctx, hinfo, hq, W, b, hmask, qmask, simi, want_logits):
+        N, M, V, w = hinfo.shape
+        op = ops.FocalAttention(N, M, V, hq.shape[1], w, simi, False, feat_order=1)
+        _, a = op.forward(hinfo, hq, hmask, qmask, W, b, want_logits=want_logits)
+        u = op.read_u()
+        ctx.set_materialize_grads(False)
+        if any(ctx.needs_input_grad):
+            # what fvta_attn_bwd_u does not cover (N * M > 65535) is refused here, not in backward()
+            if op.lib.fvta_attn_bwd_u_workspace_bytes(ctypes.byref(op.desc)) == 0:
+                raise _lib.FvtaError("attention_keeprank1: " + op.lib.fvta_last_error().decode())
+            ctx.op = op
+            ctx.masks = (hmask, qmask)
+            ctx.save_for_backward(hinfo, hq, W, b)
+        return u, a
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_u, g_a):
+        none = (None,) * 8
+        if g_u is None and g_a is None:
+            return none
+        hinfo, hq, W, b = ctx.saved_tensors
+        hmask, qmask = ctx.masks
+        op = ctx.op
+        dh, dq = torch.empty_like(hinfo), torch.empty_like(hq)
+        dW, db = torch.zeros_like(W), torch.zeros_like(b)
+        if g_u is not None:
+            op.backward_u(hinfo, hq, hmask, qmask, W, b, _c(g_u), dh, dq, dW, db, 0)
+        if g_a is not None:
+            r = ctypes.byref(op.desc)
+            work = ops._bytes(op.lib.fvta_attn_cube_bwd_workspace_bytes(r), op.dev)
+            check(op.lib.fvta_attn_cube_bwd(r, ptr(hinfo), ptr(hq), ptr(W), ptr(b), ptr(_c(g_a)), ptr(dh), ptr(dq), ptr(dW),
+                                            ptr(db), 0 if g_u is None else 1, ptr(work), stream_ptr()), "fvta_attn_cube_bwd")
+        need = ctx.needs_input_grad
+        return (dh if need[0] else None, dq if need[1] else None, dW if need[2] else None, db if need[3] else None) + (None,) * 4
+
+
+def keeprank1(hinfo, hq, W, b, hmask=None, qmask=None, simi=1, want_logits=False):
+    return _KeepRank1.apply(hinfo, hq, W, b, hmask, qmask, int(simi), bool(want_logits))
 
 
 class _AttnQSide(torch.autograd.Function):

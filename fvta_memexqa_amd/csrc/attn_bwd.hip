@@ -113,12 +113,81 @@ __global__ __launch_bounds__(1024) void attn_bwd_prep_kernel(AttnShape s, AttnSa
   }
 }
 
+// ---- the same scalars when every (n,k) is an attention of its own (fvta_attn_bwd_u): g = d_u[n,k], no softmax over k --
+// r[k] = 1 and the k-softmax term dss is 0.  A row's logit gradient is p[t] (g.h[t] - g.u) and sums to 0 over a list; the
+// forward's L and u come from an online softmax (products of several expf), so against the weights the main kernel
+// recomputes, expf(amax - Mz) / L, they are off by a few 1e-7 per row -- with a gradient vector per (n,k) that is a
+// residue of ~1e-6 per list in db, 2.5e-5 at a thousand lists where the result is 0.  So this kernel takes both from the
+// weights the main kernel will use: L = sum_t e[t] and g.u = sum_t e[t] (g.h[t]) / L with e[t] = expf(amax[t] - Mz) -- the
+// same expression as there -- over the list's rows, in fp64, rounded once.  One more read of the rows (no target here).
+// A wave per (n,k), grid ceil(N K / 4); a lane sums its channels over all rows, one wave reduction at the end.
+__global__ __launch_bounds__(256) void attn_bwd_prep_u_kernel(AttnShape s, AttnSaved sv, AttnBwdWork wk,
+                                                              const float* __restrict__ hinfo,
+                                                              const float* __restrict__ d_u) {
+  const int nk = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (nk >= s.N * s.K) return;
+  const int T = s.T, w = s.w, cnt = sv.cnt[nk];
+  const float* g = d_u + (size_t)nk * w;
+  const float* h = hinfo + (size_t)nk * T * w;
+  const int32_t* idx = sv.idx + (size_t)nk * T;
+  const float* amax = sv.amax + (size_t)nk * T;
+  const float Mz = sv.Mz[nk];
+  double L = 0.0, acc = 0.0;
+  for (int i = 0; i < cnt; ++i) {
+    const int t = idx[i];
+    const double e = (double)expf(tw_logit(amax[t], 1.f) - Mz);
+    L += e;
+    double row = 0.0;
+    for (int c = lane; c < w; c += 64) row += (double)g[c] * (double)h[(size_t)t * w + c];
+    acc += e * row;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+  if (lane == 0) {
+    wk.coef[nk] = (float)(1.0 / L);
+    wk.gu[nk] = (float)(acc / L);
+    wk.dss[nk] = 0.f;
+  }
+}
+
+// ---- db of fvta_attn_bwd_u, summed in fp64 straight from the d ct partials of the main kernel.  db is the sum of every
+// row's logit gradient, and with a gradient vector per (n,k) these are N K T terms of order 1 that cancel (exactly so per
+// list without tanh): through the fp32 folds (reduce_q's per-n sums, then the bias block of attn_bwd_params) the partial
+// sums reach ~50 at a thousand lists and leave ~2e-5 of rounding where the result is 0.  Fixed order, no atomics:
+// grid N, 256 threads -> one double per n; then one workgroup adds those in n order.
+__global__ __launch_bounds__(256) void attn_bwd_db_u_kernel(const float* __restrict__ dctp, size_t per_n,
+                                                            double* __restrict__ dbn) {
+  __shared__ double s_acc[256];
+  const float* p = dctp + (size_t)blockIdx.x * per_n;
+  double acc = 0.0;
+  for (size_t i = threadIdx.x; i < per_n; i += 256) acc += (double)p[i];
+  s_acc[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s_acc[threadIdx.x] += s_acc[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) dbn[blockIdx.x] = s_acc[0];
+}
+__global__ __launch_bounds__(256) void attn_bwd_db_u_sum_kernel(const double* __restrict__ dbn, int N, float* __restrict__ db) {
+  __shared__ double s_acc[256];
+  double acc = 0.0;
+  for (int n = threadIdx.x; n < N; n += 256) acc += dbn[n];
+  s_acc[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s_acc[threadIdx.x] += s_acc[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) db[0] += (float)s_acc[0];
+}
+
 struct AttnBwdArgs {
   AttnShape s;
   AttnSaved sv;
   AttnBwdWork wk;
   const float* hinfo;
-  const float* d_h_a;
+  const float* d_h_a;  // [N,w]; PERK kernels: d_u [N,K,w]
   float* d_hinfo;
   int accumulate;
   const float* tscale;  // [N,T] or null (time_warp_att): the inner softmax ran on z = amax * tscale
@@ -138,9 +207,12 @@ struct AttnBwdArgs {
 // SH: the rows are read from the encoders' bf16 shadow (two half-rows per row, addressed through a.table: see
 // attn_fwd_shadow.hip) -- 8 bytes per thread and row instead of 16; the chunk's 2 x rows addresses are fetched after the
 // row sort and kept in LDS.  G == 1, no cosine.
-template <int TPR, int G, int TR, bool COS, bool ACC, bool SH = false>
+// PERK: the incoming gradient is per (n,k) (fvta_attn_bwd_u: d_u [N,K,w] in a.d_h_a) -- launched with gk == 1 only, so a
+// workgroup's one k is k0 and its gv is loaded once, as before.  Compile-time: the h_a instantiations are unchanged.
+template <int TPR, int G, int TR, bool COS, bool ACC, bool SH = false, bool PERK = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_main(AttnBwdArgs a) {
   static_assert(!SH || (G == 1 && !COS && TPR >= 2), "shadow rows: bilinear shapes with one float4 per thread and row");
+  static_assert(!PERK || (!COS && !SH), "per-stream gradient: fp32 rows, simiMatrix 1-3");
   constexpr int RH = 256 / TPR;
   constexpr int RPT = TR / RH;
   constexpr int WPR = TPR >= 64 ? TPR / 64 : 1;  // waves that share a row
@@ -276,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_main(AttnBwdArgs a) {
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const int c4 = cq + g * TPR;
-    gv[g] = ld4b(a.d_h_a + (size_t)n * w + 4 * c4);
+    gv[g] = ld4b(a.d_h_a + (size_t)(PERK ? nk : n) * w + 4 * c4);
     rh4[g] = ld4b(a.sv.vecs + VEC_RH * w + 4 * c4);
     r24[g] = ld4b(a.sv.vecs + VEC_R2 * w + 4 * c4);
     accq[g] = accRh[g] = accR2[g] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -778,6 +850,14 @@ static int attn_bwd_impl(const fvta_attn_desc* d, const float* hinfo, const uint
                          const float* d_h_a, const void* saved, float* d_hinfo, float* d_hq, float* dW, float* db,
                          float* d_tscale, int accumulate, void* workspace, fvta_stream_t stream_);
 
+static int attn_bwd_nt_mode() {
+  static const int nt = [] {
+    const char* e = getenv("FVTA_ATTN_BWD_NT");
+    return e ? atoi(e) : FVTA_ATTN_BWD_NT_DEFAULT;
+  }();
+  return nt;
+}
+
 extern "C" int fvta_attn_bwd_tw(const fvta_attn_desc* d, const float* hinfo, const float* hq, const uint8_t* hmask,
                                 const uint8_t* qmask, const float* W, const float* b, const float* tscale,
                                 const float* d_h_a, const void* saved, float* d_hinfo, float* d_hq, float* dW, float* db,
@@ -838,13 +918,7 @@ static int attn_bwd_impl(const fvta_attn_desc* d, const float* hinfo, const uint
   a.accumulate = accumulate;
   a.tscale = tscale;
   a.hstride = d->hinfo_stride ? (size_t)d->hinfo_stride : (size_t)s.T * s.w;
-  {
-    static const int nt = [] {
-      const char* e = getenv("FVTA_ATTN_BWD_NT");
-      return e ? atoi(e) : FVTA_ATTN_BWD_NT_DEFAULT;
-    }();
-    a.nt = nt;
-  }
+  a.nt = attn_bwd_nt_mode();
   const dim3 grid(s.bsplit, s.N * s.ng);
   const bool prof_it = (size_t)s.N * s.K * s.T >= 65536;  // the context attention, see attn_fwd.hip
   if (prof_it) fvta_prof_begin(FVTA_PROF_ATTN_BWD_MAIN, stream);
@@ -895,5 +969,88 @@ static int attn_bwd_impl(const fvta_attn_desc* d, const float* hinfo, const uint
     hipLaunchKernelGGL(attn_bwd_params_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, stream, s, wk, dW, db);
   }
   FVTA_CHECK_LAUNCH("attn_bwd_reduce");
+  return FVTA_OK;
+}
+
+// ---- fvta_attn_bwd_u: the backward of "fvta_attn_fwd, then fvta_attn_read_u" -- every (n,k) an attention of its own, its
+// gradient d_u[n,k] in place of d_h_a[n].  `saved` does not depend on how the backward groups its work, so this entry runs
+// on a shape of its own with one k per workgroup (gk = 1, ng = K: a grouped workgroup loads ONE gradient vector) and
+// bsplit as attn_shape() chose it; the slabs of its workspace are laid out for that shape.
+static AttnShape attn_shape_u(const fvta_attn_desc* d, bool use_mask) {
+  AttnShape s = attn_shape(d, use_mask);
+  s.gk = 1;
+  s.ng = s.K;
+  return s;
+}
+
+static int attn_bwd_u_check(const fvta_attn_desc* d) {
+  if (int e = fvta_attn_check_desc(d)) return e;
+  FVTA_CHECK_ARG(d->simi != 4, "attn_bwd_u: simiMatrix 4 is not supported (simiMatrix 1-3)");
+  FVTA_CHECK_ARG(d->hinfo_stride == 0, "attn_bwd_u: hinfo_stride=%lld is not supported (dense hinfo only)", (long long)d->hinfo_stride);
+  FVTA_CHECK_ARG((long long)d->N * d->K <= 65535, "attn_bwd_u: N*K=%lld exceeds 65535 workgroup rows", (long long)d->N * d->K);
+  return FVTA_OK;
+}
+
+// the backward's workspace for that shape, then one double per n (attn_bwd_db_u_kernel)
+static size_t attn_bwd_u_dbn_offset(const AttnBwdWork& wk) { return fvta_align_up(wk.bytes, 256); }
+
+extern "C" size_t fvta_attn_bwd_u_workspace_bytes(const fvta_attn_desc* d) {
+  if (attn_bwd_u_check(d)) return 0;
+  return attn_bwd_u_dbn_offset(bwd_work_view(attn_shape_u(d, true), nullptr)) + (size_t)d->N * sizeof(double);
+}
+
+extern "C" int fvta_attn_bwd_u(const fvta_attn_desc* d, const float* hinfo, const float* hq, const uint8_t* hmask,
+                               const uint8_t* qmask, const float* W, const float* b, const float* d_u, const void* saved,
+                               float* d_hinfo, float* d_hq, float* dW, float* db, int accumulate, void* workspace,
+                               fvta_stream_t stream_) {
+  if (int e = attn_bwd_u_check(d)) return e;
+  FVTA_CHECK_ARG(accumulate == 0 || accumulate == 1, "attn_bwd_u: accumulate=%d (0: overwrite, 1: add)", accumulate);
+  FVTA_CHECK_ARG(hinfo && hq && d_u && saved && d_hinfo && d_hq && dW && db && workspace, "attn_bwd_u: null pointer");
+  hipStream_t stream = (hipStream_t)stream_;
+  const bool use_mask = hmask && qmask;
+  const AttnShape s = attn_shape_u(d, use_mask);
+  AttnSaved sv = attn_saved_view(s, const_cast<void*>(saved));
+  AttnBwdWork wk = bwd_work_view(s, workspace);
+  const int RH = bwd_rh(s.W4);
+  FVTA_CHECK_HIP(hipMemsetAsync(wk.slabs, 0, wk.slab_bytes, stream));
+  if (accumulate == 0 && use_mask)  // every valid row is written by the main kernel (a fully masked stream: all of its rows)
+    hipLaunchKernelGGL(attn_zero_masked_rows_kernel, dim3((unsigned)(((size_t)s.N * s.K * s.T + 3) / 4)), dim3(256), 0, stream, s,
+                       hmask, d_hinfo);
+  hipLaunchKernelGGL(attn_bwd_prep_u_kernel, dim3((s.N * s.K + 3) / 4), dim3(256), 0, stream, s, sv, wk, hinfo, d_u);
+  AttnBwdArgs a;
+  a.s = s;
+  a.sv = sv;
+  a.wk = wk;
+  a.hinfo = hinfo;
+  a.table = nullptr;
+  a.d_h_a = d_u;
+  a.d_hinfo = d_hinfo;
+  a.accumulate = accumulate;
+  a.tscale = nullptr;
+  a.hstride = (size_t)s.T * s.w;
+  a.nt = attn_bwd_nt_mode();
+  const dim3 grid(s.bsplit, s.N * s.ng);
+  switch (s.w) {
+#define FVTA_BWD_U_LAUNCH(TPR, G, TR)                                                                                       \
+  do {                                                                                                                    \
+    if (accumulate == 1) hipLaunchKernelGGL((attn_bwd_main<TPR, G, TR, false, true, false, true>), grid, dim3(256), 0, stream, a);  \
+    else hipLaunchKernelGGL((attn_bwd_main<TPR, G, TR, false, false, false, true>), grid, dim3(256), 0, stream, a);        \
+  } while (0)
+    case 64: FVTA_BWD_U_LAUNCH(16, 1, 32); break;
+    case 128: FVTA_BWD_U_LAUNCH(32, 1, 32); break;
+    case 256: FVTA_BWD_U_LAUNCH(64, 1, 32); break;
+    case 512: FVTA_BWD_U_LAUNCH(128, 1, 32); break;
+    case 1024: FVTA_BWD_U_LAUNCH(256, 1, 32); break;
+    case 2048: FVTA_BWD_U_LAUNCH(256, 2, 8); break;  // (16-row tiles: 24 bytes of scratch per lane, as the h_a path has)
+#undef FVTA_BWD_U_LAUNCH
+  }
+  FVTA_CHECK_LAUNCH("attn_bwd_main (per-stream gradient)");
+  hipLaunchKernelGGL(attn_bwd_reduce_q_kernel, dim3(s.N, (s.w + 255) / 256, attn_bwd_jz(s)), dim3(256), 0, stream, s, sv, wk, RH, hq,
+                     d_hq, accumulate);
+  hipLaunchKernelGGL(attn_bwd_params_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, stream, s, wk, dW, (float*)nullptr);  // (db: below)
+  double* dbn = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + attn_bwd_u_dbn_offset(wk));
+  hipLaunchKernelGGL(attn_bwd_db_u_kernel, dim3(s.N), dim3(256), 0, stream, wk.dctp, (size_t)s.ng * s.bsplit * RH * s.JP, dbn);
+  hipLaunchKernelGGL(attn_bwd_db_u_sum_kernel, dim3(1), dim3(256), 0, stream, dbn, s.N, db);
+  FVTA_CHECK_LAUNCH("attn_bwd_u reduce");
   return FVTA_OK;
 }

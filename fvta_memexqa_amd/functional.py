@@ -10,22 +10,22 @@
                  time_warp_att=False, C=None, bidirect=False, scope=None)            model_v2.py:210-298
     attention_keeprank1(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None,
                         bidirect=False, scope=None) -> h_a [N,M,w]                   model.py:247-314
+      (attention_raw / attention_keeprank1_raw: the same with explicit W, b instead of the variable store)
     attention_tgif(hinfo, lq, hinfo_mask=None, wd=None, mlp_dim=512, scope=None)     model.py:210-244
 
 Tensors are torch CUDA tensors; every op is one call into libfvta_hip.so, wrapped in a `torch.autograd.Function`
 (autograd.py): a tensor that requires grad gets its gradient through the library's backward kernels, and when nothing
-requires grad the same forward kernels run and nothing is kept.  `attention_keeprank1` alone is forward only.  The
-variable store keeps plain tensors; `variables[name].requires_grad_()` makes one a leaf that receives its gradient.
-On the focal attentions' `h_a` path two deviations of the model's backward kernels carry over: an
-exact tie in the max over the question sends its gradient to the FIRST arg-max (TensorFlow splits it), and a fully
-masked (n,k) row list sends no gradient into its logits.  Where the reference creates TF variables (`linear`'s W / b, the
+requires grad the same forward kernels run and nothing is kept.  The variable store keeps plain tensors;
+`variables[name].requires_grad_()` makes one a leaf that receives its gradient.
+On the focal attentions' `h_a` path, and on `attention_keeprank1`'s per-(n,m) vectors, two deviations of the model's
+backward kernels carry over: an exact tie in the max over the question sends its gradient to the
+FIRST arg-max (TensorFlow splits it), and a fully masked (n,k) row list sends no gradient into its logits.  Where the reference creates TF variables (`linear`'s W / b, the
 `att_logits` linear inside the attentions) the variable lives in a module-level store under the same scoped name
 (`variable_scope("attention")` + `scope="all"` -> "attention/all/att_logits/W"), initialised like the reference
 (truncated normal 0.1 / zeros) and reused on the next call, which is what `tf.get_variable` under reuse does.
 `wd` appends the l2 terms to `losses` like `add_wd` (model_v2.py:347-354).
 """
 import contextlib
-import ctypes
 import zlib
 
 import torch
@@ -242,41 +242,51 @@ def attention(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, a
     return h_a, a
 
 
-@torch.no_grad()
-def attention_keeprank1(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, bidirect=False, scope=None):
-    """model.py:247-314: hinfo [N,M,...,w] -> h_a [N,M,w] ([N,M,2w] with `bidirect`), each album attended on its own (softsel over the rows of
-    (n, m) with the max-over-question logits; no softmax over m).  That is the inner stage of attention_3d with K = M:
-    one fvta_attn_fwd, then the per-(n,k) result is read back out of the saved state.  model.py's feature order for
-    simiMatrix 2 is [(h-q)^2, h*q] (feat_order 1); no tanh on the logits.
-    FORWARD ONLY (runs under torch.no_grad): the per-(n,k) read-out has no backward kernel, so the result carries no
-    grad_fn even when an input requires grad (the other helpers of this module are differentiable)."""
+def attention_keeprank1_raw(hinfo, hq, W, b, hinfo_mask=None, hq_mask=None, simiMatrix=1, bidirect=False):
+    """attention_keeprank1 with explicit weights: hinfo [N,M,...,w], hq [N,JQ,w], W [F*w, 1] (any shape with F*w
+    elements), b [1] -> h_a [N,M,w] ([N,M,2w] with `bidirect`).  w is zero padded to a kernel width, W block-wise with it;
+    the result is differentiable (fvta_attn_bwd_u; the bidirect half through fvta_attn_cube_bwd).  With a gradient wanted
+    N * M is at most 65535, and backward() allocates a workspace of one dQs slab set per (n,m) -- N M bsplit
+    (256 / min(w/4, 256)) 32 ceil(JQ/32) w floats, 136 MB at N M = 1040 and w = 64: wide batches of narrow rows cost memory."""
     if simiMatrix not in (1, 2, 3):
         raise ValueError("similarity matrix not implemented")              # model.py:283-285 (sys.exit there)
     hinfo, hq = _f32(hinfo), _f32(hq)
     N, M, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
     h = hinfo.reshape(N, M, -1, w)
-    V, JQ = h.shape[2], hq.shape[1]
+    V = h.shape[2]
     wp = next((c for c in SUPPORTED_W if w <= c), None)
     if wp is None:
         raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
     F = {1: 3, 2: 2, 3: 4}[simiMatrix]
-    with variable_scope(scope or "attention_2vector"):
-        wn, bn = _name("att_logits", "W"), _name("att_logits", "b")
-        Wv = get_variable(wn, (F * w, 1))
-        b = get_variable(bn, (1,), init="zeros")
-        W = _pad_channels(Wv.reshape(F, w), wp).reshape(-1).contiguous()
-        _add_wd([wn, bn], wd)
-    op = ops.FocalAttention(N, M, V, JQ, wp, simiMatrix, False, feat_order=1)
+    W = _pad_channels(_f32(W).reshape(F, w), wp).reshape(-1).contiguous()
+    ops.require_gpu()
     both = hinfo_mask is not None and hq_mask is not None
     hm = ops.as_mask_u8(hinfo_mask.reshape(N, M, V)) if both else None
     qm = ops.as_mask_u8(hq_mask) if both else None
-    _, a = op.forward(_pad_channels(h, wp), _pad_channels(hq, wp), hm, qm, W, b, want_logits=bool(bidirect))
-    u = torch.empty(N, M, wp, dtype=torch.float32, device=h.device)
-    check(op.lib.fvta_attn_read_u(ctypes.byref(op.desc), ptr(op.saved), ptr(u), stream_ptr()), "fvta_attn_read_u")
+    u, a = autograd.keeprank1(_pad_channels(h, wp), _pad_channels(hq, wp), W, _f32(b), hm, qm, simiMatrix,
+                              want_logits=bool(bidirect))
     u = u[..., :w].contiguous()
     if bidirect:                                                            # model.py:297-307 -> [N,M,2w]
         u = torch.cat([u, _bidirect_q_a(a, hq, (N, M))], 2)
     return u
+
+
+def attention_keeprank1(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, bidirect=False, scope=None):
+    """model.py:247-314: hinfo [N,M,...,w] -> h_a [N,M,w] ([N,M,2w] with `bidirect`), each album attended on its own (softsel over the rows of
+    (n, m) with the max-over-question logits; no softmax over m).  That is the inner stage of attention_3d with K = M:
+    one fvta_attn_fwd, then the per-(n,k) result is read back out of the saved state; its gradient runs through
+    fvta_attn_bwd_u, every (n,m) an attention of its own.  model.py's feature order for simiMatrix 2 is
+    [(h-q)^2, h*q] (feat_order 1); no tanh on the logits."""
+    if simiMatrix not in (1, 2, 3):
+        raise ValueError("similarity matrix not implemented")              # model.py:283-285 (sys.exit there)
+    w = hinfo.shape[-1]
+    F = {1: 3, 2: 2, 3: 4}[simiMatrix]
+    with variable_scope(scope or "attention_2vector"):
+        wn, bn = _name("att_logits", "W"), _name("att_logits", "b")
+        W = get_variable(wn, (F * w, 1))
+        b = get_variable(bn, (1,), init="zeros")
+        _add_wd([wn, bn], wd)
+    return attention_keeprank1_raw(hinfo, hq, W, b, hinfo_mask, hq_mask, simiMatrix, bidirect)
 
 
 def attention_tgif(hinfo, lq, hinfo_mask=None, wd=None, mlp_dim=512, scope=None):

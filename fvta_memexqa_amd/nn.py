@@ -126,6 +126,23 @@ class QuestionAttention(_AttLogits):
         return h_a, a
 
 
+class ChoicesAttention(_AttLogits):
+    """attention_keeprank1 (model.py:247-314), what `use_choices_att` runs (:966-968): hinfo [N,M,...,w], hq [N,JQ,w] ->
+    h_a [N,M,w], every (n,m) attended on its own; with bidirect [N,M,2w] = concat([h_a, q_a]).  model.py's feature order
+    ([(h-q)^2, h*q] under simiMatrix 2), simiMatrix 1-3, no tanh on the logits.  Training needs N * M <= 65535; the
+    backward's workspace is sized in functional.attention_keeprank1_raw's docstring."""
+
+    def __init__(self, w, simiMatrix=1, bidirect=False, seed=None):
+        if simiMatrix not in (1, 2, 3):
+            raise ValueError("similarity matrix not implemented")          # model.py:283-285
+        super().__init__(w, simiMatrix, False, seed)
+        self.bidirect = bool(bidirect)
+
+    def forward(self, hinfo, hq, hinfo_mask=None, hq_mask=None):
+        W, b = self._wb()
+        return functional.attention_keeprank1_raw(hinfo, hq, W, b, hinfo_mask, hq_mask, self.simiMatrix, self.bidirect)
+
+
 class AnswerScorer(_Module):
     """model_v2.py:1053-1096: gq, g1 [N,w], gch [N,C,w], y [N,C] -> (loss, logits [N,C], yp [N,C]); `choicelogits/W`
     [5w, 1] (7w with use_eu_output) truncated normal(0.1), `choicelogits/b` [1] zeros.  Only the loss is differentiable."""

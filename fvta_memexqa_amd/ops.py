@@ -261,6 +261,25 @@ class FocalAttention:
                                         ptr(dW), ptr(db), ptr(d_tscale), int(accumulate), ptr(self.work), stream_ptr()),
               "fvta_attn_bwd")
 
+    def backward_u(self, hinfo, hq, hmask, qmask, W, b, d_u, d_hinfo, d_hq, dW, db, accumulate):
+        """the backward of forward() + fvta_attn_read_u from d_u [N,K,w]: every (n,k) an attention of its own
+        (fvta_attn_bwd_u; simiMatrix 1-3, accumulate 0 | 1, N * K <= 65535).  Its workspace is sized by its own query and
+        allocated on first use: one dQs slab set per (n,k), 136 MB at N K = 1040 and w = 64."""
+        if getattr(self, "work_u", None) is None:
+            nb = self.lib.fvta_attn_bwd_u_workspace_bytes(ctypes.byref(self.desc))
+            if nb == 0:
+                raise _lib.FvtaError("attention: " + self.lib.fvta_last_error().decode())
+            self.work_u = _bytes(nb, self.dev)
+        check(self.lib.fvta_attn_bwd_u(ctypes.byref(self.desc), ptr(hinfo), ptr(hq), ptr(hmask), ptr(qmask), ptr(W), ptr(b),
+                                       ptr(_f32c(d_u)), ptr(self.saved), ptr(d_hinfo), ptr(d_hq), ptr(dW), ptr(db),
+                                       int(accumulate), ptr(self.work_u), stream_ptr()), "fvta_attn_bwd_u")
+
+    def read_u(self):
+        """u [N,K,w]: the per-(n,k) softsel result the last forward() left in `saved` (fvta_attn_read_u)"""
+        u = torch.empty(self.N, self.K, self.w, dtype=torch.float32, device=self.dev)
+        check(self.lib.fvta_attn_read_u(ctypes.byref(self.desc), ptr(self.saved), ptr(u), stream_ptr()), "fvta_attn_read_u")
+        return u
+
 
 def linear_fwd(x, W, b, y, M, din, dout, add_tanh=False, blk=None):
     """y [M,dout] = x [M,din] W [din,dout] + b (+ tanh); blk = (rows_per_blk, blk_stride): x rows in blocks"""

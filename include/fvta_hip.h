@@ -510,6 +510,21 @@ int fvta_softsel_bwd(const float* target, const float* logits, const float* d_ou
 /* attention_keeprank1 (model.py:247-314) = the per-(n,k) inner softsel of attention_3d without the softmax over k:
  * after fvta_attn_fwd(desc with K = M) this copies that result, u[N,K,w], out of the saved state. */
 int fvta_attn_read_u(const fvta_attn_desc* d, const void* saved, float* u_out, fvta_stream_t stream);
+/* Backward of "fvta_attn_fwd, then fvta_attn_read_u" given d_u [N,K,w]: every (n,k) is an attention of its own (no softmax
+ * over k), d_hq is summed over k.  Arguments as fvta_attn_bwd; `saved` is what fvta_attn_fwd left, `workspace` has
+ * fvta_attn_bwd_u_workspace_bytes (its own size: one k per workgroup at every shape).  accumulate = 0: d_hinfo and d_hq
+ * are overwritten (masked rows of d_hinfo get zeros); 1: both are accumulated into; dW, db are always accumulated into.
+ * simiMatrix 1-3, both feat_orders, add_tanh, every width, both masks or neither; FVTA_ERR_INVALID_ARG for simiMatrix 4,
+ * a non-zero hinfo_stride, N*K > 65535 and any other accumulate.  The deviations of fvta_attn_bwd carry over (first
+ * arg-max takes a tie; a fully masked (n,k) passes nothing into its logits).  Fixed summation order, no atomics; db --
+ * N K T terms that largely cancel -- is summed in fp64 and rounded once, and the softmax denominators and g.u are recomputed
+ * from the rows of hinfo (one more read of the row lists) so that they match the weights the row pass uses.
+ * The workspace holds one dQs slab set per (n,k): N K bsplit (256 / min(w/4, 256)) 32 ceil(JQ/32) w floats, cleared on
+ * every call -- 136 MB at N K = 1040, w = 64. */
+size_t fvta_attn_bwd_u_workspace_bytes(const fvta_attn_desc* d);
+int fvta_attn_bwd_u(const fvta_attn_desc* d, const float* hinfo, const float* hq, const uint8_t* hmask, const uint8_t* qmask,
+                    const float* W, const float* b, const float* d_u, const void* saved, float* d_hinfo, float* d_hq,
+                    float* dW, float* db, int accumulate, void* workspace, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Test hooks (not part of the reference surface): the MFMA tile engines the

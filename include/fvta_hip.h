@@ -175,7 +175,9 @@ size_t fvta_lstm_workspace_bytes(const fvta_lstm_desc* d);
 
 /* Length-sorted schedule for one call (device side, no host sync).
  * len [B] int32 (mask row sums, model_v2.py:667-678), seq_J [B] padded length
- * of each sequence, x_off/out_off [B] element offsets, out_ld row stride. */
+ * of each sequence, x_off/out_off [B] element offsets, out_ld row stride.
+ * Contract: 0 <= len[b] <= seq_J[b] <= J.  The plan clamps len to [0, J] only: a sequence with seq_J[b] < len[b] would
+ * run (and write rows) past its own seq_J rows, into whatever the arenas hold behind them. */
 int fvta_lstm_plan(const fvta_lstm_desc* d, const int32_t* len, const int32_t* seq_J, const int64_t* x_off,
                    const int64_t* out_off, int64_t out_ld, void* plan, fvta_stream_t stream);
 

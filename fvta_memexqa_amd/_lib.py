@@ -45,6 +45,18 @@ class ScorerDesc(Structure):
     _fields_ = [(n, c_int32) for n in ("N", "C", "w", "use_eu_output", "add_tanh", "xent_grad")]
 
 
+class GuardDesc(Structure):
+    _fields_ = [("grad_scale", c_float), ("clip_value", c_float), ("clip_norm", c_float), ("skip_nonfinite", c_int32),
+                ("adam", c_int32), ("lr", c_float), ("beta1", c_float), ("beta2", c_float)]
+
+
+class GuardCtl(Structure):
+    """the device-resident control block of the gradient guard (fvta_guard_ctl); read back with ops.guard_ctl_read"""
+    _fields_ = [("grad_scale", c_float), ("clip_value", c_float), ("factor", c_float), ("lr_t", c_float), ("apply", c_int32),
+                ("maxabs", c_float), ("norm", ctypes.c_double), ("nonfinite", c_int64), ("applied", c_int64),
+                ("skipped", c_int64)]
+
+
 P = c_void_p
 _SIGS = {
     "fvta_version": (c_int, []),
@@ -92,6 +104,10 @@ _SIGS = {
     "fvta_adadelta_step": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, P]),
     "fvta_adam_step": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float, P]),
     "fvta_weight_decay": (c_int, [P, P, c_int64, c_float, P, P]),
+    "fvta_grad_guard_workspace_bytes": (c_size_t, [c_int64]),
+    "fvta_grad_guard": (c_int, [POINTER(GuardDesc), P, c_int64, P, P, P]),
+    "fvta_adadelta_step_guarded": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, P, P]),
+    "fvta_adam_step_guarded": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, P, P]),
     "fvta_probe_hbm_read": (c_int, [P, ctypes.c_size_t, P, P]),
     "fvta_probe_spin": (c_int, [c_int64, P]),
     "fvta_probe_hbm_mix": (c_int, [P, ctypes.c_size_t, c_int32, c_int32, P]),
@@ -157,7 +173,7 @@ def load():
         fn.restype = res
         fn.argtypes = args
     # the descriptor structs are declared twice (include/fvta_hip.h and above): refuse a library whose layout differs
-    for which, cls in enumerate((AttnDesc, LstmDesc, ScorerDesc, TimewarpDesc, EmbedDesc, ImgTransDesc)):
+    for which, cls in enumerate((AttnDesc, LstmDesc, ScorerDesc, TimewarpDesc, EmbedDesc, ImgTransDesc, GuardDesc, GuardCtl)):
         have, want = ctypes.sizeof(cls), lib.fvta_abi_struct_bytes(which)
         if have != want:
             raise FvtaError("%s is %d bytes here but %d in %s: rebuild the library (descriptor layouts differ)"

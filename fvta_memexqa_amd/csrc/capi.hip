@@ -29,6 +29,8 @@ extern "C" int64_t fvta_abi_struct_bytes(int32_t which) {
     case 3: return (int64_t)sizeof(fvta_timewarp_desc);
     case 4: return (int64_t)sizeof(fvta_embed_desc);
     case 5: return (int64_t)sizeof(fvta_imgtrans_desc);
+    case 6: return (int64_t)sizeof(fvta_guard_desc);
+    case 7: return (int64_t)sizeof(fvta_guard_ctl);
     default: return -1;
   }
 }

@@ -395,6 +395,53 @@ def adam_step(var, grad, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-8, grad_sca
                                      grad_scale, stream_ptr()), "fvta_adam_step")
 
 
+# ------------------------------------------------------------ gradient guard
+def guard_ctl_new(dev, applied=0, skipped=0):
+    """A zeroed control block (fvta_guard_ctl) on `dev` with its running counters preset; a uint8 tensor."""
+    host = _lib.GuardCtl(applied=int(applied), skipped=int(skipped))
+    return torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(dev)
+
+
+def guard_ctl_read(ctl):
+    """The control block as a dict -- ONE device-to-host copy, which waits for the stream."""
+    host = _lib.GuardCtl.from_buffer_copy(ctl.cpu().numpy().tobytes())
+    return {name: getattr(host, name) for name, _ in _lib.GuardCtl._fields_}
+
+
+def grad_guard_workspace(n, dev):
+    nbytes = _lib.load().fvta_grad_guard_workspace_bytes(int(n))
+    if nbytes == 0:
+        check(-1, "fvta_grad_guard_workspace_bytes")
+    return _bytes(nbytes, dev)
+
+
+def grad_guard(grad, ctl, workspace=None, grad_scale=1.0, clip_value=0.0, clip_norm=0.0, skip_nonfinite=False, adam=None):
+    """Statistics of the flat gradient and the decision of this step into the device control block `ctl`
+    (guard_ctl_new), asynchronously on the current stream; follow it with adadelta_step_guarded / adam_step_guarded.
+    grad: 1-D float32, any 4-byte aligned start (a slice is fine).  adam = (lr, beta1, beta2) also computes lr_t."""
+    assert grad.is_cuda and grad.dtype == torch.float32 and grad.is_contiguous(), "expected a contiguous float32 CUDA tensor"
+    assert ctl.is_cuda and ctl.dtype == torch.uint8 and ctl.numel() == ctypes.sizeof(_lib.GuardCtl)
+    if workspace is None:
+        workspace = grad_guard_workspace(grad.numel(), grad.device)
+    lr, b1, b2 = adam if adam is not None else (0.0, 0.0, 0.0)
+    d = _lib.GuardDesc(float(grad_scale), float(clip_value), float(clip_norm), int(bool(skip_nonfinite)),
+                       int(adam is not None), float(lr), float(b1), float(b2))
+    check(_lib.load().fvta_grad_guard(ctypes.byref(d), ptr(grad), grad.numel(), ptr(workspace), ptr(ctl), stream_ptr()),
+          "fvta_grad_guard")
+    return ctl
+
+
+def adadelta_step_guarded(var, grad, accum, accum_update, ctl, lr, rho=0.95, eps=1e-8):
+    check(_lib.load().fvta_adadelta_step_guarded(ptr(var), ptr(grad), ptr(accum), ptr(accum_update), var.numel(), lr, rho,
+                                                 eps, ptr(ctl), stream_ptr()), "fvta_adadelta_step_guarded")
+
+
+def adam_step_guarded(var, grad, m, v, ctl, beta1=0.9, beta2=0.999, eps=1e-8):
+    """lr, the step count and the bias correction come from ctl (grad_guard(..., adam=(lr, beta1, beta2)))"""
+    check(_lib.load().fvta_adam_step_guarded(ptr(var), ptr(grad), ptr(m), ptr(v), var.numel(), beta1, beta2, eps,
+                                             ptr(ctl), stream_ptr()), "fvta_adam_step_guarded")
+
+
 def weight_decay(var, grad, coef, loss):
     """add_wd (model_v2.py:347-354) for one variable: loss += coef/2 * sum(var^2), grad += coef * var (either may be None)."""
     check(_lib.load().fvta_weight_decay(ptr(var), ptr(grad) if grad is not None else None, var.numel(), float(coef),

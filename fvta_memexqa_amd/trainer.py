@@ -21,6 +21,13 @@ class AdadeltaOptimizer:
             self.state = (torch.zeros_like(params.flat), torch.zeros_like(params.flat))
         ops.adadelta_step(params.flat, params.grad, self.state[0], self.state[1], self.lr, self.rho, self.eps, grad_scale)
 
+    guard_adam = None                       # ops.grad_guard(adam=): no bias correction to compute
+
+    def apply_guarded(self, params, ctl):
+        if self.state is None:
+            self.state = (torch.zeros_like(params.flat), torch.zeros_like(params.flat))
+        ops.adadelta_step_guarded(params.flat, params.grad, self.state[0], self.state[1], ctl, self.lr, self.rho, self.eps)
+
 
 class AdamOptimizer:
     """tf.train.AdamOptimizer(init_lr), the commented-out alternative of trainer.py:17."""
@@ -38,11 +45,53 @@ class AdamOptimizer:
         ops.adam_step(params.flat, params.grad, self.state[0], self.state[1], self.t, self.lr, self.b1, self.b2, self.eps,
                       grad_scale)
 
+    @property
+    def guard_adam(self):
+        return (self.lr, self.b1, self.b2)
+
+    def apply_guarded(self, params, ctl):
+        """the step count lives in ctl (`applied`): self.t is brought up to date by Trainer.guard_stats / save"""
+        if self.state is None:
+            self.state = (torch.zeros_like(params.flat), torch.zeros_like(params.flat))
+        ops.adam_step_guarded(params.flat, params.grad, self.state[0], self.state[1], ctl, self.b1, self.b2, self.eps)
+
+
+def _threshold(config_get, key):
+    """a clipping threshold of the config: a finite number >= 0, 0 / None / False = off"""
+    v = config_get(key, 0.0)
+    if v is None or v is False:
+        return 0.0
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be a number >= 0 (0 = off), got %r" % (key, v))
+    if isinstance(v, bool) or not (0.0 <= f < float("inf")) or f > 3.4028234e38:
+        raise ValueError("%s must be a finite float32 number >= 0 (0 = off), got %r" % (key, v))
+    return f
+
 
 class Trainer:
+    """Gradient guard (off by default): `clip_gradient_value` clamps every element of the scaled gradient
+    (the reference's commented-out tf.clip_by_value, trainer.py:24-25, which it calls clip_gradient_norm),
+    `clip_global_norm` is tf.clip_by_global_norm over the whole flat gradient, `skip_nonfinite` leaves parameters and
+    optimiser slots untouched when the gradient holds a NaN / inf.  Decided on the device: the step stays free of host
+    synchronisation.  guard_stats() is the only call that waits for the device."""
+
     def __init__(self, model, config):
         self.config = config
         self.model = model
+        get = config.get if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
+        self.clip_value = _threshold(get, "clip_gradient_value")
+        self.clip_norm = _threshold(get, "clip_global_norm")
+        skip = get("skip_nonfinite", False)
+        if skip is None:
+            skip = False
+        if not (isinstance(skip, (bool, np.bool_)) or (isinstance(skip, int) and skip in (0, 1))):
+            raise ValueError("skip_nonfinite must be a bool, got %r" % (skip,))
+        self.skip_nonfinite = bool(skip)
+        self.guard_on = self.clip_value > 0 or self.clip_norm > 0 or self.skip_nonfinite
+        self.guard_ctl, self._guard_ws = None, None      # device control block / workspace: made at the first guarded step
+        self._guard_counts = None                        # (applied, skipped) a restore brought back, until guard_ctl exists
         name = getattr(config, "optimizer", "adadelta") if not isinstance(config, dict) else config.get("optimizer", "adadelta")
         lr = getattr(config, "init_lr", 0.5) if not isinstance(config, dict) else config.get("init_lr", 0.5)
         self.opt = AdamOptimizer(lr) if name == "adam" else AdadeltaOptimizer(lr)   # trainer.py:16-17
@@ -84,12 +133,46 @@ class Trainer:
         m.zero_grad()
         m.forward(layout)
         m.backward(layout, loss_scale=1.0, need_dx=self.need_dx)
+        self.apply_update()
+        return m.loss
+
+    def apply_update(self):
+        """The tail of a step, for a gradient already in model.params.grad: all-reduce, (guarded) optimiser step,
+        global_step += 1 -- which numbers batches, so a skipped step counts too.  No host synchronisation."""
+        m = self.model
         # one flat gradient bucket; its early part (scorer / attention / photo cell) may already be on the wire
         early, m.early_work = getattr(m, "early_work", None), None
         scale = dist.allreduce_grads(m.params.grad, getattr(m.params, "early_numel", 0), early)
-        self.opt.apply(m.params, scale)
+        if self.guard_on:
+            # every rank holds the same reduced buffer and the statistics have one fixed summation order: all ranks
+            # take the same decision without another collective
+            if self.guard_ctl is None:
+                applied, skipped = self._guard_counts or (getattr(self.opt, "t", 0), 0)
+                self.guard_ctl = ops.guard_ctl_new(m.params.grad.device, applied, skipped)
+                self._guard_ws = ops.grad_guard_workspace(m.params.grad.numel(), m.params.grad.device)
+            ops.grad_guard(m.params.grad, self.guard_ctl, self._guard_ws, scale, self.clip_value, self.clip_norm,
+                           self.skip_nonfinite, self.opt.guard_adam)
+            self.opt.apply_guarded(m.params, self.guard_ctl)
+        else:
+            self.opt.apply(m.params, scale)
         m.global_step += 1
-        return m.loss
+
+    def guard_stats(self):
+        """What the guard saw at the last step and its running counters: dict(norm, maxabs, nonfinite, factor, applied,
+        skipped) of the scaled, value-clipped gradient.  ONE device-to-host copy: the only call here that waits for the
+        device (Trainer.guard_ctl is the device tensor itself).  Before the first guarded step: the counters only."""
+        if self.guard_ctl is None:
+            applied, skipped = self._guard_counts or (getattr(self.opt, "t", 0), 0)
+            return dict(norm=0.0, maxabs=0.0, nonfinite=0, factor=1.0, applied=int(applied), skipped=int(skipped))
+        c = ops.guard_ctl_read(self.guard_ctl)
+        if hasattr(self.opt, "t"):
+            self.opt.t = int(c["applied"])      # Adam's step count is the number of APPLIED steps
+        return {k: c[k] for k in ("norm", "maxabs", "nonfinite", "factor", "applied", "skipped")}
+
+    def _guard_set_counts(self, applied, skipped):
+        self._guard_counts = (int(applied), int(skipped))
+        if self.guard_ctl is not None:
+            self.guard_ctl.copy_(ops.guard_ctl_new(self.guard_ctl.device, applied, skipped))
 
     def step(self, sess, batch, get_summary=False):
         """trainer.py:30-40: batch = (batchIdx, batch_data); returns (loss, summary, train_op)."""
@@ -113,6 +196,9 @@ class Trainer:
             for slot, flat in zip(self.opt.SLOTS, self.opt.state):
                 for k, v in m.get_weights(flat=flat).items():
                     out["%s/%s/%s:0" % (m.scope, k, slot)] = v
+        if self.guard_on:                       # (waits for the device; brings Adam's t up to `applied`)
+            st = self.guard_stats()
+            out["applied_steps"], out["skipped_steps"] = np.int64(st["applied"]), np.int64(st["skipped"])
         if hasattr(self.opt, "t"):
             out["step_count"] = np.int64(self.opt.t)
         out["dropout_calls"] = np.array(int(getattr(m, "_dropout_calls", 0)))   # the dropout mask sequence continues on resume
@@ -150,6 +236,10 @@ class Trainer:
                 self.opt.state = state
             if "step_count" in z.files and hasattr(self.opt, "t"):
                 self.opt.t = int(z["step_count"])
+            # the guard's counters; a file without them (an unguarded run's) restores as before: Adam goes on from
+            # step_count, the skipped count starts at 0
+            applied = int(z["applied_steps"]) if "applied_steps" in z.files else getattr(self.opt, "t", 0)
+            self._guard_set_counts(applied, int(z["skipped_steps"]) if "skipped_steps" in z.files else 0)
             if "dropout_calls" in z.files:
                 m._dropout_calls = int(z["dropout_calls"])
         return True
@@ -194,4 +284,5 @@ class Trainer:
                         raise ValueError("checkpoint %s: beta1_power %g is not a power of beta1 = %g" %
                                          (path, float(b1p), self.opt.b1))
                     self.opt.t = e - 1
+                self._guard_set_counts(self.opt.t, 0)
         return found == len(self.opt.SLOTS)

@@ -45,7 +45,8 @@ typedef void* fvta_stream_t; /* hipStream_t */
 int fvta_version(void);
 const char* fvta_last_error(void);
 /* sizeof of a descriptor struct as the library was compiled: which = 0 fvta_attn_desc, 1 fvta_lstm_desc,
- * 2 fvta_scorer_desc, 3 fvta_timewarp_desc, 4 fvta_embed_desc, 5 fvta_imgtrans_desc; -1 otherwise.  A binding compares
+ * 2 fvta_scorer_desc, 3 fvta_timewarp_desc, 4 fvta_embed_desc, 5 fvta_imgtrans_desc, 6 fvta_guard_desc,
+ * 7 fvta_guard_ctl; -1 otherwise.  A binding compares
  * its own layout with it when it loads the library (fvta_memexqa_amd/_lib.py does). */
 int64_t fvta_abi_struct_bytes(int32_t which);
 
@@ -414,6 +415,51 @@ int fvta_adam_step(float* var, const float* grad, float* m, float* v, int64_t n,
  * of add_wd calls that cover the variable (the shared char-CNN filter is covered once per conv1d call,
  * model_v2.py:564-571).  Fixed summation order. */
 int fvta_weight_decay(const float* var, float* grad, int64_t n, float coef, float* loss, fvta_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
+ * Gradient guard: clipping and a skip-on-overflow step with no host synchronisation.  The reference's trainer carries
+ * the intent only (trainer.py:24-25, a commented-out tf.clip_by_value over every gradient).  Over the flat gradient:
+ *   g'  = grad[i] * grad_scale
+ *   g'' = clip_value > 0 ? clamp(g', -clip_value, clip_value) : g'      (a NaN stays a NaN)
+ *   norm   = sqrt(sum g''^2)           maxabs = largest finite |g''|
+ *   nonfinite = how many raw grad[i] are NaN or +-inf (exact)
+ *   factor = clip_norm > 0 ? clip_norm / max(norm, clip_norm) : 1       (tf.clip_by_global_norm; exactly 1.0f below
+ *            the threshold; a NaN norm leaves factor = 1, the NaN elements themselves carry on)
+ *   apply  = !(skip_nonfinite && (nonfinite > 0 || !isfinite(norm)));   apply ? ++applied : ++skipped
+ * fvta_grad_guard makes two launches: a streaming read that leaves one partial per workgroup in `workspace` (plain
+ * stores; the grid depends on n alone, so the order of summation is the same on every device and in every run), and one
+ * workgroup that adds the partials in double in a fixed order and writes the DEVICE-resident control block.  The
+ * guarded steps are fvta_adadelta_step / fvta_adam_step fed with g = g'' * factor, taking grad_scale, clip_value,
+ * factor, apply and (Adam) lr_t from that block; with apply == 0 they write nothing.  With factor == 1 and no
+ * clip_value they are bit-identical to the unguarded steps called with the same grad_scale.
+ * grad needs 4-byte alignment only (any n >= 1); ctl 8-byte.  The caller zeroes ctl once and may preset `applied`
+ * (Adam's bias correction uses applied + 1) and `skipped`; every other field is overwritten by each call.
+ * ------------------------------------------------------------------------- */
+typedef struct fvta_guard_desc {
+  float grad_scale;       /* 1/world, as fvta_adadelta_step's grad_scale */
+  float clip_value;       /* 0 = off */
+  float clip_norm;        /* 0 = off */
+  int32_t skip_nonfinite; /* 0 / 1 */
+  int32_t adam;           /* 1: also compute lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t), t = applied + 1, in double */
+  float lr, beta1, beta2; /* read when adam == 1 */
+} fvta_guard_desc;
+
+typedef struct fvta_guard_ctl {
+  float grad_scale, clip_value, factor, lr_t; /* what the guarded steps read ... */
+  int32_t apply;                              /* ... and 0 = leave var and both slots alone */
+  float maxabs;
+  double norm;
+  int64_t nonfinite;
+  int64_t applied, skipped; /* running counters, advanced by every fvta_grad_guard */
+} fvta_guard_ctl;
+
+size_t fvta_grad_guard_workspace_bytes(int64_t n); /* 0 (and a message) for n <= 0 */
+int fvta_grad_guard(const fvta_guard_desc* d, const float* grad, int64_t n, void* workspace, fvta_guard_ctl* ctl,
+                    fvta_stream_t stream);
+int fvta_adadelta_step_guarded(float* var, const float* grad, float* accum, float* accum_update, int64_t n, float lr,
+                               float rho, float eps, const fvta_guard_ctl* ctl, fvta_stream_t stream);
+int fvta_adam_step_guarded(float* var, const float* grad, float* m, float* v, int64_t n, float beta1, float beta2,
+                           float eps, const fvta_guard_ctl* ctl, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Stand-alone forms of the reference's small graph helpers (SURVEY 8b "functional ops"); their backwards follow below.

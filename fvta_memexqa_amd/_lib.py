@@ -45,6 +45,13 @@ class ScorerDesc(Structure):
     _fields_ = [(n, c_int32) for n in ("N", "C", "w", "use_eu_output", "add_tanh", "xent_grad")]
 
 
+CTX_KMAX = 8
+
+
+class ContextDesc(Structure):
+    _fields_ = [(n, c_int32) for n in ("N", "K", "M", "w")] + [("J", c_int32 * CTX_KMAX)]
+
+
 class GuardDesc(Structure):
     _fields_ = [("grad_scale", c_float), ("clip_value", c_float), ("clip_norm", c_float), ("skip_nonfinite", c_int32),
                 ("adam", c_int32), ("lr", c_float), ("beta1", c_float), ("beta2", c_float)]
@@ -101,6 +108,8 @@ _SIGS = {
     "fvta_embed_bwd": (c_int, [POINTER(EmbedDesc), P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_image_trans_fwd": (c_int, [POINTER(ImgTransDesc), P, P, P, P, P, P, P]),
     "fvta_image_trans_bwd": (c_int, [POINTER(ImgTransDesc), P, P, P, P, P, P, P, P, P]),
+    "fvta_context_fwd": (c_int, [POINTER(ContextDesc), POINTER(P), POINTER(P), P, P, P]),
+    "fvta_context_bwd": (c_int, [POINTER(ContextDesc), P, POINTER(P), P]),
     "fvta_adadelta_step": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, P]),
     "fvta_adam_step": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float, P]),
     "fvta_weight_decay": (c_int, [P, P, c_int64, c_float, P, P]),

@@ -372,3 +372,178 @@ def scorer_ce(gq, g1, gch, W, b, y, use_eu_output=False, add_tanh=False, tf_xent
     f = lambda t: t.to(torch.float32).contiguous()
     return _ScorerCE.apply(f(gq), f(g1), f(gch), f(W).reshape(-1), f(b), ops.as_mask_u8(y), bool(use_eu_output),
                            bool(add_tanh), bool(tf_xent_grad))
+
+
+# ------------------------------------------------------------- context tensor
+class _ContextTensor(torch.autograd.Function):
+    """(K, streams[0..K) [N,M,J_k,w], then masks[0..K) u8 [N,M,J_k] or nothing) -> (hall [N,K,M,JMAX,w], hall_mask
+    [N,K,M,JMAX] bool | None): model_v2.py:863-914, one fvta_context_fwd.  The backward is the slice back, one
+    fvta_context_bwd, only into the streams that need a gradient."""
+
+    @staticmethod
+    def forward(ctx, K, *tensors):
+        streams, masks = tensors[:K], (tensors[K:] or None)
+        N, M, _, w = streams[0].shape
+        Js = [s.shape[2] for s in streams]
+        hall = torch.empty(N, K, M, max(Js), w, dtype=torch.float32, device=streams[0].device)
+        hall_mask = torch.empty(N, K, M, max(Js), dtype=torch.bool, device=hall.device) if masks else None
+        ops.context_fwd(streams, masks, hall, hall_mask)
+        ctx.dims = (N, M, Js, w)
+        ctx.set_materialize_grads(False)
+        if hall_mask is not None:
+            ctx.mark_non_differentiable(hall_mask)
+        return hall, hall_mask
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_hall, _g_mask):
+        N, M, Js, w = ctx.dims
+        K = len(Js)
+        if g_hall is None:
+            return (None,) * len(ctx.needs_input_grad)
+        need = ctx.needs_input_grad[1:1 + K]
+        ds = [torch.empty(N, M, J, w, dtype=torch.float32, device=g_hall.device) if n else None for J, n in zip(Js, need)]
+        if any(need):
+            ops.context_bwd(_c(g_hall), ds, N, M, Js, w)
+        return (None,) + tuple(ds) + (None,) * (len(ctx.needs_input_grad) - 1 - K)
+
+
+def context_tensor(streams, masks=None):
+    """streams: K contiguous fp32 [N,M,J_k,w]; masks: K u8 [N,M,J_k] or None -> (hall, hall_mask bool | None)"""
+    K = len(streams)
+    return _ContextTensor.apply(K, *streams, *(masks or ()))
+
+
+# ------------------------------------------------------------------ time warp
+class _TimeWarp(torch.autograd.Function):
+    """(hall [N,K,T,w], lq [N,w], WH_W [2w,w], WH_b [w], WC_W [w], WC_b [1]; warp_type, window_t) -> (warp_h [N,K,T,w],
+    scale [N,T] = c[n,t] cnt(t)): model_v2.py:953-1009 in the closed form of SURVEY 3.4.  Each call owns its ops.TimeWarp
+    and with it the saved c.  Backward: fvta_timewarp_bwd_att (g_scale = the attention's d_tscale under time_warp_att)."""
+
+    @staticmethod
+    def forward(ctx, hall, lq, WH_W, WH_b, WC_W, WC_b, warp_type, window_t):
+        N, K, T, w = hall.shape
+        op = ops.TimeWarp(N, K, T, w, warp_type, window_t)
+        warp_h = torch.empty_like(hall)
+        op.forward(hall, lq, WH_W, WH_b, WC_W, WC_b, warp_h)
+        ctx.set_materialize_grads(False)
+        if any(ctx.needs_input_grad):
+            ctx.op = op
+            ctx.save_for_backward(hall, lq, WH_W, WH_b, WC_W, WC_b)
+        return warp_h, op.scale
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_warp, g_scale):
+        if g_warp is None and g_scale is None:
+            return (None,) * 8
+        hall, lq, WH_W, WH_b, WC_W, WC_b = ctx.saved_tensors
+        g_warp = torch.zeros_like(hall) if g_warp is None else _c(g_warp)
+        d_hall = torch.empty_like(hall)                 # overwritten; the rest is accumulated into
+        d_lq, dWH_W, dWH_b, dWC_W, dWC_b = (torch.zeros_like(t) for t in (lq, WH_W, WH_b, WC_W, WC_b))
+        ctx.op.backward(hall, lq, WH_W, WH_b, WC_W, WC_b, g_warp, d_hall, d_lq, dWH_W, dWH_b, dWC_W, dWC_b,
+                        d_scale_att=_c(g_scale))
+        need = ctx.needs_input_grad
+        return tuple(t if n else None for t, n in zip((d_hall, d_lq, dWH_W, dWH_b, dWC_W, dWC_b), need[:6])) + (None, None)
+
+
+def time_warp(hall, lq, WH_W, WH_b, WC_W, WC_b, warp_type=1, window_t=3.0):
+    """hall [N,K,T,w] (w % 4 == 0; functional.time_warp pads any width), lq [N,w], WH_W [2w,w], WH_b [w], WC_W [w] (or
+    [w,1]), WC_b [1] -> (warp_h, scale [N,T]).  window_t gets no gradient (tf.ceil, model_v2.py:335)."""
+    ops.require_gpu()
+    f = lambda t: t.to(torch.float32).contiguous()
+    return _TimeWarp.apply(f(hall), f(lq), f(WH_W), f(WH_b), f(WC_W).reshape(-1), f(WC_b).reshape(-1), int(warp_type),
+                           float(window_t))
+
+
+# ------------------------------------------------------------------ front-end
+class _TokenEmbed(torch.autograd.Function):
+    """(word_ids [ntok] i32, char_ids [ntok,W] i32 | None, word_emb [VW,wdim], fixed_emb [G,wdim], char_emb [VC,cdim] |
+    None, filt [height,cdim,cwdim] | None, bias [cwdim] | None) -> x [ntok, cwdim + wdim] = [char part | word part]
+    (model_v2.py:524-620, fvta_embed_fwd; rows dense).  Backward: one fvta_embed_bwd into fresh zero buffers; the frozen
+    table gets none.  `argpos` lives in the call's own ops.TokenEmbed."""
+
+    @staticmethod
+    def forward(ctx, word_ids, char_ids, word_emb, fixed_emb, char_emb, filt, bias):
+        ntok = word_ids.numel()
+        VW, wdim = word_emb.shape
+        cw = 0 if char_emb is None else filt.shape[2]
+        W = 0 if char_emb is None else char_ids.shape[1]
+        height, cdim = (filt.shape[0], filt.shape[1]) if cw else (5, 0)
+        op = ops.TokenEmbed(ntok, W, cdim, cw, wdim, VW, VW + fixed_emb.shape[0], char_emb.shape[0] if cw else 1, height)
+        tok_off = torch.arange(ntok, dtype=torch.int64, device=word_emb.device) * (cw + wdim)
+        x = torch.empty(ntok, cw + wdim, dtype=torch.float32, device=word_emb.device)
+        op.forward(word_ids, char_ids, tok_off, word_emb, fixed_emb if fixed_emb.shape[0] else None, char_emb, filt, bias, x)
+        if any(ctx.needs_input_grad):
+            ctx.op, ctx.ids = op, (word_ids, char_ids, tok_off)
+            ctx.save_for_backward(word_emb, char_emb, filt, bias)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        word_emb, char_emb, filt, bias = ctx.saved_tensors
+        word_ids, char_ids, tok_off = ctx.ids
+        z = lambda t: None if t is None else torch.zeros_like(t)
+        dwe, dce, dfl, dbi = z(word_emb), z(char_emb), z(filt), z(bias)
+        ctx.op.backward(word_ids, char_ids, tok_off, char_emb, filt, _c(g), dwe, dce, dfl, dbi)
+        need = ctx.needs_input_grad
+        return (None, None, dwe if need[2] else None, None, dce if need[4] else None, dfl if need[5] else None,
+                dbi if need[6] else None)
+
+
+def token_embed(word_ids, char_ids, word_emb, fixed_emb, char_emb=None, filt=None, bias=None):
+    """ids of any shape [...] (chars [..., W]) -> x [..., cwdim + wdim]; filt [height, cdim, cwdim] (or TF's
+    [1, height, cdim, cwdim]).  Ids >= VW read fixed_emb[id - VW].  keep_prob is 1 (no char dropout here)."""
+    dev = ops.require_gpu()
+    f = lambda t: None if t is None else t.to(dev, torch.float32).contiguous()
+    i32 = lambda t: t.to(dev, torch.int32).contiguous()
+    lead = tuple(word_ids.shape)
+    if char_emb is not None:
+        filt = filt.reshape(filt.shape[-3:])
+        char_ids = i32(char_ids).reshape(-1, char_ids.shape[-1])
+    else:
+        char_ids = filt = bias = None
+    x = _TokenEmbed.apply(i32(word_ids).reshape(-1), char_ids, f(word_emb), f(fixed_emb), f(char_emb), f(filt), f(bias))
+    return x.reshape(lead + (x.shape[-1],))
+
+
+class _PhotoFeatures(torch.autograd.Function):
+    """(pidx [R] i32, image_emb_mat [P,idim], W [idim,tdim] | None, b [tdim] | None; add_tanh) -> x [R, tdim or idim]
+    (model_v2.py:634-645, fvta_image_trans_fwd).  image_emb_mat is a placeholder in the reference: no gradient."""
+
+    @staticmethod
+    def forward(ctx, pidx, image_emb_mat, W, b, add_tanh):
+        R, idim = pidx.numel(), image_emb_mat.shape[1]
+        tdim = idim if W is None else W.shape[1]
+        op = ops.ImageTrans(R, idim, tdim, add_tanh and W is not None)
+        row_off = torch.arange(R, dtype=torch.int64, device=pidx.device) * tdim
+        x = torch.empty(R, tdim, dtype=torch.float32, device=pidx.device)
+        op.forward(pidx, row_off, image_emb_mat, W, b, x)
+        if W is not None and any(ctx.needs_input_grad):
+            ctx.op, ctx.idx = op, (pidx, row_off)
+            ctx.save_for_backward(image_emb_mat, W, x)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[2] and not ctx.needs_input_grad[3]:
+            return (None,) * 5
+        image_emb_mat, W, x = ctx.saved_tensors
+        pidx, row_off = ctx.idx
+        dW = torch.zeros_like(W)
+        db = torch.zeros(W.shape[1], dtype=torch.float32, device=W.device)
+        ctx.op.backward(pidx, row_off, image_emb_mat, x, _c(g), dW, db)
+        need = ctx.needs_input_grad
+        return None, None, dW if need[2] else None, db if need[3] else None, None
+
+
+def photo_features(pis, image_emb_mat, W=None, b=None, add_tanh=False):
+    """pis [...] photo indices into image_emb_mat [P,idim] -> [..., tdim] through image_trans_linear W [idim,tdim], b [tdim]
+    (+ tanh), or the gathered rows [..., idim] without W."""
+    dev = ops.require_gpu()
+    f = lambda t: None if t is None else t.to(dev, torch.float32).contiguous()
+    x = _PhotoFeatures.apply(pis.to(dev, torch.int32).contiguous().reshape(-1), f(image_emb_mat).detach(), f(W), f(b),
+                             bool(add_tanh))
+    return x.reshape(tuple(pis.shape) + (x.shape[-1],))

@@ -12,6 +12,9 @@
                         bidirect=False, scope=None) -> h_a [N,M,w]                   model.py:247-314
       (attention_raw / attention_keeprank1_raw: the same with explicit W, b instead of the variable store)
     attention_tgif(hinfo, lq, hinfo_mask=None, wd=None, mlp_dim=512, scope=None)     model.py:210-244
+    context_tensor(streams, masks=None) -> (hall, hall_mask)                         model_v2.py:863-914
+    time_warp(hall, lq, warp_type=1, window_t=None, scope=None) -> (warp_h, scale)   model_v2.py:953-1009
+    time_indication_func(C, warp_type=1, window_t=3.0) -> (C_windowed, window_t)     model_v2.py:301-341
 
 Tensors are torch CUDA tensors; every op is one call into libfvta_hip.so, wrapped in a `torch.autograd.Function`
 (autograd.py): a tensor that requires grad gets its gradient through the library's backward kernels, and when nothing
@@ -177,9 +180,20 @@ def _attention(hinfo, hq, hinfo_mask, hq_mask, simiMatrix, wd, add_tanh, scope, 
     return attention_raw(hinfo, hq, W, b, hinfo_mask, hq_mask, simiMatrix, add_tanh, feat_order, tscale)
 
 
+def _tscale_of(C, N):
+    """model_v2.py:269-275: a_logits_maxed[n,k,t] * sum_t' C[n,t,t'] -- the row sums of C [N,T,T] as a linear layer with
+    an all-ones weight (fvta_linear_fwd); a C [N,T] is taken as those row sums already (time_warp's `scale`)."""
+    C = _f32(C)
+    if C.dim() == 2:
+        return C
+    T = C.shape[-1]
+    return linear_raw(C.reshape(N * T, T), torch.ones(T, 1, dtype=torch.float32, device=C.device), None).reshape(N, T)
+
+
 def attention_3d(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, add_tanh=False, time_warp_att=False,
                  C=None, bidirect=False, scope=None):
-    """hinfo [N,K,M,JX,w] (or [N,K,T,w]), hq [N,JQ,w], masks [N,K,M,JX] / [N,JQ] -> (h_a [N,w], a_logits [N,K,T,JQ])."""
+    """hinfo [N,K,M,JX,w] (or [N,K,T,w]), hq [N,JQ,w], masks [N,K,M,JX] / [N,JQ] -> (h_a [N,w], a_logits [N,K,T,JQ]).
+    C: [N,T,T] as in the reference, or its row sums [N,T] (time_warp's `scale`), which skips the N T^2 tensor."""
     if bidirect:
         raise NotImplementedError("bidirect: the 3-D branch cannot run in the reference either (SURVEY 3.5)")
     N, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
@@ -187,11 +201,7 @@ def attention_3d(hinfo, hq, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None
     if time_warp_att:
         if C is None:
             raise ValueError("time_warp_att needs C [N,T,T] (model_v2.py:269-275)")
-        # model_v2.py:269-275: a_logits_maxed[n,k,t] * sum_t' C[n,t,t'] -- the row sums of C [N,T,T] as a linear layer
-        # with an all-ones weight (fvta_linear_fwd)
-        C = _f32(C)
-        T = C.shape[-1]
-        tscale = linear_raw(C.reshape(N * T, T), torch.ones(T, 1, dtype=torch.float32, device=C.device), None).reshape(N, T)
+        tscale = _tscale_of(C, N)
     return _attention(hinfo.reshape(N, K, -1, w), hq, hinfo_mask, hq_mask, simiMatrix, wd, add_tanh,
                       scope or "attention_2vector", 0, tscale=tscale)
 
@@ -311,6 +321,113 @@ def attention_tgif(hinfo, lq, hinfo_mask=None, wd=None, mlp_dim=512, scope=None)
         if wd is not None:                                                    # add_wd over the whole scope (:241-242)
             _add_wd([n for n in variables if n.startswith(_name("") )], wd)
     return final + lq, att
+
+
+# ------------------------------------------------------------------ context tensor (model_v2.py:863-914)
+def context_tensor(streams, masks=None):
+    """The 12 tf.pad + 2 tf.stack of model_v2.py:863-914 as one library call each way: streams, a list of K <= 8 tensors
+    [N,M,J_k,w] (the caller reshapes hpts to [N,M,JI*JXP,w], :886), masks a list of K [N,M,J_k] bool / u8 or None ->
+    (hall [N,K,M,JMAX,w], hall_mask [N,K,M,JMAX] bool, or None without masks); JMAX = max_k J_k, rows j >= J_k are zeros /
+    False.  Rows are copied whatever their mask bit says, as tf.pad does.  The K order is the caller's (the reference's:
+    at, ad, when, where, pts, pis, :910).  The gradient of hall is sliced back into the streams that require one."""
+    streams = list(streams)
+    K = len(streams)
+    if not 1 <= K <= _lib.CTX_KMAX:
+        raise ValueError("context_tensor: K = %d streams (1..%d)" % (K, _lib.CTX_KMAX))
+    if any(s.dim() != 4 for s in streams):
+        raise ValueError("context_tensor: every stream is [N,M,J_k,w]")
+    N, M, _, w = streams[0].shape
+    for k, s in enumerate(streams):
+        if (s.shape[0], s.shape[1], s.shape[3]) != (N, M, w) or s.shape[2] < 1:
+            raise ValueError("context_tensor: stream %d is %s, stream 0 is %s: N, M and w must agree and J_k >= 1"
+                             % (k, tuple(s.shape), tuple(streams[0].shape)))
+    if masks is not None:
+        masks = list(masks)
+        if len(masks) != K:
+            raise ValueError("context_tensor: %d masks for %d streams" % (len(masks), K))
+        for k, (m, s) in enumerate(zip(masks, streams)):
+            if tuple(m.shape) != tuple(s.shape[:3]):
+                raise ValueError("context_tensor: mask %d is %s, its stream %s" % (k, tuple(m.shape), tuple(s.shape)))
+    ops.require_gpu()
+    return autograd.context_tensor([_f32(s) for s in streams], None if masks is None else [ops.as_mask_u8(m) for m in masks])
+
+
+# ------------------------------------------------------------------ time warp (model_v2.py:301-341, 953-1009)
+_WARP_TYPES = (1, 2, 3, 4, 5)
+
+
+def _check_warp_type(warp_type):
+    if warp_type not in _WARP_TYPES:
+        raise Exception("time warping type not implemented")                # model_v2.py:341
+
+
+def time_warp_raw(hall, lq, WH_W, WH_b, WC_W, WC_b, warp_type=1, window_t=3.0):
+    """The time warp with explicit weights: hall [N,K,M,JX,w] or [N,K,T,w], lq [N,w], WH_W [2w,w], WH_b [w], WC_W [w,1],
+    WC_b [1] -> (warp_h in hall's shape, scale [N,T] = c[n,t] cnt(t), the row sums of the reference's windowed C).  The
+    kernels take w % 4 == 0; another width is zero padded here (exact: the padded channels of WH, WH_b, WC and lq are
+    zero) and sliced back, with differentiable torch ops."""
+    _check_warp_type(warp_type)
+    hall, lq = _f32(hall), _f32(lq)
+    shape, w = hall.shape, hall.shape[-1]
+    N, K = shape[0], shape[1]
+    wp = (w + 3) // 4 * 4
+    h = hall.reshape(N, K, -1, w)
+    WH_W, WH_b, WC_W = _f32(WH_W), _f32(WH_b), _f32(WC_W).reshape(w)
+    if wp != w:
+        pad = torch.nn.functional.pad
+        h, lq, WH_b, WC_W = pad(h, (0, wp - w)), pad(lq, (0, wp - w)), pad(WH_b, (0, wp - w)), pad(WC_W, (0, wp - w))
+        WH_W = pad(WH_W.reshape(2, w, w), (0, wp - w, 0, wp - w)).reshape(2 * wp, wp)
+    warp_h, scale = autograd.time_warp(h, lq, WH_W, WH_b, WC_W, _f32(WC_b), warp_type, float(window_t))
+    if wp != w:
+        warp_h = warp_h[..., :w]
+    return warp_h.reshape(shape), scale
+
+
+def time_warp(hall, lq, warp_type=1, window_t=None, scope=None):
+    """model_v2.py:953-1009: hall [N,K,M,JX,w] or [N,K,T,w], lq [N,w] -> (warp_h in hall's shape, scale [N,T]).  The
+    variables WH/W [2w,w], WH/b [w], WC/W [w,1], WC/b [1] live below `scope or "time_warp"` (truncated normal 0.1 / zeros);
+    for warp_type 5 the window is time_warp_C/time_warp_window_t, a 0-d tensor initialised to 3.0 and used when `window_t`
+    is None (it never receives a gradient: tf.ceil, :335).  `scale` is what attention_3d(time_warp_att=True, C=scale)
+    takes in place of the reference's C [N,T,T]."""
+    _check_warp_type(warp_type)
+    w = hall.shape[-1]
+    with variable_scope(scope or "time_warp"):
+        WH_W = get_variable(_name("WH", "W"), (2 * w, w))
+        WH_b = get_variable(_name("WH", "b"), (w,), init="zeros")
+        WC_W = get_variable(_name("WC", "W"), (w, 1))
+        WC_b = get_variable(_name("WC", "b"), (1,), init="zeros")
+        if warp_type == 5:
+            wn = _name("time_warp_C", "time_warp_window_t")
+            if wn not in variables:
+                variables[wn] = torch.full((), 3.0, dtype=torch.float32, device=ops.require_gpu())
+            if window_t is None:
+                window_t = float(variables[wn])
+    return time_warp_raw(hall, lq, WH_W, WH_b, WC_W, WC_b, warp_type, 3.0 if window_t is None else float(window_t))
+
+
+_bands = {}      # (T, warp_type, win, device) -> the 0/1 band [T,T], built once
+
+
+def time_indication_func(C, warp_type=1, window_t=3.0):
+    """model_v2.py:301-341: C [N,T,T] times the 0/1 indicator of the warp type (1 all, 2 current, 3 past, 4 future, 5 a
+    window of ceil(window_t) either side) -> (C_windowed, window_t for type 5 | None).  One fvta_wsum_fwd over the
+    elements (J = d = 1: a product) with the band, built once per (T, warp_type, window); differentiable in C.  It
+    exists for code written against the reference's signature -- the [N,T] path (time_warp's `scale`) needs no C."""
+    import math
+    _check_warp_type(warp_type)
+    C = _f32(C)
+    N, T = C.shape[0], C.shape[-1]
+    dev = ops.require_gpu()
+    win = int(math.ceil(float(window_t))) if warp_type == 5 else 0
+    key = (T, warp_type, win, str(C.device))
+    if key not in _bands:
+        ones = torch.ones(T, T, dtype=torch.float32)
+        band = {1: ones, 2: torch.eye(T), 3: torch.tril(ones), 4: torch.triu(ones),
+                5: torch.triu(torch.tril(ones, win), -win)}[warp_type]
+        _bands[key] = band.to(C.device)
+    band = _bands[key][None].expand(N, T, T).reshape(-1, 1)
+    out = autograd.wsum(C.reshape(-1, 1, 1), band).reshape(N, T, T)
+    return out, (window_t if warp_type == 5 else None)
 
 
 # ------------------------------------------------------------------ DMN+ episode (model_dmnplus.py:89-136)

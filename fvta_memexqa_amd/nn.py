@@ -89,18 +89,15 @@ class _AttLogits(_Module):
 
 class FocalAttention3D(_AttLogits):
     """attention_3d (model_v2.py:210-298): hinfo [N,K,...,w], hq [N,JQ,w], masks -> (h_a [N,w], a_logits [N,K,T,JQ]), both
-    differentiable.  With C [N,T,T] the max-pooled logits are scaled by its row sums (time_warp_att)."""
+    differentiable.  With C [N,T,T] the max-pooled logits are scaled by its row sums (time_warp_att); C [N,T] is taken as
+    those row sums already (TimeWarp's `scale`)."""
 
     def __init__(self, w, simiMatrix=1, add_tanh=False, seed=None):
         super().__init__(w, simiMatrix, add_tanh, seed)
 
     def forward(self, hinfo, hq, hinfo_mask=None, hq_mask=None, C=None):
         N, K = hinfo.shape[0], hinfo.shape[1]
-        tscale = None
-        if C is not None:
-            T = C.shape[-1]
-            ones = torch.ones(T, 1, dtype=torch.float32, device=C.device)
-            tscale = functional.linear_raw(C.to(torch.float32).reshape(N * T, T), ones, None).reshape(N, T)
+        tscale = functional._tscale_of(C, N) if C is not None else None
         W, b = self._wb()
         return functional.attention_raw(hinfo.reshape(N, K, -1, self.w), hq, W, b, hinfo_mask, hq_mask, self.simiMatrix,
                                         self.add_tanh, 0, tscale)
@@ -156,3 +153,90 @@ class AnswerScorer(_Module):
     def forward(self, gq, g1, gch, y):
         return autograd.scorer_ce(gq, g1, gch, self.p("choicelogits/W"), self.p("choicelogits/b"), y,
                                   use_eu_output=self.use_eu_output, add_tanh=self.add_tanh, tf_xent_grad=self.tf_xent_grad)
+
+
+class TimeWarp(_Module):
+    """The time warp of the context tensor (model_v2.py:953-1009): forward(hall [N,K,M,JX,w] or [N,K,T,w], lq [N,w]) ->
+    (warp_h in hall's shape, scale [N,T]); `scale` feeds FocalAttention3D(..., C=scale).  Parameters `WH/W` [2w,w], `WC/W`
+    [w,1] truncated normal(0.1), `WH/b` [w], `WC/b` [1] zeros; the buffer `time_warp_C/time_warp_window_t` (a 0-d tensor,
+    the reference's variable of that name) is in state_dict() and never receives a gradient (tf.ceil, :335)."""
+
+    def __init__(self, w, warp_type=1, window_t=3.0, seed=None):
+        super().__init__()
+        functional._check_warp_type(warp_type)
+        self.w, self.warp_type = int(w), int(warp_type)
+        shapes = (("WH/W", (2 * self.w, self.w)), ("WH/b", (self.w,)), ("WC/W", (self.w, 1)), ("WC/b", (1,)))
+        for i, (name, shape) in enumerate(shapes):
+            if name.endswith("/b"):
+                self._param(name, torch.zeros(shape))
+            else:
+                self._param(name, _trunc_normal(_gen(name, None if seed is None else seed + i), shape))
+        self.register_buffer("time_warp_C/time_warp_window_t", torch.tensor(float(window_t), dtype=torch.float32, device=self._dev))
+        self._win = None
+
+    def window_t(self):
+        """the window as a host number, read back from the buffer only after it changed (load_state_dict)"""
+        buf = self._buffers["time_warp_C/time_warp_window_t"]
+        if self._win is None or self._win[0] != (buf._version, buf.data_ptr()):
+            self._win = ((buf._version, buf.data_ptr()), float(buf))
+        return self._win[1]
+
+    def forward(self, hall, lq):
+        return functional.time_warp_raw(hall, lq, self.p("WH/W"), self.p("WH/b"), self.p("WC/W"), self.p("WC/b"),
+                                        self.warp_type, self.window_t())
+
+
+def _glorot_any(gen, shape):
+    """tf.get_variable's default initialiser as Model.init_parameters applies it to the front-end's variables"""
+    fan = (shape[-3] * shape[-2], shape[-1]) if len(shape) >= 3 else (shape[0], shape[-1])
+    lim = (6.0 / (fan[0] + fan[1])) ** 0.5
+    return (torch.rand(shape, generator=gen) * 2 - 1) * lim
+
+
+class TokenEmbedding(_Module):
+    """The text front-end (model_v2.py:524-620): forward(word_ids [...], char_ids [..., W] | None, existing_emb_mat
+    [G,wdim]) -> x [..., cwdim + wdim] = [char-CNN part | word part].  Ids < VW read `word/var/word_emb_mat` [VW,wdim]
+    (trainable, N(0,1) rows as main.py:308), ids >= VW read existing_emb_mat[id - VW], the frozen pre-trained table: it
+    gets no gradient.  With cwdim > 0 the char-CNN: `var/char_emb` [VC,cdim], `conv/conv1d/filter` [1,height,cdim,cwdim],
+    `conv/conv1d/bias` [cwdim] (tf.get_variable's default, as Model initialises them).  The limits of fvta_embed_desc
+    (cwdim <= 128, height <= W <= 64, VC <= 1024, ...) surface as the library's own error.  No char dropout here."""
+
+    def __init__(self, VW, wdim, VC=0, cdim=0, cwdim=0, W=0, height=5, seed=None):
+        super().__init__()
+        self.VW, self.wdim, self.VC, self.cdim, self.cwdim, self.W, self.height = (int(v) for v in (VW, wdim, VC, cdim, cwdim, W, height))
+        sd = lambda i: None if seed is None else seed + i
+        self._param("word/var/word_emb_mat", torch.randn(self.VW, self.wdim, generator=_gen("word/var/word_emb_mat", sd(0))))
+        if self.cwdim > 0:
+            self._param("var/char_emb", _glorot_any(_gen("var/char_emb", sd(1)), (self.VC, self.cdim)))
+            self._param("conv/conv1d/filter", _glorot_any(_gen("conv/conv1d/filter", sd(2)), (1, self.height, self.cdim, self.cwdim)))
+            self._param("conv/conv1d/bias", _glorot_any(_gen("conv/conv1d/bias", sd(3)), (self.cwdim,)))
+
+    def forward(self, word_ids, char_ids, existing_emb_mat):
+        if self.cwdim > 0:
+            if char_ids is None or char_ids.shape[-1] != self.W or tuple(char_ids.shape[:-1]) != tuple(word_ids.shape):
+                raise ValueError("TokenEmbedding: char_ids must be word_ids' shape + [%d]" % self.W)
+            return autograd.token_embed(word_ids, char_ids, self.p("word/var/word_emb_mat"), existing_emb_mat,
+                                        self.p("var/char_emb"), self.p("conv/conv1d/filter"), self.p("conv/conv1d/bias"))
+        return autograd.token_embed(word_ids, None, self.p("word/var/word_emb_mat"), existing_emb_mat)
+
+
+class PhotoFeatures(_Module):
+    """The photo front-end (model_v2.py:634-645): forward(pis [...], image_emb_mat [P,idim]) -> [..., tdim or idim].  With
+    tdim: `image_transform/image_trans_linear/{W [idim,tdim] truncated normal(0.1), b [tdim] zeros}` (+ tanh with add_tanh);
+    without, the gathered rows and no parameters.  image_emb_mat is the reference's placeholder: no gradient flows into it."""
+
+    def __init__(self, idim, tdim=None, add_tanh=False, seed=None):
+        super().__init__()
+        self.idim, self.tdim, self.add_tanh = int(idim), (None if tdim is None else int(tdim)), bool(add_tanh)
+        if self.tdim is not None:
+            name = "image_transform/image_trans_linear/W"
+            self._param(name, _trunc_normal(_gen(name, seed), (self.idim, self.tdim)))
+            self._param("image_transform/image_trans_linear/b", torch.zeros(self.tdim))
+
+    def forward(self, pis, image_emb_mat):
+        if image_emb_mat.shape[-1] != self.idim:
+            raise ValueError("PhotoFeatures: image_emb_mat is %s, idim %d" % (tuple(image_emb_mat.shape), self.idim))
+        if self.tdim is None:
+            return autograd.photo_features(pis, image_emb_mat)
+        return autograd.photo_features(pis, image_emb_mat, self.p("image_transform/image_trans_linear/W"),
+                                       self.p("image_transform/image_trans_linear/b"), self.add_tanh)

@@ -516,6 +516,39 @@ class TimeWarp:
                                                 stream_ptr()), "fvta_timewarp_bwd_shadow")
 
 
+# ------------------------------------------------------------ context tensor
+def _ptr_table(tensors, K):
+    """a HOST array of K device pointers (None -> NULL); the kernels take the pointers by value, nothing is copied"""
+    return (ctypes.c_void_p * K)(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _context_desc(N, M, Js, w):
+    if not 1 <= len(Js) <= _lib.CTX_KMAX:
+        raise ValueError("context_tensor: K must be in 1..%d (got %d)" % (_lib.CTX_KMAX, len(Js)))
+    d = _lib.ContextDesc(int(N), len(Js), int(M), int(w))
+    for k, J in enumerate(Js):
+        d.J[k] = int(J)
+    return d
+
+
+def context_fwd(streams, masks, hall, hall_mask):
+    """model_v2.py:863-914: streams[k] [N,M,J_k,w] f32 (masks[k] [N,M,J_k] u8, or masks = hall_mask = None) ->
+    hall [N,K,M,JMAX,w], hall_mask [N,K,M,JMAX] u8; every element written once (fvta_context_fwd, one launch)."""
+    N, M, _, w = streams[0].shape
+    K = len(streams)
+    d = _context_desc(N, M, [s.shape[2] for s in streams], w)
+    check(_lib.load().fvta_context_fwd(ctypes.byref(d), _ptr_table([_f32c(s) for s in streams], K),
+                                       None if masks is None else _ptr_table(masks, K), ptr(_f32c(hall)), ptr(hall_mask),
+                                       stream_ptr()), "fvta_context_fwd")
+
+
+def context_bwd(d_hall, d_streams, N, M, Js, w):
+    """d_streams[k] [N,M,J_k,w] <- d_hall[:, k, :, :J_k] (overwritten; a None entry is skipped; fvta_context_bwd)"""
+    d = _context_desc(N, M, Js, w)
+    check(_lib.load().fvta_context_bwd(ctypes.byref(d), ptr(_f32c(d_hall)), _ptr_table(d_streams, len(Js)), stream_ptr()),
+          "fvta_context_bwd")
+
+
 # ------------------------------------------------------- embedding front-end
 class TokenEmbed:
     """model_v2.py:524-620 for all text tokens of a batch: char-CNN + word lookup, rows written at tok_off.

@@ -338,6 +338,31 @@ int fvta_timewarp_bwd_att(const fvta_timewarp_desc* d, const float* hall, const 
                           float* dWH_b, float* dWC_W, float* dWC_b, void* workspace, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * Context tensor: model_v2.py:863-914, the 12 tf.pad + 2 tf.stack that turn the K encoder outputs
+ * into hall [N,K,M,JMAX,w] and hall_mask [N,K,M,JMAX], JMAX = max_k J[k] (:869).  Model never builds it this way (its
+ * bi-LSTMs write into the arena); this is the stand-alone form for graphs composed from the functional surface.
+ *   streams / masks / d_streams: HOST arrays of K device pointers, passed to the kernel by value (no device table, no
+ *   hidden allocation, no copy); streams[k] [N,M,J[k],w] f32, masks[k] [N,M,J[k]] u8.
+ * fvta_context_fwd, one launch: hall[n,k,m,j,:] = streams[k][n,m,j,:] for j < J[k], zeros otherwise; hall_mask the same
+ *   from masks[k].  Rows are copied whether or not their mask bit is set (tf.pad does; the encoders zero rows past the
+ *   length themselves).  masks == NULL together with hall_mask == NULL: no mask is produced; one without the other is
+ *   an invalid argument.  Every element of both outputs is written exactly once and none is read (no zero-fill).
+ * fvta_context_bwd, one launch: d_streams[k][n,m,j,:] = d_hall[n,k,m,j,:] for j < J[k] (tf.pad's gradient, a slice);
+ *   overwritten; an entry d_streams[k] == NULL is skipped.  The mask plays no part.
+ * 16-byte loads and stores when w % 4 == 0 and every pointer is 16-byte aligned, 4-byte ones otherwise; every element
+ * index is 64-bit (BASELINE.json configs[4]: 3.3 G elements).  N * K * M < 2^31.
+ * ------------------------------------------------------------------------- */
+#define FVTA_CTX_KMAX 8
+typedef struct fvta_context_desc {
+  int32_t N, K, M, w;       /* K <= FVTA_CTX_KMAX; w = floats per row, any value >= 1 */
+  int32_t J[FVTA_CTX_KMAX]; /* rows per album of stream k (>= 1 for k < K) */
+} fvta_context_desc;        /* 48 bytes, twelve int32: a layout with no padding to disagree about */
+
+int fvta_context_fwd(const fvta_context_desc* d, const float* const* streams, const uint8_t* const* masks,
+                     float* hall /* [N,K,M,JMAX,w] */, uint8_t* hall_mask /* [N,K,M,JMAX] */, fvta_stream_t stream);
+int fvta_context_bwd(const fvta_context_desc* d, const float* d_hall, float* const* d_streams, fvta_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Embedding front-end (model_v2.py:524-645): what turns the
  * reference's token-id feed into the encoder inputs.
  *

@@ -21,7 +21,6 @@
 
 namespace fvta {
 
-__device__ __forceinline__ f32x4 ld4b(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 constexpr int BWD_CHMAX = 1024;  // rows per backward workgroup chunk (LDS sort capacity)
 
@@ -348,9 +347,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_main(AttnBwdArgs a) {
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const int c4 = cq + g * TPR;
-    gv[g] = ld4b(a.d_h_a + (size_t)(PERK ? nk : n) * w + 4 * c4);
-    rh4[g] = ld4b(a.sv.vecs + VEC_RH * w + 4 * c4);
-    r24[g] = ld4b(a.sv.vecs + VEC_R2 * w + 4 * c4);
+    gv[g] = ld4(a.d_h_a + (size_t)(PERK ? nk : n) * w + 4 * c4);
+    rh4[g] = ld4(a.sv.vecs + VEC_RH * w + 4 * c4);
+    r24[g] = ld4(a.sv.vecs + VEC_R2 * w + 4 * c4);
     accq[g] = accRh[g] = accR2[g] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   int cur_j = -1;
@@ -514,7 +513,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_main(AttnBwdArgs a) {
         // compiler must wait vmcnt(0) at every row's first use, which drains the row stores one by one.)
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-          qs_cur[g] = ld4b(Qs + ((size_t)(cq + g * TPR) * JP + j) * 4);
+          qs_cur[g] = ld4(Qs + ((size_t)(cq + g * TPR) * JP + j) * 4);
           asm volatile("" : "+v"(qs_cur[g]));
         }
       }
@@ -524,13 +523,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_main(AttnBwdArgs a) {
         const int c4 = cq + g * TPR;
         const f32x4 h = row_val(i, g);
 #ifdef FVTA_ATTN_BWD_QS_PER_ROW  // (A/B: the per-row gather this replaced)
-        const f32x4 qs = ld4b(Qs + ((size_t)c4 * JP + j) * 4);
+        const f32x4 qs = ld4(Qs + ((size_t)c4 * JP + j) * 4);
 #else
         const f32x4 qs = qs_cur[g];
 #endif
         f32x4 dh = cosine ? gv[g] * pr + qs * dx + h * self : gv[g] * pr + (qs + rh4[g] + r24[g] * h * 2.f) * dx;
         float* dst = dhbase + (size_t)t * w + 4 * c4;
-        if constexpr (ACC) dh += ld4b(dst);
+        if constexpr (ACC) dh += ld4(dst);
         if ((a.nt & 1) && !ACC)
           __builtin_nontemporal_store(dh, reinterpret_cast<f32x4*>(dst));
         else
@@ -783,12 +782,12 @@ __global__ __launch_bounds__(256) void attn_bwd_pad_kernel(AttnBwdArgs a, const 
         float* drow = a.d_hinfo + ((size_t)nk * T + tt) * w;
         float dot = 0.f;
         for (int c = 4 * tid; c < w; c += 1024) {
-          const f32x4 hv = ld4b(row + c), gv = ld4b(g + c);
+          const f32x4 hv = ld4(row + c), gv = ld4(g + c);
           const f32x4 pdt = hv * gv;
           dot += (pdt[0] + pdt[1]) + (pdt[2] + pdt[3]);
           if (pass == 1) {
             f32x4 dh = gv * pr;
-            if (a.accumulate != 2) dh += ld4b(drow + c);  // modes 0/3 zeroed the row first, mode 1 accumulates; 2: plain store
+            if (a.accumulate != 2) dh += ld4(drow + c);  // modes 0/3 zeroed the row first, mode 1 accumulates; 2: plain store
             *reinterpret_cast<f32x4*>(drow + c) = dh;
           }
         }

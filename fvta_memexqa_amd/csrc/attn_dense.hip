@@ -16,25 +16,14 @@ namespace fvta {
 
 constexpr int DENSE_MAX = 8192;  // V * JQ floats of one batch row in LDS
 
-__device__ __forceinline__ float dn_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float dn_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // p[v, j] = softmax_j(a[v, :]) into LDS (a wave per row, a lane per j: JQ <= 64), pbar[j] = mean_v p[v, j]
 __device__ __forceinline__ void qside_probs(const float* __restrict__ a, float* s_p, float* s_pbar, int V, int JQ) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   for (int v = wave; v < V; v += 4) {
     const float x = lane < JQ ? a[v * JQ + lane] : -INFINITY;
-    const float m = dn_wave_max(x);
+    const float m = wave_max(x);
     const float e = lane < JQ ? expf(x - m) : 0.f;
-    const float s = dn_wave_sum(e);
+    const float s = wave_sum(e);
     if (lane < JQ) s_p[v * JQ + lane] = e / s;
   }
   __syncthreads();
@@ -75,7 +64,7 @@ __global__ __launch_bounds__(256) void attn_qside_bwd_kernel(const float* __rest
   for (int j = wave; j < JQ; j += 4) {  // d pbar[j] = g . hq[j]
     float acc = 0.f;
     for (int c = lane; c < w; c += 64) acc += g[c] * q[(int64_t)j * w + c];
-    acc = dn_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) s_dpb[j] = acc;
   }
   __syncthreads();
@@ -83,7 +72,7 @@ __global__ __launch_bounds__(256) void attn_qside_bwd_kernel(const float* __rest
   for (int v = wave; v < V; v += 4) {  // softmax backward per row; d p[v,j] = d pbar[j] / V
     const float p = lane < JQ ? s_p[v * JQ + lane] : 0.f;
     const float dp = lane < JQ ? s_dpb[lane] * invV : 0.f;
-    const float dot = dn_wave_sum(p * dp);
+    const float dot = wave_sum(p * dp);
     if (lane < JQ) dA[(r * V + v) * JQ + lane] = p * (dp - dot);
   }
   float* dq = d_hq + r * JQ * w;
@@ -115,7 +104,7 @@ __global__ __launch_bounds__(256) void attn_logits_bwd_kernel(const float* __res
     s_d[i] = v;
     tot += v;
   }
-  tot = dn_wave_sum(tot);
+  tot = wave_sum(tot);
   if ((tid & 63) == 0) s_red[tid >> 6] = tot;
   __syncthreads();
   if (tid == 0) pb[n] = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);

@@ -14,7 +14,6 @@
 
 namespace fvta {
 
-__device__ __forceinline__ f32x4 ld4g(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 #ifndef FVTA_ATTN_WAVE16_DEFAULT
 #define FVTA_ATTN_WAVE16_DEFAULT 3
 #endif
@@ -109,11 +108,11 @@ __global__ __launch_bounds__(256) void attn_prep_q_kernel(AttnShape s, AttnSaved
     const int c4 = u / s.JP, j = u % s.JP;
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     if (j < s.JQ) {
-      const f32x4 qv = ld4g(q + (size_t)j * w + 4 * c4);
+      const f32x4 qv = ld4(q + (size_t)j * w + 4 * c4);
       if (s.simi == 4) {
         o = qv * s_rq[j];
       } else {
-        const f32x4 uv = ld4g(Uv + 4 * c4);
+        const f32x4 uv = ld4(Uv + 4 * c4);
         o = qv * uv;
       }
     }
@@ -356,7 +355,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 1 : 2) void attn_fwd_main(AttnFw
         const int c4 = sl * SLAB4 + wave * (NSC * SCW) + sc * SCW + c4l;
         // unconditional load from a clamped row, zeroed afterwards: a load under a per-lane branch would be
         // waited for one at a time
-        const f32x4 v = ld4g(hbase + (size_t)max(t, 0) * w + 4 * c4);
+        const f32x4 v = ld4(hbase + (size_t)max(t, 0) * w + 4 * c4);
         hreg[sc][p] = t >= 0 ? v : f32x4{0.f, 0.f, 0.f, 0.f};
       }
   };
@@ -1464,8 +1463,8 @@ __global__ __launch_bounds__(256) void attn_pad_terms_kernel(AttnShape s, AttnSa
       const float wt = s_wt[i];
       lsum += wt;
       const float* row = hinfo + ((size_t)nk * T + s_list[i]) * w;
-      if (4 * tid < w) acc[0] += ld4g(row + 4 * tid) * wt;
-      if (4 * tid + 1024 < w) acc[1] += ld4g(row + 4 * tid + 1024) * wt;
+      if (4 * tid < w) acc[0] += ld4(row + 4 * tid) * wt;
+      if (4 * tid + 1024 < w) acc[1] += ld4(row + 4 * tid + 1024) * wt;
     }
   }
   if (4 * tid < w) *reinterpret_cast<f32x4*>(pd + 4 + 4 * tid) = acc[0];

@@ -11,6 +11,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short bf16_t;  // a bf16 value as its raw 16 bits
 
 #define FVTA_WAVE 64
 #define FVTA_NEG (-1e30f)  // utils.py:205 VERY_NEGATIVE_NUMBER
@@ -82,6 +83,9 @@ __device__ __forceinline__ float fvta_tanh(float x) {
   const float e = __expf(-2.0f * fabsf(x));  // in (0,1]: no overflow
   return copysignf((1.0f - e) * __builtin_amdgcn_rcpf(1.0f + e), x);
 }
+
+// 16-byte load of four floats
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

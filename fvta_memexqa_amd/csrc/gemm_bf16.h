@@ -24,7 +24,6 @@ namespace fvta {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short bf16_t;
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
 union Pack8 {

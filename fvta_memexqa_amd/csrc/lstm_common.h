@@ -4,8 +4,6 @@
 
 namespace fvta {
 
-typedef unsigned short bf16_t;
-
 // ------------------------------------------------------------------ plan ----
 struct PlanHeader {
   int64_t out_ld;

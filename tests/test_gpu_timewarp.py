@@ -7,8 +7,16 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("warp_type", [1, 2, 3, 4, 5])
-@pytest.mark.parametrize("N,K,T,w", [(2, 3, 17, 64), (3, 6, 50, 256)])
+# every warp type on: the separate kernels (w = 64), the fused G4 = 1, 2 and 4 (the last with K = TW_KMAX), the fused forward
+# G4 = 8 with the separate backward (w = 2048), and K > TW_KMAX at a width the fused kernels would otherwise take
+_TW_SHAPES = [(2, 3, 17, 64), (3, 6, 50, 256), (1, 2, 9, 512), (1, 8, 5, 1024), (1, 2, 5, 2048), (1, 9, 5, 256)]
+# N T = 2200 > the 2048 wave slots of the fused kernels: some waves run two positions, n = pos / T changes inside a wave's
+# stride.  Types 2 and 5 only: 1 / 3 / 4 scale every row by a count of up to 1100, and the tolerance on warp_h would then be
+# judging the fp32 rounding of c near zero, not the loop
+_TW_CASES = [s + (wt,) for wt in (1, 2, 3, 4, 5) for s in _TW_SHAPES] + [(2, 2, 1100, 256, wt) for wt in (2, 5)]
+
+
+@pytest.mark.parametrize("N,K,T,w,warp_type", _TW_CASES)
 def test_timewarp_forward_backward(warp_type, N, K, T, w):
     from fvta_memexqa_amd import ops
     from oracle import fvta_fused as F
@@ -150,8 +158,11 @@ def test_model_with_time_warp_att(warp_type):
         Model(dict(spec.cfg(), use_time_warp_att=True, batch_size=spec.N), text_in=spec.text_in, img_in=spec.img_in)
 
 
-@pytest.mark.parametrize("warp_type", [1, 3, 5])
-@pytest.mark.parametrize("N,K,T,w", [(2, 3, 17, 512), (3, 6, 50, 1024), (1, 8, 9, 512)])
+# (the last case: N T = 4200 > the 4096 waves of the shadow forward, two to three positions per wave in the shadow backward;
+#  the last positions of a wave's stride take the clamped table prefetch)
+@pytest.mark.parametrize("N,K,T,w,warp_type",
+                         [s + (wt,) for wt in (1, 3, 5) for s in [(2, 3, 17, 512), (3, 6, 50, 1024), (1, 8, 9, 512)]] +
+                         [(2, 3, 2100, 512, 5)])
 def test_timewarp_over_shadow_rows(warp_type, N, K, T, w):
     """fvta_timewarp_fwd_shadow / _bwd_shadow (the bf16 engine: the context tensor is never stored in fp32) against the
     fp32-row kernels on the SAME bf16-valued rows: c / scale equal, the warped rows = bf16 of the fp32 kernel's, and every

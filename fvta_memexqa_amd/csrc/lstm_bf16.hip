@@ -17,25 +17,9 @@
 // Gates, c, h, accumulators and weight-gradient slabs stay fp32; the saved gate
 // activations are bf16 in this engine.
 #include "gemm_bf16.h"
-#include <type_traits>
 #include "lstm_common.h"
 
 namespace fvta {
-
-static inline int pad8(int v) { return (v + 7) / 8 * 8; }
-
-template <int B, int E, class F>
-__device__ __forceinline__ void bf_static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    bf_static_for<B + 1, E>(f);
-  }
-}
-
-template <class K>
-static void allow_big_lds(K kernel, int bytes) {  // > 64 KB of dynamic LDS must be opted into, per kernel symbol
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
 
 // ---- weight shadows in the internal row order [x rows | ones row | zero pad | h rows] -----------
 // kernel [in+d][N4] fp32 -> wb [in_i+d][xm N4] bf16, wt [N4][xm (in_i+d)] bf16.  grid (N4/32, (in_i+d)/32), 256 threads
@@ -80,7 +64,7 @@ __global__ void cvt_weights_kernel(const float* __restrict__ W, bf16_t* __restri
 }
 
 void launch_cvt_weights_bf16(const float* W, bf16_t* wt, bf16_t* wb, int in, int in_i, int d, int xm, hipStream_t s) {
-  hipLaunchKernelGGL(cvt_weights_kernel, dim3(4 * d / 32, (in_i + d) / 32), dim3(256), 0, s, W, wt, wb, in, in_i, d, xm);
+  lstm_launch(cvt_weights_kernel, dim3(4 * d / 32, (in_i + d) / 32), dim3(256), 0, s, W, wt, wb, in, in_i, d, xm);
 }
 
 // ---- input shadow: xs[dir][t][i][:] for every active (dir, t, i).  grid (ceil(B/16), J), 256 threads ----------
@@ -135,7 +119,7 @@ __global__ __launch_bounds__(256) void cvt_x_kernel(PlanView pv, const float* __
 }
 
 void launch_cvt_x_bf16(const PlanView& pv, const float* x, bf16_t* xs, int B, int J, int in, int in_i, int xm, hipStream_t s) {
-  hipLaunchKernelGGL(cvt_x_kernel, dim3((B + 15) / 16, J), dim3(256), 0, s, pv, x, xs, B, J, in, in_i, xm);
+  lstm_launch(cvt_x_kernel, dim3((B + 15) / 16, J), dim3(256), 0, s, pv, x, xs, B, J, in, in_i, xm);
 }
 
 // ------------------------------------------------------------ forward step --
@@ -146,8 +130,10 @@ void launch_cvt_x_bf16(const PlanView& pv, const float* x, bf16_t* xs, int B, in
 // grid (pad8(row tiles), d/32, 2), 256 threads, two workgroups per CU
 // XM = 2 (split engine): 64-element stage rows (32 k of hi | lo), two stages of 48 KB, the plain loop
 template <int XM>
+using StepFwdCfg = TileCfgT<1, 2, 4, XM == 1 ? 3 : 2, XM == 1 ? 32 : 64>;
+template <int XM>
 __global__ __launch_bounds__(256, XM == 1 ? 2 : 1) void lstm_step_fwd_bf16(StepArgs a) {
-  typedef TileCfgT<1, 2, 4, XM == 1 ? 3 : 2, XM == 1 ? 32 : 64> Cfg;
+  typedef StepFwdCfg<XM> Cfg;
   constexpr int BK = Cfg::BK;
   extern __shared__ __attribute__((aligned(16))) bf16_t smem_h[];
   int64_t* s_oo = reinterpret_cast<int64_t*>(smem_h + Cfg::STAGES * Cfg::STAGE_ELEMS);  // [256], same array
@@ -208,19 +194,18 @@ __global__ __launch_bounds__(256, XM == 1 ? 2 : 1) void lstm_step_fwd_bf16(StepA
   lstm_gate_epilogue_staged(mma, a, dir, m0, u0, nact, trow, s_oo, cprev, reinterpret_cast<char*>(smem_h) + mma.wave_all * 9216, t);
 }
 
-void launch_step_fwd_bf16(const StepArgs& a, hipStream_t s) {
-  const dim3 grid(pad8((a.B + 255) / 256), a.d / 32, 2);
-  if (a.xm == 1) {
-    constexpr int LDS = TileCfg::LDS_BYTES + 256 * 8;
-    allow_big_lds(lstm_step_fwd_bf16<1>, LDS);
-    hipLaunchKernelGGL(lstm_step_fwd_bf16<1>, grid, dim3(256), LDS, s, a);
-  } else {
-    constexpr int LDS = TileCfgT<1, 2, 4, 2, 64>::LDS_BYTES + 256 * 8;
-    allow_big_lds(lstm_step_fwd_bf16<2>, LDS);
-    hipLaunchKernelGGL(lstm_step_fwd_bf16<2>, grid, dim3(256), LDS, s, a);
-  }
+template <int XM>
+static void launch_step_fwd_xm(const StepArgs& a, hipStream_t s) {
+  typedef StepFwdCfg<XM> Cfg;  // the ring + s_oo[BM]
+  auto* k = lstm_step_fwd_bf16<XM>;
+  lstm_launch(k, dim3(pad8((a.B + Cfg::BM - 1) / Cfg::BM), a.d / 32, 2), dim3(Cfg::NT), Cfg::LDS_BYTES + Cfg::BM * 8, s, a);
 }
-
+void launch_step_fwd_bf16(const StepArgs& a, hipStream_t s) {
+  if (a.xm == 1)
+    launch_step_fwd_xm<1>(a, s);
+  else
+    launch_step_fwd_xm<2>(a, s);
+}
 
 
 // ------------------------------------------------- fused backward step (bf16) --
@@ -298,7 +283,6 @@ __device__ __forceinline__ void lstm_bwd_tile_step(const FusedBwdArgs& a, int t,
   // 8 rows, units 4 (lane % 8) ..), 256 vector-memory instructions per wave tile instead of the 1,536 four- and
   // eight-byte accesses the MFMA C layout would give (a wave stands ~124 cycles at every one, whatever its width:
   // tools/probes/store_issue_probe.hip).  Measured -1.7 %: the epilogue's 538 MB per launch sit on the HBM roof.
-  constexpr int LDP = 36;  // floats per scratch row (32 + pad, keeps 16-byte alignment)
   float* pl_ = reinterpret_cast<float*>(smem_h) + (size_t)mma.wave_all * (32 * LDP);
   const int io_row = mma.lane >> 3, io_c4 = mma.lane & 7;
   const float* __restrict__ cs_p = a.cs + (trow - a.B) * d;  // step t-1 (unused at t == 0)
@@ -310,10 +294,6 @@ __device__ __forceinline__ void lstm_bwd_tile_step(const FusedBwdArgs& a, int t,
   unsigned long long dz_base = (unsigned long long)reinterpret_cast<uintptr_t>(a.dzb + trow * (size_t)K);
   asm volatile("" : "+s"(dz_base));
   typedef f32x4 __attribute__((address_space(1)))* gf4_ptr;
-  auto wave_sync = [] {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-  };
   struct In {
     f32x4 g0, g1, g2, g3, cp, dout, dcv;  // g0, g1: packed bf16 gates of four units; split engine: g0..g3 fp32 gates, one unit each
   };
@@ -326,10 +306,6 @@ __device__ __forceinline__ void lstm_bwd_tile_step(const FusedBwdArgs& a, int t,
   auto ldnt = [](const float* p) {
     if constexpr ((ntb & 1) != 0) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));  // read once
     else return *reinterpret_cast<const f32x4*>(p);
-  };
-  auto st16 = [](float* p, const f32x4 v, bool nt) {
-    if (nt) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-    else *reinterpret_cast<f32x4*>(p) = v;
   };
   // The wave tile's TM x TN planes of four passes each form ONE sequence of passes; the loads of pass P + EPD are requested
   // when pass P is done, also across plane boundaries (the loads do not depend on the plane's scratch): EPD passes of
@@ -377,7 +353,7 @@ __device__ __forceinline__ void lstm_bwd_tile_step(const FusedBwdArgs& a, int t,
     const int pl = P >> 2, it = P & 3, ti = pl / MmaB::TN;
     const int u = plane_u(pl);
     const int lr = it * 8 + io_row, i = grow_of(mma.wave * MmaB::WROWS + ti * 32 + lr);
-    const f32x4 dh4 = *reinterpret_cast<const f32x4*>(&pl_[lr * LDP + 4 * io_c4]);
+    const f32x4 dh4 = plane_row16(pl_, lr, io_c4);
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 ga = __builtin_bit_cast(u32x4, in.g0), gb = __builtin_bit_cast(u32x4, in.g1);
     u32x4 za, zb, la, lb;  // dz of the four units, packed bf16 (i, j | f, o); la / lb: the low terms (split engine)
@@ -433,14 +409,14 @@ __device__ __forceinline__ void lstm_bwd_tile_step(const FusedBwdArgs& a, int t,
   In ins[EPD];
   // (RPW < 64: the passes over a wave tile's padding rows -- rows (pl / TN) 32 + 8 it >= RPW -- do not exist)
   auto pass_live = [](int P) constexpr { return ((P >> 2) / MmaB::TN) * 32 + (P & 3) * 8 < RPW; };
-  bf_static_for<0, EPD>([&](auto P_c) { load_pass(decltype(P_c)::value, ins[decltype(P_c)::value]); });
-  bf_static_for<0, NPASS>([&](auto P_c) {  // (compile-time indices: the pass buffers stay in registers)
+  static_for<0, EPD>([&](auto P_c) { load_pass(decltype(P_c)::value, ins[decltype(P_c)::value]); });
+  static_for<0, NPASS>([&](auto P_c) {  // (compile-time indices: the pass buffers stay in registers)
     constexpr int P = decltype(P_c)::value;
     if constexpr ((P & 3) == 0) {  // a new plane: its 32 x 32 accumulators -> scratch, row-contiguous
       constexpr int pl = P >> 2, ti = pl / MmaB::TN, tj = pl % MmaB::TN;
       if constexpr (P != 0) wave_sync();  // the previous plane's reads are done
 #pragma unroll
-      for (int r = 0; r < 16; ++r) pl_[((r & 3) + 8 * (r >> 2) + 4 * mma.hf) * LDP + mma.l31] = mma.acc[ti][tj][r];
+      for (int r = 0; r < 16; ++r) pl_[plane_c_idx(r, mma.hf, mma.l31)] = mma.acc[ti][tj][r];
       wave_sync();
     }
     if constexpr (pass_live(P)) do_pass(P, ins[P % EPD]);
@@ -455,13 +431,12 @@ __global__ __launch_bounds__((TileCfgT<WN, 2, WM>::NT), (WN == 1 && XM == 1 ? 2 
   lstm_bwd_tile_step<WN, WM, XM, BK, ST, RPW, TN>(a, a.t, blockIdx.z, blockIdx.x * (RPW == 64 ? TileCfg::BM : 4 * RPW), blockIdx.y * TileCfg::BN, smem_h);
 }
 
-static int bwd_cus() {
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  return cus;
+// one instantiation, named once: its tile configuration gives the block size and the LDS bytes (the ring + s_oo[BM])
+template <int WN, int WM, int XM, int BK, int ST, int RPW = 64, int TN = 4>
+static void launch_bwd_tile(const FusedBwdArgs& a, int row_tiles, int col_tiles, hipStream_t s) {
+  typedef TileCfgT<WN, 2, WM, ST, BK, TN> Cfg;
+  auto* k = lstm_bwd_fused_bf16<WN, WM, XM, BK, ST, RPW, TN>;
+  lstm_launch(k, dim3(row_tiles, col_tiles, 2), dim3(Cfg::NT), Cfg::LDS_BYTES + Cfg::BM * 8, s, a);
 }
 
 template <int XM>
@@ -472,17 +447,11 @@ static void launch_bwd_fused_xm(const FusedBwdArgs& a, hipStream_t s) {
     // the split engine's photo cell: the 64 x 128 tile on FOUR waves of 64 x 32 (TN = 1) -- one wave's chain of 64 k-tiles was
     // 24 DMA pieces + 48 MFMAs per tile in ONE instruction stream (~360 us per step under the text cell, 40 steps: longer than the
     // text cell's own backward); four waves share them
-    constexpr int LDS = TileCfgT<4, 2, 1, NST, NBK, 1>::LDS_BYTES + 64 * 8;
-    allow_big_lds(lstm_bwd_fused_bf16<4, 1, XM, NBK, NST, 64, 1>, LDS);
-    hipLaunchKernelGGL((lstm_bwd_fused_bf16<4, 1, XM, NBK, NST, 64, 1>), dim3((a.B + 63) / 64, a.d / 128, 2), dim3(256), LDS, s, a);
+    launch_bwd_tile<4, 1, XM, NBK, NST, 64, 1>(a, (a.B + 63) / 64, a.d / 128, s);
   } else if (a.B <= 64) {  // few sequences (the photo cell): row tiles of 64 / 128
-    constexpr int LDS = TileCfgT<1, 2, 1, NST, NBK>::LDS_BYTES + 64 * 8;
-    allow_big_lds(lstm_bwd_fused_bf16<1, 1, XM, NBK, NST>, LDS);
-    hipLaunchKernelGGL((lstm_bwd_fused_bf16<1, 1, XM, NBK, NST>), dim3((a.B + 63) / 64, (a.d + 127) / 128, 2), dim3(64), LDS, s, a);
+    launch_bwd_tile<1, 1, XM, NBK, NST>(a, (a.B + 63) / 64, (a.d + 127) / 128, s);
   } else if (a.B <= 128) {
-    constexpr int LDS = TileCfgT<1, 2, 2, NST, NBK>::LDS_BYTES + 128 * 8;
-    allow_big_lds(lstm_bwd_fused_bf16<1, 2, XM, NBK, NST>, LDS);
-    hipLaunchKernelGGL((lstm_bwd_fused_bf16<1, 2, XM, NBK, NST>), dim3((a.B + 127) / 128, (a.d + 127) / 128, 2), dim3(128), LDS, s, a);
+    launch_bwd_tile<1, 2, XM, NBK, NST>(a, (a.B + 127) / 128, (a.d + 127) / 128, s);
   } else if (a.d % 256 == 0 && !(a.nact_hint >= 0 && 4 * ((a.nact_hint + 255) / 256) <= 160)) {
     // 256 x 256 tile: dz (the A operand, K = 4d wide) is re-read d/256 instead of d/128 times.  NOT for a step whose
     // active rows (the host's lengths, when it has them: fvta_bilstm_bwd_hint) fill at most 160 of the CUs with such
@@ -490,7 +459,6 @@ static void launch_bwd_fused_xm(const FusedBwdArgs& a, hipStream_t s) {
     // workgroups per CU, spread the same rows over twice as many (ragged batches: 7.06 -> 6.74 ms per step; dense
     // batches keep the wide tile: 5.48 vs 5.72 ms per backward)
     constexpr int BK = 64, ST = 2;      // whole-line DMA pieces (gemm_bf16.h); 4d XM is a multiple of 64
-    constexpr int LDS = TileCfgT<2, 2, 4, ST, BK>::LDS_BYTES + 256 * 8;
     // row tiles of 224 rows (RPW 56) when the 256-row tiles leave CUs idle that the 224-row tiles would use: one dispatch
     // round either way (-DFVTA_BWD_RPW=64, or FVTA_BWD_RPW=64 in the environment: off)
 #ifndef FVTA_BWD_RPW
@@ -498,21 +466,17 @@ static void launch_bwd_fused_xm(const FusedBwdArgs& a, hipStream_t s) {
 #endif
     constexpr int RPW = FVTA_BWD_RPW;
     if constexpr (RPW != 64) {
-      const int rows = a.nact_hint >= 0 ? a.nact_hint : a.B, percol = 2 * (a.d / 256), cus = bwd_cus();
+      const int rows = a.nact_hint >= 0 ? a.nact_hint : a.B, percol = 2 * (a.d / 256), cus = lstm_cus();
       const int t256 = (rows + 255) / 256 * percol, tr = (rows + 4 * RPW - 1) / (4 * RPW) * percol;
       static const bool rpw_on = [] { const char* e = getenv("FVTA_BWD_RPW"); return !(e && e[0] == '6' && e[1] == '4'); }();  // A/B runs
       if (rpw_on && t256 <= cus && tr <= cus && tr > t256) {
-        allow_big_lds(lstm_bwd_fused_bf16<2, 4, XM, BK, ST, RPW>, LDS);
-        hipLaunchKernelGGL((lstm_bwd_fused_bf16<2, 4, XM, BK, ST, RPW>), dim3(pad8((a.B + 4 * RPW - 1) / (4 * RPW)), a.d / 256, 2), dim3(512), LDS, s, a);
+        launch_bwd_tile<2, 4, XM, BK, ST, RPW>(a, pad8((a.B + 4 * RPW - 1) / (4 * RPW)), a.d / 256, s);
         return;
       }
     }
-    allow_big_lds(lstm_bwd_fused_bf16<2, 4, XM, BK, ST>, LDS);
-    hipLaunchKernelGGL((lstm_bwd_fused_bf16<2, 4, XM, BK, ST>), dim3(pad8((a.B + 255) / 256), a.d / 256, 2), dim3(512), LDS, s, a);
+    launch_bwd_tile<2, 4, XM, BK, ST>(a, pad8((a.B + 255) / 256), a.d / 256, s);
   } else {
-    constexpr int LDS = TileCfgT<1, 2, 4, NST, NBK>::LDS_BYTES + 256 * 8;
-    allow_big_lds(lstm_bwd_fused_bf16<1, 4, XM, NBK, NST>, LDS);
-    hipLaunchKernelGGL((lstm_bwd_fused_bf16<1, 4, XM, NBK, NST>), dim3(pad8((a.B + 255) / 256), (a.d + 127) / 128, 2), dim3(256), LDS, s, a);
+    launch_bwd_tile<1, 4, XM, NBK, NST>(a, pad8((a.B + 255) / 256), (a.d + 127) / 128, s);
   }
 }
 
@@ -617,13 +581,8 @@ __global__ __launch_bounds__((TileCfgT<WN, 2, WM>::NT), (WN == 1 && XM == 1 ? 2 
   // ---- epilogue with every global access 16 bytes of a row: each 32 x 32 plane goes through a wave-private LDS scratch and
   // comes back row-contiguous (lane = row lane / 8 of a pass of 8 rows, columns 4 (lane % 8) ..): a quarter of the
   // vector-memory instructions of the accumulator layout's 4-byte accesses, which is what bounds this epilogue
-  constexpr int LDP = 36;
   float* pl = reinterpret_cast<float*>(smem_h) + (size_t)mma.wave_all * (32 * LDP);
   const int io_row = mma.lane >> 3, io_c4 = mma.lane & 7;
-  auto wave_sync = [] {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-  };
 #pragma unroll
   for (int ti = 0; ti < MmaB::TM; ++ti)
 #pragma unroll
@@ -631,7 +590,7 @@ __global__ __launch_bounds__((TileCfgT<WN, 2, WM>::NT), (WN == 1 && XM == 1 ? 2 
       const int nb = n0 + mma.wn * MmaB::WCOLS + tj * 32;  // first column of the plane
       if (nb >= in) continue;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) pl[((r & 3) + 8 * (r >> 2) + 4 * mma.hf) * LDP + mma.l31] = mma.acc[ti][tj][r];
+      for (int r = 0; r < 16; ++r) pl[plane_c_idx(r, mma.hf, mma.l31)] = mma.acc[ti][tj][r];
       wave_sync();
       const int n = nb + 4 * io_c4;
       f32x4 old[4];
@@ -652,7 +611,7 @@ __global__ __launch_bounds__((TileCfgT<WN, 2, WM>::NT), (WN == 1 && XM == 1 ? 2 
       }
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
-        const f32x4 v = old[it] + *reinterpret_cast<const f32x4*>(&pl[(it * 8 + io_row) * LDP + 4 * io_c4]);
+        const f32x4 v = old[it] + plane_row16(pl, it * 8 + io_row, io_c4);
         if (ok[it] && (!(abl & 4) || v[0] == 1234.5f)) {
           if ((reinterpret_cast<uintptr_t>(ptr[it]) & 15) == 0) {
             *reinterpret_cast<f32x4*>(ptr[it]) = v;
@@ -679,6 +638,14 @@ static bool dx_wide_both(const FusedBwdArgs& a) {
 }
 bool dx_writes_whole_rows(const FusedBwdArgs& a) { return dx_wide_both(a); }
 
+// one instantiation, named once: its tile configuration gives the block size and the LDS bytes (the ring + s_xo[BM])
+template <int WN, int BK, int ST, bool BOTH, bool NOACC, int XM, int WM = 4, int TN = 4>
+static void launch_dx_tile(const FusedBwdArgs& a, dim3 grid, int dir, int accumulate, hipStream_t s) {
+  typedef TileCfgT<WN, 2, WM, ST, BK, TN> Cfg;
+  auto* k = lstm_dx_bf16<WN, BK, ST, BOTH, NOACC, XM, WM, TN>;
+  lstm_launch(k, grid, dim3(Cfg::NT), Cfg::LDS_BYTES + Cfg::BM * 8, s, a, dir, accumulate);
+}
+
 template <int XM>
 static void launch_dx_xm(const FusedBwdArgs& a, hipStream_t s) {
   if (FVTA_DX_WIDE && a.in > 128 && a.in <= 256 && (4 * a.d * a.xm) % 64 == 0) {
@@ -687,43 +654,31 @@ static void launch_dx_xm(const FusedBwdArgs& a, hipStream_t s) {
 #define FVTA_DX_ST 2
 #endif
     static_assert(XM == 1 || FVTA_DX_BK == 64, "split engine: 64-element stage rows");
-    typedef TileCfgT<2, 2, 4, FVTA_DX_ST, FVTA_DX_BK> Cfg;
-    constexpr int LDS = Cfg::LDS_BYTES + 256 * 8;
-    allow_big_lds(lstm_dx_bf16<2, FVTA_DX_BK, FVTA_DX_ST, false, false, XM>, LDS);
+    constexpr int BK = FVTA_DX_BK, ST = FVTA_DX_ST;
     const dim3 grid(pad8((a.B + 255) / 256), 1, a.J);
     // both directions in one launch when one descriptor covers a direction's dz (the kernel falls back by itself when the
     // directions have separate inputs)
     if (dx_wide_both(a)) {
       FusedBwdArgs b = a;
       b.dx_both = 1;
-      if (!a.dx_accumulate) {
-        allow_big_lds(lstm_dx_bf16<2, FVTA_DX_BK, FVTA_DX_ST, true, true, XM>, LDS);
-        hipLaunchKernelGGL((lstm_dx_bf16<2, FVTA_DX_BK, FVTA_DX_ST, true, true, XM>), grid, dim3(512), LDS, s, b, 0, 0);
-      } else {
-        allow_big_lds(lstm_dx_bf16<2, FVTA_DX_BK, FVTA_DX_ST, true, false, XM>, LDS);
-        hipLaunchKernelGGL((lstm_dx_bf16<2, FVTA_DX_BK, FVTA_DX_ST, true, false, XM>), grid, dim3(512), LDS, s, b, 0, a.dx_accumulate);
-      }
-      hipLaunchKernelGGL((lstm_dx_bf16<2, FVTA_DX_BK, FVTA_DX_ST, false, false, XM>), grid, dim3(512), LDS, s, b, 1, a.dx_accumulate);  // (separate inputs: its own dx copy)
+      if (!a.dx_accumulate)
+        launch_dx_tile<2, BK, ST, true, true, XM>(b, grid, 0, 0, s);
+      else
+        launch_dx_tile<2, BK, ST, true, false, XM>(b, grid, 0, a.dx_accumulate, s);
+      launch_dx_tile<2, BK, ST, false, false, XM>(b, grid, 1, a.dx_accumulate, s);  // (separate inputs: its own dx copy)
       return;
     }
-    for (int dir = 0; dir < 2; ++dir)
-      hipLaunchKernelGGL((lstm_dx_bf16<2, FVTA_DX_BK, FVTA_DX_ST, false, false, XM>), grid, dim3(512), LDS, s, a, dir, a.dx_accumulate || dir);
+    for (int dir = 0; dir < 2; ++dir) launch_dx_tile<2, BK, ST, false, false, XM>(a, grid, dir, a.dx_accumulate || dir, s);
     return;
   }
   constexpr int NBK = XM == 1 ? 32 : 64, NST = XM == 1 ? 3 : 2;
   if (XM == 2 && a.B <= 64 && a.in <= 128) {  // the split engine's photo cell: a 64 x 128 tile on four waves (no DMA of 192 rows that do not exist)
-    constexpr int LDSP = TileCfgT<4, 2, 1, NST, NBK, 1>::LDS_BYTES + 64 * 8;
-    allow_big_lds(lstm_dx_bf16<4, NBK, NST, false, false, XM, 1, 1>, LDSP);
     const dim3 gridp((a.B + 63) / 64, 1, a.J);
-    for (int dir = 0; dir < 2; ++dir)
-      hipLaunchKernelGGL((lstm_dx_bf16<4, NBK, NST, false, false, XM, 1, 1>), gridp, dim3(256), LDSP, s, a, dir, a.dx_accumulate || dir);
+    for (int dir = 0; dir < 2; ++dir) launch_dx_tile<4, NBK, NST, false, false, XM, 1, 1>(a, gridp, dir, a.dx_accumulate || dir, s);
     return;
   }
-  constexpr int LDS1 = TileCfgT<1, 2, 4, NST, NBK>::LDS_BYTES + 256 * 8;
-  allow_big_lds(lstm_dx_bf16<1, NBK, NST, false, false, XM>, LDS1);
   const dim3 grid(pad8((a.B + 255) / 256), (a.in + 127) / 128, a.J);
-  for (int dir = 0; dir < 2; ++dir)
-    hipLaunchKernelGGL((lstm_dx_bf16<1, NBK, NST, false, false, XM>), grid, dim3(256), LDS1, s, a, dir, a.dx_accumulate || dir);
+  for (int dir = 0; dir < 2; ++dir) launch_dx_tile<1, NBK, NST, false, false, XM>(a, grid, dir, a.dx_accumulate || dir, s);
 }
 
 void launch_dx_bf16(const FusedBwdArgs& a, hipStream_t s) {
@@ -738,6 +693,8 @@ void launch_dx_bf16(const FusedBwdArgs& a, hipStream_t s) {
 #define FVTA_DW_STAGES 4
 #endif
 constexpr int dw_stages(int wn) { return wn == 2 ? FVTA_DW_STAGES : 3; }  // ring depth (TileCfgT)
+template <int WN>
+using DwCfg = TileCfgT<WN, 2, 4, dw_stages(WN)>;
 
 // slab(dir, split) [in_i+d][4d] = sum over the split's steps of [xs_t | hs_{t-1}]^T * dz_t.  Both operands
 // are k-major in memory: staged as they lie, read through the transposing LDS read.
@@ -746,7 +703,7 @@ constexpr int dw_stages(int wn) { return wn == 2 ? FVTA_DW_STAGES : 3; }  // rin
 // at the rate the address unit feeds the LDS).
 template <int WN>
 __global__ __launch_bounds__((TileCfgT<WN>::NT), (WN == 1 ? 2 : 1)) void lstm_dw_bf16(DwArgs a) {
-  typedef TileCfgT<WN, 2, 4, dw_stages(WN)> TileCfg;
+  typedef DwCfg<WN> TileCfg;
   typedef MmaBT<WN, 2, 4, dw_stages(WN)> MmaB;
   extern __shared__ __attribute__((aligned(16))) bf16_t smem_h[];
   const int tid = threadIdx.x;
@@ -856,24 +813,20 @@ __global__ __launch_bounds__(512, 1) void lstm_dw_x2(DwArgs a) {
     }
 }
 
-void launch_dw_bf16(const DwArgs& a, hipStream_t s) {
+// the 1-D grid of a weight-gradient kernel with tile configuration Cfg: 8 XCDs x tiles of a slice x slices per XCD
+template <class Cfg, class K>
+static void launch_dw_tiles(K* k, const DwArgs& a, hipStream_t s) {
   const int slices8 = (2 * a.nsplit + 7) / 8;  // slices per XCD
-  if (a.xm == 2) {  // (4d is a multiple of 128; a 256-column tile past the end stores nothing)
-    allow_big_lds(lstm_dw_x2, DwX2Cfg::LDS_BYTES);
-    const int per = ((a.in_i + 255) / 256 + (a.d + 255) / 256) * ((4 * a.d + 255) / 256);
-    hipLaunchKernelGGL(lstm_dw_x2, dim3(8 * per * slices8), dim3(512), DwX2Cfg::LDS_BYTES, s, a);
-    return;
-  }
-  if ((4 * a.d) % 256 == 0) {
-    constexpr int LDS2 = TileCfgT<2, 2, 4, dw_stages(2)>::LDS_BYTES;
-    allow_big_lds(lstm_dw_bf16<2>, LDS2);
-    const int per = ((a.in_i + 255) / 256 + (a.d + 255) / 256) * (4 * a.d / 256);
-    hipLaunchKernelGGL((lstm_dw_bf16<2>), dim3(8 * per * slices8), dim3(512), LDS2, s, a);
-  } else {
-    allow_big_lds(lstm_dw_bf16<1>, TileCfgT<1>::LDS_BYTES);
-    const int per = ((a.in_i + 255) / 256 + (a.d + 255) / 256) * (4 * a.d / 128);
-    hipLaunchKernelGGL((lstm_dw_bf16<1>), dim3(8 * per * slices8), dim3(256), TileCfgT<1>::LDS_BYTES, s, a);
-  }
+  const int per = ((a.in_i + 255) / 256 + (a.d + 255) / 256) * ((4 * a.d + Cfg::BN - 1) / Cfg::BN);
+  lstm_launch(k, dim3(8 * per * slices8), dim3(Cfg::NT), Cfg::LDS_BYTES, s, a);
+}
+void launch_dw_bf16(const DwArgs& a, hipStream_t s) {
+  if (a.xm == 2)  // (4d is a multiple of 128; a 256-column tile past the end stores nothing)
+    launch_dw_tiles<DwX2Cfg>(lstm_dw_x2, a, s);
+  else if ((4 * a.d) % 256 == 0)
+    launch_dw_tiles<DwCfg<2>>(lstm_dw_bf16<2>, a, s);
+  else
+    launch_dw_tiles<DwCfg<1>>(lstm_dw_bf16<1>, a, s);
 }
 
 // slabs (internal row order) -> dkernel [in+d][4d] and dbias [4d], accumulated, fixed summation order
@@ -904,8 +857,7 @@ __global__ __launch_bounds__(256) void lstm_dw_reduce_bf16(const float* __restri
 void launch_dw_reduce_bf16(const float* slabs, int nslab, int in, int in_i, int d, float* dW, float* dbias,
                            hipStream_t s) {
   const size_t n = (size_t)(in_i + d) * d;  // threads: one per (row, unit)
-  hipLaunchKernelGGL(lstm_dw_reduce_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, slabs, nslab, in, in_i, d, dW,
-                     dbias);
+  lstm_launch(lstm_dw_reduce_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, slabs, nslab, in, in_i, d, dW, dbias);
 }
 
 // ------------------------------------------------------------------ test gemm
@@ -975,7 +927,7 @@ __global__ void cvt_f32_il32_kernel(const float* __restrict__ src, bf16_t* __res
 // layouts 3 / 4: the split engine's row / k-major tiles on il32 two-term operands
 __global__ __launch_bounds__(256, 1) void test_gemm_x2_rows_kernel(int M, int N, int K, const bf16_t* __restrict__ A,
                                                                     const bf16_t* __restrict__ B, float* __restrict__ C) {
-  typedef TileCfgT<1, 2, 4, 2, 64> Cfg;
+  typedef StepFwdCfg<2> Cfg;  // the split engine's row tile
   typedef MmaBT<1, 2, 4, 2, 64, true> Mma;
   extern __shared__ __attribute__((aligned(16))) bf16_t smem_h[];
   const int m0 = blockIdx.x * Cfg::BM, n0 = blockIdx.y * Cfg::BN;
@@ -1048,29 +1000,17 @@ int test_gemm_bf16(int layout, int M, int N, int K, const float* A, const float*
     return FVTA_ERR_LAUNCH;
   if (layout >= 3) {
     const int la = layout == 3 ? K : M, lb = layout == 3 ? K : N;
-    hipLaunchKernelGGL(cvt_f32_il32_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, A, Ab, na / la, la);
-    hipLaunchKernelGGL(cvt_f32_il32_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, B, Bb, nb / lb, lb);
-    if (layout == 3) {
-      constexpr int LDS = TileCfgT<1, 2, 4, 2, 64>::LDS_BYTES;
-      allow_big_lds(test_gemm_x2_rows_kernel, LDS);
-      hipLaunchKernelGGL(test_gemm_x2_rows_kernel, dim3((M + 255) / 256, (N + 127) / 128), dim3(256), LDS, s, M, N, K, Ab, Bb, C);
-    } else {
-      allow_big_lds(test_gemm_x2_kmajor_kernel, DwX2Cfg::LDS_BYTES);
-      hipLaunchKernelGGL(test_gemm_x2_kmajor_kernel, dim3((M + 255) / 256, (N + 255) / 256), dim3(512), DwX2Cfg::LDS_BYTES, s, M, N, K, Ab, Bb, C);
-    }
-    (void)hipFreeAsync(Ab, s);
-    (void)hipFreeAsync(Bb, s);
-    return FVTA_OK;
-  }
-  hipLaunchKernelGGL(cvt_f32_bf16_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, A, Ab, na);
-  hipLaunchKernelGGL(cvt_f32_bf16_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, B, Bb, nb);
-  const dim3 grid((M + TileCfg::BM - 1) / TileCfg::BM, (N + TileCfg::BN - 1) / TileCfg::BN);
-  if (layout == 1) {
-    allow_big_lds(test_gemm_bf16_kernel<1>, TileCfg::LDS_BYTES);
-    hipLaunchKernelGGL(test_gemm_bf16_kernel<1>, grid, dim3(256), TileCfg::LDS_BYTES, s, M, N, K, Ab, Bb, C);
+    lstm_launch(cvt_f32_il32_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, A, Ab, na / la, la);
+    lstm_launch(cvt_f32_il32_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, B, Bb, nb / lb, lb);
+    if (layout == 3)
+      lstm_launch(test_gemm_x2_rows_kernel, dim3((M + 255) / 256, (N + 127) / 128), dim3(256), StepFwdCfg<2>::LDS_BYTES, s, M, N, K, Ab, Bb, C);
+    else
+      lstm_launch(test_gemm_x2_kmajor_kernel, dim3((M + 255) / 256, (N + 255) / 256), dim3(512), DwX2Cfg::LDS_BYTES, s, M, N, K, Ab, Bb, C);
   } else {
-    allow_big_lds(test_gemm_bf16_kernel<2>, TileCfg::LDS_BYTES);
-    hipLaunchKernelGGL(test_gemm_bf16_kernel<2>, grid, dim3(256), TileCfg::LDS_BYTES, s, M, N, K, Ab, Bb, C);
+    lstm_launch(cvt_f32_bf16_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, A, Ab, na);
+    lstm_launch(cvt_f32_bf16_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, s, B, Bb, nb);
+    auto* k = layout == 1 ? test_gemm_bf16_kernel<1> : test_gemm_bf16_kernel<2>;
+    lstm_launch(k, dim3((M + TileCfg::BM - 1) / TileCfg::BM, (N + TileCfg::BN - 1) / TileCfg::BN), dim3(256), TileCfg::LDS_BYTES, s, M, N, K, Ab, Bb, C);
   }
   (void)hipFreeAsync(Ab, s);
   (void)hipFreeAsync(Bb, s);

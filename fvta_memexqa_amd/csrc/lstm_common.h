@@ -1,5 +1,6 @@
 // Shared host/device structures of the bi-LSTM kernels (fp32 and bf16 engines).
 #pragma once
+#include <type_traits>
 #include "fvta_common.h"
 
 namespace fvta {
@@ -259,14 +260,30 @@ __device__ __forceinline__ void lstm_gate_epilogue(const Mma& mma, const StepArg
 #endif
 
 #ifdef __HIPCC__
-// The same gate math with every global access staged through LDS (bf16 engine).  In the MFMA C layout a lane holds
-// ONE unit of 16 rows, so the direct epilogue above moves 4 (or 2) bytes per lane and instruction: 160 VMEM
-// instructions per wave and tile.  The CU's address unit takes ~40-50 cycles per VMEM wave-instruction whatever its
-// width, which made the epilogue as long as the k-loop.  Here a wave transposes each 32-row x 32-unit plane through
-// a private LDS scratch (scr, >= 8704 B per wave, the k-loop's stage buffers after the closing barrier) and moves
-// 16 bytes per lane: 44 VMEM instructions per wave and tile.
-//   cprev[ti][it]: c_{t-1} of rows ti*32 + it*8 + (lane>>3), units 4*(lane&7)..+3 -- loaded by the caller BEFORE the
-//   k-loop (latency hidden), ignored when t == 0.
+// ------------------------------------------- shared by the bf16 kernels ----
+// (lstm_bf16.hip, lstm_wreg.hip, lstm_wreg_bwd.hip)
+// compile-time loop: f(std::integral_constant<int, i>) for i in [B, E) -- indices that stay constants keep arrays in registers
+template <int B, int E, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  if constexpr (B < E) {
+    f(std::integral_constant<int, B>{});
+    static_for<B + 1, E>(f);
+  }
+}
+
+// two floats -> packed bf16 pair (round to nearest even, v_cvt_pk_bf16_f32): a in the low half
+__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
+  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+  typedef float f32x2_t __attribute__((ext_vector_type(2)));
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
+}
+
+// a wave's own LDS traffic has landed and is visible to all of its lanes (wave-private scratch: no workgroup barrier)
+__device__ __forceinline__ void wave_sync() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+
 __device__ __forceinline__ void st16(float* p, const f32x4 v, bool nt) {
   if (nt)
     __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
@@ -274,12 +291,63 @@ __device__ __forceinline__ void st16(float* p, const f32x4 v, bool nt) {
     *reinterpret_cast<f32x4*>(p) = v;
 }
 
+// A 32 x 32 fp32 plane in a wave-private LDS scratch of 32 rows x LDP floats: written in the MFMA C layout (a lane holds ONE
+// column of 16 rows: value r of lane (hf, l31) at plane_c_idx), read back row-contiguous, 16 bytes per lane -- 8 lanes per
+// row, 8 rows per instruction (plane_row16) -- or the other way round.  The callers keep the loops and place the wave_sync()s.
+constexpr int LDP = 36;  // floats per scratch row (32 + pad, keeps 16-byte alignment)
+__device__ __forceinline__ int plane_c_idx(int r, int hf, int l31) { return ((r & 3) + 8 * (r >> 2) + 4 * hf) * LDP + l31; }
+// the 16-byte piece at (row, columns 4 c4 .. + 3); a pass `it` (of 4) of a wave takes row it * 8 + lane / 8, c4 = lane % 8
+__device__ __forceinline__ f32x4& plane_row16(float* pl, int row, int c4) {
+  return *reinterpret_cast<f32x4*>(&pl[row * LDP + 4 * c4]);
+}
+
+// ---- host side of the launches
+static inline int pad8(int v) { return (v + 7) / 8 * 8; }
+
+static inline int lstm_cus() {  // compute units of the current device
+  static const int cus = [] {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 0 ? n : 256;
+  }();
+  return cus;
+}
+
+// Row groups of a weights-stationary grid (2 directions x RG row groups x CB column blocks): as many as fill the CUs,
+// (2 x RG) a multiple of 8 (one (direction, row group) pair per XCD slot), and no more than there are row tiles
+static inline int wreg_row_groups(int CB, int tiles, int cap = 1 << 30) {
+  int rg = lstm_cus() / (2 * CB) / 4 * 4;
+  if (rg < 4) rg = 4;
+  if (rg > cap) rg = cap;
+  while (rg > 4 && rg - 4 >= tiles) rg -= 4;
+  return rg;
+}
+
+template <class K>
+static inline void allow_big_lds(K kernel, int bytes) {  // > 64 KB of dynamic LDS must be opted into, per kernel symbol
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
+// the one way a bf16 LSTM kernel is launched: `auto* k = kernel<...>;` names the instantiation once
+template <class... P, class... A>
+static inline void lstm_launch(void (*k)(P...), dim3 grid, dim3 block, int lds, hipStream_t s, const A&... args) {
+  if (lds > 64 * 1024) allow_big_lds(k, lds);
+  hipLaunchKernelGGL(k, grid, block, (unsigned)lds, s, args...);
+}
+
+// The same gate math as lstm_gate_epilogue with every global access staged through LDS (bf16 engine).  In the MFMA C layout
+// a lane holds ONE unit of 16 rows, so the direct epilogue above moves 4 (or 2) bytes per lane and instruction: 160 VMEM
+// instructions per wave and tile.  The CU's address unit takes ~40-50 cycles per VMEM wave-instruction whatever its
+// width, which made the epilogue as long as the k-loop.  Here a wave transposes each 32-row x 32-unit plane through
+// a private LDS scratch (scr, >= 8704 B per wave, the k-loop's stage buffers after the closing barrier) and moves
+// 16 bytes per lane: 44 VMEM instructions per wave and tile.
+//   cprev[ti][it]: c_{t-1} of rows ti*32 + it*8 + (lane>>3), units 4*(lane&7)..+3 -- loaded by the caller BEFORE the
+//   k-loop (latency hidden), ignored when t == 0.
 template <class Mma>
 __device__ __forceinline__ void lstm_gate_epilogue_staged(const Mma& mma, const StepArgs& a, int dir, int m0, int u0,
                                                           int nact, size_t trow, const int64_t* s_oo,
                                                           const f32x4 (&cprev)[Mma::TM][4], char* scr, int t) {
   static_assert(Mma::TN == 4 && Mma::WAVES_N == 1, "wave tile: 32 TM rows x the four gate strips");
-  constexpr int LDP = 36;  // floats per staged fp32 row (32 + pad, keeps 16-byte alignment)
   const int d = a.d, lane = mma.lane;  // t: the step (a.t for the per-step kernels; the sequence-stationary kernel loops over it)
   const float* __restrict__ bias = a.bias[dir];
   const int u = u0 + mma.l31;
@@ -287,10 +355,6 @@ __device__ __forceinline__ void lstm_gate_epilogue_staged(const Mma& mma, const 
   float* pl = reinterpret_cast<float*>(scr);
   bf16_t* plh = reinterpret_cast<bf16_t*>(scr);
   const int io_row = lane >> 3, io_c4 = lane & 7;  // fp32 planes: 8 lanes x 16 B per row, 8 rows per instruction
-  auto wave_sync = [] {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-  };
 #pragma unroll
   for (int ti = 0; ti < Mma::TM; ++ti) {
     const int wrow0 = mma.wave * Mma::WROWS + ti * 32;  // first tile row of this 32-row slice of the wave tile
@@ -298,10 +362,10 @@ __device__ __forceinline__ void lstm_gate_epilogue_staged(const Mma& mma, const 
     float cp[16];
     if (t > 0) {
 #pragma unroll
-      for (int it = 0; it < 4; ++it) *reinterpret_cast<f32x4*>(&pl[(it * 8 + io_row) * LDP + 4 * io_c4]) = cprev[ti][it];
+      for (int it = 0; it < 4; ++it) plane_row16(pl, it * 8 + io_row, io_c4) = cprev[ti][it];
       wave_sync();
 #pragma unroll
-      for (int r = 0; r < 16; ++r) cp[r] = pl[((r & 3) + 8 * (r >> 2) + 4 * mma.hf) * LDP + mma.l31];
+      for (int r = 0; r < 16; ++r) cp[r] = pl[plane_c_idx(r, mma.hf, mma.l31)];
       wave_sync();
     } else {
 #pragma unroll
@@ -330,13 +394,13 @@ __device__ __forceinline__ void lstm_gate_epilogue_staged(const Mma& mma, const 
     // ---- c_t -> cs (training) or the rolling cstate
     {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) pl[((r & 3) + 8 * (r >> 2) + 4 * mma.hf) * LDP + mma.l31] = cv[r];
+      for (int r = 0; r < 16; ++r) pl[plane_c_idx(r, mma.hf, mma.l31)] = cv[r];
       wave_sync();
       float* dst = a.cs ? a.cs + trow * d : a.cstate + (size_t)dir * a.B * d;
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int lr = it * 8 + io_row, i = m0 + wrow0 + lr;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(&pl[lr * LDP + 4 * io_c4]);
+        const f32x4 v = plane_row16(pl, lr, io_c4);
         if (i < nact) st16(dst + (size_t)i * d + u0 + 4 * io_c4, v, a.nt != 0);
       }
       wave_sync();
@@ -344,13 +408,13 @@ __device__ __forceinline__ void lstm_gate_epilogue_staged(const Mma& mma, const 
     // ---- h_t -> the caller's output rows (fp32)
     {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) pl[((r & 3) + 8 * (r >> 2) + 4 * mma.hf) * LDP + mma.l31] = hv[r];
+      for (int r = 0; r < 16; ++r) pl[plane_c_idx(r, mma.hf, mma.l31)] = hv[r];
       wave_sync();
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const int lr = it * 8 + io_row;
         const int64_t oo = s_oo[wrow0 + lr];
-        const f32x4 v = *reinterpret_cast<const f32x4*>(&pl[lr * LDP + 4 * io_c4]);
+        const f32x4 v = plane_row16(pl, lr, io_c4);
         if (oo >= a.out_skip) {   // (inactive rows are -1, out_skip >= 0)
           float* o = a.out + oo + u0 + 4 * io_c4;
           if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {

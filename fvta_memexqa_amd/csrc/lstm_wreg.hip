@@ -21,25 +21,9 @@
 // Operand traffic per step: the activations x (column blocks per direction) + one pass over the weights = ~0.4 GB at
 // the metric shape, a third of the tiled kernel's.  Workgroups that share rows share an XCD (blockIdx & 7).
 #include "gemm_bf16.h"
-#include <type_traits>
 #include "lstm_common.h"
 
 namespace fvta {
-
-// two floats -> packed bf16 pair (round to nearest even, v_cvt_pk_bf16_f32): a in the low half
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
-}
-
-template <int B, int E, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    static_for<B + 1, E>(f);
-  }
-}
 
 // (An EIGHT-wave form of this kernel -- two waves per SIMD of 256 registers, 32 columns each, nine weight fragments per
 //  wave in LDS, ring of six slots -- was built and measured: 4.10 ms against 3.75 ms per text-cell forward; what it gains in
@@ -579,22 +563,6 @@ __global__ __launch_bounds__(64 * C::NW, C::NW / 4) void lstm_fwd_wreg_bf16(Step
 }
 
 // ---- host side --------------------------------------------------------------------------------------
-template <class K>
-static void wreg_allow_lds(K kernel, int bytes) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-}
-
-static int wreg_cus() {
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  return cus;
-}
-
-// waves per workgroup of the configuration a shape runs on
-// column tiles per wave for a shape, 0: not built
 // FVTA_LSTM_WREG (A/B measurements): bit 0 the weights-stationary forward, bit 1 the weights-stationary backward of steps
 // with few rows, bit 2 the pipelined weights-stationary backward (d = 512, every row count); default 7, 0: the tiled step
 // kernels for every shape
@@ -612,76 +580,49 @@ int wreg_set_mode(int mode) {
   return prev;
 }
 
+// The shapes lstm_fwd_wreg_bf16 is built for, written once: f(WregCfg<in_i / 16, d / 16, NCT, X3>{}) on the row that matches;
+// false: not built (the tiled kernel runs).  The split engine (x3) has one column tile per wave; its d = 1024 does not fit:
+// 156 fragments.
+template <class F>
+static bool wreg_visit(int in_i, int d, bool x3, F&& f) {
+  if (!(wreg_mode() & 1) || in_i % 16 || d % 128) return false;
+  auto row = [&](auto c) {
+    typedef decltype(c) C;
+    if (C::IN_I != in_i || C::D != d || C::X3 != x3) return false;
+    f(c);
+    return true;
+  };
+  return row(WregCfg<14, 32, 2>{}) || row(WregCfg<8, 32, 2>{}) || row(WregCfg<14, 64, 1>{}) || row(WregCfg<8, 64, 1>{}) ||
+         row(WregCfg<8, 8, 2>{}) || row(WregCfg<2, 8, 2>{}) ||  //
+         row(WregCfg<14, 32, 1, true>{}) || row(WregCfg<8, 32, 1, true>{}) || row(WregCfg<8, 8, 1, true>{}) || row(WregCfg<2, 8, 1, true>{});
+}
+
+// column tiles per wave for a shape, 0: not built
 int wreg_nct(int in_i, int d) {
-  if (!(wreg_mode() & 1)) return 0;
-  const int nx = in_i / 16, nd = d / 16;
-  if (in_i % 16 || d % 128) return 0;
-  if (nd == 32 && (nx == 14 || nx == 8)) return 2;
-  if (nd == 64 && (nx == 14 || nx == 8)) return 1;
-  if (nd == 8 && (nx == 8 || nx == 2)) return 2;
-  return 0;
+  int nct = 0;
+  wreg_visit(in_i, d, false, [&](auto c) { nct = decltype(c)::NCT; });
+  return nct;
 }
-// the split engine's shapes (one column tile per wave; d = 1024 does not fit: 156 fragments)
-bool wreg_x3_built(int in_i, int d) {
-  if (!(wreg_mode() & 1) || in_i % 32 || d % 128) return false;
-  const int nx = in_i / 16, nd = d / 16;
-  return (nd == 32 && (nx == 14 || nx == 8)) || (nd == 8 && (nx == 8 || nx == 2));
-}
+bool wreg_x3_built(int in_i, int d) { return wreg_visit(in_i, d, true, [](auto) {}); }
 
 void launch_cvt_weights_frag(const float* W, const float* bias, bf16_t* wf, int in, int in_i, int d, int xm, hipStream_t s) {
-  const int nk16 = (in_i + d) / 16;
-  if (xm == 2) {
-    if (!wreg_x3_built(in_i, d)) return;
-    const size_t total = (size_t)d * nk16 * 8 * 2;  // one thread per 8 weights of the [4d][K] kernel, two terms
-    hipLaunchKernelGGL((cvt_weights_frag_kernel<2, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, W, bias, wf, in, in_i, d, nk16);
-    return;
-  }
-  const int nct = wreg_nct(in_i, d);
-  if (!nct) return;
-  const size_t total = (size_t)d * nk16 * 8;  // one thread per 8 weights of the [4d][K] kernel
-  const unsigned grid = (unsigned)((total + 255) / 256);
-  if (nct == 2)
-    hipLaunchKernelGGL(cvt_weights_frag_kernel<2>, dim3(grid), dim3(256), 0, s, W, bias, wf, in, in_i, d, nk16);
-  else
-    hipLaunchKernelGGL(cvt_weights_frag_kernel<1>, dim3(grid), dim3(256), 0, s, W, bias, wf, in, in_i, d, nk16);
-}
-
-template <class C>
-static void launch_wreg(const StepArgs& a, hipStream_t s) {
-  wreg_allow_lds(lstm_fwd_wreg_bf16<C>, C::LDS_BYTES);
-  // row groups: as many as fill the CUs, (2 directions x RG) a multiple of 8 (one (direction, row group) pair per XCD
-  // slot), and no more than there are row tiles
-  int rg = wreg_cus() / (2 * C::CB);
-  rg = rg / 4 * 4;
-  if (rg < 4) rg = 4;
-  const int tiles = (a.B + 31) / 32;
-  while (rg > 4 && rg - 4 >= tiles) rg -= 4;
-  hipLaunchKernelGGL(lstm_fwd_wreg_bf16<C>, dim3(2 * rg * C::CB), dim3(64 * C::NW), C::LDS_BYTES, s, a, rg);
+  wreg_visit(in_i, d, xm == 2, [&](auto c) {
+    typedef decltype(c) C;
+    const int nk16 = (in_i + d) / 16;
+    const size_t total = (size_t)d * nk16 * 8 * C::XM;  // one thread per 8 weights of the [4d][K] kernel (split engine: two terms)
+    auto* k = cvt_weights_frag_kernel<C::X3 ? 2 : C::NCT, C::X3>;
+    lstm_launch(k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, W, bias, wf, in, in_i, d, nk16);
+  });
 }
 
 bool launch_step_fwd_wreg(const StepArgs& a, hipStream_t s) {
-  const int in_i = a.Kp - a.d;
-  if (a.xm == 2) {  // the split engine
-    if (!wreg_x3_built(in_i, a.d) || !a.Wf[0] || !a.hs) return false;
-    const int nx = in_i / 16, nd = a.d / 16;
-    if (nd == 32 && nx == 14) launch_wreg<WregCfg<14, 32, 1, true>>(a, s);
-    else if (nd == 32 && nx == 8) launch_wreg<WregCfg<8, 32, 1, true>>(a, s);
-    else if (nd == 8 && nx == 8) launch_wreg<WregCfg<8, 8, 1, true>>(a, s);
-    else if (nd == 8 && nx == 2) launch_wreg<WregCfg<2, 8, 1, true>>(a, s);
-    else return false;
-    return true;
-  }
-  const int nct = wreg_nct(in_i, a.d);
-  if (!nct || !a.Wf[0] || !a.hs) return false;
-  const int nx = in_i / 16, nd = a.d / 16;
-  if (nd == 32 && nx == 14) launch_wreg<WregCfg<14, 32, 2>>(a, s);
-  else if (nd == 32 && nx == 8) launch_wreg<WregCfg<8, 32, 2>>(a, s);
-  else if (nd == 64 && nx == 14) launch_wreg<WregCfg<14, 64, 1>>(a, s);
-  else if (nd == 64 && nx == 8) launch_wreg<WregCfg<8, 64, 1>>(a, s);
-  else if (nd == 8 && nx == 8) launch_wreg<WregCfg<8, 8, 2>>(a, s);
-  else if (nd == 8 && nx == 2) launch_wreg<WregCfg<2, 8, 2>>(a, s);
-  else return false;
-  return true;
+  if (!a.Wf[0] || !a.hs) return false;
+  return wreg_visit(a.Kp - a.d, a.d, a.xm == 2, [&](auto c) {
+    typedef decltype(c) C;
+    auto* k = lstm_fwd_wreg_bf16<C>;
+    const int rg = wreg_row_groups(C::CB, (a.B + 31) / 32);
+    lstm_launch(k, dim3(2 * rg * C::CB), dim3(64 * C::NW), C::LDS_BYTES, s, a, rg);
+  });
 }
 
 }  // namespace fvta

@@ -14,18 +14,9 @@
 // 4 NCT units of one row with 16-byte accesses.  dz_{t+1} is read once per column block (d / (32 NCT) times) -- that
 // is why the tiled kernel keeps the steps with many rows (launch_bwd_wreg's row limit).
 #include "gemm_bf16.h"
-#include <type_traits>
 #include "lstm_common.h"
 
 namespace fvta {
-
-template <int B, int E, class F>
-__device__ __forceinline__ void wb_static_for(F&& f) {
-  if constexpr (B < E) {
-    f(std::integral_constant<int, B>{});
-    wb_static_for<B + 1, E>(f);
-  }
-}
 
 template <int ND16, int NCT_>
 struct WbwdCfg {
@@ -44,13 +35,6 @@ struct WbwdCfg {
 };
 
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-// two floats -> packed bf16 pair (round to nearest even, v_cvt_pk_bf16_f32): a in the low half
-__device__ __forceinline__ unsigned wb_pk_bf16(float a, float b) {
-  typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-  typedef float f32x2_t __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2_t{a, b}, bf16x2_t));
-}
 
 template <class C>
 __global__ __launch_bounds__(64 * C::NW, 1) void lstm_bwd_wreg_bf16(FusedBwdArgs a, int RG) {
@@ -146,14 +130,14 @@ __global__ __launch_bounds__(64 * C::NW, 1) void lstm_bwd_wreg_bf16(FusedBwdArgs
             asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(acc[ct]) : "v"(cur), "v"(w[ks][ct]));
         }
       };
-      wb_static_for<0, C::NKS>([&](auto ks_c) {
+      static_for<0, C::NKS>([&](auto ks_c) {
         constexpr int ks = decltype(ks_c)::value;
         const bf16x8_t cur = fr[ks % C::PF];
         if constexpr (ks + C::PF < C::NKS)
           fr[ks % C::PF] = lda(voff, ks + C::PF);
         else
           fr[ks % C::PF] = lda(voffn, ks + C::PF - C::NKS);
-        wb_static_for<0, NCT>([&](auto ct_c) { mfma(ks_c, ct_c, cur); });
+        static_for<0, NCT>([&](auto ct_c) { mfma(ks_c, ct_c, cur); });
       });
       // (the asm statements are opaque to the hazard recogniser: cover the matrix pipe's write -> LDS store distance)
       if constexpr (NCT == 2)
@@ -434,12 +418,12 @@ __global__ __launch_bounds__(64 * C::NW, 1) void lstm_bwd_ring_bf16(FusedBwdArgs
         asm volatile("" : "+v"(tc), "+v"(dc));
       } else if constexpr (k == 2) {
         const float dzi = dc * jg * ig * (1.f - ig), dzj = dc * ig * (1.f - jg * jg);
-        unsigned z0 = wb_pk_bf16(dzi, dzj);
+        unsigned z0 = pk_bf16(dzi, dzj);
         asm volatile("" : "+v"(z0));
         zw[g][2 * e] = z0;
       } else {
         const float dzf = dc * in.cp[g][e] * fg * (1.f - fg), dzo = dh * tc * og * (1.f - og);
-        unsigned z1 = wb_pk_bf16(dzf, dzo);
+        unsigned z1 = pk_bf16(dzf, dzo);
         float o = dc * fg;
         asm volatile("" : "+v"(z1), "+v"(o));
         zw[g][2 * e + 1] = z1;
@@ -478,7 +462,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void lstm_bwd_ring_bf16(FusedBwdArgs
   auto body = [&](int it, const RingIn& inP, RingIn& inC, int m0p) {
     const int m0 = 32 * (rg + RG * it);
     oo_sel = oo_nxt;  // (requested during the tile pass before)
-    wb_static_for<0, C::NKS>([&](auto q_c) {
+    static_for<0, C::NKS>([&](auto q_c) {
       constexpr int q = decltype(q_c)::value, n = q + C::PF;
       if constexpr (n % C::SLOT_KS == 0) {
         constexpr int s = (n / C::SLOT_KS) % C::SLOTS;
@@ -486,10 +470,10 @@ __global__ __launch_bounds__(64 * C::NW, 1) void lstm_bwd_ring_bf16(FusedBwdArgs
       }
       fr[n % C::NB].f = *reinterpret_cast<const f32x4*>(ap[n % C::SLOT_KS] + ((n / C::SLOT_KS) % C::SLOTS) * C::SLOT_ELEMS);
       if constexpr (q == 0) row_offsets_issue(m0 + 32 * RG);
-      wb_static_for<0, NCT>([&](auto ct_c) {
+      static_for<0, NCT>([&](auto ct_c) {
         constexpr int p = 2 * q + decltype(ct_c)::value;
         mfma(q_c, ct_c, fr[q % C::NB].b);
-        if constexpr (!(abl & 1)) wb_static_for<C::stage_begin(p), C::stage_begin(p + 1)>([&](auto st_c) { run_stage(st_c, inP); });
+        if constexpr (!(abl & 1)) static_for<C::stage_begin(p), C::stage_begin(p + 1)>([&](auto st_c) { run_stage(st_c, inP); });
       });
     });
     // the tile's partial sums -> LDS.  First barrier: every wave has read the previous tile's partials (its stages 0, 1
@@ -509,8 +493,8 @@ __global__ __launch_bounds__(64 * C::NW, 1) void lstm_bwd_ring_bf16(FusedBwdArgs
   };
   // the last tile's gate gradient, nothing to hide behind
   auto finish = [&](const RingIn& inP, int m0p) {
-    wb_static_for<0, C::NSTAGES>([&](auto st_c) { run_stage(st_c, inP); });
-    wb_static_for<0, 6>([&](auto n_c) { epi_store(n_c, m0p); });
+    static_for<0, C::NSTAGES>([&](auto st_c) { run_stage(st_c, inP); });
+    static_for<0, 6>([&](auto n_c) { epi_store(n_c, m0p); });
     wait_vmcnt<0>();  // the ring's trailing DMA pieces must not outlive the workgroup's LDS allocation
   };
 
@@ -527,7 +511,7 @@ __global__ __launch_bounds__(64 * C::NW, 1) void lstm_bwd_ring_bf16(FusedBwdArgs
   row_offsets_issue(32 * rg);  // the first tile's
   epi_pair(std::integral_constant<int, 1>{}, inB, m0_none, m0_none);
   asm volatile("" ::: "memory");
-  wb_static_for<2, 8>([&](auto s_c) {
+  static_for<2, 8>([&](auto s_c) {
     constexpr int s = decltype(s_c)::value;
     issue_dma(std::integral_constant<int, s - 2>{}, 0);
     epi_pair(s_c, inB, m0_none, m0_none);
@@ -555,27 +539,6 @@ __global__ __launch_bounds__(64 * C::NW, 1) void lstm_bwd_ring_bf16(FusedBwdArgs
 }
 
 // ------------------------------------------------------------------------------------------------------- host ----
-static int wbwd_cus() {
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  return cus;
-}
-
-template <class C>
-static void launch_wbwd(const FusedBwdArgs& a, int rows, hipStream_t s) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_bwd_wreg_bf16<C>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            C::LDS_BYTES);
-  int rg = wbwd_cus() / (2 * C::CB);
-  rg = rg / 4 * 4;
-  if (rg < 4) rg = 4;
-  const int tiles = (rows + 31) / 32;
-  while (rg > 4 && rg - 4 >= tiles) rg -= 4;
-  hipLaunchKernelGGL(lstm_bwd_wreg_bf16<C>, dim3(2 * rg * C::CB), dim3(64 * C::NW), C::LDS_BYTES, s, a, rg);
-}
-
 // Steps with at most this many rows (the host's count of active sequences when it has one, else the call's B) run here:
 // dz_{t+1} crosses L2 -> CU once per column block, which the tiled kernel's 256-row tiles do d/256 times only.
 #ifndef FVTA_WBWD_MAX_ROWS
@@ -587,15 +550,9 @@ constexpr int WBWD_MAX_ROWS = FVTA_WBWD_MAX_ROWS;
 static bool launch_bwd_ring(const FusedBwdArgs& a, int rows, hipStream_t s) {
   typedef RingCfg C;
   if (a.d != C::D || (size_t)(a.B + 4096) * C::K * 2 >= (1ull << 31)) return false;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_bwd_ring_bf16<C>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            C::LDS_BYTES);
-  int rg = wbwd_cus() / (2 * C::CB);
-  rg = rg / 4 * 4;
-  if (rg < 4) rg = 4;
-  if (rg > 32) rg = 32;  // (row tiles past the end are addressed up to 2 rg tiles beyond B: the 4096-row margin above)
-  const int tiles = (rows + 31) / 32;
-  while (rg > 4 && rg - 4 >= tiles) rg -= 4;
-  hipLaunchKernelGGL(lstm_bwd_ring_bf16<C>, dim3(2 * rg * C::CB), dim3(64 * C::NW), C::LDS_BYTES, s, a, rg);
+  auto* k = lstm_bwd_ring_bf16<C>;
+  const int rg = wreg_row_groups(C::CB, (rows + 31) / 32, 32);  // (row tiles past the end are addressed up to 2 rg tiles beyond B: the 4096-row margin above)
+  lstm_launch(k, dim3(2 * rg * C::CB), dim3(64 * C::NW), C::LDS_BYTES, s, a, rg);
   return true;
 }
 
@@ -621,10 +578,15 @@ bool launch_bwd_wreg(const FusedBwdArgs& a, hipStream_t s) {
   }
   if (!(wreg_mode() & 2)) return false;
   if (rows > WBWD_MAX_ROWS) return false;
-  if (a.d == 512) launch_wbwd<WbwdCfg<32, 2>>(a, rows > 0 ? rows : 1, s);
-  else if (a.d == 1024) launch_wbwd<WbwdCfg<64, 1>>(a, rows > 0 ? rows : 1, s);
-  else if (a.d == 128) launch_wbwd<WbwdCfg<8, 2>>(a, rows > 0 ? rows : 1, s);
-  else return false;
+  auto row = [&](auto c) {  // the built WbwdCfg<d / 16, NCT>: one per hidden size
+    typedef decltype(c) C;
+    if (C::D != a.d) return false;
+    auto* k = lstm_bwd_wreg_bf16<C>;
+    const int rg = wreg_row_groups(C::CB, ((rows > 0 ? rows : 1) + 31) / 32);
+    lstm_launch(k, dim3(2 * rg * C::CB), dim3(64 * C::NW), C::LDS_BYTES, s, a, rg);
+    return true;
+  };
+  if (!(row(WbwdCfg<32, 2>{}) || row(WbwdCfg<64, 1>{}) || row(WbwdCfg<8, 2>{}))) return false;
   if (a.B > 64) ++g_bwd_step_counts[2];
   return true;
 }

@@ -32,8 +32,8 @@ def _dx_row_error(dx, ref):
 
 
 def _split_bwd_tiles(B, d, hint=None):
-    """The split engine's backward step tile for each step, restating launch_bwd_fused_xm (csrc/lstm_bf16.hip:471-516;
-    launch_bwd_wreg never takes XM = 2, lstm_wreg_bwd.hip:612).  hint: the host's active rows per step (None: unknown,
+    """The split engine's backward step tile for each step, restating launch_bwd_fused_xm (csrc/lstm_bf16.hip;
+    launch_bwd_wreg, lstm_wreg_bwd.hip, never takes XM = 2).  hint: the host's active rows per step (None: unknown,
     the launcher sizes by B).  -> one of "photo", "w1m1", "w1m2", "t224" (<2,4,2,64,2,56>), "t256" (<2,4,2,64,2>),
     "t1x4" (<1,4,2,64,2>) per step -- so that a change of the heuristics moves no case silently onto another kernel."""
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -99,7 +99,12 @@ def test_mfma_split_engine_gemm_layouts(layout, shape):
 # (shapes 3-6 run the weights-in-registers forward step kernel, csrc/lstm_wreg.hip: in_i / d = 128 / 128,
 #  224 / 512, 224 / 512 with separate fw / bw kernels, 32 / 128 with a ragged tail tile; the first two the tiled one.
 #  Every d = 512 shape runs the pipelined backward step lstm_bwd_ring_bf16; the last two give its workgroups two and
-#  three row tiles each -- both exits of the loop unrolled by two -- with a ragged / a dense tail)
+#  three row tiles each -- both exits of the loop unrolled by two -- with a ragged / a dense tail.
+#  The built rows of the weights-stationary shape tables and the cases that run them -- forward, WregCfg<in_i / 16, d / 16,
+#  NCT>: <14,32,2> (64,30,200,512) and every other din = 200, d = 512 case; <8,32,2> (1030,3,100,512); <14,64,1>
+#  (70,3,200,1024); <8,64,1> (40,3,100,1024); <8,8,2> (130,7,104,128); <2,8,2> (33,5,12,128).  Backward of steps with few
+#  rows, WbwdCfg<d / 16, NCT>: <64,1> the two d = 1024 cases, <8,2> the two d = 128 cases; <32,2> (d = 512) stands behind
+#  the pipelined kernel and runs under fvta_lstm_kernel_select(3) only: test_bilstm_bf16_backward_step_routing)
 @pytest.mark.parametrize("B,J,din,d,dense,share", [(5, 6, 8, 32, False, True), (300, 9, 16, 64, False, False),
                                                    (130, 7, 104, 128, True, True), (64, 30, 200, 512, False, True),
                                                    (70, 6, 200, 512, False, False), (33, 5, 12, 128, False, True),
@@ -107,7 +112,8 @@ def test_mfma_split_engine_gemm_layouts(layout, shape):
                                                    # more than 8192 active rows per step: the regime bench.py times, i.e.
                                                    # the tiled backward step kernel lstm_bwd_fused_bf16 (dense steps) --
                                                    # and, ragged, its hand-over to the pipelined one below 8192 rows
-                                                   (9000, 3, 200, 512, True, True), (9100, 4, 200, 512, False, True)])
+                                                   (9000, 3, 200, 512, True, True), (9100, 4, 200, 512, False, True),
+                                                   (70, 3, 200, 1024, False, True), (40, 3, 100, 1024, True, False)])
 def test_bilstm_bf16_forward_backward(B, J, din, d, dense, share):
     from fvta_memexqa_amd import ops
     from oracle import fvta_fused as F
@@ -257,7 +263,11 @@ def test_backward_with_host_lengths_hint_is_bitwise_the_same(precision, B, J, di
                                                    (64, 30, 200, 512, False, True), (333, 12, 200, 1024, False, True),
                                                    # the photo cell's regime (<= 64 sequences, input <= 128 wide, d = 512): the
                                                    # backward step and the input gradient on the four-wave 64 x 128 tiles
-                                                   (40, 7, 100, 512, False, True), (64, 40, 100, 512, True, False)])
+                                                   (40, 7, 100, 512, False, True), (64, 40, 100, 512, True, False),
+                                                   # the d = 128 rows of the weights-stationary forward's shape table (the
+                                                   # d = 512 rows: <14,32,1,true> case 5, <8,32,1,true> the two above)
+                                                   (130, 5, 100, 128, True, False),     # WregCfg<8, 8, 1, true>
+                                                   (33, 5, 12, 128, False, True)])      # WregCfg<2, 8, 1, true>
 def test_bilstm_bf16x3_meets_the_fp32_tolerances(B, J, din, d, dense, share):
     """precision = bf16x3: every MFMA operand split in two bf16 terms, three products per GEMM (hi hi + hi lo + lo hi),
     fp32 saved gates -- the bi-LSTM forward and every gradient against autograd of the fp64 oracle at north_star's
@@ -413,6 +423,51 @@ def test_bilstm_bf16_backward_step_kernels_agree(B, J, din, dense):
     for name, a, b in zip(("dx", "dkernel", "dbias"), res["ring"], res["tiled"]):
         err = ((a - b).double().norm() / (b.double().norm() + 1e-30)).item()
         assert err < 2e-3, "%s: pipelined vs tiled backward step differ by %.5f (relative L2)" % (name, err)
+
+
+@pytest.mark.parametrize("B,J,d,expect", [
+    # [tiled, pipelined, round-3 weights-stationary] launches per backward under fvta_lstm_kernel_select(7 / 3 / 1)
+    (100, 3, 128, {7: [0, 0, 3], 3: [0, 0, 3], 1: [3, 0, 0]}),      # WbwdCfg<8, 2>
+    (100, 3, 256, {7: [3, 0, 0], 3: [3, 0, 0], 1: [3, 0, 0]}),      # no weights-stationary kernel is built for d = 256
+    (100, 3, 512, {7: [0, 3, 0], 3: [0, 0, 3], 1: [3, 0, 0]}),      # the pipelined kernel; behind it WbwdCfg<32, 2>
+    (100, 3, 1024, {7: [0, 0, 3], 3: [0, 0, 3], 1: [3, 0, 0]}),     # WbwdCfg<64, 1>
+    (8200, 2, 512, {7: [2, 0, 0]}),                                 # more rows than both limits (8192, 6144): tiled
+])
+def test_bilstm_bf16_backward_step_routing(B, J, d, expect):
+    """Which kernel launch_bwd_wreg / launch_bwd_fused_bf16 hand each backward step to, by hidden size and selection:
+    fvta_lstm_bwd_kernel_counts after one backward of B > 64 sequences (calls of <= 64 are not counted), dense lengths,
+    no host lengths.  The kernels differ in the summation order of dh_rec only (test_bilstm_bf16_backward_step_kernels_agree:
+    2e-3 relative L2), so every selection's gradients are held to the tiled kernel's as well."""
+    import ctypes
+    from fvta_memexqa_amd import _lib, ops
+    lib = _lib.load()
+    din = 8
+    g = torch.Generator().manual_seed(B + J + d)
+    x = torch.randn(B, J, din, generator=g).cuda()
+    lim = (6.0 / (din + 5 * d)) ** 0.5
+    kf = ((torch.rand(din + d, 4 * d, generator=g) * 2 - 1) * lim).cuda()
+    bf = (torch.randn(4 * d, generator=g) * 0.1).cuda()
+    g_out = torch.randn(B, J, 2 * d, generator=g).cuda()
+    out, last, op = ops.bilstm_simple(x, torch.full((B,), J), kf, bf, None, None, training=True, precision=BF16)
+    counts, res = (ctypes.c_int64 * 3)(), {}
+    prev = lib.fvta_lstm_kernel_select(-1)
+    try:
+        for mode in expect:
+            lib.fvta_lstm_kernel_select(mode)
+            dx, dk, db = torch.zeros_like(x), torch.zeros_like(kf), torch.zeros_like(bf)
+            lib.fvta_lstm_bwd_kernel_counts(counts)     # (reading resets the counters)
+            op.backward(x, out, g_out, kf, None, dx, dk, db, None, None)
+            torch.cuda.synchronize()
+            lib.fvta_lstm_bwd_kernel_counts(counts)
+            assert list(counts) == expect[mode], "d = %d, select %d: %r" % (d, mode, list(counts))
+            res[mode] = (dx, dk, db)
+    finally:
+        lib.fvta_lstm_kernel_select(-1 if prev == 7 else prev)
+    for mode in res:
+        if mode != 1 and 1 in res:
+            for name, a, b in zip(("dx", "dkernel", "dbias"), res[mode], res[1]):
+                err = ((a - b).double().norm() / (b.double().norm() + 1e-30)).item()
+                assert err < 2e-3, "%s: select %d vs the tiled backward step differ by %.5f (relative L2)" % (name, mode, err)
 
 
 @pytest.mark.parametrize("precision", [F32, BF16, 2])   # 2: the split-bf16 engine (its dx kernels add: rows zeroed by the library)

@@ -1,16 +1,21 @@
-// Embedding front-end for gfx950: model_v2.py:524-645 (char lookup -> conv1d 52-70 -> concat with the word
-// lookup; photo feature lookup -> image_trans_linear).  SURVEY.md 8f rank 1: the step immediately before the
-// encoders.  Per token the char-CNN is 12 windows x 100 filters x 40 MACs -- 1.6 % of one LSTM step's work -- so
-// this is a gather/scatter problem, not a GEMM: one 128-thread workgroup walks tokens; thread f owns filter f with
-// its 40 weights in registers, the token's W x cdim character embeddings sit in LDS and are read as broadcasts,
-// and the token's row (char part | word part) is written once, straight into the encoder input arena.
+// Token embedding for gfx950: model_v2.py:524-645 (char lookup -> conv1d 52-70 -> concat with the word lookup).  SURVEY.md
+// 8f rank 1: the step immediately before the encoders.  A token's row (char part | word part) is written once, straight
+// into the encoder input arena; the backward leaves the char-CNN gradients in per-workgroup (or per-wave) slabs that
+// embed_bwd_reduce_kernel sums in a fixed order, and adds the trainable word rows by atomics.  Four kernel families:
+//  * general (embed_fwd_general<BIG> / embed_bwd_general<BIG>): a 128-thread workgroup walks tokens, thread f owns filter f.
+//    BIG = false: height * cdim <= 64 and W * cdim <= 1024, filter in registers (forward) / LDS (backward) -- every narrow shape
+//    the wave-per-token kernels do not take, and cwdim == 0 (word rows only).  BIG = true: any deeper window, filter streamed
+//    from L2 -- the tested fallback of the wide kernels (FVTA_EMBED_MFMA=0, wdim > 128, VC > 128, W > 16, cwdim != 100);
+//  * wave per token (embed_fwd_5x8_mfma / embed_bwd_5x8_char / embed_bwd_5x8_filt): the reference's default shape, height 5,
+//    cdim 8, 100 filters, W <= 16, VC <= 256, on the fp32 matrix pipe;
+//  * workgroup per token (embed_fwdw_f16x3 / embed_bwdw_filt_tok / embed_bwdw_char_tok): the published flag set's shape,
+//    height 5, cdim 100, 100 filters, 5 <= W <= 16, wdim <= 128, VC <= 128, on the fp16 / bf16 matrix pipe.
+// The photo-feature transform is image_trans.hip.
 #include "fvta_common.h"
-#include "gemm_f32.h"
 #include "attn_fwd_shared.h"  // split_f16x2: the fp16 (hi, lo') split of an fp32 value
 #ifndef FVTA_EMBW_ABL
-#define FVTA_EMBW_ABL 0   // timing ablations of the wide backward kernels (results garbage): d filt 1 no MFMA, 2 no word-row atomics,
-                          // 4 no character gather, 8 no gradient-row gather; d char_emb 16 no MFMA, 32 no fold / LDS adds, 64 no gathers, 128 no adds;
-                          // forward (f16x3) 256 no k loop, 512 no staging stores, 1024 no barrier
+#define FVTA_EMBW_ABL 0   // timing ablations of the wide forward embed_fwdw_f16x3 (results garbage): 256 no k loop, 512 no staging
+                          // stores, 1024 no barrier (bits 1 .. 128 belonged to the wave-per-(token, slice) backward kernels: gone with them)
 #endif
 
 namespace fvta {
@@ -21,6 +26,14 @@ constexpr int EMB_MAXWC = 1024;   // W * cdim of the register-resident kernels
 constexpr int EMB_BIG_WC = 8192;  // W * cdim of the general kernels (the published flag set: char_emb_size 100)
 constexpr int EMB_MAXVC = 1024;   // char vocabulary (backward's per-workgroup table)
 constexpr int EMB_BWD_BLOCKS = 2048;  // slabs of the backward workspace (one per workgroup, or per wave of the wave-per-token kernels)
+
+// a slab of the backward workspace: [KC * cwdim d filt | cwdim d bias | VC * cdim d char_emb], KC = height * cdim
+struct EmbSlab {
+  size_t bias, chars, floats;  // offsets of the bias and char parts (the filter part is at 0), floats of one slab
+  __host__ __device__ EmbSlab(int KC, int cwdim, int VC, int cdim)  // (kernels of one shape pass their compile-time sizes)
+      : bias((size_t)KC * cwdim), chars(bias + cwdim), floats(chars + (size_t)VC * cdim) {}
+  __host__ __device__ EmbSlab(const fvta_embed_desc& d) : EmbSlab(d.height * d.cdim, d.cwdim, d.VC, d.cdim) {}
+};
 
 struct EmbArgs {
   fvta_embed_desc d;
@@ -37,7 +50,7 @@ struct EmbArgs {
   // backward
   const float* dx;
   float* d_word_emb;
-  float* slab;  // [blocks][KC*cwdim + cwdim + VC*cdim]
+  float* slab;  // [blocks] EmbSlab
   // conv1d's dropout of the gathered char embeddings while training (model_v2.py:58-62): element (tok, pos, c) of the
   // [ntok, W, cdim] block is kept by the hash of (seed, (tok * W + pos) * cdim + c) and scaled by 1 / keep_prob; thr 0 = off
   unsigned long long drop_thr, drop_seed;
@@ -48,30 +61,81 @@ __device__ __forceinline__ float emb_ks(const EmbArgs& a, int tok, int i, int WC
   if (a.drop_thr == 0ull) return 1.f;
   return dropout_keep(a.drop_seed, (unsigned long long)tok * WC + i, a.drop_thr) ? a.drop_scale : 0.f;
 }
-static inline void emb_set_dropout(EmbArgs& a, const fvta_embed_desc* d) {
+// the arguments every launch shares (the caller fills in its own tables, outputs and gradients)
+static inline EmbArgs emb_args(const fvta_embed_desc* d, const int32_t* word_ids, const int32_t* char_ids, const int64_t* tok_off,
+                               const float* char_emb, const float* filt, const uint8_t* argpos) {
+  EmbArgs a{};
+  a.d = *d;
+  a.word_ids = word_ids; a.char_ids = char_ids; a.tok_off = tok_off;
+  a.char_emb = char_emb; a.filt = filt; a.argpos = const_cast<uint8_t*>(argpos);
   a.drop_thr = (d->keep_prob > 0.f && d->keep_prob < 1.f) ? dropout_thr(d->keep_prob) : 0ull;
   a.drop_seed = d->dropout_seed;
   a.drop_scale = a.drop_thr ? 1.0f / d->keep_prob : 1.f;
+  return a;
 }
 
-__global__ __launch_bounds__(EMB_NT) void embed_fwd_kernel(EmbArgs a) {
-  __shared__ float s_E[EMB_MAXWC];
+// ---- what the kernels below share ------------------------------------------------------------------------------------
+// The matrix-pipe kernels sit at the edge of their register budgets (embed_bwdw_filt_tok 256 VGPRs, embed_bwdw_char_tok 248,
+// embed_fwd_5x8_mfma 168 = its launch bound), and their schedules move with the spelling of the source: each of them uses a
+// helper from here only where its instruction stream came out unchanged.  What stays spelled out in them for that reason: the
+// slab address in embed_bwd_5x8_char / _filt and embed_bwdw_filt_tok (int arithmetic there, folded into their stores), the
+// 5 x 8 kernels' per-lane setup and look-ahead loads, the word-row atomics (the matrix-pipe kernels hold the elements in registers),
+// the ReLU / arg-max store of embed_fwdw_f16x3, the four-pair fp16 splits of the wide kernels.
+// this workgroup's (wave's) slab
+__device__ __forceinline__ float* emb_slab(const EmbArgs& a, const EmbSlab& sl, unsigned idx) { return a.slab + (size_t)idx * sl.floats; }
+// a word's row: the trainable table first, then the fixed (pre-trained) one
+__device__ __forceinline__ const float* emb_word_src(const EmbArgs& a, int id) {
+  return id < a.d.VW ? a.word_emb + (size_t)id * a.d.wdim : a.fixed_emb + (size_t)(id - a.d.VW) * a.d.wdim;
+}
+// token index clamped to the last token (look-ahead loads stay branch-free) and hidden from the compiler's uniformity
+// analysis: it would move each freshly loaded id / offset into scalar registers with v_readfirstlane -- behind an
+// s_waitcnt vmcnt(0) in every iteration, a round trip that also drains the prefetch queue
+__device__ __forceinline__ int emb_ctok(const EmbArgs& a, int t) {
+  int c = t < a.d.ntok ? t : a.d.ntok - 1;
+  asm volatile("" : "+v"(c));
+  return c;
+}
+// y = max over the windows + bias -> ReLU; the arg-max position is kept for the active filters only (255: inactive)
+__device__ __forceinline__ void emb_relu_argpos(float best, float bias, int bp, float& y_out, uint8_t& ap_out) {
+  const float y = best + bias;
+  y_out = y > 0.f ? y : 0.f;
+  ap_out = y > 0.f ? (uint8_t)bp : (uint8_t)255;
+}
+// token tok's character block [W][cdim], gathered and dropped, into E (EMB_NT threads)
+__device__ __forceinline__ void emb_gather_block(const EmbArgs& a, int tok, int tid, float* E) {
+  const fvta_embed_desc& d = a.d;
+  const int WC = d.W * d.cdim;
+  for (int i = tid; i < WC; i += EMB_NT)
+    E[i] = a.char_emb[(size_t)a.char_ids[(size_t)tok * d.W + i / d.cdim] * d.cdim + i % d.cdim] * emb_ks(a, tok, i, WC);
+}
+
+// ---- general shapes: one 128-thread workgroup walks tokens, thread f owns filter f; the token's W x cdim character
+// embeddings sit in LDS and are read as broadcasts.  Per token the default char-CNN is 12 windows x 100 filters x 40 MACs --
+// 1.6 % of one LSTM step's work -- so this is a gather/scatter problem, not a GEMM.
+// BIG = false: the filter's height * cdim <= EMB_MAXKC weights in registers; also the cwdim == 0 path (word rows only).
+// BIG = true (any height * cdim, W * cdim <= EMB_BIG_WC): correct and order-fixed, not fast -- the filter does not fit
+// registers or LDS, so it is streamed from L2 (coalesced over the filter index); dynamic LDS E [W * cdim].
+template <bool BIG>
+__global__ __launch_bounds__(EMB_NT) void embed_fwd_general(EmbArgs a) {
+  __shared__ float s_Es[BIG ? 1 : EMB_MAXWC];
+  extern __shared__ float s_dyn[];
   const fvta_embed_desc& d = a.d;
   const int tid = threadIdx.x;
   const int KC = d.height * d.cdim, P = d.W - d.height + 1;
-  float wf[EMB_MAXKC];
+  float* s_E = BIG ? s_dyn : s_Es;
+  float wf[BIG ? 1 : EMB_MAXKC];
   float bf = 0.f;
   if (tid < d.cwdim) {
+    if constexpr (!BIG)
 #pragma unroll
-    for (int i = 0; i < EMB_MAXKC; ++i) wf[i] = i < KC ? a.filt[(size_t)i * d.cwdim + tid] : 0.f;
+      for (int i = 0; i < EMB_MAXKC; ++i) wf[i] = i < KC ? a.filt[(size_t)i * d.cwdim + tid] : 0.f;
     bf = a.bias[tid];
   }
   for (int tok = blockIdx.x; tok < d.ntok; tok += gridDim.x) {
     float* row = a.x + a.tok_off[tok];
-    if (d.cwdim > 0) {
+    if (BIG || d.cwdim > 0) {
       __syncthreads();  // the previous token's readers of s_E are done
-      for (int i = tid; i < d.W * d.cdim; i += EMB_NT)
-        s_E[i] = a.char_emb[(size_t)a.char_ids[(size_t)tok * d.W + i / d.cdim] * d.cdim + i % d.cdim] * emb_ks(a, tok, i, d.W * d.cdim);
+      emb_gather_block(a, tok, tid, s_E);
       __syncthreads();
       if (tid < d.cwdim) {
         float best = -INFINITY;
@@ -79,56 +143,66 @@ __global__ __launch_bounds__(EMB_NT) void embed_fwd_kernel(EmbArgs a) {
         for (int p = 0; p < P; ++p) {
           const float* e = s_E + p * d.cdim;  // the window's height*cdim values are contiguous
           float v = 0.f;
+          if constexpr (BIG) {
+            for (int i = 0; i < KC; ++i) v += e[i] * a.filt[(size_t)i * d.cwdim + tid];
+          } else {
 #pragma unroll
-          for (int i = 0; i < EMB_MAXKC; ++i)
-            if (i < KC) v += e[i] * wf[i];
+            for (int i = 0; i < EMB_MAXKC; ++i)
+              if (i < KC) v += e[i] * wf[i];
+          }
           if (v > best) {  // first arg-max
             best = v;
             bp = p;
           }
         }
-        const float y = best + bf;
-        row[tid] = y > 0.f ? y : 0.f;
-        a.argpos[(size_t)tok * d.cwdim + tid] = y > 0.f ? (uint8_t)bp : (uint8_t)255;
+        emb_relu_argpos(best, bf, bp, row[tid], a.argpos[(size_t)tok * d.cwdim + tid]);
       }
     }
-    const int id = a.word_ids[tok];
-    const float* src = id < d.VW ? a.word_emb + (size_t)id * d.wdim : a.fixed_emb + (size_t)(id - d.VW) * d.wdim;
+    const float* src = emb_word_src(a, a.word_ids[tok]);
     for (int i = tid; i < d.wdim; i += EMB_NT) row[d.cwdim + i] = src[i];
   }
 }
 
-// gradients of the char-CNN parameters per workgroup (fixed token order), word rows by atomics
-__global__ __launch_bounds__(EMB_NT) void embed_bwd_kernel(EmbArgs a) {
-  __shared__ float s_E[EMB_MAXWC], s_dE[EMB_MAXWC];
+// gradients of the char-CNN parameters per workgroup (fixed token order), word rows by atomics.
+// BIG = false: partial d filt / d bias in registers, filter and char table dC in dynamic LDS (filt [KC][cwdim], then
+// dC [VC][cdim]), written to the slab at the end.  BIG = true: the slab of this workgroup is zeroed by the launcher and
+// accumulated in place by the owner threads of its columns, the filter is streamed; dynamic LDS E [W*cdim], dE [W*cdim].
+template <bool BIG>
+__global__ __launch_bounds__(EMB_NT) void embed_bwd_general(EmbArgs a) {
+  __shared__ float s_EdE[BIG ? 1 : 2 * EMB_MAXWC];
   __shared__ float s_g[EMB_NT];
   __shared__ int s_p[EMB_NT];
   __shared__ int s_ch[64];
-  extern __shared__ float s_dyn[];  // filt [KC][cwdim], then dC [VC][cdim]
+  extern __shared__ float s_dyn[];
   const fvta_embed_desc& d = a.d;
   const int tid = threadIdx.x;
   const int KC = d.height * d.cdim, WC = d.W * d.cdim;
-  float* s_filt = s_dyn;
-  float* s_dC = s_dyn + KC * d.cwdim;
-  float acc[EMB_MAXKC];
-#pragma unroll
-  for (int i = 0; i < EMB_MAXKC; ++i) acc[i] = 0.f;
+  const EmbSlab sl(d);
+  float* slab = emb_slab(a, sl, blockIdx.x);
+  float* s_E = BIG ? s_dyn : s_EdE;
+  float* s_dE = BIG ? s_dyn + WC : s_EdE + EMB_MAXWC;
+  float* s_filt = s_dyn;                 // (!BIG)
+  float* s_dC = s_dyn + KC * d.cwdim;    // (!BIG)
+  float acc[BIG ? 1 : EMB_MAXKC];
   float accb = 0.f;
-  if (d.cwdim > 0) {
-    for (int i = tid; i < KC * d.cwdim; i += EMB_NT) s_filt[i] = a.filt[i];
-    for (int i = tid; i < d.VC * d.cdim; i += EMB_NT) s_dC[i] = 0.f;
+  if constexpr (!BIG) {
+#pragma unroll
+    for (int i = 0; i < EMB_MAXKC; ++i) acc[i] = 0.f;
+    if (d.cwdim > 0) {
+      for (int i = tid; i < KC * d.cwdim; i += EMB_NT) s_filt[i] = a.filt[i];
+      for (int i = tid; i < d.VC * d.cdim; i += EMB_NT) s_dC[i] = 0.f;
+    }
   }
   for (int tok = blockIdx.x; tok < d.ntok; tok += gridDim.x) {
     const float* row = a.dx + a.tok_off[tok];
     const int id = a.word_ids[tok];
-    if (id < d.VW)
+    if (id < d.VW)  // (the fixed rows get no gradient)
       for (int i = tid; i < d.wdim; i += EMB_NT) atomicAdd(a.d_word_emb + (size_t)id * d.wdim + i, row[d.cwdim + i]);
-    if (d.cwdim == 0) continue;
+    if (!BIG && d.cwdim == 0) continue;
     __syncthreads();
     if (tid < d.W) s_ch[tid] = a.char_ids[(size_t)tok * d.W + tid];
-    for (int i = tid; i < WC; i += EMB_NT)
-      s_E[i] = a.char_emb[(size_t)a.char_ids[(size_t)tok * d.W + i / d.cdim] * d.cdim + i % d.cdim] * emb_ks(a, tok, i, WC);
-    float g = 0.f;
+    emb_gather_block(a, tok, tid, s_E);
+    float g = 0.f;  // thread f: the gradient of filter f's output and its arg-max position (inactive filters: 0, 0)
     int p = 0;
     if (tid < d.cwdim) {
       const int ap = a.argpos[(size_t)tok * d.cwdim + tid];
@@ -140,44 +214,51 @@ __global__ __launch_bounds__(EMB_NT) void embed_bwd_kernel(EmbArgs a) {
     s_g[tid] = g;
     s_p[tid] = p;
     __syncthreads();
-    if (tid < d.cwdim) {  // d filt[:, :, f] += g * window(p); d bias[f] += g
-      const float* e = s_E + p * d.cdim;
+    // d filt[:, :, f] += g * window(p); d bias[f] += g
+    const float* e = s_E + p * d.cdim;
+    if constexpr (BIG) {
+      if (tid < d.cwdim && g != 0.f) {  // the owner of filter column f accumulates its slab column
+        slab[sl.bias + tid] += g;
+        for (int i = 0; i < KC; ++i) slab[(size_t)i * d.cwdim + tid] += g * e[i];
+      }
+    } else if (tid < d.cwdim) {
       accb += g;
 #pragma unroll
       for (int i = 0; i < EMB_MAXKC; ++i)
         if (i < KC) acc[i] += g * e[i];
     }
-    // d E[pos][c] = sum_f g_f * filt[pos - p_f][c][f], one thread per (pos, c), f in order (inactive filters carry
-    // g = 0 and p = 0: they only cost the compare)
+    // d E[pos][c] = sum_f g_f * filt[pos - p_f][c][f], one thread per (pos, c), f in order (inactive filters carry g = 0
+    // and p = 0: they only cost the compare)
+    const float* filt = BIG ? a.filt : s_filt;
     for (int i = tid; i < WC; i += EMB_NT) {
       const int pos = i / d.cdim, c = i % d.cdim;
       float v = 0.f;
       for (int f = 0; f < d.cwdim; ++f) {
         const int k = pos - s_p[f];
-        const float g = s_g[f];
-        if (g != 0.f && k >= 0 && k < d.height) v += g * s_filt[(k * d.cdim + c) * d.cwdim + f];
+        const float gf = s_g[f];
+        if (gf != 0.f && k >= 0 && k < d.height) v += gf * filt[(size_t)(k * d.cdim + c) * d.cwdim + f];
       }
       s_dE[i] = v * emb_ks(a, tok, i, WC);  // (dropout: the gradient reaches the table through the kept elements only)
     }
     __syncthreads();
     // into the workgroup's char table: thread c walks the positions serially (two positions may hold the same char)
+    float* dC = BIG ? slab + sl.chars : s_dC;
     if (tid < d.cdim)
-      for (int pos = 0; pos < d.W; ++pos) s_dC[s_ch[pos] * d.cdim + tid] += s_dE[pos * d.cdim + tid];
+      for (int pos = 0; pos < d.W; ++pos) dC[(size_t)s_ch[pos] * d.cdim + tid] += s_dE[pos * d.cdim + tid];
   }
-  if (d.cwdim == 0) return;
+  if (BIG || d.cwdim == 0) return;
   __syncthreads();
-  float* slab = a.slab + (size_t)blockIdx.x * (KC * d.cwdim + d.cwdim + d.VC * d.cdim);
   if (tid < d.cwdim) {
 #pragma unroll
     for (int i = 0; i < EMB_MAXKC; ++i)
       if (i < KC) slab[(size_t)i * d.cwdim + tid] = acc[i];
-    slab[KC * d.cwdim + tid] = accb;
+    slab[sl.bias + tid] = accb;
   }
-  for (int i = tid; i < d.VC * d.cdim; i += EMB_NT) slab[KC * d.cwdim + d.cwdim + i] = s_dC[i];
+  for (int i = tid; i < d.VC * d.cdim; i += EMB_NT) slab[sl.chars + i] = s_dC[i];
 }
 
 // ---- the reference's shape on the matrix pipe: one WAVE per token ------------------------------------------------------
-// The register kernels above spend their time waiting (two to four workgroup barriers and an LDS read-modify-write chain
+// The general kernels above spend their time waiting (two to four workgroup barriers and an LDS read-modify-write chain
 // per token), not computing.  Here a wave owns a token from its ids to its gradients and never meets a workgroup barrier:
 //  * forward: Y[p][f] = sum_kc E[p*8 + kc] filt[kc][f] is a 16 x 40 x CW product on v_mfma_f32_16x16x4_f32 (an exact fmaf
 //    chain per output): rows = window positions (12 of 16 used), the filter fragments live in registers for the whole
@@ -189,9 +270,9 @@ __global__ __launch_bounds__(EMB_NT) void embed_bwd_kernel(EmbArgs a) {
 //    addresses are distinct within an instruction and ordered between instructions (one wave, in-order LDS: a fixed
 //    order), then into the wave's own char-gradient table; d filt stays the sparse form (lane f: 40 FMAs against the
 //    window of ITS arg-max position).  Every wave writes its own slab; embed_bwd_reduce_kernel sums them in order.
-// Word part as in the register kernels.  Shape: height 5, cdim 8, W <= 16, cwdim == CW (a multiple of 4, <= 128).
+// Word part as in the general kernels.  Shape: height 5, cdim 8, W <= 16, cwdim == CW (a multiple of 4, <= 128).
 #ifndef FVTA_EMB_ABL
-#define FVTA_EMB_ABL 0  // timing ablations (tools/r03_build_abl.sh): 1 no MFMA, 2 no LDS adds / no arg-max epilogue, 4 no stores
+#define FVTA_EMB_ABL 0  // timing ablations (SRC=embed MACRO=FVTA_EMB_ABL tools/build_abl.sh): 1 no MFMA, 2 no LDS adds / no arg-max epilogue, 4 no stores
 #endif
 template <int CW>
 struct Emb5x8 {
@@ -250,16 +331,13 @@ __global__ __launch_bounds__(256, 3) void embed_fwd_5x8_mfma(EmbArgs a) {
     wid = a.word_ids[t];
     off = a.tok_off[t];
   };
-  auto word_src = [&](int wid) {
-    return wid < d.VW ? a.word_emb + (size_t)wid * d.wdim : a.fixed_emb + (size_t)(wid - d.VW) * d.wdim;
-  };
   auto stage = [&](float* E, int tok, int cA, int cB) {
     E[lane] = pos < W ? s_dyn[cA * 8 + c] * emb_ks(a, tok, lane, W * 8) : 0.f;
     E[64 + lane] = pos + 8 < W ? s_dyn[cB * 8 + c] * emb_ks(a, tok, 64 + lane, W * 8) : 0.f;
   };
   auto product = [&](const float* E, f32x4 (&acc)[C::NCF]) {
 #pragma unroll
-    for (int ct = 0; ct < C::NCF; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ct = 0; ct < C::NCF; ++ct) acc[ct] = zero4();
 #pragma unroll
     for (int ks = 0; ks < 10; ++ks) {
       const float av = E[j * 8 + 4 * ks + q];
@@ -301,9 +379,7 @@ __global__ __launch_bounds__(256, 3) void embed_fwd_5x8_mfma(EmbArgs a) {
       }
       const int f = 16 * ct + j;
       const int slot = (q == 0 && f < CW) ? f : 112 + j;
-      const float y = best + s_bias[16 * ct + j];
-      s_Y[wv][slot] = y > 0.f ? y : 0.f;
-      s_A[wv][slot] = y > 0.f ? (uint8_t)bp : (uint8_t)255;
+      emb_relu_argpos(best, s_bias[16 * ct + j], bp, s_Y[wv][slot], s_A[wv][slot]);
     }
     if constexpr (FVTA_EMB_ABL & 4) {
       float t = 0.f;
@@ -323,7 +399,7 @@ __global__ __launch_bounds__(256, 3) void embed_fwd_5x8_mfma(EmbArgs a) {
     if (lane < d.wdim) row[CW + lane] = w0;
     if (lane + 64 < d.wdim) row[CW + 64 + lane] = w1;
     if (d.wdim > 128) {
-      const float* src = word_src(wid);
+      const float* src = emb_word_src(a, wid);
       for (int i = lane + 128; i < d.wdim; i += 64) row[CW + i] = src[i];
     }
   };
@@ -334,7 +410,7 @@ __global__ __launch_bounds__(256, 3) void embed_fwd_5x8_mfma(EmbArgs a) {
   load_ids(tok + step, cA1, cB1, wid1, off1);
   for (; tok < d.ntok; tok += step) {
     load_ids(tok + 2 * step, cA2, cB2, wid2, off2);
-    const float w0 = word_src(wid0)[wl0], w1 = word_src(wid0)[wl1];  // stored after the product
+    const float w0 = emb_word_src(a, wid0)[wl0], w1 = emb_word_src(a, wid0)[wl1];  // stored after the product
     stage(s_E[wv], tok, cA0, cB0);
     wave_lds_fence();
     f32x4 acc[C::NCF];
@@ -420,7 +496,7 @@ __global__ __launch_bounds__(256, 3) void embed_bwd_5x8_char(EmbArgs a) {
     }
     f32x4 accT[3];
 #pragma unroll
-    for (int ct = 0; ct < 3; ++ct) accT[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ct = 0; ct < 3; ++ct) accT[ct] = zero4();
 #pragma unroll
     for (int v = 0; v < C::GP / 4; ++v) {
       const f32x4 Gv = *reinterpret_cast<const f32x4*>(&s_G[wv][q * C::GP + 4 * v]);
@@ -562,44 +638,6 @@ __global__ __launch_bounds__(256, 2) void embed_bwd_5x8_filt(EmbArgs a) {
   if (has2) slab[40 * CW + 64 + lane] = accb2;
 }
 
-// ---- general shape (any height * cdim, e.g. README.MD:144's --char_emb_size 100: a 500-deep window) ------------
-// Correct and order-fixed, not fast: the filter does not fit registers or LDS, so it is streamed from L2
-// (coalesced over the filter index) and the workgroup's filter-gradient slab is accumulated in global memory by
-// its owner threads.  The reference's default shape never gets here (embed_*_5x8_* below).
-__global__ __launch_bounds__(EMB_NT) void embed_fwd_kernel_big(EmbArgs a) {
-  extern __shared__ float s_dyn[];  // E [W * cdim]
-  const fvta_embed_desc& d = a.d;
-  const int tid = threadIdx.x;
-  const int KC = d.height * d.cdim, P = d.W - d.height + 1, WC = d.W * d.cdim;
-  const float bf = tid < d.cwdim ? a.bias[tid] : 0.f;
-  for (int tok = blockIdx.x; tok < d.ntok; tok += gridDim.x) {
-    float* row = a.x + a.tok_off[tok];
-    __syncthreads();
-    for (int i = tid; i < WC; i += EMB_NT)
-      s_dyn[i] = a.char_emb[(size_t)a.char_ids[(size_t)tok * d.W + i / d.cdim] * d.cdim + i % d.cdim] * emb_ks(a, tok, i, WC);
-    __syncthreads();
-    if (tid < d.cwdim) {
-      float best = -INFINITY;
-      int bp = 0;
-      for (int p = 0; p < P; ++p) {
-        const float* e = s_dyn + p * d.cdim;
-        float v = 0.f;
-        for (int i = 0; i < KC; ++i) v += e[i] * a.filt[(size_t)i * d.cwdim + tid];
-        if (v > best) {
-          best = v;
-          bp = p;
-        }
-      }
-      const float y = best + bf;
-      row[tid] = y > 0.f ? y : 0.f;
-      a.argpos[(size_t)tok * d.cwdim + tid] = y > 0.f ? (uint8_t)bp : (uint8_t)255;
-    }
-    const int id = a.word_ids[tok];
-    const float* src = id < d.VW ? a.word_emb + (size_t)id * d.wdim : a.fixed_emb + (size_t)(id - d.VW) * d.wdim;
-    for (int i = tid; i < d.wdim; i += EMB_NT) row[d.cwdim + i] = src[i];
-  }
-}
-
 // ---- wide char embeddings on the matrix pipe (README.MD:144's --char_emb_size 100) ----------------------------------
 // With a 500-deep window the convolution IS a GEMM: rows (token, window position p), k = (kh, c) -- the window of
 // position p is the CONTIGUOUS slice E[tok][p*cdim .. p*cdim + height*cdim) of the token's character block -- columns
@@ -608,16 +646,16 @@ __global__ __launch_bounds__(EMB_NT) void embed_fwd_kernel_big(EmbArgs a) {
 // value x = hi + 2^-11 lo' (hi = rtz_f16(x), lo' = f16((x - hi) 2^11)), product = hi hi + 2^-11 (hi lo' + lo' hi): three
 // v_mfma_f32_16x16x32_f16 (16 cycles each) per 32 k instead of eight v_mfma_f32_16x16x4_f32 (32 cycles each), <= 3 2^-22
 // |E| |filt| per product -- the fp32 kernel's own rounding is 2^-24 per product.  One workgroup = SEVEN waves = the seven
-// 16-filter slices: the token's character block is gathered, dropped and split ONCE (the wave-per-(token, slice) form above
+// 16-filter slices: the token's character block is gathered, dropped and split ONCE (the earlier wave-per-(token, slice) form
 // re-staged it seven times: 45 KB of L2 reads per token), double-buffered in LDS as two fp16 arrays, and every wave multiplies
 // it with its slice's filter fragments (2 x 64 registers, resident for the whole launch).  A[p][kc] = E[p CD + kc]: the
-// windows overlap in memory, a lane's 8 consecutive k are 16 contiguous bytes of the block.  8.4 -> see DESIGN.md ms at the
+// windows overlap in memory, a lane's 8 consecutive k are 16 contiguous bytes of the block.  8.4 -> 2.6 ms at the
 // published flag set's 394 k tokens.  grid (blocks), 448 threads.
-template <int CW, int CD, int SPW>  // SPW: 16-filter slices per wave
-__global__ __launch_bounds__(64 * ((((CW + 15) / 16) + SPW - 1) / SPW), 1) void embed_fwdw_f16x3(EmbArgs a) {
+template <int CW, int CD>
+__global__ __launch_bounds__(64 * ((CW + 15) / 16), 1) void embed_fwdw_f16x3(EmbArgs a) {
   constexpr int KC = 5 * CD, NKS = (KC + 31) / 32;            // k-steps of 32
   constexpr int EB = 15 * CD + 32 * NKS, EBP = (EB + 7) / 8 * 8;  // halves of a staged block (the last window's reach)
-  constexpr int NS = (CW + 15) / 16, NWV = (NS + SPW - 1) / SPW, NT = 64 * NWV;  // filter slices, waves, threads
+  constexpr int NS = (CW + 15) / 16, NT = 64 * NS;            // filter slices = waves, threads
   constexpr int NU = 16 * CD / 4, NL = (NU + NT - 1) / NT;    // 16-byte pieces of a character block, pieces per thread
   static_assert(CD % 4 == 0, "character rows are read 16 bytes at a time");
   __shared__ __attribute__((aligned(16))) _Float16 s_hi[2][EBP], s_lo[2][EBP];
@@ -626,32 +664,27 @@ __global__ __launch_bounds__(64 * ((((CW + 15) / 16) + SPW - 1) / SPW), 1) void 
   const int j = lane & 15, q = lane >> 4;
   const int W = d.W, P = W - 4;
   // the wave's filter fragments: B[k = 32 ks + 8 q + e][n = j] = filt[k][f] (k >= KC, f >= CW: zero)
-  half8 Bh[SPW][NKS], Bl[SPW][NKS];
-  float bias[SPW];
+  half8 Bh[NKS], Bl[NKS];
+  const int f = wv * 16 + j, fc = f < CW ? f : CW - 1;
 #pragma unroll
-  for (int sl = 0; sl < SPW; ++sl) {
-    const int f = (wv * SPW + sl) * 16 + j, fc = f < CW ? f : CW - 1;
+  for (int ks = 0; ks < NKS; ++ks) {
+    half2v h[4], l[4];
 #pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      half2v h[4], l[4];
-#pragma unroll
-      for (int e2 = 0; e2 < 4; ++e2) {
-        // (unconditional loads of clamped addresses, then a select: under a branch each of the loads was its own round trip)
-        const int k0 = 32 * ks + 8 * q + 2 * e2;
-        const float y0 = a.filt[(size_t)(k0 < KC ? k0 : KC - 1) * CW + fc], y1 = a.filt[(size_t)(k0 + 1 < KC ? k0 + 1 : KC - 1) * CW + fc];
-        const float x0 = (k0 < KC && f < CW) ? y0 : 0.f, x1 = (k0 + 1 < KC && f < CW) ? y1 : 0.f;
-        split_f16x2(x0, x1, h[e2], l[e2]);
-      }
-      Bh[sl][ks] = cat_h2(h[0], h[1], h[2], h[3]);
-      Bl[sl][ks] = cat_h2(l[0], l[1], l[2], l[3]);
+    for (int e2 = 0; e2 < 4; ++e2) {
+      // (unconditional loads of clamped addresses, then a select: under a branch each of the loads was its own round trip)
+      const int k0 = 32 * ks + 8 * q + 2 * e2;
+      const float y0 = a.filt[(size_t)(k0 < KC ? k0 : KC - 1) * CW + fc], y1 = a.filt[(size_t)(k0 + 1 < KC ? k0 + 1 : KC - 1) * CW + fc];
+      const float x0 = (k0 < KC && f < CW) ? y0 : 0.f, x1 = (k0 + 1 < KC && f < CW) ? y1 : 0.f;
+      split_f16x2(x0, x1, h[e2], l[e2]);
     }
-    bias[sl] = a.bias[fc];
+    Bh[ks] = cat_h2(h[0], h[1], h[2], h[3]);
+    Bl[ks] = cat_h2(l[0], l[1], l[2], l[3]);
   }
+  const float bias = a.bias[fc];
   for (int i = tid; i < 2 * EBP; i += NT) {  // (positions >= W and the reach beyond the block stay zero)
     (&s_hi[0][0])[i] = (_Float16)0.f;
     (&s_lo[0][0])[i] = (_Float16)0.f;
   }
-  auto word_src = [&](int id) { return id < d.VW ? a.word_emb + (size_t)id * d.wdim : a.fixed_emb + (size_t)(id - d.VW) * d.wdim; };
   // piece u = tid + NT i: four channels of one character (clamped token and position: branch-free)
   int pos[NL], c4[NL], posc[NL];
   bool stager[NL];
@@ -707,13 +740,8 @@ __global__ __launch_bounds__(64 * ((((CW + 15) / 16) + SPW - 1) / SPW), 1) void 
   Ids cid_n = load_id(tok + (PD + 1) * step);  // (the ids one more token ahead of the rows they address)
   // the token's row address and word id travel PD tokens ahead too, the word's row (element tid) one token ahead: left to
   // the token's own iteration, the word copy was two dependent round trips that every wave waited for at the barrier
-  // (the index is hidden from the compiler's uniformity analysis: it would move each freshly loaded id / offset into scalar
-  //  registers with v_readfirstlane -- behind an s_waitcnt vmcnt(0) in every iteration, a round trip that also drains the gather)
-  auto ctok = [&](int t) {
-    int c = t < d.ntok ? t : d.ntok - 1;
-    asm volatile("" : "+v"(c));
-    return c;
-  };
+  // (the index is hidden from the compiler's uniformity analysis: emb_ctok)
+  auto ctok = [&](int t) { return emb_ctok(a, t); };
   int64_t off_q[PD + 1];
   int wid_q[PD + 1];
 #pragma unroll
@@ -722,7 +750,7 @@ __global__ __launch_bounds__(64 * ((((CW + 15) / 16) + SPW - 1) / SPW), 1) void 
     wid_q[i] = a.word_ids[ctok(tok + i * step)];
   }
   const int wcol = tid < d.wdim ? tid : 0;
-  float w_cur = word_src(wid_q[0])[wcol];
+  float w_cur = emb_word_src(a, wid_q[0])[wcol];
   __syncthreads();
   for (int it = 0; tok < d.ntok; tok += step, ++it) {
     const int buf = it & 1;
@@ -736,56 +764,48 @@ __global__ __launch_bounds__(64 * ((((CW + 15) / 16) + SPW - 1) / SPW), 1) void 
     cid_n = load_id(tok + (PD + 2) * step);
     off_q[PD] = a.tok_off[ctok(tok + (PD + 1) * step)];
     wid_q[PD] = a.word_ids[ctok(tok + (PD + 1) * step)];
-    const float w_nxt = word_src(wid_q[0])[wcol];
-    f32x4 acc[SPW][3];  // (three independent chains per slice: hi hi, hi lo', lo' hi)
-#pragma unroll
-    for (int sl = 0; sl < SPW; ++sl) acc[sl][0] = acc[sl][1] = acc[sl][2] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float w_nxt = emb_word_src(a, wid_q[0])[wcol];
+    f32x4 acc[3];  // (three independent chains: hi hi, hi lo', lo' hi)
+    acc[0] = acc[1] = acc[2] = zero4();
     const _Float16* ah = &s_hi[buf][j * CD + 8 * q];  // window position p = j
     const _Float16* al = &s_lo[buf][j * CD + 8 * q];
 #pragma unroll
     for (int ks = 0; ks < ((FVTA_EMBW_ABL & 256) ? 0 : NKS); ++ks) {
-      // (8-byte aligned: 2 (100 p + 32 ks + 8 q) bytes); ONE read of the A fragments feeds the wave's SPW slices
+      // (8-byte aligned: 2 (100 p + 32 ks + 8 q) bytes)
       const half4v h0 = *reinterpret_cast<const half4v*>(ah + 32 * ks), h1 = *reinterpret_cast<const half4v*>(ah + 32 * ks + 4);
       const half4v l0 = *reinterpret_cast<const half4v*>(al + 32 * ks), l1 = *reinterpret_cast<const half4v*>(al + 32 * ks + 4);
       const half8 Ah = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7), Al = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
-#pragma unroll
-      for (int sl = 0; sl < SPW; ++sl) {
-        // (a slice past the last filter multiplies zeros: a wave-uniform skip here would cut the unrolled loop into blocks)
-        acc[sl][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bh[sl][ks], acc[sl][0], 0, 0, 0);
-        acc[sl][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bl[sl][ks], acc[sl][1], 0, 0, 0);
-        acc[sl][2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, Bh[sl][ks], acc[sl][2], 0, 0, 0);
-      }
+      // (the last slice's filters past CW multiply zeros: a wave-uniform skip here would cut the unrolled loop into blocks)
+      acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bh[ks], acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bl[ks], acc[1], 0, 0, 0);
+      acc[2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, Bh[ks], acc[2], 0, 0, 0);
     }
     float* row = a.x + off;
+    // D[p = 4 q + r][f = j]: max / FIRST arg-max over the valid positions
+    float best = -INFINITY;
+    int bp = 0;
 #pragma unroll
-    for (int sl = 0; sl < SPW; ++sl) {
-      const int f = (wv * SPW + sl) * 16 + j;
-      // D[p = 4 q + r][f = j]: max / FIRST arg-max over the valid positions
-      float best = -INFINITY;
-      int bp = 0;
+    for (int r = 0; r < 4; ++r) {
+      const float v = acc[0][r] + (acc[1][r] + acc[2][r]) * (1.f / 2048.f);
+      const int p = 4 * q + r;
+      if (p < P && v > best) {
+        best = v;
+        bp = p;
+      }
+    }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float v = acc[sl][0][r] + (acc[sl][1][r] + acc[sl][2][r]) * (1.f / 2048.f);
-        const int p = 4 * q + r;
-        if (p < P && v > best) {
-          best = v;
-          bp = p;
-        }
+    for (int sh = 16; sh <= 32; sh <<= 1) {
+      const float ob = __shfl_xor(best, sh, 64);
+      const int op = __shfl_xor(bp, sh, 64);
+      if (ob > best || (ob == best && op < bp)) {
+        best = ob;
+        bp = op;
       }
-#pragma unroll
-      for (int sh = 16; sh <= 32; sh <<= 1) {
-        const float ob = __shfl_xor(best, sh, 64);
-        const int op = __shfl_xor(bp, sh, 64);
-        if (ob > best || (ob == best && op < bp)) {
-          best = ob;
-          bp = op;
-        }
-      }
-      if (q == 0 && f < CW) {
-        const float y = best + bias[sl];
-        row[f] = y > 0.f ? y : 0.f;
-        a.argpos[(size_t)tok * CW + f] = y > 0.f ? (uint8_t)bp : (uint8_t)255;
-      }
+    }
+    if (q == 0 && f < CW) {
+      const float y = best + bias;
+      row[f] = y > 0.f ? y : 0.f;
+      a.argpos[(size_t)tok * CW + f] = y > 0.f ? (uint8_t)bp : (uint8_t)255;
     }
     if (tid < d.wdim) row[CW + tid] = w_cur;  // the word part of the row (wdim <= threads: the launcher's condition -- a copy
                                               // loop here made the compiler drain every prefetch at the end of each token)
@@ -794,13 +814,7 @@ __global__ __launch_bounds__(64 * ((((CW + 15) / 16) + SPW - 1) / SPW), 1) void 
     if constexpr (!(FVTA_EMBW_ABL & 1024)) __syncthreads();
   }
 }
-template __global__ void embed_fwdw_f16x3<100, 100, 1>(EmbArgs);
-template __global__ void embed_fwdw_f16x3<100, 100, 2>(EmbArgs);
-
-#ifndef FVTA_EMBW_SPW
-#define FVTA_EMBW_SPW 1     // filter slices per wave of embed_fwdw_f16x3: 1 = seven waves (2.6 ms at the published flag set), 2 = four
-                            // waves with half the LDS reads but one wave per SIMD (3.3 ms: the kernel is not LDS-bound)
-#endif
+template __global__ void embed_fwdw_f16x3<100, 100>(EmbArgs);
 
 // d filt / d bias of the wide shape, a WORKGROUP per token (round 4's form ran a wave per (token, slice): seven
 // waves somewhere on the chip each gather the token's gradient row, arg-max positions and their 16 channels of its characters --
@@ -811,14 +825,14 @@ template __global__ void embed_fwdw_f16x3<100, 100, 2>(EmbArgs);
 // 5 x 7 x 3 v_mfma_f32_16x16x4_f32 per token as before, exact -- and keeps its 80 x 112 accumulator tile for the whole launch;
 // no reduction across waves at the end (a slice belongs to one wave).  grid (blocks <= 256), 448 threads, slab part
 // [0, KC cw + cw) of block x.
-// X3: the product on the bf16 matrix pipe with a three-term split -- x = hi + lo, both bf16 (fp32's exponent range: the low
+// The product runs on the bf16 matrix pipe with a three-term split -- x = hi + lo, both bf16 (fp32's exponent range: the low
 // terms need no scaling), hi hi + hi lo + lo hi into ONE accumulator, ~2^-16 per product (the arg-max positions are inputs
 // here: nothing can flip) -- one k-step of v_mfma_f32_16x16x16_bf16 over the 16 window positions instead of three of
 // v_mfma_f32_16x16x4_f32: 105 x 16 matrix-pipe cycles per token and slice instead of 105 x 32.  The character block and the
 // gradient row are split ONCE, by the threads that stage them, and kept in LDS as packed (hi | lo << 16) words.
-template <int CW, int CD, bool X3>
+template <int CW, int CD>
 __global__ __launch_bounds__(448, 1) void embed_bwdw_filt_tok(EmbArgs a) {
-  constexpr int CS = 16, NMT = 5, NNT = (CW + 15) / 16, NKS = 3, NS = (CD + CS - 1) / CS;
+  constexpr int CS = 16, NMT = 5, NNT = (CW + 15) / 16, NS = (CD + CS - 1) / CS;
   typedef short bf4 __attribute__((ext_vector_type(4)));
   typedef unsigned u2 __attribute__((ext_vector_type(2)));
   auto pack_hl = [](float x) {  // bf16(x) | bf16(x - bf16(x)) << 16, both rounded to nearest
@@ -829,7 +843,7 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_filt_tok(EmbArgs a) {
   constexpr int NU = 16 * CD / 4;                       // 16-byte pieces of a character block
   __shared__ __attribute__((aligned(16))) float s_E[2][20 * CD];  // (positions 16 .. 19 stay zero: the reach of window position 15)
   __shared__ float s_g[2][16 * NNT];
-  __shared__ unsigned s_gx[2][X3 ? 16 * NNT : 1];  // (X3: the gradient row as packed hi | lo)
+  __shared__ unsigned s_gx[2][16 * NNT];  // (the gradient row as packed hi | lo)
   __shared__ int s_ap[2][16 * NNT];
   const fvta_embed_desc& d = a.d;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -840,7 +854,7 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_filt_tok(EmbArgs a) {
 #pragma unroll
   for (int mt = 0; mt < NMT; ++mt)
 #pragma unroll
-    for (int nt = 0; nt < NNT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int nt = 0; nt < NNT; ++nt) acc[mt][nt] = zero4();
   float accb[NNT];
 #pragma unroll
   for (int nt = 0; nt < NNT; ++nt) accb[nt] = 0.f;
@@ -848,25 +862,21 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_filt_tok(EmbArgs a) {
   for (int i = tid; i < 2 * 16 * NNT; i += 448) {
     (&s_g[0][0])[i] = 0.f;
     (&s_ap[0][0])[i] = 255;
-    if constexpr (X3) (&s_gx[0][0])[i] = 0u;
+    (&s_gx[0][0])[i] = 0u;
   }
   // A operand: lane (row l = 16 mt + j = tap mt, channel j; k phase q) reads E[(4 ks + q) + mt][c0 + j]; channels beyond the
   // slice multiply by zero
   const bool a_ok = j < nc;
-  const int a0 = (X3 ? 4 * q : q) * CD + c0 + (a_ok ? j : 0);  // (X3: the lane's four window positions 4 q .. 4 q + 3)
+  const int a0 = 4 * q * CD + c0 + (a_ok ? j : 0);  // (the lane's four window positions 4 q .. 4 q + 3)
   // staging: thread u < NU gathers four channels of one character; thread u < CW one gradient value and its arg-max position
   const int pos = tid / (CD / 4), c4 = tid % (CD / 4);
   const bool stager = tid < NU && pos < W;
   const int posc = pos < W ? pos : W - 1;
   const int fcol = tid < CW ? tid : CW - 1;
-  auto ctok = [&](int t) {  // (hidden from the uniformity analysis: see embed_fwdw_f16x3)
-    int c = t < d.ntok ? t : d.ntok - 1;
-    asm volatile("" : "+v"(c));
-    return c;
-  };
+  auto ctok = [&](int t) { return emb_ctok(a, t); };
   auto load_id = [&](int tok) { return a.char_ids[(size_t)ctok(tok) * W + posc]; };
   auto load_E = [&](int cid) {
-    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 v = zero4();
     if (stager) v = *reinterpret_cast<const f32x4*>(a.char_emb + (size_t)cid * CD + 4 * c4);
     return v;
   };
@@ -879,16 +889,15 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_filt_tok(EmbArgs a) {
 #pragma unroll
         for (int x = 0; x < 4; ++x) v[x] *= emb_ks(a, t, pos * CD + 4 * c4 + x, W * CD);
       }
-      if constexpr (X3)
 #pragma unroll
-        for (int x = 0; x < 4; ++x) v[x] = __uint_as_float(pack_hl(v[x]));
+      for (int x = 0; x < 4; ++x) v[x] = __uint_as_float(pack_hl(v[x]));
       *reinterpret_cast<f32x4*>(&s_E[buf][pos * CD + 4 * c4]) = v;
     }
     if (tid < CW) {
       const float gm = ap == 255 ? 0.f : g;
       s_g[buf][tid] = gm;
       s_ap[buf][tid] = ap;
-      if constexpr (X3) s_gx[buf][tid] = pack_hl(gm);
+      s_gx[buf][tid] = pack_hl(gm);
     }
   };
   const int step = gridDim.x;
@@ -948,7 +957,7 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_filt_tok(EmbArgs a) {
     }
     w0 = w0n, w1 = w1n;
     const float* Es = s_E[buf];
-    if constexpr (X3) {
+    {
       bf4 Bh[NNT], Bl[NNT];
 #pragma unroll
       for (int nt = 0; nt < NNT; ++nt) {
@@ -974,21 +983,6 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_filt_tok(EmbArgs a) {
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(Al, Bh[nt], acc[mt][nt], 0, 0, 0);
         }
       }
-    } else
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      float av[NMT], bv[NNT];
-#pragma unroll
-      for (int mt = 0; mt < NMT; ++mt) {
-        const float v = Es[a0 + (4 * ks + mt) * CD];
-        av[mt] = a_ok ? v : 0.f;
-      }
-#pragma unroll
-      for (int nt = 0; nt < NNT; ++nt) bv[nt] = ap_c[nt] == 4 * ks + q ? g_c[nt] : 0.f;
-#pragma unroll
-      for (int mt = 0; mt < NMT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NNT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
     }
     store_tok(buf ^ 1, e_q[0], g_q[0], ap_q[0], tok + step);  // (that buffer's readers finished before the last barrier)
     __syncthreads();
@@ -1012,7 +1006,7 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_filt_tok(EmbArgs a) {
     for (int nt = 0; nt < NNT; ++nt)
       if (16 * nt + j < CW) slab[(size_t)KC * CW + 16 * nt + j] = accb[nt];
 }
-template __global__ void embed_bwdw_filt_tok<100, 100, true>(EmbArgs);
+template __global__ void embed_bwdw_filt_tok<100, 100>(EmbArgs);
 
 // d char_emb of the wide shape, a WORKGROUP per token, with NO transposed tile, NO 5-tap fold and NO LDS float adds (those three
 // were 3.7 of the wave-per-(token, slice) form's 6.2 ms: -DFVTA_EMBW_ABL).  Two matrix products per token and 16-channel slice (wave):
@@ -1064,16 +1058,12 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_char_tok(EmbArgs a) {
   }
   f32x4 tab[NVT];
 #pragma unroll
-  for (int mt = 0; mt < NVT; ++mt) tab[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int mt = 0; mt < NVT; ++mt) tab[mt] = zero4();
   for (int i = tid; i < 2 * (FP + 8); i += 448) {
     (&s_g[0][0])[i] = 0.f;
     (&s_ap[0][0])[i] = 255;
   }
-  auto ctok = [&](int t) {  // (hidden from the uniformity analysis: see embed_fwdw_f16x3)
-    int c = t < d.ntok ? t : d.ntok - 1;
-    asm volatile("" : "+v"(c));
-    return c;
-  };
+  auto ctok = [&](int t) { return emb_ctok(a, t); };
   const int fcol = tid < CW ? tid : CW - 1, pcol = tid < W ? tid : W - 1;
   // stage token `tok`'s gradient row, arg-max positions and characters (values already in registers)
   auto stage = [&](int tokidx, float g, int ap, int ch) {
@@ -1149,10 +1139,8 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_char_tok(EmbArgs a) {
       const half8 Ah = s_A[buf][ks][0][lane], Al = s_A[buf][ks][1][lane];
       aT = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, Bh[ks], aT, 0, 0, 0);
       half8 bl;
-      if constexpr (true) {
-        if (ks < NKS - NBL) bl = Bl[ks < NKS - NBL ? ks : 0];
-        else bl = s_Bl[wv][ks >= NKS - NBL ? ks - (NKS - NBL) : 0][lane];
-      }
+      if (ks < NKS - NBL) bl = Bl[ks < NKS - NBL ? ks : 0];
+      else bl = s_Bl[wv][ks >= NKS - NBL ? ks - (NKS - NBL) : 0][lane];
       aX = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah, bl, aX, 0, 0, 0);
       aY = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al, Bh[ks], aY, 0, 0, 0);
       if (ks & 1) __builtin_amdgcn_sched_barrier(0);  // (the scheduler would hoist all 34 fragment reads: 136 registers, spills)
@@ -1173,7 +1161,7 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_char_tok(EmbArgs a) {
       const half4v_ oh = {(_Float16)(chq.x == v ? 1.f : 0.f), (_Float16)(chq.y == v ? 1.f : 0.f), (_Float16)(chq.z == v ? 1.f : 0.f),
                           (_Float16)(chq.w == v ? 1.f : 0.f)};
       // (the low half through a temporary: a second table of 32 registers spilled the filter fragments)
-      const f32x4 lo = __builtin_amdgcn_mfma_f32_16x16x16f16(oh, El, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+      const f32x4 lo = __builtin_amdgcn_mfma_f32_16x16x16f16(oh, El, zero4(), 0, 0, 0);
       tab[mt] = __builtin_amdgcn_mfma_f32_16x16x16f16(oh, Eh, tab[mt], 0, 0, 0);
       tab[mt] += lo * (1.f / 2048.f);
     }
@@ -1183,8 +1171,8 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_char_tok(EmbArgs a) {
     __syncthreads();
   }
   // ---- the slab: table tile mt, lane (c = j, q), element r: character v = 16 mt + 4 q + r
-  const int KC = 5 * CD;
-  float* slab_c = a.slab + (size_t)blockIdx.x * ((size_t)KC * CW + CW + (size_t)d.VC * CD) + (size_t)KC * CW + CW;
+  const EmbSlab sl(5 * CD, CW, d.VC, CD);
+  float* slab_c = emb_slab(a, sl, blockIdx.x) + sl.chars;
 #pragma unroll
   for (int mt = 0; mt < NVT; ++mt)
 #pragma unroll
@@ -1194,63 +1182,6 @@ __global__ __launch_bounds__(448, 1) void embed_bwdw_char_tok(EmbArgs a) {
     }
 }
 template __global__ void embed_bwdw_char_tok<100, 100>(EmbArgs);
-
-// d char_emb of the wide shape on the matrix pipe (height 5, CW = 100 filters, W <= 16; any cdim in slices of EMBM_CS channels;
-// the slab [KC*cwdim | cwdim | VC*cdim] of this workgroup is zeroed by the launcher and accumulated in place
-__global__ __launch_bounds__(EMB_NT) void embed_bwd_kernel_big(EmbArgs a) {
-  extern __shared__ float s_dyn[];  // E [W*cdim], dE [W*cdim]
-  __shared__ float s_g[EMB_NT];
-  __shared__ int s_p[EMB_NT];
-  __shared__ int s_ch[64];
-  const fvta_embed_desc& d = a.d;
-  const int tid = threadIdx.x;
-  const int KC = d.height * d.cdim, WC = d.W * d.cdim;
-  float* s_E = s_dyn;
-  float* s_dE = s_dyn + WC;
-  float* slab = a.slab + (size_t)blockIdx.x * ((size_t)KC * d.cwdim + d.cwdim + (size_t)d.VC * d.cdim);
-  float* slab_b = slab + (size_t)KC * d.cwdim;
-  float* slab_c = slab_b + d.cwdim;
-  for (int tok = blockIdx.x; tok < d.ntok; tok += gridDim.x) {
-    const float* row = a.dx + a.tok_off[tok];
-    const int id = a.word_ids[tok];
-    if (id < d.VW)
-      for (int i = tid; i < d.wdim; i += EMB_NT) atomicAdd(a.d_word_emb + (size_t)id * d.wdim + i, row[d.cwdim + i]);
-    __syncthreads();
-    if (tid < d.W) s_ch[tid] = a.char_ids[(size_t)tok * d.W + tid];
-    for (int i = tid; i < WC; i += EMB_NT)
-      s_E[i] = a.char_emb[(size_t)a.char_ids[(size_t)tok * d.W + i / d.cdim] * d.cdim + i % d.cdim] * emb_ks(a, tok, i, WC);
-    float g = 0.f;
-    int p = 0;
-    if (tid < d.cwdim) {
-      const int ap = a.argpos[(size_t)tok * d.cwdim + tid];
-      if (ap != 255) {
-        g = row[tid];
-        p = ap;
-      }
-    }
-    s_g[tid] = g;
-    s_p[tid] = p;
-    __syncthreads();
-    if (tid < d.cwdim && g != 0.f) {  // the owner of filter column f accumulates its slab column
-      slab_b[tid] += g;
-      const float* e = s_E + p * d.cdim;
-      for (int i = 0; i < KC; ++i) slab[(size_t)i * d.cwdim + tid] += g * e[i];
-    }
-    for (int i = tid; i < WC; i += EMB_NT) {
-      const int pos = i / d.cdim, c = i % d.cdim;
-      float v = 0.f;
-      for (int f = 0; f < d.cwdim; ++f) {
-        const int k = pos - s_p[f];
-        const float gf = s_g[f];
-        if (gf != 0.f && k >= 0 && k < d.height) v += gf * a.filt[(size_t)(k * d.cdim + c) * d.cwdim + f];
-      }
-      s_dE[i] = v * emb_ks(a, tok, i, WC);  // (dropout: the gradient reaches the table through the kept elements only)
-    }
-    __syncthreads();
-    if (tid < d.cdim)
-      for (int pos = 0; pos < d.W; ++pos) slab_c[(size_t)s_ch[pos] * d.cdim + tid] += s_dE[pos * d.cdim + tid];
-  }
-}
 
 // slabs -> d_filt, d_bias, d_char_emb (accumulate), fixed order over slabs
 // 1024 threads = 64 elements x 16 slab groups (group g sums slabs g, g+16, ...; the partials combine pairwise in order)
@@ -1278,258 +1209,6 @@ __global__ __launch_bounds__(64 * EMB_RED_G) void embed_bwd_reduce_kernel(const 
   else d_char[i - nfb] += v;
 }
 
-// ---- photo features ---------------------------------------------------------------------------------------
-// y[m][n] = act(sum_k feat[pidx[m]][k] W[k][n] + b[n]) -> x + row_off[m].  32 x 32 tiles, 256 threads.
-__global__ __launch_bounds__(256) void img_fwd_kernel(fvta_imgtrans_desc d, const int32_t* __restrict__ pidx,
-                                                      const int64_t* __restrict__ row_off,
-                                                      const float* __restrict__ feat, const float* __restrict__ W,
-                                                      const float* __restrict__ b, float* __restrict__ x) {
-  __shared__ float As[32][33], Bs[32][33];
-  __shared__ int64_t s_src[32];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int m0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
-  if (threadIdx.x < 32) s_src[threadIdx.x] = m0 + threadIdx.x < d.M ? (int64_t)pidx[m0 + threadIdx.x] * d.idim : -1;
-  __syncthreads();
-  if (W == nullptr) {  // plain gather: tdim == idim
-    for (int r = ty; r < 32; r += 8)
-      if (s_src[r] >= 0 && n0 + tx < d.idim) x[row_off[m0 + r] + n0 + tx] = feat[s_src[r] + n0 + tx];
-    return;
-  }
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < d.idim; k0 += 32) {
-    for (int r = ty; r < 32; r += 8) {
-      const int k = k0 + tx;
-      As[r][tx] = (s_src[r] >= 0 && k < d.idim) ? feat[s_src[r] + k] : 0.f;
-      const int kk = k0 + r, n = n0 + tx;
-      Bs[r][tx] = (kk < d.idim && n < d.tdim) ? W[(size_t)kk * d.tdim + n] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-      const float bv = Bs[k][tx];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] += As[ty + 8 * i][k] * bv;
-    }
-    __syncthreads();
-  }
-  const int n = n0 + tx;
-  if (n >= d.tdim) return;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = ty + 8 * i;
-    if (s_src[r] < 0) continue;
-    const float v = acc[i] + b[n];
-    x[row_off[m0 + r] + n] = d.add_tanh ? tanhf(v) : v;
-  }
-}
-
-// dpre[m][n] = dx * (1 - y^2) (tanh) or dx
-__global__ void img_dpre_kernel(fvta_imgtrans_desc d, const int64_t* __restrict__ row_off, const float* __restrict__ x,
-                                const float* __restrict__ dx, float* __restrict__ dpre) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)d.M * d.tdim) return;
-  const int m = (int)(i / d.tdim), n = (int)(i % d.tdim);
-  const float g = dx[row_off[m] + n];
-  const float y = x[row_off[m] + n];
-  dpre[i] = d.add_tanh ? g * (1.f - y * y) : g;
-}
-
-// dW[k][n] += sum_m feat[pidx[m]][k] dpre[m][n] (m in order); grid (ceil(idim/32), ceil(tdim/32)); db by block row 0
-__global__ __launch_bounds__(256) void img_dw_kernel(fvta_imgtrans_desc d, const int32_t* __restrict__ pidx,
-                                                     const float* __restrict__ feat, const float* __restrict__ dpre,
-                                                     float* __restrict__ dW, float* __restrict__ db) {
-  __shared__ float As[32][33], Bs[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int k0 = blockIdx.x * 32, n0 = blockIdx.y * 32;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  float colsum = 0.f;
-  for (int m0 = 0; m0 < d.M; m0 += 32) {
-    for (int r = ty; r < 32; r += 8) {
-      // As[kk = r][mm = tx] = feat[pidx[m0+tx]][k0 + r]
-      const int m = m0 + tx, k = k0 + r;
-      As[r][tx] = (m < d.M && k < d.idim) ? feat[(size_t)pidx[m] * d.idim + k] : 0.f;
-      const int mm = m0 + r, n = n0 + tx;
-      Bs[r][tx] = (mm < d.M && n < d.tdim) ? dpre[(size_t)mm * d.tdim + n] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int mm = 0; mm < 32; ++mm) {
-      const float bv = Bs[mm][tx];
-      if (ty == 0) colsum += bv;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) acc[i] += As[ty + 8 * i][mm] * bv;
-    }
-    __syncthreads();
-  }
-  const int n = n0 + tx;
-  if (n >= d.tdim) return;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int k = k0 + ty + 8 * i;
-    if (k < d.idim) dW[(size_t)k * d.tdim + n] += acc[i];
-  }
-  if (blockIdx.x == 0 && ty == 0) db[n] += colsum;
-}
-
-
-// ---- photo features on the matrix pipe -------------------------------------------------------------------------
-// The transform 2537 -> 100 of 2560 photos is a 0.65 GMAC GEMM: exact-fp32 MFMA (v_mfma_f32_16x16x4_f32, an fmaf
-// chain per output), operands straight from global memory into the one-register fragments, no LDS staging.  A workgroup
-// owns 16 output rows and all (<= 128) columns; its IMG_NW waves split the reduction index and combine in wave order
-// through LDS.  Column tile (u, e) of a lane's 16-byte loads holds the columns n = 64 u + 4 j + e (j = lane & 15), so
-// the B operand of a step is two dwordx4 loads per lane instead of eight dword loads.
-// Needs tdim % 4 == 0, tdim <= 128 and 16-byte aligned W / workspace rows (the launcher checks).
-constexpr int IMG_NW = 8;
-
-__device__ __forceinline__ f32x4 img_ld4(const float* p, bool ok) {
-  return ok ? *reinterpret_cast<const f32x4*>(p) : f32x4{0.f, 0.f, 0.f, 0.f};
-}
-
-// sum of the IMG_NW waves' accumulators: element (t, r, lane) of the 16 x 128 output tile, in wave order
-__device__ __forceinline__ float img_reduce(const float (*red)[8][4][64], int t, int r, int ln) {
-  float v = red[0][t][r][ln];
-#pragma unroll
-  for (int w = 1; w < IMG_NW; ++w) v += red[w][t][r][ln];
-  return v;
-}
-
-__global__ __launch_bounds__(64 * IMG_NW) void img_fwd_mfma(fvta_imgtrans_desc d, const int32_t* __restrict__ pidx,
-                                                           const int64_t* __restrict__ row_off,
-                                                           const float* __restrict__ feat, const float* __restrict__ W,
-                                                           const float* __restrict__ b, float* __restrict__ x) {
-  __shared__ float s_red[IMG_NW][8][4][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int i = lane & 15, q = lane >> 4;
-  const int m0 = blockIdx.x * 16;
-  const int m = m0 + i < d.M ? m0 + i : d.M - 1;
-  const float* arow = feat + (size_t)pidx[m] * d.idim;
-  const bool c0 = 4 * i < d.tdim, c1 = 64 + 4 * i < d.tdim;
-  const int nchunk = (d.idim + 15) / 16;
-  f32x4 acc[8];
-#pragma unroll
-  for (int t = 0; t < 8; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float a[4], an[4];
-  f32x4 b0[4], b1[4], b0n[4], b1n[4];
-  auto load = [&](int c, float* av, f32x4* v0, f32x4* v1) {
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int k = c * 16 + 4 * q + s;
-      const bool ok = c < nchunk && k < d.idim;
-      av[s] = ok ? arow[k] : 0.f;
-      const float* wr = W + (size_t)(ok ? k : 0) * d.tdim + 4 * i;
-      v0[s] = img_ld4(wr, ok && c0);
-      v1[s] = img_ld4(wr + 64, ok && c1);
-    }
-  };
-  load(wv, a, b0, b1);
-  for (int c = wv; c < nchunk; c += IMG_NW) {
-    load(c + IMG_NW, an, b0n, b1n);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b0[s][e], acc[e], 0, 0, 0);
-        acc[4 + e] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], b1[s][e], acc[4 + e], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      a[s] = an[s];
-      b0[s] = b0n[s];
-      b1[s] = b1n[s];
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 8; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) s_red[wv][t][r][lane] = acc[t][r];
-  __syncthreads();
-#pragma unroll
-  for (int z = 0; z < 2048 / (64 * IMG_NW); ++z) {
-    const int idx = threadIdx.x + 64 * IMG_NW * z;
-    const int t = idx >> 8, r = (idx >> 6) & 3, ln = idx & 63;
-    const int row = m0 + 4 * (ln >> 4) + r, n = 64 * (t >> 2) + 4 * (ln & 15) + (t & 3);
-    if (row >= d.M || n >= d.tdim) continue;
-    const float v = img_reduce(s_red, t, r, ln) + b[n];
-    x[row_off[row] + n] = d.add_tanh ? tanhf(v) : v;
-  }
-}
-
-// dW[k][n] += sum_m feat[pidx[m]][k] dpre[m][n]: a workgroup owns 16 rows k and all columns, its waves split m
-// (wave w takes the steps w, w + IMG_NW, ...: four photos a step) and combine in wave order; db by workgroup 0.
-__global__ __launch_bounds__(64 * IMG_NW) void img_dw_mfma(fvta_imgtrans_desc d, const int32_t* __restrict__ pidx,
-                                                          const float* __restrict__ feat, const float* __restrict__ dpre,
-                                                          float* __restrict__ dW, float* __restrict__ db) {
-  __shared__ float s_red[IMG_NW][8][4][64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int i = lane & 15, q = lane >> 4;
-  const int k0 = blockIdx.x * 16;
-  const bool kok = k0 + i < d.idim;
-  const bool c0 = 4 * i < d.tdim, c1 = 64 + 4 * i < d.tdim;
-  const int nstep = (d.M + 3) / 4;
-  f32x4 acc[8], cs[2];
-#pragma unroll
-  for (int t = 0; t < 8; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  cs[0] = cs[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int U = 4;  // steps in flight
-  float a[U];
-  f32x4 b0[U], b1[U];
-  auto load = [&](int st, float& av, f32x4& v0, f32x4& v1) {
-    const int m = 4 * st + q;
-    const bool ok = st < nstep && m < d.M;
-    const int row = ok ? pidx[m] : 0;
-    av = (ok && kok) ? feat[(size_t)row * d.idim + k0 + i] : 0.f;
-    const float* pr = dpre + (size_t)(ok ? m : 0) * d.tdim + 4 * i;
-    v0 = img_ld4(pr, ok && c0);
-    v1 = img_ld4(pr + 64, ok && c1);
-  };
-#pragma unroll
-  for (int u = 0; u < U; ++u) load(wv + IMG_NW * u, a[u], b0[u], b1[u]);
-  for (int st = wv; st < nstep; st += IMG_NW * U) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const float av = a[u];
-      const f32x4 v0 = b0[u], v1 = b1[u];
-      load(st + IMG_NW * (u + U), a[u], b0[u], b1[u]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        acc[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, v0[e], acc[e], 0, 0, 0);
-        acc[4 + e] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, v1[e], acc[4 + e], 0, 0, 0);
-      }
-      cs[0] += v0;
-      cs[1] += v1;
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 8; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) s_red[wv][t][r][lane] = acc[t][r];
-  __syncthreads();
-#pragma unroll
-  for (int z = 0; z < 2048 / (64 * IMG_NW); ++z) {
-    const int idx = threadIdx.x + 64 * IMG_NW * z;
-    const int t = idx >> 8, r = (idx >> 6) & 3, ln = idx & 63;
-    const int k = k0 + 4 * (ln >> 4) + r, n = 64 * (t >> 2) + 4 * (ln & 15) + (t & 3);
-    if (k >= d.idim || n >= d.tdim) continue;
-    dW[(size_t)k * d.tdim + n] += img_reduce(s_red, t, r, ln);
-  }
-  if (blockIdx.x != 0) return;
-  __syncthreads();
-  // column sums: lane (j, q) of wave w holds the sum over ITS photos of columns 64 u + 4 j + e; combine q, then waves
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s_red[wv][u * 4 + e][0][lane] = cs[u][e];
-  __syncthreads();
-  const int n = threadIdx.x;
-  if (n < d.tdim && n < 128) {
-    const int t = (n >> 6) * 4 + (n & 3), j = (n & 63) >> 2;
-    float v = 0.f;
-    for (int w = 0; w < IMG_NW; ++w)
-      for (int qq = 0; qq < 4; ++qq) v += s_red[w][t][0][qq * 16 + j];
-    db[n] += v;
-  }
-}
 
 template __global__ void embed_fwd_5x8_mfma<100>(EmbArgs);
 template __global__ void embed_bwd_5x8_char<100>(EmbArgs);
@@ -1553,14 +1232,14 @@ static bool embed_is_big(const fvta_embed_desc* d) {
 constexpr int EMB_BIG_BLOCKS = 256;
 // the published flag set's char-CNN (README.MD:144: --char_emb_size 100, 100 filters of height 5): the matrix-pipe kernels
 // embed_fwdw_f16x3 / embed_bwdw_filt_tok / embed_bwdw_char_tok.  Every other deep window runs the general kernels
-// embed_fwd_kernel_big / embed_bwd_kernel_big (FVTA_EMBED_MFMA=0 sends the published shape there too: the A/B of the tests).
+// embed_fwd_general<true> / embed_bwd_general<true> (FVTA_EMBED_MFMA=0 sends the published shape there too: the A/B of the tests).
 static bool embed_wide_ok(const fvta_embed_desc* d) {
   static const bool off = [] {
     const char* e = getenv("FVTA_EMBED_MFMA");
     return e && e[0] == '0';
   }();
   return !off && d->cwdim == 100 && d->cdim == 100 && d->height == 5 && d->W >= 5 && d->W <= 16 && d->wdim <= 128 &&
-         d->wdim <= 64 * ((7 + FVTA_EMBW_SPW - 1) / FVTA_EMBW_SPW) && d->VC <= 128;
+         d->VC <= 128;
 }
 
 // the reference's default shape (height 5, char_emb 8, 100 filters): wave-per-token kernels on the matrix pipe
@@ -1569,13 +1248,9 @@ static bool embed_wave_ok(const fvta_embed_desc* d) {
   return d->cwdim == 100 && d->height == 5 && d->cdim == 8 && d->W <= 16 && d->VC <= 256;
 }
 
-static size_t embed_slab_floats(const fvta_embed_desc* d) {
-  return (size_t)d->height * d->cdim * d->cwdim + d->cwdim + (size_t)d->VC * d->cdim;
-}
-
 extern "C" size_t fvta_embed_workspace_bytes(const fvta_embed_desc* d) {
   if (check_embed(d)) return 0;
-  const size_t b = (size_t)(embed_is_big(d) ? EMB_BIG_BLOCKS : EMB_BWD_BLOCKS) * embed_slab_floats(d) * sizeof(float);
+  const size_t b = (size_t)(embed_is_big(d) ? EMB_BIG_BLOCKS : EMB_BWD_BLOCKS) * EmbSlab(*d).floats * sizeof(float);
   return b < 256 ? 256 : b;
 }
 
@@ -1588,27 +1263,22 @@ extern "C" int fvta_embed_fwd(const fvta_embed_desc* d, const int32_t* word_ids,
   FVTA_CHECK_ARG(d->VW == 0 || word_emb, "embed_fwd: word_emb required");
   FVTA_CHECK_ARG(d->VT == d->VW || fixed_emb, "embed_fwd: fixed_emb required");
   FVTA_CHECK_ARG(d->cwdim == 0 || (char_ids && char_emb && filt && bias && argpos), "embed_fwd: char-CNN pointers");
-  EmbArgs a{};
-  a.d = *d;
-  a.word_ids = word_ids; a.char_ids = char_ids; a.tok_off = tok_off;
-  a.word_emb = word_emb; a.fixed_emb = fixed_emb; a.char_emb = char_emb; a.filt = filt; a.bias = bias;
-  a.x = x; a.argpos = argpos;
-  emb_set_dropout(a, d);
+  EmbArgs a = emb_args(d, word_ids, char_ids, tok_off, char_emb, filt, argpos);
+  a.word_emb = word_emb; a.fixed_emb = fixed_emb; a.bias = bias; a.x = x;
   const int blocks = d->ntok < 8192 ? d->ntok : 8192;
   if (embed_wide_ok(d)) {
     // the published --char_emb_size 100 on the fp16 matrix pipe (3-term split): a workgroup per token, its waves the filter
-    // slices (FVTA_EMBW_SPW slices each); one workgroup per CU (its filter fragments are loaded once)
+    // slices; one workgroup per CU (its filter fragments are loaded once)
     const int nbt = d->ntok < 256 ? d->ntok : 256;
-    hipLaunchKernelGGL((embed_fwdw_f16x3<100, 100, FVTA_EMBW_SPW>), dim3(nbt), dim3(64 * ((7 + FVTA_EMBW_SPW - 1) / FVTA_EMBW_SPW)), 0,
-                       (hipStream_t)stream_, a);
+    hipLaunchKernelGGL((embed_fwdw_f16x3<100, 100>), dim3(nbt), dim3(448), 0, (hipStream_t)stream_, a);
   } else if (embed_is_big(d)) {     // every other deep window: the general kernel
     const size_t dyn = (size_t)d->W * d->cdim * sizeof(float);
-    hipLaunchKernelGGL(embed_fwd_kernel_big, dim3(blocks), dim3(EMB_NT), dyn, (hipStream_t)stream_, a);
+    hipLaunchKernelGGL(embed_fwd_general<true>, dim3(blocks), dim3(EMB_NT), dyn, (hipStream_t)stream_, a);
   } else if (embed_wave_ok(d)) {
     const int nb = (d->ntok + 3) / 4 < EMB_WAVE_FWD_BLOCKS ? (d->ntok + 3) / 4 : EMB_WAVE_FWD_BLOCKS;
     hipLaunchKernelGGL(embed_fwd_5x8_mfma<100>, dim3(nb), dim3(256), (size_t)d->VC * 8 * sizeof(float), (hipStream_t)stream_, a);
   } else
-    hipLaunchKernelGGL(embed_fwd_kernel, dim3(blocks), dim3(EMB_NT), 0, (hipStream_t)stream_, a);
+    hipLaunchKernelGGL(embed_fwd_general<false>, dim3(blocks), dim3(EMB_NT), 0, (hipStream_t)stream_, a);
   FVTA_CHECK_LAUNCH("embed_fwd");
   return FVTA_OK;
 }
@@ -1623,30 +1293,26 @@ extern "C" int fvta_embed_bwd(const fvta_embed_desc* d, const int32_t* word_ids,
   FVTA_CHECK_ARG(d->cwdim == 0 || (char_ids && char_emb && filt && argpos && d_char_emb && d_filt && d_bias),
                  "embed_bwd: char-CNN pointers");
   hipStream_t stream = (hipStream_t)stream_;
-  EmbArgs a{};
-  a.d = *d;
-  a.word_ids = word_ids; a.char_ids = char_ids; a.tok_off = tok_off;
-  a.char_emb = char_emb; a.filt = filt; a.argpos = const_cast<uint8_t*>(argpos);
+  EmbArgs a = emb_args(d, word_ids, char_ids, tok_off, char_emb, filt, argpos);
   a.dx = dx; a.d_word_emb = d_word_emb; a.slab = (float*)workspace;
-  emb_set_dropout(a, d);
   int blocks;
   if (embed_wide_ok(d)) {
     // the published shape: a workgroup per token for both gradients (d filt / d bias: the bf16 three-term product; d char_emb:
     // the tap fold and the table scatter as two chained matrix products); slabs reduced in a fixed order below
     blocks = d->ntok < EMB_BIG_BLOCKS ? d->ntok : EMB_BIG_BLOCKS;
-    hipLaunchKernelGGL((embed_bwdw_filt_tok<100, 100, true>), dim3(blocks), dim3(448), 0, stream, a);
+    hipLaunchKernelGGL((embed_bwdw_filt_tok<100, 100>), dim3(blocks), dim3(448), 0, stream, a);
     constexpr int frag_bytes = 2 * 17 * 2 * 64 * 16 + 7 * 7 * 64 * 16;  // the A fragments (two tokens) + the waves' low filter fragments
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(embed_bwdw_char_tok<100, 100>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               frag_bytes);
     hipLaunchKernelGGL((embed_bwdw_char_tok<100, 100>), dim3(blocks), dim3(448), frag_bytes, stream, a);
   } else if (embed_is_big(d)) {
     blocks = d->ntok < EMB_BIG_BLOCKS ? d->ntok : EMB_BIG_BLOCKS;
-    FVTA_CHECK_HIP(hipMemsetAsync(workspace, 0, (size_t)blocks * embed_slab_floats(d) * sizeof(float), stream));
+    FVTA_CHECK_HIP(hipMemsetAsync(workspace, 0, (size_t)blocks * EmbSlab(*d).floats * sizeof(float), stream));
     const size_t dyn = (size_t)2 * d->W * d->cdim * sizeof(float);
     if (dyn > 32 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(embed_bwd_kernel_big),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(embed_bwd_general<true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-    hipLaunchKernelGGL(embed_bwd_kernel_big, dim3(blocks), dim3(EMB_NT), dyn, stream, a);
+    hipLaunchKernelGGL(embed_bwd_general<true>, dim3(blocks), dim3(EMB_NT), dyn, stream, a);
   } else if (embed_wave_ok(d)) {
     // one slab per WAVE: 4 * blocks <= EMB_BWD_BLOCKS slabs
     blocks = (d->ntok + 3) / 4 < EMB_BWD_BLOCKS / 4 ? (d->ntok + 3) / 4 : EMB_BWD_BLOCKS / 4;
@@ -1665,9 +1331,9 @@ extern "C" int fvta_embed_bwd(const fvta_embed_desc* d, const int32_t* word_ids,
     if (blocks > EMB_BWD_BLOCKS) blocks = EMB_BWD_BLOCKS;
     if (blocks > d->ntok) blocks = d->ntok;
     if (dyn > 32 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(embed_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(embed_bwd_general<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)dyn);
-    hipLaunchKernelGGL(embed_bwd_kernel, dim3(blocks), dim3(EMB_NT), dyn, stream, a);
+    hipLaunchKernelGGL(embed_bwd_general<false>, dim3(blocks), dim3(EMB_NT), dyn, stream, a);
   }
   if (d->cwdim > 0) {
     const int nfilt = d->height * d->cdim * d->cwdim, nfb = nfilt + d->cwdim, nchar = d->VC * d->cdim;
@@ -1675,49 +1341,5 @@ extern "C" int fvta_embed_bwd(const fvta_embed_desc* d, const int32_t* word_ids,
                        (const float*)workspace, blocks, nfb, nchar, d_filt, d_bias, nfilt, d_char_emb);
   }
   FVTA_CHECK_LAUNCH("embed_bwd");
-  return FVTA_OK;
-}
-
-// shapes the matrix-pipe photo kernels take: rows of `mat` (W [idim][tdim] or dpre [M][tdim]) read 16 bytes at a time
-static bool img_mfma_ok(const fvta_imgtrans_desc* d, const float* mat) {
-  return d->tdim % 4 == 0 && d->tdim <= 128 && ((uintptr_t)mat & 15) == 0;
-}
-
-extern "C" int fvta_image_trans_fwd(const fvta_imgtrans_desc* d, const int32_t* pidx, const int64_t* row_off,
-                                    const float* image_emb_mat, const float* W, const float* b, float* x,
-                                    fvta_stream_t stream_) {
-  FVTA_CHECK_ARG(d && d->M > 0 && d->idim > 0 && d->tdim > 0 && pidx && row_off && image_emb_mat && x,
-                 "image_trans_fwd: bad argument");
-  FVTA_CHECK_ARG(W ? b != nullptr : d->tdim == d->idim, "image_trans_fwd: W without b, or tdim != idim without W");
-  const int nd = W ? d->tdim : d->idim;
-  if (W && img_mfma_ok(d, W)) {
-    hipLaunchKernelGGL(img_fwd_mfma, dim3((d->M + 15) / 16), dim3(64 * IMG_NW), 0, (hipStream_t)stream_, *d, pidx, row_off,
-                       image_emb_mat, W, b, x);
-    FVTA_CHECK_LAUNCH("image_trans_fwd");
-    return FVTA_OK;
-  }
-  hipLaunchKernelGGL(img_fwd_kernel, dim3((d->M + 31) / 32, (nd + 31) / 32), dim3(256), 0, (hipStream_t)stream_, *d, pidx,
-                     row_off, image_emb_mat, W, b, x);
-  FVTA_CHECK_LAUNCH("image_trans_fwd");
-  return FVTA_OK;
-}
-
-extern "C" int fvta_image_trans_bwd(const fvta_imgtrans_desc* d, const int32_t* pidx, const int64_t* row_off,
-                                    const float* image_emb_mat, const float* x, const float* dx, float* dW,
-                                    float* db, void* workspace, fvta_stream_t stream_) {
-  FVTA_CHECK_ARG(d && d->M > 0 && d->idim > 0 && d->tdim > 0 && pidx && row_off && image_emb_mat && x && dx && dW &&
-                     db && workspace,
-                 "image_trans_bwd: bad argument");
-  hipStream_t stream = (hipStream_t)stream_;
-  float* dpre = (float*)workspace;
-  const size_t n = (size_t)d->M * d->tdim;
-  hipLaunchKernelGGL(img_dpre_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, *d, row_off, x, dx, dpre);
-  if (img_mfma_ok(d, dpre))
-    hipLaunchKernelGGL(img_dw_mfma, dim3((d->idim + 15) / 16), dim3(64 * IMG_NW), 0, stream, *d, pidx, image_emb_mat, dpre,
-                       dW, db);
-  else
-    hipLaunchKernelGGL(img_dw_kernel, dim3((d->idim + 31) / 32, (d->tdim + 31) / 32), dim3(256), 0, stream, *d, pidx,
-                       image_emb_mat, dpre, dW, db);
-  FVTA_CHECK_LAUNCH("image_trans_bwd");
   return FVTA_OK;
 }

@@ -86,6 +86,7 @@ __device__ __forceinline__ float fvta_tanh(float x) {
 
 // 16-byte load of four floats
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

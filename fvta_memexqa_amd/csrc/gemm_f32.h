@@ -175,6 +175,4 @@ __device__ __forceinline__ void gemm_mainloop(Mma& mma, SA& sa, SB& sb, FA&& fa,
   }
 }
 
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-
 }  // namespace fvta

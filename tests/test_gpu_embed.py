@@ -129,9 +129,105 @@ def test_token_embed_without_char_cnn():
     op = ops.TokenEmbed(ntok, 16, 8, 0, 50, 20, 30, 30)
     cu = lambda t: t.cuda().contiguous()
     x = torch.zeros(ntok * 50, device="cuda")
-    op.forward(cu(ids.reshape(-1)), None, cu(torch.arange(ntok, dtype=torch.int64) * 50), cu(p["word_emb"]), cu(p["fixed"]),
-               None, None, None, x)
+    tok_off = cu(torch.arange(ntok, dtype=torch.int64) * 50)
+    op.forward(cu(ids.reshape(-1)), None, tok_off, cu(p["word_emb"]), cu(p["fixed"]), None, None, None, x)
     _close(x.view(ntok, 50), ref.reshape(ntok, 50))
+    # backward: the trainable word rows only; nothing is written elsewhere (the workspace keeps its sentinel)
+    gout = torch.randn(ntok, 50, generator=torch.Generator().manual_seed(5))
+    flat = ids.reshape(-1).long()
+    ref_dwe = torch.zeros(20, 50, dtype=torch.float64).index_add_(0, flat[flat < 20], gout.double()[flat < 20])
+    dwe = torch.zeros(20, 50, device="cuda")
+    op.work.view(torch.uint8).fill_(0xA5)
+    op.backward(cu(ids.reshape(-1)), None, tok_off, None, None, cu(gout.reshape(-1)), dwe, None, None, None)
+    _close(dwe, ref_dwe, atol=1e-4, msg="d word_emb")
+    assert bool((op.work.view(torch.uint8) == 0xA5).all()), "the workspace was written"
+
+
+@pytest.mark.parametrize("B,J,W,cd,cw,wd,VW,VF,VC", [(110, 30, 13, 8, 100, 20, 50, 30, 40),     # wave per token: 3,300 tokens, W < 16
+                                                      (280, 30, 9, 4, 24, 20, 7, 5, 11),        # register kernels: 8,400 tokens
+                                                      (280, 30, 9, 16, 24, 20, 7, 5, 11),       # height * cdim = 80: the fallback, 256 slabs
+                                                      (40, 30, 16, 100, 100, 60, 30, 30, 70)])  # wide: 1,200 tokens, 256 workgroups
+def test_token_embed_token_loops_with_dropout(B, J, W, cd, cw, wd, VW, VF, VC):
+    """More tokens than one round of workgroups (waves), with conv1d's dropout on: every kernel's token loop turns over and
+    the keep mask is indexed by the look-ahead token.  With this many (token, filter) pairs fp32 and fp64 order some
+    near-tied windows differently -- a property of the input -- so the arg-max is compared where it is unambiguous (margin
+    to the runner-up and of y to zero at least twice the forward bound 1e-4 |y| + 1e-5; at most 0.1 % of the entries may
+    be ambiguous: a condition on the input, not a tolerance), and the backward runs on the oracle's positions, against
+    gradients computed here from those same positions."""
+    from fvta_memexqa_amd import ops
+    from oracle import fvta_fused as F
+    keep, seed = 0.8, 0xABCDEF0123
+    p, ids, ch = _case(B + J + W + 1, B, J, W, cd, cw, wd, VW, VF, VC)
+    ntok, P, KC = B * J, W - 4, 5 * cd
+    km = F.dropout_keep_flat(ntok * W * cd, keep, seed).reshape(B, J, W, cd)
+    p64 = {k: v.double().requires_grad_() for k, v in p.items()}
+    ref = F.embed_tokens(ids, ch, p64["word_emb"], p64["fixed"], p64["char_emb"], p64["filt"], p64["bias"], char_keep=km,
+                         keep_prob=keep).detach().reshape(ntok, -1)
+    # fp64 window sums, first arg-max and its margins
+    scale = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(keep, dtype=torch.float32))
+    flat_ids, flat_ch = ids.reshape(-1).long(), ch.reshape(ntok, W).long()
+    E = p64["char_emb"][flat_ch] * scale * km.reshape(ntok, W, cd).double()                 # [ntok, W, cd]
+    win = E.unfold(1, 5, 1).permute(0, 1, 3, 2).reshape(ntok, P, KC)                         # window p = E[p : p + 5] flattened
+    S = win @ p64["filt"].reshape(KC, cw)                                                    # [ntok, P, cw]
+    Sn = S.detach().numpy()
+    pos = torch.from_numpy(Sn.argmax(1))                                                     # (numpy: the first maximum)
+    top2 = torch.from_numpy(np.sort(Sn, axis=1)[:, -2:, :])
+    y = top2[:, 1] + p64["bias"].detach()
+    np.testing.assert_allclose(torch.relu(y).numpy(), ref[:, :cw].numpy(), rtol=1e-12, atol=1e-12)  # the oracle's own rows
+    bound = RTOL * y.abs() + 1e-5
+    ambiguous = ((top2[:, 1] - top2[:, 0]) < 2 * bound) | (y.abs() < 2 * bound)
+    share = float(ambiguous.double().mean())
+    print("ambiguous share %.2e of %d entries" % (share, ambiguous.numel()))
+    assert share <= 1e-3
+    active = y > 0
+    want_ap = torch.where(active, pos, torch.full_like(pos, 255)).to(torch.uint8)
+    # forward
+    stride = cw + wd
+    op = ops.TokenEmbed(ntok, W, cd, cw, wd, VW, VW + VF, VC)
+    op.set_dropout(keep, seed)
+    cu = lambda t: t.cuda().contiguous()
+    tok_off = cu(torch.arange(ntok, dtype=torch.int64) * stride)
+    x = torch.zeros(ntok * stride, device="cuda")
+    filt = cu(p["filt"].reshape(5, cd, cw))
+    args = (cu(ids.reshape(-1)), cu(ch.reshape(-1, W)), tok_off)
+    op.forward(*args, cu(p["word_emb"]), cu(p["fixed"]), cu(p["char_emb"]), filt, cu(p["bias"]), x)
+    _close(x.view(ntok, stride), ref, msg="x")
+    got_ap = op.argpos.view(ntok, cw).cpu()
+    assert torch.equal(got_ap[~ambiguous], want_ap[~ambiguous]), "argpos"
+    # backward on the oracle's positions; the reference gradients from those same positions
+    op.argpos.copy_(cu(want_ap.reshape(-1)))
+    gout = torch.randn(ntok, cw + wd, generator=torch.Generator().manual_seed(6))
+    g = gout[:, :cw].double() * active
+    loss = ((S.gather(1, pos[:, None, :])[:, 0] + p64["bias"]) * g).sum() + \
+        (torch.cat([p64["word_emb"], p64["fixed"]], 0)[flat_ids] * gout[:, cw:].double()).sum()
+    loss.backward()
+    dwe, dce = torch.zeros(VW, wd, device="cuda"), torch.zeros(VC, cd, device="cuda")
+    dfl, dbi = torch.zeros(5, cd, cw, device="cuda"), torch.zeros(cw, device="cuda")
+    op.backward(*args, cu(p["char_emb"]), filt, cu(gout.reshape(-1)), dwe, dce, dfl, dbi)
+    _close(dwe, p64["word_emb"].grad, atol=1e-4, msg="d word_emb")
+    _close(dce, p64["char_emb"].grad, atol=1e-4, msg="d char_emb")
+    ref_dfl = p64["filt"].grad.reshape(5, cd, cw)    # (wide shape: the bf16x3 bound, see test_token_embed_forward_backward)
+    _close(dfl, ref_dfl, atol=max(1e-4, 3e-5 * float(ref_dfl.abs().max())) if cd > 8 else 1e-4, msg="d filt")
+    _close(dbi, p64["bias"].grad, atol=1e-4, msg="d bias")
+
+
+def test_embed_build_switches_named_in_tests_and_tools_exist():
+    """Every FVTA_EMB_* / FVTA_EMBW_* switch that a test or a tool names is still read by a source of the library."""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "fvta_memexqa_amd", "csrc")
+    have = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h")):
+            have |= set(re.findall(r"(?:#\s*ifn?def|defined\(|getenv\(\")\s*(FVTA_EMBW?_[A-Z0-9_]+)", open(os.path.join(csrc, f)).read()))
+    named = set()
+    for d in ("tests", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(root, d)):
+            for f in files:
+                if f.endswith((".py", ".sh", ".md")):
+                    named |= set(re.findall(r"FVTA_EMBW?_[A-Z0-9_]*[A-Z0-9]", open(os.path.join(dirpath, f)).read()))
+    assert named and named <= have, sorted(named - have)
 
 
 @pytest.mark.parametrize("trans,tanh,shape", [(True, True, (37, 157, 100, 45)), (True, False, (37, 157, 100, 45)),

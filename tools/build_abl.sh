@@ -1,7 +1,8 @@
 #!/bin/bash
 # builds diag/libfvta_hip_<src>_abl<bits>.so variants of the library with one source compiled -D<MACRO>=<bits>
 #   tools/build_abl.sh 1 2 4                                    (lstm_wreg.hip, -DFVTA_WREG_ABL)
-#   SRC=embed MACRO=FVTA_EMB_ABL tools/build_abl.sh 1 2 4       (embed.hip)
+#   SRC=embed MACRO=FVTA_EMB_ABL tools/build_abl.sh 1 2 4       (embed.hip: the wave-per-token kernels)
+#   SRC=embed MACRO=FVTA_EMBW_ABL tools/build_abl.sh 256 512 1024  (embed.hip: the wide forward embed_fwdw_f16x3)
 SRC=${SRC:-lstm_wreg}; MACRO=${MACRO:-FVTA_WREG_ABL}
 cd "$(dirname "$0")/../fvta_memexqa_amd/csrc" && mkdir -p diag
 for b in "$@"; do

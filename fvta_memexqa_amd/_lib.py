@@ -45,6 +45,10 @@ class ScorerDesc(Structure):
     _fields_ = [(n, c_int32) for n in ("N", "C", "w", "use_eu_output", "add_tanh", "xent_grad")]
 
 
+class AttGruSeqDesc(Structure):
+    _fields_ = [(n, c_int32) for n in ("N", "F", "d", "training")]
+
+
 CTX_KMAX = 8
 
 
@@ -98,6 +102,11 @@ _SIGS = {
     "fvta_scorer_ce_bwd": (c_int, [POINTER(ScorerDesc), P, P, P, P, P, P, P, P, c_float, P, P, P, P, P, P]),
     "fvta_attgru_fwd": (c_int, [c_int32, c_int32, P, P, P, P, P, P, P, P, P, P]),
     "fvta_attgru_bwd": (c_int, [c_int32, c_int32, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_attgru_seq_saved_bytes": (c_size_t, [POINTER(AttGruSeqDesc)]),
+    "fvta_attgru_seq_workspace_bytes": (c_size_t, [POINTER(AttGruSeqDesc), c_int32]),
+    "fvta_attgru_seq_plan": (c_int, [POINTER(AttGruSeqDesc), POINTER(c_int32)]),
+    "fvta_attgru_seq_fwd": (c_int, [POINTER(AttGruSeqDesc), P, P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_attgru_seq_bwd": (c_int, [POINTER(AttGruSeqDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int32, P, P]),
     "fvta_timewarp_workspace_bytes": (c_size_t, [POINTER(TimewarpDesc)]),
     "fvta_timewarp_fwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_bwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
@@ -182,7 +191,8 @@ def load():
         fn.restype = res
         fn.argtypes = args
     # the descriptor structs are declared twice (include/fvta_hip.h and above): refuse a library whose layout differs
-    for which, cls in enumerate((AttnDesc, LstmDesc, ScorerDesc, TimewarpDesc, EmbedDesc, ImgTransDesc, GuardDesc, GuardCtl)):
+    for which, cls in list(enumerate((AttnDesc, LstmDesc, ScorerDesc, TimewarpDesc, EmbedDesc, ImgTransDesc, GuardDesc, GuardCtl))) + \
+            [(9, AttGruSeqDesc)]:
         have, want = ctypes.sizeof(cls), lib.fvta_abi_struct_bytes(which)
         if have != want:
             raise FvtaError("%s is %d bytes here but %d in %s: rebuild the library (descriptor layouts differ)"

@@ -547,3 +547,107 @@ def photo_features(pis, image_emb_mat, W=None, b=None, add_tanh=False):
     x = _PhotoFeatures.apply(pis.to(dev, torch.int32).contiguous().reshape(-1), f(image_emb_mat).detach(), f(W), f(b),
                              bool(add_tanh))
     return x.reshape(tuple(pis.shape) + (x.shape[-1],))
+
+
+# ------------------------------------------------------- DMN+ episodic memory
+class _AttGruSeq(torch.autograd.Function):
+    """(facts [N,F,d], gate [N,F], h0 [N,d] | None, Wg [2d,d], bg [d], Wc [d,d], Wi [d,d], bi [d]) -> h_last [N,d]: the
+    AttentionGRUCell (attention_gru_cell.py:50-70) over all F facts with the state carried, one fvta_attgru_seq_fwd.
+    Each call owns its ops.AttentionGRUSeq and with it `saved`; the backward (one fvta_attgru_seq_bwd, workspace
+    allocated there) only reads it, so a retained graph may be walked again."""
+
+    @staticmethod
+    def forward(ctx, facts, gate, h0, Wg, bg, Wc, Wi, bi):
+        N, F, d = facts.shape
+        need = any(ctx.needs_input_grad)
+        op = ops.AttentionGRUSeq(N, F, d, training=need)
+        h_last = op.forward(facts, gate, h0, Wg, bg, Wc, Wi, bi)
+        ctx.set_materialize_grads(False)
+        if need:
+            ctx.op = op
+            ctx.save_for_backward(facts, gate, Wg, Wc, Wi)
+        return h_last
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 8
+        facts, gate, Wg, Wc, Wi = ctx.saved_tensors
+        N, F, d = facts.shape
+        need = ctx.needs_input_grad
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=facts.device)
+        d_facts, d_gate = new(N, F, d), new(N, F)
+        d_h0 = new(N, d) if need[2] else None
+        dWg, dbg, dWc, dWi, dbi = new(2 * d, d), new(d), new(d, d), new(d, d), new(d)     # stored: accumulate = 0
+        ctx.op.backward(facts, gate, Wg, Wc, Wi, _c(g), d_facts, d_gate, d_h0, dWg, dbg, dWc, dWi, dbi, accumulate=False)
+        return tuple(t if n else None for t, n in zip((d_facts, d_gate, d_h0, dWg, dbg, dWc, dWi, dbi), need))
+
+
+def attgru_seq(facts, gate, h0, Wg, bg, Wc, Wi, bi):
+    """facts [N,F,d], gate [N,F] (the attention times `t < length`: a gate of 0 copies the state through), h0 [N,d] or
+    None (zeros), the five cell variables -> h_last [N,d]"""
+    ops.require_gpu()
+    f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+    return _AttGruSeq.apply(f(facts), f(gate), f(h0), f(Wg), f(bg), f(Wc), f(Wi), f(bi))
+
+
+class _DmnFeatures(torch.autograd.Function):
+    """(facts [N,F,d], q [N,d], m [N,d]) -> [N,F,4d] = [fact*q, fact*m, |fact-q|, |fact-m|] (model_dmnplus.py:93-98,
+    fvta_dmn_features); backward: fvta_dmn_features_bwd into fresh zero buffers (it accumulates)."""
+
+    @staticmethod
+    def forward(ctx, facts, q, m):
+        N, F, d = facts.shape
+        out = torch.empty(N, F, 4 * d, dtype=torch.float32, device=facts.device)
+        check(_lib.load().fvta_dmn_features(ptr(facts), ptr(q), ptr(m), ptr(out), N, F, d, stream_ptr()), "fvta_dmn_features")
+        ctx.set_materialize_grads(False)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(facts, q, m)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        facts, q, m = ctx.saved_tensors
+        N, F, d = facts.shape
+        d_facts, d_q, d_m = torch.zeros_like(facts), torch.zeros_like(q), torch.zeros_like(m)
+        check(_lib.load().fvta_dmn_features_bwd(ptr(facts), ptr(q), ptr(m), ptr(_c(g)), ptr(d_facts), ptr(d_q), ptr(d_m),
+                                                N, F, d, stream_ptr()), "fvta_dmn_features_bwd")
+        return tuple(t if n else None for t, n in zip((d_facts, d_q, d_m), ctx.needs_input_grad))
+
+
+def dmn_features(facts, q, m):
+    ops.require_gpu()
+    f = lambda t: t.to(torch.float32).contiguous()
+    return _DmnFeatures.apply(f(facts), f(q), f(m))
+
+
+class _Relu(torch.autograd.Function):
+    """fvta_relu_fwd; the backward reads the OUTPUT (fvta_relu_bwd: dx = dy where y > 0)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = torch.empty_like(x)
+        check(_lib.load().fvta_relu_fwd(ptr(x), ptr(y), x.numel(), stream_ptr()), "fvta_relu_fwd")
+        ctx.set_materialize_grads(False)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return None
+        y, = ctx.saved_tensors
+        dx = torch.empty_like(y)
+        check(_lib.load().fvta_relu_bwd(ptr(y), ptr(_c(g)), ptr(dx), y.numel(), stream_ptr()), "fvta_relu_bwd")
+        return dx
+
+
+def relu(x):
+    ops.require_gpu()
+    return _Relu.apply(x.to(torch.float32).contiguous())

@@ -1,0 +1,511 @@
+// The AttentionGRU over a whole fact sequence (model_dmnplus.py:123-134: dynamic_rnn over AttentionGRUCell,
+// attention_gru_cell.py:50-70), forward and backward, for gfx950:
+//   r_t  = sigmoid(x_t Wg[:d] + h_{t-1} Wg[d:] + bg)     hc_t = h_{t-1} Wc     xi_t = x_t Wi + bi
+//   hh_t = tanh(r_t * hc_t + xi_t)                        h_t  = (1 - g_t) h_{t-1} + g_t hh_t
+// What does not depend on the state is hoisted out of the recurrence: pre = [x Wg[:d] + bg | x Wi + bi] for all N*F rows
+// before it (fvta_linear_fwd), and d_facts, dWg, dWc, dWi, dbg, dbi as contractions over all N*F rows after the reverse
+// recurrence (fvta_linear_bwd over the gate gradients the recurrence leaves in the workspace).
+// The recurrence itself: row n's chain never reads another row, so a workgroup owns SEQ_RT = 16 rows (the M of
+// v_mfma_f32_16x16x4_f32, exact fp32) and no workgroup ever waits for another.  Two regimes, by d:
+//   A (dp = d rounded up to 16 <= 128): ONE launch for all F steps.  [Wg[d:] | Wc] stay in LDS for the whole launch,
+//     as [unit][k] images with a row pad of 2 floats (conflict-free MFMA operand reads); the state tile stays on chip
+//     (registers in the MFMA C layout + an LDS image as the next step's A operand).  A wave owns 16 units: r and hc of a
+//     unit land in the same lane.  The backward keeps the same two matrices untransposed ([c][u] IS its [n][k] image).
+//   B (larger d): the weights do not fit a CU, so a step is one fused launch over (row tiles x 64-unit column tiles): the
+//     state-side product with the gate math as its epilogue; in the backward the gate gradient (recomputed per column
+//     tile while the A operand is staged) with the d_h product.  Issued F times from one C call, ordered by the stream.
+// No atomics, fixed summation order: two runs are bitwise equal.  The backward only reads `saved`.
+#include "fvta_common.h"
+
+namespace fvta {
+
+constexpr int SEQ_RT = 16;          // rows of a workgroup tile
+constexpr int SEQ_A_WAVES = 8;      // regime A: one wave per 16-unit column tile
+constexpr int SEQ_A_DP_MAX = 16 * SEQ_A_WAVES;
+constexpr int SEQ_B_KC = 32;        // regime B: k-chunk staged through LDS
+constexpr int SEQ_B_CT = 64;        // regime B: units per workgroup (4 waves x 16)
+constexpr int SEQ_B_LD = SEQ_B_KC + 2;
+
+struct SeqFwdArgs {
+  int N, F, d, dp;
+  const float *gate, *h0, *Wg, *Wc, *preR, *preI;
+  float *h_last, *S_h, *S_r, *S_hc, *S_hh;
+};
+struct SeqBwdArgs {
+  int N, F, d, dp;
+  const float *gate, *Wg, *Wc, *S_h, *S_r, *S_hc, *S_hh, *d_h_last;
+  float *G_r, *G_c, *G_x, *d_gate, *d_h0;
+};
+
+// acc += A[16][K] * B[16][K]^T for LDS images whose rows are k-contiguous (ld = 2 mod 32: lanes 0..31 hit 32 banks).
+// lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15] = image[j][k]
+__device__ __forceinline__ void seq_mma2(const float* __restrict__ A, int lda, const float* __restrict__ B0,
+                                         const float* __restrict__ B1, int ldb, int K, int lane, f32x4& acc0, f32x4& acc1) {
+  const float* ap = A + (lane & 15) * lda + (lane >> 4);
+  const float* b0 = B0 + (lane & 15) * ldb + (lane >> 4);
+  const float* b1 = B1 + (lane & 15) * ldb + (lane >> 4);
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    const float av = ap[k0];
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0[k0], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1[k0], acc1, 0, 0, 0);
+  }
+}
+__device__ __forceinline__ void seq_mma_ab(const float* __restrict__ A0, const float* __restrict__ A1, int lda,
+                                           const float* __restrict__ B0, const float* __restrict__ B1, int ldb, int K,
+                                           int lane, f32x4& acc0, f32x4& acc1) {
+  const int o = (lane & 15) * lda + (lane >> 4), ob = (lane & 15) * ldb + (lane >> 4);
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(A0[o + k0], B0[ob + k0], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(A1[o + k0], B1[ob + k0], acc1, 0, 0, 0);
+  }
+}
+
+// one element of the cell: returns h_t; r and hh come back for `saved`.  The two fused multiply-adds are spelled out: left
+// to the compiler, the training and the inference instantiation contracted (1 - g) h + g hh differently (one bit apart).
+// A gate of 0 returns h itself.
+__device__ __forceinline__ float seq_gate_fwd(float pre_r, float hc, float pre_i, float g, float h, float& r, float& hh) {
+  r = fvta_sigmoid(pre_r);
+  hh = fvta_tanh(fmaf(r, hc, pre_i));
+  return fmaf(g, hh, (1.f - g) * h);
+}
+// gate gradient of one element: dr_pre, dhc, dxi; returns this element's share of d_gate
+__device__ __forceinline__ float seq_gate_bwd(float dn, float g, float r, float hc, float hh, float h, float& dr, float& dhc,
+                                              float& dxi) {
+  const float dpre = dn * g * (1.f - hh * hh);
+  dr = dpre * hc * r * (1.f - r);
+  dhc = dpre * r;
+  dxi = dpre;
+  return dn * (hh - h);
+}
+
+// ---------------------------------------------------------------- regime A
+// grid ceil(N/16), 512 threads, dynamic LDS (2 dp + 16) (dp + 2) floats
+template <bool TRAIN>
+__global__ __launch_bounds__(64 * SEQ_A_WAVES) void attgru_seq_fwd_a(SeqFwdArgs a) {
+  extern __shared__ float smem[];
+  const int N = a.N, F = a.F, d = a.d, dp = a.dp, ld = dp + 2;
+  float* Wg_l = smem;             // [u][k] = Wg[d + k][u]
+  float* Wc_l = Wg_l + dp * ld;   // [u][k] = Wc[k][u]
+  float* H_l = Wc_l + dp * ld;    // [16][ld]: h_{t-1} of the tile
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int m0 = blockIdx.x * SEQ_RT;
+  for (int idx = tid; idx < dp * dp; idx += 64 * SEQ_A_WAVES) {
+    const int k = idx / dp, u = idx - k * dp;
+    const bool ok = k < d && u < d;
+    const size_t src = ok ? (size_t)k * d + u : 0;
+    const float vg = a.Wg[(size_t)d * d + src], vc = a.Wc[src];
+    Wg_l[u * ld + k] = ok ? vg : 0.f;
+    Wc_l[u * ld + k] = ok ? vc : 0.f;
+  }
+  for (int idx = tid; idx < SEQ_RT * dp; idx += 64 * SEQ_A_WAVES) {
+    const int i = idx / dp, u = idx - i * dp, n = m0 + i;
+    float v = 0.f;
+    if (a.h0 && n < N && u < d) v = a.h0[(size_t)n * d + u];
+    H_l[i * ld + u] = v;
+  }
+  __syncthreads();
+  const bool active = wave * 16 < dp;
+  const int u = wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+  float h[4];
+  bool ok[4];
+  int64_t row[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int n = m0 + i0 + r;
+    ok[r] = n < N && u < d;
+    row[r] = n < N ? n : 0;
+    h[r] = active ? H_l[(i0 + r) * ld + u] : 0.f;
+  }
+  for (int t = 0; t < F; ++t) {
+    float pr[4], pi[4], g[4];
+    int64_t sidx[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {   // (state independent: issued ahead of the product)
+      sidx[r] = ok[r] ? (row[r] * F + t) * d + u : 0;
+      pr[r] = a.preR[sidx[r]];
+      pi[r] = a.preI[sidx[r]];
+      g[r] = a.gate[row[r] * F + t];
+    }
+    f32x4 acc_r = {0.f, 0.f, 0.f, 0.f}, acc_c = {0.f, 0.f, 0.f, 0.f};
+    if (active) seq_mma2(H_l, ld, Wg_l + wave * 16 * ld, Wc_l + wave * 16 * ld, ld, dp, lane, acc_r, acc_c);
+    __syncthreads();                // every wave has read H_l
+    if (active) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float rr, hh;
+        const float hn = seq_gate_fwd(acc_r[r] + pr[r], acc_c[r], pi[r], g[r], h[r], rr, hh);
+        if (TRAIN && ok[r]) {
+          a.S_h[sidx[r]] = h[r];
+          a.S_r[sidx[r]] = rr;
+          a.S_hc[sidx[r]] = acc_c[r];
+          a.S_hh[sidx[r]] = hh;
+        }
+        h[r] = ok[r] ? hn : 0.f;
+        H_l[(i0 + r) * ld + u] = h[r];
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (ok[r]) a.h_last[row[r] * d + u] = h[r];
+}
+
+// grid ceil(N/16), 512 threads, dynamic LDS (2 dp + 32) (dp + 2) + 128 floats
+__global__ __launch_bounds__(64 * SEQ_A_WAVES) void attgru_seq_bwd_a(SeqBwdArgs a) {
+  extern __shared__ float smem[];
+  const int N = a.N, F = a.F, d = a.d, dp = a.dp, ld = dp + 2;
+  float* Wg_l = smem;             // [c][u] = Wg[d + c][u]
+  float* Wc_l = Wg_l + dp * ld;   // [c][u] = Wc[c][u]
+  float* Tr = Wc_l + dp * ld;     // [16][ld]: dr of the step
+  float* Tc = Tr + SEQ_RT * ld;   // [16][ld]: dhc
+  float* part = Tc + SEQ_RT * ld; // [waves][16]: d_gate shares
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int m0 = blockIdx.x * SEQ_RT;
+  for (int idx = tid; idx < dp * dp; idx += 64 * SEQ_A_WAVES) {
+    const int c = idx / dp, k = idx - c * dp;
+    const bool ok = c < d && k < d;
+    const size_t src = ok ? (size_t)c * d + k : 0;
+    const float vg = a.Wg[(size_t)d * d + src], vc = a.Wc[src];
+    Wg_l[c * ld + k] = ok ? vg : 0.f;
+    Wc_l[c * ld + k] = ok ? vc : 0.f;
+  }
+  const bool active = wave * 16 < dp;
+  const int u = wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+  float dn[4];
+  bool ok[4];
+  int64_t row[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int n = m0 + i0 + r;
+    ok[r] = n < N && u < d;
+    row[r] = n < N ? n : 0;
+    dn[r] = ok[r] ? a.d_h_last[row[r] * d + u] : 0.f;
+  }
+  __syncthreads();
+  for (int t = F - 1; t >= 0; --t) {
+    f32x4 acc0, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t sidx = ok[r] ? (row[r] * F + t) * d + u : 0;
+      const float g = a.gate[row[r] * F + t];
+      const float rr = a.S_r[sidx], hc = a.S_hc[sidx], hh = a.S_hh[sidx], hp = a.S_h[sidx];
+      float dr, dhc, dxi;
+      float pg = seq_gate_bwd(dn[r], g, rr, hc, hh, hp, dr, dhc, dxi);   // (dn is 0 off the tensor: all of these are 0 there)
+      if (ok[r]) {
+        a.G_r[sidx] = dr;
+        a.G_c[sidx] = dhc;
+        a.G_x[sidx] = dxi;
+      }
+      if (active) {
+        Tr[(i0 + r) * ld + u] = dr;
+        Tc[(i0 + r) * ld + u] = dhc;
+      }
+      pg = row16_sum(pg);           // over the wave's 16 units of row i0 + r
+      if ((lane & 15) == 0) part[wave * SEQ_RT + i0 + r] = pg;
+      acc0[r] = dn[r] * (1.f - g);
+    }
+    __syncthreads();
+    if (active) seq_mma_ab(Tr, Tc, ld, Wg_l + wave * 16 * ld, Wc_l + wave * 16 * ld, ld, dp, lane, acc0, acc1);
+    if (tid < SEQ_RT && m0 + tid < N) {
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < SEQ_A_WAVES; ++w) s += part[w * SEQ_RT + tid];
+      a.d_gate[(int64_t)(m0 + tid) * F + t] = s;
+    }
+    __syncthreads();                // Tr / Tc / part are free again
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dn[r] = ok[r] ? acc0[r] + acc1[r] : 0.f;
+  }
+  if (a.d_h0)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (ok[r]) a.d_h0[row[r] * d + u] = dn[r];
+}
+
+// ---------------------------------------------------------------- regime B
+// One step.  grid (ceil(N/16), ceil(d/64)), 256 threads.  h_prev [N] rows of stride ldp (NULL: zeros), h_new of stride ldn.
+template <bool TRAIN>
+__global__ __launch_bounds__(256) void attgru_seq_fwd_b(SeqFwdArgs a, int t, const float* __restrict__ h_prev, int64_t ldp,
+                                                        float* __restrict__ h_new, int64_t ldn, int store_prev) {
+  __shared__ float A_l[SEQ_RT * SEQ_B_LD], Bg_l[SEQ_B_CT * SEQ_B_LD], Bc_l[SEQ_B_CT * SEQ_B_LD];
+  const int N = a.N, F = a.F, d = a.d;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int m0 = blockIdx.x * SEQ_RT, c0 = blockIdx.y * SEQ_B_CT;
+  f32x4 acc_r = {0.f, 0.f, 0.f, 0.f}, acc_c = {0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < d; k0 += SEQ_B_KC) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int idx = tid + p * 256, i = idx >> 5, kk = idx & 31, n = m0 + i, k = k0 + kk;
+      float v = 0.f;
+      if (h_prev && n < N && k < d) v = h_prev[(int64_t)n * ldp + k];
+      A_l[i * SEQ_B_LD + kk] = v;
+    }
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {   // [c][kk] images of W[k][c]: read along c
+      const int idx = tid + p * 256, c = idx & 63, kk = idx >> 6, uu = c0 + c, k = k0 + kk;
+      const bool ok = uu < d && k < d;
+      const size_t src = ok ? (size_t)k * d + uu : 0;
+      const float vg = a.Wg[(size_t)d * d + src], vc = a.Wc[src];
+      Bg_l[c * SEQ_B_LD + kk] = ok ? vg : 0.f;
+      Bc_l[c * SEQ_B_LD + kk] = ok ? vc : 0.f;
+    }
+    __syncthreads();
+    seq_mma2(A_l, SEQ_B_LD, Bg_l + wave * 16 * SEQ_B_LD, Bc_l + wave * 16 * SEQ_B_LD, SEQ_B_LD, SEQ_B_KC, lane, acc_r, acc_c);
+    __syncthreads();
+  }
+  const int u = c0 + wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int n = m0 + i0 + r;
+    if (n < N && u < d) {
+      const int64_t sidx = ((int64_t)n * F + t) * d + u;
+      const float hp = h_prev ? h_prev[(int64_t)n * ldp + u] : 0.f;
+      float rr, hh;
+      const float hn = seq_gate_fwd(acc_r[r] + a.preR[sidx], acc_c[r], a.preI[sidx], a.gate[(int64_t)n * F + t], hp, rr, hh);
+      if (TRAIN) {
+        if (store_prev) a.S_h[sidx] = hp;
+        a.S_r[sidx] = rr;
+        a.S_hc[sidx] = acc_c[r];
+        a.S_hh[sidx] = hh;
+      }
+      h_new[(int64_t)n * ldn + u] = hn;
+    }
+  }
+}
+
+// One reverse step.  grid as above.  d_cur / d_next [N,d] (d_next differs from d_cur: other column tiles read d_cur)
+__global__ __launch_bounds__(256) void attgru_seq_bwd_b(SeqBwdArgs a, int t, const float* __restrict__ d_cur,
+                                                        float* __restrict__ d_next) {
+  __shared__ float Tr[SEQ_RT * SEQ_B_LD], Tc[SEQ_RT * SEQ_B_LD], Bg_l[SEQ_B_CT * SEQ_B_LD], Bc_l[SEQ_B_CT * SEQ_B_LD];
+  const int N = a.N, F = a.F, d = a.d;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int m0 = blockIdx.x * SEQ_RT, c0 = blockIdx.y * SEQ_B_CT;
+  const bool first = blockIdx.y == 0;   // the column tile that also writes the gate gradients and d_gate
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  float pg[2] = {0.f, 0.f};
+  for (int k0 = 0; k0 < d; k0 += SEQ_B_KC) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int idx = tid + p * 256, i = idx >> 5, kk = idx & 31, n = m0 + i, uu = k0 + kk;
+      float dr = 0.f, dhc = 0.f, dxi = 0.f;
+      if (n < N && uu < d) {
+        const int64_t sidx = ((int64_t)n * F + t) * d + uu;
+        pg[p] += seq_gate_bwd(d_cur[(int64_t)n * d + uu], a.gate[(int64_t)n * F + t], a.S_r[sidx], a.S_hc[sidx], a.S_hh[sidx],
+                              a.S_h[sidx], dr, dhc, dxi);
+        if (first) {
+          a.G_r[sidx] = dr;
+          a.G_c[sidx] = dhc;
+          a.G_x[sidx] = dxi;
+        }
+      }
+      Tr[i * SEQ_B_LD + kk] = dr;
+      Tc[i * SEQ_B_LD + kk] = dhc;
+    }
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {   // [c][kk] images of W[c][k]: read along k
+      const int idx = tid + p * 256, kk = idx & 31, c = idx >> 5, cc = c0 + c, k = k0 + kk;
+      const bool ok = cc < d && k < d;
+      const size_t src = ok ? (size_t)cc * d + k : 0;
+      const float vg = a.Wg[(size_t)d * d + src], vc = a.Wc[src];
+      Bg_l[c * SEQ_B_LD + kk] = ok ? vg : 0.f;
+      Bc_l[c * SEQ_B_LD + kk] = ok ? vc : 0.f;
+    }
+    __syncthreads();
+    seq_mma_ab(Tr, Tc, SEQ_B_LD, Bg_l + wave * 16 * SEQ_B_LD, Bc_l + wave * 16 * SEQ_B_LD, SEQ_B_LD, SEQ_B_KC, lane, acc0, acc1);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {     // row i = (tid >> 5) + 8 p lives in one 32-lane half: fixed-order tree inside it
+    float s = pg[p];
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    const int n = m0 + (tid >> 5) + 8 * p;
+    if (first && (tid & 31) == 0 && n < N) a.d_gate[(int64_t)n * F + t] = s;
+  }
+  const int u = c0 + wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int n = m0 + i0 + r;
+    if (n < N && u < d)
+      d_next[(int64_t)n * d + u] = d_cur[(int64_t)n * d + u] * (1.f - a.gate[(int64_t)n * F + t]) + acc0[r] + acc1[r];
+  }
+}
+
+// the five parameter gradients of an `accumulate = 0` backward start at zero (fvta_linear_bwd adds)
+__global__ __launch_bounds__(256) void attgru_seq_zero(float* dWg, float* dbg, float* dWc, float* dWi, float* dbi, int d) {
+  const int64_t dd = (int64_t)d * d, total = 4 * dd + 2 * d;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    if (i < 2 * dd) dWg[i] = 0.f;
+    else if (i < 3 * dd) dWc[i - 2 * dd] = 0.f;
+    else if (i < 4 * dd) dWi[i - 3 * dd] = 0.f;
+    else if (i < 4 * dd + d) dbg[i - 4 * dd] = 0.f;
+    else dbi[i - 4 * dd - d] = 0.f;
+  }
+}
+
+static inline int seq_dp(int d) { return (d + 15) / 16 * 16; }
+static inline bool seq_regime_a(int d) { return seq_dp(d) <= SEQ_A_DP_MAX; }
+static inline size_t seq_lds_fwd_a(int dp) { return (size_t)(2 * dp + SEQ_RT) * (dp + 2) * sizeof(float); }
+static inline size_t seq_lds_bwd_a(int dp) {
+  return ((size_t)(2 * dp + 2 * SEQ_RT) * (dp + 2) + SEQ_A_WAVES * SEQ_RT) * sizeof(float);
+}
+static_assert((2 * SEQ_A_DP_MAX + 2 * SEQ_RT) * (SEQ_A_DP_MAX + 2) * 4 + SEQ_A_WAVES * SEQ_RT * 4 <= 160 * 1024,
+              "regime A's weights and tiles must fit the 160 KiB of a CU");
+
+template <class K>
+static inline void seq_allow_lds(K kernel, size_t bytes) {  // > 64 KB of dynamic LDS is opted into per kernel symbol
+  if (bytes > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+struct SeqSaved {
+  float *S_h, *S_r, *S_hc, *S_hh;
+  size_t bytes;
+  SeqSaved(const fvta_attgru_seq_desc& d, void* p) {
+    FvtaCarver c(p);
+    const size_t n = (size_t)d.N * d.F * d.d;
+    S_h = c.take<float>(n);
+    S_r = c.take<float>(n);
+    S_hc = c.take<float>(n);
+    S_hh = c.take<float>(n);
+    bytes = c.off;
+  }
+};
+struct SeqWork {  // forward: pre_r, pre_i, two state rows (regime B without `saved`); backward: the gate gradients, two d_h rows
+  float *p0, *p1, *p2, *s0, *s1;
+  size_t bytes;
+  SeqWork(const fvta_attgru_seq_desc& d, int backward, void* p) {
+    FvtaCarver c(p);
+    const size_t n = (size_t)d.N * d.F * d.d, nd = (size_t)d.N * d.d;
+    p0 = c.take<float>(n);
+    p1 = c.take<float>(n);
+    p2 = backward ? c.take<float>(n) : nullptr;
+    s0 = c.take<float>(nd);
+    s1 = c.take<float>(nd);
+    bytes = c.off;
+  }
+};
+
+static inline bool seq_desc_ok(const fvta_attgru_seq_desc* d) { return d && d->N > 0 && d->F > 0 && d->d > 0; }
+
+}  // namespace fvta
+using namespace fvta;
+
+extern "C" size_t fvta_attgru_seq_saved_bytes(const fvta_attgru_seq_desc* d) {
+  if (!seq_desc_ok(d)) {
+    fvta_set_error("attgru_seq_saved_bytes: bad N/F/d");
+    return 0;
+  }
+  return d->training ? SeqSaved(*d, nullptr).bytes : 0;
+}
+
+extern "C" size_t fvta_attgru_seq_workspace_bytes(const fvta_attgru_seq_desc* d, int32_t backward) {
+  if (!seq_desc_ok(d)) {
+    fvta_set_error("attgru_seq_workspace_bytes: bad N/F/d");
+    return 0;
+  }
+  return SeqWork(*d, backward, nullptr).bytes;
+}
+
+extern "C" int fvta_attgru_seq_plan(const fvta_attgru_seq_desc* d, int32_t* out) {
+  FVTA_CHECK_ARG(seq_desc_ok(d), "attgru_seq_plan: bad N/F/d");
+  FVTA_CHECK_ARG(out, "attgru_seq_plan: null pointer");
+  const bool A = seq_regime_a(d->d);
+  out[0] = A ? 0 : 1;
+  out[1] = 2 + (A ? 1 : d->F);          // the two hoisted products, then the recurrence
+  out[2] = 1 + (A ? 1 : d->F) + 6;      // the fill of an accumulate = 0 call, the recurrence, fvta_linear_bwd's six kernels
+  out[3] = SEQ_RT;
+  return FVTA_OK;
+}
+
+extern "C" int fvta_attgru_seq_fwd(const fvta_attgru_seq_desc* d, const float* facts, const float* gate, const float* h0,
+                                   const float* Wg, const float* bg, const float* Wc, const float* Wi, const float* bi,
+                                   float* h_last, void* saved, void* workspace, fvta_stream_t stream_) {
+  FVTA_CHECK_ARG(seq_desc_ok(d), "attgru_seq_fwd: bad N/F/d");
+  FVTA_CHECK_ARG(facts && gate && Wg && bg && Wc && Wi && bi && h_last && workspace, "attgru_seq_fwd: null pointer");
+  FVTA_CHECK_ARG(!d->training || saved, "attgru_seq_fwd: training wants `saved`");
+  hipStream_t s = (hipStream_t)stream_;
+  const int N = d->N, F = d->F, dd = d->d;
+  SeqWork w(*d, 0, workspace);
+  SeqSaved sv(*d, d->training ? saved : nullptr);
+  const int64_t M = (int64_t)N * F;
+  int st = fvta_linear_fwd(facts, Wg, bg, w.p0, M, dd, dd, 0, stream_);   // x Wg[:d] + bg  (attention_gru_cell.py:63)
+  if (st != FVTA_OK) return st;
+  st = fvta_linear_fwd(facts, Wi, bi, w.p1, M, dd, dd, 0, stream_);       // x Wi + bi      (:68)
+  if (st != FVTA_OK) return st;
+  SeqFwdArgs a{N, F, dd, seq_dp(dd), gate, h0, Wg, Wc, w.p0, w.p1, h_last, sv.S_h, sv.S_r, sv.S_hc, sv.S_hh};
+  const unsigned row_tiles = (unsigned)((N + SEQ_RT - 1) / SEQ_RT);
+  if (seq_regime_a(dd)) {
+    const size_t lds = seq_lds_fwd_a(a.dp);
+    if (d->training) {
+      seq_allow_lds(attgru_seq_fwd_a<true>, lds);
+      hipLaunchKernelGGL(attgru_seq_fwd_a<true>, dim3(row_tiles), dim3(64 * SEQ_A_WAVES), lds, s, a);
+    } else {
+      seq_allow_lds(attgru_seq_fwd_a<false>, lds);
+      hipLaunchKernelGGL(attgru_seq_fwd_a<false>, dim3(row_tiles), dim3(64 * SEQ_A_WAVES), lds, s, a);
+    }
+  } else {
+    const dim3 grid(row_tiles, (unsigned)((dd + SEQ_B_CT - 1) / SEQ_B_CT));
+    const int64_t lds_saved = (int64_t)F * dd;
+    float* buf[2] = {w.s0, w.s1};
+    for (int t = 0; t < F; ++t) {
+      const bool last = t + 1 == F;
+      if (d->training) {   // h_t goes straight into the next step's slot of `saved`
+        const float* hp = t == 0 ? h0 : sv.S_h + (size_t)t * dd;
+        float* hn = last ? h_last : sv.S_h + (size_t)(t + 1) * dd;
+        hipLaunchKernelGGL(attgru_seq_fwd_b<true>, grid, dim3(256), 0, s, a, t, hp, t == 0 ? (int64_t)dd : lds_saved, hn,
+                           last ? (int64_t)dd : lds_saved, t == 0 ? 1 : 0);
+      } else {
+        const float* hp = t == 0 ? h0 : buf[t & 1];
+        float* hn = last ? h_last : buf[(t + 1) & 1];
+        hipLaunchKernelGGL(attgru_seq_fwd_b<false>, grid, dim3(256), 0, s, a, t, hp, (int64_t)dd, hn, (int64_t)dd, 0);
+      }
+    }
+  }
+  FVTA_CHECK_LAUNCH("attgru_seq_fwd");
+  return FVTA_OK;
+}
+
+extern "C" int fvta_attgru_seq_bwd(const fvta_attgru_seq_desc* d, const float* facts, const float* gate, const float* Wg,
+                                   const float* Wc, const float* Wi, const void* saved, const float* d_h_last,
+                                   float* d_facts, float* d_gate, float* d_h0, float* dWg, float* dbg, float* dWc,
+                                   float* dWi, float* dbi, int32_t accumulate, void* workspace, fvta_stream_t stream_) {
+  FVTA_CHECK_ARG(seq_desc_ok(d), "attgru_seq_bwd: bad N/F/d");
+  FVTA_CHECK_ARG(d->training, "attgru_seq_bwd: the forward ran with training = 0, nothing was saved");
+  FVTA_CHECK_ARG(facts && gate && Wg && Wc && Wi && saved && d_h_last && d_facts && d_gate && dWg && dbg && dWc && dWi &&
+                     dbi && workspace,
+                 "attgru_seq_bwd: null pointer");
+  hipStream_t s = (hipStream_t)stream_;
+  const int N = d->N, F = d->F, dd = d->d;
+  SeqWork w(*d, 1, workspace);
+  SeqSaved sv(*d, const_cast<void*>(saved));
+  if (!accumulate) hipLaunchKernelGGL(attgru_seq_zero, dim3(64), dim3(256), 0, s, dWg, dbg, dWc, dWi, dbi, dd);
+  SeqBwdArgs a{N, F, dd, seq_dp(dd), gate, Wg, Wc, sv.S_h, sv.S_r, sv.S_hc, sv.S_hh, d_h_last, w.p0, w.p1, w.p2, d_gate, d_h0};
+  const unsigned row_tiles = (unsigned)((N + SEQ_RT - 1) / SEQ_RT);
+  if (seq_regime_a(dd)) {
+    const size_t lds = seq_lds_bwd_a(a.dp);
+    seq_allow_lds(attgru_seq_bwd_a, lds);
+    hipLaunchKernelGGL(attgru_seq_bwd_a, dim3(row_tiles), dim3(64 * SEQ_A_WAVES), lds, s, a);
+  } else {
+    const dim3 grid(row_tiles, (unsigned)((dd + SEQ_B_CT - 1) / SEQ_B_CT));
+    float* buf[2] = {w.s0, w.s1};
+    const float* cur = d_h_last;
+    for (int t = F - 1; t >= 0; --t) {
+      float* nxt = (t == 0 && d_h0) ? d_h0 : buf[t & 1];
+      hipLaunchKernelGGL(attgru_seq_bwd_b, grid, dim3(256), 0, s, a, t, cur, nxt);
+      cur = nxt;
+    }
+  }
+  FVTA_CHECK_LAUNCH("attgru_seq_bwd");
+  // contractions over all N*F rows: d_facts = dr Wg[:d]^T + dxi Wi^T; dWg[:d], dbg, dWi, dbi from x; dWg[d:], dWc from h_{t-1}
+  const int64_t M = (int64_t)N * F;
+  const size_t dsq = (size_t)dd * dd;
+  int st = fvta_linear_bwd(facts, Wg, nullptr, w.p0, d_facts, dWg, dbg, M, dd, dd, 0, 0, stream_);
+  if (st != FVTA_OK) return st;
+  st = fvta_linear_bwd(facts, Wi, nullptr, w.p2, d_facts, dWi, dbi, M, dd, dd, 0, 1, stream_);
+  if (st != FVTA_OK) return st;
+  st = fvta_linear_bwd(sv.S_h, Wg + dsq, nullptr, w.p0, nullptr, dWg + dsq, nullptr, M, dd, dd, 0, 0, stream_);
+  if (st != FVTA_OK) return st;
+  return fvta_linear_bwd(sv.S_h, Wc, nullptr, w.p1, nullptr, dWc, nullptr, M, dd, dd, 0, 0, stream_);
+}

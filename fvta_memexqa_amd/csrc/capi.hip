@@ -31,6 +31,7 @@ extern "C" int64_t fvta_abi_struct_bytes(int32_t which) {
     case 5: return (int64_t)sizeof(fvta_imgtrans_desc);
     case 6: return (int64_t)sizeof(fvta_guard_desc);
     case 7: return (int64_t)sizeof(fvta_guard_ctl);
+    case 9: return (int64_t)sizeof(fvta_attgru_seq_desc);  // (8 stays -1: the host tests probe it as the unknown id)
     default: return -1;
   }
 }

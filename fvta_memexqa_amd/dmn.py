@@ -9,7 +9,10 @@
 
 Every hop shares the attention MLP and the AttentionGRU (the reference's reuse flags, :117, :123); each hop has its own
 dense layer ("hop_%d").  All arithmetic runs in the HIP library (feature vector, linears, softmax, the gated recurrence
-one fact per launch, relu); torch only owns the buffers.  What the reference builds AROUND this module in the DMN+
+over all facts in one fvta_attgru_seq_fwd, relu).  The class is a shell with explicit `params` / `grads` dictionaries over
+the library's one differentiable hop loop (functional.episodic_memory_raw, which nn.EpisodicMemory and
+functional.episodic_memory run too): `forward` records the autograd graph, `backward` walks it (and may walk it
+again) and ADDS the parameter gradients into `grads`.  What the reference builds AROUND this module in the DMN+
 model -- uni-directional encoders, the bi-GRU fusion of the facts, its own output layer (model_dmnplus.py:300-500,
 :518-560) -- is not built: DESIGN.md section 7.
 
@@ -19,36 +22,47 @@ memory/attention_gru/rnn/attention_gru_cell/{gates,candidate,input}/{weights[,bi
 """
 import torch
 
-from . import _lib, ops
-from .ops import check, ptr, stream_ptr
+from . import functional, ops
 
 CELL = "memory/attention_gru/rnn/attention_gru_cell/"
-CELL_VARS = (("gates/weights", lambda d: (2 * d, d)), ("gates/biases", lambda d: (d,)), ("candidate/weights", lambda d: (d, d)),
-             ("input/weights", lambda d: (d, d)), ("input/biases", lambda d: (d,)))
+CELL_VARS = functional._CELL_VARS
+ATT_VARS = ("memory/attention/fc1/weights", "memory/attention/fc1/biases", "memory/attention/fc2/weights",
+            "memory/attention/fc2/biases")
+
+
+def init_params(hidden_size, num_hops, seed=0):
+    """The 9 + 2 * num_hops variables under their TF names, on the CPU: Glorot uniform weights drawn in this order from one
+    generator, zero biases (bias_start 0.0, attention_gru_cell.py:72)."""
+    d = int(hidden_size)
+    g = torch.Generator().manual_seed(seed)
+
+    def glorot(fi, fo):
+        lim = (6.0 / (fi + fo)) ** 0.5
+        return (torch.rand(fi, fo, generator=g) * 2 - 1) * lim
+
+    p = {ATT_VARS[0]: glorot(4 * d, d), ATT_VARS[1]: torch.zeros(d), ATT_VARS[2]: glorot(d, 1), ATT_VARS[3]: torch.zeros(1)}
+    for name, shape in CELL_VARS:
+        sh = shape(d)
+        p[CELL + name] = torch.zeros(*sh) if name.endswith("biases") else glorot(*sh)
+    for i in range(int(num_hops)):
+        p["memory/hop_%d/dense/kernel" % i] = glorot(3 * d, d)
+        p["memory/hop_%d/dense/bias" % i] = torch.zeros(d)
+    return p
+
+
+def split_params(p, num_hops, prefix="memory/"):
+    """(att_vars, cell_vars, hop_vars) of functional.episodic_memory_raw out of a name -> tensor mapping"""
+    cell = prefix + CELL[len("memory/"):]
+    return (tuple(p[prefix + k[len("memory/"):]] for k in ATT_VARS), tuple(p[cell + name] for name, _ in CELL_VARS),
+            [(p[prefix + "hop_%d/dense/kernel" % i], p[prefix + "hop_%d/dense/bias" % i]) for i in range(int(num_hops))])
 
 
 class EpisodicMemory:
     def __init__(self, hidden_size, num_hops, device="cuda", seed=0):
         ops.require_gpu()
         self.d, self.num_hops, self.device = int(hidden_size), int(num_hops), torch.device(device)
-        d = self.d
-        g = torch.Generator().manual_seed(seed)
-
-        def glorot(fi, fo):
-            lim = (6.0 / (fi + fo)) ** 0.5
-            return ((torch.rand(fi, fo, generator=g) * 2 - 1) * lim).to(self.device)
-
-        zeros = lambda *s: torch.zeros(*s, device=self.device)
-        p = {"memory/attention/fc1/weights": glorot(4 * d, d), "memory/attention/fc1/biases": zeros(d),
-             "memory/attention/fc2/weights": glorot(d, 1), "memory/attention/fc2/biases": zeros(1)}
-        for name, shape in CELL_VARS:
-            sh = shape(d)
-            p[CELL + name] = zeros(*sh) if name.endswith("biases") else glorot(*sh)   # bias_start 0.0 (attention_gru_cell.py:72)
-        for i in range(self.num_hops):
-            p["memory/hop_%d/dense/kernel" % i] = glorot(3 * d, d)
-            p["memory/hop_%d/dense/bias" % i] = zeros(d)
-        self.params = p
-        self.grads = {k: torch.zeros_like(v) for k, v in p.items()}
+        self.params = {k: v.to(self.device) for k, v in init_params(self.d, self.num_hops, seed).items()}
+        self.grads = {k: torch.zeros_like(v) for k, v in self.params.items()}
         self._saved = None
 
     # ------------------------------------------------------------------ weights
@@ -66,50 +80,19 @@ class EpisodicMemory:
     # ------------------------------------------------------------------ forward
     def forward(self, gq, facts, facts_length):
         """gq [N,d] (the question vector, also the first memory), facts [N,F,d], facts_length [N] -> output [N,d]."""
-        lib, p, d = _lib.load(), self.params, self.d
+        d = self.d
         gq = gq.to(self.device, torch.float32).contiguous()
         facts = facts.to(self.device, torch.float32).contiguous()
-        N, F, _ = facts.shape
+        N = facts.shape[0]
         if gq.shape != (N, d) or facts.shape[2] != d:
             raise ValueError("EpisodicMemory: gq %s / facts %s do not fit hidden size %d" % (tuple(gq.shape), tuple(facts.shape), d))
-        live = (torch.arange(F, device=self.device)[None, :] < torch.as_tensor(facts_length).to(self.device)[:, None])
-        live = live.to(torch.float32).contiguous()                                  # dynamic_rnn's sequence_length (:130)
-        new = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
-        hops, prev = [], gq
-        for i in range(self.num_hops):
-            h = {"prev": prev}
-            # ---- _get_attention for all facts at once (:89-111), softmax over ALL F facts (:120, no mask)
-            feats = new(N, F, 4 * d)
-            check(lib.fvta_dmn_features(ptr(facts), ptr(gq), ptr(prev), ptr(feats), N, F, d, stream_ptr()), "fvta_dmn_features")
-            h["a1"] = new(N * F, d)
-            ops.linear_fwd(feats, p["memory/attention/fc1/weights"], p["memory/attention/fc1/biases"], h["a1"], N * F, 4 * d, d, True)
-            logit = new(N * F, 1)
-            ops.linear_fwd(h["a1"], p["memory/attention/fc2/weights"], p["memory/attention/fc2/biases"], logit, N * F, d, 1)
-            h["att"] = new(N, F)
-            ops.softmax_fwd(logit, h["att"], N, F)
-            # ---- the gated recurrence (:123-134): beyond a row's length dynamic_rnn copies the state through, which the
-            # cell does by itself for a gate of 0
-            g = new(N * F, 1)
-            ops.wsum_fwd(h["att"], live, g, N * F, 1, 1)
-            h["gru_in"] = torch.cat([facts, g.view(N, F, 1)], 2).contiguous()       # tf.concat([fact_vecs, attentions], 2)
-            states, saved = [torch.zeros(N, d, device=self.device)], []
-            for t in range(F):
-                x_t = h["gru_in"][:, t].contiguous()
-                s_t, sv = ops.attgru_fwd(x_t, states[-1], p[CELL + "gates/weights"], p[CELL + "gates/biases"],
-                                         p[CELL + "candidate/weights"], p[CELL + "input/weights"], p[CELL + "input/biases"])
-                states.append(s_t)
-                saved.append(sv)
-            h["states"], h["saved"] = states, saved
-            # ---- memory update (:510-514)
-            h["cat3"] = torch.cat([prev, states[-1], gq], 1).contiguous()
-            pre = new(N, d)
-            ops.linear_fwd(h["cat3"], p["memory/hop_%d/dense/kernel" % i], p["memory/hop_%d/dense/bias" % i], pre, N, 3 * d, d)
-            h["out"] = new(N, d)
-            check(lib.fvta_relu_fwd(ptr(pre), ptr(h["out"]), N * d, stream_ptr()), "fvta_relu_fwd")
-            prev = h["out"]
-            hops.append(h)
-        self._saved = (gq, facts, live, hops)
-        return prev
+        # leaves of this call's graph: views of the inputs and of `params` (shared storage, no copy)
+        leaves = {k: v.detach().requires_grad_() for k, v in self.params.items()}
+        gq_l, facts_l = gq.detach().requires_grad_(), facts.detach().requires_grad_()
+        with torch.enable_grad():
+            out = functional.episodic_memory_raw(gq_l, facts_l, facts_length, *split_params(leaves, self.num_hops))
+        self._saved = (out, gq_l, facts_l, leaves)
+        return out.detach()
 
     __call__ = forward
 
@@ -118,52 +101,11 @@ class EpisodicMemory:
         """Gradient of the last forward: returns (d_gq [N,d], d_facts [N,F,d]); parameter gradients are ADDED to self.grads."""
         if self._saved is None:
             raise RuntimeError("EpisodicMemory.backward before forward")
-        lib, p, gr, d = _lib.load(), self.params, self.grads, self.d
-        gq, facts, live, hops = self._saved
-        N, F, _ = facts.shape
-        new = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
-        d_gq = torch.zeros(N, d, device=self.device)
-        d_facts = torch.zeros(N, F, d, device=self.device)
-        d_mem = d_output.to(self.device, torch.float32).contiguous()
-        for i in reversed(range(self.num_hops)):
-            h = hops[i]
-            # ---- memory update
-            d_pre = new(N, d)
-            check(lib.fvta_relu_bwd(ptr(h["out"]), ptr(d_mem), ptr(d_pre), N * d, stream_ptr()), "fvta_relu_bwd")
-            d_cat3 = new(N, 3 * d)
-            ops.linear_bwd(h["cat3"], p["memory/hop_%d/dense/kernel" % i], h["out"], d_pre, d_cat3,
-                           gr["memory/hop_%d/dense/kernel" % i], gr["memory/hop_%d/dense/bias" % i], N, 3 * d, d)
-            d_prev = d_cat3[:, :d].contiguous()
-            d_state = d_cat3[:, d:2 * d].contiguous()
-            d_gq += d_cat3[:, 2 * d:]
-            # ---- the gated recurrence, last fact first
-            d_gru_in = new(N, F, d + 1)
-            for t in reversed(range(F)):
-                x_t = h["gru_in"][:, t].contiguous()
-                d_x, d_state = ops.attgru_bwd(x_t, h["states"][t], p[CELL + "gates/weights"], p[CELL + "candidate/weights"],
-                                              p[CELL + "input/weights"], h["saved"][t], d_state, gr[CELL + "gates/weights"],
-                                              gr[CELL + "gates/biases"], gr[CELL + "candidate/weights"],
-                                              gr[CELL + "input/weights"], gr[CELL + "input/biases"])
-                d_gru_in[:, t] = d_x
-            # (the initial state is the constant 0: d_state ends here)
-            d_facts += d_gru_in[:, :, :d]
-            d_g = d_gru_in[:, :, d].contiguous()                                      # [N,F]
-            d_att = new(N * F, 1)
-            ops.wsum_fwd(d_g, live, d_att, N * F, 1, 1)                               # d att = d g * (t < length)
-            d_logit = new(N * F, 1)
-            ops.softmax_bwd(h["att"], d_att, d_logit, N, F)
-            # ---- attention MLP
-            d_a1 = new(N * F, d)
-            logit_unused = d_logit                                                    # (no tanh on fc2: y is not read)
-            ops.linear_bwd(h["a1"], p["memory/attention/fc2/weights"], logit_unused, d_logit, d_a1,
-                           gr["memory/attention/fc2/weights"], gr["memory/attention/fc2/biases"], N * F, d, 1)
-            feats = new(N, F, 4 * d)                                                  # recomputed, not kept
-            check(lib.fvta_dmn_features(ptr(facts), ptr(gq), ptr(h["prev"]), ptr(feats), N, F, d, stream_ptr()), "fvta_dmn_features")
-            d_feats = new(N * F, 4 * d)
-            ops.linear_bwd(feats, p["memory/attention/fc1/weights"], h["a1"], d_a1, d_feats,
-                           gr["memory/attention/fc1/weights"], gr["memory/attention/fc1/biases"], N * F, 4 * d, d, True)
-            check(lib.fvta_dmn_features_bwd(ptr(facts), ptr(gq), ptr(h["prev"]), ptr(d_feats), ptr(d_facts), ptr(d_gq), ptr(d_prev),
-                                            N, F, d, stream_ptr()), "fvta_dmn_features_bwd")
-            d_mem = d_prev
-        d_gq += d_mem                                                                 # the first memory IS gq (:506)
-        return d_gq, d_facts
+        out, gq_l, facts_l, leaves = self._saved
+        names = list(leaves)
+        gs = torch.autograd.grad(out, [gq_l, facts_l] + [leaves[k] for k in names],
+                                 d_output.to(self.device, torch.float32).contiguous(), retain_graph=True, allow_unused=True)
+        for k, g in zip(names, gs[2:]):
+            if g is not None:
+                self.grads[k] += g
+        return gs[0], gs[1]

@@ -15,6 +15,11 @@
     context_tensor(streams, masks=None) -> (hall, hall_mask)                         model_v2.py:863-914
     time_warp(hall, lq, warp_type=1, window_t=None, scope=None) -> (warp_h, scale)   model_v2.py:953-1009
     time_indication_func(C, warp_type=1, window_t=3.0) -> (C_windowed, window_t)     model_v2.py:301-341
+    generate_episode(memory, q_vec, fact_vecs, fact_vecs_length, hop_index,
+                     hidden_size, scope=None) -> episode [N,d]                       model_dmnplus.py:113-136
+    episodic_memory(gq, facts, facts_length, num_hops, hidden_size,
+                    scope="memory") -> [N,hidden_size]                               model_dmnplus.py:503-516
+      (generate_episode_raw / episodic_memory_raw: the same with explicit variables)
 
 Tensors are torch CUDA tensors; every op is one call into libfvta_hip.so, wrapped in a `torch.autograd.Function`
 (autograd.py): a tensor that requires grad gets its gradient through the library's backward kernels, and when nothing
@@ -430,45 +435,86 @@ def time_indication_func(C, warp_type=1, window_t=3.0):
     return out, (window_t if warp_type == 5 else None)
 
 
-# ------------------------------------------------------------------ DMN+ episode (model_dmnplus.py:89-136)
+# ------------------------------------------------------------------ DMN+ episodic memory (model_dmnplus.py:89-136, 503-516)
+_CELL_VARS = (("gates/weights", lambda d: (2 * d, d)), ("gates/biases", lambda d: (d,)), ("candidate/weights", lambda d: (d, d)),
+              ("input/weights", lambda d: (d, d)), ("input/biases", lambda d: (d,)))
+
+
+def get_attention_raw(q_vec, prev_memory, fact_vecs, W1, b1, W2, b2):
+    """model_dmnplus.py:89-111 for ALL facts at once with explicit fc1 / fc2 variables: facts [N,F,d] -> logits [N,F].
+    Differentiable in the facts, the question, the memory and the four variables."""
+    N, F, d = fact_vecs.shape
+    feats = autograd.dmn_features(fact_vecs, q_vec, prev_memory)
+    a1 = linear_raw(feats, W1, b1, add_tanh=True)
+    return linear_raw(a1, W2, b2).reshape(N, F)
+
+
+def generate_episode_raw(memory, q_vec, fact_vecs, fact_vecs_length, att_vars, cell_vars):
+    """model_dmnplus.py:113-136 with explicit variables: att_vars = (fc1 W, fc1 b, fc2 W, fc2 b), cell_vars = (gates W,
+    gates b, candidate W, input W, input b).  The ONE episode of the library: generate_episode, episodic_memory,
+    nn.EpisodicMemory and dmn.EpisodicMemory all run it."""
+    fact_vecs = _f32(fact_vecs)
+    N, F, d = fact_vecs.shape
+    att = softmax(get_attention_raw(q_vec, memory, fact_vecs, *att_vars))                     # [N,F], over ALL facts (:120)
+    live = (torch.arange(F, device=att.device)[None, :] < torch.as_tensor(fact_vecs_length).to(att.device)[:, None])
+    g = _wsum(att.reshape(N * F, 1, 1), live.to(torch.float32).reshape(N * F, 1)).reshape(N, F)   # att * (t < length)
+    return autograd.attgru_seq(fact_vecs, g, None, *cell_vars)                                # dynamic_rnn, zero state (:127-131)
+
+
+def episodic_memory_raw(gq, facts, facts_length, att_vars, cell_vars, hop_vars):
+    """model_dmnplus.py:503-516, the ONE hop loop of the library: hop_vars = [(kernel [3d,d], bias [d])] per hop."""
+    prev = gq = _f32(gq)
+    for kernel, bias in hop_vars:
+        episode = generate_episode_raw(prev, gq, facts, facts_length, att_vars, cell_vars)
+        prev = autograd.relu(linear_raw(torch.cat([prev, episode, gq], 1), kernel, bias))     # :510-514
+    return prev
+
+
 def _get_attention(q_vec, prev_memory, fact_vecs, hidden_size):
     """model_dmnplus.py:89-111 for ALL facts at once (the reference unstacks the facts and reuses the two
     fully_connected layers): facts [N,F,d] -> attention logits [N,F].  Variables attention/fc1/{weights,biases}
     (tanh), attention/fc2/{weights,biases} (tf.contrib.layers.fully_connected: Glorot weights, zero biases)."""
-    N, F, d = fact_vecs.shape
-    feats = torch.empty(N, F, 4 * d, dtype=torch.float32, device=fact_vecs.device)
-    check(_lib.load().fvta_dmn_features(ptr(_f32(fact_vecs)), ptr(_f32(q_vec)), ptr(_f32(prev_memory)), ptr(feats), N, F, d,
-                                        stream_ptr()), "fvta_dmn_features")
+    return get_attention_raw(_f32(q_vec), _f32(prev_memory), _f32(fact_vecs), *_attention_vars(fact_vecs.shape[2], hidden_size))
+
+
+def _attention_vars(d, hidden_size):
     with variable_scope("attention"):
         W1 = get_variable(_name("fc1", "weights"), (4 * d, hidden_size), init="glorot")
         b1 = get_variable(_name("fc1", "biases"), (hidden_size,), init="zeros")
         W2 = get_variable(_name("fc2", "weights"), (hidden_size, 1), init="glorot")
         b2 = get_variable(_name("fc2", "biases"), (1,), init="zeros")
-    a1 = linear_raw(feats, W1, b1, add_tanh=True)
-    return linear_raw(a1, W2, b2).reshape(N, F)
+    return W1, b1, W2, b2
+
+
+def _cell_vars(d):
+    with variable_scope("attention_gru"):
+        return tuple(get_variable(_name("attention_gru_cell", n_), sh(d), init="zeros" if n_.endswith("biases") else "glorot")
+                     for n_, sh in _CELL_VARS)
 
 
 def generate_episode(memory, q_vec, fact_vecs, fact_vecs_length, hop_index, hidden_size, scope=None):
     """model_dmnplus.py:113-136 `_generate_episode`: attention over the facts from (question, previous memory), softmax
     over ALL F facts (no mask in the reference), then the AttentionGRUCell (attention_gru_cell.py:50-70) run by
     dynamic_rnn over the facts with sequence_length: the state is carried past a row's length -- which the cell does by
-    itself when the attention gate is 0, so the gates of steps >= length are zeroed.  Returns the episode [N,d].
+    itself when the attention gate is 0, so the gates of steps >= length are zeroed.  Returns the episode [N,d],
+    differentiable in the facts, the question, the memory and the nine variables (autograd.dmn_features, .attgru_seq).
     Variables live under the current scope (hop_index > 0 reuses them, as the reference's reuse flags do)."""
-    from .attention_gru_cell import AttentionGRUCell
-    fact_vecs = _f32(fact_vecs)
-    N, F, d = fact_vecs.shape
+    d = fact_vecs.shape[2]
     with variable_scope(scope):
-        att = softmax(_get_attention(q_vec, memory, fact_vecs, hidden_size))                  # [N,F]
-        live = (torch.arange(F, device=att.device)[None, :] < fact_vecs_length.to(att.device)[:, None]).to(torch.float32)
-        g = _wsum(att.reshape(N * F, 1, 1), live.reshape(N * F, 1)).reshape(N, F, 1)          # att * (t < length)
-        gru_inputs = torch.cat([fact_vecs, g], 2).contiguous()                               # [N,F,d+1] (tf.concat)
-        with variable_scope("attention_gru"):
-            cell = AttentionGRUCell(hidden_size)
-            names = ("gates/weights", "gates/biases", "candidate/weights", "input/weights", "input/biases")
-            shapes = ((2 * d, d), (d,), (d, d), (d, d), (d,))
-            params = {n_: get_variable(_name("attention_gru_cell", n_), sh, init="zeros" if n_.endswith("biases") else "glorot")
-                      for n_, sh in zip(names, shapes)}
-        state = torch.zeros(N, d, dtype=torch.float32, device=att.device)
-        for t in range(F):
-            state, _ = cell(gru_inputs[:, t].contiguous(), state, params)
-    return state
+        att_vars = _attention_vars(d, hidden_size)
+        cell_vars = _cell_vars(d)
+    return generate_episode_raw(memory, q_vec, fact_vecs, fact_vecs_length, att_vars, cell_vars)
+
+
+def episodic_memory(gq, facts, facts_length, num_hops, hidden_size, scope="memory"):
+    """model_dmnplus.py:503-516: prev_memory = gq; per hop, episode = generate_episode(prev_memory, gq, facts, ...) and
+    prev_memory = relu(dense(concat([prev_memory, episode, gq], 1), hidden_size)) with its own `hop_<i>/dense/{kernel,
+    bias}` (tf.layers.dense: Glorot / zeros); the attention MLP and the AttentionGRU are shared by the hops.  gq [N,d],
+    facts [N,F,d], facts_length [N] -> [N,hidden_size], differentiable in everything."""
+    d = facts.shape[2]
+    with variable_scope(scope):
+        att_vars = _attention_vars(d, hidden_size)
+        cell_vars = _cell_vars(d)
+        hop_vars = [(get_variable(_name("hop_%d" % i, "dense", "kernel"), (3 * d, hidden_size), init="glorot"),
+                     get_variable(_name("hop_%d" % i, "dense", "bias"), (hidden_size,), init="zeros")) for i in range(int(num_hops))]
+    return episodic_memory_raw(gq, facts, facts_length, att_vars, cell_vars, hop_vars)

@@ -240,3 +240,46 @@ class PhotoFeatures(_Module):
             return autograd.photo_features(pis, image_emb_mat)
         return autograd.photo_features(pis, image_emb_mat, self.p("image_transform/image_trans_linear/W"),
                                        self.p("image_transform/image_trans_linear/b"), self.add_tanh)
+
+
+class AttentionGRU(_Module):
+    """The AttentionGRUCell (attention_gru_cell.py:50-70) run over a whole fact sequence, the state carried:
+    forward(facts [N,F,hidden], gate [N,F], h0 [N,hidden] | None) -> h_last [N,hidden] (autograd.attgru_seq, one library
+    call each way).  A gate of 0 copies the state through, so a caller masks the gates of steps past a row's length.
+    Parameters `attention_gru_cell/{gates/weights [2h,h], gates/biases [h], candidate/weights [h,h], input/weights [h,h],
+    input/biases [h]}`: Glorot uniform / zeros (bias_start 0.0, :72)."""
+
+    def __init__(self, hidden, seed=None):
+        super().__init__()
+        self.hidden = int(hidden)
+        for i, (name, shape) in enumerate(functional._CELL_VARS):
+            name = "attention_gru_cell/" + name
+            sh = shape(self.hidden)
+            self._param(name, torch.zeros(sh) if name.endswith("biases") else
+                        _glorot(_gen(name, None if seed is None else seed + i), *sh))
+
+    def forward(self, facts, gate, h0=None):
+        if facts.shape[-1] != self.hidden:
+            raise ValueError("AttentionGRU: facts %s do not fit hidden size %d" % (tuple(facts.shape), self.hidden))
+        return autograd.attgru_seq(facts, gate, h0, *(self.p("attention_gru_cell/" + name) for name, _ in functional._CELL_VARS))
+
+
+class EpisodicMemory(_Module):
+    """The DMN+ episodic memory (model_dmnplus.py:503-516 over `_generate_episode` :113-136): forward(gq [N,hidden],
+    facts [N,F,hidden], facts_length [N]) -> [N,hidden], differentiable in everything.  Parameters under dmn.py's names
+    without the `memory/` scope -- `attention/fc{1,2}/{weights,biases}`, `attention_gru/rnn/attention_gru_cell/...`,
+    `hop_<i>/dense/{kernel,bias}` -- and initialised like dmn.EpisodicMemory (the same draws for the same seed)."""
+
+    def __init__(self, hidden, num_hops, seed=None):
+        super().__init__()
+        from . import dmn
+        self.hidden, self.num_hops = int(hidden), int(num_hops)
+        seed = zlib.crc32(b"memory") if seed is None else int(seed)
+        for k, v in dmn.init_params(self.hidden, self.num_hops, seed).items():
+            self._param(k[len("memory/"):], v)
+
+    def forward(self, gq, facts, facts_length):
+        from . import dmn
+        if gq.shape[-1] != self.hidden or facts.shape[-1] != self.hidden:
+            raise ValueError("EpisodicMemory: gq %s / facts %s do not fit hidden size %d" % (tuple(gq.shape), tuple(facts.shape), self.hidden))
+        return functional.episodic_memory_raw(gq, facts, facts_length, *dmn.split_params(self._parameters, self.num_hops, prefix=""))

@@ -9,8 +9,8 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import (F32, BF16, AttnDesc, EmbedDesc, ImgTransDesc, LstmDesc, ScorerDesc, TimewarpDesc, check, ptr,
-                   stream_ptr)
+from ._lib import (F32, BF16, AttGruSeqDesc, AttnDesc, EmbedDesc, ImgTransDesc, LstmDesc, ScorerDesc, TimewarpDesc, check,
+                   ptr, stream_ptr)
 
 
 def require_gpu():
@@ -471,6 +471,55 @@ def attgru_bwd(inputs, state, Wg, Wc, Wi, saved, d_new_h, dWg, dbg, dWc, dWi, db
                               ptr(d_inputs), ptr(d_state), ptr(dWg), ptr(dbg), ptr(dWc), ptr(dWi), ptr(dbi), ptr(ws),
                               stream_ptr()), "fvta_attgru_bwd")
     return d_inputs, d_state
+
+
+def attgru_seq_plan(N, F, d):
+    """How the library runs the AttentionGRU over F facts at this shape (fvta_attgru_seq_plan; a host query, no GPU):
+    regime "A" (the whole recurrence in one launch) or "B" (one fused launch per step), kernel launches of a forward and
+    of a backward, rows of a workgroup tile."""
+    out = (ctypes.c_int32 * 4)()
+    check(_lib.load().fvta_attgru_seq_plan(ctypes.byref(AttGruSeqDesc(N, F, d, 1)), out), "fvta_attgru_seq_plan")
+    return dict(regime="AB"[out[0]], fwd_launches=out[1], bwd_launches=out[2], row_tile=out[3])
+
+
+class AttentionGRUSeq:
+    """F steps of the AttentionGRUCell with the state carried (dynamic_rnn over the facts, model_dmnplus.py:123-134):
+    facts [N,F,d], gate [N,F], h0 [N,d] | None -> h_last [N,d].  training=False keeps nothing (`saved` stays None)."""
+
+    def __init__(self, N, F, d, training=True):
+        self.lib = _lib.load()
+        self.dev = require_gpu()
+        self.N, self.F, self.d = int(N), int(F), int(d)
+        self.desc = AttGruSeqDesc(self.N, self.F, self.d, int(bool(training)))
+        self.saved = None
+
+    def _work(self, backward):
+        nb = self.lib.fvta_attgru_seq_workspace_bytes(ctypes.byref(self.desc), int(backward))
+        if nb == 0:
+            raise _lib.FvtaError("attgru_seq: " + self.lib.fvta_last_error().decode())
+        return _bytes(nb, self.dev)
+
+    def forward(self, facts, gate, h0, Wg, bg, Wc, Wi, bi):
+        h_last = torch.empty(self.N, self.d, dtype=torch.float32, device=self.dev)
+        work = self._work(False)
+        if self.desc.training:
+            self.saved = _bytes(self.lib.fvta_attgru_seq_saved_bytes(ctypes.byref(self.desc)), self.dev)
+        check(self.lib.fvta_attgru_seq_fwd(ctypes.byref(self.desc), ptr(_f32c(facts)), ptr(_f32c(gate)),
+                                           ptr(None if h0 is None else _f32c(h0)), ptr(_f32c(Wg)), ptr(_f32c(bg)),
+                                           ptr(_f32c(Wc)), ptr(_f32c(Wi)), ptr(_f32c(bi)), ptr(h_last), ptr(self.saved),
+                                           ptr(work), stream_ptr()), "fvta_attgru_seq_fwd")
+        return h_last
+
+    def backward(self, facts, gate, Wg, Wc, Wi, d_h_last, d_facts, d_gate, d_h0, dWg, dbg, dWc, dWi, dbi, accumulate=False):
+        """d_facts, d_gate, d_h0 (may be None) are overwritten; the parameter gradients stored, or added to under
+        `accumulate`.  `saved` is only read: the call may be repeated."""
+        if self.saved is None:
+            raise _lib.FvtaError("AttentionGRUSeq.backward: no training forward ran")
+        work = self._work(True)
+        check(self.lib.fvta_attgru_seq_bwd(ctypes.byref(self.desc), ptr(facts), ptr(gate), ptr(Wg), ptr(Wc), ptr(Wi),
+                                           ptr(self.saved), ptr(_f32c(d_h_last)), ptr(d_facts), ptr(d_gate), ptr(d_h0),
+                                           ptr(dWg), ptr(dbg), ptr(dWc), ptr(dWi), ptr(dbi), int(accumulate), ptr(work),
+                                           stream_ptr()), "fvta_attgru_seq_bwd")
 
 
 # ------------------------------------------------------------------ time warp

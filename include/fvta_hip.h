@@ -46,7 +46,8 @@ int fvta_version(void);
 const char* fvta_last_error(void);
 /* sizeof of a descriptor struct as the library was compiled: which = 0 fvta_attn_desc, 1 fvta_lstm_desc,
  * 2 fvta_scorer_desc, 3 fvta_timewarp_desc, 4 fvta_embed_desc, 5 fvta_imgtrans_desc, 6 fvta_guard_desc,
- * 7 fvta_guard_ctl; -1 otherwise.  A binding compares
+ * 7 fvta_guard_ctl, 9 fvta_attgru_seq_desc (8 stays unassigned: bindings probe it as the unknown id); -1 otherwise.
+ * A binding compares
  * its own layout with it when it loads the library (fvta_memexqa_amd/_lib.py does). */
 int64_t fvta_abi_struct_bytes(int32_t which);
 
@@ -293,6 +294,37 @@ int fvta_attgru_bwd(int32_t B, int32_t d, const float* inputs, const float* stat
                     float* dbi, void* workspace /* B*4d floats */, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ * The AttentionGRU over a whole fact sequence: exactly F applications of the cell above with the state carried between
+ * them (dynamic_rnn over the facts, model_dmnplus.py:123-134), forward and backward.
+ *   facts [N,F,d]  gate [N,F] (the attention times `t < length`: a gate of 0 copies the state through, so the op takes
+ *   no lengths)  h0 [N,d] or NULL (zeros)  Wg [2d,d] bg [d] Wc [d,d] Wi [d,d] bi [d]  ->  h_last [N,d]
+ * The input-side products run once for all N*F rows ahead of the recurrence, the parameter and fact gradients as
+ * contractions over all N*F rows after the reverse recurrence.  The recurrence has two regimes, by d (fvta_attgru_seq_plan):
+ *   0: every d <= 128 -- ONE launch for all F steps, [Wg[d:] | Wc] resident in LDS, the state tile on chip;
+ *   1: larger d -- one fused launch per step (state-side product + gate math; backward: gate gradient + d_h product).
+ * Exact fp32 (v_mfma_f32_16x16x4_f32), no atomics, fixed summation order: two runs are bitwise equal.
+ * training = 0: nothing is saved, `saved` may be NULL, and there is no backward.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int32_t N, F, d;
+  int32_t training; /* 1: the forward fills `saved` for fvta_attgru_seq_bwd */
+} fvta_attgru_seq_desc;
+
+size_t fvta_attgru_seq_saved_bytes(const fvta_attgru_seq_desc* d); /* 0 with training = 0 */
+size_t fvta_attgru_seq_workspace_bytes(const fvta_attgru_seq_desc* d, int32_t backward); /* 0: of _fwd, 1: of _bwd */
+/* out[4] = {regime (0 / 1), launches of a forward, launches of a backward with accumulate = 0, rows per workgroup tile} */
+int fvta_attgru_seq_plan(const fvta_attgru_seq_desc* d, int32_t* out);
+int fvta_attgru_seq_fwd(const fvta_attgru_seq_desc* d, const float* facts, const float* gate, const float* h0,
+                        const float* Wg, const float* bg, const float* Wc, const float* Wi, const float* bi,
+                        float* h_last, void* saved, void* workspace, fvta_stream_t stream);
+/* From d_h_last [N,d]: d_facts [N,F,d], d_gate [N,F] and d_h0 [N,d] (may be NULL) are overwritten; dWg, dbg, dWc, dWi,
+ * dbi are stored (accumulate = 0) or added to (1).  `saved` is only read: a second backward gives the same result. */
+int fvta_attgru_seq_bwd(const fvta_attgru_seq_desc* d, const float* facts, const float* gate, const float* Wg,
+                        const float* Wc, const float* Wi, const void* saved, const float* d_h_last, float* d_facts,
+                        float* d_gate, float* d_h0, float* dWg, float* dbg, float* dWc, float* dWi, float* dbi,
+                        int32_t accumulate, void* workspace, fvta_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  * Time warp of the context tensor: model_v2.py:953-1009 with the indicator of
  * time_indication_func (301-341), in the closed form the reference's expression
  * reduces to:  warp_h[n,k,t,:] = hall[n,k,t,:] * c[n,t] * cnt(t).
@@ -527,7 +559,7 @@ int fvta_wsum_bwd(const float* target, const float* weights, const float* d_out,
 /* The feature vector of the DMN+ episode attention, model_dmnplus.py:93-98 (`_get_attention`), for all facts at once:
  * out[n,f,:] = [fact*q, fact*m, |fact-q|, |fact-m|]  (facts [N,F,d], q / m [N,d] -> out [N,F,4d]).  The two
  * fully_connected layers on top of it are fvta_linear_fwd, the softmax over facts fvta_softmax_fwd, the gated recurrence
- * fvta_attgru_fwd per fact (functional.generate_episode). */
+ * fvta_attgru_seq_fwd over all facts (functional.generate_episode). */
 int fvta_dmn_features(const float* facts, const float* q, const float* m, float* out, int32_t N, int32_t F, int32_t d,
                       fvta_stream_t stream);
 /* Its backward (d_out [N,F,4d]): d_facts [N,F,d], d_q and d_m [N,d] are ACCUMULATED into (the facts and the question feed

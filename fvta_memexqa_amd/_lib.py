@@ -49,6 +49,10 @@ class AttGruSeqDesc(Structure):
     _fields_ = [(n, c_int32) for n in ("N", "F", "d", "training")]
 
 
+class GruSeqDesc(Structure):
+    _fields_ = [(n, c_int32) for n in ("N", "T", "in_dim", "d", "reverse", "training")]
+
+
 CTX_KMAX = 8
 
 
@@ -107,6 +111,11 @@ _SIGS = {
     "fvta_attgru_seq_plan": (c_int, [POINTER(AttGruSeqDesc), POINTER(c_int32)]),
     "fvta_attgru_seq_fwd": (c_int, [POINTER(AttGruSeqDesc), P, P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_attgru_seq_bwd": (c_int, [POINTER(AttGruSeqDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int32, P, P]),
+    "fvta_gru_seq_saved_bytes": (c_size_t, [POINTER(GruSeqDesc)]),
+    "fvta_gru_seq_workspace_bytes": (c_size_t, [POINTER(GruSeqDesc), c_int32]),
+    "fvta_gru_seq_plan": (c_int, [POINTER(GruSeqDesc), POINTER(c_int32)]),
+    "fvta_gru_seq_fwd": (c_int, [POINTER(GruSeqDesc), P, P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_gru_seq_bwd": (c_int, [POINTER(GruSeqDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, c_int32, P, P]),
     "fvta_timewarp_workspace_bytes": (c_size_t, [POINTER(TimewarpDesc)]),
     "fvta_timewarp_fwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_bwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
@@ -192,7 +201,7 @@ def load():
         fn.argtypes = args
     # the descriptor structs are declared twice (include/fvta_hip.h and above): refuse a library whose layout differs
     for which, cls in list(enumerate((AttnDesc, LstmDesc, ScorerDesc, TimewarpDesc, EmbedDesc, ImgTransDesc, GuardDesc, GuardCtl))) + \
-            [(9, AttGruSeqDesc)]:
+            [(9, AttGruSeqDesc), (10, GruSeqDesc)]:
         have, want = ctypes.sizeof(cls), lib.fvta_abi_struct_bytes(which)
         if have != want:
             raise FvtaError("%s is %d bytes here but %d in %s: rebuild the library (descriptor layouts differ)"

@@ -592,6 +592,57 @@ def attgru_seq(facts, gate, h0, Wg, bg, Wc, Wi, bi):
     return _AttGruSeq.apply(f(facts), f(gate), f(h0), f(Wg), f(bg), f(Wc), f(Wi), f(bi))
 
 
+class _GruSeq(torch.autograd.Function):
+    """(x [N,T,in], lens int32 [N] | None, h0 [N,d] | None, Wg [in+d,2d], bg [2d], Wc [in+d,d], bc [d], reverse) ->
+    (out [N,T,d], h_last [N,d]): TF's GRUCell under dynamic_rnn, one fvta_gru_seq_fwd.  Each call owns its ops.GRUSeq and
+    with it `saved`; the backward (one fvta_gru_seq_bwd) only reads it, so a retained graph may be walked again.  An output
+    nobody used arrives as a None gradient and goes down as NULL."""
+
+    @staticmethod
+    def forward(ctx, x, lens, h0, Wg, bg, Wc, bc, reverse):
+        N, T, din = x.shape
+        d = Wc.shape[1]
+        need = any(ctx.needs_input_grad)
+        op = ops.GRUSeq(N, T, din, d, reverse=reverse, training=need)
+        out, h_last = op.forward(x, lens, h0, Wg, bg, Wc, bc)
+        ctx.set_materialize_grads(False)
+        if need:
+            ctx.op = op
+            ctx.save_for_backward(x, lens, Wg, Wc)
+        return out, h_last
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_last):
+        if g_out is None and g_last is None:
+            return (None,) * 8
+        x, lens, Wg, Wc = ctx.saved_tensors
+        N, T, din = x.shape
+        d = Wc.shape[1]
+        need = ctx.needs_input_grad
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=x.device)
+        d_x = new(N, T, din)
+        d_h0 = new(N, d) if need[2] else None
+        dWg, dbg, dWc, dbc = new(din + d, 2 * d), new(2 * d), new(din + d, d), new(d)     # stored: accumulate = 0
+        ctx.op.backward(x, lens, Wg, Wc, _c(g_out), _c(g_last), d_x, d_h0, dWg, dbg, dWc, dbc, accumulate=False)
+        grads = (d_x, None, d_h0, dWg, dbg, dWc, dbc, None)
+        return tuple(t if n else None for t, n in zip(grads, need))
+
+
+def gru_seq(x, lens, h0, Wg, bg, Wc, bc, reverse=False):
+    """x [N,T,in], lens [N] (any integer tensor or list) or None (every row has length T), h0 [N,d] or None (zeros), TF's
+    GRUCell variables gates/{kernel [in+d,2d], bias [2d]} and candidate/{kernel [in+d,d], bias [d]} -> (out [N,T,d] with
+    rows t >= lens[n] zero, h_last [N,d]); reverse=True walks every row from lens[n] - 1 down to 0."""
+    dev = ops.require_gpu()
+    f = lambda t: None if t is None else t.to(torch.float32).contiguous()
+    if lens is not None:
+        lens = torch.as_tensor(lens).to(dev, torch.int32).contiguous()
+    x, Wg, Wc = f(x), f(Wg), f(Wc)
+    if x.dim() != 3 or Wc.dim() != 2 or Wc.shape[0] != x.shape[2] + Wc.shape[1] or tuple(Wg.shape) != (Wc.shape[0], 2 * Wc.shape[1]):
+        raise ValueError("gru_seq: x %s, gates kernel %s, candidate kernel %s do not fit" % (tuple(x.shape), tuple(Wg.shape), tuple(Wc.shape)))
+    return _GruSeq.apply(x, lens, f(h0), Wg, f(bg), Wc, f(bc), bool(reverse))
+
+
 class _DmnFeatures(torch.autograd.Function):
     """(facts [N,F,d], q [N,d], m [N,d]) -> [N,F,4d] = [fact*q, fact*m, |fact-q|, |fact-m|] (model_dmnplus.py:93-98,
     fvta_dmn_features); backward: fvta_dmn_features_bwd into fresh zero buffers (it accumulates)."""

@@ -15,16 +15,12 @@
 //     state-side product with the gate math as its epilogue; in the backward the gate gradient (recomputed per column
 //     tile while the A operand is staged) with the d_h product.  Issued F times from one C call, ordered by the stream.
 // No atomics, fixed summation order: two runs are bitwise equal.  The backward only reads `saved`.
-#include "fvta_common.h"
+#include "seq_common.h"
 
 namespace fvta {
 
-constexpr int SEQ_RT = 16;          // rows of a workgroup tile
 constexpr int SEQ_A_WAVES = 8;      // regime A: one wave per 16-unit column tile
 constexpr int SEQ_A_DP_MAX = 16 * SEQ_A_WAVES;
-constexpr int SEQ_B_KC = 32;        // regime B: k-chunk staged through LDS
-constexpr int SEQ_B_CT = 64;        // regime B: units per workgroup (4 waves x 16)
-constexpr int SEQ_B_LD = SEQ_B_KC + 2;
 
 struct SeqFwdArgs {
   int N, F, d, dp;
@@ -36,29 +32,6 @@ struct SeqBwdArgs {
   const float *gate, *Wg, *Wc, *S_h, *S_r, *S_hc, *S_hh, *d_h_last;
   float *G_r, *G_c, *G_x, *d_gate, *d_h0;
 };
-
-// acc += A[16][K] * B[16][K]^T for LDS images whose rows are k-contiguous (ld = 2 mod 32: lanes 0..31 hit 32 banks).
-// lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15] = image[j][k]
-__device__ __forceinline__ void seq_mma2(const float* __restrict__ A, int lda, const float* __restrict__ B0,
-                                         const float* __restrict__ B1, int ldb, int K, int lane, f32x4& acc0, f32x4& acc1) {
-  const float* ap = A + (lane & 15) * lda + (lane >> 4);
-  const float* b0 = B0 + (lane & 15) * ldb + (lane >> 4);
-  const float* b1 = B1 + (lane & 15) * ldb + (lane >> 4);
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    const float av = ap[k0];
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b0[k0], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b1[k0], acc1, 0, 0, 0);
-  }
-}
-__device__ __forceinline__ void seq_mma_ab(const float* __restrict__ A0, const float* __restrict__ A1, int lda,
-                                           const float* __restrict__ B0, const float* __restrict__ B1, int ldb, int K,
-                                           int lane, f32x4& acc0, f32x4& acc1) {
-  const int o = (lane & 15) * lda + (lane >> 4), ob = (lane & 15) * ldb + (lane >> 4);
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(A0[o + k0], B0[ob + k0], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(A1[o + k0], B1[ob + k0], acc1, 0, 0, 0);
-  }
-}
 
 // one element of the cell: returns h_t; r and hh come back for `saved`.  The two fused multiply-adds are spelled out: left
 // to the compiler, the training and the inference instantiation contracted (1 - g) h + g hh differently (one bit apart).

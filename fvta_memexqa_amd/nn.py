@@ -283,3 +283,100 @@ class EpisodicMemory(_Module):
         if gq.shape[-1] != self.hidden or facts.shape[-1] != self.hidden:
             raise ValueError("EpisodicMemory: gq %s / facts %s do not fit hidden size %d" % (tuple(gq.shape), tuple(facts.shape), self.hidden))
         return functional.episodic_memory_raw(gq, facts, facts_length, *dmn.split_params(self._parameters, self.num_hops, prefix=""))
+
+
+_GRU_VARS = ("gru_cell/gates/kernel", "gru_cell/gates/bias", "gru_cell/candidate/kernel", "gru_cell/candidate/bias")
+
+
+def _gru_cell_init(in_dim, hidden, prefix, seed):
+    """tf.nn.rnn_cell.GRUCell's four variables as TF creates them: Glorot uniform kernels (tf.get_variable's default), the
+    gate bias 1, the candidate bias 0"""
+    sd = lambda name, i: _gen(name, None if seed is None else seed + i)
+    gk, ck = prefix + _GRU_VARS[0], prefix + _GRU_VARS[2]
+    return {gk: _glorot(sd(gk, 0), in_dim + hidden, 2 * hidden), prefix + _GRU_VARS[1]: torch.ones(2 * hidden),
+            ck: _glorot(sd(ck, 1), in_dim + hidden, hidden), prefix + _GRU_VARS[3]: torch.zeros(hidden)}
+
+
+class GRUEncoder(_Module):
+    """One dynamic_rnn over tf.nn.rnn_cell.GRUCell (the uni-directional encoders of model_dmnplus.py:344-440):
+    forward(x [..., T, in_dim], lens [...]) -> (out [..., T, hidden] with rows t >= len zero, last [..., hidden]), one
+    autograd.gru_seq over all leading axes flattened.  Parameters `gru_cell/gates/{kernel [in_dim+hidden, 2*hidden], bias
+    [2*hidden]}` and `gru_cell/candidate/{kernel [in_dim+hidden, hidden], bias [hidden]}`: Glorot uniform kernels, the gate
+    bias 1, the candidate bias 0 (TF's initialisers).  reverse=True walks every row from its last valid step down."""
+
+    def __init__(self, in_dim, hidden, reverse=False, seed=None):
+        super().__init__()
+        self.in_dim, self.hidden, self.reverse = int(in_dim), int(hidden), bool(reverse)
+        for k, v in _gru_cell_init(self.in_dim, self.hidden, "", seed).items():
+            self._param(k, v)
+
+    def forward(self, x, lens=None, h0=None):
+        if x.shape[-1] != self.in_dim:
+            raise ValueError("GRUEncoder: x %s does not fit in_dim %d" % (tuple(x.shape), self.in_dim))
+        lead, T = tuple(x.shape[:-2]), x.shape[-2]
+        out, last = autograd.gru_seq(x.reshape(-1, T, self.in_dim), None if lens is None else torch.as_tensor(lens).reshape(-1),
+                                     None if h0 is None else h0.reshape(-1, self.hidden), *(self.p(n) for n in _GRU_VARS),
+                                     reverse=self.reverse)
+        return out.reshape(lead + (T, self.hidden)), last.reshape(lead + (self.hidden,))
+
+
+def _bigru_sum(f_in, lens, fw_vars, bw_vars):
+    """bidirectional_dynamic_rnn over two GRUCells, the two output sequences summed (model_dmnplus.py:478-486)"""
+    fw, _ = autograd.gru_seq(f_in, lens, None, *fw_vars, reverse=False)
+    bw, _ = autograd.gru_seq(f_in, lens, None, *bw_vars, reverse=True)
+    return fw + bw
+
+
+class BiGRUFusion(_Module):
+    """The fusion of the facts (model_dmnplus.py:470-486): forward(f_in [N,F,hidden], lens [N]) -> [N,F,hidden] = the
+    forward GRU's outputs + the backward GRU's, rows past a length zero.  Two autograd.gru_seq calls and one torch add.
+    Parameters `{fw,bw}/gru_cell/{gates,candidate}/{kernel,bias}`, initialised as in GRUEncoder."""
+
+    def __init__(self, hidden, seed=None):
+        super().__init__()
+        self.hidden = int(hidden)
+        for i, dr in enumerate(_DIRS):
+            for k, v in _gru_cell_init(self.hidden, self.hidden, dr + "/", None if seed is None else seed + 2 * i).items():
+                self._param(k, v)
+
+    def forward(self, f_in, lens=None):
+        if f_in.dim() != 3 or f_in.shape[-1] != self.hidden:
+            raise ValueError("BiGRUFusion: f_in %s does not fit hidden size %d" % (tuple(f_in.shape), self.hidden))
+        return _bigru_sum(f_in, lens, *(tuple(self.p("%s/%s" % (dr, n)) for n in _GRU_VARS) for dr in _DIRS))
+
+
+class DMNPlusHead(_Module):
+    """The DMN+ baseline from the stacked facts to the choice logits (model_dmnplus.py:460-537): forward(lq [N,hidden],
+    lchoices [N,C,hidden], f_in [N,F,hidden], facts_length [N]) -> logits [N,C].  The bi-directional GRU fusion of the
+    facts (`input_facts/{fw,bw}/gru_cell/...`, as BiGRUFusion), the episodic memory over them with gq = lq (`memory/...`,
+    as EpisodicMemory), then linear(concat([tile(gq), tile(output), gchoices]), 1) under `output/choicelogits/{W [3h,1]
+    truncated normal(0.1), b [1] zeros}`.  Tiling and concat are torch plumbing; every product runs in the library.
+    The loss is the caller's (the reference takes softmax cross-entropy of these logits), and there is no dropout: the
+    reference's two tf.nn.dropout calls (:491, :521) are left out."""
+
+    def __init__(self, hidden, num_hops, num_choice=4, seed=None):
+        super().__init__()
+        from . import dmn
+        self.hidden, self.num_hops, self.num_choice = int(hidden), int(num_hops), int(num_choice)
+        for i, dr in enumerate(_DIRS):
+            pre = "input_facts/%s/" % dr
+            for k, v in _gru_cell_init(self.hidden, self.hidden, pre, None if seed is None else seed + 2 * i).items():
+                self._param(k, v)
+        for k, v in dmn.init_params(self.hidden, self.num_hops, zlib.crc32(b"memory") if seed is None else int(seed) + 4).items():
+            self._param(k, v)
+        name = "output/choicelogits/W"
+        self._param(name, _trunc_normal(_gen(name, None if seed is None else seed + 5), (3 * self.hidden, 1)))
+        self._param("output/choicelogits/b", torch.zeros(1))
+
+    def forward(self, lq, lchoices, f_in, facts_length):
+        from . import dmn
+        h, C = self.hidden, self.num_choice
+        if lq.shape[-1] != h or f_in.shape[-1] != h or tuple(lchoices.shape[1:]) != (C, h):
+            raise ValueError("DMNPlusHead: lq %s / lchoices %s / f_in %s do not fit hidden size %d, %d choices"
+                             % (tuple(lq.shape), tuple(lchoices.shape), tuple(f_in.shape), h, C))
+        facts = _bigru_sum(f_in, facts_length, *(tuple(self.p("input_facts/%s/%s" % (dr, n)) for n in _GRU_VARS) for dr in _DIRS))
+        gq = lq.to(torch.float32)
+        output = functional.episodic_memory_raw(gq, facts, facts_length, *dmn.split_params(self._parameters, self.num_hops))
+        cat = torch.cat([gq[:, None, :].expand(-1, C, -1), output[:, None, :].expand(-1, C, -1), lchoices.to(torch.float32)], 2)
+        logits = functional.linear_raw(cat.contiguous(), self.p("output/choicelogits/W"), self.p("output/choicelogits/b"))
+        return logits.reshape(-1, C)

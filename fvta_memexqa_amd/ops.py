@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import (F32, BF16, AttGruSeqDesc, AttnDesc, EmbedDesc, ImgTransDesc, LstmDesc, ScorerDesc, TimewarpDesc, check,
+from ._lib import (F32, BF16, AttGruSeqDesc, AttnDesc, EmbedDesc, GruSeqDesc, ImgTransDesc, LstmDesc, ScorerDesc, TimewarpDesc, check,
                    ptr, stream_ptr)
 
 
@@ -520,6 +520,63 @@ class AttentionGRUSeq:
                                            ptr(self.saved), ptr(_f32c(d_h_last)), ptr(d_facts), ptr(d_gate), ptr(d_h0),
                                            ptr(dWg), ptr(dbg), ptr(dWc), ptr(dWi), ptr(dbi), int(accumulate), ptr(work),
                                            stream_ptr()), "fvta_attgru_seq_bwd")
+
+
+def gru_seq_plan(N, T, in_dim, d):
+    """How the library runs the GRU over T steps at this shape (fvta_gru_seq_plan; a host query, no GPU): regime "A" (the
+    whole recurrence in one launch) or "B" (two fused launches per step), kernel launches of a forward and of a backward,
+    rows of a workgroup tile."""
+    out = (ctypes.c_int32 * 4)()
+    check(_lib.load().fvta_gru_seq_plan(ctypes.byref(GruSeqDesc(N, T, in_dim, d, 0, 1)), out), "fvta_gru_seq_plan")
+    return dict(regime="AB"[out[0]], fwd_launches=out[1], bwd_launches=out[2], row_tile=out[3])
+
+
+def _i32c(t):
+    assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous(), "expected a contiguous int32 CUDA tensor"
+    return t
+
+
+class GRUSeq:
+    """TF's GRUCell under dynamic_rnn(sequence_length) (model_dmnplus.py:344-345, 470-471): x [N,T,in_dim], lens int32 [N]
+    | None (all T), h0 [N,d] | None -> (out [N,T,d] with padded rows zero, h_last [N,d]); reverse=True is the backward half
+    of bidirectional_dynamic_rnn.  training=False keeps nothing (`saved` stays None)."""
+
+    def __init__(self, N, T, in_dim, d, reverse=False, training=True):
+        self.lib = _lib.load()
+        self.dev = require_gpu()
+        self.N, self.T, self.in_dim, self.d = int(N), int(T), int(in_dim), int(d)
+        self.desc = GruSeqDesc(self.N, self.T, self.in_dim, self.d, int(bool(reverse)), int(bool(training)))
+        self.saved = None
+
+    def _work(self, backward):
+        nb = self.lib.fvta_gru_seq_workspace_bytes(ctypes.byref(self.desc), int(backward))
+        if nb == 0:
+            raise _lib.FvtaError("gru_seq: " + self.lib.fvta_last_error().decode())
+        return _bytes(nb, self.dev)
+
+    def forward(self, x, lens, h0, Wg, bg, Wc, bc, want_out=True):
+        out = torch.empty(self.N, self.T, self.d, dtype=torch.float32, device=self.dev) if want_out else None
+        h_last = torch.empty(self.N, self.d, dtype=torch.float32, device=self.dev)
+        work = self._work(False)
+        if self.desc.training:
+            self.saved = _bytes(self.lib.fvta_gru_seq_saved_bytes(ctypes.byref(self.desc)), self.dev)
+        check(self.lib.fvta_gru_seq_fwd(ctypes.byref(self.desc), ptr(_f32c(x)), ptr(None if lens is None else _i32c(lens)),
+                                        ptr(None if h0 is None else _f32c(h0)), ptr(_f32c(Wg)), ptr(_f32c(bg)), ptr(_f32c(Wc)),
+                                        ptr(_f32c(bc)), ptr(out), ptr(h_last), ptr(self.saved), ptr(work), stream_ptr()),
+              "fvta_gru_seq_fwd")
+        return out, h_last
+
+    def backward(self, x, lens, Wg, Wc, d_out, d_h_last, d_x, d_h0, dWg, dbg, dWc, dbc, accumulate=False):
+        """d_out / d_h_last: either may be None, not both.  d_x, d_h0 (may be None) are overwritten; the parameter
+        gradients stored, or added to under `accumulate`.  `saved` is only read: the call may be repeated."""
+        if self.saved is None:
+            raise _lib.FvtaError("GRUSeq.backward: no training forward ran")
+        work = self._work(True)
+        check(self.lib.fvta_gru_seq_bwd(ctypes.byref(self.desc), ptr(x), ptr(lens), ptr(Wg), ptr(Wc), ptr(self.saved),
+                                        ptr(None if d_out is None else _f32c(d_out)),
+                                        ptr(None if d_h_last is None else _f32c(d_h_last)), ptr(d_x), ptr(d_h0), ptr(dWg),
+                                        ptr(dbg), ptr(dWc), ptr(dbc), int(accumulate), ptr(work), stream_ptr()),
+              "fvta_gru_seq_bwd")
 
 
 # ------------------------------------------------------------------ time warp

@@ -46,7 +46,8 @@ int fvta_version(void);
 const char* fvta_last_error(void);
 /* sizeof of a descriptor struct as the library was compiled: which = 0 fvta_attn_desc, 1 fvta_lstm_desc,
  * 2 fvta_scorer_desc, 3 fvta_timewarp_desc, 4 fvta_embed_desc, 5 fvta_imgtrans_desc, 6 fvta_guard_desc,
- * 7 fvta_guard_ctl, 9 fvta_attgru_seq_desc (8 stays unassigned: bindings probe it as the unknown id); -1 otherwise.
+ * 7 fvta_guard_ctl, 9 fvta_attgru_seq_desc, 10 fvta_gru_seq_desc (8 stays unassigned: bindings probe it as the unknown
+ * id); -1 otherwise.
  * A binding compares
  * its own layout with it when it loads the library (fvta_memexqa_amd/_lib.py does). */
 int64_t fvta_abi_struct_bytes(int32_t which);
@@ -323,6 +324,48 @@ int fvta_attgru_seq_bwd(const fvta_attgru_seq_desc* d, const float* facts, const
                         const float* Wc, const float* Wi, const void* saved, const float* d_h_last, float* d_facts,
                         float* d_gate, float* d_h0, float* dWg, float* dbg, float* dWc, float* dWi, float* dbi,
                         int32_t accumulate, void* workspace, fvta_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
+ * A GRU over a whole sequence: TensorFlow 1's GRUCell under dynamic_rnn(sequence_length=lens), the cell the DMN+ baseline
+ * instantiates for its encoders and for the fusion of the facts (model_dmnplus.py:344-345, 470-471):
+ *   [r | u] = sigmoid([x_t, h] Wg + bg)      Wg [in+d, 2d], bg [2d] (TF initialises it to 1)
+ *   c       = tanh([x_t, r * h] Wc + bc)     Wc [in+d, d],  bc [d]
+ *   h'      = u * h + (1 - u) * c
+ * PARITY UNPINNED: there is no TensorFlow to compare with, so these formulas (tensorflow/python/ops/rnn_cell_impl.py,
+ * GRUCell.call, with its `gates` / `candidate` kernels) are the contract; the tests check them against an fp64 restatement.
+ *   x [N,T,in]  lens int32 [N] or NULL (every row has length T)  h0 [N,d] or NULL (zeros)
+ *   -> out [N,T,d] (may be NULL), h_last [N,d]
+ * At a step t >= lens[n] the state of row n is carried and out[n,t] is zero; h_last[n] is the state after step
+ * lens[n] - 1 (h0, or zero, when lens[n] == 0).  reverse = 1 is the backward half of bidirectional_dynamic_rnn: row n is
+ * walked from lens[n] - 1 down to 0, out[n,t] is the state after consuming positions lens[n]-1 .. t, padded rows are zero;
+ * the op indexes, it does not copy.
+ * The input-side products run once for all N*T rows ahead of the recurrence, d_x and the parameter gradients as
+ * contractions over all N*T rows after the reverse recurrence.  The recurrence is two dependent products per step and has
+ * two regimes, by d (fvta_gru_seq_plan):
+ *   0: every d <= 128 -- ONE launch for all T steps, the state-side weights in registers, the state tile in LDS;
+ *   1: larger d -- two fused launches per step (one per product, the gate math as epilogue).
+ * Exact fp32 (v_mfma_f32_16x16x4_f32), no atomics, fixed summation order: two runs are bitwise equal.
+ * training = 0: nothing is saved, `saved` may be NULL, and there is no backward.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int32_t N, T, in_dim, d;
+  int32_t reverse;  /* 0 / 1 */
+  int32_t training; /* 1: the forward fills `saved` for fvta_gru_seq_bwd */
+} fvta_gru_seq_desc;
+
+size_t fvta_gru_seq_saved_bytes(const fvta_gru_seq_desc* d); /* 0 with training = 0 */
+size_t fvta_gru_seq_workspace_bytes(const fvta_gru_seq_desc* d, int32_t backward); /* 0: of _fwd, 1: of _bwd */
+/* out[4] = {regime (0 / 1), launches of a forward, launches of a backward with accumulate = 0, rows per workgroup tile} */
+int fvta_gru_seq_plan(const fvta_gru_seq_desc* d, int32_t* out);
+int fvta_gru_seq_fwd(const fvta_gru_seq_desc* d, const float* x, const int32_t* lens, const float* h0, const float* Wg,
+                     const float* bg, const float* Wc, const float* bc, float* out, float* h_last, void* saved,
+                     void* workspace, fvta_stream_t stream);
+/* From d_out [N,T,d] and d_h_last [N,d] (either may be NULL, not both): d_x [N,T,in] and d_h0 [N,d] (may be NULL) are
+ * overwritten; dWg, dbg, dWc, dbc are stored (accumulate = 0) or added to (1).  `saved` is only read: a second backward
+ * gives the same result. */
+int fvta_gru_seq_bwd(const fvta_gru_seq_desc* d, const float* x, const int32_t* lens, const float* Wg, const float* Wc,
+                     const void* saved, const float* d_out, const float* d_h_last, float* d_x, float* d_h0, float* dWg,
+                     float* dbg, float* dWc, float* dbc, int32_t accumulate, void* workspace, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Time warp of the context tensor: model_v2.py:953-1009 with the indicator of

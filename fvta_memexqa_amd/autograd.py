@@ -643,6 +643,52 @@ def gru_seq(x, lens, h0, Wg, bg, Wc, bc, reverse=False):
     return _GruSeq.apply(x, lens, f(h0), Wg, f(bg), Wc, f(bc), bool(reverse))
 
 
+class _CompactBilinear(torch.autograd.Function):
+    """(x [N*P, d1], q [N, d2], device tables h1, s1, h2, s2; D, P, normalize) -> [N*P, D]: one fvta_cbp_fwd.  Each call
+    owns its ops.CompactBilinear; the backward (one fvta_cbp_bwd, accumulate = 0) only reads what it kept.  The gradient
+    at an exactly zero bucket of the normalised form is 0 (the convention of include/fvta_hip.h; TF gives NaN there)."""
+
+    @staticmethod
+    def forward(ctx, x, q, h1, s1, h2, s2, D, P, normalize):
+        need = any(ctx.needs_input_grad)
+        op = ops.CompactBilinear(q.shape[0], P, x.shape[1], q.shape[1], D, normalize=normalize, training=need)
+        out = op.forward(x, q, h1, s1, h2, s2)
+        ctx.set_materialize_grads(False)
+        if need:
+            ctx.op = op
+            ctx.save_for_backward(x, q, h1, s1, h2, s2)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        if g is None:
+            return (None,) * 9
+        x, q, h1, s1, h2, s2 = ctx.saved_tensors
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dq = torch.empty_like(q) if ctx.needs_input_grad[1] else None
+        ctx.op.backward(x, q, h1, s1, h2, s2, _c(g), dx, dq, accumulate=False)
+        return (dx, dq) + (None,) * 7
+
+
+def compact_bilinear(x, q, h1, s1, h2, s2, D, P=1, normalize=False):
+    """x [N*P, d1], q [N, d2] (row n of q is shared by rows n*P .. n*P+P-1 of x; P = 1: one q row per x row), the count
+    sketch tables as device tensors (ops.upload_sketch_tables validates and uploads them) -> z [N*P, D], the count sketch of
+    the outer products, or with normalize its l2-normalised square root of the magnitude (model_mcb.py:645).
+    Non-contiguous inputs are made contiguous."""
+    ops.require_gpu()
+    f = lambda t: t.to(torch.float32).contiguous()
+    x, q = f(x), f(q)
+    D, P = int(D), int(P)
+    if x.dim() != 2 or q.dim() != 2 or P < 1 or x.shape[0] != q.shape[0] * P:
+        raise ValueError("compact_bilinear: x %s and q %s do not fit P = %d" % (tuple(x.shape), tuple(q.shape), P))
+    if h1.numel() != x.shape[1] or s1.numel() != x.shape[1] or h2.numel() != q.shape[1] or s2.numel() != q.shape[1]:
+        raise ValueError("compact_bilinear: the tables do not fit d1 = %d, d2 = %d" % (x.shape[1], q.shape[1]))
+    i = lambda t: t.to(x.device, torch.int32).contiguous()
+    g = lambda t: t.to(x.device, torch.float32).contiguous()
+    return _CompactBilinear.apply(x, q, i(h1), g(s1), i(h2), g(s2), D, P, bool(normalize))
+
+
 class _DmnFeatures(torch.autograd.Function):
     """(facts [N,F,d], q [N,d], m [N,d]) -> [N,F,4d] = [fact*q, fact*m, |fact-q|, |fact-m|] (model_dmnplus.py:93-98,
     fvta_dmn_features); backward: fvta_dmn_features_bwd into fresh zero buffers (it accumulates)."""

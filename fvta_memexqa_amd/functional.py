@@ -20,6 +20,10 @@
     episodic_memory(gq, facts, facts_length, num_hops, hidden_size,
                     scope="memory") -> [N,hidden_size]                               model_dmnplus.py:503-516
       (generate_episode_raw / episodic_memory_raw: the same with explicit variables)
+    compact_bilinear_pooling_layer(bottom1, bottom2, output_dim, sum_pool=True, rand_h_1=None, rand_s_1=None,
+                                   rand_h_2=None, rand_s_2=None, seed_h_1=1, seed_s_1=3, seed_h_2=5, seed_s_2=7,
+                                   sequential=True, compute_size=128)                model_mcb.py:1254-1363
+    mcb_attention_raw(hpis, gq, tables, filter_conv1, filter_conv2) -> (attended, att)   model_mcb.py:628-672
 
 Tensors are torch CUDA tensors; every op is one call into libfvta_hip.so, wrapped in a `torch.autograd.Function`
 (autograd.py): a tensor that requires grad gets its gradient through the library's backward kernels, and when nothing
@@ -518,3 +522,75 @@ def episodic_memory(gq, facts, facts_length, num_hops, hidden_size, scope="memor
         hop_vars = [(get_variable(_name("hop_%d" % i, "dense", "kernel"), (3 * d, hidden_size), init="glorot"),
                      get_variable(_name("hop_%d" % i, "dense", "bias"), (hidden_size,), init="zeros")) for i in range(int(num_hops))]
     return episodic_memory_raw(gq, facts, facts_length, att_vars, cell_vars, hop_vars)
+
+
+# ------------------------------------------------------------------ MCB (model_mcb.py:623-681, 1254-1363)
+_SKETCH_CACHE = {}
+
+
+def sketch_tables(d1, d2, D, rand_h_1=None, rand_s_1=None, rand_h_2=None, rand_s_2=None, seeds=(1, 3, 5, 7)):
+    """The layer's four tables on the device: those the reference draws from `seeds` (ops.count_sketch_tables), each
+    replaced by the caller's own where one is given; validated on the host, uploaded, and kept per (sizes, seeds) when all
+    four are drawn."""
+    given = (rand_h_1, rand_s_1, rand_h_2, rand_s_2)
+    key = (int(d1), int(d2), int(D), tuple(int(s) for s in seeds), torch.cuda.current_device())
+    if all(t is None for t in given) and key in _SKETCH_CACHE:
+        return _SKETCH_CACHE[key]
+    drawn = ops.count_sketch_tables(d1, d2, D, seeds)
+    tabs = ops.upload_sketch_tables(*(dr if t is None else t for t, dr in zip(given, drawn)), d1, d2, D)
+    if all(t is None for t in given):
+        _SKETCH_CACHE[key] = tabs
+    return tabs
+
+
+def compact_bilinear_pooling_layer(bottom1, bottom2, output_dim, sum_pool=True, rand_h_1=None, rand_s_1=None, rand_h_2=None,
+                                   rand_s_2=None, seed_h_1=1, seed_s_1=3, seed_h_2=5, seed_s_2=7, sequential=True,
+                                   compute_size=128):
+    """model_mcb.py:1254-1363 with the reference's signature: bottom1 [B,H,W,d1], bottom2 [B,H,W,d2] (one row of it per
+    position) or [B,1,1,d2] (one row per b, shared by its H*W positions: what the model's tiled question is) ->
+    [B,H,W,output_dim], or its sum over H and W [B,output_dim] with sum_pool (a torch sum).  The count sketch of the outer
+    product in exact fp32 (autograd.compact_bilinear), where the reference goes through FFTs; `sequential` and
+    `compute_size` steer those FFTs and are accepted and ignored.  Differentiable in both bottoms."""
+    if bottom1.dim() != 4 or bottom2.dim() != 4:
+        raise ValueError("compact_bilinear_pooling_layer: bottoms must be [B,H,W,d], got %s and %s" % (tuple(bottom1.shape), tuple(bottom2.shape)))
+    tabs = sketch_tables(bottom1.shape[-1], bottom2.shape[-1], output_dim, rand_h_1, rand_s_1, rand_h_2, rand_s_2,
+                         (seed_h_1, seed_s_1, seed_h_2, seed_s_2))
+    return compact_bilinear_pooling_raw(bottom1, bottom2, tabs, output_dim, sum_pool=sum_pool)
+
+
+def compact_bilinear_pooling_raw(bottom1, bottom2, tables, output_dim, sum_pool=True, normalize=False):
+    """compact_bilinear_pooling_layer with explicit device tables (h1, s1, h2, s2); normalize fuses the
+    l2_normalize(sqrt|.|) of model_mcb.py:645 behind the un-pooled rows"""
+    B, H, W, d1 = bottom1.shape
+    d2 = bottom2.shape[-1]
+    if tuple(bottom2.shape[:3]) == (B, H, W):
+        P = 1
+    elif tuple(bottom2.shape[:3]) == (B, 1, 1):
+        P = H * W
+    else:
+        raise ValueError("compact_bilinear_pooling_layer: bottom2 %s fits neither [%d,%d,%d,d2] nor [%d,1,1,d2]"
+                         % (tuple(bottom2.shape), B, H, W, B))
+    cbp = autograd.compact_bilinear(bottom1.reshape(B * H * W, d1), bottom2.reshape(-1, d2), *tables, int(output_dim), P=P,
+                                    normalize=normalize)
+    cbp = cbp.reshape(B, H, W, int(output_dim))
+    return cbp.sum((1, 2)) if sum_pool else cbp
+
+
+def mcb_attention_raw(hpis, gq, tables, filter_conv1, filter_conv2):
+    """model_mcb.py:628-672 with explicit variables: hpis [N,M,JI,idim] (the raw photo rows), gq [N,2d] (the question's
+    last state), tables = (h1, s1, h2, s2) on the device, filter_conv1 [D,c1], filter_conv2 [c1,1] (the 1x1 convolutions
+    are linears without a bias) -> (attended [N,idim], att [N, M*JI]).  The pooled rows are normalised inside the op
+    (l2_normalize(sqrt|.|), never stored un-normalised), relu(linear) twice, a softmax over ALL M*JI positions (unmasked,
+    as in the reference) and the weighted sum of hpis: every product is a library call, the reshapes are torch.
+    Left out: the tf.nn.dropout of :649 and the forward NaN scrubs of :635 / :646 (inputs are taken to be finite; the one
+    0/0 the graph can produce, a zero bucket under the square root's gradient, is defined as 0)."""
+    hpis, gq = _f32(hpis), _f32(gq)
+    N, M, JI, idim = hpis.shape
+    T = M * JI
+    D = filter_conv1.shape[0]
+    rows = hpis.reshape(N * T, idim)
+    g_mcb = autograd.compact_bilinear(rows, gq, *tables, D, P=T, normalize=True)                # [N*T, D]  (:641-645)
+    c1 = autograd.relu(linear_raw(g_mcb, filter_conv1, None))                                   # [N*T, c1] (:658)
+    c2 = autograd.relu(linear_raw(c1, filter_conv2, None))                                      # [N*T, 1]  (:664)
+    att = softmax(c2.reshape(N, T))                                                             # (:666)
+    return _wsum(hpis.reshape(N, T, idim), att), att                                            # (:672)

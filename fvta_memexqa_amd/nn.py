@@ -380,3 +380,110 @@ class DMNPlusHead(_Module):
         cat = torch.cat([gq[:, None, :].expand(-1, C, -1), output[:, None, :].expand(-1, C, -1), lchoices.to(torch.float32)], 2)
         logits = functional.linear_raw(cat.contiguous(), self.p("output/choicelogits/W"), self.p("output/choicelogits/b"))
         return logits.reshape(-1, C)
+
+
+_MCB_TABLES = ("rand_h_1", "rand_s_1", "rand_h_2", "rand_s_2")
+
+
+def _register_tables(mod, prefix, d1, d2, D, seeds=(1, 3, 5, 7)):
+    """the layer's four count sketch tables, drawn as the reference draws them, as buffers of `mod` (its own copies:
+    load_state_dict writes into them)"""
+    for name, t in zip(_MCB_TABLES, ops.upload_sketch_tables(*ops.count_sketch_tables(d1, d2, D, seeds), d1, d2, D)):
+        mod.register_buffer(prefix + name, t)
+
+
+class CompactBilinearPooling(_Module):
+    """compact_bilinear_pooling_layer (model_mcb.py:1254-1363) as a module: forward(bottom1 [B,H,W,d1], bottom2 [B,H,W,d2]
+    or [B,1,1,d2]) -> [B,H,W,output_dim] (sum_pool=True: [B,output_dim]); with normalize the l2_normalize(sqrt|.|) of :645
+    is fused behind the pooling (and sum_pool is refused: the reference normalises the un-pooled rows).  The four count
+    sketch tables are BUFFERS (`rand_h_1`, `rand_s_1`, `rand_h_2`, `rand_s_2`), drawn from `seeds` exactly as the
+    reference draws them (ops.count_sketch_tables), so they travel in state_dict(); no parameters."""
+
+    def __init__(self, d1, d2, output_dim, normalize=False, sum_pool=False, seeds=(1, 3, 5, 7)):
+        super().__init__()
+        self.d1, self.d2, self.output_dim = int(d1), int(d2), int(output_dim)
+        self.normalize, self.sum_pool = bool(normalize), bool(sum_pool)
+        if self.normalize and self.sum_pool:
+            raise ValueError("CompactBilinearPooling: normalize applies to the un-pooled rows, not with sum_pool")
+        _register_tables(self, "", self.d1, self.d2, self.output_dim, seeds)
+
+    def forward(self, bottom1, bottom2):
+        if bottom1.dim() != 4 or bottom2.dim() != 4 or bottom1.shape[-1] != self.d1 or bottom2.shape[-1] != self.d2:
+            raise ValueError("CompactBilinearPooling: bottoms %s / %s do not fit d1 = %d, d2 = %d"
+                             % (tuple(bottom1.shape), tuple(bottom2.shape), self.d1, self.d2))
+        return functional.compact_bilinear_pooling_raw(bottom1, bottom2, tuple(self._buffers[n] for n in _MCB_TABLES),
+                                                       self.output_dim, sum_pool=self.sum_pool, normalize=self.normalize)
+
+
+def _mcb_attention_init(mod, prefix, idim, qdim, mcb_outdim, conv1_out, seed):
+    """the variables and tables of `mcb_attention` (model_mcb.py:641-664) on module `mod`, below `prefix`"""
+    _register_tables(mod, prefix, idim, qdim, mcb_outdim)
+    for i, (name, shape) in enumerate((("filter_conv1", (mcb_outdim, conv1_out)), ("filter_conv2", (conv1_out, 1)))):
+        mod._param(prefix + name, _trunc_normal(_gen(prefix + name, None if seed is None else seed + i), shape, std=0.02))
+
+
+def _mcb_attention(mod, prefix, hpis, gq):
+    tabs = tuple(mod._buffers[prefix + n] for n in _MCB_TABLES)
+    return functional.mcb_attention_raw(hpis, gq, tabs, mod.p(prefix + "filter_conv1"), mod.p(prefix + "filter_conv2"))
+
+
+class MCBAttention(_Module):
+    """The MCB attention over the photos (model_mcb.py:623-672): forward(hpis [N,M,JI,idim], gq [N,qdim]) -> (attended
+    [N,idim], att [N, M*JI]) through functional.mcb_attention_raw.  Parameters `filter_conv1` [mcb_outdim, conv1_out] and
+    `filter_conv2` [conv1_out, 1], truncated normal(0.02): the reference's [1,1,in,out] 1x1 convolution filters without
+    their two leading axes.  The count sketch tables are buffers, drawn as the reference draws them (seeds 1/3/5/7).
+    No dropout (:649) and no NaN scrubs, as functional.mcb_attention_raw says."""
+
+    def __init__(self, idim, qdim, mcb_outdim=16000, conv1_out=512, seed=None):
+        super().__init__()
+        self.idim, self.qdim, self.mcb_outdim, self.conv1_out = int(idim), int(qdim), int(mcb_outdim), int(conv1_out)
+        _mcb_attention_init(self, "", self.idim, self.qdim, self.mcb_outdim, self.conv1_out, seed)
+
+    def forward(self, hpis, gq):
+        if hpis.dim() != 4 or hpis.shape[-1] != self.idim or gq.dim() != 2 or gq.shape[-1] != self.qdim:
+            raise ValueError("MCBAttention: hpis %s / gq %s do not fit idim = %d, qdim = %d"
+                             % (tuple(hpis.shape), tuple(gq.shape), self.idim, self.qdim))
+        return _mcb_attention(self, "", hpis, gq)
+
+
+class MCBHead(_Module):
+    """The MCB baseline from the encoders' outputs to the choice logits (model_mcb.py:614-748): forward(lq [N,hidden2],
+    g1 [N,hidden2], hpis [N,M,JI,idim], lchoices [N,C,hidden2]) -> logits [N,C]; the attention weights of the call are
+    kept as `.att` [N, M*JI].  hidden2 is the reference's 2d (a bi-LSTM's last state).  gq = lq attends the raw photo rows
+    (`mcb_attention/{filter_conv1, filter_conv2}` and the table buffers, as MCBAttention), the attended row goes through `mcb_attention/g_mcb_trans/{W [idim,hidden2],
+    b}` (:681), and `output/att_logits/{W [7*hidden2, 1], b}` scores concat([gq, g1, g_mcb, gchoices, gq*g1, gq*g_mcb,
+    gq*gchoices]) per choice (:740); both linears truncated normal(0.1) / zeros, with tanh under add_tanh.  g1 is the
+    mean-pooled text representation of :700-717, torch plumbing the caller writes.  Tiling, concat and
+    the three element-wise products are torch; every matrix product runs in the library.
+    Left out: the tf.nn.dropout of :649, the forward NaN scrubs of :621 / :635 / :646 / :715 (inputs are taken to be
+    finite) and the loss (the reference takes softmax cross-entropy of these logits)."""
+
+    def __init__(self, idim, hidden2, mcb_outdim=16000, num_choice=4, add_tanh=False, conv1_out=512, seed=None):
+        super().__init__()
+        self.idim, self.hidden2, self.num_choice, self.add_tanh = int(idim), int(hidden2), int(num_choice), bool(add_tanh)
+        self.mcb_outdim, self.conv1_out = int(mcb_outdim), int(conv1_out)
+        _mcb_attention_init(self, "mcb_attention/", self.idim, self.hidden2, self.mcb_outdim, self.conv1_out, seed)
+        sd = lambda i: None if seed is None else seed + i
+        for i, (name, shape) in enumerate((("mcb_attention/g_mcb_trans/W", (self.idim, self.hidden2)),
+                                           ("output/att_logits/W", (7 * self.hidden2, 1)))):
+            self._param(name, _trunc_normal(_gen(name, sd(2 + i)), shape))
+            self._param(name[:-1] + "b", torch.zeros(shape[1]))
+        self.att = None
+
+    def forward(self, lq, g1, hpis, lchoices):
+        h, C = self.hidden2, self.num_choice
+        if lq.shape[-1] != h or g1.shape[-1] != h or tuple(lchoices.shape[1:]) != (C, h):
+            raise ValueError("MCBHead: lq %s / g1 %s / lchoices %s do not fit hidden2 = %d, %d choices"
+                             % (tuple(lq.shape), tuple(g1.shape), tuple(lchoices.shape), h, C))
+        gq, g1, gch = lq.to(torch.float32), g1.to(torch.float32), lchoices.to(torch.float32)
+        if hpis.dim() != 4 or hpis.shape[-1] != self.idim:
+            raise ValueError("MCBHead: hpis %s does not fit [N,M,JI,%d]" % (tuple(hpis.shape), self.idim))
+        attended, att = _mcb_attention(self, "mcb_attention/", hpis, gq)
+        self.att = att.detach()
+        g_mcb = functional.linear_raw(attended, self.p("mcb_attention/g_mcb_trans/W"), self.p("mcb_attention/g_mcb_trans/b"),
+                                      self.add_tanh)
+        tile = lambda t: t[:, None, :].expand(-1, C, -1)
+        q_t, g1_t, m_t = tile(gq), tile(g1), tile(g_mcb)
+        cat = torch.cat([q_t, g1_t, m_t, gch, q_t * g1_t, q_t * m_t, q_t * gch], 2)
+        logits = functional.linear_raw(cat.contiguous(), self.p("output/att_logits/W"), self.p("output/att_logits/b"), self.add_tanh)
+        return logits.reshape(-1, C)

@@ -579,6 +579,87 @@ class GRUSeq:
               "fvta_gru_seq_bwd")
 
 
+# ------------------------------------------------------------------ compact bilinear pooling
+def count_sketch_tables(d1, d2, D, seeds=(1, 3, 5, 7)):
+    """The four count-sketch tables compact_bilinear_pooling_layer draws (model_mcb.py:1313-1326), as numpy arrays
+    (h1 [d1], s1 [d1], h2 [d2], s2 [d2]): `np.random.seed(s); np.random.randint(D, size=d)` for the indices and
+    `2 * np.random.randint(2, size=d) - 1` for the signs.  np.random.RandomState(s) is that legacy stream and is stable
+    across numpy versions, so a checkpoint the reference trained meets the same hash.  A host function: no GPU."""
+    import numpy as np
+    sh1, ss1, sh2, ss2 = (int(s) for s in seeds)
+    draw_h = lambda s, d: np.random.RandomState(s).randint(int(D), size=int(d))
+    draw_s = lambda s, d: 2 * np.random.RandomState(s).randint(2, size=int(d)) - 1
+    return draw_h(sh1, d1), draw_s(ss1, d1), draw_h(sh2, d2), draw_s(ss2, d2)
+
+
+def check_sketch_tables(h1, s1, h2, s2, d1, d2, D):
+    """Host-side validation of user-supplied tables, before they are uploaded (the kernels trust them): lengths d1 / d2,
+    integer indices in [0, D), signs +1 / -1.  Returns them as numpy (int32, float32, int32, float32)."""
+    import numpy as np
+    out = []
+    for name, t, d, is_h in (("rand_h_1", h1, d1, True), ("rand_s_1", s1, d1, False), ("rand_h_2", h2, d2, True),
+                             ("rand_s_2", s2, d2, False)):
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        if a.ndim != 1 or a.shape[0] != int(d):
+            raise ValueError("%s: expected %d entries, got shape %s" % (name, int(d), tuple(a.shape)))
+        if is_h:
+            if not (np.issubdtype(a.dtype, np.integer) or np.all(a == np.floor(a))):
+                raise ValueError("%s: indices must be integers" % name)
+            if a.min() < 0 or a.max() >= int(D):
+                raise ValueError("%s: indices must lie in [0, %d), got [%d, %d]" % (name, int(D), int(a.min()), int(a.max())))
+            out.append(np.ascontiguousarray(a, dtype=np.int32))
+        else:
+            if not np.all(np.abs(a) == 1):
+                raise ValueError("%s: signs must be +1 or -1" % name)
+            out.append(np.ascontiguousarray(a, dtype=np.float32))
+    return tuple(out)
+
+
+def upload_sketch_tables(h1, s1, h2, s2, d1, d2, D):
+    """validated tables as device tensors (h1 int32, s1 float32, h2 int32, s2 float32)"""
+    dev = require_gpu()
+    return tuple(torch.from_numpy(a).to(dev) for a in check_sketch_tables(h1, s1, h2, s2, d1, d2, D))
+
+
+class CompactBilinear:
+    """compact_bilinear_pooling_layer without its sum pool (model_mcb.py:1254-1363), optionally with the
+    l2_normalize(sqrt|.|) of :645 fused: x [N*P, d1], q [N, d2] (shared by the P rows of its n) -> [N*P, D].  The tables are
+    device tensors from upload_sketch_tables (validated there: the kernels trust them).  training=False keeps nothing."""
+
+    def __init__(self, N, P, d1, d2, D, normalize=False, training=True):
+        self.lib = _lib.load()
+        self.dev = require_gpu()
+        self.N, self.P, self.d1, self.d2, self.D = int(N), int(P), int(d1), int(d2), int(D)
+        self.desc = _lib.CbpDesc(self.N, self.P, self.d1, self.d2, self.D, int(bool(normalize)), int(bool(training)))
+        self.saved = None
+
+    def _work(self, backward):
+        nb = self.lib.fvta_cbp_workspace_bytes(ctypes.byref(self.desc), int(backward))
+        if nb == 0:
+            raise _lib.FvtaError("compact_bilinear: " + self.lib.fvta_last_error().decode())
+        return _bytes(nb, self.dev)
+
+    def forward(self, x, q, h1, s1, h2, s2):
+        work = self._work(False)
+        out = torch.empty(self.N * self.P, self.D, dtype=torch.float32, device=self.dev)
+        if self.desc.training:
+            self.saved = _bytes(self.lib.fvta_cbp_saved_bytes(ctypes.byref(self.desc)), self.dev)
+        check(self.lib.fvta_cbp_fwd(ctypes.byref(self.desc), ptr(_f32c(x)), ptr(_f32c(q)), ptr(_i32c(h1)), ptr(_f32c(s1)),
+                                    ptr(_i32c(h2)), ptr(_f32c(s2)), ptr(out), ptr(self.saved), ptr(work), stream_ptr()),
+              "fvta_cbp_fwd")
+        return out
+
+    def backward(self, x, q, h1, s1, h2, s2, dy, dx, dq, accumulate=False):
+        """dx [N*P, d1] / dq [N, d2]: either may be None, not both; stored, or added to under `accumulate`.  `saved` is only
+        read: the call may be repeated."""
+        if self.saved is None:
+            raise _lib.FvtaError("CompactBilinear.backward: no training forward ran")
+        work = self._work(True)
+        check(self.lib.fvta_cbp_bwd(ctypes.byref(self.desc), ptr(_f32c(x)), ptr(_f32c(q)), ptr(_i32c(h1)), ptr(_f32c(s1)),
+                                    ptr(_i32c(h2)), ptr(_f32c(s2)), ptr(self.saved), ptr(_f32c(dy)), ptr(dx), ptr(dq),
+                                    int(accumulate), ptr(work), stream_ptr()), "fvta_cbp_bwd")
+
+
 # ------------------------------------------------------------------ time warp
 class TimeWarp:
     """model_v2.py:953-1009 (closed form): warp_h = hall * c[n,t] * cnt(t)."""

@@ -46,8 +46,8 @@ int fvta_version(void);
 const char* fvta_last_error(void);
 /* sizeof of a descriptor struct as the library was compiled: which = 0 fvta_attn_desc, 1 fvta_lstm_desc,
  * 2 fvta_scorer_desc, 3 fvta_timewarp_desc, 4 fvta_embed_desc, 5 fvta_imgtrans_desc, 6 fvta_guard_desc,
- * 7 fvta_guard_ctl, 9 fvta_attgru_seq_desc, 10 fvta_gru_seq_desc (8 stays unassigned: bindings probe it as the unknown
- * id); -1 otherwise.
+ * 7 fvta_guard_ctl, 9 fvta_attgru_seq_desc, 10 fvta_gru_seq_desc, 11 fvta_cbp_desc (8 stays unassigned: bindings probe
+ * it as the unknown id); -1 otherwise.
  * A binding compares
  * its own layout with it when it loads the library (fvta_memexqa_amd/_lib.py does). */
 int64_t fvta_abi_struct_bytes(int32_t which);
@@ -366,6 +366,45 @@ int fvta_gru_seq_fwd(const fvta_gru_seq_desc* d, const float* x, const int32_t* 
 int fvta_gru_seq_bwd(const fvta_gru_seq_desc* d, const float* x, const int32_t* lens, const float* Wg, const float* Wc,
                      const void* saved, const float* d_out, const float* d_h_last, float* d_x, float* d_h0, float* dWg,
                      float* dbg, float* dWc, float* dbc, int32_t accumulate, void* workspace, fvta_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
+ * Compact bilinear pooling: model_mcb.py:1254-1363 `compact_bilinear_pooling_layer` without its sum pool, and with
+ * normalize = 1 the `tf.nn.l2_normalize(tf.sqrt(tf.sign(g) * g), dim=-1)` of :645 fused behind it.  The reference takes
+ * two count sketches through FFTs of length D; their circular convolution is the count sketch of the outer product, and
+ * that is what runs here, in exact fp32 with a fixed summation order (no FFT):
+ *   z[r,k] = sum over (i,j) with (h1[i] + h2[j]) mod D = k of  s1[i] s2[j] x[r,i] q[n,j],   n = r / P
+ *   x [N*P, d1]   q [N, d2]: shared by the P rows of its n (P = 1 is the general per-row layer)
+ *   device tables h1 [d1], h2 [d2]: int32 in [0, D);  s1 [d1], s2 [d2]: +1 / -1.  The kernels trust them: a binding
+ *   validates them on the host (ops.CompactBilinear does).
+ *   normalize = 0: out = z [N*P, D]
+ *   normalize = 1: out = y = w * rsqrt(max(sum_k w_k^2, 1e-12)), w = sqrt|z| (sum w^2 is taken as sum |z|).  The sign is
+ *     not restored: the reference does not restore it.  A row whose z is all zero (a padded photo, a zero question) gives
+ *     y = 0.  z is never written to memory; `saved` keeps one word per row.
+ * Backward, from dy [N*P, D]:
+ *   dx[r,i] = s1[i] sum_j s2[j] q[n,j] dz[r,(h1[i]+h2[j]) mod D]
+ *   dq[n,j] = s2[j] sum_{r in n} sum_i s1[i] x[r,i] dz[r,(h1[i]+h2[j]) mod D]      (rows of n folded in order)
+ * with dz = dy, or dy taken through the normalisation.  CONVENTION at z = 0: d w / d z = sign(z) / (2 sqrt|z|) for
+ * z != 0 and 0 at z = 0, so dz is 0 at an empty or exactly cancelled bucket.  TensorFlow gives inf / NaN there (the
+ * reference's tf.where(is_nan) scrubs only the forward); inputs are taken to be finite.
+ * One workgroup owns an output row in LDS, so D is bounded: D <= 16384.  Above it the size queries return 0 and the
+ * calls FVTA_ERR_UNSUPPORTED, with a message naming the limit.  d1 and d2 are any value >= 1 (d1 > D, d2 > D are legal).
+ * No floating-point atomics: two runs are bitwise equal.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int32_t N, P, d1, d2, D;
+  int32_t normalize; /* 0 / 1 */
+  int32_t training;  /* 1: the forward fills `saved` for fvta_cbp_bwd */
+} fvta_cbp_desc;
+
+size_t fvta_cbp_saved_bytes(const fvta_cbp_desc* d); /* 0 with training = 0 or normalize = 0 */
+size_t fvta_cbp_workspace_bytes(const fvta_cbp_desc* d, int32_t backward); /* 0: of _fwd, 1: of _bwd; 0 bytes: see fvta_last_error */
+int fvta_cbp_fwd(const fvta_cbp_desc* d, const float* x, const float* q, const int32_t* h1, const float* s1,
+                 const int32_t* h2, const float* s2, float* out, void* saved, void* workspace, fvta_stream_t stream);
+/* dx [N*P, d1] and dq [N, d2] (either may be NULL, not both) are stored (accumulate = 0) or added to (1).  `saved` is only
+ * read (it may be NULL with normalize = 0): a second backward gives the same result. */
+int fvta_cbp_bwd(const fvta_cbp_desc* d, const float* x, const float* q, const int32_t* h1, const float* s1,
+                 const int32_t* h2, const float* s2, const void* saved, const float* dy, float* dx, float* dq,
+                 int32_t accumulate, void* workspace, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Time warp of the context tensor: model_v2.py:953-1009 with the indicator of

@@ -1,0 +1,354 @@
+"""GPU parity of compact bilinear pooling (fvta_cbp_fwd / _bwd, ops.CompactBilinear, autograd.compact_bilinear,
+functional.compact_bilinear_pooling_layer) and of the MCB modules built on it (nn.CompactBilinearPooling / MCBAttention /
+MCBHead) against fp64 autograd of tests/_mcb_ref.py.
+
+Tolerances are those of tests/test_gpu_gru_seq.py for the project's exact-fp32 ops: outputs rtol 2e-4 / atol 2e-5, every
+gradient tensor |a - b|_2 <= 2e-4 |b|_2 + 1e-5.  Inputs: x = relu(randn) (non-negative, like CNN features), q = 0.5 randn,
+with one all-zero row of x and one all-zero row of q where N P > 2.
+
+The normalised form takes sqrt|z|, whose derivative 1 / (2 sqrt|z|) is ill-conditioned where a bucket's terms cancel:
+there the upstream gradient is set to zero -- at the elements whose fp64 |z| < 1e-3 * (sum of |terms| of the bucket) --
+and each case asserts that this drops at most 1 % of the elements with a non-empty bucket.  Exactly empty buckets stay in:
+y = 0 there, and the gradient convention (0 at z = 0) is what the parity of the gradients checks."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from tests import _mcb_ref as R
+
+pytestmark = pytest.mark.gpu
+
+# (N, P, d1, d2, D): mostly empty buckets; D neither a power of two nor a multiple of 64; d1 > D, many terms per bucket,
+# P = 64; -; P = 1; the workload's row, two of them; the largest D
+CASES = [(1, 1, 8, 4, 64), (2, 3, 37, 10, 100), (3, 64, 300, 40, 250), (2, 5, 257, 128, 1000), (5, 1, 64, 64, 4096),
+         (1, 2, 2537, 100, 16000), (2, 2, 100, 20, 16384)]
+REPRO = (3, 64, 300, 40, 250)
+
+
+def _close_out(got, want, tag):
+    np.testing.assert_allclose(got.detach().cpu().numpy(), want.detach().numpy(), rtol=2e-4, atol=2e-5, err_msg=tag)
+
+
+def _close_grad(got, want, tag):
+    assert got is not None, "%s: no gradient" % tag
+    a, b = got.detach().cpu().double().numpy(), want.detach().double().numpy()
+    assert np.isfinite(a).all(), "%s: non-finite gradient" % tag
+    err, ref = np.linalg.norm(a - b), np.linalg.norm(b)
+    print("%s: |a-b| %.3g, |b| %.3g, ratio %.3g" % (tag, err, ref, err / max(ref, 1e-300)))
+    assert err <= 2e-4 * ref + 1e-5, "%s: |a-b| %.3g, |b| %.3g" % (tag, err, ref)
+
+
+def _tables(d1, d2, D):
+    from fvta_memexqa_amd import ops
+    return ops.count_sketch_tables(d1, d2, D)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(N, P, d1, d2, D):
+    """inputs (fp32, CPU) and the fp64 reference of one case in both forms, computed once and shared"""
+    g = torch.Generator().manual_seed(1000003 * N + 10007 * P + 101 * d1 + 7 * d2 + D)
+    Rr = N * P
+    x = torch.relu(torch.randn(Rr, d1, generator=g))
+    q = 0.5 * torch.randn(N, d2, generator=g)
+    zero_x = zero_q = None
+    if Rr > 2:
+        zero_x = 1
+        x[zero_x] = 0
+        if N > 1:
+            zero_q = N - 1
+            q[zero_q] = 0
+    gz, gy = torch.randn(Rr, D, generator=g), torch.randn(Rr, D, generator=g)
+    tabs = _tables(d1, d2, D)
+    x64, q64 = x.double().requires_grad_(), q.double().requires_grad_()
+    z = R.cbp_direct(x64, q64, *tabs, D, P)
+    dx0, dq0 = torch.autograd.grad((z * gz.double()).sum(), (x64, q64), retain_graph=True)
+    scale = R.cbp_abs_terms(x64.detach(), q64.detach(), *tabs, D, P)
+    zd = z.detach()
+    ill = (scale > 0) & (zd.abs() < 1e-3 * scale)
+    gy = gy * (~ill)
+    y = R.normalize(z)
+    dx1, dq1 = torch.autograd.grad((y * gy.double()).sum(), (x64, q64))
+    return dict(N=N, P=P, d1=d1, d2=d2, D=D, x=x, q=q, tabs=tabs, gz=gz, gy=gy, z=zd, y=y.detach(), dx0=dx0, dq0=dq0,
+                dx1=dx1, dq1=dq1, scale=scale, ill=ill, zero_x=zero_x, zero_q=zero_q)
+
+
+def _dev_tables(c):
+    from fvta_memexqa_amd import ops
+    return ops.upload_sketch_tables(*c["tabs"], c["d1"], c["d2"], c["D"])
+
+
+def _run(c, normalize, x=None, q=None, P=None):
+    """(out, dx, dq) through autograd.compact_bilinear (the accumulate = 0 path of the C ABI)"""
+    from fvta_memexqa_amd import autograd
+    x = (c["x"] if x is None else x).cuda().requires_grad_()
+    q = (c["q"] if q is None else q).cuda().requires_grad_()
+    out = autograd.compact_bilinear(x, q, *_dev_tables(c), c["D"], P=c["P"] if P is None else P, normalize=normalize)
+    (out * (c["gy"] if normalize else c["gz"]).cuda()).sum().backward()
+    return out.detach(), x.grad, q.grad
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_plain_form_matches_reference(case):
+    c = _case(*case)
+    z, dx, dq = _run(c, False)
+    tag = str(case)
+    _close_out(z, c["z"], "z " + tag)
+    _close_grad(dx, c["dx0"], "dx " + tag)
+    _close_grad(dq, c["dq0"], "dq " + tag)
+    assert (z.cpu()[c["scale"] == 0] == 0).all(), "a bucket without a non-zero term must be exactly zero"
+
+
+@pytest.mark.parametrize("case", [(2, 3, 37, 10, 100), (2, 5, 257, 128, 1000)])
+def test_raw_call_accumulates_onto_a_start(case):
+    """ops.CompactBilinear.backward(accumulate=True) adds what the accumulate = 0 path stores; one fp32 addition apart"""
+    from fvta_memexqa_amd import ops
+    c = _case(*case)
+    _, dx, dq = _run(c, False)
+    g = torch.Generator().manual_seed(5)
+    dx0, dq0 = torch.randn(c["x"].shape, generator=g).cuda(), torch.randn(c["q"].shape, generator=g).cuda()
+    op = ops.CompactBilinear(c["N"], c["P"], c["d1"], c["d2"], c["D"], normalize=False, training=True)
+    tabs = _dev_tables(c)
+    x, q = c["x"].cuda(), c["q"].cuda()
+    z = op.forward(x, q, *tabs)
+    _close_out(z, c["z"], "z (raw) " + str(case))
+    dxa, dqa = dx0.clone(), dq0.clone()
+    op.backward(x, q, *tabs, c["gz"].cuda(), dxa, dqa, accumulate=True)
+    torch.testing.assert_close(dxa, dx0 + dx, rtol=1e-6, atol=1e-6)
+    torch.testing.assert_close(dqa, dq0 + dq, rtol=1e-6, atol=1e-6)
+    _close_grad(dxa - dx0, c["dx0"], "dx (accumulate) " + str(case))
+    _close_grad(dqa - dq0, c["dq0"], "dq (accumulate) " + str(case))
+    only_q = dq0.clone()                                               # dx may be NULL
+    op.backward(x, q, *tabs, c["gz"].cuda(), None, only_q, accumulate=True)
+    assert torch.equal(only_q, dqa)
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_normalised_form_matches_reference(case):
+    c = _case(*case)
+    live = c["scale"] > 0
+    dropped = int(c["ill"].sum()) / max(int(live.sum()), 1)
+    print("%s: %d of %d non-empty elements ill-conditioned (%.3f %%)" % (case, int(c["ill"].sum()), int(live.sum()), 100 * dropped))
+    assert dropped <= 0.01
+    y, dx, dq = _run(c, True)
+    tag = str(case)
+    yc = y.cpu().double()
+    assert torch.isfinite(yc).all()
+    row_err = (yc - c["y"]).norm(dim=1)
+    print("%s: max row |y - ref|_2 %.3g" % (tag, float(row_err.max())))
+    assert float(row_err.max()) <= 2e-4                                # rows have unit norm
+    well = ~c["ill"]
+    np.testing.assert_allclose(yc[well].numpy(), c["y"][well].numpy(), rtol=2e-4, atol=2e-5, err_msg="y " + tag)
+    assert (yc[c["scale"] == 0] == 0).all(), "y must be exactly zero where the bucket is"
+    norms = (yc * yc).sum(1)
+    has = c["z"].abs().sum(1) > 0
+    assert torch.allclose(norms[has], torch.ones(int(has.sum()), dtype=torch.float64), atol=1e-5)
+    _close_grad(dx, c["dx1"], "dx " + tag)
+    _close_grad(dq, c["dq1"], "dq " + tag)
+    if c["zero_x"] is not None:                                        # a padded photo: y = 0, finite gradients
+        assert (yc[c["zero_x"]] == 0).all() and torch.isfinite(dx[c["zero_x"]]).all()
+    if c["zero_q"] is not None:                                        # a zero question: y = 0 and dx = 0 on all its rows
+        rows = slice(c["zero_q"] * c["P"], (c["zero_q"] + 1) * c["P"])
+        assert (yc[rows] == 0).all() and (dx[rows] == 0).all() and torch.isfinite(dq[c["zero_q"]]).all()
+
+
+@pytest.mark.parametrize("normalize", [False, True])
+def test_shared_rows_equal_tiled_rows(normalize):
+    c = _case(2, 3, 37, 10, 100)
+    out_s, dx_s, dq_s = _run(c, normalize)
+    out_t, dx_t, dq_t = _run(c, normalize, q=c["q"].repeat_interleave(3, 0), P=1)
+    assert torch.equal(out_s, out_t) and torch.equal(dx_s, dx_t)
+    want = (c["dq1"] if normalize else c["dq0"])
+    _close_grad(dq_t.reshape(2, 3, 10).sum(1), want, "tiled dq summed")
+    _close_grad(dq_s, dq_t.reshape(2, 3, 10).sum(1).cpu(), "shared dq against the tiled sum")
+
+
+@pytest.mark.parametrize("normalize", [False, True])
+def test_two_calls_are_bitwise_equal(normalize):
+    c = _case(*REPRO)
+    a, b = _run(c, normalize), _run(c, normalize)
+    for name, u, v in zip(("out", "dx", "dq"), a, b):
+        assert torch.equal(u, v), name
+
+
+def test_non_contiguous_x():
+    c = _case(2, 5, 257, 128, 1000)
+    wide = torch.zeros(c["x"].shape[0], c["d1"] + 9)
+    wide[:, 4:4 + c["d1"]] = c["x"]
+    from fvta_memexqa_amd import autograd
+    wide = wide.cuda().requires_grad_()
+    view = wide[:, 4:4 + c["d1"]]
+    assert not view.is_contiguous()
+    q = c["q"].cuda().requires_grad_()
+    out = autograd.compact_bilinear(view, q, *_dev_tables(c), c["D"], P=c["P"], normalize=True)
+    (out * c["gy"].cuda()).sum().backward()
+    ref_out, ref_dx, ref_dq = _run(c, True)
+    assert torch.equal(out.detach(), ref_out) and torch.equal(q.grad, ref_dq)
+    assert torch.equal(wide.grad[:, 4:4 + c["d1"]], ref_dx) and (wide.grad[:, :4] == 0).all() and (wide.grad[:, 4 + c["d1"]:] == 0).all()
+
+
+def test_bad_shapes_and_tables_raise():
+    from fvta_memexqa_amd import autograd, ops
+    c = _case(2, 3, 37, 10, 100)
+    tabs = _dev_tables(c)
+    with pytest.raises(ValueError, match="do not fit P"):
+        autograd.compact_bilinear(c["x"].cuda(), c["q"].cuda(), *tabs, 100, P=2)
+    with pytest.raises(ValueError, match="tables do not fit"):
+        autograd.compact_bilinear(c["x"].cuda()[:, :30], c["q"].cuda(), *tabs, 100, P=3)
+    with pytest.raises(Exception, match="16384"):
+        ops.CompactBilinear(1, 1, 8, 4, 20000).forward(None, None, None, None, None, None)
+
+
+@functools.lru_cache(maxsize=None)
+def _layer_case():
+    B, H, W, d1, d2, D = 2, 2, 3, 37, 10, 100
+    g = torch.Generator().manual_seed(77)
+    b1 = torch.relu(torch.randn(B, H, W, d1, generator=g))
+    b2 = 0.5 * torch.randn(B, H, W, d2, generator=g)
+    b2s = 0.5 * torch.randn(B, 1, 1, d2, generator=g)
+    return B, H, W, d1, d2, D, b1, b2, b2s
+
+
+def test_pooling_layer_keeps_the_references_signature():
+    from fvta_memexqa_amd import functional as F
+    B, H, W, d1, d2, D, b1, b2, b2s = _layer_case()
+    tabs = _tables(d1, d2, D)                                           # the default seeds 1 / 3 / 5 / 7
+    flat = lambda t: t.double().reshape(-1, t.shape[-1])
+    ref = R.cbp_direct(flat(b1), flat(b2), *tabs, D).reshape(B, H, W, D)
+    got = F.compact_bilinear_pooling_layer(b1.cuda(), b2.cuda(), D, sum_pool=False, sequential=False, compute_size=16)
+    _close_out(got, ref, "layer, per position")
+    pooled = F.compact_bilinear_pooling_layer(b1.cuda(), b2.cuda(), D)  # sum_pool=True is the default
+    assert tuple(pooled.shape) == (B, D)
+    _close_out(pooled, ref.sum((1, 2)), "layer, sum pooled")
+    shared = F.compact_bilinear_pooling_layer(b1.cuda(), b2s.cuda(), D, sum_pool=False)
+    tiled = F.compact_bilinear_pooling_layer(b1.cuda(), b2s.expand(B, H, W, d2).cuda(), D, sum_pool=False)
+    assert torch.equal(shared, tiled)
+    _close_out(shared, R.cbp_direct(flat(b1), b2s.double().reshape(B, d2), *tabs, D, P=H * W).reshape(B, H, W, D), "layer, shared row")
+    other = _tables_seeded(d1, d2, D, (11, 13, 15, 17))
+    got = F.compact_bilinear_pooling_layer(b1.cuda(), b2.cuda(), D, sum_pool=False, seed_h_1=11, seed_s_1=13, seed_h_2=15, seed_s_2=17)
+    _close_out(got, R.cbp_direct(flat(b1), flat(b2), *other, D).reshape(B, H, W, D), "layer, other seeds")
+    got = F.compact_bilinear_pooling_layer(b1.cuda(), b2.cuda(), D, sum_pool=False, rand_h_1=other[0], rand_s_1=other[1])
+    _close_out(got, R.cbp_direct(flat(b1), flat(b2), other[0], other[1], tabs[2], tabs[3], D).reshape(B, H, W, D), "layer, given tables")
+    bad = other[0].copy()
+    bad[0] = D
+    with pytest.raises(ValueError, match="rand_h_1"):
+        F.compact_bilinear_pooling_layer(b1.cuda(), b2.cuda(), D, rand_h_1=bad)
+
+
+def _tables_seeded(d1, d2, D, seeds):
+    from fvta_memexqa_amd import ops
+    return ops.count_sketch_tables(d1, d2, D, seeds)
+
+
+def test_pooling_module_and_its_gradients():
+    from fvta_memexqa_amd import nn
+    B, H, W, d1, d2, D, b1, b2, b2s = _layer_case()
+    mod = nn.CompactBilinearPooling(d1, d2, D, sum_pool=True)
+    assert sorted(mod.state_dict()) == ["rand_h_1", "rand_h_2", "rand_s_1", "rand_s_2"] and not list(mod.parameters())
+    tabs = _tables(d1, d2, D)
+    assert (mod.state_dict()["rand_h_1"].cpu().numpy() == tabs[0]).all()
+    x, q = b1.cuda().requires_grad_(), b2s.cuda().requires_grad_()
+    g = torch.randn(B, D, generator=torch.Generator().manual_seed(3))
+    out = mod(x, q)
+    (out * g.cuda()).sum().backward()
+    x64, q64 = b1.double().requires_grad_(), b2s.double().requires_grad_()
+    ref = R.cbp_direct(x64.reshape(-1, d1), q64.reshape(B, d2), *tabs, D, P=H * W).reshape(B, H * W, D).sum(1)
+    (ref * g.double()).sum().backward()
+    _close_out(out, ref, "module")
+    _close_grad(x.grad, x64.grad, "module d_bottom1")
+    _close_grad(q.grad, q64.grad, "module d_bottom2")
+
+
+# ------------------------------------------------------------------ the attention and the head
+HEAD = dict(N=3, M=2, JI=3, idim=37, h2=16, D=250, c1=32, C=4)
+
+
+@functools.lru_cache(maxsize=None)
+def _head_case(add_tanh=False):
+    s = HEAD
+    g = torch.Generator().manual_seed(2024)
+    rn = lambda *shape: torch.randn(*shape, generator=g)
+    w = lambda fan_in, fan_out: 0.5 / fan_in ** 0.5 * rn(fan_in, fan_out)
+    inputs = dict(lq=0.5 * rn(s["N"], s["h2"]), g1=0.5 * rn(s["N"], s["h2"]), hpis=torch.relu(rn(s["N"], s["M"], s["JI"], s["idim"])),
+                  lchoices=0.5 * rn(s["N"], s["C"], s["h2"]))
+    params = {"mcb_attention/filter_conv1": w(s["D"], s["c1"]), "mcb_attention/filter_conv2": w(s["c1"], 1),
+              "mcb_attention/g_mcb_trans/W": w(s["idim"], s["h2"]), "mcb_attention/g_mcb_trans/b": 0.1 * rn(s["h2"]),
+              "output/att_logits/W": w(7 * s["h2"], 1), "output/att_logits/b": 0.1 * rn(1)}
+    g_att, g_out, g_logits = rn(s["N"], s["idim"]), rn(s["N"], s["M"] * s["JI"]), rn(s["N"], s["C"])
+    tabs = _tables(s["idim"], s["h2"], s["D"])
+    i64 = {k: v.double().requires_grad_() for k, v in inputs.items()}
+    p64 = {k: v.double().requires_grad_() for k, v in params.items()}
+    attended, att = R.mcb_attention(i64["hpis"], i64["lq"], tabs, p64["mcb_attention/filter_conv1"], p64["mcb_attention/filter_conv2"])
+    att_leaves = (i64["hpis"], i64["lq"], p64["mcb_attention/filter_conv1"], p64["mcb_attention/filter_conv2"])
+    att_grads = torch.autograd.grad((attended * g_att.double()).sum() + (att * g_out.double()).sum(), att_leaves)
+    logits, att2 = R.mcb_head(i64["lq"], i64["g1"], i64["hpis"], i64["lchoices"], tabs, *(p64[k] for k in params), add_tanh=add_tanh)
+    leaves = list(i64.values()) + list(p64.values())
+    head_grads = torch.autograd.grad((logits * g_logits.double()).sum(), leaves)
+    return dict(inputs=inputs, params=params, g_att=g_att, g_out=g_out, g_logits=g_logits, attended=attended.detach(),
+                att=att.detach(), att_grads=att_grads, logits=logits.detach(), head_grads=dict(zip(list(i64) + list(p64), head_grads)))
+
+
+def _load(mod, params, prefix=""):
+    with torch.no_grad():
+        for k, v in params.items():
+            if k.startswith(prefix) and k[len(prefix):] in mod._parameters:
+                mod._parameters[k[len(prefix):]].copy_(v)
+
+
+def test_mcb_attention_matches_reference():
+    from fvta_memexqa_amd import nn
+    s, c = HEAD, _head_case()
+    mod = nn.MCBAttention(s["idim"], s["h2"], mcb_outdim=s["D"], conv1_out=s["c1"])
+    assert sorted(n for n, _ in mod.named_parameters()) == ["filter_conv1", "filter_conv2"]
+    assert tuple(mod.p("filter_conv1").shape) == (s["D"], s["c1"]) and tuple(mod.p("filter_conv2").shape) == (s["c1"], 1)
+    assert 0 < float(mod.p("filter_conv1").detach().abs().max()) <= 0.04 + 1e-6          # truncated normal(0.02): nothing past 2 sigma
+    _load(mod, c["params"], "mcb_attention/")
+    hpis, gq = c["inputs"]["hpis"].cuda().requires_grad_(), c["inputs"]["lq"].cuda().requires_grad_()
+    attended, att = mod(hpis, gq)
+    _close_out(attended, c["attended"], "attended")
+    _close_out(att, c["att"], "att")
+    assert torch.allclose(att.sum(1), torch.ones(s["N"], device=att.device), atol=1e-5)
+    ((attended * c["g_att"].cuda()).sum() + (att * c["g_out"].cuda()).sum()).backward()
+    got = (hpis.grad, gq.grad, mod.p("filter_conv1").grad, mod.p("filter_conv2").grad)
+    for name, a, b in zip(("d_hpis", "d_gq", "d_filter_conv1", "d_filter_conv2"), got, c["att_grads"]):
+        _close_grad(a, b, "MCBAttention " + name)
+
+
+@pytest.mark.parametrize("add_tanh", [False, True])
+def test_mcb_head_matches_reference(add_tanh):
+    from fvta_memexqa_amd import nn
+    s, c = HEAD, _head_case(add_tanh)
+    head = nn.MCBHead(s["idim"], s["h2"], mcb_outdim=s["D"], num_choice=s["C"], add_tanh=add_tanh, conv1_out=s["c1"])
+    assert sorted(n for n, _ in head.named_parameters()) == sorted(c["params"])
+    assert tuple(head.p("output/att_logits/W").shape) == (7 * s["h2"], 1)
+    _load(head, c["params"])
+    leaves = {k: v.cuda().requires_grad_() for k, v in c["inputs"].items()}
+    logits = head(leaves["lq"], leaves["g1"], leaves["hpis"], leaves["lchoices"])
+    assert tuple(logits.shape) == (s["N"], s["C"])
+    _close_out(logits, c["logits"], "logits")
+    _close_out(head.att, c["att"], "head.att")
+    assert torch.allclose(head.att.sum(1), torch.ones(s["N"], device=logits.device), atol=1e-5)
+    (logits * c["g_logits"].cuda()).sum().backward()
+    for k, v in leaves.items():
+        _close_grad(v.grad, c["head_grads"][k], "MCBHead d_" + k)
+    for k in c["params"]:
+        _close_grad(head.p(k).grad, c["head_grads"][k], "MCBHead d_" + k)
+
+
+def test_adam_lowers_the_loss_of_the_head():
+    from fvta_memexqa_amd import nn
+    s, c = HEAD, _head_case()
+    head = nn.MCBHead(s["idim"], s["h2"], mcb_outdim=s["D"], num_choice=s["C"], conv1_out=s["c1"], seed=1)
+    _load(head, c["params"])
+    inputs = {k: v.cuda() for k, v in c["inputs"].items()}
+    y = torch.tensor([0, 3, 1], device="cuda")
+    opt = torch.optim.Adam(head.parameters(), lr=0.01)
+    losses = []
+    for _ in range(10):
+        opt.zero_grad()
+        loss = torch.nn.functional.cross_entropy(head(inputs["lq"], inputs["g1"], inputs["hpis"], inputs["lchoices"]), y)
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+    assert np.isfinite(losses).all() and losses[-1] < losses[0], losses

@@ -57,6 +57,10 @@ class CbpDesc(Structure):
     _fields_ = [(n, c_int32) for n in ("N", "P", "d1", "d2", "D", "normalize", "training")]
 
 
+class AttnSharedDesc(Structure):
+    _fields_ = [(n, c_int32) for n in ("A", "NQ", "K", "T", "JQ", "w", "simi", "add_tanh")]
+
+
 CTX_KMAX = 8
 
 
@@ -124,6 +128,9 @@ _SIGS = {
     "fvta_cbp_workspace_bytes": (c_size_t, [POINTER(CbpDesc), c_int32]),
     "fvta_cbp_fwd": (c_int, [POINTER(CbpDesc), P, P, P, P, P, P, P, P, P, P]),
     "fvta_cbp_bwd": (c_int, [POINTER(CbpDesc), P, P, P, P, P, P, P, P, P, P, c_int32, P, P]),
+    "fvta_attn_shared_workspace_bytes": (c_size_t, [POINTER(AttnSharedDesc)]),
+    "fvta_attn_shared_plan": (c_int, [POINTER(AttnSharedDesc), POINTER(c_int32)]),
+    "fvta_attn_shared_fwd": (c_int, [POINTER(AttnSharedDesc), P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_workspace_bytes": (c_size_t, [POINTER(TimewarpDesc)]),
     "fvta_timewarp_fwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_bwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
@@ -209,7 +216,7 @@ def load():
         fn.argtypes = args
     # the descriptor structs are declared twice (include/fvta_hip.h and above): refuse a library whose layout differs
     for which, cls in list(enumerate((AttnDesc, LstmDesc, ScorerDesc, TimewarpDesc, EmbedDesc, ImgTransDesc, GuardDesc, GuardCtl))) + \
-            [(9, AttGruSeqDesc), (10, GruSeqDesc), (11, CbpDesc)]:
+            [(9, AttGruSeqDesc), (10, GruSeqDesc), (11, CbpDesc), (12, AttnSharedDesc)]:
         have, want = ctypes.sizeof(cls), lib.fvta_abi_struct_bytes(which)
         if have != want:
             raise FvtaError("%s is %d bytes here but %d in %s: rebuild the library (descriptor layouts differ)"

@@ -1,0 +1,491 @@
+// Focal attention forward for MANY QUESTIONS OVER ONE ALBUM (fvta_attn_shared_fwd): hinfo [A,K,T,w] holds each album's
+// context rows once, question i reads album[i]'s.  Per question the result is fvta_attn_fwd's on the pair
+// (hinfo[album[i]], hq[i]) -- model_v2.py:210-298 -- but a row is fetched once per GROUP of up to G questions of the same
+// album instead of once per question, and the logits of a group are one [rows, w] x [w, G JP] product on the fp32 matrix
+// pipe (gemm_f32.h: v_mfma_f32_32x32x2_f32, exact fp32).  Forward only: no `saved`, no time warp, no shadow rows.
+//
+// Bilinear form (attn_common.h): x[t,(g,j)] = rs[t] sum_c h[t,c] Qs[g,j,c] + (Rh.h[t] + R2.h[t]^2) + ct[g,j].
+// Launches, all on the caller's stream, none waits for the host:
+//   1. attn_vecs_kernel            the per-channel vectors of att_logits/W (attn_fwd.hip's)
+//   2. attn_shared_prep_q_kernel   Qs [NQ][JP][w] (rows j >= JQ zero), ct [NQ][JP]; JP = 32 (JQ <= 32) or 64
+//   3. attn_shared_plan_kernel     one workgroup: counting sort of `album` (clamped into [0, A)), groups of <= G questions
+//                                  cut per album: grp[] = {album, first, count}, order[], qslot[], ngroups
+//   4. attn_shared_logits_kernel   one workgroup per (group, k, tile of SH_R rows): the product (BM x BN 256 = G JP), row
+//                                  terms, tanh, exp_mask, max over j -> amax [NQ,K,T] (and a_logits).  A tile without a
+//                                  valid row skips the product: its logits are -1e30 whatever the rows hold
+//   5. attn_shared_softmax_kernel  per question: M[k] = max_t amax, L[k] = sum_t exp(amax - M[k]), coef[k] =
+//                                  softmax_k(M)[k] / L[k].  Masking needs no special case: a fully masked (album, k) or
+//                                  question has amax = -1e30 everywhere, which IS the uniform softmax over all T
+//   6. attn_shared_wsum_kernel     one workgroup per (group, k, split of T): part[g] = coef sum_t exp(amax - M) h[t] for
+//                                  the G questions from ONE read of each row
+//   7. attn_shared_merge_kernel    h_a[q] = sum over (k, split) of the partials, in that order
+// Row traffic: (4) and (6) read each row of an album once per group of that album: twice per group, never per question.
+// Determinism: no floating-point atomics.  The split of T depends on the descriptor only; a question's numbers do not
+// depend on which group, slot or wave it lands in (every column of the product is its own k-ordered fmaf chain, every
+// question has its own accumulators), so the integer atomics that place the questions in `order` cannot change a bit.
+#include "attn_common.h"
+#include "gemm_f32.h"
+
+namespace fvta {
+
+constexpr int SH_BN = 256;   // question columns of a group: G * JP
+constexpr int SH_NT = 256;
+constexpr int SH_CH = 64;    // rows whose softmax weights the weighted-sum kernel stages at a time
+constexpr int SH_PLAN_NT = 1024;
+// 64 rows x 256 columns, a wave 64 x 64: 200 registers, two workgroups per CU.  (MmaF32<2, 2, 2, 4>, 128 rows and half the
+// question staging per row, was measured: 331 registers, one wave per SIMD, and no faster at 8 questions per album, 20 %
+// slower at one -- DESIGN.md 4.1)
+typedef MmaF32<1, 4, 2, 2> ShMma;
+constexpr int SH_R = ShMma::BM;      // rows of a tile of the logits kernel
+static_assert(ShMma::BN == SH_BN && ShMma::NT == SH_NT && ShMma::TN % 2 == 0, "tile shape");
+
+struct ShShape {
+  int A, NQ, K, T, JQ, w, simi, add_tanh, use_mask;
+  int JP, G;      // padded question length (32 / 64), questions per group (8 / 4)
+  int ntile;      // row tiles of a (k): ceil(T / SH_R)
+  int S, rps;     // T splits of the weighted sum, rows per split
+  int ngmax;      // upper bound of the number of groups: floor(NQ / G) + min(A, NQ), at most NQ
+};
+
+static ShShape sh_shape(const fvta_attn_shared_desc* d) {
+  ShShape s;
+  s.A = d->A, s.NQ = d->NQ, s.K = d->K, s.T = d->T, s.JQ = d->JQ, s.w = d->w, s.simi = d->simi, s.add_tanh = d->add_tanh;
+  s.use_mask = 0;
+  s.JP = d->JQ <= 32 ? 32 : 64;
+  s.G = SH_BN / s.JP;
+  s.ntile = (d->T + SH_R - 1) / SH_R;
+  const int64_t ng = (int64_t)d->NQ / s.G + (d->A < d->NQ ? d->A : d->NQ);
+  s.ngmax = (int)(ng < d->NQ ? ng : d->NQ);
+  // about 1024 workgroups of the weighted sum (4 per CU), a split not shorter than one chunk
+  int64_t S = (1024 + (int64_t)s.ngmax * d->K - 1) / ((int64_t)s.ngmax * d->K);
+  const int maxs = (d->T + SH_CH - 1) / SH_CH;
+  if (S > maxs) S = maxs;
+  if (S < 1) S = 1;
+  s.rps = (int)((d->T + S - 1) / S);
+  s.S = (d->T + s.rps - 1) / s.rps;
+  return s;
+}
+
+struct ShWork {
+  float *vecs, *Qs, *ct, *amax, *M, *coef, *part;
+  int *acnt, *astart, *agrp, *order, *qslot, *ngroups;
+  int4* grp;
+  size_t bytes;
+  ShWork(const ShShape& s, void* p) {
+    FvtaCarver c(p);
+    vecs = c.take<float>((size_t)VEC_COUNT * s.w);
+    Qs = c.take<float>((size_t)s.NQ * s.JP * s.w);
+    ct = c.take<float>((size_t)s.NQ * s.JP);
+    amax = c.take<float>((size_t)s.NQ * s.K * s.T);
+    M = c.take<float>((size_t)s.NQ * s.K);
+    coef = c.take<float>((size_t)s.NQ * s.K);
+    part = c.take<float>((size_t)s.ngmax * s.K * s.S * s.G * s.w);
+    acnt = c.take<int>((size_t)s.A);
+    astart = c.take<int>((size_t)s.A);
+    agrp = c.take<int>((size_t)s.A);
+    order = c.take<int>((size_t)s.NQ);
+    qslot = c.take<int>((size_t)s.NQ);
+    ngroups = c.take<int>(1);
+    grp = c.take<int4>((size_t)s.ngmax);
+    bytes = c.off;
+  }
+};
+
+// the per-channel vectors of att_logits/W in attn_common.h's layout: attn_fwd.hip's kernel (feat_order 0 = model_v2.py's)
+__global__ void attn_vecs_kernel(const float* __restrict__ W, int w, int simi, int feat_order, float* __restrict__ vecs);
+
+// ---- question side.  grid (NQ, JP / 4), 256 threads: a wave per position j
+__global__ __launch_bounds__(256) void attn_shared_prep_q_kernel(ShShape s, ShWork wk, const float* __restrict__ hq,
+                                                                 const float* __restrict__ bptr) {
+  const int q = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, w = s.w;
+  const float* Uv = wk.vecs + VEC_U * w;
+  const float* Cq = wk.vecs + VEC_CQ * w;
+  const float* C2 = wk.vecs + VEC_C2 * w;
+  const float bias = (s.simi == 4 || bptr == nullptr) ? 0.f : bptr[0];
+  const int j = 4 * blockIdx.y + wave;
+  float* dst = wk.Qs + ((size_t)q * s.JP + j) * w;
+  if (j >= s.JQ) {  // (wave-uniform)
+    for (int c = lane; c < w; c += 64) dst[c] = 0.f;
+    if (lane == 0) wk.ct[(size_t)q * s.JP + j] = 0.f;
+    return;
+  }
+  const float* row = hq + ((size_t)q * s.JQ + j) * w;
+  float s1 = 0.f, s2 = 0.f;
+  for (int c = lane; c < w; c += 64) {
+    const float v = row[c];
+    s1 += Cq[c] * v + C2[c] * v * v;
+    s2 += v * v;
+  }
+  s1 = wave_sum(s1);
+  s2 = wave_sum(s2);
+  const float rq = rsqrtf(fmaxf(s2, 1e-12f));  // tf.nn.l2_normalize eps (cosine only)
+  for (int c = lane; c < w; c += 64) dst[c] = s.simi == 4 ? row[c] * rq : row[c] * Uv[c];
+  if (lane == 0) wk.ct[(size_t)q * s.JP + j] = s.simi == 4 ? 0.f : s1 + bias;
+}
+
+// ---- the plan.  One workgroup.  Indices are data: clamped before they address anything.
+__device__ __forceinline__ int sh_album(const int* album, int i, int A) {
+  const int a = album[i];
+  return a < 0 ? 0 : (a >= A ? A - 1 : a);
+}
+__global__ __launch_bounds__(SH_PLAN_NT) void attn_shared_plan_kernel(ShShape s, ShWork wk, const int* __restrict__ album) {
+  __shared__ int cell_c[SH_PLAN_NT], cell_g[SH_PLAN_NT];
+  const int tid = threadIdx.x, A = s.A, NQ = s.NQ, G = s.G;
+  for (int a = tid; a < A; a += SH_PLAN_NT) wk.acnt[a] = 0;
+  __syncthreads();
+  for (int i = tid; i < NQ; i += SH_PLAN_NT) atomicAdd(&wk.acnt[sh_album(album, i, A)], 1);
+  __syncthreads();
+  const int C = (A + SH_PLAN_NT - 1) / SH_PLAN_NT;
+  const int lo = min(tid * C, A), hi = min(lo + C, A);
+  int mine_c = 0, mine_g = 0;
+  for (int a = lo; a < hi; ++a) {
+    const int c = wk.acnt[a];
+    mine_c += c;
+    mine_g += (c + G - 1) / G;
+  }
+  cell_c[tid] = mine_c;
+  cell_g[tid] = mine_g;
+  __syncthreads();
+  for (int o = 1; o < SH_PLAN_NT; o <<= 1) {  // inclusive scans of the chunk sums
+    const int vc = tid >= o ? cell_c[tid - o] : 0, vg = tid >= o ? cell_g[tid - o] : 0;
+    __syncthreads();
+    cell_c[tid] += vc;
+    cell_g[tid] += vg;
+    __syncthreads();
+  }
+  int run_c = cell_c[tid] - mine_c, run_g = cell_g[tid] - mine_g;
+  for (int a = lo; a < hi; ++a) {
+    const int c = wk.acnt[a], ng = (c + G - 1) / G;
+    wk.astart[a] = run_c;
+    wk.agrp[a] = run_g;
+    wk.acnt[a] = 0;  // from here on the album's cursor
+    for (int x = 0; x < ng; ++x)
+      if (run_g + x < s.ngmax) wk.grp[run_g + x] = int4{a, run_c + x * G, min(G, c - x * G), 0};
+    run_c += c;
+    run_g += ng;
+  }
+  if (tid == SH_PLAN_NT - 1) *wk.ngroups = min(cell_g[tid], s.ngmax);
+  __syncthreads();
+  for (int i = tid; i < NQ; i += SH_PLAN_NT) {
+    const int a = sh_album(album, i, A);
+    const int off = atomicAdd(&wk.acnt[a], 1);
+    wk.order[wk.astart[a] + off] = i;
+    wk.qslot[i] = (wk.agrp[a] + off / G) * G + off % G;
+  }
+}
+
+// ---- logits.  grid ngmax * K * ntile, 256 threads
+template <int JT>
+__global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, ShWork wk, const float* __restrict__ hinfo,
+                                                                  const uint8_t* __restrict__ hmask,
+                                                                  const uint8_t* __restrict__ qmask,
+                                                                  float* __restrict__ a_logits) {
+  constexpr int JP = 32 * JT, G = SH_BN / JP;
+  __shared__ __attribute__((aligned(16))) float smem[ShMma::LDS_FLOATS];
+  __shared__ float s_rt[SH_R], s_ct[SH_BN];
+  __shared__ int s_q[G];
+  __shared__ uint8_t s_hv[SH_R], s_cv[SH_BN];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tile = blockIdx.x % s.ntile, k = (blockIdx.x / s.ntile) % s.K, grp = blockIdx.x / (s.ntile * s.K);
+  if (grp >= *wk.ngroups) return;
+  const int4 gi = wk.grp[grp];
+  const int a = gi.x, first = gi.y, cnt = gi.z;
+  const int T = s.T, w = s.w, JQ = s.JQ, K = s.K, t0 = tile * SH_R;
+  const size_t ak = (size_t)a * K + k;
+  if (tid < G) s_q[tid] = tid < cnt ? wk.order[first + tid] : -1;
+  bool rowv = false;
+  if (tid < SH_R) {
+    const int t = t0 + tid;
+    rowv = t < T && (!s.use_mask || hmask[ak * T + t] != 0);
+    s_hv[tid] = rowv;
+  }
+  __syncthreads();
+  {
+    const int q = s_q[tid / JP], j = tid % JP;
+    const bool ok = q >= 0 && j < JQ;
+    s_ct[tid] = ok ? wk.ct[(size_t)q * JP + j] : 0.f;
+    s_cv[tid] = ok && (!s.use_mask || qmask[(size_t)q * JQ + j] != 0);
+  }
+  const int anyrow = __syncthreads_or(rowv ? 1 : 0);
+  if (!anyrow) {  // every logit of the tile is masked: -1e30, whatever the rows hold
+    const int rows = min(SH_R, T - t0);
+    for (int e = tid; e < cnt * rows; e += SH_NT) wk.amax[((size_t)s_q[e / rows] * K + k) * T + t0 + e % rows] = FVTA_NEG;
+    if (a_logits)
+      for (int g = 0; g < cnt; ++g) {
+        float* dst = a_logits + (((size_t)s_q[g] * K + k) * T + t0) * JQ;
+        for (int e = tid; e < rows * JQ; e += SH_NT) dst[e] = FVTA_NEG;
+      }
+    return;
+  }
+  const float* hbase = hinfo + ak * T * w;
+  // row terms: a wave per SH_R / 4 rows.  cosine: 1 / |h| instead
+  {
+    const float* Rh = wk.vecs + VEC_RH * w;
+    const float* R2 = wk.vecs + VEC_R2 * w;
+    for (int r = wave * (SH_R / 4); r < (wave + 1) * (SH_R / 4); ++r) {
+      const int t = t0 + r;
+      float acc = 0.f;
+      if (t < T)
+        for (int c = 4 * lane; c < w; c += 256) {
+          const f32x4 h = ld4(hbase + (size_t)t * w + c);
+          const f32x4 v = h * (ld4(Rh + c) + ld4(R2 + c) * h);
+          acc += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+      acc = wave_sum(acc);
+      if (lane == 0) s_rt[r] = s.simi == 4 ? rsqrtf(fmaxf(acc, 1e-12f)) : acc;
+    }
+  }
+  ShMma mma;
+  mma.init(tid);
+  StageKContig<SH_R, ShMma::BK, SH_NT, ShMma::LDA> sa;
+  StageKContig<SH_BN, ShMma::BK, SH_NT, ShMma::LDB> sb;
+  auto fa = [&](int r, int kk, bool& ok) -> const float* {
+    const int t = t0 + r;
+    ok = t < T;
+    return hbase + (ok ? (size_t)t * w + kk : (size_t)0);
+  };
+  const float* Qs = wk.Qs;
+  auto fb = [&](int c, int kk, bool& ok) -> const float* {
+    const int q = s_q[c / JP];
+    ok = q >= 0;
+    return Qs + (ok ? ((size_t)q * JP + c % JP) * w + kk : (size_t)0);
+  };
+  gemm_mainloop(mma, sa, sb, fa, fb, 0, w, smem, tid);  // (ends on a barrier: s_rt is visible)
+  // epilogue.  A wave holds TM x TN tiles of 32 x 32: JT = 1: a question per column tile; JT = 2: one per pair of them
+  const bool cosine = s.simi == 4, tanh_on = s.add_tanh && !cosine;
+#pragma unroll
+  for (int i = 0; i < ShMma::TM; ++i) {
+    float mx[ShMma::TN][16];
+#pragma unroll
+    for (int jn = 0; jn < ShMma::TN; ++jn) {
+      const int col = mma.col_of(jn), q = s_q[col / JP], j = col % JP;
+      const bool colv = s_cv[col] != 0, live = q >= 0 && j < JQ;
+      const float ctv = s_ct[col];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = mma.row_of(i, r), t = t0 + row;
+        float x = mma.acc[i][jn][r];
+        x = cosine ? x * s_rt[row] : x + s_rt[row] + ctv;
+        if (tanh_on) x = tanhf(x);
+        const float v = (colv && s_hv[row]) ? x : FVTA_NEG;  // exp_mask: x + -1e30 is -1e30 in fp32
+        if (a_logits && live && t < T) a_logits[(((size_t)q * K + k) * T + t) * JQ + j] = v;
+        mx[jn][r] = live ? v : -INFINITY;
+      }
+    }
+#pragma unroll
+    for (int jn = 0; jn < ShMma::TN; jn += JT) {
+      const int q = s_q[mma.col_of(jn) / JP];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float m = JT == 2 ? fmaxf(mx[jn][r], mx[jn + 1][r]) : mx[jn][r];
+#pragma unroll
+        for (int o = 16; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));  // over the 32 columns, rows stay apart
+        const int t = t0 + mma.row_of(i, r);
+        if (mma.l31 == r && q >= 0 && t < T) wk.amax[((size_t)q * K + k) * T + t] = m;
+      }
+    }
+  }
+}
+
+// the same bits in every thread: butterflies inside a wave, the four wave results in order
+__device__ __forceinline__ float sh_block_max(float v, float* red) {
+  v = wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+__device__ __forceinline__ float sh_block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// ---- the two softmaxes' scalars.  grid NQ, 256 threads, K <= 64
+__global__ __launch_bounds__(256) void attn_shared_softmax_kernel(ShShape s, ShWork wk) {
+  __shared__ float red[4], s_M[64], s_L[64];
+  const int q = blockIdx.x, tid = threadIdx.x, T = s.T, K = s.K;
+  for (int k = 0; k < K; ++k) {
+    const float* am = wk.amax + ((size_t)q * K + k) * T;
+    float m = -INFINITY;
+    for (int t = tid; t < T; t += 256) m = fmaxf(m, am[t]);
+    m = sh_block_max(m, red);
+    float l = 0.f;
+    for (int t = tid; t < T; t += 256) l += expf(am[t] - m);
+    l = sh_block_sum(l, red);
+    if (tid == 0) {
+      s_M[k] = m;
+      s_L[k] = l;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {  // outer softsel over K (model_v2.py:278): logits = max over (t, j) of the masked logits
+    float mx = -INFINITY, sum = 0.f;
+    for (int k = 0; k < K; ++k) mx = fmaxf(mx, s_M[k]);
+    for (int k = 0; k < K; ++k) sum += expf(s_M[k] - mx);
+    for (int k = 0; k < K; ++k) {
+      wk.M[(size_t)q * K + k] = s_M[k];
+      wk.coef[(size_t)q * K + k] = expf(s_M[k] - mx) / sum / s_L[k];
+    }
+  }
+}
+
+// ---- weighted sums.  grid ngmax * K * S, 256 threads: thread tid owns channels 4 tid .. + 3 (+ 1024 per further CPT)
+template <int G, int CPT>
+__global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork wk, const float* __restrict__ hinfo) {
+  __shared__ float s_p[SH_CH][G], s_M[G], s_cf[G];
+  __shared__ int s_q[G];
+  const int tid = threadIdx.x;
+  const int sp = blockIdx.x % s.S, k = (blockIdx.x / s.S) % s.K, grp = blockIdx.x / (s.S * s.K);
+  if (grp >= *wk.ngroups) return;
+  const int4 gi = wk.grp[grp];
+  const int a = gi.x, first = gi.y, cnt = gi.z;
+  const int T = s.T, w = s.w, K = s.K;
+  if (tid < G) {
+    const int q = tid < cnt ? wk.order[first + tid] : -1;
+    s_q[tid] = q;
+    s_M[tid] = q >= 0 ? wk.M[(size_t)q * K + k] : 0.f;
+    s_cf[tid] = q >= 0 ? wk.coef[(size_t)q * K + k] : 0.f;
+  }
+  f32x4 acc[G][CPT];
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int i = 0; i < CPT; ++i) acc[g][i] = zero4();
+  const int tb = sp * s.rps, te = min(T, tb + s.rps);
+  const float* hbase = hinfo + ((size_t)a * K + k) * T * w;
+  const bool mine = 4 * tid < w;
+  for (int c0 = tb; c0 < te; c0 += SH_CH) {
+    __syncthreads();
+    for (int e = tid; e < SH_CH * G; e += 256) {
+      const int g = e / SH_CH, r = e % SH_CH, t = c0 + r, q = s_q[g];
+      s_p[r][g] = (t < te && q >= 0) ? expf(wk.amax[((size_t)q * K + k) * T + t] - s_M[g]) : 0.f;
+    }
+    __syncthreads();
+    const int nr = min(SH_CH, te - c0);
+    if (mine) {
+#pragma unroll 4
+      for (int r = 0; r < nr; ++r) {
+        const float* row = hbase + (size_t)(c0 + r) * w + 4 * tid;
+        f32x4 h[CPT];
+#pragma unroll
+        for (int i = 0; i < CPT; ++i) h[i] = ld4(row + 1024 * i);
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          const float p = s_p[r][g];
+#pragma unroll
+          for (int i = 0; i < CPT; ++i) acc[g][i] += h[i] * p;
+        }
+      }
+    }
+  }
+  if (mine) {
+    float* dst = wk.part + (((size_t)grp * K + k) * s.S + sp) * G * w + 4 * tid;
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+      if (g < cnt) {
+        const float cf = s_cf[g];
+#pragma unroll
+        for (int i = 0; i < CPT; ++i) *reinterpret_cast<f32x4*>(dst + (size_t)g * w + 1024 * i) = acc[g][i] * cf;
+      }
+  }
+}
+
+// ---- merge.  grid (NQ, ceil(w / 256)): a channel per thread, the partials in (k, split) order
+__global__ __launch_bounds__(256) void attn_shared_merge_kernel(ShShape s, ShWork wk, float* __restrict__ h_a) {
+  const int q = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+  if (c >= s.w) return;
+  const int slot = wk.qslot[q], grp = slot / s.G, g = slot % s.G;
+  float v = 0.f;
+  for (int k = 0; k < s.K; ++k)
+    for (int sp = 0; sp < s.S; ++sp) v += wk.part[((((size_t)grp * s.K + k) * s.S + sp) * s.G + g) * s.w + c];
+  h_a[(size_t)q * s.w + c] = v;
+}
+
+// 0: fine, else the status with the message set
+static int sh_check(const fvta_attn_shared_desc* d, const char* who) {
+  FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
+  FVTA_CHECK_ARG(d->A > 0 && d->NQ > 0 && d->K > 0 && d->T > 0 && d->JQ > 0 && d->w > 0, "%s: bad A/NQ/K/T/JQ/w (%d,%d,%d,%d,%d,%d)",
+                 who, d->A, d->NQ, d->K, d->T, d->JQ, d->w);
+  const char* why = nullptr;
+  const int w = d->w;
+  if (d->simi < 1 || d->simi > 4) {
+    fvta_set_error("%s: similarity matrix not implemented (simiMatrix=%d)", who, d->simi);
+    return FVTA_ERR_UNSUPPORTED;
+  }
+  if (!(w == 64 || w == 128 || w == 256 || w == 512 || w == 1024 || w == 2048))
+    why = "w must be one of 64,128,256,512,1024,2048";
+  else if (d->JQ > 64)
+    why = "JQ must be 1..64";
+  else if (d->K > 64)
+    why = "K must be 1..64";
+  else if (d->A > (1 << 28) || d->NQ > (1 << 28))
+    why = "A and NQ must not exceed 2^28";
+  if (!why) {
+    const ShShape s = sh_shape(d);
+    if ((int64_t)s.ngmax * d->K * s.ntile > 0x7fffffff || (int64_t)s.ngmax * d->K * s.S > 0x7fffffff) why = "too many workgroups";
+  }
+  if (why) {
+    fvta_set_error("%s: unsupported shape (A=%d NQ=%d K=%d T=%d JQ=%d w=%d): %s", who, d->A, d->NQ, d->K, d->T, d->JQ, w, why);
+    return FVTA_ERR_UNSUPPORTED;
+  }
+  return FVTA_OK;
+}
+
+template <int G>
+static void sh_launch_wsum(const ShShape& s, const ShWork& wk, const float* hinfo, hipStream_t st) {
+  const dim3 grid((unsigned)((int64_t)s.ngmax * s.K * s.S));
+  if (s.w <= 1024)
+    hipLaunchKernelGGL((attn_shared_wsum_kernel<G, 1>), grid, dim3(256), 0, st, s, wk, hinfo);
+  else
+    hipLaunchKernelGGL((attn_shared_wsum_kernel<G, 2>), grid, dim3(256), 0, st, s, wk, hinfo);
+}
+
+}  // namespace fvta
+using namespace fvta;
+
+extern "C" size_t fvta_attn_shared_workspace_bytes(const fvta_attn_shared_desc* d) {
+  if (sh_check(d, "attn_shared_workspace_bytes") != FVTA_OK) return 0;
+  return ShWork(sh_shape(d), nullptr).bytes;
+}
+
+extern "C" int fvta_attn_shared_plan(const fvta_attn_shared_desc* d, int32_t out[4]) {
+  if (int e = sh_check(d, "attn_shared_plan")) return e;
+  FVTA_CHECK_ARG(out != nullptr, "attn_shared_plan: null pointer");
+  const ShShape s = sh_shape(d);
+  out[0] = s.G;
+  out[1] = SH_R;
+  out[2] = s.S;
+  out[3] = 0;
+  return FVTA_OK;
+}
+
+extern "C" int fvta_attn_shared_fwd(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
+                                    const uint8_t* qmask, const int32_t* album, const float* W, const float* b, float* h_a,
+                                    float* a_logits, void* workspace, fvta_stream_t stream_) {
+  if (int e = sh_check(d, "attn_shared_fwd")) return e;
+  FVTA_CHECK_ARG(hinfo && hq && album && h_a && workspace, "attn_shared_fwd: null pointer");
+  FVTA_CHECK_ARG(d->simi == 4 || W, "attn_shared_fwd: simiMatrix %d needs att_logits/W", d->simi);
+  hipStream_t st = (hipStream_t)stream_;
+  ShShape s = sh_shape(d);
+  s.use_mask = (hmask && qmask) ? 1 : 0;  // model_v2.py:233: the mask applies only when both are given
+  const ShWork wk(s, workspace);
+  hipLaunchKernelGGL(attn_vecs_kernel, dim3((s.w + 255) / 256), dim3(256), 0, st, W, s.w, s.simi, 0, wk.vecs);
+  hipLaunchKernelGGL(attn_shared_prep_q_kernel, dim3(s.NQ, s.JP / 4), dim3(256), 0, st, s, wk, hq, b);
+  hipLaunchKernelGGL(attn_shared_plan_kernel, dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)album);
+  const dim3 lgrid((unsigned)((int64_t)s.ngmax * s.K * s.ntile));
+  if (s.JP == 32)
+    hipLaunchKernelGGL(attn_shared_logits_kernel<1>, lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits);
+  else
+    hipLaunchKernelGGL(attn_shared_logits_kernel<2>, lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits);
+  hipLaunchKernelGGL(attn_shared_softmax_kernel, dim3(s.NQ), dim3(256), 0, st, s, wk);
+  if (s.G == 8)
+    sh_launch_wsum<8>(s, wk, hinfo, st);
+  else
+    sh_launch_wsum<4>(s, wk, hinfo, st);
+  hipLaunchKernelGGL(attn_shared_merge_kernel, dim3(s.NQ, (s.w + 255) / 256), dim3(256), 0, st, s, wk, h_a);
+  FVTA_CHECK_LAUNCH("attn_shared_fwd");
+  return FVTA_OK;
+}

@@ -34,6 +34,7 @@ extern "C" int64_t fvta_abi_struct_bytes(int32_t which) {
     case 9: return (int64_t)sizeof(fvta_attgru_seq_desc);  // (8 stays -1: the host tests probe it as the unknown id)
     case 10: return (int64_t)sizeof(fvta_gru_seq_desc);
     case 11: return (int64_t)sizeof(fvta_cbp_desc);
+    case 12: return (int64_t)sizeof(fvta_attn_shared_desc);
     default: return -1;
   }
 }

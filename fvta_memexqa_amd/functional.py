@@ -173,6 +173,45 @@ def attention_raw(hinfo, hq, W, b, hinfo_mask=None, hq_mask=None, simiMatrix=1, 
     return h_a[:, :w].contiguous(), a
 
 
+def attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask=None, hq_mask=None, simiMatrix=1, add_tanh=False):
+    """attention_3d for NQ questions over A albums held once: hinfo [A,K,T,w] (or [A,K,M,JX,w]), hq [NQ,JQ,w], album [NQ]
+    integers in [0, A) (validated on the host before the upload), W / b as attention_raw -> (h_a [NQ,w], a_logits
+    [NQ,K,T,JQ]): question i attends album[i]'s rows, with attention_raw's result for that pair.  FORWARD ONLY
+    (fvta_attn_shared_fwd keeps nothing for a backward): with gradient mode on and an argument that requires grad this
+    raises instead of returning a detached result; train through attention_3d / attention_raw per question."""
+    if simiMatrix not in (1, 2, 3, 4):
+        raise ValueError("similarity matrix not implemented")
+    tensors = [t for t in (hinfo, hq, W, b) if torch.is_tensor(t)]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("attention_3d_shared_raw is forward-only: call it under torch.no_grad(), or use the per-question "
+                           "attention_3d (functional.attention_3d / attention_raw, nn.FocalAttention3D.forward), which is "
+                           "the differentiable route")
+    hinfo, hq = _f32(hinfo.detach()), _f32(hq.detach())
+    A, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
+    hinfo = hinfo.reshape(A, K, -1, w)
+    T = hinfo.shape[2]
+    NQ, JQ = hq.shape[0], hq.shape[1]
+    idx = ops.check_album_index(album, A)
+    if idx.shape[0] != NQ:
+        raise ValueError("album index: %d entries for %d questions" % (idx.shape[0], NQ))
+    wp = next((c for c in SUPPORTED_W if w <= c), None)
+    if wp is None:
+        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
+    F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
+    if F:
+        W = _pad_channels(_f32(W.detach()).reshape(F, w), wp).reshape(-1)
+        b = _f32(b.detach())
+    else:
+        W = b = None
+    dev = ops.require_gpu()
+    both = hinfo_mask is not None and hq_mask is not None                  # model_v2.py:233: only when BOTH are given
+    hm = ops.as_mask_u8(hinfo_mask.reshape(A, K, T)) if both else None
+    qm = ops.as_mask_u8(hq_mask) if both else None
+    op = ops.SharedFocalAttention(A, NQ, K, T, JQ, wp, simiMatrix, add_tanh)
+    h_a, a = op.forward(_pad_channels(hinfo, wp), hm, _pad_channels(hq, wp), qm, idx.to(dev), W, b, want_logits=True)
+    return h_a[:, :w].contiguous(), a
+
+
 def _attention(hinfo, hq, hinfo_mask, hq_mask, simiMatrix, wd, add_tanh, scope, feat_order, tscale=None):
     """attention_raw with the `att_logits` variables of the scope (linear(..., output_size=1, scope="att_logits"))"""
     if simiMatrix not in (1, 2, 3, 4):

@@ -102,6 +102,39 @@ class FocalAttention3D(_AttLogits):
         return functional.attention_raw(hinfo.reshape(N, K, -1, self.w), hq, W, b, hinfo_mask, hq_mask, self.simiMatrix,
                                         self.add_tanh, 0, tscale)
 
+    def forward_shared(self, hinfo, hq, album, hinfo_mask=None, hq_mask=None):
+        """forward() for NQ questions over A albums held once: hinfo [A,K,...,w], hq [NQ,JQ,w], album [NQ] in [0, A) ->
+        (h_a [NQ,w], a_logits [NQ,K,T,JQ]) with this module's att_logits/{W,b}.  Forward only
+        (functional.attention_3d_shared_raw): under gradient mode the parameters require grad and the call raises; use it
+        under torch.no_grad() and train through forward()."""
+        W, b = self._wb()
+        return functional.attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask, hq_mask, self.simiMatrix, self.add_tanh)
+
+
+class AlbumMemory:
+    """The context of A encoded albums, kept for any number of questions: hall [A,K,T,w] (or [A,K,M,JX,w]) and hall_mask
+    [A,K,T] as functional.context_tensor returns them, held contiguous fp32 / u8 on the device and detached.  No
+    parameters, no encoder: the caller encodes each album once and asks with attend()."""
+
+    def __init__(self, hall, hall_mask=None):
+        dev = ops.require_gpu()
+        A, K, w = hall.shape[0], hall.shape[1], hall.shape[-1]
+        self.hall = hall.detach().to(dev, torch.float32).reshape(A, K, -1, w).contiguous()
+        self.hall_mask = None if hall_mask is None else ops.as_mask_u8(hall_mask.detach().to(dev).reshape(A, K, -1))
+        if self.hall_mask is not None and tuple(self.hall_mask.shape) != tuple(self.hall.shape[:3]):
+            raise ValueError("AlbumMemory: mask %s does not match the rows %s" % (tuple(hall_mask.shape), tuple(hall.shape)))
+
+    def __len__(self):
+        return self.hall.shape[0]
+
+    def attend(self, attention, hq, hq_mask, album):
+        """(h_a [NQ,w], a_logits [NQ,K,T,JQ]) of `attention` (an nn.FocalAttention3D) for questions hq [NQ,JQ,w] about
+        albums album [NQ]; a bad index raises ValueError before anything reaches the library."""
+        idx = ops.check_album_index(album, len(self))
+        if idx.shape[0] != hq.shape[0]:
+            raise ValueError("album index: %d entries for %d questions" % (idx.shape[0], hq.shape[0]))
+        return attention.forward_shared(self.hall, hq, idx, self.hall_mask, hq_mask)
+
 
 class QuestionAttention(_AttLogits):
     """attention (model_v2.py:125-201), the K = 1 form `question_emb/question_att` uses: hinfo [N,...,w] flattened to

@@ -281,6 +281,54 @@ class FocalAttention:
         return u
 
 
+# ------------------------------------------------------------------ attention, many questions over one album
+def check_album_index(album, A):
+    """Host-side validation of a question -> album index, before it is uploaded (the kernels only clamp it): one
+    dimension, an integer dtype, every value in [0, A).  Returns it as a contiguous int32 CPU tensor.  Pure host: no GPU,
+    no library."""
+    t = album if torch.is_tensor(album) else torch.as_tensor(album)
+    if t.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+        raise ValueError("album index: an integer dtype is needed, got %s" % t.dtype)
+    if t.dim() != 1:
+        raise ValueError("album index: expected one dimension [NQ], got shape %s" % (tuple(t.shape),))
+    t = t.detach().cpu()
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= int(A)):
+        raise ValueError("album index: values must lie in [0, %d), got [%d, %d]" % (int(A), int(t.min()), int(t.max())))
+    return t.to(torch.int32).contiguous()
+
+
+class SharedFocalAttention:
+    """attention_3d (model_v2.py:210-298) of NQ questions over A albums whose context rows are held ONCE: hinfo [A,K,T,w],
+    hmask [A,K,T], hq [NQ,JQ,w], qmask [NQ,JQ], album [NQ] int32 on the device (validate it with check_album_index before
+    the upload).  Forward only (fvta_attn_shared_fwd); question i gets FocalAttention's result on album[i]'s rows."""
+
+    def __init__(self, A, NQ, K, T, JQ, w, simi, add_tanh):
+        self.lib = _lib.load()
+        self.dev = require_gpu()
+        self.A, self.NQ, self.K, self.T, self.JQ, self.w = int(A), int(NQ), int(K), int(T), int(JQ), int(w)
+        self.desc = _lib.AttnSharedDesc(self.A, self.NQ, self.K, self.T, self.JQ, self.w, int(simi), int(bool(add_tanh)))
+        nb = self.lib.fvta_attn_shared_workspace_bytes(ctypes.byref(self.desc))
+        if nb == 0:
+            raise _lib.FvtaError("shared attention: " + self.lib.fvta_last_error().decode())
+        self.work = _bytes(nb, self.dev)
+
+    def plan(self):
+        """{G, rows, tsplit}: questions per group, rows per logits tile, T splits of the weighted sum (host only)"""
+        out = (ctypes.c_int32 * 4)()
+        check(self.lib.fvta_attn_shared_plan(ctypes.byref(self.desc), out), "fvta_attn_shared_plan")
+        return dict(zip(("G", "rows", "tsplit"), (int(v) for v in out[:3])))
+
+    def forward(self, hinfo, hmask, hq, qmask, album, W, b, want_logits=False):
+        assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
+        assert album.is_cuda and album.dtype == torch.int32 and album.is_contiguous() and tuple(album.shape) == (self.NQ,)
+        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
+        a_logits = torch.empty(self.NQ, self.K, self.T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
+        check(self.lib.fvta_attn_shared_fwd(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)), ptr(qmask),
+                                            ptr(album), ptr(W), ptr(b), ptr(h_a), ptr(a_logits), ptr(self.work),
+                                            stream_ptr()), "fvta_attn_shared_fwd")
+        return h_a, a_logits
+
+
 def linear_fwd(x, W, b, y, M, din, dout, add_tanh=False, blk=None):
     """y [M,dout] = x [M,din] W [din,dout] + b (+ tanh); blk = (rows_per_blk, blk_stride): x rows in blocks"""
     rpb, bs = blk if blk else (M, 0)

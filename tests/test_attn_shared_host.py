@@ -1,0 +1,141 @@
+"""CPU-side checks of the shared-context focal attention (fvta_attn_shared_*): header and binding, descriptor size, the
+size query and its refusals, the host-only plan, argument errors as status codes, ops.check_album_index, and the two fp64
+references of tests/_attn_shared_ref.py against each other on every shape the GPU tests use.  No GPU."""
+import ctypes
+import os
+import re
+
+import pytest
+import torch
+
+from tests import _attn_shared_ref as R
+from fvta_memexqa_amd import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMS = ("fvta_attn_shared_workspace_bytes", "fvta_attn_shared_plan", "fvta_attn_shared_fwd")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__ as g
+        g.build()
+    return _lib.load()
+
+
+def _err(lib):
+    return lib.fvta_last_error()
+
+
+def test_header_and_binding_agree():
+    src = open(os.path.join(ROOT, "include", "fvta_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    declared = set(re.findall(r"\b(fvta_[a-z0-9_]+)\s*\(", src))
+    for s in SYMS:
+        assert s in declared and s in _lib.exported_symbols(), s
+    assert "fvta_attn_shared_desc" in src
+    res, args = _lib._SIGS["fvta_attn_shared_fwd"]
+    assert res is ctypes.c_int and len(args) == 12             # the descriptor, 10 pointers, the stream
+
+
+def test_descriptor_size(lib):
+    assert lib.fvta_abi_struct_bytes(12) == ctypes.sizeof(_lib.AttnSharedDesc) == 32
+    for s in SYMS:
+        assert hasattr(lib, s)
+
+
+def test_workspace_query_and_refusals(lib):
+    ok = _lib.AttnSharedDesc(8, 64, 6, 1200, 30, 1024, 2, 0)
+    nb = lib.fvta_attn_shared_workspace_bytes(ctypes.byref(ok))
+    assert nb > 64 * 6 * 1200 * 4                               # at least the max-pooled logits
+    assert nb < 8 * 64 * 6 * 1200 * 1024 * 4 // 8               # and nowhere near an expanded [NQ,K,T,w] tensor
+    for bad in (_lib.AttnSharedDesc(8, 64, 6, 1200, 30, 1000, 2, 0), _lib.AttnSharedDesc(8, 64, 6, 1200, 65, 1024, 2, 0)):
+        assert lib.fvta_attn_shared_workspace_bytes(ctypes.byref(bad)) == 0
+        assert b"unsupported" in _err(lib)
+    bad5 = _lib.AttnSharedDesc(8, 64, 6, 1200, 30, 1024, 5, 0)
+    assert lib.fvta_attn_shared_workspace_bytes(ctypes.byref(bad5)) == 0
+    assert b"similarity matrix not implemented" in _err(lib)
+    for zero in (_lib.AttnSharedDesc(0, 64, 6, 1200, 30, 1024, 2, 0), _lib.AttnSharedDesc(8, 0, 6, 1200, 30, 1024, 2, 0),
+                 _lib.AttnSharedDesc(8, 64, 6, -3, 30, 1024, 2, 0)):
+        assert lib.fvta_attn_shared_workspace_bytes(ctypes.byref(zero)) == 0 and b"bad A/NQ" in _err(lib)
+    assert lib.fvta_attn_shared_workspace_bytes(None) == 0
+    # every supported width and both column regimes answer; A > NQ and NQ > A alike
+    for w in (64, 128, 256, 512, 1024, 2048):
+        for JQ in (1, 32, 33, 64):
+            for A, NQ in ((1, 1), (100, 3), (3, 100)):
+                assert lib.fvta_attn_shared_workspace_bytes(ctypes.byref(_lib.AttnSharedDesc(A, NQ, 2, 70, JQ, w, 1, 0))) > 0
+
+
+def test_plan_answers_on_the_host(lib):
+    out = (ctypes.c_int32 * 4)()
+    d30 = _lib.AttnSharedDesc(8, 64, 6, 1200, 30, 1024, 2, 0)
+    assert lib.fvta_attn_shared_plan(ctypes.byref(d30), out) == 0
+    G, rows, tsplit, zero = (int(v) for v in out)
+    assert G >= 8 and rows >= 1 and tsplit >= 1 and zero == 0
+    assert G * 32 <= 256 or G * 30 <= 256                       # the group's columns fit the product's N side
+    d60 = _lib.AttnSharedDesc(8, 64, 6, 1200, 60, 1024, 2, 0)
+    assert lib.fvta_attn_shared_plan(ctypes.byref(d60), out) == 0 and out[0] >= 4
+    # the T splits depend on the descriptor only: the same answer twice, and never more splits than rows
+    again = (ctypes.c_int32 * 4)()
+    assert lib.fvta_attn_shared_plan(ctypes.byref(d60), again) == 0 and tuple(again) == tuple(out)
+    d1 = _lib.AttnSharedDesc(1, 1, 1, 1, 1, 64, 1, 0)
+    assert lib.fvta_attn_shared_plan(ctypes.byref(d1), out) == 0 and out[2] == 1
+    assert lib.fvta_attn_shared_plan(ctypes.byref(d30), None) == -1 and b"null pointer" in _err(lib)
+    bad = _lib.AttnSharedDesc(8, 64, 6, 1200, 30, 1000, 2, 0)
+    assert lib.fvta_attn_shared_plan(ctypes.byref(bad), out) == -3 and b"unsupported" in _err(lib)
+
+
+def test_forward_refuses_null_pointers(lib):
+    ok = _lib.AttnSharedDesc(2, 3, 2, 10, 5, 64, 2, 0)
+    st = lib.fvta_attn_shared_fwd(ctypes.byref(ok), None, None, None, None, None, None, None, None, None, None, None)
+    assert st == -1 and b"null pointer" in _err(lib)
+    assert lib.fvta_attn_shared_fwd(None, None, None, None, None, None, None, None, None, None, None, None) == -1
+    bad = _lib.AttnSharedDesc(2, 3, 2, 10, 65, 64, 2, 0)
+    st = lib.fvta_attn_shared_fwd(ctypes.byref(bad), None, None, None, None, None, None, None, None, None, None, None)
+    assert st == -3 and b"unsupported" in _err(lib)
+
+
+def test_check_album_index():
+    from fvta_memexqa_amd import ops
+    idx = torch.tensor([3, 0, 3, 1, 2, 2, 0, 3])
+    out = ops.check_album_index(idx, 4)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.tolist() == idx.tolist()
+    assert ops.check_album_index(torch.tensor([0, 0], dtype=torch.int32), 1).tolist() == [0, 0]
+    assert ops.check_album_index([1, 0], 2).tolist() == [1, 0]
+    for bad in (torch.tensor([0, -1]), torch.tensor([0, 4]), torch.tensor([0.0, 1.0]), torch.tensor([[0, 1]])):
+        with pytest.raises(ValueError):
+            ops.check_album_index(bad, 4)
+
+
+@pytest.mark.parametrize("name,simi,tanh,masked", R.CASES, ids=R.CASE_IDS)
+def test_the_two_references_agree(lib, name, simi, tanh, masked):
+    c = R.build_case(name, simi, masked)
+    ha1, a1 = R.reference(c, tanh)
+    ha2, a2 = R.grouped(c, tanh)
+    assert tuple(ha1.shape) == (c["NQ"], c["w"]) and tuple(a1.shape) == (c["NQ"], c["K"], c["T"], c["JQ"])
+    assert torch.allclose(ha1, ha2, rtol=0, atol=1e-10), float((ha1 - ha2).abs().max())
+    live = a1 > -1e29                                            # masked logits are -1e30 in both, exactly
+    assert torch.equal(live, a2 > -1e29)
+    assert torch.allclose(a1[live], a2[live], rtol=0, atol=1e-10)
+    assert torch.equal(a1[~live], a2[~live])
+
+
+def test_case_recipe_covers_the_edges(lib):
+    """the masked `mix` case holds what the GPU tests rely on: a fully masked (album, k), a single-row (album, k), a fully
+    masked question, an album without a question, group sizes 1, G, G+1, 2G+1, a shuffled index"""
+    c = R.build_case("mix", 1, True)
+    G, _ = R.host_plan(c["JQ"], c["w"])
+    cnt = torch.bincount(c["album"], minlength=c["A"]).tolist()
+    assert sorted(cnt) == sorted([0, 1, G, G + 1, 2 * G + 1]) and cnt[0] > 0
+    assert c["album"].tolist() != sorted(c["album"].tolist())
+    assert not c["hm"][0, 0].any() and int(c["hm"][0, 1].sum()) == 1 and not c["qm"][-1].any() and c["qm"][:-1, 0].all()
+
+
+def test_end_to_end_seed_keeps_every_answer_clear():
+    """the tiny end-to-end graph's seed: every question's top two probabilities differ by more than the margin in fp64, so
+    the GPU test's argmax comparison excludes nothing"""
+    c = R.e2e_case()
+    logits, yp = R.e2e_reference(c)
+    assert tuple(yp.shape) == (c["NQ"], c["C"])
+    assert bool((R.top2_margin(yp) > c["margin"]).all()), R.top2_margin(yp)
+    assert len(set(c["album"].tolist())) == c["A"]

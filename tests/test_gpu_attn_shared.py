@@ -1,0 +1,199 @@
+"""GPU parity of the shared-context focal attention (fvta_attn_shared_fwd, ops.SharedFocalAttention,
+functional.attention_3d_shared_raw, nn.FocalAttention3D.forward_shared, nn.AlbumMemory) against the fp64 reference of
+tests/_attn_shared_ref.py, at the tolerances of tests/test_gpu_forward.py (BASELINE.json north_star: 1e-4 relative).
+
+The shapes (tests/_attn_shared_ref.py SPECS) are the smallest that turn every loop over: groups of 1, G, G+1 and 2G+1
+questions and an album without one, row tiles at T = 1, 7, R-1, R, R+1, 333, question columns at JQ = 1, 30, 32, 33, 64,
+every width from 64 to 2048, A = NQ = 1, K = 6; G and R are read from fvta_attn_shared_plan."""
+import numpy as np
+import pytest
+import torch
+
+from tests import _attn_shared_ref as R
+
+pytestmark = pytest.mark.gpu
+
+_REF = {}
+
+
+def _close(a, b, rtol=1e-4, atol=1e-5, msg=""):
+    a = a.detach().cpu().double().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, np.float64)
+    b = b.detach().cpu().double().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float64)
+    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
+
+
+def _cu(t):
+    return None if t is None else t.cuda().contiguous()
+
+
+def _case(name, simi, tanh, masked):
+    """the case and its fp64 reference, computed once per session and never written to"""
+    key = (name, simi, tanh, masked)
+    if key not in _REF:
+        c = R.build_case(name, simi, masked)
+        _REF[key] = (c, R.reference(c, tanh))
+    return _REF[key]
+
+
+def _run(c, tanh, want_logits=True, rows=None):
+    """ops.SharedFocalAttention on case c; rows: a subset of the questions (an index list), else all of them"""
+    from fvta_memexqa_amd import ops
+    q, qm, al = c["q"], c["qm"], c["album"]
+    if rows is not None:
+        q, al = q[rows], al[rows]
+        qm = None if qm is None else qm[rows]
+    op = ops.SharedFocalAttention(c["A"], q.shape[0], c["K"], c["T"], c["JQ"], c["w"], c["simi"], tanh)
+    idx = ops.check_album_index(al, c["A"])
+    return op.forward(_cu(c["h"]), _cu(ops.as_mask_u8(c["hm"])), _cu(q), _cu(ops.as_mask_u8(qm)), idx.cuda(),
+                      None if c["W"] is None else _cu(c["W"].reshape(-1)), _cu(c["b"]), want_logits=want_logits)
+
+
+def _expanded(c, tanh, want_logits=False):
+    """today's route: index_select of the rows to [NQ,...], then the per-question kernel"""
+    from fvta_memexqa_amd import ops
+    al = c["album"].cuda()
+    h = _cu(c["h"]).index_select(0, al)
+    hm = None if c["hm"] is None else _cu(ops.as_mask_u8(c["hm"])).index_select(0, al)
+    op = ops.FocalAttention(c["NQ"], c["K"], c["T"], c["JQ"], c["w"], c["simi"], tanh)
+    return op.forward(h, _cu(c["q"]), hm, _cu(ops.as_mask_u8(c["qm"])), None if c["W"] is None else _cu(c["W"].reshape(-1)),
+                      _cu(c["b"]), want_logits=want_logits)
+
+
+@pytest.mark.parametrize("name,simi,tanh,masked", R.CASES, ids=R.CASE_IDS)
+def test_matches_the_fp64_reference(name, simi, tanh, masked):
+    c, (ref_ha, ref_a) = _case(name, simi, tanh, masked)
+    ha, a = _run(c, tanh)
+    _close(ha, ref_ha, msg="h_a")
+    _close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
+
+
+def test_plan_is_what_the_shapes_assume():
+    from fvta_memexqa_amd import ops
+    p = ops.SharedFocalAttention(5, 40, 2, 50, 10, 64, 1, False).plan()
+    assert p["G"] >= 8 and (p["G"], p["rows"]) == R.host_plan(10, 64)
+    assert ops.SharedFocalAttention(2, 5, 2, 40, 33, 128, 1, False).plan()["G"] >= 4
+
+
+@pytest.mark.parametrize("name,simi,tanh,masked", [("mix", 2, True, True), ("rows5", 2, True, True)])
+def test_same_result_as_the_per_question_kernel(name, simi, tanh, masked, attn_select):
+    c, _ = _case(name, simi, tanh, masked)
+    attn_select.exact()
+    ref_ha, _ = _expanded(c, tanh)
+    ha, _ = _run(c, tanh, want_logits=False)
+    _close(ha, ref_ha, rtol=2e-5, atol=2e-6, msg="h_a against the per-question exact kernel")
+
+
+def test_a_question_does_not_depend_on_its_company():
+    c, _ = _case("mix", 3, True, True)
+    G, _ = R.host_plan(c["JQ"], c["w"])
+    big = int(torch.bincount(c["album"], minlength=c["A"]).argmax())          # the album with 2G+1 questions
+    members = torch.nonzero(c["album"] == big).reshape(-1)
+    assert members.numel() == 2 * G + 1
+    ha_all, a_all = _run(c, True)
+    again_ha, again_a = _run(c, True)
+    assert torch.equal(ha_all, again_ha) and torch.equal(a_all, again_a)       # the same call twice: the same bits
+    i = int(members[G])
+    ha_one, a_one = _run(c, True, rows=[i])
+    _close(ha_one[0], ha_all[i], rtol=2e-5, atol=2e-6, msg="alone against in company")
+    _close(a_one[0], a_all[i], rtol=2e-5, atol=2e-6)
+    ha_nol, none = _run(c, True, want_logits=False)
+    assert none is None and torch.equal(ha_nol, ha_all)                        # want_logits changes no bit of h_a
+
+
+def test_functional_and_nn_surface():
+    from fvta_memexqa_amd import functional as Fn, nn
+    c, (ref_ha, ref_a) = _case("rows4", 1, False, True)                        # w = 256, simiMatrix 1, no tanh
+    ha_ops, a_ops = _run(c, False)
+    h, q, W, b = _cu(c["h"]), _cu(c["q"]), _cu(c["W"]), _cu(c["b"])
+    hm, qm = _cu(c["hm"]), _cu(c["qm"])
+    with torch.no_grad():
+        ha, a = Fn.attention_3d_shared_raw(h, q, c["album"], W, b, hm, qm, simiMatrix=1, add_tanh=False)
+    assert torch.equal(ha, ha_ops) and torch.equal(a, a_ops)
+    qg = q.clone().requires_grad_()
+    with pytest.raises(RuntimeError, match="attention_3d"):
+        Fn.attention_3d_shared_raw(h, qg, c["album"], W, b, hm, qm, simiMatrix=1)
+    with torch.no_grad():                                                      # gradient mode off: allowed, nothing to detach
+        ha2, _ = Fn.attention_3d_shared_raw(h, qg, c["album"], W, b, hm, qm, simiMatrix=1)
+    assert torch.equal(ha2, ha_ops)
+    with pytest.raises(ValueError):
+        Fn.attention_3d_shared_raw(h, q, c["album"] + c["A"], W, b, hm, qm, simiMatrix=1)
+    att = nn.FocalAttention3D(c["w"], simiMatrix=1, add_tanh=False)
+    with torch.no_grad():
+        att.p("att_logits/W").copy_(W)
+        att.p("att_logits/b").copy_(b)
+        al = c["album"].cuda()
+        ha_f, a_f = att.forward(h.index_select(0, al), q, hm.index_select(0, al), qm)
+        ha_s, a_s = att.forward_shared(h, q, c["album"], hm, qm)
+    _close(ha_s, ha_f, msg="forward_shared against forward")
+    _close(a_s, a_f, rtol=1e-4, atol=2e-5)
+    _close(ha_s, ref_ha)
+    with pytest.raises(RuntimeError):                                          # the parameters require grad
+        att.forward_shared(h, q, c["album"], hm, qm)
+
+
+def test_album_memory_validates_before_any_library_call(monkeypatch):
+    from fvta_memexqa_amd import nn, ops
+    c, _ = _case("single", 1, False, True)
+    mem = nn.AlbumMemory(_cu(c["h"]), _cu(c["hm"]))
+    assert len(mem) == c["A"] and mem.hall.is_contiguous() and mem.hall.dtype == torch.float32
+    assert not isinstance(mem, torch.nn.Module)                                # no parameters, no encoder
+    att = nn.FocalAttention3D(c["w"], simiMatrix=1)
+
+    def boom(*a, **k):
+        raise AssertionError("the library was reached with an invalid index")
+    monkeypatch.setattr(ops.SharedFocalAttention, "forward", boom)
+    monkeypatch.setattr(ops.SharedFocalAttention, "__init__", boom)
+    with torch.no_grad():
+        for bad in (torch.tensor([c["A"]]), torch.tensor([-1]), torch.tensor([0.0]), torch.tensor([[0]])):
+            with pytest.raises(ValueError):
+                mem.attend(att, _cu(c["q"]), _cu(c["qm"]), bad)
+        with pytest.raises(ValueError):
+            mem.attend(att, _cu(c["q"]), _cu(c["qm"]), torch.tensor([0, 0]))   # two indices for one question
+
+
+def test_end_to_end_many_questions_over_encoded_albums():
+    """A = 2 albums encoded ONCE (two bi-LSTM streams -> context tensor), NQ = 5 questions through AlbumMemory,
+    QuestionAttention and the scorer, against the per-question graph on the expanded context and the fp64 oracle."""
+    from fvta_memexqa_amd import functional as Fn, nn, ops
+    c = R.e2e_case()
+    ref_logits, ref_yp = R.e2e_reference(c)
+    margin = R.top2_margin(ref_yp)
+    assert bool((margin > c["margin"]).all()), margin                          # the argmax check below excludes nothing
+    A, M, w = c["A"], c["M"], 2 * c["hidden"]
+    with torch.no_grad():
+        streams, masks = [], []
+        for x, ln, k, b in zip(c["x"], c["lens"], c["lstm_k"], c["lstm_b"]):
+            enc = nn.BiLSTMEncoder(c["din"], c["hidden"], share_fw_bw=True)
+            enc.p("fw/basic_lstm_cell/kernel").copy_(k)
+            enc.p("fw/basic_lstm_cell/bias").copy_(b)
+            out, _ = enc(x.cuda(), ln.cuda())
+            streams.append(out.reshape(A, M, x.shape[1], w))
+            masks.append((torch.arange(x.shape[1])[None, :] < ln[:, None]).reshape(A, M, -1).cuda())
+        hall, hall_mask = Fn.context_tensor(streams, masks)
+        att = nn.FocalAttention3D(w, simiMatrix=c["simi"], add_tanh=c["tanh"])
+        qatt = nn.QuestionAttention(w, simiMatrix=c["simi"], add_tanh=c["tanh"])
+        for mod, W, b in ((att, c["att_W"], c["att_b"]), (qatt, c["qatt_W"], c["qatt_b"])):
+            mod.p("att_logits/W").copy_(W)
+            mod.p("att_logits/b").copy_(b)
+        hq = c["hq"].cuda()
+        qmask = (torch.arange(c["JQ"])[None, :] < c["qlen"][:, None]).cuda()
+        ones = torch.ones(c["NQ"], 1, dtype=torch.bool, device="cuda")
+        gch, oW, ob = c["gch"].cuda(), c["out_W"].reshape(-1).cuda(), c["out_b"].cuda()
+
+        def head(g1):
+            gq, _ = qatt(hq, g1[:, None, :].contiguous(), qmask, ones)
+            logits, yp, _ = ops.scorer_ce_fwd(gq.contiguous(), g1.contiguous(), gch, oW, ob)
+            return logits, yp
+
+        mem = nn.AlbumMemory(hall, hall_mask)
+        assert len(mem) == A
+        g1_shared, _ = mem.attend(att, hq, qmask, c["album"])
+        al = c["album"].cuda()
+        g1_each, _ = att(hall.index_select(0, al), hq, hall_mask.index_select(0, al), qmask)
+        logits_s, yp_s = head(g1_shared)
+        logits_e, yp_e = head(g1_each)
+    _close(logits_s, logits_e, msg="shared against per-question")
+    _close(logits_s, ref_logits, msg="shared against the fp64 oracle")
+    clear = margin > c["margin"]
+    assert torch.equal(yp_s.argmax(-1).cpu()[clear], ref_yp.argmax(-1)[clear])
+    assert torch.equal(yp_s.argmax(-1), yp_e.argmax(-1))

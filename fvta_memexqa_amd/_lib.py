@@ -131,6 +131,11 @@ _SIGS = {
     "fvta_attn_shared_workspace_bytes": (c_size_t, [POINTER(AttnSharedDesc)]),
     "fvta_attn_shared_plan": (c_int, [POINTER(AttnSharedDesc), POINTER(c_int32)]),
     "fvta_attn_shared_fwd": (c_int, [POINTER(AttnSharedDesc), P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_attn_shared_saved_bytes": (c_size_t, [POINTER(AttnSharedDesc)]),
+    "fvta_attn_shared_bwd_workspace_bytes": (c_size_t, [POINTER(AttnSharedDesc)]),
+    "fvta_attn_shared_bwd_plan": (c_int, [POINTER(AttnSharedDesc), POINTER(c_int32)]),
+    "fvta_attn_shared_fwd_train": (c_int, [POINTER(AttnSharedDesc), P, P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_attn_shared_bwd": (c_int, [POINTER(AttnSharedDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_workspace_bytes": (c_size_t, [POINTER(TimewarpDesc)]),
     "fvta_timewarp_fwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_bwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),

@@ -199,6 +199,46 @@ def focal_attention(hinfo, hq, W, b, hmask=None, qmask=None, simi=1, add_tanh=Fa
     return _FocalAttention.apply(hinfo, hq, W, b, tscale, hmask, qmask, int(simi), bool(add_tanh), int(feat_order))
 
 
+class _SharedFocalAttention(torch.autograd.Function):
+    """(hinfo [A,K,T,w], hq [NQ,JQ,w], album int32 [NQ] on the device, W [F*w], b [1]; masks u8 | None) ->
+    (h_a [NQ,w], a_logits [NQ,K,T,JQ]): question i over album[i]'s rows, the rows held once (fvta_attn_shared_fwd_train /
+    fvta_attn_shared_bwd; simiMatrix 1-3).  a_logits is not differentiable here.  Each call owns its handle."""
+
+    @staticmethod
+    def forward(ctx, hinfo, hq, album, W, b, hmask, qmask, simi, add_tanh):
+        A, K, T, w = hinfo.shape
+        op = ops.SharedFocalAttention(A, hq.shape[0], K, T, hq.shape[1], w, simi, add_tanh)
+        h_a, a = op.forward_train(hinfo, hmask, hq, qmask, album, W, b, want_logits=True)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(a)
+        ctx.op = op
+        ctx.aux = (album, hmask, qmask)
+        ctx.save_for_backward(hinfo, hq, W, b)
+        return h_a, a
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ha, g_a):
+        if g_ha is None:
+            return (None,) * 9
+        hinfo, hq, W, b = ctx.saved_tensors
+        album, hmask, qmask = ctx.aux
+        dh, dq = torch.empty_like(hinfo), torch.empty_like(hq)
+        dW, db = torch.zeros_like(W), torch.zeros_like(b)
+        ctx.op.backward(hinfo, hmask, hq, qmask, album, W, b, _c(g_ha), dh, dq, dW, db)
+        need = ctx.needs_input_grad
+        return (dh if need[0] else None, dq if need[1] else None, None, dW if need[3] else None, db if need[4] else None,
+                None, None, None, None)
+
+
+def shared_focal_attention(hinfo, hq, album, W, b, hmask=None, qmask=None, simi=1, add_tanh=False):
+    """album: int32 [NQ] on the device, validated by the caller (ops.check_album_index)"""
+    if int(simi) == 4:
+        raise NotImplementedError("shared_focal_attention: simiMatrix 4 has no shared-context backward; the per-question "
+                                  "focal_attention on gathered rows covers it")
+    return _SharedFocalAttention.apply(hinfo, hq, album, W, b, hmask, qmask, int(simi), bool(add_tanh))
+
+
 class _KeepRank1(torch.autograd.Function):
     """attention_keeprank1 (model.py:247-314): (hinfo [N,M,V,w], hq [N,JQ,w], W [F*w], b [1]; masks u8 | None) ->
     (u [N,M,w], a_logits [N,M,V,JQ] | None).  Forward: fvta_attn_fwd at K = M in model.py's feature order, then the

@@ -13,6 +13,7 @@
 // (TF splits exact ties) and fully masked (n,k) rows pass no gradient into the
 // masked logits.
 #include "attn_common.h"
+#include "attn_bwd_params.h"
 #include "fvta_prof.h"
 
 #ifndef FVTA_ATTN_BWD_NT_DEFAULT
@@ -719,21 +720,7 @@ __global__ __launch_bounds__(256) void attn_bwd_params_kernel(AttnShape s, AttnB
   if (grp == 0 && c < w) {
 #pragma unroll
     for (int k = 0; k < VEC_COUNT; ++k) v[k] = (s_p[0][k][cl] + s_p[1][k][cl]) + (s_p[2][k][cl] + s_p[3][k][cl]);
-    const float dU = v[VEC_U], dRh = v[VEC_RH], dR2 = v[VEC_R2], dCq = v[VEC_CQ], dC2 = v[VEC_C2];
-    if (s.simi == 1) {
-      dW[c] += dRh;
-      dW[w + c] += dCq;
-      dW[2 * w + c] += dU;
-    } else if (s.simi == 2) {
-      const float d1 = dU, d2 = -2.f * dU + dR2 + dC2;
-      dW[c] += s.feat_order == 0 ? d1 : d2;
-      dW[w + c] += s.feat_order == 0 ? d2 : d1;
-    } else if (s.simi == 3) {
-      dW[c] += dRh;
-      dW[w + c] += dCq;
-      dW[2 * w + c] += -2.f * dU + dR2 + dC2;
-      dW[3 * w + c] += dU;
-    }
+    attn_bwd_add_dW(s.simi, s.feat_order, w, c, v[VEC_U], v[VEC_RH], v[VEC_R2], v[VEC_CQ], v[VEC_C2], dW);
   }
 }
 

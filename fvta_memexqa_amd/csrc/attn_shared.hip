@@ -2,7 +2,9 @@
 // context rows once, question i reads album[i]'s.  Per question the result is fvta_attn_fwd's on the pair
 // (hinfo[album[i]], hq[i]) -- model_v2.py:210-298 -- but a row is fetched once per GROUP of up to G questions of the same
 // album instead of once per question, and the logits of a group are one [rows, w] x [w, G JP] product on the fp32 matrix
-// pipe (gemm_f32.h: v_mfma_f32_32x32x2_f32, exact fp32).  Forward only: no `saved`, no time warp, no shadow rows.
+// pipe (gemm_f32.h: v_mfma_f32_32x32x2_f32, exact fp32).  No time warp, no shadow rows.  fvta_attn_shared_fwd keeps nothing
+// for a backward; fvta_attn_shared_fwd_train runs the same kernels -- the same bits -- with the ordered plan (3) and the
+// arg-max (4) compiled in, and leaves what attn_shared_bwd.hip reads in the caller-held `saved` (attn_shared_common.h).
 //
 // Bilinear form (attn_common.h): x[t,(g,j)] = rs[t] sum_c h[t,c] Qs[g,j,c] + (Rh.h[t] + R2.h[t]^2) + ct[g,j].
 // Launches, all on the caller's stream, none waits for the host:
@@ -23,73 +25,18 @@
 // Determinism: no floating-point atomics.  The split of T depends on the descriptor only; a question's numbers do not
 // depend on which group, slot or wave it lands in (every column of the product is its own k-ordered fmaf chain, every
 // question has its own accumulators), so the integer atomics that place the questions in `order` cannot change a bit.
-#include "attn_common.h"
+// The backward DOES sum over an album's questions in `order`: the training plan fills it by ascending question index from a
+// single wave (attn_shared_plan_kernel<true>), a function of `album` alone.
+#include "attn_shared_common.h"
 #include "gemm_f32.h"
 
 namespace fvta {
 
-constexpr int SH_BN = 256;   // question columns of a group: G * JP
-constexpr int SH_NT = 256;
-constexpr int SH_CH = 64;    // rows whose softmax weights the weighted-sum kernel stages at a time
-constexpr int SH_PLAN_NT = 1024;
 // 64 rows x 256 columns, a wave 64 x 64: 200 registers, two workgroups per CU.  (MmaF32<2, 2, 2, 4>, 128 rows and half the
 // question staging per row, was measured: 331 registers, one wave per SIMD, and no faster at 8 questions per album, 20 %
 // slower at one -- DESIGN.md 4.1)
 typedef MmaF32<1, 4, 2, 2> ShMma;
-constexpr int SH_R = ShMma::BM;      // rows of a tile of the logits kernel
-static_assert(ShMma::BN == SH_BN && ShMma::NT == SH_NT && ShMma::TN % 2 == 0, "tile shape");
-
-struct ShShape {
-  int A, NQ, K, T, JQ, w, simi, add_tanh, use_mask;
-  int JP, G;      // padded question length (32 / 64), questions per group (8 / 4)
-  int ntile;      // row tiles of a (k): ceil(T / SH_R)
-  int S, rps;     // T splits of the weighted sum, rows per split
-  int ngmax;      // upper bound of the number of groups: floor(NQ / G) + min(A, NQ), at most NQ
-};
-
-static ShShape sh_shape(const fvta_attn_shared_desc* d) {
-  ShShape s;
-  s.A = d->A, s.NQ = d->NQ, s.K = d->K, s.T = d->T, s.JQ = d->JQ, s.w = d->w, s.simi = d->simi, s.add_tanh = d->add_tanh;
-  s.use_mask = 0;
-  s.JP = d->JQ <= 32 ? 32 : 64;
-  s.G = SH_BN / s.JP;
-  s.ntile = (d->T + SH_R - 1) / SH_R;
-  const int64_t ng = (int64_t)d->NQ / s.G + (d->A < d->NQ ? d->A : d->NQ);
-  s.ngmax = (int)(ng < d->NQ ? ng : d->NQ);
-  // about 1024 workgroups of the weighted sum (4 per CU), a split not shorter than one chunk
-  int64_t S = (1024 + (int64_t)s.ngmax * d->K - 1) / ((int64_t)s.ngmax * d->K);
-  const int maxs = (d->T + SH_CH - 1) / SH_CH;
-  if (S > maxs) S = maxs;
-  if (S < 1) S = 1;
-  s.rps = (int)((d->T + S - 1) / S);
-  s.S = (d->T + s.rps - 1) / s.rps;
-  return s;
-}
-
-struct ShWork {
-  float *vecs, *Qs, *ct, *amax, *M, *coef, *part;
-  int *acnt, *astart, *agrp, *order, *qslot, *ngroups;
-  int4* grp;
-  size_t bytes;
-  ShWork(const ShShape& s, void* p) {
-    FvtaCarver c(p);
-    vecs = c.take<float>((size_t)VEC_COUNT * s.w);
-    Qs = c.take<float>((size_t)s.NQ * s.JP * s.w);
-    ct = c.take<float>((size_t)s.NQ * s.JP);
-    amax = c.take<float>((size_t)s.NQ * s.K * s.T);
-    M = c.take<float>((size_t)s.NQ * s.K);
-    coef = c.take<float>((size_t)s.NQ * s.K);
-    part = c.take<float>((size_t)s.ngmax * s.K * s.S * s.G * s.w);
-    acnt = c.take<int>((size_t)s.A);
-    astart = c.take<int>((size_t)s.A);
-    agrp = c.take<int>((size_t)s.A);
-    order = c.take<int>((size_t)s.NQ);
-    qslot = c.take<int>((size_t)s.NQ);
-    ngroups = c.take<int>(1);
-    grp = c.take<int4>((size_t)s.ngmax);
-    bytes = c.off;
-  }
-};
+static_assert(ShMma::BM == SH_R && ShMma::BN == SH_BN && ShMma::NT == SH_NT && ShMma::TN % 2 == 0, "tile shape");
 
 // the per-channel vectors of att_logits/W in attn_common.h's layout: attn_fwd.hip's kernel (feat_order 0 = model_v2.py's)
 __global__ void attn_vecs_kernel(const float* __restrict__ W, int w, int simi, int feat_order, float* __restrict__ vecs);
@@ -128,6 +75,14 @@ __device__ __forceinline__ int sh_album(const int* album, int i, int A) {
   const int a = album[i];
   return a < 0 ? 0 : (a >= A ? A - 1 : a);
 }
+// ORDERED (the training plan): the questions of an album stand in `order` by ascending question index, so that the
+// backward's sum over an album's questions has ONE order, a function of `album` alone.  The cursor atomics below place a
+// question wherever its atomic happens to arrive; here wave 0 alone walks the questions 64 at a time in ascending order,
+// and per distinct album of a batch ONE lane advances that album's cursor by the number of the batch's questions about
+// it, which take their places by lane rank.  Every cursor update is issued by a single wave in program order, one after
+// the other: nothing depends on the order in which atomics of different waves arrive.  (An integer atomic is still the
+// instruction, because it reads the cursor at L2, past this wave's own vector cache.)
+template <bool ORDERED>
 __global__ __launch_bounds__(SH_PLAN_NT) void attn_shared_plan_kernel(ShShape s, ShWork wk, const int* __restrict__ album) {
   __shared__ int cell_c[SH_PLAN_NT], cell_g[SH_PLAN_NT];
   const int tid = threadIdx.x, A = s.A, NQ = s.NQ, G = s.G;
@@ -166,16 +121,41 @@ __global__ __launch_bounds__(SH_PLAN_NT) void attn_shared_plan_kernel(ShShape s,
   }
   if (tid == SH_PLAN_NT - 1) *wk.ngroups = min(cell_g[tid], s.ngmax);
   __syncthreads();
-  for (int i = tid; i < NQ; i += SH_PLAN_NT) {
-    const int a = sh_album(album, i, A);
-    const int off = atomicAdd(&wk.acnt[a], 1);
-    wk.order[wk.astart[a] + off] = i;
-    wk.qslot[i] = (wk.agrp[a] + off / G) * G + off % G;
+  if constexpr (ORDERED) {
+    if (tid >= 64) return;
+    for (int base = 0; base < NQ; base += 64) {
+      const int i = base + tid;
+      const bool ok = i < NQ;
+      const int a = ok ? sh_album(album, i, A) : -1;
+      unsigned long long todo = __ballot(ok);
+      while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const int av = __shfl(a, leader, 64);
+        const unsigned long long same = __ballot(ok && a == av);
+        int first = 0;
+        if (tid == leader) first = atomicAdd(&wk.acnt[av], __popcll(same));
+        first = __shfl(first, leader, 64);
+        if (ok && a == av) {
+          const int off = first + __popcll(same & ((1ull << tid) - 1ull));
+          wk.order[wk.astart[a] + off] = i;
+          wk.qslot[i] = (wk.agrp[a] + off / G) * G + off % G;
+        }
+        todo &= ~same;
+      }
+    }
+  } else {
+    for (int i = tid; i < NQ; i += SH_PLAN_NT) {
+      const int a = sh_album(album, i, A);
+      const int off = atomicAdd(&wk.acnt[a], 1);
+      wk.order[wk.astart[a] + off] = i;
+      wk.qslot[i] = (wk.agrp[a] + off / G) * G + off % G;
+    }
   }
 }
 
 // ---- logits.  grid ngmax * K * ntile, 256 threads
-template <int JT>
+// TRAIN: also the FIRST arg-max j of every row's maximum -> jmax [NQ,K,T] (compile-time: the inference kernel is unchanged)
+template <int JT, bool TRAIN>
 __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, ShWork wk, const float* __restrict__ hinfo,
                                                                   const uint8_t* __restrict__ hmask,
                                                                   const uint8_t* __restrict__ qmask,
@@ -209,7 +189,11 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
   const int anyrow = __syncthreads_or(rowv ? 1 : 0);
   if (!anyrow) {  // every logit of the tile is masked: -1e30, whatever the rows hold
     const int rows = min(SH_R, T - t0);
-    for (int e = tid; e < cnt * rows; e += SH_NT) wk.amax[((size_t)s_q[e / rows] * K + k) * T + t0 + e % rows] = FVTA_NEG;
+    for (int e = tid; e < cnt * rows; e += SH_NT) {
+      const size_t at = ((size_t)s_q[e / rows] * K + k) * T + t0 + e % rows;
+      wk.amax[at] = FVTA_NEG;
+      if constexpr (TRAIN) wk.jmax[at] = 0;
+    }
     if (a_logits)
       for (int g = 0; g < cnt; ++g) {
         float* dst = a_logits + (((size_t)s_q[g] * K + k) * T + t0) * JQ;
@@ -282,6 +266,13 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
         for (int o = 16; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));  // over the 32 columns, rows stay apart
         const int t = t0 + mma.row_of(i, r);
         if (mma.l31 == r && q >= 0 && t < T) wk.amax[((size_t)q * K + k) * T + t] = m;
+        if constexpr (TRAIN) {  // columns of a lane: j = l31 (and 32 + l31); a dead column holds -inf and never equals m
+          int jm = mx[jn][r] == m ? mma.l31 : 255;
+          if (JT == 2 && jm == 255 && mx[jn + 1][r] == m) jm = 32 + mma.l31;
+#pragma unroll
+          for (int o = 16; o > 0; o >>= 1) jm = min(jm, __shfl_xor(jm, o, 64));
+          if (mma.l31 == r && q >= 0 && t < T) wk.jmax[((size_t)q * K + k) * T + t] = (uint8_t)min(jm, JQ - 1);
+        }
       }
     }
   }
@@ -328,6 +319,10 @@ __global__ __launch_bounds__(256) void attn_shared_softmax_kernel(ShShape s, ShW
     for (int k = 0; k < K; ++k) {
       wk.M[(size_t)q * K + k] = s_M[k];
       wk.coef[(size_t)q * K + k] = expf(s_M[k] - mx) / sum / s_L[k];
+      if (wk.L) {  // training: the two factors of coef, apart
+        wk.L[(size_t)q * K + k] = s_L[k];
+        wk.r[(size_t)q * K + k] = expf(s_M[k] - mx) / sum;
+      }
     }
   }
 }
@@ -399,13 +394,23 @@ __global__ __launch_bounds__(256) void attn_shared_merge_kernel(ShShape s, ShWor
   if (c >= s.w) return;
   const int slot = wk.qslot[q], grp = slot / s.G, g = slot % s.G;
   float v = 0.f;
-  for (int k = 0; k < s.K; ++k)
-    for (int sp = 0; sp < s.S; ++sp) v += wk.part[((((size_t)grp * s.K + k) * s.S + sp) * s.G + g) * s.w + c];
+  for (int k = 0; k < s.K; ++k) {
+    float vk = 0.f;  // training: r[k] u[k], beside h_a's own chain (whose order of sums stays what it is)
+    for (int sp = 0; sp < s.S; ++sp) {
+      const float p = wk.part[((((size_t)grp * s.K + k) * s.S + sp) * s.G + g) * s.w + c];
+      v += p;
+      vk += p;
+    }
+    if (wk.u) {  // r = 0 (underflow): u[k] reaches nothing in the backward, every use carries a factor r
+      const float r = wk.r[(size_t)q * s.K + k];
+      wk.u[((size_t)q * s.K + k) * s.w + c] = r > 0.f ? vk / r : 0.f;
+    }
+  }
   h_a[(size_t)q * s.w + c] = v;
 }
 
 // 0: fine, else the status with the message set
-static int sh_check(const fvta_attn_shared_desc* d, const char* who) {
+int fvta_attn_shared_check(const fvta_attn_shared_desc* d, const char* who) {
   FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
   FVTA_CHECK_ARG(d->A > 0 && d->NQ > 0 && d->K > 0 && d->T > 0 && d->JQ > 0 && d->w > 0, "%s: bad A/NQ/K/T/JQ/w (%d,%d,%d,%d,%d,%d)",
                  who, d->A, d->NQ, d->K, d->T, d->JQ, d->w);
@@ -447,12 +452,12 @@ static void sh_launch_wsum(const ShShape& s, const ShWork& wk, const float* hinf
 using namespace fvta;
 
 extern "C" size_t fvta_attn_shared_workspace_bytes(const fvta_attn_shared_desc* d) {
-  if (sh_check(d, "attn_shared_workspace_bytes") != FVTA_OK) return 0;
+  if (fvta_attn_shared_check(d, "attn_shared_workspace_bytes") != FVTA_OK) return 0;
   return ShWork(sh_shape(d), nullptr).bytes;
 }
 
 extern "C" int fvta_attn_shared_plan(const fvta_attn_shared_desc* d, int32_t out[4]) {
-  if (int e = sh_check(d, "attn_shared_plan")) return e;
+  if (int e = fvta_attn_shared_check(d, "attn_shared_plan")) return e;
   FVTA_CHECK_ARG(out != nullptr, "attn_shared_plan: null pointer");
   const ShShape s = sh_shape(d);
   out[0] = s.G;
@@ -462,30 +467,63 @@ extern "C" int fvta_attn_shared_plan(const fvta_attn_shared_desc* d, int32_t out
   return FVTA_OK;
 }
 
-extern "C" int fvta_attn_shared_fwd(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
-                                    const uint8_t* qmask, const int32_t* album, const float* W, const float* b, float* h_a,
-                                    float* a_logits, void* workspace, fvta_stream_t stream_) {
-  if (int e = sh_check(d, "attn_shared_fwd")) return e;
-  FVTA_CHECK_ARG(hinfo && hq && album && h_a && workspace, "attn_shared_fwd: null pointer");
-  FVTA_CHECK_ARG(d->simi == 4 || W, "attn_shared_fwd: simiMatrix %d needs att_logits/W", d->simi);
-  hipStream_t st = (hipStream_t)stream_;
-  ShShape s = sh_shape(d);
+// the seven launches; TRAIN: the ordered plan and the arg-max, wk carved from (saved, workspace)
+template <bool TRAIN>
+static int sh_forward(ShShape s, const ShWork& wk, const float* hinfo, const uint8_t* hmask, const float* hq, const uint8_t* qmask,
+                      const int32_t* album, const float* W, const float* b, float* h_a, float* a_logits, hipStream_t st) {
   s.use_mask = (hmask && qmask) ? 1 : 0;  // model_v2.py:233: the mask applies only when both are given
-  const ShWork wk(s, workspace);
   hipLaunchKernelGGL(attn_vecs_kernel, dim3((s.w + 255) / 256), dim3(256), 0, st, W, s.w, s.simi, 0, wk.vecs);
   hipLaunchKernelGGL(attn_shared_prep_q_kernel, dim3(s.NQ, s.JP / 4), dim3(256), 0, st, s, wk, hq, b);
-  hipLaunchKernelGGL(attn_shared_plan_kernel, dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)album);
+  hipLaunchKernelGGL(attn_shared_plan_kernel<TRAIN>, dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)album);
   const dim3 lgrid((unsigned)((int64_t)s.ngmax * s.K * s.ntile));
   if (s.JP == 32)
-    hipLaunchKernelGGL(attn_shared_logits_kernel<1>, lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits);
+    hipLaunchKernelGGL((attn_shared_logits_kernel<1, TRAIN>), lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits);
   else
-    hipLaunchKernelGGL(attn_shared_logits_kernel<2>, lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits);
+    hipLaunchKernelGGL((attn_shared_logits_kernel<2, TRAIN>), lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits);
   hipLaunchKernelGGL(attn_shared_softmax_kernel, dim3(s.NQ), dim3(256), 0, st, s, wk);
   if (s.G == 8)
     sh_launch_wsum<8>(s, wk, hinfo, st);
   else
     sh_launch_wsum<4>(s, wk, hinfo, st);
   hipLaunchKernelGGL(attn_shared_merge_kernel, dim3(s.NQ, (s.w + 255) / 256), dim3(256), 0, st, s, wk, h_a);
-  FVTA_CHECK_LAUNCH("attn_shared_fwd");
+  FVTA_CHECK_LAUNCH(TRAIN ? "attn_shared_fwd_train" : "attn_shared_fwd");
   return FVTA_OK;
+}
+
+extern "C" int fvta_attn_shared_fwd(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
+                                    const uint8_t* qmask, const int32_t* album, const float* W, const float* b, float* h_a,
+                                    float* a_logits, void* workspace, fvta_stream_t stream_) {
+  if (int e = fvta_attn_shared_check(d, "attn_shared_fwd")) return e;
+  FVTA_CHECK_ARG(hinfo && hq && album && h_a && workspace, "attn_shared_fwd: null pointer");
+  FVTA_CHECK_ARG(d->simi == 4 || W, "attn_shared_fwd: simiMatrix %d needs att_logits/W", d->simi);
+  const ShShape s = sh_shape(d);
+  return sh_forward<false>(s, ShWork(s, workspace), hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, (hipStream_t)stream_);
+}
+
+// ---- training.  The same kernels on the same numbers (h_a and a_logits are fvta_attn_shared_fwd's bits: the placement of
+// a question changes none, see the header), with what the backward (attn_shared_bwd.hip) reads left in `saved`.
+int fvta::fvta_attn_shared_check_train(const fvta_attn_shared_desc* d, const char* who) {
+  if (int e = fvta_attn_shared_check(d, who)) return e;
+  if (d->simi == 4) {
+    fvta_set_error("%s: simiMatrix 4 has no shared-context backward (simiMatrix 1-3); the per-question route "
+                   "(fvta_attn_fwd / fvta_attn_bwd on the gathered rows) covers it", who);
+    return FVTA_ERR_UNSUPPORTED;
+  }
+  return FVTA_OK;
+}
+
+extern "C" size_t fvta_attn_shared_saved_bytes(const fvta_attn_shared_desc* d) {
+  if (fvta_attn_shared_check_train(d, "attn_shared_saved_bytes") != FVTA_OK) return 0;
+  return ShWork(sh_shape(d), nullptr, nullptr).saved_bytes;
+}
+
+extern "C" int fvta_attn_shared_fwd_train(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask,
+                                          const float* hq, const uint8_t* qmask, const int32_t* album, const float* W,
+                                          const float* b, float* h_a, float* a_logits, void* saved, void* workspace,
+                                          fvta_stream_t stream_) {
+  if (int e = fvta_attn_shared_check_train(d, "attn_shared_fwd_train")) return e;
+  FVTA_CHECK_ARG(hinfo && hq && album && W && h_a && saved && workspace, "attn_shared_fwd_train: null pointer");
+  const ShShape s = sh_shape(d);
+  return sh_forward<true>(s, ShWork(s, saved, workspace), hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits,
+                          (hipStream_t)stream_);
 }

@@ -1,0 +1,103 @@
+// What the shared-context focal attention's forward (attn_shared.hip) and backward (attn_shared_bwd.hip) agree on: the
+// shape, the plan's layout, the forward's buffers and -- in training -- which of them live in the caller-held `saved`.
+#pragma once
+#include "attn_common.h"
+
+namespace fvta {
+
+constexpr int SH_BN = 256;   // question columns of a group: G * JP
+constexpr int SH_NT = 256;
+constexpr int SH_CH = 64;    // rows whose softmax weights the weighted-sum kernel stages at a time
+constexpr int SH_PLAN_NT = 1024;
+constexpr int SH_R = 64;     // rows of a tile of the logits kernel (ShMma::BM)
+
+struct ShShape {
+  int A, NQ, K, T, JQ, w, simi, add_tanh, use_mask;
+  int JP, G;      // padded question length (32 / 64), questions per group (8 / 4)
+  int ntile;      // row tiles of a (k): ceil(T / SH_R)
+  int S, rps;     // T splits of the weighted sum, rows per split
+  int ngmax;      // upper bound of the number of groups: floor(NQ / G) + min(A, NQ), at most NQ
+};
+
+inline ShShape sh_shape(const fvta_attn_shared_desc* d) {
+  ShShape s;
+  s.A = d->A, s.NQ = d->NQ, s.K = d->K, s.T = d->T, s.JQ = d->JQ, s.w = d->w, s.simi = d->simi, s.add_tanh = d->add_tanh;
+  s.use_mask = 0;
+  s.JP = d->JQ <= 32 ? 32 : 64;
+  s.G = SH_BN / s.JP;
+  s.ntile = (d->T + SH_R - 1) / SH_R;
+  const int64_t ng = (int64_t)d->NQ / s.G + (d->A < d->NQ ? d->A : d->NQ);
+  s.ngmax = (int)(ng < d->NQ ? ng : d->NQ);
+  // about 1024 workgroups of the weighted sum (4 per CU), a split not shorter than one chunk
+  int64_t S = (1024 + (int64_t)s.ngmax * d->K - 1) / ((int64_t)s.ngmax * d->K);
+  const int maxs = (d->T + SH_CH - 1) / SH_CH;
+  if (S > maxs) S = maxs;
+  if (S < 1) S = 1;
+  s.rps = (int)((d->T + S - 1) / S);
+  s.S = (d->T + s.rps - 1) / s.rps;
+  return s;
+}
+
+// The forward's buffers.  Inference (fvta_attn_shared_fwd) carves all of them from the workspace.  Training
+// (fvta_attn_shared_fwd_train) carves what the backward reads from `saved` -- the four training-only pieces included -- and
+// only the rest (coef, part, agrp) from the workspace; `bytes` is the workspace's share, `saved_bytes` the other.
+struct ShWork {
+  float *vecs, *Qs, *ct, *amax, *M, *coef, *part;
+  int *acnt, *astart, *agrp, *order, *qslot, *ngroups;
+  int4* grp;
+  uint8_t* jmax;     // training only (else null): [NQ,K,T] FIRST arg-max j of the masked (tanh'd) logits
+  float *L, *r, *u;  // training only: L [NQ,K] = sum_t exp(amax - M), r [NQ,K] = softmax_k(M), u [NQ,K,w] = inner softsel
+  size_t bytes, saved_bytes;
+  ShWork(const ShShape& s, void* p) {
+    FvtaCarver c(p);
+    vecs = c.take<float>((size_t)VEC_COUNT * s.w);
+    Qs = c.take<float>((size_t)s.NQ * s.JP * s.w);
+    ct = c.take<float>((size_t)s.NQ * s.JP);
+    amax = c.take<float>((size_t)s.NQ * s.K * s.T);
+    M = c.take<float>((size_t)s.NQ * s.K);
+    coef = c.take<float>((size_t)s.NQ * s.K);
+    part = c.take<float>((size_t)s.ngmax * s.K * s.S * s.G * s.w);
+    acnt = c.take<int>((size_t)s.A);
+    astart = c.take<int>((size_t)s.A);
+    agrp = c.take<int>((size_t)s.A);
+    order = c.take<int>((size_t)s.NQ);
+    qslot = c.take<int>((size_t)s.NQ);
+    ngroups = c.take<int>(1);
+    grp = c.take<int4>((size_t)s.ngmax);
+    bytes = c.off;
+    saved_bytes = 0;
+    jmax = nullptr;
+    L = r = u = nullptr;
+  }
+  ShWork(const ShShape& s, void* saved, void* work) {
+    FvtaCarver c(saved), v(work);
+    const size_t nk = (size_t)s.NQ * s.K;
+    amax = c.take<float>(nk * s.T);
+    jmax = c.take<uint8_t>(nk * s.T);
+    M = c.take<float>(nk);
+    L = c.take<float>(nk);
+    r = c.take<float>(nk);
+    u = c.take<float>(nk * s.w);
+    Qs = c.take<float>((size_t)s.NQ * s.JP * s.w);
+    ct = c.take<float>((size_t)s.NQ * s.JP);
+    vecs = c.take<float>((size_t)VEC_COUNT * s.w);
+    grp = c.take<int4>((size_t)s.ngmax);
+    order = c.take<int>((size_t)s.NQ);
+    qslot = c.take<int>((size_t)s.NQ);
+    ngroups = c.take<int>(1);
+    astart = c.take<int>((size_t)s.A);   // an album's questions are order[astart[a] .. + acnt[a])
+    acnt = c.take<int>((size_t)s.A);
+    saved_bytes = c.off;
+    coef = v.take<float>(nk);
+    part = v.take<float>((size_t)s.ngmax * s.K * s.S * s.G * s.w);
+    agrp = v.take<int>((size_t)s.A);
+    bytes = v.off;
+  }
+};
+
+// 0: fine, else the status with the message set (attn_shared.hip)
+int fvta_attn_shared_check(const fvta_attn_shared_desc* d, const char* who);
+// the same, and simiMatrix 1-3 (training: the cosine form has no shared-context backward)
+int fvta_attn_shared_check_train(const fvta_attn_shared_desc* d, const char* who);
+
+}  // namespace fvta

@@ -173,20 +173,30 @@ def attention_raw(hinfo, hq, W, b, hinfo_mask=None, hq_mask=None, simiMatrix=1, 
     return h_a[:, :w].contiguous(), a
 
 
-def attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask=None, hq_mask=None, simiMatrix=1, add_tanh=False):
+def attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask=None, hq_mask=None, simiMatrix=1, add_tanh=False,
+                            differentiable=False):
     """attention_3d for NQ questions over A albums held once: hinfo [A,K,T,w] (or [A,K,M,JX,w]), hq [NQ,JQ,w], album [NQ]
     integers in [0, A) (validated on the host before the upload), W / b as attention_raw -> (h_a [NQ,w], a_logits
-    [NQ,K,T,JQ]): question i attends album[i]'s rows, with attention_raw's result for that pair.  FORWARD ONLY
-    (fvta_attn_shared_fwd keeps nothing for a backward): with gradient mode on and an argument that requires grad this
-    raises instead of returning a detached result; train through attention_3d / attention_raw per question."""
+    [NQ,K,T,JQ]): question i attends album[i]'s rows, with attention_raw's result for that pair.
+    differentiable=False (the default) is the inference call (fvta_attn_shared_fwd keeps nothing for a backward): with
+    gradient mode on and an argument that requires grad it raises instead of returning a detached result.
+    differentiable=True goes through autograd.shared_focal_attention (simiMatrix 1-3; 4 raises NotImplementedError):
+    gradients flow from h_a to hinfo -- summed over each album's questions, [A,K,T,w] -- hq, W and b; a_logits carries
+    none."""
     if simiMatrix not in (1, 2, 3, 4):
         raise ValueError("similarity matrix not implemented")
+    if differentiable and simiMatrix == 4:
+        raise NotImplementedError("attention_3d_shared_raw(differentiable=True): simiMatrix 4 has no shared-context backward; "
+                                  "use the per-question attention_3d (attention_raw) on hinfo.index_select(0, album)")
     tensors = [t for t in (hinfo, hq, W, b) if torch.is_tensor(t)]
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise RuntimeError("attention_3d_shared_raw is forward-only: call it under torch.no_grad(), or use the per-question "
-                           "attention_3d (functional.attention_3d / attention_raw, nn.FocalAttention3D.forward), which is "
-                           "the differentiable route")
-    hinfo, hq = _f32(hinfo.detach()), _f32(hq.detach())
+    if not differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("attention_3d_shared_raw is forward-only by default: pass differentiable=True (simiMatrix 1-3), call "
+                           "it under torch.no_grad(), or use the per-question attention_3d (functional.attention_3d / "
+                           "attention_raw, nn.FocalAttention3D.forward)")
+    if not differentiable:
+        hinfo, hq = hinfo.detach(), hq.detach()
+        W, b = (None if W is None else W.detach()), (None if b is None else b.detach())
+    hinfo, hq = _f32(hinfo), _f32(hq)
     A, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
     hinfo = hinfo.reshape(A, K, -1, w)
     T = hinfo.shape[2]
@@ -199,17 +209,40 @@ def attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask=None, hq_mask=Non
         raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
     F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
     if F:
-        W = _pad_channels(_f32(W.detach()).reshape(F, w), wp).reshape(-1)
-        b = _f32(b.detach())
+        W = _pad_channels(_f32(W).reshape(F, w), wp).reshape(-1)
+        b = _f32(b)
     else:
         W = b = None
     dev = ops.require_gpu()
     both = hinfo_mask is not None and hq_mask is not None                  # model_v2.py:233: only when BOTH are given
     hm = ops.as_mask_u8(hinfo_mask.reshape(A, K, T)) if both else None
     qm = ops.as_mask_u8(hq_mask) if both else None
-    op = ops.SharedFocalAttention(A, NQ, K, T, JQ, wp, simiMatrix, add_tanh)
-    h_a, a = op.forward(_pad_channels(hinfo, wp), hm, _pad_channels(hq, wp), qm, idx.to(dev), W, b, want_logits=True)
+    if differentiable:
+        h_a, a = autograd.shared_focal_attention(_pad_channels(hinfo, wp), _pad_channels(hq, wp), idx.to(dev), W, b, hm, qm,
+                                                 simiMatrix, add_tanh)
+    else:
+        op = ops.SharedFocalAttention(A, NQ, K, T, JQ, wp, simiMatrix, add_tanh)
+        h_a, a = op.forward(_pad_channels(hinfo, wp), hm, _pad_channels(hq, wp), qm, idx.to(dev), W, b, want_logits=True)
     return h_a[:, :w].contiguous(), a
+
+
+def attention_3d_shared(hinfo, hq, album, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, add_tanh=False,
+                        scope=None):
+    """attention_3d (model_v2.py:210-298) of NQ questions over A albums whose rows are held once, with the `att_logits`
+    variables of the scope (the ones attention_3d uses under the same scope); always differentiable (simiMatrix 1-3)."""
+    if simiMatrix not in (1, 2, 3, 4):
+        raise ValueError("similarity matrix not implemented")
+    if simiMatrix == 4:
+        raise NotImplementedError("attention_3d_shared: simiMatrix 4 has no shared-context backward; use attention_3d on "
+                                  "hinfo.index_select(0, album)")
+    w = hinfo.shape[-1]
+    F = {1: 3, 2: 2, 3: 4}[simiMatrix]
+    with variable_scope(scope or "attention_2vector"):
+        wn, bn = _name("att_logits", "W"), _name("att_logits", "b")
+        W = get_variable(wn, (F * w, 1))
+        b = get_variable(bn, (1,), init="zeros")
+        _add_wd([wn, bn], wd)
+    return attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask, hq_mask, simiMatrix, add_tanh, differentiable=True)
 
 
 def _attention(hinfo, hq, hinfo_mask, hq_mask, simiMatrix, wd, add_tanh, scope, feat_order, tscale=None):

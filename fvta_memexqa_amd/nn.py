@@ -102,13 +102,15 @@ class FocalAttention3D(_AttLogits):
         return functional.attention_raw(hinfo.reshape(N, K, -1, self.w), hq, W, b, hinfo_mask, hq_mask, self.simiMatrix,
                                         self.add_tanh, 0, tscale)
 
-    def forward_shared(self, hinfo, hq, album, hinfo_mask=None, hq_mask=None):
+    def forward_shared(self, hinfo, hq, album, hinfo_mask=None, hq_mask=None, differentiable=False):
         """forward() for NQ questions over A albums held once: hinfo [A,K,...,w], hq [NQ,JQ,w], album [NQ] in [0, A) ->
-        (h_a [NQ,w], a_logits [NQ,K,T,JQ]) with this module's att_logits/{W,b}.  Forward only
-        (functional.attention_3d_shared_raw): under gradient mode the parameters require grad and the call raises; use it
-        under torch.no_grad() and train through forward()."""
+        (h_a [NQ,w], a_logits [NQ,K,T,JQ]) with this module's att_logits/{W,b} (functional.attention_3d_shared_raw).
+        differentiable=False is the inference call: under gradient mode the parameters require grad and the call raises;
+        use it under torch.no_grad().  differentiable=True trains over the shared rows (simiMatrix 1-3; 4 raises
+        NotImplementedError): h_a's gradient reaches hinfo [A,K,...,w], hq and the parameters, a_logits carries none."""
         W, b = self._wb()
-        return functional.attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask, hq_mask, self.simiMatrix, self.add_tanh)
+        return functional.attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask, hq_mask, self.simiMatrix, self.add_tanh,
+                                                  differentiable=differentiable)
 
 
 class AlbumMemory:

@@ -300,7 +300,9 @@ def check_album_index(album, A):
 class SharedFocalAttention:
     """attention_3d (model_v2.py:210-298) of NQ questions over A albums whose context rows are held ONCE: hinfo [A,K,T,w],
     hmask [A,K,T], hq [NQ,JQ,w], qmask [NQ,JQ], album [NQ] int32 on the device (validate it with check_album_index before
-    the upload).  Forward only (fvta_attn_shared_fwd); question i gets FocalAttention's result on album[i]'s rows."""
+    the upload).  Question i gets FocalAttention's result on album[i]'s rows.  forward() is the inference call
+    (fvta_attn_shared_fwd, nothing kept); forward_train() / backward() are the training pair (simiMatrix 1-3), whose
+    d_hinfo stays [A,K,T,w]: the sum of the per-question row gradients over each album's questions."""
 
     def __init__(self, A, NQ, K, T, JQ, w, simi, add_tanh):
         self.lib = _lib.load()
@@ -327,6 +329,47 @@ class SharedFocalAttention:
                                             ptr(album), ptr(W), ptr(b), ptr(h_a), ptr(a_logits), ptr(self.work),
                                             stream_ptr()), "fvta_attn_shared_fwd")
         return h_a, a_logits
+
+    def _sized(self, query, what):
+        nb = getattr(self.lib, query)(ctypes.byref(self.desc))
+        if nb == 0:
+            raise _lib.FvtaError("shared attention %s: %s" % (what, self.lib.fvta_last_error().decode()))
+        return _bytes(nb, self.dev)
+
+    def bwd_plan(self):
+        """{rows, tsplit, channels}: rows per tile of the backward's row pass, T splits and channels per slice of its
+        question pass (fvta_attn_shared_bwd_plan; host only, simiMatrix 1-3)"""
+        out = (ctypes.c_int32 * 4)()
+        check(self.lib.fvta_attn_shared_bwd_plan(ctypes.byref(self.desc), out), "fvta_attn_shared_bwd_plan")
+        return dict(zip(("rows", "tsplit", "channels"), (int(v) for v in out[:3])))
+
+    def forward_train(self, hinfo, hmask, hq, qmask, album, W, b, want_logits=False):
+        """forward() -- the same bits -- that leaves in self.saved (allocated on first use) what backward() reads
+        (fvta_attn_shared_fwd_train; simiMatrix 1-3)"""
+        assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
+        assert album.is_cuda and album.dtype == torch.int32 and album.is_contiguous() and tuple(album.shape) == (self.NQ,)
+        if getattr(self, "saved", None) is None:
+            self.saved = self._sized("fvta_attn_shared_saved_bytes", "saved")
+        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
+        a_logits = torch.empty(self.NQ, self.K, self.T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
+        check(self.lib.fvta_attn_shared_fwd_train(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)),
+                                                  ptr(qmask), ptr(album), ptr(_f32c(W)), ptr(b), ptr(h_a), ptr(a_logits),
+                                                  ptr(self.saved), ptr(self.work), stream_ptr()), "fvta_attn_shared_fwd_train")
+        return h_a, a_logits
+
+    def backward(self, hinfo, hmask, hq, qmask, album, W, b, d_h_a, d_hinfo, d_hq, dW, db):
+        """After forward_train() with the same arguments: d_hinfo [A,K,T,w] and d_hq [NQ,JQ,w] are overwritten, dW [F] and
+        db [1] accumulated into (fvta_attn_shared_bwd).  Its workspace is allocated on first use."""
+        if getattr(self, "saved", None) is None:
+            raise _lib.FvtaError("shared attention: backward() needs a forward_train() first")
+        if getattr(self, "work_bwd", None) is None:
+            self.work_bwd = self._sized("fvta_attn_shared_bwd_workspace_bytes", "backward workspace")
+        assert tuple(d_hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(d_hq.shape) == (self.NQ, self.JQ, self.w)
+        assert tuple(d_h_a.shape) == (self.NQ, self.w)
+        check(self.lib.fvta_attn_shared_bwd(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)), ptr(qmask),
+                                            ptr(album), ptr(_f32c(W)), ptr(b), ptr(_f32c(d_h_a)), ptr(self.saved),
+                                            ptr(_f32c(d_hinfo)), ptr(_f32c(d_hq)), ptr(_f32c(dW)), ptr(_f32c(db)),
+                                            ptr(self.work_bwd), stream_ptr()), "fvta_attn_shared_bwd")
 
 
 def linear_fwd(x, W, b, y, M, din, dout, add_tanh=False, blk=None):

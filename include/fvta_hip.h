@@ -131,7 +131,8 @@ int fvta_attn_bwd_tw(const fvta_attn_desc* d, const float* hinfo, const float* h
                      int accumulate, void* workspace, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
- * Focal attention, many questions over one album (FORWARD ONLY): the context tensor of model_v2.py:863-914 depends on
+ * Focal attention, many questions over one album (this call: forward only; training: below).
+ * The context tensor of model_v2.py:863-914 depends on
  * the album alone, the question enters at attention_3d (:210-298).  hinfo [A,K,T,w] / hmask [A,K,T] hold each album
  * once; question i (hq [NQ,JQ,w], qmask [NQ,JQ]) attends album[i]:
  *   h_a[i], a_logits[i] = what fvta_attn_fwd returns for (hinfo[album[i]], hq[i], hmask[album[i]], qmask[i]),
@@ -142,7 +143,8 @@ int fvta_attn_bwd_tw(const fvta_attn_desc* d, const float* hinfo, const float* h
  *   (ops.check_album_index does).
  *   W, b: as fvta_attn_fwd (feature order of model_v2.py:242-254; simi 4 takes NULL).  a_logits [NQ,K,T,JQ] or NULL.
  * Not here: time_warp_att and the time warp (the warped tensor depends on the question: nothing to share), shadow rows,
- * and a backward -- there is no `saved`; training goes through fvta_attn_fwd / fvta_attn_bwd per question.
+ * and a backward of THIS call -- it keeps no `saved`; fvta_attn_shared_fwd_train / fvta_attn_shared_bwd below train over
+ * the shared rows (simiMatrix 1-3), fvta_attn_fwd / fvta_attn_bwd per question otherwise.
  * Range: w in {64,128,256,512,1024,2048}, JQ 1..64, K 1..64, simi 1..4, any T, A >= 1, NQ >= 1; otherwise the size
  * query returns 0 and the calls FVTA_ERR_UNSUPPORTED / FVTA_ERR_INVALID_ARG with a message.
  * The questions are grouped by album ON THE DEVICE (counting sort, groups of at most G: 8 at JQ <= 32, 4 above), no
@@ -163,6 +165,37 @@ int fvta_attn_shared_plan(const fvta_attn_shared_desc* d, int32_t out[4]);
 int fvta_attn_shared_fwd(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
                          const uint8_t* qmask, const int32_t* album, const float* W, const float* b, float* h_a,
                          float* a_logits, void* workspace, fvta_stream_t stream);
+
+/* Training over shared rows (simiMatrix 1-3; with simi 4 the two size queries return 0 and the calls
+ * FVTA_ERR_UNSUPPORTED: the per-question route, fvta_attn_fwd / fvta_attn_bwd on gathered rows, covers the cosine form).
+ * fvta_attn_shared_fwd_train: the kernels of fvta_attn_shared_fwd -- h_a and a_logits are its bits -- and, in the
+ *   caller-held `saved` (fvta_attn_shared_saved_bytes), what the backward reads: amax [NQ,K,T], the FIRST arg-max jmax
+ *   [NQ,K,T] (u8), M, L, r [NQ,K], u [NQ,K,w], Qs, ct, the per-channel vectors, and the plan (grp, order, qslot, ngroups,
+ *   per-album starts and counts).  In this plan the questions of an album stand by ascending question index.
+ *   `workspace`: fvta_attn_shared_workspace_bytes, free again when the call returns.
+ * fvta_attn_shared_bwd: from d_h_a [NQ,w], for question i: d_hq[i] and i's share of dW / db are what fvta_attn_bwd
+ *   (accumulate = 0) gives for (hinfo[album[i]], hq[i], hmask[album[i]], qmask[i], d_h_a[i]); d_hinfo[a] is the sum of
+ *   those calls' d_hinfo over the questions of album a.  d_hinfo [A,K,T,w] and d_hq [NQ,JQ,w] are OVERWRITTEN (an album
+ *   without a question: zeros; a masked row: zeros, unless a fully masked question or (album, k) spreads its uniform
+ *   softmax over it, as in fvta_attn_bwd); dW [F] and db [1] are accumulated into.  fvta_attn_bwd's deviations carry
+ *   over: the max over j routes to the first arg-max, ties of the max over t are split, a fully masked (album, k) or
+ *   question passes nothing into its masked logits.  The same arguments as the forward call; `workspace`:
+ *   fvta_attn_shared_bwd_workspace_bytes.  Not here: time warp, shadow rows, accumulate modes, the gradient of a_logits.
+ *   No [NQ,K,T,w]-sized buffer: each d_hinfo row is written once, rows are read once per (album, k) and once per group of
+ *   the album's questions.  No floating-point atomics, fixed summation order (the sum over an album's questions runs by
+ *   ascending question index): two calls are bitwise equal in all four outputs.  No host synchronisation.
+ * fvta_attn_shared_bwd_plan (host only): out = {rows per tile of the row pass, T splits of the question pass, channels
+ *   per slice of the question pass, 0}. */
+size_t fvta_attn_shared_saved_bytes(const fvta_attn_shared_desc* d);         /* 0 bytes: see fvta_last_error */
+size_t fvta_attn_shared_bwd_workspace_bytes(const fvta_attn_shared_desc* d); /* 0 bytes: see fvta_last_error */
+int fvta_attn_shared_bwd_plan(const fvta_attn_shared_desc* d, int32_t out[4]);
+int fvta_attn_shared_fwd_train(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
+                               const uint8_t* qmask, const int32_t* album, const float* W, const float* b, float* h_a,
+                               float* a_logits, void* saved, void* workspace, fvta_stream_t stream);
+int fvta_attn_shared_bwd(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
+                         const uint8_t* qmask, const int32_t* album, const float* W, const float* b, const float* d_h_a,
+                         const void* saved, float* d_hinfo, float* d_hq, float* dW, float* db, void* workspace,
+                         fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * bi-LSTM modality encoders: model_v2.py:652-661 (cells), 667-678 (lengths),

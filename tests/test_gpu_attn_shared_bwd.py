@@ -1,0 +1,312 @@
+"""GPU parity of the shared-context focal attention's training calls (fvta_attn_shared_fwd_train / fvta_attn_shared_bwd,
+ops.SharedFocalAttention.forward_train / backward, autograd.shared_focal_attention, functional.attention_3d_shared[_raw],
+nn.FocalAttention3D.forward_shared(differentiable=True)) against fp64 autograd of the oracle on h[album]
+(tests/_attn_shared_bwd_ref.py), at the tolerance of tests/test_gpu_backward.py: rtol 1e-4, atol 1e-5 x max(1, max|ref|).
+
+The shapes are the smallest that turn every loop over: groups of G+1, 1, 0, 2G+1 and G questions, T around the row pass's
+tile (fvta_attn_shared_bwd_plan) and across a T split of the question pass, JQ = 1, 30, 32, 33, 64, every width from 64 to
+2048, A = NQ = 1, K = 6.  The pinned seeds keep every arg-max clear in fp64 (tests/test_attn_shared_bwd_host.py); the
+first test also holds the GPU's own logits to a quarter of the case's smallest gap."""
+import numpy as np
+import pytest
+import torch
+
+from tests import _attn_shared_bwd_ref as B
+from tests import _attn_shared_ref as R
+
+pytestmark = pytest.mark.gpu
+
+_REF = {}
+
+
+def _close(a, b, rtol=1e-4, atol=1e-5, msg=""):
+    a = a.detach().cpu().double().numpy()
+    b = b.detach().cpu().double().numpy()
+    scale = max(1.0, float(np.abs(b).max()))
+    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol * scale, err_msg=msg)
+
+
+def _cu(t):
+    return None if t is None else t.cuda().contiguous()
+
+
+def _case(name):
+    """the case and its fp64 reference, computed once per session and never written to"""
+    if name not in _REF:
+        c = B.build_case(name)
+        _REF[name] = (c, B.reference(c))
+    return _REF[name]
+
+
+class _Run:
+    """ops.SharedFocalAttention on case c (rows: a subset of the questions), its device tensors kept for backward()"""
+
+    def __init__(self, c, rows=None):
+        from fvta_memexqa_amd import ops
+        q, qm, al, g = c["q"], c["qm"], c["album"], c["gout"]
+        if rows is not None:
+            q, al, g = q[rows], al[rows], g[rows]
+            qm = None if qm is None else qm[rows]
+        self.c, self.NQ = c, q.shape[0]
+        self.op = ops.SharedFocalAttention(c["A"], self.NQ, c["K"], c["T"], c["JQ"], c["w"], c["simi"], c["tanh"])
+        self.args = (_cu(c["h"]), _cu(ops.as_mask_u8(c["hm"])), _cu(q), _cu(ops.as_mask_u8(qm)),
+                     ops.check_album_index(al, c["A"]).cuda(), _cu(c["W"].reshape(-1)), _cu(c["b"]))
+        self.g = _cu(g)
+
+    def forward_train(self, want_logits=True):
+        return self.op.forward_train(*self.args, want_logits=want_logits)
+
+    def forward(self, want_logits=True):
+        return self.op.forward(*self.args, want_logits=want_logits)
+
+    def backward(self, dW=None, db=None, fill=7.0):
+        c = self.c
+        dh = torch.full((c["A"], c["K"], c["T"], c["w"]), fill, device="cuda")
+        dq = torch.full((self.NQ, c["JQ"], c["w"]), fill, device="cuda")
+        dW = torch.zeros_like(self.args[5]) if dW is None else dW
+        db = torch.zeros(1, device="cuda") if db is None else db
+        self.op.backward(*self.args, self.g, dh, dq, dW, db)
+        return dh, dq, dW, db
+
+
+@pytest.mark.parametrize("name", B.CASE_IDS)
+def test_gradients_match_fp64_autograd(name):
+    c, ref = _case(name)
+    run = _Run(c)
+    ha, a = run.forward_train()
+    # the arg-max the backward routes through is the reference's: the GPU's logits are within a quarter of the smallest gap
+    jgap, tgap, _ = B.conditions(c, ref["a_logits"])
+    v = B.valid_mask(c)
+    err = float((a.cpu().double() - ref["a_logits"])[v].abs().max())
+    print("%s: max |a_logits - fp64| over valid entries %.3g, smallest gap %.3g" % (name, err, min(jgap, tgap)))
+    assert err < min(jgap, tgap) / 4, (err, jgap, tgap)
+    _close(ha, ref["h_a"], msg="h_a")
+    dh, dq, dW, db = run.backward()                              # d_hinfo / d_hq prefilled with 7.0: overwritten
+    for got, key in ((dh, "dh"), (dq, "dq"), (dW, "dW"), (db, "db")):
+        print("%s %s: max |got - ref| %.3g, max |ref| %.3g" % (name, key, float((got.cpu().double() - ref[key]).abs().max()),
+                                                               float(ref[key].abs().max())))
+    _close(dh, ref["dh"], msg="d_hinfo")
+    _close(dq, ref["dq"], msg="d_hq")
+    _close(dW, ref["dW"], msg="dW")
+    _close(db, ref["db"], msg="db")
+    dh2, dq2, dW2, db2 = run.backward(dW=dW, db=db, fill=-3.0)   # a second call: dW / db accumulate, the others do not
+    _close(dW2, 2 * ref["dW"], atol=2e-5, msg="dW accumulates")
+    _close(db2, 2 * ref["db"], atol=2e-5, msg="db accumulates")
+    _close(dh2, ref["dh"], msg="d_hinfo overwritten")
+    _close(dq2, ref["dq"], msg="d_hq overwritten")
+
+
+def test_same_result_as_the_per_question_route(attn_select):
+    """The masked `mix` case as make_case leaves it: a fully masked (album, k), a single-row (album, k), a fully masked
+    question and an album without a question.  The contract is the expanded per-question route: index_select,
+    ops.FocalAttention forward + backward (accumulate = 0), index_add_ of the row gradient.  Zeros: the question-less
+    album's rows, and every masked row -- except where fvta_attn_bwd itself writes one: a fully masked QUESTION's
+    softmax is uniform over all T rows of every k of its album, masked ones included (p r g, no logit gradient), so
+    that album's masked rows hold exactly that term and are compared like all others."""
+    from fvta_memexqa_amd import ops
+    c = B.build_case(B.MIX_MASKED, parity=False)
+    run = _Run(c)
+    run.forward_train(want_logits=False)
+    dh, dq, dW, db = run.backward()
+    attn_select.exact()
+    h, hm, q, qm, al, W, b = run.args
+    al64 = al.long()
+    he, hme = h.index_select(0, al64), hm.index_select(0, al64)
+    op = ops.FocalAttention(c["NQ"], c["K"], c["T"], c["JQ"], c["w"], c["simi"], c["tanh"])
+    op.forward(he, q, hme, qm, W, b)
+    dhe, dqe = torch.full_like(he, 7.0), torch.full_like(q, 7.0)
+    dWe, dbe = torch.zeros_like(W), torch.zeros(1, device="cuda")
+    op.backward(he, q, hme, qm, W, b, run.g, dhe, dqe, dWe, dbe, 0)
+    dh_ref = torch.zeros_like(h).index_add_(0, al64, dhe)
+    _close(dh, dh_ref, msg="d_hinfo against index_add_ of the per-question gradient")
+    _close(dq, dqe, msg="d_hq")
+    _close(dW, dWe, msg="dW")
+    _close(db, dbe, msg="db")
+    cnt = torch.bincount(c["album"], minlength=c["A"])
+    empty = int((cnt == 0).nonzero()[0])
+    assert float(dh[empty].abs().max()) == 0.0                   # the album without a question: exactly zero
+    fully_masked_q = (~c["qm"].any(-1)).nonzero().reshape(-1)
+    assert fully_masked_q.numel() == 1
+    spread = set(c["album"][fully_masked_q].tolist())            # albums whose masked rows carry a uniform softmax
+    checked = 0
+    for a in range(c["A"]):
+        if a in spread:
+            continue
+        masked_rows = ~c["hm"][a]                                # [K,T]
+        assert float(dh[a].cpu()[masked_rows].abs().max()) == 0.0
+        checked += int(masked_rows.sum())
+    assert checked > 0
+    assert float(dq[int(fully_masked_q[0])].abs().max()) == 0.0  # nothing passes into a fully masked question
+
+
+@pytest.mark.parametrize("name", ["mix-simi2-masked", "cols-jq33-w128", "rows-T333", "wide2048"])
+def test_forward_train_has_the_bits_of_the_inference_forward(name):
+    c, _ = _case(name)
+    run = _Run(c)
+    ha_t, a_t = run.forward_train()
+    ha_i, a_i = run.forward()
+    assert torch.equal(ha_t, ha_i) and torch.equal(a_t, a_i)
+    ha_n, none = run.forward_train(want_logits=False)
+    assert none is None and torch.equal(ha_n, ha_i)
+
+
+@pytest.mark.parametrize("name", ["mix-simi3-masked", "rows-T333", "cols-jq64-w512"])
+def test_three_backward_calls_are_bitwise_equal(name):
+    c, _ = _case(name)
+    outs = []
+    for _ in range(3):
+        run = _Run(c)                                            # a fresh handle: plan, saved and workspace anew
+        run.forward_train(want_logits=False)
+        outs.append(run.backward())
+    for other in outs[1:]:
+        for x, y in zip(outs[0], other):
+            assert torch.equal(x, y)
+
+
+def test_a_questions_gradient_does_not_depend_on_its_company():
+    c, _ = _case("mix-simi3-masked")
+    G, _ = R.host_plan(c["JQ"], c["w"])
+    big = int(torch.bincount(c["album"], minlength=c["A"]).argmax())          # the album with 2G+1 questions
+    members = torch.nonzero(c["album"] == big).reshape(-1)
+    assert members.numel() == 2 * G + 1
+    run = _Run(c)
+    run.forward_train(want_logits=False)
+    _, dq_all, _, _ = run.backward()
+    i = int(members[G])
+    one = _Run(c, rows=[i])
+    one.forward_train(want_logits=False)
+    dh_one, dq_one, _, _ = one.backward()
+    _close(dq_one[0], dq_all[i], msg="d_hq alone against in company")
+    others = [a for a in range(c["A"]) if a != big]
+    assert float(dh_one[others].abs().max()) == 0.0                            # and it reaches its own album only
+
+
+def test_functional_and_nn_surface():
+    from fvta_memexqa_amd import functional as Fn, nn
+    c, ref = _case("rows-TRb+1")                                               # w = 256
+    h, q, W, b = (_cu(c[k]).requires_grad_() for k in ("h", "q", "W", "b"))
+    hm, qm, g = _cu(c["hm"]), _cu(c["qm"]), _cu(c["gout"])
+    ha, a = Fn.attention_3d_shared_raw(h, q, c["album"], W, b, hm, qm, simiMatrix=c["simi"], add_tanh=c["tanh"],
+                                       differentiable=True)
+    assert ha.requires_grad and not a.requires_grad
+    (ha * g).sum().backward()
+    _close(ha, ref["h_a"])
+    _close(h.grad, ref["dh"], msg="functional d_hinfo")
+    _close(q.grad, ref["dq"], msg="functional d_hq")
+    _close(W.grad.reshape(-1), ref["dW"], msg="functional dW")
+    _close(b.grad, ref["db"], msg="functional db")
+    with pytest.raises(RuntimeError, match="attention_3d"):                    # the default still refuses under gradient mode
+        Fn.attention_3d_shared_raw(h, q, c["album"], W, b, hm, qm, simiMatrix=c["simi"], add_tanh=c["tanh"])
+    with pytest.raises(NotImplementedError):
+        Fn.attention_3d_shared_raw(h, q, c["album"], None, None, hm, qm, simiMatrix=4, differentiable=True)
+
+    att = nn.FocalAttention3D(c["w"], simiMatrix=c["simi"], add_tanh=c["tanh"])
+    with torch.no_grad():
+        att.p("att_logits/W").copy_(_cu(c["W"]))
+        att.p("att_logits/b").copy_(_cu(c["b"]))
+    h2, q2 = _cu(c["h"]).requires_grad_(), _cu(c["q"]).requires_grad_()
+    ha2, a2 = att.forward_shared(h2, q2, c["album"], hm, qm, differentiable=True)
+    assert not a2.requires_grad
+    (ha2 * g).sum().backward()
+    _close(h2.grad, ref["dh"], msg="nn d_hinfo")
+    _close(q2.grad, ref["dq"], msg="nn d_hq")
+    _close(att.p("att_logits/W").grad.reshape(-1), ref["dW"], msg="nn dW")
+    _close(att.p("att_logits/b").grad, ref["db"], msg="nn db")
+    with pytest.raises(RuntimeError):
+        att.forward_shared(h2, q2, c["album"], hm, qm)
+    with pytest.raises(NotImplementedError):
+        nn.FocalAttention3D(c["w"], simiMatrix=4).forward_shared(h2, q2, c["album"], hm, qm, differentiable=True)
+
+    # the scope's att_logits variables, as attention_3d has them: the same variables, the same result
+    Fn.reset_default_graph()
+    try:
+        with torch.no_grad():
+            al = c["album"].cuda()
+            ha_each, _ = Fn.attention_3d(_cu(c["h"]).index_select(0, al), _cu(c["q"]), hm.index_select(0, al), qm,
+                                         simiMatrix=c["simi"], add_tanh=c["tanh"], scope="att")
+        names = set(Fn.variables)
+        h3 = _cu(c["h"]).requires_grad_()
+        ha3, a3 = Fn.attention_3d_shared(h3, _cu(c["q"]), c["album"], hm, qm, simiMatrix=c["simi"], add_tanh=c["tanh"],
+                                         scope="att")
+        assert set(Fn.variables) == names and any(n.endswith("att_logits/W") for n in names)
+        assert ha3.requires_grad and not a3.requires_grad
+        _close(ha3, ha_each, msg="attention_3d_shared against attention_3d on gathered rows")
+        ha3.sum().backward()
+        assert h3.grad is not None and float(h3.grad.abs().max()) > 0
+    finally:
+        Fn.reset_default_graph()
+
+
+def test_unpadded_width_goes_through_channel_padding():
+    from fvta_memexqa_amd import functional as Fn
+    c = B.odd_width_case()                                                     # w = 100 -> the 128-wide kernels
+    ref = B.reference(c)
+    assert B.qualifies(c, ref["a_logits"])
+    h, q, W, b = (_cu(c[k]).requires_grad_() for k in ("h", "q", "W", "b"))
+    ha, a = Fn.attention_3d_shared_raw(h, q, c["album"], W, b, _cu(c["hm"]), _cu(c["qm"]), simiMatrix=c["simi"],
+                                       add_tanh=c["tanh"], differentiable=True)
+    assert tuple(ha.shape) == (c["NQ"], 100)
+    (ha * _cu(c["gout"])).sum().backward()
+    _close(ha, ref["h_a"])
+    _close(h.grad, ref["dh"], msg="d_hinfo")
+    _close(q.grad, ref["dq"], msg="d_hq")
+    _close(W.grad.reshape(-1), ref["dW"], msg="dW")
+    _close(b.grad, ref["db"], msg="db")
+
+
+def test_end_to_end_training_over_albums_encoded_once():
+    """A = 2 albums encoded ONCE by two bi-LSTM encoders -> context tensor -> shared differentiable attention (NQ = 5)
+    -> question attention -> scorer loss -> backward(); every parameter gradient and hq.grad against the same graph on
+    hall.index_select(0, album) through forward()."""
+    from fvta_memexqa_amd import functional as Fn, nn
+    c = R.e2e_case()
+    A, M, w = c["A"], c["M"], 2 * c["hidden"]
+    y = torch.zeros(c["NQ"], c["C"])
+    y[torch.arange(c["NQ"]), torch.randint(0, c["C"], (c["NQ"],), generator=torch.Generator().manual_seed(11))] = 1.0
+    encs = [nn.BiLSTMEncoder(c["din"], c["hidden"], share_fw_bw=True) for _ in c["x"]]
+    att = nn.FocalAttention3D(w, simiMatrix=c["simi"], add_tanh=c["tanh"])
+    qatt = nn.QuestionAttention(w, simiMatrix=c["simi"], add_tanh=c["tanh"])
+    scorer = nn.AnswerScorer(w)
+    with torch.no_grad():
+        for enc, k, b in zip(encs, c["lstm_k"], c["lstm_b"]):
+            enc.p("fw/basic_lstm_cell/kernel").copy_(k)
+            enc.p("fw/basic_lstm_cell/bias").copy_(b)
+        for mod, W, b in ((att, c["att_W"], c["att_b"]), (qatt, c["qatt_W"], c["qatt_b"])):
+            mod.p("att_logits/W").copy_(W)
+            mod.p("att_logits/b").copy_(b)
+        scorer.p("choicelogits/W").copy_(c["out_W"])
+        scorer.p("choicelogits/b").copy_(c["out_b"])
+    mods = encs + [att, qatt, scorer]
+    qmask = (torch.arange(c["JQ"])[None, :] < c["qlen"][:, None]).cuda()
+    ones = torch.ones(c["NQ"], 1, dtype=torch.bool, device="cuda")
+    al = c["album"].cuda()
+
+    def step(shared):
+        for m in mods:
+            m.zero_grad(set_to_none=True)
+        hq = c["hq"].cuda().requires_grad_()
+        streams, masks = [], []
+        for enc, x, ln in zip(encs, c["x"], c["lens"]):
+            out, _ = enc(x.cuda(), ln.cuda())
+            streams.append(out.reshape(A, M, x.shape[1], w))
+            masks.append((torch.arange(x.shape[1])[None, :] < ln[:, None]).reshape(A, M, -1).cuda())
+        hall, hall_mask = Fn.context_tensor(streams, masks)
+        if shared:
+            g1, _ = att.forward_shared(hall, hq, c["album"], hall_mask, qmask, differentiable=True)
+        else:
+            g1, _ = att(hall.index_select(0, al), hq, hall_mask.index_select(0, al), qmask)
+        gq, _ = qatt(hq, g1[:, None, :].contiguous(), qmask, ones)
+        loss = scorer(gq, g1, c["gch"].cuda(), y.cuda())[0]
+        loss.sum().backward()
+        grads = {"hq": hq.grad.clone(), "loss": loss.detach().clone()}
+        for i, m in enumerate(mods):
+            for n, p in m.named_parameters():
+                assert p.grad is not None, (i, n)
+                grads["%d/%s" % (i, n)] = p.grad.clone()
+        return grads
+
+    each, shared = step(False), step(True)
+    assert set(each) == set(shared) and len(each) >= 2 + 2 * len(encs) + 6
+    for key in each:
+        _close(shared[key], each[key], msg=key)
+    assert float(each["0/" + next(n for n, _ in encs[0].named_parameters())].abs().max()) > 0

@@ -463,7 +463,7 @@ extern "C" int fvta_attn_shared_plan(const fvta_attn_shared_desc* d, int32_t out
   out[0] = s.G;
   out[1] = SH_R;
   out[2] = s.S;
-  out[3] = 0;
+  out[3] = s.rps;
   return FVTA_OK;
 }
 

@@ -475,7 +475,7 @@ extern "C" int fvta_attn_shared_bwd_plan(const fvta_attn_shared_desc* d, int32_t
   out[0] = b.TR;
   out[1] = b.TS;
   out[2] = SHB_CS;
-  out[3] = 0;
+  out[3] = b.tpw;
   return FVTA_OK;
 }
 

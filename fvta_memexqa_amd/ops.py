@@ -315,10 +315,11 @@ class SharedFocalAttention:
         self.work = _bytes(nb, self.dev)
 
     def plan(self):
-        """{G, rows, tsplit}: questions per group, rows per logits tile, T splits of the weighted sum (host only)"""
+        """{G, rows, tsplit, rows_per_split}: questions per group, rows per logits tile, T splits of the weighted sum and
+        the rows of one split (host only)"""
         out = (ctypes.c_int32 * 4)()
         check(self.lib.fvta_attn_shared_plan(ctypes.byref(self.desc), out), "fvta_attn_shared_plan")
-        return dict(zip(("G", "rows", "tsplit"), (int(v) for v in out[:3])))
+        return dict(zip(("G", "rows", "tsplit", "rows_per_split"), (int(v) for v in out)))
 
     def forward(self, hinfo, hmask, hq, qmask, album, W, b, want_logits=False):
         assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
@@ -337,11 +338,11 @@ class SharedFocalAttention:
         return _bytes(nb, self.dev)
 
     def bwd_plan(self):
-        """{rows, tsplit, channels}: rows per tile of the backward's row pass, T splits and channels per slice of its
-        question pass (fvta_attn_shared_bwd_plan; host only, simiMatrix 1-3)"""
+        """{rows, tsplit, channels, tiles_per_wg}: rows per tile of the backward's row pass, T splits and channels per slice
+        of its question pass, row tiles per workgroup of the row pass (fvta_attn_shared_bwd_plan; host only, simiMatrix 1-3)"""
         out = (ctypes.c_int32 * 4)()
         check(self.lib.fvta_attn_shared_bwd_plan(ctypes.byref(self.desc), out), "fvta_attn_shared_bwd_plan")
-        return dict(zip(("rows", "tsplit", "channels"), (int(v) for v in out[:3])))
+        return dict(zip(("rows", "tsplit", "channels", "tiles_per_wg"), (int(v) for v in out)))
 
     def forward_train(self, hinfo, hmask, hq, qmask, album, W, b, want_logits=False):
         """forward() -- the same bits -- that leaves in self.saved (allocated on first use) what backward() reads

@@ -152,7 +152,8 @@ int fvta_attn_bwd_tw(const fvta_attn_desc* d, const float* hinfo, const float* h
  * The logits are an exact-fp32 [rows, w] x [w, G*JP] product per group.  No floating-point atomics, fixed summation
  * order (the T splits depend on the descriptor only): two runs are bitwise equal, and a question's result does not
  * depend on which other questions are in the call.
- * fvta_attn_shared_plan (host only, launches nothing): out = {G, rows per logits tile, T splits of the weighted sum, 0}.
+ * fvta_attn_shared_plan (host only, launches nothing): out = {G, rows per logits tile, T splits of the weighted sum,
+ * rows per split of the weighted sum}; the weighted sum stages a split's softmax weights 64 rows at a time.
  * ------------------------------------------------------------------------- */
 typedef struct fvta_attn_shared_desc {
   int32_t A, NQ, K, T, JQ, w; /* A albums (context rows [A,K,T,w]), NQ questions */
@@ -185,7 +186,7 @@ int fvta_attn_shared_fwd(const fvta_attn_shared_desc* d, const float* hinfo, con
  *   the album's questions.  No floating-point atomics, fixed summation order (the sum over an album's questions runs by
  *   ascending question index): two calls are bitwise equal in all four outputs.  No host synchronisation.
  * fvta_attn_shared_bwd_plan (host only): out = {rows per tile of the row pass, T splits of the question pass, channels
- *   per slice of the question pass, 0}. */
+ *   per slice of the question pass, row tiles per workgroup of the row pass}. */
 size_t fvta_attn_shared_saved_bytes(const fvta_attn_shared_desc* d);         /* 0 bytes: see fvta_last_error */
 size_t fvta_attn_shared_bwd_workspace_bytes(const fvta_attn_shared_desc* d); /* 0 bytes: see fvta_last_error */
 int fvta_attn_shared_bwd_plan(const fvta_attn_shared_desc* d, int32_t out[4]);

@@ -9,7 +9,11 @@ gradient vanishes -- a broken question pass would pass -- and the fp32 arg-max i
 Every case must satisfy `conditions` (tests/test_attn_shared_bwd_host.py asserts them per pinned seed in fp64), so that
 the GPU test excludes nothing: the first and second valid logit over j of every valid row, and the two largest amax
 over t of every (question, k), lie more than GAP apart, and under tanh fewer than 5 % of the valid logits have
-|x| > 0.99.  SEEDS holds, per case, the first seed of `seed_candidates` that qualifies."""
+|x| > 0.99.  SEEDS holds, per case, the first seed of `seed_candidates` that qualifies.
+
+Beside the shapes that turn over T, JQ and the widths, SPECS ends with those of tests/_attn_shared_ref.py LOOP_SPECS, which
+go past one round of the plan's and the row pass's loops: `many` (A = 1500, NQ = 1284), `heavy` ([150, 0, 50] questions),
+`tiles-w64` / `-w512` / `-w2048` (two row tiles per workgroup at each thread layout of the row pass), `k17`, `k64`."""
 import torch
 
 from tests import _attn_shared_ref as R
@@ -22,11 +26,17 @@ ROW_TS = ["1", "7", "Rb-1", "Rb", "Rb+1", "63", "64", "65", "333"]
 
 def host_bwd_plan(K, T, JQ, w, A=1, NQ=1):
     """(rows per tile of the row pass, T splits of the question pass, channels per slice): host only, no GPU"""
+    p = host_bwd_plan_words(A, NQ, K, T, JQ, w)
+    return p["rows"], p["tsplit"], p["channels"]
+
+
+def host_bwd_plan_words(A, NQ, K, T, JQ, w):
+    """all four words of fvta_attn_shared_bwd_plan, named as ops.SharedFocalAttention.bwd_plan() names them"""
     import ctypes
     from fvta_memexqa_amd import _lib
     out = (ctypes.c_int32 * 4)()
     assert _lib.load().fvta_attn_shared_bwd_plan(ctypes.byref(_lib.AttnSharedDesc(A, NQ, K, T, JQ, w, 1, 0)), out) == 0
-    return int(out[0]), int(out[1]), int(out[2])
+    return dict(zip(("rows", "tsplit", "channels", "tiles_per_wg"), (int(v) for v in out)))
 
 
 def _row_T(tag, Rb):
@@ -50,6 +60,8 @@ def _specs():
     out.append(("wide2048", lambda G: [3, 2], 2, lambda Rb: 70, 30, 2048, 3, True, True))
     out.append(("single", lambda G: [1], 2, lambda Rb: 50, 10, 64, 2, True, True))
     out.append(("k6", lambda G: [2, 1], 6, lambda Rb: 50, 10, 64, 3, True, True))
+    # past one round of the plan and tile loops (tests/_attn_shared_ref.py LOOP_SPECS; `chunks` is the forward's alone)
+    out.extend(spec for spec in R.LOOP_SPECS if spec[0] not in R.FORWARD_ONLY)
     return out
 
 
@@ -94,6 +106,13 @@ SEEDS = {
     "wide2048": 6310,
     "single": 6420,
     "k6": 1610,
+    "many": 4370,
+    "heavy": 5410,
+    "tiles-w64": 8150,
+    "tiles-w512": 8612,
+    "tiles-w2048": 9151,
+    "k17": 2110,
+    "k64": 2130,
 }
 
 
@@ -113,16 +132,13 @@ def build_case(name, seed=None, parity=True):
     """parity: as tests/test_gpu_backward.py, every (album, k) and every question partly valid (the fully masked ones
     carry fvta_attn_bwd's documented deviation); parity=False leaves make_case's masks as they are."""
     counts, K, T, JQ, w, simi, tanh, masked = shape_of(name)
-    c = R.make_case(counts, K, T, JQ, w, simi, masked, SEEDS[name] if seed is None else seed)
-    c["W"] = c["W"] * (64.0 / w) ** 0.5
-    c["tanh"] = tanh
-    if masked and parity:
-        c["hm"][0, 0, :3] = True
-        if c["NQ"] > 1:
-            c["qm"][c["NQ"] - 1, :2] = True
-        c["hm"][:, :, 0] |= ~c["hm"].any(-1)            # (a short T can leave further (album, k) without a valid row)
-    c["gout"] = torch.randn(c["NQ"], w, generator=torch.Generator().manual_seed(99))
-    return c
+    return R.train_recipe(counts, K, T, JQ, w, simi, tanh, masked, SEEDS[name] if seed is None else seed, parity)
+
+
+def plans_of(c):
+    """the words of both host-only plans for case c's shape"""
+    shape = (c["A"], c["NQ"], c["K"], c["T"], c["JQ"], c["w"])
+    return R.host_plan_words(*shape), host_bwd_plan_words(*shape)
 
 
 def reference(c):

@@ -5,7 +5,7 @@ albums whose context rows [A,K,T,w] are held once, question i attending album[i]
 `grouped` is an independent restatement in the order the kernels work in: the logits of ALL questions of an album from one
 [K*T, w] x [w, nq*JQ] product, written out from att_logits/W per similarity (not through the oracle's helpers), the mask
 as a select, the two softmaxes by hand.  tests/test_attn_shared_host.py holds the two against each other on every shape
-the GPU tests use (SPECS)."""
+the GPU tests use (SPECS, and LOOP_SPECS: the shapes with many albums and many questions)."""
 import torch
 
 NEG = -1e30
@@ -68,11 +68,17 @@ CASE_IDS = ["%s-simi%d-%s" % (name, s, "masked" if m else "open") for name, s, t
 
 def host_plan(JQ, w=64):
     """(G, R) of fvta_attn_shared_plan: a host-only call, it needs the built library but no GPU"""
+    p = host_plan_words(1, 1, 1, 1, JQ, w)
+    return p["G"], p["rows"]
+
+
+def host_plan_words(A, NQ, K, T, JQ, w):
+    """all four words of fvta_attn_shared_plan for a whole shape, named as ops.SharedFocalAttention.plan() names them"""
     import ctypes
     from fvta_memexqa_amd import _lib
     out = (ctypes.c_int32 * 4)()
-    assert _lib.load().fvta_attn_shared_plan(ctypes.byref(_lib.AttnSharedDesc(1, 1, 1, 1, JQ, w, 1, 0)), out) == 0
-    return int(out[0]), int(out[1])
+    assert _lib.load().fvta_attn_shared_plan(ctypes.byref(_lib.AttnSharedDesc(A, NQ, K, T, JQ, w, 1, 0)), out) == 0
+    return dict(zip(("G", "rows", "tsplit", "rows_per_split"), (int(v) for v in out)))
 
 
 def build_case(name, simi, masked):
@@ -83,14 +89,118 @@ def build_case(name, simi, masked):
     return make_case(counts(G), K, T(R), JQ, w, simi, masked, seed)
 
 
+# ------------------------------------------------------------------ past one round of the plan and tile loops
+# Shapes tiny in T, JQ and w but NOT in what the shared context is for -- many albums, many questions -- each the smallest
+# that reaches its loop.  (name, counts(G), K, T, JQ, w, simi, tanh, masked), the tuple of tests/_attn_shared_bwd_ref.py,
+# which runs all but `chunks` through the backward as well.  loop_regime() states what each one reaches:
+#   many         A = 1500, NQ = 1284: a plan thread owns two albums and carries its running offsets across them; 21
+#                ordered batches of 64 questions; the strided counting and placing loops; ngmax clamped to NQ; one T split
+#   heavy        [150, 0, 50]: one album's cursor advanced by every ordered batch, 19 groups of one album, a 150-question
+#                row pass
+#   chunks       [2] x 120, T = 200 (forward only): the weighted sum's splits hold more than SH_CH = 64 rows and no multiple
+#                of it: a second, ragged round of its staging loop
+#   tiles-w64    A = 260, five albums with questions, T = 260: the backward's row pass walks two tiles per workgroup, the
+#                last workgroup of an (album, k) one; albums without a question walk them too
+#   tiles-w512   two tiles per workgroup where two waves share a row;  tiles-w2048  where a thread holds two float4 per row
+#   k17, k64     the backward's per-k wave loop a second and a fourth time; K at its limit of 64
+PLAN_THREADS = 1024          # SH_PLAN_NT: threads of the plan's single workgroup
+PLAN_BATCH = 64              # questions per batch of the ordered (training) plan
+WSUM_CHUNK = 64              # SH_CH: rows the weighted sum stages at a time
+
+
+def _many_counts(G):
+    return [2 * G + 1 if a % 97 == 0 else G if a % 41 == 0 else 1 if a % 2 == 0 else 0 for a in range(1500)]
+
+
+def _sparse_counts(A, at):
+    return lambda G: [at.get(a, 0) for a in range(A)]
+
+
+LOOP_SPECS = [
+    ("many", _many_counts, 1, lambda Rb: 5, 3, 64, 2, True, True),
+    ("heavy", lambda G: [150, 0, 50], 2, lambda Rb: 40, 3, 64, 3, True, True),
+    ("chunks", lambda G: [2] * 120, 3, lambda Rb: 200, 5, 64, 1, False, True),
+    ("tiles-w64", _sparse_counts(260, {0: 9, 3: 1, 7: 17, 100: 8, 259: 5}), 2, lambda Rb: 260, 4, 64, 1, False, True),
+    ("tiles-w512", _sparse_counts(40, {0: 5, 1: 1, 20: 4, 39: 2}), 2, lambda Rb: 220, 4, 512, 2, True, True),
+    ("tiles-w2048", _sparse_counts(6, {0: 3, 2: 1, 5: 3}), 2, lambda Rb: 360, 4, 2048, 3, True, False),
+    ("k17", lambda G: [3, 2], 17, lambda Rb: 9, 4, 64, 2, True, True),
+    ("k64", lambda G: [3, 2], 64, lambda Rb: 9, 4, 64, 3, True, True),
+]
+LOOP_IDS = [s[0] for s in LOOP_SPECS]
+FORWARD_ONLY = ["chunks"]
+CHUNKS_SEED = sum(map(ord, "chunks")) * 10      # no arg-max condition on a forward: the first candidate
+
+
+def train_recipe(counts, K, T, JQ, w, simi, tanh, masked, seed, parity=True):
+    """The recipe of tests/_attn_shared_bwd_ref.build_case: make_case with att_logits/W scaled by sqrt(64 / w) (the logits
+    stay clear of tanh's saturation at every width), d_h_a = randn of seed 99 and -- parity, as tests/test_gpu_backward.py --
+    every (album, k) and every question partly valid (the fully masked ones carry fvta_attn_bwd's documented deviation)."""
+    c = make_case(counts, K, T, JQ, w, simi, masked, seed)
+    c["W"] = c["W"] * (64.0 / w) ** 0.5
+    c["tanh"] = tanh
+    if masked and parity:
+        c["hm"][0, 0, :3] = True
+        if c["NQ"] > 1:
+            c["qm"][c["NQ"] - 1, :2] = True
+        c["hm"][:, :, 0] |= ~c["hm"].any(-1)            # (a short T can leave further (album, k) without a valid row)
+    c["gout"] = torch.randn(c["NQ"], w, generator=torch.Generator().manual_seed(99))
+    return c
+
+
+def loop_case(name, seed):
+    _, counts, K, T, JQ, w, simi, tanh, masked = next(s for s in LOOP_SPECS if s[0] == name)
+    return train_recipe(counts(host_plan(JQ, w)[0]), K, T(0), JQ, w, simi, tanh, masked, seed)
+
+
+def loop_regime(name, c, plan, bwd_plan=None):
+    """Asserts that case c of LOOP_SPECS reaches the code it is there for.  plan / bwd_plan: the words of
+    fvta_attn_shared_plan / fvta_attn_shared_bwd_plan for c's shape, as ops.SharedFocalAttention.plan() / bwd_plan() name
+    them (bwd_plan None: a forward-only case).  Other names pass.  A retuned constant that moves a shape out of its regime
+    fails here: then the SHAPE changes."""
+    if name not in LOOP_IDS:
+        return
+    A, NQ, K, T, G = c["A"], c["NQ"], c["K"], c["T"], plan["G"]
+    cnt = torch.bincount(c["album"], minlength=A)
+    assert c["album"].tolist() != sorted(c["album"].tolist())                          # shuffled
+    if name == "many":
+        assert A > PLAN_THREADS and NQ > PLAN_THREADS, (A, NQ)                          # albums per thread 2, strided loops
+        assert NQ // G + min(A, NQ) > NQ                                                # ngmax clamped to NQ
+        assert {0, 1, G, 2 * G + 1} == set(cnt.tolist()) and plan["tsplit"] == 1
+    elif name == "heavy":
+        assert NQ > 3 * PLAN_BATCH and int(cnt.max()) > 2 * PLAN_BATCH and int(cnt.min()) == 0
+        assert -(-int(cnt.max()) // G) >= 19, G                                         # groups of ONE album
+    elif name == "chunks":
+        rps, S = plan["rows_per_split"], plan["tsplit"]
+        last = T - (S - 1) * rps
+        assert rps > WSUM_CHUNK and rps % WSUM_CHUNK != 0, plan
+        assert S >= 2 and last > WSUM_CHUNK and last % WSUM_CHUNK != 0, (plan, last)
+    elif name.startswith("tiles-"):
+        ntb = -(-T // bwd_plan["rows"])
+        assert bwd_plan["tiles_per_wg"] >= 2, bwd_plan
+        assert int((cnt == 0).sum()) > 0 and int(cnt[0]) > 0
+        if name == "tiles-w64":
+            assert ntb % bwd_plan["tiles_per_wg"] != 0, (ntb, bwd_plan)                 # a ragged last chunk of tiles
+        assert c["w"] == int(name[len("tiles-w"):])
+    elif name in ("k17", "k64"):
+        assert K == int(name[1:])
+
+
 # ------------------------------------------------------------------ references (fp64, CPU)
 def _dd(t):
     return None if t is None else t.double()
 
 
-def reference(c, tanh):
-    """the definition: rows gathered per question, oracle.fvta_fused.attention_3d -> (h_a [NQ,w], a_logits [NQ,K,T,JQ])"""
+def reference(c, tanh, block=None):
+    """the definition: rows gathered per question, oracle.fvta_fused.attention_3d -> (h_a [NQ,w], a_logits [NQ,K,T,JQ]);
+    block: that many questions at a time (the gathered rows of all of them at once would not fit)"""
     from oracle import fvta_fused as F
+    if block is not None and block < c["NQ"]:
+        parts = []
+        for i in range(0, c["NQ"], block):
+            sub = dict(c, q=c["q"][i:i + block], album=c["album"][i:i + block],
+                       qm=None if c["qm"] is None else c["qm"][i:i + block])
+            parts.append(reference(sub, tanh))
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
     al = c["album"]
     hm = None if c["hm"] is None else c["hm"][al]
     return F.attention_3d(_dd(c["h"])[al], _dd(c["q"]), _dd(c["W"]), _dd(c["b"]), hm, c["qm"], simiMatrix=c["simi"],

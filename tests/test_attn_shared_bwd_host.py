@@ -9,6 +9,7 @@ import re
 import pytest
 
 from tests import _attn_shared_bwd_ref as B
+from tests import _attn_shared_ref as R
 from fvta_memexqa_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -104,11 +105,18 @@ def test_backward_plan_is_deterministic_and_host_only(lib):
             a, b = (ctypes.c_int32 * 4)(), (ctypes.c_int32 * 4)()
             assert lib.fvta_attn_shared_bwd_plan(ctypes.byref(d), a) == 0
             assert lib.fvta_attn_shared_bwd_plan(ctypes.byref(d), b) == 0 and tuple(a) == tuple(b)
-            rows, tsplit, chan, zero = (int(v) for v in a)
-            assert rows >= 1 and 1 <= tsplit <= T and chan >= 4 and w % chan == 0 and zero == 0
+            rows, tsplit, chan, tpw = (int(v) for v in a)
+            assert rows >= 1 and 1 <= tsplit <= T and chan >= 4 and w % chan == 0
+            assert 1 <= tpw <= -(-T // rows)                   # tiles per workgroup: at most the tiles of an (album, k)
             first = first or (rows, chan)
             assert (rows, chan) == first
     assert B.host_bwd_plan(1, 1, 1, 64)[1] == 1
+    # few tiles in all: one per workgroup; more (album, k, tile) than the row pass wants workgroups: several, and more
+    # of them as the albums grow
+    small = B.host_bwd_plan_words(5, 35, 2, 333, 10, 64)
+    assert set(small) == {"rows", "tsplit", "channels", "tiles_per_wg"} and small["tiles_per_wg"] == 1
+    grown = [B.host_bwd_plan_words(A, 35, 2, 1200, 10, 64)["tiles_per_wg"] for A in (8, 256, 1024, 4096)]
+    assert grown[0] == 1 and grown[-1] > 1 and grown == sorted(grown)
 
 
 def test_the_row_cases_stand_on_the_edges(lib):
@@ -139,6 +147,18 @@ def test_pinned_seed_meets_the_reference_conditions(lib, name):
         assert bool(c["hm"].flatten(2).any(-1).all()) and bool(c["qm"].any(-1).all())
     assert tuple(ref["dh"].shape) == tuple(c["h"].shape) and tuple(ref["dq"].shape) == tuple(c["q"].shape)
     assert float(ref["dq"].abs().max()) > 0 and float(ref["dW"].abs().max()) > 0   # the logit gradient is alive
+
+
+@pytest.mark.parametrize("name", [n for n in R.LOOP_IDS if n not in R.FORWARD_ONLY])
+def test_loop_case_seed_is_the_first_that_qualifies_and_the_shape_its_regime(lib, name):
+    """the pinned seed was not picked among the qualifying ones: every candidate before it fails the conditions; and the
+    case stands in the regime it is named for, by the words of the two host-only plans"""
+    for seed in B.seed_candidates(name)[:B.seed_candidates(name).index(B.SEEDS[name])]:
+        c = B.build_case(name, seed=seed)
+        assert not B.qualifies(c, B.reference(c)["a_logits"]), seed
+    c = B.build_case(name)
+    plan, bwd_plan = B.plans_of(c)
+    R.loop_regime(name, c, plan, bwd_plan)
 
 
 def test_the_unmodified_mix_case_keeps_its_edges(lib):

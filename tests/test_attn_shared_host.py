@@ -1,6 +1,7 @@
 """CPU-side checks of the shared-context focal attention (fvta_attn_shared_*): header and binding, descriptor size, the
 size query and its refusals, the host-only plan, argument errors as status codes, ops.check_album_index, and the two fp64
-references of tests/_attn_shared_ref.py against each other on every shape the GPU tests use.  No GPU."""
+references of tests/_attn_shared_ref.py against each other on every shape the GPU tests use, and the regime of each
+LOOP_SPECS case by the plan's words.  No GPU."""
 import ctypes
 import os
 import re
@@ -70,16 +71,23 @@ def test_plan_answers_on_the_host(lib):
     out = (ctypes.c_int32 * 4)()
     d30 = _lib.AttnSharedDesc(8, 64, 6, 1200, 30, 1024, 2, 0)
     assert lib.fvta_attn_shared_plan(ctypes.byref(d30), out) == 0
-    G, rows, tsplit, zero = (int(v) for v in out)
-    assert G >= 8 and rows >= 1 and tsplit >= 1 and zero == 0
+    G, rows, tsplit, rps = (int(v) for v in out)
+    assert G >= 8 and rows >= 1 and tsplit >= 1
     assert G * 32 <= 256 or G * 30 <= 256                       # the group's columns fit the product's N side
+    assert rps >= 1 and (tsplit - 1) * rps < 1200 <= tsplit * rps   # the splits of rps rows cover T, none of them empty
     d60 = _lib.AttnSharedDesc(8, 64, 6, 1200, 60, 1024, 2, 0)
     assert lib.fvta_attn_shared_plan(ctypes.byref(d60), out) == 0 and out[0] >= 4
     # the T splits depend on the descriptor only: the same answer twice, and never more splits than rows
     again = (ctypes.c_int32 * 4)()
     assert lib.fvta_attn_shared_plan(ctypes.byref(d60), again) == 0 and tuple(again) == tuple(out)
     d1 = _lib.AttnSharedDesc(1, 1, 1, 1, 1, 64, 1, 0)
-    assert lib.fvta_attn_shared_plan(ctypes.byref(d1), out) == 0 and out[2] == 1
+    assert lib.fvta_attn_shared_plan(ctypes.byref(d1), out) == 0 and out[2] == 1 and out[3] == 1
+    # the words by name, and over shapes: every split within T, the rows per split what ceil(T / splits) gives
+    for A, NQ, K, T in ((1, 1, 1, 1), (5, 40, 2, 50), (120, 240, 3, 200), (3, 5, 6, 333), (8, 64, 6, 1200)):
+        p = R.host_plan_words(A, NQ, K, T, 10, 64)
+        assert set(p) == {"G", "rows", "tsplit", "rows_per_split"}
+        assert (p["tsplit"] - 1) * p["rows_per_split"] < T <= p["tsplit"] * p["rows_per_split"], (T, p)
+        assert p["rows_per_split"] == -(-T // p["tsplit"]), (T, p)
     assert lib.fvta_attn_shared_plan(ctypes.byref(d30), None) == -1 and b"null pointer" in _err(lib)
     bad = _lib.AttnSharedDesc(8, 64, 6, 1200, 30, 1000, 2, 0)
     assert lib.fvta_attn_shared_plan(ctypes.byref(bad), out) == -3 and b"unsupported" in _err(lib)
@@ -118,6 +126,31 @@ def test_the_two_references_agree(lib, name, simi, tanh, masked):
     assert torch.equal(live, a2 > -1e29)
     assert torch.allclose(a1[live], a2[live], rtol=0, atol=1e-10)
     assert torch.equal(a1[~live], a2[~live])
+
+
+def _loop_case(name):
+    from tests import _attn_shared_bwd_ref as B
+    return R.loop_case(name, R.CHUNKS_SEED) if name in R.FORWARD_ONLY else B.build_case(name)
+
+
+@pytest.mark.parametrize("name", R.LOOP_IDS)
+def test_the_loop_cases_reach_their_loops_and_the_references_agree(lib, name):
+    """every case of LOOP_SPECS stands in the regime it is named for, by the plan's own words; the blocked evaluation of
+    the definition is the unblocked one, and the album-by-album restatement agrees with it"""
+    from tests import _attn_shared_bwd_ref as B
+    c = _loop_case(name)
+    plan, bwd_plan = B.plans_of(c)
+    R.loop_regime(name, c, plan, None if name in R.FORWARD_ONLY else bwd_plan)
+    assert (name in B.CASE_IDS) == (name not in R.FORWARD_ONLY)
+    ha1, a1 = R.reference(c, c["tanh"], block=100)
+    ha2, a2 = R.grouped(c, c["tanh"])
+    assert tuple(ha1.shape) == (c["NQ"], c["w"]) and tuple(a1.shape) == (c["NQ"], c["K"], c["T"], c["JQ"])
+    assert torch.allclose(ha1, ha2, rtol=0, atol=1e-10), float((ha1 - ha2).abs().max())
+    live = a1 > -1e29
+    assert torch.equal(live, a2 > -1e29) and torch.allclose(a1[live], a2[live], rtol=0, atol=1e-10)
+    if c["NQ"] <= 300:
+        ha0, a0 = R.reference(c, c["tanh"])
+        assert torch.allclose(ha0, ha1, rtol=0, atol=1e-12) and torch.allclose(a0, a1, rtol=0, atol=1e-12)
 
 
 def test_case_recipe_covers_the_edges(lib):

@@ -4,7 +4,13 @@ tests/_attn_shared_ref.py, at the tolerances of tests/test_gpu_forward.py (BASEL
 
 The shapes (tests/_attn_shared_ref.py SPECS) are the smallest that turn every loop over: groups of 1, G, G+1 and 2G+1
 questions and an album without one, row tiles at T = 1, 7, R-1, R, R+1, 333, question columns at JQ = 1, 30, 32, 33, 64,
-every width from 64 to 2048, A = NQ = 1, K = 6; G and R are read from fvta_attn_shared_plan."""
+every width from 64 to 2048, A = NQ = 1, K = 6; G and R are read from fvta_attn_shared_plan.
+
+LOOP_SPECS there goes past one round of the plan's and the weighted sum's loops, on the training recipe (W scaled by
+sqrt(64 / w), partly valid masks), each case asserting its regime through the plans' words before it launches: `many`
+A = 1500 / NQ = 1284 (two albums per plan thread, 21 ordered batches, strided loops, ngmax clamped), `heavy` [150, 0, 50]
+questions (19 groups of one album), `chunks` [2] x 120 at T = 200 (67 rows per split of the weighted sum: 64 + 3), and the
+backward's `tiles-w64` / `-w512` / `-w2048` (T = 260 / 220 / 360), `k17`, `k64`."""
 import numpy as np
 import pytest
 import torch
@@ -71,6 +77,10 @@ def test_plan_is_what_the_shapes_assume():
     from fvta_memexqa_amd import ops
     p = ops.SharedFocalAttention(5, 40, 2, 50, 10, 64, 1, False).plan()
     assert p["G"] >= 8 and (p["G"], p["rows"]) == R.host_plan(10, 64)
+    from tests import _attn_shared_bwd_ref as B
+    op = ops.SharedFocalAttention(120, 240, 3, 200, 5, 64, 1, False)           # the handle's words are the host calls'
+    assert op.plan() == R.host_plan_words(120, 240, 3, 200, 5, 64) and op.plan()["rows_per_split"] >= 1
+    assert op.bwd_plan() == B.host_bwd_plan_words(120, 240, 3, 200, 5, 64) and op.bwd_plan()["tiles_per_wg"] >= 1
     assert ops.SharedFocalAttention(2, 5, 2, 40, 33, 128, 1, False).plan()["G"] >= 4
 
 
@@ -100,9 +110,74 @@ def test_a_question_does_not_depend_on_its_company():
     assert none is None and torch.equal(ha_nol, ha_all)                        # want_logits changes no bit of h_a
 
 
+# ---- past one round of the plan and tile loops (R.LOOP_SPECS): many albums, many questions
+def _loop_case(name):
+    """a LOOP_SPECS case (the training recipe and, where the backward runs it too, its pinned seed) and its fp64 reference,
+    evaluated in blocks of questions; once per session, never written to"""
+    if name not in _REF:
+        from tests import _attn_shared_bwd_ref as B
+        c = R.loop_case(name, R.CHUNKS_SEED) if name in R.FORWARD_ONLY else B.build_case(name)
+        _REF[name] = (c, R.reference(c, c["tanh"], block=100))
+    return _REF[name]
+
+
+def _loop_op(c):
+    """a fresh handle on case c and its device arguments; the regime the case is named for is asserted here, through the
+    plans' words, before anything is launched"""
+    from fvta_memexqa_amd import ops
+    op = ops.SharedFocalAttention(c["A"], c["NQ"], c["K"], c["T"], c["JQ"], c["w"], c["simi"], c["tanh"])
+    args = (_cu(c["h"]), _cu(ops.as_mask_u8(c["hm"])), _cu(c["q"]), _cu(ops.as_mask_u8(c["qm"])),
+            ops.check_album_index(c["album"], c["A"]).cuda(), _cu(c["W"].reshape(-1)), _cu(c["b"]))
+    return op, args
+
+
+@pytest.mark.parametrize("name", R.LOOP_IDS)
+def test_loop_cases_match_the_fp64_reference(name):
+    c, (ref_ha, ref_a) = _loop_case(name)
+    op, args = _loop_op(c)
+    R.loop_regime(name, c, op.plan(), None if name in R.FORWARD_ONLY else op.bwd_plan())
+    ha, a = op.forward(*args, want_logits=True)
+    live = ref_a > -1e29
+    print("%s h_a: max |got - ref| %.3g, max |ref| %.3g" % (name, float((ha.cpu().double() - ref_ha).abs().max()),
+                                                            float(ref_ha.abs().max())))
+    print("%s a_logits: max |got - ref| over valid entries %.3g" % (name, float((a.cpu().double() - ref_a)[live].abs().max())))
+    _close(ha, ref_ha, msg="h_a")
+    _close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
+    ha_t, a_t = op.forward_train(*args, want_logits=True)        # the ordered plan: other places, the same bits
+    assert torch.equal(ha_t, ha) and torch.equal(a_t, a)
+
+
+@pytest.mark.parametrize("name", ["many", "heavy"])
+def test_loop_cases_three_forward_calls_are_bitwise_equal(name):
+    """the unordered plan's cursor atomics race across the waves of its workgroup here (NQ > 64): where a question lands
+    changes no bit"""
+    c, _ = _loop_case(name)
+    outs = []
+    for _ in range(3):
+        op, args = _loop_op(c)                                   # a fresh handle: workspace and plan anew
+        outs.append(op.forward(*args, want_logits=True))
+    for ha, a in outs[1:]:
+        assert torch.equal(ha, outs[0][0]) and torch.equal(a, outs[0][1])
+
+
+def test_many_a_question_does_not_depend_on_its_company():
+    c, _ = _loop_case("many")
+    G, _ = R.host_plan(c["JQ"], c["w"])
+    cnt = torch.bincount(c["album"], minlength=c["A"])
+    ha_all, a_all = _run(c, c["tanh"])
+    for size in (1, G, 2 * G + 1):                               # one question each of a 1-, a G- and a 2G+1-album
+        album = int((cnt == size).nonzero()[-1])
+        members = torch.nonzero(c["album"] == album).reshape(-1)
+        assert members.numel() == size
+        i = int(members[size // 2])
+        ha_one, a_one = _run(c, c["tanh"], rows=[i])
+        _close(ha_one[0], ha_all[i], rtol=2e-5, atol=2e-6, msg="alone against in company, album of %d" % size)
+        _close(a_one[0], a_all[i], rtol=2e-5, atol=2e-6)
+
+
 def test_functional_and_nn_surface():
     from fvta_memexqa_amd import functional as Fn, nn
-    c, (ref_ha, ref_a) = _case("rows4", 1, False, True)                        # w = 256, simiMatrix 1, no tanh
+    c, (ref_ha, ref_a) = _case("rows4", 1, False, True)                       # w = 256, simiMatrix 1, no tanh
     ha_ops, a_ops = _run(c, False)
     h, q, W, b = _cu(c["h"]), _cu(c["q"]), _cu(c["W"]), _cu(c["b"])
     hm, qm = _cu(c["hm"]), _cu(c["qm"])

@@ -5,7 +5,9 @@ nn.FocalAttention3D.forward_shared(differentiable=True)) against fp64 autograd o
 
 The shapes are the smallest that turn every loop over: groups of G+1, 1, 0, 2G+1 and G questions, T around the row pass's
 tile (fvta_attn_shared_bwd_plan) and across a T split of the question pass, JQ = 1, 30, 32, 33, 64, every width from 64 to
-2048, A = NQ = 1, K = 6.  The pinned seeds keep every arg-max clear in fp64 (tests/test_attn_shared_bwd_host.py); the
+2048, A = NQ = 1, K = 6; and, past one round of the plan's and the row pass's loops (tests/_attn_shared_ref.py LOOP_SPECS,
+each asserting its regime through the two plans' words): `many` A = 1500 / NQ = 1284, `heavy` [150, 0, 50] questions,
+`tiles-w64` / `-w512` / `-w2048` with two row tiles per workgroup (T = 260 / 220 / 360), `k17`, `k64`.  The pinned seeds keep every arg-max clear in fp64 (tests/test_attn_shared_bwd_host.py); the
 first test also holds the GPU's own logits to a quarter of the case's smallest gap."""
 import numpy as np
 import pytest
@@ -73,6 +75,7 @@ class _Run:
 def test_gradients_match_fp64_autograd(name):
     c, ref = _case(name)
     run = _Run(c)
+    R.loop_regime(name, c, run.op.plan(), run.op.bwd_plan())    # a LOOP_SPECS case reaches its loop, before any launch
     ha, a = run.forward_train()
     # the arg-max the backward routes through is the reference's: the GPU's logits are within a quarter of the smallest gap
     jgap, tgap, _ = B.conditions(c, ref["a_logits"])
@@ -89,6 +92,9 @@ def test_gradients_match_fp64_autograd(name):
     _close(dq, ref["dq"], msg="d_hq")
     _close(dW, ref["dW"], msg="dW")
     _close(db, ref["db"], msg="db")
+    empty = torch.bincount(c["album"], minlength=c["A"]) == 0
+    if bool(empty.any()):                                        # albums without a question: exactly zero, not the 7.0
+        assert float(dh.cpu()[empty].abs().max()) == 0.0
     dh2, dq2, dW2, db2 = run.backward(dW=dW, db=db, fill=-3.0)   # a second call: dW / db accumulate, the others do not
     _close(dW2, 2 * ref["dW"], atol=2e-5, msg="dW accumulates")
     _close(db2, 2 * ref["db"], atol=2e-5, msg="db accumulates")
@@ -150,8 +156,9 @@ def test_forward_train_has_the_bits_of_the_inference_forward(name):
     assert none is None and torch.equal(ha_n, ha_i)
 
 
-@pytest.mark.parametrize("name", ["mix-simi3-masked", "rows-T333", "cols-jq64-w512"])
+@pytest.mark.parametrize("name", ["mix-simi3-masked", "rows-T333", "cols-jq64-w512", "many", "heavy", "tiles-w64"])
 def test_three_backward_calls_are_bitwise_equal(name):
+    """`many` and `heavy`: an album's questions span several batches of the ordered plan, whose promise this is"""
     c, _ = _case(name)
     outs = []
     for _ in range(3):

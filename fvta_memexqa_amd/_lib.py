@@ -61,6 +61,10 @@ class AttnSharedDesc(Structure):
     _fields_ = [(n, c_int32) for n in ("A", "NQ", "K", "T", "JQ", "w", "simi", "add_tanh")]
 
 
+class AttnSharedTwDesc(Structure):
+    _fields_ = [("shape", AttnSharedDesc), ("warp_type", c_int32), ("window_t", c_float)]
+
+
 CTX_KMAX = 8
 
 
@@ -136,6 +140,9 @@ _SIGS = {
     "fvta_attn_shared_bwd_plan": (c_int, [POINTER(AttnSharedDesc), POINTER(c_int32)]),
     "fvta_attn_shared_fwd_train": (c_int, [POINTER(AttnSharedDesc), P, P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_attn_shared_bwd": (c_int, [POINTER(AttnSharedDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_attn_shared_tw_workspace_bytes": (c_size_t, [POINTER(AttnSharedTwDesc)]),
+    "fvta_attn_shared_energy": (c_int, [POINTER(AttnSharedTwDesc), P, P, P, P, P, P]),
+    "fvta_attn_shared_fwd_tw": (c_int, [POINTER(AttnSharedTwDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_workspace_bytes": (c_size_t, [POINTER(TimewarpDesc)]),
     "fvta_timewarp_fwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_bwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
@@ -221,7 +228,7 @@ def load():
         fn.argtypes = args
     # the descriptor structs are declared twice (include/fvta_hip.h and above): refuse a library whose layout differs
     for which, cls in list(enumerate((AttnDesc, LstmDesc, ScorerDesc, TimewarpDesc, EmbedDesc, ImgTransDesc, GuardDesc, GuardCtl))) + \
-            [(9, AttGruSeqDesc), (10, GruSeqDesc), (11, CbpDesc), (12, AttnSharedDesc)]:
+            [(9, AttGruSeqDesc), (10, GruSeqDesc), (11, CbpDesc), (12, AttnSharedDesc), (13, AttnSharedTwDesc)]:
         have, want = ctypes.sizeof(cls), lib.fvta_abi_struct_bytes(which)
         if have != want:
             raise FvtaError("%s is %d bytes here but %d in %s: rebuild the library (descriptor layouts differ)"

@@ -2,7 +2,8 @@
 // context rows once, question i reads album[i]'s.  Per question the result is fvta_attn_fwd's on the pair
 // (hinfo[album[i]], hq[i]) -- model_v2.py:210-298 -- but a row is fetched once per GROUP of up to G questions of the same
 // album instead of once per question, and the logits of a group are one [rows, w] x [w, G JP] product on the fp32 matrix
-// pipe (gemm_f32.h: v_mfma_f32_32x32x2_f32, exact fp32).  No time warp, no shadow rows.  fvta_attn_shared_fwd keeps nothing
+// pipe (gemm_f32.h: v_mfma_f32_32x32x2_f32, exact fp32).  No shadow rows; the time warp: fvta_attn_shared_fwd_tw, the TW
+// instantiations of (4) and (6), further down.  fvta_attn_shared_fwd keeps nothing
 // for a backward; fvta_attn_shared_fwd_train runs the same kernels -- the same bits -- with the ordered plan (3) and the
 // arg-max (4) compiled in, and leaves what attn_shared_bwd.hip reads in the caller-held `saved` (attn_shared_common.h).
 //
@@ -29,6 +30,7 @@
 // single wave (attn_shared_plan_kernel<true>), a function of `album` alone.
 #include "attn_shared_common.h"
 #include "gemm_f32.h"
+#include "timewarp_common.h"
 
 namespace fvta {
 
@@ -155,14 +157,21 @@ __global__ __launch_bounds__(SH_PLAN_NT) void attn_shared_plan_kernel(ShShape s,
 
 // ---- logits.  grid ngmax * K * ntile, 256 threads
 // TRAIN: also the FIRST arg-max j of every row's maximum -> jmax [NQ,K,T] (compile-time: the inference kernel is unchanged)
-template <int JT, bool TRAIN>
+// TW (compile-time too; tw_scale [NQ,T], else unused): the logits of the WARPED rows h' = s h, s = tw_scale[q,t], from the
+// rows as they are held.  The scalar goes through the bilinear form: x = s (h.Qs + Rh.h) + s^2 (R2.h^2) + ct, cosine
+// x = (h.Qn) s rsqrt(max(s^2 |h|^2, 1e-12)) -- the row pass keeps Rh.h and R2.h^2 (cosine: the raw sum h^2) apart, and
+// the scales of the tile's rows for the group's questions are staged in LDS
+template <int JT, bool TRAIN, bool TW>
 __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, ShWork wk, const float* __restrict__ hinfo,
                                                                   const uint8_t* __restrict__ hmask,
                                                                   const uint8_t* __restrict__ qmask,
-                                                                  float* __restrict__ a_logits) {
+                                                                  float* __restrict__ a_logits,
+                                                                  const float* __restrict__ tw_scale) {
   constexpr int JP = 32 * JT, G = SH_BN / JP;
   __shared__ __attribute__((aligned(16))) float smem[ShMma::LDS_FLOATS];
   __shared__ float s_rt[SH_R], s_ct[SH_BN];
+  // TW: s_rt holds Rh.h, s_r2 R2.h^2 (cosine: sum h^2); s_sc, s_s2 the factor of the product and the addend per (question, row)
+  __shared__ float s_r2[TW ? SH_R : 1], s_sc[TW ? G : 1][TW ? SH_R : 1], s_s2[TW ? G : 1][TW ? SH_R : 1];
   __shared__ int s_q[G];
   __shared__ uint8_t s_hv[SH_R], s_cv[SH_BN];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -209,15 +218,37 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
     for (int r = wave * (SH_R / 4); r < (wave + 1) * (SH_R / 4); ++r) {
       const int t = t0 + r;
       float acc = 0.f;
-      if (t < T)
-        for (int c = 4 * lane; c < w; c += 256) {
-          const f32x4 h = ld4(hbase + (size_t)t * w + c);
-          const f32x4 v = h * (ld4(Rh + c) + ld4(R2 + c) * h);
-          acc += (v[0] + v[1]) + (v[2] + v[3]);
+      if constexpr (TW) {
+        float acc2 = 0.f;
+        if (t < T)
+          for (int c = 4 * lane; c < w; c += 256) {
+            const f32x4 h = ld4(hbase + (size_t)t * w + c);
+            const f32x4 v1 = h * ld4(Rh + c), v2 = h * h * ld4(R2 + c);
+            acc += (v1[0] + v1[1]) + (v1[2] + v1[3]);
+            acc2 += (v2[0] + v2[1]) + (v2[2] + v2[3]);
+          }
+        acc = wave_sum(acc);
+        acc2 = wave_sum(acc2);
+        if (lane == 0) {
+          s_rt[r] = acc;
+          s_r2[r] = acc2;
         }
-      acc = wave_sum(acc);
-      if (lane == 0) s_rt[r] = s.simi == 4 ? rsqrtf(fmaxf(acc, 1e-12f)) : acc;
+      } else {
+        if (t < T)
+          for (int c = 4 * lane; c < w; c += 256) {
+            const f32x4 h = ld4(hbase + (size_t)t * w + c);
+            const f32x4 v = h * (ld4(Rh + c) + ld4(R2 + c) * h);
+            acc += (v[0] + v[1]) + (v[2] + v[3]);
+          }
+        acc = wave_sum(acc);
+        if (lane == 0) s_rt[r] = s.simi == 4 ? rsqrtf(fmaxf(acc, 1e-12f)) : acc;
+      }
     }
+    if constexpr (TW)  // the scales of the tile's rows, per question of the group (an empty slot, a row past T: 0)
+      for (int e = tid; e < G * SH_R; e += SH_NT) {
+        const int q = s_q[e / SH_R], t = t0 + e % SH_R;
+        s_sc[e / SH_R][e % SH_R] = (q >= 0 && t < T) ? tw_scale[(size_t)q * T + t] : 0.f;
+      }
   }
   ShMma mma;
   mma.init(tid);
@@ -234,7 +265,15 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
     ok = q >= 0;
     return Qs + (ok ? ((size_t)q * JP + c % JP) * w + kk : (size_t)0);
   };
-  gemm_mainloop(mma, sa, sb, fa, fb, 0, w, smem, tid);  // (ends on a barrier: s_rt is visible)
+  gemm_mainloop(mma, sa, sb, fa, fb, 0, w, smem, tid);  // (ends on a barrier: s_rt -- TW: s_r2, s_sc -- is visible)
+  if constexpr (TW) {  // x = sc (h.Qs + Rh.h) + sc^2 R2.h^2 + ct; cosine (Rh.h = ct = 0): x = h.Qn sc rsqrt(max(sc^2 |h|^2, 1e-12))
+    for (int e = tid; e < G * SH_R; e += SH_NT) {
+      const float sc = s_sc[e / SH_R][e % SH_R], r2 = sc * sc * s_r2[e % SH_R];
+      s_sc[e / SH_R][e % SH_R] = s.simi == 4 ? sc * rsqrtf(fmaxf(r2, 1e-12f)) : sc;
+      s_s2[e / SH_R][e % SH_R] = s.simi == 4 ? 0.f : r2;
+    }
+    __syncthreads();
+  }
   // epilogue.  A wave holds TM x TN tiles of 32 x 32: JT = 1: a question per column tile; JT = 2: one per pair of them
   const bool cosine = s.simi == 4, tanh_on = s.add_tanh && !cosine;
 #pragma unroll
@@ -249,7 +288,11 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
       for (int r = 0; r < 16; ++r) {
         const int row = mma.row_of(i, r), t = t0 + row;
         float x = mma.acc[i][jn][r];
-        x = cosine ? x * s_rt[row] : x + s_rt[row] + ctv;
+        if constexpr (TW) {
+          x = s_sc[col / JP][row] * (x + s_rt[row]) + s_s2[col / JP][row] + ctv;
+        } else {
+          x = cosine ? x * s_rt[row] : x + s_rt[row] + ctv;
+        }
         if (tanh_on) x = tanhf(x);
         const float v = (colv && s_hv[row]) ? x : FVTA_NEG;  // exp_mask: x + -1e30 is -1e30 in fp32
         if (a_logits && live && t < T) a_logits[(((size_t)q * K + k) * T + t) * JQ + j] = v;
@@ -328,8 +371,10 @@ __global__ __launch_bounds__(256) void attn_shared_softmax_kernel(ShShape s, ShW
 }
 
 // ---- weighted sums.  grid ngmax * K * S, 256 threads: thread tid owns channels 4 tid .. + 3 (+ 1024 per further CPT)
-template <int G, int CPT>
-__global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork wk, const float* __restrict__ hinfo) {
+// TW (compile-time; tw_scale [NQ,T], else unused): the sum runs over the warped rows s h: the staged weight carries s
+template <int G, int CPT, bool TW>
+__global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork wk, const float* __restrict__ hinfo,
+                                                               const float* __restrict__ tw_scale) {
   __shared__ float s_p[SH_CH][G], s_M[G], s_cf[G];
   __shared__ int s_q[G];
   const int tid = threadIdx.x;
@@ -356,7 +401,9 @@ __global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork
     __syncthreads();
     for (int e = tid; e < SH_CH * G; e += 256) {
       const int g = e / SH_CH, r = e % SH_CH, t = c0 + r, q = s_q[g];
-      s_p[r][g] = (t < te && q >= 0) ? expf(wk.amax[((size_t)q * K + k) * T + t] - s_M[g]) : 0.f;
+      float p = (t < te && q >= 0) ? expf(wk.amax[((size_t)q * K + k) * T + t] - s_M[g]) : 0.f;
+      if constexpr (TW) p = (t < te && q >= 0) ? p * tw_scale[(size_t)q * T + t] : 0.f;
+      s_p[r][g] = p;
     }
     __syncthreads();
     const int nr = min(SH_CH, te - c0);
@@ -409,6 +456,63 @@ __global__ __launch_bounds__(256) void attn_shared_merge_kernel(ShShape s, ShWor
   h_a[(size_t)q * s.w + c] = v;
 }
 
+// ---- under the time warp (fvta_attn_shared_fwd_tw).  The warp (timewarp.hip) is one scalar per (question, position):
+//   h'[q,k,t,:] = h[a,k,t,:] scale[q,t],   scale[q,t] = tanh(e[a,t] + K (s0 + WC . lq[q])) cnt(t),   a = album[q]
+//   e[a,t] = sum_k sum_c v[c] h[a,k,t,c]^2,   v = WH[:w] WC,   s0 = b_WH . WC + b_WC
+// and only e reads the rows: it belongs to the album and is computed once per album set (fvta_attn_shared_energy).
+// v[c] = sum_o WH[c][o] WC[o]: tw_vec_kernel's arithmetic (a wave per output, lane-strided, wave_sum).  grid w / 4
+__global__ __launch_bounds__(256) void attn_shared_tw_vec_kernel(int w, const float* __restrict__ WH, const float* __restrict__ WC,
+                                                                 float* __restrict__ v) {
+  const int o = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (o >= w) return;
+  float acc = 0.f;
+  for (int c = lane; c < w; c += 64) acc += WH[(size_t)o * w + c] * WC[c];
+  acc = wave_sum(acc);
+  if (lane == 0) v[o] = acc;
+}
+
+// e[a,t]: a wave per (a, t), every k (masked rows included, as tw_coef_kernel), in tw_coef_kernel's order.  grid ceil(A T / 4)
+__global__ __launch_bounds__(256) void attn_shared_energy_kernel(ShShape s, const float* __restrict__ hinfo, const float* __restrict__ v,
+                                                                 float* __restrict__ energy) {
+  const int64_t pos = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (pos >= (int64_t)s.A * s.T) return;
+  const int a = (int)(pos / s.T), t = (int)(pos % s.T);
+  float acc = 0.f;
+  for (int k = 0; k < s.K; ++k) {
+    const float* row = hinfo + (((size_t)a * s.K + k) * s.T + t) * s.w;
+    for (int c = lane * 4; c < s.w; c += 256) {
+      const f32x4 h = ld4(row + c), vv = ld4(v + c);
+      const f32x4 p = h * h * vv;
+      acc += (p[0] + p[1]) + (p[2] + p[3]);
+    }
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) energy[pos] = acc;
+}
+
+// scale[q,t].  grid (NQ, ceil(T / 256)), 256 threads; every wave takes the two dot products itself (w floats each)
+__global__ __launch_bounds__(256) void attn_shared_tw_scale_kernel(ShShape s, int warp_type, int win, const float* __restrict__ energy,
+                                                                   const float* __restrict__ lq, const int* __restrict__ album,
+                                                                   const float* __restrict__ WHb, const float* __restrict__ WC,
+                                                                   const float* __restrict__ WCb, float* __restrict__ scale,
+                                                                   float* __restrict__ scale_out) {
+  const int q = blockIdx.x, lane = threadIdx.x & 63, t = blockIdx.y * 256 + threadIdx.x;
+  float s0 = 0.f, sq = 0.f;
+  for (int c = lane; c < s.w; c += 64) {
+    const float wc = WC[c];
+    s0 += WHb[c] * wc;
+    sq += lq[(size_t)q * s.w + c] * wc;
+  }
+  s0 = wave_sum(s0) + WCb[0];
+  sq = wave_sum(sq);
+  if (t >= s.T) return;
+  const int a = sh_album(album, q, s.A);
+  const float sc = tanhf(energy[(size_t)a * s.T + t] + (float)s.K * (s0 + sq)) * tw_count(t, s.T, warp_type, win);
+  scale[(size_t)q * s.T + t] = sc;
+  if (scale_out) scale_out[(size_t)q * s.T + t] = sc;
+}
+
 // 0: fine, else the status with the message set
 int fvta_attn_shared_check(const fvta_attn_shared_desc* d, const char* who) {
   FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
@@ -439,13 +543,13 @@ int fvta_attn_shared_check(const fvta_attn_shared_desc* d, const char* who) {
   return FVTA_OK;
 }
 
-template <int G>
-static void sh_launch_wsum(const ShShape& s, const ShWork& wk, const float* hinfo, hipStream_t st) {
+template <int G, bool TW>
+static void sh_launch_wsum(const ShShape& s, const ShWork& wk, const float* hinfo, const float* tw_scale, hipStream_t st) {
   const dim3 grid((unsigned)((int64_t)s.ngmax * s.K * s.S));
   if (s.w <= 1024)
-    hipLaunchKernelGGL((attn_shared_wsum_kernel<G, 1>), grid, dim3(256), 0, st, s, wk, hinfo);
+    hipLaunchKernelGGL((attn_shared_wsum_kernel<G, 1, TW>), grid, dim3(256), 0, st, s, wk, hinfo, tw_scale);
   else
-    hipLaunchKernelGGL((attn_shared_wsum_kernel<G, 2>), grid, dim3(256), 0, st, s, wk, hinfo);
+    hipLaunchKernelGGL((attn_shared_wsum_kernel<G, 2, TW>), grid, dim3(256), 0, st, s, wk, hinfo, tw_scale);
 }
 
 }  // namespace fvta
@@ -467,26 +571,30 @@ extern "C" int fvta_attn_shared_plan(const fvta_attn_shared_desc* d, int32_t out
   return FVTA_OK;
 }
 
-// the seven launches; TRAIN: the ordered plan and the arg-max, wk carved from (saved, workspace)
-template <bool TRAIN>
+// the seven launches; TRAIN: the ordered plan and the arg-max, wk carved from (saved, workspace); TW: under the time warp,
+// tw_scale [NQ,T] written by an earlier launch on the same stream
+template <bool TRAIN, bool TW = false>
 static int sh_forward(ShShape s, const ShWork& wk, const float* hinfo, const uint8_t* hmask, const float* hq, const uint8_t* qmask,
-                      const int32_t* album, const float* W, const float* b, float* h_a, float* a_logits, hipStream_t st) {
+                      const int32_t* album, const float* W, const float* b, float* h_a, float* a_logits, hipStream_t st,
+                      const float* tw_scale = nullptr, const char* who = nullptr) {
   s.use_mask = (hmask && qmask) ? 1 : 0;  // model_v2.py:233: the mask applies only when both are given
   hipLaunchKernelGGL(attn_vecs_kernel, dim3((s.w + 255) / 256), dim3(256), 0, st, W, s.w, s.simi, 0, wk.vecs);
   hipLaunchKernelGGL(attn_shared_prep_q_kernel, dim3(s.NQ, s.JP / 4), dim3(256), 0, st, s, wk, hq, b);
   hipLaunchKernelGGL(attn_shared_plan_kernel<TRAIN>, dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)album);
   const dim3 lgrid((unsigned)((int64_t)s.ngmax * s.K * s.ntile));
   if (s.JP == 32)
-    hipLaunchKernelGGL((attn_shared_logits_kernel<1, TRAIN>), lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits);
+    hipLaunchKernelGGL((attn_shared_logits_kernel<1, TRAIN, TW>), lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits,
+                       tw_scale);
   else
-    hipLaunchKernelGGL((attn_shared_logits_kernel<2, TRAIN>), lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits);
+    hipLaunchKernelGGL((attn_shared_logits_kernel<2, TRAIN, TW>), lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits,
+                       tw_scale);
   hipLaunchKernelGGL(attn_shared_softmax_kernel, dim3(s.NQ), dim3(256), 0, st, s, wk);
   if (s.G == 8)
-    sh_launch_wsum<8>(s, wk, hinfo, st);
+    sh_launch_wsum<8, TW>(s, wk, hinfo, tw_scale, st);
   else
-    sh_launch_wsum<4>(s, wk, hinfo, st);
+    sh_launch_wsum<4, TW>(s, wk, hinfo, tw_scale, st);
   hipLaunchKernelGGL(attn_shared_merge_kernel, dim3(s.NQ, (s.w + 255) / 256), dim3(256), 0, st, s, wk, h_a);
-  FVTA_CHECK_LAUNCH(TRAIN ? "attn_shared_fwd_train" : "attn_shared_fwd");
+  FVTA_CHECK_LAUNCH(who ? who : (TRAIN ? "attn_shared_fwd_train" : "attn_shared_fwd"));
   return FVTA_OK;
 }
 
@@ -526,4 +634,70 @@ extern "C" int fvta_attn_shared_fwd_train(const fvta_attn_shared_desc* d, const 
   const ShShape s = sh_shape(d);
   return sh_forward<true>(s, ShWork(s, saved, workspace), hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits,
                           (hipStream_t)stream_);
+}
+
+// ---- under the time warp.  The workspace: fvta_attn_shared_fwd's, then scale [NQ,T], then v [w] (the energy call's)
+namespace fvta {
+struct ShTwWork {
+  ShWork wk;
+  float *scale, *v;
+  size_t bytes;
+  ShTwWork(const ShShape& s, void* p) : wk(s, p) {
+    FvtaCarver c(p);
+    c.off = wk.bytes;
+    scale = c.take<float>((size_t)s.NQ * s.T);
+    v = c.take<float>((size_t)s.w);
+    bytes = c.off;
+  }
+};
+
+static int sh_check_tw(const fvta_attn_shared_tw_desc* d, const char* who) {
+  FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
+  if (int e = fvta_attn_shared_check(&d->shape, who)) return e;
+  if (d->warp_type < 1 || d->warp_type > 5) {
+    fvta_set_error("%s: time warping type not implemented (warp_type=%d)", who, d->warp_type);  // model_v2.py:341
+    return FVTA_ERR_INVALID_ARG;
+  }
+  FVTA_CHECK_ARG(d->window_t >= 0.f && d->window_t <= 1e9f, "%s: bad window_t (%g)", who, (double)d->window_t);
+  if (d->shape.T > 65535 * 256) {
+    fvta_set_error("%s: unsupported shape (T=%d): T must not exceed 65535 * 256 under the time warp", who, d->shape.T);
+    return FVTA_ERR_UNSUPPORTED;
+  }
+  return FVTA_OK;
+}
+}  // namespace fvta
+
+extern "C" size_t fvta_attn_shared_tw_workspace_bytes(const fvta_attn_shared_tw_desc* d) {
+  if (sh_check_tw(d, "attn_shared_tw_workspace_bytes") != FVTA_OK) return 0;
+  return ShTwWork(sh_shape(&d->shape), nullptr).bytes;
+}
+
+extern "C" int fvta_attn_shared_energy(const fvta_attn_shared_tw_desc* d, const float* hinfo, const float* WH_W, const float* WC_W,
+                                       float* energy, void* workspace, fvta_stream_t stream_) {
+  if (int e = sh_check_tw(d, "attn_shared_energy")) return e;
+  FVTA_CHECK_ARG(hinfo && WH_W && WC_W && energy && workspace, "attn_shared_energy: null pointer");
+  const ShShape s = sh_shape(&d->shape);
+  const ShTwWork tw(s, workspace);
+  hipStream_t st = (hipStream_t)stream_;
+  hipLaunchKernelGGL(attn_shared_tw_vec_kernel, dim3((s.w + 3) / 4), dim3(256), 0, st, s.w, WH_W, WC_W, tw.v);
+  hipLaunchKernelGGL(attn_shared_energy_kernel, dim3((unsigned)(((int64_t)s.A * s.T + 3) / 4)), dim3(256), 0, st, s, hinfo, tw.v,
+                     energy);
+  FVTA_CHECK_LAUNCH("attn_shared_energy");
+  return FVTA_OK;
+}
+
+extern "C" int fvta_attn_shared_fwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinfo, const uint8_t* hmask,
+                                       const float* energy, const float* hq, const uint8_t* qmask, const float* lq,
+                                       const int32_t* album, const float* W, const float* b, const float* WH_b, const float* WC_W,
+                                       const float* WC_b, float* h_a, float* a_logits, float* scale_out, void* workspace,
+                                       fvta_stream_t stream_) {
+  if (int e = sh_check_tw(d, "attn_shared_fwd_tw")) return e;
+  FVTA_CHECK_ARG(hinfo && energy && hq && lq && album && WH_b && WC_W && WC_b && h_a && workspace, "attn_shared_fwd_tw: null pointer");
+  FVTA_CHECK_ARG(d->shape.simi == 4 || W, "attn_shared_fwd_tw: simiMatrix %d needs att_logits/W", d->shape.simi);
+  const ShShape s = sh_shape(&d->shape);
+  const ShTwWork tw(s, workspace);
+  hipStream_t st = (hipStream_t)stream_;
+  hipLaunchKernelGGL(attn_shared_tw_scale_kernel, dim3(s.NQ, (s.T + 255) / 256), dim3(256), 0, st, s, d->warp_type,
+                     (int)ceilf(d->window_t), energy, lq, (const int*)album, WH_b, WC_W, WC_b, tw.scale, scale_out);
+  return sh_forward<false, true>(s, tw.wk, hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, st, tw.scale, "attn_shared_fwd_tw");
 }

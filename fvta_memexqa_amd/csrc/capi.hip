@@ -35,6 +35,7 @@ extern "C" int64_t fvta_abi_struct_bytes(int32_t which) {
     case 10: return (int64_t)sizeof(fvta_gru_seq_desc);
     case 11: return (int64_t)sizeof(fvta_cbp_desc);
     case 12: return (int64_t)sizeof(fvta_attn_shared_desc);
+    case 13: return (int64_t)sizeof(fvta_attn_shared_tw_desc);
     default: return -1;
   }
 }

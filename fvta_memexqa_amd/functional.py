@@ -226,6 +226,86 @@ def attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask=None, hq_mask=Non
     return h_a[:, :w].contiguous(), a
 
 
+def _warp_weights(w, wp, WH_W, WC_W, WH_b=None, WC_b=None):
+    """the time warp's weights as the shared-context kernels read them: WH_W's first w rows [wp,wp], WC_W [wp], and --
+    where given -- WH_b [wp], WC_b [1], zero padded to the kernel width (exact: a zero channel adds nothing to v, s0 or
+    WC . lq)"""
+    pad = torch.nn.functional.pad
+    WH = pad(_f32(WH_W).detach().reshape(-1, w)[:w], (0, wp - w, 0, wp - w)).contiguous()
+    WC = pad(_f32(WC_W).detach().reshape(w), (0, wp - w)).contiguous()
+    WH_b = None if WH_b is None else pad(_f32(WH_b).detach().reshape(w), (0, wp - w)).contiguous()
+    WC_b = None if WC_b is None else _f32(WC_b).detach().reshape(1)
+    return WH, WC, WH_b, WC_b
+
+
+def album_energy(hinfo, WH_W, WC_W):
+    """e [A,T] = sum_k sum_c v[c] hinfo[a,k,t,c]^2, v = WH_W[:w] WC_W: the one term of the time warp's scale that reads the
+    rows (fvta_attn_shared_energy).  It belongs to the albums -- attention_3d_shared_warped_raw(energy=) takes it, and it
+    holds as long as hinfo, WH/W and WC/W do.  Forward only, detached."""
+    hinfo = _f32(hinfo).detach()
+    A, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
+    hinfo = hinfo.reshape(A, K, -1, w)
+    wp = next((c for c in SUPPORTED_W if w <= c), None)
+    if wp is None:
+        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
+    ops.require_gpu()
+    WH, WC, _, _ = _warp_weights(w, wp, WH_W, WC_W)
+    op = ops.SharedWarpedFocalAttention(A, 1, K, hinfo.shape[2], 1, wp, 1, False, 1)
+    return op.album_energy(_pad_channels(hinfo, wp), WH, WC)
+
+
+def attention_3d_shared_warped_raw(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W, WC_b, hinfo_mask=None, hq_mask=None,
+                                   simiMatrix=1, add_tanh=False, warp_type=1, window_t=3.0, energy=None):
+    """attention_3d_shared_raw under the time warp (use_time_warp without use_time_warp_att), forward only: hinfo [A,K,T,w]
+    (or [A,K,M,JX,w]) held once, hq [NQ,JQ,w], album [NQ], lq [NQ,w] the questions' last states, W / b as attention_raw,
+    the warp's weights as time_warp_raw -> (h_a [NQ,w], a_logits [NQ,K,T,JQ], scale [NQ,T]): for question i, attention_raw
+    on time_warp_raw's warp of (hinfo[album[i]], lq[i]), and that warp's scale.  No [NQ,K,T,w] tensor is built: the warp is
+    one scalar per (question, position), applied inside the kernels (fvta_attn_shared_fwd_tw).  energy [A,T]: album_energy
+    of (hinfo, WH_W, WC_W), None computes it on the spot.  With gradient mode on and an argument that requires grad it
+    raises, as attention_3d_shared_raw(differentiable=False) does."""
+    if simiMatrix not in (1, 2, 3, 4):
+        raise ValueError("similarity matrix not implemented")
+    _check_warp_type(warp_type)
+    tensors = [t for t in (hinfo, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b) if torch.is_tensor(t)]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("attention_3d_shared_warped_raw is forward-only: call it under torch.no_grad(), or use the "
+                           "per-question time_warp + attention_3d (functional.time_warp_raw / attention_raw, nn.TimeWarp / "
+                           "nn.FocalAttention3D.forward) on hinfo.index_select(0, album)")
+    hinfo, hq, lq = _f32(hinfo).detach(), _f32(hq).detach(), _f32(lq).detach()
+    A, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
+    hinfo = hinfo.reshape(A, K, -1, w)
+    T = hinfo.shape[2]
+    NQ, JQ = hq.shape[0], hq.shape[1]
+    if tuple(lq.shape) != (NQ, w):
+        raise ValueError("lq: expected the questions' last states [%d, %d], got %s" % (NQ, w, tuple(lq.shape)))
+    idx = ops.check_album_index(album, A)
+    if idx.shape[0] != NQ:
+        raise ValueError("album index: %d entries for %d questions" % (idx.shape[0], NQ))
+    if energy is not None and tuple(energy.shape) != (A, T):
+        raise ValueError("energy: expected [%d, %d], got %s" % (A, T, tuple(energy.shape)))
+    wp = next((c for c in SUPPORTED_W if w <= c), None)
+    if wp is None:
+        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
+    F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
+    if F:
+        W = _pad_channels(_f32(W).detach().reshape(F, w), wp).reshape(-1)
+        b = _f32(b).detach()
+    else:
+        W = b = None
+    dev = ops.require_gpu()
+    both = hinfo_mask is not None and hq_mask is not None                  # model_v2.py:233: only when BOTH are given
+    hm = ops.as_mask_u8(hinfo_mask.reshape(A, K, T)) if both else None
+    qm = ops.as_mask_u8(hq_mask) if both else None
+    WH, WC, WHb, WCb = _warp_weights(w, wp, WH_W, WC_W, WH_b, WC_b)
+    op = ops.SharedWarpedFocalAttention(A, NQ, K, T, JQ, wp, simiMatrix, add_tanh, warp_type, float(window_t))
+    rows = _pad_channels(hinfo, wp)
+    if energy is None:
+        energy = op.album_energy(rows, WH, WC)
+    h_a, a, scale = op.forward(rows, hm, _f32(energy).detach().contiguous(), _pad_channels(hq, wp), qm, _pad_channels(lq, wp),
+                               idx.to(dev), W, b, WHb, WC, WCb, want_logits=True, want_scale=True)
+    return h_a[:, :w].contiguous(), a, scale
+
+
 def attention_3d_shared(hinfo, hq, album, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, add_tanh=False,
                         scope=None):
     """attention_3d (model_v2.py:210-298) of NQ questions over A albums whose rows are held once, with the `att_logits`

@@ -102,13 +102,34 @@ class FocalAttention3D(_AttLogits):
         return functional.attention_raw(hinfo.reshape(N, K, -1, self.w), hq, W, b, hinfo_mask, hq_mask, self.simiMatrix,
                                         self.add_tanh, 0, tscale)
 
-    def forward_shared(self, hinfo, hq, album, hinfo_mask=None, hq_mask=None, differentiable=False):
+    def forward_shared(self, hinfo, hq, album, hinfo_mask=None, hq_mask=None, differentiable=False, time_warp=None, lq=None,
+                       energy=None):
         """forward() for NQ questions over A albums held once: hinfo [A,K,...,w], hq [NQ,JQ,w], album [NQ] in [0, A) ->
         (h_a [NQ,w], a_logits [NQ,K,T,JQ]) with this module's att_logits/{W,b} (functional.attention_3d_shared_raw).
         differentiable=False is the inference call: under gradient mode the parameters require grad and the call raises;
         use it under torch.no_grad().  differentiable=True trains over the shared rows (simiMatrix 1-3; 4 raises
-        NotImplementedError): h_a's gradient reaches hinfo [A,K,...,w], hq and the parameters, a_logits carries none."""
+        NotImplementedError): h_a's gradient reaches hinfo [A,K,...,w], hq and the parameters, a_logits carries none.
+        time_warp (an nn.TimeWarp) with lq [NQ,w], the questions' last states: the attention over the rows warped per
+        question -- forward(time_warp(hinfo[album], lq)[0], ...) -- with the rows still held once
+        (functional.attention_3d_shared_warped_raw; inference only).  Its parameters and its window buffer are used;
+        energy [A,T]: functional.album_energy of (hinfo, WH/W, WC/W) when the caller keeps it, else computed here."""
         W, b = self._wb()
+        if time_warp is None and (lq is not None or energy is not None):
+            raise ValueError("forward_shared: lq / energy belong to the time warp; pass time_warp (an nn.TimeWarp) with them")
+        if time_warp is not None:
+            if lq is None:
+                raise ValueError("forward_shared: the time warp needs lq [NQ,w], the questions' last states")
+            if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
+                raise ValueError("forward_shared: lq must be [%d, %d], got %s"
+                                 % (hq.shape[0], self.w, tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
+            if differentiable:
+                raise NotImplementedError("forward_shared: the shared-context attention under the time warp is forward-only; "
+                                          "train through time_warp(hinfo.index_select(0, album), lq) and forward()")
+            tw = time_warp
+            h_a, a, _ = functional.attention_3d_shared_warped_raw(
+                hinfo, hq, album, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), hinfo_mask, hq_mask,
+                self.simiMatrix, self.add_tanh, tw.warp_type, tw.window_t(), energy)
+            return h_a, a
         return functional.attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask, hq_mask, self.simiMatrix, self.add_tanh,
                                                   differentiable=differentiable)
 
@@ -125,17 +146,40 @@ class AlbumMemory:
         self.hall_mask = None if hall_mask is None else ops.as_mask_u8(hall_mask.detach().to(dev).reshape(A, K, -1))
         if self.hall_mask is not None and tuple(self.hall_mask.shape) != tuple(self.hall.shape[:3]):
             raise ValueError("AlbumMemory: mask %s does not match the rows %s" % (tuple(hall_mask.shape), tuple(hall.shape)))
+        self._energy = None              # (key of the time warp's weights, e [A,T]): see energy()
 
     def __len__(self):
         return self.hall.shape[0]
 
-    def attend(self, attention, hq, hq_mask, album):
+    def attend(self, attention, hq, hq_mask, album, time_warp=None, lq=None):
         """(h_a [NQ,w], a_logits [NQ,K,T,JQ]) of `attention` (an nn.FocalAttention3D) for questions hq [NQ,JQ,w] about
-        albums album [NQ]; a bad index raises ValueError before anything reaches the library."""
+        albums album [NQ]; a bad index raises ValueError before anything reaches the library.
+        time_warp (an nn.TimeWarp) with lq [NQ,w]: the attention over the rows warped per question, the rows still held
+        once.  The albums' share of the warp, the energy [A,T], is computed on first use and kept; it is recomputed when
+        WH/W or WC/W of the time warp have changed since (an in-place update, load_state_dict, another module)."""
         idx = ops.check_album_index(album, len(self))
         if idx.shape[0] != hq.shape[0]:
             raise ValueError("album index: %d entries for %d questions" % (idx.shape[0], hq.shape[0]))
-        return attention.forward_shared(self.hall, hq, idx, self.hall_mask, hq_mask)
+        if time_warp is None:
+            if lq is not None:
+                raise ValueError("attend: lq belongs to the time warp; pass time_warp (an nn.TimeWarp) with it")
+            return attention.forward_shared(self.hall, hq, idx, self.hall_mask, hq_mask)
+        if lq is None:
+            raise ValueError("attend: the time warp needs lq [NQ,w], the questions' last states")
+        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.hall.shape[-1]):
+            raise ValueError("attend: lq must be [%d, %d], got %s"
+                             % (hq.shape[0], self.hall.shape[-1], tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
+        return attention.forward_shared(self.hall, hq, idx, self.hall_mask, hq_mask, time_warp=time_warp, lq=lq,
+                                        energy=self.energy(time_warp))
+
+    def energy(self, time_warp):
+        """e [A,T] of functional.album_energy for this memory's rows and time_warp's WH/W, WC/W: kept, and recomputed when
+        either parameter is another tensor or has been written to since (its version counter)"""
+        WH, WC = time_warp.p("WH/W"), time_warp.p("WC/W")
+        key = tuple((id(t), t.data_ptr(), t._version) for t in (WH, WC))
+        if self._energy is None or self._energy[0] != key:
+            self._energy = (key, functional.album_energy(self.hall, WH, WC))
+        return self._energy[1]
 
 
 class QuestionAttention(_AttLogits):

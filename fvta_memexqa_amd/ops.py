@@ -373,6 +373,49 @@ class SharedFocalAttention:
                                             ptr(self.work_bwd), stream_ptr()), "fvta_attn_shared_bwd")
 
 
+class SharedWarpedFocalAttention:
+    """SharedFocalAttention.forward under the time warp (model_v2.py:953-1009, use_time_warp without use_time_warp_att;
+    forward only): question i gets FocalAttention's result on TimeWarp's warp of (hinfo[album[i]], lq[i]), from the rows
+    [A,K,T,w] as they are held -- the warp is one scalar per (question, position), and the only term of it that reads the
+    rows, the energy e [A,T], belongs to the album: album_energy() computes it once per album set, forward() takes it."""
+
+    def __init__(self, A, NQ, K, T, JQ, w, simi, add_tanh, warp_type, window_t=3.0):
+        self.lib = _lib.load()
+        self.dev = require_gpu()
+        self.A, self.NQ, self.K, self.T, self.JQ, self.w = int(A), int(NQ), int(K), int(T), int(JQ), int(w)
+        shape = _lib.AttnSharedDesc(self.A, self.NQ, self.K, self.T, self.JQ, self.w, int(simi), int(bool(add_tanh)))
+        self.desc = _lib.AttnSharedTwDesc(shape, int(warp_type), float(window_t))
+        nb = self.lib.fvta_attn_shared_tw_workspace_bytes(ctypes.byref(self.desc))
+        if nb == 0:                      # (a bad warp type: "time warping type not implemented", model_v2.py:341)
+            raise _lib.FvtaError("shared attention under the time warp: " + self.lib.fvta_last_error().decode())
+        self.work = _bytes(nb, self.dev)
+
+    def album_energy(self, hinfo, WH_W, WC_W):
+        """e [A,T] = sum_k sum_c (WH_W[:w] WC_W)[c] hinfo[a,k,t,c]^2 (fvta_attn_shared_energy): a function of the rows and
+        of WH/W, WC/W alone -- keep it as long as those stay what they are.  WH_W [2w,w] or its first w rows, WC_W [w]"""
+        assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w)
+        assert WH_W.numel() >= self.w * self.w and WC_W.numel() == self.w
+        energy = torch.empty(self.A, self.T, device=self.dev, dtype=torch.float32)
+        check(self.lib.fvta_attn_shared_energy(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(_f32c(WH_W)), ptr(_f32c(WC_W)),
+                                               ptr(energy), ptr(self.work), stream_ptr()), "fvta_attn_shared_energy")
+        return energy
+
+    def forward(self, hinfo, hmask, energy, hq, qmask, lq, album, W, b, WH_b, WC_W, WC_b, want_logits=False, want_scale=False):
+        """-> (h_a [NQ,w], a_logits [NQ,K,T,JQ] | None, scale [NQ,T] | None); scale is TimeWarp's, per question"""
+        assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
+        assert tuple(energy.shape) == (self.A, self.T) and tuple(lq.shape) == (self.NQ, self.w)
+        assert album.is_cuda and album.dtype == torch.int32 and album.is_contiguous() and tuple(album.shape) == (self.NQ,)
+        assert WH_b.numel() == self.w and WC_W.numel() == self.w and WC_b.numel() == 1
+        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
+        a_logits = torch.empty(self.NQ, self.K, self.T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
+        scale = torch.empty(self.NQ, self.T, device=self.dev, dtype=torch.float32) if want_scale else None
+        check(self.lib.fvta_attn_shared_fwd_tw(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(energy)),
+                                               ptr(_f32c(hq)), ptr(qmask), ptr(_f32c(lq)), ptr(album), ptr(W), ptr(b),
+                                               ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)), ptr(h_a), ptr(a_logits),
+                                               ptr(scale), ptr(self.work), stream_ptr()), "fvta_attn_shared_fwd_tw")
+        return h_a, a_logits, scale
+
+
 def linear_fwd(x, W, b, y, M, din, dout, add_tanh=False, blk=None):
     """y [M,dout] = x [M,din] W [din,dout] + b (+ tanh); blk = (rows_per_blk, blk_stride): x rows in blocks"""
     rpb, bs = blk if blk else (M, 0)

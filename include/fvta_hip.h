@@ -46,8 +46,8 @@ int fvta_version(void);
 const char* fvta_last_error(void);
 /* sizeof of a descriptor struct as the library was compiled: which = 0 fvta_attn_desc, 1 fvta_lstm_desc,
  * 2 fvta_scorer_desc, 3 fvta_timewarp_desc, 4 fvta_embed_desc, 5 fvta_imgtrans_desc, 6 fvta_guard_desc,
- * 7 fvta_guard_ctl, 9 fvta_attgru_seq_desc, 10 fvta_gru_seq_desc, 11 fvta_cbp_desc, 12 fvta_attn_shared_desc (8 stays
- * unassigned: bindings probe it as the unknown id); -1 otherwise.
+ * 7 fvta_guard_ctl, 9 fvta_attgru_seq_desc, 10 fvta_gru_seq_desc, 11 fvta_cbp_desc, 12 fvta_attn_shared_desc,
+ * 13 fvta_attn_shared_tw_desc (8 stays unassigned: bindings probe it as the unknown id); -1 otherwise.
  * A binding compares
  * its own layout with it when it loads the library (fvta_memexqa_amd/_lib.py does). */
 int64_t fvta_abi_struct_bytes(int32_t which);
@@ -142,9 +142,11 @@ int fvta_attn_bwd_tw(const fvta_attn_desc* d, const float* hinfo, const float* h
  *   kernels clamp them into [0, A) before they address anything; a binding validates them on the host
  *   (ops.check_album_index does).
  *   W, b: as fvta_attn_fwd (feature order of model_v2.py:242-254; simi 4 takes NULL).  a_logits [NQ,K,T,JQ] or NULL.
- * Not here: time_warp_att and the time warp (the warped tensor depends on the question: nothing to share), shadow rows,
- * and a backward of THIS call -- it keeps no `saved`; fvta_attn_shared_fwd_train / fvta_attn_shared_bwd below train over
- * the shared rows (simiMatrix 1-3), fvta_attn_fwd / fvta_attn_bwd per question otherwise.
+ * The time warp (use_time_warp, every warp type) is covered by fvta_attn_shared_fwd_tw further down, forward only: the
+ * warp is one scalar per (question, position), so the rows stay shared.  Not here, nor there: time_warp_att (a masked row
+ * takes the softmax where its scale is negative), shadow rows, and a backward of THIS call -- it keeps no `saved`;
+ * fvta_attn_shared_fwd_train / fvta_attn_shared_bwd below train over the shared rows (simiMatrix 1-3, no time warp),
+ * fvta_attn_fwd / fvta_attn_bwd per question otherwise.
  * Range: w in {64,128,256,512,1024,2048}, JQ 1..64, K 1..64, simi 1..4, any T, A >= 1, NQ >= 1; otherwise the size
  * query returns 0 and the calls FVTA_ERR_UNSUPPORTED / FVTA_ERR_INVALID_ARG with a message.
  * The questions are grouped by album ON THE DEVICE (counting sort, groups of at most G: 8 at JQ <= 32, 4 above), no
@@ -197,6 +199,40 @@ int fvta_attn_shared_bwd(const fvta_attn_shared_desc* d, const float* hinfo, con
                          const uint8_t* qmask, const int32_t* album, const float* W, const float* b, const float* d_h_a,
                          const void* saved, float* d_hinfo, float* d_hq, float* dW, float* db, void* workspace,
                          fvta_stream_t stream);
+
+/* fvta_attn_shared_fwd under the time warp (use_time_warp without use_time_warp_att; forward only).  The warp of
+ * model_v2.py:953-1009 (fvta_timewarp_fwd below) takes the question's last state lq, but it is one scalar per
+ * (question, position):
+ *   h'[q,k,t,:] = hinfo[a,k,t,:] scale[q,t]                               a = album[q]
+ *   scale[q,t]  = tanh(e[a,t] + K (s0 + WC . lq[q])) cnt(t)               cnt: the warp type's count, window ceil(window_t)
+ *   e[a,t]      = sum_k sum_c v[c] hinfo[a,k,t,c]^2                       v = WH[:w] WC,  s0 = b_WH . WC + b_WC
+ * Only e reads the rows, and it belongs to the album.  The scalar goes through the bilinear form of the logits and
+ * through the weighted sum, so the rows stay held once and are read twice per group as in fvta_attn_shared_fwd; no
+ * [NQ,K,T,w] tensor exists, warped or not.
+ * fvta_attn_shared_energy: energy [A,T] = e, every k summed (masked rows too, as fvta_timewarp_fwd), fixed order.  It
+ *   depends on hinfo, WH_W and WC_W alone: compute it once per album set and keep it while those stay what they are
+ *   (A T floats beside the A K T w of the rows).  WH_W [2w,w]: the first w rows are read.  NQ, JQ and simi of the
+ *   descriptor must be valid but do not enter.
+ * fvta_attn_shared_fwd_tw: h_a[i], a_logits[i] = what fvta_attn_fwd returns for (fvta_timewarp_fwd's warp_h of
+ *   (hinfo[album[i]], lq[i]), hq[i], hmask[album[i]], qmask[i]); scale_out [NQ,T] (or NULL) = that call's scale_out.
+ *   lq [NQ,w]; WH_b [w], WC_W [w], WC_b [1]; the other arguments as fvta_attn_shared_fwd.  The masks stay the albums':
+ *   a masked row is -1e30 whatever its scale.
+ * `workspace`: fvta_attn_shared_tw_workspace_bytes, for either call.  warp_type outside 1..5: FVTA_ERR_INVALID_ARG, "time
+ * warping type not implemented" (model_v2.py:341), and 0 from the size query.  No host synchronisation, no
+ * floating-point atomics: two calls are bitwise equal, and a question's numbers do not depend on the other questions. */
+typedef struct fvta_attn_shared_tw_desc {
+  fvta_attn_shared_desc shape;
+  int32_t warp_type; /* 1..5 (model_v2.py:301-341) */
+  float window_t;    /* warp_type 5: time_warp_window_t */
+} fvta_attn_shared_tw_desc; /* fvta_abi_struct_bytes(13) */
+
+size_t fvta_attn_shared_tw_workspace_bytes(const fvta_attn_shared_tw_desc* d); /* 0 bytes: see fvta_last_error */
+int fvta_attn_shared_energy(const fvta_attn_shared_tw_desc* d, const float* hinfo, const float* WH_W, const float* WC_W,
+                            float* energy, void* workspace, fvta_stream_t stream);
+int fvta_attn_shared_fwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinfo, const uint8_t* hmask, const float* energy,
+                            const float* hq, const uint8_t* qmask, const float* lq, const int32_t* album, const float* W,
+                            const float* b, const float* WH_b, const float* WC_W, const float* WC_b, float* h_a,
+                            float* a_logits, float* scale_out, void* workspace, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * bi-LSTM modality encoders: model_v2.py:652-661 (cells), 667-678 (lengths),

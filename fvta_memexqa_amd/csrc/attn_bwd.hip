@@ -12,8 +12,11 @@
 // Deviation: gradient through reduce_max goes to the FIRST arg-max
 // (TF splits exact ties) and fully masked (n,k) rows pass no gradient into the
 // masked logits.
-#include "attn_common.h"
-#include "attn_bwd_params.h"
+//
+// What the small kernels here share with attn_shared_bwd.hip -- the prep body, the slot sum, the fold body, the pieces of
+// the parameter kernel, the fp64 block sum -- is in attn_bwd_shared.h; the W mapping (attn_bwd_add_dW) and the
+// declaration of fvta_attn_check_desc in attn_common.h.
+#include "attn_bwd_shared.h"
 #include "fvta_prof.h"
 
 #ifndef FVTA_ATTN_BWD_NT_DEFAULT
@@ -25,7 +28,6 @@ namespace fvta {
 
 constexpr int BWD_CHMAX = 1024;  // rows per backward workgroup chunk (LDS sort capacity)
 
-constexpr int ATTN_BWD_JG = 8;  // question positions per workgroup of the slab fold: two per wave (four, one per wave: no faster)
 static inline __host__ __device__ int attn_bwd_jz(const AttnShape& s) { return (s.JQ + ATTN_BWD_JG - 1) / ATTN_BWD_JG; }
 
 struct AttnBwdWork {
@@ -66,51 +68,13 @@ static AttnBwdWork bwd_work_view(const AttnShape& s, void* p) {
   return v;
 }
 
-// ---- per-(n,k) scalars.  grid N, 1024 threads; a wave per k (no workgroup barrier inside the k loop; 16 waves: a stream's
-// dot product and tie count are one chain of load latencies, 10 streams per wave took 20 us at K = 40)
+// ---- per-(n,k) scalars (attn_bwd_shared.h: attn_bwd_prep_body).  grid N, 1024 threads (256 at K <= 4); a wave per k
 __global__ __launch_bounds__(1024) void attn_bwd_prep_kernel(AttnShape s, AttnSaved sv, AttnBwdWork wk,
                                                             const float* __restrict__ d_h_a) {
-  __shared__ float s_gu[64];
-  __shared__ int s_ties[64];
-  const int n = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int w = s.w, K = s.K, T = s.T;
-  const float* g = d_h_a + (size_t)n * w;
-  for (int k = wave; k < K; k += (int)(blockDim.x >> 6)) {
-    const float* u = sv.u + ((size_t)n * K + k) * w;
-    float acc = 0.f;
-    for (int c = lane; c < w; c += 64) acc += g[c] * u[c];
-    acc = wave_sum(acc);
-    const float M = sv.M[n * K + k];
-    const float* am = sv.amax + ((size_t)n * K + k) * T;
-    int ties = 0;
-    for (int t = lane; t < T; t += 64) ties += (am[t] == M) ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ties += __shfl_xor(ties, o, 64);
-    if (lane == 0) {
-      s_gu[k] = acc;
-      s_ties[k] = ties;
-    }
-  }
-  // thread k finishes stream k (one thread walked all K with three dependent global loads each: ~20 of the launch's 25 us);
-  // the mean is summed in k order by every thread from LDS
-  __shared__ float s_r[64];
-  float r = 0.f, L = 1.f;
-  int am_ = 0;
-  if (tid < K) {
-    r = sv.r[n * K + tid];
-    L = sv.L[n * K + tid];
-    am_ = sv.allmasked[n * K + tid];
-    s_r[tid] = r;
-  }
-  __syncthreads();
-  if (tid < K) {
-    float mean = 0.f;
-    for (int k = 0; k < K; ++k) mean += s_r[k] * s_gu[k];
-    wk.coef[n * K + tid] = r / L;
-    wk.gu[n * K + tid] = s_gu[tid];
-    const float ds = r * (s_gu[tid] - mean);
-    wk.dss[n * K + tid] = am_ ? 0.f : ds / (float)max(1, s_ties[tid]);
-  }
+  const size_t n = blockIdx.x, nk = n * s.K;
+  const bool allmasked = (int)threadIdx.x < s.K && sv.allmasked[nk + threadIdx.x];
+  attn_bwd_prep_body(d_h_a + n * s.w, sv.u + nk * s.w, sv.M + nk, sv.amax + nk * s.T, sv.r + nk, sv.L + nk, allmasked, s.w, s.K,
+                     s.T, wk.coef + nk, wk.gu + nk, wk.dss + nk);
 }
 
 // ---- the same scalars when every (n,k) is an attention of its own (fvta_attn_bwd_u): g = d_u[n,k], no softmax over k --
@@ -152,34 +116,22 @@ __global__ __launch_bounds__(256) void attn_bwd_prep_u_kernel(AttnShape s, AttnS
 
 // ---- db of fvta_attn_bwd_u, summed in fp64 straight from the d ct partials of the main kernel.  db is the sum of every
 // row's logit gradient, and with a gradient vector per (n,k) these are N K T terms of order 1 that cancel (exactly so per
-// list without tanh): through the fp32 folds (reduce_q's per-n sums, then the bias block of attn_bwd_params) the partial
+// list without tanh): through the fp32 folds (reduce_q's per-n sums, then the bias block of attn_bwd_params_kernel) the partial
 // sums reach ~50 at a thousand lists and leave ~2e-5 of rounding where the result is 0.  Fixed order, no atomics:
 // grid N, 256 threads -> one double per n; then one workgroup adds those in n order.
 __global__ __launch_bounds__(256) void attn_bwd_db_u_kernel(const float* __restrict__ dctp, size_t per_n,
                                                             double* __restrict__ dbn) {
-  __shared__ double s_acc[256];
   const float* p = dctp + (size_t)blockIdx.x * per_n;
   double acc = 0.0;
   for (size_t i = threadIdx.x; i < per_n; i += 256) acc += (double)p[i];
-  s_acc[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s_acc[threadIdx.x] += s_acc[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) dbn[blockIdx.x] = s_acc[0];
+  acc = attn_bwd_block_sum_f64(acc);
+  if (threadIdx.x == 0) dbn[blockIdx.x] = acc;
 }
 __global__ __launch_bounds__(256) void attn_bwd_db_u_sum_kernel(const double* __restrict__ dbn, int N, float* __restrict__ db) {
-  __shared__ double s_acc[256];
   double acc = 0.0;
   for (int n = threadIdx.x; n < N; n += 256) acc += dbn[n];
-  s_acc[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) s_acc[threadIdx.x] += s_acc[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) db[0] += (float)s_acc[0];
+  acc = attn_bwd_block_sum_f64(acc);
+  if (threadIdx.x == 0) db[0] += (float)acc;
 }
 
 struct AttnBwdArgs {
@@ -551,82 +503,26 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_main(AttnBwdArgs a) {
   }
 }
 
-// ---- fold slabs per n: d_hq and per-n parameter partials.  grid (N, ceil(w/256), ceil(JQ/8)): a block takes 8 question
-// positions x 256 channels; a lane owns 4 channels (16-byte loads), wave v the positions j_lo + v and j_lo + v + 4, and the
-// slots of a position are loaded eight at a time before they are summed in slot order (one thread per channel walking its
-// slots one dependent 4-byte load after the other: 105 us at the metric shape, 0.6 TB/s)
+// ---- fold slabs per n: d_hq and per-n parameter partials (attn_bwd_shared.h: attn_bwd_fold_body).  grid (N, ceil(w/256),
+// ceil(JQ/8)); the slots of a position are summed in slot order, eight loads in flight.  Block jz == 0 also folds the
+// d Rh / d R2 partials; a block's row of pvec holds all five vectors.
 __global__ __launch_bounds__(256) void attn_bwd_reduce_q_kernel(AttnShape s, AttnSaved sv, AttnBwdWork wk, int RH,
                                                                 const float* __restrict__ hq,
                                                                 float* __restrict__ d_hq, int accumulate) {
-  __shared__ float s_dct[64];
-  __shared__ f32x4 s_p[3][3][64];  // waves 1..3 hand their partial pU / pCq / pC2 to wave 0
-  const int n = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int c = blockIdx.y * 256 + 4 * lane;
+  const int n = blockIdx.x, jz = blockIdx.z, c = blockIdx.y * 256 + 4 * (threadIdx.x & 63);
   const int w = s.w, JP = s.JP, JQ = s.JQ;
   const int nslot = s.ng * s.bsplit * RH;
   const size_t slot0 = (size_t)n * nslot;
-  if (threadIdx.x < JP) {
-    float acc = 0.f;
-    int sl = 0;
-    for (; sl + 8 <= nslot; sl += 8) {  // eight slots in flight, summed in slot order
-      float v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = wk.dctp[(slot0 + sl + i) * JP + threadIdx.x];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc += v[i];
-    }
-    for (; sl < nslot; ++sl) acc += wk.dctp[(slot0 + sl) * JP + threadIdx.x];
-    s_dct[threadIdx.x] = acc;
-    if (blockIdx.y == 0 && blockIdx.z == 0) wk.dctn[(size_t)n * JP + threadIdx.x] = acc;
-  }
-  __syncthreads();
-  const bool live = c < w;  // (w is a multiple of 4: a lane's four channels are inside or outside together)
-  const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto ld4 = [&](const float* p) { return live ? *reinterpret_cast<const f32x4*>(p) : zero; };
-  // slots summed in slot order, eight loads in flight
+  const bool live = c < w;
   auto fold = [&](const float* base, size_t stride) {
-    f32x4 acc = zero;
-    int sl = 0;
-    for (; sl + 8 <= nslot; sl += 8) {
-      f32x4 v[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = ld4(base + (size_t)(sl + i) * stride);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) acc += v[i];
-    }
-    for (; sl < nslot; ++sl) acc += ld4(base + (size_t)sl * stride);
-    return acc;
+    return attn_bwd_slot_sum<f32x4>(nslot, [&](int sl) { return ld4_if(live, base + (size_t)sl * stride); });
   };
-  const f32x4 U = ld4(sv.vecs + VEC_U * w + c), Cq = ld4(sv.vecs + VEC_CQ * w + c), C2 = ld4(sv.vecs + VEC_C2 * w + c);
-  f32x4 pU = zero, pCq = zero, pC2 = zero;
-  const int jz = blockIdx.z, j_lo = jz * ATTN_BWD_JG, j_hi = min(JQ, j_lo + ATTN_BWD_JG);
-  for (int j = j_lo + wave; j < j_hi; j += 4) {
-    const f32x4 dQ = fold(wk.slabs + (slot0 * JP + j) * w + c, (size_t)JP * w);
-    const f32x4 qv = ld4(hq + ((size_t)n * JQ + j) * w + c);
-    const float dct = s_dct[j];
-    const f32x4 dq = U * dQ + dct * (Cq + 2.f * C2 * qv);
-    if (live) {
-      f32x4* dst = reinterpret_cast<f32x4*>(d_hq + ((size_t)n * JQ + j) * w + c);
-      *dst = accumulate != 0 ? *dst + dq : dq;
-    }
-    pU += dQ * qv;
-    pCq += dct * qv;
-    pC2 += dct * qv * qv;
-  }
-  if (wave) {
-    s_p[wave - 1][0][lane] = pU;
-    s_p[wave - 1][1][lane] = pCq;
-    s_p[wave - 1][2][lane] = pC2;
-  }
-  __syncthreads();
-  if (wave || !live) return;
-#pragma unroll
-  for (int v = 0; v < 3; ++v) {  // wave order: positions j_lo + v (+ 4) after j_lo (+ 4)
-    pU += s_p[v][0][lane];
-    pCq += s_p[v][1][lane];
-    pC2 += s_p[v][2][lane];
-  }
-  f32x4 pRh = zero, pR2 = zero;
+  f32x4 pU, pCq, pC2;
+  if (!attn_bwd_fold_body(sv.vecs, hq + (size_t)n * JQ * w, d_hq + (size_t)n * JQ * w, accumulate != 0, wk.dctp + slot0 * JP,
+                          (size_t)JP, nslot, wk.dctn + (size_t)n * JP, w, JP, JQ,
+                          [&](int j) { return fold(wk.slabs + (slot0 * JP + j) * w + c, (size_t)JP * w); }, pU, pCq, pC2))
+    return;
+  f32x4 pRh = zero4(), pR2 = zero4();
   if (jz == 0) {
     pRh = fold(wk.rowp + slot0 * 2 * w + c, (size_t)2 * w);
     pR2 = fold(wk.rowp + slot0 * 2 * w + w + c, (size_t)2 * w);
@@ -678,50 +574,20 @@ __global__ __launch_bounds__(256) void attn_bwd_cosine_q_kernel(AttnShape s, Att
   }
 }
 
-// ---- sum over n, map back to att_logits/W's layout.  grid ceil(w/64) + 1; 256 threads = 64 channels x 4 n-groups
-// (fixed summation order: bitwise reproducible)
+// ---- sum over n, map back to att_logits/W's layout (attn_bwd_shared.h: the parameter kernels' pieces).  grid ceil(w/64) + 1;
+// rows of pvec = (n, group of question positions).  db null: left to the caller (fvta_attn_bwd_u)
 __global__ __launch_bounds__(256) void attn_bwd_params_kernel(AttnShape s, AttnBwdWork wk, float* __restrict__ dW,
                                                               float* __restrict__ db) {
-  __shared__ float s_p[4][VEC_COUNT][64];
-  __shared__ float s_b[4];
-  const int tid = threadIdx.x, w = s.w;
-  if (blockIdx.x == gridDim.x - 1) {  // the bias block
-    float acc = 0.f;
-    for (int i = tid; i < s.N * s.JP; i += 256) acc += wk.dctn[i];
-    acc = wave_sum(acc);
-    if ((tid & 63) == 0) s_b[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0 && db) db[0] += (s_b[0] + s_b[1]) + (s_b[2] + s_b[3]);
+  if (blockIdx.x == gridDim.x - 1) {
+    attn_bwd_bias_block(wk.dctn, (size_t)s.N * s.JP, db);
     return;
   }
-  const int cl = tid & 63, grp = tid >> 6, c = blockIdx.x * 64 + cl;
+  const int part = threadIdx.x >> 6, c = blockIdx.x * 64 + (threadIdx.x & 63);
   float v[VEC_COUNT] = {0, 0, 0, 0, 0};
-  if (c < w) {
-    const int rows = s.N * attn_bwd_jz(s);   // rows = (n, group of question positions)
-    int n = grp;
-    for (; n + 12 < rows; n += 16) {         // four rows per round, their 20 loads in flight together; same order of sums
-      float x[4][VEC_COUNT];
+  if (c < s.w)
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int k = 0; k < VEC_COUNT; ++k) x[i][k] = wk.pvec[((size_t)(n + 4 * i) * VEC_COUNT + k) * w + c];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int k = 0; k < VEC_COUNT; ++k) v[k] += x[i][k];
-    }
-    for (; n < rows; n += 4)
-#pragma unroll
-      for (int k = 0; k < VEC_COUNT; ++k) v[k] += wk.pvec[((size_t)n * VEC_COUNT + k) * w + c];
-  }
-#pragma unroll
-  for (int k = 0; k < VEC_COUNT; ++k) s_p[grp][k][cl] = v[k];
-  __syncthreads();
-  if (grp == 0 && c < w) {
-#pragma unroll
-    for (int k = 0; k < VEC_COUNT; ++k) v[k] = (s_p[0][k][cl] + s_p[1][k][cl]) + (s_p[2][k][cl] + s_p[3][k][cl]);
-    attn_bwd_add_dW(s.simi, s.feat_order, w, c, v[VEC_U], v[VEC_RH], v[VEC_R2], v[VEC_CQ], v[VEC_C2], dW);
-  }
+    for (int k = 0; k < VEC_COUNT; ++k) v[k] = attn_bwd_sum_rows(wk.pvec, (size_t)s.N * attn_bwd_jz(s), VEC_COUNT, k, part, s.w, c);
+  attn_bwd_combine_dW(v, s.simi, s.feat_order, s.w, c, dW);
 }
 
 // ---- time_warp_att: the masked rows that carry softmax weight (see attn_pad_terms_kernel in attn_fwd.hip): their
@@ -821,7 +687,6 @@ __global__ void attn_bwd_dscale_kernel(AttnShape s, const float* __restrict__ ds
 using namespace fvta;
 
 size_t fvta_attn_bwd_workspace_bytes(const AttnShape& s) { return bwd_work_view(s, nullptr).bytes; }
-int fvta_attn_check_desc(const fvta_attn_desc* d);  // attn_fwd.hip
 
 extern "C" int fvta_attn_bwd(const fvta_attn_desc* d, const float* hinfo, const float* hq, const uint8_t* hmask,
                              const uint8_t* qmask, const float* W, const float* b, const float* d_h_a,
@@ -842,6 +707,36 @@ static int attn_bwd_nt_mode() {
     return e ? atoi(e) : FVTA_ATTN_BWD_NT_DEFAULT;
   }();
   return nt;
+}
+
+// ---- what the two entries (attn_bwd_impl: one gradient vector per n; fvta_attn_bwd_u: one per (n,k)) share on the host
+static AttnBwdArgs attn_bwd_args(const AttnShape& s, const AttnSaved& sv, const AttnBwdWork& wk, const float* hinfo,
+                                 const uint64_t* table, const float* g, float* d_hinfo, int accumulate, const float* tscale,
+                                 size_t hstride) {
+  return AttnBwdArgs{s, sv, wk, hinfo, g, d_hinfo, accumulate, tscale, hstride ? hstride : (size_t)s.T * s.w, attn_bwd_nt_mode(),
+                     reinterpret_cast<const unsigned long long*>(table)};
+}
+
+// the main kernel of one shape: ACC (d_hinfo accumulated into) is accumulate == 1
+template <int TPR, int G, int TR, bool COS, bool SH = false, bool PERK = false>
+static void attn_bwd_launch(const AttnBwdArgs& a, hipStream_t stream) {
+  const dim3 grid(a.s.bsplit, a.s.N * a.s.ng);
+  if (a.accumulate == 1) hipLaunchKernelGGL((attn_bwd_main<TPR, G, TR, COS, true, SH, PERK>), grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((attn_bwd_main<TPR, G, TR, COS, false, SH, PERK>), grid, dim3(256), 0, stream, a);
+}
+
+// before the main kernel: the slabs are zeros (a workgroup without rows writes none), and with `zero_rows` (accumulate 0 / 3)
+// so are the rows of d_hinfo the main kernel does not write -- the MASKED rows; without masks every row is valid and written
+static int attn_bwd_prologue(const fvta_attn_desc* d, const AttnShape& s, const AttnBwdWork& wk, const uint8_t* hmask,
+                             float* d_hinfo, bool zero_rows, hipStream_t stream) {
+  FVTA_CHECK_HIP(hipMemsetAsync(wk.slabs, 0, wk.slab_bytes, stream));
+  if (zero_rows && d->hinfo_stride)
+    FVTA_CHECK_HIP(hipMemset2DAsync(d_hinfo, (size_t)d->hinfo_stride * sizeof(float), 0, (size_t)s.T * s.w * sizeof(float),
+                                    (size_t)s.N, stream));
+  else if (zero_rows && s.use_mask)  // every valid row is written by the main kernel (a fully masked stream: all of its rows)
+    hipLaunchKernelGGL(attn_zero_masked_rows_kernel, dim3((unsigned)(((size_t)s.N * s.K * s.T + 3) / 4)), dim3(256), 0, stream, s,
+                       hmask, d_hinfo);
+  return FVTA_OK;
 }
 
 extern "C" int fvta_attn_bwd_tw(const fvta_attn_desc* d, const float* hinfo, const float* hq, const uint8_t* hmask,
@@ -881,64 +776,33 @@ static int attn_bwd_impl(const fvta_attn_desc* d, const float* hinfo, const uint
   AttnSaved sv = attn_saved_view(s, const_cast<void*>(saved));
   AttnBwdWork wk = bwd_work_view(s, workspace);
   const int RH = bwd_rh(s.W4);
-  FVTA_CHECK_HIP(hipMemsetAsync(wk.slabs, 0, wk.slab_bytes, stream));
   if (tscale) FVTA_CHECK_HIP(hipMemsetAsync(wk.dscr, 0, (size_t)s.N * s.K * s.T * sizeof(float), stream));
-  if (accumulate == 0 || accumulate == 3) {
-    if (d->hinfo_stride)
-      FVTA_CHECK_HIP(hipMemset2DAsync(d_hinfo, (size_t)d->hinfo_stride * sizeof(float), 0, (size_t)s.T * s.w * sizeof(float),
-                                      (size_t)s.N, stream));
-    else if (use_mask)  // every valid row is written by the main kernel (a fully masked stream: all of its rows)
-      hipLaunchKernelGGL(attn_zero_masked_rows_kernel, dim3((unsigned)(((size_t)s.N * s.K * s.T + 3) / 4)), dim3(256), 0, stream, s,
-                         hmask, d_hinfo);
-    // (no masks: every row is valid and written)
-  }
+  if (int e = attn_bwd_prologue(d, s, wk, hmask, d_hinfo, accumulate == 0 || accumulate == 3, stream)) return e;
   hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(s.N), dim3(s.K > 4 ? 1024 : 256), 0, stream, s, sv, wk, d_h_a);
-  AttnBwdArgs a;
-  a.s = s;
-  a.sv = sv;
-  a.wk = wk;
-  a.hinfo = hinfo;
-  a.table = reinterpret_cast<const unsigned long long*>(table);
-  a.d_h_a = d_h_a;
-  a.d_hinfo = d_hinfo;
-  a.accumulate = accumulate;
-  a.tscale = tscale;
-  a.hstride = d->hinfo_stride ? (size_t)d->hinfo_stride : (size_t)s.T * s.w;
-  a.nt = attn_bwd_nt_mode();
-  const dim3 grid(s.bsplit, s.N * s.ng);
+  const AttnBwdArgs a = attn_bwd_args(s, sv, wk, hinfo, table, d_h_a, d_hinfo, accumulate, tscale, (size_t)d->hinfo_stride);
   const bool prof_it = (size_t)s.N * s.K * s.T >= 65536;  // the context attention, see attn_fwd.hip
   if (prof_it) fvta_prof_begin(FVTA_PROF_ATTN_BWD_MAIN, stream);
-  if (table) {
-    if (s.w == 512) {
-      if (accumulate == 1) hipLaunchKernelGGL((attn_bwd_main<128, 1, 32, false, true, true>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((attn_bwd_main<128, 1, 32, false, false, true>), grid, dim3(256), 0, stream, a);
-    } else {
-      if (accumulate == 1) hipLaunchKernelGGL((attn_bwd_main<256, 1, 32, false, true, true>), grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((attn_bwd_main<256, 1, 32, false, false, true>), grid, dim3(256), 0, stream, a);
+  if (table) {  // shadow rows
+    if (s.w == 512) attn_bwd_launch<128, 1, 32, false, true>(a, stream);
+    else attn_bwd_launch<256, 1, 32, false, true>(a, stream);
+  } else if (s.simi == 4) {
+    switch (s.w) {
+      case 64: attn_bwd_launch<16, 1, 32, true>(a, stream); break;
+      case 128: attn_bwd_launch<32, 1, 32, true>(a, stream); break;
+      case 256: attn_bwd_launch<64, 1, 32, true>(a, stream); break;
+      case 512: attn_bwd_launch<128, 1, 32, true>(a, stream); break;
+      case 1024: attn_bwd_launch<256, 1, 16, true>(a, stream); break;  // (the cosine variant of the 32-row tile would spill)
+      case 2048: attn_bwd_launch<256, 2, 16, true>(a, stream); break;
     }
-  } else
-  switch (s.w) {
-#define FVTA_BWD_LAUNCH2(TPR, G, TR, COS)                                                                             \
-  do {                                                                                                              \
-    if (accumulate == 1) hipLaunchKernelGGL((attn_bwd_main<TPR, G, TR, COS, true>), grid, dim3(256), 0, stream, a);  \
-    else hipLaunchKernelGGL((attn_bwd_main<TPR, G, TR, COS, false>), grid, dim3(256), 0, stream, a);                 \
-  } while (0)
-#define FVTA_BWD_LAUNCH(TPR, G, TR)                                                                      \
-  do {                                                                                                   \
-    if (s.simi == 4) FVTA_BWD_LAUNCH2(TPR, G, TR, true);                                                 \
-    else FVTA_BWD_LAUNCH2(TPR, G, TR, false);                                                            \
-  } while (0)
-    case 64: FVTA_BWD_LAUNCH(16, 1, 32); break;
-    case 128: FVTA_BWD_LAUNCH(32, 1, 32); break;
-    case 256: FVTA_BWD_LAUNCH(64, 1, 32); break;
-    case 512: FVTA_BWD_LAUNCH(128, 1, 32); break;
-    case 1024:  // (the cosine variant of the 32-row tile would spill: 16 rows)
-      if (s.simi == 4) FVTA_BWD_LAUNCH2(256, 1, 16, true);
-      else FVTA_BWD_LAUNCH2(256, 1, 32, false);
-      break;
-    case 2048: FVTA_BWD_LAUNCH(256, 2, 16); break;
-#undef FVTA_BWD_LAUNCH
-#undef FVTA_BWD_LAUNCH2
+  } else {
+    switch (s.w) {
+      case 64: attn_bwd_launch<16, 1, 32, false>(a, stream); break;
+      case 128: attn_bwd_launch<32, 1, 32, false>(a, stream); break;
+      case 256: attn_bwd_launch<64, 1, 32, false>(a, stream); break;
+      case 512: attn_bwd_launch<128, 1, 32, false>(a, stream); break;
+      case 1024: attn_bwd_launch<256, 1, 32, false>(a, stream); break;
+      case 2048: attn_bwd_launch<256, 2, 16, false>(a, stream); break;
+    }
   }
   if (prof_it) fvta_prof_end(FVTA_PROF_ATTN_BWD_MAIN, 1, stream);
   FVTA_CHECK_LAUNCH("attn_bwd_main");
@@ -998,37 +862,16 @@ extern "C" int fvta_attn_bwd_u(const fvta_attn_desc* d, const float* hinfo, cons
   AttnSaved sv = attn_saved_view(s, const_cast<void*>(saved));
   AttnBwdWork wk = bwd_work_view(s, workspace);
   const int RH = bwd_rh(s.W4);
-  FVTA_CHECK_HIP(hipMemsetAsync(wk.slabs, 0, wk.slab_bytes, stream));
-  if (accumulate == 0 && use_mask)  // every valid row is written by the main kernel (a fully masked stream: all of its rows)
-    hipLaunchKernelGGL(attn_zero_masked_rows_kernel, dim3((unsigned)(((size_t)s.N * s.K * s.T + 3) / 4)), dim3(256), 0, stream, s,
-                       hmask, d_hinfo);
+  if (int e = attn_bwd_prologue(d, s, wk, hmask, d_hinfo, accumulate == 0, stream)) return e;
   hipLaunchKernelGGL(attn_bwd_prep_u_kernel, dim3((s.N * s.K + 3) / 4), dim3(256), 0, stream, s, sv, wk, hinfo, d_u);
-  AttnBwdArgs a;
-  a.s = s;
-  a.sv = sv;
-  a.wk = wk;
-  a.hinfo = hinfo;
-  a.table = nullptr;
-  a.d_h_a = d_u;
-  a.d_hinfo = d_hinfo;
-  a.accumulate = accumulate;
-  a.tscale = nullptr;
-  a.hstride = (size_t)s.T * s.w;
-  a.nt = attn_bwd_nt_mode();
-  const dim3 grid(s.bsplit, s.N * s.ng);
+  const AttnBwdArgs a = attn_bwd_args(s, sv, wk, hinfo, nullptr, d_u, d_hinfo, accumulate, nullptr, 0);
   switch (s.w) {
-#define FVTA_BWD_U_LAUNCH(TPR, G, TR)                                                                                       \
-  do {                                                                                                                    \
-    if (accumulate == 1) hipLaunchKernelGGL((attn_bwd_main<TPR, G, TR, false, true, false, true>), grid, dim3(256), 0, stream, a);  \
-    else hipLaunchKernelGGL((attn_bwd_main<TPR, G, TR, false, false, false, true>), grid, dim3(256), 0, stream, a);        \
-  } while (0)
-    case 64: FVTA_BWD_U_LAUNCH(16, 1, 32); break;
-    case 128: FVTA_BWD_U_LAUNCH(32, 1, 32); break;
-    case 256: FVTA_BWD_U_LAUNCH(64, 1, 32); break;
-    case 512: FVTA_BWD_U_LAUNCH(128, 1, 32); break;
-    case 1024: FVTA_BWD_U_LAUNCH(256, 1, 32); break;
-    case 2048: FVTA_BWD_U_LAUNCH(256, 2, 8); break;  // (16-row tiles: 24 bytes of scratch per lane, as the h_a path has)
-#undef FVTA_BWD_U_LAUNCH
+    case 64: attn_bwd_launch<16, 1, 32, false, false, true>(a, stream); break;
+    case 128: attn_bwd_launch<32, 1, 32, false, false, true>(a, stream); break;
+    case 256: attn_bwd_launch<64, 1, 32, false, false, true>(a, stream); break;
+    case 512: attn_bwd_launch<128, 1, 32, false, false, true>(a, stream); break;
+    case 1024: attn_bwd_launch<256, 1, 32, false, false, true>(a, stream); break;
+    case 2048: attn_bwd_launch<256, 2, 8, false, false, true>(a, stream); break;  // (16-row tiles: 24 bytes of scratch per lane, as the h_a path has)
   }
   FVTA_CHECK_LAUNCH("attn_bwd_main (per-stream gradient)");
   hipLaunchKernelGGL(attn_bwd_reduce_q_kernel, dim3(s.N, (s.w + 255) / 256, attn_bwd_jz(s)), dim3(256), 0, stream, s, sv, wk, RH, hq,

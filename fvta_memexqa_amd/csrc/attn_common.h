@@ -2,6 +2,9 @@
 #pragma once
 #include "fvta_common.h"
 
+// 0: the descriptor is one the attention kernels take, else the status with the message set (attn_fwd.hip)
+int fvta_attn_check_desc(const fvta_attn_desc* d);
+
 namespace fvta {
 
 // Bilinear form of the similarity logits:
@@ -73,6 +76,51 @@ __device__ __forceinline__ float tw_logit(float amax, float tscale) {
 
 // per-channel vectors of the bilinear form, float [5][w]: U, Rh, R2, Cq, C2
 enum { VEC_U = 0, VEC_RH = 1, VEC_R2 = 2, VEC_CQ = 3, VEC_C2 = 4, VEC_COUNT = 5 };
+
+#ifdef __HIPCC__
+// The one copy of the mapping between att_logits/W in its own feature order (model_v2.py:242-248, model.py:146-151) and
+// those vectors.  Forward: channel c of W -> (U, Rh, R2, Cq, C2); attn_vecs_kernel stores them, the dense backward kernels
+// (attn_dense.hip, attn_cube_bwd.hip) read W through it directly.  COS = false: the caller has refused simiMatrix 4 (both
+// dense entry points do) and compiles the cosine branch out -- with it attn_cube_bwd_kernel's instruction stream changes.
+template <bool COS = true>
+__device__ __forceinline__ void attn_vecs_of(const float* __restrict__ W, int w, int simi, int feat_order, int c, float& U,
+                                             float& Rh, float& R2, float& Cq, float& C2) {
+  U = Rh = R2 = Cq = C2 = 0.f;
+  if (simi == 1) {  // [h, q, h*q]
+    Rh = W[c]; Cq = W[w + c]; U = W[2 * w + c];
+  } else if (simi == 2) {  // v2: [h*q, (h-q)^2]; model.py: [(h-q)^2, h*q]
+    const float W1 = feat_order == 0 ? W[c] : W[w + c];
+    const float W2 = feat_order == 0 ? W[w + c] : W[c];
+    U = W1 - 2.f * W2; R2 = W2; C2 = W2;
+  } else if (!COS || simi == 3) {  // [h, q, (h-q)^2, h*q]
+    Rh = W[c]; Cq = W[w + c];
+    const float W2 = W[2 * w + c];
+    U = W[3 * w + c] - 2.f * W2; R2 = W2; C2 = W2;
+  } else {  // cosine: row "term" slot carries sum h^2 for the norm
+    U = 1.f; R2 = 1.f;
+  }
+}
+// Its inverse: the gradients of the five vectors at channel c, accumulated into dW (the cosine form has no W)
+__device__ __forceinline__ void attn_bwd_add_dW(int simi, int feat_order, int w, int c, float dU, float dRh, float dR2,
+                                                float dCq, float dC2, float* __restrict__ dW) {
+  if (simi == 1) {
+    dW[c] += dRh;
+    dW[w + c] += dCq;
+    dW[2 * w + c] += dU;
+  } else if (simi == 2) {
+    const float d1 = dU, d2 = -2.f * dU + dR2 + dC2;
+    dW[c] += feat_order == 0 ? d1 : d2;
+    dW[w + c] += feat_order == 0 ? d2 : d1;
+  } else if (simi == 3) {
+    dW[c] += dRh;
+    dW[w + c] += dCq;
+    dW[2 * w + c] += -2.f * dU + dR2 + dC2;
+    dW[3 * w + c] += dU;
+  }
+}
+// per-channel vectors from att_logits/W into vecs [5][w] (attn_fwd.hip).  grid ceil(w / 256), 256 threads
+__global__ void attn_vecs_kernel(const float* __restrict__ W, int w, int simi, int feat_order, float* __restrict__ vecs);
+#endif
 
 // "saved" buffer: forward state the backward needs (all device side)
 struct AttnSaved {

@@ -14,8 +14,9 @@
 // pre-activation is a register-tiled product (4 x 4 per thread) ahead of that walk: the workgroup reads its rows a
 // second time, right after the first (from L2 / the memory-side cache when the range fits).
 // d_hq and the parameter vectors leave every workgroup as its own slab; fixed-order folds add them up (no atomics:
-// two runs are bitwise equal).
-#include "attn_dense_shared.h"
+// two runs are bitwise equal).  The vectors come from W through attn_common.h's attn_vecs_of (no cosine branch: the entry
+// refuses simiMatrix 4); the last fold is attn_dense.hip's attn_logits_bwd_params_kernel (attn_bwd_shared.h).
+#include "attn_bwd_shared.h"
 
 namespace fvta {
 
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(256, 2) void attn_cube_bwd_kernel(const float* __re
       float acc = 0.f;
       for (int c = lane; c < w; c += 64) {
         float U, Rh, R2, Cq, C2;
-        dense_vecs(W, w, simi, feat_order, c, U, Rh, R2, Cq, C2);
+        attn_vecs_of<false>(W, w, simi, feat_order, c, U, Rh, R2, Cq, C2);
         const float qv = q[(size_t)j * w + c];
         acc += qv * (Cq + C2 * qv);
       }
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(256, 2) void attn_cube_bwd_kernel(const float* __re
         {
           const int cc = tid & 31, rb = tid >> 5;  // 8 rows of the slice per pass, this thread's channel fixed
           float U, Rh, R2, Cq, C2;
-          dense_vecs(W, w, simi, feat_order, c0 + cc, U, Rh, R2, Cq, C2);
+          attn_vecs_of<false>(W, w, simi, feat_order, c0 + cc, U, Rh, R2, Cq, C2);
 #pragma unroll
           for (int i = 0; i < XR / 8; ++i) {
             const int rr = rb + 8 * i;
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void attn_cube_bwd_kernel(const float* __re
 
   for (int c = tid; c < w; c += 256) {
     float U, Rh, R2, Cq, C2;
-    dense_vecs(W, w, simi, feat_order, c, U, Rh, R2, Cq, C2);
+    attn_vecs_of<false>(W, w, simi, feat_order, c, U, Rh, R2, Cq, C2);
     f32x2 qv[JT / 2], dq[JT / 2];  // pairs of questions: v_pk_fma_f32
 #pragma unroll
     for (int j = 0; j < JT / 2; ++j) {

@@ -9,8 +9,10 @@
 // In the reference's graphs this branch only ever runs on short row lists (the K per-stream vectors, the question's or a
 // choice's tokens: model.py:904, 967, 978), so one workgroup per batch row with the dA tile in LDS is all it takes; these
 // are not hot kernels.  Fixed summation orders throughout (bitwise reproducible).
-#include "attn_common.h"
-#include "attn_dense_shared.h"
+// The vectors U, Rh, R2, Cq, C2 are read straight from the reference's W layout through attn_common.h's attn_vecs_of (no
+// cosine branch: the entry refuses simiMatrix 4); attn_logits_bwd_params_kernel, which folds the per-n parameter partials
+// back into that layout through attn_bwd_add_dW, is defined here and declared in attn_bwd_shared.h for attn_cube_bwd.hip.
+#include "attn_bwd_shared.h"
 
 namespace fvta {
 
@@ -121,7 +123,7 @@ __global__ __launch_bounds__(256) void attn_logits_bwd_kernel(const float* __res
   __syncthreads();
   for (int c = tid; c < w; c += 256) {
     float U, Rh, R2, Cq, C2;
-    dense_vecs(W, w, simi, feat_order, c, U, Rh, R2, Cq, C2);
+    attn_vecs_of<false>(W, w, simi, feat_order, c, U, Rh, R2, Cq, C2);
     float dRh = 0.f, dR2 = 0.f, dCq = 0.f, dC2 = 0.f, dU = 0.f;
     for (int t = 0; t < T; ++t) {  // d h[t,c]
       const float hv = h[(int64_t)t * w + c];
@@ -149,6 +151,28 @@ __global__ __launch_bounds__(256) void attn_logits_bwd_kernel(const float* __res
     pv[VEC_CQ * w + c] = dCq;
     pv[VEC_C2 * w + c] = dC2;
   }
+}
+
+// fold the per-n partials in n order into dW (the reference's W layout: attn_common.h's mapping) and db.  grid
+// ceil(w/256) + 1.  Declared in attn_bwd_shared.h: attn_cube_bwd.hip ends in it as well
+__global__ __launch_bounds__(256) void attn_logits_bwd_params_kernel(const float* __restrict__ pvec, const float* __restrict__ pb,
+                                                                    float* __restrict__ dW, float* __restrict__ db, int N, int w,
+                                                                    int simi, int feat_order) {
+  if (blockIdx.x == gridDim.x - 1) {
+    if (threadIdx.x == 0) {
+      float acc = 0.f;
+      for (int n = 0; n < N; ++n) acc += pb[n];
+      db[0] += acc;
+    }
+    return;
+  }
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= w) return;
+  float v[VEC_COUNT] = {0, 0, 0, 0, 0};
+  for (int n = 0; n < N; ++n)
+#pragma unroll
+    for (int k = 0; k < VEC_COUNT; ++k) v[k] += pvec[((size_t)n * VEC_COUNT + k) * w + c];
+  attn_bwd_add_dW(simi, feat_order, w, c, v[VEC_U], v[VEC_RH], v[VEC_R2], v[VEC_CQ], v[VEC_C2], dW);
 }
 
 }  // namespace fvta

@@ -36,25 +36,13 @@ __device__ __forceinline__ void wait_vmcnt_upto(int n) {
   }
 }
 
-// ---- per-channel vectors from att_logits/W (model_v2.py:242-248, model.py:146-151)
+// ---- per-channel vectors from att_logits/W (attn_common.h: attn_vecs_of)
 __global__ void attn_vecs_kernel(const float* __restrict__ W, int w, int simi, int feat_order,
                                  float* __restrict__ vecs) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= w) return;
-  float U = 0, Rh = 0, R2 = 0, Cq = 0, C2 = 0;
-  if (simi == 1) {  // [h, q, h*q]
-    Rh = W[c]; Cq = W[w + c]; U = W[2 * w + c];
-  } else if (simi == 2) {  // v2: [h*q, (h-q)^2]; model.py: [(h-q)^2, h*q]
-    const float W1 = feat_order == 0 ? W[c] : W[w + c];
-    const float W2 = feat_order == 0 ? W[w + c] : W[c];
-    U = W1 - 2.f * W2; R2 = W2; C2 = W2;
-  } else if (simi == 3) {  // [h, q, (h-q)^2, h*q]
-    Rh = W[c]; Cq = W[w + c];
-    const float W2 = W[2 * w + c];
-    U = W[3 * w + c] - 2.f * W2; R2 = W2; C2 = W2;
-  } else {  // cosine: row "term" slot carries sum h^2 for the norm
-    U = 1.f; R2 = 1.f;
-  }
+  float U, Rh, R2, Cq, C2;
+  attn_vecs_of(W, w, simi, feat_order, c, U, Rh, R2, Cq, C2);
   vecs[VEC_U * w + c] = U;
   vecs[VEC_RH * w + c] = Rh;
   vecs[VEC_R2 * w + c] = R2;

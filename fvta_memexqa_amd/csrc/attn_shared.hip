@@ -40,9 +40,6 @@ namespace fvta {
 typedef MmaF32<1, 4, 2, 2> ShMma;
 static_assert(ShMma::BM == SH_R && ShMma::BN == SH_BN && ShMma::NT == SH_NT && ShMma::TN % 2 == 0, "tile shape");
 
-// the per-channel vectors of att_logits/W in attn_common.h's layout: attn_fwd.hip's kernel (feat_order 0 = model_v2.py's)
-__global__ void attn_vecs_kernel(const float* __restrict__ W, int w, int simi, int feat_order, float* __restrict__ vecs);
-
 // ---- question side.  grid (NQ, JP / 4), 256 threads: a wave per position j
 __global__ __launch_bounds__(256) void attn_shared_prep_q_kernel(ShShape s, ShWork wk, const float* __restrict__ hq,
                                                                  const float* __restrict__ bptr) {
@@ -578,6 +575,7 @@ static int sh_forward(ShShape s, const ShWork& wk, const float* hinfo, const uin
                       const int32_t* album, const float* W, const float* b, float* h_a, float* a_logits, hipStream_t st,
                       const float* tw_scale = nullptr, const char* who = nullptr) {
   s.use_mask = (hmask && qmask) ? 1 : 0;  // model_v2.py:233: the mask applies only when both are given
+  // attn_fwd.hip's kernel, declared in attn_common.h (feat_order 0 = model_v2.py's)
   hipLaunchKernelGGL(attn_vecs_kernel, dim3((s.w + 255) / 256), dim3(256), 0, st, W, s.w, s.simi, 0, wk.vecs);
   hipLaunchKernelGGL(attn_shared_prep_q_kernel, dim3(s.NQ, s.JP / 4), dim3(256), 0, st, s, wk, hq, b);
   hipLaunchKernelGGL(attn_shared_plan_kernel<TRAIN>, dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)album);

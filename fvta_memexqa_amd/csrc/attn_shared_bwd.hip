@@ -22,18 +22,20 @@
 //                                     regions (runs of four rows, round robin) and adds the regions in order
 //   4. attn_shared_bwd_fold_kernel    per (question, 8 positions, 256 channels): the splits in order; d_hq = U dQs +
 //                                     dct (Cq + 2 C2 q); parameter-vector partials per (question, 8 positions)
-//   5. attn_shared_bwd_params_kernel  all partials in index order -> dW / db through attn_bwd_params.h's mapping
+//   5. attn_shared_bwd_params_kernel  all partials in index order -> dW / db through attn_common.h's mapping
 // Row traffic: (2) reads each row once and writes its gradient once; (3) reads each row once per group of its album.
 // Determinism: no floating-point atomics.  The chunks, slices and splits depend on the descriptor only
 // (fvta_attn_shared_bwd_plan); the one sum whose order depends on data -- d_hinfo over an album's questions -- runs in
 // `order`, which the training plan fills by ascending question index (attn_shared.hip: attn_shared_plan_kernel<true>).
+// Kernels 1, 4 and 5 are a few lines each around attn_bwd_shared.h's prep body, fold body and parameter pieces -- the one
+// copy attn_bwd.hip runs too; the row and question passes (2, 3) are this file's own.
 #include "attn_shared_common.h"
-#include "attn_bwd_params.h"
+#include "attn_bwd_shared.h"
 
 namespace fvta {
 
 constexpr int SHB_CS = 32;            // channels per slice of the question pass
-constexpr int SHB_JG = 8;             // question positions per workgroup of the fold
+constexpr int SHB_JG = ATTN_BWD_JG;   // question positions per workgroup of the fold
 constexpr int SHB_ROW_WGS = 1024;     // about this many workgroups of the row pass (then several tiles per workgroup)
 constexpr int SHB_Q_WAVES = 1280;     // about this many waves of the question pass (5 x 32 KB of LDS per CU)
 
@@ -94,47 +96,14 @@ struct ShBwdWork {
   }
 };
 
-// ---- per-(question, k) scalars: attn_bwd_prep_kernel on the shared forward's `saved`.  grid NQ; a wave per k
+// ---- per-(question, k) scalars: attn_bwd_shared.h's prep body on the shared forward's `saved`.  grid NQ; a wave per k
 __global__ __launch_bounds__(1024) void attn_shared_bwd_prep_kernel(ShShape s, ShWork sv, ShBwdWork wk,
                                                                    const float* __restrict__ d_h_a) {
-  __shared__ float s_gu[64], s_r[64];
-  __shared__ int s_ties[64];
-  const int q = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int w = s.w, K = s.K, T = s.T;
-  const float* g = d_h_a + (size_t)q * w;
-  for (int k = wave; k < K; k += (int)(blockDim.x >> 6)) {
-    const float* u = sv.u + ((size_t)q * K + k) * w;
-    float acc = 0.f;
-    for (int c = lane; c < w; c += 64) acc += g[c] * u[c];
-    acc = wave_sum(acc);
-    const float M = sv.M[(size_t)q * K + k];
-    const float* am = sv.amax + ((size_t)q * K + k) * T;
-    int ties = 0;
-    for (int t = lane; t < T; t += 64) ties += (am[t] == M) ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ties += __shfl_xor(ties, o, 64);
-    if (lane == 0) {
-      s_gu[k] = acc;
-      s_ties[k] = ties;
-    }
-  }
-  float r = 0.f, L = 1.f, M = 0.f;
-  if (tid < K) {
-    r = sv.r[(size_t)q * K + tid];
-    L = sv.L[(size_t)q * K + tid];
-    M = sv.M[(size_t)q * K + tid];
-    s_r[tid] = r;
-  }
-  __syncthreads();
-  if (tid < K) {
-    float mean = 0.f;
-    for (int k = 0; k < K; ++k) mean += s_r[k] * s_gu[k];
-    wk.coef[(size_t)q * K + tid] = r / L;
-    wk.gu[(size_t)q * K + tid] = s_gu[tid];
-    const float ds = r * (s_gu[tid] - mean);
-    // a (question, k) without a valid (t, j) pair has M = -1e30: nothing passes into its masked logits
-    wk.dss[(size_t)q * K + tid] = M == FVTA_NEG ? 0.f : ds / (float)max(1, s_ties[tid]);
-  }
+  const size_t q = blockIdx.x, qk = q * s.K;
+  // a (question, k) without a valid (t, j) pair has M = -1e30: nothing passes into its masked logits
+  const bool allmasked = (int)threadIdx.x < s.K && sv.M[qk + threadIdx.x] == FVTA_NEG;
+  attn_bwd_prep_body(d_h_a + q * s.w, sv.u + qk * s.w, sv.M + qk, sv.amax + qk * s.T, sv.r + qk, sv.L + qk, allmasked, s.w, s.K,
+                     s.T, wk.coef + qk, wk.gu + qk, wk.dss + qk);
 }
 
 // ---- row pass.  grid A K nch, 256 threads = RH row groups x TPR threads; a thread holds RPT rows x CPT float4
@@ -343,107 +312,49 @@ __global__ __launch_bounds__(64) void attn_shared_bwd_q_kernel(ShShape s, ShBwdS
     }
 }
 
-// ---- fold.  grid (NQ, ceil(w / 256), JZ), 256 threads: a lane owns 4 channels, wave v the positions j_lo + v, j_lo + v + 4
+// ---- fold (attn_bwd_shared.h: attn_bwd_fold_body).  grid (NQ, ceil(w / 256), JZ); the question's TS splits in order
 __global__ __launch_bounds__(256) void attn_shared_bwd_fold_kernel(ShShape s, ShBwdShape bs, ShWork sv, ShBwdWork wk,
                                                                   const float* __restrict__ hq, float* __restrict__ d_hq) {
-  __shared__ float s_dct[64];
-  __shared__ f32x4 s_p[3][3][64];  // waves 1..3 hand their partial pU / pCq / pC2 to wave 0
-  const int q = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int c = blockIdx.y * 256 + 4 * lane;
+  const int q = blockIdx.x, c = blockIdx.y * 256 + 4 * (threadIdx.x & 63);
   const int w = s.w, JP = s.JP, JQ = s.JQ, TS = bs.TS;
   int slot = sv.qslot[q];
   slot = min(max(slot, 0), s.ngmax * s.G - 1);
   const int grp = slot / s.G, g = slot % s.G;
   const size_t row0 = (size_t)grp * TS * SH_BN + (size_t)g * JP;  // + ts * SH_BN + j
-  if ((int)threadIdx.x < JP) {
-    float acc = 0.f;
-    for (int ts = 0; ts < TS; ++ts) acc += wk.dctp[row0 + (size_t)ts * SH_BN + threadIdx.x];
-    s_dct[threadIdx.x] = acc;
-    if (blockIdx.y == 0 && blockIdx.z == 0) wk.dctn[(size_t)q * JP + threadIdx.x] = acc;
-  }
-  __syncthreads();
   const bool live = c < w;
-  const f32x4 zero = zero4();
-  auto ldz = [&](const float* p) { return live ? *reinterpret_cast<const f32x4*>(p) : zero; };
-  const f32x4 U = ldz(sv.vecs + VEC_U * w + c), Cq = ldz(sv.vecs + VEC_CQ * w + c), C2 = ldz(sv.vecs + VEC_C2 * w + c);
-  f32x4 pU = zero, pCq = zero, pC2 = zero;
-  const int jz = blockIdx.z, j_lo = jz * SHB_JG, j_hi = min(JQ, j_lo + SHB_JG);
-  for (int j = j_lo + wave; j < j_hi; j += 4) {
-    f32x4 dQ = zero;
-    for (int ts = 0; ts < TS; ++ts) dQ += ldz(wk.qpart + (row0 + (size_t)ts * SH_BN + j) * w + c);  // the splits in order
-    const f32x4 qv = ldz(hq + ((size_t)q * JQ + j) * w + c);
-    const float dct = s_dct[j];
-    if (live) *reinterpret_cast<f32x4*>(d_hq + ((size_t)q * JQ + j) * w + c) = U * dQ + dct * (Cq + 2.f * C2 * qv);
-    pU += dQ * qv;
-    pCq += dct * qv;
-    pC2 += dct * qv * qv;
-  }
-  if (wave) {
-    s_p[wave - 1][0][lane] = pU;
-    s_p[wave - 1][1][lane] = pCq;
-    s_p[wave - 1][2][lane] = pC2;
-  }
-  __syncthreads();
-  if (wave || !live) return;
-#pragma unroll
-  for (int v = 0; v < 3; ++v) {
-    pU += s_p[v][0][lane];
-    pCq += s_p[v][1][lane];
-    pC2 += s_p[v][2][lane];
-  }
-  float* pv = wk.pvec + ((size_t)q * bs.JZ + jz) * 3 * w;
+  f32x4 pU, pCq, pC2;
+  if (!attn_bwd_fold_body(sv.vecs, hq + (size_t)q * JQ * w, d_hq + (size_t)q * JQ * w, false, wk.dctp + row0, (size_t)SH_BN, TS,
+                          wk.dctn + (size_t)q * JP, w, JP, JQ,
+                          [&](int j) {
+                            return attn_bwd_slot_sum<f32x4>(
+                                TS, [&](int ts) { return ld4_if(live, wk.qpart + (row0 + (size_t)ts * SH_BN + j) * w + c); });
+                          },
+                          pU, pCq, pC2))
+    return;
+  float* pv = wk.pvec + ((size_t)q * bs.JZ + blockIdx.z) * 3 * w;  // (no d Rh / d R2 here: the row pass leaves them per slot)
   *reinterpret_cast<f32x4*>(pv + c) = pU;
   *reinterpret_cast<f32x4*>(pv + w + c) = pCq;
   *reinterpret_cast<f32x4*>(pv + 2 * w + c) = pC2;
 }
 
-// ---- parameters.  grid ceil(w / 64) + 1; 256 threads = 64 channels x 4 strides over the partials (fixed order)
+// ---- parameters (attn_bwd_shared.h: the parameter kernels' pieces).  grid ceil(w / 64) + 1; all partials in index order
 __global__ __launch_bounds__(256) void attn_shared_bwd_params_kernel(ShShape s, ShBwdShape bs, ShBwdWork wk,
                                                                     float* __restrict__ dW, float* __restrict__ db) {
-  __shared__ float s_p[4][VEC_COUNT][64];
-  __shared__ float s_b[4];
-  const int tid = threadIdx.x, w = s.w;
-  if (blockIdx.x == gridDim.x - 1) {  // the bias block: db += sum of every d ct
-    float acc = 0.f;
-    for (size_t i = tid; i < (size_t)s.NQ * s.JP; i += 256) acc += wk.dctn[i];
-    acc = wave_sum(acc);
-    if ((tid & 63) == 0) s_b[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) db[0] += (s_b[0] + s_b[1]) + (s_b[2] + s_b[3]);
+  if (blockIdx.x == gridDim.x - 1) {
+    attn_bwd_bias_block(wk.dctn, (size_t)s.NQ * s.JP, db);
     return;
   }
-  const int cl = tid & 63, part = tid >> 6, c = blockIdx.x * 64 + cl;
+  const int part = threadIdx.x >> 6, w = s.w, c = blockIdx.x * 64 + (threadIdx.x & 63);
   float v[VEC_COUNT] = {0, 0, 0, 0, 0};
   if (c < w) {
     const size_t qrows = (size_t)s.NQ * bs.JZ, slots = (size_t)s.A * s.K * bs.nch * bs.RH;
-    // eight rows of a stride in flight, added in index order
-    auto sum_rows = [&](const float* base, size_t rows, int per, int which) {
-      float acc = 0.f;
-      size_t i = part;
-      for (; i + 28 < rows; i += 32) {
-        float x[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = base[((i + 4 * u) * per + which) * w + c];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += x[u];
-      }
-      for (; i < rows; i += 4) acc += base[(i * per + which) * w + c];
-      return acc;
-    };
-    v[VEC_U] = sum_rows(wk.pvec, qrows, 3, 0);
-    v[VEC_CQ] = sum_rows(wk.pvec, qrows, 3, 1);
-    v[VEC_C2] = sum_rows(wk.pvec, qrows, 3, 2);
-    v[VEC_RH] = sum_rows(wk.rowp, slots, 2, 0);
-    v[VEC_R2] = sum_rows(wk.rowp, slots, 2, 1);
+    v[VEC_U] = attn_bwd_sum_rows(wk.pvec, qrows, 3, 0, part, w, c);
+    v[VEC_CQ] = attn_bwd_sum_rows(wk.pvec, qrows, 3, 1, part, w, c);
+    v[VEC_C2] = attn_bwd_sum_rows(wk.pvec, qrows, 3, 2, part, w, c);
+    v[VEC_RH] = attn_bwd_sum_rows(wk.rowp, slots, 2, 0, part, w, c);
+    v[VEC_R2] = attn_bwd_sum_rows(wk.rowp, slots, 2, 1, part, w, c);
   }
-#pragma unroll
-  for (int k = 0; k < VEC_COUNT; ++k) s_p[part][k][cl] = v[k];
-  __syncthreads();
-  if (part == 0 && c < w) {
-#pragma unroll
-    for (int k = 0; k < VEC_COUNT; ++k) v[k] = (s_p[0][k][cl] + s_p[1][k][cl]) + (s_p[2][k][cl] + s_p[3][k][cl]);
-    attn_bwd_add_dW(s.simi, 0, w, c, v[VEC_U], v[VEC_RH], v[VEC_R2], v[VEC_CQ], v[VEC_C2], dW);
-  }
+  attn_bwd_combine_dW(v, s.simi, 0, w, c, dW);
 }
 
 // 0: fine, else the status with the message set

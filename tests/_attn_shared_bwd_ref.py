@@ -13,7 +13,8 @@ over t of every (question, k), lie more than GAP apart, and under tanh fewer tha
 
 Beside the shapes that turn over T, JQ and the widths, SPECS ends with those of tests/_attn_shared_ref.py LOOP_SPECS, which
 go past one round of the plan's and the row pass's loops: `many` (A = 1500, NQ = 1284), `heavy` ([150, 0, 50] questions),
-`tiles-w64` / `-w512` / `-w2048` (two row tiles per workgroup at each thread layout of the row pass), `k17`, `k64`."""
+`tiles-w64` / `-w512` / `-w2048` (two row tiles per workgroup at each thread layout of the row pass), `k17`, `k64`,
+`splits9` (nine T splits of the question pass)."""
 import torch
 
 from tests import _attn_shared_ref as R
@@ -113,6 +114,7 @@ SEEDS = {
     "tiles-w2048": 9151,
     "k17": 2110,
     "k64": 2130,
+    "splits9": 7280,
 }
 
 

@@ -103,6 +103,8 @@ def build_case(name, simi, masked):
 #                last workgroup of an (album, k) one; albums without a question walk them too
 #   tiles-w512   two tiles per workgroup where two waves share a row;  tiles-w2048  where a thread holds two float4 per row
 #   k17, k64     the backward's per-k wave loop a second and a fourth time; K at its limit of 64
+#   splits9      [2, 1], K = 1, T = 513: the backward's question pass cuts T into nine splits, so its fold sums a question's
+#                slots as one full round of eight loads in flight and a remainder of one
 PLAN_THREADS = 1024          # SH_PLAN_NT: threads of the plan's single workgroup
 PLAN_BATCH = 64              # questions per batch of the ordered (training) plan
 WSUM_CHUNK = 64              # SH_CH: rows the weighted sum stages at a time
@@ -125,6 +127,7 @@ LOOP_SPECS = [
     ("tiles-w2048", _sparse_counts(6, {0: 3, 2: 1, 5: 3}), 2, lambda Rb: 360, 4, 2048, 3, True, False),
     ("k17", lambda G: [3, 2], 17, lambda Rb: 9, 4, 64, 2, True, True),
     ("k64", lambda G: [3, 2], 64, lambda Rb: 9, 4, 64, 3, True, True),
+    ("splits9", lambda G: [2, 1], 1, lambda Rb: 513, 4, 64, 1, False, True),
 ]
 LOOP_IDS = [s[0] for s in LOOP_SPECS]
 FORWARD_ONLY = ["chunks"]
@@ -183,6 +186,8 @@ def loop_regime(name, c, plan, bwd_plan=None):
         assert c["w"] == int(name[len("tiles-w"):])
     elif name in ("k17", "k64"):
         assert K == int(name[1:])
+    elif name == "splits9":
+        assert bwd_plan["tsplit"] >= 9 and bwd_plan["tsplit"] % 8 != 0, bwd_plan       # a full round of eight and a rest
 
 
 # ------------------------------------------------------------------ references (fp64, CPU)

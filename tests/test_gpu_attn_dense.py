@@ -1,4 +1,4 @@
-"""The reversed ("bidirect") half of the 1-D attentions (csrc/attn_dense.hip, csrc/attn_dense_shared.h) and the stand-alone
+"""The reversed ("bidirect") half of the 1-D attentions (csrc/attn_dense.hip, csrc/attn_bwd_shared.h) and the stand-alone
 helpers the fallback route chains together (csrc/elementwise.hip, fvta_softsel_bwd), at the shapes where their loops turn
 over and their LDS tiles fill up -- the other tests reach them at one small shape each (w <= 128, V * JQ <= 66).
 

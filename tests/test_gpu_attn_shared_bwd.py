@@ -7,7 +7,8 @@ The shapes are the smallest that turn every loop over: groups of G+1, 1, 0, 2G+1
 tile (fvta_attn_shared_bwd_plan) and across a T split of the question pass, JQ = 1, 30, 32, 33, 64, every width from 64 to
 2048, A = NQ = 1, K = 6; and, past one round of the plan's and the row pass's loops (tests/_attn_shared_ref.py LOOP_SPECS,
 each asserting its regime through the two plans' words): `many` A = 1500 / NQ = 1284, `heavy` [150, 0, 50] questions,
-`tiles-w64` / `-w512` / `-w2048` with two row tiles per workgroup (T = 260 / 220 / 360), `k17`, `k64`.  The pinned seeds keep every arg-max clear in fp64 (tests/test_attn_shared_bwd_host.py); the
+`tiles-w64` / `-w512` / `-w2048` with two row tiles per workgroup (T = 260 / 220 / 360), `k17`, `k64`, `splits9` (nine T
+splits of the question pass: the fold's eight-in-flight slot sum and its remainder).  The pinned seeds keep every arg-max clear in fp64 (tests/test_attn_shared_bwd_host.py); the
 first test also holds the GPU's own logits to a quarter of the case's smallest gap."""
 import numpy as np
 import pytest
@@ -156,9 +157,10 @@ def test_forward_train_has_the_bits_of_the_inference_forward(name):
     assert none is None and torch.equal(ha_n, ha_i)
 
 
-@pytest.mark.parametrize("name", ["mix-simi3-masked", "rows-T333", "cols-jq64-w512", "many", "heavy", "tiles-w64"])
+@pytest.mark.parametrize("name", ["mix-simi3-masked", "rows-T333", "cols-jq64-w512", "many", "heavy", "tiles-w64", "splits9"])
 def test_three_backward_calls_are_bitwise_equal(name):
-    """`many` and `heavy`: an album's questions span several batches of the ordered plan, whose promise this is"""
+    """`many` and `heavy`: an album's questions span several batches of the ordered plan, whose promise this is;
+    `splits9`: the fold sums nine slots per question, eight of them in flight at a time"""
     c, _ = _case(name)
     outs = []
     for _ in range(3):

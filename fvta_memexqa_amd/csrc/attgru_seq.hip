@@ -19,9 +19,6 @@
 
 namespace fvta {
 
-constexpr int SEQ_A_WAVES = 8;      // regime A: one wave per 16-unit column tile
-constexpr int SEQ_A_DP_MAX = 16 * SEQ_A_WAVES;
-
 struct SeqFwdArgs {
   int N, F, d, dp;
   const float *gate, *h0, *Wg, *Wc, *preR, *preI;
@@ -33,8 +30,7 @@ struct SeqBwdArgs {
   float *G_r, *G_c, *G_x, *d_gate, *d_h0;
 };
 
-// one element of the cell: returns h_t; r and hh come back for `saved`.  The two fused multiply-adds are spelled out: left
-// to the compiler, the training and the inference instantiation contracted (1 - g) h + g hh differently (one bit apart).
+// one element of the cell: returns h_t; r and hh come back for `saved` (the two fmafs: see "Rounding" in seq_common.h).
 // A gate of 0 returns h itself.
 __device__ __forceinline__ float seq_gate_fwd(float pre_r, float hc, float pre_i, float g, float h, float& r, float& hh) {
   r = fvta_sigmoid(pre_r);
@@ -52,7 +48,22 @@ __device__ __forceinline__ float seq_gate_bwd(float dn, float g, float r, float 
 }
 
 // ---------------------------------------------------------------- regime A
-// grid ceil(N/16), 512 threads, dynamic LDS (2 dp + 16) (dp + 2) floats
+// [Wg[d:] | Wc] into LDS for the whole launch, rows padded to dp and zero off the matrices: image[row][col] = W[row][col], or
+// its transpose (TRANSPOSED: the forward's [u][k] = W[k][u]); either way consecutive threads read along a row of W
+template <bool TRANSPOSED>
+__device__ __forceinline__ void attgru_load_w(float* Wg_l, float* Wc_l, int ld, const float* Wg, const float* Wc, int d, int dp,
+                                              int tid) {
+  for (int idx = tid; idx < dp * dp; idx += 64 * SEQ_A_WAVES) {
+    const int row = idx / dp, col = idx - row * dp, dst = TRANSPOSED ? col * ld + row : row * ld + col;
+    const bool ok = row < d && col < d;
+    const size_t src = ok ? (size_t)row * d + col : 0;
+    const float vg = Wg[(size_t)d * d + src], vc = Wc[src];
+    Wg_l[dst] = ok ? vg : 0.f;
+    Wc_l[dst] = ok ? vc : 0.f;
+  }
+}
+
+// grid ceil(N/16), 512 threads (a wave per 16-unit column tile), dynamic LDS (2 dp + 16) (dp + 2) floats
 template <bool TRAIN>
 __global__ __launch_bounds__(64 * SEQ_A_WAVES) void attgru_seq_fwd_a(SeqFwdArgs a) {
   extern __shared__ float smem[];
@@ -62,14 +73,7 @@ __global__ __launch_bounds__(64 * SEQ_A_WAVES) void attgru_seq_fwd_a(SeqFwdArgs 
   float* H_l = Wc_l + dp * ld;    // [16][ld]: h_{t-1} of the tile
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int m0 = blockIdx.x * SEQ_RT;
-  for (int idx = tid; idx < dp * dp; idx += 64 * SEQ_A_WAVES) {
-    const int k = idx / dp, u = idx - k * dp;
-    const bool ok = k < d && u < d;
-    const size_t src = ok ? (size_t)k * d + u : 0;
-    const float vg = a.Wg[(size_t)d * d + src], vc = a.Wc[src];
-    Wg_l[u * ld + k] = ok ? vg : 0.f;
-    Wc_l[u * ld + k] = ok ? vc : 0.f;
-  }
+  attgru_load_w<true>(Wg_l, Wc_l, ld, a.Wg, a.Wc, d, dp, tid);
   for (int idx = tid; idx < SEQ_RT * dp; idx += 64 * SEQ_A_WAVES) {
     const int i = idx / dp, u = idx - i * dp, n = m0 + i;
     float v = 0.f;
@@ -78,17 +82,13 @@ __global__ __launch_bounds__(64 * SEQ_A_WAVES) void attgru_seq_fwd_a(SeqFwdArgs 
   }
   __syncthreads();
   const bool active = wave * 16 < dp;
-  const int u = wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+  const auto [u, i0] = seq_lane(wave, lane);
   float h[4];
   bool ok[4];
   int64_t row[4];
+  seq_lane_rows(m0, i0, u, N, d, ok, row);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int n = m0 + i0 + r;
-    ok[r] = n < N && u < d;
-    row[r] = n < N ? n : 0;
-    h[r] = active ? H_l[(i0 + r) * ld + u] : 0.f;
-  }
+  for (int r = 0; r < 4; ++r) h[r] = active ? H_l[(i0 + r) * ld + u] : 0.f;
   for (int t = 0; t < F; ++t) {
     float pr[4], pi[4], g[4];
     int64_t sidx[4];
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(64 * SEQ_A_WAVES) void attgru_seq_fwd_a(SeqFwdArgs 
       pi[r] = a.preI[sidx[r]];
       g[r] = a.gate[row[r] * F + t];
     }
-    f32x4 acc_r = {0.f, 0.f, 0.f, 0.f}, acc_c = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc_r = zero4(), acc_c = zero4();
     if (active) seq_mma2(H_l, ld, Wg_l + wave * 16 * ld, Wc_l + wave * 16 * ld, ld, dp, lane, acc_r, acc_c);
     __syncthreads();                // every wave has read H_l
     if (active) {
@@ -119,9 +119,7 @@ __global__ __launch_bounds__(64 * SEQ_A_WAVES) void attgru_seq_fwd_a(SeqFwdArgs 
     }
     __syncthreads();
   }
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-    if (ok[r]) a.h_last[row[r] * d + u] = h[r];
+  seq_store_rows(a.h_last, h, ok, row, d, u);
 }
 
 // grid ceil(N/16), 512 threads, dynamic LDS (2 dp + 32) (dp + 2) + 128 floats
@@ -135,29 +133,18 @@ __global__ __launch_bounds__(64 * SEQ_A_WAVES) void attgru_seq_bwd_a(SeqBwdArgs 
   float* part = Tc + SEQ_RT * ld; // [waves][16]: d_gate shares
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int m0 = blockIdx.x * SEQ_RT;
-  for (int idx = tid; idx < dp * dp; idx += 64 * SEQ_A_WAVES) {
-    const int c = idx / dp, k = idx - c * dp;
-    const bool ok = c < d && k < d;
-    const size_t src = ok ? (size_t)c * d + k : 0;
-    const float vg = a.Wg[(size_t)d * d + src], vc = a.Wc[src];
-    Wg_l[c * ld + k] = ok ? vg : 0.f;
-    Wc_l[c * ld + k] = ok ? vc : 0.f;
-  }
+  attgru_load_w<false>(Wg_l, Wc_l, ld, a.Wg, a.Wc, d, dp, tid);
   const bool active = wave * 16 < dp;
-  const int u = wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+  const auto [u, i0] = seq_lane(wave, lane);
   float dn[4];
   bool ok[4];
   int64_t row[4];
+  seq_lane_rows(m0, i0, u, N, d, ok, row);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int n = m0 + i0 + r;
-    ok[r] = n < N && u < d;
-    row[r] = n < N ? n : 0;
-    dn[r] = ok[r] ? a.d_h_last[row[r] * d + u] : 0.f;
-  }
+  for (int r = 0; r < 4; ++r) dn[r] = ok[r] ? a.d_h_last[row[r] * d + u] : 0.f;
   __syncthreads();
   for (int t = F - 1; t >= 0; --t) {
-    f32x4 acc0, acc1 = {0.f, 0.f, 0.f, 0.f};
+    f32x4 acc0, acc1 = zero4();
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int64_t sidx = ok[r] ? (row[r] * F + t) * d + u : 0;
@@ -190,10 +177,7 @@ __global__ __launch_bounds__(64 * SEQ_A_WAVES) void attgru_seq_bwd_a(SeqBwdArgs 
 #pragma unroll
     for (int r = 0; r < 4; ++r) dn[r] = ok[r] ? acc0[r] + acc1[r] : 0.f;
   }
-  if (a.d_h0)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (ok[r]) a.d_h0[row[r] * d + u] = dn[r];
+  seq_store_rows(a.d_h0, dn, ok, row, d, u);
 }
 
 // ---------------------------------------------------------------- regime B
@@ -205,33 +189,19 @@ __global__ __launch_bounds__(256) void attgru_seq_fwd_b(SeqFwdArgs a, int t, con
   const int N = a.N, F = a.F, d = a.d;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int m0 = blockIdx.x * SEQ_RT, c0 = blockIdx.y * SEQ_B_CT;
-  f32x4 acc_r = {0.f, 0.f, 0.f, 0.f}, acc_c = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc_r = zero4(), acc_c = zero4();
   for (int k0 = 0; k0 < d; k0 += SEQ_B_KC) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int idx = tid + p * 256, i = idx >> 5, kk = idx & 31, n = m0 + i, k = k0 + kk;
-      float v = 0.f;
-      if (h_prev && n < N && k < d) v = h_prev[(int64_t)n * ldp + k];
-      A_l[i * SEQ_B_LD + kk] = v;
-    }
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {   // [c][kk] images of W[k][c]: read along c
-      const int idx = tid + p * 256, c = idx & 63, kk = idx >> 6, uu = c0 + c, k = k0 + kk;
-      const bool ok = uu < d && k < d;
-      const size_t src = ok ? (size_t)k * d + uu : 0;
-      const float vg = a.Wg[(size_t)d * d + src], vc = a.Wc[src];
-      Bg_l[c * SEQ_B_LD + kk] = ok ? vg : 0.f;
-      Bc_l[c * SEQ_B_LD + kk] = ok ? vc : 0.f;
-    }
+    seq_stage_a(A_l, h_prev, ldp, N, d, m0, k0, tid);
+    seq_stage_w2<false>(Bg_l, Bc_l, a.Wg + (size_t)d * d, a.Wc, d, d, c0, k0, tid);
     __syncthreads();
     seq_mma2(A_l, SEQ_B_LD, Bg_l + wave * 16 * SEQ_B_LD, Bc_l + wave * 16 * SEQ_B_LD, SEQ_B_LD, SEQ_B_KC, lane, acc_r, acc_c);
     __syncthreads();
   }
-  const int u = c0 + wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+  const auto [u, i0] = seq_lane(wave, lane, c0);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int n = m0 + i0 + r;
-    if (n < N && u < d) {
+    if (seq_live(n, u, N, d)) {
       const int64_t sidx = ((int64_t)n * F + t) * d + u;
       const float hp = h_prev ? h_prev[(int64_t)n * ldp + u] : 0.f;
       float rr, hh;
@@ -255,12 +225,14 @@ __global__ __launch_bounds__(256) void attgru_seq_bwd_b(SeqBwdArgs a, int t, con
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int m0 = blockIdx.x * SEQ_RT, c0 = blockIdx.y * SEQ_B_CT;
   const bool first = blockIdx.y == 0;   // the column tile that also writes the gate gradients and d_gate
-  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc0 = zero4(), acc1 = zero4();
   float pg[2] = {0.f, 0.f};
   for (int k0 = 0; k0 < d; k0 += SEQ_B_KC) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-      const int idx = tid + p * 256, i = idx >> 5, kk = idx & 31, n = m0 + i, uu = k0 + kk;
+      int i, kk;
+      seq_b_decode(tid, p, i, kk);
+      const int n = m0 + i, uu = k0 + kk;
       float dr = 0.f, dhc = 0.f, dxi = 0.f;
       if (n < N && uu < d) {
         const int64_t sidx = ((int64_t)n * F + t) * d + uu;
@@ -275,15 +247,7 @@ __global__ __launch_bounds__(256) void attgru_seq_bwd_b(SeqBwdArgs a, int t, con
       Tr[i * SEQ_B_LD + kk] = dr;
       Tc[i * SEQ_B_LD + kk] = dhc;
     }
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {   // [c][kk] images of W[c][k]: read along k
-      const int idx = tid + p * 256, kk = idx & 31, c = idx >> 5, cc = c0 + c, k = k0 + kk;
-      const bool ok = cc < d && k < d;
-      const size_t src = ok ? (size_t)cc * d + k : 0;
-      const float vg = a.Wg[(size_t)d * d + src], vc = a.Wc[src];
-      Bg_l[c * SEQ_B_LD + kk] = ok ? vg : 0.f;
-      Bc_l[c * SEQ_B_LD + kk] = ok ? vc : 0.f;
-    }
+    seq_stage_w2<true>(Bg_l, Bc_l, a.Wg + (size_t)d * d, a.Wc, d, d, c0, k0, tid);
     __syncthreads();
     seq_mma_ab(Tr, Tc, SEQ_B_LD, Bg_l + wave * 16 * SEQ_B_LD, Bc_l + wave * 16 * SEQ_B_LD, SEQ_B_LD, SEQ_B_KC, lane, acc0, acc1);
     __syncthreads();
@@ -292,33 +256,27 @@ __global__ __launch_bounds__(256) void attgru_seq_bwd_b(SeqBwdArgs a, int t, con
   for (int p = 0; p < 2; ++p) {     // row i = (tid >> 5) + 8 p lives in one 32-lane half: fixed-order tree inside it
     float s = pg[p];
 #pragma unroll
-    for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    for (int o = 16; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);   // (row16_sum adds in another order: other bits)
     const int n = m0 + (tid >> 5) + 8 * p;
     if (first && (tid & 31) == 0 && n < N) a.d_gate[(int64_t)n * F + t] = s;
   }
-  const int u = c0 + wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+  const auto [u, i0] = seq_lane(wave, lane, c0);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int n = m0 + i0 + r;
-    if (n < N && u < d)
+    if (seq_live(n, u, N, d))
       d_next[(int64_t)n * d + u] = d_cur[(int64_t)n * d + u] * (1.f - a.gate[(int64_t)n * F + t]) + acc0[r] + acc1[r];
   }
 }
 
-// the five parameter gradients of an `accumulate = 0` backward start at zero (fvta_linear_bwd adds)
-__global__ __launch_bounds__(256) void attgru_seq_zero(float* dWg, float* dbg, float* dWc, float* dWi, float* dbi, int d) {
-  const int64_t dd = (int64_t)d * d, total = 4 * dd + 2 * d;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    if (i < 2 * dd) dWg[i] = 0.f;
-    else if (i < 3 * dd) dWc[i - 2 * dd] = 0.f;
-    else if (i < 4 * dd) dWi[i - 3 * dd] = 0.f;
-    else if (i < 4 * dd + d) dbg[i - 4 * dd] = 0.f;
-    else dbi[i - 4 * dd - d] = 0.f;
-  }
+// seq_common.h's fill, for gru_seq.hip too.  grid 64, 256 threads
+__global__ __launch_bounds__(256) void seq_zero_params_kernel(SeqZeroTable t) {
+#pragma unroll
+  for (int j = 0; j < 5; ++j)
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < t.n[j]; i += (int64_t)gridDim.x * 256) t.p[j][i] = 0.f;
 }
+void seq_zero_params(const SeqZeroTable& t, hipStream_t s) { hipLaunchKernelGGL(seq_zero_params_kernel, dim3(64), dim3(256), 0, s, t); }
 
-static inline int seq_dp(int d) { return (d + 15) / 16 * 16; }
-static inline bool seq_regime_a(int d) { return seq_dp(d) <= SEQ_A_DP_MAX; }
 static inline size_t seq_lds_fwd_a(int dp) { return (size_t)(2 * dp + SEQ_RT) * (dp + 2) * sizeof(float); }
 static inline size_t seq_lds_bwd_a(int dp) {
   return ((size_t)(2 * dp + 2 * SEQ_RT) * (dp + 2) + SEQ_A_WAVES * SEQ_RT) * sizeof(float);
@@ -326,39 +284,12 @@ static inline size_t seq_lds_bwd_a(int dp) {
 static_assert((2 * SEQ_A_DP_MAX + 2 * SEQ_RT) * (SEQ_A_DP_MAX + 2) * 4 + SEQ_A_WAVES * SEQ_RT * 4 <= 160 * 1024,
               "regime A's weights and tiles must fit the 160 KiB of a CU");
 
-template <class K>
-static inline void seq_allow_lds(K kernel, size_t bytes) {  // > 64 KB of dynamic LDS is opted into per kernel symbol
-  if (bytes > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+static inline size_t attgru_n(const fvta_attgru_seq_desc& d) { return (size_t)d.N * d.F * d.d; }
+// saved: h_{t-1}, r, hc, hh.  workspace, forward: pre_r (a), pre_i (b), two state rows (regime B without `saved`); backward:
+// the gate gradients dr (a), dhc (b), dxi (c), two d_h rows
+static inline SeqWork attgru_work(const fvta_attgru_seq_desc& d, int backward, void* p) {
+  return SeqWork(attgru_n(d), (size_t)d.N * d.d, 1, backward != 0, p);
 }
-
-struct SeqSaved {
-  float *S_h, *S_r, *S_hc, *S_hh;
-  size_t bytes;
-  SeqSaved(const fvta_attgru_seq_desc& d, void* p) {
-    FvtaCarver c(p);
-    const size_t n = (size_t)d.N * d.F * d.d;
-    S_h = c.take<float>(n);
-    S_r = c.take<float>(n);
-    S_hc = c.take<float>(n);
-    S_hh = c.take<float>(n);
-    bytes = c.off;
-  }
-};
-struct SeqWork {  // forward: pre_r, pre_i, two state rows (regime B without `saved`); backward: the gate gradients, two d_h rows
-  float *p0, *p1, *p2, *s0, *s1;
-  size_t bytes;
-  SeqWork(const fvta_attgru_seq_desc& d, int backward, void* p) {
-    FvtaCarver c(p);
-    const size_t n = (size_t)d.N * d.F * d.d, nd = (size_t)d.N * d.d;
-    p0 = c.take<float>(n);
-    p1 = c.take<float>(n);
-    p2 = backward ? c.take<float>(n) : nullptr;
-    s0 = c.take<float>(nd);
-    s1 = c.take<float>(nd);
-    bytes = c.off;
-  }
-};
 
 static inline bool seq_desc_ok(const fvta_attgru_seq_desc* d) { return d && d->N > 0 && d->F > 0 && d->d > 0; }
 
@@ -366,29 +297,19 @@ static inline bool seq_desc_ok(const fvta_attgru_seq_desc* d) { return d && d->N
 using namespace fvta;
 
 extern "C" size_t fvta_attgru_seq_saved_bytes(const fvta_attgru_seq_desc* d) {
-  if (!seq_desc_ok(d)) {
-    fvta_set_error("attgru_seq_saved_bytes: bad N/F/d");
-    return 0;
-  }
-  return d->training ? SeqSaved(*d, nullptr).bytes : 0;
+  if (!seq_desc_ok(d)) return seq_refuse("attgru_seq_saved_bytes: bad N/F/d");
+  return d->training ? SeqSaved(attgru_n(*d), nullptr).bytes : 0;
 }
 
 extern "C" size_t fvta_attgru_seq_workspace_bytes(const fvta_attgru_seq_desc* d, int32_t backward) {
-  if (!seq_desc_ok(d)) {
-    fvta_set_error("attgru_seq_workspace_bytes: bad N/F/d");
-    return 0;
-  }
-  return SeqWork(*d, backward, nullptr).bytes;
+  if (!seq_desc_ok(d)) return seq_refuse("attgru_seq_workspace_bytes: bad N/F/d");
+  return attgru_work(*d, backward, nullptr).bytes;
 }
 
 extern "C" int fvta_attgru_seq_plan(const fvta_attgru_seq_desc* d, int32_t* out) {
   FVTA_CHECK_ARG(seq_desc_ok(d), "attgru_seq_plan: bad N/F/d");
   FVTA_CHECK_ARG(out, "attgru_seq_plan: null pointer");
-  const bool A = seq_regime_a(d->d);
-  out[0] = A ? 0 : 1;
-  out[1] = 2 + (A ? 1 : d->F);          // the two hoisted products, then the recurrence
-  out[2] = 1 + (A ? 1 : d->F) + 6;      // the fill of an accumulate = 0 call, the recurrence, fvta_linear_bwd's six kernels
-  out[3] = SEQ_RT;
+  seq_fill_plan(out, seq_regime_a(d->d), 1, d->F);
   return FVTA_OK;
 }
 
@@ -400,33 +321,33 @@ extern "C" int fvta_attgru_seq_fwd(const fvta_attgru_seq_desc* d, const float* f
   FVTA_CHECK_ARG(!d->training || saved, "attgru_seq_fwd: training wants `saved`");
   hipStream_t s = (hipStream_t)stream_;
   const int N = d->N, F = d->F, dd = d->d;
-  SeqWork w(*d, 0, workspace);
-  SeqSaved sv(*d, d->training ? saved : nullptr);
+  const SeqWork w = attgru_work(*d, 0, workspace);
+  const SeqSaved sv(attgru_n(*d), d->training ? saved : nullptr);
   const int64_t M = (int64_t)N * F;
-  int st = fvta_linear_fwd(facts, Wg, bg, w.p0, M, dd, dd, 0, stream_);   // x Wg[:d] + bg  (attention_gru_cell.py:63)
+  int st = fvta_linear_fwd(facts, Wg, bg, w.a, M, dd, dd, 0, stream_);   // x Wg[:d] + bg  (attention_gru_cell.py:63)
   if (st != FVTA_OK) return st;
-  st = fvta_linear_fwd(facts, Wi, bi, w.p1, M, dd, dd, 0, stream_);       // x Wi + bi      (:68)
+  st = fvta_linear_fwd(facts, Wi, bi, w.b, M, dd, dd, 0, stream_);       // x Wi + bi      (:68)
   if (st != FVTA_OK) return st;
-  SeqFwdArgs a{N, F, dd, seq_dp(dd), gate, h0, Wg, Wc, w.p0, w.p1, h_last, sv.S_h, sv.S_r, sv.S_hc, sv.S_hh};
-  const unsigned row_tiles = (unsigned)((N + SEQ_RT - 1) / SEQ_RT);
+  SeqFwdArgs a{N, F, dd, seq_dp(dd), gate, h0, Wg, Wc, w.a, w.b, h_last, sv.s[0], sv.s[1], sv.s[2], sv.s[3]};
+  const unsigned row_tiles = seq_row_tiles(N);
   if (seq_regime_a(dd)) {
     const size_t lds = seq_lds_fwd_a(a.dp);
     if (d->training) {
-      seq_allow_lds(attgru_seq_fwd_a<true>, lds);
+      fvta_allow_lds(attgru_seq_fwd_a<true>, lds);
       hipLaunchKernelGGL(attgru_seq_fwd_a<true>, dim3(row_tiles), dim3(64 * SEQ_A_WAVES), lds, s, a);
     } else {
-      seq_allow_lds(attgru_seq_fwd_a<false>, lds);
+      fvta_allow_lds(attgru_seq_fwd_a<false>, lds);
       hipLaunchKernelGGL(attgru_seq_fwd_a<false>, dim3(row_tiles), dim3(64 * SEQ_A_WAVES), lds, s, a);
     }
   } else {
-    const dim3 grid(row_tiles, (unsigned)((dd + SEQ_B_CT - 1) / SEQ_B_CT));
+    const dim3 grid = seq_grid_b(N, dd);
     const int64_t lds_saved = (int64_t)F * dd;
     float* buf[2] = {w.s0, w.s1};
     for (int t = 0; t < F; ++t) {
       const bool last = t + 1 == F;
       if (d->training) {   // h_t goes straight into the next step's slot of `saved`
-        const float* hp = t == 0 ? h0 : sv.S_h + (size_t)t * dd;
-        float* hn = last ? h_last : sv.S_h + (size_t)(t + 1) * dd;
+        const float* hp = t == 0 ? h0 : sv.s[0] + (size_t)t * dd;
+        float* hn = last ? h_last : sv.s[0] + (size_t)(t + 1) * dd;
         hipLaunchKernelGGL(attgru_seq_fwd_b<true>, grid, dim3(256), 0, s, a, t, hp, t == 0 ? (int64_t)dd : lds_saved, hn,
                            last ? (int64_t)dd : lds_saved, t == 0 ? 1 : 0);
       } else {
@@ -451,17 +372,18 @@ extern "C" int fvta_attgru_seq_bwd(const fvta_attgru_seq_desc* d, const float* f
                  "attgru_seq_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream_;
   const int N = d->N, F = d->F, dd = d->d;
-  SeqWork w(*d, 1, workspace);
-  SeqSaved sv(*d, const_cast<void*>(saved));
-  if (!accumulate) hipLaunchKernelGGL(attgru_seq_zero, dim3(64), dim3(256), 0, s, dWg, dbg, dWc, dWi, dbi, dd);
-  SeqBwdArgs a{N, F, dd, seq_dp(dd), gate, Wg, Wc, sv.S_h, sv.S_r, sv.S_hc, sv.S_hh, d_h_last, w.p0, w.p1, w.p2, d_gate, d_h0};
-  const unsigned row_tiles = (unsigned)((N + SEQ_RT - 1) / SEQ_RT);
+  const SeqWork w = attgru_work(*d, 1, workspace);
+  const SeqSaved sv(attgru_n(*d), const_cast<void*>(saved));
+  const int64_t dsq = (int64_t)dd * dd;
+  if (!accumulate) seq_zero_params({{dWg, dWc, dWi, dbg, dbi}, {2 * dsq, dsq, dsq, dd, dd}}, s);
+  SeqBwdArgs a{N, F, dd, seq_dp(dd), gate, Wg, Wc, sv.s[0], sv.s[1], sv.s[2], sv.s[3], d_h_last, w.a, w.b, w.c, d_gate, d_h0};
+  const unsigned row_tiles = seq_row_tiles(N);
   if (seq_regime_a(dd)) {
     const size_t lds = seq_lds_bwd_a(a.dp);
-    seq_allow_lds(attgru_seq_bwd_a, lds);
+    fvta_allow_lds(attgru_seq_bwd_a, lds);
     hipLaunchKernelGGL(attgru_seq_bwd_a, dim3(row_tiles), dim3(64 * SEQ_A_WAVES), lds, s, a);
   } else {
-    const dim3 grid(row_tiles, (unsigned)((dd + SEQ_B_CT - 1) / SEQ_B_CT));
+    const dim3 grid = seq_grid_b(N, dd);
     float* buf[2] = {w.s0, w.s1};
     const float* cur = d_h_last;
     for (int t = F - 1; t >= 0; --t) {
@@ -473,12 +395,11 @@ extern "C" int fvta_attgru_seq_bwd(const fvta_attgru_seq_desc* d, const float* f
   FVTA_CHECK_LAUNCH("attgru_seq_bwd");
   // contractions over all N*F rows: d_facts = dr Wg[:d]^T + dxi Wi^T; dWg[:d], dbg, dWi, dbi from x; dWg[d:], dWc from h_{t-1}
   const int64_t M = (int64_t)N * F;
-  const size_t dsq = (size_t)dd * dd;
-  int st = fvta_linear_bwd(facts, Wg, nullptr, w.p0, d_facts, dWg, dbg, M, dd, dd, 0, 0, stream_);
+  int st = fvta_linear_bwd(facts, Wg, nullptr, w.a, d_facts, dWg, dbg, M, dd, dd, 0, 0, stream_);
   if (st != FVTA_OK) return st;
-  st = fvta_linear_bwd(facts, Wi, nullptr, w.p2, d_facts, dWi, dbi, M, dd, dd, 0, 1, stream_);
+  st = fvta_linear_bwd(facts, Wi, nullptr, w.c, d_facts, dWi, dbi, M, dd, dd, 0, 1, stream_);
   if (st != FVTA_OK) return st;
-  st = fvta_linear_bwd(sv.S_h, Wg + dsq, nullptr, w.p0, nullptr, dWg + dsq, nullptr, M, dd, dd, 0, 0, stream_);
+  st = fvta_linear_bwd(sv.s[0], Wg + dsq, nullptr, w.a, nullptr, dWg + dsq, nullptr, M, dd, dd, 0, 0, stream_);
   if (st != FVTA_OK) return st;
-  return fvta_linear_bwd(sv.S_h, Wc, nullptr, w.p1, nullptr, dWc, nullptr, M, dd, dd, 0, 0, stream_);
+  return fvta_linear_bwd(sv.s[0], Wc, nullptr, w.b, nullptr, dWc, nullptr, M, dd, dd, 0, 0, stream_);
 }

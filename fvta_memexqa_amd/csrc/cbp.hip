@@ -271,12 +271,6 @@ __global__ __launch_bounds__(256) void cbp_dq_fold(const float* __restrict__ dqp
   }
 }
 
-template <typename K>
-static inline void cbp_allow_lds(K kernel, size_t bytes) {  // > 64 KB of dynamic LDS is opted into per kernel symbol
-  if (bytes > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 static inline int cbp_kpt(int D) { return D <= CBP_THREADS ? 1 : (D <= 4 * CBP_THREADS ? 4 : CBP_KPT_MAX); }
 static inline size_t cbp_lds_bytes(int D) { return ((size_t)cbp_kpt(D) * CBP_THREADS + D + CBP_SCRATCH) * sizeof(float); }
 
@@ -312,10 +306,10 @@ template <int KPT>
 static void cbp_launch_fwd(const CbpArgs& a, bool norm, size_t lds, hipStream_t s) {
   const dim3 grid((unsigned)((int64_t)a.N * a.P));
   if (norm) {
-    cbp_allow_lds(cbp_fwd_k<KPT, true>, lds);
+    fvta_allow_lds(cbp_fwd_k<KPT, true>, lds);
     hipLaunchKernelGGL((cbp_fwd_k<KPT, true>), grid, dim3(CBP_THREADS), lds, s, a);
   } else {
-    cbp_allow_lds(cbp_fwd_k<KPT, false>, lds);
+    fvta_allow_lds(cbp_fwd_k<KPT, false>, lds);
     hipLaunchKernelGGL((cbp_fwd_k<KPT, false>), grid, dim3(CBP_THREADS), lds, s, a);
   }
 }
@@ -323,17 +317,17 @@ template <int KPT>
 static void cbp_launch_bwd(const CbpArgs& a, bool norm, size_t lds, hipStream_t s) {
   const dim3 grid((unsigned)((int64_t)a.N * a.P));
   if (norm) {
-    cbp_allow_lds(cbp_bwd_k<KPT, true>, lds);
+    fvta_allow_lds(cbp_bwd_k<KPT, true>, lds);
     hipLaunchKernelGGL((cbp_bwd_k<KPT, true>), grid, dim3(CBP_THREADS), lds, s, a);
   } else {
-    cbp_allow_lds(cbp_bwd_k<KPT, false>, lds);
+    fvta_allow_lds(cbp_bwd_k<KPT, false>, lds);
     hipLaunchKernelGGL((cbp_bwd_k<KPT, false>), grid, dim3(CBP_THREADS), lds, s, a);
   }
 }
 
 static void cbp_launch_csr(const fvta_cbp_desc& d, const int* h1, const CbpWork& w, hipStream_t s) {
   const size_t lds = ((size_t)(d.D + 3) / 4 * 4 + CBP_THREADS) * sizeof(int);
-  cbp_allow_lds(cbp_csr, lds);
+  fvta_allow_lds(cbp_csr, lds);
   hipLaunchKernelGGL(cbp_csr, dim3(1), dim3(CBP_THREADS), lds, s, h1, d.d1, d.D, w.start, w.perm);
 }
 

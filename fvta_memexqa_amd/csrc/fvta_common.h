@@ -74,6 +74,13 @@ struct FvtaCarver {
   }
 };
 
+// > 64 KB of dynamic LDS is opted into per kernel symbol
+template <typename K>
+static inline void fvta_allow_lds(K kernel, size_t bytes) {
+  if (bytes > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
 // ---- device math ------------------------------------------------------------
 // Gate non-linearities on the hardware transcendental units (v_exp_f32 / v_rcp_f32, ~1 ulp each):
 // absolute error ~1e-7 on values in [-1,1], far inside the 1e-4 parity budget, and ~10x fewer VALU

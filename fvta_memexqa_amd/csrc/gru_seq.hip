@@ -20,14 +20,12 @@
 
 namespace fvta {
 
-constexpr int GRU_A_WAVES_MAX = 8;                     // 512 threads: two waves per SIMD
-constexpr int GRU_A_DP_MAX = 16 * GRU_A_WAVES_MAX;
 // Register budget of regime A: a SIMD has 512 registers per lane; at two waves per SIMD a wave may use 256.  The weight
 // fragments take 3 dp / 4 of them, the rest of a step (accumulators, gate inputs, addresses, the state) fits in 96.
-constexpr int GRU_A_REGS_PER_WAVE = 512 / (GRU_A_WAVES_MAX / 4);
+constexpr int GRU_A_REGS_PER_WAVE = 512 / (SEQ_A_WAVES / 4);   // (SEQ_A_WAVES = 8, 512 threads: two waves per SIMD)
 constexpr int GRU_A_REGS_OTHER = 96;
-static_assert(3 * GRU_A_DP_MAX / 4 + GRU_A_REGS_OTHER <= GRU_A_REGS_PER_WAVE, "regime A's weight fragments must fit the registers");
-static_assert(4 * SEQ_RT * (GRU_A_DP_MAX + 2) * 4 <= 64 * 1024, "regime A's tiles must fit static LDS");
+static_assert(3 * SEQ_A_DP_MAX / 4 + GRU_A_REGS_OTHER <= GRU_A_REGS_PER_WAVE, "regime A's weight fragments must fit the registers");
+static_assert(4 * SEQ_RT * (SEQ_A_DP_MAX + 2) * 4 <= 64 * 1024, "regime A's tiles must fit static LDS");
 
 struct GruFwdArgs {
   int N, T, in, d, reverse;
@@ -50,7 +48,7 @@ __device__ __forceinline__ int gru_len(const int* lens, int n, int T) {
   return l < 0 ? 0 : (l > T ? T : l);
 }
 
-// The state update.  The fused multiply-add is spelled out so that the training and the inference instantiation round alike.
+// The state update (the fmaf: see "Rounding" in seq_common.h)
 __device__ __forceinline__ float gru_update(float u, float h, float c) { return fmaf(u, h, (1.f - u) * c); }
 
 // gate gradients of one element from dt = d(h'): returns the part of d(h) that does not pass through a product
@@ -61,6 +59,8 @@ __device__ __forceinline__ float gru_gate_bwd(float dt, float hp, float u, float
 }
 
 // ---------------------------------------------------------------- regime A
+// These two kernels keep their lane preamble, h0 load and row stores written out: with any of seq_common.h's helpers in
+// them the compiler schedules the register-tight step loop differently (measured: 0.2-0.4 % slower at d = 100).
 // grid ceil(N/16), 64 KT threads; KT = dp / 16
 template <int KT, bool TRAIN>
 __global__ __launch_bounds__(64 * KT) void gru_seq_fwd_a(GruFwdArgs a) {
@@ -260,31 +260,17 @@ __global__ __launch_bounds__(256) void gru_seq_fwd_b1(GruFwdArgs a, int s, const
   const float* Wgs = a.Wg + (size_t)a.in * 2 * d;
   f32x4 acc_r = zero4(), acc_u = zero4();
   for (int k0 = 0; k0 < d; k0 += SEQ_B_KC) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int idx = tid + p * 256, i = idx >> 5, kk = idx & 31, n = m0 + i, k = k0 + kk;
-      float v = 0.f;
-      if (h_prev && n < N && k < d) v = h_prev[(int64_t)n * d + k];
-      A_l[i * SEQ_B_LD + kk] = v;
-    }
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {   // [c][kk] images of W[k][c]: read along c
-      const int idx = tid + p * 256, c = idx & 63, kk = idx >> 6, uu = c0 + c, k = k0 + kk;
-      const bool ok = uu < d && k < d;
-      const size_t src = ok ? (size_t)k * 2 * d + uu : 0;
-      const float vr = Wgs[src], vu = Wgs[ok ? src + d : 0];
-      Br_l[c * SEQ_B_LD + kk] = ok ? vr : 0.f;
-      Bu_l[c * SEQ_B_LD + kk] = ok ? vu : 0.f;
-    }
+    seq_stage_a(A_l, h_prev, d, N, d, m0, k0, tid);
+    seq_stage_w2<false>(Br_l, Bu_l, Wgs, Wgs + d, (size_t)2 * d, d, c0, k0, tid);
     __syncthreads();
     seq_mma2(A_l, SEQ_B_LD, Br_l + wave * 16 * SEQ_B_LD, Bu_l + wave * 16 * SEQ_B_LD, SEQ_B_LD, SEQ_B_KC, lane, acc_r, acc_u);
     __syncthreads();
   }
-  const int u = c0 + wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+  const auto [u, i0] = seq_lane(wave, lane, c0);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int n = m0 + i0 + r;
-    if (n < N && u < d) {
+    if (seq_live(n, u, N, d)) {
       const int len = gru_len(a.lens, n, T);
       const int64_t rt = (int64_t)n * T + gru_pos(s, len, a.reverse);
       const float hp = h_prev ? h_prev[(int64_t)n * d + u] : 0.f;
@@ -312,25 +298,17 @@ __global__ __launch_bounds__(256) void gru_seq_fwd_b2(GruFwdArgs a, int s, const
   const float* Wcs = a.Wc + (size_t)a.in * d;
   f32x4 acc = zero4();
   for (int k0 = 0; k0 < d; k0 += SEQ_B_KC) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int idx = tid + p * 256, i = idx >> 5, kk = idx & 31, n = m0 + i, k = k0 + kk;
-      A_l[i * SEQ_B_LD + kk] = (n < N && k < d) ? rh[(int64_t)n * d + k] : 0.f;
-    }
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-      const int idx = tid + p * 256, c = idx & 63, kk = idx >> 6, uu = c0 + c, k = k0 + kk;
-      Bc_l[c * SEQ_B_LD + kk] = (uu < d && k < d) ? Wcs[(size_t)k * d + uu] : 0.f;
-    }
+    seq_stage_a(A_l, rh, d, N, d, m0, k0, tid);
+    seq_stage_w1<false>(Bc_l, Wcs, d, d, c0, k0, tid);
     __syncthreads();
     seq_mma1(A_l, SEQ_B_LD, Bc_l + wave * 16 * SEQ_B_LD, SEQ_B_LD, SEQ_B_KC, lane, acc);
     __syncthreads();
   }
-  const int u = c0 + wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+  const auto [u, i0] = seq_lane(wave, lane, c0);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int n = m0 + i0 + r;
-    if (n < N && u < d) {
+    if (seq_live(n, u, N, d)) {
       const int len = gru_len(a.lens, n, T);
       const int64_t sidx = ((int64_t)n * T + gru_pos(s, len, a.reverse)) * d + u;
       const bool valid = s < len;
@@ -357,7 +335,9 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_b1(GruBwdArgs a, int s, const
   for (int k0 = 0; k0 < d; k0 += SEQ_B_KC) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {   // the A operand: dc_pre of (n, j), recomputed by every column tile
-      const int idx = tid + p * 256, i = idx >> 5, kk = idx & 31, n = m0 + i, j = k0 + kk;
+      int i, kk;
+      seq_b_decode(tid, p, i, kk);
+      const int n = m0 + i, j = k0 + kk;
       float dc_pre = 0.f, du_pre;
       if (n < N && j < d) {
         const int len = gru_len(a.lens, n, T);
@@ -369,20 +349,16 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_b1(GruBwdArgs a, int s, const
       }
       Tc[i * SEQ_B_LD + kk] = dc_pre;
     }
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {   // [c][kk] images of W[c][k]: read along k
-      const int idx = tid + p * 256, kk = idx & 31, c = idx >> 5, cc = c0 + c, k = k0 + kk;
-      Bc_l[c * SEQ_B_LD + kk] = (cc < d && k < d) ? Wcs[(size_t)cc * d + k] : 0.f;
-    }
+    seq_stage_w1<true>(Bc_l, Wcs, d, d, c0, k0, tid);
     __syncthreads();
     seq_mma1(Tc, SEQ_B_LD, Bc_l + wave * 16 * SEQ_B_LD, SEQ_B_LD, SEQ_B_KC, lane, acc);
     __syncthreads();
   }
-  const int u = c0 + wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+  const auto [u, i0] = seq_lane(wave, lane, c0);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int n = m0 + i0 + r;
-    if (n < N && u < d) {
+    if (seq_live(n, u, N, d)) {
       const int len = gru_len(a.lens, n, T);
       const int64_t rt = (int64_t)n * T + gru_pos(s, len, a.reverse), sidx = rt * d + u;
       const float dc = d_cur ? d_cur[(int64_t)n * d + u] : 0.f;
@@ -415,7 +391,9 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_b2(GruBwdArgs a, int s, const
   for (int k0 = 0; k0 < d; k0 += SEQ_B_KC) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-      const int idx = tid + p * 256, i = idx >> 5, kk = idx & 31, n = m0 + i, j = k0 + kk;
+      int i, kk;
+      seq_b_decode(tid, p, i, kk);
+      const int n = m0 + i, j = k0 + kk;
       float vr = 0.f, vu = 0.f;
       if (n < N && j < d) {
         const int64_t g = ((int64_t)n * T + gru_pos(s, gru_len(a.lens, n, T), a.reverse)) * 2 * d + j;
@@ -425,69 +403,25 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_b2(GruBwdArgs a, int s, const
       Tr[i * SEQ_B_LD + kk] = vr;
       Tu[i * SEQ_B_LD + kk] = vu;
     }
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-      const int idx = tid + p * 256, kk = idx & 31, c = idx >> 5, cc = c0 + c, k = k0 + kk;
-      const bool ok = cc < d && k < d;
-      const size_t src = ok ? (size_t)cc * 2 * d + k : 0;
-      const float vr = Wgs[src], vu = Wgs[ok ? src + d : 0];
-      Br_l[c * SEQ_B_LD + kk] = ok ? vr : 0.f;
-      Bu_l[c * SEQ_B_LD + kk] = ok ? vu : 0.f;
-    }
+    seq_stage_w2<true>(Br_l, Bu_l, Wgs, Wgs + d, (size_t)2 * d, d, c0, k0, tid);
     __syncthreads();
     seq_mma_ab(Tr, Tu, SEQ_B_LD, Br_l + wave * 16 * SEQ_B_LD, Bu_l + wave * 16 * SEQ_B_LD, SEQ_B_LD, SEQ_B_KC, lane, acc0, acc1);
     __syncthreads();
   }
-  const int u = c0 + wave * 16 + (lane & 15), i0 = 4 * (lane >> 4);
+  const auto [u, i0] = seq_lane(wave, lane, c0);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int n = m0 + i0 + r;
-    if (n < N && u < d) d_next[(int64_t)n * d + u] = dhp[(int64_t)n * d + u] + (acc0[r] + acc1[r]);
+    if (seq_live(n, u, N, d)) d_next[(int64_t)n * d + u] = dhp[(int64_t)n * d + u] + (acc0[r] + acc1[r]);
   }
 }
 
-// the four parameter gradients of an `accumulate = 0` backward start at zero (fvta_linear_bwd adds)
-__global__ __launch_bounds__(256) void gru_seq_zero(float* dWg, float* dbg, float* dWc, float* dbc, int in, int d) {
-  const int64_t ng = (int64_t)(in + d) * 2 * d, nc = (int64_t)(in + d) * d, total = ng + nc + 3 * d;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    if (i < ng) dWg[i] = 0.f;
-    else if (i < ng + nc) dWc[i - ng] = 0.f;
-    else if (i < ng + nc + 2 * d) dbg[i - ng - nc] = 0.f;
-    else dbc[i - ng - nc - 2 * d] = 0.f;
-  }
+static inline size_t gru_n(const fvta_gru_seq_desc& d) { return (size_t)d.N * d.T * d.d; }
+// saved: h_{t-1}, r, u, c.  workspace, forward: the hoisted products x Wg[:in] + bg (a, 2 n) and x Wc[:in] + bc (b), r * h and
+// u of a step (s0, s1: regime B); backward: the gate gradients [dr | du] (a) and dc (b), r * h of every step (c), two d_h rows
+static inline SeqWork gru_work(const fvta_gru_seq_desc& d, int backward, void* p) {
+  return SeqWork(gru_n(d), (size_t)d.N * d.d, 2, backward != 0, p);
 }
-
-static inline int gru_dp(int d) { return (d + 15) / 16 * 16; }
-static inline bool gru_regime_a(int d) { return gru_dp(d) <= GRU_A_DP_MAX; }
-
-struct GruSaved {
-  float *S_h, *S_r, *S_u, *S_c;
-  size_t bytes;
-  GruSaved(const fvta_gru_seq_desc& d, void* p) {
-    FvtaCarver c(p);
-    const size_t n = (size_t)d.N * d.T * d.d;
-    S_h = c.take<float>(n);
-    S_r = c.take<float>(n);
-    S_u = c.take<float>(n);
-    S_c = c.take<float>(n);
-    bytes = c.off;
-  }
-};
-struct GruWork {  // forward: the hoisted products, r * h and u of a step (regime B); backward: the gate gradients, r * h of
-                  // every step, two d_h rows (regime B)
-  float *g2, *g1, *rh_all, *s0, *s1;
-  size_t bytes;
-  GruWork(const fvta_gru_seq_desc& d, int backward, void* p) {
-    FvtaCarver c(p);
-    const size_t n = (size_t)d.N * d.T * d.d, nd = (size_t)d.N * d.d;
-    g2 = c.take<float>(2 * n);
-    g1 = c.take<float>(n);
-    rh_all = backward ? c.take<float>(n) : nullptr;
-    s0 = c.take<float>(nd);
-    s1 = c.take<float>(nd);
-    bytes = c.off;
-  }
-};
 
 static inline bool gru_desc_ok(const fvta_gru_seq_desc* d) {
   return d && d->N > 0 && d->T > 0 && d->in_dim > 0 && d->d > 0 && (d->reverse == 0 || d->reverse == 1);
@@ -519,29 +453,19 @@ using namespace fvta;
   }
 
 extern "C" size_t fvta_gru_seq_saved_bytes(const fvta_gru_seq_desc* d) {
-  if (!gru_desc_ok(d)) {
-    fvta_set_error("gru_seq_saved_bytes: bad N/T/in_dim/d/reverse");
-    return 0;
-  }
-  return d->training ? GruSaved(*d, nullptr).bytes : 0;
+  if (!gru_desc_ok(d)) return seq_refuse("gru_seq_saved_bytes: bad N/T/in_dim/d/reverse");
+  return d->training ? SeqSaved(gru_n(*d), nullptr).bytes : 0;
 }
 
 extern "C" size_t fvta_gru_seq_workspace_bytes(const fvta_gru_seq_desc* d, int32_t backward) {
-  if (!gru_desc_ok(d)) {
-    fvta_set_error("gru_seq_workspace_bytes: bad N/T/in_dim/d/reverse");
-    return 0;
-  }
-  return GruWork(*d, backward, nullptr).bytes;
+  if (!gru_desc_ok(d)) return seq_refuse("gru_seq_workspace_bytes: bad N/T/in_dim/d/reverse");
+  return gru_work(*d, backward, nullptr).bytes;
 }
 
 extern "C" int fvta_gru_seq_plan(const fvta_gru_seq_desc* d, int32_t* out) {
   FVTA_CHECK_ARG(gru_desc_ok(d), "gru_seq_plan: bad N/T/in_dim/d/reverse");
   FVTA_CHECK_ARG(out, "gru_seq_plan: null pointer");
-  const bool A = gru_regime_a(d->d);
-  out[0] = A ? 0 : 1;
-  out[1] = 2 + (A ? 1 : 2 * d->T);          // the two hoisted products, then the recurrence
-  out[2] = 1 + (A ? 1 : 2 * d->T) + 6;      // the fill of an accumulate = 0 call, the recurrence, fvta_linear_bwd's six kernels
-  out[3] = SEQ_RT;
+  seq_fill_plan(out, seq_regime_a(d->d), 2, d->T);
   return FVTA_OK;
 }
 
@@ -553,22 +477,22 @@ extern "C" int fvta_gru_seq_fwd(const fvta_gru_seq_desc* d, const float* x, cons
   FVTA_CHECK_ARG(!d->training || saved, "gru_seq_fwd: training wants `saved`");
   hipStream_t s = (hipStream_t)stream_;
   const int N = d->N, T = d->T, in = d->in_dim, dd = d->d;
-  GruWork w(*d, 0, workspace);
-  GruSaved sv(*d, d->training ? saved : nullptr);
+  const SeqWork w = gru_work(*d, 0, workspace);
+  const SeqSaved sv(gru_n(*d), d->training ? saved : nullptr);
   const int64_t M = (int64_t)N * T;
-  int st = fvta_linear_fwd(x, Wg, bg, w.g2, M, in, 2 * dd, 0, stream_);   // x Wg[:in] + bg
+  int st = fvta_linear_fwd(x, Wg, bg, w.a, M, in, 2 * dd, 0, stream_);   // x Wg[:in] + bg
   if (st != FVTA_OK) return st;
-  st = fvta_linear_fwd(x, Wc, bc, w.g1, M, in, dd, 0, stream_);           // x Wc[:in] + bc
+  st = fvta_linear_fwd(x, Wc, bc, w.b, M, in, dd, 0, stream_);           // x Wc[:in] + bc
   if (st != FVTA_OK) return st;
-  GruFwdArgs a{N, T, in, dd, d->reverse, lens, h0, Wg, Wc, w.g2, w.g1, out, h_last, sv.S_h, sv.S_r, sv.S_u, sv.S_c};
-  const unsigned row_tiles = (unsigned)((N + SEQ_RT - 1) / SEQ_RT);
-  if (gru_regime_a(dd)) {
+  GruFwdArgs a{N, T, in, dd, d->reverse, lens, h0, Wg, Wc, w.a, w.b, out, h_last, sv.s[0], sv.s[1], sv.s[2], sv.s[3]};
+  const unsigned row_tiles = seq_row_tiles(N);
+  if (seq_regime_a(dd)) {
     const bool tr = d->training != 0;
 #define GRU_CALL(KT) gru_launch_fwd_a<KT>(a, tr, row_tiles, s)
-    GRU_A_DISPATCH(gru_dp(dd) / 16, GRU_CALL)
+    GRU_A_DISPATCH(seq_dp(dd) / 16, GRU_CALL)
 #undef GRU_CALL
   } else {
-    const dim3 grid(row_tiles, (unsigned)((dd + SEQ_B_CT - 1) / SEQ_B_CT));
+    const dim3 grid = seq_grid_b(N, dd);
     for (int t = 0; t < T; ++t) {   // the state lives in h_last from the first step on
       const float* hp = t == 0 ? h0 : h_last;
       if (d->training) {
@@ -594,17 +518,18 @@ extern "C" int fvta_gru_seq_bwd(const fvta_gru_seq_desc* d, const float* x, cons
   FVTA_CHECK_ARG(d_out || d_h_last, "gru_seq_bwd: d_out and d_h_last are both NULL");
   hipStream_t s = (hipStream_t)stream_;
   const int N = d->N, T = d->T, in = d->in_dim, dd = d->d;
-  GruWork w(*d, 1, workspace);
-  GruSaved sv(*d, const_cast<void*>(saved));
-  if (!accumulate) hipLaunchKernelGGL(gru_seq_zero, dim3(64), dim3(256), 0, s, dWg, dbg, dWc, dbc, in, dd);
-  GruBwdArgs a{N, T, in, dd, d->reverse, lens, Wg, Wc, sv.S_h, sv.S_r, sv.S_u, sv.S_c, d_out, d_h_last, w.g2, w.g1, w.rh_all, d_h0};
-  const unsigned row_tiles = (unsigned)((N + SEQ_RT - 1) / SEQ_RT);
-  if (gru_regime_a(dd)) {
+  const SeqWork w = gru_work(*d, 1, workspace);
+  const SeqSaved sv(gru_n(*d), const_cast<void*>(saved));
+  if (!accumulate)
+    seq_zero_params({{dWg, dWc, dbg, dbc}, {(int64_t)(in + dd) * 2 * dd, (int64_t)(in + dd) * dd, 2 * dd, dd}}, s);
+  GruBwdArgs a{N, T, in, dd, d->reverse, lens, Wg, Wc, sv.s[0], sv.s[1], sv.s[2], sv.s[3], d_out, d_h_last, w.a, w.b, w.c, d_h0};
+  const unsigned row_tiles = seq_row_tiles(N);
+  if (seq_regime_a(dd)) {
 #define GRU_CALL(KT) gru_launch_bwd_a<KT>(a, row_tiles, s)
-    GRU_A_DISPATCH(gru_dp(dd) / 16, GRU_CALL)
+    GRU_A_DISPATCH(seq_dp(dd) / 16, GRU_CALL)
 #undef GRU_CALL
   } else {
-    const dim3 grid(row_tiles, (unsigned)((dd + SEQ_B_CT - 1) / SEQ_B_CT));
+    const dim3 grid = seq_grid_b(N, dd);
     const float* cur = d_h_last;
     for (int t = T - 1; t >= 0; --t) {
       float* nxt = (t == 0 && d_h0) ? d_h0 : w.s0;
@@ -618,11 +543,11 @@ extern "C" int fvta_gru_seq_bwd(const fvta_gru_seq_desc* d, const float* x, cons
   // dWg[in:] from h_{t-1}, dWc[in:] from r * h_{t-1}
   const int64_t M = (int64_t)N * T;
   const size_t og = (size_t)in * 2 * dd, oc = (size_t)in * dd;
-  int st = fvta_linear_bwd(x, Wg, nullptr, w.g2, d_x, dWg, dbg, M, in, 2 * dd, 0, 0, stream_);
+  int st = fvta_linear_bwd(x, Wg, nullptr, w.a, d_x, dWg, dbg, M, in, 2 * dd, 0, 0, stream_);
   if (st != FVTA_OK) return st;
-  st = fvta_linear_bwd(x, Wc, nullptr, w.g1, d_x, dWc, dbc, M, in, dd, 0, 1, stream_);
+  st = fvta_linear_bwd(x, Wc, nullptr, w.b, d_x, dWc, dbc, M, in, dd, 0, 1, stream_);
   if (st != FVTA_OK) return st;
-  st = fvta_linear_bwd(sv.S_h, Wg + og, nullptr, w.g2, nullptr, dWg + og, nullptr, M, dd, 2 * dd, 0, 0, stream_);
+  st = fvta_linear_bwd(sv.s[0], Wg + og, nullptr, w.a, nullptr, dWg + og, nullptr, M, dd, 2 * dd, 0, 0, stream_);
   if (st != FVTA_OK) return st;
-  return fvta_linear_bwd(w.rh_all, Wc + oc, nullptr, w.g1, nullptr, dWc + oc, nullptr, M, dd, dd, 0, 0, stream_);
+  return fvta_linear_bwd(w.c, Wc + oc, nullptr, w.b, nullptr, dWc + oc, nullptr, M, dd, dd, 0, 0, stream_);
 }

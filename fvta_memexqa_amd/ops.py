@@ -28,6 +28,14 @@ def _bytes(n, dev):
     return torch.empty(max(int(n), 256), dtype=torch.uint8, device=dev)
 
 
+def _sized(op, query, prefix, *args):
+    """a buffer of the bytes the library's size query names for op.desc; 0 is its refusal, raised with its message"""
+    nb = getattr(op.lib, query)(ctypes.byref(op.desc), *args)
+    if nb == 0:
+        raise _lib.FvtaError(prefix + op.lib.fvta_last_error().decode())
+    return _bytes(nb, op.dev)
+
+
 # ------------------------------------------------------------------ side stream
 def concurrency_ratio(main, cand, spin_us=400, repeats=3, others=()):
     """time(one spin wave on each of the streams main, others..., cand) / time(one spin wave on `main`): about 1 when
@@ -331,12 +339,6 @@ class SharedFocalAttention:
                                             stream_ptr()), "fvta_attn_shared_fwd")
         return h_a, a_logits
 
-    def _sized(self, query, what):
-        nb = getattr(self.lib, query)(ctypes.byref(self.desc))
-        if nb == 0:
-            raise _lib.FvtaError("shared attention %s: %s" % (what, self.lib.fvta_last_error().decode()))
-        return _bytes(nb, self.dev)
-
     def bwd_plan(self):
         """{rows, tsplit, channels, tiles_per_wg}: rows per tile of the backward's row pass, T splits and channels per slice
         of its question pass, row tiles per workgroup of the row pass (fvta_attn_shared_bwd_plan; host only, simiMatrix 1-3)"""
@@ -350,7 +352,7 @@ class SharedFocalAttention:
         assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
         assert album.is_cuda and album.dtype == torch.int32 and album.is_contiguous() and tuple(album.shape) == (self.NQ,)
         if getattr(self, "saved", None) is None:
-            self.saved = self._sized("fvta_attn_shared_saved_bytes", "saved")
+            self.saved = _sized(self, "fvta_attn_shared_saved_bytes", "shared attention saved: ")
         h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
         a_logits = torch.empty(self.NQ, self.K, self.T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
         check(self.lib.fvta_attn_shared_fwd_train(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)),
@@ -364,7 +366,7 @@ class SharedFocalAttention:
         if getattr(self, "saved", None) is None:
             raise _lib.FvtaError("shared attention: backward() needs a forward_train() first")
         if getattr(self, "work_bwd", None) is None:
-            self.work_bwd = self._sized("fvta_attn_shared_bwd_workspace_bytes", "backward workspace")
+            self.work_bwd = _sized(self, "fvta_attn_shared_bwd_workspace_bytes", "shared attention backward workspace: ")
         assert tuple(d_hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(d_hq.shape) == (self.NQ, self.JQ, self.w)
         assert tuple(d_h_a.shape) == (self.NQ, self.w)
         check(self.lib.fvta_attn_shared_bwd(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)), ptr(qmask),
@@ -628,15 +630,9 @@ class AttentionGRUSeq:
         self.desc = AttGruSeqDesc(self.N, self.F, self.d, int(bool(training)))
         self.saved = None
 
-    def _work(self, backward):
-        nb = self.lib.fvta_attgru_seq_workspace_bytes(ctypes.byref(self.desc), int(backward))
-        if nb == 0:
-            raise _lib.FvtaError("attgru_seq: " + self.lib.fvta_last_error().decode())
-        return _bytes(nb, self.dev)
-
     def forward(self, facts, gate, h0, Wg, bg, Wc, Wi, bi):
         h_last = torch.empty(self.N, self.d, dtype=torch.float32, device=self.dev)
-        work = self._work(False)
+        work = _sized(self, "fvta_attgru_seq_workspace_bytes", "attgru_seq: ", 0)
         if self.desc.training:
             self.saved = _bytes(self.lib.fvta_attgru_seq_saved_bytes(ctypes.byref(self.desc)), self.dev)
         check(self.lib.fvta_attgru_seq_fwd(ctypes.byref(self.desc), ptr(_f32c(facts)), ptr(_f32c(gate)),
@@ -650,7 +646,7 @@ class AttentionGRUSeq:
         `accumulate`.  `saved` is only read: the call may be repeated."""
         if self.saved is None:
             raise _lib.FvtaError("AttentionGRUSeq.backward: no training forward ran")
-        work = self._work(True)
+        work = _sized(self, "fvta_attgru_seq_workspace_bytes", "attgru_seq: ", 1)
         check(self.lib.fvta_attgru_seq_bwd(ctypes.byref(self.desc), ptr(facts), ptr(gate), ptr(Wg), ptr(Wc), ptr(Wi),
                                            ptr(self.saved), ptr(_f32c(d_h_last)), ptr(d_facts), ptr(d_gate), ptr(d_h0),
                                            ptr(dWg), ptr(dbg), ptr(dWc), ptr(dWi), ptr(dbi), int(accumulate), ptr(work),
@@ -683,16 +679,10 @@ class GRUSeq:
         self.desc = GruSeqDesc(self.N, self.T, self.in_dim, self.d, int(bool(reverse)), int(bool(training)))
         self.saved = None
 
-    def _work(self, backward):
-        nb = self.lib.fvta_gru_seq_workspace_bytes(ctypes.byref(self.desc), int(backward))
-        if nb == 0:
-            raise _lib.FvtaError("gru_seq: " + self.lib.fvta_last_error().decode())
-        return _bytes(nb, self.dev)
-
     def forward(self, x, lens, h0, Wg, bg, Wc, bc, want_out=True):
         out = torch.empty(self.N, self.T, self.d, dtype=torch.float32, device=self.dev) if want_out else None
         h_last = torch.empty(self.N, self.d, dtype=torch.float32, device=self.dev)
-        work = self._work(False)
+        work = _sized(self, "fvta_gru_seq_workspace_bytes", "gru_seq: ", 0)
         if self.desc.training:
             self.saved = _bytes(self.lib.fvta_gru_seq_saved_bytes(ctypes.byref(self.desc)), self.dev)
         check(self.lib.fvta_gru_seq_fwd(ctypes.byref(self.desc), ptr(_f32c(x)), ptr(None if lens is None else _i32c(lens)),
@@ -706,7 +696,7 @@ class GRUSeq:
         gradients stored, or added to under `accumulate`.  `saved` is only read: the call may be repeated."""
         if self.saved is None:
             raise _lib.FvtaError("GRUSeq.backward: no training forward ran")
-        work = self._work(True)
+        work = _sized(self, "fvta_gru_seq_workspace_bytes", "gru_seq: ", 1)
         check(self.lib.fvta_gru_seq_bwd(ctypes.byref(self.desc), ptr(x), ptr(lens), ptr(Wg), ptr(Wc), ptr(self.saved),
                                         ptr(None if d_out is None else _f32c(d_out)),
                                         ptr(None if d_h_last is None else _f32c(d_h_last)), ptr(d_x), ptr(d_h0), ptr(dWg),
@@ -768,14 +758,8 @@ class CompactBilinear:
         self.desc = _lib.CbpDesc(self.N, self.P, self.d1, self.d2, self.D, int(bool(normalize)), int(bool(training)))
         self.saved = None
 
-    def _work(self, backward):
-        nb = self.lib.fvta_cbp_workspace_bytes(ctypes.byref(self.desc), int(backward))
-        if nb == 0:
-            raise _lib.FvtaError("compact_bilinear: " + self.lib.fvta_last_error().decode())
-        return _bytes(nb, self.dev)
-
     def forward(self, x, q, h1, s1, h2, s2):
-        work = self._work(False)
+        work = _sized(self, "fvta_cbp_workspace_bytes", "compact_bilinear: ", 0)
         out = torch.empty(self.N * self.P, self.D, dtype=torch.float32, device=self.dev)
         if self.desc.training:
             self.saved = _bytes(self.lib.fvta_cbp_saved_bytes(ctypes.byref(self.desc)), self.dev)
@@ -789,7 +773,7 @@ class CompactBilinear:
         read: the call may be repeated."""
         if self.saved is None:
             raise _lib.FvtaError("CompactBilinear.backward: no training forward ran")
-        work = self._work(True)
+        work = _sized(self, "fvta_cbp_workspace_bytes", "compact_bilinear: ", 1)
         check(self.lib.fvta_cbp_bwd(ctypes.byref(self.desc), ptr(_f32c(x)), ptr(_f32c(q)), ptr(_i32c(h1)), ptr(_f32c(s1)),
                                     ptr(_i32c(h2)), ptr(_f32c(s2)), ptr(self.saved), ptr(_f32c(dy)), ptr(dx), ptr(dq),
                                     int(accumulate), ptr(work), stream_ptr()), "fvta_cbp_bwd")

@@ -15,7 +15,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 GRADS = ("d_facts", "d_gate", "d_h0", "dWg", "dbg", "dWc", "dWi", "dbi")
-SHAPES = [(5, 1, 16), (17, 2, 100), (33, 9, 80), (6, 33, 64), (1, 3, 64), (9, 5, 136), (65, 4, 256)]
+# (17, 3, 131), regime B: a last k-chunk of 3 columns, a last column tile of 3 units, a second row tile with one live row
+SHAPES = [(5, 1, 16), (17, 2, 100), (33, 9, 80), (6, 33, 64), (1, 3, 64), (9, 5, 136), (65, 4, 256), (17, 3, 131)]
 
 
 def _close_out(got, want, tag):
@@ -83,6 +84,8 @@ def test_sequence_op_matches_the_oracle(N, F, d, with_h0):
     """h_last and all eight gradients with and without h0; accumulate = 0 (through autograd) and accumulate = 1 onto
     non-zero buffers (through ops.AttentionGRUSeq), d_facts / d_gate / d_h0 overwritten either way."""
     from fvta_memexqa_amd import ops
+    if (N, F, d) == (17, 3, 131):
+        assert ops.attgru_seq_plan(N, F, d)["regime"] == "B"
     c, _, _ = _check_case(N, F, d, with_h0)
     cu = lambda t: None if t is None else t.cuda().contiguous()
     facts, gate, h0, P = cu(c["facts"]), cu(c["gate"]), cu(c["h0"]), [cu(p) for p in c["P"]]

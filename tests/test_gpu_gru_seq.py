@@ -18,7 +18,8 @@ pytestmark = pytest.mark.gpu
 
 GRADS = ("d_x", "d_h0", "dWg", "dbg", "dWc", "dbc")
 SHAPES_A = [(1, 1, 4, 16), (5, 3, 7, 16), (17, 2, 37, 100), (33, 9, 24, 80), (6, 33, 12, 64), (16, 4, 100, 100)]
-SHAPES_B = [(9, 5, 20, 136), (65, 4, 48, 256)]
+# (17, 3, 5, 131): a last k-chunk of 3 columns, a last column tile of 3 units, a second row tile with one live row
+SHAPES_B = [(9, 5, 20, 136), (65, 4, 48, 256), (17, 3, 5, 131)]
 
 
 def _close_out(got, want, tag):

@@ -143,6 +143,10 @@ _SIGS = {
     "fvta_attn_shared_tw_workspace_bytes": (c_size_t, [POINTER(AttnSharedTwDesc)]),
     "fvta_attn_shared_energy": (c_int, [POINTER(AttnSharedTwDesc), P, P, P, P, P, P]),
     "fvta_attn_shared_fwd_tw": (c_int, [POINTER(AttnSharedTwDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_attn_shared_tw_saved_bytes": (c_size_t, [POINTER(AttnSharedTwDesc)]),
+    "fvta_attn_shared_tw_bwd_workspace_bytes": (c_size_t, [POINTER(AttnSharedTwDesc)]),
+    "fvta_attn_shared_fwd_tw_train": (c_int, [POINTER(AttnSharedTwDesc)] + [P] * 18),
+    "fvta_attn_shared_bwd_tw": (c_int, [POINTER(AttnSharedTwDesc)] + [P] * 25),
     "fvta_timewarp_workspace_bytes": (c_size_t, [POINTER(TimewarpDesc)]),
     "fvta_timewarp_fwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_bwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),

@@ -239,6 +239,58 @@ def shared_focal_attention(hinfo, hq, album, W, b, hmask=None, qmask=None, simi=
     return _SharedFocalAttention.apply(hinfo, hq, album, W, b, hmask, qmask, int(simi), bool(add_tanh))
 
 
+class _SharedWarpedFocalAttention(torch.autograd.Function):
+    """_SharedFocalAttention under the time warp (fvta_attn_shared_fwd_tw_train / fvta_attn_shared_bwd_tw; simiMatrix 1-3):
+    (hinfo [A,K,T,w], hq [NQ,JQ,w], lq [NQ,w], album int32 [NQ] on the device, W [F*w], b [1], WH_W [2w,w] or its first w
+    rows, WH_b [w], WC_W [w], WC_b [1]; masks u8 | None; energy [A,T] | None) -> (h_a [NQ,w], a_logits [NQ,K,T,JQ],
+    scale [NQ,T]).  a_logits and scale are not differentiable.  `energy` is a cached value of the forward alone: the
+    gradient through e reaches hinfo, WH_W and WC_W whether it was given or computed here."""
+
+    @staticmethod
+    def forward(ctx, hinfo, hq, lq, album, W, b, WH_W, WH_b, WC_W, WC_b, hmask, qmask, simi, add_tanh, warp_type, window_t,
+                energy):
+        A, K, T, w = hinfo.shape
+        op = ops.SharedWarpedFocalAttention(A, hq.shape[0], K, T, hq.shape[1], w, simi, add_tanh, warp_type, window_t)
+        if energy is None:
+            energy = op.album_energy(hinfo, WH_W, WC_W)
+        h_a, a, scale = op.forward_train(hinfo, hmask, energy, hq, qmask, lq, album, W, b, WH_b, WC_W, WC_b, want_logits=True,
+                                         want_scale=True)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(a, scale)
+        ctx.op = op
+        ctx.aux = (album, hmask, qmask)
+        ctx.save_for_backward(hinfo, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b)
+        return h_a, a, scale
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ha, g_a, g_scale):
+        if g_ha is None:
+            return (None,) * 17
+        hinfo, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b = ctx.saved_tensors
+        album, hmask, qmask = ctx.aux
+        dh, dq, dlq = torch.empty_like(hinfo), torch.empty_like(hq), torch.empty_like(lq)   # overwritten
+        dW, db, dWH_W, dWH_b, dWC_W, dWC_b = (torch.zeros_like(t) for t in (W, b, WH_W, WH_b, WC_W, WC_b))
+        ctx.op.backward(hinfo, hmask, hq, qmask, lq, album, W, b, WH_W, WH_b, WC_W, WC_b, _c(g_ha), dh, dq, dlq, dW, db, dWH_W,
+                        dWH_b, dWC_W, dWC_b)
+        need = ctx.needs_input_grad
+        grads = (dh, dq, dlq, None, dW, db, dWH_W, dWH_b, dWC_W, dWC_b)
+        return tuple(g if n else None for g, n in zip(grads, need[:10])) + (None,) * 7
+
+
+def shared_warped_focal_attention(hinfo, hq, lq, album, W, b, WH_W, WH_b, WC_W, WC_b, hmask=None, qmask=None, simi=1,
+                                  add_tanh=False, warp_type=1, window_t=3.0, energy=None):
+    """album: int32 [NQ] on the device, validated by the caller (ops.check_album_index); WC_W [w] (or [w,1]), WC_b [1];
+    the width is the kernels' (functional.attention_3d_shared_warped_raw pads any)"""
+    if int(simi) == 4:
+        raise NotImplementedError("shared_warped_focal_attention: simiMatrix 4 has no shared-context backward; the "
+                                  "per-question time_warp + focal_attention on gathered rows cover it")
+    f = lambda t: t.to(torch.float32).contiguous()
+    return _SharedWarpedFocalAttention.apply(f(hinfo), f(hq), f(lq), album, f(W), f(b), f(WH_W), f(WH_b), f(WC_W).reshape(-1),
+                                             f(WC_b).reshape(-1), hmask, qmask, int(simi), bool(add_tanh), int(warp_type),
+                                             float(window_t), None if energy is None else f(energy.detach()))
+
+
 class _KeepRank1(torch.autograd.Function):
     """attention_keeprank1 (model.py:247-314): (hinfo [N,M,V,w], hq [N,JQ,w], W [F*w], b [1]; masks u8 | None) ->
     (u [N,M,w], a_logits [N,M,V,JQ] | None).  Forward: fvta_attn_fwd at K = M in model.py's feature order, then the

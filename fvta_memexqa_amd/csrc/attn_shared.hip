@@ -6,6 +6,7 @@
 // instantiations of (4) and (6), further down.  fvta_attn_shared_fwd keeps nothing
 // for a backward; fvta_attn_shared_fwd_train runs the same kernels -- the same bits -- with the ordered plan (3) and the
 // arg-max (4) compiled in, and leaves what attn_shared_bwd.hip reads in the caller-held `saved` (attn_shared_common.h).
+// fvta_attn_shared_fwd_tw_train is that under the time warp: <TRAIN, TW> of (4), which also leaves lin at the arg-max and r2.
 //
 // Bilinear form (attn_common.h): x[t,(g,j)] = rs[t] sum_c h[t,c] Qs[g,j,c] + (Rh.h[t] + R2.h[t]^2) + ct[g,j].
 // Launches, all on the caller's stream, none waits for the host:
@@ -162,9 +163,9 @@ template <int JT, bool TRAIN, bool TW>
 __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, ShWork wk, const float* __restrict__ hinfo,
                                                                   const uint8_t* __restrict__ hmask,
                                                                   const uint8_t* __restrict__ qmask,
-                                                                  float* __restrict__ a_logits,
-                                                                  const float* __restrict__ tw_scale) {
+                                                                  float* __restrict__ a_logits, ShTwArgs tw) {
   constexpr int JP = 32 * JT, G = SH_BN / JP;
+  const float* __restrict__ tw_scale = tw.scale;
   __shared__ __attribute__((aligned(16))) float smem[ShMma::LDS_FLOATS];
   __shared__ float s_rt[SH_R], s_ct[SH_BN];
   // TW: s_rt holds Rh.h, s_r2 R2.h^2 (cosine: sum h^2); s_sc, s_s2 the factor of the product and the addend per (question, row)
@@ -199,7 +200,11 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
       const size_t at = ((size_t)s_q[e / rows] * K + k) * T + t0 + e % rows;
       wk.amax[at] = FVTA_NEG;
       if constexpr (TRAIN) wk.jmax[at] = 0;
+      if constexpr (TRAIN && TW) tw.lin[at] = 0.f;  // (no gradient passes through a masked logit: written, never used)
     }
+    if constexpr (TRAIN && TW)
+      if (grp == wk.agrp[a])
+        for (int e = tid; e < rows; e += SH_NT) tw.r2[ak * T + t0 + e] = 0.f;
     if (a_logits)
       for (int g = 0; g < cnt; ++g) {
         float* dst = a_logits + (((size_t)s_q[g] * K + k) * T + t0) * JQ;
@@ -263,6 +268,10 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
     return Qs + (ok ? ((size_t)q * JP + c % JP) * w + kk : (size_t)0);
   };
   gemm_mainloop(mma, sa, sb, fa, fb, 0, w, smem, tid);  // (ends on a barrier: s_rt -- TW: s_r2, s_sc -- is visible)
+  if constexpr (TRAIN && TW) {  // r2 [A,K,T] for the backward: every group of the album holds the same bits, its first stores
+    if (grp == wk.agrp[a])
+      for (int e = tid; e < min(SH_R, T - t0); e += SH_NT) tw.r2[ak * T + t0 + e] = s_r2[e];
+  }
   if constexpr (TW) {  // x = sc (h.Qs + Rh.h) + sc^2 R2.h^2 + ct; cosine (Rh.h = ct = 0): x = h.Qn sc rsqrt(max(sc^2 |h|^2, 1e-12))
     for (int e = tid; e < G * SH_R; e += SH_NT) {
       const float sc = s_sc[e / SH_R][e % SH_R], r2 = sc * sc * s_r2[e % SH_R];
@@ -312,6 +321,14 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
 #pragma unroll
           for (int o = 16; o > 0; o >>= 1) jm = min(jm, __shfl_xor(jm, o, 64));
           if (mma.l31 == r && q >= 0 && t < T) wk.jmax[((size_t)q * K + k) * T + t] = (uint8_t)min(jm, JQ - 1);
+          if constexpr (TW) {  // lin at the winner: the one lane that holds column jm puts it in, 31 zeros are added to it
+            const int mine = mx[jn][r] == m ? mma.l31 : ((JT == 2 && mx[jn + 1][r] == m) ? 32 + mma.l31 : 255);
+            const float acc = (JT == 2 && mine >= 32) ? mma.acc[i][JT == 2 ? jn + 1 : jn][r] : mma.acc[i][jn][r];
+            float lv = (mine == jm && jm != 255) ? acc + s_rt[mma.row_of(i, r)] : 0.f;
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) lv += __shfl_xor(lv, o, 64);
+            if (mma.l31 == r && q >= 0 && t < T) tw.lin[((size_t)q * K + k) * T + t] = lv;
+          }
         }
       }
     }
@@ -489,11 +506,13 @@ __global__ __launch_bounds__(256) void attn_shared_energy_kernel(ShShape s, cons
 }
 
 // scale[q,t].  grid (NQ, ceil(T / 256)), 256 threads; every wave takes the two dot products itself (w floats each)
+// TRAIN: tanh(z) beside it, for the backward
+template <bool TRAIN>
 __global__ __launch_bounds__(256) void attn_shared_tw_scale_kernel(ShShape s, int warp_type, int win, const float* __restrict__ energy,
                                                                    const float* __restrict__ lq, const int* __restrict__ album,
                                                                    const float* __restrict__ WHb, const float* __restrict__ WC,
                                                                    const float* __restrict__ WCb, float* __restrict__ scale,
-                                                                   float* __restrict__ scale_out) {
+                                                                   float* __restrict__ scale_out, float* __restrict__ tz_out) {
   const int q = blockIdx.x, lane = threadIdx.x & 63, t = blockIdx.y * 256 + threadIdx.x;
   float s0 = 0.f, sq = 0.f;
   for (int c = lane; c < s.w; c += 64) {
@@ -505,7 +524,9 @@ __global__ __launch_bounds__(256) void attn_shared_tw_scale_kernel(ShShape s, in
   sq = wave_sum(sq);
   if (t >= s.T) return;
   const int a = sh_album(album, q, s.A);
-  const float sc = tanhf(energy[(size_t)a * s.T + t] + (float)s.K * (s0 + sq)) * tw_count(t, s.T, warp_type, win);
+  const float tz = tanhf(energy[(size_t)a * s.T + t] + (float)s.K * (s0 + sq));
+  const float sc = tz * tw_count(t, s.T, warp_type, win);
+  if constexpr (TRAIN) tz_out[(size_t)q * s.T + t] = tz;
   scale[(size_t)q * s.T + t] = sc;
   if (scale_out) scale_out[(size_t)q * s.T + t] = sc;
 }
@@ -573,19 +594,20 @@ extern "C" int fvta_attn_shared_plan(const fvta_attn_shared_desc* d, int32_t out
 template <bool TRAIN, bool TW = false>
 static int sh_forward(ShShape s, const ShWork& wk, const float* hinfo, const uint8_t* hmask, const float* hq, const uint8_t* qmask,
                       const int32_t* album, const float* W, const float* b, float* h_a, float* a_logits, hipStream_t st,
-                      const float* tw_scale = nullptr, const char* who = nullptr) {
+                      const float* tw_scale = nullptr, const char* who = nullptr, float* tw_lin = nullptr, float* tw_r2 = nullptr) {
   s.use_mask = (hmask && qmask) ? 1 : 0;  // model_v2.py:233: the mask applies only when both are given
   // attn_fwd.hip's kernel, declared in attn_common.h (feat_order 0 = model_v2.py's)
   hipLaunchKernelGGL(attn_vecs_kernel, dim3((s.w + 255) / 256), dim3(256), 0, st, W, s.w, s.simi, 0, wk.vecs);
   hipLaunchKernelGGL(attn_shared_prep_q_kernel, dim3(s.NQ, s.JP / 4), dim3(256), 0, st, s, wk, hq, b);
   hipLaunchKernelGGL(attn_shared_plan_kernel<TRAIN>, dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)album);
   const dim3 lgrid((unsigned)((int64_t)s.ngmax * s.K * s.ntile));
+  const ShTwArgs tw{tw_scale, tw_lin, tw_r2};
   if (s.JP == 32)
     hipLaunchKernelGGL((attn_shared_logits_kernel<1, TRAIN, TW>), lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits,
-                       tw_scale);
+                       tw);
   else
     hipLaunchKernelGGL((attn_shared_logits_kernel<2, TRAIN, TW>), lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits,
-                       tw_scale);
+                       tw);
   hipLaunchKernelGGL(attn_shared_softmax_kernel, dim3(s.NQ), dim3(256), 0, st, s, wk);
   if (s.G == 8)
     sh_launch_wsum<8, TW>(s, wk, hinfo, tw_scale, st);
@@ -649,9 +671,9 @@ struct ShTwWork {
   }
 };
 
-static int sh_check_tw(const fvta_attn_shared_tw_desc* d, const char* who) {
+int fvta_attn_shared_check_tw(const fvta_attn_shared_tw_desc* d, const char* who, bool train) {
   FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  if (int e = fvta_attn_shared_check(&d->shape, who)) return e;
+  if (int e = train ? fvta_attn_shared_check_train(&d->shape, who) : fvta_attn_shared_check(&d->shape, who)) return e;
   if (d->warp_type < 1 || d->warp_type > 5) {
     fvta_set_error("%s: time warping type not implemented (warp_type=%d)", who, d->warp_type);  // model_v2.py:341
     return FVTA_ERR_INVALID_ARG;
@@ -666,13 +688,13 @@ static int sh_check_tw(const fvta_attn_shared_tw_desc* d, const char* who) {
 }  // namespace fvta
 
 extern "C" size_t fvta_attn_shared_tw_workspace_bytes(const fvta_attn_shared_tw_desc* d) {
-  if (sh_check_tw(d, "attn_shared_tw_workspace_bytes") != FVTA_OK) return 0;
+  if (fvta_attn_shared_check_tw(d, "attn_shared_tw_workspace_bytes") != FVTA_OK) return 0;
   return ShTwWork(sh_shape(&d->shape), nullptr).bytes;
 }
 
 extern "C" int fvta_attn_shared_energy(const fvta_attn_shared_tw_desc* d, const float* hinfo, const float* WH_W, const float* WC_W,
                                        float* energy, void* workspace, fvta_stream_t stream_) {
-  if (int e = sh_check_tw(d, "attn_shared_energy")) return e;
+  if (int e = fvta_attn_shared_check_tw(d, "attn_shared_energy")) return e;
   FVTA_CHECK_ARG(hinfo && WH_W && WC_W && energy && workspace, "attn_shared_energy: null pointer");
   const ShShape s = sh_shape(&d->shape);
   const ShTwWork tw(s, workspace);
@@ -689,13 +711,40 @@ extern "C" int fvta_attn_shared_fwd_tw(const fvta_attn_shared_tw_desc* d, const 
                                        const int32_t* album, const float* W, const float* b, const float* WH_b, const float* WC_W,
                                        const float* WC_b, float* h_a, float* a_logits, float* scale_out, void* workspace,
                                        fvta_stream_t stream_) {
-  if (int e = sh_check_tw(d, "attn_shared_fwd_tw")) return e;
+  if (int e = fvta_attn_shared_check_tw(d, "attn_shared_fwd_tw")) return e;
   FVTA_CHECK_ARG(hinfo && energy && hq && lq && album && WH_b && WC_W && WC_b && h_a && workspace, "attn_shared_fwd_tw: null pointer");
   FVTA_CHECK_ARG(d->shape.simi == 4 || W, "attn_shared_fwd_tw: simiMatrix %d needs att_logits/W", d->shape.simi);
   const ShShape s = sh_shape(&d->shape);
   const ShTwWork tw(s, workspace);
   hipStream_t st = (hipStream_t)stream_;
-  hipLaunchKernelGGL(attn_shared_tw_scale_kernel, dim3(s.NQ, (s.T + 255) / 256), dim3(256), 0, st, s, d->warp_type,
-                     (int)ceilf(d->window_t), energy, lq, (const int*)album, WH_b, WC_W, WC_b, tw.scale, scale_out);
+  hipLaunchKernelGGL(attn_shared_tw_scale_kernel<false>, dim3(s.NQ, (s.T + 255) / 256), dim3(256), 0, st, s, d->warp_type,
+                     (int)ceilf(d->window_t), energy, lq, (const int*)album, WH_b, WC_W, WC_b, tw.scale, scale_out, (float*)nullptr);
   return sh_forward<false, true>(s, tw.wk, hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, st, tw.scale, "attn_shared_fwd_tw");
+}
+
+// ---- training under the time warp.  The kernels of fvta_attn_shared_fwd_tw on the same numbers -- h_a, a_logits and
+// scale_out are its bits -- with the ordered plan, the arg-max, and in `saved` what attn_shared_bwd.hip's
+// fvta_attn_shared_bwd_tw reads: fvta_attn_shared_fwd_train's pieces, then scale, tanh(z), lin at the arg-max and r2.
+extern "C" size_t fvta_attn_shared_tw_saved_bytes(const fvta_attn_shared_tw_desc* d) {
+  if (fvta_attn_shared_check_tw(d, "attn_shared_tw_saved_bytes", true) != FVTA_OK) return 0;
+  const ShShape s = sh_shape(&d->shape);
+  return ShTwSaved(s, ShWork(s, nullptr, nullptr), nullptr).bytes;
+}
+
+extern "C" int fvta_attn_shared_fwd_tw_train(const fvta_attn_shared_tw_desc* d, const float* hinfo, const uint8_t* hmask,
+                                             const float* energy, const float* hq, const uint8_t* qmask, const float* lq,
+                                             const int32_t* album, const float* W, const float* b, const float* WH_b,
+                                             const float* WC_W, const float* WC_b, float* h_a, float* a_logits, float* scale_out,
+                                             void* saved, void* workspace, fvta_stream_t stream_) {
+  if (int e = fvta_attn_shared_check_tw(d, "attn_shared_fwd_tw_train", true)) return e;
+  FVTA_CHECK_ARG(hinfo && energy && hq && lq && album && W && WH_b && WC_W && WC_b && h_a && saved && workspace,
+                 "attn_shared_fwd_tw_train: null pointer");
+  const ShShape s = sh_shape(&d->shape);
+  const ShWork wk(s, saved, workspace);  // (its share of the workspace is no larger than the inference call's)
+  const ShTwSaved ts(s, wk, saved);
+  hipStream_t st = (hipStream_t)stream_;
+  hipLaunchKernelGGL(attn_shared_tw_scale_kernel<true>, dim3(s.NQ, (s.T + 255) / 256), dim3(256), 0, st, s, d->warp_type,
+                     (int)ceilf(d->window_t), energy, lq, (const int*)album, WH_b, WC_W, WC_b, ts.scale, scale_out, ts.tz);
+  return sh_forward<true, true>(s, wk, hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, st, ts.scale, "attn_shared_fwd_tw_train",
+                                ts.lin, ts.r2);
 }

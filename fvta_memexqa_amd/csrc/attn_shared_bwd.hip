@@ -29,8 +29,11 @@
 // `order`, which the training plan fills by ascending question index (attn_shared.hip: attn_shared_plan_kernel<true>).
 // Kernels 1, 4 and 5 are a few lines each around attn_bwd_shared.h's prep body, fold body and parameter pieces -- the one
 // copy attn_bwd.hip runs too; the row and question passes (2, 3) are this file's own.
+// Under the time warp (fvta_attn_shared_bwd_tw, the gradient of fvta_attn_shared_fwd_tw_train): the TW instantiations of
+// (2) and (3) and six small kernels of the warp's own backward, at the end of this file.
 #include "attn_shared_common.h"
 #include "attn_bwd_shared.h"
+#include "timewarp_common.h"
 
 namespace fvta {
 
@@ -38,6 +41,7 @@ constexpr int SHB_CS = 32;            // channels per slice of the question pass
 constexpr int SHB_JG = ATTN_BWD_JG;   // question positions per workgroup of the fold
 constexpr int SHB_ROW_WGS = 1024;     // about this many workgroups of the row pass (then several tiles per workgroup)
 constexpr int SHB_Q_WAVES = 1280;     // about this many waves of the question pass (5 x 32 KB of LDS per CU)
+constexpr int SHB_E_WGS = 512;        // at most this many workgroups of the energy backward: one dv partial each
 
 struct ShBwdShape {
   int TPR, CPT, RH, RPT, TR;  // row pass: threads per row, float4 per thread and row, row groups, rows per thread, tile rows
@@ -106,12 +110,34 @@ __global__ __launch_bounds__(1024) void attn_shared_bwd_prep_kernel(ShShape s, S
                      s.T, wk.coef + qk, wk.gu + qk, wk.dss + qk);
 }
 
+// what the row and question passes take under the time warp: the forward's saved pieces, and three arrays [NQ,K,T] of the
+// backward's workspace: ds (the gradient of the scale, per k), dx s (the question pass multiplies the rows by it), dbt (the
+// row's term of db, see the row pass)
+struct ShBwdTwArgs {
+  const float *scale, *lin, *r2;
+  float *ds, *dxs, *dbt;
+};
+
+// dx s^2 per row of the tile, beside s_pr / s_dx: LDS of the TW instantiations alone
+template <int TR>
+__device__ __forceinline__ float* shb_tw_d2() {
+  __shared__ float s_d2[TR];
+  return s_d2;
+}
+
 // ---- row pass.  grid A K nch, 256 threads = RH row groups x TPR threads; a thread holds RPT rows x CPT float4
-template <int TPR, int CPT, int RPT>
+// TW (compile-time): under the time warp the attention saw the rows s h, s = scale[q,t].  pr and dx are what they were, on
+// g.(s h); the thread that computes them also reads s, lin and r2 and stores ds = pr g.h + dx (lin + 2 s r2), dx and dx s;
+// the rows' gradient takes s pr g + dx s (Qs + Rh) + 2 dx s^2 R2 h, the Rh / R2 partials sum dx s and dx s^2.
+// db under the warp is NOT the sum of the d ct: the gradients damax of a question's max-pooled logits sum to zero over
+// (k, t) -- two softmaxes -- so sum dx = sum damax (1 - x^2) = - sum damax x^2 under tanh and 0 without.  The warped rows
+// are up to cmax times the rows, damax is of order 1 where db is of order 1e-3, and the plain sum kept the fp32 noise of
+// that cancellation (1e-5 at w = 512); dbt [NQ,K,T] = - damax x^2 has none to cancel.  d ct per (question, j) stays dx
+template <int TPR, int CPT, int RPT, bool TW>
 __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, ShBwdShape bs, ShWork sv, ShBwdWork wk,
                                                                   const float* __restrict__ hinfo,
                                                                   const float* __restrict__ d_h_a,
-                                                                  float* __restrict__ d_hinfo) {
+                                                                  float* __restrict__ d_hinfo, ShBwdTwArgs tw) {
   constexpr int RH = 256 / TPR, TR = RH * RPT;
   constexpr int WPR = TPR >= 64 ? TPR / 64 : 1;  // waves that share a row
   __shared__ float s_dot[4][TR], s_pr[TR], s_dx[TR];
@@ -134,11 +160,12 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, Sh
   for (int tile = ch * bs.tpw; tile < tile_end; ++tile) {
     const int t0 = tile * TR;
     f32x4 h[RPT][CPT], dh[RPT][CPT];
-    float sdx[RPT];
+    float sdx[RPT], sdx2[TW ? RPT : 1];
 #pragma unroll
     for (int i = 0; i < RPT; ++i) {
       const int t = t0 + rh * RPT + i;
       sdx[i] = 0.f;
+      if constexpr (TW) sdx2[i] = 0.f;
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
         h[i][c] = t < T ? ld4(hbase + (size_t)t * w + 4 * (cq + c * TPR)) : zero4();
@@ -171,7 +198,7 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, Sh
       __syncthreads();
       if (tid < TR) {
         const int t = t0 + tid;
-        float pr = 0.f, dx = 0.f;
+        float pr = 0.f, dx = 0.f, sc = 0.f, dbt = 0.f;
         int j = 0;
         if (t < T) {
           float gh = 0.f;
@@ -184,17 +211,32 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, Sh
           }
           const size_t qk = (size_t)q * K + k;
           const float M = sv.M[qk], am = sv.amax[qk * T + t];
+          if constexpr (TW) sc = tw.scale[(size_t)q * T + t];
           pr = expf(am - M) * wk.coef[qk];
           // pr = 0: a masked row beside valid ones (its g.h may be anything), or r underflowed (then ds is 0 as well)
           if (pr != 0.f && M != FVTA_NEG) {
-            const float damax = pr * (gh - wk.gu[qk]) + (am == M ? wk.dss[qk] : 0.f);
+            const float damax = pr * ((TW ? sc * gh : gh) - wk.gu[qk]) + (am == M ? wk.dss[qk] : 0.f);
             dx = s.add_tanh ? damax * (1.f - am * am) : damax;
+            if constexpr (TW) dbt = s.add_tanh ? -(damax * am * am) : 0.f;
           }
           j = min((int)sv.jmax[qk * T + t], JP - 1);
           wk.dx[qk * T + t] = dx;
+          if constexpr (TW) {  // (pr = 0 beside a g.h that may be anything: no product with it)
+            tw.dbt[qk * T + t] = dbt;
+            float ds = pr != 0.f ? pr * gh : 0.f;
+            if (dx != 0.f) ds += dx * (tw.lin[qk * T + t] + 2.f * sc * tw.r2[(size_t)ak * T + t]);
+            tw.ds[qk * T + t] = ds;
+            tw.dxs[qk * T + t] = dx * sc;
+          }
         }
-        s_pr[tid] = pr;
-        s_dx[tid] = dx;
+        if constexpr (TW) {
+          s_pr[tid] = pr * sc;
+          s_dx[tid] = dx * sc;
+          shb_tw_d2<TR>()[tid] = dx * sc * sc;
+        } else {
+          s_pr[tid] = pr;
+          s_dx[tid] = dx;
+        }
         s_jj[tid] = j;
       }
       __syncthreads();
@@ -210,9 +252,13 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, Sh
 #pragma unroll
           for (int c = 0; c < CPT; ++c) {
             const f32x4 qs = ld4(Qs + (size_t)j * w + 4 * (cq + c * TPR));
-            dh[i][c] += (qs + rh4[c] + r24[c] * h[i][c] * 2.f) * dx;
+            if constexpr (TW)
+              dh[i][c] += (qs + rh4[c]) * dx + r24[c] * h[i][c] * (2.f * shb_tw_d2<TR>()[row]);
+            else
+              dh[i][c] += (qs + rh4[c] + r24[c] * h[i][c] * 2.f) * dx;
           }
           sdx[i] += dx;
+          if constexpr (TW) sdx2[i] += shb_tw_d2<TR>()[row];
         }
       }
       // (the next question's s_dot is written after this barrier pair, its s_pr / s_dx after the next first barrier, which
@@ -225,7 +271,10 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, Sh
 #pragma unroll
         for (int c = 0; c < CPT; ++c) {
           *reinterpret_cast<f32x4*>(dhbase + (size_t)t * w + 4 * (cq + c * TPR)) = dh[i][c];
-          if (sdx[i] != 0.f) {
+          if constexpr (TW) {
+            accRh[c] += h[i][c] * sdx[i];
+            accR2[c] += h[i][c] * h[i][c] * sdx2[i];
+          } else if (sdx[i] != 0.f) {
             accRh[c] += h[i][c] * sdx[i];
             accR2[c] += h[i][c] * h[i][c] * sdx[i];
           }
@@ -243,9 +292,10 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, Sh
 }
 
 // ---- question pass.  grid ngmax TS nsl, 64 threads: lane = (question g of the group, 4 of the slice's 32 channels)
-template <int G>
+// TW (compile-time): the rows entered as s h: dQs takes dx s (dxs [NQ,K,T], the row pass's), d ct dx as it is
+template <int G, bool TW>
 __global__ __launch_bounds__(64) void attn_shared_bwd_q_kernel(ShShape s, ShBwdShape bs, ShWork sv, ShBwdWork wk,
-                                                              const float* __restrict__ hinfo) {
+                                                              const float* __restrict__ hinfo, const float* __restrict__ dxs) {
   constexpr int JP = SH_BN / G, C4 = SHB_CS / 4;
   __shared__ f32x4 s_acc[SH_BN][C4];
   __shared__ float s_dct[SH_BN];
@@ -271,22 +321,24 @@ __global__ __launch_bounds__(64) void attn_shared_bwd_q_kernel(ShShape s, ShBwdS
     for (int k = 0; k < K; ++k) {
       const float* __restrict__ hrow = hinfo + ((size_t)a * K + k) * T * w + sl * SHB_CS + 4 * c4;
       const float* __restrict__ dxp = wk.dx + ((size_t)q * K + k) * T;
+      const float* __restrict__ dsp = TW ? dxs + ((size_t)q * K + k) * T : nullptr;
       const uint8_t* __restrict__ jp = sv.jmax + ((size_t)q * K + k) * T;
       for (int t4 = tb + 4 * part; t4 < te; t4 += 4 * rep) {  // four rows in flight
-        float dx[4];
+        float dx[4], dm[TW ? 4 : 1];
         int j[4];
         f32x4 h[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int t = min(t4 + i, te - 1);
           dx[i] = t4 + i < te ? dxp[t] : 0.f;
+          if constexpr (TW) dm[i] = dsp[t];
           j[i] = min((int)jp[t], JP - 1);
           h[i] = ld4(hrow + (size_t)t * w);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           if (dx[i] != 0.f) {
-            s_acc[gl * JP + j[i]][c4] += h[i] * dx[i];
+            s_acc[gl * JP + j[i]][c4] += h[i] * (TW ? dm[i] : dx[i]);
             if (sl == 0 && c4 == 0) s_dct[gl * JP + j[i]] += dx[i];
           }
       }
@@ -370,6 +422,210 @@ static int shb_check(const fvta_attn_shared_desc* d, const char* who) {
   return FVTA_OK;
 }
 
+// ================= under the time warp (fvta_attn_shared_bwd_tw): the gradient of fvta_attn_shared_fwd_tw_train ==========
+// The attention saw the rows s h, s[q,t] = tanh(z[q,t]) cnt(t), z = e[a,t] + K (s0 + WC.lq[q]).  The row and question passes
+// above run as their TW instantiations and leave ds [NQ,K,T]; from there the warp's own backward, which never meets a
+// [NQ,K,T,w] tensor either: s is one scalar per (question, position) and only e reads the rows.
+//   a. attn_shared_tw_vec_kernel        v = WH[:w] WC (attn_shared.hip's)
+//   b. attn_shared_bwd_tw_dz_kernel     per question: dz[q,t] = cnt(t) (1 - tanh(z)^2) sum_k ds[q,k,t] (k in index order),
+//                                       Dq[q] = K sum_t dz[q,t] by a fixed tree, d_lq[q] = Dq[q] WC; dbq[q] = sum dbt
+//   c. attn_shared_bwd_tw_de_kernel     de[a,t] = sum of dz[q,t] over the album's questions in plan order (ascending q)
+//   d. attn_shared_bwd_tw_energy_kernel a wave per (album, t), all K rows: d_hinfo += 2 de v h (masked rows too: e sums
+//                                       them), dv partials per workgroup.  An album without a question is skipped: its de
+//                                       is 0 and the row pass has stored its zeros.  One more read of the rows and one
+//                                       read-modify-write of d_hinfo: de depends on every k and every question of the album
+//   e. attn_shared_bwd_tw_dv_kernel     dv = the partials in index order; ds0 = sum_q Dq[q]; db += sum_q dbq[q]
+//   f. attn_shared_bwd_tw_params_kernel dWH_W[:w] += dv (x) WC, dWH_b += ds0 WC, dWC_W += WH^T dv + ds0 b_WH + Dq^T lq,
+//                                       dWC_b += ds0
+struct ShBwdTwWork {
+  ShBwdWork base;
+  float *ds, *dxs, *dbt;  // [NQ,K,T]
+  float* dz;        // [NQ,T]
+  float* de;        // [A,T]
+  float* Dq;        // [NQ]  K sum_t dz
+  float* dbq;       // [NQ]  sum_{k,t} dbt
+  float* v;         // [w]
+  float* dvp;       // [ewg][w]
+  float* dv;        // [w]
+  float* ds0;       // [1]
+  int ewg;
+  size_t bytes;
+  ShBwdTwWork(const ShShape& s, const ShBwdShape& b, void* p) : base(s, b, p) {
+    FvtaCarver c(p);
+    c.off = base.bytes;
+    const size_t nk = (size_t)s.NQ * s.K;
+    const int64_t waves = ((int64_t)s.A * s.T + 3) / 4;
+    ewg = (int)(waves < SHB_E_WGS ? waves : SHB_E_WGS);
+    ds = c.take<float>(nk * s.T);
+    dxs = c.take<float>(nk * s.T);
+    dbt = c.take<float>(nk * s.T);
+    dz = c.take<float>((size_t)s.NQ * s.T);
+    de = c.take<float>((size_t)s.A * s.T);
+    Dq = c.take<float>((size_t)s.NQ);
+    dbq = c.take<float>((size_t)s.NQ);
+    v = c.take<float>((size_t)s.w);
+    dvp = c.take<float>((size_t)ewg * s.w);
+    dv = c.take<float>((size_t)s.w);
+    ds0 = c.take<float>(1);
+    bytes = c.off;
+  }
+};
+
+// the workgroup's 256 values, added by a fixed tree; the result in every thread (the leading barrier: a second call may
+// not write while a thread still reads the first one's result)
+__device__ __forceinline__ float shb_block_tree_sum(float v) {
+  __shared__ float s_red[256];
+  __syncthreads();
+  s_red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s_red[threadIdx.x] += s_red[threadIdx.x + o];
+    __syncthreads();
+  }
+  return s_red[0];
+}
+
+// ---- b.  grid NQ, 256 threads
+__global__ __launch_bounds__(256) void attn_shared_bwd_tw_dz_kernel(ShShape s, int warp_type, int win, const float* __restrict__ tz,
+                                                                   const float* __restrict__ WC, ShBwdTwWork wk,
+                                                                   float* __restrict__ d_lq) {
+  const int q = blockIdx.x, tid = threadIdx.x, T = s.T, K = s.K;
+  float acc = 0.f, accb = 0.f;
+  for (int t = tid; t < T; t += 256) {
+    float sum = 0.f;
+    for (int k = 0; k < K; ++k) {
+      sum += wk.ds[((size_t)q * K + k) * T + t];
+      accb += wk.dbt[((size_t)q * K + k) * T + t];
+    }
+    const float c = tz[(size_t)q * T + t];
+    const float dz = sum * tw_count(t, T, warp_type, win) * (1.f - c * c);
+    wk.dz[(size_t)q * T + t] = dz;
+    acc += dz;
+  }
+  const float D = shb_block_tree_sum(acc) * (float)K;
+  const float dbq = shb_block_tree_sum(accb);
+  if (tid == 0) {
+    wk.Dq[q] = D;
+    wk.dbq[q] = dbq;
+  }
+  for (int c = tid; c < s.w; c += 256) d_lq[(size_t)q * s.w + c] = D * WC[c];
+}
+
+// ---- c.  grid (A, ceil(T / 256)), 256 threads
+__global__ __launch_bounds__(256) void attn_shared_bwd_tw_de_kernel(ShShape s, ShWork sv, ShBwdTwWork wk) {
+  const int a = blockIdx.x, t = blockIdx.y * 256 + threadIdx.x;
+  if (t >= s.T) return;
+  const int q0 = min(max(sv.astart[a], 0), s.NQ), nqa = min(sv.acnt[a], s.NQ - q0);
+  float acc = 0.f;
+  for (int qi = 0; qi < nqa; ++qi) {
+    int q = sv.order[q0 + qi];
+    q = q < 0 ? 0 : (q >= s.NQ ? s.NQ - 1 : q);
+    acc += wk.dz[(size_t)q * s.T + t];
+  }
+  wk.de[(size_t)a * s.T + t] = acc;
+}
+
+// ---- d.  grid ewg, 256 threads: a wave per (album, t), positions strided over the waves; lane l holds channels
+// 256 g + 4 l .. + 3 (CPT = max(1, w / 256) quads)
+template <int CPT>
+__global__ __launch_bounds__(256) void attn_shared_bwd_tw_energy_kernel(ShShape s, ShWork sv, ShBwdTwWork wk,
+                                                                       const float* __restrict__ hinfo,
+                                                                       float* __restrict__ d_hinfo) {
+  __shared__ f32x4 s_dv[3][CPT][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t npos = (int64_t)s.A * s.T, nwv = (int64_t)gridDim.x * 4;
+  const int w = s.w;
+  f32x4 v[CPT], dvacc[CPT];
+#pragma unroll
+  for (int g = 0; g < CPT; ++g) {
+    v[g] = 256 * g + 4 * lane < w ? ld4(wk.v + 256 * g + 4 * lane) : zero4();
+    dvacc[g] = zero4();
+  }
+  for (int64_t pos = (int64_t)blockIdx.x * 4 + wave; pos < npos; pos += nwv) {
+    const int a = (int)(pos / s.T), t = (int)(pos % s.T);
+    if (sv.acnt[a] <= 0) continue;  // (wave-uniform; no barrier inside the loop)
+    const float de = wk.de[pos];
+    for (int k = 0; k < s.K; ++k) {
+      const size_t ro = (((size_t)a * s.K + k) * s.T + t) * w + 4 * lane;
+#pragma unroll
+      for (int g = 0; g < CPT; ++g)
+        if (256 * g + 4 * lane < w) {
+          const f32x4 h = ld4(hinfo + ro + 256 * g);
+          f32x4* dst = reinterpret_cast<f32x4*>(d_hinfo + ro + 256 * g);
+          *dst = *dst + h * v[g] * (2.f * de);
+          dvacc[g] += h * h * de;
+        }
+    }
+  }
+  if (wave)
+#pragma unroll
+    for (int g = 0; g < CPT; ++g) s_dv[wave - 1][g][lane] = dvacc[g];
+  __syncthreads();
+  if (wave) return;
+#pragma unroll
+  for (int g = 0; g < CPT; ++g)
+    if (256 * g + 4 * lane < w) {
+      f32x4 acc = dvacc[g];
+#pragma unroll
+      for (int u = 0; u < 3; ++u) acc += s_dv[u][g][lane];
+      *reinterpret_cast<f32x4*>(wk.dvp + (size_t)blockIdx.x * w + 256 * g + 4 * lane) = acc;
+    }
+}
+
+// ---- e.  grid ceil(w / 64) + 1, 256 threads = 64 channels x 4 thread groups; the last block: ds0 and db
+__global__ __launch_bounds__(256) void attn_shared_bwd_tw_dv_kernel(ShShape s, ShBwdTwWork wk, float* __restrict__ db) {
+  if (blockIdx.x == gridDim.x - 1) {
+    float acc = 0.f, accb = 0.f;
+    for (int q = threadIdx.x; q < s.NQ; q += 256) {
+      acc += wk.Dq[q];
+      accb += wk.dbq[q];
+    }
+    acc = shb_block_tree_sum(acc);
+    accb = shb_block_tree_sum(accb);
+    if (threadIdx.x == 0) {
+      wk.ds0[0] = acc;
+      db[0] += accb;
+    }
+    return;
+  }
+  __shared__ float s_p[4][64];
+  const int part = threadIdx.x >> 6, cl = threadIdx.x & 63, c = blockIdx.x * 64 + cl;
+  s_p[part][cl] = c < s.w ? attn_bwd_sum_rows(wk.dvp, (size_t)wk.ewg, 1, 0, part, s.w, c) : 0.f;
+  __syncthreads();
+  if (part == 0 && c < s.w) wk.dv[c] = (s_p[0][cl] + s_p[1][cl]) + (s_p[2][cl] + s_p[3][cl]);
+}
+
+// ---- f.  grid ceil(w / 64), 256 threads = 64 columns o x 4 thread groups over the rows (WH: [.,w] row-major, the first w rows)
+__global__ __launch_bounds__(256) void attn_shared_bwd_tw_params_kernel(ShShape s, ShBwdTwWork wk, const float* __restrict__ WH,
+                                                                       const float* __restrict__ WHb, const float* __restrict__ WC,
+                                                                       const float* __restrict__ lq, float* __restrict__ dWH,
+                                                                       float* __restrict__ dWHb, float* __restrict__ dWC,
+                                                                       float* __restrict__ dWCb) {
+  __shared__ float s_p[4][64];
+  const int part = threadIdx.x >> 6, cl = threadIdx.x & 63, o = blockIdx.x * 64 + cl, w = s.w;
+  const bool live = o < w;
+  const float wco = live ? WC[o] : 0.f;
+  float acc = 0.f;
+  if (live) {
+    for (int c = part; c < w; c += 4) acc += wk.dv[c] * WH[(size_t)c * w + o];
+    for (int q = part; q < s.NQ; q += 4) acc += wk.Dq[q] * lq[(size_t)q * w + o];
+    for (int c = part; c < w; c += 4) dWH[(size_t)c * w + o] += wk.dv[c] * wco;  // rows w..2w of WH see a zero feature
+  }
+  s_p[part][cl] = acc;
+  __syncthreads();
+  if (part == 0 && live) {
+    const float ds0 = wk.ds0[0];
+    dWC[o] += (s_p[0][cl] + s_p[1][cl]) + (s_p[2][cl] + s_p[3][cl]) + ds0 * WHb[o];
+    dWHb[o] += ds0 * wco;
+    if (o == 0) dWCb[0] += ds0;
+  }
+}
+
+static int shb_check_tw(const fvta_attn_shared_tw_desc* d, const char* who) {
+  if (int e = fvta_attn_shared_check_tw(d, who, true)) return e;
+  return shb_check(&d->shape, who);
+}
+
 }  // namespace fvta
 using namespace fvta;
 
@@ -406,7 +662,8 @@ extern "C" int fvta_attn_shared_bwd(const fvta_attn_shared_desc* d, const float*
   hipLaunchKernelGGL(attn_shared_bwd_prep_kernel, dim3(s.NQ), dim3(s.K > 4 ? 1024 : 256), 0, st, s, sv, wk, d_h_a);
   const dim3 rgrid((unsigned)((int64_t)s.A * s.K * bs.nch));
 #define FVTA_SHB_ROWS(TPR, CPT, RPT) \
-  hipLaunchKernelGGL((attn_shared_bwd_rows_kernel<TPR, CPT, RPT>), rgrid, dim3(256), 0, st, s, bs, sv, wk, hinfo, d_h_a, d_hinfo)
+  hipLaunchKernelGGL((attn_shared_bwd_rows_kernel<TPR, CPT, RPT, false>), rgrid, dim3(256), 0, st, s, bs, sv, wk, hinfo, d_h_a, \
+                     d_hinfo, ShBwdTwArgs{})
   switch (s.w) {
     case 64: FVTA_SHB_ROWS(16, 1, 8); break;
     case 128: FVTA_SHB_ROWS(32, 1, 8); break;
@@ -418,11 +675,77 @@ extern "C" int fvta_attn_shared_bwd(const fvta_attn_shared_desc* d, const float*
 #undef FVTA_SHB_ROWS
   const dim3 qgrid((unsigned)((int64_t)s.ngmax * bs.TS * bs.nsl));
   if (s.G == 8)
-    hipLaunchKernelGGL(attn_shared_bwd_q_kernel<8>, qgrid, dim3(64), 0, st, s, bs, sv, wk, hinfo);
+    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<8, false>), qgrid, dim3(64), 0, st, s, bs, sv, wk, hinfo, (const float*)nullptr);
   else
-    hipLaunchKernelGGL(attn_shared_bwd_q_kernel<4>, qgrid, dim3(64), 0, st, s, bs, sv, wk, hinfo);
+    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<4, false>), qgrid, dim3(64), 0, st, s, bs, sv, wk, hinfo, (const float*)nullptr);
   hipLaunchKernelGGL(attn_shared_bwd_fold_kernel, dim3(s.NQ, (s.w + 255) / 256, bs.JZ), dim3(256), 0, st, s, bs, sv, wk, hq, d_hq);
   hipLaunchKernelGGL(attn_shared_bwd_params_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, st, s, bs, wk, dW, db);
   FVTA_CHECK_LAUNCH("attn_shared_bwd");
+  return FVTA_OK;
+}
+
+extern "C" size_t fvta_attn_shared_tw_bwd_workspace_bytes(const fvta_attn_shared_tw_desc* d) {
+  if (shb_check_tw(d, "attn_shared_tw_bwd_workspace_bytes") != FVTA_OK) return 0;
+  const ShShape s = sh_shape(&d->shape);
+  return ShBwdTwWork(s, shb_shape(s), nullptr).bytes;
+}
+
+extern "C" int fvta_attn_shared_bwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
+                                       const uint8_t* qmask, const float* lq, const int32_t* album, const float* W, const float* b,
+                                       const float* WH_W, const float* WH_b, const float* WC_W, const float* WC_b,
+                                       const float* d_h_a, const void* saved, float* d_hinfo, float* d_hq, float* d_lq, float* dW,
+                                       float* db, float* dWH_W, float* dWH_b, float* dWC_W, float* dWC_b, void* workspace,
+                                       fvta_stream_t stream_) {
+  if (int e = shb_check_tw(d, "attn_shared_bwd_tw")) return e;
+  FVTA_CHECK_ARG(hinfo && hq && lq && album && W && WH_W && WH_b && WC_W && WC_b && d_h_a && saved && d_hinfo && d_hq && d_lq && dW &&
+                     db && dWH_W && dWH_b && dWC_W && dWC_b && workspace,
+                 "attn_shared_bwd_tw: null pointer");
+  hipStream_t st = (hipStream_t)stream_;
+  ShShape s = sh_shape(&d->shape);
+  s.use_mask = (hmask && qmask) ? 1 : 0;
+  const ShBwdShape bs = shb_shape(s);
+  const ShWork sv(s, const_cast<void*>(saved), nullptr);
+  const ShTwSaved ts(s, sv, const_cast<void*>(saved));
+  const ShBwdTwWork tw(s, bs, workspace);
+  const ShBwdWork& wk = tw.base;
+  const ShBwdTwArgs ta{ts.scale, ts.lin, ts.r2, tw.ds, tw.dxs, tw.dbt};
+  const int win = (int)ceilf(d->window_t);
+  hipLaunchKernelGGL(attn_shared_bwd_prep_kernel, dim3(s.NQ), dim3(s.K > 4 ? 1024 : 256), 0, st, s, sv, wk, d_h_a);
+  hipLaunchKernelGGL(attn_shared_tw_vec_kernel, dim3((s.w + 3) / 4), dim3(256), 0, st, s.w, WH_W, WC_W, tw.v);
+  const dim3 rgrid((unsigned)((int64_t)s.A * s.K * bs.nch));
+#define FVTA_SHB_ROWS(TPR, CPT, RPT) \
+  hipLaunchKernelGGL((attn_shared_bwd_rows_kernel<TPR, CPT, RPT, true>), rgrid, dim3(256), 0, st, s, bs, sv, wk, hinfo, d_h_a, \
+                     d_hinfo, ta)
+  switch (s.w) {
+    case 64: FVTA_SHB_ROWS(16, 1, 8); break;
+    case 128: FVTA_SHB_ROWS(32, 1, 8); break;
+    case 256: FVTA_SHB_ROWS(64, 1, 8); break;
+    case 512: FVTA_SHB_ROWS(128, 1, 8); break;
+    case 1024: FVTA_SHB_ROWS(256, 1, 8); break;
+    default: FVTA_SHB_ROWS(256, 2, 4); break;
+  }
+#undef FVTA_SHB_ROWS
+  const dim3 qgrid((unsigned)((int64_t)s.ngmax * bs.TS * bs.nsl));
+  if (s.G == 8)
+    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<8, true>), qgrid, dim3(64), 0, st, s, bs, sv, wk, hinfo, (const float*)tw.dxs);
+  else
+    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<4, true>), qgrid, dim3(64), 0, st, s, bs, sv, wk, hinfo, (const float*)tw.dxs);
+  hipLaunchKernelGGL(attn_shared_bwd_tw_dz_kernel, dim3(s.NQ), dim3(256), 0, st, s, d->warp_type, win, (const float*)ts.tz, WC_W, tw,
+                     d_lq);
+  hipLaunchKernelGGL(attn_shared_bwd_tw_de_kernel, dim3(s.A, (s.T + 255) / 256), dim3(256), 0, st, s, sv, tw);
+  const dim3 egrid((unsigned)tw.ewg);
+  switch (s.w <= 256 ? 1 : s.w / 256) {
+    case 1: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<1>, egrid, dim3(256), 0, st, s, sv, tw, hinfo, d_hinfo); break;
+    case 2: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<2>, egrid, dim3(256), 0, st, s, sv, tw, hinfo, d_hinfo); break;
+    case 4: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<4>, egrid, dim3(256), 0, st, s, sv, tw, hinfo, d_hinfo); break;
+    default: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<8>, egrid, dim3(256), 0, st, s, sv, tw, hinfo, d_hinfo); break;
+  }
+  hipLaunchKernelGGL(attn_shared_bwd_fold_kernel, dim3(s.NQ, (s.w + 255) / 256, bs.JZ), dim3(256), 0, st, s, bs, sv, wk, hq, d_hq);
+  // (db: not the sum of the d ct here -- the row pass says why; the parameter kernel's bias block adds into nothing)
+  hipLaunchKernelGGL(attn_shared_bwd_params_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, st, s, bs, wk, dW, (float*)nullptr);
+  hipLaunchKernelGGL(attn_shared_bwd_tw_dv_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, st, s, tw, db);
+  hipLaunchKernelGGL(attn_shared_bwd_tw_params_kernel, dim3((s.w + 63) / 64), dim3(256), 0, st, s, tw, WH_W, WH_b, WC_W, lq, dWH_W,
+                     dWH_b, dWC_W, dWC_b);
+  FVTA_CHECK_LAUNCH("attn_shared_bwd_tw");
   return FVTA_OK;
 }

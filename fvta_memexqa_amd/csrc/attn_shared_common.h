@@ -95,9 +95,40 @@ struct ShWork {
   }
 };
 
+// Training under the time warp (fvta_attn_shared_fwd_tw_train): `saved` is the training ShWork's share, then these four.
+// The backward (fvta_attn_shared_bwd_tw) reads them; none is the size of the rows.
+struct ShTwSaved {
+  float* scale;  // [NQ,T]   s = tanh(z) cnt(t)
+  float* tz;     // [NQ,T]   tanh(z): cnt(t) >= 1 does not divide out of s exactly
+  float* lin;    // [NQ,K,T] h.Qs[q,j] + Rh.h at j = jmax[q,k,t], before the scale enters
+  float* r2;     // [A,K,T]  R2.h^2
+  size_t bytes;  // of the whole `saved`
+  ShTwSaved(const ShShape& s, const ShWork& wk, void* saved) {
+    FvtaCarver c(saved);
+    c.off = wk.saved_bytes;
+    scale = c.take<float>((size_t)s.NQ * s.T);
+    tz = c.take<float>((size_t)s.NQ * s.T);
+    lin = c.take<float>((size_t)s.NQ * s.K * s.T);
+    r2 = c.take<float>((size_t)s.A * s.K * s.T);
+    bytes = c.off;
+  }
+};
+
+// what the logits kernel takes under the warp: the scale it reads and -- training -- the two pieces it leaves
+struct ShTwArgs {
+  const float* scale;
+  float *lin, *r2;
+};
+
 // 0: fine, else the status with the message set (attn_shared.hip)
 int fvta_attn_shared_check(const fvta_attn_shared_desc* d, const char* who);
 // the same, and simiMatrix 1-3 (training: the cosine form has no shared-context backward)
 int fvta_attn_shared_check_train(const fvta_attn_shared_desc* d, const char* who);
+// under the time warp: the shape, the warp type (1..5: else FVTA_ERR_INVALID_ARG), the window; `train`: simiMatrix 1-3 too
+int fvta_attn_shared_check_tw(const fvta_attn_shared_tw_desc* d, const char* who, bool train = false);
+
+// v[c] = sum_o WH[c][o] WC[o] (attn_shared.hip).  grid ceil(w / 4), 256 threads
+__global__ __launch_bounds__(256) void attn_shared_tw_vec_kernel(int w, const float* __restrict__ WH, const float* __restrict__ WC,
+                                                                 float* __restrict__ v);
 
 }  // namespace fvta

@@ -255,17 +255,28 @@ def album_energy(hinfo, WH_W, WC_W):
 
 
 def attention_3d_shared_warped_raw(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W, WC_b, hinfo_mask=None, hq_mask=None,
-                                   simiMatrix=1, add_tanh=False, warp_type=1, window_t=3.0, energy=None):
-    """attention_3d_shared_raw under the time warp (use_time_warp without use_time_warp_att), forward only: hinfo [A,K,T,w]
+                                   simiMatrix=1, add_tanh=False, warp_type=1, window_t=3.0, energy=None, differentiable=False):
+    """attention_3d_shared_raw under the time warp (use_time_warp without use_time_warp_att): hinfo [A,K,T,w]
     (or [A,K,M,JX,w]) held once, hq [NQ,JQ,w], album [NQ], lq [NQ,w] the questions' last states, W / b as attention_raw,
     the warp's weights as time_warp_raw -> (h_a [NQ,w], a_logits [NQ,K,T,JQ], scale [NQ,T]): for question i, attention_raw
     on time_warp_raw's warp of (hinfo[album[i]], lq[i]), and that warp's scale.  No [NQ,K,T,w] tensor is built: the warp is
     one scalar per (question, position), applied inside the kernels (fvta_attn_shared_fwd_tw).  energy [A,T]: album_energy
-    of (hinfo, WH_W, WC_W), None computes it on the spot.  With gradient mode on and an argument that requires grad it
-    raises, as attention_3d_shared_raw(differentiable=False) does."""
+    of (hinfo, WH_W, WC_W), None computes it on the spot.
+    differentiable=False (the default) is the inference call, forward only: with gradient mode on and an argument that
+    requires grad it raises, as attention_3d_shared_raw(differentiable=False) does.
+    differentiable=True goes through autograd.shared_warped_focal_attention (simiMatrix 1-3; 4 raises NotImplementedError):
+    gradients flow from h_a to hinfo -- summed over each album's questions, [A,K,T,w] -- hq, lq, W, b and the warp's four
+    parameters (WH_W's rows w..2w-1 get zeros: they see a zero feature); a_logits and scale carry none.  A given energy is
+    used as a cached value of the forward; the gradient through e is taken all the same."""
     if simiMatrix not in (1, 2, 3, 4):
         raise ValueError("similarity matrix not implemented")
     _check_warp_type(warp_type)
+    if differentiable and simiMatrix == 4:
+        raise NotImplementedError("attention_3d_shared_warped_raw(differentiable=True): simiMatrix 4 has no shared-context "
+                                  "backward; use the per-question time_warp_raw + attention_raw on hinfo.index_select(0, album)")
+    if differentiable:
+        return _attention_3d_shared_warped_train(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W, WC_b, hinfo_mask, hq_mask, simiMatrix,
+                                                 add_tanh, warp_type, window_t, energy)
     tensors = [t for t in (hinfo, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b) if torch.is_tensor(t)]
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         raise RuntimeError("attention_3d_shared_warped_raw is forward-only: call it under torch.no_grad(), or use the "
@@ -303,6 +314,42 @@ def attention_3d_shared_warped_raw(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W,
         energy = op.album_energy(rows, WH, WC)
     h_a, a, scale = op.forward(rows, hm, _f32(energy).detach().contiguous(), _pad_channels(hq, wp), qm, _pad_channels(lq, wp),
                                idx.to(dev), W, b, WHb, WC, WCb, want_logits=True, want_scale=True)
+    return h_a[:, :w].contiguous(), a, scale
+
+
+def _attention_3d_shared_warped_train(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W, WC_b, hinfo_mask, hq_mask, simiMatrix, add_tanh,
+                                      warp_type, window_t, energy):
+    """attention_3d_shared_warped_raw(differentiable=True): the same checks and the same channel padding, with
+    differentiable torch ops (the gradients come back sliced to w; WH_W's comes back [2w,w] with zeros below row w)"""
+    pad = torch.nn.functional.pad
+    hinfo, hq, lq = _f32(hinfo), _f32(hq), _f32(lq)
+    A, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
+    hinfo = hinfo.reshape(A, K, -1, w)
+    T = hinfo.shape[2]
+    NQ, JQ = hq.shape[0], hq.shape[1]
+    if tuple(lq.shape) != (NQ, w):
+        raise ValueError("lq: expected the questions' last states [%d, %d], got %s" % (NQ, w, tuple(lq.shape)))
+    idx = ops.check_album_index(album, A)
+    if idx.shape[0] != NQ:
+        raise ValueError("album index: %d entries for %d questions" % (idx.shape[0], NQ))
+    if energy is not None and tuple(energy.shape) != (A, T):
+        raise ValueError("energy: expected [%d, %d], got %s" % (A, T, tuple(energy.shape)))
+    wp = next((c for c in SUPPORTED_W if w <= c), None)
+    if wp is None:
+        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
+    F = {1: 3, 2: 2, 3: 4}[simiMatrix]
+    W = _pad_channels(_f32(W).reshape(F, w), wp).reshape(-1)
+    dev = ops.require_gpu()
+    both = hinfo_mask is not None and hq_mask is not None                  # model_v2.py:233: only when BOTH are given
+    hm = ops.as_mask_u8(hinfo_mask.reshape(A, K, T)) if both else None
+    qm = ops.as_mask_u8(hq_mask) if both else None
+    WH = pad(_f32(WH_W).reshape(-1, w)[:w], (0, wp - w, 0, wp - w))         # the first w rows: the rest sees a zero feature
+    WC = pad(_f32(WC_W).reshape(w), (0, wp - w))
+    WHb = pad(_f32(WH_b).reshape(w), (0, wp - w))
+    h_a, a, scale = autograd.shared_warped_focal_attention(
+        _pad_channels(hinfo, wp), _pad_channels(hq, wp), _pad_channels(lq, wp), idx.to(dev), W, _f32(b), WH, WHb, WC,
+        _f32(WC_b).reshape(1), hm, qm, simiMatrix, add_tanh, warp_type, float(window_t),
+        None if energy is None else _f32(energy).detach())
     return h_a[:, :w].contiguous(), a, scale
 
 

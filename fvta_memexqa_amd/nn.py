@@ -111,8 +111,9 @@ class FocalAttention3D(_AttLogits):
         NotImplementedError): h_a's gradient reaches hinfo [A,K,...,w], hq and the parameters, a_logits carries none.
         time_warp (an nn.TimeWarp) with lq [NQ,w], the questions' last states: the attention over the rows warped per
         question -- forward(time_warp(hinfo[album], lq)[0], ...) -- with the rows still held once
-        (functional.attention_3d_shared_warped_raw; inference only).  Its parameters and its window buffer are used;
-        energy [A,T]: functional.album_energy of (hinfo, WH/W, WC/W) when the caller keeps it, else computed here."""
+        (functional.attention_3d_shared_warped_raw; inference only here -- forward_shared_warped() is the training call).
+        Its parameters and its window buffer are used; energy [A,T]: functional.album_energy of (hinfo, WH/W, WC/W) when
+        the caller keeps it, else computed here."""
         W, b = self._wb()
         if time_warp is None and (lq is not None or energy is not None):
             raise ValueError("forward_shared: lq / energy belong to the time warp; pass time_warp (an nn.TimeWarp) with them")
@@ -123,8 +124,8 @@ class FocalAttention3D(_AttLogits):
                 raise ValueError("forward_shared: lq must be [%d, %d], got %s"
                                  % (hq.shape[0], self.w, tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
             if differentiable:
-                raise NotImplementedError("forward_shared: the shared-context attention under the time warp is forward-only; "
-                                          "train through time_warp(hinfo.index_select(0, album), lq) and forward()")
+                raise NotImplementedError("forward_shared: under the time warp this call is the inference one; "
+                                          "forward_shared_warped(hinfo, hq, album, lq, time_warp, ...) trains over the shared rows")
             tw = time_warp
             h_a, a, _ = functional.attention_3d_shared_warped_raw(
                 hinfo, hq, album, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), hinfo_mask, hq_mask,
@@ -132,6 +133,23 @@ class FocalAttention3D(_AttLogits):
             return h_a, a
         return functional.attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask, hq_mask, self.simiMatrix, self.add_tanh,
                                                   differentiable=differentiable)
+
+    def forward_shared_warped(self, hinfo, hq, album, lq, time_warp, hinfo_mask=None, hq_mask=None, energy=None):
+        """The training call under the time warp: forward(time_warp(hinfo[album], lq)[0], hq, ...) for NQ questions over A
+        albums held once -> (h_a [NQ,w], a_logits [NQ,K,T,JQ]); no [NQ,K,T,w] tensor in either direction
+        (functional.attention_3d_shared_warped_raw(differentiable=True); simiMatrix 1-3, 4 raises NotImplementedError).
+        h_a's gradient reaches hinfo [A,K,...,w] (summed over each album's questions), hq, lq, this module's att_logits/{W,b}
+        and time_warp's WH/{W,b}, WC/{W,b}; a_logits carries none.  energy [A,T]: a cached functional.album_energy, used
+        for the forward; the gradient through it is taken all the same."""
+        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
+            raise ValueError("forward_shared_warped: lq must be [%d, %d], got %s"
+                             % (hq.shape[0], self.w, tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
+        W, b = self._wb()
+        tw = time_warp
+        h_a, a, _ = functional.attention_3d_shared_warped_raw(
+            hinfo, hq, album, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), hinfo_mask, hq_mask,
+            self.simiMatrix, self.add_tanh, tw.warp_type, tw.window_t(), energy, differentiable=True)
+        return h_a, a
 
 
 class AlbumMemory:

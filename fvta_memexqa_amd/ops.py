@@ -417,6 +417,56 @@ class SharedWarpedFocalAttention:
                                                ptr(scale), ptr(self.work), stream_ptr()), "fvta_attn_shared_fwd_tw")
         return h_a, a_logits, scale
 
+    def bwd_plan(self):
+        """{rows, tsplit, channels, tiles_per_wg} of the backward's row and question passes: the words of
+        SharedFocalAttention.bwd_plan() for the same shape -- the warp changes none (host only, simiMatrix 1-3)"""
+        out = (ctypes.c_int32 * 4)()
+        check(self.lib.fvta_attn_shared_bwd_plan(ctypes.byref(self.desc.shape), out), "fvta_attn_shared_bwd_plan")
+        return dict(zip(("rows", "tsplit", "channels", "tiles_per_wg"), (int(v) for v in out)))
+
+    def forward_train(self, hinfo, hmask, energy, hq, qmask, lq, album, W, b, WH_b, WC_W, WC_b, want_logits=False,
+                      want_scale=False):
+        """forward() -- the same bits -- that leaves in self.saved (allocated on first use) what backward() reads
+        (fvta_attn_shared_fwd_tw_train; simiMatrix 1-3)"""
+        assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
+        assert tuple(energy.shape) == (self.A, self.T) and tuple(lq.shape) == (self.NQ, self.w)
+        assert album.is_cuda and album.dtype == torch.int32 and album.is_contiguous() and tuple(album.shape) == (self.NQ,)
+        assert WH_b.numel() == self.w and WC_W.numel() == self.w and WC_b.numel() == 1
+        if getattr(self, "saved", None) is None:
+            self.saved = _sized(self, "fvta_attn_shared_tw_saved_bytes", "shared attention under the time warp, saved: ")
+        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
+        a_logits = torch.empty(self.NQ, self.K, self.T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
+        scale = torch.empty(self.NQ, self.T, device=self.dev, dtype=torch.float32) if want_scale else None
+        check(self.lib.fvta_attn_shared_fwd_tw_train(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(energy)),
+                                                     ptr(_f32c(hq)), ptr(qmask), ptr(_f32c(lq)), ptr(album), ptr(_f32c(W)), ptr(b),
+                                                     ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)), ptr(h_a),
+                                                     ptr(a_logits), ptr(scale), ptr(self.saved), ptr(self.work), stream_ptr()),
+              "fvta_attn_shared_fwd_tw_train")
+        return h_a, a_logits, scale
+
+    def backward(self, hinfo, hmask, hq, qmask, lq, album, W, b, WH_W, WH_b, WC_W, WC_b, d_h_a, d_hinfo, d_hq, d_lq, dW, db,
+                 dWH_W, dWH_b, dWC_W, dWC_b):
+        """After forward_train() with the same arguments: d_hinfo [A,K,T,w], d_hq [NQ,JQ,w] and d_lq [NQ,w] are overwritten;
+        dW [F], db [1], dWH_W (its first w rows, [w,w]), dWH_b [w], dWC_W [w] and dWC_b [1] accumulated into
+        (fvta_attn_shared_bwd_tw).  WH_W: [2w,w] or its first w rows.  Its workspace is allocated on first use."""
+        if getattr(self, "saved", None) is None:
+            raise _lib.FvtaError("shared attention under the time warp: backward() needs a forward_train() first")
+        if getattr(self, "work_bwd", None) is None:
+            self.work_bwd = _sized(self, "fvta_attn_shared_tw_bwd_workspace_bytes",
+                                   "shared attention under the time warp, backward workspace: ")
+        assert tuple(d_hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(d_hq.shape) == (self.NQ, self.JQ, self.w)
+        assert tuple(d_h_a.shape) == (self.NQ, self.w) and tuple(d_lq.shape) == (self.NQ, self.w)
+        assert WH_W.numel() >= self.w * self.w and dWH_W.numel() >= self.w * self.w
+        assert dWH_b.numel() == self.w and dWC_W.numel() == self.w and dWC_b.numel() == 1
+        for t in (d_hinfo, d_hq, d_lq, dW, db, dWH_W, dWH_b, dWC_W, dWC_b):
+            assert t.is_contiguous() and t.dtype == torch.float32, "gradient outputs are written in place"
+        check(self.lib.fvta_attn_shared_bwd_tw(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)), ptr(qmask),
+                                               ptr(_f32c(lq)), ptr(album), ptr(_f32c(W)), ptr(b), ptr(_f32c(WH_W)),
+                                               ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)), ptr(_f32c(d_h_a)),
+                                               ptr(self.saved), ptr(d_hinfo), ptr(d_hq), ptr(d_lq), ptr(dW), ptr(db), ptr(dWH_W),
+                                               ptr(dWH_b), ptr(dWC_W), ptr(dWC_b), ptr(self.work_bwd), stream_ptr()),
+              "fvta_attn_shared_bwd_tw")
+
 
 def linear_fwd(x, W, b, y, M, din, dout, add_tanh=False, blk=None):
     """y [M,dout] = x [M,din] W [din,dout] + b (+ tanh); blk = (rows_per_blk, blk_stride): x rows in blocks"""

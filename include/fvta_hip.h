@@ -142,7 +142,8 @@ int fvta_attn_bwd_tw(const fvta_attn_desc* d, const float* hinfo, const float* h
  *   kernels clamp them into [0, A) before they address anything; a binding validates them on the host
  *   (ops.check_album_index does).
  *   W, b: as fvta_attn_fwd (feature order of model_v2.py:242-254; simi 4 takes NULL).  a_logits [NQ,K,T,JQ] or NULL.
- * The time warp (use_time_warp, every warp type) is covered by fvta_attn_shared_fwd_tw further down, forward only: the
+ * The time warp (use_time_warp, every warp type) is covered by fvta_attn_shared_fwd_tw further down (training:
+ * fvta_attn_shared_fwd_tw_train / fvta_attn_shared_bwd_tw): the
  * warp is one scalar per (question, position), so the rows stay shared.  Not here, nor there: time_warp_att (a masked row
  * takes the softmax where its scale is negative), shadow rows, and a backward of THIS call -- it keeps no `saved`;
  * fvta_attn_shared_fwd_train / fvta_attn_shared_bwd below train over the shared rows (simiMatrix 1-3, no time warp),
@@ -183,7 +184,8 @@ int fvta_attn_shared_fwd(const fvta_attn_shared_desc* d, const float* hinfo, con
  *   softmax over it, as in fvta_attn_bwd); dW [F] and db [1] are accumulated into.  fvta_attn_bwd's deviations carry
  *   over: the max over j routes to the first arg-max, ties of the max over t are split, a fully masked (album, k) or
  *   question passes nothing into its masked logits.  The same arguments as the forward call; `workspace`:
- *   fvta_attn_shared_bwd_workspace_bytes.  Not here: time warp, shadow rows, accumulate modes, the gradient of a_logits.
+ *   fvta_attn_shared_bwd_workspace_bytes.  Not here: shadow rows, accumulate modes, the gradient of a_logits; under the
+ *   time warp fvta_attn_shared_bwd_tw (further down) is the call.
  *   No [NQ,K,T,w]-sized buffer: each d_hinfo row is written once, rows are read once per (album, k) and once per group of
  *   the album's questions.  No floating-point atomics, fixed summation order (the sum over an album's questions runs by
  *   ascending question index): two calls are bitwise equal in all four outputs.  No host synchronisation.
@@ -200,7 +202,7 @@ int fvta_attn_shared_bwd(const fvta_attn_shared_desc* d, const float* hinfo, con
                          const void* saved, float* d_hinfo, float* d_hq, float* dW, float* db, void* workspace,
                          fvta_stream_t stream);
 
-/* fvta_attn_shared_fwd under the time warp (use_time_warp without use_time_warp_att; forward only).  The warp of
+/* fvta_attn_shared_fwd under the time warp (use_time_warp without use_time_warp_att).  The warp of
  * model_v2.py:953-1009 (fvta_timewarp_fwd below) takes the question's last state lq, but it is one scalar per
  * (question, position):
  *   h'[q,k,t,:] = hinfo[a,k,t,:] scale[q,t]                               a = album[q]
@@ -233,6 +235,38 @@ int fvta_attn_shared_fwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinf
                             const float* hq, const uint8_t* qmask, const float* lq, const int32_t* album, const float* W,
                             const float* b, const float* WH_b, const float* WC_W, const float* WC_b, float* h_a,
                             float* a_logits, float* scale_out, void* workspace, fvta_stream_t stream);
+
+/* Training under the time warp over shared rows (simiMatrix 1-3; with simi 4 the two size queries return 0 and the calls
+ * FVTA_ERR_UNSUPPORTED; a warp type outside 1..5: 0 and FVTA_ERR_INVALID_ARG).
+ * fvta_attn_shared_fwd_tw_train: the kernels of fvta_attn_shared_fwd_tw -- h_a, a_logits and scale_out are its bits --
+ *   with the ordered plan of fvta_attn_shared_fwd_train, and in the caller-held `saved` (fvta_attn_shared_tw_saved_bytes)
+ *   what fvta_attn_shared_fwd_train saves, then scale [NQ,T], tanh(z) [NQ,T], lin [NQ,K,T] (h.Qs + Rh.h at the arg-max,
+ *   before the scale enters) and r2 [A,K,T] (R2.h^2).  `workspace`: fvta_attn_shared_tw_workspace_bytes.
+ * fvta_attn_shared_bwd_tw: from d_h_a [NQ,w], for question i what fvta_timewarp_fwd -> fvta_attn_fwd -> fvta_attn_bwd
+ *   (accumulate 0, masked rows zero) -> fvta_timewarp_bwd give on (hinfo[album[i]], lq[i], hq[i], ...), the row gradients
+ *   summed per album, the parameter gradients over all questions.  d_hinfo [A,K,T,w], d_hq [NQ,JQ,w] and d_lq [NQ,w] are
+ *   OVERWRITTEN (an album without a question: zeros); dW [F], db [1], dWH_W (its first w rows, [w,w]; rows w..2w-1 have no
+ *   gradient and are not touched), dWH_b [w], dWC_W [w] and dWC_b [1] are accumulated into.  fvta_attn_bwd's deviations
+ *   carry over (first arg-max over j, ties over t split, a fully masked (album, k) or question).  window_t has no gradient.
+ *   db is summed as -sum damax x^2 (tanh; 0 without): the same number as the sum of the d ct without its cancellation.
+ *   The energy is not an argument: tanh(z) is in `saved`, and the gradient through e reaches d_hinfo, dWH_W and dWC_W.
+ *   No time_warp_att, no shadow rows, no gradient of a_logits or scale_out.  No [NQ,K,T,w]-sized buffer; each d_hinfo row
+ *   is written once by the row pass and read and written once more by the energy's backward; the rows are read once per
+ *   (album, k), once per group of the album's questions and once for the energy.  No floating-point atomics, fixed
+ *   summation order (an album's questions by ascending index): two calls are bitwise equal in all nine outputs.  No host
+ *   synchronisation, no memset.  `workspace`: fvta_attn_shared_tw_bwd_workspace_bytes. */
+size_t fvta_attn_shared_tw_saved_bytes(const fvta_attn_shared_tw_desc* d);         /* 0 bytes: see fvta_last_error */
+size_t fvta_attn_shared_tw_bwd_workspace_bytes(const fvta_attn_shared_tw_desc* d); /* 0 bytes: see fvta_last_error */
+int fvta_attn_shared_fwd_tw_train(const fvta_attn_shared_tw_desc* d, const float* hinfo, const uint8_t* hmask,
+                                  const float* energy, const float* hq, const uint8_t* qmask, const float* lq,
+                                  const int32_t* album, const float* W, const float* b, const float* WH_b, const float* WC_W,
+                                  const float* WC_b, float* h_a, float* a_logits, float* scale_out, void* saved, void* workspace,
+                                  fvta_stream_t stream);
+int fvta_attn_shared_bwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
+                            const uint8_t* qmask, const float* lq, const int32_t* album, const float* W, const float* b,
+                            const float* WH_W, const float* WH_b, const float* WC_W, const float* WC_b, const float* d_h_a,
+                            const void* saved, float* d_hinfo, float* d_hq, float* d_lq, float* dW, float* db, float* dWH_W,
+                            float* dWH_b, float* dWC_W, float* dWC_b, void* workspace, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * bi-LSTM modality encoders: model_v2.py:652-661 (cells), 667-678 (lengths),

@@ -16,25 +16,46 @@ struct ShShape {
   int JP, G;      // padded question length (32 / 64), questions per group (8 / 4)
   int ntile;      // row tiles of a (k): ceil(T / SH_R)
   int S, rps;     // T splits of the weighted sum, rows per split
-  int ngmax;      // upper bound of the number of groups: floor(NQ / G) + min(A, NQ), at most NQ
+  int ngmax;      // upper bound of the number of groups: floor(NR / G) + min(A, NR), at most NR
+  // A reference is what a column block of a group's product stands for.  Shared context: a question (M = 1, NR = NQ,
+  // TO = T).  Album pool (attn_pool.hip): a (question, slot) pair -- A = P pooled albums of T = JX rows each, M slots per
+  // question, NR = NQ M references, TO = M T positions per question
+  int M, NR, TO;
 };
+
+// the derived words, from A, NQ, K, T, JQ, M
+inline void sh_derive(ShShape& s) {
+  s.use_mask = 0;
+  s.NR = s.NQ * s.M;
+  s.TO = s.M * s.T;
+  s.JP = s.JQ <= 32 ? 32 : 64;
+  s.G = SH_BN / s.JP;
+  s.ntile = (s.T + SH_R - 1) / SH_R;
+  const int64_t ng = (int64_t)s.NR / s.G + (s.A < s.NR ? s.A : s.NR);
+  s.ngmax = (int)(ng < s.NR ? ng : s.NR);
+  // about 1024 workgroups of the weighted sum (4 per CU), a split not shorter than one chunk
+  int64_t S = (1024 + (int64_t)s.ngmax * s.K - 1) / ((int64_t)s.ngmax * s.K);
+  const int maxs = (s.T + SH_CH - 1) / SH_CH;
+  if (S > maxs) S = maxs;
+  if (S < 1) S = 1;
+  s.rps = (int)((s.T + S - 1) / S);
+  s.S = (s.T + s.rps - 1) / s.rps;
+}
 
 inline ShShape sh_shape(const fvta_attn_shared_desc* d) {
   ShShape s;
   s.A = d->A, s.NQ = d->NQ, s.K = d->K, s.T = d->T, s.JQ = d->JQ, s.w = d->w, s.simi = d->simi, s.add_tanh = d->add_tanh;
-  s.use_mask = 0;
-  s.JP = d->JQ <= 32 ? 32 : 64;
-  s.G = SH_BN / s.JP;
-  s.ntile = (d->T + SH_R - 1) / SH_R;
-  const int64_t ng = (int64_t)d->NQ / s.G + (d->A < d->NQ ? d->A : d->NQ);
-  s.ngmax = (int)(ng < d->NQ ? ng : d->NQ);
-  // about 1024 workgroups of the weighted sum (4 per CU), a split not shorter than one chunk
-  int64_t S = (1024 + (int64_t)s.ngmax * d->K - 1) / ((int64_t)s.ngmax * d->K);
-  const int maxs = (d->T + SH_CH - 1) / SH_CH;
-  if (S > maxs) S = maxs;
-  if (S < 1) S = 1;
-  s.rps = (int)((d->T + S - 1) / S);
-  s.S = (d->T + s.rps - 1) / s.rps;
+  s.M = 1;
+  sh_derive(s);
+  return s;
+}
+
+// the pooled call's shape (checked by fvta_attn_pool_check: NQ M and M JX are within range)
+inline ShShape sh_pool_shape(const fvta_attn_pool_desc* d) {
+  ShShape s;
+  s.A = d->P, s.NQ = d->NQ, s.K = d->K, s.T = d->JX, s.JQ = d->JQ, s.w = d->w, s.simi = d->simi, s.add_tanh = d->add_tanh;
+  s.M = d->M;
+  sh_derive(s);
   return s;
 }
 
@@ -53,15 +74,15 @@ struct ShWork {
     vecs = c.take<float>((size_t)VEC_COUNT * s.w);
     Qs = c.take<float>((size_t)s.NQ * s.JP * s.w);
     ct = c.take<float>((size_t)s.NQ * s.JP);
-    amax = c.take<float>((size_t)s.NQ * s.K * s.T);
+    amax = c.take<float>((size_t)s.NQ * s.K * s.TO);
     M = c.take<float>((size_t)s.NQ * s.K);
     coef = c.take<float>((size_t)s.NQ * s.K);
     part = c.take<float>((size_t)s.ngmax * s.K * s.S * s.G * s.w);
     acnt = c.take<int>((size_t)s.A);
     astart = c.take<int>((size_t)s.A);
     agrp = c.take<int>((size_t)s.A);
-    order = c.take<int>((size_t)s.NQ);
-    qslot = c.take<int>((size_t)s.NQ);
+    order = c.take<int>((size_t)s.NR);
+    qslot = c.take<int>((size_t)s.NR);
     ngroups = c.take<int>(1);
     grp = c.take<int4>((size_t)s.ngmax);
     bytes = c.off;

@@ -36,6 +36,7 @@ extern "C" int64_t fvta_abi_struct_bytes(int32_t which) {
     case 11: return (int64_t)sizeof(fvta_cbp_desc);
     case 12: return (int64_t)sizeof(fvta_attn_shared_desc);
     case 13: return (int64_t)sizeof(fvta_attn_shared_tw_desc);
+    case 14: return (int64_t)sizeof(fvta_attn_pool_desc);
     default: return -1;
   }
 }

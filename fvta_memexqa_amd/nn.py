@@ -152,6 +152,54 @@ class FocalAttention3D(_AttLogits):
         return h_a, a
 
 
+    def forward_pooled(self, pool, hq, albums, pool_mask=None, hq_mask=None):
+        """forward() for NQ questions that each list M albums of one pool: pool [P,K,JX,w], hq [NQ,JQ,w], albums [NQ,M]
+        (entries in [0, P), -1 an empty slot -- which needs both masks) -> (h_a [NQ,w], a_logits [NQ,K,M*JX,JQ]) with this
+        module's att_logits/{W,b} (functional.attention_3d_pooled_raw): forward() on each question's albums laid end to
+        end, with no such tensor built.  Inference only: under gradient mode the parameters require grad and the call
+        raises; use it under torch.no_grad()."""
+        W, b = self._wb()
+        return functional.attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask, hq_mask, self.simiMatrix, self.add_tanh)
+
+
+class AlbumPool:
+    """P encoded albums, each kept ONCE for any number of questions and any album lists: pool [P,K,JX,w] and pool_mask
+    [P,K,JX], held contiguous fp32 / u8 on the device and detached.  Where nn.AlbumMemory keeps one context per distinct
+    LIST of albums, this keeps one block of rows per ALBUM and every question names the albums it reads (MemexQA's
+    album_ids).  No parameters, no encoder."""
+
+    def __init__(self, pool, pool_mask=None):
+        dev = ops.require_gpu()
+        if pool.dim() != 4:
+            raise ValueError("AlbumPool: expected [P,K,JX,w], got shape %s" % (tuple(pool.shape),))
+        self.pool = pool.detach().to(dev, torch.float32).contiguous()
+        self.pool_mask = None if pool_mask is None else ops.as_mask_u8(pool_mask.detach().to(dev))
+        if self.pool_mask is not None and tuple(self.pool_mask.shape) != tuple(self.pool.shape[:3]):
+            raise ValueError("AlbumPool: mask %s does not match the rows %s" % (tuple(pool_mask.shape), tuple(pool.shape)))
+
+    def __len__(self):
+        return self.pool.shape[0]
+
+    @classmethod
+    def from_context(cls, hall, hall_mask=None):
+        """The context tensor functional.context_tensor produces, hall [N,K,M,JX,w] / hall_mask [N,K,M,JX], cut into its
+        albums: (pool of P = N*M albums, albums [N,M] = arange(N*M): question n's own M albums in order)."""
+        if hall.dim() != 5:
+            raise ValueError("AlbumPool.from_context: expected [N,K,M,JX,w], got shape %s" % (tuple(hall.shape),))
+        N, K, M, JX, w = hall.shape
+        pool = hall.detach().permute(0, 2, 1, 3, 4).reshape(N * M, K, JX, w)
+        mask = None if hall_mask is None else hall_mask.detach().reshape(N, K, M, JX).permute(0, 2, 1, 3).reshape(N * M, K, JX)
+        return cls(pool, mask), torch.arange(N * M, dtype=torch.int32).reshape(N, M)
+
+    def attend(self, attention, hq, hq_mask, albums):
+        """(h_a [NQ,w], a_logits [NQ,K,M*JX,JQ]) of `attention` (an nn.FocalAttention3D) for questions hq [NQ,JQ,w] that list
+        albums [NQ,M] of this pool; a bad list raises ValueError before anything reaches the library."""
+        idx = ops.check_album_lists(albums, len(self), self.pool_mask is not None and hq_mask is not None)
+        if idx.shape[0] != hq.shape[0]:
+            raise ValueError("album lists: %d lists for %d questions" % (idx.shape[0], hq.shape[0]))
+        return attention.forward_pooled(self.pool, hq, idx, self.pool_mask, hq_mask)
+
+
 class AlbumMemory:
     """The context of A encoded albums, kept for any number of questions: hall [A,K,T,w] (or [A,K,M,JX,w]) and hall_mask
     [A,K,T] as functional.context_tensor returns them, held contiguous fp32 / u8 on the device and detached.  No

@@ -375,6 +375,77 @@ class SharedFocalAttention:
                                             ptr(self.work_bwd), stream_ptr()), "fvta_attn_shared_bwd")
 
 
+# ------------------------------------------------------------------ attention, per-question album lists over one pool
+def check_album_lists(albums, P, masked):
+    """Host-side validation of per-question album lists, before they are uploaded (the kernels only clamp them): a
+    [NQ,M] integer tensor / array, or a list of lists -- ragged lists are padded with -1 (an empty slot) to the longest.
+    Every entry lies in [-1, P); -1 needs masked=True (an empty slot is masked rows, and the attention masks only when
+    both masks are given).  Returns a contiguous int32 CPU tensor [NQ,M].  Pure host: no GPU, no library."""
+    if not torch.is_tensor(albums) and not hasattr(albums, "shape"):
+        rows = [list(r) if isinstance(r, (list, tuple)) else r for r in list(albums)]
+        if len(rows) == 0:
+            raise ValueError("album lists: no question")
+        if all(isinstance(r, list) for r in rows):
+            M = max(len(r) for r in rows)
+            rows = [r + [-1] * (M - len(r)) for r in rows]
+        albums = rows
+    t = albums if torch.is_tensor(albums) else torch.as_tensor(albums)
+    if t.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+        if t.numel() == 0:
+            raise ValueError("album lists: empty (shape %s)" % (tuple(t.shape),))
+        raise ValueError("album lists: an integer dtype is needed, got %s" % t.dtype)
+    if t.dim() != 2:
+        raise ValueError("album lists: expected two dimensions [NQ,M], got shape %s" % (tuple(t.shape),))
+    if t.shape[0] == 0 or t.shape[1] == 0:
+        raise ValueError("album lists: empty (NQ = %d, M = %d)" % (t.shape[0], t.shape[1]))
+    t = t.detach().cpu()
+    lo, hi = int(t.min()), int(t.max())
+    if lo < -1 or hi >= int(P):
+        raise ValueError("album lists: values must lie in [-1, %d) (-1: an empty slot), got [%d, %d]" % (int(P), lo, hi))
+    if lo < 0 and not masked:
+        raise ValueError("album lists: an empty slot (-1) needs both masks: without them the attention masks nothing, "
+                         "and an empty slot is masked rows")
+    return t.to(torch.int32).contiguous()
+
+
+class PooledFocalAttention:
+    """attention_3d (model_v2.py:210-298) of NQ questions that each list M albums of ONE pool of P encoded albums: pool
+    [P,K,JX,w], pool_mask [P,K,JX], hq [NQ,JQ,w], qmask [NQ,JQ], albums [NQ,M] int32 on the device (validate them with
+    check_album_lists before the upload; -1 is an empty slot).  Question i gets FocalAttention's result on its albums' rows
+    laid end to end, [K, M*JX, w], which is never built.  Inference only (fvta_attn_pool_fwd, nothing kept)."""
+
+    def __init__(self, P, NQ, M, K, JX, JQ, w, simi, add_tanh):
+        self.lib = _lib.load()
+        self.dev = require_gpu()
+        self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w = int(P), int(NQ), int(M), int(K), int(JX), int(JQ), int(w)
+        self.desc = _lib.AttnPoolDesc(self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w, int(simi), int(bool(add_tanh)))
+        nb = self.lib.fvta_attn_pool_workspace_bytes(ctypes.byref(self.desc))
+        if nb == 0:
+            raise _lib.FvtaError("pooled attention: " + self.lib.fvta_last_error().decode())
+        self.work = _bytes(nb, self.dev)
+
+    def plan(self):
+        """{G, rows, tsplit, rows_per_split}: references per group, rows per logits tile, splits of JX in the weighted sum
+        and the rows of one split (host only)"""
+        out = (ctypes.c_int32 * 4)()
+        check(self.lib.fvta_attn_pool_plan(ctypes.byref(self.desc), out), "fvta_attn_pool_plan")
+        return dict(zip(("G", "rows", "tsplit", "rows_per_split"), (int(v) for v in out)))
+
+    def forward(self, pool, pool_mask, hq, qmask, albums, W, b, want_logits=False):
+        assert tuple(pool.shape) == (self.P, self.K, self.JX, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
+        assert albums.is_cuda and albums.dtype == torch.int32 and albums.is_contiguous() and \
+            tuple(albums.shape) == (self.NQ, self.M)
+        assert pool_mask is None or (pool_mask.dtype == torch.uint8 and tuple(pool_mask.shape) == (self.P, self.K, self.JX))
+        assert qmask is None or (qmask.dtype == torch.uint8 and tuple(qmask.shape) == (self.NQ, self.JQ))
+        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
+        a_logits = torch.empty(self.NQ, self.K, self.M * self.JX, self.JQ, device=self.dev, dtype=torch.float32) \
+            if want_logits else None
+        check(self.lib.fvta_attn_pool_fwd(ctypes.byref(self.desc), ptr(_f32c(pool)), ptr(pool_mask), ptr(_f32c(hq)), ptr(qmask),
+                                          ptr(albums), ptr(W), ptr(b), ptr(h_a), ptr(a_logits), ptr(self.work),
+                                          stream_ptr()), "fvta_attn_pool_fwd")
+        return h_a, a_logits
+
+
 class SharedWarpedFocalAttention:
     """SharedFocalAttention.forward under the time warp (model_v2.py:953-1009, use_time_warp without use_time_warp_att;
     forward only): question i gets FocalAttention's result on TimeWarp's warp of (hinfo[album[i]], lq[i]), from the rows

@@ -47,7 +47,7 @@ const char* fvta_last_error(void);
 /* sizeof of a descriptor struct as the library was compiled: which = 0 fvta_attn_desc, 1 fvta_lstm_desc,
  * 2 fvta_scorer_desc, 3 fvta_timewarp_desc, 4 fvta_embed_desc, 5 fvta_imgtrans_desc, 6 fvta_guard_desc,
  * 7 fvta_guard_ctl, 9 fvta_attgru_seq_desc, 10 fvta_gru_seq_desc, 11 fvta_cbp_desc, 12 fvta_attn_shared_desc,
- * 13 fvta_attn_shared_tw_desc (8 stays unassigned: bindings probe it as the unknown id); -1 otherwise.
+ * 13 fvta_attn_shared_tw_desc, 14 fvta_attn_pool_desc (8 stays unassigned: bindings probe it as the unknown id); -1 otherwise.
  * A binding compares
  * its own layout with it when it loads the library (fvta_memexqa_amd/_lib.py does). */
 int64_t fvta_abi_struct_bytes(int32_t which);
@@ -267,6 +267,41 @@ int fvta_attn_shared_bwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinf
                             const float* WH_W, const float* WH_b, const float* WC_W, const float* WC_b, const float* d_h_a,
                             const void* saved, float* d_hinfo, float* d_hq, float* d_lq, float* dW, float* db, float* dWH_W,
                             float* dWH_b, float* dWC_W, float* dWC_b, void* workspace, fvta_stream_t stream);
+
+/* Focal attention over per-question album LISTS from one album pool (forward only, inference).  The encoders run per
+ * (question, album) (model_v2.py:704-760), so the JX context rows of one album do not depend on which albums stand beside
+ * it: pool [P,K,JX,w] / pool_mask [P,K,JX] hold every encoded album once, and question i lists M of them,
+ * albums [NQ,M] int32 on the DEVICE: entries in [0, P), or negative for an EMPTY slot.  With T = M JX,
+ *   hinfo_i[k, m JX + j] = pool[albums[i,m], k, j]   (an empty slot: JX zero rows, mask 0)
+ *   h_a[i], a_logits[i] = what fvta_attn_fwd returns for (hinfo_i, hq[i], its mask, qmask[i]);
+ * no [NQ,K,T,w] tensor exists anywhere.  h_a [NQ,w], a_logits [NQ,K,T,JQ] or NULL.  The same album may stand twice in one
+ * list; an album nobody lists is never read; a question whose slots are all empty gets h_a = 0 (the uniform softmax over
+ * T zero rows).  Indices are data: the kernels take a negative entry as empty and clamp an entry >= P to P - 1 before it
+ * addresses anything; a binding validates them on the host (ops.check_album_lists does).
+ * The masks apply only when both are given, as everywhere; an EMPTY SLOT IS MASKED ALL THE SAME (its positions hold
+ * -1e30 whether or not masks are given), which is no longer the reference's unmasked result: a binding refuses empty
+ * slots without masks (ops.check_album_lists(masked=False) does).
+ * The kernels are fvta_attn_shared_fwd's with a column block of a group's product standing for a (question, slot)
+ * reference instead of a question: the NQ M references are grouped by pooled album on the device (counting sort, groups
+ * of at most G), a pooled album's rows are read twice per group of references to it, however many distinct lists there
+ * are.  The softmax runs per question over its T positions; h_a[i] is the sum of its references' partial sums in
+ * (k, slot, split) order.  No floating-point atomics, splits from the descriptor only: two calls are bitwise equal, so is
+ * a call after relabelling the pool, and at M = 1 the call returns fvta_attn_shared_fwd's bits for (A = P, T = JX).
+ * Range: fvta_attn_shared_fwd's (w, JQ <= 64, K <= 64, simi 1..4), P, NQ, M, JX >= 1, NQ M <= 2^28, M JX within int.
+ * No host synchronisation, no memset, everything on the caller's stream.
+ * fvta_attn_pool_plan (host only): out = {G, rows per logits tile, splits of JX in the weighted sum, rows per split}.
+ * Not here: the time warp, training, shadow rows. */
+typedef struct fvta_attn_pool_desc {
+  int32_t P, NQ, M, K, JX, JQ, w; /* P pooled albums [P,K,JX,w], NQ questions listing M albums each */
+  int32_t simi;                   /* 1..4 */
+  int32_t add_tanh;
+} fvta_attn_pool_desc; /* fvta_abi_struct_bytes(14) */
+
+size_t fvta_attn_pool_workspace_bytes(const fvta_attn_pool_desc* d); /* 0 bytes: see fvta_last_error */
+int fvta_attn_pool_plan(const fvta_attn_pool_desc* d, int32_t out[4]);
+int fvta_attn_pool_fwd(const fvta_attn_pool_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
+                       const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a,
+                       float* a_logits, void* workspace, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * bi-LSTM modality encoders: model_v2.py:652-661 (cells), 667-678 (lengths),

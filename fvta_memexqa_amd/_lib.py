@@ -69,6 +69,10 @@ class AttnPoolDesc(Structure):
     _fields_ = [(n, c_int32) for n in ("P", "NQ", "M", "K", "JX", "JQ", "w", "simi", "add_tanh")]
 
 
+class AttnPoolTwDesc(Structure):
+    _fields_ = [("shape", AttnPoolDesc), ("warp_type", c_int32), ("window_t", c_float)]
+
+
 CTX_KMAX = 8
 
 
@@ -154,6 +158,9 @@ _SIGS = {
     "fvta_attn_pool_workspace_bytes": (c_size_t, [POINTER(AttnPoolDesc)]),
     "fvta_attn_pool_plan": (c_int, [POINTER(AttnPoolDesc), POINTER(c_int32)]),
     "fvta_attn_pool_fwd": (c_int, [POINTER(AttnPoolDesc), P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_attn_pool_tw_workspace_bytes": (c_size_t, [POINTER(AttnPoolTwDesc)]),
+    "fvta_attn_pool_energy": (c_int, [POINTER(AttnPoolTwDesc), P, P, P, P, P, P]),
+    "fvta_attn_pool_fwd_tw": (c_int, [POINTER(AttnPoolTwDesc)] + [P] * 17),
     "fvta_timewarp_workspace_bytes": (c_size_t, [POINTER(TimewarpDesc)]),
     "fvta_timewarp_fwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_bwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
@@ -240,7 +247,7 @@ def load():
     # the descriptor structs are declared twice (include/fvta_hip.h and above): refuse a library whose layout differs
     for which, cls in list(enumerate((AttnDesc, LstmDesc, ScorerDesc, TimewarpDesc, EmbedDesc, ImgTransDesc, GuardDesc, GuardCtl))) + \
             [(9, AttGruSeqDesc), (10, GruSeqDesc), (11, CbpDesc), (12, AttnSharedDesc), (13, AttnSharedTwDesc),
-             (14, AttnPoolDesc)]:
+             (14, AttnPoolDesc), (15, AttnPoolTwDesc)]:
         have, want = ctypes.sizeof(cls), lib.fvta_abi_struct_bytes(which)
         if have != want:
             raise FvtaError("%s is %d bytes here but %d in %s: rebuild the library (descriptor layouts differ)"

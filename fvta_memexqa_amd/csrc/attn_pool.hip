@@ -24,7 +24,14 @@
 // are; an album nobody lists is never read.  Determinism: as attn_shared.hip -- no floating-point atomics, the splits
 // depend on the descriptor only, a reference's numbers do not depend on its group, block or wave.  At M = 1 every launch
 // computes what attn_shared.hip's does: the same bits.
+//
+// Under the time warp (fvta_attn_pool_fwd_tw): the warp is one scalar per (question, position of its M JX), so the rows
+// stay pooled.  attn_pool_tw_scale_kernel goes in front and writes scale [NQ,M JX] from energy [P,JX] (a pooled album's,
+// fvta_attn_pool_energy: attn_shared.hip's two energy launches with A = P, T = JX) and the count of the GLOBAL position
+// t = m JX + j; (4) and (6) are the <TW, POOL> instantiations, which read the scale at the reference's slot.  At M = 1
+// every launch computes what fvta_attn_shared_fwd_tw's does: the same bits.
 #include "attn_shared_kernels.h"
+#include "timewarp_common.h"
 
 namespace fvta {
 
@@ -55,6 +62,32 @@ __global__ __launch_bounds__(256) void attn_pool_merge_kernel(ShShape s, ShWork 
       for (int sp = 0; sp < s.S; ++sp) v += wk.part[((((size_t)grp * s.K + k) * s.S + sp) * s.G + g) * s.w + c];
     }
   h_a[(size_t)q * s.w + c] = v;
+}
+
+// ---- scale[q,t] under the time warp, t = m JX + j over the question's WHOLE M JX positions.  grid (NQ, ceil(M JX / 256)),
+// 256 threads.  attn_shared_tw_scale_kernel's arithmetic (s0, WC.lq, tanhf, tw_count: at M = 1 its bits) with the energy
+// taken per slot: the album index clamped as the plan clamps it, an empty slot's e = 0 (JX zero rows)
+__global__ __launch_bounds__(256) void attn_pool_tw_scale_kernel(ShShape s, int warp_type, int win, const float* __restrict__ energy,
+                                                                 const float* __restrict__ lq, const int* __restrict__ albums,
+                                                                 const float* __restrict__ WHb, const float* __restrict__ WC,
+                                                                 const float* __restrict__ WCb, float* __restrict__ scale,
+                                                                 float* __restrict__ scale_out) {
+  const int q = blockIdx.x, lane = threadIdx.x & 63, t = blockIdx.y * 256 + threadIdx.x;
+  float s0 = 0.f, sq = 0.f;
+  for (int c = lane; c < s.w; c += 64) {
+    const float wc = WC[c];
+    s0 += WHb[c] * wc;
+    sq += lq[(size_t)q * s.w + c] * wc;
+  }
+  s0 = wave_sum(s0) + WCb[0];
+  sq = wave_sum(sq);
+  if (t >= s.TO) return;
+  const int m = t / s.T, a = sh_ref_album<true>(albums, q * s.M + m, s.A);
+  const float e = a < 0 ? 0.f : energy[(size_t)a * s.T + (t - m * s.T)];
+  const float tz = tanhf(e + (float)s.K * (s0 + sq));
+  const float sc = tz * tw_count(t, s.TO, warp_type, win);
+  scale[(size_t)q * s.TO + t] = sc;
+  if (scale_out) scale_out[(size_t)q * s.TO + t] = sc;
 }
 
 // 0: fine, else the status with the message set
@@ -90,6 +123,37 @@ static int fvta_attn_pool_check(const fvta_attn_pool_desc* d, const char* who) {
   return FVTA_OK;
 }
 
+// under the time warp: the shape, the warp type and window (attn_shared.hip's checks), M JX within the scale kernel's grid
+static int fvta_attn_pool_check_tw(const fvta_attn_pool_tw_desc* d, const char* who) {
+  FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
+  if (int e = fvta_attn_pool_check(&d->shape, who)) return e;
+  if (int e = fvta_attn_shared_check_warp(d->warp_type, d->window_t, who)) return e;
+  if ((int64_t)d->shape.M * d->shape.JX > 65535 * 256) {
+    fvta_set_error("%s: unsupported shape (M=%d JX=%d): M*JX must not exceed 65535 * 256 under the time warp", who, d->shape.M,
+                   d->shape.JX);
+    return FVTA_ERR_UNSUPPORTED;
+  }
+  if (((int64_t)d->shape.P * d->shape.JX + 3) / 4 > 0x7fffffff) {
+    fvta_set_error("%s: unsupported shape (P=%d JX=%d): too many workgroups", who, d->shape.P, d->shape.JX);
+    return FVTA_ERR_UNSUPPORTED;
+  }
+  return FVTA_OK;
+}
+
+// the workspace under the warp: fvta_attn_pool_fwd's, then scale [NQ,M JX], then v [w] (the energy call's)
+struct PoolTwWork {
+  ShWork wk;
+  float *scale, *v;
+  size_t bytes;
+  PoolTwWork(const ShShape& s, void* p) : wk(s, p) {
+    FvtaCarver c(p);
+    c.off = wk.bytes;
+    scale = c.take<float>((size_t)s.NQ * s.TO);
+    v = c.take<float>((size_t)s.w);
+    bytes = c.off;
+  }
+};
+
 }  // namespace fvta
 using namespace fvta;
 
@@ -109,36 +173,79 @@ extern "C" int fvta_attn_pool_plan(const fvta_attn_pool_desc* d, int32_t out[4])
   return FVTA_OK;
 }
 
-extern "C" int fvta_attn_pool_fwd(const fvta_attn_pool_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
-                                  const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a,
-                                  float* a_logits, void* workspace, fvta_stream_t stream_) {
-  if (int e = fvta_attn_pool_check(d, "attn_pool_fwd")) return e;
-  FVTA_CHECK_ARG(pool && hq && albums && h_a && workspace, "attn_pool_fwd: null pointer");
-  FVTA_CHECK_ARG(d->simi == 4 || W, "attn_pool_fwd: simiMatrix %d needs att_logits/W", d->simi);
-  ShShape s = sh_pool_shape(d);
+// the eight launches; TW: under the time warp, tw_scale [NQ,M JX] written by an earlier launch on the same stream
+template <bool TW>
+static int pool_forward(ShShape s, const ShWork& wk, const float* pool, const uint8_t* pool_mask, const float* hq,
+                        const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a, float* a_logits,
+                        hipStream_t st, const float* tw_scale, const char* who) {
   s.use_mask = (pool_mask && qmask) ? 1 : 0;  // model_v2.py:233: the mask applies only when both are given
-  const ShWork wk(s, workspace);
-  hipStream_t st = (hipStream_t)stream_;
   hipLaunchKernelGGL(attn_vecs_kernel, dim3((s.w + 255) / 256), dim3(256), 0, st, W, s.w, s.simi, 0, wk.vecs);
   hipLaunchKernelGGL(attn_shared_prep_q_kernel, dim3(s.NQ, s.JP / 4), dim3(256), 0, st, s, wk, hq, b);
   hipLaunchKernelGGL((attn_shared_plan_kernel<false, true>), dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)albums);
   const dim3 lgrid((unsigned)((int64_t)s.ngmax * s.K * s.ntile));
-  const ShTwArgs tw{nullptr, nullptr, nullptr};
+  const ShTwArgs tw{tw_scale, nullptr, nullptr};
   if (s.JP == 32)
-    hipLaunchKernelGGL((attn_shared_logits_kernel<1, false, false, true>), lgrid, dim3(SH_NT), 0, st, s, wk, pool, pool_mask, qmask,
+    hipLaunchKernelGGL((attn_shared_logits_kernel<1, false, TW, true>), lgrid, dim3(SH_NT), 0, st, s, wk, pool, pool_mask, qmask,
                        a_logits, tw);
   else
-    hipLaunchKernelGGL((attn_shared_logits_kernel<2, false, false, true>), lgrid, dim3(SH_NT), 0, st, s, wk, pool, pool_mask, qmask,
+    hipLaunchKernelGGL((attn_shared_logits_kernel<2, false, TW, true>), lgrid, dim3(SH_NT), 0, st, s, wk, pool, pool_mask, qmask,
                        a_logits, tw);
   hipLaunchKernelGGL(attn_pool_empty_kernel, dim3(s.NR), dim3(256), 0, st, s, wk, (const int*)albums, a_logits);
   ShShape sq = s;  // the softmaxes run per question over all of its positions
   sq.T = s.TO;
   hipLaunchKernelGGL(attn_shared_softmax_kernel, dim3(s.NQ), dim3(256), 0, st, sq, wk);
   if (s.G == 8)
-    sh_launch_wsum<8, false, true>(s, wk, pool, nullptr, st);
+    sh_launch_wsum<8, TW, true>(s, wk, pool, tw_scale, st);
   else
-    sh_launch_wsum<4, false, true>(s, wk, pool, nullptr, st);
+    sh_launch_wsum<4, TW, true>(s, wk, pool, tw_scale, st);
   hipLaunchKernelGGL(attn_pool_merge_kernel, dim3(s.NQ, (s.w + 255) / 256), dim3(256), 0, st, s, wk, h_a);
-  FVTA_CHECK_LAUNCH("attn_pool_fwd");
+  FVTA_CHECK_LAUNCH(who);
   return FVTA_OK;
+}
+
+extern "C" int fvta_attn_pool_fwd(const fvta_attn_pool_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
+                                  const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a,
+                                  float* a_logits, void* workspace, fvta_stream_t stream_) {
+  if (int e = fvta_attn_pool_check(d, "attn_pool_fwd")) return e;
+  FVTA_CHECK_ARG(pool && hq && albums && h_a && workspace, "attn_pool_fwd: null pointer");
+  FVTA_CHECK_ARG(d->simi == 4 || W, "attn_pool_fwd: simiMatrix %d needs att_logits/W", d->simi);
+  const ShShape s = sh_pool_shape(d);
+  return pool_forward<false>(s, ShWork(s, workspace), pool, pool_mask, hq, qmask, albums, W, b, h_a, a_logits, (hipStream_t)stream_,
+                             nullptr, "attn_pool_fwd");
+}
+
+// ---- under the time warp
+extern "C" size_t fvta_attn_pool_tw_workspace_bytes(const fvta_attn_pool_tw_desc* d) {
+  if (fvta_attn_pool_check_tw(d, "attn_pool_tw_workspace_bytes") != FVTA_OK) return 0;
+  return PoolTwWork(sh_pool_shape(&d->shape), nullptr).bytes;
+}
+
+extern "C" int fvta_attn_pool_energy(const fvta_attn_pool_tw_desc* d, const float* pool, const float* WH_W, const float* WC_W,
+                                     float* energy, void* workspace, fvta_stream_t stream_) {
+  if (int e = fvta_attn_pool_check_tw(d, "attn_pool_energy")) return e;
+  FVTA_CHECK_ARG(pool && WH_W && WC_W && energy && workspace, "attn_pool_energy: null pointer");
+  const ShShape s = sh_pool_shape(&d->shape);  // (A = P, T = JX: the energy of a pooled album's own rows)
+  const PoolTwWork tw(s, workspace);
+  hipStream_t st = (hipStream_t)stream_;
+  hipLaunchKernelGGL(attn_shared_tw_vec_kernel, dim3((s.w + 3) / 4), dim3(256), 0, st, s.w, WH_W, WC_W, tw.v);
+  hipLaunchKernelGGL(attn_shared_energy_kernel, dim3((unsigned)(((int64_t)s.A * s.T + 3) / 4)), dim3(256), 0, st, s, pool, tw.v,
+                     energy);
+  FVTA_CHECK_LAUNCH("attn_pool_energy");
+  return FVTA_OK;
+}
+
+extern "C" int fvta_attn_pool_fwd_tw(const fvta_attn_pool_tw_desc* d, const float* pool, const uint8_t* pool_mask,
+                                     const float* energy, const float* hq, const uint8_t* qmask, const float* lq,
+                                     const int32_t* albums, const float* W, const float* b, const float* WH_b, const float* WC_W,
+                                     const float* WC_b, float* h_a, float* a_logits, float* scale_out, void* workspace,
+                                     fvta_stream_t stream_) {
+  if (int e = fvta_attn_pool_check_tw(d, "attn_pool_fwd_tw")) return e;
+  FVTA_CHECK_ARG(pool && energy && hq && lq && albums && WH_b && WC_W && WC_b && h_a && workspace, "attn_pool_fwd_tw: null pointer");
+  FVTA_CHECK_ARG(d->shape.simi == 4 || W, "attn_pool_fwd_tw: simiMatrix %d needs att_logits/W", d->shape.simi);
+  const ShShape s = sh_pool_shape(&d->shape);
+  const PoolTwWork tw(s, workspace);
+  hipStream_t st = (hipStream_t)stream_;
+  hipLaunchKernelGGL(attn_pool_tw_scale_kernel, dim3(s.NQ, (s.TO + 255) / 256), dim3(256), 0, st, s, d->warp_type,
+                     (int)ceilf(d->window_t), energy, lq, (const int*)albums, WH_b, WC_W, WC_b, tw.scale, scale_out);
+  return pool_forward<true>(s, tw.wk, pool, pool_mask, hq, qmask, albums, W, b, h_a, a_logits, st, tw.scale, "attn_pool_fwd_tw");
 }

@@ -327,14 +327,19 @@ struct ShTwWork {
   }
 };
 
+int fvta_attn_shared_check_warp(int warp_type, float window_t, const char* who) {
+  if (warp_type < 1 || warp_type > 5) {
+    fvta_set_error("%s: time warping type not implemented (warp_type=%d)", who, warp_type);  // model_v2.py:341
+    return FVTA_ERR_INVALID_ARG;
+  }
+  FVTA_CHECK_ARG(window_t >= 0.f && window_t <= 1e9f, "%s: bad window_t (%g)", who, (double)window_t);
+  return FVTA_OK;
+}
+
 int fvta_attn_shared_check_tw(const fvta_attn_shared_tw_desc* d, const char* who, bool train) {
   FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
   if (int e = train ? fvta_attn_shared_check_train(&d->shape, who) : fvta_attn_shared_check(&d->shape, who)) return e;
-  if (d->warp_type < 1 || d->warp_type > 5) {
-    fvta_set_error("%s: time warping type not implemented (warp_type=%d)", who, d->warp_type);  // model_v2.py:341
-    return FVTA_ERR_INVALID_ARG;
-  }
-  FVTA_CHECK_ARG(d->window_t >= 0.f && d->window_t <= 1e9f, "%s: bad window_t (%g)", who, (double)d->window_t);
+  if (int e = fvta_attn_shared_check_warp(d->warp_type, d->window_t, who)) return e;
   if (d->shape.T > 65535 * 256) {
     fvta_set_error("%s: unsupported shape (T=%d): T must not exceed 65535 * 256 under the time warp", who, d->shape.T);
     return FVTA_ERR_UNSUPPORTED;

@@ -147,9 +147,14 @@ int fvta_attn_shared_check(const fvta_attn_shared_desc* d, const char* who);
 int fvta_attn_shared_check_train(const fvta_attn_shared_desc* d, const char* who);
 // under the time warp: the shape, the warp type (1..5: else FVTA_ERR_INVALID_ARG), the window; `train`: simiMatrix 1-3 too
 int fvta_attn_shared_check_tw(const fvta_attn_shared_tw_desc* d, const char* who, bool train = false);
+// its warp type (1..5: else FVTA_ERR_INVALID_ARG) and window checks alone: the pooled call under the warp makes them too
+int fvta_attn_shared_check_warp(int warp_type, float window_t, const char* who);
 
 // v[c] = sum_o WH[c][o] WC[o] (attn_shared.hip).  grid ceil(w / 4), 256 threads
 __global__ __launch_bounds__(256) void attn_shared_tw_vec_kernel(int w, const float* __restrict__ WH, const float* __restrict__ WC,
                                                                  float* __restrict__ v);
+// e[a,t] = sum_k sum_c v[c] h[a,k,t,c]^2 (attn_shared.hip).  grid ceil(A T / 4), 256 threads; reads s.A, s.K, s.T, s.w
+__global__ __launch_bounds__(256) void attn_shared_energy_kernel(ShShape s, const float* __restrict__ hinfo, const float* __restrict__ v,
+                                                                 float* __restrict__ energy);
 
 }  // namespace fvta

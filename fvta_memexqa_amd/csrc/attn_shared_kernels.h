@@ -144,7 +144,7 @@ __global__ __launch_bounds__(SH_PLAN_NT) void attn_shared_plan_kernel(ShShape s,
 
 // ---- logits.  grid ngmax * K * ntile, 256 threads
 // TRAIN: also the FIRST arg-max j of every row's maximum -> jmax [NQ,K,T] (compile-time: the inference kernel is unchanged)
-// TW (compile-time too; tw_scale [NQ,T], else unused): the logits of the WARPED rows h' = s h, s = tw_scale[q,t], from the
+// TW (compile-time too; tw_scale [NQ,T] -- POOL: [NQ,M T], read at the reference's slot -- else unused): the logits of the WARPED rows h' = s h, s = tw_scale[q,t], from the
 // rows as they are held.  The scalar goes through the bilinear form: x = s (h.Qs + Rh.h) + s^2 (R2.h^2) + ct, cosine
 // x = (h.Qn) s rsqrt(max(s^2 |h|^2, 1e-12)) -- the row pass keeps Rh.h and R2.h^2 (cosine: the raw sum h^2) apart, and
 // the scales of the tile's rows for the group's questions are staged in LDS
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
   // TW: s_rt holds Rh.h, s_r2 R2.h^2 (cosine: sum h^2); s_sc, s_s2 the factor of the product and the addend per (question, row)
   __shared__ float s_r2[TW ? SH_R : 1], s_sc[TW ? G : 1][TW ? SH_R : 1], s_s2[TW ? G : 1][TW ? SH_R : 1];
   __shared__ int s_q[G], s_o[POOL ? G : 1];  // a column block's question and -- POOL -- its slot's first position
-  static_assert(!(POOL && (TRAIN || TW)), "the pooled call is the plain inference one");
+  static_assert(!(POOL && TRAIN), "the pooled calls are inference ones");
   __shared__ uint8_t s_hv[SH_R], s_cv[SH_BN];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int tile = blockIdx.x % s.ntile, k = (blockIdx.x / s.ntile) % s.K, grp = blockIdx.x / (s.ntile * s.K);
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
     if constexpr (TW)  // the scales of the tile's rows, per question of the group (an empty slot, a row past T: 0)
       for (int e = tid; e < G * SH_R; e += SH_NT) {
         const int q = s_q[e / SH_R], t = t0 + e % SH_R;
-        s_sc[e / SH_R][e % SH_R] = (q >= 0 && t < T) ? tw_scale[(size_t)q * T + t] : 0.f;
+        s_sc[e / SH_R][e % SH_R] = (q >= 0 && t < T) ? tw_scale[(size_t)q * TP + (POOL ? s_o[e / SH_R] : 0) + t] : 0.f;
       }
   }
   ShMma mma;
@@ -332,13 +332,12 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
 }
 
 // ---- weighted sums.  grid ngmax * K * S, 256 threads: thread tid owns channels 4 tid .. + 3 (+ 1024 per further CPT)
-// TW (compile-time; tw_scale [NQ,T], else unused): the sum runs over the warped rows s h: the staged weight carries s
+// TW (compile-time; tw_scale [NQ,T] -- POOL: [NQ,M T] -- else unused): the sum runs over the warped rows s h: the staged weight carries s
 template <int G, int CPT, bool TW, bool POOL = false>
 __global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork wk, const float* __restrict__ hinfo,
                                                                const float* __restrict__ tw_scale) {
   __shared__ float s_p[SH_CH][G], s_M[G], s_cf[G];
   __shared__ int s_q[G], s_o[POOL ? G : 1];  // as the logits kernel's
-  static_assert(!(POOL && TW), "the pooled call is the plain inference one");
   const int tid = threadIdx.x;
   const int sp = blockIdx.x % s.S, k = (blockIdx.x / s.S) % s.K, grp = blockIdx.x / (s.S * s.K);
   if (grp >= *wk.ngroups) return;
@@ -366,7 +365,7 @@ __global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork
     for (int e = tid; e < SH_CH * G; e += 256) {
       const int g = e / SH_CH, r = e % SH_CH, t = c0 + r, q = s_q[g];
       float p = (t < te && q >= 0) ? expf(wk.amax[((size_t)q * K + k) * TP + (POOL ? s_o[g] : 0) + t] - s_M[g]) : 0.f;
-      if constexpr (TW) p = (t < te && q >= 0) ? p * tw_scale[(size_t)q * T + t] : 0.f;
+      if constexpr (TW) p = (t < te && q >= 0) ? p * tw_scale[(size_t)q * TP + (POOL ? s_o[g] : 0) + t] : 0.f;
       s_p[r][g] = p;
     }
     __syncthreads();

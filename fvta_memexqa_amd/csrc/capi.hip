@@ -37,6 +37,7 @@ extern "C" int64_t fvta_abi_struct_bytes(int32_t which) {
     case 12: return (int64_t)sizeof(fvta_attn_shared_desc);
     case 13: return (int64_t)sizeof(fvta_attn_shared_tw_desc);
     case 14: return (int64_t)sizeof(fvta_attn_pool_desc);
+    case 15: return (int64_t)sizeof(fvta_attn_pool_tw_desc);
     default: return -1;
   }
 }

@@ -284,7 +284,9 @@ def _warp_weights(w, wp, WH_W, WC_W, WH_b=None, WC_b=None):
 def album_energy(hinfo, WH_W, WC_W):
     """e [A,T] = sum_k sum_c v[c] hinfo[a,k,t,c]^2, v = WH_W[:w] WC_W: the one term of the time warp's scale that reads the
     rows (fvta_attn_shared_energy).  It belongs to the albums -- attention_3d_shared_warped_raw(energy=) takes it, and it
-    holds as long as hinfo, WH/W and WC/W do.  Forward only, detached."""
+    holds as long as hinfo, WH/W and WC/W do.  Forward only, detached.
+    An album pool [P,K,JX,w] is accepted as it is and gives e [P,JX], the energy attention_3d_pooled_warped_raw(energy=)
+    takes (fvta_attn_pool_energy makes the same two launches: the same bits)."""
     hinfo = _f32(hinfo).detach()
     A, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
     hinfo = hinfo.reshape(A, K, -1, w)
@@ -356,6 +358,59 @@ def attention_3d_shared_warped_raw(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W,
     if energy is None:
         energy = op.album_energy(rows, WH, WC)
     h_a, a, scale = op.forward(rows, hm, _f32(energy).detach().contiguous(), _pad_channels(hq, wp), qm, _pad_channels(lq, wp),
+                               idx.to(dev), W, b, WHb, WC, WCb, want_logits=True, want_scale=True)
+    return h_a[:, :w].contiguous(), a, scale
+
+
+def attention_3d_pooled_warped_raw(pool, hq, albums, lq, W, b, WH_W, WH_b, WC_W, WC_b, pool_mask=None, hq_mask=None,
+                                   simiMatrix=1, add_tanh=False, warp_type=1, window_t=3.0, energy=None):
+    """attention_3d_pooled_raw under the time warp (use_time_warp without use_time_warp_att): pool [P,K,JX,w] held once,
+    hq [NQ,JQ,w], albums [NQ,M] as attention_3d_pooled_raw takes them, lq [NQ,w] the questions' last states, W / b as
+    attention_raw, the warp's weights as time_warp_raw -> (h_a [NQ,w], a_logits [NQ,K,M*JX,JQ], scale [NQ,M*JX]): for
+    question i, attention_raw on time_warp_raw's warp of (its albums' rows laid end to end, lq[i]), and that warp's scale.
+    A position's count runs over the question's whole M*JX positions (a band, past or future crosses slot boundaries).
+    Neither the [NQ,K,M*JX,w] context nor its warp is built: the warp is one scalar per (question, position), applied
+    inside the kernels (fvta_attn_pool_fwd_tw).  energy [P,JX]: album_energy of (pool, WH_W, WC_W), None computes it on the
+    spot.  Forward-only: with gradient mode on and an argument that requires grad it raises."""
+    if simiMatrix not in (1, 2, 3, 4):
+        raise ValueError("similarity matrix not implemented")
+    _check_warp_type(warp_type)
+    tensors = [t for t in (pool, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b) if torch.is_tensor(t)]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("attention_3d_pooled_warped_raw is forward-only: call it under torch.no_grad(), or use the "
+                           "per-question time_warp + attention_3d (functional.time_warp_raw / attention_raw, nn.TimeWarp / "
+                           "nn.FocalAttention3D.forward) on the gathered rows")
+    pool, hq, lq = _f32(pool).detach(), _f32(hq).detach(), _f32(lq).detach()
+    if pool.dim() != 4:
+        raise ValueError("album pool: expected [P,K,JX,w], got shape %s" % (tuple(pool.shape),))
+    P, K, JX, w = pool.shape
+    NQ, JQ = hq.shape[0], hq.shape[1]
+    if tuple(lq.shape) != (NQ, w):
+        raise ValueError("lq: expected the questions' last states [%d, %d], got %s" % (NQ, w, tuple(lq.shape)))
+    both = pool_mask is not None and hq_mask is not None                   # model_v2.py:233: only when BOTH are given
+    idx = ops.check_album_lists(albums, P, both)
+    if idx.shape[0] != NQ:
+        raise ValueError("album lists: %d lists for %d questions" % (idx.shape[0], NQ))
+    if energy is not None and tuple(energy.shape) != (P, JX):
+        raise ValueError("energy: expected [%d, %d], got %s" % (P, JX, tuple(energy.shape)))
+    wp = next((c for c in SUPPORTED_W if w <= c), None)
+    if wp is None:
+        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
+    F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
+    if F:
+        W = _pad_channels(_f32(W).detach().reshape(F, w), wp).reshape(-1)
+        b = _f32(b).detach()
+    else:
+        W = b = None
+    dev = ops.require_gpu()
+    pm = ops.as_mask_u8(pool_mask.reshape(P, K, JX)) if both else None
+    qm = ops.as_mask_u8(hq_mask) if both else None
+    WH, WC, WHb, WCb = _warp_weights(w, wp, WH_W, WC_W, WH_b, WC_b)
+    op = ops.PooledWarpedFocalAttention(P, NQ, idx.shape[1], K, JX, JQ, wp, simiMatrix, add_tanh, warp_type, float(window_t))
+    rows = _pad_channels(pool, wp)
+    if energy is None:
+        energy = op.album_energy(rows, WH, WC)
+    h_a, a, scale = op.forward(rows, pm, _f32(energy).detach().contiguous(), _pad_channels(hq, wp), qm, _pad_channels(lq, wp),
                                idx.to(dev), W, b, WHb, WC, WCb, want_logits=True, want_scale=True)
     return h_a[:, :w].contiguous(), a, scale
 

@@ -152,14 +152,47 @@ class FocalAttention3D(_AttLogits):
         return h_a, a
 
 
-    def forward_pooled(self, pool, hq, albums, pool_mask=None, hq_mask=None):
+    def forward_pooled(self, pool, hq, albums, pool_mask=None, hq_mask=None, time_warp=None, lq=None, energy=None):
         """forward() for NQ questions that each list M albums of one pool: pool [P,K,JX,w], hq [NQ,JQ,w], albums [NQ,M]
         (entries in [0, P), -1 an empty slot -- which needs both masks) -> (h_a [NQ,w], a_logits [NQ,K,M*JX,JQ]) with this
         module's att_logits/{W,b} (functional.attention_3d_pooled_raw): forward() on each question's albums laid end to
         end, with no such tensor built.  Inference only: under gradient mode the parameters require grad and the call
-        raises; use it under torch.no_grad()."""
+        raises; use it under torch.no_grad().
+        time_warp (an nn.TimeWarp) with lq [NQ,w], the questions' last states: the attention over each question's albums
+        laid end to end and warped for that question -- forward(time_warp(hinfo_i, lq)[0], ...) -- with the pool still
+        held once (functional.attention_3d_pooled_warped_raw).  Its parameters and its window buffer are used; energy
+        [P,JX]: functional.album_energy of (pool, WH/W, WC/W) when the caller keeps it, else computed here."""
         W, b = self._wb()
-        return functional.attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask, hq_mask, self.simiMatrix, self.add_tanh)
+        if time_warp is None and (lq is not None or energy is not None):
+            raise ValueError("forward_pooled: lq / energy belong to the time warp; pass time_warp (an nn.TimeWarp) with them")
+        if time_warp is None:
+            return functional.attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask, hq_mask, self.simiMatrix, self.add_tanh)
+        if lq is None:
+            raise ValueError("forward_pooled: the time warp needs lq [NQ,w], the questions' last states")
+        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
+            raise ValueError("forward_pooled: lq must be [%d, %d], got %s"
+                             % (hq.shape[0], self.w, tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
+        tw = time_warp
+        h_a, a, _ = functional.attention_3d_pooled_warped_raw(
+            pool, hq, albums, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), pool_mask, hq_mask,
+            self.simiMatrix, self.add_tanh, tw.warp_type, tw.window_t(), energy)
+        return h_a, a
+
+
+class _EnergyCache:
+    """The rows' share of the time warp, functional.album_energy(rows, WH/W, WC/W), kept by whoever holds the rows
+    (AlbumMemory, AlbumPool): recomputed when either parameter is another tensor or has been written to since (its version
+    counter)"""
+
+    def __init__(self):
+        self._kept = None                # (key of the time warp's weights, the energy)
+
+    def get(self, rows, time_warp):
+        WH, WC = time_warp.p("WH/W"), time_warp.p("WC/W")
+        key = tuple((id(t), t.data_ptr(), t._version) for t in (WH, WC))
+        if self._kept is None or self._kept[0] != key:
+            self._kept = (key, functional.album_energy(rows, WH, WC))
+        return self._kept[1]
 
 
 class AlbumPool:
@@ -176,6 +209,7 @@ class AlbumPool:
         self.pool_mask = None if pool_mask is None else ops.as_mask_u8(pool_mask.detach().to(dev))
         if self.pool_mask is not None and tuple(self.pool_mask.shape) != tuple(self.pool.shape[:3]):
             raise ValueError("AlbumPool: mask %s does not match the rows %s" % (tuple(pool_mask.shape), tuple(pool.shape)))
+        self._energy = _EnergyCache()    # e [P,JX] under a time warp's weights: see energy()
 
     def __len__(self):
         return self.pool.shape[0]
@@ -191,13 +225,32 @@ class AlbumPool:
         mask = None if hall_mask is None else hall_mask.detach().reshape(N, K, M, JX).permute(0, 2, 1, 3).reshape(N * M, K, JX)
         return cls(pool, mask), torch.arange(N * M, dtype=torch.int32).reshape(N, M)
 
-    def attend(self, attention, hq, hq_mask, albums):
+    def attend(self, attention, hq, hq_mask, albums, time_warp=None, lq=None):
         """(h_a [NQ,w], a_logits [NQ,K,M*JX,JQ]) of `attention` (an nn.FocalAttention3D) for questions hq [NQ,JQ,w] that list
-        albums [NQ,M] of this pool; a bad list raises ValueError before anything reaches the library."""
+        albums [NQ,M] of this pool; a bad list raises ValueError before anything reaches the library.
+        time_warp (an nn.TimeWarp) with lq [NQ,w]: the attention over each question's albums laid end to end and warped
+        for that question, the pool still held once.  The albums' share of the warp, the energy [P,JX], is computed on
+        first use and kept; it is recomputed when WH/W or WC/W of the time warp have changed since (an in-place update,
+        load_state_dict, another module)."""
         idx = ops.check_album_lists(albums, len(self), self.pool_mask is not None and hq_mask is not None)
         if idx.shape[0] != hq.shape[0]:
             raise ValueError("album lists: %d lists for %d questions" % (idx.shape[0], hq.shape[0]))
-        return attention.forward_pooled(self.pool, hq, idx, self.pool_mask, hq_mask)
+        if time_warp is None:
+            if lq is not None:
+                raise ValueError("attend: lq belongs to the time warp; pass time_warp (an nn.TimeWarp) with it")
+            return attention.forward_pooled(self.pool, hq, idx, self.pool_mask, hq_mask)
+        if lq is None:
+            raise ValueError("attend: the time warp needs lq [NQ,w], the questions' last states")
+        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.pool.shape[-1]):
+            raise ValueError("attend: lq must be [%d, %d], got %s"
+                             % (hq.shape[0], self.pool.shape[-1], tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
+        return attention.forward_pooled(self.pool, hq, idx, self.pool_mask, hq_mask, time_warp=time_warp, lq=lq,
+                                        energy=self.energy(time_warp))
+
+    def energy(self, time_warp):
+        """e [P,JX] of functional.album_energy for this pool's rows and time_warp's WH/W, WC/W: kept, and recomputed when
+        either parameter is another tensor or has been written to since (its version counter)"""
+        return self._energy.get(self.pool, time_warp)
 
 
 class AlbumMemory:
@@ -212,7 +265,7 @@ class AlbumMemory:
         self.hall_mask = None if hall_mask is None else ops.as_mask_u8(hall_mask.detach().to(dev).reshape(A, K, -1))
         if self.hall_mask is not None and tuple(self.hall_mask.shape) != tuple(self.hall.shape[:3]):
             raise ValueError("AlbumMemory: mask %s does not match the rows %s" % (tuple(hall_mask.shape), tuple(hall.shape)))
-        self._energy = None              # (key of the time warp's weights, e [A,T]): see energy()
+        self._energy = _EnergyCache()    # e [A,T] under a time warp's weights: see energy()
 
     def __len__(self):
         return self.hall.shape[0]
@@ -241,11 +294,7 @@ class AlbumMemory:
     def energy(self, time_warp):
         """e [A,T] of functional.album_energy for this memory's rows and time_warp's WH/W, WC/W: kept, and recomputed when
         either parameter is another tensor or has been written to since (its version counter)"""
-        WH, WC = time_warp.p("WH/W"), time_warp.p("WC/W")
-        key = tuple((id(t), t.data_ptr(), t._version) for t in (WH, WC))
-        if self._energy is None or self._energy[0] != key:
-            self._energy = (key, functional.album_energy(self.hall, WH, WC))
-        return self._energy[1]
+        return self._energy.get(self.hall, time_warp)
 
 
 class QuestionAttention(_AttLogits):

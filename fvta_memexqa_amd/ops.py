@@ -539,6 +539,62 @@ class SharedWarpedFocalAttention:
               "fvta_attn_shared_bwd_tw")
 
 
+class PooledWarpedFocalAttention:
+    """PooledFocalAttention.forward under the time warp (model_v2.py:953-1009, use_time_warp without use_time_warp_att;
+    forward only): question i gets FocalAttention's result on TimeWarp's warp of (its albums' rows laid end to end, lq[i]),
+    from the pool [P,K,JX,w] as it is held -- the warp is one scalar per (question, position t = m*JX + j of its M*JX), and
+    the only term of it that reads the rows, the energy e [P,JX], belongs to the pooled album: album_energy() computes it
+    once per pool, forward() takes it.  The count of a position runs over the question's whole M*JX positions."""
+
+    def __init__(self, P, NQ, M, K, JX, JQ, w, simi, add_tanh, warp_type, window_t=3.0):
+        self.lib = _lib.load()
+        self.dev = require_gpu()
+        self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w = int(P), int(NQ), int(M), int(K), int(JX), int(JQ), int(w)
+        shape = _lib.AttnPoolDesc(self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w, int(simi), int(bool(add_tanh)))
+        self.desc = _lib.AttnPoolTwDesc(shape, int(warp_type), float(window_t))
+        nb = self.lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(self.desc))
+        if nb == 0:                      # (a bad warp type: "time warping type not implemented", model_v2.py:341)
+            raise _lib.FvtaError("pooled attention under the time warp: " + self.lib.fvta_last_error().decode())
+        self.work = _bytes(nb, self.dev)
+
+    def plan(self):
+        """PooledFocalAttention.plan()'s words for the same shape -- the warp changes none (host only)"""
+        out = (ctypes.c_int32 * 4)()
+        check(self.lib.fvta_attn_pool_plan(ctypes.byref(self.desc.shape), out), "fvta_attn_pool_plan")
+        return dict(zip(("G", "rows", "tsplit", "rows_per_split"), (int(v) for v in out)))
+
+    def album_energy(self, pool, WH_W, WC_W):
+        """e [P,JX] = sum_k sum_c (WH_W[:w] WC_W)[c] pool[p,k,j,c]^2 (fvta_attn_pool_energy): a function of the pool and of
+        WH/W, WC/W alone -- keep it as long as those stay what they are.  WH_W [2w,w] or its first w rows, WC_W [w]"""
+        assert tuple(pool.shape) == (self.P, self.K, self.JX, self.w)
+        assert WH_W.numel() >= self.w * self.w and WC_W.numel() == self.w
+        energy = torch.empty(self.P, self.JX, device=self.dev, dtype=torch.float32)
+        check(self.lib.fvta_attn_pool_energy(ctypes.byref(self.desc), ptr(_f32c(pool)), ptr(_f32c(WH_W)), ptr(_f32c(WC_W)),
+                                             ptr(energy), ptr(self.work), stream_ptr()), "fvta_attn_pool_energy")
+        return energy
+
+    def forward(self, pool, pool_mask, energy, hq, qmask, lq, albums, W, b, WH_b, WC_W, WC_b, want_logits=False,
+                want_scale=False):
+        """-> (h_a [NQ,w], a_logits [NQ,K,M*JX,JQ] | None, scale [NQ,M*JX] | None); scale is TimeWarp's on the question's
+        albums laid end to end"""
+        assert tuple(pool.shape) == (self.P, self.K, self.JX, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
+        assert tuple(energy.shape) == (self.P, self.JX) and tuple(lq.shape) == (self.NQ, self.w)
+        assert albums.is_cuda and albums.dtype == torch.int32 and albums.is_contiguous() and \
+            tuple(albums.shape) == (self.NQ, self.M)
+        assert pool_mask is None or (pool_mask.dtype == torch.uint8 and tuple(pool_mask.shape) == (self.P, self.K, self.JX))
+        assert qmask is None or (qmask.dtype == torch.uint8 and tuple(qmask.shape) == (self.NQ, self.JQ))
+        assert WH_b.numel() == self.w and WC_W.numel() == self.w and WC_b.numel() == 1
+        T = self.M * self.JX
+        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
+        a_logits = torch.empty(self.NQ, self.K, T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
+        scale = torch.empty(self.NQ, T, device=self.dev, dtype=torch.float32) if want_scale else None
+        check(self.lib.fvta_attn_pool_fwd_tw(ctypes.byref(self.desc), ptr(_f32c(pool)), ptr(pool_mask), ptr(_f32c(energy)),
+                                             ptr(_f32c(hq)), ptr(qmask), ptr(_f32c(lq)), ptr(albums), ptr(W), ptr(b),
+                                             ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)), ptr(h_a), ptr(a_logits),
+                                             ptr(scale), ptr(self.work), stream_ptr()), "fvta_attn_pool_fwd_tw")
+        return h_a, a_logits, scale
+
+
 def linear_fwd(x, W, b, y, M, din, dout, add_tanh=False, blk=None):
     """y [M,dout] = x [M,din] W [din,dout] + b (+ tanh); blk = (rows_per_blk, blk_stride): x rows in blocks"""
     rpb, bs = blk if blk else (M, 0)

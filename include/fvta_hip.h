@@ -47,7 +47,8 @@ const char* fvta_last_error(void);
 /* sizeof of a descriptor struct as the library was compiled: which = 0 fvta_attn_desc, 1 fvta_lstm_desc,
  * 2 fvta_scorer_desc, 3 fvta_timewarp_desc, 4 fvta_embed_desc, 5 fvta_imgtrans_desc, 6 fvta_guard_desc,
  * 7 fvta_guard_ctl, 9 fvta_attgru_seq_desc, 10 fvta_gru_seq_desc, 11 fvta_cbp_desc, 12 fvta_attn_shared_desc,
- * 13 fvta_attn_shared_tw_desc, 14 fvta_attn_pool_desc (8 stays unassigned: bindings probe it as the unknown id); -1 otherwise.
+ * 13 fvta_attn_shared_tw_desc, 14 fvta_attn_pool_desc, 15 fvta_attn_pool_tw_desc (8 stays unassigned: bindings probe it
+ * as the unknown id); -1 otherwise.
  * A binding compares
  * its own layout with it when it loads the library (fvta_memexqa_amd/_lib.py does). */
 int64_t fvta_abi_struct_bytes(int32_t which);
@@ -290,7 +291,8 @@ int fvta_attn_shared_bwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinf
  * Range: fvta_attn_shared_fwd's (w, JQ <= 64, K <= 64, simi 1..4), P, NQ, M, JX >= 1, NQ M <= 2^28, M JX within int.
  * No host synchronisation, no memset, everything on the caller's stream.
  * fvta_attn_pool_plan (host only): out = {G, rows per logits tile, splits of JX in the weighted sum, rows per split}.
- * Not here: the time warp, training, shadow rows. */
+ * The time warp (use_time_warp, every warp type) is fvta_attn_pool_fwd_tw further down.  Not here, nor there: training
+ * over the pool, time_warp_att, shadow rows. */
 typedef struct fvta_attn_pool_desc {
   int32_t P, NQ, M, K, JX, JQ, w; /* P pooled albums [P,K,JX,w], NQ questions listing M albums each */
   int32_t simi;                   /* 1..4 */
@@ -302,6 +304,40 @@ int fvta_attn_pool_plan(const fvta_attn_pool_desc* d, int32_t out[4]);
 int fvta_attn_pool_fwd(const fvta_attn_pool_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
                        const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a,
                        float* a_logits, void* workspace, fvta_stream_t stream);
+
+/* fvta_attn_pool_fwd under the time warp (use_time_warp without use_time_warp_att; forward only, inference).  Per
+ * question the result is what fvta_attn_fwd returns on fvta_timewarp_fwd's warp of (hinfo_i, lq[i]), hinfo_i the
+ * question's M albums laid end to end as above (an empty slot: JX zero rows, mask 0), with hinfo_i's masks.  The warp is
+ * one scalar per (question, position), so neither hinfo_i nor its warp is ever built:
+ *   scale[i,t] = tanh(e_i[t] + K (s0 + WC . lq[i])) cnt(t)       t = m JX + j, cnt over the question's WHOLE M JX positions
+ *   e_i[t]     = energy[albums[i,m], j], 0 for an empty slot       (a band, past or future runs across slot boundaries)
+ *   energy[p,j] = sum_k sum_c v[c] pool[p,k,j,c]^2                 v = WH[:w] WC,  s0 = b_WH . WC + b_WC
+ * fvta_attn_pool_energy: energy [P,JX], the two launches of fvta_attn_shared_energy with A = P, T = JX: its bits.  It
+ *   depends on pool, WH_W and WC_W alone: compute it once per pool and keep it while those stay what they are.  NQ, M, JQ
+ *   and simi of the descriptor must be valid but do not enter.
+ * fvta_attn_pool_fwd_tw: lq [NQ,w]; WH_b [w], WC_W [w], WC_b [1]; h_a [NQ,w], a_logits [NQ,K,M JX,JQ] or NULL, scale_out
+ *   [NQ,M JX] or NULL (an empty slot's positions: tanh(K (s0 + WC . lq)) cnt(t), what the definition gives on zero rows);
+ *   the other arguments as fvta_attn_pool_fwd.  The masks stay the albums': a masked row is -1e30 whatever its scale.
+ *   The launches are fvta_attn_pool_fwd's with the scale kernel in front; at M = 1 all three outputs are
+ *   fvta_attn_shared_fwd_tw's bits for (A = P, T = JX).
+ * `workspace`: fvta_attn_pool_tw_workspace_bytes, for either call (no [NQ,K,M JX,w]-sized piece).  Range:
+ * fvta_attn_pool_fwd's, and M JX <= 65535 * 256.  warp_type outside 1..5: FVTA_ERR_INVALID_ARG, "time warping type not
+ * implemented" (model_v2.py:341), and 0 from the size query.  No host synchronisation, no memset, no floating-point
+ * atomics, everything on the caller's stream: two calls are bitwise equal, and a question's numbers do not depend on the
+ * other questions. */
+typedef struct fvta_attn_pool_tw_desc {
+  fvta_attn_pool_desc shape;
+  int32_t warp_type; /* 1..5 (model_v2.py:301-341) */
+  float window_t;    /* warp_type 5: time_warp_window_t */
+} fvta_attn_pool_tw_desc; /* fvta_abi_struct_bytes(15) */
+
+size_t fvta_attn_pool_tw_workspace_bytes(const fvta_attn_pool_tw_desc* d); /* 0 bytes: see fvta_last_error */
+int fvta_attn_pool_energy(const fvta_attn_pool_tw_desc* d, const float* pool, const float* WH_W, const float* WC_W,
+                          float* energy, void* workspace, fvta_stream_t stream);
+int fvta_attn_pool_fwd_tw(const fvta_attn_pool_tw_desc* d, const float* pool, const uint8_t* pool_mask, const float* energy,
+                          const float* hq, const uint8_t* qmask, const float* lq, const int32_t* albums, const float* W,
+                          const float* b, const float* WH_b, const float* WC_W, const float* WC_b, float* h_a,
+                          float* a_logits, float* scale_out, void* workspace, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * bi-LSTM modality encoders: model_v2.py:652-661 (cells), 667-678 (lengths),

@@ -158,6 +158,11 @@ _SIGS = {
     "fvta_attn_pool_workspace_bytes": (c_size_t, [POINTER(AttnPoolDesc)]),
     "fvta_attn_pool_plan": (c_int, [POINTER(AttnPoolDesc), POINTER(c_int32)]),
     "fvta_attn_pool_fwd": (c_int, [POINTER(AttnPoolDesc), P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_attn_pool_saved_bytes": (c_size_t, [POINTER(AttnPoolDesc)]),
+    "fvta_attn_pool_bwd_workspace_bytes": (c_size_t, [POINTER(AttnPoolDesc)]),
+    "fvta_attn_pool_bwd_plan": (c_int, [POINTER(AttnPoolDesc), POINTER(c_int32)]),
+    "fvta_attn_pool_fwd_train": (c_int, [POINTER(AttnPoolDesc), P, P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_attn_pool_bwd": (c_int, [POINTER(AttnPoolDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_attn_pool_tw_workspace_bytes": (c_size_t, [POINTER(AttnPoolTwDesc)]),
     "fvta_attn_pool_energy": (c_int, [POINTER(AttnPoolTwDesc), P, P, P, P, P, P]),
     "fvta_attn_pool_fwd_tw": (c_int, [POINTER(AttnPoolTwDesc)] + [P] * 17),

@@ -239,6 +239,47 @@ def shared_focal_attention(hinfo, hq, album, W, b, hmask=None, qmask=None, simi=
     return _SharedFocalAttention.apply(hinfo, hq, album, W, b, hmask, qmask, int(simi), bool(add_tanh))
 
 
+class _PooledFocalAttention(torch.autograd.Function):
+    """(pool [P,K,JX,w], hq [NQ,JQ,w], albums int32 [NQ,M] on the device, W [F*w], b [1]; masks u8 | None) ->
+    (h_a [NQ,w], a_logits [NQ,K,M*JX,JQ]): question i over its albums' rows laid end to end, the pool held once
+    (fvta_attn_pool_fwd_train / fvta_attn_pool_bwd; simiMatrix 1-3).  The gradient of pool stays [P,K,JX,w]: the sum over
+    every (question, slot) that refers to the album.  a_logits is not differentiable here.  Each call owns its handle."""
+
+    @staticmethod
+    def forward(ctx, pool, hq, albums, W, b, pool_mask, qmask, simi, add_tanh):
+        P, K, JX, w = pool.shape
+        op = ops.PooledFocalAttention(P, hq.shape[0], albums.shape[1], K, JX, hq.shape[1], w, simi, add_tanh)
+        h_a, a = op.forward_train(pool, pool_mask, hq, qmask, albums, W, b, want_logits=True)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(a)
+        ctx.op = op
+        ctx.aux = (albums, pool_mask, qmask)
+        ctx.save_for_backward(pool, hq, W, b)
+        return h_a, a
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ha, g_a):
+        if g_ha is None:
+            return (None,) * 9
+        pool, hq, W, b = ctx.saved_tensors
+        albums, pool_mask, qmask = ctx.aux
+        dp, dq = torch.empty_like(pool), torch.empty_like(hq)
+        dW, db = torch.zeros_like(W), torch.zeros_like(b)
+        ctx.op.backward(pool, pool_mask, hq, qmask, albums, W, b, _c(g_ha), dp, dq, dW, db)
+        need = ctx.needs_input_grad
+        return (dp if need[0] else None, dq if need[1] else None, None, dW if need[3] else None, db if need[4] else None,
+                None, None, None, None)
+
+
+def pooled_focal_attention(pool, hq, albums, W, b, pool_mask=None, qmask=None, simi=1, add_tanh=False):
+    """albums: int32 [NQ,M] on the device, validated by the caller (ops.check_album_lists)"""
+    if int(simi) == 4:
+        raise NotImplementedError("pooled_focal_attention: simiMatrix 4 has no pooled backward; the per-question "
+                                  "focal_attention on gathered rows covers it")
+    return _PooledFocalAttention.apply(_c(pool), _c(hq), albums, _c(W), _c(b), pool_mask, qmask, int(simi), bool(add_tanh))
+
+
 class _SharedWarpedFocalAttention(torch.autograd.Function):
     """_SharedFocalAttention under the time warp (fvta_attn_shared_fwd_tw_train / fvta_attn_shared_bwd_tw; simiMatrix 1-3):
     (hinfo [A,K,T,w], hq [NQ,JQ,w], lq [NQ,w], album int32 [NQ] on the device, W [F*w], b [1], WH_W [2w,w] or its first w

@@ -3,7 +3,8 @@
 // those albums laid end to end: hinfo_i[k, m JX + j] = pool[albums[i,m], k, j], T = M JX (model_v2.py:863-914 builds that
 // tensor per question; the encoders run per (question, album), :704-760, so an album's rows do not depend on its
 // neighbours).  Per question the result is fvta_attn_fwd's on (hinfo_i, hq[i]) -- model_v2.py:210-298 -- and no
-// [NQ,K,T,w] tensor exists.  Inference only: nothing is kept for a backward.
+// [NQ,K,T,w] tensor exists.  fvta_attn_pool_fwd keeps nothing for a backward; the training pair (fvta_attn_pool_fwd_train /
+// fvta_attn_pool_bwd) is at the end of this file.
 //
 // The launches are attn_shared.hip's seven with one change of meaning: a column block of a group's product stands for a
 // REFERENCE (question q, slot m), id q M + m, instead of a question (attn_shared_kernels.h, POOL = true):
@@ -31,11 +32,14 @@
 // t = m JX + j; (4) and (6) are the <TW, POOL> instantiations, which read the scale at the reference's slot.  At M = 1
 // every launch computes what fvta_attn_shared_fwd_tw's does: the same bits.
 #include "attn_shared_kernels.h"
+#include "attn_shared_bwd_kernels.h"
 #include "timewarp_common.h"
 
 namespace fvta {
 
 // ---- empty slots.  grid NQ M, 256 threads: a workgroup per reference, gone at once unless its slot is empty
+// TRAIN: jmax = 0 over the slot's positions too (never read: no reference stands there; defined all the same)
+template <bool TRAIN>
 __global__ __launch_bounds__(256) void attn_pool_empty_kernel(ShShape s, ShWork wk, const int* __restrict__ albums,
                                                               float* __restrict__ a_logits) {
   const int ref = blockIdx.x;
@@ -44,23 +48,38 @@ __global__ __launch_bounds__(256) void attn_pool_empty_kernel(ShShape s, ShWork 
   for (int k = 0; k < s.K; ++k) {
     const size_t at = ((size_t)q * s.K + k) * s.TO + off;
     for (int e = threadIdx.x; e < s.T; e += 256) wk.amax[at + e] = FVTA_NEG;
+    if constexpr (TRAIN)
+      for (int e = threadIdx.x; e < s.T; e += 256) wk.jmax[at + e] = 0;
     if (a_logits)
       for (int64_t e = threadIdx.x; e < (int64_t)s.T * s.JQ; e += 256) a_logits[at * s.JQ + e] = FVTA_NEG;
   }
 }
 
 // ---- merge.  grid (NQ, ceil(w / 256)): a channel per thread, the partials in (k, slot, split) order
+// TRAIN: u[q,k] = (the partials of k, in (slot, split) order) / r[q,k] beside it, by attn_shared_merge_kernel's rule: r = 0
+// (underflow) leaves u = 0, and h_a's own chain of sums is what it was
+template <bool TRAIN>
 __global__ __launch_bounds__(256) void attn_pool_merge_kernel(ShShape s, ShWork wk, float* __restrict__ h_a) {
   const int q = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
   if (c >= s.w) return;
   float v = 0.f;
-  for (int k = 0; k < s.K; ++k)
+  for (int k = 0; k < s.K; ++k) {
+    float vk = 0.f;
     for (int m = 0; m < s.M; ++m) {
       const int slot = wk.qslot[(size_t)q * s.M + m];
       if (slot < 0) continue;  // (an empty slot: its rows are zero)
       const int grp = slot / s.G, g = slot % s.G;
-      for (int sp = 0; sp < s.S; ++sp) v += wk.part[((((size_t)grp * s.K + k) * s.S + sp) * s.G + g) * s.w + c];
+      for (int sp = 0; sp < s.S; ++sp) {
+        const float p = wk.part[((((size_t)grp * s.K + k) * s.S + sp) * s.G + g) * s.w + c];
+        v += p;
+        if constexpr (TRAIN) vk += p;
+      }
     }
+    if constexpr (TRAIN) {
+      const float r = wk.r[(size_t)q * s.K + k];
+      wk.u[((size_t)q * s.K + k) * s.w + c] = r > 0.f ? vk / r : 0.f;
+    }
+  }
   h_a[(size_t)q * s.w + c] = v;
 }
 
@@ -173,24 +192,26 @@ extern "C" int fvta_attn_pool_plan(const fvta_attn_pool_desc* d, int32_t out[4])
   return FVTA_OK;
 }
 
-// the eight launches; TW: under the time warp, tw_scale [NQ,M JX] written by an earlier launch on the same stream
-template <bool TW>
+// the eight launches; TW: under the time warp, tw_scale [NQ,M JX] written by an earlier launch on the same stream;
+// TRAIN: the ordered plan, the arg-max, L / r / u, wk carved from (saved, workspace)
+template <bool TW, bool TRAIN = false>
 static int pool_forward(ShShape s, const ShWork& wk, const float* pool, const uint8_t* pool_mask, const float* hq,
                         const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a, float* a_logits,
                         hipStream_t st, const float* tw_scale, const char* who) {
   s.use_mask = (pool_mask && qmask) ? 1 : 0;  // model_v2.py:233: the mask applies only when both are given
   hipLaunchKernelGGL(attn_vecs_kernel, dim3((s.w + 255) / 256), dim3(256), 0, st, W, s.w, s.simi, 0, wk.vecs);
   hipLaunchKernelGGL(attn_shared_prep_q_kernel, dim3(s.NQ, s.JP / 4), dim3(256), 0, st, s, wk, hq, b);
-  hipLaunchKernelGGL((attn_shared_plan_kernel<false, true>), dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)albums);
+  static_assert(!(TW && TRAIN), "training over the pool is not under the time warp");
+  hipLaunchKernelGGL((attn_shared_plan_kernel<TRAIN, true>), dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)albums);
   const dim3 lgrid((unsigned)((int64_t)s.ngmax * s.K * s.ntile));
   const ShTwArgs tw{tw_scale, nullptr, nullptr};
   if (s.JP == 32)
-    hipLaunchKernelGGL((attn_shared_logits_kernel<1, false, TW, true>), lgrid, dim3(SH_NT), 0, st, s, wk, pool, pool_mask, qmask,
+    hipLaunchKernelGGL((attn_shared_logits_kernel<1, TRAIN, TW, true>), lgrid, dim3(SH_NT), 0, st, s, wk, pool, pool_mask, qmask,
                        a_logits, tw);
   else
-    hipLaunchKernelGGL((attn_shared_logits_kernel<2, false, TW, true>), lgrid, dim3(SH_NT), 0, st, s, wk, pool, pool_mask, qmask,
+    hipLaunchKernelGGL((attn_shared_logits_kernel<2, TRAIN, TW, true>), lgrid, dim3(SH_NT), 0, st, s, wk, pool, pool_mask, qmask,
                        a_logits, tw);
-  hipLaunchKernelGGL(attn_pool_empty_kernel, dim3(s.NR), dim3(256), 0, st, s, wk, (const int*)albums, a_logits);
+  hipLaunchKernelGGL(attn_pool_empty_kernel<TRAIN>, dim3(s.NR), dim3(256), 0, st, s, wk, (const int*)albums, a_logits);
   ShShape sq = s;  // the softmaxes run per question over all of its positions
   sq.T = s.TO;
   hipLaunchKernelGGL(attn_shared_softmax_kernel, dim3(s.NQ), dim3(256), 0, st, sq, wk);
@@ -198,7 +219,7 @@ static int pool_forward(ShShape s, const ShWork& wk, const float* pool, const ui
     sh_launch_wsum<8, TW, true>(s, wk, pool, tw_scale, st);
   else
     sh_launch_wsum<4, TW, true>(s, wk, pool, tw_scale, st);
-  hipLaunchKernelGGL(attn_pool_merge_kernel, dim3(s.NQ, (s.w + 255) / 256), dim3(256), 0, st, s, wk, h_a);
+  hipLaunchKernelGGL(attn_pool_merge_kernel<TRAIN>, dim3(s.NQ, (s.w + 255) / 256), dim3(256), 0, st, s, wk, h_a);
   FVTA_CHECK_LAUNCH(who);
   return FVTA_OK;
 }
@@ -248,4 +269,194 @@ extern "C" int fvta_attn_pool_fwd_tw(const fvta_attn_pool_tw_desc* d, const floa
   hipLaunchKernelGGL(attn_pool_tw_scale_kernel, dim3(s.NQ, (s.TO + 255) / 256), dim3(256), 0, st, s, d->warp_type,
                      (int)ceilf(d->window_t), energy, lq, (const int*)albums, WH_b, WC_W, WC_b, tw.scale, scale_out);
   return pool_forward<true>(s, tw.wk, pool, pool_mask, hq, qmask, albums, W, b, h_a, a_logits, st, tw.scale, "attn_pool_fwd_tw");
+}
+
+// ================= training over the pool (fvta_attn_pool_fwd_train / fvta_attn_pool_bwd) ================================
+// The forward is pool_forward<false, true>: the launches above on the training ShWork -- the ordered plan (an album's
+// references by ascending id q M + m), the arg-max at the reference's slot, L / r / u -- with what the backward reads in
+// `saved`.  h_a and a_logits are fvta_attn_pool_fwd's bits: the placement of a reference changes none.
+// The backward is attn_shared_bwd.hip's five launches with the album's questions replaced by the album's references
+// (attn_shared_bwd_kernels.h, POOL = true), and one small kernel in front of the fold:
+//   1. attn_shared_bwd_prep_kernel            per question over its M JX positions
+//   2. attn_shared_bwd_rows_kernel<.., POOL>  per (pooled album, k, chunk of row tiles): the album's references in plan
+//                                             order; dx -> [NQ,K,M JX] at the reference's slot; every d_pool row stored once
+//   3. attn_shared_bwd_q_kernel<G, ., POOL>   a lane group per reference; partials per (group, split)
+//   3b. attn_pool_bwd_dct_kernel              d ct[q] = its non-empty slots' partials in (slot, split) order -> dctq [NQ,JP]
+//   4. attn_pool_bwd_fold_kernel              attn_bwd_fold_body with dQs[q,j] summed the same way (slot ascending, then
+//                                             split) and d ct taken from dctq as ONE slot; a question without a reference
+//                                             sums nothing: d_hq = exact zeros
+//   5. attn_shared_bwd_params_kernel          as it is: pvec per (question, 8 positions), rowp per row-pass workgroup
+// Determinism: as attn_shared_bwd.hip.  The one sum whose order depends on data -- d_pool over an album's references --
+// runs in `order`, a function of `albums` alone.  At M = 1 every launch computes what fvta_attn_shared_bwd's does (a sum
+// over one slot starts from 0 + x): the same bits.
+namespace fvta {
+
+// the backward's workspace: attn_shared_bwd.hip's for the pooled shape, then dctq [NQ,JP]
+struct PoolBwdWork {
+  ShBwdWork base;
+  float* dctq;
+  size_t bytes;
+  PoolBwdWork(const ShShape& s, const ShBwdShape& b, void* p) : base(s, b, p) {
+    FvtaCarver c(p);
+    c.off = base.bytes;
+    dctq = c.take<float>((size_t)s.NQ * s.JP);
+    bytes = c.off;
+  }
+};
+
+// slot of reference (q, m) in the partials, -1 for an empty slot; the plan's own number, bounded all the same
+__device__ __forceinline__ int pool_ref_slot(const ShShape& s, const ShWork& sv, int q, int m) {
+  const int slot = sv.qslot[(size_t)q * s.M + m];
+  return slot < 0 ? -1 : min(slot, s.ngmax * s.G - 1);
+}
+
+// acc += ld(0), += ld(1), ... in that order, eight loads in flight (attn_bwd_slot_sum's chain, continued across slots)
+template <class V, class LD>
+__device__ __forceinline__ void pool_slot_add(V& acc, int n, LD ld) {
+  int i = 0;
+  for (; i + 8 <= n; i += 8) {
+    V v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = ld(i + u);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc += v[u];
+  }
+  for (; i < n; ++i) acc += ld(i);
+}
+
+// ---- 3b.  grid NQ, 64 threads: thread j < JP
+__global__ __launch_bounds__(64) void attn_pool_bwd_dct_kernel(ShShape s, ShBwdShape bs, ShWork sv, ShBwdWork wk,
+                                                              float* __restrict__ dctq) {
+  const int q = blockIdx.x, j = threadIdx.x;
+  if (j >= s.JP) return;
+  float acc = 0.f;
+  for (int m = 0; m < s.M; ++m) {
+    const int slot = pool_ref_slot(s, sv, q, m);
+    if (slot < 0) continue;
+    const size_t row0 = (size_t)(slot / s.G) * bs.TS * SH_BN + (size_t)(slot % s.G) * s.JP + j;
+    pool_slot_add(acc, bs.TS, [&](int ts) { return wk.dctp[row0 + (size_t)ts * SH_BN]; });
+  }
+  dctq[(size_t)q * s.JP + j] = acc;
+}
+
+// ---- 4.  grid (NQ, ceil(w / 256), JZ), 256 threads
+__global__ __launch_bounds__(256) void attn_pool_bwd_fold_kernel(ShShape s, ShBwdShape bs, ShWork sv, ShBwdWork wk,
+                                                                const float* __restrict__ dctq, const float* __restrict__ hq,
+                                                                float* __restrict__ d_hq) {
+  const int q = blockIdx.x, c = blockIdx.y * 256 + 4 * (threadIdx.x & 63);
+  const int w = s.w, JP = s.JP, JQ = s.JQ, TS = bs.TS;
+  const bool live = c < w;
+  f32x4 pU, pCq, pC2;
+  if (!attn_bwd_fold_body(sv.vecs, hq + (size_t)q * JQ * w, d_hq + (size_t)q * JQ * w, false, dctq + (size_t)q * JP, (size_t)0, 1,
+                          wk.dctn + (size_t)q * JP, w, JP, JQ,
+                          [&](int j) {
+                            f32x4 acc = zero4();
+                            for (int m = 0; m < s.M; ++m) {
+                              const int slot = pool_ref_slot(s, sv, q, m);
+                              if (slot < 0) continue;
+                              const size_t row0 = (size_t)(slot / s.G) * TS * SH_BN + (size_t)(slot % s.G) * JP + j;
+                              pool_slot_add(acc, TS, [&](int ts) { return ld4_if(live, wk.qpart + (row0 + (size_t)ts * SH_BN) * w + c); });
+                            }
+                            return acc;
+                          },
+                          pU, pCq, pC2))
+    return;
+  float* pv = wk.pvec + ((size_t)q * bs.JZ + blockIdx.z) * 3 * w;
+  *reinterpret_cast<f32x4*>(pv + c) = pU;
+  *reinterpret_cast<f32x4*>(pv + w + c) = pCq;
+  *reinterpret_cast<f32x4*>(pv + 2 * w + c) = pC2;
+}
+
+// training: the shape, simiMatrix 1-3, the backward's grids
+static int fvta_attn_pool_check_train(const fvta_attn_pool_desc* d, const char* who) {
+  if (int e = fvta_attn_pool_check(d, who)) return e;
+  if (d->simi == 4) {
+    fvta_set_error("%s: simiMatrix 4 has no pooled backward (simiMatrix 1-3); the per-question route "
+                   "(fvta_attn_fwd / fvta_attn_bwd on the gathered rows) covers it", who);
+    return FVTA_ERR_UNSUPPORTED;
+  }
+  const ShShape s = sh_pool_shape(d);
+  const ShBwdShape b = shb_shape(s);
+  if ((int64_t)s.A * s.K * b.nch > 0x7fffffff || (int64_t)s.ngmax * b.TS * b.nsl > 0x7fffffff) {
+    fvta_set_error("%s: unsupported shape (P=%d NQ=%d M=%d K=%d JX=%d JQ=%d w=%d): too many workgroups", who, d->P, d->NQ, d->M,
+                   d->K, d->JX, d->JQ, d->w);
+    return FVTA_ERR_UNSUPPORTED;
+  }
+  return FVTA_OK;
+}
+
+}  // namespace fvta
+
+extern "C" size_t fvta_attn_pool_saved_bytes(const fvta_attn_pool_desc* d) {
+  if (fvta_attn_pool_check_train(d, "attn_pool_saved_bytes") != FVTA_OK) return 0;
+  return ShWork(sh_pool_shape(d), nullptr, nullptr).saved_bytes;
+}
+
+extern "C" int fvta_attn_pool_fwd_train(const fvta_attn_pool_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
+                                        const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a,
+                                        float* a_logits, void* saved, void* workspace, fvta_stream_t stream_) {
+  if (int e = fvta_attn_pool_check_train(d, "attn_pool_fwd_train")) return e;
+  FVTA_CHECK_ARG(pool && hq && albums && W && h_a && saved && workspace, "attn_pool_fwd_train: null pointer");
+  const ShShape s = sh_pool_shape(d);  // (the training ShWork's share of the workspace is no larger than the inference call's)
+  return pool_forward<false, true>(s, ShWork(s, saved, workspace), pool, pool_mask, hq, qmask, albums, W, b, h_a, a_logits,
+                                   (hipStream_t)stream_, nullptr, "attn_pool_fwd_train");
+}
+
+extern "C" size_t fvta_attn_pool_bwd_workspace_bytes(const fvta_attn_pool_desc* d) {
+  if (fvta_attn_pool_check_train(d, "attn_pool_bwd_workspace_bytes") != FVTA_OK) return 0;
+  const ShShape s = sh_pool_shape(d);
+  return PoolBwdWork(s, shb_shape(s), nullptr).bytes;
+}
+
+extern "C" int fvta_attn_pool_bwd_plan(const fvta_attn_pool_desc* d, int32_t out[4]) {
+  if (int e = fvta_attn_pool_check_train(d, "attn_pool_bwd_plan")) return e;
+  FVTA_CHECK_ARG(out != nullptr, "attn_pool_bwd_plan: null pointer");
+  const ShBwdShape b = shb_shape(sh_pool_shape(d));
+  out[0] = b.TR;
+  out[1] = b.TS;
+  out[2] = SHB_CS;
+  out[3] = b.tpw;
+  return FVTA_OK;
+}
+
+extern "C" int fvta_attn_pool_bwd(const fvta_attn_pool_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
+                                  const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, const float* d_h_a,
+                                  const void* saved, float* d_pool, float* d_hq, float* dW, float* db, void* workspace,
+                                  fvta_stream_t stream_) {
+  if (int e = fvta_attn_pool_check_train(d, "attn_pool_bwd")) return e;
+  FVTA_CHECK_ARG(pool && hq && albums && d_h_a && saved && d_pool && d_hq && dW && db && workspace, "attn_pool_bwd: null pointer");
+  hipStream_t st = (hipStream_t)stream_;
+  ShShape s = sh_pool_shape(d);
+  s.use_mask = (pool_mask && qmask) ? 1 : 0;
+  const ShBwdShape bs = shb_shape(s);
+  const ShWork sv(s, const_cast<void*>(saved), nullptr);
+  const PoolBwdWork pw(s, bs, workspace);
+  const ShBwdWork& wk = pw.base;
+  ShShape sq = s;  // the prep runs per question over all of its positions
+  sq.T = s.TO;
+  hipLaunchKernelGGL(attn_shared_bwd_prep_kernel, dim3(s.NQ), dim3(s.K > 4 ? 1024 : 256), 0, st, sq, sv, wk, d_h_a);
+  const dim3 rgrid((unsigned)((int64_t)s.A * s.K * bs.nch));
+#define FVTA_POOL_ROWS(TPR, CPT, RPT) \
+  hipLaunchKernelGGL((attn_shared_bwd_rows_kernel<TPR, CPT, RPT, false, true>), rgrid, dim3(256), 0, st, s, bs, sv, wk, pool, d_h_a, \
+                     d_pool, ShBwdTwArgs{})
+  switch (s.w) {
+    case 64: FVTA_POOL_ROWS(16, 1, 8); break;
+    case 128: FVTA_POOL_ROWS(32, 1, 8); break;
+    case 256: FVTA_POOL_ROWS(64, 1, 8); break;
+    case 512: FVTA_POOL_ROWS(128, 1, 8); break;
+    case 1024: FVTA_POOL_ROWS(256, 1, 8); break;
+    default: FVTA_POOL_ROWS(256, 2, 4); break;
+  }
+#undef FVTA_POOL_ROWS
+  const dim3 qgrid((unsigned)((int64_t)s.ngmax * bs.TS * bs.nsl));
+  if (s.G == 8)
+    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<8, false, true>), qgrid, dim3(64), 0, st, s, bs, sv, wk, pool, (const float*)nullptr);
+  else
+    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<4, false, true>), qgrid, dim3(64), 0, st, s, bs, sv, wk, pool, (const float*)nullptr);
+  hipLaunchKernelGGL(attn_pool_bwd_dct_kernel, dim3(s.NQ), dim3(64), 0, st, s, bs, sv, wk, pw.dctq);
+  hipLaunchKernelGGL(attn_pool_bwd_fold_kernel, dim3(s.NQ, (s.w + 255) / 256, bs.JZ), dim3(256), 0, st, s, bs, sv, wk,
+                     (const float*)pw.dctq, hq, d_hq);
+  hipLaunchKernelGGL(attn_shared_bwd_params_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, st, s, bs, wk, dW, db);
+  FVTA_CHECK_LAUNCH("attn_pool_bwd");
+  return FVTA_OK;
 }

@@ -59,6 +59,24 @@ inline ShShape sh_pool_shape(const fvta_attn_pool_desc* d) {
   return s;
 }
 
+// a reference's question, its first position in that question, and the positions per question (the stride of amax /
+// jmax / a_logits / dx); POOL = false: (ref, 0, T)
+template <bool POOL>
+__device__ __forceinline__ int sh_ref_q(const ShShape& s, int ref) {
+  if constexpr (POOL) return ref / s.M;
+  return ref;
+}
+template <bool POOL>
+__device__ __forceinline__ int sh_ref_off(const ShShape& s, int ref) {  // first position of the reference in its question
+  if constexpr (POOL) return (ref % s.M) * s.T;
+  return 0;
+}
+template <bool POOL>
+__device__ __forceinline__ int sh_positions(const ShShape& s) {  // positions per question: the stride of amax / a_logits
+  if constexpr (POOL) return s.TO;
+  return s.T;
+}
+
 // The forward's buffers.  Inference (fvta_attn_shared_fwd) carves all of them from the workspace.  Training
 // (fvta_attn_shared_fwd_train) carves what the backward reads from `saved` -- the four training-only pieces included -- and
 // only the rest (coef, part, agrp) from the workspace; `bytes` is the workspace's share, `saved_bytes` the other.
@@ -66,7 +84,7 @@ struct ShWork {
   float *vecs, *Qs, *ct, *amax, *M, *coef, *part;
   int *acnt, *astart, *agrp, *order, *qslot, *ngroups;
   int4* grp;
-  uint8_t* jmax;     // training only (else null): [NQ,K,T] FIRST arg-max j of the masked (tanh'd) logits
+  uint8_t* jmax;     // training only (else null): [NQ,K,TO] FIRST arg-max j of the masked (tanh'd) logits
   float *L, *r, *u;  // training only: L [NQ,K] = sum_t exp(amax - M), r [NQ,K] = softmax_k(M), u [NQ,K,w] = inner softsel
   size_t bytes, saved_bytes;
   ShWork(const ShShape& s, void* p) {
@@ -93,8 +111,8 @@ struct ShWork {
   ShWork(const ShShape& s, void* saved, void* work) {
     FvtaCarver c(saved), v(work);
     const size_t nk = (size_t)s.NQ * s.K;
-    amax = c.take<float>(nk * s.T);
-    jmax = c.take<uint8_t>(nk * s.T);
+    amax = c.take<float>(nk * s.TO);   // (the pooled call: M T positions per question, NR = NQ M references)
+    jmax = c.take<uint8_t>(nk * s.TO);
     M = c.take<float>(nk);
     L = c.take<float>(nk);
     r = c.take<float>(nk);
@@ -103,10 +121,10 @@ struct ShWork {
     ct = c.take<float>((size_t)s.NQ * s.JP);
     vecs = c.take<float>((size_t)VEC_COUNT * s.w);
     grp = c.take<int4>((size_t)s.ngmax);
-    order = c.take<int>((size_t)s.NQ);
-    qslot = c.take<int>((size_t)s.NQ);
+    order = c.take<int>((size_t)s.NR);
+    qslot = c.take<int>((size_t)s.NR);
     ngroups = c.take<int>(1);
-    astart = c.take<int>((size_t)s.A);   // an album's questions are order[astart[a] .. + acnt[a])
+    astart = c.take<int>((size_t)s.A);   // an album's questions (references) are order[astart[a] .. + acnt[a])
     acnt = c.take<int>((size_t)s.A);
     saved_bytes = c.off;
     coef = v.take<float>(nk);

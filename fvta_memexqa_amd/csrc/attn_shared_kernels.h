@@ -5,8 +5,9 @@
 //   POOL = true   a reference is a (question, slot) pair, id q * M + m: the block reads question q's Qs / ct / qmask and
 //                 writes positions m * T .. + T of q's M * T (s.T = JX, the rows of ONE pooled album; s.TO = M * T).
 //                 A negative index is an empty slot: it joins no group and its qslot is -1
-// sh_ref_q / sh_ref_off below are the whole of it; with POOL = false they fold to (ref, 0) and the kernels are what they
-// were.  The non-template kernels both callers launch (question side, the softmaxes' scalars) stay in attn_shared.hip.
+// sh_ref_q / sh_ref_off (attn_shared_common.h: the backward's kernels use them too) are the whole of it; with
+// POOL = false they fold to (ref, 0) and the kernels are what they were.  The non-template kernels both callers launch
+// (question side, the softmaxes' scalars) stay in attn_shared.hip.
 #pragma once
 #include "attn_shared_common.h"
 #include "gemm_f32.h"
@@ -18,22 +19,6 @@ __global__ __launch_bounds__(256) void attn_shared_prep_q_kernel(ShShape s, ShWo
                                                                  const float* __restrict__ bptr);
 // attn_shared.hip.  grid NQ, 256 threads: over s.T positions per (question, k) -- the pooled caller passes T = M * JX
 __global__ __launch_bounds__(256) void attn_shared_softmax_kernel(ShShape s, ShWork wk);
-
-template <bool POOL>
-__device__ __forceinline__ int sh_ref_q(const ShShape& s, int ref) {
-  if constexpr (POOL) return ref / s.M;
-  return ref;
-}
-template <bool POOL>
-__device__ __forceinline__ int sh_ref_off(const ShShape& s, int ref) {  // first position of the reference in its question
-  if constexpr (POOL) return (ref % s.M) * s.T;
-  return 0;
-}
-template <bool POOL>
-__device__ __forceinline__ int sh_positions(const ShShape& s) {  // positions per question: the stride of amax / a_logits
-  if constexpr (POOL) return s.TO;
-  return s.T;
-}
 
 // 64 rows x 256 columns, a wave 64 x 64: 200 registers, two workgroups per CU.  (MmaF32<2, 2, 2, 4>, 128 rows and half the
 // question staging per row, was measured: 331 registers, one wave per SIMD, and no faster at 8 questions per album, 20 %
@@ -62,12 +47,12 @@ __device__ __forceinline__ int sh_ref_album(const int* album, int i, int A) {
 // and per distinct album of a batch ONE lane advances that album's cursor by the number of the batch's questions about
 // it, which take their places by lane rank.  Every cursor update is issued by a single wave in program order, one after
 // the other: nothing depends on the order in which atomics of different waves arrive.  (An integer atomic is still the
-// instruction, because it reads the cursor at L2, past this wave's own vector cache.)
+// instruction, because it reads the cursor at L2, past this wave's own vector cache.)  ORDERED and POOL: the walk runs over
+// the reference ids q M + m, so an album's references stand by ascending id; an empty slot joins no batch.
 template <bool ORDERED, bool POOL = false>
 __global__ __launch_bounds__(SH_PLAN_NT) void attn_shared_plan_kernel(ShShape s, ShWork wk, const int* __restrict__ album) {
   __shared__ int cell_c[SH_PLAN_NT], cell_g[SH_PLAN_NT];
   const int tid = threadIdx.x, A = s.A, NR = s.NR, G = s.G;
-  static_assert(!(ORDERED && POOL), "the ordered plan is the training one: questions only");
   for (int a = tid; a < A; a += SH_PLAN_NT) wk.acnt[a] = 0;
   __syncthreads();
   for (int i = tid; i < NR; i += SH_PLAN_NT) {
@@ -110,8 +95,12 @@ __global__ __launch_bounds__(SH_PLAN_NT) void attn_shared_plan_kernel(ShShape s,
     if (tid >= 64) return;
     for (int base = 0; base < NR; base += 64) {
       const int i = base + tid;
-      const bool ok = i < NR;
-      const int a = ok ? sh_album(album, i, A) : -1;
+      bool ok = i < NR;
+      const int a = ok ? sh_ref_album<POOL>(album, i, A) : -1;
+      if constexpr (POOL) {  // an empty slot: in no group, and out of the walk
+        if (ok && a < 0) wk.qslot[i] = -1;
+        ok = ok && a >= 0;
+      }
       unsigned long long todo = __ballot(ok);
       while (todo) {
         const int leader = __ffsll((long long)todo) - 1;
@@ -143,7 +132,8 @@ __global__ __launch_bounds__(SH_PLAN_NT) void attn_shared_plan_kernel(ShShape s,
 }
 
 // ---- logits.  grid ngmax * K * ntile, 256 threads
-// TRAIN: also the FIRST arg-max j of every row's maximum -> jmax [NQ,K,T] (compile-time: the inference kernel is unchanged)
+// TRAIN: also the FIRST arg-max j of every row's maximum -> jmax [NQ,K,T] -- POOL: [NQ,K,M T], at the reference's slot --
+// (compile-time: the inference kernel is unchanged)
 // TW (compile-time too; tw_scale [NQ,T] -- POOL: [NQ,M T], read at the reference's slot -- else unused): the logits of the WARPED rows h' = s h, s = tw_scale[q,t], from the
 // rows as they are held.  The scalar goes through the bilinear form: x = s (h.Qs + Rh.h) + s^2 (R2.h^2) + ct, cosine
 // x = (h.Qn) s rsqrt(max(s^2 |h|^2, 1e-12)) -- the row pass keeps Rh.h and R2.h^2 (cosine: the raw sum h^2) apart, and
@@ -160,7 +150,7 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
   // TW: s_rt holds Rh.h, s_r2 R2.h^2 (cosine: sum h^2); s_sc, s_s2 the factor of the product and the addend per (question, row)
   __shared__ float s_r2[TW ? SH_R : 1], s_sc[TW ? G : 1][TW ? SH_R : 1], s_s2[TW ? G : 1][TW ? SH_R : 1];
   __shared__ int s_q[G], s_o[POOL ? G : 1];  // a column block's question and -- POOL -- its slot's first position
-  static_assert(!(POOL && TRAIN), "the pooled calls are inference ones");
+  static_assert(!(POOL && TRAIN && TW), "the pooled training call is not under the time warp");
   __shared__ uint8_t s_hv[SH_R], s_cv[SH_BN];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int tile = blockIdx.x % s.ntile, k = (blockIdx.x / s.ntile) % s.K, grp = blockIdx.x / (s.ntile * s.K);
@@ -316,7 +306,7 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
           if (JT == 2 && jm == 255 && mx[jn + 1][r] == m) jm = 32 + mma.l31;
 #pragma unroll
           for (int o = 16; o > 0; o >>= 1) jm = min(jm, __shfl_xor(jm, o, 64));
-          if (mma.l31 == r && q >= 0 && t < T) wk.jmax[((size_t)q * K + k) * T + t] = (uint8_t)min(jm, JQ - 1);
+          if (mma.l31 == r && q >= 0 && t < T) wk.jmax[at_of(q, mma.col_of(jn) / JP, t)] = (uint8_t)min(jm, JQ - 1);
           if constexpr (TW) {  // lin at the winner: the one lane that holds column jm puts it in, 31 zeros are added to it
             const int mine = mx[jn][r] == m ? mma.l31 : ((JT == 2 && mx[jn + 1][r] == m) ? 32 + mma.l31 : 255);
             const float acc = (JT == 2 && mine >= 32) ? mma.acc[i][JT == 2 ? jn + 1 : jn][r] : mma.acc[i][jn][r];

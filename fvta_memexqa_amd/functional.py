@@ -226,24 +226,32 @@ def attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask=None, hq_mask=Non
     return h_a[:, :w].contiguous(), a
 
 
-def attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask=None, hq_mask=None, simiMatrix=1, add_tanh=False):
+def attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask=None, hq_mask=None, simiMatrix=1, add_tanh=False,
+                            differentiable=False):
     """attention_3d for NQ questions that each LIST M albums of one pool of encoded albums: pool [P,K,JX,w], hq [NQ,JQ,w],
     albums [NQ,M] (a tensor, an array or a list of lists -- ragged lists are padded; entries in [0, P), or -1 for an empty
     slot, which needs both masks; validated on the host before the upload), W / b as attention_raw -> (h_a [NQ,w],
     a_logits [NQ,K,M*JX,JQ]): question i attends its albums' rows laid end to end, hinfo_i[k, m*JX + j] =
     pool[albums[i,m], k, j] (an empty slot: JX masked zero rows), with attention_raw's result for that context -- which is
     never built: each pooled album is held once and read once per group of the (question, slot) references that name it
-    (fvta_attn_pool_fwd).  Forward-only: with gradient mode on and an argument that requires grad it raises, as
-    attention_3d_shared_raw does."""
+    (fvta_attn_pool_fwd).  differentiable=False (the default) is that inference call: with gradient mode on and an
+    argument that requires grad it raises, as attention_3d_shared_raw does.  differentiable=True goes through
+    autograd.pooled_focal_attention (simiMatrix 1-3; 4 raises NotImplementedError): gradients flow from h_a to pool --
+    summed over every (question, slot) that names the album, [P,K,JX,w] -- hq, W and b; a_logits carries none."""
     if simiMatrix not in (1, 2, 3, 4):
         raise ValueError("similarity matrix not implemented")
+    if differentiable and simiMatrix == 4:
+        raise NotImplementedError("attention_3d_pooled_raw(differentiable=True): simiMatrix 4 has no pooled backward; use the "
+                                  "per-question attention_3d (attention_raw) on the gathered rows")
     tensors = [t for t in (pool, hq, W, b) if torch.is_tensor(t)]
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+    if not differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         raise RuntimeError("attention_3d_pooled_raw is forward-only: call it under torch.no_grad(), or use the per-question "
                            "attention_3d (functional.attention_3d / attention_raw, nn.FocalAttention3D.forward) on the "
                            "gathered rows")
-    pool, hq = _f32(pool.detach()), _f32(hq.detach())
-    W, b = (None if W is None else W.detach()), (None if b is None else b.detach())
+    if not differentiable:
+        pool, hq = pool.detach(), hq.detach()
+        W, b = (None if W is None else W.detach()), (None if b is None else b.detach())
+    pool, hq = _f32(pool), _f32(hq)
     if pool.dim() != 4:
         raise ValueError("album pool: expected [P,K,JX,w], got shape %s" % (tuple(pool.shape),))
     P, K, JX, w = pool.shape
@@ -264,8 +272,12 @@ def attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask=None, hq_mask=None
     dev = ops.require_gpu()
     pm = ops.as_mask_u8(pool_mask.reshape(P, K, JX)) if both else None
     qm = ops.as_mask_u8(hq_mask) if both else None
-    op = ops.PooledFocalAttention(P, NQ, idx.shape[1], K, JX, JQ, wp, simiMatrix, add_tanh)
-    h_a, a = op.forward(_pad_channels(pool, wp), pm, _pad_channels(hq, wp), qm, idx.to(dev), W, b, want_logits=True)
+    if differentiable:
+        h_a, a = autograd.pooled_focal_attention(_pad_channels(pool, wp), _pad_channels(hq, wp), idx.to(dev), W, b, pm, qm,
+                                                 simiMatrix, add_tanh)
+    else:
+        op = ops.PooledFocalAttention(P, NQ, idx.shape[1], K, JX, JQ, wp, simiMatrix, add_tanh)
+        h_a, a = op.forward(_pad_channels(pool, wp), pm, _pad_channels(hq, wp), qm, idx.to(dev), W, b, want_logits=True)
     return h_a[:, :w].contiguous(), a
 
 

@@ -152,12 +152,17 @@ class FocalAttention3D(_AttLogits):
         return h_a, a
 
 
-    def forward_pooled(self, pool, hq, albums, pool_mask=None, hq_mask=None, time_warp=None, lq=None, energy=None):
+    def forward_pooled(self, pool, hq, albums, pool_mask=None, hq_mask=None, time_warp=None, lq=None, energy=None,
+                       differentiable=False):
         """forward() for NQ questions that each list M albums of one pool: pool [P,K,JX,w], hq [NQ,JQ,w], albums [NQ,M]
         (entries in [0, P), -1 an empty slot -- which needs both masks) -> (h_a [NQ,w], a_logits [NQ,K,M*JX,JQ]) with this
         module's att_logits/{W,b} (functional.attention_3d_pooled_raw): forward() on each question's albums laid end to
-        end, with no such tensor built.  Inference only: under gradient mode the parameters require grad and the call
-        raises; use it under torch.no_grad().
+        end, with no such tensor built.  differentiable=False is the inference call: under gradient mode the parameters
+        require grad and the call raises; use it under torch.no_grad().  differentiable=True trains over the pool
+        (simiMatrix 1-3; 4 raises NotImplementedError): h_a's gradient reaches pool [P,K,JX,w] -- summed over every
+        (question, slot) that names the album -- hq and the parameters, a_logits carries none.  Not under the time warp:
+        with time_warp it raises NotImplementedError; the per-question route (forward() on nn.TimeWarp's warp of the
+        gathered rows) trains there.
         time_warp (an nn.TimeWarp) with lq [NQ,w], the questions' last states: the attention over each question's albums
         laid end to end and warped for that question -- forward(time_warp(hinfo_i, lq)[0], ...) -- with the pool still
         held once (functional.attention_3d_pooled_warped_raw).  Its parameters and its window buffer are used; energy
@@ -166,7 +171,11 @@ class FocalAttention3D(_AttLogits):
         if time_warp is None and (lq is not None or energy is not None):
             raise ValueError("forward_pooled: lq / energy belong to the time warp; pass time_warp (an nn.TimeWarp) with them")
         if time_warp is None:
-            return functional.attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask, hq_mask, self.simiMatrix, self.add_tanh)
+            return functional.attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask, hq_mask, self.simiMatrix, self.add_tanh,
+                                                      differentiable=differentiable)
+        if differentiable:
+            raise NotImplementedError("forward_pooled: under the time warp this call is the inference one; the per-question "
+                                      "route (forward() on time_warp's warp of each question's gathered rows) trains there")
         if lq is None:
             raise ValueError("forward_pooled: the time warp needs lq [NQ,w], the questions' last states")
         if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
@@ -199,7 +208,9 @@ class AlbumPool:
     """P encoded albums, each kept ONCE for any number of questions and any album lists: pool [P,K,JX,w] and pool_mask
     [P,K,JX], held contiguous fp32 / u8 on the device and detached.  Where nn.AlbumMemory keeps one context per distinct
     LIST of albums, this keeps one block of rows per ALBUM and every question names the albums it reads (MemexQA's
-    album_ids).  No parameters, no encoder."""
+    album_ids).  No parameters, no encoder.  It stays a detached inference holder: no gradient reaches the rows it was
+    built from.  Training over a pool goes through nn.FocalAttention3D.forward_pooled(differentiable=True) on a pool
+    tensor that requires grad."""
 
     def __init__(self, pool, pool_mask=None):
         dev = ops.require_gpu()

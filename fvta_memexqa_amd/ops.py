@@ -412,7 +412,9 @@ class PooledFocalAttention:
     """attention_3d (model_v2.py:210-298) of NQ questions that each list M albums of ONE pool of P encoded albums: pool
     [P,K,JX,w], pool_mask [P,K,JX], hq [NQ,JQ,w], qmask [NQ,JQ], albums [NQ,M] int32 on the device (validate them with
     check_album_lists before the upload; -1 is an empty slot).  Question i gets FocalAttention's result on its albums' rows
-    laid end to end, [K, M*JX, w], which is never built.  Inference only (fvta_attn_pool_fwd, nothing kept)."""
+    laid end to end, [K, M*JX, w], which is never built.  forward() is the inference call (fvta_attn_pool_fwd, nothing
+    kept); forward_train() / backward() are the training pair (simiMatrix 1-3), whose d_pool stays [P,K,JX,w]: the sum of
+    the per-question row gradients over every (question, slot) that refers to the album."""
 
     def __init__(self, P, NQ, M, K, JX, JQ, w, simi, add_tanh):
         self.lib = _lib.load()
@@ -444,6 +446,51 @@ class PooledFocalAttention:
                                           ptr(albums), ptr(W), ptr(b), ptr(h_a), ptr(a_logits), ptr(self.work),
                                           stream_ptr()), "fvta_attn_pool_fwd")
         return h_a, a_logits
+
+    def _check_inputs(self, pool, pool_mask, hq, qmask, albums):
+        assert tuple(pool.shape) == (self.P, self.K, self.JX, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
+        assert albums.is_cuda and albums.dtype == torch.int32 and albums.is_contiguous() and \
+            tuple(albums.shape) == (self.NQ, self.M)
+        assert pool_mask is None or (pool_mask.dtype == torch.uint8 and tuple(pool_mask.shape) == (self.P, self.K, self.JX))
+        assert qmask is None or (qmask.dtype == torch.uint8 and tuple(qmask.shape) == (self.NQ, self.JQ))
+
+    def bwd_plan(self):
+        """{rows, tsplit, channels, tiles_per_wg}: rows per tile of the backward's row pass, JX splits and channels per
+        slice of its question pass, row tiles per workgroup of the row pass (fvta_attn_pool_bwd_plan; host only,
+        simiMatrix 1-3)"""
+        out = (ctypes.c_int32 * 4)()
+        check(self.lib.fvta_attn_pool_bwd_plan(ctypes.byref(self.desc), out), "fvta_attn_pool_bwd_plan")
+        return dict(zip(("rows", "tsplit", "channels", "tiles_per_wg"), (int(v) for v in out)))
+
+    def forward_train(self, pool, pool_mask, hq, qmask, albums, W, b, want_logits=False):
+        """forward() -- the same bits -- that leaves in self.saved (allocated on first use) what backward() reads
+        (fvta_attn_pool_fwd_train; simiMatrix 1-3)"""
+        self._check_inputs(pool, pool_mask, hq, qmask, albums)
+        if getattr(self, "saved", None) is None:
+            self.saved = _sized(self, "fvta_attn_pool_saved_bytes", "pooled attention saved: ")
+        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
+        a_logits = torch.empty(self.NQ, self.K, self.M * self.JX, self.JQ, device=self.dev, dtype=torch.float32) \
+            if want_logits else None
+        check(self.lib.fvta_attn_pool_fwd_train(ctypes.byref(self.desc), ptr(_f32c(pool)), ptr(pool_mask), ptr(_f32c(hq)),
+                                                ptr(qmask), ptr(albums), ptr(_f32c(W)), ptr(b), ptr(h_a), ptr(a_logits),
+                                                ptr(self.saved), ptr(self.work), stream_ptr()), "fvta_attn_pool_fwd_train")
+        return h_a, a_logits
+
+    def backward(self, pool, pool_mask, hq, qmask, albums, W, b, d_h_a, d_pool, d_hq, dW, db):
+        """After forward_train() with the same arguments: d_pool [P,K,JX,w] and d_hq [NQ,JQ,w] are overwritten, dW [F] and
+        db [1] accumulated into (fvta_attn_pool_bwd).  Its workspace is allocated on first use."""
+        if getattr(self, "saved", None) is None:
+            raise _lib.FvtaError("pooled attention: backward() needs a forward_train() first")
+        if getattr(self, "work_bwd", None) is None:
+            self.work_bwd = _sized(self, "fvta_attn_pool_bwd_workspace_bytes", "pooled attention backward workspace: ")
+        self._check_inputs(pool, pool_mask, hq, qmask, albums)
+        assert tuple(d_pool.shape) == (self.P, self.K, self.JX, self.w) and tuple(d_hq.shape) == (self.NQ, self.JQ, self.w)
+        assert tuple(d_h_a.shape) == (self.NQ, self.w)
+        assert d_pool.is_contiguous() and d_hq.is_contiguous() and dW.is_contiguous() and db.is_contiguous()
+        check(self.lib.fvta_attn_pool_bwd(ctypes.byref(self.desc), ptr(_f32c(pool)), ptr(pool_mask), ptr(_f32c(hq)), ptr(qmask),
+                                          ptr(albums), ptr(_f32c(W)), ptr(b), ptr(_f32c(d_h_a)), ptr(self.saved),
+                                          ptr(d_pool), ptr(d_hq), ptr(dW), ptr(db), ptr(self.work_bwd), stream_ptr()),
+              "fvta_attn_pool_bwd")
 
 
 class SharedWarpedFocalAttention:

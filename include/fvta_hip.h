@@ -291,8 +291,9 @@ int fvta_attn_shared_bwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinf
  * Range: fvta_attn_shared_fwd's (w, JQ <= 64, K <= 64, simi 1..4), P, NQ, M, JX >= 1, NQ M <= 2^28, M JX within int.
  * No host synchronisation, no memset, everything on the caller's stream.
  * fvta_attn_pool_plan (host only): out = {G, rows per logits tile, splits of JX in the weighted sum, rows per split}.
- * The time warp (use_time_warp, every warp type) is fvta_attn_pool_fwd_tw further down.  Not here, nor there: training
- * over the pool, time_warp_att, shadow rows. */
+ * The time warp (use_time_warp, every warp type) is fvta_attn_pool_fwd_tw further down; training over the pool
+ * (simiMatrix 1-3, no time warp) is fvta_attn_pool_fwd_train / fvta_attn_pool_bwd below.  Not here, nor there: training
+ * over the pool under the time warp, time_warp_att, shadow rows. */
 typedef struct fvta_attn_pool_desc {
   int32_t P, NQ, M, K, JX, JQ, w; /* P pooled albums [P,K,JX,w], NQ questions listing M albums each */
   int32_t simi;                   /* 1..4 */
@@ -304,6 +305,37 @@ int fvta_attn_pool_plan(const fvta_attn_pool_desc* d, int32_t out[4]);
 int fvta_attn_pool_fwd(const fvta_attn_pool_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
                        const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a,
                        float* a_logits, void* workspace, fvta_stream_t stream);
+
+/* Training over the pool (simiMatrix 1-3, no time warp; with simi 4 the two size queries return 0 and the calls
+ * FVTA_ERR_UNSUPPORTED: the per-question route, fvta_attn_fwd / fvta_attn_bwd on gathered rows, covers the cosine form).
+ * The contract is fvta_attn_shared_bwd's read per REFERENCE (question i, slot m):
+ * fvta_attn_pool_fwd_train: the kernels of fvta_attn_pool_fwd -- h_a and a_logits are its bits -- and, in the
+ *   caller-held `saved` (fvta_attn_pool_saved_bytes), what the backward reads: amax and the FIRST arg-max jmax (u8), both
+ *   [NQ,K,M JX], M, L, r [NQ,K], u [NQ,K,w], Qs, ct, the per-channel vectors and the plan, in which the references of a
+ *   pooled album stand by ascending id i M + m.  `workspace`: fvta_attn_pool_workspace_bytes.
+ * fvta_attn_pool_bwd: from d_h_a [NQ,w], for question i: d_hq[i] and i's share of dW / db are what fvta_attn_bwd
+ *   (accumulate = 0) gives for (hinfo_i, hq[i], its mask, qmask[i], d_h_a[i]); d_pool[p] is the sum of those calls' row
+ *   gradients over every reference albums[i,m] == p (a question that lists p twice contributes twice).  d_pool
+ *   [P,K,JX,w] and d_hq [NQ,JQ,w] are OVERWRITTEN in full (an album nobody lists: zeros; a masked row: zeros, unless a
+ *   fully masked question or (question, k) spreads its uniform softmax over it; a question that lists nothing: d_hq = 0);
+ *   dW [F] and db [1] are accumulated into.  fvta_attn_bwd's deviations carry over: first arg-max over j, ties of the max
+ *   over t split, nothing passes into the masked logits of a fully masked (question, k) or question.  The same arguments
+ *   as the forward call; `workspace`: fvta_attn_pool_bwd_workspace_bytes.
+ *   No [NQ,K,M JX,w]-sized buffer in either direction: each d_pool row is written once, a pooled album's rows are read
+ *   once per (album, k) and once per group of references to it.  No floating-point atomics, fixed summation order (an
+ *   album's references by ascending id, a question's slots by ascending slot): two calls are bitwise equal in all four
+ *   outputs, and at M = 1 they are fvta_attn_shared_bwd's bits for (A = P, T = JX).  No host synchronisation, no memset.
+ * fvta_attn_pool_bwd_plan (host only): the four words of fvta_attn_shared_bwd_plan for (A = P, T = JX, NQ M references). */
+size_t fvta_attn_pool_saved_bytes(const fvta_attn_pool_desc* d);         /* 0 bytes: see fvta_last_error */
+size_t fvta_attn_pool_bwd_workspace_bytes(const fvta_attn_pool_desc* d); /* 0 bytes: see fvta_last_error */
+int fvta_attn_pool_bwd_plan(const fvta_attn_pool_desc* d, int32_t out[4]);
+int fvta_attn_pool_fwd_train(const fvta_attn_pool_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
+                             const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a,
+                             float* a_logits, void* saved, void* workspace, fvta_stream_t stream);
+int fvta_attn_pool_bwd(const fvta_attn_pool_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
+                       const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, const float* d_h_a,
+                       const void* saved, float* d_pool, float* d_hq, float* dW, float* db, void* workspace,
+                       fvta_stream_t stream);
 
 /* fvta_attn_pool_fwd under the time warp (use_time_warp without use_time_warp_att; forward only, inference).  Per
  * question the result is what fvta_attn_fwd returns on fvta_timewarp_fwd's warp of (hinfo_i, lq[i]), hinfo_i the

@@ -199,36 +199,44 @@ def focal_attention(hinfo, hq, W, b, hmask=None, qmask=None, simi=1, add_tanh=Fa
     return _FocalAttention.apply(hinfo, hq, W, b, tscale, hmask, qmask, int(simi), bool(add_tanh), int(feat_order))
 
 
-class _SharedFocalAttention(torch.autograd.Function):
-    """(hinfo [A,K,T,w], hq [NQ,JQ,w], album int32 [NQ] on the device, W [F*w], b [1]; masks u8 | None) ->
-    (h_a [NQ,w], a_logits [NQ,K,T,JQ]): question i over album[i]'s rows, the rows held once (fvta_attn_shared_fwd_train /
-    fvta_attn_shared_bwd; simiMatrix 1-3).  a_logits is not differentiable here.  Each call owns its handle."""
+class _AlbumFocalAttention(torch.autograd.Function):
+    """The focal attention over context rows held once (simiMatrix 1-3), by the static word `pooled`:
+    False  (hinfo [A,K,T,w], hq [NQ,JQ,w], album int32 [NQ] on the device, W [F*w], b [1]; masks u8 | None) ->
+           (h_a [NQ,w], a_logits [NQ,K,T,JQ]): question i over album[i]'s rows (fvta_attn_shared_fwd_train /
+           fvta_attn_shared_bwd)
+    True   (pool [P,K,JX,w], hq, albums int32 [NQ,M] on the device, ...) -> (h_a, a_logits [NQ,K,M*JX,JQ]): question i over
+           its albums' rows laid end to end (fvta_attn_pool_fwd_train / fvta_attn_pool_bwd).  The gradient of pool stays
+           [P,K,JX,w]: the sum over every (question, slot) that refers to the album.
+    a_logits is not differentiable here.  Each call owns its handle."""
 
     @staticmethod
-    def forward(ctx, hinfo, hq, album, W, b, hmask, qmask, simi, add_tanh):
-        A, K, T, w = hinfo.shape
-        op = ops.SharedFocalAttention(A, hq.shape[0], K, T, hq.shape[1], w, simi, add_tanh)
-        h_a, a = op.forward_train(hinfo, hmask, hq, qmask, album, W, b, want_logits=True)
+    def forward(ctx, rows, hq, index, W, b, rows_mask, qmask, simi, add_tanh, pooled):
+        A, K, T, w = rows.shape
+        if pooled:
+            op = ops.PooledFocalAttention(A, hq.shape[0], index.shape[1], K, T, hq.shape[1], w, simi, add_tanh)
+        else:
+            op = ops.SharedFocalAttention(A, hq.shape[0], K, T, hq.shape[1], w, simi, add_tanh)
+        h_a, a = op.forward_train(rows, rows_mask, hq, qmask, index, W, b, want_logits=True)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(a)
         ctx.op = op
-        ctx.aux = (album, hmask, qmask)
-        ctx.save_for_backward(hinfo, hq, W, b)
+        ctx.aux = (index, rows_mask, qmask)
+        ctx.save_for_backward(rows, hq, W, b)
         return h_a, a
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_ha, g_a):
         if g_ha is None:
-            return (None,) * 9
-        hinfo, hq, W, b = ctx.saved_tensors
-        album, hmask, qmask = ctx.aux
-        dh, dq = torch.empty_like(hinfo), torch.empty_like(hq)
+            return (None,) * 10
+        rows, hq, W, b = ctx.saved_tensors
+        index, rows_mask, qmask = ctx.aux
+        dr, dq = torch.empty_like(rows), torch.empty_like(hq)
         dW, db = torch.zeros_like(W), torch.zeros_like(b)
-        ctx.op.backward(hinfo, hmask, hq, qmask, album, W, b, _c(g_ha), dh, dq, dW, db)
+        ctx.op.backward(rows, rows_mask, hq, qmask, index, W, b, _c(g_ha), dr, dq, dW, db)
         need = ctx.needs_input_grad
-        return (dh if need[0] else None, dq if need[1] else None, None, dW if need[3] else None, db if need[4] else None,
-                None, None, None, None)
+        return (dr if need[0] else None, dq if need[1] else None, None, dW if need[3] else None, db if need[4] else None,
+                None, None, None, None, None)
 
 
 def shared_focal_attention(hinfo, hq, album, W, b, hmask=None, qmask=None, simi=1, add_tanh=False):
@@ -236,40 +244,7 @@ def shared_focal_attention(hinfo, hq, album, W, b, hmask=None, qmask=None, simi=
     if int(simi) == 4:
         raise NotImplementedError("shared_focal_attention: simiMatrix 4 has no shared-context backward; the per-question "
                                   "focal_attention on gathered rows covers it")
-    return _SharedFocalAttention.apply(hinfo, hq, album, W, b, hmask, qmask, int(simi), bool(add_tanh))
-
-
-class _PooledFocalAttention(torch.autograd.Function):
-    """(pool [P,K,JX,w], hq [NQ,JQ,w], albums int32 [NQ,M] on the device, W [F*w], b [1]; masks u8 | None) ->
-    (h_a [NQ,w], a_logits [NQ,K,M*JX,JQ]): question i over its albums' rows laid end to end, the pool held once
-    (fvta_attn_pool_fwd_train / fvta_attn_pool_bwd; simiMatrix 1-3).  The gradient of pool stays [P,K,JX,w]: the sum over
-    every (question, slot) that refers to the album.  a_logits is not differentiable here.  Each call owns its handle."""
-
-    @staticmethod
-    def forward(ctx, pool, hq, albums, W, b, pool_mask, qmask, simi, add_tanh):
-        P, K, JX, w = pool.shape
-        op = ops.PooledFocalAttention(P, hq.shape[0], albums.shape[1], K, JX, hq.shape[1], w, simi, add_tanh)
-        h_a, a = op.forward_train(pool, pool_mask, hq, qmask, albums, W, b, want_logits=True)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(a)
-        ctx.op = op
-        ctx.aux = (albums, pool_mask, qmask)
-        ctx.save_for_backward(pool, hq, W, b)
-        return h_a, a
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_ha, g_a):
-        if g_ha is None:
-            return (None,) * 9
-        pool, hq, W, b = ctx.saved_tensors
-        albums, pool_mask, qmask = ctx.aux
-        dp, dq = torch.empty_like(pool), torch.empty_like(hq)
-        dW, db = torch.zeros_like(W), torch.zeros_like(b)
-        ctx.op.backward(pool, pool_mask, hq, qmask, albums, W, b, _c(g_ha), dp, dq, dW, db)
-        need = ctx.needs_input_grad
-        return (dp if need[0] else None, dq if need[1] else None, None, dW if need[3] else None, db if need[4] else None,
-                None, None, None, None)
+    return _AlbumFocalAttention.apply(hinfo, hq, album, W, b, hmask, qmask, int(simi), bool(add_tanh), False)
 
 
 def pooled_focal_attention(pool, hq, albums, W, b, pool_mask=None, qmask=None, simi=1, add_tanh=False):
@@ -277,11 +252,11 @@ def pooled_focal_attention(pool, hq, albums, W, b, pool_mask=None, qmask=None, s
     if int(simi) == 4:
         raise NotImplementedError("pooled_focal_attention: simiMatrix 4 has no pooled backward; the per-question "
                                   "focal_attention on gathered rows covers it")
-    return _PooledFocalAttention.apply(_c(pool), _c(hq), albums, _c(W), _c(b), pool_mask, qmask, int(simi), bool(add_tanh))
+    return _AlbumFocalAttention.apply(_c(pool), _c(hq), albums, _c(W), _c(b), pool_mask, qmask, int(simi), bool(add_tanh), True)
 
 
 class _SharedWarpedFocalAttention(torch.autograd.Function):
-    """_SharedFocalAttention under the time warp (fvta_attn_shared_fwd_tw_train / fvta_attn_shared_bwd_tw; simiMatrix 1-3):
+    """_AlbumFocalAttention (pooled = False) under the time warp (fvta_attn_shared_fwd_tw_train / fvta_attn_shared_bwd_tw; simiMatrix 1-3):
     (hinfo [A,K,T,w], hq [NQ,JQ,w], lq [NQ,w], album int32 [NQ] on the device, W [F*w], b [1], WH_W [2w,w] or its first w
     rows, WH_b [w], WC_W [w], WC_b [1]; masks u8 | None; energy [A,T] | None) -> (h_a [NQ,w], a_logits [NQ,K,T,JQ],
     scale [NQ,T]).  a_logits and scale are not differentiable.  `energy` is a cached value of the forward alone: the

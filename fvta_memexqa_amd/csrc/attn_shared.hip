@@ -23,15 +23,19 @@
 //   6. attn_shared_wsum_kernel     one workgroup per (group, k, split of T): part[g] = coef sum_t exp(amax - M) h[t] for
 //                                  the G questions from ONE read of each row
 //   7. attn_shared_merge_kernel    h_a[q] = sum over (k, split) of the partials, in that order
+// Under the time warp attn_shared_tw_scale_kernel goes in front: 8.  ONE driver makes them for every forward entry point:
+// sh_forward, near the end of this file, which says what TRAIN, TW and POOL each change.
 // Row traffic: (4) and (6) read each row of an album once per group of that album: twice per group, never per question.
 // Determinism: no floating-point atomics.  The split of T depends on the descriptor only; a question's numbers do not
 // depend on which group, slot or wave it lands in (every column of the product is its own k-ordered fmaf chain, every
 // question has its own accumulators), so the integer atomics that place the questions in `order` cannot change a bit.
 // The backward DOES sum over an album's questions in `order`: the training plan fills it by ascending question index from a
 // single wave (attn_shared_plan_kernel<true>), a function of `album` alone.
-// The templates of (3), (4) and (6) stand in attn_shared_kernels.h: attn_pool.hip (per-question album lists over one
-// album pool) instantiates them with its own addressing.
+// The templates of (3), (4) and (6) stand in attn_shared_kernels.h with the compile-time word POOL: the pooled call
+// (per-question album lists over one album pool; attn_pool.hip has its entry points and says what POOL means) runs through
+// the same driver, which adds attn_pool_empty_kernel after (4): 8 launches, 9 under the warp.
 #include "attn_shared_kernels.h"
+#include "attn_shared_bwd_kernels.h"  // (ShBwdShape: the training checks cover the backward's grids)
 #include "timewarp_common.h"
 
 namespace fvta {
@@ -114,20 +118,46 @@ __global__ __launch_bounds__(256) void attn_shared_softmax_kernel(ShShape s, ShW
   }
 }
 
-// ---- merge.  grid (NQ, ceil(w / 256)): a channel per thread, the partials in (k, split) order
+// ---- the pooled call's empty slots.  grid NQ M, 256 threads: a workgroup per reference, gone at once unless its slot is
+// empty; then the slot's JX positions get amax = -1e30 for every k (a_logits too): no product, no row read
+// TRAIN: jmax = 0 over the slot's positions too (never read: no reference stands there; defined all the same)
+template <bool TRAIN>
+__global__ __launch_bounds__(256) void attn_pool_empty_kernel(ShShape s, ShWork wk, const int* __restrict__ albums,
+                                                              float* __restrict__ a_logits) {
+  const int ref = blockIdx.x;
+  if (albums[ref] >= 0) return;
+  const int q = ref / s.M, off = (ref % s.M) * s.T;
+  for (int k = 0; k < s.K; ++k) {
+    const size_t at = ((size_t)q * s.K + k) * s.TO + off;
+    for (int e = threadIdx.x; e < s.T; e += 256) wk.amax[at + e] = FVTA_NEG;
+    if constexpr (TRAIN)
+      for (int e = threadIdx.x; e < s.T; e += 256) wk.jmax[at + e] = 0;
+    if (a_logits)
+      for (int64_t e = threadIdx.x; e < (int64_t)s.T * s.JQ; e += 256) a_logits[at * s.JQ + e] = FVTA_NEG;
+  }
+}
+
+// ---- merge.  grid (NQ, ceil(w / 256)): a channel per thread, the question's partials in (k, slot, split) order -- (k, split)
+// with one slot; POOL: M slots, an empty one (qslot < 0) passed over: its rows are zero
+// TRAIN: u[q,k] = (the partials of k, in that order) / r[q,k] beside h_a's own chain, whose order of sums stays what it is
+template <bool TRAIN, bool POOL>
 __global__ __launch_bounds__(256) void attn_shared_merge_kernel(ShShape s, ShWork wk, float* __restrict__ h_a) {
-  const int q = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x;
+  const int q = blockIdx.x, c = blockIdx.y * 256 + threadIdx.x, M = POOL ? s.M : 1;
   if (c >= s.w) return;
-  const int slot = wk.qslot[q], grp = slot / s.G, g = slot % s.G;
   float v = 0.f;
   for (int k = 0; k < s.K; ++k) {
-    float vk = 0.f;  // training: r[k] u[k], beside h_a's own chain (whose order of sums stays what it is)
-    for (int sp = 0; sp < s.S; ++sp) {
-      const float p = wk.part[((((size_t)grp * s.K + k) * s.S + sp) * s.G + g) * s.w + c];
-      v += p;
-      vk += p;
+    float vk = 0.f;
+    for (int m = 0; m < M; ++m) {
+      const int slot = wk.qslot[(size_t)q * M + m];
+      if (POOL && slot < 0) continue;
+      const int grp = slot / s.G, g = slot % s.G;
+      for (int sp = 0; sp < s.S; ++sp) {
+        const float p = wk.part[((((size_t)grp * s.K + k) * s.S + sp) * s.G + g) * s.w + c];
+        v += p;
+        if constexpr (TRAIN) vk += p;
+      }
     }
-    if (wk.u) {  // r = 0 (underflow): u[k] reaches nothing in the backward, every use carries a factor r
+    if constexpr (TRAIN) {  // r = 0 (underflow): u[k] reaches nothing in the backward, every use carries a factor r
       const float r = wk.r[(size_t)q * s.K + k];
       wk.u[((size_t)q * s.K + k) * s.w + c] = r > 0.f ? vk / r : 0.f;
     }
@@ -170,9 +200,11 @@ __global__ __launch_bounds__(256) void attn_shared_energy_kernel(ShShape s, cons
   if (lane == 0) energy[pos] = acc;
 }
 
-// scale[q,t].  grid (NQ, ceil(T / 256)), 256 threads; every wave takes the two dot products itself (w floats each)
-// TRAIN: tanh(z) beside it, for the backward
-template <bool TRAIN>
+// scale[q,t] over the question's WHOLE TO positions.  grid (NQ, ceil(TO / 256)), 256 threads; every wave takes the two dot
+// products itself (w floats each).  TRAIN: tanh(z) beside it, for the backward
+// POOL: t = m JX + j; the energy is taken per slot -- the album index clamped as the plan clamps it, an empty slot's e = 0
+// (JX zero rows) -- and the count is that of the GLOBAL position t.  With one slot: the same bits
+template <bool TRAIN, bool POOL>
 __global__ __launch_bounds__(256) void attn_shared_tw_scale_kernel(ShShape s, int warp_type, int win, const float* __restrict__ energy,
                                                                    const float* __restrict__ lq, const int* __restrict__ album,
                                                                    const float* __restrict__ WHb, const float* __restrict__ WC,
@@ -187,57 +219,98 @@ __global__ __launch_bounds__(256) void attn_shared_tw_scale_kernel(ShShape s, in
   }
   s0 = wave_sum(s0) + WCb[0];
   sq = wave_sum(sq);
-  if (t >= s.T) return;
-  const int a = sh_album(album, q, s.A);
-  const float tz = tanhf(energy[(size_t)a * s.T + t] + (float)s.K * (s0 + sq));
-  const float sc = tz * tw_count(t, s.T, warp_type, win);
-  if constexpr (TRAIN) tz_out[(size_t)q * s.T + t] = tz;
-  scale[(size_t)q * s.T + t] = sc;
-  if (scale_out) scale_out[(size_t)q * s.T + t] = sc;
+  if (t >= s.TO) return;
+  const int m = POOL ? t / s.T : 0, a = sh_ref_album<POOL>(album, q * s.M + m, s.A);
+  const float e = POOL && a < 0 ? 0.f : energy[(size_t)a * s.T + (t - m * s.T)];
+  const float tz = tanhf(e + (float)s.K * (s0 + sq));
+  const float sc = tz * tw_count(t, s.TO, warp_type, win);
+  if constexpr (TRAIN) tz_out[(size_t)q * s.TO + t] = tz;
+  scale[(size_t)q * s.TO + t] = sc;
+  if (scale_out) scale_out[(size_t)q * s.TO + t] = sc;
 }
 
-// 0: fine, else the status with the message set
-int fvta_attn_shared_check(const fvta_attn_shared_desc* d, const char* who) {
-  FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  FVTA_CHECK_ARG(d->A > 0 && d->NQ > 0 && d->K > 0 && d->T > 0 && d->JQ > 0 && d->w > 0, "%s: bad A/NQ/K/T/JQ/w (%d,%d,%d,%d,%d,%d)",
-                 who, d->A, d->NQ, d->K, d->T, d->JQ, d->w);
+// ---- the checks.  How a refusal prints the descriptor: the family's own letters
+static const char* sh_describe(const ShShape& s, bool pool, char (&buf)[128]) {
+  if (pool)
+    snprintf(buf, sizeof buf, "P=%d NQ=%d M=%d K=%d JX=%d JQ=%d w=%d", s.A, s.NQ, s.M, s.K, s.T, s.JQ, s.w);
+  else
+    snprintf(buf, sizeof buf, "A=%d NQ=%d K=%d T=%d JQ=%d w=%d", s.A, s.NQ, s.K, s.T, s.JQ, s.w);
+  return buf;
+}
+
+static int sh_refuse_shape(const ShShape& s, bool pool, const char* who, const char* why) {
+  char buf[128];
+  fvta_set_error("%s: unsupported shape (%s): %s", who, sh_describe(s, pool, buf), why);
+  return FVTA_ERR_UNSUPPORTED;
+}
+
+// the backward's grids: the row pass's and the question pass's
+static int sh_check_bwd_grids(const ShShape& s, bool pool, const char* who) {
+  const ShBwdShape b = shb_shape(s);
+  if ((int64_t)s.A * s.K * b.nch > 0x7fffffff || (int64_t)s.ngmax * b.TS * b.nsl > 0x7fffffff)
+    return sh_refuse_shape(s, pool, who, "too many workgroups");
+  return FVTA_OK;
+}
+
+int sh_check(ShShape& s, bool pool, const char* who, ShLevel level) {
+  if (pool)
+    FVTA_CHECK_ARG(s.A > 0 && s.NQ > 0 && s.M > 0 && s.K > 0 && s.T > 0 && s.JQ > 0 && s.w > 0,
+                   "%s: bad P/NQ/M/K/JX/JQ/w (%d,%d,%d,%d,%d,%d,%d)", who, s.A, s.NQ, s.M, s.K, s.T, s.JQ, s.w);
+  else
+    FVTA_CHECK_ARG(s.A > 0 && s.NQ > 0 && s.K > 0 && s.T > 0 && s.JQ > 0 && s.w > 0, "%s: bad A/NQ/K/T/JQ/w (%d,%d,%d,%d,%d,%d)",
+                   who, s.A, s.NQ, s.K, s.T, s.JQ, s.w);
   const char* why = nullptr;
-  const int w = d->w;
-  if (d->simi < 1 || d->simi > 4) {
-    fvta_set_error("%s: similarity matrix not implemented (simiMatrix=%d)", who, d->simi);
+  const int w = s.w;
+  if (s.simi < 1 || s.simi > 4) {
+    fvta_set_error("%s: similarity matrix not implemented (simiMatrix=%d)", who, s.simi);
     return FVTA_ERR_UNSUPPORTED;
   }
   if (!(w == 64 || w == 128 || w == 256 || w == 512 || w == 1024 || w == 2048))
     why = "w must be one of 64,128,256,512,1024,2048";
-  else if (d->JQ > 64)
+  else if (s.JQ > 64)
     why = "JQ must be 1..64";
-  else if (d->K > 64)
+  else if (s.K > 64)
     why = "K must be 1..64";
-  else if (d->A > (1 << 28) || d->NQ > (1 << 28))
-    why = "A and NQ must not exceed 2^28";
+  else if (s.A > (1 << 28) || (int64_t)s.NQ * s.M > (1 << 28))
+    why = pool ? "P and NQ*M must not exceed 2^28" : "A and NQ must not exceed 2^28";
+  else if ((int64_t)s.M * s.T > 0x7fffffff)  // (one slot: T is an int)
+    why = "M*JX must fit a 32-bit int";
   if (!why) {
-    const ShShape s = sh_shape(d);
-    if ((int64_t)s.ngmax * d->K * s.ntile > 0x7fffffff || (int64_t)s.ngmax * d->K * s.S > 0x7fffffff) why = "too many workgroups";
+    sh_derive(s);
+    if ((int64_t)s.ngmax * s.K * s.ntile > 0x7fffffff || (int64_t)s.ngmax * s.K * s.S > 0x7fffffff) why = "too many workgroups";
   }
-  if (why) {
-    fvta_set_error("%s: unsupported shape (A=%d NQ=%d K=%d T=%d JQ=%d w=%d): %s", who, d->A, d->NQ, d->K, d->T, d->JQ, w, why);
+  if (why) return sh_refuse_shape(s, pool, who, why);
+  if (level >= SH_TRAIN && s.simi == 4) {
+    fvta_set_error("%s: simiMatrix 4 has no %s backward (simiMatrix 1-3); the per-question route "
+                   "(fvta_attn_fwd / fvta_attn_bwd on the gathered rows) covers it", who, pool ? "pooled" : "shared-context");
     return FVTA_ERR_UNSUPPORTED;
   }
-  return FVTA_OK;
+  return level >= SH_BWD ? sh_check_bwd_grids(s, pool, who) : FVTA_OK;
 }
 
-}  // namespace fvta
-using namespace fvta;
-
-extern "C" size_t fvta_attn_shared_workspace_bytes(const fvta_attn_shared_desc* d) {
-  if (fvta_attn_shared_check(d, "attn_shared_workspace_bytes") != FVTA_OK) return 0;
-  return ShWork(sh_shape(d), nullptr).bytes;
+int sh_check_tw(ShShape& s, bool pool, int warp_type, float window_t, const char* who, ShLevel level) {
+  if (int e = sh_check(s, pool, who, level >= SH_TRAIN ? SH_TRAIN : SH_FWD)) return e;
+  if (warp_type < 1 || warp_type > 5) {
+    fvta_set_error("%s: time warping type not implemented (warp_type=%d)", who, warp_type);  // model_v2.py:341
+    return FVTA_ERR_INVALID_ARG;
+  }
+  FVTA_CHECK_ARG(window_t >= 0.f && window_t <= 1e9f, "%s: bad window_t (%g)", who, (double)window_t);
+  if (s.TO > 65535 * 256) {  // the scale kernel's grid
+    if (pool)
+      fvta_set_error("%s: unsupported shape (M=%d JX=%d): M*JX must not exceed 65535 * 256 under the time warp", who, s.M, s.T);
+    else
+      fvta_set_error("%s: unsupported shape (T=%d): T must not exceed 65535 * 256 under the time warp", who, s.T);
+    return FVTA_ERR_UNSUPPORTED;
+  }
+  if (pool && ((int64_t)s.A * s.T + 3) / 4 > 0x7fffffff) {  // the energy kernel's grid
+    fvta_set_error("%s: unsupported shape (P=%d JX=%d): too many workgroups", who, s.A, s.T);
+    return FVTA_ERR_UNSUPPORTED;
+  }
+  return level >= SH_BWD ? sh_check_bwd_grids(s, pool, who) : FVTA_OK;
 }
 
-extern "C" int fvta_attn_shared_plan(const fvta_attn_shared_desc* d, int32_t out[4]) {
-  if (int e = fvta_attn_shared_check(d, "attn_shared_plan")) return e;
-  FVTA_CHECK_ARG(out != nullptr, "attn_shared_plan: null pointer");
-  const ShShape s = sh_shape(d);
+int sh_plan(const ShShape& s, const char* who, int32_t out[4]) {
+  FVTA_CHECK_ARG(out != nullptr, "%s: null pointer", who);
   out[0] = s.G;
   out[1] = SH_R;
   out[2] = s.S;
@@ -245,126 +318,136 @@ extern "C" int fvta_attn_shared_plan(const fvta_attn_shared_desc* d, int32_t out
   return FVTA_OK;
 }
 
-// the seven launches; TRAIN: the ordered plan and the arg-max, wk carved from (saved, workspace); TW: under the time warp,
-// tw_scale [NQ,T] written by an earlier launch on the same stream
-template <bool TRAIN, bool TW = false>
-static int sh_forward(ShShape s, const ShWork& wk, const float* hinfo, const uint8_t* hmask, const float* hq, const uint8_t* qmask,
-                      const int32_t* album, const float* W, const float* b, float* h_a, float* a_logits, hipStream_t st,
-                      const float* tw_scale = nullptr, const char* who = nullptr, float* tw_lin = nullptr, float* tw_r2 = nullptr) {
-  s.use_mask = (hmask && qmask) ? 1 : 0;  // model_v2.py:233: the mask applies only when both are given
-  // attn_fwd.hip's kernel, declared in attn_common.h (feat_order 0 = model_v2.py's)
-  hipLaunchKernelGGL(attn_vecs_kernel, dim3((s.w + 255) / 256), dim3(256), 0, st, W, s.w, s.simi, 0, wk.vecs);
-  hipLaunchKernelGGL(attn_shared_prep_q_kernel, dim3(s.NQ, s.JP / 4), dim3(256), 0, st, s, wk, hq, b);
-  hipLaunchKernelGGL(attn_shared_plan_kernel<TRAIN>, dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)album);
-  const dim3 lgrid((unsigned)((int64_t)s.ngmax * s.K * s.ntile));
-  const ShTwArgs tw{tw_scale, tw_lin, tw_r2};
-  if (s.JP == 32)
-    hipLaunchKernelGGL((attn_shared_logits_kernel<1, TRAIN, TW>), lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits,
-                       tw);
-  else
-    hipLaunchKernelGGL((attn_shared_logits_kernel<2, TRAIN, TW>), lgrid, dim3(SH_NT), 0, st, s, wk, hinfo, hmask, qmask, a_logits,
-                       tw);
-  hipLaunchKernelGGL(attn_shared_softmax_kernel, dim3(s.NQ), dim3(256), 0, st, s, wk);
-  if (s.G == 8)
-    sh_launch_wsum<8, TW>(s, wk, hinfo, tw_scale, st);
-  else
-    sh_launch_wsum<4, TW>(s, wk, hinfo, tw_scale, st);
-  hipLaunchKernelGGL(attn_shared_merge_kernel, dim3(s.NQ, (s.w + 255) / 256), dim3(256), 0, st, s, wk, h_a);
-  FVTA_CHECK_LAUNCH(who ? who : (TRAIN ? "attn_shared_fwd_train" : "attn_shared_fwd"));
+int sh_energy(const ShShape& s, const char* who, const float* rows, const float* WH_W, const float* WC_W, float* energy,
+              void* workspace, fvta_stream_t stream) {
+  FVTA_CHECK_ARG(rows && WH_W && WC_W && energy && workspace, "%s: null pointer", who);
+  const ShTwWork tw(s, workspace);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(attn_shared_tw_vec_kernel, dim3((s.w + 3) / 4), dim3(256), 0, st, s.w, WH_W, WC_W, tw.v);
+  hipLaunchKernelGGL(attn_shared_energy_kernel, dim3((unsigned)(((int64_t)s.A * s.T + 3) / 4)), dim3(256), 0, st, s, rows, tw.v,
+                     energy);
+  FVTA_CHECK_LAUNCH(who);
   return FVTA_OK;
+}
+
+// ---- the forward driver.  The launches of the header, in its order, for every entry point of both families:
+//   TW    the scale kernel in front (into the workspace, TRAIN: into `saved`, tanh(z) beside it) and the TW logits / weighted sum
+//   TRAIN the ordered plan, the arg-max, L / r / u: wk carved from (saved, workspace) -- its share of the workspace is no
+//         larger than the inference call's
+//   POOL  the references' addressing in plan / logits / weighted sum / merge, and the empty slots' launch after the logits
+// and nothing else depends on any of the three
+template <bool TRAIN, bool TW, bool POOL>
+static int sh_forward_as(ShShape s, const char* who, const ShFwdCall& c, const ShWarpCall* warp) {
+  static_assert(!(TW && TRAIN && POOL), "training over the pool is not under the time warp");
+  hipStream_t st = (hipStream_t)c.stream;
+  const ShWork wk = TRAIN ? ShWork(s, c.saved, c.workspace) : ShWork(s, c.workspace);
+  ShTwArgs tw{nullptr, nullptr, nullptr};
+  if constexpr (TW) {
+    float *scale, *tz = nullptr;
+    if constexpr (TRAIN) {
+      const ShTwSaved ts(s, wk, c.saved);
+      scale = ts.scale, tz = ts.tz, tw.lin = ts.lin, tw.r2 = ts.r2;
+    } else {
+      scale = ShTwWork(s, c.workspace).scale;
+    }
+    tw.scale = scale;
+    hipLaunchKernelGGL((attn_shared_tw_scale_kernel<TRAIN, POOL>), dim3(s.NQ, (s.TO + 255) / 256), dim3(256), 0, st, s, warp->warp_type,
+                       (int)ceilf(warp->window_t), warp->energy, warp->lq, (const int*)c.index, warp->WH_b, warp->WC_W, warp->WC_b,
+                       scale, warp->scale_out, tz);
+  }
+  s.use_mask = (c.rows_mask && c.qmask) ? 1 : 0;  // model_v2.py:233: the mask applies only when both are given
+  // attn_fwd.hip's kernel, declared in attn_common.h (feat_order 0 = model_v2.py's)
+  hipLaunchKernelGGL(attn_vecs_kernel, dim3((s.w + 255) / 256), dim3(256), 0, st, c.W, s.w, s.simi, 0, wk.vecs);
+  hipLaunchKernelGGL(attn_shared_prep_q_kernel, dim3(s.NQ, s.JP / 4), dim3(256), 0, st, s, wk, c.hq, c.b);
+  hipLaunchKernelGGL((attn_shared_plan_kernel<TRAIN, POOL>), dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)c.index);
+  const dim3 lgrid((unsigned)((int64_t)s.ngmax * s.K * s.ntile));
+  if (s.JP == 32)
+    hipLaunchKernelGGL((attn_shared_logits_kernel<1, TRAIN, TW, POOL>), lgrid, dim3(SH_NT), 0, st, s, wk, c.rows, c.rows_mask, c.qmask,
+                       c.a_logits, tw);
+  else
+    hipLaunchKernelGGL((attn_shared_logits_kernel<2, TRAIN, TW, POOL>), lgrid, dim3(SH_NT), 0, st, s, wk, c.rows, c.rows_mask, c.qmask,
+                       c.a_logits, tw);
+  if constexpr (POOL)
+    hipLaunchKernelGGL(attn_pool_empty_kernel<TRAIN>, dim3(s.NR), dim3(256), 0, st, s, wk, (const int*)c.index, c.a_logits);
+  ShShape sq = s;  // the softmaxes run per question over all of its positions
+  sq.T = s.TO;
+  hipLaunchKernelGGL(attn_shared_softmax_kernel, dim3(s.NQ), dim3(256), 0, st, sq, wk);
+  if (s.G == 8)
+    sh_launch_wsum<8, TW, POOL>(s, wk, c.rows, tw.scale, st);
+  else
+    sh_launch_wsum<4, TW, POOL>(s, wk, c.rows, tw.scale, st);
+  hipLaunchKernelGGL((attn_shared_merge_kernel<TRAIN, POOL>), dim3(s.NQ, (s.w + 255) / 256), dim3(256), 0, st, s, wk, c.h_a);
+  FVTA_CHECK_LAUNCH(who);
+  return FVTA_OK;
+}
+
+// <TRAIN, TW, POOL> per entry point: TRAIN = a `saved` to fill, TW = the warp's arguments
+//   fvta_attn_shared_fwd <0,0,0>   _fwd_train <1,0,0>   _fwd_tw <0,1,0>   _fwd_tw_train <1,1,0>
+//   fvta_attn_pool_fwd   <0,0,1>   _fwd_train <1,0,1>   _fwd_tw <0,1,1>   (no <1,1,1>: FVTA_ERR_UNSUPPORTED)
+int sh_forward(const ShShape& s, bool pool, const char* who, const ShFwdCall& c, const ShWarpCall* warp) {
+  const bool train = c.saved != nullptr;
+  if (!pool) {
+    if (warp) return train ? sh_forward_as<true, true, false>(s, who, c, warp) : sh_forward_as<false, true, false>(s, who, c, warp);
+    return train ? sh_forward_as<true, false, false>(s, who, c, warp) : sh_forward_as<false, false, false>(s, who, c, warp);
+  }
+  if (!warp) return train ? sh_forward_as<true, false, true>(s, who, c, warp) : sh_forward_as<false, false, true>(s, who, c, warp);
+  if (!train) return sh_forward_as<false, true, true>(s, who, c, warp);
+  fvta_set_error("%s: training over the pool is not under the time warp", who);
+  return FVTA_ERR_UNSUPPORTED;
+}
+
+}  // namespace fvta
+using namespace fvta;
+
+extern "C" size_t fvta_attn_shared_workspace_bytes(const fvta_attn_shared_desc* d) {
+  ShShape s;
+  return sh_open(d, "attn_shared_workspace_bytes", s) == FVTA_OK ? ShWork(s, nullptr).bytes : 0;
+}
+
+extern "C" int fvta_attn_shared_plan(const fvta_attn_shared_desc* d, int32_t out[4]) {
+  ShShape s;
+  if (int e = sh_open(d, "attn_shared_plan", s)) return e;
+  return sh_plan(s, "attn_shared_plan", out);
 }
 
 extern "C" int fvta_attn_shared_fwd(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
                                     const uint8_t* qmask, const int32_t* album, const float* W, const float* b, float* h_a,
                                     float* a_logits, void* workspace, fvta_stream_t stream_) {
-  if (int e = fvta_attn_shared_check(d, "attn_shared_fwd")) return e;
+  ShShape s;
+  if (int e = sh_open(d, "attn_shared_fwd", s)) return e;
   FVTA_CHECK_ARG(hinfo && hq && album && h_a && workspace, "attn_shared_fwd: null pointer");
   FVTA_CHECK_ARG(d->simi == 4 || W, "attn_shared_fwd: simiMatrix %d needs att_logits/W", d->simi);
-  const ShShape s = sh_shape(d);
-  return sh_forward<false>(s, ShWork(s, workspace), hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, (hipStream_t)stream_);
+  return sh_forward(s, false, "attn_shared_fwd", {hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, nullptr, workspace, stream_});
 }
 
 // ---- training.  The same kernels on the same numbers (h_a and a_logits are fvta_attn_shared_fwd's bits: the placement of
 // a question changes none, see the header), with what the backward (attn_shared_bwd.hip) reads left in `saved`.
-int fvta::fvta_attn_shared_check_train(const fvta_attn_shared_desc* d, const char* who) {
-  if (int e = fvta_attn_shared_check(d, who)) return e;
-  if (d->simi == 4) {
-    fvta_set_error("%s: simiMatrix 4 has no shared-context backward (simiMatrix 1-3); the per-question route "
-                   "(fvta_attn_fwd / fvta_attn_bwd on the gathered rows) covers it", who);
-    return FVTA_ERR_UNSUPPORTED;
-  }
-  return FVTA_OK;
-}
-
 extern "C" size_t fvta_attn_shared_saved_bytes(const fvta_attn_shared_desc* d) {
-  if (fvta_attn_shared_check_train(d, "attn_shared_saved_bytes") != FVTA_OK) return 0;
-  return ShWork(sh_shape(d), nullptr, nullptr).saved_bytes;
+  ShShape s;
+  return sh_open(d, "attn_shared_saved_bytes", s, SH_TRAIN) == FVTA_OK ? ShWork(s, nullptr, nullptr).saved_bytes : 0;
 }
 
 extern "C" int fvta_attn_shared_fwd_train(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask,
                                           const float* hq, const uint8_t* qmask, const int32_t* album, const float* W,
                                           const float* b, float* h_a, float* a_logits, void* saved, void* workspace,
                                           fvta_stream_t stream_) {
-  if (int e = fvta_attn_shared_check_train(d, "attn_shared_fwd_train")) return e;
+  ShShape s;
+  if (int e = sh_open(d, "attn_shared_fwd_train", s, SH_TRAIN)) return e;
   FVTA_CHECK_ARG(hinfo && hq && album && W && h_a && saved && workspace, "attn_shared_fwd_train: null pointer");
-  const ShShape s = sh_shape(d);
-  return sh_forward<true>(s, ShWork(s, saved, workspace), hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits,
-                          (hipStream_t)stream_);
+  return sh_forward(s, false, "attn_shared_fwd_train", {hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, saved, workspace, stream_});
 }
 
-// ---- under the time warp.  The workspace: fvta_attn_shared_fwd's, then scale [NQ,T], then v [w] (the energy call's)
-namespace fvta {
-struct ShTwWork {
-  ShWork wk;
-  float *scale, *v;
-  size_t bytes;
-  ShTwWork(const ShShape& s, void* p) : wk(s, p) {
-    FvtaCarver c(p);
-    c.off = wk.bytes;
-    scale = c.take<float>((size_t)s.NQ * s.T);
-    v = c.take<float>((size_t)s.w);
-    bytes = c.off;
-  }
-};
-
-int fvta_attn_shared_check_warp(int warp_type, float window_t, const char* who) {
-  if (warp_type < 1 || warp_type > 5) {
-    fvta_set_error("%s: time warping type not implemented (warp_type=%d)", who, warp_type);  // model_v2.py:341
-    return FVTA_ERR_INVALID_ARG;
-  }
-  FVTA_CHECK_ARG(window_t >= 0.f && window_t <= 1e9f, "%s: bad window_t (%g)", who, (double)window_t);
-  return FVTA_OK;
-}
-
-int fvta_attn_shared_check_tw(const fvta_attn_shared_tw_desc* d, const char* who, bool train) {
-  FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
-  if (int e = train ? fvta_attn_shared_check_train(&d->shape, who) : fvta_attn_shared_check(&d->shape, who)) return e;
-  if (int e = fvta_attn_shared_check_warp(d->warp_type, d->window_t, who)) return e;
-  if (d->shape.T > 65535 * 256) {
-    fvta_set_error("%s: unsupported shape (T=%d): T must not exceed 65535 * 256 under the time warp", who, d->shape.T);
-    return FVTA_ERR_UNSUPPORTED;
-  }
-  return FVTA_OK;
-}
-}  // namespace fvta
-
+// ---- under the time warp.  The workspace: ShTwWork (attn_shared_common.h)
 extern "C" size_t fvta_attn_shared_tw_workspace_bytes(const fvta_attn_shared_tw_desc* d) {
-  if (fvta_attn_shared_check_tw(d, "attn_shared_tw_workspace_bytes") != FVTA_OK) return 0;
-  return ShTwWork(sh_shape(&d->shape), nullptr).bytes;
+  ShShape s;
+  return sh_open_tw(d, "attn_shared_tw_workspace_bytes", s) == FVTA_OK ? ShTwWork(s, nullptr).bytes : 0;
 }
 
 extern "C" int fvta_attn_shared_energy(const fvta_attn_shared_tw_desc* d, const float* hinfo, const float* WH_W, const float* WC_W,
                                        float* energy, void* workspace, fvta_stream_t stream_) {
-  if (int e = fvta_attn_shared_check_tw(d, "attn_shared_energy")) return e;
-  FVTA_CHECK_ARG(hinfo && WH_W && WC_W && energy && workspace, "attn_shared_energy: null pointer");
-  const ShShape s = sh_shape(&d->shape);
-  const ShTwWork tw(s, workspace);
-  hipStream_t st = (hipStream_t)stream_;
-  hipLaunchKernelGGL(attn_shared_tw_vec_kernel, dim3((s.w + 3) / 4), dim3(256), 0, st, s.w, WH_W, WC_W, tw.v);
-  hipLaunchKernelGGL(attn_shared_energy_kernel, dim3((unsigned)(((int64_t)s.A * s.T + 3) / 4)), dim3(256), 0, st, s, hinfo, tw.v,
-                     energy);
-  FVTA_CHECK_LAUNCH("attn_shared_energy");
-  return FVTA_OK;
+  ShShape s;
+  if (int e = sh_open_tw(d, "attn_shared_energy", s)) return e;
+  return sh_energy(s, "attn_shared_energy", hinfo, WH_W, WC_W, energy, workspace, stream_);
 }
 
 extern "C" int fvta_attn_shared_fwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinfo, const uint8_t* hmask,
@@ -372,23 +455,21 @@ extern "C" int fvta_attn_shared_fwd_tw(const fvta_attn_shared_tw_desc* d, const 
                                        const int32_t* album, const float* W, const float* b, const float* WH_b, const float* WC_W,
                                        const float* WC_b, float* h_a, float* a_logits, float* scale_out, void* workspace,
                                        fvta_stream_t stream_) {
-  if (int e = fvta_attn_shared_check_tw(d, "attn_shared_fwd_tw")) return e;
+  ShShape s;
+  if (int e = sh_open_tw(d, "attn_shared_fwd_tw", s)) return e;
   FVTA_CHECK_ARG(hinfo && energy && hq && lq && album && WH_b && WC_W && WC_b && h_a && workspace, "attn_shared_fwd_tw: null pointer");
   FVTA_CHECK_ARG(d->shape.simi == 4 || W, "attn_shared_fwd_tw: simiMatrix %d needs att_logits/W", d->shape.simi);
-  const ShShape s = sh_shape(&d->shape);
-  const ShTwWork tw(s, workspace);
-  hipStream_t st = (hipStream_t)stream_;
-  hipLaunchKernelGGL(attn_shared_tw_scale_kernel<false>, dim3(s.NQ, (s.T + 255) / 256), dim3(256), 0, st, s, d->warp_type,
-                     (int)ceilf(d->window_t), energy, lq, (const int*)album, WH_b, WC_W, WC_b, tw.scale, scale_out, (float*)nullptr);
-  return sh_forward<false, true>(s, tw.wk, hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, st, tw.scale, "attn_shared_fwd_tw");
+  const ShWarpCall warp{d->warp_type, d->window_t, energy, lq, WH_b, WC_W, WC_b, scale_out};
+  return sh_forward(s, false, "attn_shared_fwd_tw", {hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, nullptr, workspace, stream_},
+                    &warp);
 }
 
 // ---- training under the time warp.  The kernels of fvta_attn_shared_fwd_tw on the same numbers -- h_a, a_logits and
 // scale_out are its bits -- with the ordered plan, the arg-max, and in `saved` what attn_shared_bwd.hip's
 // fvta_attn_shared_bwd_tw reads: fvta_attn_shared_fwd_train's pieces, then scale, tanh(z), lin at the arg-max and r2.
 extern "C" size_t fvta_attn_shared_tw_saved_bytes(const fvta_attn_shared_tw_desc* d) {
-  if (fvta_attn_shared_check_tw(d, "attn_shared_tw_saved_bytes", true) != FVTA_OK) return 0;
-  const ShShape s = sh_shape(&d->shape);
+  ShShape s;
+  if (sh_open_tw(d, "attn_shared_tw_saved_bytes", s, SH_TRAIN) != FVTA_OK) return 0;
   return ShTwSaved(s, ShWork(s, nullptr, nullptr), nullptr).bytes;
 }
 
@@ -397,15 +478,11 @@ extern "C" int fvta_attn_shared_fwd_tw_train(const fvta_attn_shared_tw_desc* d, 
                                              const int32_t* album, const float* W, const float* b, const float* WH_b,
                                              const float* WC_W, const float* WC_b, float* h_a, float* a_logits, float* scale_out,
                                              void* saved, void* workspace, fvta_stream_t stream_) {
-  if (int e = fvta_attn_shared_check_tw(d, "attn_shared_fwd_tw_train", true)) return e;
+  ShShape s;
+  if (int e = sh_open_tw(d, "attn_shared_fwd_tw_train", s, SH_TRAIN)) return e;
   FVTA_CHECK_ARG(hinfo && energy && hq && lq && album && W && WH_b && WC_W && WC_b && h_a && saved && workspace,
                  "attn_shared_fwd_tw_train: null pointer");
-  const ShShape s = sh_shape(&d->shape);
-  const ShWork wk(s, saved, workspace);  // (its share of the workspace is no larger than the inference call's)
-  const ShTwSaved ts(s, wk, saved);
-  hipStream_t st = (hipStream_t)stream_;
-  hipLaunchKernelGGL(attn_shared_tw_scale_kernel<true>, dim3(s.NQ, (s.T + 255) / 256), dim3(256), 0, st, s, d->warp_type,
-                     (int)ceilf(d->window_t), energy, lq, (const int*)album, WH_b, WC_W, WC_b, ts.scale, scale_out, ts.tz);
-  return sh_forward<true, true>(s, wk, hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, st, ts.scale, "attn_shared_fwd_tw_train",
-                                ts.lin, ts.r2);
+  const ShWarpCall warp{d->warp_type, d->window_t, energy, lq, WH_b, WC_W, WC_b, scale_out};
+  return sh_forward(s, false, "attn_shared_fwd_tw_train", {hinfo, hmask, hq, qmask, album, W, b, h_a, a_logits, saved, workspace, stream_},
+                    &warp);
 }

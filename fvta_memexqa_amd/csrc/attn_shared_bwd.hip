@@ -29,7 +29,8 @@
 // `order`, which the training plan fills by ascending question index (attn_shared.hip: attn_shared_plan_kernel<true>).
 // Kernels 1, 4 and 5 are a few lines each around attn_bwd_shared.h's prep body, fold body and parameter pieces -- the one
 // copy attn_bwd.hip runs too; the row and question passes (2, 3), the backward's shape and its workspace stand in
-// attn_shared_bwd_kernels.h: attn_pool.hip (training over per-question album lists) instantiates them with its own addressing.
+// attn_shared_bwd_kernels.h, with the compile-time word POOL for training over per-question album lists (attn_pool.hip).
+// ONE driver makes the launches for the three backward entry points: shb_backward, near the end of this file.
 // Under the time warp (fvta_attn_shared_bwd_tw, the gradient of fvta_attn_shared_fwd_tw_train): the TW instantiations of
 // (2) and (3) and six small kernels of the warp's own backward, at the end of this file.
 #include "attn_shared_bwd_kernels.h"
@@ -92,19 +93,6 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_params_kernel(ShShape s, 
     v[VEC_R2] = attn_bwd_sum_rows(wk.rowp, slots, 2, 1, part, w, c);
   }
   attn_bwd_combine_dW(v, s.simi, 0, w, c, dW);
-}
-
-// 0: fine, else the status with the message set
-static int shb_check(const fvta_attn_shared_desc* d, const char* who) {
-  if (int e = fvta_attn_shared_check_train(d, who)) return e;
-  const ShShape s = sh_shape(d);
-  const ShBwdShape b = shb_shape(s);
-  if ((int64_t)s.A * s.K * b.nch > 0x7fffffff || (int64_t)s.ngmax * b.TS * b.nsl > 0x7fffffff) {
-    fvta_set_error("%s: unsupported shape (A=%d NQ=%d K=%d T=%d JQ=%d w=%d): too many workgroups", who, d->A, d->NQ, d->K, d->T,
-                   d->JQ, d->w);
-    return FVTA_ERR_UNSUPPORTED;
-  }
-  return FVTA_OK;
 }
 
 // ================= under the time warp (fvta_attn_shared_bwd_tw): the gradient of fvta_attn_shared_fwd_tw_train ==========
@@ -306,49 +294,14 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_tw_params_kernel(ShShape 
   }
 }
 
-static int shb_check_tw(const fvta_attn_shared_tw_desc* d, const char* who) {
-  if (int e = fvta_attn_shared_check_tw(d, who, true)) return e;
-  return shb_check(&d->shape, who);
-}
-
-}  // namespace fvta
-using namespace fvta;
-
-extern "C" size_t fvta_attn_shared_bwd_workspace_bytes(const fvta_attn_shared_desc* d) {
-  if (shb_check(d, "attn_shared_bwd_workspace_bytes") != FVTA_OK) return 0;
-  const ShShape s = sh_shape(d);
-  return ShBwdWork(s, shb_shape(s), nullptr).bytes;
-}
-
-extern "C" int fvta_attn_shared_bwd_plan(const fvta_attn_shared_desc* d, int32_t out[4]) {
-  if (int e = shb_check(d, "attn_shared_bwd_plan")) return e;
-  FVTA_CHECK_ARG(out != nullptr, "attn_shared_bwd_plan: null pointer");
-  const ShBwdShape b = shb_shape(sh_shape(d));
-  out[0] = b.TR;
-  out[1] = b.TS;
-  out[2] = SHB_CS;
-  out[3] = b.tpw;
-  return FVTA_OK;
-}
-
-extern "C" int fvta_attn_shared_bwd(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
-                                    const uint8_t* qmask, const int32_t* album, const float* W, const float* b,
-                                    const float* d_h_a, const void* saved, float* d_hinfo, float* d_hq, float* dW, float* db,
-                                    void* workspace, fvta_stream_t stream_) {
-  if (int e = shb_check(d, "attn_shared_bwd")) return e;
-  FVTA_CHECK_ARG(hinfo && hq && album && d_h_a && saved && d_hinfo && d_hq && dW && db && workspace,
-                 "attn_shared_bwd: null pointer");
-  hipStream_t st = (hipStream_t)stream_;
-  ShShape s = sh_shape(d);
-  s.use_mask = (hmask && qmask) ? 1 : 0;
-  const ShBwdShape bs = shb_shape(s);
-  const ShWork sv(s, const_cast<void*>(saved), nullptr);
-  const ShBwdWork wk(s, bs, workspace);
-  hipLaunchKernelGGL(attn_shared_bwd_prep_kernel, dim3(s.NQ), dim3(s.K > 4 ? 1024 : 256), 0, st, s, sv, wk, d_h_a);
+// ---- the row pass's launch: w -> <TPR, CPT, RPT>, the one table
+template <bool TW, bool POOL>
+static void shb_launch_rows(const ShShape& s, const ShBwdShape& bs, const ShWork& sv, const ShBwdWork& wk, const float* rows,
+                            const float* d_h_a, float* d_rows, const ShBwdTwArgs& ta, hipStream_t st) {
   const dim3 rgrid((unsigned)((int64_t)s.A * s.K * bs.nch));
 #define FVTA_SHB_ROWS(TPR, CPT, RPT) \
-  hipLaunchKernelGGL((attn_shared_bwd_rows_kernel<TPR, CPT, RPT, false>), rgrid, dim3(256), 0, st, s, bs, sv, wk, hinfo, d_h_a, \
-                     d_hinfo, ShBwdTwArgs{})
+  hipLaunchKernelGGL((attn_shared_bwd_rows_kernel<TPR, CPT, RPT, TW, POOL>), rgrid, dim3(256), 0, st, s, bs, sv, wk, rows, d_h_a, \
+                     d_rows, ta)
   switch (s.w) {
     case 64: FVTA_SHB_ROWS(16, 1, 8); break;
     case 128: FVTA_SHB_ROWS(32, 1, 8); break;
@@ -358,20 +311,125 @@ extern "C" int fvta_attn_shared_bwd(const fvta_attn_shared_desc* d, const float*
     default: FVTA_SHB_ROWS(256, 2, 4); break;
   }
 #undef FVTA_SHB_ROWS
+}
+
+// ---- the question pass's: G = 256 / JP
+template <bool TW, bool POOL>
+static void shb_launch_q(const ShShape& s, const ShBwdShape& bs, const ShWork& sv, const ShBwdWork& wk, const float* rows,
+                         const float* dxs, hipStream_t st) {
   const dim3 qgrid((unsigned)((int64_t)s.ngmax * bs.TS * bs.nsl));
   if (s.G == 8)
-    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<8, false>), qgrid, dim3(64), 0, st, s, bs, sv, wk, hinfo, (const float*)nullptr);
+    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<8, TW, POOL>), qgrid, dim3(64), 0, st, s, bs, sv, wk, rows, dxs);
   else
-    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<4, false>), qgrid, dim3(64), 0, st, s, bs, sv, wk, hinfo, (const float*)nullptr);
-  hipLaunchKernelGGL(attn_shared_bwd_fold_kernel, dim3(s.NQ, (s.w + 255) / 256, bs.JZ), dim3(256), 0, st, s, bs, sv, wk, hq, d_hq);
-  hipLaunchKernelGGL(attn_shared_bwd_params_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, st, s, bs, wk, dW, db);
-  FVTA_CHECK_LAUNCH("attn_shared_bwd");
+    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<4, TW, POOL>), qgrid, dim3(64), 0, st, s, bs, sv, wk, rows, dxs);
+}
+
+// ---- the backward driver: the five launches of the header (1 prep, 2 rows, 3 question pass, 4 fold, 5 parameters) for
+// fvta_attn_shared_bwd <TW = 0, POOL = 0>, fvta_attn_shared_bwd_tw <1, 0> and fvta_attn_pool_bwd <0, 1>, with
+//   TW    the warp's own kernels (a .. f above) around them, and db left to (e)
+//   POOL  3b attn_pool_bwd_dct_kernel in front of the fold, and the pooled fold (attn_pool.hip)
+template <bool TW, bool POOL>
+static int shb_backward_as(ShShape s, const char* who, const ShBwdCall& c, const ShBwdWarpCall* warp) {
+  static_assert(!(TW && POOL), "the pooled backward is not under the time warp");
+  hipStream_t st = (hipStream_t)c.stream;
+  s.use_mask = (c.rows_mask && c.qmask) ? 1 : 0;
+  const ShBwdShape bs = shb_shape(s);
+  const ShWork sv(s, const_cast<void*>(c.saved), nullptr);
+  const ShBwdTwWork tw(s, bs, c.workspace);  // (what it carves past `base` is the TW call's alone: its workspace is larger)
+  const ShBwdWork& wk = tw.base;
+  ShBwdTwArgs ta{};
+  const float* tz = nullptr;
+  if constexpr (TW) {
+    const ShTwSaved ts(s, sv, const_cast<void*>(c.saved));
+    ta = ShBwdTwArgs{ts.scale, ts.lin, ts.r2, tw.ds, tw.dxs, tw.dbt};
+    tz = ts.tz;
+  }
+  ShShape sq = s;  // the prep runs per question over all of its positions
+  sq.T = s.TO;
+  hipLaunchKernelGGL(attn_shared_bwd_prep_kernel, dim3(s.NQ), dim3(s.K > 4 ? 1024 : 256), 0, st, sq, sv, wk, c.d_h_a);
+  if constexpr (TW) hipLaunchKernelGGL(attn_shared_tw_vec_kernel, dim3((s.w + 3) / 4), dim3(256), 0, st, s.w, warp->WH_W, warp->WC_W, tw.v);
+  shb_launch_rows<TW, POOL>(s, bs, sv, wk, c.rows, c.d_h_a, c.d_rows, ta, st);
+  shb_launch_q<TW, POOL>(s, bs, sv, wk, c.rows, TW ? (const float*)tw.dxs : nullptr, st);
+  if constexpr (TW) {
+    hipLaunchKernelGGL(attn_shared_bwd_tw_dz_kernel, dim3(s.NQ), dim3(256), 0, st, s, warp->warp_type, (int)ceilf(warp->window_t), tz,
+                       warp->WC_W, tw, warp->d_lq);
+    hipLaunchKernelGGL(attn_shared_bwd_tw_de_kernel, dim3(s.A, (s.T + 255) / 256), dim3(256), 0, st, s, sv, tw);
+    const dim3 egrid((unsigned)tw.ewg);
+    switch (s.w <= 256 ? 1 : s.w / 256) {
+      case 1: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<1>, egrid, dim3(256), 0, st, s, sv, tw, c.rows, c.d_rows); break;
+      case 2: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<2>, egrid, dim3(256), 0, st, s, sv, tw, c.rows, c.d_rows); break;
+      case 4: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<4>, egrid, dim3(256), 0, st, s, sv, tw, c.rows, c.d_rows); break;
+      default: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<8>, egrid, dim3(256), 0, st, s, sv, tw, c.rows, c.d_rows); break;
+    }
+  }
+  const dim3 fgrid(s.NQ, (s.w + 255) / 256, bs.JZ);
+  if constexpr (POOL) {
+    float* dctq = PoolBwdWork(s, bs, c.workspace).dctq;
+    hipLaunchKernelGGL(attn_pool_bwd_dct_kernel, dim3(s.NQ), dim3(64), 0, st, s, bs, sv, wk, dctq);
+    hipLaunchKernelGGL(attn_pool_bwd_fold_kernel, fgrid, dim3(256), 0, st, s, bs, sv, wk, (const float*)dctq, c.hq, c.d_hq);
+  } else {
+    hipLaunchKernelGGL(attn_shared_bwd_fold_kernel, fgrid, dim3(256), 0, st, s, bs, sv, wk, c.hq, c.d_hq);
+  }
+  // (TW: db is not the sum of the d ct -- the row pass says why; the parameter kernel's bias block adds into nothing)
+  hipLaunchKernelGGL(attn_shared_bwd_params_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, st, s, bs, wk, c.dW,
+                     TW ? (float*)nullptr : c.db);
+  if constexpr (TW) {
+    hipLaunchKernelGGL(attn_shared_bwd_tw_dv_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, st, s, tw, c.db);
+    hipLaunchKernelGGL(attn_shared_bwd_tw_params_kernel, dim3((s.w + 63) / 64), dim3(256), 0, st, s, tw, warp->WH_W, warp->WH_b,
+                       warp->WC_W, warp->lq, warp->dWH_W, warp->dWH_b, warp->dWC_W, warp->dWC_b);
+  }
+  FVTA_CHECK_LAUNCH(who);
   return FVTA_OK;
 }
 
+int shb_backward(const ShShape& s, bool pool, const char* who, const ShBwdCall& c, const ShBwdWarpCall* warp) {
+  if (pool) return shb_backward_as<false, true>(s, who, c, nullptr);
+  return warp ? shb_backward_as<true, false>(s, who, c, warp) : shb_backward_as<false, false>(s, who, c, nullptr);
+}
+
+size_t shb_workspace_bytes(const ShShape& s, bool pool) {
+  const ShBwdShape b = shb_shape(s);
+  return pool ? PoolBwdWork(s, b, nullptr).bytes : ShBwdWork(s, b, nullptr).bytes;
+}
+
+int shb_plan(const ShShape& s, const char* who, int32_t out[4]) {
+  FVTA_CHECK_ARG(out != nullptr, "%s: null pointer", who);
+  const ShBwdShape b = shb_shape(s);
+  out[0] = b.TR;
+  out[1] = b.TS;
+  out[2] = SHB_CS;
+  out[3] = b.tpw;
+  return FVTA_OK;
+}
+
+}  // namespace fvta
+using namespace fvta;
+
+extern "C" size_t fvta_attn_shared_bwd_workspace_bytes(const fvta_attn_shared_desc* d) {
+  ShShape s;
+  return sh_open(d, "attn_shared_bwd_workspace_bytes", s, SH_BWD) == FVTA_OK ? shb_workspace_bytes(s, false) : 0;
+}
+
+extern "C" int fvta_attn_shared_bwd_plan(const fvta_attn_shared_desc* d, int32_t out[4]) {
+  ShShape s;
+  if (int e = sh_open(d, "attn_shared_bwd_plan", s, SH_BWD)) return e;
+  return shb_plan(s, "attn_shared_bwd_plan", out);
+}
+
+extern "C" int fvta_attn_shared_bwd(const fvta_attn_shared_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,
+                                    const uint8_t* qmask, const int32_t* album, const float* W, const float* b,
+                                    const float* d_h_a, const void* saved, float* d_hinfo, float* d_hq, float* dW, float* db,
+                                    void* workspace, fvta_stream_t stream_) {
+  ShShape s;
+  if (int e = sh_open(d, "attn_shared_bwd", s, SH_BWD)) return e;
+  FVTA_CHECK_ARG(hinfo && hq && album && d_h_a && saved && d_hinfo && d_hq && dW && db && workspace,
+                 "attn_shared_bwd: null pointer");
+  return shb_backward(s, false, "attn_shared_bwd", {hinfo, hmask, hq, qmask, d_h_a, saved, d_hinfo, d_hq, dW, db, workspace, stream_});
+}
+
 extern "C" size_t fvta_attn_shared_tw_bwd_workspace_bytes(const fvta_attn_shared_tw_desc* d) {
-  if (shb_check_tw(d, "attn_shared_tw_bwd_workspace_bytes") != FVTA_OK) return 0;
-  const ShShape s = sh_shape(&d->shape);
+  ShShape s;
+  if (sh_open_tw(d, "attn_shared_tw_bwd_workspace_bytes", s, SH_BWD) != FVTA_OK) return 0;
   return ShBwdTwWork(s, shb_shape(s), nullptr).bytes;
 }
 
@@ -381,56 +439,12 @@ extern "C" int fvta_attn_shared_bwd_tw(const fvta_attn_shared_tw_desc* d, const 
                                        const float* d_h_a, const void* saved, float* d_hinfo, float* d_hq, float* d_lq, float* dW,
                                        float* db, float* dWH_W, float* dWH_b, float* dWC_W, float* dWC_b, void* workspace,
                                        fvta_stream_t stream_) {
-  if (int e = shb_check_tw(d, "attn_shared_bwd_tw")) return e;
+  ShShape s;
+  if (int e = sh_open_tw(d, "attn_shared_bwd_tw", s, SH_BWD)) return e;
   FVTA_CHECK_ARG(hinfo && hq && lq && album && W && WH_W && WH_b && WC_W && WC_b && d_h_a && saved && d_hinfo && d_hq && d_lq && dW &&
                      db && dWH_W && dWH_b && dWC_W && dWC_b && workspace,
                  "attn_shared_bwd_tw: null pointer");
-  hipStream_t st = (hipStream_t)stream_;
-  ShShape s = sh_shape(&d->shape);
-  s.use_mask = (hmask && qmask) ? 1 : 0;
-  const ShBwdShape bs = shb_shape(s);
-  const ShWork sv(s, const_cast<void*>(saved), nullptr);
-  const ShTwSaved ts(s, sv, const_cast<void*>(saved));
-  const ShBwdTwWork tw(s, bs, workspace);
-  const ShBwdWork& wk = tw.base;
-  const ShBwdTwArgs ta{ts.scale, ts.lin, ts.r2, tw.ds, tw.dxs, tw.dbt};
-  const int win = (int)ceilf(d->window_t);
-  hipLaunchKernelGGL(attn_shared_bwd_prep_kernel, dim3(s.NQ), dim3(s.K > 4 ? 1024 : 256), 0, st, s, sv, wk, d_h_a);
-  hipLaunchKernelGGL(attn_shared_tw_vec_kernel, dim3((s.w + 3) / 4), dim3(256), 0, st, s.w, WH_W, WC_W, tw.v);
-  const dim3 rgrid((unsigned)((int64_t)s.A * s.K * bs.nch));
-#define FVTA_SHB_ROWS(TPR, CPT, RPT) \
-  hipLaunchKernelGGL((attn_shared_bwd_rows_kernel<TPR, CPT, RPT, true>), rgrid, dim3(256), 0, st, s, bs, sv, wk, hinfo, d_h_a, \
-                     d_hinfo, ta)
-  switch (s.w) {
-    case 64: FVTA_SHB_ROWS(16, 1, 8); break;
-    case 128: FVTA_SHB_ROWS(32, 1, 8); break;
-    case 256: FVTA_SHB_ROWS(64, 1, 8); break;
-    case 512: FVTA_SHB_ROWS(128, 1, 8); break;
-    case 1024: FVTA_SHB_ROWS(256, 1, 8); break;
-    default: FVTA_SHB_ROWS(256, 2, 4); break;
-  }
-#undef FVTA_SHB_ROWS
-  const dim3 qgrid((unsigned)((int64_t)s.ngmax * bs.TS * bs.nsl));
-  if (s.G == 8)
-    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<8, true>), qgrid, dim3(64), 0, st, s, bs, sv, wk, hinfo, (const float*)tw.dxs);
-  else
-    hipLaunchKernelGGL((attn_shared_bwd_q_kernel<4, true>), qgrid, dim3(64), 0, st, s, bs, sv, wk, hinfo, (const float*)tw.dxs);
-  hipLaunchKernelGGL(attn_shared_bwd_tw_dz_kernel, dim3(s.NQ), dim3(256), 0, st, s, d->warp_type, win, (const float*)ts.tz, WC_W, tw,
-                     d_lq);
-  hipLaunchKernelGGL(attn_shared_bwd_tw_de_kernel, dim3(s.A, (s.T + 255) / 256), dim3(256), 0, st, s, sv, tw);
-  const dim3 egrid((unsigned)tw.ewg);
-  switch (s.w <= 256 ? 1 : s.w / 256) {
-    case 1: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<1>, egrid, dim3(256), 0, st, s, sv, tw, hinfo, d_hinfo); break;
-    case 2: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<2>, egrid, dim3(256), 0, st, s, sv, tw, hinfo, d_hinfo); break;
-    case 4: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<4>, egrid, dim3(256), 0, st, s, sv, tw, hinfo, d_hinfo); break;
-    default: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<8>, egrid, dim3(256), 0, st, s, sv, tw, hinfo, d_hinfo); break;
-  }
-  hipLaunchKernelGGL(attn_shared_bwd_fold_kernel, dim3(s.NQ, (s.w + 255) / 256, bs.JZ), dim3(256), 0, st, s, bs, sv, wk, hq, d_hq);
-  // (db: not the sum of the d ct here -- the row pass says why; the parameter kernel's bias block adds into nothing)
-  hipLaunchKernelGGL(attn_shared_bwd_params_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, st, s, bs, wk, dW, (float*)nullptr);
-  hipLaunchKernelGGL(attn_shared_bwd_tw_dv_kernel, dim3((s.w + 63) / 64 + 1), dim3(256), 0, st, s, tw, db);
-  hipLaunchKernelGGL(attn_shared_bwd_tw_params_kernel, dim3((s.w + 63) / 64), dim3(256), 0, st, s, tw, WH_W, WH_b, WC_W, lq, dWH_W,
-                     dWH_b, dWC_W, dWC_b);
-  FVTA_CHECK_LAUNCH("attn_shared_bwd_tw");
-  return FVTA_OK;
+  const ShBwdWarpCall warp{d->warp_type, d->window_t, lq, WH_W, WH_b, WC_W, WC_b, d_lq, dWH_W, dWH_b, dWC_W, dWC_b};
+  return shb_backward(s, false, "attn_shared_bwd_tw", {hinfo, hmask, hq, qmask, d_h_a, saved, d_hinfo, d_hq, dW, db, workspace, stream_},
+                      &warp);
 }

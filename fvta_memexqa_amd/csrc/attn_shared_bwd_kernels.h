@@ -75,6 +75,49 @@ struct ShBwdWork {
   }
 };
 
+// the pooled backward's workspace: ShBwdWork for the pooled shape, then dctq [NQ,JP]
+struct PoolBwdWork {
+  ShBwdWork base;
+  float* dctq;
+  size_t bytes;
+  PoolBwdWork(const ShShape& s, const ShBwdShape& b, void* p) : base(s, b, p) {
+    FvtaCarver c(p);
+    c.off = base.bytes;
+    dctq = c.take<float>((size_t)s.NQ * s.JP);
+    bytes = c.off;
+  }
+};
+
+// ---- the backward driver (attn_shared_bwd.hip): fvta_attn_shared_bwd, fvta_attn_shared_bwd_tw and fvta_attn_pool_bwd end in it
+struct ShBwdCall {
+  const float* rows;          // hinfo [A,K,T,w] / pool [P,K,JX,w]
+  const uint8_t* rows_mask;
+  const float* hq;
+  const uint8_t* qmask;
+  const float* d_h_a;
+  const void* saved;
+  float *d_rows, *d_hq, *dW, *db;
+  void* workspace;
+  fvta_stream_t stream;
+};
+struct ShBwdWarpCall {        // under the time warp: the warp's parameters, the question's state and their gradients
+  int warp_type;
+  float window_t;
+  const float *lq, *WH_W, *WH_b, *WC_W, *WC_b;
+  float *d_lq, *dWH_W, *dWH_b, *dWC_W, *dWC_b;
+};
+int shb_backward(const ShShape& s, bool pool, const char* who, const ShBwdCall& c, const ShBwdWarpCall* warp = nullptr);
+// the workspace of the backward not under the warp; TR, TS, SHB_CS, tpw (the *_bwd_workspace_bytes / *_bwd_plan pairs)
+size_t shb_workspace_bytes(const ShShape& s, bool pool);
+int shb_plan(const ShShape& s, const char* who, int32_t out[4]);
+
+// attn_pool.hip.  3b: grid NQ, 64 threads; 4: grid (NQ, ceil(w / 256), JZ), 256 threads
+__global__ __launch_bounds__(64) void attn_pool_bwd_dct_kernel(ShShape s, ShBwdShape bs, ShWork sv, ShBwdWork wk,
+                                                              float* __restrict__ dctq);
+__global__ __launch_bounds__(256) void attn_pool_bwd_fold_kernel(ShShape s, ShBwdShape bs, ShWork sv, ShBwdWork wk,
+                                                                const float* __restrict__ dctq, const float* __restrict__ hq,
+                                                                float* __restrict__ d_hq);
+
 // attn_shared_bwd.hip.  grid NQ, 1024 (K > 4) or 256 threads: attn_bwd_shared.h's prep body over s.T positions per
 // (question, k) -- the pooled caller passes T = M * JX
 __global__ __launch_bounds__(1024) void attn_shared_bwd_prep_kernel(ShShape s, ShWork sv, ShBwdWork wk,

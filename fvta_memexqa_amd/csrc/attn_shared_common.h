@@ -1,6 +1,7 @@
 // What the shared-context focal attention's forward (attn_shared.hip) and backward (attn_shared_bwd.hip) agree on: the
 // shape, the plan's layout, the forward's buffers and -- in training -- which of them live in the caller-held `saved`.
 #pragma once
+#include <type_traits>
 #include "attn_common.h"
 
 namespace fvta {
@@ -42,20 +43,19 @@ inline void sh_derive(ShShape& s) {
   s.S = (s.T + s.rps - 1) / s.rps;
 }
 
-inline ShShape sh_shape(const fvta_attn_shared_desc* d) {
-  ShShape s;
+// the descriptor's own words (M = 1: a question is its one reference); sh_check derives the rest
+inline ShShape sh_words(const fvta_attn_shared_desc* d) {
+  ShShape s{};
   s.A = d->A, s.NQ = d->NQ, s.K = d->K, s.T = d->T, s.JQ = d->JQ, s.w = d->w, s.simi = d->simi, s.add_tanh = d->add_tanh;
   s.M = 1;
-  sh_derive(s);
   return s;
 }
 
-// the pooled call's shape (checked by fvta_attn_pool_check: NQ M and M JX are within range)
-inline ShShape sh_pool_shape(const fvta_attn_pool_desc* d) {
-  ShShape s;
+// the pooled call's: A = P pooled albums of T = JX rows each, M slots per question
+inline ShShape sh_words(const fvta_attn_pool_desc* d) {
+  ShShape s{};
   s.A = d->P, s.NQ = d->NQ, s.K = d->K, s.T = d->JX, s.JQ = d->JQ, s.w = d->w, s.simi = d->simi, s.add_tanh = d->add_tanh;
   s.M = d->M;
-  sh_derive(s);
   return s;
 }
 
@@ -159,14 +159,71 @@ struct ShTwArgs {
   float *lin, *r2;
 };
 
-// 0: fine, else the status with the message set (attn_shared.hip)
-int fvta_attn_shared_check(const fvta_attn_shared_desc* d, const char* who);
-// the same, and simiMatrix 1-3 (training: the cosine form has no shared-context backward)
-int fvta_attn_shared_check_train(const fvta_attn_shared_desc* d, const char* who);
-// under the time warp: the shape, the warp type (1..5: else FVTA_ERR_INVALID_ARG), the window; `train`: simiMatrix 1-3 too
-int fvta_attn_shared_check_tw(const fvta_attn_shared_tw_desc* d, const char* who, bool train = false);
-// its warp type (1..5: else FVTA_ERR_INVALID_ARG) and window checks alone: the pooled call under the warp makes them too
-int fvta_attn_shared_check_warp(int warp_type, float window_t, const char* who);
+// The workspace under the warp: the inference ShWork's, then scale [NQ,TO], then v [w] (the energy call's)
+struct ShTwWork {
+  ShWork wk;
+  float *scale, *v;
+  size_t bytes;
+  ShTwWork(const ShShape& s, void* p) : wk(s, p) {
+    FvtaCarver c(p);
+    c.off = wk.bytes;
+    scale = c.take<float>((size_t)s.NQ * s.TO);
+    v = c.take<float>((size_t)s.w);
+    bytes = c.off;
+  }
+};
+
+// ---- the checks (attn_shared.hip), ONE ladder for both families.  0: fine, else the status with the message set.  The
+// refusal texts are part of the interface and each family keeps its own letters (A/NQ/K/T/JQ/w against
+// P/NQ/M/K/JX/JQ/w): `pool` picks them.  s comes in with the descriptor's words (sh_words) and leaves with the derived ones
+enum ShLevel {
+  SH_FWD,    // the shape
+  SH_TRAIN,  // and simiMatrix 1-3: the cosine form has no backward here
+  SH_BWD     // and the backward's grids (attn_shared_bwd_kernels.h: ShBwdShape)
+};
+int sh_check(ShShape& s, bool pool, const char* who, ShLevel level = SH_FWD);
+// the same under the time warp: then the warp type (1..5: else FVTA_ERR_INVALID_ARG), the window, the scale kernel's grid
+// (TO <= 65535 * 256) and the pooled energy call's
+int sh_check_tw(ShShape& s, bool pool, int warp_type, float window_t, const char* who, ShLevel level = SH_FWD);
+
+// what every entry point begins with: the descriptor (D: fvta_attn_shared_desc or fvta_attn_pool_desc) into s, checked
+template <class D>
+int sh_open(const D* d, const char* who, ShShape& s, ShLevel level = SH_FWD) {
+  FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
+  s = sh_words(d);
+  return sh_check(s, std::is_same<D, fvta_attn_pool_desc>::value, who, level);
+}
+template <class D>  // D: fvta_attn_shared_tw_desc or fvta_attn_pool_tw_desc
+int sh_open_tw(const D* d, const char* who, ShShape& s, ShLevel level = SH_FWD) {
+  FVTA_CHECK_ARG(d != nullptr, "%s: null descriptor", who);
+  s = sh_words(&d->shape);
+  return sh_check_tw(s, std::is_same<D, fvta_attn_pool_tw_desc>::value, d->warp_type, d->window_t, who, level);
+}
+
+// ---- the forward driver (attn_shared.hip): every forward entry point of both families ends in it
+struct ShFwdCall {
+  const float* rows;          // hinfo [A,K,T,w] / pool [P,K,JX,w]
+  const uint8_t* rows_mask;
+  const float* hq;
+  const uint8_t* qmask;
+  const int32_t* index;       // album [NQ] / albums [NQ,M]
+  const float *W, *b;
+  float *h_a, *a_logits;
+  void *saved, *workspace;    // saved: training (else null)
+  fvta_stream_t stream;
+};
+struct ShWarpCall {           // under the time warp: what the scale kernel reads, and where the caller wants the scale
+  int warp_type;
+  float window_t;
+  const float *energy, *lq, *WH_b, *WC_W, *WC_b;
+  float* scale_out;
+};
+int sh_forward(const ShShape& s, bool pool, const char* who, const ShFwdCall& c, const ShWarpCall* warp = nullptr);
+// the two launches of e[a,t] over the rows of A albums of T positions: fvta_attn_shared_energy, fvta_attn_pool_energy
+int sh_energy(const ShShape& s, const char* who, const float* rows, const float* WH_W, const float* WC_W, float* energy,
+              void* workspace, fvta_stream_t stream);
+// G, SH_R, S, rps (fvta_attn_shared_plan, fvta_attn_pool_plan)
+int sh_plan(const ShShape& s, const char* who, int32_t out[4]);
 
 // v[c] = sum_o WH[c][o] WC[o] (attn_shared.hip).  grid ceil(w / 4), 256 threads
 __global__ __launch_bounds__(256) void attn_shared_tw_vec_kernel(int w, const float* __restrict__ WH, const float* __restrict__ WC,

@@ -173,6 +173,65 @@ def attention_raw(hinfo, hq, W, b, hinfo_mask=None, hq_mask=None, simiMatrix=1, 
     return h_a[:, :w].contiguous(), a
 
 
+def _album_attention_args(rows, hq, index, W, b, rows_mask, hq_mask, simiMatrix, pooled, differentiable, no_backward,
+                          forward_only, warp=None):
+    """The preparation the five attention_3d_{shared,pooled}[_warped]_raw functions share, every refusal before any
+    library or device call and in one order: the similarity matrix (and warp type), differentiable with simiMatrix 4
+    (`no_backward`), gradient mode on a forward-only call (`forward_only`), the shapes, the index, the width.  rows:
+    [A,K,T,w] / [A,K,M,JX,w], `pooled`: a pool [P,K,JX,w] with album lists.  warp: None, or (lq, WH_W, WH_b, WC_W, WC_b,
+    warp_type, energy).  Without `differentiable` everything is detached.  -> a namespace: rows / hq / lq padded to the
+    kernel width wp, idx on the device, W padded block-wise, b, the two uint8 masks (None unless BOTH are given:
+    model_v2.py:233), the warp's weights as the kernels read them, energy (detached, or None), and A K T NQ JQ w wp."""
+    from types import SimpleNamespace
+    if simiMatrix not in (1, 2, 3, 4):
+        raise ValueError("similarity matrix not implemented")
+    lq, WH_W, WH_b, WC_W, WC_b, warp_type, energy = warp if warp is not None else (None,) * 7
+    if warp is not None:
+        _check_warp_type(warp_type)
+    if differentiable and simiMatrix == 4:
+        raise NotImplementedError(no_backward)
+    tensors = [t for t in (rows, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b) if torch.is_tensor(t)]
+    if not differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError(forward_only)
+    det = (lambda t: t) if differentiable else (lambda t: t.detach())
+    rows, hq = det(_f32(rows)), det(_f32(hq))
+    lq = None if warp is None else det(_f32(lq))
+    if pooled and rows.dim() != 4:
+        raise ValueError("album pool: expected [P,K,JX,w], got shape %s" % (tuple(rows.shape),))
+    A, K, w = rows.shape[0], rows.shape[1], rows.shape[-1]
+    rows = rows.reshape(A, K, -1, w)
+    T = rows.shape[2]
+    NQ, JQ = hq.shape[0], hq.shape[1]
+    if warp is not None and tuple(lq.shape) != (NQ, w):
+        raise ValueError("lq: expected the questions' last states [%d, %d], got %s" % (NQ, w, tuple(lq.shape)))
+    both = rows_mask is not None and hq_mask is not None
+    idx = ops.check_album_lists(index, A, both) if pooled else ops.check_album_index(index, A)
+    if idx.shape[0] != NQ:
+        raise ValueError(("album lists: %d lists for %d questions" if pooled else "album index: %d entries for %d questions")
+                         % (idx.shape[0], NQ))
+    if energy is not None and tuple(energy.shape) != (A, T):
+        raise ValueError("energy: expected [%d, %d], got %s" % (A, T, tuple(energy.shape)))
+    wp = next((c for c in SUPPORTED_W if w <= c), None)
+    if wp is None:
+        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
+    F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
+    if F:
+        W = _pad_channels(det(_f32(W)).reshape(F, w), wp).reshape(-1)
+        b = det(_f32(b))
+    else:
+        W = b = None
+    dev = ops.require_gpu()
+    p = SimpleNamespace(A=A, K=K, T=T, NQ=NQ, JQ=JQ, w=w, wp=wp, W=W, b=b, idx=idx.to(dev),
+                        rows=_pad_channels(rows, wp), hq=_pad_channels(hq, wp),
+                        rm=ops.as_mask_u8(rows_mask.reshape(A, K, T)) if both else None,
+                        qm=ops.as_mask_u8(hq_mask) if both else None)
+    if warp is not None:
+        p.WH, p.WC, p.WHb, p.WCb = _warp_weights(w, wp, WH_W, WC_W, WH_b, WC_b, detach=not differentiable)
+        p.lq = _pad_channels(lq, wp)
+        p.energy = None if energy is None else _f32(energy).detach().contiguous()
+    return p
+
+
 def attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask=None, hq_mask=None, simiMatrix=1, add_tanh=False,
                             differentiable=False):
     """attention_3d for NQ questions over A albums held once: hinfo [A,K,T,w] (or [A,K,M,JX,w]), hq [NQ,JQ,w], album [NQ]
@@ -183,47 +242,19 @@ def attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask=None, hq_mask=Non
     differentiable=True goes through autograd.shared_focal_attention (simiMatrix 1-3; 4 raises NotImplementedError):
     gradients flow from h_a to hinfo -- summed over each album's questions, [A,K,T,w] -- hq, W and b; a_logits carries
     none."""
-    if simiMatrix not in (1, 2, 3, 4):
-        raise ValueError("similarity matrix not implemented")
-    if differentiable and simiMatrix == 4:
-        raise NotImplementedError("attention_3d_shared_raw(differentiable=True): simiMatrix 4 has no shared-context backward; "
-                                  "use the per-question attention_3d (attention_raw) on hinfo.index_select(0, album)")
-    tensors = [t for t in (hinfo, hq, W, b) if torch.is_tensor(t)]
-    if not differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise RuntimeError("attention_3d_shared_raw is forward-only by default: pass differentiable=True (simiMatrix 1-3), call "
-                           "it under torch.no_grad(), or use the per-question attention_3d (functional.attention_3d / "
-                           "attention_raw, nn.FocalAttention3D.forward)")
-    if not differentiable:
-        hinfo, hq = hinfo.detach(), hq.detach()
-        W, b = (None if W is None else W.detach()), (None if b is None else b.detach())
-    hinfo, hq = _f32(hinfo), _f32(hq)
-    A, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
-    hinfo = hinfo.reshape(A, K, -1, w)
-    T = hinfo.shape[2]
-    NQ, JQ = hq.shape[0], hq.shape[1]
-    idx = ops.check_album_index(album, A)
-    if idx.shape[0] != NQ:
-        raise ValueError("album index: %d entries for %d questions" % (idx.shape[0], NQ))
-    wp = next((c for c in SUPPORTED_W if w <= c), None)
-    if wp is None:
-        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
-    F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
-    if F:
-        W = _pad_channels(_f32(W).reshape(F, w), wp).reshape(-1)
-        b = _f32(b)
-    else:
-        W = b = None
-    dev = ops.require_gpu()
-    both = hinfo_mask is not None and hq_mask is not None                  # model_v2.py:233: only when BOTH are given
-    hm = ops.as_mask_u8(hinfo_mask.reshape(A, K, T)) if both else None
-    qm = ops.as_mask_u8(hq_mask) if both else None
+    p = _album_attention_args(
+        hinfo, hq, album, W, b, hinfo_mask, hq_mask, simiMatrix, False, differentiable,
+        "attention_3d_shared_raw(differentiable=True): simiMatrix 4 has no shared-context backward; "
+        "use the per-question attention_3d (attention_raw) on hinfo.index_select(0, album)",
+        "attention_3d_shared_raw is forward-only by default: pass differentiable=True (simiMatrix 1-3), call "
+        "it under torch.no_grad(), or use the per-question attention_3d (functional.attention_3d / "
+        "attention_raw, nn.FocalAttention3D.forward)")
     if differentiable:
-        h_a, a = autograd.shared_focal_attention(_pad_channels(hinfo, wp), _pad_channels(hq, wp), idx.to(dev), W, b, hm, qm,
-                                                 simiMatrix, add_tanh)
+        h_a, a = autograd.shared_focal_attention(p.rows, p.hq, p.idx, p.W, p.b, p.rm, p.qm, simiMatrix, add_tanh)
     else:
-        op = ops.SharedFocalAttention(A, NQ, K, T, JQ, wp, simiMatrix, add_tanh)
-        h_a, a = op.forward(_pad_channels(hinfo, wp), hm, _pad_channels(hq, wp), qm, idx.to(dev), W, b, want_logits=True)
-    return h_a[:, :w].contiguous(), a
+        op = ops.SharedFocalAttention(p.A, p.NQ, p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh)
+        h_a, a = op.forward(p.rows, p.rm, p.hq, p.qm, p.idx, p.W, p.b, want_logits=True)
+    return h_a[:, :p.w].contiguous(), a
 
 
 def attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask=None, hq_mask=None, simiMatrix=1, add_tanh=False,
@@ -238,58 +269,31 @@ def attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask=None, hq_mask=None
     argument that requires grad it raises, as attention_3d_shared_raw does.  differentiable=True goes through
     autograd.pooled_focal_attention (simiMatrix 1-3; 4 raises NotImplementedError): gradients flow from h_a to pool --
     summed over every (question, slot) that names the album, [P,K,JX,w] -- hq, W and b; a_logits carries none."""
-    if simiMatrix not in (1, 2, 3, 4):
-        raise ValueError("similarity matrix not implemented")
-    if differentiable and simiMatrix == 4:
-        raise NotImplementedError("attention_3d_pooled_raw(differentiable=True): simiMatrix 4 has no pooled backward; use the "
-                                  "per-question attention_3d (attention_raw) on the gathered rows")
-    tensors = [t for t in (pool, hq, W, b) if torch.is_tensor(t)]
-    if not differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise RuntimeError("attention_3d_pooled_raw is forward-only: call it under torch.no_grad(), or use the per-question "
-                           "attention_3d (functional.attention_3d / attention_raw, nn.FocalAttention3D.forward) on the "
-                           "gathered rows")
-    if not differentiable:
-        pool, hq = pool.detach(), hq.detach()
-        W, b = (None if W is None else W.detach()), (None if b is None else b.detach())
-    pool, hq = _f32(pool), _f32(hq)
-    if pool.dim() != 4:
-        raise ValueError("album pool: expected [P,K,JX,w], got shape %s" % (tuple(pool.shape),))
-    P, K, JX, w = pool.shape
-    NQ, JQ = hq.shape[0], hq.shape[1]
-    both = pool_mask is not None and hq_mask is not None                   # model_v2.py:233: only when BOTH are given
-    idx = ops.check_album_lists(albums, P, both)
-    if idx.shape[0] != NQ:
-        raise ValueError("album lists: %d lists for %d questions" % (idx.shape[0], NQ))
-    wp = next((c for c in SUPPORTED_W if w <= c), None)
-    if wp is None:
-        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
-    F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
-    if F:
-        W = _pad_channels(_f32(W).reshape(F, w), wp).reshape(-1)
-        b = _f32(b)
-    else:
-        W = b = None
-    dev = ops.require_gpu()
-    pm = ops.as_mask_u8(pool_mask.reshape(P, K, JX)) if both else None
-    qm = ops.as_mask_u8(hq_mask) if both else None
+    p = _album_attention_args(
+        pool, hq, albums, W, b, pool_mask, hq_mask, simiMatrix, True, differentiable,
+        "attention_3d_pooled_raw(differentiable=True): simiMatrix 4 has no pooled backward; use the "
+        "per-question attention_3d (attention_raw) on the gathered rows",
+        "attention_3d_pooled_raw is forward-only: call it under torch.no_grad(), or use the per-question "
+        "attention_3d (functional.attention_3d / attention_raw, nn.FocalAttention3D.forward) on the "
+        "gathered rows")
     if differentiable:
-        h_a, a = autograd.pooled_focal_attention(_pad_channels(pool, wp), _pad_channels(hq, wp), idx.to(dev), W, b, pm, qm,
-                                                 simiMatrix, add_tanh)
+        h_a, a = autograd.pooled_focal_attention(p.rows, p.hq, p.idx, p.W, p.b, p.rm, p.qm, simiMatrix, add_tanh)
     else:
-        op = ops.PooledFocalAttention(P, NQ, idx.shape[1], K, JX, JQ, wp, simiMatrix, add_tanh)
-        h_a, a = op.forward(_pad_channels(pool, wp), pm, _pad_channels(hq, wp), qm, idx.to(dev), W, b, want_logits=True)
-    return h_a[:, :w].contiguous(), a
+        op = ops.PooledFocalAttention(p.A, p.NQ, p.idx.shape[1], p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh)
+        h_a, a = op.forward(p.rows, p.rm, p.hq, p.qm, p.idx, p.W, p.b, want_logits=True)
+    return h_a[:, :p.w].contiguous(), a
 
 
-def _warp_weights(w, wp, WH_W, WC_W, WH_b=None, WC_b=None):
-    """the time warp's weights as the shared-context kernels read them: WH_W's first w rows [wp,wp], WC_W [wp], and --
-    where given -- WH_b [wp], WC_b [1], zero padded to the kernel width (exact: a zero channel adds nothing to v, s0 or
-    WC . lq)"""
+def _warp_weights(w, wp, WH_W, WC_W, WH_b=None, WC_b=None, detach=True):
+    """the time warp's weights as the shared-context kernels read them: WH_W's first w rows [wp,wp] (the rest sees a zero
+    feature), WC_W [wp], and -- where given -- WH_b [wp], WC_b [1], zero padded to the kernel width (exact: a zero channel
+    adds nothing to v, s0 or WC . lq); detach=False: with differentiable torch ops"""
     pad = torch.nn.functional.pad
-    WH = pad(_f32(WH_W).detach().reshape(-1, w)[:w], (0, wp - w, 0, wp - w)).contiguous()
-    WC = pad(_f32(WC_W).detach().reshape(w), (0, wp - w)).contiguous()
-    WH_b = None if WH_b is None else pad(_f32(WH_b).detach().reshape(w), (0, wp - w)).contiguous()
-    WC_b = None if WC_b is None else _f32(WC_b).detach().reshape(1)
+    f = (lambda t: _f32(t).detach()) if detach else _f32
+    WH = pad(f(WH_W).reshape(-1, w)[:w], (0, wp - w, 0, wp - w)).contiguous()
+    WC = pad(f(WC_W).reshape(w), (0, wp - w)).contiguous()
+    WH_b = None if WH_b is None else pad(f(WH_b).reshape(w), (0, wp - w)).contiguous()
+    WC_b = None if WC_b is None else f(WC_b).reshape(1)
     return WH, WC, WH_b, WC_b
 
 
@@ -325,53 +329,23 @@ def attention_3d_shared_warped_raw(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W,
     gradients flow from h_a to hinfo -- summed over each album's questions, [A,K,T,w] -- hq, lq, W, b and the warp's four
     parameters (WH_W's rows w..2w-1 get zeros: they see a zero feature); a_logits and scale carry none.  A given energy is
     used as a cached value of the forward; the gradient through e is taken all the same."""
-    if simiMatrix not in (1, 2, 3, 4):
-        raise ValueError("similarity matrix not implemented")
-    _check_warp_type(warp_type)
-    if differentiable and simiMatrix == 4:
-        raise NotImplementedError("attention_3d_shared_warped_raw(differentiable=True): simiMatrix 4 has no shared-context "
-                                  "backward; use the per-question time_warp_raw + attention_raw on hinfo.index_select(0, album)")
-    if differentiable:
-        return _attention_3d_shared_warped_train(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W, WC_b, hinfo_mask, hq_mask, simiMatrix,
-                                                 add_tanh, warp_type, window_t, energy)
-    tensors = [t for t in (hinfo, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b) if torch.is_tensor(t)]
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise RuntimeError("attention_3d_shared_warped_raw is forward-only: call it under torch.no_grad(), or use the "
-                           "per-question time_warp + attention_3d (functional.time_warp_raw / attention_raw, nn.TimeWarp / "
-                           "nn.FocalAttention3D.forward) on hinfo.index_select(0, album)")
-    hinfo, hq, lq = _f32(hinfo).detach(), _f32(hq).detach(), _f32(lq).detach()
-    A, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
-    hinfo = hinfo.reshape(A, K, -1, w)
-    T = hinfo.shape[2]
-    NQ, JQ = hq.shape[0], hq.shape[1]
-    if tuple(lq.shape) != (NQ, w):
-        raise ValueError("lq: expected the questions' last states [%d, %d], got %s" % (NQ, w, tuple(lq.shape)))
-    idx = ops.check_album_index(album, A)
-    if idx.shape[0] != NQ:
-        raise ValueError("album index: %d entries for %d questions" % (idx.shape[0], NQ))
-    if energy is not None and tuple(energy.shape) != (A, T):
-        raise ValueError("energy: expected [%d, %d], got %s" % (A, T, tuple(energy.shape)))
-    wp = next((c for c in SUPPORTED_W if w <= c), None)
-    if wp is None:
-        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
-    F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
-    if F:
-        W = _pad_channels(_f32(W).detach().reshape(F, w), wp).reshape(-1)
-        b = _f32(b).detach()
+    p = _album_attention_args(
+        hinfo, hq, album, W, b, hinfo_mask, hq_mask, simiMatrix, False, differentiable,
+        "attention_3d_shared_warped_raw(differentiable=True): simiMatrix 4 has no shared-context "
+        "backward; use the per-question time_warp_raw + attention_raw on hinfo.index_select(0, album)",
+        "attention_3d_shared_warped_raw is forward-only: call it under torch.no_grad(), or use the "
+        "per-question time_warp + attention_3d (functional.time_warp_raw / attention_raw, nn.TimeWarp / "
+        "nn.FocalAttention3D.forward) on hinfo.index_select(0, album)",
+        warp=(lq, WH_W, WH_b, WC_W, WC_b, warp_type, energy))
+    if differentiable:     # (the gradients come back sliced to w; WH_W's comes back [2w,w] with zeros below row w)
+        h_a, a, scale = autograd.shared_warped_focal_attention(p.rows, p.hq, p.lq, p.idx, p.W, p.b, p.WH, p.WHb, p.WC, p.WCb, p.rm,
+                                                               p.qm, simiMatrix, add_tanh, warp_type, float(window_t), p.energy)
     else:
-        W = b = None
-    dev = ops.require_gpu()
-    both = hinfo_mask is not None and hq_mask is not None                  # model_v2.py:233: only when BOTH are given
-    hm = ops.as_mask_u8(hinfo_mask.reshape(A, K, T)) if both else None
-    qm = ops.as_mask_u8(hq_mask) if both else None
-    WH, WC, WHb, WCb = _warp_weights(w, wp, WH_W, WC_W, WH_b, WC_b)
-    op = ops.SharedWarpedFocalAttention(A, NQ, K, T, JQ, wp, simiMatrix, add_tanh, warp_type, float(window_t))
-    rows = _pad_channels(hinfo, wp)
-    if energy is None:
-        energy = op.album_energy(rows, WH, WC)
-    h_a, a, scale = op.forward(rows, hm, _f32(energy).detach().contiguous(), _pad_channels(hq, wp), qm, _pad_channels(lq, wp),
-                               idx.to(dev), W, b, WHb, WC, WCb, want_logits=True, want_scale=True)
-    return h_a[:, :w].contiguous(), a, scale
+        op = ops.SharedWarpedFocalAttention(p.A, p.NQ, p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh, warp_type, float(window_t))
+        energy = op.album_energy(p.rows, p.WH, p.WC) if p.energy is None else p.energy
+        h_a, a, scale = op.forward(p.rows, p.rm, energy, p.hq, p.qm, p.lq, p.idx, p.W, p.b, p.WHb, p.WC, p.WCb, want_logits=True,
+                                   want_scale=True)
+    return h_a[:, :p.w].contiguous(), a, scale
 
 
 def attention_3d_pooled_warped_raw(pool, hq, albums, lq, W, b, WH_W, WH_b, WC_W, WC_b, pool_mask=None, hq_mask=None,
@@ -384,83 +358,18 @@ def attention_3d_pooled_warped_raw(pool, hq, albums, lq, W, b, WH_W, WH_b, WC_W,
     Neither the [NQ,K,M*JX,w] context nor its warp is built: the warp is one scalar per (question, position), applied
     inside the kernels (fvta_attn_pool_fwd_tw).  energy [P,JX]: album_energy of (pool, WH_W, WC_W), None computes it on the
     spot.  Forward-only: with gradient mode on and an argument that requires grad it raises."""
-    if simiMatrix not in (1, 2, 3, 4):
-        raise ValueError("similarity matrix not implemented")
-    _check_warp_type(warp_type)
-    tensors = [t for t in (pool, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b) if torch.is_tensor(t)]
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise RuntimeError("attention_3d_pooled_warped_raw is forward-only: call it under torch.no_grad(), or use the "
-                           "per-question time_warp + attention_3d (functional.time_warp_raw / attention_raw, nn.TimeWarp / "
-                           "nn.FocalAttention3D.forward) on the gathered rows")
-    pool, hq, lq = _f32(pool).detach(), _f32(hq).detach(), _f32(lq).detach()
-    if pool.dim() != 4:
-        raise ValueError("album pool: expected [P,K,JX,w], got shape %s" % (tuple(pool.shape),))
-    P, K, JX, w = pool.shape
-    NQ, JQ = hq.shape[0], hq.shape[1]
-    if tuple(lq.shape) != (NQ, w):
-        raise ValueError("lq: expected the questions' last states [%d, %d], got %s" % (NQ, w, tuple(lq.shape)))
-    both = pool_mask is not None and hq_mask is not None                   # model_v2.py:233: only when BOTH are given
-    idx = ops.check_album_lists(albums, P, both)
-    if idx.shape[0] != NQ:
-        raise ValueError("album lists: %d lists for %d questions" % (idx.shape[0], NQ))
-    if energy is not None and tuple(energy.shape) != (P, JX):
-        raise ValueError("energy: expected [%d, %d], got %s" % (P, JX, tuple(energy.shape)))
-    wp = next((c for c in SUPPORTED_W if w <= c), None)
-    if wp is None:
-        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
-    F = {1: 3, 2: 2, 3: 4, 4: 0}[simiMatrix]
-    if F:
-        W = _pad_channels(_f32(W).detach().reshape(F, w), wp).reshape(-1)
-        b = _f32(b).detach()
-    else:
-        W = b = None
-    dev = ops.require_gpu()
-    pm = ops.as_mask_u8(pool_mask.reshape(P, K, JX)) if both else None
-    qm = ops.as_mask_u8(hq_mask) if both else None
-    WH, WC, WHb, WCb = _warp_weights(w, wp, WH_W, WC_W, WH_b, WC_b)
-    op = ops.PooledWarpedFocalAttention(P, NQ, idx.shape[1], K, JX, JQ, wp, simiMatrix, add_tanh, warp_type, float(window_t))
-    rows = _pad_channels(pool, wp)
-    if energy is None:
-        energy = op.album_energy(rows, WH, WC)
-    h_a, a, scale = op.forward(rows, pm, _f32(energy).detach().contiguous(), _pad_channels(hq, wp), qm, _pad_channels(lq, wp),
-                               idx.to(dev), W, b, WHb, WC, WCb, want_logits=True, want_scale=True)
-    return h_a[:, :w].contiguous(), a, scale
-
-
-def _attention_3d_shared_warped_train(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W, WC_b, hinfo_mask, hq_mask, simiMatrix, add_tanh,
-                                      warp_type, window_t, energy):
-    """attention_3d_shared_warped_raw(differentiable=True): the same checks and the same channel padding, with
-    differentiable torch ops (the gradients come back sliced to w; WH_W's comes back [2w,w] with zeros below row w)"""
-    pad = torch.nn.functional.pad
-    hinfo, hq, lq = _f32(hinfo), _f32(hq), _f32(lq)
-    A, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
-    hinfo = hinfo.reshape(A, K, -1, w)
-    T = hinfo.shape[2]
-    NQ, JQ = hq.shape[0], hq.shape[1]
-    if tuple(lq.shape) != (NQ, w):
-        raise ValueError("lq: expected the questions' last states [%d, %d], got %s" % (NQ, w, tuple(lq.shape)))
-    idx = ops.check_album_index(album, A)
-    if idx.shape[0] != NQ:
-        raise ValueError("album index: %d entries for %d questions" % (idx.shape[0], NQ))
-    if energy is not None and tuple(energy.shape) != (A, T):
-        raise ValueError("energy: expected [%d, %d], got %s" % (A, T, tuple(energy.shape)))
-    wp = next((c for c in SUPPORTED_W if w <= c), None)
-    if wp is None:
-        raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
-    F = {1: 3, 2: 2, 3: 4}[simiMatrix]
-    W = _pad_channels(_f32(W).reshape(F, w), wp).reshape(-1)
-    dev = ops.require_gpu()
-    both = hinfo_mask is not None and hq_mask is not None                  # model_v2.py:233: only when BOTH are given
-    hm = ops.as_mask_u8(hinfo_mask.reshape(A, K, T)) if both else None
-    qm = ops.as_mask_u8(hq_mask) if both else None
-    WH = pad(_f32(WH_W).reshape(-1, w)[:w], (0, wp - w, 0, wp - w))         # the first w rows: the rest sees a zero feature
-    WC = pad(_f32(WC_W).reshape(w), (0, wp - w))
-    WHb = pad(_f32(WH_b).reshape(w), (0, wp - w))
-    h_a, a, scale = autograd.shared_warped_focal_attention(
-        _pad_channels(hinfo, wp), _pad_channels(hq, wp), _pad_channels(lq, wp), idx.to(dev), W, _f32(b), WH, WHb, WC,
-        _f32(WC_b).reshape(1), hm, qm, simiMatrix, add_tanh, warp_type, float(window_t),
-        None if energy is None else _f32(energy).detach())
-    return h_a[:, :w].contiguous(), a, scale
+    p = _album_attention_args(
+        pool, hq, albums, W, b, pool_mask, hq_mask, simiMatrix, True, False, None,
+        "attention_3d_pooled_warped_raw is forward-only: call it under torch.no_grad(), or use the "
+        "per-question time_warp + attention_3d (functional.time_warp_raw / attention_raw, nn.TimeWarp / "
+        "nn.FocalAttention3D.forward) on the gathered rows",
+        warp=(lq, WH_W, WH_b, WC_W, WC_b, warp_type, energy))
+    op = ops.PooledWarpedFocalAttention(p.A, p.NQ, p.idx.shape[1], p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh, warp_type,
+                                        float(window_t))
+    energy = op.album_energy(p.rows, p.WH, p.WC) if p.energy is None else p.energy
+    h_a, a, scale = op.forward(p.rows, p.rm, energy, p.hq, p.qm, p.lq, p.idx, p.W, p.b, p.WHb, p.WC, p.WCb, want_logits=True,
+                               want_scale=True)
+    return h_a[:, :p.w].contiguous(), a, scale
 
 
 def attention_3d_shared(hinfo, hq, album, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, add_tanh=False,

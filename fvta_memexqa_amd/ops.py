@@ -305,7 +305,127 @@ def check_album_index(album, A):
     return t.to(torch.int32).contiguous()
 
 
-class SharedFocalAttention:
+class _AlbumAttention:
+    """What the four classes of this section share: context rows held ONCE ([A,K,T,w] per album, or a pool [P,K,JX,w]),
+    an int32 index on the device that says which of them a question reads (album [NQ], or albums [NQ,M]), and the library's
+    entry points under one prefix (fvta_attn_shared / fvta_attn_pool).  A subclass's constructor names the prefix, the
+    FvtaError prefix, the descriptor, the rows' and the index's shape and the positions per question (T, or M*JX)."""
+    _tw, _sep = "", " "               # the warped pair: "_tw" in its size queries, ", " in its messages
+
+    def _setup(self, sym, what, desc, rows_shape, index_shape, positions):
+        self.lib = _lib.load()
+        self.dev = require_gpu()
+        self._sym, self._what, self.desc = sym, what, desc
+        self._shape_desc = desc.shape if self._tw else desc
+        self._rows, self._index, self._TO = tuple(rows_shape), tuple(index_shape), int(positions)
+        # (under the warp a refusal may be a bad warp type: "time warping type not implemented", model_v2.py:341)
+        self.work = _sized(self, sym + self._tw + "_workspace_bytes", what + ": ")
+
+    def _call(self, name, *args):
+        check(getattr(self.lib, name)(ctypes.byref(self.desc), *args, stream_ptr()), name)
+
+    def _words(self, name, keys):
+        out = (ctypes.c_int32 * 4)()
+        check(getattr(self.lib, name)(ctypes.byref(self._shape_desc), out), name)
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def plan(self):
+        """{G, rows, tsplit, rows_per_split}: questions (references) per group, rows per logits tile, splits of T (JX) in
+        the weighted sum and the rows of one split (fvta_attn_{shared,pool}_plan; host only; the warp changes none)"""
+        return self._words(self._sym + "_plan", ("G", "rows", "tsplit", "rows_per_split"))
+
+    def bwd_plan(self):
+        """{rows, tsplit, channels, tiles_per_wg}: rows per tile of the backward's row pass, T (JX) splits and channels per
+        slice of its question pass, row tiles per workgroup of the row pass (fvta_attn_{shared,pool}_bwd_plan; host only,
+        simiMatrix 1-3; the warp changes none)"""
+        return self._words(self._sym + "_bwd_plan", ("rows", "tsplit", "channels", "tiles_per_wg"))
+
+    def _check_inputs(self, rows, rows_mask, hq, qmask, index):
+        assert tuple(rows.shape) == self._rows and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
+        assert index.is_cuda and index.dtype == torch.int32 and index.is_contiguous() and tuple(index.shape) == self._index
+        assert rows_mask is None or (rows_mask.dtype == torch.uint8 and tuple(rows_mask.shape) == self._rows[:3])
+        assert qmask is None or (qmask.dtype == torch.uint8 and tuple(qmask.shape) == (self.NQ, self.JQ))
+
+    def _run(self, train, rows, rows_mask, hq, qmask, index, W, b, want_logits, warp=None, want_scale=False):
+        """the forward call: -> (h_a [NQ,w], a_logits [NQ,K,positions,JQ] | None), under the warp also scale
+        [NQ,positions] | None.  train: leaves in self.saved (allocated on first use) what backward() reads.
+        warp: (energy, lq, WH_b, WC_W, WC_b), which the entry points under the time warp take between the others"""
+        self._check_inputs(rows, rows_mask, hq, qmask, index)
+        if warp is not None:
+            energy, lq, WH_b, WC_W, WC_b = warp
+            assert tuple(energy.shape) == (self._rows[0], self._rows[2]) and tuple(lq.shape) == (self.NQ, self.w)
+            assert WH_b.numel() == self.w and WC_W.numel() == self.w and WC_b.numel() == 1
+        if train and getattr(self, "saved", None) is None:
+            self.saved = _sized(self, self._sym + self._tw + "_saved_bytes", self._what + self._sep + "saved: ")
+        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
+        a_logits = torch.empty(self.NQ, self.K, self._TO, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
+        scale = torch.empty(self.NQ, self._TO, device=self.dev, dtype=torch.float32) if want_scale else None
+        W = _f32c(W) if train else W                                 # (inference: simiMatrix 4 takes no W)
+        e, q, wb, sc = [], [], [], []                                # the warp's arguments, where the entry points take them
+        if warp is not None:
+            e, q, sc = [ptr(_f32c(energy))], [ptr(_f32c(lq))], [ptr(scale)]
+            wb = [ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b))]
+        args = [ptr(_f32c(rows)), ptr(rows_mask)] + e + [ptr(_f32c(hq)), ptr(qmask)] + q + [ptr(index), ptr(W), ptr(b)] + wb + \
+            [ptr(h_a), ptr(a_logits)] + sc + ([ptr(self.saved)] if train else []) + [ptr(self.work)]
+        self._call(self._sym + "_fwd" + self._tw + ("_train" if train else ""), *args)
+        return (h_a, a_logits) if warp is None else (h_a, a_logits, scale)
+
+    def forward(self, rows, rows_mask, hq, qmask, index, W, b, want_logits=False):
+        """the inference call (fvta_attn_{shared,pool}_fwd): nothing kept"""
+        return self._run(False, rows, rows_mask, hq, qmask, index, W, b, want_logits)
+
+    def forward_train(self, rows, rows_mask, hq, qmask, index, W, b, want_logits=False):
+        """forward() -- the same bits -- that leaves in self.saved (allocated on first use) what backward() reads
+        (fvta_attn_{shared,pool}_fwd_train; simiMatrix 1-3)"""
+        return self._run(True, rows, rows_mask, hq, qmask, index, W, b, want_logits)
+
+    def _begin_backward(self, rows, rows_mask, hq, qmask, index, d_h_a, d_rows, d_hq, *grads):
+        """what every backward starts with: the saved state, the workspace (allocated on first use), the arguments"""
+        if getattr(self, "saved", None) is None:
+            raise _lib.FvtaError(self._what + ": backward() needs a forward_train() first")
+        if getattr(self, "work_bwd", None) is None:
+            self.work_bwd = _sized(self, self._sym + self._tw + "_bwd_workspace_bytes",
+                                   self._what + self._sep + "backward workspace: ")
+        self._check_inputs(rows, rows_mask, hq, qmask, index)
+        assert tuple(d_rows.shape) == self._rows and tuple(d_hq.shape) == (self.NQ, self.JQ, self.w)
+        assert tuple(d_h_a.shape) == (self.NQ, self.w)
+        for t in (d_rows, d_hq) + grads:
+            assert t.is_contiguous() and t.dtype == torch.float32, "gradient outputs are written in place"
+
+    def backward(self, rows, rows_mask, hq, qmask, index, W, b, d_h_a, d_rows, d_hq, dW, db):
+        """After forward_train() with the same arguments: d_rows (the rows' shape) and d_hq [NQ,JQ,w] are overwritten, dW
+        [F] and db [1] accumulated into (fvta_attn_{shared,pool}_bwd).  Its workspace is allocated on first use."""
+        self._begin_backward(rows, rows_mask, hq, qmask, index, d_h_a, d_rows, d_hq, dW, db)
+        self._call(self._sym + "_bwd", ptr(_f32c(rows)), ptr(rows_mask), ptr(_f32c(hq)), ptr(qmask), ptr(index), ptr(_f32c(W)),
+                   ptr(b), ptr(_f32c(d_h_a)), ptr(self.saved), ptr(d_rows), ptr(d_hq), ptr(_f32c(dW)), ptr(_f32c(db)),
+                   ptr(self.work_bwd))
+
+
+class _WarpedAlbumAttention(_AlbumAttention):
+    """_AlbumAttention under the time warp: the descriptor with the warp's type and window, the energy of the rows
+    (album_energy: once per album set), and forward calls that take it with the warp's other arguments."""
+    _tw, _sep = "_tw", ", "
+
+    def _album_energy(self, rows, WH_W, WC_W):
+        assert tuple(rows.shape) == self._rows
+        assert WH_W.numel() >= self.w * self.w and WC_W.numel() == self.w
+        energy = torch.empty(self._rows[0], self._rows[2], device=self.dev, dtype=torch.float32)
+        self._call(self._sym + "_energy", ptr(_f32c(rows)), ptr(_f32c(WH_W)), ptr(_f32c(WC_W)), ptr(energy), ptr(self.work))
+        return energy
+
+    def forward(self, rows, rows_mask, energy, hq, qmask, lq, index, W, b, WH_b, WC_W, WC_b, want_logits=False, want_scale=False):
+        """-> (h_a [NQ,w], a_logits [NQ,K,positions,JQ] | None, scale [NQ,positions] | None); scale is TimeWarp's, per
+        question over its positions (T, or the M*JX of its albums laid end to end)"""
+        return self._run(False, rows, rows_mask, hq, qmask, index, W, b, want_logits, (energy, lq, WH_b, WC_W, WC_b), want_scale)
+
+    def forward_train(self, rows, rows_mask, energy, hq, qmask, lq, index, W, b, WH_b, WC_W, WC_b, want_logits=False,
+                      want_scale=False):
+        """forward() -- the same bits -- that leaves in self.saved (allocated on first use) what backward() reads
+        (fvta_attn_shared_fwd_tw_train; simiMatrix 1-3)"""
+        return self._run(True, rows, rows_mask, hq, qmask, index, W, b, want_logits, (energy, lq, WH_b, WC_W, WC_b), want_scale)
+
+
+class SharedFocalAttention(_AlbumAttention):
     """attention_3d (model_v2.py:210-298) of NQ questions over A albums whose context rows are held ONCE: hinfo [A,K,T,w],
     hmask [A,K,T], hq [NQ,JQ,w], qmask [NQ,JQ], album [NQ] int32 on the device (validate it with check_album_index before
     the upload).  Question i gets FocalAttention's result on album[i]'s rows.  forward() is the inference call
@@ -313,66 +433,9 @@ class SharedFocalAttention:
     d_hinfo stays [A,K,T,w]: the sum of the per-question row gradients over each album's questions."""
 
     def __init__(self, A, NQ, K, T, JQ, w, simi, add_tanh):
-        self.lib = _lib.load()
-        self.dev = require_gpu()
         self.A, self.NQ, self.K, self.T, self.JQ, self.w = int(A), int(NQ), int(K), int(T), int(JQ), int(w)
-        self.desc = _lib.AttnSharedDesc(self.A, self.NQ, self.K, self.T, self.JQ, self.w, int(simi), int(bool(add_tanh)))
-        nb = self.lib.fvta_attn_shared_workspace_bytes(ctypes.byref(self.desc))
-        if nb == 0:
-            raise _lib.FvtaError("shared attention: " + self.lib.fvta_last_error().decode())
-        self.work = _bytes(nb, self.dev)
-
-    def plan(self):
-        """{G, rows, tsplit, rows_per_split}: questions per group, rows per logits tile, T splits of the weighted sum and
-        the rows of one split (host only)"""
-        out = (ctypes.c_int32 * 4)()
-        check(self.lib.fvta_attn_shared_plan(ctypes.byref(self.desc), out), "fvta_attn_shared_plan")
-        return dict(zip(("G", "rows", "tsplit", "rows_per_split"), (int(v) for v in out)))
-
-    def forward(self, hinfo, hmask, hq, qmask, album, W, b, want_logits=False):
-        assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
-        assert album.is_cuda and album.dtype == torch.int32 and album.is_contiguous() and tuple(album.shape) == (self.NQ,)
-        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
-        a_logits = torch.empty(self.NQ, self.K, self.T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
-        check(self.lib.fvta_attn_shared_fwd(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)), ptr(qmask),
-                                            ptr(album), ptr(W), ptr(b), ptr(h_a), ptr(a_logits), ptr(self.work),
-                                            stream_ptr()), "fvta_attn_shared_fwd")
-        return h_a, a_logits
-
-    def bwd_plan(self):
-        """{rows, tsplit, channels, tiles_per_wg}: rows per tile of the backward's row pass, T splits and channels per slice
-        of its question pass, row tiles per workgroup of the row pass (fvta_attn_shared_bwd_plan; host only, simiMatrix 1-3)"""
-        out = (ctypes.c_int32 * 4)()
-        check(self.lib.fvta_attn_shared_bwd_plan(ctypes.byref(self.desc), out), "fvta_attn_shared_bwd_plan")
-        return dict(zip(("rows", "tsplit", "channels", "tiles_per_wg"), (int(v) for v in out)))
-
-    def forward_train(self, hinfo, hmask, hq, qmask, album, W, b, want_logits=False):
-        """forward() -- the same bits -- that leaves in self.saved (allocated on first use) what backward() reads
-        (fvta_attn_shared_fwd_train; simiMatrix 1-3)"""
-        assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
-        assert album.is_cuda and album.dtype == torch.int32 and album.is_contiguous() and tuple(album.shape) == (self.NQ,)
-        if getattr(self, "saved", None) is None:
-            self.saved = _sized(self, "fvta_attn_shared_saved_bytes", "shared attention saved: ")
-        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
-        a_logits = torch.empty(self.NQ, self.K, self.T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
-        check(self.lib.fvta_attn_shared_fwd_train(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)),
-                                                  ptr(qmask), ptr(album), ptr(_f32c(W)), ptr(b), ptr(h_a), ptr(a_logits),
-                                                  ptr(self.saved), ptr(self.work), stream_ptr()), "fvta_attn_shared_fwd_train")
-        return h_a, a_logits
-
-    def backward(self, hinfo, hmask, hq, qmask, album, W, b, d_h_a, d_hinfo, d_hq, dW, db):
-        """After forward_train() with the same arguments: d_hinfo [A,K,T,w] and d_hq [NQ,JQ,w] are overwritten, dW [F] and
-        db [1] accumulated into (fvta_attn_shared_bwd).  Its workspace is allocated on first use."""
-        if getattr(self, "saved", None) is None:
-            raise _lib.FvtaError("shared attention: backward() needs a forward_train() first")
-        if getattr(self, "work_bwd", None) is None:
-            self.work_bwd = _sized(self, "fvta_attn_shared_bwd_workspace_bytes", "shared attention backward workspace: ")
-        assert tuple(d_hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(d_hq.shape) == (self.NQ, self.JQ, self.w)
-        assert tuple(d_h_a.shape) == (self.NQ, self.w)
-        check(self.lib.fvta_attn_shared_bwd(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)), ptr(qmask),
-                                            ptr(album), ptr(_f32c(W)), ptr(b), ptr(_f32c(d_h_a)), ptr(self.saved),
-                                            ptr(_f32c(d_hinfo)), ptr(_f32c(d_hq)), ptr(_f32c(dW)), ptr(_f32c(db)),
-                                            ptr(self.work_bwd), stream_ptr()), "fvta_attn_shared_bwd")
+        desc = _lib.AttnSharedDesc(self.A, self.NQ, self.K, self.T, self.JQ, self.w, int(simi), int(bool(add_tanh)))
+        self._setup("fvta_attn_shared", "shared attention", desc, (self.A, self.K, self.T, self.w), (self.NQ,), self.T)
 
 
 # ------------------------------------------------------------------ attention, per-question album lists over one pool
@@ -408,7 +471,7 @@ def check_album_lists(albums, P, masked):
     return t.to(torch.int32).contiguous()
 
 
-class PooledFocalAttention:
+class PooledFocalAttention(_AlbumAttention):
     """attention_3d (model_v2.py:210-298) of NQ questions that each list M albums of ONE pool of P encoded albums: pool
     [P,K,JX,w], pool_mask [P,K,JX], hq [NQ,JQ,w], qmask [NQ,JQ], albums [NQ,M] int32 on the device (validate them with
     check_album_lists before the upload; -1 is an empty slot).  Question i gets FocalAttention's result on its albums' rows
@@ -417,176 +480,45 @@ class PooledFocalAttention:
     the per-question row gradients over every (question, slot) that refers to the album."""
 
     def __init__(self, P, NQ, M, K, JX, JQ, w, simi, add_tanh):
-        self.lib = _lib.load()
-        self.dev = require_gpu()
         self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w = int(P), int(NQ), int(M), int(K), int(JX), int(JQ), int(w)
-        self.desc = _lib.AttnPoolDesc(self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w, int(simi), int(bool(add_tanh)))
-        nb = self.lib.fvta_attn_pool_workspace_bytes(ctypes.byref(self.desc))
-        if nb == 0:
-            raise _lib.FvtaError("pooled attention: " + self.lib.fvta_last_error().decode())
-        self.work = _bytes(nb, self.dev)
-
-    def plan(self):
-        """{G, rows, tsplit, rows_per_split}: references per group, rows per logits tile, splits of JX in the weighted sum
-        and the rows of one split (host only)"""
-        out = (ctypes.c_int32 * 4)()
-        check(self.lib.fvta_attn_pool_plan(ctypes.byref(self.desc), out), "fvta_attn_pool_plan")
-        return dict(zip(("G", "rows", "tsplit", "rows_per_split"), (int(v) for v in out)))
-
-    def forward(self, pool, pool_mask, hq, qmask, albums, W, b, want_logits=False):
-        assert tuple(pool.shape) == (self.P, self.K, self.JX, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
-        assert albums.is_cuda and albums.dtype == torch.int32 and albums.is_contiguous() and \
-            tuple(albums.shape) == (self.NQ, self.M)
-        assert pool_mask is None or (pool_mask.dtype == torch.uint8 and tuple(pool_mask.shape) == (self.P, self.K, self.JX))
-        assert qmask is None or (qmask.dtype == torch.uint8 and tuple(qmask.shape) == (self.NQ, self.JQ))
-        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
-        a_logits = torch.empty(self.NQ, self.K, self.M * self.JX, self.JQ, device=self.dev, dtype=torch.float32) \
-            if want_logits else None
-        check(self.lib.fvta_attn_pool_fwd(ctypes.byref(self.desc), ptr(_f32c(pool)), ptr(pool_mask), ptr(_f32c(hq)), ptr(qmask),
-                                          ptr(albums), ptr(W), ptr(b), ptr(h_a), ptr(a_logits), ptr(self.work),
-                                          stream_ptr()), "fvta_attn_pool_fwd")
-        return h_a, a_logits
-
-    def _check_inputs(self, pool, pool_mask, hq, qmask, albums):
-        assert tuple(pool.shape) == (self.P, self.K, self.JX, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
-        assert albums.is_cuda and albums.dtype == torch.int32 and albums.is_contiguous() and \
-            tuple(albums.shape) == (self.NQ, self.M)
-        assert pool_mask is None or (pool_mask.dtype == torch.uint8 and tuple(pool_mask.shape) == (self.P, self.K, self.JX))
-        assert qmask is None or (qmask.dtype == torch.uint8 and tuple(qmask.shape) == (self.NQ, self.JQ))
-
-    def bwd_plan(self):
-        """{rows, tsplit, channels, tiles_per_wg}: rows per tile of the backward's row pass, JX splits and channels per
-        slice of its question pass, row tiles per workgroup of the row pass (fvta_attn_pool_bwd_plan; host only,
-        simiMatrix 1-3)"""
-        out = (ctypes.c_int32 * 4)()
-        check(self.lib.fvta_attn_pool_bwd_plan(ctypes.byref(self.desc), out), "fvta_attn_pool_bwd_plan")
-        return dict(zip(("rows", "tsplit", "channels", "tiles_per_wg"), (int(v) for v in out)))
-
-    def forward_train(self, pool, pool_mask, hq, qmask, albums, W, b, want_logits=False):
-        """forward() -- the same bits -- that leaves in self.saved (allocated on first use) what backward() reads
-        (fvta_attn_pool_fwd_train; simiMatrix 1-3)"""
-        self._check_inputs(pool, pool_mask, hq, qmask, albums)
-        if getattr(self, "saved", None) is None:
-            self.saved = _sized(self, "fvta_attn_pool_saved_bytes", "pooled attention saved: ")
-        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
-        a_logits = torch.empty(self.NQ, self.K, self.M * self.JX, self.JQ, device=self.dev, dtype=torch.float32) \
-            if want_logits else None
-        check(self.lib.fvta_attn_pool_fwd_train(ctypes.byref(self.desc), ptr(_f32c(pool)), ptr(pool_mask), ptr(_f32c(hq)),
-                                                ptr(qmask), ptr(albums), ptr(_f32c(W)), ptr(b), ptr(h_a), ptr(a_logits),
-                                                ptr(self.saved), ptr(self.work), stream_ptr()), "fvta_attn_pool_fwd_train")
-        return h_a, a_logits
-
-    def backward(self, pool, pool_mask, hq, qmask, albums, W, b, d_h_a, d_pool, d_hq, dW, db):
-        """After forward_train() with the same arguments: d_pool [P,K,JX,w] and d_hq [NQ,JQ,w] are overwritten, dW [F] and
-        db [1] accumulated into (fvta_attn_pool_bwd).  Its workspace is allocated on first use."""
-        if getattr(self, "saved", None) is None:
-            raise _lib.FvtaError("pooled attention: backward() needs a forward_train() first")
-        if getattr(self, "work_bwd", None) is None:
-            self.work_bwd = _sized(self, "fvta_attn_pool_bwd_workspace_bytes", "pooled attention backward workspace: ")
-        self._check_inputs(pool, pool_mask, hq, qmask, albums)
-        assert tuple(d_pool.shape) == (self.P, self.K, self.JX, self.w) and tuple(d_hq.shape) == (self.NQ, self.JQ, self.w)
-        assert tuple(d_h_a.shape) == (self.NQ, self.w)
-        assert d_pool.is_contiguous() and d_hq.is_contiguous() and dW.is_contiguous() and db.is_contiguous()
-        check(self.lib.fvta_attn_pool_bwd(ctypes.byref(self.desc), ptr(_f32c(pool)), ptr(pool_mask), ptr(_f32c(hq)), ptr(qmask),
-                                          ptr(albums), ptr(_f32c(W)), ptr(b), ptr(_f32c(d_h_a)), ptr(self.saved),
-                                          ptr(d_pool), ptr(d_hq), ptr(dW), ptr(db), ptr(self.work_bwd), stream_ptr()),
-              "fvta_attn_pool_bwd")
+        desc = _lib.AttnPoolDesc(self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w, int(simi), int(bool(add_tanh)))
+        self._setup("fvta_attn_pool", "pooled attention", desc, (self.P, self.K, self.JX, self.w), (self.NQ, self.M),
+                    self.M * self.JX)
 
 
-class SharedWarpedFocalAttention:
+class SharedWarpedFocalAttention(_WarpedAlbumAttention):
     """SharedFocalAttention.forward under the time warp (model_v2.py:953-1009, use_time_warp without use_time_warp_att;
     forward only): question i gets FocalAttention's result on TimeWarp's warp of (hinfo[album[i]], lq[i]), from the rows
     [A,K,T,w] as they are held -- the warp is one scalar per (question, position), and the only term of it that reads the
     rows, the energy e [A,T], belongs to the album: album_energy() computes it once per album set, forward() takes it."""
 
     def __init__(self, A, NQ, K, T, JQ, w, simi, add_tanh, warp_type, window_t=3.0):
-        self.lib = _lib.load()
-        self.dev = require_gpu()
         self.A, self.NQ, self.K, self.T, self.JQ, self.w = int(A), int(NQ), int(K), int(T), int(JQ), int(w)
         shape = _lib.AttnSharedDesc(self.A, self.NQ, self.K, self.T, self.JQ, self.w, int(simi), int(bool(add_tanh)))
-        self.desc = _lib.AttnSharedTwDesc(shape, int(warp_type), float(window_t))
-        nb = self.lib.fvta_attn_shared_tw_workspace_bytes(ctypes.byref(self.desc))
-        if nb == 0:                      # (a bad warp type: "time warping type not implemented", model_v2.py:341)
-            raise _lib.FvtaError("shared attention under the time warp: " + self.lib.fvta_last_error().decode())
-        self.work = _bytes(nb, self.dev)
+        self._setup("fvta_attn_shared", "shared attention under the time warp",
+                    _lib.AttnSharedTwDesc(shape, int(warp_type), float(window_t)), (self.A, self.K, self.T, self.w), (self.NQ,), self.T)
 
     def album_energy(self, hinfo, WH_W, WC_W):
         """e [A,T] = sum_k sum_c (WH_W[:w] WC_W)[c] hinfo[a,k,t,c]^2 (fvta_attn_shared_energy): a function of the rows and
         of WH/W, WC/W alone -- keep it as long as those stay what they are.  WH_W [2w,w] or its first w rows, WC_W [w]"""
-        assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w)
-        assert WH_W.numel() >= self.w * self.w and WC_W.numel() == self.w
-        energy = torch.empty(self.A, self.T, device=self.dev, dtype=torch.float32)
-        check(self.lib.fvta_attn_shared_energy(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(_f32c(WH_W)), ptr(_f32c(WC_W)),
-                                               ptr(energy), ptr(self.work), stream_ptr()), "fvta_attn_shared_energy")
-        return energy
-
-    def forward(self, hinfo, hmask, energy, hq, qmask, lq, album, W, b, WH_b, WC_W, WC_b, want_logits=False, want_scale=False):
-        """-> (h_a [NQ,w], a_logits [NQ,K,T,JQ] | None, scale [NQ,T] | None); scale is TimeWarp's, per question"""
-        assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
-        assert tuple(energy.shape) == (self.A, self.T) and tuple(lq.shape) == (self.NQ, self.w)
-        assert album.is_cuda and album.dtype == torch.int32 and album.is_contiguous() and tuple(album.shape) == (self.NQ,)
-        assert WH_b.numel() == self.w and WC_W.numel() == self.w and WC_b.numel() == 1
-        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
-        a_logits = torch.empty(self.NQ, self.K, self.T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
-        scale = torch.empty(self.NQ, self.T, device=self.dev, dtype=torch.float32) if want_scale else None
-        check(self.lib.fvta_attn_shared_fwd_tw(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(energy)),
-                                               ptr(_f32c(hq)), ptr(qmask), ptr(_f32c(lq)), ptr(album), ptr(W), ptr(b),
-                                               ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)), ptr(h_a), ptr(a_logits),
-                                               ptr(scale), ptr(self.work), stream_ptr()), "fvta_attn_shared_fwd_tw")
-        return h_a, a_logits, scale
-
-    def bwd_plan(self):
-        """{rows, tsplit, channels, tiles_per_wg} of the backward's row and question passes: the words of
-        SharedFocalAttention.bwd_plan() for the same shape -- the warp changes none (host only, simiMatrix 1-3)"""
-        out = (ctypes.c_int32 * 4)()
-        check(self.lib.fvta_attn_shared_bwd_plan(ctypes.byref(self.desc.shape), out), "fvta_attn_shared_bwd_plan")
-        return dict(zip(("rows", "tsplit", "channels", "tiles_per_wg"), (int(v) for v in out)))
-
-    def forward_train(self, hinfo, hmask, energy, hq, qmask, lq, album, W, b, WH_b, WC_W, WC_b, want_logits=False,
-                      want_scale=False):
-        """forward() -- the same bits -- that leaves in self.saved (allocated on first use) what backward() reads
-        (fvta_attn_shared_fwd_tw_train; simiMatrix 1-3)"""
-        assert tuple(hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
-        assert tuple(energy.shape) == (self.A, self.T) and tuple(lq.shape) == (self.NQ, self.w)
-        assert album.is_cuda and album.dtype == torch.int32 and album.is_contiguous() and tuple(album.shape) == (self.NQ,)
-        assert WH_b.numel() == self.w and WC_W.numel() == self.w and WC_b.numel() == 1
-        if getattr(self, "saved", None) is None:
-            self.saved = _sized(self, "fvta_attn_shared_tw_saved_bytes", "shared attention under the time warp, saved: ")
-        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
-        a_logits = torch.empty(self.NQ, self.K, self.T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
-        scale = torch.empty(self.NQ, self.T, device=self.dev, dtype=torch.float32) if want_scale else None
-        check(self.lib.fvta_attn_shared_fwd_tw_train(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(energy)),
-                                                     ptr(_f32c(hq)), ptr(qmask), ptr(_f32c(lq)), ptr(album), ptr(_f32c(W)), ptr(b),
-                                                     ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)), ptr(h_a),
-                                                     ptr(a_logits), ptr(scale), ptr(self.saved), ptr(self.work), stream_ptr()),
-              "fvta_attn_shared_fwd_tw_train")
-        return h_a, a_logits, scale
+        return self._album_energy(hinfo, WH_W, WC_W)
 
     def backward(self, hinfo, hmask, hq, qmask, lq, album, W, b, WH_W, WH_b, WC_W, WC_b, d_h_a, d_hinfo, d_hq, d_lq, dW, db,
                  dWH_W, dWH_b, dWC_W, dWC_b):
         """After forward_train() with the same arguments: d_hinfo [A,K,T,w], d_hq [NQ,JQ,w] and d_lq [NQ,w] are overwritten;
         dW [F], db [1], dWH_W (its first w rows, [w,w]), dWH_b [w], dWC_W [w] and dWC_b [1] accumulated into
         (fvta_attn_shared_bwd_tw).  WH_W: [2w,w] or its first w rows.  Its workspace is allocated on first use."""
-        if getattr(self, "saved", None) is None:
-            raise _lib.FvtaError("shared attention under the time warp: backward() needs a forward_train() first")
-        if getattr(self, "work_bwd", None) is None:
-            self.work_bwd = _sized(self, "fvta_attn_shared_tw_bwd_workspace_bytes",
-                                   "shared attention under the time warp, backward workspace: ")
-        assert tuple(d_hinfo.shape) == (self.A, self.K, self.T, self.w) and tuple(d_hq.shape) == (self.NQ, self.JQ, self.w)
-        assert tuple(d_h_a.shape) == (self.NQ, self.w) and tuple(d_lq.shape) == (self.NQ, self.w)
+        self._begin_backward(hinfo, hmask, hq, qmask, album, d_h_a, d_hinfo, d_hq, d_lq, dW, db, dWH_W, dWH_b, dWC_W, dWC_b)
+        assert tuple(d_lq.shape) == (self.NQ, self.w)
         assert WH_W.numel() >= self.w * self.w and dWH_W.numel() >= self.w * self.w
         assert dWH_b.numel() == self.w and dWC_W.numel() == self.w and dWC_b.numel() == 1
-        for t in (d_hinfo, d_hq, d_lq, dW, db, dWH_W, dWH_b, dWC_W, dWC_b):
-            assert t.is_contiguous() and t.dtype == torch.float32, "gradient outputs are written in place"
-        check(self.lib.fvta_attn_shared_bwd_tw(ctypes.byref(self.desc), ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)), ptr(qmask),
-                                               ptr(_f32c(lq)), ptr(album), ptr(_f32c(W)), ptr(b), ptr(_f32c(WH_W)),
-                                               ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)), ptr(_f32c(d_h_a)),
-                                               ptr(self.saved), ptr(d_hinfo), ptr(d_hq), ptr(d_lq), ptr(dW), ptr(db), ptr(dWH_W),
-                                               ptr(dWH_b), ptr(dWC_W), ptr(dWC_b), ptr(self.work_bwd), stream_ptr()),
-              "fvta_attn_shared_bwd_tw")
+        self._call("fvta_attn_shared_bwd_tw", ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)), ptr(qmask), ptr(_f32c(lq)), ptr(album),
+                   ptr(_f32c(W)), ptr(b), ptr(_f32c(WH_W)), ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)),
+                   ptr(_f32c(d_h_a)), ptr(self.saved), ptr(d_hinfo), ptr(d_hq), ptr(d_lq), ptr(dW), ptr(db), ptr(dWH_W),
+                   ptr(dWH_b), ptr(dWC_W), ptr(dWC_b), ptr(self.work_bwd))
 
 
-class PooledWarpedFocalAttention:
+class PooledWarpedFocalAttention(_WarpedAlbumAttention):
     """PooledFocalAttention.forward under the time warp (model_v2.py:953-1009, use_time_warp without use_time_warp_att;
     forward only): question i gets FocalAttention's result on TimeWarp's warp of (its albums' rows laid end to end, lq[i]),
     from the pool [P,K,JX,w] as it is held -- the warp is one scalar per (question, position t = m*JX + j of its M*JX), and
@@ -594,52 +526,20 @@ class PooledWarpedFocalAttention:
     once per pool, forward() takes it.  The count of a position runs over the question's whole M*JX positions."""
 
     def __init__(self, P, NQ, M, K, JX, JQ, w, simi, add_tanh, warp_type, window_t=3.0):
-        self.lib = _lib.load()
-        self.dev = require_gpu()
         self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w = int(P), int(NQ), int(M), int(K), int(JX), int(JQ), int(w)
         shape = _lib.AttnPoolDesc(self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w, int(simi), int(bool(add_tanh)))
-        self.desc = _lib.AttnPoolTwDesc(shape, int(warp_type), float(window_t))
-        nb = self.lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(self.desc))
-        if nb == 0:                      # (a bad warp type: "time warping type not implemented", model_v2.py:341)
-            raise _lib.FvtaError("pooled attention under the time warp: " + self.lib.fvta_last_error().decode())
-        self.work = _bytes(nb, self.dev)
-
-    def plan(self):
-        """PooledFocalAttention.plan()'s words for the same shape -- the warp changes none (host only)"""
-        out = (ctypes.c_int32 * 4)()
-        check(self.lib.fvta_attn_pool_plan(ctypes.byref(self.desc.shape), out), "fvta_attn_pool_plan")
-        return dict(zip(("G", "rows", "tsplit", "rows_per_split"), (int(v) for v in out)))
+        self._setup("fvta_attn_pool", "pooled attention under the time warp",
+                    _lib.AttnPoolTwDesc(shape, int(warp_type), float(window_t)), (self.P, self.K, self.JX, self.w),
+                    (self.NQ, self.M), self.M * self.JX)
 
     def album_energy(self, pool, WH_W, WC_W):
         """e [P,JX] = sum_k sum_c (WH_W[:w] WC_W)[c] pool[p,k,j,c]^2 (fvta_attn_pool_energy): a function of the pool and of
         WH/W, WC/W alone -- keep it as long as those stay what they are.  WH_W [2w,w] or its first w rows, WC_W [w]"""
-        assert tuple(pool.shape) == (self.P, self.K, self.JX, self.w)
-        assert WH_W.numel() >= self.w * self.w and WC_W.numel() == self.w
-        energy = torch.empty(self.P, self.JX, device=self.dev, dtype=torch.float32)
-        check(self.lib.fvta_attn_pool_energy(ctypes.byref(self.desc), ptr(_f32c(pool)), ptr(_f32c(WH_W)), ptr(_f32c(WC_W)),
-                                             ptr(energy), ptr(self.work), stream_ptr()), "fvta_attn_pool_energy")
-        return energy
+        return self._album_energy(pool, WH_W, WC_W)
 
-    def forward(self, pool, pool_mask, energy, hq, qmask, lq, albums, W, b, WH_b, WC_W, WC_b, want_logits=False,
-                want_scale=False):
-        """-> (h_a [NQ,w], a_logits [NQ,K,M*JX,JQ] | None, scale [NQ,M*JX] | None); scale is TimeWarp's on the question's
-        albums laid end to end"""
-        assert tuple(pool.shape) == (self.P, self.K, self.JX, self.w) and tuple(hq.shape) == (self.NQ, self.JQ, self.w)
-        assert tuple(energy.shape) == (self.P, self.JX) and tuple(lq.shape) == (self.NQ, self.w)
-        assert albums.is_cuda and albums.dtype == torch.int32 and albums.is_contiguous() and \
-            tuple(albums.shape) == (self.NQ, self.M)
-        assert pool_mask is None or (pool_mask.dtype == torch.uint8 and tuple(pool_mask.shape) == (self.P, self.K, self.JX))
-        assert qmask is None or (qmask.dtype == torch.uint8 and tuple(qmask.shape) == (self.NQ, self.JQ))
-        assert WH_b.numel() == self.w and WC_W.numel() == self.w and WC_b.numel() == 1
-        T = self.M * self.JX
-        h_a = torch.empty(self.NQ, self.w, device=self.dev, dtype=torch.float32)
-        a_logits = torch.empty(self.NQ, self.K, T, self.JQ, device=self.dev, dtype=torch.float32) if want_logits else None
-        scale = torch.empty(self.NQ, T, device=self.dev, dtype=torch.float32) if want_scale else None
-        check(self.lib.fvta_attn_pool_fwd_tw(ctypes.byref(self.desc), ptr(_f32c(pool)), ptr(pool_mask), ptr(_f32c(energy)),
-                                             ptr(_f32c(hq)), ptr(qmask), ptr(_f32c(lq)), ptr(albums), ptr(W), ptr(b),
-                                             ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)), ptr(h_a), ptr(a_logits),
-                                             ptr(scale), ptr(self.work), stream_ptr()), "fvta_attn_pool_fwd_tw")
-        return h_a, a_logits, scale
+    def forward_train(self, *args, **kwargs):
+        raise NotImplementedError("pooled attention under the time warp: forward only (the library has no training pair)")
+    backward = forward_train
 
 
 def linear_fwd(x, W, b, y, M, din, dout, add_tanh=False, blk=None):

@@ -166,6 +166,10 @@ _SIGS = {
     "fvta_attn_pool_tw_workspace_bytes": (c_size_t, [POINTER(AttnPoolTwDesc)]),
     "fvta_attn_pool_energy": (c_int, [POINTER(AttnPoolTwDesc), P, P, P, P, P, P]),
     "fvta_attn_pool_fwd_tw": (c_int, [POINTER(AttnPoolTwDesc)] + [P] * 17),
+    "fvta_attn_pool_tw_saved_bytes": (c_size_t, [POINTER(AttnPoolTwDesc)]),
+    "fvta_attn_pool_tw_bwd_workspace_bytes": (c_size_t, [POINTER(AttnPoolTwDesc)]),
+    "fvta_attn_pool_fwd_tw_train": (c_int, [POINTER(AttnPoolTwDesc)] + [P] * 18),
+    "fvta_attn_pool_bwd_tw": (c_int, [POINTER(AttnPoolTwDesc)] + [P] * 25),
     "fvta_timewarp_workspace_bytes": (c_size_t, [POINTER(TimewarpDesc)]),
     "fvta_timewarp_fwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P]),
     "fvta_timewarp_bwd": (c_int, [POINTER(TimewarpDesc), P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),

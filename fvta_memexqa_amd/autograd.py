@@ -255,43 +255,59 @@ def pooled_focal_attention(pool, hq, albums, W, b, pool_mask=None, qmask=None, s
     return _AlbumFocalAttention.apply(_c(pool), _c(hq), albums, _c(W), _c(b), pool_mask, qmask, int(simi), bool(add_tanh), True)
 
 
-class _SharedWarpedFocalAttention(torch.autograd.Function):
-    """_AlbumFocalAttention (pooled = False) under the time warp (fvta_attn_shared_fwd_tw_train / fvta_attn_shared_bwd_tw; simiMatrix 1-3):
-    (hinfo [A,K,T,w], hq [NQ,JQ,w], lq [NQ,w], album int32 [NQ] on the device, W [F*w], b [1], WH_W [2w,w] or its first w
-    rows, WH_b [w], WC_W [w], WC_b [1]; masks u8 | None; energy [A,T] | None) -> (h_a [NQ,w], a_logits [NQ,K,T,JQ],
-    scale [NQ,T]).  a_logits and scale are not differentiable.  `energy` is a cached value of the forward alone: the
-    gradient through e reaches hinfo, WH_W and WC_W whether it was given or computed here."""
+class _AlbumWarpedFocalAttention(torch.autograd.Function):
+    """_AlbumFocalAttention under the time warp (simiMatrix 1-3), by the same static word `pooled`:
+    False  (hinfo [A,K,T,w], hq [NQ,JQ,w], lq [NQ,w], album int32 [NQ] on the device, W [F*w], b [1], WH_W [2w,w] or its
+           first w rows, WH_b [w], WC_W [w], WC_b [1]; masks u8 | None; energy [A,T] | None) -> (h_a [NQ,w], a_logits
+           [NQ,K,T,JQ], scale [NQ,T])  (fvta_attn_shared_fwd_tw_train / fvta_attn_shared_bwd_tw)
+    True   (pool [P,K,JX,w], hq, lq, albums int32 [NQ,M] on the device, ...; energy [P,JX] | None) -> (h_a, a_logits
+           [NQ,K,M*JX,JQ], scale [NQ,M*JX])  (fvta_attn_pool_fwd_tw_train / fvta_attn_pool_bwd_tw).  The gradient of pool
+           stays [P,K,JX,w]: the sum over every (question, slot) that refers to the album.
+    a_logits and scale are not differentiable.  `energy` is a cached value of the forward alone: the gradient through e
+    reaches the rows, WH_W and WC_W whether it was given or computed here."""
 
     @staticmethod
-    def forward(ctx, hinfo, hq, lq, album, W, b, WH_W, WH_b, WC_W, WC_b, hmask, qmask, simi, add_tanh, warp_type, window_t,
-                energy):
-        A, K, T, w = hinfo.shape
-        op = ops.SharedWarpedFocalAttention(A, hq.shape[0], K, T, hq.shape[1], w, simi, add_tanh, warp_type, window_t)
+    def forward(ctx, rows, hq, lq, index, W, b, WH_W, WH_b, WC_W, WC_b, rows_mask, qmask, simi, add_tanh, warp_type, window_t,
+                energy, pooled):
+        A, K, T, w = rows.shape
+        if pooled:
+            op = ops.PooledWarpedFocalAttention(A, hq.shape[0], index.shape[1], K, T, hq.shape[1], w, simi, add_tanh, warp_type,
+                                                window_t)
+        else:
+            op = ops.SharedWarpedFocalAttention(A, hq.shape[0], K, T, hq.shape[1], w, simi, add_tanh, warp_type, window_t)
         if energy is None:
-            energy = op.album_energy(hinfo, WH_W, WC_W)
-        h_a, a, scale = op.forward_train(hinfo, hmask, energy, hq, qmask, lq, album, W, b, WH_b, WC_W, WC_b, want_logits=True,
+            energy = op.album_energy(rows, WH_W, WC_W)
+        h_a, a, scale = op.forward_train(rows, rows_mask, energy, hq, qmask, lq, index, W, b, WH_b, WC_W, WC_b, want_logits=True,
                                          want_scale=True)
         ctx.set_materialize_grads(False)
         ctx.mark_non_differentiable(a, scale)
         ctx.op = op
-        ctx.aux = (album, hmask, qmask)
-        ctx.save_for_backward(hinfo, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b)
+        ctx.aux = (index, rows_mask, qmask)
+        ctx.save_for_backward(rows, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b)
         return h_a, a, scale
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_ha, g_a, g_scale):
         if g_ha is None:
-            return (None,) * 17
-        hinfo, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b = ctx.saved_tensors
-        album, hmask, qmask = ctx.aux
-        dh, dq, dlq = torch.empty_like(hinfo), torch.empty_like(hq), torch.empty_like(lq)   # overwritten
+            return (None,) * 18
+        rows, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b = ctx.saved_tensors
+        index, rows_mask, qmask = ctx.aux
+        dh, dq, dlq = torch.empty_like(rows), torch.empty_like(hq), torch.empty_like(lq)   # overwritten
         dW, db, dWH_W, dWH_b, dWC_W, dWC_b = (torch.zeros_like(t) for t in (W, b, WH_W, WH_b, WC_W, WC_b))
-        ctx.op.backward(hinfo, hmask, hq, qmask, lq, album, W, b, WH_W, WH_b, WC_W, WC_b, _c(g_ha), dh, dq, dlq, dW, db, dWH_W,
+        ctx.op.backward(rows, rows_mask, hq, qmask, lq, index, W, b, WH_W, WH_b, WC_W, WC_b, _c(g_ha), dh, dq, dlq, dW, db, dWH_W,
                         dWH_b, dWC_W, dWC_b)
         need = ctx.needs_input_grad
         grads = (dh, dq, dlq, None, dW, db, dWH_W, dWH_b, dWC_W, dWC_b)
-        return tuple(g if n else None for g, n in zip(grads, need[:10])) + (None,) * 7
+        return tuple(g if n else None for g, n in zip(grads, need[:10])) + (None,) * 8
+
+
+def _warped_apply(pooled, rows, hq, lq, index, W, b, WH_W, WH_b, WC_W, WC_b, rows_mask, qmask, simi, add_tanh, warp_type, window_t,
+                  energy):
+    f = lambda t: t.to(torch.float32).contiguous()
+    return _AlbumWarpedFocalAttention.apply(f(rows), f(hq), f(lq), index, f(W), f(b), f(WH_W), f(WH_b), f(WC_W).reshape(-1),
+                                            f(WC_b).reshape(-1), rows_mask, qmask, int(simi), bool(add_tanh), int(warp_type),
+                                            float(window_t), None if energy is None else f(energy.detach()), pooled)
 
 
 def shared_warped_focal_attention(hinfo, hq, lq, album, W, b, WH_W, WH_b, WC_W, WC_b, hmask=None, qmask=None, simi=1,
@@ -301,10 +317,19 @@ def shared_warped_focal_attention(hinfo, hq, lq, album, W, b, WH_W, WH_b, WC_W, 
     if int(simi) == 4:
         raise NotImplementedError("shared_warped_focal_attention: simiMatrix 4 has no shared-context backward; the "
                                   "per-question time_warp + focal_attention on gathered rows cover it")
-    f = lambda t: t.to(torch.float32).contiguous()
-    return _SharedWarpedFocalAttention.apply(f(hinfo), f(hq), f(lq), album, f(W), f(b), f(WH_W), f(WH_b), f(WC_W).reshape(-1),
-                                             f(WC_b).reshape(-1), hmask, qmask, int(simi), bool(add_tanh), int(warp_type),
-                                             float(window_t), None if energy is None else f(energy.detach()))
+    return _warped_apply(False, hinfo, hq, lq, album, W, b, WH_W, WH_b, WC_W, WC_b, hmask, qmask, simi, add_tanh, warp_type,
+                         window_t, energy)
+
+
+def pooled_warped_focal_attention(pool, hq, lq, albums, W, b, WH_W, WH_b, WC_W, WC_b, pool_mask=None, qmask=None, simi=1,
+                                  add_tanh=False, warp_type=1, window_t=3.0, energy=None):
+    """albums: int32 [NQ,M] on the device, validated by the caller (ops.check_album_lists); energy [P,JX] | None; the rest
+    as shared_warped_focal_attention (functional.attention_3d_pooled_warped_raw pads any width)"""
+    if int(simi) == 4:
+        raise NotImplementedError("pooled_warped_focal_attention: simiMatrix 4 has no pooled backward; the per-question "
+                                  "time_warp + focal_attention on gathered rows cover it")
+    return _warped_apply(True, pool, hq, lq, albums, W, b, WH_W, WH_b, WC_W, WC_b, pool_mask, qmask, simi, add_tanh, warp_type,
+                         window_t, energy)
 
 
 class _KeepRank1(torch.autograd.Function):

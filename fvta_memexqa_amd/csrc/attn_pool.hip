@@ -31,7 +31,8 @@
 // stay pooled.  attn_shared_tw_scale_kernel<., true> goes in front and writes scale [NQ,M JX] from energy [P,JX] (a pooled
 // album's, fvta_attn_pool_energy: attn_shared.hip's two energy launches with A = P, T = JX) and the count of the GLOBAL
 // position t = m JX + j; (4) and (6) are the <TW, POOL> instantiations, which read the scale at the reference's slot.  At
-// M = 1 every launch computes what fvta_attn_shared_fwd_tw's does: the same bits.
+// M = 1 every launch computes what fvta_attn_shared_fwd_tw's does: the same bits.  Training under the warp
+// (fvta_attn_pool_fwd_tw_train / fvta_attn_pool_bwd_tw): further down, after the unwarped training pair.
 //
 // This file holds the pooled descriptor's entry points -- thin calls of attn_shared.hip's and attn_shared_bwd.hip's checks
 // and drivers -- and the two kernels of the backward that only the pool has.
@@ -57,6 +58,22 @@
 // Determinism: as attn_shared_bwd.hip.  The one sum whose order depends on data -- d_pool over an album's references --
 // runs in `order`, a function of `albums` alone.  At M = 1 every launch computes what fvta_attn_shared_bwd's does (a sum
 // over one slot starts from 0 + x): the same bits.
+//
+// ================= training over the pool under the time warp (fvta_attn_pool_fwd_tw_train / fvta_attn_pool_bwd_tw) ======
+// The contract of fvta_attn_shared_fwd_tw_train / fvta_attn_shared_bwd_tw over the pooled descriptor.  The forward is
+// sh_forward's <TRAIN, TW, POOL>: `saved` takes the training ShWork's share, then scale / tanh(z) [NQ,M JX], lin
+// [NQ,K,M JX] at the reference's slot, r2 [P,K,JX] at the album's own row.  The backward is shb_backward's <TW, POOL>:
+//   1. prep over M JX;  a. attn_shared_tw_vec_kernel;  2., 3. the <TW, POOL> row and question passes: ds / dx s / dbt
+//      [NQ,K,M JX] at the reference's slot
+//   b. attn_shared_bwd_tw_dz_kernel<POOL>   per question over its M JX positions, the count at the GLOBAL position
+//                                           m JX + j; an empty slot's positions: dz = 0, nothing into dbq, by the slot's
+//                                           own word (qslot < 0) -- no row pass wrote their ds, and zero is their value
+//   c. attn_shared_bwd_tw_de_kernel<POOL>   de[p,j] = sum of dz[q, m JX + j] over album p's references in plan order
+//   d. attn_shared_bwd_tw_energy_kernel     over [P,JX]: d_pool += 2 de v h; an album nobody lists is skipped
+//   3b., 4. the pooled dct and fold;  5. parameters with db left to (e);  e., f. the warp's parameter kernels
+// d_pool holds the attention's row gradient and the energy's term, both summed over every (question, slot) reference in
+// plan order.  No [NQ,K,M JX,w] tensor, no floating-point atomics, no memset, no host wait; at M = 1 the bits of the
+// shared warped pair, `saved` included.
 namespace fvta {
 
 // slot of reference (q, m) in the partials, -1 for an empty slot; the plan's own number, bounded all the same
@@ -209,4 +226,45 @@ extern "C" int fvta_attn_pool_bwd(const fvta_attn_pool_desc* d, const float* poo
   if (int e = sh_open(d, "attn_pool_bwd", s, SH_BWD)) return e;
   FVTA_CHECK_ARG(pool && hq && albums && d_h_a && saved && d_pool && d_hq && dW && db && workspace, "attn_pool_bwd: null pointer");
   return shb_backward(s, true, "attn_pool_bwd", {pool, pool_mask, hq, qmask, d_h_a, saved, d_pool, d_hq, dW, db, workspace, stream_});
+}
+
+// ---- training under the time warp: the warped descriptor through sh_check_tw at SH_BWD, the same two drivers
+extern "C" size_t fvta_attn_pool_tw_saved_bytes(const fvta_attn_pool_tw_desc* d) {
+  ShShape s;
+  if (sh_open_tw(d, "attn_pool_tw_saved_bytes", s, SH_BWD) != FVTA_OK) return 0;
+  return ShTwSaved(s, ShWork(s, nullptr, nullptr), nullptr).bytes;
+}
+
+extern "C" int fvta_attn_pool_fwd_tw_train(const fvta_attn_pool_tw_desc* d, const float* pool, const uint8_t* pool_mask,
+                                           const float* energy, const float* hq, const uint8_t* qmask, const float* lq,
+                                           const int32_t* albums, const float* W, const float* b, const float* WH_b,
+                                           const float* WC_W, const float* WC_b, float* h_a, float* a_logits, float* scale_out,
+                                           void* saved, void* workspace, fvta_stream_t stream_) {
+  ShShape s;
+  if (int e = sh_open_tw(d, "attn_pool_fwd_tw_train", s, SH_BWD)) return e;
+  FVTA_CHECK_ARG(pool && energy && hq && lq && albums && W && WH_b && WC_W && WC_b && h_a && saved && workspace,
+                 "attn_pool_fwd_tw_train: null pointer");
+  const ShWarpCall warp{d->warp_type, d->window_t, energy, lq, WH_b, WC_W, WC_b, scale_out};
+  return sh_forward(s, true, "attn_pool_fwd_tw_train", {pool, pool_mask, hq, qmask, albums, W, b, h_a, a_logits, saved, workspace, stream_},
+                    &warp);
+}
+
+extern "C" size_t fvta_attn_pool_tw_bwd_workspace_bytes(const fvta_attn_pool_tw_desc* d) {
+  ShShape s;
+  return sh_open_tw(d, "attn_pool_tw_bwd_workspace_bytes", s, SH_BWD) == FVTA_OK ? shb_workspace_bytes(s, true, true) : 0;
+}
+
+extern "C" int fvta_attn_pool_bwd_tw(const fvta_attn_pool_tw_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
+                                     const uint8_t* qmask, const float* lq, const int32_t* albums, const float* W, const float* b,
+                                     const float* WH_W, const float* WH_b, const float* WC_W, const float* WC_b, const float* d_h_a,
+                                     const void* saved, float* d_pool, float* d_hq, float* d_lq, float* dW, float* db, float* dWH_W,
+                                     float* dWH_b, float* dWC_W, float* dWC_b, void* workspace, fvta_stream_t stream_) {
+  ShShape s;
+  if (int e = sh_open_tw(d, "attn_pool_bwd_tw", s, SH_BWD)) return e;
+  FVTA_CHECK_ARG(pool && hq && lq && albums && W && WH_W && WH_b && WC_W && WC_b && d_h_a && saved && d_pool && d_hq && d_lq && dW &&
+                     db && dWH_W && dWH_b && dWC_W && dWC_b && workspace,
+                 "attn_pool_bwd_tw: null pointer");
+  const ShBwdWarpCall warp{d->warp_type, d->window_t, lq, WH_W, WH_b, WC_W, WC_b, d_lq, dWH_W, dWH_b, dWC_W, dWC_b};
+  return shb_backward(s, true, "attn_pool_bwd_tw", {pool, pool_mask, hq, qmask, d_h_a, saved, d_pool, d_hq, dW, db, workspace, stream_},
+                      &warp);
 }

@@ -6,7 +6,8 @@
 // instantiations of (4) and (6), further down.  fvta_attn_shared_fwd keeps nothing
 // for a backward; fvta_attn_shared_fwd_train runs the same kernels -- the same bits -- with the ordered plan (3) and the
 // arg-max (4) compiled in, and leaves what attn_shared_bwd.hip reads in the caller-held `saved` (attn_shared_common.h).
-// fvta_attn_shared_fwd_tw_train is that under the time warp: <TRAIN, TW> of (4), which also leaves lin at the arg-max and r2.
+// fvta_attn_shared_fwd_tw_train is that under the time warp: <TRAIN, TW> of (4), which also leaves lin at the arg-max and r2
+// (fvta_attn_pool_fwd_tw_train: <TRAIN, TW, POOL>, lin at the reference's slot, r2 per pooled album).
 //
 // Bilinear form (attn_common.h): x[t,(g,j)] = rs[t] sum_c h[t,c] Qs[g,j,c] + (Rh.h[t] + R2.h[t]^2) + ct[g,j].
 // Launches, all on the caller's stream, none waits for the host:
@@ -338,7 +339,6 @@ int sh_energy(const ShShape& s, const char* who, const float* rows, const float*
 // and nothing else depends on any of the three
 template <bool TRAIN, bool TW, bool POOL>
 static int sh_forward_as(ShShape s, const char* who, const ShFwdCall& c, const ShWarpCall* warp) {
-  static_assert(!(TW && TRAIN && POOL), "training over the pool is not under the time warp");
   hipStream_t st = (hipStream_t)c.stream;
   const ShWork wk = TRAIN ? ShWork(s, c.saved, c.workspace) : ShWork(s, c.workspace);
   ShTwArgs tw{nullptr, nullptr, nullptr};
@@ -383,7 +383,7 @@ static int sh_forward_as(ShShape s, const char* who, const ShFwdCall& c, const S
 
 // <TRAIN, TW, POOL> per entry point: TRAIN = a `saved` to fill, TW = the warp's arguments
 //   fvta_attn_shared_fwd <0,0,0>   _fwd_train <1,0,0>   _fwd_tw <0,1,0>   _fwd_tw_train <1,1,0>
-//   fvta_attn_pool_fwd   <0,0,1>   _fwd_train <1,0,1>   _fwd_tw <0,1,1>   (no <1,1,1>: FVTA_ERR_UNSUPPORTED)
+//   fvta_attn_pool_fwd   <0,0,1>   _fwd_train <1,0,1>   _fwd_tw <0,1,1>   _fwd_tw_train <1,1,1>
 int sh_forward(const ShShape& s, bool pool, const char* who, const ShFwdCall& c, const ShWarpCall* warp) {
   const bool train = c.saved != nullptr;
   if (!pool) {
@@ -391,9 +391,7 @@ int sh_forward(const ShShape& s, bool pool, const char* who, const ShFwdCall& c,
     return train ? sh_forward_as<true, false, false>(s, who, c, warp) : sh_forward_as<false, false, false>(s, who, c, warp);
   }
   if (!warp) return train ? sh_forward_as<true, false, true>(s, who, c, warp) : sh_forward_as<false, false, true>(s, who, c, warp);
-  if (!train) return sh_forward_as<false, true, true>(s, who, c, warp);
-  fvta_set_error("%s: training over the pool is not under the time warp", who);
-  return FVTA_ERR_UNSUPPORTED;
+  return train ? sh_forward_as<true, true, true>(s, who, c, warp) : sh_forward_as<false, true, true>(s, who, c, warp);
 }
 
 }  // namespace fvta

@@ -30,9 +30,10 @@
 // Kernels 1, 4 and 5 are a few lines each around attn_bwd_shared.h's prep body, fold body and parameter pieces -- the one
 // copy attn_bwd.hip runs too; the row and question passes (2, 3), the backward's shape and its workspace stand in
 // attn_shared_bwd_kernels.h, with the compile-time word POOL for training over per-question album lists (attn_pool.hip).
-// ONE driver makes the launches for the three backward entry points: shb_backward, near the end of this file.
+// ONE driver makes the launches for the four backward entry points: shb_backward, near the end of this file.
 // Under the time warp (fvta_attn_shared_bwd_tw, the gradient of fvta_attn_shared_fwd_tw_train): the TW instantiations of
-// (2) and (3) and six small kernels of the warp's own backward, at the end of this file.
+// (2) and (3) and six small kernels of the warp's own backward, at the end of this file.  Over the pool under the warp
+// (fvta_attn_pool_bwd_tw): <TW, POOL> of (2) and (3), and of the warp's kernels (b) and (c) their POOL instantiations.
 #include "attn_shared_bwd_kernels.h"
 #include "timewarp_common.h"
 
@@ -99,6 +100,8 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_params_kernel(ShShape s, 
 // The attention saw the rows s h, s[q,t] = tanh(z[q,t]) cnt(t), z = e[a,t] + K (s0 + WC.lq[q]).  The row and question passes
 // above run as their TW instantiations and leave ds [NQ,K,T]; from there the warp's own backward, which never meets a
 // [NQ,K,T,w] tensor either: s is one scalar per (question, position) and only e reads the rows.
+// POOL: z[q, m T + j] = e[albums[q,m], j] + K (s0 + WC.lq[q]) over the question's TO = M T positions, the count that of the
+// global position; (b) runs over TO, (c) sums an album's references, (d) - (f) are what they are with A = P, T = JX.
 //   a. attn_shared_tw_vec_kernel        v = WH[:w] WC (attn_shared.hip's)
 //   b. attn_shared_bwd_tw_dz_kernel     per question: dz[q,t] = cnt(t) (1 - tanh(z)^2) sum_k ds[q,k,t] (k in index order),
 //                                       Dq[q] = K sum_t dz[q,t] by a fixed tree, d_lq[q] = Dq[q] WC; dbq[q] = sum dbt
@@ -110,10 +113,12 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_params_kernel(ShShape s, 
 //   e. attn_shared_bwd_tw_dv_kernel     dv = the partials in index order; ds0 = sum_q Dq[q]; db += sum_q dbq[q]
 //   f. attn_shared_bwd_tw_params_kernel dWH_W[:w] += dv (x) WC, dWH_b += ds0 WC, dWC_W += WH^T dv + ds0 b_WH + Dq^T lq,
 //                                       dWC_b += ds0
+// Over the pool (fvta_attn_pool_bwd_tw) these arrays stand past the pooled backward's dctq (PoolBwdWork), and what is per
+// question runs over its TO = M T positions; de stays per pooled album.  Not pooled, TO = T: every address is what it was
 struct ShBwdTwWork {
   ShBwdWork base;
-  float *ds, *dxs, *dbt;  // [NQ,K,T]
-  float* dz;        // [NQ,T]
+  float *ds, *dxs, *dbt;  // [NQ,K,TO]
+  float* dz;        // [NQ,TO]
   float* de;        // [A,T]
   float* Dq;        // [NQ]  K sum_t dz
   float* dbq;       // [NQ]  sum_{k,t} dbt
@@ -123,16 +128,16 @@ struct ShBwdTwWork {
   float* ds0;       // [1]
   int ewg;
   size_t bytes;
-  ShBwdTwWork(const ShShape& s, const ShBwdShape& b, void* p) : base(s, b, p) {
+  ShBwdTwWork(const ShShape& s, const ShBwdShape& b, void* p, bool pool = false) : base(s, b, p) {
     FvtaCarver c(p);
-    c.off = base.bytes;
+    c.off = pool ? PoolBwdWork(s, b, p).bytes : base.bytes;
     const size_t nk = (size_t)s.NQ * s.K;
     const int64_t waves = ((int64_t)s.A * s.T + 3) / 4;
     ewg = (int)(waves < SHB_E_WGS ? waves : SHB_E_WGS);
-    ds = c.take<float>(nk * s.T);
-    dxs = c.take<float>(nk * s.T);
-    dbt = c.take<float>(nk * s.T);
-    dz = c.take<float>((size_t)s.NQ * s.T);
+    ds = c.take<float>(nk * s.TO);
+    dxs = c.take<float>(nk * s.TO);
+    dbt = c.take<float>(nk * s.TO);
+    dz = c.take<float>((size_t)s.NQ * s.TO);
     de = c.take<float>((size_t)s.A * s.T);
     Dq = c.take<float>((size_t)s.NQ);
     dbq = c.take<float>((size_t)s.NQ);
@@ -159,12 +164,22 @@ __device__ __forceinline__ float shb_block_tree_sum(float v) {
 }
 
 // ---- b.  grid NQ, 256 threads
-__global__ __launch_bounds__(256) void attn_shared_bwd_tw_dz_kernel(ShShape s, int warp_type, int win, const float* __restrict__ tz,
-                                                                   const float* __restrict__ WC, ShBwdTwWork wk,
-                                                                   float* __restrict__ d_lq) {
-  const int q = blockIdx.x, tid = threadIdx.x, T = s.T, K = s.K;
+// POOL: over the question's TO = M T positions, the count that of the GLOBAL position t = m T + j, as the forward's scale
+// kernel takes it.  No row pass visits the positions of an empty slot (qslot < 0: the plan's word for albums[q,m] < 0), so
+// their ds / dbt hold whatever the workspace held: they are not read.  dz = 0 there is the true value -- an empty slot is
+// T zero rows and ds a dot product with them -- and dbt's share is 0 for the same reason
+template <bool POOL>
+__global__ __launch_bounds__(256) void attn_shared_bwd_tw_dz_kernel(ShShape s, const int* __restrict__ qslot, int warp_type, int win,
+                                                                   const float* __restrict__ tz, const float* __restrict__ WC,
+                                                                   ShBwdTwWork wk, float* __restrict__ d_lq) {
+  const int q = blockIdx.x, tid = threadIdx.x, T = sh_positions<POOL>(s), K = s.K;
   float acc = 0.f, accb = 0.f;
   for (int t = tid; t < T; t += 256) {
+    if constexpr (POOL)
+      if (qslot[(size_t)q * s.M + t / s.T] < 0) {
+        wk.dz[(size_t)q * T + t] = 0.f;
+        continue;
+      }
     float sum = 0.f;
     for (int k = 0; k < K; ++k) {
       sum += wk.ds[((size_t)q * K + k) * T + t];
@@ -185,15 +200,19 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_tw_dz_kernel(ShShape s, i
 }
 
 // ---- c.  grid (A, ceil(T / 256)), 256 threads
+// POOL: over the pooled album's references in plan order (ascending id q M + m), each read at its slot of its question's
+// TO positions; a question that lists the album twice stands twice in the sum
+template <bool POOL>
 __global__ __launch_bounds__(256) void attn_shared_bwd_tw_de_kernel(ShShape s, ShWork sv, ShBwdTwWork wk) {
   const int a = blockIdx.x, t = blockIdx.y * 256 + threadIdx.x;
   if (t >= s.T) return;
-  const int q0 = min(max(sv.astart[a], 0), s.NQ), nqa = min(sv.acnt[a], s.NQ - q0);
+  const int TP = sh_positions<POOL>(s), NRF = POOL ? s.NR : s.NQ;
+  const int q0 = min(max(sv.astart[a], 0), NRF), nqa = min(sv.acnt[a], NRF - q0);
   float acc = 0.f;
   for (int qi = 0; qi < nqa; ++qi) {
-    int q = sv.order[q0 + qi];
-    q = q < 0 ? 0 : (q >= s.NQ ? s.NQ - 1 : q);
-    acc += wk.dz[(size_t)q * s.T + t];
+    int ref = sv.order[q0 + qi];
+    ref = ref < 0 ? 0 : (ref >= NRF ? NRF - 1 : ref);
+    acc += wk.dz[(size_t)sh_ref_q<POOL>(s, ref) * TP + sh_ref_off<POOL>(s, ref) + t];
   }
   wk.de[(size_t)a * s.T + t] = acc;
 }
@@ -325,17 +344,18 @@ static void shb_launch_q(const ShShape& s, const ShBwdShape& bs, const ShWork& s
 }
 
 // ---- the backward driver: the five launches of the header (1 prep, 2 rows, 3 question pass, 4 fold, 5 parameters) for
-// fvta_attn_shared_bwd <TW = 0, POOL = 0>, fvta_attn_shared_bwd_tw <1, 0> and fvta_attn_pool_bwd <0, 1>, with
+// fvta_attn_shared_bwd <TW = 0, POOL = 0>, fvta_attn_shared_bwd_tw <1, 0>, fvta_attn_pool_bwd <0, 1> and
+// fvta_attn_pool_bwd_tw <1, 1>, with
 //   TW    the warp's own kernels (a .. f above) around them, and db left to (e)
 //   POOL  3b attn_pool_bwd_dct_kernel in front of the fold, and the pooled fold (attn_pool.hip)
+// and both at once: the POOL instantiations of (b) and (c), the rest as it is -- (d) runs over [P,JX]
 template <bool TW, bool POOL>
 static int shb_backward_as(ShShape s, const char* who, const ShBwdCall& c, const ShBwdWarpCall* warp) {
-  static_assert(!(TW && POOL), "the pooled backward is not under the time warp");
   hipStream_t st = (hipStream_t)c.stream;
   s.use_mask = (c.rows_mask && c.qmask) ? 1 : 0;
   const ShBwdShape bs = shb_shape(s);
   const ShWork sv(s, const_cast<void*>(c.saved), nullptr);
-  const ShBwdTwWork tw(s, bs, c.workspace);  // (what it carves past `base` is the TW call's alone: its workspace is larger)
+  const ShBwdTwWork tw(s, bs, c.workspace, POOL);  // (what it carves past `base` is the TW calls' alone: their workspace is larger)
   const ShBwdWork& wk = tw.base;
   ShBwdTwArgs ta{};
   const float* tz = nullptr;
@@ -351,9 +371,9 @@ static int shb_backward_as(ShShape s, const char* who, const ShBwdCall& c, const
   shb_launch_rows<TW, POOL>(s, bs, sv, wk, c.rows, c.d_h_a, c.d_rows, ta, st);
   shb_launch_q<TW, POOL>(s, bs, sv, wk, c.rows, TW ? (const float*)tw.dxs : nullptr, st);
   if constexpr (TW) {
-    hipLaunchKernelGGL(attn_shared_bwd_tw_dz_kernel, dim3(s.NQ), dim3(256), 0, st, s, warp->warp_type, (int)ceilf(warp->window_t), tz,
-                       warp->WC_W, tw, warp->d_lq);
-    hipLaunchKernelGGL(attn_shared_bwd_tw_de_kernel, dim3(s.A, (s.T + 255) / 256), dim3(256), 0, st, s, sv, tw);
+    hipLaunchKernelGGL(attn_shared_bwd_tw_dz_kernel<POOL>, dim3(s.NQ), dim3(256), 0, st, s, (const int*)sv.qslot, warp->warp_type,
+                       (int)ceilf(warp->window_t), tz, warp->WC_W, tw, warp->d_lq);
+    hipLaunchKernelGGL(attn_shared_bwd_tw_de_kernel<POOL>, dim3(s.A, (s.T + 255) / 256), dim3(256), 0, st, s, sv, tw);
     const dim3 egrid((unsigned)tw.ewg);
     switch (s.w <= 256 ? 1 : s.w / 256) {
       case 1: hipLaunchKernelGGL(attn_shared_bwd_tw_energy_kernel<1>, egrid, dim3(256), 0, st, s, sv, tw, c.rows, c.d_rows); break;
@@ -383,12 +403,13 @@ static int shb_backward_as(ShShape s, const char* who, const ShBwdCall& c, const
 }
 
 int shb_backward(const ShShape& s, bool pool, const char* who, const ShBwdCall& c, const ShBwdWarpCall* warp) {
-  if (pool) return shb_backward_as<false, true>(s, who, c, nullptr);
+  if (pool) return warp ? shb_backward_as<true, true>(s, who, c, warp) : shb_backward_as<false, true>(s, who, c, nullptr);
   return warp ? shb_backward_as<true, false>(s, who, c, warp) : shb_backward_as<false, false>(s, who, c, nullptr);
 }
 
-size_t shb_workspace_bytes(const ShShape& s, bool pool) {
+size_t shb_workspace_bytes(const ShShape& s, bool pool, bool warp) {
   const ShBwdShape b = shb_shape(s);
+  if (warp) return ShBwdTwWork(s, b, nullptr, pool).bytes;
   return pool ? PoolBwdWork(s, b, nullptr).bytes : ShBwdWork(s, b, nullptr).bytes;
 }
 
@@ -430,7 +451,7 @@ extern "C" int fvta_attn_shared_bwd(const fvta_attn_shared_desc* d, const float*
 extern "C" size_t fvta_attn_shared_tw_bwd_workspace_bytes(const fvta_attn_shared_tw_desc* d) {
   ShShape s;
   if (sh_open_tw(d, "attn_shared_tw_bwd_workspace_bytes", s, SH_BWD) != FVTA_OK) return 0;
-  return ShBwdTwWork(s, shb_shape(s), nullptr).bytes;
+  return shb_workspace_bytes(s, false, true);
 }
 
 extern "C" int fvta_attn_shared_bwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinfo, const uint8_t* hmask, const float* hq,

@@ -88,7 +88,8 @@ struct PoolBwdWork {
   }
 };
 
-// ---- the backward driver (attn_shared_bwd.hip): fvta_attn_shared_bwd, fvta_attn_shared_bwd_tw and fvta_attn_pool_bwd end in it
+// ---- the backward driver (attn_shared_bwd.hip): fvta_attn_shared_bwd, fvta_attn_shared_bwd_tw, fvta_attn_pool_bwd and
+// fvta_attn_pool_bwd_tw end in it
 struct ShBwdCall {
   const float* rows;          // hinfo [A,K,T,w] / pool [P,K,JX,w]
   const uint8_t* rows_mask;
@@ -107,8 +108,8 @@ struct ShBwdWarpCall {        // under the time warp: the warp's parameters, the
   float *d_lq, *dWH_W, *dWH_b, *dWC_W, *dWC_b;
 };
 int shb_backward(const ShShape& s, bool pool, const char* who, const ShBwdCall& c, const ShBwdWarpCall* warp = nullptr);
-// the workspace of the backward not under the warp; TR, TS, SHB_CS, tpw (the *_bwd_workspace_bytes / *_bwd_plan pairs)
-size_t shb_workspace_bytes(const ShShape& s, bool pool);
+// the backward's workspace, `warp`: under the time warp; TR, TS, SHB_CS, tpw (the *_bwd_workspace_bytes / *_bwd_plan pairs)
+size_t shb_workspace_bytes(const ShShape& s, bool pool, bool warp = false);
 int shb_plan(const ShShape& s, const char* who, int32_t out[4]);
 
 // attn_pool.hip.  3b: grid NQ, 64 threads; 4: grid (NQ, ceil(w / 256), JZ), 256 threads
@@ -126,7 +127,7 @@ __global__ __launch_bounds__(1024) void attn_shared_bwd_prep_kernel(ShShape s, S
 __global__ __launch_bounds__(256) void attn_shared_bwd_params_kernel(ShShape s, ShBwdShape bs, ShBwdWork wk,
                                                                     float* __restrict__ dW, float* __restrict__ db);
 
-// what the row and question passes take under the time warp: the forward's saved pieces, and three arrays [NQ,K,T] of the
+// what the row and question passes take under the time warp: the forward's saved pieces, and three arrays [NQ,K,TO] of the
 // backward's workspace: ds (the gradient of the scale, per k), dx s (the question pass multiplies the rows by it), dbt (the
 // row's term of db, see the row pass)
 struct ShBwdTwArgs {
@@ -149,15 +150,15 @@ __device__ __forceinline__ float* shb_tw_d2() {
 // (k, t) -- two softmaxes -- so sum dx = sum damax (1 - x^2) = - sum damax x^2 under tanh and 0 without.  The warped rows
 // are up to cmax times the rows, damax is of order 1 where db is of order 1e-3, and the plain sum kept the fp32 noise of
 // that cancellation (1e-5 at w = 512); dbt [NQ,K,T] = - damax x^2 has none to cancel.  d ct per (question, j) stays dx
-// POOL (compile-time, not under the warp): the loop runs over the pooled album's references; reference q M + m reads
-// question q's scalars and d_h_a, and amax / jmax and writes dx at positions m T + t of q's TO.  A question that lists the
-// album twice stands twice in the loop
+// POOL (compile-time): the loop runs over the pooled album's references; reference q M + m reads question q's scalars and
+// d_h_a, and amax / jmax and writes dx at positions m T + t of q's TO.  A question that lists the album twice stands twice
+// in the loop.  TW and POOL: scale, lin, ds, dx s and dbt are per question over its TO positions too, read and written at
+// the same m T + t; r2 stays the album's own row
 template <int TPR, int CPT, int RPT, bool TW, bool POOL = false>
 __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, ShBwdShape bs, ShWork sv, ShBwdWork wk,
                                                                   const float* __restrict__ hinfo,
                                                                   const float* __restrict__ d_h_a,
                                                                   float* __restrict__ d_hinfo, ShBwdTwArgs tw) {
-  static_assert(!(TW && POOL), "the pooled backward is not under the time warp");
   constexpr int RH = 256 / TPR, TR = RH * RPT;
   constexpr int WPR = TPR >= 64 ? TPR / 64 : 1;  // waves that share a row
   __shared__ float s_dot[4][TR], s_pr[TR], s_dx[TR];
@@ -233,7 +234,7 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, Sh
           }
           const size_t qk = (size_t)q * K + k, at = qk * TP + off + t;  // (q, k, the reference's position t)
           const float M = sv.M[qk], am = sv.amax[at];
-          if constexpr (TW) sc = tw.scale[(size_t)q * T + t];
+          if constexpr (TW) sc = tw.scale[(size_t)q * TP + off + t];
           pr = expf(am - M) * wk.coef[qk];
           // pr = 0: a masked row beside valid ones (its g.h may be anything), or r underflowed (then ds is 0 as well)
           if (pr != 0.f && M != FVTA_NEG) {
@@ -244,11 +245,11 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, Sh
           j = min((int)sv.jmax[at], JP - 1);
           wk.dx[at] = dx;
           if constexpr (TW) {  // (pr = 0 beside a g.h that may be anything: no product with it)
-            tw.dbt[qk * T + t] = dbt;
+            tw.dbt[at] = dbt;
             float ds = pr != 0.f ? pr * gh : 0.f;
-            if (dx != 0.f) ds += dx * (tw.lin[qk * T + t] + 2.f * sc * tw.r2[(size_t)ak * T + t]);
-            tw.ds[qk * T + t] = ds;
-            tw.dxs[qk * T + t] = dx * sc;
+            if (dx != 0.f) ds += dx * (tw.lin[at] + 2.f * sc * tw.r2[(size_t)ak * T + t]);
+            tw.ds[at] = ds;
+            tw.dxs[at] = dx * sc;
           }
         }
         if constexpr (TW) {
@@ -314,13 +315,12 @@ __global__ __launch_bounds__(256) void attn_shared_bwd_rows_kernel(ShShape s, Sh
 }
 
 // ---- question pass.  grid ngmax TS nsl, 64 threads: lane = (question g of the group, 4 of the slice's 32 channels)
-// TW (compile-time): the rows entered as s h: dQs takes dx s (dxs [NQ,K,T], the row pass's), d ct dx as it is
+// TW (compile-time): the rows entered as s h: dQs takes dx s (dxs [NQ,K,TO], the row pass's), d ct dx as it is
 // POOL (compile-time): a lane group stands for a REFERENCE of the group's pooled album: dx / jmax are read at the
 // reference's positions of its question; the partials stay per (group, split) and the pooled fold adds a question's slots
 template <int G, bool TW, bool POOL = false>
 __global__ __launch_bounds__(64) void attn_shared_bwd_q_kernel(ShShape s, ShBwdShape bs, ShWork sv, ShBwdWork wk,
                                                               const float* __restrict__ hinfo, const float* __restrict__ dxs) {
-  static_assert(!(TW && POOL), "the pooled backward is not under the time warp");
   constexpr int JP = SH_BN / G, C4 = SHB_CS / 4;
   __shared__ f32x4 s_acc[SH_BN][C4];
   __shared__ float s_dct[SH_BN];
@@ -348,7 +348,7 @@ __global__ __launch_bounds__(64) void attn_shared_bwd_q_kernel(ShShape s, ShBwdS
     for (int k = 0; k < K; ++k) {
       const float* __restrict__ hrow = hinfo + ((size_t)a * K + k) * T * w + sl * SHB_CS + 4 * c4;
       const float* __restrict__ dxp = wk.dx + ((size_t)q * K + k) * TP + off;
-      const float* __restrict__ dsp = TW ? dxs + ((size_t)q * K + k) * T : nullptr;
+      const float* __restrict__ dsp = TW ? dxs + ((size_t)q * K + k) * TP + off : nullptr;
       const uint8_t* __restrict__ jp = sv.jmax + ((size_t)q * K + k) * TP + off;
       for (int t4 = tb + 4 * part; t4 < te; t4 += 4 * rep) {  // four rows in flight
         float dx[4], dm[TW ? 4 : 1];

@@ -134,20 +134,22 @@ struct ShWork {
   }
 };
 
-// Training under the time warp (fvta_attn_shared_fwd_tw_train): `saved` is the training ShWork's share, then these four.
-// The backward (fvta_attn_shared_bwd_tw) reads them; none is the size of the rows.
+// Training under the time warp (fvta_attn_shared_fwd_tw_train, fvta_attn_pool_fwd_tw_train): `saved` is the training
+// ShWork's share, then these four.  The backward (fvta_attn_shared_bwd_tw, fvta_attn_pool_bwd_tw) reads them; none is the
+// size of the rows.  The first three are per question over its TO positions (the pooled call: M T, a reference's at its
+// slot; else TO = T); r2 belongs to the rows
 struct ShTwSaved {
-  float* scale;  // [NQ,T]   s = tanh(z) cnt(t)
-  float* tz;     // [NQ,T]   tanh(z): cnt(t) >= 1 does not divide out of s exactly
-  float* lin;    // [NQ,K,T] h.Qs[q,j] + Rh.h at j = jmax[q,k,t], before the scale enters
-  float* r2;     // [A,K,T]  R2.h^2
+  float* scale;  // [NQ,TO]   s = tanh(z) cnt(t)
+  float* tz;     // [NQ,TO]   tanh(z): cnt(t) >= 1 does not divide out of s exactly
+  float* lin;    // [NQ,K,TO] h.Qs[q,j] + Rh.h at j = jmax[q,k,t], before the scale enters
+  float* r2;     // [A,K,T]   R2.h^2
   size_t bytes;  // of the whole `saved`
   ShTwSaved(const ShShape& s, const ShWork& wk, void* saved) {
     FvtaCarver c(saved);
     c.off = wk.saved_bytes;
-    scale = c.take<float>((size_t)s.NQ * s.T);
-    tz = c.take<float>((size_t)s.NQ * s.T);
-    lin = c.take<float>((size_t)s.NQ * s.K * s.T);
+    scale = c.take<float>((size_t)s.NQ * s.TO);
+    tz = c.take<float>((size_t)s.NQ * s.TO);
+    lin = c.take<float>((size_t)s.NQ * s.K * s.TO);
     r2 = c.take<float>((size_t)s.A * s.K * s.T);
     bytes = c.off;
   }

@@ -133,7 +133,8 @@ __global__ __launch_bounds__(SH_PLAN_NT) void attn_shared_plan_kernel(ShShape s,
 
 // ---- logits.  grid ngmax * K * ntile, 256 threads
 // TRAIN: also the FIRST arg-max j of every row's maximum -> jmax [NQ,K,T] -- POOL: [NQ,K,M T], at the reference's slot --
-// (compile-time: the inference kernel is unchanged)
+// (compile-time: the inference kernel is unchanged).  TRAIN and TW: lin beside jmax, at the same address; r2 [A,K,T] at the
+// album's own row, whichever reference's group computes it
 // TW (compile-time too; tw_scale [NQ,T] -- POOL: [NQ,M T], read at the reference's slot -- else unused): the logits of the WARPED rows h' = s h, s = tw_scale[q,t], from the
 // rows as they are held.  The scalar goes through the bilinear form: x = s (h.Qs + Rh.h) + s^2 (R2.h^2) + ct, cosine
 // x = (h.Qn) s rsqrt(max(s^2 |h|^2, 1e-12)) -- the row pass keeps Rh.h and R2.h^2 (cosine: the raw sum h^2) apart, and
@@ -150,7 +151,6 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
   // TW: s_rt holds Rh.h, s_r2 R2.h^2 (cosine: sum h^2); s_sc, s_s2 the factor of the product and the addend per (question, row)
   __shared__ float s_r2[TW ? SH_R : 1], s_sc[TW ? G : 1][TW ? SH_R : 1], s_s2[TW ? G : 1][TW ? SH_R : 1];
   __shared__ int s_q[G], s_o[POOL ? G : 1];  // a column block's question and -- POOL -- its slot's first position
-  static_assert(!(POOL && TRAIN && TW), "the pooled training call is not under the time warp");
   __shared__ uint8_t s_hv[SH_R], s_cv[SH_BN];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int tile = blockIdx.x % s.ntile, k = (blockIdx.x / s.ntile) % s.K, grp = blockIdx.x / (s.ntile * s.K);
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
             float lv = (mine == jm && jm != 255) ? acc + s_rt[mma.row_of(i, r)] : 0.f;
 #pragma unroll
             for (int o = 16; o > 0; o >>= 1) lv += __shfl_xor(lv, o, 64);
-            if (mma.l31 == r && q >= 0 && t < T) tw.lin[((size_t)q * K + k) * T + t] = lv;
+            if (mma.l31 == r && q >= 0 && t < T) tw.lin[at_of(q, mma.col_of(jn) / JP, t)] = lv;
           }
         }
       }

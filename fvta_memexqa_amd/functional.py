@@ -349,7 +349,7 @@ def attention_3d_shared_warped_raw(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W,
 
 
 def attention_3d_pooled_warped_raw(pool, hq, albums, lq, W, b, WH_W, WH_b, WC_W, WC_b, pool_mask=None, hq_mask=None,
-                                   simiMatrix=1, add_tanh=False, warp_type=1, window_t=3.0, energy=None):
+                                   simiMatrix=1, add_tanh=False, warp_type=1, window_t=3.0, energy=None, differentiable=False):
     """attention_3d_pooled_raw under the time warp (use_time_warp without use_time_warp_att): pool [P,K,JX,w] held once,
     hq [NQ,JQ,w], albums [NQ,M] as attention_3d_pooled_raw takes them, lq [NQ,w] the questions' last states, W / b as
     attention_raw, the warp's weights as time_warp_raw -> (h_a [NQ,w], a_logits [NQ,K,M*JX,JQ], scale [NQ,M*JX]): for
@@ -357,18 +357,30 @@ def attention_3d_pooled_warped_raw(pool, hq, albums, lq, W, b, WH_W, WH_b, WC_W,
     A position's count runs over the question's whole M*JX positions (a band, past or future crosses slot boundaries).
     Neither the [NQ,K,M*JX,w] context nor its warp is built: the warp is one scalar per (question, position), applied
     inside the kernels (fvta_attn_pool_fwd_tw).  energy [P,JX]: album_energy of (pool, WH_W, WC_W), None computes it on the
-    spot.  Forward-only: with gradient mode on and an argument that requires grad it raises."""
+    spot.
+    differentiable=False (the default) is the inference call, forward only: with gradient mode on and an argument that
+    requires grad it raises, as attention_3d_pooled_raw(differentiable=False) does.
+    differentiable=True goes through autograd.pooled_warped_focal_attention (simiMatrix 1-3; 4 raises NotImplementedError):
+    gradients flow from h_a to pool -- summed over every (question, slot) that names the album, [P,K,JX,w] -- hq, lq, W, b
+    and the warp's four parameters (WH_W's rows w..2w-1 get zeros); a_logits and scale carry none.  A given energy is used
+    as a cached value of the forward; the gradient through e is taken all the same."""
     p = _album_attention_args(
-        pool, hq, albums, W, b, pool_mask, hq_mask, simiMatrix, True, False, None,
-        "attention_3d_pooled_warped_raw is forward-only: call it under torch.no_grad(), or use the "
-        "per-question time_warp + attention_3d (functional.time_warp_raw / attention_raw, nn.TimeWarp / "
-        "nn.FocalAttention3D.forward) on the gathered rows",
+        pool, hq, albums, W, b, pool_mask, hq_mask, simiMatrix, True, differentiable,
+        "attention_3d_pooled_warped_raw(differentiable=True): simiMatrix 4 has no pooled backward; use the "
+        "per-question time_warp_raw + attention_raw on the gathered rows",
+        "attention_3d_pooled_warped_raw is forward-only by default: pass differentiable=True (simiMatrix 1-3), call "
+        "it under torch.no_grad(), or use the per-question time_warp + attention_3d (functional.time_warp_raw / "
+        "attention_raw, nn.TimeWarp / nn.FocalAttention3D.forward) on the gathered rows",
         warp=(lq, WH_W, WH_b, WC_W, WC_b, warp_type, energy))
-    op = ops.PooledWarpedFocalAttention(p.A, p.NQ, p.idx.shape[1], p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh, warp_type,
-                                        float(window_t))
-    energy = op.album_energy(p.rows, p.WH, p.WC) if p.energy is None else p.energy
-    h_a, a, scale = op.forward(p.rows, p.rm, energy, p.hq, p.qm, p.lq, p.idx, p.W, p.b, p.WHb, p.WC, p.WCb, want_logits=True,
-                               want_scale=True)
+    if differentiable:     # (the gradients come back sliced to w; WH_W's comes back [2w,w] with zeros below row w)
+        h_a, a, scale = autograd.pooled_warped_focal_attention(p.rows, p.hq, p.lq, p.idx, p.W, p.b, p.WH, p.WHb, p.WC, p.WCb, p.rm,
+                                                               p.qm, simiMatrix, add_tanh, warp_type, float(window_t), p.energy)
+    else:
+        op = ops.PooledWarpedFocalAttention(p.A, p.NQ, p.idx.shape[1], p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh, warp_type,
+                                            float(window_t))
+        energy = op.album_energy(p.rows, p.WH, p.WC) if p.energy is None else p.energy
+        h_a, a, scale = op.forward(p.rows, p.rm, energy, p.hq, p.qm, p.lq, p.idx, p.W, p.b, p.WHb, p.WC, p.WCb, want_logits=True,
+                                   want_scale=True)
     return h_a[:, :p.w].contiguous(), a, scale
 
 

@@ -160,9 +160,9 @@ class FocalAttention3D(_AttLogits):
         end, with no such tensor built.  differentiable=False is the inference call: under gradient mode the parameters
         require grad and the call raises; use it under torch.no_grad().  differentiable=True trains over the pool
         (simiMatrix 1-3; 4 raises NotImplementedError): h_a's gradient reaches pool [P,K,JX,w] -- summed over every
-        (question, slot) that names the album -- hq and the parameters, a_logits carries none.  Not under the time warp:
-        with time_warp it raises NotImplementedError; the per-question route (forward() on nn.TimeWarp's warp of the
-        gathered rows) trains there.
+        (question, slot) that names the album -- hq and the parameters, a_logits carries none.  Under the time warp this
+        call is the inference one: with time_warp and differentiable=True it raises NotImplementedError (the per-question
+        route is not needed: forward_pooled_warped() trains over the pool).
         time_warp (an nn.TimeWarp) with lq [NQ,w], the questions' last states: the attention over each question's albums
         laid end to end and warped for that question -- forward(time_warp(hinfo_i, lq)[0], ...) -- with the pool still
         held once (functional.attention_3d_pooled_warped_raw).  Its parameters and its window buffer are used; energy
@@ -174,8 +174,10 @@ class FocalAttention3D(_AttLogits):
             return functional.attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask, hq_mask, self.simiMatrix, self.add_tanh,
                                                       differentiable=differentiable)
         if differentiable:
-            raise NotImplementedError("forward_pooled: under the time warp this call is the inference one; the per-question "
-                                      "route (forward() on time_warp's warp of each question's gathered rows) trains there")
+            raise NotImplementedError("forward_pooled: under the time warp this call is the inference one; "
+                                      "forward_pooled_warped(pool, hq, albums, lq, time_warp, ...) trains over the pool (as "
+                                      "does the per-question route: forward() on time_warp's warp of each question's "
+                                      "gathered rows)")
         if lq is None:
             raise ValueError("forward_pooled: the time warp needs lq [NQ,w], the questions' last states")
         if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
@@ -185,6 +187,24 @@ class FocalAttention3D(_AttLogits):
         h_a, a, _ = functional.attention_3d_pooled_warped_raw(
             pool, hq, albums, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), pool_mask, hq_mask,
             self.simiMatrix, self.add_tanh, tw.warp_type, tw.window_t(), energy)
+        return h_a, a
+
+    def forward_pooled_warped(self, pool, hq, albums, lq, time_warp, pool_mask=None, hq_mask=None, energy=None):
+        """The training call over the pool under the time warp: forward(time_warp(hinfo_i, lq)[0], hq, ...) for NQ questions
+        that each list M albums of one pool, hinfo_i the question's albums laid end to end -> (h_a [NQ,w], a_logits
+        [NQ,K,M*JX,JQ]); no [NQ,K,M*JX,w] tensor in either direction
+        (functional.attention_3d_pooled_warped_raw(differentiable=True); simiMatrix 1-3, 4 raises NotImplementedError).
+        h_a's gradient reaches pool [P,K,JX,w] (summed over every (question, slot) that names the album), hq, lq, this
+        module's att_logits/{W,b} and time_warp's WH/{W,b}, WC/{W,b}; a_logits carries none.  energy [P,JX]: a cached
+        functional.album_energy, used for the forward; the gradient through it is taken all the same."""
+        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
+            raise ValueError("forward_pooled_warped: lq must be [%d, %d], got %s"
+                             % (hq.shape[0], self.w, tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
+        W, b = self._wb()
+        tw = time_warp
+        h_a, a, _ = functional.attention_3d_pooled_warped_raw(
+            pool, hq, albums, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), pool_mask, hq_mask,
+            self.simiMatrix, self.add_tanh, tw.warp_type, tw.window_t(), energy, differentiable=True)
         return h_a, a
 
 
@@ -209,8 +229,8 @@ class AlbumPool:
     [P,K,JX], held contiguous fp32 / u8 on the device and detached.  Where nn.AlbumMemory keeps one context per distinct
     LIST of albums, this keeps one block of rows per ALBUM and every question names the albums it reads (MemexQA's
     album_ids).  No parameters, no encoder.  It stays a detached inference holder: no gradient reaches the rows it was
-    built from.  Training over a pool goes through nn.FocalAttention3D.forward_pooled(differentiable=True) on a pool
-    tensor that requires grad."""
+    built from.  Training over a pool goes through nn.FocalAttention3D.forward_pooled(differentiable=True) -- under the time
+    warp forward_pooled_warped() -- on a pool tensor that requires grad."""
 
     def __init__(self, pool, pool_mask=None):
         dev = ops.require_gpu()

@@ -403,7 +403,8 @@ class _AlbumAttention:
 
 class _WarpedAlbumAttention(_AlbumAttention):
     """_AlbumAttention under the time warp: the descriptor with the warp's type and window, the energy of the rows
-    (album_energy: once per album set), and forward calls that take it with the warp's other arguments."""
+    (album_energy: once per album set), forward calls that take it with the warp's other arguments, and the backward with
+    the warp's parameters and their gradients."""
     _tw, _sep = "_tw", ", "
 
     def _album_energy(self, rows, WH_W, WC_W):
@@ -421,8 +422,23 @@ class _WarpedAlbumAttention(_AlbumAttention):
     def forward_train(self, rows, rows_mask, energy, hq, qmask, lq, index, W, b, WH_b, WC_W, WC_b, want_logits=False,
                       want_scale=False):
         """forward() -- the same bits -- that leaves in self.saved (allocated on first use) what backward() reads
-        (fvta_attn_shared_fwd_tw_train; simiMatrix 1-3)"""
+        (fvta_attn_{shared,pool}_fwd_tw_train; simiMatrix 1-3)"""
         return self._run(True, rows, rows_mask, hq, qmask, index, W, b, want_logits, (energy, lq, WH_b, WC_W, WC_b), want_scale)
+
+    def backward(self, rows, rows_mask, hq, qmask, lq, index, W, b, WH_W, WH_b, WC_W, WC_b, d_h_a, d_rows, d_hq, d_lq, dW, db,
+                 dWH_W, dWH_b, dWC_W, dWC_b):
+        """After forward_train() with the same arguments: d_rows (the rows' shape: [A,K,T,w], or [P,K,JX,w] -- the sum over
+        every (question, slot) that names the album), d_hq [NQ,JQ,w] and d_lq [NQ,w] are overwritten; dW [F], db [1], dWH_W
+        (its first w rows, [w,w]), dWH_b [w], dWC_W [w] and dWC_b [1] accumulated into (fvta_attn_{shared,pool}_bwd_tw).
+        WH_W: [2w,w] or its first w rows.  Its workspace is allocated on first use."""
+        self._begin_backward(rows, rows_mask, hq, qmask, index, d_h_a, d_rows, d_hq, d_lq, dW, db, dWH_W, dWH_b, dWC_W, dWC_b)
+        assert tuple(d_lq.shape) == (self.NQ, self.w)
+        assert WH_W.numel() >= self.w * self.w and dWH_W.numel() >= self.w * self.w
+        assert dWH_b.numel() == self.w and dWC_W.numel() == self.w and dWC_b.numel() == 1
+        self._call(self._sym + "_bwd_tw", ptr(_f32c(rows)), ptr(rows_mask), ptr(_f32c(hq)), ptr(qmask), ptr(_f32c(lq)), ptr(index),
+                   ptr(_f32c(W)), ptr(b), ptr(_f32c(WH_W)), ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)),
+                   ptr(_f32c(d_h_a)), ptr(self.saved), ptr(d_rows), ptr(d_hq), ptr(d_lq), ptr(dW), ptr(db), ptr(dWH_W),
+                   ptr(dWH_b), ptr(dWC_W), ptr(dWC_b), ptr(self.work_bwd))
 
 
 class SharedFocalAttention(_AlbumAttention):
@@ -487,10 +503,11 @@ class PooledFocalAttention(_AlbumAttention):
 
 
 class SharedWarpedFocalAttention(_WarpedAlbumAttention):
-    """SharedFocalAttention.forward under the time warp (model_v2.py:953-1009, use_time_warp without use_time_warp_att;
-    forward only): question i gets FocalAttention's result on TimeWarp's warp of (hinfo[album[i]], lq[i]), from the rows
+    """SharedFocalAttention under the time warp (model_v2.py:953-1009, use_time_warp without use_time_warp_att):
+    question i gets FocalAttention's result on TimeWarp's warp of (hinfo[album[i]], lq[i]), from the rows
     [A,K,T,w] as they are held -- the warp is one scalar per (question, position), and the only term of it that reads the
-    rows, the energy e [A,T], belongs to the album: album_energy() computes it once per album set, forward() takes it."""
+    rows, the energy e [A,T], belongs to the album: album_energy() computes it once per album set, forward() takes it.
+    forward_train() / backward() are the training pair (simiMatrix 1-3), whose d_hinfo stays [A,K,T,w]."""
 
     def __init__(self, A, NQ, K, T, JQ, w, simi, add_tanh, warp_type, window_t=3.0):
         self.A, self.NQ, self.K, self.T, self.JQ, self.w = int(A), int(NQ), int(K), int(T), int(JQ), int(w)
@@ -503,27 +520,16 @@ class SharedWarpedFocalAttention(_WarpedAlbumAttention):
         of WH/W, WC/W alone -- keep it as long as those stay what they are.  WH_W [2w,w] or its first w rows, WC_W [w]"""
         return self._album_energy(hinfo, WH_W, WC_W)
 
-    def backward(self, hinfo, hmask, hq, qmask, lq, album, W, b, WH_W, WH_b, WC_W, WC_b, d_h_a, d_hinfo, d_hq, d_lq, dW, db,
-                 dWH_W, dWH_b, dWC_W, dWC_b):
-        """After forward_train() with the same arguments: d_hinfo [A,K,T,w], d_hq [NQ,JQ,w] and d_lq [NQ,w] are overwritten;
-        dW [F], db [1], dWH_W (its first w rows, [w,w]), dWH_b [w], dWC_W [w] and dWC_b [1] accumulated into
-        (fvta_attn_shared_bwd_tw).  WH_W: [2w,w] or its first w rows.  Its workspace is allocated on first use."""
-        self._begin_backward(hinfo, hmask, hq, qmask, album, d_h_a, d_hinfo, d_hq, d_lq, dW, db, dWH_W, dWH_b, dWC_W, dWC_b)
-        assert tuple(d_lq.shape) == (self.NQ, self.w)
-        assert WH_W.numel() >= self.w * self.w and dWH_W.numel() >= self.w * self.w
-        assert dWH_b.numel() == self.w and dWC_W.numel() == self.w and dWC_b.numel() == 1
-        self._call("fvta_attn_shared_bwd_tw", ptr(_f32c(hinfo)), ptr(hmask), ptr(_f32c(hq)), ptr(qmask), ptr(_f32c(lq)), ptr(album),
-                   ptr(_f32c(W)), ptr(b), ptr(_f32c(WH_W)), ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b)),
-                   ptr(_f32c(d_h_a)), ptr(self.saved), ptr(d_hinfo), ptr(d_hq), ptr(d_lq), ptr(dW), ptr(db), ptr(dWH_W),
-                   ptr(dWH_b), ptr(dWC_W), ptr(dWC_b), ptr(self.work_bwd))
-
 
 class PooledWarpedFocalAttention(_WarpedAlbumAttention):
-    """PooledFocalAttention.forward under the time warp (model_v2.py:953-1009, use_time_warp without use_time_warp_att;
-    forward only): question i gets FocalAttention's result on TimeWarp's warp of (its albums' rows laid end to end, lq[i]),
+    """PooledFocalAttention under the time warp (model_v2.py:953-1009, use_time_warp without use_time_warp_att):
+    question i gets FocalAttention's result on TimeWarp's warp of (its albums' rows laid end to end, lq[i]),
     from the pool [P,K,JX,w] as it is held -- the warp is one scalar per (question, position t = m*JX + j of its M*JX), and
     the only term of it that reads the rows, the energy e [P,JX], belongs to the pooled album: album_energy() computes it
-    once per pool, forward() takes it.  The count of a position runs over the question's whole M*JX positions."""
+    once per pool, forward() takes it.  The count of a position runs over the question's whole M*JX positions.
+    forward_train() / backward() are the training pair (fvta_attn_pool_fwd_tw_train / fvta_attn_pool_bwd_tw; simiMatrix
+    1-3), whose d_pool stays [P,K,JX,w]: the sum -- the attention's row gradient and the energy's -- over every (question,
+    slot) that refers to the album."""
 
     def __init__(self, P, NQ, M, K, JX, JQ, w, simi, add_tanh, warp_type, window_t=3.0):
         self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w = int(P), int(NQ), int(M), int(K), int(JX), int(JQ), int(w)
@@ -536,10 +542,6 @@ class PooledWarpedFocalAttention(_WarpedAlbumAttention):
         """e [P,JX] = sum_k sum_c (WH_W[:w] WC_W)[c] pool[p,k,j,c]^2 (fvta_attn_pool_energy): a function of the pool and of
         WH/W, WC/W alone -- keep it as long as those stay what they are.  WH_W [2w,w] or its first w rows, WC_W [w]"""
         return self._album_energy(pool, WH_W, WC_W)
-
-    def forward_train(self, *args, **kwargs):
-        raise NotImplementedError("pooled attention under the time warp: forward only (the library has no training pair)")
-    backward = forward_train
 
 
 def linear_fwd(x, W, b, y, M, din, dout, add_tanh=False, blk=None):

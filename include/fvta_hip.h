@@ -292,8 +292,9 @@ int fvta_attn_shared_bwd_tw(const fvta_attn_shared_tw_desc* d, const float* hinf
  * No host synchronisation, no memset, everything on the caller's stream.
  * fvta_attn_pool_plan (host only): out = {G, rows per logits tile, splits of JX in the weighted sum, rows per split}.
  * The time warp (use_time_warp, every warp type) is fvta_attn_pool_fwd_tw further down; training over the pool
- * (simiMatrix 1-3, no time warp) is fvta_attn_pool_fwd_train / fvta_attn_pool_bwd below.  Not here, nor there: training
- * over the pool under the time warp, time_warp_att, shadow rows. */
+ * (simiMatrix 1-3) is fvta_attn_pool_fwd_train / fvta_attn_pool_bwd below, and under the time warp
+ * fvta_attn_pool_fwd_tw_train / fvta_attn_pool_bwd_tw at the end of this section.  Not here, nor there: time_warp_att,
+ * shadow rows. */
 typedef struct fvta_attn_pool_desc {
   int32_t P, NQ, M, K, JX, JQ, w; /* P pooled albums [P,K,JX,w], NQ questions listing M albums each */
   int32_t simi;                   /* 1..4 */
@@ -306,8 +307,9 @@ int fvta_attn_pool_fwd(const fvta_attn_pool_desc* d, const float* pool, const ui
                        const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a,
                        float* a_logits, void* workspace, fvta_stream_t stream);
 
-/* Training over the pool (simiMatrix 1-3, no time warp; with simi 4 the two size queries return 0 and the calls
- * FVTA_ERR_UNSUPPORTED: the per-question route, fvta_attn_fwd / fvta_attn_bwd on gathered rows, covers the cosine form).
+/* Training over the pool (simiMatrix 1-3; under the time warp: the pair at the end of this section; with simi 4 the
+ * two size queries return 0 and the calls FVTA_ERR_UNSUPPORTED: the per-question route, fvta_attn_fwd / fvta_attn_bwd on
+ * gathered rows, covers the cosine form).
  * The contract is fvta_attn_shared_bwd's read per REFERENCE (question i, slot m):
  * fvta_attn_pool_fwd_train: the kernels of fvta_attn_pool_fwd -- h_a and a_logits are its bits -- and, in the
  *   caller-held `saved` (fvta_attn_pool_saved_bytes), what the backward reads: amax and the FIRST arg-max jmax (u8), both
@@ -370,6 +372,44 @@ int fvta_attn_pool_fwd_tw(const fvta_attn_pool_tw_desc* d, const float* pool, co
                           const float* hq, const uint8_t* qmask, const float* lq, const int32_t* albums, const float* W,
                           const float* b, const float* WH_b, const float* WC_W, const float* WC_b, float* h_a,
                           float* a_logits, float* scale_out, void* workspace, fvta_stream_t stream);
+
+/* Training over the pool under the time warp (simiMatrix 1-3, every warp type, no time_warp_att; with simi 4 the two size
+ * queries return 0 and the calls FVTA_ERR_UNSUPPORTED: the per-question route covers it; a warp type outside 1..5: 0 and
+ * FVTA_ERR_INVALID_ARG).  The contract is fvta_attn_shared_fwd_tw_train / fvta_attn_shared_bwd_tw's read per REFERENCE
+ * (question i, slot m), on the descriptor of fvta_attn_pool_fwd_tw:
+ * fvta_attn_pool_fwd_tw_train: the kernels of fvta_attn_pool_fwd_tw -- h_a, a_logits and scale_out are its bits -- with
+ *   the ordered plan of fvta_attn_pool_fwd_train, and in the caller-held `saved` (fvta_attn_pool_tw_saved_bytes) what
+ *   fvta_attn_pool_fwd_train saves, then scale [NQ,M JX], tanh(z) [NQ,M JX], lin [NQ,K,M JX] (h.Qs + Rh.h at the arg-max,
+ *   at the reference's slot) and r2 [P,K,JX] (R2.h^2 of the pooled album's own row).  `workspace`:
+ *   fvta_attn_pool_tw_workspace_bytes.
+ * fvta_attn_pool_bwd_tw: from d_h_a [NQ,w], for question i what fvta_timewarp_fwd -> fvta_attn_fwd -> fvta_attn_bwd
+ *   (accumulate 0, masked rows zero) -> fvta_timewarp_bwd give on (hinfo_i, lq[i], hq[i], ...), hinfo_i the question's M
+ *   albums laid end to end; d_pool[p] is the sum of those row gradients -- the attention's and the energy's 2 de v h --
+ *   over every reference albums[i,m] == p in plan order (ascending id i M + m; a question that lists p twice contributes
+ *   twice), the parameter gradients run over all questions.  d_pool [P,K,JX,w], d_hq [NQ,JQ,w] and d_lq [NQ,w] are
+ *   OVERWRITTEN (an album nobody lists: zeros; a question that lists nothing: d_hq = 0 and d_lq = 0); dW [F], db [1], dWH_W
+ *   (its first w rows, [w,w]; rows w..2w-1 are not touched), dWH_b [w], dWC_W [w] and dWC_b [1] are accumulated into.
+ *   The count of a position is that of the global position m JX + j of the question's M JX: a band, past or future runs
+ *   across slot boundaries.  The positions of an empty slot are zero rows: their dz is 0 and they add nothing to db; the
+ *   kernels take that from the slot itself, never from memory no launch has written.  fvta_attn_shared_bwd_tw's
+ *   deviations and its db carry over; window_t has no gradient; the energy is not an argument.  No [NQ,K,M JX,w]-sized
+ *   buffer in either direction: each d_pool row is written once by the row pass and read and written once more by the
+ *   energy's backward.  No floating-point atomics, fixed summation order: two calls are bitwise equal in all nine outputs,
+ *   and at M = 1 the outputs and `saved` are the shared warped pair's bits for (A = P, T = JX).  No host synchronisation,
+ *   no memset.  `workspace`: fvta_attn_pool_tw_bwd_workspace_bytes (the unwarped pooled backward's, then the warp's
+ *   arrays: ds / dx s / dbt [NQ,K,M JX], dz [NQ,M JX], de [P,JX] and the small vectors). */
+size_t fvta_attn_pool_tw_saved_bytes(const fvta_attn_pool_tw_desc* d);         /* 0 bytes: see fvta_last_error */
+size_t fvta_attn_pool_tw_bwd_workspace_bytes(const fvta_attn_pool_tw_desc* d); /* 0 bytes: see fvta_last_error */
+int fvta_attn_pool_fwd_tw_train(const fvta_attn_pool_tw_desc* d, const float* pool, const uint8_t* pool_mask,
+                                const float* energy, const float* hq, const uint8_t* qmask, const float* lq,
+                                const int32_t* albums, const float* W, const float* b, const float* WH_b, const float* WC_W,
+                                const float* WC_b, float* h_a, float* a_logits, float* scale_out, void* saved, void* workspace,
+                                fvta_stream_t stream);
+int fvta_attn_pool_bwd_tw(const fvta_attn_pool_tw_desc* d, const float* pool, const uint8_t* pool_mask, const float* hq,
+                          const uint8_t* qmask, const float* lq, const int32_t* albums, const float* W, const float* b,
+                          const float* WH_W, const float* WH_b, const float* WC_W, const float* WC_b, const float* d_h_a,
+                          const void* saved, float* d_pool, float* d_hq, float* d_lq, float* dW, float* db, float* dWH_W,
+                          float* dWH_b, float* dWC_W, float* dWC_b, void* workspace, fvta_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * bi-LSTM modality encoders: model_v2.py:652-661 (cells), 667-678 (lengths),

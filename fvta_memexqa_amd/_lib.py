@@ -166,6 +166,9 @@ _SIGS = {
     "fvta_attn_pool_tw_workspace_bytes": (c_size_t, [POINTER(AttnPoolTwDesc)]),
     "fvta_attn_pool_energy": (c_int, [POINTER(AttnPoolTwDesc), P, P, P, P, P, P]),
     "fvta_attn_pool_fwd_tw": (c_int, [POINTER(AttnPoolTwDesc)] + [P] * 17),
+    "fvta_attn_pool_fwd_bf16": (c_int, [POINTER(AttnPoolDesc), P, P, P, P, P, P, P, P, P, P, P]),
+    "fvta_attn_pool_energy_bf16": (c_int, [POINTER(AttnPoolTwDesc), P, P, P, P, P, P]),
+    "fvta_attn_pool_fwd_tw_bf16": (c_int, [POINTER(AttnPoolTwDesc)] + [P] * 17),
     "fvta_attn_pool_tw_saved_bytes": (c_size_t, [POINTER(AttnPoolTwDesc)]),
     "fvta_attn_pool_tw_bwd_workspace_bytes": (c_size_t, [POINTER(AttnPoolTwDesc)]),
     "fvta_attn_pool_fwd_tw_train": (c_int, [POINTER(AttnPoolTwDesc)] + [P] * 18),

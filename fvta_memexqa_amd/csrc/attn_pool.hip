@@ -192,6 +192,52 @@ extern "C" int fvta_attn_pool_fwd_tw(const fvta_attn_pool_tw_desc* d, const floa
                     &warp);
 }
 
+// ---- the pool held in bf16 (raw bits; torch.bfloat16), inference only: the three calls above through the same checks,
+// helpers and driver, with the rows' pointer in ShFwdCall::rows_bf16 / sh_energy's last argument -- the ROW = bf16_t
+// instantiations of the three kernels that read rows (attn_shared_kernels.h).  Those load four bf16 where the fp32 kernels
+// load four floats and widen them in registers, which is exact, and every lane keeps its channels: the results are the
+// fp32 calls' on the widened pool, bit for bit.  Same launches, same workspace (the fp32 size queries serve)
+static int pool_bf16_aligned(const uint16_t* pool, const char* who) {
+  FVTA_CHECK_ARG(((uintptr_t)pool & 7) == 0, "%s: the bf16 pool must be 8-byte aligned", who);
+  return FVTA_OK;
+}
+
+extern "C" int fvta_attn_pool_fwd_bf16(const fvta_attn_pool_desc* d, const uint16_t* pool, const uint8_t* pool_mask, const float* hq,
+                                       const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a,
+                                       float* a_logits, void* workspace, fvta_stream_t stream_) {
+  ShShape s;
+  if (int e = sh_open(d, "attn_pool_fwd_bf16", s)) return e;
+  FVTA_CHECK_ARG(pool && hq && albums && h_a && workspace, "attn_pool_fwd_bf16: null pointer");
+  FVTA_CHECK_ARG(d->simi == 4 || W, "attn_pool_fwd_bf16: simiMatrix %d needs att_logits/W", d->simi);
+  if (int e = pool_bf16_aligned(pool, "attn_pool_fwd_bf16")) return e;
+  return sh_forward(s, true, "attn_pool_fwd_bf16",
+                    {nullptr, pool_mask, hq, qmask, albums, W, b, h_a, a_logits, nullptr, workspace, stream_, pool});
+}
+
+extern "C" int fvta_attn_pool_energy_bf16(const fvta_attn_pool_tw_desc* d, const uint16_t* pool, const float* WH_W, const float* WC_W,
+                                          float* energy, void* workspace, fvta_stream_t stream_) {
+  ShShape s;
+  if (int e = sh_open_tw(d, "attn_pool_energy_bf16", s)) return e;
+  if (int e = pool_bf16_aligned(pool, "attn_pool_energy_bf16")) return e;
+  return sh_energy(s, "attn_pool_energy_bf16", nullptr, WH_W, WC_W, energy, workspace, stream_, pool);
+}
+
+extern "C" int fvta_attn_pool_fwd_tw_bf16(const fvta_attn_pool_tw_desc* d, const uint16_t* pool, const uint8_t* pool_mask,
+                                          const float* energy, const float* hq, const uint8_t* qmask, const float* lq,
+                                          const int32_t* albums, const float* W, const float* b, const float* WH_b, const float* WC_W,
+                                          const float* WC_b, float* h_a, float* a_logits, float* scale_out, void* workspace,
+                                          fvta_stream_t stream_) {
+  ShShape s;
+  if (int e = sh_open_tw(d, "attn_pool_fwd_tw_bf16", s)) return e;
+  FVTA_CHECK_ARG(pool && energy && hq && lq && albums && WH_b && WC_W && WC_b && h_a && workspace,
+                 "attn_pool_fwd_tw_bf16: null pointer");
+  FVTA_CHECK_ARG(d->shape.simi == 4 || W, "attn_pool_fwd_tw_bf16: simiMatrix %d needs att_logits/W", d->shape.simi);
+  if (int e = pool_bf16_aligned(pool, "attn_pool_fwd_tw_bf16")) return e;
+  const ShWarpCall warp{d->warp_type, d->window_t, energy, lq, WH_b, WC_W, WC_b, scale_out};
+  return sh_forward(s, true, "attn_pool_fwd_tw_bf16",
+                    {nullptr, pool_mask, hq, qmask, albums, W, b, h_a, a_logits, nullptr, workspace, stream_, pool}, &warp);
+}
+
 // training: the checks at SH_TRAIN / SH_BWD -- simiMatrix 1-3, and from the backward's entries its grids
 extern "C" size_t fvta_attn_pool_saved_bytes(const fvta_attn_pool_desc* d) {
   ShShape s;

@@ -182,7 +182,9 @@ __global__ __launch_bounds__(256) void attn_shared_tw_vec_kernel(int w, const fl
 }
 
 // e[a,t]: a wave per (a, t), every k (masked rows included, as tw_coef_kernel), in tw_coef_kernel's order.  grid ceil(A T / 4)
-__global__ __launch_bounds__(256) void attn_shared_energy_kernel(ShShape s, const float* __restrict__ hinfo, const float* __restrict__ v,
+// ROW: float, or bf16_t for a pool held in bf16 (attn_shared_kernels.h: the load widens, the sums are the fp32 kernel's)
+template <class ROW>
+__global__ __launch_bounds__(256) void attn_shared_energy_kernel(ShShape s, const ROW* __restrict__ hinfo, const float* __restrict__ v,
                                                                  float* __restrict__ energy) {
   const int64_t pos = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -190,7 +192,7 @@ __global__ __launch_bounds__(256) void attn_shared_energy_kernel(ShShape s, cons
   const int a = (int)(pos / s.T), t = (int)(pos % s.T);
   float acc = 0.f;
   for (int k = 0; k < s.K; ++k) {
-    const float* row = hinfo + (((size_t)a * s.K + k) * s.T + t) * s.w;
+    const ROW* row = hinfo + (((size_t)a * s.K + k) * s.T + t) * s.w;
     for (int c = lane * 4; c < s.w; c += 256) {
       const f32x4 h = ld4(row + c), vv = ld4(v + c);
       const f32x4 p = h * h * vv;
@@ -320,13 +322,16 @@ int sh_plan(const ShShape& s, const char* who, int32_t out[4]) {
 }
 
 int sh_energy(const ShShape& s, const char* who, const float* rows, const float* WH_W, const float* WC_W, float* energy,
-              void* workspace, fvta_stream_t stream) {
-  FVTA_CHECK_ARG(rows && WH_W && WC_W && energy && workspace, "%s: null pointer", who);
+              void* workspace, fvta_stream_t stream, const bf16_t* rows_bf16) {
+  FVTA_CHECK_ARG((rows || rows_bf16) && WH_W && WC_W && energy && workspace, "%s: null pointer", who);
   const ShTwWork tw(s, workspace);
   hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)(((int64_t)s.A * s.T + 3) / 4));
   hipLaunchKernelGGL(attn_shared_tw_vec_kernel, dim3((s.w + 3) / 4), dim3(256), 0, st, s.w, WH_W, WC_W, tw.v);
-  hipLaunchKernelGGL(attn_shared_energy_kernel, dim3((unsigned)(((int64_t)s.A * s.T + 3) / 4)), dim3(256), 0, st, s, rows, tw.v,
-                     energy);
+  if (rows_bf16)
+    hipLaunchKernelGGL(attn_shared_energy_kernel<bf16_t>, grid, dim3(256), 0, st, s, rows_bf16, tw.v, energy);
+  else
+    hipLaunchKernelGGL(attn_shared_energy_kernel<float>, grid, dim3(256), 0, st, s, rows, tw.v, energy);
   FVTA_CHECK_LAUNCH(who);
   return FVTA_OK;
 }
@@ -336,10 +341,13 @@ int sh_energy(const ShShape& s, const char* who, const float* rows, const float*
 //   TRAIN the ordered plan, the arg-max, L / r / u: wk carved from (saved, workspace) -- its share of the workspace is no
 //         larger than the inference call's
 //   POOL  the references' addressing in plan / logits / weighted sum / merge, and the empty slots' launch after the logits
-// and nothing else depends on any of the three
-template <bool TRAIN, bool TW, bool POOL>
+//   ROW   how the logits and the weighted sum load a row: c.rows (float), or c.rows_bf16 (bf16_t; <false, ., true> only)
+// and nothing else depends on any of the four
+template <bool TRAIN, bool TW, bool POOL, class ROW = float>
 static int sh_forward_as(ShShape s, const char* who, const ShFwdCall& c, const ShWarpCall* warp) {
   hipStream_t st = (hipStream_t)c.stream;
+  const ROW* rows;
+  if constexpr (std::is_same<ROW, bf16_t>::value) rows = c.rows_bf16; else rows = c.rows;
   const ShWork wk = TRAIN ? ShWork(s, c.saved, c.workspace) : ShWork(s, c.workspace);
   ShTwArgs tw{nullptr, nullptr, nullptr};
   if constexpr (TW) {
@@ -362,20 +370,20 @@ static int sh_forward_as(ShShape s, const char* who, const ShFwdCall& c, const S
   hipLaunchKernelGGL((attn_shared_plan_kernel<TRAIN, POOL>), dim3(1), dim3(SH_PLAN_NT), 0, st, s, wk, (const int*)c.index);
   const dim3 lgrid((unsigned)((int64_t)s.ngmax * s.K * s.ntile));
   if (s.JP == 32)
-    hipLaunchKernelGGL((attn_shared_logits_kernel<1, TRAIN, TW, POOL>), lgrid, dim3(SH_NT), 0, st, s, wk, c.rows, c.rows_mask, c.qmask,
-                       c.a_logits, tw);
+    hipLaunchKernelGGL((attn_shared_logits_kernel<1, TRAIN, TW, POOL, ROW>), lgrid, dim3(SH_NT), 0, st, s, wk, rows, c.rows_mask,
+                       c.qmask, c.a_logits, tw);
   else
-    hipLaunchKernelGGL((attn_shared_logits_kernel<2, TRAIN, TW, POOL>), lgrid, dim3(SH_NT), 0, st, s, wk, c.rows, c.rows_mask, c.qmask,
-                       c.a_logits, tw);
+    hipLaunchKernelGGL((attn_shared_logits_kernel<2, TRAIN, TW, POOL, ROW>), lgrid, dim3(SH_NT), 0, st, s, wk, rows, c.rows_mask,
+                       c.qmask, c.a_logits, tw);
   if constexpr (POOL)
     hipLaunchKernelGGL(attn_pool_empty_kernel<TRAIN>, dim3(s.NR), dim3(256), 0, st, s, wk, (const int*)c.index, c.a_logits);
   ShShape sq = s;  // the softmaxes run per question over all of its positions
   sq.T = s.TO;
   hipLaunchKernelGGL(attn_shared_softmax_kernel, dim3(s.NQ), dim3(256), 0, st, sq, wk);
   if (s.G == 8)
-    sh_launch_wsum<8, TW, POOL>(s, wk, c.rows, tw.scale, st);
+    sh_launch_wsum<8, TW, POOL, ROW>(s, wk, rows, tw.scale, st);
   else
-    sh_launch_wsum<4, TW, POOL>(s, wk, c.rows, tw.scale, st);
+    sh_launch_wsum<4, TW, POOL, ROW>(s, wk, rows, tw.scale, st);
   hipLaunchKernelGGL((attn_shared_merge_kernel<TRAIN, POOL>), dim3(s.NQ, (s.w + 255) / 256), dim3(256), 0, st, s, wk, c.h_a);
   FVTA_CHECK_LAUNCH(who);
   return FVTA_OK;
@@ -384,8 +392,13 @@ static int sh_forward_as(ShShape s, const char* who, const ShFwdCall& c, const S
 // <TRAIN, TW, POOL> per entry point: TRAIN = a `saved` to fill, TW = the warp's arguments
 //   fvta_attn_shared_fwd <0,0,0>   _fwd_train <1,0,0>   _fwd_tw <0,1,0>   _fwd_tw_train <1,1,0>
 //   fvta_attn_pool_fwd   <0,0,1>   _fwd_train <1,0,1>   _fwd_tw <0,1,1>   _fwd_tw_train <1,1,1>
+//   fvta_attn_pool_fwd_bf16 <0,0,1,bf16_t>   _fwd_tw_bf16 <0,1,1,bf16_t>: the only two with bf16 rows
 int sh_forward(const ShShape& s, bool pool, const char* who, const ShFwdCall& c, const ShWarpCall* warp) {
   const bool train = c.saved != nullptr;
+  if (c.rows_bf16) {
+    FVTA_CHECK_ARG(pool && !train && !c.rows, "%s: bf16 rows are the pooled inference calls' only", who);
+    return warp ? sh_forward_as<false, true, true, bf16_t>(s, who, c, warp) : sh_forward_as<false, false, true, bf16_t>(s, who, c, warp);
+  }
   if (!pool) {
     if (warp) return train ? sh_forward_as<true, true, false>(s, who, c, warp) : sh_forward_as<false, true, false>(s, who, c, warp);
     return train ? sh_forward_as<true, false, false>(s, who, c, warp) : sh_forward_as<false, false, false>(s, who, c, warp);

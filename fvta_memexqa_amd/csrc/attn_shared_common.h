@@ -213,6 +213,9 @@ struct ShFwdCall {
   float *h_a, *a_logits;
   void *saved, *workspace;    // saved: training (else null)
   fvta_stream_t stream;
+  // the pool held in bf16 (raw bits, 8-byte aligned) IN PLACE OF rows, which is then null: the pooled inference calls
+  // only (sh_forward refuses anything else).  The kernels' ROW = bf16_t instantiations; launches and workspace unchanged
+  const bf16_t* rows_bf16 = nullptr;
 };
 struct ShWarpCall {           // under the time warp: what the scale kernel reads, and where the caller wants the scale
   int warp_type;
@@ -221,17 +224,15 @@ struct ShWarpCall {           // under the time warp: what the scale kernel read
   float* scale_out;
 };
 int sh_forward(const ShShape& s, bool pool, const char* who, const ShFwdCall& c, const ShWarpCall* warp = nullptr);
-// the two launches of e[a,t] over the rows of A albums of T positions: fvta_attn_shared_energy, fvta_attn_pool_energy
+// the two launches of e[a,t] over the rows of A albums of T positions: fvta_attn_shared_energy, fvta_attn_pool_energy;
+// rows_bf16 in place of rows (then null), as ShFwdCall's: fvta_attn_pool_energy_bf16
 int sh_energy(const ShShape& s, const char* who, const float* rows, const float* WH_W, const float* WC_W, float* energy,
-              void* workspace, fvta_stream_t stream);
+              void* workspace, fvta_stream_t stream, const bf16_t* rows_bf16 = nullptr);
 // G, SH_R, S, rps (fvta_attn_shared_plan, fvta_attn_pool_plan)
 int sh_plan(const ShShape& s, const char* who, int32_t out[4]);
 
 // v[c] = sum_o WH[c][o] WC[o] (attn_shared.hip).  grid ceil(w / 4), 256 threads
 __global__ __launch_bounds__(256) void attn_shared_tw_vec_kernel(int w, const float* __restrict__ WH, const float* __restrict__ WC,
                                                                  float* __restrict__ v);
-// e[a,t] = sum_k sum_c v[c] h[a,k,t,c]^2 (attn_shared.hip).  grid ceil(A T / 4), 256 threads; reads s.A, s.K, s.T, s.w
-__global__ __launch_bounds__(256) void attn_shared_energy_kernel(ShShape s, const float* __restrict__ hinfo, const float* __restrict__ v,
-                                                                 float* __restrict__ energy);
 
 }  // namespace fvta

@@ -6,7 +6,9 @@
 //                 writes positions m * T .. + T of q's M * T (s.T = JX, the rows of ONE pooled album; s.TO = M * T).
 //                 A negative index is an empty slot: it joins no group and its qslot is -1
 // sh_ref_q / sh_ref_off (attn_shared_common.h: the backward's kernels use them too) are the whole of it; with
-// POOL = false they fold to (ref, 0) and the kernels are what they were.  The non-template kernels both callers launch
+// POOL = false they fold to (ref, 0) and the kernels are what they were.  The kernels that read rows also take the rows'
+// type, ROW: float, or bf16_t for a pool held in bf16 (the fvta_attn_pool_*_bf16 entry points) -- the loads widen, the
+// arithmetic is the fp32 kernel's.  The non-template kernels both callers launch
 // (question side, the softmaxes' scalars) stay in attn_shared.hip.
 #pragma once
 #include "attn_shared_common.h"
@@ -24,6 +26,9 @@ __global__ __launch_bounds__(256) void attn_shared_softmax_kernel(ShShape s, ShW
 // question staging per row, was measured: 331 registers, one wave per SIMD, and no faster at 8 questions per album, 20 %
 // slower at one -- DESIGN.md 4.1)
 typedef MmaF32<1, 4, 2, 2> ShMma;
+// the row types a kernel of this file may be instantiated with: fp32 anywhere, bf16 bits where they are used
+template <class ROW, bool TRAIN, bool POOL>
+constexpr bool sh_row_ok = std::is_same<ROW, float>::value || (std::is_same<ROW, bf16_t>::value && !TRAIN && POOL);
 static_assert(ShMma::BM == SH_R && ShMma::BN == SH_BN && ShMma::NT == SH_NT && ShMma::TN % 2 == 0, "tile shape");
 
 // ---- the plan.  One workgroup.  Indices are data: clamped before they address anything.
@@ -139,11 +144,15 @@ __global__ __launch_bounds__(SH_PLAN_NT) void attn_shared_plan_kernel(ShShape s,
 // rows as they are held.  The scalar goes through the bilinear form: x = s (h.Qs + Rh.h) + s^2 (R2.h^2) + ct, cosine
 // x = (h.Qn) s rsqrt(max(s^2 |h|^2, 1e-12)) -- the row pass keeps Rh.h and R2.h^2 (cosine: the raw sum h^2) apart, and
 // the scales of the tile's rows for the group's questions are staged in LDS
-template <int JT, bool TRAIN, bool TW, bool POOL = false>
-__global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, ShWork wk, const float* __restrict__ hinfo,
+// ROW (compile-time; float, or bf16_t: rows held as bf16 bits): how a row is LOADED, and nothing else -- ld4 / the staging
+// widen four bf16 in registers, exactly, every lane keeps its channels, and from there on the kernel is the fp32 one on
+// the widened rows: the same bits
+template <int JT, bool TRAIN, bool TW, bool POOL = false, class ROW = float>
+__global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, ShWork wk, const ROW* __restrict__ hinfo,
                                                                   const uint8_t* __restrict__ hmask,
                                                                   const uint8_t* __restrict__ qmask,
                                                                   float* __restrict__ a_logits, ShTwArgs tw) {
+  static_assert(sh_row_ok<ROW, TRAIN, POOL>, "bf16 rows: the pooled inference calls only");
   constexpr int JP = 32 * JT, G = SH_BN / JP;
   const float* __restrict__ tw_scale = tw.scale;
   __shared__ __attribute__((aligned(16))) float smem[ShMma::LDS_FLOATS];
@@ -198,7 +207,7 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
       }
     return;
   }
-  const float* hbase = hinfo + ak * T * w;
+  const ROW* hbase = hinfo + ak * T * w;
   // row terms: a wave per SH_R / 4 rows.  cosine: 1 / |h| instead
   {
     const float* Rh = wk.vecs + VEC_RH * w;
@@ -242,7 +251,7 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
   mma.init(tid);
   StageKContig<SH_R, ShMma::BK, SH_NT, ShMma::LDA> sa;
   StageKContig<SH_BN, ShMma::BK, SH_NT, ShMma::LDB> sb;
-  auto fa = [&](int r, int kk, bool& ok) -> const float* {
+  auto fa = [&](int r, int kk, bool& ok) -> const ROW* {
     const int t = t0 + r;
     ok = t < T;
     return hbase + (ok ? (size_t)t * w + kk : (size_t)0);
@@ -323,9 +332,11 @@ __global__ __launch_bounds__(SH_NT) void attn_shared_logits_kernel(ShShape s, Sh
 
 // ---- weighted sums.  grid ngmax * K * S, 256 threads: thread tid owns channels 4 tid .. + 3 (+ 1024 per further CPT)
 // TW (compile-time; tw_scale [NQ,T] -- POOL: [NQ,M T] -- else unused): the sum runs over the warped rows s h: the staged weight carries s
-template <int G, int CPT, bool TW, bool POOL = false>
-__global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork wk, const float* __restrict__ hinfo,
+// ROW: as the logits kernel's -- with bf16 rows the further CPT's offset of 1024 counts 2-byte elements
+template <int G, int CPT, bool TW, bool POOL = false, class ROW = float>
+__global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork wk, const ROW* __restrict__ hinfo,
                                                                const float* __restrict__ tw_scale) {
+  static_assert(sh_row_ok<ROW, false, POOL>, "bf16 rows: the pooled calls only");
   __shared__ float s_p[SH_CH][G], s_M[G], s_cf[G];
   __shared__ int s_q[G], s_o[POOL ? G : 1];  // as the logits kernel's
   const int tid = threadIdx.x;
@@ -348,7 +359,7 @@ __global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork
 #pragma unroll
     for (int i = 0; i < CPT; ++i) acc[g][i] = zero4();
   const int tb = sp * s.rps, te = min(T, tb + s.rps);
-  const float* hbase = hinfo + ((size_t)a * K + k) * T * w;
+  const ROW* hbase = hinfo + ((size_t)a * K + k) * T * w;
   const bool mine = 4 * tid < w;
   for (int c0 = tb; c0 < te; c0 += SH_CH) {
     __syncthreads();
@@ -363,7 +374,7 @@ __global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork
     if (mine) {
 #pragma unroll 4
       for (int r = 0; r < nr; ++r) {
-        const float* row = hbase + (size_t)(c0 + r) * w + 4 * tid;
+        const ROW* row = hbase + (size_t)(c0 + r) * w + 4 * tid;
         f32x4 h[CPT];
 #pragma unroll
         for (int i = 0; i < CPT; ++i) h[i] = ld4(row + 1024 * i);
@@ -388,13 +399,13 @@ __global__ __launch_bounds__(256) void attn_shared_wsum_kernel(ShShape s, ShWork
   }
 }
 
-template <int G, bool TW, bool POOL = false>
-static void sh_launch_wsum(const ShShape& s, const ShWork& wk, const float* hinfo, const float* tw_scale, hipStream_t st) {
+template <int G, bool TW, bool POOL = false, class ROW = float>
+static void sh_launch_wsum(const ShShape& s, const ShWork& wk, const ROW* hinfo, const float* tw_scale, hipStream_t st) {
   const dim3 grid((unsigned)((int64_t)s.ngmax * s.K * s.S));
   if (s.w <= 1024)
-    hipLaunchKernelGGL((attn_shared_wsum_kernel<G, 1, TW, POOL>), grid, dim3(256), 0, st, s, wk, hinfo, tw_scale);
+    hipLaunchKernelGGL((attn_shared_wsum_kernel<G, 1, TW, POOL, ROW>), grid, dim3(256), 0, st, s, wk, hinfo, tw_scale);
   else
-    hipLaunchKernelGGL((attn_shared_wsum_kernel<G, 2, TW, POOL>), grid, dim3(256), 0, st, s, wk, hinfo, tw_scale);
+    hipLaunchKernelGGL((attn_shared_wsum_kernel<G, 2, TW, POOL, ROW>), grid, dim3(256), 0, st, s, wk, hinfo, tw_scale);
 }
 
 }  // namespace fvta

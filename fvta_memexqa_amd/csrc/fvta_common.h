@@ -94,6 +94,14 @@ __device__ __forceinline__ float fvta_tanh(float x) {
 // 16-byte load of four floats
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+// four bf16 (raw bits, two dwords) as four floats: a shift and a mask per dword.  Exact: bf16 is the upper half of an fp32
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x4 bf4_widen(u32x2 u) {
+  return f32x4{__uint_as_float(u[0] << 16), __uint_as_float(u[0] & 0xffff0000u), __uint_as_float(u[1] << 16),
+               __uint_as_float(u[1] & 0xffff0000u)};
+}
+// the same four channels from a row held in bf16: one 8-byte load (p 8-byte aligned), widened in registers
+__device__ __forceinline__ f32x4 ld4(const bf16_t* p) { return bf4_widen(*reinterpret_cast<const u32x2*>(p)); }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

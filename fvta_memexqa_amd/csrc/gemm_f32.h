@@ -74,7 +74,17 @@ struct MmaF32 {
 // Fetch protocol (both stage kinds): f(i, j, ok) returns an ALWAYS DEREFERENCEABLE pointer to
 // 4 floats and sets ok; the stage loads unconditionally and zeroes the value afterwards.  A load
 // under a data-dependent branch makes hipcc wait vmcnt(0) per load (serialised L2 round trips).
+// StageKContig also takes a source held in bf16: f returns a pointer to 4 bf16 (raw bits, 8-byte aligned), which are
+// widened in registers -- exact -- so the LDS image is the one the widened rows would give.
 //
+// The staged load itself.  Every staging source is global memory; said explicitly: the address-provider lambdas return
+// generic pointers, and through those the loads were FLAT instructions -- which count on lgkmcnt too, so every wait for an
+// LDS operand of the k-loop also waited for the next tile's global loads
+__device__ __forceinline__ f32x4 ldg4(const float* src) { return *(const f32x4 __attribute__((address_space(1)))*)(uintptr_t)src; }
+__device__ __forceinline__ f32x4 ldg4(const bf16_t* src) {
+  return bf4_widen(*(const u32x2 __attribute__((address_space(1)))*)(uintptr_t)src);
+}
+
 // Register-staged tile whose SOURCE rows are k-contiguous: f(r, k, ok) -> &src[r][k].  Stored transposed.
 template <int ROWS, int BK, int NT, int LD>
 struct StageKContig {
@@ -88,11 +98,8 @@ struct StageKContig {
       const int u = tid + p * NT;
       if (UNITS % NT == 0 || u < UNITS) {
         bool ok;
-        const float* src = f(u / (BK / 4), k0 + (u % (BK / 4)) * 4, ok);
-        // (every staging source is global memory; said explicitly: the address-provider lambdas return generic pointers, and
-        //  through those the loads were FLAT instructions -- which count on lgkmcnt too, so every wait for an LDS operand of
-        //  the k-loop also waited for the next tile's global loads)
-        const f32x4 t = *(const f32x4 __attribute__((address_space(1)))*)(uintptr_t)src;
+        const auto* src = f(u / (BK / 4), k0 + (u % (BK / 4)) * 4, ok);  // (const float*, or const bf16_t*: ldg4 widens)
+        const f32x4 t = ldg4(src);
         v[p] = ok ? t : f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
@@ -124,10 +131,7 @@ struct StageMNContig {
       if (UNITS % NT == 0 || u < UNITS) {
         bool ok;
         const float* src = f(k0 + u / (COLS / 4), (u % (COLS / 4)) * 4, ok);
-        // (every staging source is global memory; said explicitly: the address-provider lambdas return generic pointers, and
-        //  through those the loads were FLAT instructions -- which count on lgkmcnt too, so every wait for an LDS operand of
-        //  the k-loop also waited for the next tile's global loads)
-        const f32x4 t = *(const f32x4 __attribute__((address_space(1)))*)(uintptr_t)src;
+        const f32x4 t = ldg4(src);
         v[p] = ok ? t : f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }

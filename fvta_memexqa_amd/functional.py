@@ -179,7 +179,9 @@ def _album_attention_args(rows, hq, index, W, b, rows_mask, hq_mask, simiMatrix,
     library or device call and in one order: the similarity matrix (and warp type), differentiable with simiMatrix 4
     (`no_backward`), gradient mode on a forward-only call (`forward_only`), the shapes, the index, the width.  rows:
     [A,K,T,w] / [A,K,M,JX,w], `pooled`: a pool [P,K,JX,w] with album lists.  warp: None, or (lq, WH_W, WH_b, WC_W, WC_b,
-    warp_type, energy).  Without `differentiable` everything is detached.  -> a namespace: rows / hq / lq padded to the
+    warp_type, energy).  Without `differentiable` everything is detached, and a `pooled` torch.bfloat16 pool STAYS bf16
+    (through the reshape and the zero padding of the width, both exact): the inference ops read it as it is, no fp32 copy.
+    With `differentiable`, and for the shared family, bf16 rows are widened as ever.  -> a namespace: rows / hq / lq padded to the
     kernel width wp, idx on the device, W padded block-wise, b, the two uint8 masks (None unless BOTH are given:
     model_v2.py:233), the warp's weights as the kernels read them, energy (detached, or None), and A K T NQ JQ w wp."""
     from types import SimpleNamespace
@@ -194,7 +196,8 @@ def _album_attention_args(rows, hq, index, W, b, rows_mask, hq_mask, simiMatrix,
     if not differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         raise RuntimeError(forward_only)
     det = (lambda t: t) if differentiable else (lambda t: t.detach())
-    rows, hq = det(_f32(rows)), det(_f32(hq))
+    keep_bf16 = pooled and not differentiable and torch.is_tensor(rows) and rows.dtype == torch.bfloat16
+    rows, hq = det(rows.contiguous() if keep_bf16 else _f32(rows)), det(_f32(hq))
     lq = None if warp is None else det(_f32(lq))
     if pooled and rows.dim() != 4:
         raise ValueError("album pool: expected [P,K,JX,w], got shape %s" % (tuple(rows.shape),))
@@ -265,7 +268,9 @@ def attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask=None, hq_mask=None
     a_logits [NQ,K,M*JX,JQ]): question i attends its albums' rows laid end to end, hinfo_i[k, m*JX + j] =
     pool[albums[i,m], k, j] (an empty slot: JX masked zero rows), with attention_raw's result for that context -- which is
     never built: each pooled album is held once and read once per group of the (question, slot) references that name it
-    (fvta_attn_pool_fwd).  differentiable=False (the default) is that inference call: with gradient mode on and an
+    (fvta_attn_pool_fwd).  A torch.bfloat16 pool is read as it is by the inference call (fvta_attn_pool_fwd_bf16: no fp32
+    copy, the bits of the call on pool.float()); differentiable=True widens it, and the gradient reaches it through the
+    cast.  differentiable=False (the default) is that inference call: with gradient mode on and an
     argument that requires grad it raises, as attention_3d_shared_raw does.  differentiable=True goes through
     autograd.pooled_focal_attention (simiMatrix 1-3; 4 raises NotImplementedError): gradients flow from h_a to pool --
     summed over every (question, slot) that names the album, [P,K,JX,w] -- hq, W and b; a_logits carries none."""
@@ -302,8 +307,11 @@ def album_energy(hinfo, WH_W, WC_W):
     rows (fvta_attn_shared_energy).  It belongs to the albums -- attention_3d_shared_warped_raw(energy=) takes it, and it
     holds as long as hinfo, WH/W and WC/W do.  Forward only, detached.
     An album pool [P,K,JX,w] is accepted as it is and gives e [P,JX], the energy attention_3d_pooled_warped_raw(energy=)
-    takes (fvta_attn_pool_energy makes the same two launches: the same bits)."""
-    hinfo = _f32(hinfo).detach()
+    takes (fvta_attn_pool_energy makes the same two launches: the same bits).  A pool held in torch.bfloat16 is read as it
+    is (fvta_attn_pool_energy_bf16: no fp32 copy; the bits of the energy of pool.float()); bf16 rows of any other shape
+    are widened first."""
+    bf16_pool = torch.is_tensor(hinfo) and hinfo.dtype == torch.bfloat16 and hinfo.dim() == 4
+    hinfo = (hinfo.contiguous() if bf16_pool else _f32(hinfo)).detach()
     A, K, w = hinfo.shape[0], hinfo.shape[1], hinfo.shape[-1]
     hinfo = hinfo.reshape(A, K, -1, w)
     wp = next((c for c in SUPPORTED_W if w <= c), None)
@@ -311,7 +319,10 @@ def album_energy(hinfo, WH_W, WC_W):
         raise ValueError("attention: feature width %d too large (max %d)" % (w, SUPPORTED_W[-1]))
     ops.require_gpu()
     WH, WC, _, _ = _warp_weights(w, wp, WH_W, WC_W)
-    op = ops.SharedWarpedFocalAttention(A, 1, K, hinfo.shape[2], 1, wp, 1, False, 1)
+    if bf16_pool:
+        op = ops.PooledWarpedFocalAttention(A, 1, 1, K, hinfo.shape[2], 1, wp, 1, False, 1)
+    else:
+        op = ops.SharedWarpedFocalAttention(A, 1, K, hinfo.shape[2], 1, wp, 1, False, 1)
     return op.album_energy(_pad_channels(hinfo, wp), WH, WC)
 
 
@@ -357,7 +368,7 @@ def attention_3d_pooled_warped_raw(pool, hq, albums, lq, W, b, WH_W, WH_b, WC_W,
     A position's count runs over the question's whole M*JX positions (a band, past or future crosses slot boundaries).
     Neither the [NQ,K,M*JX,w] context nor its warp is built: the warp is one scalar per (question, position), applied
     inside the kernels (fvta_attn_pool_fwd_tw).  energy [P,JX]: album_energy of (pool, WH_W, WC_W), None computes it on the
-    spot.
+    spot.  A torch.bfloat16 pool: as attention_3d_pooled_raw (fvta_attn_pool_energy_bf16 / fvta_attn_pool_fwd_tw_bf16).
     differentiable=False (the default) is the inference call, forward only: with gradient mode on and an argument that
     requires grad it raises, as attention_3d_pooled_raw(differentiable=False) does.
     differentiable=True goes through autograd.pooled_warped_focal_attention (simiMatrix 1-3; 4 raises NotImplementedError):

@@ -166,7 +166,9 @@ class FocalAttention3D(_AttLogits):
         time_warp (an nn.TimeWarp) with lq [NQ,w], the questions' last states: the attention over each question's albums
         laid end to end and warped for that question -- forward(time_warp(hinfo_i, lq)[0], ...) -- with the pool still
         held once (functional.attention_3d_pooled_warped_raw).  Its parameters and its window buffer are used; energy
-        [P,JX]: functional.album_energy of (pool, WH/W, WC/W) when the caller keeps it, else computed here."""
+        [P,JX]: functional.album_energy of (pool, WH/W, WC/W) when the caller keeps it, else computed here.
+        A pool held in torch.bfloat16 passes through the inference calls as it is: no fp32 copy, and the result is that of
+        the same call on pool.float(), bit for bit; differentiable=True widens it."""
         W, b = self._wb()
         if time_warp is None and (lq is not None or energy is not None):
             raise ValueError("forward_pooled: lq / energy belong to the time warp; pass time_warp (an nn.TimeWarp) with them")
@@ -226,17 +228,24 @@ class _EnergyCache:
 
 class AlbumPool:
     """P encoded albums, each kept ONCE for any number of questions and any album lists: pool [P,K,JX,w] and pool_mask
-    [P,K,JX], held contiguous fp32 / u8 on the device and detached.  Where nn.AlbumMemory keeps one context per distinct
+    [P,K,JX], held contiguous fp32 (dtype=torch.float32, the default) or bf16 (dtype=torch.bfloat16) / u8 on the device
+    and detached.  In bf16 the rows take half the bytes (`nbytes`) and every read of a row moves half the bytes; attend()
+    and energy() return what an fp32 AlbumPool of the same (rounded) rows returns, bit for bit -- the kernels widen in
+    registers and compute in fp32.  The rounding (to nearest even, once, here) is the only loss, and there is none when
+    the rows came from the bf16 engine (the project's default, whose context rows are bf16: DESIGN.md 3, shadow rows):
+    those values are bf16 already.  Where nn.AlbumMemory keeps one context per distinct
     LIST of albums, this keeps one block of rows per ALBUM and every question names the albums it reads (MemexQA's
     album_ids).  No parameters, no encoder.  It stays a detached inference holder: no gradient reaches the rows it was
     built from.  Training over a pool goes through nn.FocalAttention3D.forward_pooled(differentiable=True) -- under the time
     warp forward_pooled_warped() -- on a pool tensor that requires grad."""
 
-    def __init__(self, pool, pool_mask=None):
+    def __init__(self, pool, pool_mask=None, dtype=torch.float32):
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("AlbumPool: dtype must be torch.float32 or torch.bfloat16, got %s" % (dtype,))
         dev = ops.require_gpu()
         if pool.dim() != 4:
             raise ValueError("AlbumPool: expected [P,K,JX,w], got shape %s" % (tuple(pool.shape),))
-        self.pool = pool.detach().to(dev, torch.float32).contiguous()
+        self.pool = pool.detach().to(dev, dtype).contiguous()
         self.pool_mask = None if pool_mask is None else ops.as_mask_u8(pool_mask.detach().to(dev))
         if self.pool_mask is not None and tuple(self.pool_mask.shape) != tuple(self.pool.shape[:3]):
             raise ValueError("AlbumPool: mask %s does not match the rows %s" % (tuple(pool_mask.shape), tuple(pool.shape)))
@@ -245,16 +254,22 @@ class AlbumPool:
     def __len__(self):
         return self.pool.shape[0]
 
+    @property
+    def nbytes(self):
+        """the bytes the rows take on the device (the mask is P*K*JX more)"""
+        return self.pool.numel() * self.pool.element_size()
+
     @classmethod
-    def from_context(cls, hall, hall_mask=None):
+    def from_context(cls, hall, hall_mask=None, dtype=torch.float32):
         """The context tensor functional.context_tensor produces, hall [N,K,M,JX,w] / hall_mask [N,K,M,JX], cut into its
-        albums: (pool of P = N*M albums, albums [N,M] = arange(N*M): question n's own M albums in order)."""
+        albums: (pool of P = N*M albums, albums [N,M] = arange(N*M): question n's own M albums in order).  dtype: as the
+        constructor's."""
         if hall.dim() != 5:
             raise ValueError("AlbumPool.from_context: expected [N,K,M,JX,w], got shape %s" % (tuple(hall.shape),))
         N, K, M, JX, w = hall.shape
         pool = hall.detach().permute(0, 2, 1, 3, 4).reshape(N * M, K, JX, w)
         mask = None if hall_mask is None else hall_mask.detach().reshape(N, K, M, JX).permute(0, 2, 1, 3).reshape(N * M, K, JX)
-        return cls(pool, mask), torch.arange(N * M, dtype=torch.int32).reshape(N, M)
+        return cls(pool, mask, dtype), torch.arange(N * M, dtype=torch.int32).reshape(N, M)
 
     def attend(self, attention, hq, hq_mask, albums, time_warp=None, lq=None):
         """(h_a [NQ,w], a_logits [NQ,K,M*JX,JQ]) of `attention` (an nn.FocalAttention3D) for questions hq [NQ,JQ,w] that list

@@ -324,6 +324,15 @@ class _AlbumAttention:
     def _call(self, name, *args):
         check(getattr(self.lib, name)(ctypes.byref(self.desc), *args, stream_ptr()), name)
 
+    def _rows_arg(self, rows):
+        """(suffix of the entry point's name, the rows' pointer) of an inference call.  A pool held as a contiguous
+        torch.bfloat16 tensor goes to the pooled calls' _bf16 entry points AS IT IS -- no fp32 copy; their result is the
+        fp32 call's on the widened rows, bit for bit.  Anything else must be contiguous fp32, as ever."""
+        if rows.dtype == torch.bfloat16 and self._sym == "fvta_attn_pool":
+            assert rows.is_cuda and rows.is_contiguous(), "expected a contiguous bfloat16 CUDA tensor"
+            return "_bf16", ptr(rows)
+        return "", ptr(_f32c(rows))
+
     def _words(self, name, keys):
         out = (ctypes.c_int32 * 4)()
         check(getattr(self.lib, name)(ctypes.byref(self._shape_desc), out), name)
@@ -365,9 +374,10 @@ class _AlbumAttention:
         if warp is not None:
             e, q, sc = [ptr(_f32c(energy))], [ptr(_f32c(lq))], [ptr(scale)]
             wb = [ptr(_f32c(WH_b)), ptr(_f32c(WC_W)), ptr(_f32c(WC_b))]
-        args = [ptr(_f32c(rows)), ptr(rows_mask)] + e + [ptr(_f32c(hq)), ptr(qmask)] + q + [ptr(index), ptr(W), ptr(b)] + wb + \
+        bf16, rows_ptr = ("", ptr(_f32c(rows))) if train else self._rows_arg(rows)   # (training: fp32 rows only)
+        args = [rows_ptr, ptr(rows_mask)] + e + [ptr(_f32c(hq)), ptr(qmask)] + q + [ptr(index), ptr(W), ptr(b)] + wb + \
             [ptr(h_a), ptr(a_logits)] + sc + ([ptr(self.saved)] if train else []) + [ptr(self.work)]
-        self._call(self._sym + "_fwd" + self._tw + ("_train" if train else ""), *args)
+        self._call(self._sym + "_fwd" + self._tw + ("_train" if train else "") + bf16, *args)
         return (h_a, a_logits) if warp is None else (h_a, a_logits, scale)
 
     def forward(self, rows, rows_mask, hq, qmask, index, W, b, want_logits=False):
@@ -411,7 +421,8 @@ class _WarpedAlbumAttention(_AlbumAttention):
         assert tuple(rows.shape) == self._rows
         assert WH_W.numel() >= self.w * self.w and WC_W.numel() == self.w
         energy = torch.empty(self._rows[0], self._rows[2], device=self.dev, dtype=torch.float32)
-        self._call(self._sym + "_energy", ptr(_f32c(rows)), ptr(_f32c(WH_W)), ptr(_f32c(WC_W)), ptr(energy), ptr(self.work))
+        bf16, rows_ptr = self._rows_arg(rows)
+        self._call(self._sym + "_energy" + bf16, rows_ptr, ptr(_f32c(WH_W)), ptr(_f32c(WC_W)), ptr(energy), ptr(self.work))
         return energy
 
     def forward(self, rows, rows_mask, energy, hq, qmask, lq, index, W, b, WH_b, WC_W, WC_b, want_logits=False, want_scale=False):
@@ -493,7 +504,10 @@ class PooledFocalAttention(_AlbumAttention):
     check_album_lists before the upload; -1 is an empty slot).  Question i gets FocalAttention's result on its albums' rows
     laid end to end, [K, M*JX, w], which is never built.  forward() is the inference call (fvta_attn_pool_fwd, nothing
     kept); forward_train() / backward() are the training pair (simiMatrix 1-3), whose d_pool stays [P,K,JX,w]: the sum of
-    the per-question row gradients over every (question, slot) that refers to the album."""
+    the per-question row gradients over every (question, slot) that refers to the album.
+    forward() also takes the pool as a contiguous torch.bfloat16 tensor (fvta_attn_pool_fwd_bf16): half the bytes held
+    and read, no fp32 copy made, and the result is forward()'s on pool.float(), bit for bit.  The training pair takes fp32
+    rows."""
 
     def __init__(self, P, NQ, M, K, JX, JQ, w, simi, add_tanh):
         self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w = int(P), int(NQ), int(M), int(K), int(JX), int(JQ), int(w)
@@ -529,7 +543,10 @@ class PooledWarpedFocalAttention(_WarpedAlbumAttention):
     once per pool, forward() takes it.  The count of a position runs over the question's whole M*JX positions.
     forward_train() / backward() are the training pair (fvta_attn_pool_fwd_tw_train / fvta_attn_pool_bwd_tw; simiMatrix
     1-3), whose d_pool stays [P,K,JX,w]: the sum -- the attention's row gradient and the energy's -- over every (question,
-    slot) that refers to the album."""
+    slot) that refers to the album.
+    album_energy() and forward() also take the pool as a contiguous torch.bfloat16 tensor (fvta_attn_pool_energy_bf16 /
+    fvta_attn_pool_fwd_tw_bf16): no fp32 copy, and the results are those on pool.float(), bit for bit.  The training pair
+    takes fp32 rows."""
 
     def __init__(self, P, NQ, M, K, JX, JQ, w, simi, add_tanh, warp_type, window_t=3.0):
         self.P, self.NQ, self.M, self.K, self.JX, self.JQ, self.w = int(P), int(NQ), int(M), int(K), int(JX), int(JQ), int(w)

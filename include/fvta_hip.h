@@ -373,6 +373,31 @@ int fvta_attn_pool_fwd_tw(const fvta_attn_pool_tw_desc* d, const float* pool, co
                           const float* b, const float* WH_b, const float* WC_W, const float* WC_b, float* h_a,
                           float* a_logits, float* scale_out, void* workspace, fvta_stream_t stream);
 
+/* The pool held in bf16 (inference only): pool [P,K,JX,w] as raw bf16 bits (uint16_t; torch.bfloat16), contiguous, HALF
+ * the bytes of the fp32 pool, and every row read moves half the bytes.  The three calls take the descriptors and the
+ * argument order of their fp32 namesakes; masks, questions, weights, energy, outputs and workspace are fp32 / u8 as there,
+ * and the fp32 size queries (fvta_attn_pool_workspace_bytes, fvta_attn_pool_tw_workspace_bytes) and fvta_attn_pool_plan
+ * serve them: same launches, same workspace layout, same checks and refusals under the new names.
+ * Contract: each call returns what its fp32 namesake returns on the WIDENED pool (every bf16 value as the fp32 value it
+ * stands for), BIT FOR BIT -- h_a, a_logits, scale_out, energy.  The kernels are the fp32 ones with another row load: four
+ * bf16 in one 8-byte load, widened in registers (exact), every lane on the channels it has there, the matrix pipe fed
+ * fp32 as before.  So rows that came from a bf16 encoder lose nothing here; fp32 rows are rounded ONCE, by whoever makes
+ * the bf16 pool (round to nearest even), never by these calls.
+ * Alignment: `pool` must be 8-byte aligned (w is a multiple of 64, so then every row is); else FVTA_ERR_INVALID_ARG.
+ * Not here: training (fvta_attn_pool_fwd_train / _bwd and the warped pair take fp32 rows, d_pool is fp32), the shared
+ * family (fvta_attn_shared_*), and the bi-LSTM's shadow-row address tables -- the rows must stand as one contiguous
+ * [P,K,JX,w] block. */
+int fvta_attn_pool_fwd_bf16(const fvta_attn_pool_desc* d, const uint16_t* pool, const uint8_t* pool_mask, const float* hq,
+                            const uint8_t* qmask, const int32_t* albums, const float* W, const float* b, float* h_a,
+                            float* a_logits, void* workspace, fvta_stream_t stream);
+int fvta_attn_pool_energy_bf16(const fvta_attn_pool_tw_desc* d, const uint16_t* pool, const float* WH_W, const float* WC_W,
+                               float* energy, void* workspace, fvta_stream_t stream);
+int fvta_attn_pool_fwd_tw_bf16(const fvta_attn_pool_tw_desc* d, const uint16_t* pool, const uint8_t* pool_mask,
+                               const float* energy, const float* hq, const uint8_t* qmask, const float* lq,
+                               const int32_t* albums, const float* W, const float* b, const float* WH_b, const float* WC_W,
+                               const float* WC_b, float* h_a, float* a_logits, float* scale_out, void* workspace,
+                               fvta_stream_t stream);
+
 /* Training over the pool under the time warp (simiMatrix 1-3, every warp type, no time_warp_att; with simi 4 the two size
  * queries return 0 and the calls FVTA_ERR_UNSUPPORTED: the per-question route covers it; a warp type outside 1..5: 0 and
  * FVTA_ERR_INVALID_ARG).  The contract is fvta_attn_shared_fwd_tw_train / fvta_attn_shared_bwd_tw's read per REFERENCE

@@ -235,6 +235,32 @@ def _album_attention_args(rows, hq, index, W, b, rows_mask, hq_mask, simiMatrix,
     return p
 
 
+def _album_attention(p, pooled, differentiable, simiMatrix, add_tanh, warp_type=None, window_t=None):
+    """What the four attention_3d_{shared,pooled}[_warped]_raw functions do with the namespace p of _album_attention_args:
+    differentiable, the autograd function; else the op built for p's shape and its forward (under the warp, warp_type not
+    None, with the energy it computes unless one was given) -> (h_a sliced to w, a_logits[, scale])"""
+    M = (p.idx.shape[1],) if pooled else ()
+    if warp_type is None:
+        if differentiable:
+            fn = autograd.pooled_focal_attention if pooled else autograd.shared_focal_attention
+            out = fn(p.rows, p.hq, p.idx, p.W, p.b, p.rm, p.qm, simiMatrix, add_tanh)
+        else:
+            op = (ops.PooledFocalAttention if pooled else ops.SharedFocalAttention)(
+                p.A, p.NQ, *M, p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh)
+            out = op.forward(p.rows, p.rm, p.hq, p.qm, p.idx, p.W, p.b, want_logits=True)
+    elif differentiable:   # (the gradients come back sliced to w; WH_W's comes back [2w,w] with zeros below row w)
+        fn = autograd.pooled_warped_focal_attention if pooled else autograd.shared_warped_focal_attention
+        out = fn(p.rows, p.hq, p.lq, p.idx, p.W, p.b, p.WH, p.WHb, p.WC, p.WCb, p.rm, p.qm, simiMatrix, add_tanh, warp_type,
+                 float(window_t), p.energy)
+    else:
+        op = (ops.PooledWarpedFocalAttention if pooled else ops.SharedWarpedFocalAttention)(
+            p.A, p.NQ, *M, p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh, warp_type, float(window_t))
+        energy = op.album_energy(p.rows, p.WH, p.WC) if p.energy is None else p.energy
+        out = op.forward(p.rows, p.rm, energy, p.hq, p.qm, p.lq, p.idx, p.W, p.b, p.WHb, p.WC, p.WCb, want_logits=True,
+                         want_scale=True)
+    return (out[0][:, :p.w].contiguous(),) + tuple(out[1:])
+
+
 def attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask=None, hq_mask=None, simiMatrix=1, add_tanh=False,
                             differentiable=False):
     """attention_3d for NQ questions over A albums held once: hinfo [A,K,T,w] (or [A,K,M,JX,w]), hq [NQ,JQ,w], album [NQ]
@@ -252,12 +278,7 @@ def attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask=None, hq_mask=Non
         "attention_3d_shared_raw is forward-only by default: pass differentiable=True (simiMatrix 1-3), call "
         "it under torch.no_grad(), or use the per-question attention_3d (functional.attention_3d / "
         "attention_raw, nn.FocalAttention3D.forward)")
-    if differentiable:
-        h_a, a = autograd.shared_focal_attention(p.rows, p.hq, p.idx, p.W, p.b, p.rm, p.qm, simiMatrix, add_tanh)
-    else:
-        op = ops.SharedFocalAttention(p.A, p.NQ, p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh)
-        h_a, a = op.forward(p.rows, p.rm, p.hq, p.qm, p.idx, p.W, p.b, want_logits=True)
-    return h_a[:, :p.w].contiguous(), a
+    return _album_attention(p, False, differentiable, simiMatrix, add_tanh)
 
 
 def attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask=None, hq_mask=None, simiMatrix=1, add_tanh=False,
@@ -281,12 +302,7 @@ def attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask=None, hq_mask=None
         "attention_3d_pooled_raw is forward-only: call it under torch.no_grad(), or use the per-question "
         "attention_3d (functional.attention_3d / attention_raw, nn.FocalAttention3D.forward) on the "
         "gathered rows")
-    if differentiable:
-        h_a, a = autograd.pooled_focal_attention(p.rows, p.hq, p.idx, p.W, p.b, p.rm, p.qm, simiMatrix, add_tanh)
-    else:
-        op = ops.PooledFocalAttention(p.A, p.NQ, p.idx.shape[1], p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh)
-        h_a, a = op.forward(p.rows, p.rm, p.hq, p.qm, p.idx, p.W, p.b, want_logits=True)
-    return h_a[:, :p.w].contiguous(), a
+    return _album_attention(p, True, differentiable, simiMatrix, add_tanh)
 
 
 def _warp_weights(w, wp, WH_W, WC_W, WH_b=None, WC_b=None, detach=True):
@@ -348,15 +364,7 @@ def attention_3d_shared_warped_raw(hinfo, hq, album, lq, W, b, WH_W, WH_b, WC_W,
         "per-question time_warp + attention_3d (functional.time_warp_raw / attention_raw, nn.TimeWarp / "
         "nn.FocalAttention3D.forward) on hinfo.index_select(0, album)",
         warp=(lq, WH_W, WH_b, WC_W, WC_b, warp_type, energy))
-    if differentiable:     # (the gradients come back sliced to w; WH_W's comes back [2w,w] with zeros below row w)
-        h_a, a, scale = autograd.shared_warped_focal_attention(p.rows, p.hq, p.lq, p.idx, p.W, p.b, p.WH, p.WHb, p.WC, p.WCb, p.rm,
-                                                               p.qm, simiMatrix, add_tanh, warp_type, float(window_t), p.energy)
-    else:
-        op = ops.SharedWarpedFocalAttention(p.A, p.NQ, p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh, warp_type, float(window_t))
-        energy = op.album_energy(p.rows, p.WH, p.WC) if p.energy is None else p.energy
-        h_a, a, scale = op.forward(p.rows, p.rm, energy, p.hq, p.qm, p.lq, p.idx, p.W, p.b, p.WHb, p.WC, p.WCb, want_logits=True,
-                                   want_scale=True)
-    return h_a[:, :p.w].contiguous(), a, scale
+    return _album_attention(p, False, differentiable, simiMatrix, add_tanh, warp_type, window_t)
 
 
 def attention_3d_pooled_warped_raw(pool, hq, albums, lq, W, b, WH_W, WH_b, WC_W, WC_b, pool_mask=None, hq_mask=None,
@@ -383,16 +391,7 @@ def attention_3d_pooled_warped_raw(pool, hq, albums, lq, W, b, WH_W, WH_b, WC_W,
         "it under torch.no_grad(), or use the per-question time_warp + attention_3d (functional.time_warp_raw / "
         "attention_raw, nn.TimeWarp / nn.FocalAttention3D.forward) on the gathered rows",
         warp=(lq, WH_W, WH_b, WC_W, WC_b, warp_type, energy))
-    if differentiable:     # (the gradients come back sliced to w; WH_W's comes back [2w,w] with zeros below row w)
-        h_a, a, scale = autograd.pooled_warped_focal_attention(p.rows, p.hq, p.lq, p.idx, p.W, p.b, p.WH, p.WHb, p.WC, p.WCb, p.rm,
-                                                               p.qm, simiMatrix, add_tanh, warp_type, float(window_t), p.energy)
-    else:
-        op = ops.PooledWarpedFocalAttention(p.A, p.NQ, p.idx.shape[1], p.K, p.T, p.JQ, p.wp, simiMatrix, add_tanh, warp_type,
-                                            float(window_t))
-        energy = op.album_energy(p.rows, p.WH, p.WC) if p.energy is None else p.energy
-        h_a, a, scale = op.forward(p.rows, p.rm, energy, p.hq, p.qm, p.lq, p.idx, p.W, p.b, p.WHb, p.WC, p.WCb, want_logits=True,
-                                   want_scale=True)
-    return h_a[:, :p.w].contiguous(), a, scale
+    return _album_attention(p, True, differentiable, simiMatrix, add_tanh, warp_type, window_t)
 
 
 def attention_3d_shared(hinfo, hq, album, hinfo_mask=None, hq_mask=None, simiMatrix=1, wd=None, add_tanh=False,

@@ -114,25 +114,10 @@ class FocalAttention3D(_AttLogits):
         (functional.attention_3d_shared_warped_raw; inference only here -- forward_shared_warped() is the training call).
         Its parameters and its window buffer are used; energy [A,T]: functional.album_energy of (hinfo, WH/W, WC/W) when
         the caller keeps it, else computed here."""
-        W, b = self._wb()
-        if time_warp is None and (lq is not None or energy is not None):
-            raise ValueError("forward_shared: lq / energy belong to the time warp; pass time_warp (an nn.TimeWarp) with them")
-        if time_warp is not None:
-            if lq is None:
-                raise ValueError("forward_shared: the time warp needs lq [NQ,w], the questions' last states")
-            if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
-                raise ValueError("forward_shared: lq must be [%d, %d], got %s"
-                                 % (hq.shape[0], self.w, tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
-            if differentiable:
-                raise NotImplementedError("forward_shared: under the time warp this call is the inference one; "
-                                          "forward_shared_warped(hinfo, hq, album, lq, time_warp, ...) trains over the shared rows")
-            tw = time_warp
-            h_a, a, _ = functional.attention_3d_shared_warped_raw(
-                hinfo, hq, album, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), hinfo_mask, hq_mask,
-                self.simiMatrix, self.add_tanh, tw.warp_type, tw.window_t(), energy)
-            return h_a, a
-        return functional.attention_3d_shared_raw(hinfo, hq, album, W, b, hinfo_mask, hq_mask, self.simiMatrix, self.add_tanh,
-                                                  differentiable=differentiable)
+        return self._album_forward(
+            "forward_shared", False, differentiable, hinfo, hq, album, hinfo_mask, hq_mask, time_warp, lq, energy,
+            "forward_shared: under the time warp this call is the inference one; "
+            "forward_shared_warped(hinfo, hq, album, lq, time_warp, ...) trains over the shared rows")
 
     def forward_shared_warped(self, hinfo, hq, album, lq, time_warp, hinfo_mask=None, hq_mask=None, energy=None):
         """The training call under the time warp: forward(time_warp(hinfo[album], lq)[0], hq, ...) for NQ questions over A
@@ -141,16 +126,8 @@ class FocalAttention3D(_AttLogits):
         h_a's gradient reaches hinfo [A,K,...,w] (summed over each album's questions), hq, lq, this module's att_logits/{W,b}
         and time_warp's WH/{W,b}, WC/{W,b}; a_logits carries none.  energy [A,T]: a cached functional.album_energy, used
         for the forward; the gradient through it is taken all the same."""
-        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
-            raise ValueError("forward_shared_warped: lq must be [%d, %d], got %s"
-                             % (hq.shape[0], self.w, tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
-        W, b = self._wb()
-        tw = time_warp
-        h_a, a, _ = functional.attention_3d_shared_warped_raw(
-            hinfo, hq, album, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), hinfo_mask, hq_mask,
-            self.simiMatrix, self.add_tanh, tw.warp_type, tw.window_t(), energy, differentiable=True)
-        return h_a, a
-
+        return self._album_forward("forward_shared_warped", False, True, hinfo, hq, album, hinfo_mask, hq_mask, time_warp, lq,
+                                   energy)
 
     def forward_pooled(self, pool, hq, albums, pool_mask=None, hq_mask=None, time_warp=None, lq=None, energy=None,
                        differentiable=False):
@@ -169,27 +146,14 @@ class FocalAttention3D(_AttLogits):
         [P,JX]: functional.album_energy of (pool, WH/W, WC/W) when the caller keeps it, else computed here.
         A pool held in torch.bfloat16 passes through the inference calls as it is: no fp32 copy, and the result is that of
         the same call on pool.float(), bit for bit; differentiable=True widens it."""
-        W, b = self._wb()
-        if time_warp is None and (lq is not None or energy is not None):
-            raise ValueError("forward_pooled: lq / energy belong to the time warp; pass time_warp (an nn.TimeWarp) with them")
-        if time_warp is None:
-            return functional.attention_3d_pooled_raw(pool, hq, albums, W, b, pool_mask, hq_mask, self.simiMatrix, self.add_tanh,
-                                                      differentiable=differentiable)
-        if differentiable:
-            raise NotImplementedError("forward_pooled: under the time warp this call is the inference one; "
-                                      "forward_pooled_warped(pool, hq, albums, lq, time_warp, ...) trains over the pool (as "
-                                      "does the per-question route: forward() on time_warp's warp of each question's "
-                                      "gathered rows)")
-        if lq is None:
-            raise ValueError("forward_pooled: the time warp needs lq [NQ,w], the questions' last states")
-        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
-            raise ValueError("forward_pooled: lq must be [%d, %d], got %s"
-                             % (hq.shape[0], self.w, tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
-        tw = time_warp
-        h_a, a, _ = functional.attention_3d_pooled_warped_raw(
-            pool, hq, albums, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), pool_mask, hq_mask,
-            self.simiMatrix, self.add_tanh, tw.warp_type, tw.window_t(), energy)
-        return h_a, a
+        refusal = ("forward_pooled: under the time warp this call is the inference one; "
+                   "forward_pooled_warped(pool, hq, albums, lq, time_warp, ...) trains over the pool (as "
+                   "does the per-question route: forward() on time_warp's warp of each question's "
+                   "gathered rows)")
+        if time_warp is not None and differentiable:          # (this call refuses it before it looks at lq)
+            raise NotImplementedError(refusal)
+        return self._album_forward("forward_pooled", True, differentiable, pool, hq, albums, pool_mask, hq_mask, time_warp, lq,
+                                   energy, refusal)
 
     def forward_pooled_warped(self, pool, hq, albums, lq, time_warp, pool_mask=None, hq_mask=None, energy=None):
         """The training call over the pool under the time warp: forward(time_warp(hinfo_i, lq)[0], hq, ...) for NQ questions
@@ -199,14 +163,32 @@ class FocalAttention3D(_AttLogits):
         h_a's gradient reaches pool [P,K,JX,w] (summed over every (question, slot) that names the album), hq, lq, this
         module's att_logits/{W,b} and time_warp's WH/{W,b}, WC/{W,b}; a_logits carries none.  energy [P,JX]: a cached
         functional.album_energy, used for the forward; the gradient through it is taken all the same."""
-        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
-            raise ValueError("forward_pooled_warped: lq must be [%d, %d], got %s"
-                             % (hq.shape[0], self.w, tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
+        return self._album_forward("forward_pooled_warped", True, True, pool, hq, albums, pool_mask, hq_mask, time_warp, lq,
+                                   energy)
+
+    def _album_forward(self, name, pooled, differentiable, rows, hq, index, rows_mask, hq_mask, time_warp, lq, energy,
+                       inference=None):
+        """What forward_shared / forward_pooled (pooled: a pool with album lists) and their _warped training calls share,
+        each under its own `name`: the refusals, the time warp's parameters unpacked, the functional call.  inference:
+        on the calls that are the inference ones under the time warp, the NotImplementedError they answer differentiable
+        with there; None on the training calls, which take lq and time_warp by position."""
         W, b = self._wb()
+        if time_warp is None:
+            if lq is not None or energy is not None:
+                raise ValueError("%s: lq / energy belong to the time warp; pass time_warp (an nn.TimeWarp) with them" % name)
+            raw = functional.attention_3d_pooled_raw if pooled else functional.attention_3d_shared_raw
+            return raw(rows, hq, index, W, b, rows_mask, hq_mask, self.simiMatrix, self.add_tanh, differentiable=differentiable)
+        if inference is not None and lq is None:
+            raise ValueError("%s: the time warp needs lq [NQ,w], the questions' last states" % name)
+        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.w):
+            raise ValueError("%s: lq must be [%d, %d], got %s"
+                             % (name, hq.shape[0], self.w, tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
+        if inference is not None and differentiable:
+            raise NotImplementedError(inference)
         tw = time_warp
-        h_a, a, _ = functional.attention_3d_pooled_warped_raw(
-            pool, hq, albums, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), pool_mask, hq_mask,
-            self.simiMatrix, self.add_tanh, tw.warp_type, tw.window_t(), energy, differentiable=True)
+        raw = functional.attention_3d_pooled_warped_raw if pooled else functional.attention_3d_shared_warped_raw
+        h_a, a, _ = raw(rows, hq, index, lq, W, b, tw.p("WH/W"), tw.p("WH/b"), tw.p("WC/W"), tw.p("WC/b"), rows_mask, hq_mask,
+                        self.simiMatrix, self.add_tanh, tw.warp_type, tw.window_t(), energy, differentiable=differentiable)
         return h_a, a
 
 
@@ -226,7 +208,42 @@ class _EnergyCache:
         return self._kept[1]
 
 
-class AlbumPool:
+class _AlbumRows:
+    """What nn.AlbumMemory and nn.AlbumPool share: rows held once (`_held`), asked with an index per question (an album,
+    or -- `_pooled` -- a list of albums), and the rows' energy under a time warp's weights, kept."""
+    _pooled = False
+
+    def __init__(self):
+        self._energy = _EnergyCache()    # e [A,T] / [P,JX] under a time warp's weights: see energy()
+
+    def _attend(self, attention, hq, hq_mask, index, time_warp, lq):
+        rows, mask = self._held()
+        if self._pooled:
+            idx = ops.check_album_lists(index, len(self), mask is not None and hq_mask is not None)
+        else:
+            idx = ops.check_album_index(index, len(self))
+        if idx.shape[0] != hq.shape[0]:
+            raise ValueError(("album lists: %d lists for %d questions" if self._pooled else
+                              "album index: %d entries for %d questions") % (idx.shape[0], hq.shape[0]))
+        forward = attention.forward_pooled if self._pooled else attention.forward_shared
+        if time_warp is None:
+            if lq is not None:
+                raise ValueError("attend: lq belongs to the time warp; pass time_warp (an nn.TimeWarp) with it")
+            return forward(rows, hq, idx, mask, hq_mask)
+        if lq is None:
+            raise ValueError("attend: the time warp needs lq [NQ,w], the questions' last states")
+        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], rows.shape[-1]):
+            raise ValueError("attend: lq must be [%d, %d], got %s"
+                             % (hq.shape[0], rows.shape[-1], tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
+        return forward(rows, hq, idx, mask, hq_mask, time_warp=time_warp, lq=lq, energy=self.energy(time_warp))
+
+    def energy(self, time_warp):
+        """e [A,T] (a pool's: [P,JX]) of functional.album_energy for the held rows and time_warp's WH/W, WC/W: kept, and
+        recomputed when either parameter is another tensor or has been written to since (its version counter)"""
+        return self._energy.get(self._held()[0], time_warp)
+
+
+class AlbumPool(_AlbumRows):
     """P encoded albums, each kept ONCE for any number of questions and any album lists: pool [P,K,JX,w] and pool_mask
     [P,K,JX], held contiguous fp32 (dtype=torch.float32, the default) or bf16 (dtype=torch.bfloat16) / u8 on the device
     and detached.  In bf16 the rows take half the bytes (`nbytes`) and every read of a row moves half the bytes; attend()
@@ -238,8 +255,10 @@ class AlbumPool:
     album_ids).  No parameters, no encoder.  It stays a detached inference holder: no gradient reaches the rows it was
     built from.  Training over a pool goes through nn.FocalAttention3D.forward_pooled(differentiable=True) -- under the time
     warp forward_pooled_warped() -- on a pool tensor that requires grad."""
+    _pooled = True
 
     def __init__(self, pool, pool_mask=None, dtype=torch.float32):
+        super().__init__()
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("AlbumPool: dtype must be torch.float32 or torch.bfloat16, got %s" % (dtype,))
         dev = ops.require_gpu()
@@ -249,10 +268,12 @@ class AlbumPool:
         self.pool_mask = None if pool_mask is None else ops.as_mask_u8(pool_mask.detach().to(dev))
         if self.pool_mask is not None and tuple(self.pool_mask.shape) != tuple(self.pool.shape[:3]):
             raise ValueError("AlbumPool: mask %s does not match the rows %s" % (tuple(pool_mask.shape), tuple(pool.shape)))
-        self._energy = _EnergyCache()    # e [P,JX] under a time warp's weights: see energy()
 
     def __len__(self):
         return self.pool.shape[0]
+
+    def _held(self):
+        return self.pool, self.pool_mask
 
     @property
     def nbytes(self):
@@ -278,43 +299,28 @@ class AlbumPool:
         for that question, the pool still held once.  The albums' share of the warp, the energy [P,JX], is computed on
         first use and kept; it is recomputed when WH/W or WC/W of the time warp have changed since (an in-place update,
         load_state_dict, another module)."""
-        idx = ops.check_album_lists(albums, len(self), self.pool_mask is not None and hq_mask is not None)
-        if idx.shape[0] != hq.shape[0]:
-            raise ValueError("album lists: %d lists for %d questions" % (idx.shape[0], hq.shape[0]))
-        if time_warp is None:
-            if lq is not None:
-                raise ValueError("attend: lq belongs to the time warp; pass time_warp (an nn.TimeWarp) with it")
-            return attention.forward_pooled(self.pool, hq, idx, self.pool_mask, hq_mask)
-        if lq is None:
-            raise ValueError("attend: the time warp needs lq [NQ,w], the questions' last states")
-        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.pool.shape[-1]):
-            raise ValueError("attend: lq must be [%d, %d], got %s"
-                             % (hq.shape[0], self.pool.shape[-1], tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
-        return attention.forward_pooled(self.pool, hq, idx, self.pool_mask, hq_mask, time_warp=time_warp, lq=lq,
-                                        energy=self.energy(time_warp))
-
-    def energy(self, time_warp):
-        """e [P,JX] of functional.album_energy for this pool's rows and time_warp's WH/W, WC/W: kept, and recomputed when
-        either parameter is another tensor or has been written to since (its version counter)"""
-        return self._energy.get(self.pool, time_warp)
+        return self._attend(attention, hq, hq_mask, albums, time_warp, lq)
 
 
-class AlbumMemory:
+class AlbumMemory(_AlbumRows):
     """The context of A encoded albums, kept for any number of questions: hall [A,K,T,w] (or [A,K,M,JX,w]) and hall_mask
     [A,K,T] as functional.context_tensor returns them, held contiguous fp32 / u8 on the device and detached.  No
     parameters, no encoder: the caller encodes each album once and asks with attend()."""
 
     def __init__(self, hall, hall_mask=None):
+        super().__init__()
         dev = ops.require_gpu()
         A, K, w = hall.shape[0], hall.shape[1], hall.shape[-1]
         self.hall = hall.detach().to(dev, torch.float32).reshape(A, K, -1, w).contiguous()
         self.hall_mask = None if hall_mask is None else ops.as_mask_u8(hall_mask.detach().to(dev).reshape(A, K, -1))
         if self.hall_mask is not None and tuple(self.hall_mask.shape) != tuple(self.hall.shape[:3]):
             raise ValueError("AlbumMemory: mask %s does not match the rows %s" % (tuple(hall_mask.shape), tuple(hall.shape)))
-        self._energy = _EnergyCache()    # e [A,T] under a time warp's weights: see energy()
 
     def __len__(self):
         return self.hall.shape[0]
+
+    def _held(self):
+        return self.hall, self.hall_mask
 
     def attend(self, attention, hq, hq_mask, album, time_warp=None, lq=None):
         """(h_a [NQ,w], a_logits [NQ,K,T,JQ]) of `attention` (an nn.FocalAttention3D) for questions hq [NQ,JQ,w] about
@@ -322,25 +328,7 @@ class AlbumMemory:
         time_warp (an nn.TimeWarp) with lq [NQ,w]: the attention over the rows warped per question, the rows still held
         once.  The albums' share of the warp, the energy [A,T], is computed on first use and kept; it is recomputed when
         WH/W or WC/W of the time warp have changed since (an in-place update, load_state_dict, another module)."""
-        idx = ops.check_album_index(album, len(self))
-        if idx.shape[0] != hq.shape[0]:
-            raise ValueError("album index: %d entries for %d questions" % (idx.shape[0], hq.shape[0]))
-        if time_warp is None:
-            if lq is not None:
-                raise ValueError("attend: lq belongs to the time warp; pass time_warp (an nn.TimeWarp) with it")
-            return attention.forward_shared(self.hall, hq, idx, self.hall_mask, hq_mask)
-        if lq is None:
-            raise ValueError("attend: the time warp needs lq [NQ,w], the questions' last states")
-        if not torch.is_tensor(lq) or tuple(lq.shape) != (hq.shape[0], self.hall.shape[-1]):
-            raise ValueError("attend: lq must be [%d, %d], got %s"
-                             % (hq.shape[0], self.hall.shape[-1], tuple(lq.shape) if torch.is_tensor(lq) else type(lq).__name__))
-        return attention.forward_shared(self.hall, hq, idx, self.hall_mask, hq_mask, time_warp=time_warp, lq=lq,
-                                        energy=self.energy(time_warp))
-
-    def energy(self, time_warp):
-        """e [A,T] of functional.album_energy for this memory's rows and time_warp's WH/W, WC/W: kept, and recomputed when
-        either parameter is another tensor or has been written to since (its version counter)"""
-        return self._energy.get(self.hall, time_warp)
+        return self._attend(attention, hq, hq_mask, album, time_warp, lq)
 
 
 class QuestionAttention(_AttLogits):

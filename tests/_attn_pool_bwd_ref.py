@@ -6,8 +6,8 @@ gradients over every (question, slot) reference to an album.
 Inputs are tests/_attn_pooled_ref.make_case's with att_logits/W scaled by sqrt(64 / w), for the reason given in
 tests/_attn_shared_bwd_ref.py (the tanh logits saturate from w = 512 on at the unscaled recipe), plus a seeded d_h_a.
 
-Every case must satisfy `conditions` -- tests/_attn_shared_bwd_ref.py's, unchanged in value: the top-2 gap over j of every
-valid row and the top-2 gap of amax over t of every (question, k) above GAP, under tanh fewer than 5 % of the valid
+Every case must satisfy `conditions` (tests/_album_attn_ref.py, tests/_attn_shared_bwd_ref.py's too): the top-2 gap over j
+of every valid row and the top-2 gap of amax over t of every (question, k) above GAP, under tanh fewer than 5 % of the valid
 logits with |x| > 0.99 -- with ONE adaptation: a slot that repeats an earlier slot's album in the same list is left out
 of the gap over t.  Its rows ARE the earlier slot's rows, so the tie is exact by construction, and both ways of resolving
 it (all to one slot, or split) give the same d_pool and d_hq.  SEEDS holds, per case, the first seed of `seed_candidates`
@@ -18,10 +18,11 @@ the row counts JX placed around the ROW PASS's tile (fvta_attn_pool_bwd_plan) in
 row tiles per workgroup of the row pass."""
 import torch
 
+from tests import _album_attn_ref as AR
 from tests import _attn_pooled_ref as P
 
-GAP = 1e-5
-SAT_X, SAT_FRACTION = 0.99, 0.05
+GAP, SAT_X, SAT_FRACTION = AR.GAP, AR.SAT_X, AR.SAT_FRACTION
+conditions, qualifies, valid_mask, first_slots = AR.conditions, AR.qualifies, AR.valid_mask, AR.first_slots
 SIMI_TANH = [(1, False), (2, True), (3, True)]
 ROW_JX = ["1", "7", "Rb-1", "Rb", "Rb+1", "65", "200"]
 N_CANDIDATES = 32
@@ -86,8 +87,7 @@ LOOP_IDS = ["many", "heavy", "tiles"]
 
 
 def seed_candidates(name):
-    base = sum(map(ord, name)) * 10
-    return [base + i for i in range(N_CANDIDATES)]
+    return AR.seed_candidates(name, 0, N_CANDIDATES)
 
 
 # the first qualifying candidate per case (tests/test_attn_pool_bwd_host.py re-checks every one of them)
@@ -141,15 +141,7 @@ def build_case(name, seed=None, parity=True):
     G, _ = P.host_plan(JQ, w)
     Rb = host_bwd_plan_words(1, 1, 1, K, 64, JQ, w)["rows"]
     c = P.make_case(lists(G, masked), Pn, K, JX(Rb), JQ, w, simi, masked, SEEDS[name] if seed is None else seed)
-    c["W"] = c["W"] * (64.0 / w) ** 0.5
-    c["tanh"] = tanh
-    if masked and parity:
-        c["pm"][0, 0, :3] = True
-        if c["NQ"] > 1:
-            c["qm"][c["NQ"] - 1, :2] = True
-        c["pm"][:, :, 0] |= ~c["pm"].any(-1)
-    c["gout"] = torch.randn(c["NQ"], w, generator=torch.Generator().manual_seed(99))
-    return c
+    return AR.train_inputs(c, c["pm"], tanh, parity)
 
 
 def plans_of(c):
@@ -177,56 +169,6 @@ def reference(c):
     return dict(h_a=ha.detach(), a_logits=a.detach(), dpool=dpool, dq=q.grad, dW=W.grad.reshape(-1), db=b.grad.reshape(-1))
 
 
-def valid_mask(c):
-    """[NQ,K,T,JQ] bool: the entries exp_mask leaves alone"""
-    NQ, K, T, JQ = c["NQ"], c["K"], c["T"], c["JQ"]
-    if c["pm"] is None or c["qm"] is None:
-        return torch.ones(NQ, K, T, JQ, dtype=torch.bool)
-    _, m = P.expand(c)
-    return m[:, :, :, None] & c["qm"][:, None, None, :]
-
-
-def first_slots(c):
-    """[NQ,T] bool: the positions of slots that do NOT repeat an earlier slot's album in the same list"""
-    al, JX = c["albums"], c["JX"]
-    keep = torch.ones(c["NQ"], c["M"], dtype=torch.bool)
-    for i, row in enumerate(al.tolist()):
-        for m, p in enumerate(row):
-            if p >= 0 and p in row[:m]:
-                keep[i, m] = False
-    return keep[:, :, None].expand(-1, -1, JX).reshape(c["NQ"], c["T"])
-
-
-def conditions(c, a_logits):
-    """(smallest top-2 gap over j in a valid row, smallest top-2 gap of amax over t in a (question, k) -- a repeated
-    slot's positions left out --, fraction of valid logits with |x| > SAT_X); a gap that does not exist counts as inf"""
-    v = valid_mask(c)
-    x = torch.where(v, a_logits, torch.full_like(a_logits, -float("inf")))
-    inf = float("inf")
-    jgap = inf
-    if c["JQ"] > 1:
-        top = torch.topk(x, 2, dim=-1).values                       # [NQ,K,T,2]
-        two = v.sum(-1) >= 2
-        if bool(two.any()):
-            jgap = float((top[..., 0] - top[..., 1])[two].min())
-    tgap = inf
-    first = first_slots(c)[:, None, :]                              # [NQ,1,T]
-    rowv = v.any(-1) & first                                        # [NQ,K,T]
-    amax = torch.where(rowv, x.max(-1).values, torch.full_like(x[..., 0], -inf))
-    if c["T"] > 1:
-        top = torch.topk(amax, 2, dim=-1).values
-        two = rowv.sum(-1) >= 2
-        if bool(two.any()):
-            tgap = float((top[..., 0] - top[..., 1])[two].min())
-    sat = float((a_logits[v].abs() > SAT_X).double().mean()) if c["tanh"] and bool(v.any()) else 0.0
-    return jgap, tgap, sat
-
-
-def qualifies(c, a_logits):
-    jgap, tgap, sat = conditions(c, a_logits)
-    return jgap > GAP and tgap > GAP and sat < SAT_FRACTION
-
-
 def forward_logits(c):
     """the fp64 a_logits alone (no autograd): what `conditions` reads"""
     with torch.no_grad():
@@ -236,10 +178,4 @@ def forward_logits(c):
 # ------------------------------------------------------------------ a width no kernel has (channel padding): w = 100
 def odd_width_case():
     c = P.make_case(torch.tensor([[0, 1], [1, -1], [0, 0]]), 2, 2, 20, 5, 100, 2, True, 4242)
-    c["W"] = c["W"] * (64.0 / 100) ** 0.5
-    c["tanh"] = True
-    c["pm"][0, 0, :3] = True
-    c["pm"][:, :, 0] |= ~c["pm"].any(-1)
-    c["qm"][c["NQ"] - 1, :2] = True
-    c["gout"] = torch.randn(c["NQ"], 100, generator=torch.Generator().manual_seed(99))
-    return c
+    return AR.train_inputs(c, c["pm"], True)

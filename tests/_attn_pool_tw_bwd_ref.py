@@ -4,9 +4,10 @@
 `reference` is the definition: fp64 autograd of tests/_attn_pooled_ref.expand -> oracle.fvta_fused.time_warp_closed ->
 oracle.fvta_fused.attention_3d, all nine leaves requiring grad.  expand is stack / cat of the pool's albums, so d_pool is
 the sum over every (question, slot) reference to an album of BOTH the attention's row gradient and the energy's.
-`factored_backward` is the restatement the kernels implement, by hand and without autograd: the scale per (question,
-global position m JX + j), ds per (question, k, position), dz from ds with the count of the GLOBAL position and zero at an
-empty slot, de per pooled album over its references, d_pool += 2 de v h, db as -sum damax x^2.
+`factored_backward` (tests/_album_attn_ref.py) is the restatement the kernels implement, by hand and without autograd:
+the scale per (question, global position m JX + j), ds per (question, k, position), dz from ds with the count of the
+GLOBAL position and zero at an empty slot, de per pooled album over its references, d_pool += 2 de v h, db as
+-sum damax x^2.
 tests/test_attn_pool_tw_bwd_host.py holds the two against each other.
 
 Inputs: tests/_attn_pool_bwd_ref.py's shapes and recipe (att_logits/W scaled by sqrt(64 / w), the parity masks, a seeded
@@ -22,6 +23,7 @@ positions agree (type 2 everywhere, type 5 in the band's interior) the same scal
 SEEDS pins, per case, the first qualifying one of `seed_candidates` (32; no case needed more than its first seven)."""
 import torch
 
+from tests import _album_attn_ref as AR
 from tests import _attn_pool_bwd_ref as B
 from tests import _attn_pooled_ref as P
 from tests import _attn_shared_tw_bwd_ref as STB
@@ -34,7 +36,7 @@ TOL = STB.TOL
 GRAD_KEYS = ("dpool", "dq", "dlq", "dW", "db", "dWH_W", "dWH_b", "dWC_W", "dWC_b")
 N_CANDIDATES = 32
 conditions, qualifies, valid_mask, first_slots, plans_of = B.conditions, B.qualifies, B.valid_mask, B.first_slots, B.plans_of
-cmax = STB.cmax
+cmax, count, within, factored_backward = AR.cmax, AR.count_of, AR.within, AR.factored_backward
 
 
 # (name, P, lists(G, masked) -> [NQ,M], K, JX(Rb), JQ, w, simi, tanh, masked, warp_type, window_t, zero_rows)
@@ -139,27 +141,16 @@ def build_case(name, seed=None, parity=True):
     G, _ = P.host_plan(JQ, w)
     Rb = B.host_bwd_plan_words(1, 1, 1, K, 64, JQ, w)["rows"]
     c = P.make_case(lists(G, masked), Pn, K, JX(Rb), JQ, w, simi, masked, seed)
-    c["tanh"] = tanh
-    if masked and parity:
-        c["pm"][0, 0, :3] = True
-        if c["NQ"] > 1:
-            c["qm"][c["NQ"] - 1, :2] = True
-        c["pm"][:, :, 0] |= ~c["pm"].any(-1)
+    AR.train_inputs(c, c["pm"], tanh, parity)
     if zero_rows:
         c["pool"] = c["pool"] * c["pm"][..., None]
-    c["gout"] = torch.randn(c["NQ"], w, generator=torch.Generator().manual_seed(99))
     c = TW.add_warp(c, seed, wt, win)
-    c["W"] = c["W"] * (64.0 / w) ** 0.5 / float(cmax(c["T"], wt, win)) ** 2
+    c["W"] = c["W"] / float(cmax(c["T"], wt, win)) ** 2
     return c
 
 
 def loop_regime(name, c, plan, bwd_plan):
     B.loop_regime(name, c, plan, bwd_plan)
-
-
-def count(c, dtype=torch.float64):
-    """cnt [M JX]: the count of the GLOBAL position"""
-    return TW._count(c["T"], c["warp_type"], c["window_t"], dtype)
 
 
 # ------------------------------------------------------------------ the definition
@@ -189,119 +180,6 @@ def forward_logits(c):
     return reference(c, grads=False)["a_logits"]
 
 
-# ------------------------------------------------------------------ the restatement, by hand
-def factored_backward(c, dtype=torch.float64):
-    """the gradient keys of `reference` (and db_pooled, dz [NQ,M JX], de [P,JX]) from the formulas the kernels implement:
-    tests/_attn_shared_tw_bwd_ref.factored_backward per question on its albums' rows, read from the pool slot by slot; the
-    row gradient goes back to the pool by reference, and what is per question and position runs over the GLOBAL position"""
-    cv = lambda x: x.to(dtype)
-    pool, q, lq, g, al = cv(c["pool"]), cv(c["q"]), cv(c["lq"]), cv(c["gout"]), c["albums"]
-    simi, tanh = c["simi"], c["tanh"]
-    Pn, K, JX, w = pool.shape
-    NQ, JQ = q.shape[:2]
-    M, T = c["M"], c["T"]
-    W, b = cv(c["W"]).reshape(-1), cv(c["b"])[0]
-    zero = torch.zeros(w, dtype=dtype)
-    if simi == 1:            # [h, q, h*q] . W
-        Rh, Cq, U, R2 = W[:w], W[w:2 * w], W[2 * w:], zero
-    elif simi == 2:          # [h*q, (h-q)^2] . W
-        Rh, Cq, U, R2 = zero, zero, W[:w] - 2 * W[w:], W[w:]
-    else:                    # [h, q, (h-q)^2, h*q] . W
-        Rh, Cq, U, R2 = W[:w], W[w:2 * w], W[3 * w:] - 2 * W[2 * w:3 * w], W[2 * w:3 * w]
-    WH, WHb, WC, WCb = cv(c["WH_W"])[:w], cv(c["WH_b"]), cv(c["WC_W"]).reshape(w), cv(c["WC_b"])[0]
-    v = WH @ WC
-    s0 = WHb @ WC + WCb
-    e = torch.cat([((pool * pool) @ v).sum(1), torch.zeros(1, JX, dtype=dtype)])      # [P + 1,JX]; row P: an empty slot's
-    cnt = count(c, dtype)
-    slot_e = e[torch.where(al >= 0, al, torch.full_like(al, Pn))].reshape(NQ, T)       # gathered per slot
-    tz = torch.tanh(slot_e + K * (s0 + lq @ WC)[:, None])                              # [NQ,T]
-    s_all = tz * cnt[None, :]
-    live = (al >= 0)[:, :, None].expand(NQ, M, JX).reshape(NQ, T)                      # positions of a non-empty slot
-    masked = c["pm"] is not None and c["qm"] is not None
-    zrows, zmask = torch.zeros(K, JX, w, dtype=dtype), torch.zeros(K, JX, dtype=torch.bool)
-    dpool, dq, dz = torch.zeros_like(pool), torch.zeros_like(q), torch.zeros(NQ, T, dtype=dtype)
-    dRh, dR2, dU, dCq, dC2 = (torch.zeros(w, dtype=dtype) for _ in range(5))
-    db, db_pooled = torch.zeros(1, dtype=dtype), torch.zeros(1, dtype=dtype)
-    for i in range(NQ):
-        row = al[i].tolist()
-        H = torch.cat([pool[p] if p >= 0 else zrows for p in row], 1)             # [K,T,w]: read, never kept
-        Q, gi, s = q[i], g[i], s_all[i][None, :]
-        Qs = Q * U
-        lin = H @ Qs.t() + (H @ Rh)[..., None]                                    # [K,T,JQ]
-        r2 = (H * H) @ R2                                                         # [K,T]
-        ct = Q @ Cq + (Q * Q) @ R2 + b
-        x = s[..., None] * lin + (s * s * r2)[..., None] + ct
-        if tanh:
-            x = torch.tanh(x)
-        if masked:
-            hm = torch.cat([c["pm"][p] if p >= 0 else zmask for p in row], 1)
-            x = torch.where(hm[:, :, None] & c["qm"][i][None, None, :], x, torch.full_like(x, NEG))
-        amax, jmax = x.max(-1)
-        Mk = amax.max(-1).values
-        ex = torch.exp(amax - Mk[:, None])
-        p_ = ex / ex.sum(-1, keepdim=True)
-        u = torch.einsum("kt,ktc->kc", p_ * s, H)
-        r = torch.softmax(Mk, 0)
-        gu = u @ gi
-        dsk = r * (gu - (r * gu).sum())
-        top = amax == Mk[:, None]
-        allmasked = Mk == NEG
-        dss = torch.where(allmasked, torch.zeros_like(dsk), dsk / top.sum(-1))
-        gh = H @ gi
-        pr = p_ * r[:, None]
-        damax = pr * (s * gh - gu[:, None]) + top * dss[:, None]
-        damax = torch.where((pr != 0) & ~allmasked[:, None], damax, torch.zeros_like(damax))
-        dx = damax * (1 - amax * amax) if tanh else damax
-        dx = torch.where(damax != 0, dx, torch.zeros_like(dx))
-        Qsj = Qs[jmax]
-        dH = (s * pr)[..., None] * gi + (dx * s)[..., None] * (Qsj + Rh) + 2 * (dx * s * s)[..., None] * R2 * H
-        for m, p in enumerate(row):                                               # by reference; an empty slot: nowhere
-            if p >= 0:
-                dpool[p] += dH[:, m * JX:(m + 1) * JX]
-        ds = pr * gh + dx * (lin.gather(-1, jmax[..., None])[..., 0] + 2 * s * r2)
-        dxsH = ((dx * s)[..., None] * H).reshape(K * T, w)
-        dQs = torch.zeros(JQ, w, dtype=dtype).index_add_(0, jmax.reshape(-1), dxsH)
-        dct = torch.zeros(JQ, dtype=dtype).index_add_(0, jmax.reshape(-1), dx.reshape(-1))
-        dRh += dxsH.sum(0)
-        dR2 += ((dx * s * s)[..., None] * H * H).sum((0, 1))
-        dq[i] = U * dQs + dct[:, None] * (Cq + 2 * R2 * Q)
-        dU += (dQs * Q).sum(0)
-        dCq += (dct[:, None] * Q).sum(0)
-        dC2 += (dct[:, None] * Q * Q).sum(0)
-        db += dct.sum()
-        if tanh:
-            dbt = torch.where(damax != 0, damax * amax * amax, torch.zeros_like(damax))
-            db_pooled -= dbt[:, live[i]].sum()                                    # an empty slot's positions: not read
-        # dz with the count of the GLOBAL position; zero at an empty slot WITHOUT reading ds there (the kernels cannot)
-        dz[i] = torch.where(live[i], cnt * (1 - tz[i] * tz[i]) * torch.where(live[i][None, :], ds, torch.zeros_like(ds)).sum(0),
-                            torch.zeros(T, dtype=dtype))
-        assert float(ds[:, ~live[i]].abs().max() if bool((~live[i]).any()) else 0.0) == 0.0    # ... and zero IS its value
-    de = torch.zeros(Pn, JX, dtype=dtype)
-    for i in range(NQ):                                                               # references in plan order
-        for m, p in enumerate(al[i].tolist()):
-            if p >= 0:
-                de[p] += dz[i, m * JX:(m + 1) * JX]
-    D = dz.sum(1)
-    ds0 = K * D.sum()
-    dpool += 2 * de[:, None, :, None] * v * pool                                      # every k, masked rows too
-    dv = torch.einsum("at,aktc->c", de, pool * pool)
-    dWH_W = torch.zeros(2 * w, w, dtype=dtype)
-    dWH_W[:w] = dv[:, None] * WC[None, :]
-    dD = dR2 + dC2
-    if simi == 1:
-        dW = torch.cat([dRh, dCq, dU])
-    elif simi == 2:
-        dW = torch.cat([dU, dD - 2 * dU])
-    else:
-        dW = torch.cat([dRh, dCq, dD - 2 * dU, dU])
-    return dict(scale=s_all, dpool=dpool, dq=dq, dlq=K * D[:, None] * WC[None, :], dW=dW, db=db, dWH_W=dWH_W, dWH_b=ds0 * WC,
-                dWC_W=WH.t() @ dv + ds0 * WHb + K * (D @ lq), dWC_b=ds0.reshape(1), db_pooled=db_pooled, dz=dz, de=de)
-
-
-def within(got, want, key):
-    return STB.within(got, want, {"dpool": "dh"}.get(key, key))
-
-
 # ------------------------------------------------------------------ a width no kernel has (channel padding): w = 50
 ODD_WIDTH_SEED = 4242
 
@@ -309,11 +187,6 @@ ODD_WIDTH_SEED = 4242
 def odd_width_case(seed=None):
     seed = ODD_WIDTH_SEED if seed is None else seed
     c = P.make_case(torch.tensor([[0, 1], [1, -1], [0, 0]]), 2, 2, 20, 5, 50, 2, True, seed)
-    c["tanh"] = True
-    c["pm"][0, 0, :3] = True
-    c["pm"][:, :, 0] |= ~c["pm"].any(-1)
-    c["qm"][c["NQ"] - 1, :2] = True
-    c["gout"] = torch.randn(c["NQ"], 50, generator=torch.Generator().manual_seed(99))
-    c = TW.add_warp(c, seed, 5, WINDOW_T)
-    c["W"] = c["W"] * (64.0 / 50) ** 0.5 / float(cmax(c["T"], 5, WINDOW_T)) ** 2
+    c = TW.add_warp(AR.train_inputs(c, c["pm"], True), seed, 5, WINDOW_T)
+    c["W"] = c["W"] / float(cmax(c["T"], 5, WINDOW_T)) ** 2
     return c

@@ -3,14 +3,14 @@
 and attends those albums' rows laid end to end, T = M * JX.
 
 `reference` is the definition: the context of every question assembled by concatenation (zeros and mask 0 for an empty
-slot), then oracle.fvta_fused.attention_3d.  `grouped` is an independent restatement in the order the kernels work in:
-per pooled album ONE [K*JX, w] x [w, refs*JQ] product for all (question, slot) references to it, written out from
-att_logits/W per similarity form (not through the oracle's helpers), the mask as a select, the blocks scattered to their
-slots' positions, the two softmaxes by hand.  tests/test_attn_pooled_host.py holds the two against each other on every
-shape the GPU tests use (SPECS and LOOP_SPECS)."""
+slot), then oracle.fvta_fused.attention_3d.  `grouped` (tests/_album_attn_ref.py) is an independent restatement in the
+order the kernels work in.  tests/test_attn_pooled_host.py holds the two against each other on every shape the GPU tests
+use (SPECS and LOOP_SPECS)."""
 import torch
 
-NEG = -1e30
+from tests import _album_attn_ref as AR
+
+NEG = AR.NEG
 SIMI_TANH = [(1, False), (2, True), (3, True), (4, False)]      # the parametrisation of tests/test_gpu_forward.py
 PLAN_THREADS = 1024          # threads of the plan's single workgroup
 WSUM_CHUNK = 64              # rows the weighted sum stages at a time
@@ -172,8 +172,7 @@ def loop_regime(name, c, plan):
 
 
 # ------------------------------------------------------------------ references (fp64, CPU)
-def _dd(t):
-    return None if t is None else t.double()
+_dd, grouped = AR._dd, AR.grouped
 
 
 def expand(c):
@@ -191,60 +190,3 @@ def reference(c, tanh):
     from oracle import fvta_fused as F
     h, m = expand(c)
     return F.attention_3d(_dd(h), _dd(c["q"]), _dd(c["W"]), _dd(c["b"]), m, c["qm"], simiMatrix=c["simi"], add_tanh=tanh)
-
-
-def _softmax_last(x):
-    e = torch.exp(x - x.max(-1, keepdim=True).values)
-    return e / e.sum(-1, keepdim=True)
-
-
-def grouped(c, tanh):
-    """album by album: one product for all references to the album, scattered to their slots"""
-    pool, q, al, simi = _dd(c["pool"]), _dd(c["q"]), c["albums"], c["simi"]
-    P, K, JX, w = pool.shape
-    NQ, JQ = q.shape[:2]
-    M = al.shape[1]
-    W = None if c["W"] is None else _dd(c["W"]).reshape(-1)
-    b = None if c["b"] is None else float(c["b"])
-    masked = c["pm"] is not None and c["qm"] is not None
-    logits = torch.full((NQ, K, M * JX, JQ), NEG if masked else float("nan"), dtype=torch.float64)
-    for p in range(P):
-        ref = torch.nonzero(al == p)                                      # [nref, 2]: (question, slot)
-        if ref.shape[0] == 0:
-            continue
-        qi, mi = ref[:, 0], ref[:, 1]
-        nref = qi.numel()
-        H = pool[p].reshape(K * JX, w)
-        Q = q[qi].reshape(nref * JQ, w)
-        if simi == 1:        # [h, q, h*q] . W
-            x = (H * W[2 * w:]) @ Q.t() + (H @ W[:w])[:, None] + (Q @ W[w:2 * w])[None, :] + b
-        elif simi == 2:      # [h*q, (h-q)^2] . W
-            Wd = W[w:]
-            x = (H * (W[:w] - 2 * Wd)) @ Q.t() + ((H * H) @ Wd)[:, None] + ((Q * Q) @ Wd)[None, :] + b
-        elif simi == 3:      # [h, q, (h-q)^2, h*q] . W
-            Wd = W[2 * w:3 * w]
-            x = (H * (W[3 * w:] - 2 * Wd)) @ Q.t() + (H @ W[:w] + (H * H) @ Wd)[:, None] \
-                + (Q @ W[w:2 * w] + (Q * Q) @ Wd)[None, :] + b
-        else:                # cosine
-            Hn = H / torch.sqrt(torch.clamp((H * H).sum(1, keepdim=True), min=1e-12))
-            Qn = Q / torch.sqrt(torch.clamp((Q * Q).sum(1, keepdim=True), min=1e-12))
-            x = Hn @ Qn.t()
-        if tanh and simi != 4:
-            x = torch.tanh(x)
-        x = x.reshape(K, JX, nref, JQ).permute(2, 0, 1, 3)                # [nref,K,JX,JQ]
-        if masked:
-            valid = c["pm"][p][None, :, :, None] & c["qm"][qi][:, None, None, :]
-            x = torch.where(valid, x, torch.full_like(x, NEG))
-        for r in range(nref):
-            logits[qi[r], :, mi[r] * JX:(mi[r] + 1) * JX] = x[r]
-    assert not torch.isnan(logits).any()                                   # open: every slot was written
-    amax = logits.max(-1).values                                           # [NQ,K,T]
-    pt = _softmax_last(amax)
-    u = torch.zeros(NQ, K, w, dtype=torch.float64)
-    for i in range(NQ):
-        for m in range(M):
-            p = int(al[i, m])
-            if p >= 0:
-                u[i] += torch.einsum("kt,ktc->kc", pt[i, :, m * JX:(m + 1) * JX], pool[p])
-    r = _softmax_last(amax.max(-1).values)                                 # [NQ,K]
-    return torch.einsum("gk,gkc->gc", r, u), logits

@@ -6,23 +6,24 @@ positions: a band, past or future crosses slot boundaries.
 
 `reference` is the definition: tests/_attn_pooled_ref.expand (the context of every question by concatenation, zeros and
 mask 0 for an empty slot), oracle.fvta_fused.time_warp_closed, then oracle.fvta_fused.attention_3d on the warped rows.
-`factored` is the restatement the kernels compute, written out independently and parametrised by dtype: the energy per
-POOLED ALBUM [P,JX], the scale per (question, global position t = m * JX + j), the scalar passed through the bilinear
-form of the logits and through the weighted sum, the blocks of a pooled album's references scattered to their slots'
-positions; no [NQ,K,T,w] tensor.  tests/test_attn_pooled_tw_host.py holds the two against each other on every shape the
-GPU tests use.
+`factored` (tests/_album_attn_ref.py) is the restatement the kernels compute, written out independently and parametrised
+by dtype: the energy per POOLED ALBUM [P,JX], the scale per (question, global position t = m * JX + j), the scalar
+passed through the bilinear form of the logits and through the weighted sum, the blocks of a pooled album's references
+scattered to their slots' positions; no [NQ,K,T,w] tensor.  tests/test_attn_pooled_tw_host.py holds the two against each
+other on every shape the GPU tests use.
 
 Inputs: tests/_attn_pooled_ref.make_case / lists_from_counts, the warp's parameters by tests/_attn_shared_tw_ref.add_warp.
-Tolerances: tests/_attn_shared_tw_ref.TOL."""
+Tolerances: tests/_album_attn_ref.TOL."""
 import torch
 
+from tests import _album_attn_ref as AR
 from tests import _attn_pooled_ref as R
 from tests import _attn_shared_tw_ref as TW
 
 NEG = R.NEG
 WINDOW_T = TW.WINDOW_T
-TOL = TW.TOL
-within = TW.within
+TOL, within, _dd = AR.TOL, AR.within, AR._dd
+energy, scale_of, factored = AR.energy, AR.scale_of, AR.factored
 
 
 # ------------------------------------------------------------------ the cases
@@ -103,10 +104,6 @@ def build_case(name):
 
 
 # ------------------------------------------------------------------ references (CPU)
-def _dd(t):
-    return None if t is None else t.double()
-
-
 def reference(c):
     """the definition, fp64 -> (h_a [NQ,w], a_logits [NQ,K,T,JQ], scale [NQ,T]), T = M JX"""
     from oracle import fvta_fused as F
@@ -116,89 +113,3 @@ def reference(c):
     cnt = F.time_indication_band(c["T"], c["warp_type"], c["window_t"], dtype=torch.float64).sum(-1)
     h_a, a = F.attention_3d(warped, _dd(c["q"]), _dd(c["W"]), _dd(c["b"]), m, c["qm"], simiMatrix=c["simi"], add_tanh=c["tanh"])
     return h_a, a, cc * cnt[None, :]
-
-
-def _softmax_last(x):
-    e = torch.exp(x - x.max(-1, keepdim=True).values)
-    return e / e.sum(-1, keepdim=True)
-
-
-def energy(c, dtype=torch.float64):
-    """e [P,JX] = sum_k sum_c v[c] pool[p,k,j,c]^2, v = WH[:w] WC: per pooled album"""
-    w = c["w"]
-    v = c["WH_W"].to(dtype)[:w] @ c["WC_W"].to(dtype).reshape(w)
-    h = c["pool"].to(dtype)
-    return ((h * h) @ v).sum(1)
-
-
-def scale_of(c, dtype=torch.float64):
-    """scale [NQ, M JX]: the pooled albums' energies gathered per slot (an empty slot: 0), the count of the GLOBAL position"""
-    cv = lambda t: t.to(dtype)
-    al, K, M, JX, w = c["albums"], c["K"], c["M"], c["JX"], c["w"]
-    WC = cv(c["WC_W"]).reshape(w)
-    s0 = cv(c["WH_b"]) @ WC + cv(c["WC_b"])[0]
-    e = torch.cat([energy(c, dtype), torch.zeros(1, JX, dtype=dtype)])       # row P: an empty slot's
-    ei = e[torch.where(al >= 0, al, torch.full_like(al, c["P"]))].reshape(c["NQ"], M * JX)
-    z = ei + K * (s0 + cv(c["lq"]) @ WC)[:, None]
-    return torch.tanh(z) * TW._count(M * JX, c["warp_type"], c["window_t"], dtype)[None, :]
-
-
-def factored(c, dtype=torch.float64):
-    """pooled album by pooled album: one product for all (question, slot) references to it, the scale of the reference's
-    positions through the bilinear form and the weighted sum, scattered to the slots -> (h_a, a_logits, scale) in `dtype`"""
-    cv = lambda t: None if t is None else t.to(dtype)
-    pool, q, al, simi, tanh = cv(c["pool"]), cv(c["q"]), c["albums"], c["simi"], c["tanh"]
-    P, K, JX, w = pool.shape
-    NQ, JQ = q.shape[:2]
-    M = al.shape[1]
-    T = M * JX
-    scale = scale_of(c, dtype)
-    W = None if c["W"] is None else cv(c["W"]).reshape(-1)
-    b = None if c["b"] is None else cv(c["b"])[0]
-    zero = torch.zeros(w, dtype=dtype)
-    if simi == 1:            # [h, q, h*q] . W
-        Rh, Cq, U, R2 = W[:w], W[w:2 * w], W[2 * w:], zero
-    elif simi == 2:          # [h*q, (h-q)^2] . W
-        Rh, Cq, U, R2 = zero, zero, W[:w] - 2 * W[w:], W[w:]
-    elif simi == 3:          # [h, q, (h-q)^2, h*q] . W
-        Rh, Cq, U, R2 = W[:w], W[w:2 * w], W[3 * w:] - 2 * W[2 * w:3 * w], W[2 * w:3 * w]
-    masked = c["pm"] is not None and c["qm"] is not None
-    logits = torch.full((NQ, K, T, JQ), NEG if masked else float("nan"), dtype=dtype)
-    for p in range(P):
-        ref = torch.nonzero(al == p)                                      # [nref, 2]: (question, slot)
-        if ref.shape[0] == 0:
-            continue
-        qi, mi = ref[:, 0], ref[:, 1]
-        nref = qi.numel()
-        H = pool[p].reshape(K * JX, w)
-        Q = q[qi].reshape(nref * JQ, w)
-        pos = mi[:, None] * JX + torch.arange(JX)[None, :]                # [nref,JX]: the references' global positions
-        s = torch.gather(scale[qi], 1, pos)[:, None, :].expand(nref, K, JX)
-        if simi == 4:
-            Qn = Q / torch.sqrt(torch.clamp((Q * Q).sum(1, keepdim=True), min=1e-12))
-            dot = (H @ Qn.t()).reshape(K, JX, nref, JQ).permute(2, 0, 1, 3)
-            n2 = (H * H).sum(1).reshape(K, JX)[None]
-            x = dot * (s / torch.sqrt(torch.clamp(s * s * n2, min=1e-12)))[..., None]
-        else:
-            dot = (H @ (Q * U).t()).reshape(K, JX, nref, JQ).permute(2, 0, 1, 3)
-            ct = ((Q @ Cq + (Q * Q) @ R2) + b).reshape(nref, JQ)
-            r1, r2 = (H @ Rh).reshape(K, JX)[None], ((H * H) @ R2).reshape(K, JX)[None]
-            x = s[..., None] * (dot + r1[..., None]) + (s * s * r2)[..., None] + ct[:, None, None, :]
-            if tanh:
-                x = torch.tanh(x)
-        if masked:
-            valid = c["pm"][p][None, :, :, None] & c["qm"][qi][:, None, None, :]
-            x = torch.where(valid, x, torch.full_like(x, NEG))
-        for r in range(nref):
-            logits[qi[r], :, mi[r] * JX:(mi[r] + 1) * JX] = x[r]
-    assert not torch.isnan(logits).any()                                   # open: every slot was written
-    amax = logits.max(-1).values                                           # [NQ,K,T]
-    pt = _softmax_last(amax) * scale[:, None, :]                           # the weight carries the scale
-    u = torch.zeros(NQ, K, w, dtype=dtype)
-    for i in range(NQ):
-        for m in range(M):
-            p = int(al[i, m])
-            if p >= 0:                                                     # (an empty slot: zero rows)
-                u[i] += torch.einsum("kt,ktc->kc", pt[i, :, m * JX:(m + 1) * JX], pool[p])
-    r = _softmax_last(amax.max(-1).values)                                 # [NQ,K]
-    return torch.einsum("gk,gkc->gc", r, u), logits, scale

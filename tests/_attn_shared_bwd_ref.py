@@ -6,7 +6,8 @@ Inputs are tests/_attn_shared_ref.make_case's with att_logits/W scaled by sqrt(6
 logits saturate from w = 512 on (all |x| = 1.000 in fp64, top-2 gaps down to 1e-13 at w = 2048), where the logit
 gradient vanishes -- a broken question pass would pass -- and the fp32 arg-max is arbitrary.
 
-Every case must satisfy `conditions` (tests/test_attn_shared_bwd_host.py asserts them per pinned seed in fp64), so that
+Every case must satisfy `conditions` (tests/_album_attn_ref.py, the album pool's at one album per question;
+tests/test_attn_shared_bwd_host.py asserts them per pinned seed in fp64), so that
 the GPU test excludes nothing: the first and second valid logit over j of every valid row, and the two largest amax
 over t of every (question, k), lie more than GAP apart, and under tanh fewer than 5 % of the valid logits have
 |x| > 0.99.  SEEDS holds, per case, the first seed of `seed_candidates` that qualifies.
@@ -17,10 +18,10 @@ go past one round of the plan's and the row pass's loops: `many` (A = 1500, NQ =
 `splits9` (nine T splits of the question pass)."""
 import torch
 
+from tests import _album_attn_ref as AR
 from tests import _attn_shared_ref as R
 
-GAP = 1e-5
-SAT_X, SAT_FRACTION = 0.99, 0.05
+GAP, SAT_X, SAT_FRACTION = AR.GAP, AR.SAT_X, AR.SAT_FRACTION
 SIMI_TANH = [(1, False), (2, True), (3, True)]
 ROW_TS = ["1", "7", "Rb-1", "Rb", "Rb+1", "63", "64", "65", "333"]
 
@@ -72,8 +73,7 @@ MIX_MASKED = "mix-simi2-masked"      # the case of the per-question comparison, 
 
 
 def seed_candidates(name):
-    base = sum(map(ord, name)) * 10
-    return [base + i for i in range(8)]
+    return AR.seed_candidates(name, 0, 8)
 
 
 # the first qualifying candidate per case (tests/test_attn_shared_bwd_host.py re-checks every one of them)
@@ -155,48 +155,10 @@ def reference(c):
     return dict(h_a=ha.detach(), a_logits=a.detach(), dh=dh, dq=q.grad, dW=W.grad.reshape(-1), db=b.grad.reshape(-1))
 
 
-def valid_mask(c):
-    """[NQ,K,T,JQ] bool: the entries exp_mask leaves alone"""
-    NQ, K, T, JQ = c["NQ"], c["K"], c["T"], c["JQ"]
-    if c["hm"] is None or c["qm"] is None:
-        return torch.ones(NQ, K, T, JQ, dtype=torch.bool)
-    return c["hm"][c["album"]][:, :, :, None] & c["qm"][:, None, None, :]
-
-
-def conditions(c, a_logits):
-    """(smallest top-2 gap over j in a valid row, smallest top-2 gap of amax over t in a (question, k), fraction of valid
-    logits with |x| > SAT_X); a gap that does not exist (one valid entry) counts as inf"""
-    v = valid_mask(c)
-    x = torch.where(v, a_logits, torch.full_like(a_logits, -float("inf")))
-    inf = float("inf")
-    jgap = inf
-    if c["JQ"] > 1:
-        top = torch.topk(x, 2, dim=-1).values                       # [NQ,K,T,2]
-        two = v.sum(-1) >= 2
-        if bool(two.any()):
-            jgap = float((top[..., 0] - top[..., 1])[two].min())
-    tgap = inf
-    amax = x.max(-1).values                                         # [NQ,K,T], -inf where the row is masked
-    if c["T"] > 1:
-        top = torch.topk(amax, 2, dim=-1).values
-        two = v.any(-1).sum(-1) >= 2
-        if bool(two.any()):
-            tgap = float((top[..., 0] - top[..., 1])[two].min())
-    sat = float((a_logits[v].abs() > SAT_X).double().mean()) if c["tanh"] and bool(v.any()) else 0.0
-    return jgap, tgap, sat
-
-
-def qualifies(c, a_logits):
-    jgap, tgap, sat = conditions(c, a_logits)
-    return jgap > GAP and tgap > GAP and sat < SAT_FRACTION
+valid_mask, conditions, qualifies = AR.shared(AR.valid_mask), AR.shared(AR.conditions), AR.shared(AR.qualifies)
 
 
 # ------------------------------------------------------------------ a width no kernel has (channel padding): w = 100
 def odd_width_case():
     c = R.make_case([2, 1], 2, 20, 5, 100, 2, True, 4242)
-    c["W"] = c["W"] * (64.0 / 100) ** 0.5
-    c["tanh"] = True
-    c["hm"][0, 0, :3] = True
-    c["qm"][c["NQ"] - 1, :2] = True
-    c["gout"] = torch.randn(c["NQ"], 100, generator=torch.Generator().manual_seed(99))
-    return c
+    return AR.train_inputs(c, c["hm"], True)         # (every (album, k) has a valid row: the parity's last line changes none)

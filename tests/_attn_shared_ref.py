@@ -2,13 +2,14 @@
 albums whose context rows [A,K,T,w] are held once, question i attending album[i].
 
 `reference` is the definition: gather the album's rows per question, then oracle.fvta_fused.attention_3d.
-`grouped` is an independent restatement in the order the kernels work in: the logits of ALL questions of an album from one
-[K*T, w] x [w, nq*JQ] product, written out from att_logits/W per similarity (not through the oracle's helpers), the mask
-as a select, the two softmaxes by hand.  tests/test_attn_shared_host.py holds the two against each other on every shape
-the GPU tests use (SPECS, and LOOP_SPECS: the shapes with many albums and many questions)."""
+`grouped` is an independent restatement in the order the kernels work in: tests/_album_attn_ref.grouped, the album pool's
+at one album per question.  tests/test_attn_shared_host.py holds the two against each other on every shape the GPU tests
+use (SPECS, and LOOP_SPECS: the shapes with many albums and many questions)."""
 import torch
 
-NEG = -1e30
+from tests import _album_attn_ref as AR
+
+NEG = AR.NEG
 SIMI_TANH = [(1, False), (2, True), (3, True), (4, False)]      # the parametrisation of tests/test_gpu_forward.py
 
 
@@ -139,15 +140,7 @@ def train_recipe(counts, K, T, JQ, w, simi, tanh, masked, seed, parity=True):
     stay clear of tanh's saturation at every width), d_h_a = randn of seed 99 and -- parity, as tests/test_gpu_backward.py --
     every (album, k) and every question partly valid (the fully masked ones carry fvta_attn_bwd's documented deviation)."""
     c = make_case(counts, K, T, JQ, w, simi, masked, seed)
-    c["W"] = c["W"] * (64.0 / w) ** 0.5
-    c["tanh"] = tanh
-    if masked and parity:
-        c["hm"][0, 0, :3] = True
-        if c["NQ"] > 1:
-            c["qm"][c["NQ"] - 1, :2] = True
-        c["hm"][:, :, 0] |= ~c["hm"].any(-1)            # (a short T can leave further (album, k) without a valid row)
-    c["gout"] = torch.randn(c["NQ"], w, generator=torch.Generator().manual_seed(99))
-    return c
+    return AR.train_inputs(c, c["hm"], tanh, parity)
 
 
 def loop_case(name, seed):
@@ -191,8 +184,7 @@ def loop_regime(name, c, plan, bwd_plan=None):
 
 
 # ------------------------------------------------------------------ references (fp64, CPU)
-def _dd(t):
-    return None if t is None else t.double()
+_dd = AR._dd
 
 
 def reference(c, tanh, block=None):
@@ -212,53 +204,7 @@ def reference(c, tanh, block=None):
                           add_tanh=tanh)
 
 
-def _softmax_last(x):
-    e = torch.exp(x - x.max(-1, keepdim=True).values)
-    return e / e.sum(-1, keepdim=True)
-
-
-def grouped(c, tanh):
-    """album by album: one product for all of the album's questions"""
-    h, q, al, simi = _dd(c["h"]), _dd(c["q"]), c["album"], c["simi"]
-    A, K, T, w = h.shape
-    NQ, JQ = q.shape[:2]
-    W = None if c["W"] is None else _dd(c["W"]).reshape(-1)
-    b = None if c["b"] is None else float(c["b"])
-    h_a = torch.zeros(NQ, w, dtype=torch.float64)
-    logits = torch.zeros(NQ, K, T, JQ, dtype=torch.float64)
-    for a in range(A):
-        qi = torch.nonzero(al == a).reshape(-1)
-        if qi.numel() == 0:
-            continue
-        nq = qi.numel()
-        H = h[a].reshape(K * T, w)
-        Q = q[qi].reshape(nq * JQ, w)
-        if simi == 1:        # [h, q, h*q] . W
-            x = (H * W[2 * w:]) @ Q.t() + (H @ W[:w])[:, None] + (Q @ W[w:2 * w])[None, :] + b
-        elif simi == 2:      # [h*q, (h-q)^2] . W
-            Wd = W[w:]
-            x = (H * (W[:w] - 2 * Wd)) @ Q.t() + ((H * H) @ Wd)[:, None] + ((Q * Q) @ Wd)[None, :] + b
-        elif simi == 3:      # [h, q, (h-q)^2, h*q] . W
-            Wd = W[2 * w:3 * w]
-            x = (H * (W[3 * w:] - 2 * Wd)) @ Q.t() + (H @ W[:w] + (H * H) @ Wd)[:, None] \
-                + (Q @ W[w:2 * w] + (Q * Q) @ Wd)[None, :] + b
-        else:                # cosine
-            Hn = H / torch.sqrt(torch.clamp((H * H).sum(1, keepdim=True), min=1e-12))
-            Qn = Q / torch.sqrt(torch.clamp((Q * Q).sum(1, keepdim=True), min=1e-12))
-            x = Hn @ Qn.t()
-        if tanh and simi != 4:
-            x = torch.tanh(x)
-        x = x.reshape(K, T, nq, JQ).permute(2, 0, 1, 3)                 # [nq,K,T,JQ]
-        if c["hm"] is not None and c["qm"] is not None:
-            valid = c["hm"][a][None, :, :, None] & c["qm"][qi][:, None, None, :]
-            x = torch.where(valid, x, torch.full_like(x, NEG))
-        amax = x.max(-1).values                                          # [nq,K,T]
-        p = _softmax_last(amax)
-        u = torch.einsum("gkt,ktc->gkc", p, h[a])
-        r = _softmax_last(amax.max(-1).values)                           # [nq,K]
-        h_a[qi] = torch.einsum("gk,gkc->gc", r, u)
-        logits[qi] = x
-    return h_a, logits
+grouped = AR.shared(AR.grouped)          # album by album, one product for all of the album's questions -> (h_a, a_logits)
 
 
 # ------------------------------------------------------------------ the tiny end-to-end graph

@@ -4,9 +4,10 @@
 `reference` is the definition: fp64 autograd of oracle.fvta_fused.time_warp_closed -> attention_3d on h[album]; the gather's
 own gradient sums the row gradients per album.
 `factored_backward` is the restatement the kernels implement, written out by hand without autograd and parametrised by
-dtype: the warp as one scalar s[q,t] whose only term that reads the rows, the energy e [A,T], belongs to the album; the
-gradient of s per (question, k, position) from lin at the winning column and r2; dz, de, dv and the parameter gradients
-from there.  tests/test_attn_shared_tw_bwd_host.py holds the two against each other at 1e-9 on every case.
+dtype (tests/_album_attn_ref.factored_backward, the album pool's at one album per question): the warp as one scalar
+s[q,t] whose only term that reads the rows, the energy e [A,T], belongs to the album; the gradient of s per (question, k,
+position) from lin at the winning column and r2; dz, de, dv and the parameter gradients from there.
+tests/test_attn_shared_tw_bwd_host.py holds the two against each other at 1e-9 on every case.
 
 Inputs: tests/_attn_shared_ref.train_recipe plus tests/_attn_shared_tw_ref.add_warp, with att_logits/W FURTHER DIVIDED BY
 cmax^2, cmax the largest count of the case's warp (2 ceil(window_t) + 1 for type 5, T for types 1 / 3 / 4, 1 for type 2):
@@ -17,10 +18,9 @@ satisfies tests/_attn_shared_bwd_ref.conditions (top-2 gaps over j and over t ab
 test excludes an entry -- after three cases gave way where 32 candidates held none (the division shrinks the gaps too,
 and 1e-5 is absolute): `mix-simi1-open` runs at T = 20, `tiles-w64` and `many` at window 0.5; _specs() says why at each.
 SEEDS pins, per case, the first qualifying candidate."""
-import math
-
 import torch
 
+from tests import _album_attn_ref as AR
 from tests import _attn_shared_bwd_ref as B
 from tests import _attn_shared_ref as R
 from tests import _attn_shared_tw_ref as TW
@@ -30,10 +30,7 @@ WINDOW_T = TW.WINDOW_T
 SIMI_TANH = B.SIMI_TANH
 conditions, qualifies, valid_mask = B.conditions, B.qualifies, B.valid_mask
 GRAD_KEYS = ("dh", "dq", "dlq", "dW", "db", "dWH_W", "dWH_b", "dWC_W", "dWC_b")
-# (rtol, atol x max(1, max|ref|)): tests/test_gpu_attn_shared_bwd.py's for the attention's gradients,
-# tests/test_gpu_timewarp.py's for the warp's
-TOL = dict(dh=(1e-4, 1e-5), dq=(1e-4, 1e-5), dW=(1e-4, 1e-5), db=(1e-4, 1e-5),
-           dlq=(2e-4, 2e-5), dWH_W=(2e-4, 2e-5), dWH_b=(2e-4, 2e-5), dWC_W=(2e-4, 2e-5), dWC_b=(2e-4, 2e-5))
+TOL, within, cmax, _count = AR.GRAD_TOL, AR.within, AR.cmax, AR.count_of
 
 
 # (name, counts(G), K, T(Rb), JQ, w, simi, tanh, masked, warp_type, window_t)
@@ -85,8 +82,7 @@ MIX_MASKED = "mix-simi2-masked"      # the case of the per-question comparison, 
 def seed_candidates(name, n=8):
     """eight candidates; tests/test_attn_shared_tw_bwd_host.py allows the first 32 (mix-simi2-open and mix-simi3-open needed
     them: candidates 24 and 29)"""
-    base = sum(map(ord, name)) * 10 + 3
-    return [base + i for i in range(n)]
+    return AR.seed_candidates(name, 3, n)
 
 
 # the first qualifying candidate per case (tests/test_attn_shared_tw_bwd_host.py re-checks every one of them)
@@ -158,15 +154,6 @@ def shape_of(name):
     return counts(G), K, T(Rb), JQ, w, simi, tanh, masked, wt, win
 
 
-def cmax(T, warp_type, window_t):
-    """the largest count of the warp: the factor the rows can grow by"""
-    if warp_type == 2:
-        return 1
-    if warp_type == 5:
-        return 2 * int(math.ceil(window_t)) + 1
-    return T
-
-
 def _finish(c, seed, warp_type, window_t):
     c = TW.add_warp(c, seed, warp_type, window_t)
     c["W"] = c["W"] / float(cmax(c["T"], warp_type, window_t)) ** 2
@@ -196,10 +183,6 @@ def plans_of(c):
     return B.plans_of(c)
 
 
-def _count(c, dtype):
-    return TW._count(c["T"], c["warp_type"], c["window_t"], dtype)
-
-
 # ------------------------------------------------------------------ the definition
 def reference(c, grads=True):
     """fp64 (autograd) -> dict(h_a, a_logits, scale, dh [A,K,T,w], dq, dlq, dW [F], db [1], dWH_W [2w,w], dWH_b, dWC_W [w],
@@ -224,103 +207,5 @@ def reference(c, grads=True):
 
 
 # ------------------------------------------------------------------ the restatement, by hand
-def factored_backward(c, dtype=torch.float64):
-    """the same keys as `reference`, from the formulas the kernels implement: no autograd, no [NQ,K,T,w] tensor"""
-    cv = lambda x: x.to(dtype)
-    h, q, lq, g, al = cv(c["h"]), cv(c["q"]), cv(c["lq"]), cv(c["gout"]), c["album"]
-    simi, tanh = c["simi"], c["tanh"]
-    A, K, T, w = h.shape
-    NQ, JQ = q.shape[:2]
-    W, b = cv(c["W"]).reshape(-1), cv(c["b"])[0]
-    zero = torch.zeros(w, dtype=dtype)
-    if simi == 1:            # [h, q, h*q] . W
-        Rh, Cq, U, R2 = W[:w], W[w:2 * w], W[2 * w:], zero
-    elif simi == 2:          # [h*q, (h-q)^2] . W
-        Rh, Cq, U, R2 = zero, zero, W[:w] - 2 * W[w:], W[w:]
-    else:                    # [h, q, (h-q)^2, h*q] . W
-        Rh, Cq, U, R2 = W[:w], W[w:2 * w], W[3 * w:] - 2 * W[2 * w:3 * w], W[2 * w:3 * w]
-    WH, WHb, WC, WCb = cv(c["WH_W"])[:w], cv(c["WH_b"]), cv(c["WC_W"]).reshape(w), cv(c["WC_b"])[0]
-    v = WH @ WC
-    s0 = WHb @ WC + WCb
-    e = ((h * h) @ v).sum(1)                                                  # [A,T]
-    cnt = _count(c, dtype)
-    tz = torch.tanh(e[al] + K * (s0 + lq @ WC)[:, None])                      # [NQ,T]
-    s_all = tz * cnt[None, :]
-    masked = c["hm"] is not None and c["qm"] is not None
-    dh = torch.zeros_like(h)
-    dq, dz = torch.zeros_like(q), torch.zeros(NQ, T, dtype=dtype)
-    h_a, logits = torch.zeros(NQ, w, dtype=dtype), torch.zeros(NQ, K, T, JQ, dtype=dtype)
-    dRh, dR2, dU, dCq, dC2 = (torch.zeros(w, dtype=dtype) for _ in range(5))
-    db, db_pooled = torch.zeros(1, dtype=dtype), torch.zeros(1, dtype=dtype)
-    for i in range(NQ):
-        a = int(al[i])
-        H, Q, gi, s = h[a], q[i], g[i], s_all[i][None, :]                     # [K,T,w], [JQ,w], [w], [1,T]
-        Qs = Q * U
-        lin = H @ Qs.t() + (H @ Rh)[..., None]                                # [K,T,JQ]
-        r2 = (H * H) @ R2                                                     # [K,T]
-        ct = Q @ Cq + (Q * Q) @ R2 + b
-        x = s[..., None] * lin + (s * s * r2)[..., None] + ct
-        if tanh:
-            x = torch.tanh(x)
-        if masked:
-            x = torch.where(c["hm"][a][:, :, None] & c["qm"][i][None, None, :], x, torch.full_like(x, NEG))
-        logits[i] = x
-        amax, jmax = x.max(-1)                                                # [K,T]
-        M = amax.max(-1).values                                               # [K]
-        ex = torch.exp(amax - M[:, None])
-        p = ex / ex.sum(-1, keepdim=True)
-        u = torch.einsum("kt,ktc->kc", p * s, H)
-        r = torch.softmax(M, 0)
-        h_a[i] = r @ u
-        # backward
-        gu = u @ gi
-        dsk = r * (gu - (r * gu).sum())
-        top = amax == M[:, None]
-        allmasked = M == NEG
-        dss = torch.where(allmasked, torch.zeros_like(dsk), dsk / top.sum(-1))
-        gh = H @ gi                                                           # [K,T]
-        pr = p * r[:, None]
-        damax = pr * (s * gh - gu[:, None]) + top * dss[:, None]
-        damax = torch.where((pr != 0) & ~allmasked[:, None], damax, torch.zeros_like(damax))
-        dx = damax * (1 - amax * amax) if tanh else damax
-        dx = torch.where(damax != 0, dx, torch.zeros_like(dx))
-        Qsj = Qs[jmax]                                                        # [K,T,w]
-        dh[a] += (s * pr)[..., None] * gi + (dx * s)[..., None] * (Qsj + Rh) + 2 * (dx * s * s)[..., None] * R2 * H
-        ds = pr * gh + dx * (lin.gather(-1, jmax[..., None])[..., 0] + 2 * s * r2)
-        dxsH = ((dx * s)[..., None] * H).reshape(K * T, w)
-        dQs = torch.zeros(JQ, w, dtype=dtype).index_add_(0, jmax.reshape(-1), dxsH)
-        dct = torch.zeros(JQ, dtype=dtype).index_add_(0, jmax.reshape(-1), dx.reshape(-1))
-        dRh += dxsH.sum(0)
-        dR2 += ((dx * s * s)[..., None] * H * H).sum((0, 1))
-        dq[i] = U * dQs + dct[:, None] * (Cq + 2 * R2 * Q)
-        dU += (dQs * Q).sum(0)
-        dCq += (dct[:, None] * Q).sum(0)
-        dC2 += (dct[:, None] * Q * Q).sum(0)
-        db += dct.sum()
-        if tanh:             # the form the kernels take for db: a question's damax sum to zero over (k, t)
-            db_pooled -= torch.where(damax != 0, damax * amax * amax, torch.zeros_like(damax)).sum()
-        dz[i] = cnt * (1 - tz[i] * tz[i]) * ds.sum(0)
-    de = torch.zeros(A, T, dtype=dtype).index_add_(0, al, dz)
-    D = dz.sum(1)
-    ds0 = K * D.sum()
-    dh += 2 * de[:, None, :, None] * v * h                                    # every k, masked rows too: e sums them
-    dv = torch.einsum("at,aktc->c", de, h * h)
-    dWH_W = torch.zeros(2 * w, w, dtype=dtype)
-    dWH_W[:w] = dv[:, None] * WC[None, :]
-    dD = dR2 + dC2
-    if simi == 1:
-        dW = torch.cat([dRh, dCq, dU])
-    elif simi == 2:
-        dW = torch.cat([dU, dD - 2 * dU])
-    else:
-        dW = torch.cat([dRh, dCq, dD - 2 * dU, dU])
-    return dict(h_a=h_a, a_logits=logits, scale=s_all, dh=dh, dq=dq, dlq=K * D[:, None] * WC[None, :], dW=dW, db=db, dWH_W=dWH_W,
-                dWH_b=ds0 * WC, dWC_W=WH.t() @ dv + ds0 * WHb + K * (D @ lq), dWC_b=ds0.reshape(1), db_pooled=db_pooled)
-
-
-def within(got, want, key):
-    """|got - want| <= atol max(1, max|want|) + rtol |want| at `key`'s GPU tolerance -> (ok, worst ratio)"""
-    rtol, atol = TOL[key]
-    got, want = got.detach().cpu().double(), want.double()
-    ratio = ((got - want).abs() / (atol * max(1.0, float(want.abs().max())) + rtol * want.abs())).max()
-    return bool(ratio <= 1.0), float(ratio)
+# (c, dtype=torch.float64) -> the keys of `reference` (and db_pooled, dz, de): no autograd, no [NQ,K,T,w] tensor
+factored_backward = AR.shared(AR.factored_backward)

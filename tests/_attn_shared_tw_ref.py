@@ -4,22 +4,22 @@ state lq[i] (model_v2.py:953-1009, use_time_warp without use_time_warp_att).
 
 `reference` is the definition: gather the album's rows per question, oracle.fvta_fused.time_warp_closed, then
 oracle.fvta_fused.attention_3d on the warped rows.
-`factored` is the restatement the kernels compute, written out independently and parametrised by dtype: the warp as one
-scalar per (question, position), whose only term that reads the rows -- the energy e [A,T] -- is taken per ALBUM, the
-scalar passed through the bilinear form of the logits and through the weighted sum; no [NQ,K,T,w] tensor.
+`factored` is the restatement the kernels compute, written out independently and parametrised by dtype
+(tests/_album_attn_ref.factored, the album pool's at one album per question): the warp as one scalar per (question,
+position), whose only term that reads the rows -- the energy e [A,T] -- is taken per ALBUM, the scalar passed through the
+bilinear form of the logits and through the weighted sum; no [NQ,K,T,w] tensor.
 tests/test_attn_shared_tw_host.py holds the two against each other on every shape the GPU tests use.
 
 Inputs: tests/_attn_shared_ref.make_case, and the warp parameters by the recipe of tests/test_gpu_timewarp.py (WH/W scaled
 0.3 / sqrt(w), WC/W 0.5 / sqrt(w), biases 0.1, lq 0.5)."""
-import math
-
 import torch
 
+from tests import _album_attn_ref as AR
 from tests import _attn_shared_ref as R
 
 NEG = R.NEG
 WINDOW_T = 2.3
-TOL = dict(h_a=(1e-4, 1e-5), a_logits=(1e-4, 2e-5), scale=(1e-4, 1e-5))       # (rtol, atol): tests/test_gpu_attn_shared.py's
+TOL, within, _count, _dd = AR.TOL, AR.within, AR.count, AR._dd
 
 
 # ------------------------------------------------------------------ inputs
@@ -97,10 +97,6 @@ def build_case(name):
 
 
 # ------------------------------------------------------------------ references (CPU)
-def _dd(t):
-    return None if t is None else t.double()
-
-
 def reference(c, block=None):
     """the definition, fp64 -> (h_a [NQ,w], a_logits [NQ,K,T,JQ], scale [NQ,T]); block: that many questions at a time"""
     from oracle import fvta_fused as F
@@ -122,92 +118,5 @@ def reference(c, block=None):
     return h_a, a, cc * cnt[None, :]
 
 
-def _count(T, warp_type, window_t, dtype):
-    t = torch.arange(T)
-    if warp_type == 1:
-        n = torch.full((T,), T)
-    elif warp_type == 2:
-        n = torch.ones(T, dtype=torch.int64)
-    elif warp_type == 3:
-        n = t + 1
-    elif warp_type == 4:
-        n = T - t
-    else:
-        win = int(math.ceil(window_t))
-        n = torch.clamp(t + win, max=T - 1) - torch.clamp(t - win, min=0) + 1
-    return n.to(dtype)
-
-
-def _softmax_last(x):
-    e = torch.exp(x - x.max(-1, keepdim=True).values)
-    return e / e.sum(-1, keepdim=True)
-
-
-def energy(c, dtype=torch.float64):
-    """e [A,T] = sum_k sum_c v[c] h[a,k,t,c]^2, v = WH[:w] WC"""
-    w = c["w"]
-    v = c["WH_W"].to(dtype)[:w] @ c["WC_W"].to(dtype).reshape(w)
-    h = c["h"].to(dtype)
-    return ((h * h) @ v).sum(1)
-
-
-def factored(c, dtype=torch.float64):
-    """the warp as a scalar per (question, position): energy per album, scale per question, the scalar through the bilinear
-    form and the weighted sum -> (h_a, a_logits, scale) in `dtype`"""
-    cv = lambda t: None if t is None else t.to(dtype)
-    h, q, lq, al, simi, tanh = cv(c["h"]), cv(c["q"]), cv(c["lq"]), c["album"], c["simi"], c["tanh"]
-    A, K, T, w = h.shape
-    NQ, JQ = q.shape[:2]
-    WC = cv(c["WC_W"]).reshape(w)
-    s0 = cv(c["WH_b"]) @ WC + cv(c["WC_b"])[0]
-    e = energy(c, dtype)
-    scale = torch.tanh(e[al] + K * (s0 + lq @ WC)[:, None]) * _count(T, c["warp_type"], c["window_t"], dtype)[None, :]
-    W = None if c["W"] is None else cv(c["W"]).reshape(-1)
-    b = None if c["b"] is None else cv(c["b"])[0]
-    zero = torch.zeros(w, dtype=dtype)
-    if simi == 1:            # [h, q, h*q] . W
-        Rh, Cq, U, R2 = W[:w], W[w:2 * w], W[2 * w:], zero
-    elif simi == 2:          # [h*q, (h-q)^2] . W
-        Rh, Cq, U, R2 = zero, zero, W[:w] - 2 * W[w:], W[w:]
-    elif simi == 3:          # [h, q, (h-q)^2, h*q] . W
-        Rh, Cq, U, R2 = W[:w], W[w:2 * w], W[3 * w:] - 2 * W[2 * w:3 * w], W[2 * w:3 * w]
-    h_a = torch.zeros(NQ, w, dtype=dtype)
-    logits = torch.zeros(NQ, K, T, JQ, dtype=dtype)
-    for a in range(A):
-        qi = torch.nonzero(al == a).reshape(-1)
-        nq = qi.numel()
-        if nq == 0:
-            continue
-        H = h[a].reshape(K * T, w)
-        Q = q[qi].reshape(nq * JQ, w)
-        s = scale[qi][:, None, :].expand(nq, K, T)                                  # [nq,K,T]
-        if simi == 4:
-            Qn = Q / torch.sqrt(torch.clamp((Q * Q).sum(1, keepdim=True), min=1e-12))
-            dot = (H @ Qn.t()).reshape(K, T, nq, JQ).permute(2, 0, 1, 3)            # [nq,K,T,JQ]
-            n2 = (H * H).sum(1).reshape(K, T)[None]
-            x = dot * (s / torch.sqrt(torch.clamp(s * s * n2, min=1e-12)))[..., None]
-        else:
-            dot = (H @ (Q * U).t()).reshape(K, T, nq, JQ).permute(2, 0, 1, 3)
-            ct = ((Q @ Cq + (Q * Q) @ R2) + b).reshape(nq, JQ)
-            r1, r2 = (H @ Rh).reshape(K, T)[None], ((H * H) @ R2).reshape(K, T)[None]
-            x = s[..., None] * (dot + r1[..., None]) + (s * s * r2)[..., None] + ct[:, None, None, :]
-            if tanh:
-                x = torch.tanh(x)
-        if c["hm"] is not None and c["qm"] is not None:
-            valid = c["hm"][a][None, :, :, None] & c["qm"][qi][:, None, None, :]
-            x = torch.where(valid, x, torch.full_like(x, NEG))
-        amax = x.max(-1).values
-        p = _softmax_last(amax) * s
-        u = torch.einsum("gkt,ktc->gkc", p, h[a])
-        r = _softmax_last(amax.max(-1).values)
-        h_a[qi] = torch.einsum("gk,gkc->gc", r, u)
-        logits[qi] = x
-    return h_a, logits, scale
-
-
-def within(got, want, what):
-    """|got - want| <= atol + rtol |want| at `what`'s GPU tolerance -> (ok, worst excess ratio)"""
-    rtol, atol = TOL[what]
-    got, want = got.double(), want.double()
-    ratio = ((got - want).abs() / (atol + rtol * want.abs())).max()
-    return bool(ratio <= 1.0), float(ratio)
+energy = AR.shared(AR.energy)            # e [A,T] = sum_k sum_c v[c] h[a,k,t,c]^2, v = WH[:w] WC
+factored = AR.shared(AR.factored)        # (c, dtype=torch.float64) -> (h_a, a_logits, scale) in `dtype`

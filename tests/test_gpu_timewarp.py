@@ -1,5 +1,7 @@
 """GPU parity of the time warp (model_v2.py:953-1009, closed form) forward and backward vs the oracle
 (whose closed form is itself checked against the literal O(T^2) restatement in tests/test_oracle_cross.py)."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -16,10 +18,9 @@ _TW_SHAPES = [(2, 3, 17, 64), (3, 6, 50, 256), (1, 2, 9, 512), (1, 8, 5, 1024), 
 _TW_CASES = [s + (wt,) for wt in (1, 2, 3, 4, 5) for s in _TW_SHAPES] + [(2, 2, 1100, 256, wt) for wt in (2, 5)]
 
 
-@pytest.mark.parametrize("N,K,T,w,warp_type", _TW_CASES)
-def test_timewarp_forward_backward(warp_type, N, K, T, w):
-    from fvta_memexqa_amd import ops
-    from oracle import fvta_fused as F
+def _tw_inputs(N, K, T, w, warp_type):
+    """hall [N,K,1,T,w], lq, WH_W, WH_b, WC_W [w,1], WC_b, the upstream gradient on warp_h and -- drawn last -- the one on
+    scale [N,T] (what the attention hands back under use_time_warp_att)"""
     g = torch.Generator().manual_seed(warp_type * 100 + T)
     hall = torch.randn(N, K, 1, T, w, generator=g) * 0.5
     lq = torch.randn(N, w, generator=g) * 0.5
@@ -28,6 +29,15 @@ def test_timewarp_forward_backward(warp_type, N, K, T, w):
     WC_W = torch.randn(w, 1, generator=g) * (0.5 / w ** 0.5)
     WC_b = torch.randn(1, generator=g) * 0.1
     gout = torch.randn(N, K, 1, T, w, generator=g)
+    g2 = torch.randn(N, T, generator=g)
+    return (hall, lq, WH_W, WH_b, WC_W, WC_b), gout, g2
+
+
+@pytest.mark.parametrize("N,K,T,w,warp_type", _TW_CASES)
+def test_timewarp_forward_backward(warp_type, N, K, T, w):
+    from fvta_memexqa_amd import ops
+    from oracle import fvta_fused as F
+    (hall, lq, WH_W, WH_b, WC_W, WC_b), gout, _ = _tw_inputs(N, K, T, w, warp_type)
     leaves = [t.double().requires_grad_() for t in (hall, lq, WH_W, WH_b, WC_W, WC_b)]
     ref, c = F.time_warp_closed(*leaves, warp_type=warp_type, window_t=2.3)
     (ref * gout.double()).sum().backward()
@@ -47,6 +57,184 @@ def test_timewarp_forward_backward(warp_type, N, K, T, w):
                             (dWC, leaves[4].grad.reshape(-1), "dWC_W"), (dWCb, leaves[5].grad, "dWC_b")]:
         wv = want.numpy()
         np.testing.assert_allclose(got.cpu().numpy(), wv, rtol=2e-4, atol=2e-5 * max(1.0, np.abs(wv).max()), err_msg=name)
+
+
+_TW_GRADS = ("d_hall", "d_lq", "dWH_W", "dWH_b", "dWC_W", "dWC_b")
+
+
+@functools.lru_cache(maxsize=2)          # (neighbouring cases of one parametrisation share an entry; the long ones are 36 MB a tensor)
+def _tw_reference(N, K, T, w, warp_type, window_t, modes, seed_type=None):
+    """fp64 oracle on _tw_inputs: warp_h [N,K,T,w], c, scale = c * the band's row sums, and for each of `modes` the six
+    gradients (in the kernels' layout) of  <warp_h, gout>  ("warp"),  <scale, g2>  ("scale": what d_scale_att alone
+    brings in) or their sum ("both").  Shared between tests: read only."""
+    from oracle import fvta_fused as F
+    leaves, gout, g2 = _tw_inputs(N, K, T, w, seed_type or warp_type)
+    L = [t.double().requires_grad_() for t in leaves]
+    warp, c = F.time_warp_closed(*L, warp_type=warp_type, window_t=window_t)
+    scale = c * F.time_indication_band(T, warp_type, window_t, torch.float64).sum(1)
+    loss = {"warp": (warp * gout.double()).sum(), "scale": (scale * g2.double()).sum()}
+    loss["both"] = loss["warp"] + loss["scale"]
+    grads = {}
+    for m in modes:
+        gs = torch.autograd.grad(loss[m], L, retain_graph=True)
+        grads[m] = [gs[0].reshape(N, K, T, w), gs[1], gs[2], gs[3], gs[4].reshape(-1), gs[5]]
+    return warp.detach().reshape(N, K, T, w), c.detach(), scale.detach(), grads
+
+
+def _tw_on_device(N, K, T, w, warp_type):
+    """_tw_inputs as the kernels take them: the six operands, d_warp and d_scale_att"""
+    cu = lambda t: t.cuda().contiguous()
+    (hall, lq, WH_W, WH_b, WC_W, WC_b), gout, g2 = _tw_inputs(N, K, T, w, warp_type)
+    dev = (cu(hall.reshape(N, K, T, w)), cu(lq), cu(WH_W), cu(WH_b), cu(WC_W.reshape(-1)), cu(WC_b))
+    return dev, cu(gout.reshape(N, K, T, w)), cu(g2)
+
+
+def _tw_forward(N, K, T, w, warp_type, window_t, dev):
+    from fvta_memexqa_amd import ops
+    op = ops.TimeWarp(N, K, T, w, warp_type, window_t)
+    warp = torch.full_like(dev[0], float("nan"))
+    op.forward(*dev, warp)
+    return op, warp
+
+
+def _tw_backward(op, dev, d_warp, d_scale_att, prefill=0.0):
+    """d_hall (prefilled with NaN: it is stored) and the five accumulated gradients on top of `prefill`"""
+    outs = [torch.full_like(dev[0], float("nan"))] + [torch.full_like(t, prefill) for t in dev[1:]]
+    op.backward(*dev, d_warp, *outs, d_scale_att=d_scale_att)
+    return outs
+
+
+def _tw_check_forward(op, warp, ref, tag):
+    np.testing.assert_allclose(warp.cpu().numpy(), ref[0].numpy(), rtol=1e-4, atol=1e-5, err_msg=tag + ": warp_h")
+    np.testing.assert_allclose(op.c.cpu().numpy(), ref[1].numpy(), rtol=1e-4, atol=1e-6, err_msg=tag + ": c")
+    np.testing.assert_allclose(op.scale.cpu().numpy(), ref[2].numpy(), rtol=1e-4, atol=1e-5, err_msg=tag + ": scale")
+
+
+def _tw_check_grads(outs, want, tag, on_top_of=0.0):
+    for got, ref, name in zip(outs, want, _TW_GRADS):
+        wv = ref.numpy()
+        assert bool(torch.isfinite(got).all()), "%s: %s is not finite" % (tag, name)
+        np.testing.assert_allclose(got.cpu().numpy(), wv + (0.0 if name == "d_hall" else on_top_of), rtol=2e-4,
+                                   atol=2e-5 * max(1.0, np.abs(wv).max()), err_msg="%s: %s" % (tag, name))
+    w = outs[2].shape[1]
+    assert bool((outs[2][w:] == on_top_of).all()), "%s: rows w..2w of dWH_W see a zero feature and are never touched" % tag
+
+
+def _tw_same_bits(a, b, tag, names=("warp_h", "c", "scale") + _TW_GRADS):
+    for x, y, name in zip(a, b, names):
+        assert x.dtype == torch.float32 and torch.equal(x.view(torch.int32), y.view(torch.int32)), "%s: %s" % (tag, name)
+
+
+# Every loop of the kernels past its first round.  Types 2 and 5 only, as for the long case above.
+#   (3,3,300,64)    separate kernels: 2700 rows > the 2048 workgroups of tw_apply_bwd_kernel (n changes inside a workgroup's stride, dvacc
+#                   carries over two rows), four blocks of tw_dz_kernel, T > 256 in tw_reduce_kernel's dsq
+#   (1,9,250,256)   K > TW_KMAX at a fused width: the separate kernels at w = 256, 2250 rows
+#   (2,1,1100,2048) the G4 = 8 forward past its 2048 wave slots; the separate backward with both rounds of c0 += 1024, 2200 rows
+#   (2,2,1100,512), (2,2,1100,1024)   G4 = 2 and 4, forward and backward, past the wave slots
+_TW_LONG = [(3, 3, 300, 64), (1, 9, 250, 256), (2, 1, 1100, 2048), (2, 2, 1100, 512), (2, 2, 1100, 1024)]
+
+
+@pytest.mark.parametrize("N,K,T,w,warp_type,att", [s + (wt, att) for s in _TW_LONG for wt in (2, 5) for att in (False, True)])
+def test_timewarp_loops_past_one_round(N, K, T, w, warp_type, att):
+    ref = _tw_reference(N, K, T, w, warp_type, 2.3, ("warp", "both"))
+    dev, d_warp, g2 = _tw_on_device(N, K, T, w, warp_type)
+    op, warp = _tw_forward(N, K, T, w, warp_type, 2.3, dev)
+    _tw_check_forward(op, warp, ref, "forward")
+    outs = _tw_backward(op, dev, d_warp, g2 if att else None)
+    _tw_check_grads(outs, ref[3]["both" if att else "warp"], "backward with d_scale_att" if att else "backward")
+
+
+# N > 256: the second round of n += 256 in tw_param_bwd_kernel (dWC_W and d_lq [N,w] are what it feeds), o past w + 256 in
+# tw_vec_kernel, w + N blocks of tw_reduce_kernel
+@pytest.mark.parametrize("N,K,T,w,warp_type", [s + (wt,) for s in [(300, 1, 3, 64), (260, 2, 2, 256)] for wt in (1, 2, 3, 4, 5)])
+def test_timewarp_many_questions(N, K, T, w, warp_type):
+    ref = _tw_reference(N, K, T, w, warp_type, 2.3, ("both",))
+    dev, d_warp, g2 = _tw_on_device(N, K, T, w, warp_type)
+    op, warp = _tw_forward(N, K, T, w, warp_type, 2.3, dev)
+    _tw_check_forward(op, warp, ref, "N = %d" % N)
+    _tw_check_grads(_tw_backward(op, dev, d_warp, g2), ref[3]["both"], "N = %d" % N)
+
+
+@pytest.mark.parametrize("N,K,T,w,warp_type",
+                         [s + (wt,) for s in [(2, 3, 17, 256), (1, 2, 9, 512), (1, 8, 5, 1024)] for wt in (1, 2, 3, 4, 5)])
+def test_timewarp_scale_gradient_through_the_fused_backward(N, K, T, w, warp_type):
+    """d_scale_att enters tw_bwd_fused_kernel (G4 = 1, 2, 4) in a line of its own.  The second run has it as the ONLY upstream
+    gradient (d_warp = 0: d_hall is 2 v h dz alone), so its sign and scale cannot hide behind the larger row term."""
+    ref = _tw_reference(N, K, T, w, warp_type, 2.3, ("both", "scale"))
+    dev, d_warp, g2 = _tw_on_device(N, K, T, w, warp_type)
+    op, warp = _tw_forward(N, K, T, w, warp_type, 2.3, dev)
+    _tw_check_forward(op, warp, ref, "forward")
+    _tw_check_grads(_tw_backward(op, dev, d_warp, g2), ref[3]["both"], "upstream on warp_h and scale")
+    _tw_check_grads(_tw_backward(op, dev, torch.zeros_like(d_warp), g2), ref[3]["scale"], "upstream on scale only")
+
+
+# tw_count at its edges, on the separate and the fused kernels: a single position (every count is 1), and for the band a window
+# of 0 (the diagonal), an integer window (ceil must not add one) and one wider than the sequence (both ends clamp at every t)
+_TW_EDGES = [(2, 2, 1, w, wt, 2.3) for w in (64, 256) for wt in (1, 2, 3, 4, 5)] + \
+            [(2, 2, 6, w, 5, win) for w in (64, 256) for win in (0.0, 1.0, 7.5)]
+
+
+@pytest.mark.parametrize("N,K,T,w,warp_type,window_t", _TW_EDGES)
+def test_timewarp_count_edges(N, K, T, w, warp_type, window_t):
+    ref = _tw_reference(N, K, T, w, warp_type, window_t, ("both",))
+    dev, d_warp, g2 = _tw_on_device(N, K, T, w, warp_type)
+    op, warp = _tw_forward(N, K, T, w, warp_type, window_t, dev)
+    _tw_check_forward(op, warp, ref, "window %g" % window_t)
+    _tw_check_grads(_tw_backward(op, dev, d_warp, g2), ref[3]["both"], "window %g" % window_t)
+
+
+@pytest.mark.parametrize("w", [64, 256])
+@pytest.mark.parametrize("window_t,same_as", [(0.0, 2), (7.5, 1)])
+def test_timewarp_band_at_its_ends_is_the_diagonal_and_all_time(window_t, same_as, w):
+    """On T = 6 the band of window 0.0 counts what type 2 counts and the band of window 7.5 what type 1 counts: equal floats into
+    the same arithmetic, so warp_h, c, scale and every gradient have the same bits."""
+    N, K, T = 2, 2, 6
+    dev, d_warp, g2 = _tw_on_device(N, K, T, w, 5)
+    runs = []
+    for warp_type, win in ((5, window_t), (same_as, 2.3)):
+        op, warp = _tw_forward(N, K, T, w, warp_type, win, dev)
+        runs.append([warp, op.c, op.scale] + _tw_backward(op, dev, d_warp, g2))
+    _tw_same_bits(runs[0], runs[1], "type 5 with window %g against type %d" % (window_t, same_as))
+
+
+# What the kernels' comments promise, one shape per path: the separate kernels past one round, the fused G4 = 1, 2, 4, and
+# w = 2048 (fused forward, separate backward).  Type 5 with d_scale_att.
+_TW_PATHS = [(3, 3, 300, 64), (2, 3, 17, 256), (1, 2, 9, 512), (1, 8, 5, 1024), (1, 2, 5, 2048)]
+
+
+def _tw_plain_run(N, K, T, w):
+    dev, d_warp, g2 = _tw_on_device(N, K, T, w, 5)
+    op, warp = _tw_forward(N, K, T, w, 5, 2.3, dev)
+    return dev, d_warp, g2, op, [warp, op.c, op.scale] + _tw_backward(op, dev, d_warp, g2)
+
+
+@pytest.mark.parametrize("N,K,T,w", _TW_PATHS)
+def test_timewarp_backward_owes_nothing_to_the_workspace(N, K, T, w):
+    """The backward recomputes v, s0 and sq, and every wave slot or workgroup stores its dv partials -- those without work
+    zeros: with the workspace overwritten by 0xFF bytes (NaN to any reader) after the forward, and again before a second
+    backward, every output has the bits of the run that left the workspace alone."""
+    dev, d_warp, g2, _, plain = _tw_plain_run(N, K, T, w)
+    op, warp = _tw_forward(N, K, T, w, 5, 2.3, dev)
+    for which in ("first", "second"):
+        op.work.view(torch.uint8).fill_(0xFF)
+        _tw_same_bits([warp, op.c, op.scale] + _tw_backward(op, dev, d_warp, g2), plain, which + " backward on a refilled workspace")
+
+
+@pytest.mark.parametrize("N,K,T,w", _TW_PATHS)
+def test_timewarp_backward_is_repeatable(N, K, T, w):
+    """no atomics anywhere: fixed partial sums folded in a fixed order"""
+    dev, d_warp, g2, op, plain = _tw_plain_run(N, K, T, w)
+    _tw_same_bits(_tw_backward(op, dev, d_warp, g2), plain[3:], "a second backward", _TW_GRADS)
+
+
+@pytest.mark.parametrize("N,K,T,w", _TW_PATHS)
+def test_timewarp_backward_stores_d_hall_and_accumulates_the_rest(N, K, T, w):
+    """d_hall comes back finite from a NaN prefill; d_lq and the four parameter gradients come back as prefill + gradient, rows
+    w..2w of dWH_W as the prefill exactly"""
+    ref = _tw_reference(N, K, T, w, 5, 2.3, ("both",))
+    dev, d_warp, g2 = _tw_on_device(N, K, T, w, 5)
+    op, _ = _tw_forward(N, K, T, w, 5, 2.3, dev)
+    _tw_check_grads(_tw_backward(op, dev, d_warp, g2, prefill=0.5), ref[3]["both"], "on top of 0.5", on_top_of=0.5)
 
 
 def test_unknown_warp_type_raises_like_the_reference():
@@ -159,9 +347,11 @@ def test_model_with_time_warp_att(warp_type):
 
 
 # (the last case: N T = 4200 > the 4096 waves of the shadow forward, two to three positions per wave in the shadow backward;
-#  the last positions of a wave's stride take the clamped table prefetch)
+#  the last positions of a wave's stride take the clamped table prefetch; K = 1: every lane >= 2 of the table load re-reads an
+#  entry; (1,8,5,1024): the heaviest instantiation, G4 = 4 with all TW_KMAX streams)
 @pytest.mark.parametrize("N,K,T,w,warp_type",
-                         [s + (wt,) for wt in (1, 3, 5) for s in [(2, 3, 17, 512), (3, 6, 50, 1024), (1, 8, 9, 512)]] +
+                         [s + (wt,) for wt in (1, 3, 5) for s in [(2, 3, 17, 512), (3, 6, 50, 1024), (1, 8, 9, 512), (2, 1, 9, 512),
+                                                                  (1, 8, 5, 1024)]] +
                          [(2, 3, 2100, 512, 5)])
 def test_timewarp_over_shadow_rows(warp_type, N, K, T, w):
     """fvta_timewarp_fwd_shadow / _bwd_shadow (the bf16 engine: the context tensor is never stored in fp32) against the

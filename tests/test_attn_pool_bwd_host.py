@@ -4,38 +4,22 @@ and library, the size queries and their refusals, the host-only plan, what M = 1
 the memory bound at the benchmark's shape, the Python refusals that reach no device, and the conditions
 tests/_attn_pool_bwd_ref.py puts on every pinned seed (so that the GPU test excludes nothing).  No GPU."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 from tests import _attn_pool_bwd_ref as B
+from tests._album_attn_host import declared_symbols, err, lib  # noqa: F401
 from fvta_memexqa_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("fvta_attn_pool_saved_bytes", "fvta_attn_pool_bwd_workspace_bytes", "fvta_attn_pool_bwd_plan",
         "fvta_attn_pool_fwd_train", "fvta_attn_pool_bwd")
 D = _lib.AttnPoolDesc          # (P, NQ, M, K, JX, JQ, w, simi, add_tanh)
 DS = _lib.AttnSharedDesc       # (A, NQ, K, T, JQ, w, simi, add_tanh)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.fvta_last_error()
-
-
 def test_header_binding_and_library_agree(lib):
-    src = open(os.path.join(ROOT, "include", "fvta_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(fvta_[a-z0-9_]+)\s*\(", src))
+    declared = declared_symbols()
     for s in SYMS:
         assert s in declared and s in _lib.exported_symbols() and hasattr(lib, s), s
     assert len(_lib._SIGS["fvta_attn_pool_fwd_train"][1]) == 13         # the descriptor, 11 pointers, the stream
@@ -115,31 +99,31 @@ def test_refusals_carry_a_message(lib):
     cosine = D(64, 64, 4, 6, 300, 30, 1024, 4, 0)
     for f in queries:
         assert f(ctypes.byref(cosine)) == 0
-        assert b"per-question" in _err(lib) and b"simiMatrix 4" in _err(lib)
-    assert lib.fvta_attn_pool_bwd_plan(ctypes.byref(cosine), out) == -3 and b"per-question" in _err(lib)
-    assert lib.fvta_attn_pool_fwd_train(ctypes.byref(cosine), *(None,) * 12) == -3 and b"per-question" in _err(lib)
-    assert lib.fvta_attn_pool_bwd(ctypes.byref(cosine), *(None,) * 15) == -3 and b"per-question" in _err(lib)
+        assert b"per-question" in err(lib) and b"simiMatrix 4" in err(lib)
+    assert lib.fvta_attn_pool_bwd_plan(ctypes.byref(cosine), out) == -3 and b"per-question" in err(lib)
+    assert lib.fvta_attn_pool_fwd_train(ctypes.byref(cosine), *(None,) * 12) == -3 and b"per-question" in err(lib)
+    assert lib.fvta_attn_pool_bwd(ctypes.byref(cosine), *(None,) * 15) == -3 and b"per-question" in err(lib)
     assert lib.fvta_attn_pool_workspace_bytes(ctypes.byref(cosine)) > 0          # the inference call keeps the cosine form
     for bad in (D(64, 64, 4, 6, 300, 30, 1000, 2, 0), D(64, 64, 4, 6, 300, 65, 1024, 2, 0), D(64, 64, 4, 65, 300, 30, 1024, 2, 0)):
         for f in queries:
-            assert f(ctypes.byref(bad)) == 0 and b"unsupported" in _err(lib)
-        assert lib.fvta_attn_pool_bwd_plan(ctypes.byref(bad), out) == -3 and b"unsupported" in _err(lib)
+            assert f(ctypes.byref(bad)) == 0 and b"unsupported" in err(lib)
+        assert lib.fvta_attn_pool_bwd_plan(ctypes.byref(bad), out) == -3 and b"unsupported" in err(lib)
     for zero in (D(0, 64, 4, 6, 300, 30, 1024, 2, 0), D(64, 0, 4, 6, 300, 30, 1024, 2, 0), D(64, 64, 0, 6, 300, 30, 1024, 2, 0),
                  D(64, 64, 4, 6, -3, 30, 1024, 2, 0)):
         for f in queries:
-            assert f(ctypes.byref(zero)) == 0 and b"bad P/NQ" in _err(lib)
+            assert f(ctypes.byref(zero)) == 0 and b"bad P/NQ" in err(lib)
     for f in queries:
-        assert f(None) == 0 and b"null descriptor" in _err(lib)
-    assert lib.fvta_attn_pool_bwd_plan(None, out) == -1 and b"null descriptor" in _err(lib)
+        assert f(None) == 0 and b"null descriptor" in err(lib)
+    assert lib.fvta_attn_pool_bwd_plan(None, out) == -1 and b"null descriptor" in err(lib)
 
 
 def test_null_pointers_are_refused(lib):
     ok = D(2, 3, 2, 2, 10, 5, 64, 2, 0)
-    assert lib.fvta_attn_pool_fwd_train(ctypes.byref(ok), *(None,) * 12) == -1 and b"null pointer" in _err(lib)
-    assert lib.fvta_attn_pool_bwd(ctypes.byref(ok), *(None,) * 15) == -1 and b"null pointer" in _err(lib)
+    assert lib.fvta_attn_pool_fwd_train(ctypes.byref(ok), *(None,) * 12) == -1 and b"null pointer" in err(lib)
+    assert lib.fvta_attn_pool_bwd(ctypes.byref(ok), *(None,) * 15) == -1 and b"null pointer" in err(lib)
     assert lib.fvta_attn_pool_fwd_train(None, *(None,) * 12) == -1
     assert lib.fvta_attn_pool_bwd(None, *(None,) * 15) == -1
-    assert lib.fvta_attn_pool_bwd_plan(ctypes.byref(ok), None) == -1 and b"null pointer" in _err(lib)
+    assert lib.fvta_attn_pool_bwd_plan(ctypes.byref(ok), None) == -1 and b"null pointer" in err(lib)
 
 
 def test_python_refusals_reach_no_device(monkeypatch):

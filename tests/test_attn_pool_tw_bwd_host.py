@@ -5,16 +5,14 @@ shape, the Python refusals that reach no device, the conditions tests/_attn_pool
 (so that the GPU test excludes nothing), and the factored backward the kernels compute against autograd of the
 definition.  No GPU."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 from tests import _attn_pool_tw_bwd_ref as TB
+from tests._album_attn_host import declared_symbols, err, lib  # noqa: F401
 from fvta_memexqa_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("fvta_attn_pool_tw_saved_bytes", "fvta_attn_pool_tw_bwd_workspace_bytes", "fvta_attn_pool_fwd_tw_train",
         "fvta_attn_pool_bwd_tw")
 D = _lib.AttnPoolDesc          # (P, NQ, M, K, JX, JQ, w, simi, add_tanh)
@@ -26,22 +24,8 @@ def TWD(*shape, warp_type=5, window_t=3.0):
     return _lib.AttnPoolTwDesc(D(*shape), warp_type, window_t)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.fvta_last_error()
-
-
 def test_header_binding_and_library_agree(lib):
-    src = open(os.path.join(ROOT, "include", "fvta_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(fvta_[a-z0-9_]+)\s*\(", src))
+    declared = declared_symbols()
     for s in SYMS:
         assert s in declared and s in _lib.exported_symbols() and hasattr(lib, s), s
     n = lambda s: len(_lib._SIGS[s][1])
@@ -156,36 +140,36 @@ def test_refusals_carry_a_message(lib):
     cosine = TWD(64, 64, 4, 6, 300, 30, 1024, 4, 0)
     for f in queries:
         assert f(ctypes.byref(cosine)) == 0
-        assert b"per-question" in _err(lib) and b"simiMatrix 4" in _err(lib)
-    assert lib.fvta_attn_pool_fwd_tw_train(ctypes.byref(cosine), *(None,) * 18) == -3 and b"per-question" in _err(lib)
-    assert lib.fvta_attn_pool_bwd_tw(ctypes.byref(cosine), *(None,) * 25) == -3 and b"per-question" in _err(lib)
+        assert b"per-question" in err(lib) and b"simiMatrix 4" in err(lib)
+    assert lib.fvta_attn_pool_fwd_tw_train(ctypes.byref(cosine), *(None,) * 18) == -3 and b"per-question" in err(lib)
+    assert lib.fvta_attn_pool_bwd_tw(ctypes.byref(cosine), *(None,) * 25) == -3 and b"per-question" in err(lib)
     assert lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(cosine)) > 0      # the inference call keeps the cosine form
     for bad in (TWD(64, 64, 4, 6, 300, 30, 1000, 2, 0), TWD(64, 64, 4, 6, 300, 65, 1024, 2, 0), TWD(64, 64, 4, 65, 300, 30, 1024, 2, 0)):
         for f in queries:
-            assert f(ctypes.byref(bad)) == 0 and b"unsupported" in _err(lib)
-            assert b"P=64 NQ=64 M=4" in _err(lib)                               # the pooled family's letters
-        assert lib.fvta_attn_pool_bwd_tw(ctypes.byref(bad), *(None,) * 25) == -3 and b"unsupported" in _err(lib)
+            assert f(ctypes.byref(bad)) == 0 and b"unsupported" in err(lib)
+            assert b"P=64 NQ=64 M=4" in err(lib)                               # the pooled family's letters
+        assert lib.fvta_attn_pool_bwd_tw(ctypes.byref(bad), *(None,) * 25) == -3 and b"unsupported" in err(lib)
     for zero in (TWD(0, 64, 4, 6, 300, 30, 1024, 2, 0), TWD(64, 0, 4, 6, 300, 30, 1024, 2, 0), TWD(64, 64, 0, 6, 300, 30, 1024, 2, 0),
                  TWD(64, 64, 4, 6, -3, 30, 1024, 2, 0)):
         for f in queries:
-            assert f(ctypes.byref(zero)) == 0 and b"bad P/NQ" in _err(lib)
+            assert f(ctypes.byref(zero)) == 0 and b"bad P/NQ" in err(lib)
     warp9 = TWD(64, 64, 4, 6, 300, 30, 1024, 2, 0, warp_type=9)
     for f in queries:
-        assert f(ctypes.byref(warp9)) == 0 and b"time warping type not implemented" in _err(lib)
+        assert f(ctypes.byref(warp9)) == 0 and b"time warping type not implemented" in err(lib)
     assert lib.fvta_attn_pool_fwd_tw_train(ctypes.byref(warp9), *(None,) * 18) == -1
-    assert b"time warping type not implemented" in _err(lib) and b"attn_pool_fwd_tw_train" in _err(lib)
+    assert b"time warping type not implemented" in err(lib) and b"attn_pool_fwd_tw_train" in err(lib)
     assert lib.fvta_attn_pool_bwd_tw(ctypes.byref(warp9), *(None,) * 25) == -1
-    assert b"time warping type not implemented" in _err(lib) and b"attn_pool_bwd_tw" in _err(lib)
+    assert b"time warping type not implemented" in err(lib) and b"attn_pool_bwd_tw" in err(lib)
     for f in queries:
-        assert f(None) == 0 and b"null descriptor" in _err(lib)
+        assert f(None) == 0 and b"null descriptor" in err(lib)
 
 
 def test_null_pointers_are_refused(lib):
     ok = TWD(2, 3, 2, 2, 10, 5, 64, 2, 0)
-    assert lib.fvta_attn_pool_fwd_tw_train(ctypes.byref(ok), *(None,) * 18) == -1 and b"null pointer" in _err(lib)
-    assert lib.fvta_attn_pool_bwd_tw(ctypes.byref(ok), *(None,) * 25) == -1 and b"null pointer" in _err(lib)
-    assert lib.fvta_attn_pool_fwd_tw_train(None, *(None,) * 18) == -1 and b"null descriptor" in _err(lib)
-    assert lib.fvta_attn_pool_bwd_tw(None, *(None,) * 25) == -1 and b"null descriptor" in _err(lib)
+    assert lib.fvta_attn_pool_fwd_tw_train(ctypes.byref(ok), *(None,) * 18) == -1 and b"null pointer" in err(lib)
+    assert lib.fvta_attn_pool_bwd_tw(ctypes.byref(ok), *(None,) * 25) == -1 and b"null pointer" in err(lib)
+    assert lib.fvta_attn_pool_fwd_tw_train(None, *(None,) * 18) == -1 and b"null descriptor" in err(lib)
+    assert lib.fvta_attn_pool_bwd_tw(None, *(None,) * 25) == -1 and b"null descriptor" in err(lib)
 
 
 def test_python_refusals_reach_no_device(monkeypatch):

@@ -4,28 +4,15 @@ through the new entries is a status code under the entry's own name, before anyt
 argument and nbytes; and functional.attention_3d_pooled_raw raises what it raises for an fp32 pool, in the same order.
 No GPU."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
+from tests._album_attn_host import HEADER, declared_symbols, err, header_code, lib  # noqa: F401
 from fvta_memexqa_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("fvta_attn_pool_fwd_bf16", "fvta_attn_pool_energy_bf16", "fvta_attn_pool_fwd_tw_bf16")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.fvta_last_error()
 
 
 def _desc(P=8, NQ=64, M=4, K=6, JX=64, JQ=30, w=512, simi=2, tanh=0):
@@ -37,9 +24,7 @@ def _tw(warp_type=5, window_t=3.0, **kw):
 
 
 def test_header_binding_and_library_agree_on_the_three_names(lib):
-    src = open(os.path.join(ROOT, "include", "fvta_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(fvta_[a-z0-9_]+)\s*\(", code))
+    code, declared = header_code(), declared_symbols()
     for s in SYMS:
         assert s in declared and s in _lib.exported_symbols() and hasattr(lib, s), s
         fp32 = s[:-len("_bf16")]
@@ -51,7 +36,7 @@ def test_header_binding_and_library_agree_on_the_three_names(lib):
     assert lib.fvta_abi_struct_bytes(15) == ctypes.sizeof(_lib.AttnPoolTwDesc) == 44
     assert lib.fvta_abi_struct_bytes(16) == -1
     # the header states the contract, the alignment and what is not there
-    doc = " ".join(src.split())
+    doc = " ".join(open(HEADER).read().split())
     for words in ("BIT FOR BIT", "8-byte aligned", "Not here: training"):
         assert words in doc, words
 
@@ -60,37 +45,37 @@ def test_refusals_carry_the_entry_s_own_name_and_launch_nothing(lib):
     nul11, nul17 = [None] * 11, [None] * 17
     fwd, energy, fwd_tw = lib.fvta_attn_pool_fwd_bf16, lib.fvta_attn_pool_energy_bf16, lib.fvta_attn_pool_fwd_tw_bf16
     # a null pool (everything null): FVTA_ERR_INVALID_ARG
-    assert fwd(ctypes.byref(_desc()), *nul11) == -1 and _err(lib) == b"attn_pool_fwd_bf16: null pointer"
-    assert fwd_tw(ctypes.byref(_tw()), *nul17) == -1 and _err(lib) == b"attn_pool_fwd_tw_bf16: null pointer"
-    assert energy(ctypes.byref(_tw()), *([None] * 6)) == -1 and _err(lib) == b"attn_pool_energy_bf16: null pointer"
-    assert fwd(None, *nul11) == -1 and b"attn_pool_fwd_bf16: null descriptor" in _err(lib)
+    assert fwd(ctypes.byref(_desc()), *nul11) == -1 and err(lib) == b"attn_pool_fwd_bf16: null pointer"
+    assert fwd_tw(ctypes.byref(_tw()), *nul17) == -1 and err(lib) == b"attn_pool_fwd_tw_bf16: null pointer"
+    assert energy(ctypes.byref(_tw()), *([None] * 6)) == -1 and err(lib) == b"attn_pool_energy_bf16: null pointer"
+    assert fwd(None, *nul11) == -1 and b"attn_pool_fwd_bf16: null descriptor" in err(lib)
     # simiMatrix 5, w = 1000: FVTA_ERR_UNSUPPORTED, the fp32 entries' words under the new names
     for call, d, nul, who in ((fwd, _desc, nul11, b"attn_pool_fwd_bf16"), (fwd_tw, _tw, nul17, b"attn_pool_fwd_tw_bf16"),
                               (energy, _tw, [None] * 6, b"attn_pool_energy_bf16")):
         assert call(ctypes.byref(d(simi=5)), *nul) == -3
-        assert _err(lib) == who + b": similarity matrix not implemented (simiMatrix=5)"
+        assert err(lib) == who + b": similarity matrix not implemented (simiMatrix=5)"
         assert call(ctypes.byref(d(w=1000)), *nul) == -3
-        assert _err(lib).startswith(who + b": unsupported shape (P=8 NQ=64 M=4 K=6 JX=64 JQ=30 w=1000)")
-        assert b"w must be one of 64,128,256,512,1024,2048" in _err(lib)
+        assert err(lib).startswith(who + b": unsupported shape (P=8 NQ=64 M=4 K=6 JX=64 JQ=30 w=1000)")
+        assert b"w must be one of 64,128,256,512,1024,2048" in err(lib)
     # the fp32 namesake refuses in the same words
     assert lib.fvta_attn_pool_fwd(ctypes.byref(_desc(w=1000)), *nul11) == -3
-    fp32_words = _err(lib)
+    fp32_words = err(lib)
     assert fwd(ctypes.byref(_desc(w=1000)), *nul11) == -3
-    assert _err(lib) == fp32_words.replace(b"attn_pool_fwd", b"attn_pool_fwd_bf16")
+    assert err(lib) == fp32_words.replace(b"attn_pool_fwd", b"attn_pool_fwd_bf16")
     # warp type 6: FVTA_ERR_INVALID_ARG from both warped entries
     for call, nul, who in ((fwd_tw, nul17, b"attn_pool_fwd_tw_bf16"), (energy, [None] * 6, b"attn_pool_energy_bf16")):
         assert call(ctypes.byref(_tw(warp_type=6)), *nul) == -1
-        assert _err(lib) == who + b": time warping type not implemented (warp_type=6)"
+        assert err(lib) == who + b": time warping type not implemented (warp_type=6)"
     # a pool that is not 8-byte aligned is refused before the launch (the other pointers are never followed)
     some = ctypes.c_void_p(0x1000)
     odd = ctypes.c_void_p(0x1000 + 2)
     assert fwd(ctypes.byref(_desc()), odd, None, some, None, some, some, None, some, None, some, None) == -1
-    assert _err(lib) == b"attn_pool_fwd_bf16: the bf16 pool must be 8-byte aligned"
+    assert err(lib) == b"attn_pool_fwd_bf16: the bf16 pool must be 8-byte aligned"
     assert energy(ctypes.byref(_tw()), odd, some, some, some, some, None) == -1
-    assert _err(lib) == b"attn_pool_energy_bf16: the bf16 pool must be 8-byte aligned"
+    assert err(lib) == b"attn_pool_energy_bf16: the bf16 pool must be 8-byte aligned"
     assert fwd_tw(ctypes.byref(_tw()), odd, None, some, some, None, some, some, some, None, some, some, some, some, None, None, some,
                   None) == -1
-    assert _err(lib) == b"attn_pool_fwd_tw_bf16: the bf16 pool must be 8-byte aligned"
+    assert err(lib) == b"attn_pool_fwd_tw_bf16: the bf16 pool must be 8-byte aligned"
 
 
 def test_album_pool_dtype(monkeypatch):

@@ -4,8 +4,6 @@ with its message, ops.check_album_lists and the order of validation and library 
 workspace's size against an expanded context, and the two fp64 references of tests/_attn_pooled_ref.py against each other
 on every shape the GPU tests use.  No GPU."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,22 +11,10 @@ import torch
 
 from tests import _attn_pooled_ref as R
 from tests import _attn_shared_ref as S
+from tests._album_attn_host import declared_symbols, err, header_code, lib  # noqa: F401
 from fvta_memexqa_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("fvta_attn_pool_workspace_bytes", "fvta_attn_pool_plan", "fvta_attn_pool_fwd")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.fvta_last_error()
 
 
 def _desc(P=8, NQ=64, M=4, K=6, JX=64, JQ=30, w=512, simi=2, tanh=0):
@@ -36,9 +22,7 @@ def _desc(P=8, NQ=64, M=4, K=6, JX=64, JQ=30, w=512, simi=2, tanh=0):
 
 
 def test_header_binding_and_library_export_the_symbols(lib):
-    src = open(os.path.join(ROOT, "include", "fvta_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(fvta_[a-z0-9_]+)\s*\(", src))
+    src, declared = header_code(), declared_symbols()
     for s in SYMS:
         assert s in declared and s in _lib.exported_symbols() and hasattr(lib, s), s
     assert "fvta_attn_pool_desc" in src
@@ -72,25 +56,25 @@ def test_plan_words(lib):
 def test_refusals_each_with_its_message(lib):
     out = (ctypes.c_int32 * 4)()
     for zero in (_desc(P=0), _desc(P=-1), _desc(M=0), _desc(M=-2), _desc(JX=0), _desc(JX=-5)):
-        assert lib.fvta_attn_pool_workspace_bytes(ctypes.byref(zero)) == 0 and b"bad P/NQ/M/K/JX/JQ/w" in _err(lib)
-        assert lib.fvta_attn_pool_plan(ctypes.byref(zero), out) == -1 and b"bad P/NQ/M/K/JX/JQ/w" in _err(lib)
+        assert lib.fvta_attn_pool_workspace_bytes(ctypes.byref(zero)) == 0 and b"bad P/NQ/M/K/JX/JQ/w" in err(lib)
+        assert lib.fvta_attn_pool_plan(ctypes.byref(zero), out) == -1 and b"bad P/NQ/M/K/JX/JQ/w" in err(lib)
     for bad, why in ((_desc(w=1000), b"w must be one of"), (_desc(JQ=65), b"JQ must be 1..64"), (_desc(K=65), b"K must be 1..64")):
         assert lib.fvta_attn_pool_workspace_bytes(ctypes.byref(bad)) == 0
-        assert b"unsupported shape (P=" in _err(lib) and why in _err(lib)
-        assert lib.fvta_attn_pool_plan(ctypes.byref(bad), out) == -3 and why in _err(lib)
+        assert b"unsupported shape (P=" in err(lib) and why in err(lib)
+        assert lib.fvta_attn_pool_plan(ctypes.byref(bad), out) == -3 and why in err(lib)
     assert lib.fvta_attn_pool_workspace_bytes(ctypes.byref(_desc(simi=5))) == 0
-    assert b"similarity matrix not implemented" in _err(lib)
-    assert lib.fvta_attn_pool_plan(ctypes.byref(_desc(simi=0)), out) == -3 and b"similarity matrix not implemented" in _err(lib)
-    assert lib.fvta_attn_pool_plan(ctypes.byref(_desc()), None) == -1 and b"null pointer" in _err(lib)
-    assert lib.fvta_attn_pool_workspace_bytes(None) == 0 and b"null descriptor" in _err(lib)
+    assert b"similarity matrix not implemented" in err(lib)
+    assert lib.fvta_attn_pool_plan(ctypes.byref(_desc(simi=0)), out) == -3 and b"similarity matrix not implemented" in err(lib)
+    assert lib.fvta_attn_pool_plan(ctypes.byref(_desc()), None) == -1 and b"null pointer" in err(lib)
+    assert lib.fvta_attn_pool_workspace_bytes(None) == 0 and b"null descriptor" in err(lib)
     # NQ M past 2^28, M JX past an int
-    assert lib.fvta_attn_pool_workspace_bytes(ctypes.byref(_desc(NQ=1 << 20, M=1 << 9))) == 0 and b"NQ*M" in _err(lib)
-    assert lib.fvta_attn_pool_workspace_bytes(ctypes.byref(_desc(NQ=1, M=1 << 16, JX=1 << 16))) == 0 and b"M*JX" in _err(lib)
+    assert lib.fvta_attn_pool_workspace_bytes(ctypes.byref(_desc(NQ=1 << 20, M=1 << 9))) == 0 and b"NQ*M" in err(lib)
+    assert lib.fvta_attn_pool_workspace_bytes(ctypes.byref(_desc(NQ=1, M=1 << 16, JX=1 << 16))) == 0 and b"M*JX" in err(lib)
     # the forward: status codes, nothing launched
     nul = [None] * 11
-    assert lib.fvta_attn_pool_fwd(ctypes.byref(_desc()), *nul) == -1 and b"null pointer" in _err(lib)
+    assert lib.fvta_attn_pool_fwd(ctypes.byref(_desc()), *nul) == -1 and b"null pointer" in err(lib)
     assert lib.fvta_attn_pool_fwd(None, *nul) == -1
-    assert lib.fvta_attn_pool_fwd(ctypes.byref(_desc(JQ=65)), *nul) == -3 and b"unsupported" in _err(lib)
+    assert lib.fvta_attn_pool_fwd(ctypes.byref(_desc(JQ=65)), *nul) == -3 and b"unsupported" in err(lib)
     # every supported width and both column regimes answer; P > NQ M and NQ M > P alike
     for w in (64, 128, 256, 512, 1024, 2048):
         for JQ in (1, 32, 33, 64):

@@ -7,17 +7,15 @@ shape that does not is ill conditioned: then the shape changes, never the tolera
 count runs over the question's whole M JX positions; and the Python surface's host-side errors come before any library
 call.  No GPU."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 from tests import _attn_pooled_ref as R
 from tests import _attn_pooled_tw_ref as PT
+from tests._album_attn_host import declared_symbols, err, header_code, lib  # noqa: F401
 from fvta_memexqa_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("fvta_attn_pool_tw_workspace_bytes", "fvta_attn_pool_energy", "fvta_attn_pool_fwd_tw")
 _REF = {}
 
@@ -29,27 +27,13 @@ def _case(name):
     return _REF[name]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.fvta_last_error()
-
-
 def _desc(P=8, NQ=64, M=4, K=6, JX=64, JQ=30, w=512, simi=2, tanh=0, warp_type=5, window_t=3.0):
     return _lib.AttnPoolTwDesc(_lib.AttnPoolDesc(P, NQ, M, K, JX, JQ, w, simi, tanh), warp_type, window_t)
 
 
 # ------------------------------------------------------------------ the C ABI, host side
 def test_header_binding_and_library_export_the_symbols(lib):
-    src = open(os.path.join(ROOT, "include", "fvta_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(fvta_[a-z0-9_]+)\s*\(", src))
+    src, declared = header_code(), declared_symbols()
     for s in SYMS:
         assert s in declared and s in _lib.exported_symbols() and hasattr(lib, s), s
     assert "fvta_attn_pool_tw_desc" in src                      # the fourth new symbol: the descriptor
@@ -95,39 +79,39 @@ def test_no_expansion_sized_buffer(lib):
 def test_bad_warp_type_fails_like_the_reference(lib, warp_type):
     d = _desc(warp_type=warp_type)
     assert lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(d)) == 0
-    assert b"time warping type not implemented" in _err(lib)
+    assert b"time warping type not implemented" in err(lib)
     assert lib.fvta_attn_pool_energy(ctypes.byref(d), *([None] * 6)) == -1
-    assert b"time warping type not implemented" in _err(lib)
+    assert b"time warping type not implemented" in err(lib)
     assert lib.fvta_attn_pool_fwd_tw(ctypes.byref(d), *([None] * 17)) == -1
-    assert b"time warping type not implemented" in _err(lib) and b"attn_pool_fwd_tw" in _err(lib)
+    assert b"time warping type not implemented" in err(lib) and b"attn_pool_fwd_tw" in err(lib)
 
 
 def test_refusals_each_with_its_message(lib):
     nul = [None] * 17
-    assert lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(_desc(window_t=-1.0))) == 0 and b"bad window_t" in _err(lib)
-    assert lib.fvta_attn_pool_fwd_tw(ctypes.byref(_desc(window_t=-0.5)), *nul) == -1 and b"bad window_t" in _err(lib)
+    assert lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(_desc(window_t=-1.0))) == 0 and b"bad window_t" in err(lib)
+    assert lib.fvta_attn_pool_fwd_tw(ctypes.byref(_desc(window_t=-0.5)), *nul) == -1 and b"bad window_t" in err(lib)
     # M JX past the scale kernel's grid (still within an int: the pooled call itself takes it)
     big = _desc(P=1, NQ=1, M=65535, JX=257)
     assert lib.fvta_attn_pool_workspace_bytes(ctypes.byref(big.shape)) > 0
     assert lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(big)) == 0
-    assert b"M*JX must not exceed 65535 * 256" in _err(lib)
-    assert lib.fvta_attn_pool_fwd_tw(ctypes.byref(big), *nul) == -3 and b"65535 * 256" in _err(lib)
+    assert b"M*JX must not exceed 65535 * 256" in err(lib)
+    assert lib.fvta_attn_pool_fwd_tw(ctypes.byref(big), *nul) == -3 and b"65535 * 256" in err(lib)
     assert lib.fvta_attn_pool_energy(ctypes.byref(big), *([None] * 6)) == -3
     for bad, why in ((_desc(w=100), b"w must be one of"), (_desc(w=1000), b"w must be one of"), (_desc(JQ=65), b"JQ must be 1..64"),
                      (_desc(K=65), b"K must be 1..64")):
         assert lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(bad)) == 0
-        assert b"unsupported shape (P=" in _err(lib) and why in _err(lib)
-        assert lib.fvta_attn_pool_fwd_tw(ctypes.byref(bad), *nul) == -3 and why in _err(lib)
-        assert lib.fvta_attn_pool_energy(ctypes.byref(bad), *([None] * 6)) == -3 and why in _err(lib)
+        assert b"unsupported shape (P=" in err(lib) and why in err(lib)
+        assert lib.fvta_attn_pool_fwd_tw(ctypes.byref(bad), *nul) == -3 and why in err(lib)
+        assert lib.fvta_attn_pool_energy(ctypes.byref(bad), *([None] * 6)) == -3 and why in err(lib)
     for zero in (_desc(P=0), _desc(M=0), _desc(JX=-5)):
-        assert lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(zero)) == 0 and b"bad P/NQ/M/K/JX/JQ/w" in _err(lib)
+        assert lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(zero)) == 0 and b"bad P/NQ/M/K/JX/JQ/w" in err(lib)
     assert lib.fvta_attn_pool_tw_workspace_bytes(ctypes.byref(_desc(simi=5))) == 0
-    assert b"similarity matrix not implemented" in _err(lib)
-    assert lib.fvta_attn_pool_tw_workspace_bytes(None) == 0 and b"null descriptor" in _err(lib)
+    assert b"similarity matrix not implemented" in err(lib)
+    assert lib.fvta_attn_pool_tw_workspace_bytes(None) == 0 and b"null descriptor" in err(lib)
     # null required pointers come back as status, nothing launched
-    assert lib.fvta_attn_pool_energy(ctypes.byref(_desc()), *([None] * 6)) == -1 and b"attn_pool_energy: null pointer" in _err(lib)
-    assert lib.fvta_attn_pool_fwd_tw(ctypes.byref(_desc()), *nul) == -1 and b"attn_pool_fwd_tw: null pointer" in _err(lib)
-    assert lib.fvta_attn_pool_fwd_tw(None, *nul) == -1 and b"null descriptor" in _err(lib)
+    assert lib.fvta_attn_pool_energy(ctypes.byref(_desc()), *([None] * 6)) == -1 and b"attn_pool_energy: null pointer" in err(lib)
+    assert lib.fvta_attn_pool_fwd_tw(ctypes.byref(_desc()), *nul) == -1 and b"attn_pool_fwd_tw: null pointer" in err(lib)
+    assert lib.fvta_attn_pool_fwd_tw(None, *nul) == -1 and b"null descriptor" in err(lib)
     assert lib.fvta_attn_pool_energy(None, *([None] * 6)) == -1
 
 

@@ -3,37 +3,21 @@ fvta_attn_shared_bwd_workspace_bytes, fvta_attn_shared_bwd_plan, fvta_attn_share
 binding and library, the size queries and their refusals, the host-only plan, argument errors as status codes, and the
 conditions tests/_attn_shared_bwd_ref.py puts on every pinned seed (so that the GPU test excludes nothing).  No GPU."""
 import ctypes
-import os
-import re
 
 import pytest
 
 from tests import _attn_shared_bwd_ref as B
 from tests import _attn_shared_ref as R
+from tests._album_attn_host import declared_symbols, err, lib  # noqa: F401
 from fvta_memexqa_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("fvta_attn_shared_saved_bytes", "fvta_attn_shared_bwd_workspace_bytes", "fvta_attn_shared_bwd_plan",
         "fvta_attn_shared_fwd_train", "fvta_attn_shared_bwd")
 D = _lib.AttnSharedDesc
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.fvta_last_error()
-
-
 def test_header_binding_and_library_agree(lib):
-    src = open(os.path.join(ROOT, "include", "fvta_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(fvta_[a-z0-9_]+)\s*\(", src))
+    declared = declared_symbols()
     for s in SYMS:
         assert s in declared and s in _lib.exported_symbols() and hasattr(lib, s), s
     assert len(_lib._SIGS["fvta_attn_shared_fwd_train"][1]) == 13       # the descriptor, 11 pointers, the stream
@@ -68,31 +52,31 @@ def test_refusals_carry_a_message(lib):
     cosine = D(8, 64, 6, 1200, 30, 1024, 4, 0)
     for f in queries:
         assert f(ctypes.byref(cosine)) == 0
-        assert b"per-question" in _err(lib) and b"simiMatrix 4" in _err(lib)
+        assert b"per-question" in err(lib) and b"simiMatrix 4" in err(lib)
     out = (ctypes.c_int32 * 4)()
-    assert lib.fvta_attn_shared_bwd_plan(ctypes.byref(cosine), out) == -3 and b"per-question" in _err(lib)
+    assert lib.fvta_attn_shared_bwd_plan(ctypes.byref(cosine), out) == -3 and b"per-question" in err(lib)
     nul12, nul15 = (None,) * 12, (None,) * 15
-    assert lib.fvta_attn_shared_fwd_train(ctypes.byref(cosine), *nul12) == -3 and b"per-question" in _err(lib)
-    assert lib.fvta_attn_shared_bwd(ctypes.byref(cosine), *nul15) == -3 and b"per-question" in _err(lib)
+    assert lib.fvta_attn_shared_fwd_train(ctypes.byref(cosine), *nul12) == -3 and b"per-question" in err(lib)
+    assert lib.fvta_attn_shared_bwd(ctypes.byref(cosine), *nul15) == -3 and b"per-question" in err(lib)
     for bad in (D(8, 64, 6, 1200, 30, 1000, 2, 0), D(8, 64, 6, 1200, 65, 1024, 2, 0), D(8, 64, 65, 1200, 30, 1024, 2, 0)):
         for f in queries:
-            assert f(ctypes.byref(bad)) == 0 and b"unsupported" in _err(lib)
+            assert f(ctypes.byref(bad)) == 0 and b"unsupported" in err(lib)
         assert lib.fvta_attn_shared_bwd_plan(ctypes.byref(bad), out) == -3
     for zero in (D(0, 64, 6, 1200, 30, 1024, 2, 0), D(8, 0, 6, 1200, 30, 1024, 2, 0), D(8, 64, 6, -3, 30, 1024, 2, 0)):
         for f in queries:
-            assert f(ctypes.byref(zero)) == 0 and b"bad A/NQ" in _err(lib)
+            assert f(ctypes.byref(zero)) == 0 and b"bad A/NQ" in err(lib)
     for f in queries:
-        assert f(None) == 0 and b"null descriptor" in _err(lib)
-    assert lib.fvta_attn_shared_bwd_plan(None, out) == -1 and b"null descriptor" in _err(lib)
+        assert f(None) == 0 and b"null descriptor" in err(lib)
+    assert lib.fvta_attn_shared_bwd_plan(None, out) == -1 and b"null descriptor" in err(lib)
 
 
 def test_null_pointers_are_refused(lib):
     ok = D(2, 3, 2, 10, 5, 64, 2, 0)
-    assert lib.fvta_attn_shared_fwd_train(ctypes.byref(ok), *(None,) * 12) == -1 and b"null pointer" in _err(lib)
-    assert lib.fvta_attn_shared_bwd(ctypes.byref(ok), *(None,) * 15) == -1 and b"null pointer" in _err(lib)
+    assert lib.fvta_attn_shared_fwd_train(ctypes.byref(ok), *(None,) * 12) == -1 and b"null pointer" in err(lib)
+    assert lib.fvta_attn_shared_bwd(ctypes.byref(ok), *(None,) * 15) == -1 and b"null pointer" in err(lib)
     assert lib.fvta_attn_shared_fwd_train(None, *(None,) * 12) == -1
     assert lib.fvta_attn_shared_bwd(None, *(None,) * 15) == -1
-    assert lib.fvta_attn_shared_bwd_plan(ctypes.byref(ok), None) == -1 and b"null pointer" in _err(lib)
+    assert lib.fvta_attn_shared_bwd_plan(ctypes.byref(ok), None) == -1 and b"null pointer" in err(lib)
 
 
 def test_backward_plan_is_deterministic_and_host_only(lib):

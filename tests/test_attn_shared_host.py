@@ -3,35 +3,19 @@ size query and its refusals, the host-only plan, argument errors as status codes
 references of tests/_attn_shared_ref.py against each other on every shape the GPU tests use, and the regime of each
 LOOP_SPECS case by the plan's words.  No GPU."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 from tests import _attn_shared_ref as R
+from tests._album_attn_host import declared_symbols, err, header_code, lib  # noqa: F401
 from fvta_memexqa_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("fvta_attn_shared_workspace_bytes", "fvta_attn_shared_plan", "fvta_attn_shared_fwd")
 
 
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.fvta_last_error()
-
-
 def test_header_and_binding_agree():
-    src = open(os.path.join(ROOT, "include", "fvta_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(fvta_[a-z0-9_]+)\s*\(", src))
+    src, declared = header_code(), declared_symbols()
     for s in SYMS:
         assert s in declared and s in _lib.exported_symbols(), s
     assert "fvta_attn_shared_desc" in src
@@ -52,13 +36,13 @@ def test_workspace_query_and_refusals(lib):
     assert nb < 8 * 64 * 6 * 1200 * 1024 * 4 // 8               # and nowhere near an expanded [NQ,K,T,w] tensor
     for bad in (_lib.AttnSharedDesc(8, 64, 6, 1200, 30, 1000, 2, 0), _lib.AttnSharedDesc(8, 64, 6, 1200, 65, 1024, 2, 0)):
         assert lib.fvta_attn_shared_workspace_bytes(ctypes.byref(bad)) == 0
-        assert b"unsupported" in _err(lib)
+        assert b"unsupported" in err(lib)
     bad5 = _lib.AttnSharedDesc(8, 64, 6, 1200, 30, 1024, 5, 0)
     assert lib.fvta_attn_shared_workspace_bytes(ctypes.byref(bad5)) == 0
-    assert b"similarity matrix not implemented" in _err(lib)
+    assert b"similarity matrix not implemented" in err(lib)
     for zero in (_lib.AttnSharedDesc(0, 64, 6, 1200, 30, 1024, 2, 0), _lib.AttnSharedDesc(8, 0, 6, 1200, 30, 1024, 2, 0),
                  _lib.AttnSharedDesc(8, 64, 6, -3, 30, 1024, 2, 0)):
-        assert lib.fvta_attn_shared_workspace_bytes(ctypes.byref(zero)) == 0 and b"bad A/NQ" in _err(lib)
+        assert lib.fvta_attn_shared_workspace_bytes(ctypes.byref(zero)) == 0 and b"bad A/NQ" in err(lib)
     assert lib.fvta_attn_shared_workspace_bytes(None) == 0
     # every supported width and both column regimes answer; A > NQ and NQ > A alike
     for w in (64, 128, 256, 512, 1024, 2048):
@@ -88,19 +72,19 @@ def test_plan_answers_on_the_host(lib):
         assert set(p) == {"G", "rows", "tsplit", "rows_per_split"}
         assert (p["tsplit"] - 1) * p["rows_per_split"] < T <= p["tsplit"] * p["rows_per_split"], (T, p)
         assert p["rows_per_split"] == -(-T // p["tsplit"]), (T, p)
-    assert lib.fvta_attn_shared_plan(ctypes.byref(d30), None) == -1 and b"null pointer" in _err(lib)
+    assert lib.fvta_attn_shared_plan(ctypes.byref(d30), None) == -1 and b"null pointer" in err(lib)
     bad = _lib.AttnSharedDesc(8, 64, 6, 1200, 30, 1000, 2, 0)
-    assert lib.fvta_attn_shared_plan(ctypes.byref(bad), out) == -3 and b"unsupported" in _err(lib)
+    assert lib.fvta_attn_shared_plan(ctypes.byref(bad), out) == -3 and b"unsupported" in err(lib)
 
 
 def test_forward_refuses_null_pointers(lib):
     ok = _lib.AttnSharedDesc(2, 3, 2, 10, 5, 64, 2, 0)
     st = lib.fvta_attn_shared_fwd(ctypes.byref(ok), None, None, None, None, None, None, None, None, None, None, None)
-    assert st == -1 and b"null pointer" in _err(lib)
+    assert st == -1 and b"null pointer" in err(lib)
     assert lib.fvta_attn_shared_fwd(None, None, None, None, None, None, None, None, None, None, None, None) == -1
     bad = _lib.AttnSharedDesc(2, 3, 2, 10, 65, 64, 2, 0)
     st = lib.fvta_attn_shared_fwd(ctypes.byref(bad), None, None, None, None, None, None, None, None, None, None, None)
-    assert st == -3 and b"unsupported" in _err(lib)
+    assert st == -3 and b"unsupported" in err(lib)
 
 
 def test_check_album_index():

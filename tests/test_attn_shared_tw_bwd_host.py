@@ -5,8 +5,6 @@ codes (host side, no launch); the conditions every pinned seed of tests/_attn_sh
 the GPU test excludes nothing); and the mathematics itself, independently of any kernel: the hand-written
 `factored_backward` against fp64 autograd of the definition at 1e-9 on every case.  No GPU."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
@@ -14,9 +12,9 @@ import torch
 from tests import _attn_shared_bwd_ref as B
 from tests import _attn_shared_ref as R
 from tests import _attn_shared_tw_bwd_ref as TB
+from tests._album_attn_host import declared_symbols, err, lib  # noqa: F401
 from fvta_memexqa_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("fvta_attn_shared_tw_saved_bytes", "fvta_attn_shared_tw_bwd_workspace_bytes", "fvta_attn_shared_fwd_tw_train",
         "fvta_attn_shared_bwd_tw")
 D = _lib.AttnSharedDesc
@@ -25,18 +23,6 @@ N_FWD, N_BWD = 18, 25            # arguments after the descriptor
 
 def TD(shape, warp_type=5, window_t=3.0):
     return _lib.AttnSharedTwDesc(shape, warp_type, window_t)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return _lib.load()
-
-
-def _err(lib):
-    return lib.fvta_last_error()
 
 
 _REF = {}
@@ -51,9 +37,7 @@ def _case(name):
 
 
 def test_header_binding_and_library_agree(lib):
-    src = open(os.path.join(ROOT, "include", "fvta_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    declared = set(re.findall(r"\b(fvta_[a-z0-9_]+)\s*\(", src))
+    declared = declared_symbols()
     for s in SYMS:
         assert s in declared and s in _lib.exported_symbols() and hasattr(lib, s), s
     assert len(_lib._SIGS["fvta_attn_shared_fwd_tw_train"][1]) == 1 + N_FWD    # fvta_attn_shared_fwd_tw's and `saved`
@@ -92,29 +76,29 @@ def test_refusals_carry_a_message(lib):
     cosine = TD(D(8, 64, 6, 1200, 30, 1024, 4, 0))
     for f in queries:
         assert f(ctypes.byref(cosine)) == 0
-        assert b"per-question" in _err(lib) and b"simiMatrix 4" in _err(lib)
-    assert lib.fvta_attn_shared_fwd_tw_train(ctypes.byref(cosine), *(None,) * N_FWD) == -3 and b"per-question" in _err(lib)
-    assert lib.fvta_attn_shared_bwd_tw(ctypes.byref(cosine), *(None,) * N_BWD) == -3 and b"per-question" in _err(lib)
+        assert b"per-question" in err(lib) and b"simiMatrix 4" in err(lib)
+    assert lib.fvta_attn_shared_fwd_tw_train(ctypes.byref(cosine), *(None,) * N_FWD) == -3 and b"per-question" in err(lib)
+    assert lib.fvta_attn_shared_bwd_tw(ctypes.byref(cosine), *(None,) * N_BWD) == -3 and b"per-question" in err(lib)
     for wt in (0, 6):
         bad = TD(D(8, 64, 6, 1200, 30, 1024, 2, 1), wt)
         for f in queries:
-            assert f(ctypes.byref(bad)) == 0 and b"time warping type not implemented" in _err(lib)
+            assert f(ctypes.byref(bad)) == 0 and b"time warping type not implemented" in err(lib)
         assert lib.fvta_attn_shared_fwd_tw_train(ctypes.byref(bad), *(None,) * N_FWD) == -1
-        assert b"time warping type not implemented" in _err(lib)
+        assert b"time warping type not implemented" in err(lib)
         assert lib.fvta_attn_shared_bwd_tw(ctypes.byref(bad), *(None,) * N_BWD) == -1
-        assert b"time warping type not implemented" in _err(lib)
+        assert b"time warping type not implemented" in err(lib)
     for shape in (D(8, 64, 6, 1200, 30, 1000, 2, 0), D(8, 64, 6, 1200, 65, 1024, 2, 0), D(8, 64, 65, 1200, 30, 1024, 2, 0)):
         for f in queries:
-            assert f(ctypes.byref(TD(shape))) == 0 and b"unsupported" in _err(lib)
+            assert f(ctypes.byref(TD(shape))) == 0 and b"unsupported" in err(lib)
     for f in queries:
-        assert f(ctypes.byref(TD(D(8, 64, 6, 1200, 30, 1024, 2, 0), 5, -1.0))) == 0 and b"window_t" in _err(lib)
-        assert f(None) == 0 and b"null descriptor" in _err(lib)
+        assert f(ctypes.byref(TD(D(8, 64, 6, 1200, 30, 1024, 2, 0), 5, -1.0))) == 0 and b"window_t" in err(lib)
+        assert f(None) == 0 and b"null descriptor" in err(lib)
 
 
 def test_null_pointers_are_refused(lib):
     ok = TD(D(2, 3, 2, 10, 5, 64, 2, 0))
-    assert lib.fvta_attn_shared_fwd_tw_train(ctypes.byref(ok), *(None,) * N_FWD) == -1 and b"null pointer" in _err(lib)
-    assert lib.fvta_attn_shared_bwd_tw(ctypes.byref(ok), *(None,) * N_BWD) == -1 and b"null pointer" in _err(lib)
+    assert lib.fvta_attn_shared_fwd_tw_train(ctypes.byref(ok), *(None,) * N_FWD) == -1 and b"null pointer" in err(lib)
+    assert lib.fvta_attn_shared_bwd_tw(ctypes.byref(ok), *(None,) * N_BWD) == -1 and b"null pointer" in err(lib)
     assert lib.fvta_attn_shared_fwd_tw_train(None, *(None,) * N_FWD) == -1
     assert lib.fvta_attn_shared_bwd_tw(None, *(None,) * N_BWD) == -1
 

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from tests import _attn_shared_tw_ref as TW
+from tests._album_attn_host import lib  # noqa: F401
 
 ALL = TW.NAMES + TW.EXTRA
 _REF = {}
@@ -75,12 +76,6 @@ def test_energy_is_per_album():
 
 
 # ------------------------------------------------------------------ the C ABI, host side
-@pytest.fixture(scope="module")
-def lib():
-    from fvta_memexqa_amd import _lib
-    return _lib.load()
-
-
 def _desc(A=2, NQ=3, K=2, T=50, JQ=10, w=64, simi=2, tanh=1, warp_type=5, window_t=2.3):
     from fvta_memexqa_amd import _lib
     return _lib.AttnSharedTwDesc(_lib.AttnSharedDesc(A, NQ, K, T, JQ, w, simi, tanh), warp_type, window_t)

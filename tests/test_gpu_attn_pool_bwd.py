@@ -11,81 +11,24 @@ loops, `many` (P = 1500, 1600 references), `heavy` ([150, 0, 50]: 19 groups of o
 workgroup), each asserting its regime from the plans' words before any launch.  The pinned seeds keep every arg-max clear
 in fp64 (tests/test_attn_pool_bwd_host.py); the first test also holds the GPU's own logits to a quarter of the smallest
 gap."""
-import numpy as np
 import pytest
 import torch
 
 from tests import _attn_pool_bwd_ref as B
-from tests import _attn_pooled_ref as P
+from tests._album_attn_gpu import TrainRun, case, close_scaled, cu, gather, listed
 
 pytestmark = pytest.mark.gpu
-
-_REF = {}
-
-
-def _close(a, b, rtol=1e-4, atol=1e-5, msg=""):
-    a = a.detach().cpu().double().numpy()
-    b = b.detach().cpu().double().numpy()
-    scale = max(1.0, float(np.abs(b).max()))
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol * scale, err_msg=msg)
-
-
-def _cu(t):
-    return None if t is None else t.cuda().contiguous()
 
 
 def _case(name):
     """the case and its fp64 reference, computed once per session and never written to"""
-    if name not in _REF:
-        c = B.build_case(name)
-        _REF[name] = (c, B.reference(c))
-    return _REF[name]
-
-
-class _Run:
-    """ops.PooledFocalAttention on case c (rows: a subset of the questions; pool / pm / albums: replacements), its device
-    tensors kept for backward()"""
-
-    def __init__(self, c, rows=None, pool=None, pm=None, albums=None):
-        from fvta_memexqa_amd import ops
-        q, qm, al, g = c["q"], c["qm"], (c["albums"] if albums is None else albums), c["gout"]
-        pool = c["pool"] if pool is None else pool
-        pm = c["pm"] if pm is None else pm
-        if rows is not None:
-            q, al, g = q[rows], al[rows], g[rows]
-            qm = None if qm is None else qm[rows]
-        self.c, self.NQ = c, q.shape[0]
-        self.op = ops.PooledFocalAttention(c["P"], self.NQ, c["M"], c["K"], c["JX"], c["JQ"], c["w"], c["simi"], c["tanh"])
-        self.args = (_cu(pool), _cu(ops.as_mask_u8(pm)), _cu(q), _cu(ops.as_mask_u8(qm)),
-                     ops.check_album_lists(al, c["P"], pm is not None and qm is not None).cuda(), _cu(c["W"].reshape(-1)),
-                     _cu(c["b"]))
-        self.g = _cu(g)
-
-    def forward_train(self, want_logits=True):
-        return self.op.forward_train(*self.args, want_logits=want_logits)
-
-    def forward(self, want_logits=True):
-        return self.op.forward(*self.args, want_logits=want_logits)
-
-    def backward(self, dW=None, db=None, fill=7.0):
-        c = self.c
-        dp = torch.full((c["P"], c["K"], c["JX"], c["w"]), fill, device="cuda")
-        dq = torch.full((self.NQ, c["JQ"], c["w"]), fill, device="cuda")
-        dW = torch.zeros_like(self.args[5]) if dW is None else dW
-        db = torch.zeros(1, device="cuda") if db is None else db
-        self.op.backward(*self.args, self.g, dp, dq, dW, db)
-        return dp, dq, dW, db
-
-
-def _listed(c):
-    al = c["albums"].reshape(-1)
-    return torch.bincount(al[al >= 0], minlength=c["P"])
+    return case(B, name)
 
 
 @pytest.mark.parametrize("name", B.CASE_IDS)
 def test_gradients_match_fp64_autograd(name):
     c, ref = _case(name)
-    run = _Run(c)
+    run = TrainRun(c, "pooled")
     B.loop_regime(name, c, run.op.plan(), run.op.bwd_plan())    # a past-one-round case reaches its loop, before any launch
     ha, a = run.forward_train()
     # the arg-max the backward routes through is the reference's: the GPU's logits are within a quarter of the smallest gap
@@ -94,50 +37,38 @@ def test_gradients_match_fp64_autograd(name):
     err = float((a.cpu().double() - ref["a_logits"])[v].abs().max())
     print("%s: max |a_logits - fp64| over valid entries %.3g, smallest gap %.3g" % (name, err, min(jgap, tgap)))
     assert err < min(jgap, tgap) / 4, (err, jgap, tgap)
-    _close(ha, ref["h_a"], msg="h_a")
+    close_scaled(ha, ref["h_a"], msg="h_a")
     dp, dq, dW, db = run.backward()                              # d_pool / d_hq prefilled with 7.0: overwritten
     for got, key in ((dp, "dpool"), (dq, "dq"), (dW, "dW"), (db, "db")):
         print("%s %s: max |got - ref| %.3g, max |ref| %.3g" % (name, key, float((got.cpu().double() - ref[key]).abs().max()),
                                                                float(ref[key].abs().max())))
-    _close(dp, ref["dpool"], msg="d_pool")
-    _close(dq, ref["dq"], msg="d_hq")
-    _close(dW, ref["dW"], msg="dW")
-    _close(db, ref["db"], msg="db")
-    unlisted = _listed(c) == 0
+    close_scaled(dp, ref["dpool"], msg="d_pool")
+    close_scaled(dq, ref["dq"], msg="d_hq")
+    close_scaled(dW, ref["dW"], msg="dW")
+    close_scaled(db, ref["db"], msg="db")
+    unlisted = listed(c) == 0
     if bool(unlisted.any()):                                     # albums nobody lists: exactly zero, not the 7.0
         assert float(dp.cpu()[unlisted].abs().max()) == 0.0
     nothing = (c["albums"] < 0).all(1)
     if bool(nothing.any()):                                      # a question that lists nothing: exactly zero, not the 7.0
         assert float(dq.cpu()[nothing].abs().max()) == 0.0
-    dp2, dq2, dW2, db2 = run.backward(dW=dW, db=db, fill=-3.0)   # a second call: dW / db accumulate, the others do not
-    _close(dW2, 2 * ref["dW"], atol=2e-5, msg="dW accumulates")
-    _close(db2, 2 * ref["db"], atol=2e-5, msg="db accumulates")
-    _close(dp2, ref["dpool"], msg="d_pool overwritten")
-    _close(dq2, ref["dq"], msg="d_hq overwritten")
+    dp2, dq2, dW2, db2 = run.backward(acc=(dW, db), fill=-3.0)   # a second call: dW / db accumulate, the others do not
+    close_scaled(dW2, 2 * ref["dW"], atol=2e-5, msg="dW accumulates")
+    close_scaled(db2, 2 * ref["db"], atol=2e-5, msg="db accumulates")
+    close_scaled(dp2, ref["dpool"], msg="d_pool overwritten")
+    close_scaled(dq2, ref["dq"], msg="d_hq overwritten")
 
 
 def test_exact_zeros():
     """masked `mix`, every question partly valid: the album nobody lists and every masked row hold exactly 0"""
     c, _ = _case("mix-simi3-masked")
-    run = _Run(c)
+    run = TrainRun(c, "pooled")
     run.forward_train(want_logits=False)
     dp = run.backward()[0].cpu()
-    unlisted = _listed(c) == 0
+    unlisted = listed(c) == 0
     assert int(unlisted.sum()) == 1 and float(dp[unlisted].abs().max()) == 0.0
     assert bool((~c["pm"]).any()) and float(dp[~c["pm"]].abs().max()) == 0.0
     assert float(dp[c["pm"] & ~unlisted[:, None, None]].abs().max()) > 0.0
-
-
-def _gather(pool, pm, al):
-    """on the device: (hinfo [NQ,K,M JX,w], mask [NQ,K,M JX]) of lists al [NQ,M]; an empty slot: zero rows, mask 0"""
-    NQ, M = al.shape
-    Pn, K, JX, w = pool.shape
-    live = (al >= 0)
-    idx = al.clamp(min=0).long()
-    h = pool[idx] * live[:, :, None, None, None]                                 # [NQ,M,K,JX,w]
-    m = pm[idx] * live[:, :, None, None].to(pm.dtype)
-    return (h.permute(0, 2, 1, 3, 4).reshape(NQ, K, M * JX, w).contiguous(),
-            m.permute(0, 2, 1, 3).reshape(NQ, K, M * JX).contiguous())
 
 
 def _scatter(dhe, al, Pn):
@@ -160,22 +91,22 @@ def test_same_result_as_the_per_question_route(attn_select):
     from fvta_memexqa_amd import ops
     c = B.build_case(B.MIX_MASKED, parity=False)
     assert bool((c["albums"] < 0).any())                                         # the empty slot
-    run = _Run(c)
+    run = TrainRun(c, "pooled")
     run.forward_train(want_logits=False)
     dp, dq, dW, db = run.backward()
     attn_select.exact()
     pool, pm, q, qm, al, W, b = run.args
-    he, hme = _gather(pool, pm, al)
+    he, hme = gather(pool, pm, al)
     op = ops.FocalAttention(c["NQ"], c["K"], c["T"], c["JQ"], c["w"], c["simi"], c["tanh"])
     op.forward(he, q, hme, qm, W, b)
     dhe, dqe = torch.full_like(he, 7.0), torch.full_like(q, 7.0)
     dWe, dbe = torch.zeros_like(W), torch.zeros(1, device="cuda")
     op.backward(he, q, hme, qm, W, b, run.g, dhe, dqe, dWe, dbe, 0)
-    _close(dp, _scatter(dhe, al, c["P"]), msg="d_pool against the scatter-add of the per-question gradient")
-    _close(dq, dqe, msg="d_hq")
-    _close(dW, dWe, msg="dW")
-    _close(db, dbe, msg="db")
-    unlisted = (_listed(c) == 0).nonzero().reshape(-1)
+    close_scaled(dp, _scatter(dhe, al, c["P"]), msg="d_pool against the scatter-add of the per-question gradient")
+    close_scaled(dq, dqe, msg="d_hq")
+    close_scaled(dW, dWe, msg="dW")
+    close_scaled(db, dbe, msg="db")
+    unlisted = (listed(c) == 0).nonzero().reshape(-1)
     assert unlisted.numel() == 1 and float(dp[int(unlisted[0])].abs().max()) == 0.0
     fully_masked_q = (~c["qm"].any(-1)).nonzero().reshape(-1)
     assert fully_masked_q.numel() == 1
@@ -194,7 +125,7 @@ def test_same_result_as_the_per_question_route(attn_select):
 @pytest.mark.parametrize("name", ["mix-simi2-masked", "cols-jq33-w128", "rows-JX200", "wide2048", "all-empty-simi3"])
 def test_forward_train_has_the_bits_of_the_inference_forward(name):
     c, _ = _case(name)
-    run = _Run(c)
+    run = TrainRun(c, "pooled")
     ha_t, a_t = run.forward_train()
     ha_i, a_i = run.forward()
     assert torch.equal(ha_t, ha_i) and torch.equal(a_t, a_i)
@@ -209,7 +140,7 @@ def test_one_slot_has_the_bits_of_the_shared_backward(name):
     c, _ = _case(name)
     album = c["albums"][:, 0].clamp(min=0)
     c1 = dict(c, albums=album[:, None], M=1, T=c["JX"])
-    run = _Run(c1)
+    run = TrainRun(c1, "pooled")
     run.forward_train(want_logits=False)
     got = run.backward()
     pool, pm, q, qm, _, W, b = run.args
@@ -230,7 +161,7 @@ def test_three_backward_calls_are_bitwise_equal(name):
     c, _ = _case(name)
     outs = []
     for _ in range(3):
-        run = _Run(c)                                            # a fresh handle: plan, saved and workspace anew
+        run = TrainRun(c, "pooled")                              # a fresh handle: plan, saved and workspace anew
         run.forward_train(want_logits=False)
         outs.append(run.backward())
     for other in outs[1:]:
@@ -249,27 +180,27 @@ def test_a_relabelled_pool_gives_the_same_bits(name):
     assert perm.tolist() != list(range(c["P"]))
     al = c["albums"]
     al2 = torch.where(al >= 0, perm[al.clamp(min=0)], al)
-    base = _Run(c)
+    base = TrainRun(c, "pooled")
     base.forward_train(want_logits=False)
     dp, dq, dW, db = base.backward()
-    moved = _Run(c, pool=c["pool"][inv], pm=None if c["pm"] is None else c["pm"][inv], albums=al2)
+    moved = TrainRun(c, "pooled", pool=c["pool"][inv], pm=None if c["pm"] is None else c["pm"][inv], albums=al2)
     moved.forward_train(want_logits=False)
     dp2, dq2, dW2, db2 = moved.backward()
     assert torch.equal(dp2[perm.cuda()], dp) and torch.equal(dq2, dq)
-    _close(dW2, ref["dW"], msg="dW after relabelling")
-    _close(db2, ref["db"], msg="db after relabelling")
+    close_scaled(dW2, ref["dW"], msg="dW after relabelling")
+    close_scaled(db2, ref["db"], msg="db after relabelling")
 
 
 def test_a_questions_gradient_does_not_depend_on_its_company():
     c, _ = _case("mix-simi3-masked")
-    run = _Run(c)
+    run = TrainRun(c, "pooled")
     run.forward_train(want_logits=False)
     _, dq_all, _, _ = run.backward()
     i = next(i for i, row in enumerate(c["albums"].tolist()) if min(row) >= 0 and len(set(row)) > 1)
-    one = _Run(c, rows=[i])
+    one = TrainRun(c, "pooled", rows=[i])
     one.forward_train(want_logits=False)
     dp_one, dq_one, _, _ = one.backward()
-    _close(dq_one[0], dq_all[i], msg="d_hq alone against in company")
+    close_scaled(dq_one[0], dq_all[i], msg="d_hq alone against in company")
     mine = set(c["albums"][i].tolist())
     others = [p for p in range(c["P"]) if p not in mine]
     assert others and float(dp_one[others].abs().max()) == 0.0                 # and it reaches the albums it lists only
@@ -280,18 +211,18 @@ def test_functional_and_nn_surface():
     from fvta_memexqa_amd import functional as Fn, nn
     c, ref = _case("rows-JXRb+1")                                              # w = 256, an empty slot
     lists = c["albums"].tolist()                                               # a list of lists
-    pool, q, W, b = (_cu(c[k]).requires_grad_() for k in ("pool", "q", "W", "b"))
-    pm, qm, g = _cu(c["pm"]), _cu(c["qm"]), _cu(c["gout"])
+    pool, q, W, b = (cu(c[k]).requires_grad_() for k in ("pool", "q", "W", "b"))
+    pm, qm, g = cu(c["pm"]), cu(c["qm"]), cu(c["gout"])
     ha, a = Fn.attention_3d_pooled_raw(pool, q, lists, W, b, pm, qm, simiMatrix=c["simi"], add_tanh=c["tanh"],
                                        differentiable=True)
     assert ha.requires_grad and not a.requires_grad
     assert tuple(a.shape) == (c["NQ"], c["K"], c["T"], c["JQ"])
     (ha * g).sum().backward()
-    _close(ha, ref["h_a"])
-    _close(pool.grad, ref["dpool"], msg="functional d_pool")
-    _close(q.grad, ref["dq"], msg="functional d_hq")
-    _close(W.grad.reshape(-1), ref["dW"], msg="functional dW")
-    _close(b.grad, ref["db"], msg="functional db")
+    close_scaled(ha, ref["h_a"])
+    close_scaled(pool.grad, ref["dpool"], msg="functional d_pool")
+    close_scaled(q.grad, ref["dq"], msg="functional d_hq")
+    close_scaled(W.grad.reshape(-1), ref["dW"], msg="functional dW")
+    close_scaled(b.grad, ref["db"], msg="functional db")
     with pytest.raises(RuntimeError, match="forward-only"):                    # the default still refuses under gradient mode
         Fn.attention_3d_pooled_raw(pool, q, lists, W, b, pm, qm, simiMatrix=c["simi"], add_tanh=c["tanh"])
     with torch.no_grad():                                                      # and under no_grad it is the inference call
@@ -300,16 +231,16 @@ def test_functional_and_nn_surface():
 
     att = nn.FocalAttention3D(c["w"], simiMatrix=c["simi"], add_tanh=c["tanh"])
     with torch.no_grad():
-        att.p("att_logits/W").copy_(_cu(c["W"]))
-        att.p("att_logits/b").copy_(_cu(c["b"]))
-    p2, q2 = _cu(c["pool"]).requires_grad_(), _cu(c["q"]).requires_grad_()
+        att.p("att_logits/W").copy_(cu(c["W"]))
+        att.p("att_logits/b").copy_(cu(c["b"]))
+    p2, q2 = cu(c["pool"]).requires_grad_(), cu(c["q"]).requires_grad_()
     ha2, a2 = att.forward_pooled(p2, q2, lists, pm, qm, differentiable=True)
     assert not a2.requires_grad
     (ha2 * g).sum().backward()
-    _close(p2.grad, ref["dpool"], msg="nn d_pool")
-    _close(q2.grad, ref["dq"], msg="nn d_hq")
-    _close(att.p("att_logits/W").grad.reshape(-1), ref["dW"], msg="nn dW")
-    _close(att.p("att_logits/b").grad, ref["db"], msg="nn db")
+    close_scaled(p2.grad, ref["dpool"], msg="nn d_pool")
+    close_scaled(q2.grad, ref["dq"], msg="nn d_hq")
+    close_scaled(att.p("att_logits/W").grad.reshape(-1), ref["dW"], msg="nn dW")
+    close_scaled(att.p("att_logits/b").grad, ref["db"], msg="nn db")
     with pytest.raises(RuntimeError, match="forward-only"):
         att.forward_pooled(p2, q2, lists, pm, qm)
 
@@ -319,14 +250,14 @@ def test_unpadded_width_goes_through_channel_padding():
     c = B.odd_width_case()                                                     # w = 100 -> the 128-wide kernels
     ref = B.reference(c)
     assert B.qualifies(c, ref["a_logits"])
-    pool, q, W, b = (_cu(c[k]).requires_grad_() for k in ("pool", "q", "W", "b"))
-    ha, a = Fn.attention_3d_pooled_raw(pool, q, c["albums"], W, b, _cu(c["pm"]), _cu(c["qm"]), simiMatrix=c["simi"],
+    pool, q, W, b = (cu(c[k]).requires_grad_() for k in ("pool", "q", "W", "b"))
+    ha, a = Fn.attention_3d_pooled_raw(pool, q, c["albums"], W, b, cu(c["pm"]), cu(c["qm"]), simiMatrix=c["simi"],
                                        add_tanh=c["tanh"], differentiable=True)
     assert tuple(ha.shape) == (c["NQ"], 100)
-    (ha * _cu(c["gout"])).sum().backward()
+    (ha * cu(c["gout"])).sum().backward()
     assert tuple(pool.grad.shape) == (c["P"], c["K"], c["JX"], 100) and tuple(q.grad.shape) == (c["NQ"], c["JQ"], 100)
-    _close(ha, ref["h_a"])
-    _close(pool.grad, ref["dpool"], msg="d_pool")
-    _close(q.grad, ref["dq"], msg="d_hq")
-    _close(W.grad.reshape(-1), ref["dW"], msg="dW")
-    _close(b.grad, ref["db"], msg="db")
+    close_scaled(ha, ref["h_a"])
+    close_scaled(pool.grad, ref["dpool"], msg="d_pool")
+    close_scaled(q.grad, ref["dq"], msg="d_hq")
+    close_scaled(W.grad.reshape(-1), ref["dW"], msg="dW")
+    close_scaled(b.grad, ref["db"], msg="db")

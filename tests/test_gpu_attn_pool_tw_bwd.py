@@ -17,102 +17,26 @@ odd-width one: d_pool 0.02 (heavy), d_hq 0.01, d_lq 0.01, dW 0.05 (many), db 0.0
 dWC_b 0.42 (short-M1-JX7-warp3: counts up to 7 at M JX = 7; 0.01 at most outside the short cases).  The GPU's a_logits
 stay within 0.7 % of the smallest arg-max gap.
 Against the per-question route on `mix-simi2-masked` the nine gradients differ by at most 4e-7 of their largest value."""
-import numpy as np
 import pytest
 import torch
 
 from tests import _attn_pool_tw_bwd_ref as TB
+from tests._album_attn_gpu import (TrainRun, case, check_grads, close_scaled, cu, gather, listed, modules, nan_fill, output_names,
+                                   tol_of, want_of)
 
 pytestmark = pytest.mark.gpu
 
-_REF = {}
-NAMES = ("d_pool", "d_hq", "d_lq", "dW", "db", "dWH_W", "dWH_b", "dWC_W", "dWC_b")        # backward()'s outputs, in order
-KEYS = dict(zip(NAMES, TB.GRAD_KEYS))
+NAMES = output_names("pooled", True)                             # backward()'s nine outputs, in order
 OVERWRITTEN, ACCUMULATED = NAMES[:3], NAMES[3:]
-TOL_KEY = lambda key: {"dpool": "dh"}.get(key, key)
-
-
-def _close(a, b, rtol=1e-4, atol=1e-5, msg=""):
-    a = a.detach().cpu().double().numpy()
-    b = b.detach().cpu().double().numpy()
-    scale = max(1.0, float(np.abs(b).max()))
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol * scale, err_msg=msg)
-
-
-def _cu(t):
-    return None if t is None else t.cuda().contiguous()
 
 
 def _case(name):
     """the case and its fp64 reference, computed once per session and never written to"""
-    if name not in _REF:
-        c = TB.build_case(name)
-        _REF[name] = (c, TB.reference(c))
-    return _REF[name]
-
-
-def _want(ref, n, g):
-    want = ref[KEYS[n]]
-    return want[:g.shape[0]] if n == "dWH_W" else want
+    return case(TB, name)
 
 
 def _check_grads(name, got, ref, what=""):
-    for n, g in zip(NAMES, got):
-        want = _want(ref, n, g)
-        print("%s %s%s: worst |err| / (atol max(1, max|ref|) + rtol |ref|) = %.3f, max |ref| %.3g"
-              % (name, what, n, TB.within(g, want, KEYS[n])[1], float(want.abs().max())))
-    for n, g in zip(NAMES, got):
-        rtol, atol = TB.TOL[TOL_KEY(KEYS[n])]
-        _close(g, _want(ref, n, g), rtol=rtol, atol=atol, msg=what + n)
-
-
-class _Run:
-    """ops.PooledWarpedFocalAttention on case c (rows: a subset of the questions; albums: a replacement), its device
-    tensors kept for backward()"""
-
-    def __init__(self, c, rows=None, albums=None):
-        from fvta_memexqa_amd import ops
-        q, qm, al, g, lq = c["q"], c["qm"], (c["albums"] if albums is None else albums), c["gout"], c["lq"]
-        if rows is not None:
-            q, al, g, lq = q[rows], al[rows], g[rows], lq[rows]
-            qm = None if qm is None else qm[rows]
-        self.c, self.NQ, self.M, w = c, q.shape[0], al.shape[1], c["w"]
-        self.op = ops.PooledWarpedFocalAttention(c["P"], self.NQ, self.M, c["K"], c["JX"], c["JQ"], w, c["simi"], c["tanh"],
-                                                 c["warp_type"], c["window_t"])
-        self.pool, self.pm, self.q, self.qm = _cu(c["pool"]), _cu(ops.as_mask_u8(c["pm"])), _cu(q), _cu(ops.as_mask_u8(qm))
-        self.lq = _cu(lq)
-        self.al = ops.check_album_lists(al, c["P"], c["pm"] is not None and qm is not None).cuda()
-        self.W, self.b = _cu(c["W"].reshape(-1)), _cu(c["b"])
-        self.WH, self.WHb, self.WC, self.WCb = _cu(c["WH_W"]), _cu(c["WH_b"]), _cu(c["WC_W"].reshape(-1)), _cu(c["WC_b"])
-        self.g = _cu(g)
-        self.energy = self.op.album_energy(self.pool, self.WH, self.WC)
-
-    def _fwd_args(self):
-        return (self.pool, self.pm, self.energy, self.q, self.qm, self.lq, self.al, self.W, self.b, self.WHb, self.WC, self.WCb)
-
-    def forward_train(self, want_logits=True):
-        return self.op.forward_train(*self._fwd_args(), want_logits=want_logits, want_scale=True)
-
-    def forward(self, want_logits=True):
-        return self.op.forward(*self._fwd_args(), want_logits=want_logits, want_scale=True)
-
-    def backward(self, acc=None, fill=7.0):
-        """-> the nine outputs; d_pool, d_hq, d_lq prefilled with `fill`; acc: the six accumulated ones of an earlier call"""
-        c, w = self.c, self.c["w"]
-        dp = torch.full((c["P"], c["K"], c["JX"], w), fill, device="cuda")
-        dq = torch.full((self.NQ, c["JQ"], w), fill, device="cuda")
-        dlq = torch.full((self.NQ, w), fill, device="cuda")
-        if acc is None:
-            acc = (torch.zeros_like(self.W), torch.zeros(1, device="cuda"), torch.zeros(w, w, device="cuda"),
-                   torch.zeros(w, device="cuda"), torch.zeros(w, device="cuda"), torch.zeros(1, device="cuda"))
-        self.op.backward(self.pool, self.pm, self.q, self.qm, self.lq, self.al, self.W, self.b, self.WH, self.WHb, self.WC,
-                         self.WCb, self.g, dp, dq, dlq, *acc)
-        return (dp, dq, dlq) + tuple(acc)
-
-
-def _listed(c):
-    al = c["albums"].reshape(-1)
-    return torch.bincount(al[al >= 0], minlength=c["P"])
+    check_grads(name, got, ref, NAMES, TB.TOL, TB.within, what)
 
 
 @pytest.mark.parametrize("name", TB.CASE_IDS)
@@ -121,7 +45,7 @@ def test_gradients_match_fp64_autograd(name):
     c, ref = _case(name)
     plan, bwd_plan = TB.plans_of(c)                              # the host-only plans: no device yet
     TB.loop_regime(name, c, plan, bwd_plan)                      # a past-one-round case reaches its loop, before any launch
-    run = _Run(c)
+    run = TrainRun(c, "pooled", True)
     unwarped = ops.PooledFocalAttention(c["P"], c["NQ"], c["M"], c["K"], c["JX"], c["JQ"], c["w"], c["simi"], c["tanh"])
     assert run.op.plan() == unwarped.plan() == plan and run.op.bwd_plan() == unwarped.bwd_plan() == bwd_plan   # the warp changes none
     ha, a, s = run.forward_train()
@@ -131,11 +55,11 @@ def test_gradients_match_fp64_autograd(name):
     err = float((a.cpu().double() - ref["a_logits"])[v].abs().max())
     print("%s: max |a_logits - fp64| over valid entries %.3g, smallest gap %.3g" % (name, err, min(jgap, tgap)))
     assert err < min(jgap, tgap) / 4, (err, jgap, tgap)
-    _close(ha, ref["h_a"], msg="h_a")
-    _close(s, ref["scale"], msg="scale")
+    close_scaled(ha, ref["h_a"], msg="h_a")
+    close_scaled(s, ref["scale"], msg="scale")
     got = run.backward()                                         # d_pool / d_hq / d_lq prefilled with 7.0: overwritten
     _check_grads(name, got, ref)
-    unlisted = _listed(c) == 0
+    unlisted = listed(c) == 0
     if bool(unlisted.any()):                                     # albums nobody lists: exactly zero, not the 7.0
         assert float(got[0].cpu()[unlisted].abs().max()) == 0.0
     nothing = (c["albums"] < 0).all(1)
@@ -143,18 +67,18 @@ def test_gradients_match_fp64_autograd(name):
         assert float(got[1].cpu()[nothing].abs().max()) == 0.0 and float(got[2].cpu()[nothing].abs().max()) == 0.0
     again = run.backward(acc=got[3:], fill=-3.0)                 # a second call: the parameter gradients accumulate ...
     for n, g in zip(ACCUMULATED, again[3:]):
-        rtol, atol = TB.TOL[n]
-        _close(g, 2 * _want(ref, n, g), rtol=rtol, atol=2 * atol, msg=n + " accumulates")
+        rtol, atol = tol_of(TB.TOL, n)
+        close_scaled(g, 2 * want_of(ref, n, g), rtol=rtol, atol=2 * atol, msg=n + " accumulates")
     for n, g in zip(OVERWRITTEN, again[:3]):                     # ... the others do not
-        rtol, atol = TB.TOL[TOL_KEY(KEYS[n])]
-        _close(g, _want(ref, n, g), rtol=rtol, atol=atol, msg=n + " overwritten")
+        rtol, atol = tol_of(TB.TOL, n)
+        close_scaled(g, want_of(ref, n, g), rtol=rtol, atol=atol, msg=n + " overwritten")
 
 
 @pytest.mark.parametrize("name", ["mix-simi2-masked", "cols-jq33-w128", "rows-JX260", "wide2048", "all-empty-simi3",
                                   "short-M3-JX3-warp3"])
 def test_forward_train_has_the_bits_of_the_inference_forward(name):
     c, _ = _case(name)
-    run = _Run(c)
+    run = TrainRun(c, "pooled", True)
     ha_t, a_t, s_t = run.forward_train()
     ha_i, a_i, s_i = run.forward()
     assert torch.equal(ha_t, ha_i) and torch.equal(a_t, a_i) and torch.equal(s_t, s_i)
@@ -168,16 +92,16 @@ def _shared_run(c, album):
     w = c["w"]
     sh = ops.SharedWarpedFocalAttention(c["P"], c["NQ"], c["K"], c["JX"], c["JQ"], w, c["simi"], c["tanh"], c["warp_type"],
                                         c["window_t"])
-    pool, pm, q, qm = _cu(c["pool"]), _cu(ops.as_mask_u8(c["pm"])), _cu(c["q"]), _cu(ops.as_mask_u8(c["qm"]))
-    lq, al = _cu(c["lq"]), ops.check_album_index(album, c["P"]).cuda()
-    W, b = _cu(c["W"].reshape(-1)), _cu(c["b"])
-    WH, WHb, WC, WCb = _cu(c["WH_W"]), _cu(c["WH_b"]), _cu(c["WC_W"].reshape(-1)), _cu(c["WC_b"])
+    pool, pm, q, qm = cu(c["pool"]), cu(ops.as_mask_u8(c["pm"])), cu(c["q"]), cu(ops.as_mask_u8(c["qm"]))
+    lq, al = cu(c["lq"]), ops.check_album_index(album, c["P"]).cuda()
+    W, b = cu(c["W"].reshape(-1)), cu(c["b"])
+    WH, WHb, WC, WCb = cu(c["WH_W"]), cu(c["WH_b"]), cu(c["WC_W"].reshape(-1)), cu(c["WC_b"])
     e = sh.album_energy(pool, WH, WC)
     fwd = sh.forward_train(pool, pm, e, q, qm, lq, al, W, b, WHb, WC, WCb, want_logits=True, want_scale=True)
     dh, dq, dlq = torch.full_like(pool, 7.0), torch.full_like(q, 7.0), torch.full_like(lq, 7.0)
     acc = (torch.zeros_like(W), torch.zeros(1, device="cuda"), torch.zeros(w, w, device="cuda"), torch.zeros(w, device="cuda"),
            torch.zeros(w, device="cuda"), torch.zeros(1, device="cuda"))
-    sh.backward(pool, pm, q, qm, lq, al, W, b, WH, WHb, WC, WCb, _cu(c["gout"]), dh, dq, dlq, *acc)
+    sh.backward(pool, pm, q, qm, lq, al, W, b, WH, WHb, WC, WCb, cu(c["gout"]), dh, dq, dlq, *acc)
     return fwd, (dh, dq, dlq) + acc, sh.saved
 
 
@@ -190,7 +114,7 @@ def test_one_slot_has_the_bits_of_the_shared_warped_pair(name):
     c, _ = _case(name)
     album = c["albums"][:, 0].clamp(min=0)
     c1 = dict(c, albums=album[:, None], M=1, T=c["JX"])
-    run = _Run(c1)
+    run = TrainRun(c1, "pooled", True)
     fwd = run.forward_train()
     got = run.backward()
     fwd_s, got_s, saved_s = _shared_run(c1, album)
@@ -213,11 +137,11 @@ def _shared_run_forward_only(c, album, saved):
     sh = ops.SharedWarpedFocalAttention(c["P"], c["NQ"], c["K"], c["JX"], c["JQ"], c["w"], c["simi"], c["tanh"], c["warp_type"],
                                         c["window_t"])
     sh.saved = saved
-    pool, pm, q, qm = _cu(c["pool"]), _cu(ops.as_mask_u8(c["pm"])), _cu(c["q"]), _cu(ops.as_mask_u8(c["qm"]))
-    WH, WHb, WC, WCb = _cu(c["WH_W"]), _cu(c["WH_b"]), _cu(c["WC_W"].reshape(-1)), _cu(c["WC_b"])
+    pool, pm, q, qm = cu(c["pool"]), cu(ops.as_mask_u8(c["pm"])), cu(c["q"]), cu(ops.as_mask_u8(c["qm"]))
+    WH, WHb, WC, WCb = cu(c["WH_W"]), cu(c["WH_b"]), cu(c["WC_W"].reshape(-1)), cu(c["WC_b"])
     e = sh.album_energy(pool, WH, WC)
-    sh.forward_train(pool, pm, e, q, qm, _cu(c["lq"]), ops.check_album_index(album, c["P"]).cuda(), _cu(c["W"].reshape(-1)),
-                     _cu(c["b"]), WHb, WC, WCb)
+    sh.forward_train(pool, pm, e, q, qm, cu(c["lq"]), ops.check_album_index(album, c["P"]).cuda(), cu(c["W"].reshape(-1)),
+                     cu(c["b"]), WHb, WC, WCb)
 
 
 @pytest.mark.parametrize("name", ["mix-simi3-masked", "rows-JX260", "cols-jq64-w512", "many", "heavy", "tiles", "slots9"])
@@ -227,18 +151,12 @@ def test_two_backward_calls_are_bitwise_equal(name):
     c, _ = _case(name)
     outs = []
     for _ in range(2):
-        run = _Run(c)                                            # a fresh handle: plan, saved and workspace anew
+        run = TrainRun(c, "pooled", True)                        # a fresh handle: plan, saved and workspace anew
         run.forward_train(want_logits=False)
         outs.append(run.backward())
     assert len(outs[0]) == 9
     for n, x, y in zip(NAMES, outs[0], outs[1]):
         assert torch.equal(x, y), n
-
-
-def _nan_fill(buf):
-    """every aligned four bytes of a byte buffer: the quiet NaN 0x7FC00000"""
-    flat = buf.reshape(-1)
-    flat[:flat.numel() // 4 * 4].view(torch.int32).fill_(0x7FC00000)
 
 
 @pytest.mark.parametrize("name", ["mix-simi1-masked", "mix-simi2-masked", "mix-simi3-masked", "all-empty-simi1", "all-empty-simi3"])
@@ -249,15 +167,15 @@ def test_nothing_is_read_that_no_launch_wrote(name):
     finite and the bits of an ordinary run."""
     c, _ = _case(name)
     assert bool((c["albums"] < 0).any())
-    base = _Run(c)
+    base = TrainRun(c, "pooled", True)
     base.forward_train(want_logits=False)
     want = base.backward()
-    run = _Run(c)
+    run = TrainRun(c, "pooled", True)
     run.forward_train(want_logits=False)                         # allocates op.saved
     run.backward()                                               # ... and op.work_bwd
-    _nan_fill(run.op.saved)
+    nan_fill(run.op.saved)
     run.forward_train(want_logits=False)                         # rewrites what it writes; the rest stays NaN
-    _nan_fill(run.op.work_bwd)
+    nan_fill(run.op.work_bwd)
     got = run.backward()
     for n, x, y in zip(NAMES, got, want):
         assert bool(torch.isfinite(x).all()), n
@@ -283,11 +201,11 @@ def test_a_questions_gradient_bits_do_not_depend_on_its_company(name, i):
     drop = _apart_from(c, i)
     assert drop and any(p >= 0 for p in c["albums"][i].tolist())
     keep = [j for j in range(c["NQ"]) if j not in drop]
-    run = _Run(c)
+    run = TrainRun(c, "pooled", True)
     assert run.op.bwd_plan()["tsplit"] == 1
     run.forward_train(want_logits=False)
     got_all = run.backward()
-    sub = _Run(c, rows=keep)
+    sub = TrainRun(c, "pooled", True, rows=keep)
     assert sub.op.bwd_plan()["tsplit"] == 1
     sub.forward_train(want_logits=False)
     got_sub = sub.backward()
@@ -308,32 +226,19 @@ def test_a_question_alone_keeps_its_d_lq_bits():
     spreading of a reference's rows over free accumulator regions, so d_hq's dQs sum has
     another order: held to the tolerance in this one case.  Its d_pool reaches the albums it lists only."""
     c, _ = _case("mix-simi3-masked")
-    run = _Run(c)
+    run = TrainRun(c, "pooled", True)
     run.forward_train(want_logits=False)
     got_all = run.backward()
     i = next(i for i, row in enumerate(c["albums"].tolist()) if min(row) >= 0 and len(set(row)) > 1)
-    one = _Run(c, rows=[i])
+    one = TrainRun(c, "pooled", True, rows=[i])
     one.forward_train(want_logits=False)
     got_one = one.backward()
     assert torch.equal(got_one[2][0], got_all[2][i]), "d_lq alone against in company"
-    _close(got_one[1][0], got_all[1][i], msg="d_hq alone against in company, other group counts")
+    close_scaled(got_one[1][0], got_all[1][i], msg="d_hq alone against in company, other group counts")
     mine = set(c["albums"][i].tolist())
     others = [p for p in range(c["P"]) if p not in mine]
     assert others and float(got_one[0][others].abs().max()) == 0.0
     assert all(float(got_one[0][p].abs().max()) > 0.0 for p in mine)
-
-
-def _gather(pool, pm, al):
-    """on the device, differentiable in pool: (hinfo [NQ,K,M JX,w], mask bool [NQ,K,M JX]) of lists al [NQ,M]; an empty
-    slot: zero rows, mask 0"""
-    NQ, M = al.shape
-    Pn, K, JX, w = pool.shape
-    live = (al >= 0)
-    idx = al.clamp(min=0).long()
-    h = pool[idx] * live[:, :, None, None, None]                                 # [NQ,M,K,JX,w]
-    m = pm[idx] & live[:, :, None, None]
-    return (h.permute(0, 2, 1, 3, 4).reshape(NQ, K, M * JX, w).contiguous(),
-            m.permute(0, 2, 1, 3).reshape(NQ, K, M * JX).contiguous())
 
 
 def test_same_result_as_the_per_question_route(attn_select):
@@ -344,41 +249,29 @@ def test_same_result_as_the_per_question_route(attn_select):
     the sum of their bounds: twice the tolerance of each output."""
     c = TB.build_case(TB.MIX_MASKED, parity=False)
     assert bool((c["albums"] < 0).any())
-    run = _Run(c)
+    run = TrainRun(c, "pooled", True)
     run.forward_train(want_logits=False)
     got = run.backward()
     attn_select.exact()
-    att, tw = _modules(c)
-    pool, q, lq = (_cu(c[k]).requires_grad_() for k in ("pool", "q", "lq"))
-    rows, mask = _gather(pool, _cu(c["pm"]), run.al)
+    att, tw = modules(c)
+    pool, q, lq = (cu(c[k]).requires_grad_() for k in ("pool", "q", "lq"))
+    rows, mask = gather(pool, cu(c["pm"]), run.al)
     warped = tw(rows, lq)[0]
-    h_a, _ = att(warped, q, mask, _cu(c["qm"]))
+    h_a, _ = att(warped, q, mask, cu(c["qm"]))
     (h_a * run.g).sum().backward()
     want = (pool.grad, q.grad, lq.grad, att.p("att_logits/W").grad.reshape(-1), att.p("att_logits/b").grad, tw.p("WH/W").grad,
             tw.p("WH/b").grad, tw.p("WC/W").grad.reshape(-1), tw.p("WC/b").grad)
     for n, g, wnt in zip(NAMES, got, want):
-        rtol, atol = TB.TOL[TOL_KEY(KEYS[n])]
+        rtol, atol = tol_of(TB.TOL, n)
         assert wnt is not None, n
         wnt = wnt[:g.shape[0]] if n == "dWH_W" else wnt
         print("per-question %s: max |diff| %.3g, max |ref| %.3g" % (n, float((g - wnt).abs().max()), float(wnt.abs().max())))
-        _close(g, wnt, rtol=2 * rtol, atol=2 * atol, msg=n + " against the per-question route")
-    unlisted = (_listed(c) == 0).nonzero().reshape(-1)
+        close_scaled(g, wnt, rtol=2 * rtol, atol=2 * atol, msg=n + " against the per-question route")
+    unlisted = (listed(c) == 0).nonzero().reshape(-1)
     assert unlisted.numel() == 1 and float(got[0][int(unlisted[0])].abs().max()) == 0.0
     fully_masked_q = (~c["qm"].any(-1)).nonzero().reshape(-1)
     assert fully_masked_q.numel() == 1
     assert float(got[1][int(fully_masked_q[0])].abs().max()) == 0.0   # nothing passes into a fully masked question's hq
-
-
-def _modules(c):
-    from fvta_memexqa_amd import nn
-    att = nn.FocalAttention3D(c["w"], simiMatrix=c["simi"], add_tanh=c["tanh"])
-    tw = nn.TimeWarp(c["w"], warp_type=c["warp_type"], window_t=c["window_t"])
-    with torch.no_grad():
-        att.p("att_logits/W").copy_(c["W"])
-        att.p("att_logits/b").copy_(c["b"])
-        for name, key in (("WH/W", "WH_W"), ("WH/b", "WH_b"), ("WC/W", "WC_W"), ("WC/b", "WC_b")):
-            tw.p(name).copy_(c[key])
-    return att, tw
 
 
 LEAVES = ("pool", "q", "lq", "W", "b", "WH_W", "WH_b", "WC_W", "WC_b")
@@ -393,15 +286,15 @@ def _leaf_grads(t):
 def test_public_surface_matches_the_ops_level_result():
     from fvta_memexqa_amd import autograd, functional as Fn, nn, ops
     c, ref = _case("rows-JXRb+1")                                              # w = 256, an empty slot
-    run = _Run(c)
+    run = TrainRun(c, "pooled", True)
     ha_o, a_o, s_o = run.forward_train()
     got = run.backward()
     lists = c["albums"].tolist()                                               # a list of lists
-    pm, qm, g = _cu(c["pm"]), _cu(c["qm"]), _cu(c["gout"])
+    pm, qm, g = cu(c["pm"]), cu(c["qm"]), cu(c["gout"])
     kw = dict(simiMatrix=c["simi"], add_tanh=c["tanh"], warp_type=c["warp_type"], window_t=c["window_t"])
     args = lambda d: (d["pool"], d["q"], lists, d["lq"], d["W"], d["b"], d["WH_W"], d["WH_b"], d["WC_W"], d["WC_b"], pm, qm)
     # functional
-    t = {k: _cu(c[k]).requires_grad_() for k in LEAVES}
+    t = {k: cu(c[k]).requires_grad_() for k in LEAVES}
     ha, a, s = Fn.attention_3d_pooled_warped_raw(*args(t), differentiable=True, **kw)
     assert ha.requires_grad and not a.requires_grad and not s.requires_grad
     assert tuple(a.shape) == (c["NQ"], c["K"], c["T"], c["JQ"]) and tuple(s.shape) == (c["NQ"], c["T"])
@@ -416,7 +309,7 @@ def test_public_surface_matches_the_ops_level_result():
     with torch.no_grad():
         e = Fn.album_energy(t["pool"], t["WH_W"], t["WC_W"])
     assert tuple(e.shape) == (c["P"], c["JX"])
-    t2 = {k: _cu(c[k]).requires_grad_() for k in LEAVES}
+    t2 = {k: cu(c[k]).requires_grad_() for k in LEAVES}
     ha2, a2, s2 = Fn.attention_3d_pooled_warped_raw(*args(t2), energy=e, differentiable=True, **kw)
     (ha2 * g).sum().backward()
     assert torch.equal(ha2, ha) and torch.equal(a2, a) and torch.equal(s2, s)
@@ -428,7 +321,7 @@ def test_public_surface_matches_the_ops_level_result():
         ha_i, _, _ = Fn.attention_3d_pooled_warped_raw(*args(t), **kw)
     assert torch.equal(ha_i, ha.detach())
     # autograd
-    t3 = {k: _cu(c[k]).requires_grad_() for k in LEAVES}
+    t3 = {k: cu(c[k]).requires_grad_() for k in LEAVES}
     ha3, a3, s3 = autograd.pooled_warped_focal_attention(
         t3["pool"], t3["q"], t3["lq"], run.al, t3["W"].reshape(-1), t3["b"], t3["WH_W"], t3["WH_b"], t3["WC_W"], t3["WC_b"],
         ops.as_mask_u8(pm), ops.as_mask_u8(qm), c["simi"], c["tanh"], c["warp_type"], c["window_t"])
@@ -437,8 +330,8 @@ def test_public_surface_matches_the_ops_level_result():
     for n, x, y in zip(NAMES, _leaf_grads(t3), got):
         assert torch.equal(x[:y.shape[0]] if n == "dWH_W" else x, y), "autograd " + n
     # nn
-    att, tw = _modules(c)
-    p4, q4, lq4 = (_cu(c[k]).requires_grad_() for k in ("pool", "q", "lq"))
+    att, tw = modules(c)
+    p4, q4, lq4 = (cu(c[k]).requires_grad_() for k in ("pool", "q", "lq"))
     ha4, a4 = att.forward_pooled_warped(p4, q4, lists, lq4, tw, pm, qm)
     assert ha4.requires_grad and not a4.requires_grad
     (ha4 * g).sum().backward()
@@ -458,16 +351,16 @@ def test_unpadded_width_goes_through_channel_padding():
     c = TB.odd_width_case()                                                    # w = 50 -> the 64-wide kernels
     ref = TB.reference(c)
     assert TB.qualifies(c, ref["a_logits"])
-    t = {k: _cu(c[k]).requires_grad_() for k in LEAVES}
+    t = {k: cu(c[k]).requires_grad_() for k in LEAVES}
     ha, a, s = Fn.attention_3d_pooled_warped_raw(t["pool"], t["q"], c["albums"], t["lq"], t["W"], t["b"], t["WH_W"], t["WH_b"],
-                                                 t["WC_W"], t["WC_b"], _cu(c["pm"]), _cu(c["qm"]), simiMatrix=c["simi"],
+                                                 t["WC_W"], t["WC_b"], cu(c["pm"]), cu(c["qm"]), simiMatrix=c["simi"],
                                                  add_tanh=c["tanh"], warp_type=c["warp_type"], window_t=c["window_t"],
                                                  differentiable=True)
     assert tuple(ha.shape) == (c["NQ"], 50)
-    (ha * _cu(c["gout"])).sum().backward()
+    (ha * cu(c["gout"])).sum().backward()
     assert tuple(t["pool"].grad.shape) == (c["P"], c["K"], c["JX"], 50) and tuple(t["lq"].grad.shape) == (c["NQ"], 50)
-    _close(ha, ref["h_a"])
-    _close(s, ref["scale"])
+    close_scaled(ha, ref["h_a"])
+    close_scaled(s, ref["scale"])
     grads = _leaf_grads(t)
     assert tuple(grads[5].shape) == (100, 50) and float(grads[5][50:].abs().max()) == 0.0
     _check_grads("odd-width", grads, ref)

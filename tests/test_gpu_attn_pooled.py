@@ -8,66 +8,35 @@ slots, an album twice in one list, row tiles at JX = 1, 7, R-1, R, R+1, 200, que
 widths up to 2048, nine slots, K = 6, P = NQ = M = 1, a question without any album; G and R are read from
 fvta_attn_pool_plan.  LOOP_SPECS goes past one round of the plan's and the weighted sum's loops, each case asserting its
 regime through the plan's words before it launches.  Every index given to a GPU call is valid."""
-import numpy as np
 import pytest
 import torch
 
 from tests import _attn_pooled_ref as R
 from tests import _attn_shared_ref as S
+from tests._album_attn_gpu import case, close, cu, handle, infer
 
 pytestmark = pytest.mark.gpu
 
-_REF = {}
 FP32 = dict(rtol=2e-5, atol=2e-6)
-
-
-def _close(a, b, rtol=1e-4, atol=1e-5, msg=""):
-    a = a.detach().cpu().double().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, np.float64)
-    b = b.detach().cpu().double().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float64)
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
-
-
-def _cu(t):
-    return None if t is None else t.cuda().contiguous()
 
 
 def _case(name, simi, tanh, masked):
     """the case and its fp64 reference, computed once per session and never written to"""
-    key = (name, simi, tanh, masked)
-    if key not in _REF:
-        c = R.build_case(name, simi, masked)
-        _REF[key] = (c, R.reference(c, tanh))
-    return _REF[key]
+    return case(R, (name, simi, tanh, masked), lambda key: R.build_case(name, simi, masked), lambda c: R.reference(c, tanh))
 
 
 def _loop_case(name):
-    if name not in _REF:
-        c = R.loop_case(name)
-        _REF[name] = (c, R.reference(c, c["tanh"]))
-    return _REF[name]
+    return case(R, name, R.loop_case, lambda c: R.reference(c, c["tanh"]))
 
 
-def _op(c, tanh, NQ=None):
-    from fvta_memexqa_amd import ops
-    return ops.PooledFocalAttention(c["P"], c["NQ"] if NQ is None else NQ, c["M"], c["K"], c["JX"], c["JQ"], c["w"], c["simi"],
-                                    tanh)
+def _op(c, tanh):
+    return handle(c, "pooled", tanh=tanh)
 
 
-def _run(c, tanh, want_logits=True, rows=None, albums=None, pool=None, pm=None):
+def _run(c, tanh, **kw):
     """ops.PooledFocalAttention on case c; rows: a subset of the questions (an index list); albums / pool / pm: in place
     of the case's own"""
-    from fvta_memexqa_amd import ops
-    q, qm = c["q"], c["qm"]
-    al = c["albums"] if albums is None else albums
-    pool = c["pool"] if pool is None else pool
-    pm = c["pm"] if pm is None else pm
-    if rows is not None:
-        q, al = q[rows], al[rows]
-        qm = None if qm is None else qm[rows]
-    idx = ops.check_album_lists(al, c["P"], c["pm"] is not None)
-    return _op(c, tanh, q.shape[0]).forward(_cu(pool), _cu(ops.as_mask_u8(pm)), _cu(q), _cu(ops.as_mask_u8(qm)), idx.cuda(),
-                                            None if c["W"] is None else _cu(c["W"].reshape(-1)), _cu(c["b"]),
-                                            want_logits=want_logits)
+    return infer(c, "pooled", tanh=tanh, **kw)
 
 
 def _report(name, ha, a, ref_ha, ref_a):
@@ -83,8 +52,8 @@ def test_matches_the_fp64_reference(name, simi, tanh, masked):
     c, (ref_ha, ref_a) = _case(name, simi, tanh, masked)
     ha, a = _run(c, tanh)
     _report(name, ha, a, ref_ha, ref_a)
-    _close(ha, ref_ha, msg="h_a")
-    _close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
+    close(ha, ref_ha, msg="h_a")
+    close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
     if name == "all-empty":                                                 # a question without any album: exactly 0
         assert c["albums"][1].tolist() == [-1, -1]
         assert torch.equal(ha[1].cpu(), torch.zeros(c["w"])) and bool((a[1] == R.NEG).all())
@@ -105,8 +74,8 @@ def test_loop_cases_match_the_fp64_reference(name):
     R.loop_regime(name, c, _op(c, c["tanh"]).plan())                         # before anything is launched
     ha, a = _run(c, c["tanh"])
     _report(name, ha, a, ref_ha, ref_a)
-    _close(ha, ref_ha, msg="h_a")
-    _close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
+    close(ha, ref_ha, msg="h_a")
+    close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
     ha2, a2 = _run(c, c["tanh"])                                             # the plan's cursor atomics race: no bit moves
     assert torch.equal(ha, ha2) and torch.equal(a, a2)
 
@@ -116,8 +85,8 @@ def test_loop_cases_match_the_fp64_reference(name):
 def test_one_slot_is_the_shared_call_bit_for_bit(simi, tanh, masked):
     from fvta_memexqa_amd import ops
     c = S.build_case("mix", simi, masked)
-    args = (_cu(c["h"]), _cu(ops.as_mask_u8(c["hm"])), _cu(c["q"]), _cu(ops.as_mask_u8(c["qm"])))
-    Wb = (None if c["W"] is None else _cu(c["W"].reshape(-1)), _cu(c["b"]))
+    args = (cu(c["h"]), cu(ops.as_mask_u8(c["hm"])), cu(c["q"]), cu(ops.as_mask_u8(c["qm"])))
+    Wb = (None if c["W"] is None else cu(c["W"].reshape(-1)), cu(c["b"]))
     shared = ops.SharedFocalAttention(c["A"], c["NQ"], c["K"], c["T"], c["JQ"], c["w"], simi, tanh)
     ha_s, a_s = shared.forward(*args, ops.check_album_index(c["album"], c["A"]).cuda(), *Wb, want_logits=True)
     pooled = ops.PooledFocalAttention(c["A"], c["NQ"], 1, c["K"], c["T"], c["JQ"], c["w"], simi, tanh)
@@ -136,13 +105,13 @@ def test_same_result_as_the_per_question_kernel(name, simi, tanh, masked, attn_s
     h, m = R.expand(c)                                                       # [NQ,K,T,w]: what the pooled call never builds
     attn_select.exact()
     op = ops.FocalAttention(c["NQ"], c["K"], c["T"], c["JQ"], c["w"], simi, tanh)
-    ref_ha, ref_a = op.forward(_cu(h), _cu(c["q"]), _cu(ops.as_mask_u8(m)), _cu(ops.as_mask_u8(c["qm"])),
-                               _cu(c["W"].reshape(-1)), _cu(c["b"]), want_logits=True)
+    ref_ha, ref_a = op.forward(cu(h), cu(c["q"]), cu(ops.as_mask_u8(m)), cu(ops.as_mask_u8(c["qm"])),
+                               cu(c["W"].reshape(-1)), cu(c["b"]), want_logits=True)
     ha, a = _run(c, tanh)
     print("%s against the per-question exact kernel: max |h_a diff| %.3g, max |a_logits diff| %.3g"
           % (name, float((ha - ref_ha).abs().max()), float((a - ref_a).abs().max())))
-    _close(ha, ref_ha, msg="h_a against the per-question exact kernel", **FP32)
-    _close(a, ref_a, msg="a_logits against the per-question exact kernel", **FP32)
+    close(ha, ref_ha, msg="h_a against the per-question exact kernel", **FP32)
+    close(a, ref_a, msg="a_logits against the per-question exact kernel", **FP32)
 
 
 # ---- placement changes no bit
@@ -167,8 +136,8 @@ def test_a_question_does_not_depend_on_its_company():
     twice = next(i for i, r in enumerate(c["albums"].tolist()) if min(r) >= 0 and len(set(r)) < len(r))
     for i in (0, twice, c["NQ"] - 1):                                        # the last: the one with the empty slot, fully masked
         ha_one, a_one = _run(c, True, rows=[i])
-        _close(ha_one[0], ha[i], msg="alone against in company, question %d" % i, **FP32)
-        _close(a_one[0], a[i], **FP32)
+        close(ha_one[0], ha[i], msg="alone against in company, question %d" % i, **FP32)
+        close(a_one[0], a[i], **FP32)
 
 
 def test_slot_order_permutes_the_logit_blocks():
@@ -183,7 +152,7 @@ def test_slot_order_permutes_the_logit_blocks():
     ha2, a2 = _run(c, True, albums=al)
     blocks = a[i].reshape(c["K"], c["M"], JX, c["JQ"])[:, order].reshape(c["K"], c["T"], c["JQ"])
     assert torch.equal(a2[i], blocks)                                        # its blocks move with the slots, bit for bit
-    _close(ha2[i], ha[i], msg="the merge order moves", **FP32)
+    close(ha2[i], ha[i], msg="the merge order moves", **FP32)
     keep = [j for j in range(c["NQ"]) if j != i]
     assert torch.equal(ha2[keep], ha[keep]) and torch.equal(a2[keep], a[keep])
 
@@ -193,7 +162,7 @@ def test_functional_and_nn_surface():
     from fvta_memexqa_amd import functional as Fn, nn
     c, (ref_ha, ref_a) = _case("rows1", 2, True, True)                       # w = 256, simiMatrix 2, tanh
     ha_ops, a_ops = _run(c, True)
-    pool, q, W, b, pm, qm = _cu(c["pool"]), _cu(c["q"]), _cu(c["W"]), _cu(c["b"]), _cu(c["pm"]), _cu(c["qm"])
+    pool, q, W, b, pm, qm = cu(c["pool"]), cu(c["q"]), cu(c["W"]), cu(c["b"]), cu(c["pm"]), cu(c["qm"])
     with torch.no_grad():
         ha, a = Fn.attention_3d_pooled_raw(pool, q, c["albums"], W, b, pm, qm, simiMatrix=2, add_tanh=True)
     assert torch.equal(ha, ha_ops) and torch.equal(a, a_ops)
@@ -223,11 +192,11 @@ def test_functional_pads_the_width():
     c = R.make_case(R.lists_from_counts([3, 1, 2], 2, 7, True), 3, 2, 9, 5, w, 3, True, 71)
     ref_ha, ref_a = R.reference(c, True)
     with torch.no_grad():
-        ha, a = Fn.attention_3d_pooled_raw(_cu(c["pool"]), _cu(c["q"]), c["albums"], _cu(c["W"]), _cu(c["b"]), _cu(c["pm"]),
-                                           _cu(c["qm"]), simiMatrix=3, add_tanh=True)
+        ha, a = Fn.attention_3d_pooled_raw(cu(c["pool"]), cu(c["q"]), c["albums"], cu(c["W"]), cu(c["b"]), cu(c["pm"]),
+                                           cu(c["qm"]), simiMatrix=3, add_tanh=True)
     assert tuple(ha.shape) == (c["NQ"], w) and tuple(a.shape) == (c["NQ"], c["K"], c["T"], c["JQ"])
-    _close(ha, ref_ha, msg="h_a")
-    _close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
+    close(ha, ref_ha, msg="h_a")
+    close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
 
 
 def test_from_context_agrees_with_the_per_question_forward(attn_select):
@@ -247,5 +216,5 @@ def test_from_context_agrees_with_the_per_question_forward(attn_select):
         ha_p, a_p = mem.attend(att, hq, qm, albums)
     print("from_context against forward(): max |h_a diff| %.3g, max |a_logits diff| %.3g"
           % (float((ha_p - ha_f).abs().max()), float((a_p - a_f).abs().max())))
-    _close(ha_p, ha_f, msg="h_a: the pool cut from the context against forward() on the context", **FP32)
-    _close(a_p, a_f, msg="a_logits", **FP32)
+    close(ha_p, ha_f, msg="h_a: the pool cut from the context against forward() on the context", **FP32)
+    close(a_p, a_f, msg="a_logits", **FP32)

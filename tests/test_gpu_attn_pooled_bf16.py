@@ -12,28 +12,16 @@ listed twice, an album nobody lists.  The bf16 pool of a case is c["pool"].to(to
 call is valid."""
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 
 from tests import _attn_pooled_ref as R
 from tests import _attn_pooled_tw_ref as PT
+from tests._album_attn_gpu import album_energy, close, cu, infer, modules, once
 
 pytestmark = pytest.mark.gpu
 
 BF16 = torch.bfloat16
-_CASES = {}
-_REF64 = {}
-
-
-def _close(a, b, rtol=1e-4, atol=1e-5, msg=""):
-    a = a.detach().cpu().double().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, np.float64)
-    b = b.detach().cpu().double().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float64)
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
-
-
-def _cu(t):
-    return None if t is None else t.cuda().contiguous()
 
 
 def _same(got, want, what=""):
@@ -46,7 +34,7 @@ def _same(got, want, what=""):
 def _case(key):
     """a case with its bf16 pool and the widened pool, built once and never written to.  key: (name, simi, tanh, masked) of
     R.CASES, a name of R.LOOP_IDS, or ("tw", name) of the warped reference"""
-    if key not in _CASES:
+    def make():
         if isinstance(key, tuple) and key[0] == "tw":
             c = PT.build_case(key[1])
         elif isinstance(key, tuple):
@@ -54,36 +42,25 @@ def _case(key):
         else:
             c = R.loop_case(key)
         bf = c["pool"].to(BF16)
-        _CASES[key] = dict(c, bf=bf, wide=bf.float())
-    return _CASES[key]
+        return dict(c, bf=bf, wide=bf.float())
+    return once(("bf16", key), make)
 
 
 def _fwd(c, pool, want_logits=True):
     """ops.PooledFocalAttention.forward on case c with `pool` (on the device) in place of the case's"""
-    from fvta_memexqa_amd import ops
-    op = ops.PooledFocalAttention(c["P"], c["NQ"], c["M"], c["K"], c["JX"], c["JQ"], c["w"], c["simi"], c["tanh"])
-    idx = ops.check_album_lists(c["albums"], c["P"], c["pm"] is not None)
-    return op.forward(pool, _cu(ops.as_mask_u8(c["pm"])), _cu(c["q"]), _cu(ops.as_mask_u8(c["qm"])), idx.cuda(),
-                      None if c["W"] is None else _cu(c["W"].reshape(-1)), _cu(c["b"]), want_logits=want_logits)
+    return infer(c, "pooled", pool=pool, want_logits=want_logits)
 
 
 def _fwd_tw(c, pool, energy=None):
     """ops.PooledWarpedFocalAttention on case c with `pool` -> (energy, (h_a, a_logits, scale))"""
-    from fvta_memexqa_amd import ops
-    op = ops.PooledWarpedFocalAttention(c["P"], c["NQ"], c["M"], c["K"], c["JX"], c["JQ"], c["w"], c["simi"], c["tanh"],
-                                        c["warp_type"], c["window_t"])
     if energy is None:
-        energy = op.album_energy(pool, _cu(c["WH_W"]), _cu(c["WC_W"].reshape(-1)))
-    idx = ops.check_album_lists(c["albums"], c["P"], c["pm"] is not None)
-    out = op.forward(pool, _cu(ops.as_mask_u8(c["pm"])), energy, _cu(c["q"]), _cu(ops.as_mask_u8(c["qm"])), _cu(c["lq"]), idx.cuda(),
-                     None if c["W"] is None else _cu(c["W"].reshape(-1)), _cu(c["b"]), _cu(c["WH_b"]), _cu(c["WC_W"].reshape(-1)),
-                     _cu(c["WC_b"]), want_logits=True, want_scale=True)
-    return energy, out
+        energy = album_energy(c, "pooled", rows=pool)
+    return energy, infer(c, "pooled", True, pool=pool, energy=energy)
 
 
 # ------------------------------------------------------------------ 1. the same bits
 def _same_bits_unwarped(c, what):
-    bf, wide = _cu(c["bf"]), _cu(c["wide"])
+    bf, wide = cu(c["bf"]), cu(c["wide"])
     assert bf.dtype == BF16 and wide.dtype == torch.float32
     want = _fwd(c, wide)
     got = _fwd(c, bf)
@@ -106,7 +83,7 @@ def test_loop_cases_give_the_bits_of_the_widened_pool(name):
 @pytest.mark.parametrize("name", PT.NAMES)
 def test_warped_bf16_pool_gives_the_bits_of_the_widened_pool(name):
     c = _case(("tw", name))
-    bf, wide = _cu(c["bf"]), _cu(c["wide"])
+    bf, wide = cu(c["bf"]), cu(c["wide"])
     e_want, want = _fwd_tw(c, wide)
     e_got, got = _fwd_tw(c, bf)
     assert tuple(e_got.shape) == (c["P"], c["JX"]) and torch.equal(e_got, e_want), name
@@ -126,16 +103,14 @@ FP64_CASES = [(k, i) for k, i in zip(R.CASES, R.CASE_IDS) if k[0] == "mix" or k[
 def test_matches_the_fp64_reference_on_the_widened_pool(key):
     name, simi, tanh, masked = key
     c = _case(key)
-    if key not in _REF64:
-        _REF64[key] = R.reference(dict(c, pool=c["wide"]), tanh)
-    ref_ha, ref_a = _REF64[key]
-    ha, a = _fwd(c, _cu(c["bf"]))
+    ref_ha, ref_a = once(("bf16 fp64", key), lambda: R.reference(dict(c, pool=c["wide"]), tanh))
+    ha, a = _fwd(c, cu(c["bf"]))
     live = ref_a > -1e29
     print("%s h_a: max |got - ref| %.3g, max |ref| %.3g; a_logits: max |got - ref| over valid entries %.3g"
           % (name, float((ha.cpu().double() - ref_ha).abs().max()), float(ref_ha.abs().max()),
              float((a.cpu().double() - ref_a)[live].abs().max()) if bool(live.any()) else 0.0))
-    _close(ha, ref_ha, rtol=1e-4, atol=1e-5, msg="h_a")
-    _close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
+    close(ha, ref_ha, rtol=1e-4, atol=1e-5, msg="h_a")
+    close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
 
 
 def test_the_fp64_subset_is_what_it_says():
@@ -210,7 +185,7 @@ def _poison_case(w, JX):
 def test_nothing_outside_the_listed_albums_is_read(w, jx):
     JX = 1 if jx == "1" else R.host_plan(7, w)[1] + 1
     c = _poison_case(w, JX)
-    clean = _cu(c["pool"].to(BF16))
+    clean = cu(c["pool"].to(BF16))
     n, pad = clean.numel(), 4 * w                                             # the pool stays 8-byte aligned in the buffer
     nan = torch.full((n + 2 * pad,), float("nan"), dtype=BF16, device="cuda")
     assert int(nan.view(torch.int16)[0]) == 0x7FC0                            # the bf16 NaN pattern
@@ -234,32 +209,20 @@ def test_nothing_outside_the_listed_albums_is_read(w, jx):
 
 
 # ------------------------------------------------------------------ 6. nn.AlbumPool(dtype=torch.bfloat16)
-def _modules(c):
-    from fvta_memexqa_amd import nn
-    att = nn.FocalAttention3D(c["w"], simiMatrix=c["simi"], add_tanh=c["tanh"])
-    tw = nn.TimeWarp(c["w"], warp_type=c["warp_type"], window_t=c["window_t"])
-    with torch.no_grad():
-        att.p("att_logits/W").copy_(c["W"])
-        att.p("att_logits/b").copy_(c["b"])
-        for name, key in (("WH/W", "WH_W"), ("WH/b", "WH_b"), ("WC/W", "WC_W"), ("WC/b", "WC_b")):
-            tw.p(name).copy_(c[key])
-    return att, tw
-
-
 def test_album_pool_in_bf16_is_the_fp32_pool_of_the_widened_rows():
     from fvta_memexqa_amd import functional as Fn, nn
     c = _case(("tw", "mix-simi2-masked"))
-    att, tw = _modules(c)
-    q, lq, pm, qm = _cu(c["q"]), _cu(c["lq"]), _cu(c["pm"]), _cu(c["qm"])
+    att, tw = modules(c)
+    q, lq, pm, qm = cu(c["q"]), cu(c["lq"]), cu(c["pm"]), cu(c["qm"])
     with torch.no_grad():
-        mem = nn.AlbumPool(_cu(c["pool"]), pm, dtype=BF16)                     # fp32 rows in: rounded once, here
-        ref = nn.AlbumPool(_cu(c["wide"]), pm)
+        mem = nn.AlbumPool(cu(c["pool"]), pm, dtype=BF16)                     # fp32 rows in: rounded once, here
+        ref = nn.AlbumPool(cu(c["wide"]), pm)
         assert mem.pool.dtype == BF16 and ref.pool.dtype == torch.float32 and torch.equal(mem.pool.float(), ref.pool)
         assert mem.nbytes * 2 == ref.nbytes and len(mem) == len(ref) == c["P"]
         _same(mem.attend(att, q, qm, c["albums"]), ref.attend(att, q, qm, c["albums"]), "attend")
         got = mem.attend(att, q, qm, c["albums"], time_warp=tw, lq=lq)
         _same(got, ref.attend(att, q, qm, c["albums"], time_warp=tw, lq=lq), "attend under the warp")
-        _same(got, _fwd_tw(c, _cu(c["bf"]))[1][:2], "attend against the op")
+        _same(got, _fwd_tw(c, cu(c["bf"]))[1][:2], "attend against the op")
         # the energy: computed once, kept, recomputed after an in-place change of WH/W
         e0 = mem.energy(tw)
         assert mem.energy(tw) is e0 and torch.equal(e0, ref.energy(tw)) and tuple(e0.shape) == (c["P"], c["JX"])
@@ -271,7 +234,7 @@ def test_album_pool_in_bf16_is_the_fp32_pool_of_the_widened_rows():
         _same(got2, ref.attend(att, q, qm, c["albums"], time_warp=tw, lq=lq), "attend after the update")
         assert mem.energy(tw) is e1 and not torch.equal(got2[0], got[0])
         # the functional surface on the same tensor
-        ha, a = Fn.attention_3d_pooled_raw(mem.pool, q, c["albums"], _cu(c["W"]), _cu(c["b"]), pm, qm, simiMatrix=c["simi"],
+        ha, a = Fn.attention_3d_pooled_raw(mem.pool, q, c["albums"], cu(c["W"]), cu(c["b"]), pm, qm, simiMatrix=c["simi"],
                                            add_tanh=c["tanh"])
         _same((ha, a), mem.attend(att, q, qm, c["albums"]), "functional")
 
@@ -280,8 +243,8 @@ def test_a_padded_width_stays_bf16_and_exact():
     """w = 100 runs at the kernels' 128: the bf16 pool is zero padded in bf16, which is exact"""
     from fvta_memexqa_amd import functional as Fn
     c = R.make_case(R.lists_from_counts([3, 1, 2], 2, 7, True), 3, 2, 9, 5, 100, 3, True, 71)
-    bf = _cu(c["pool"].to(BF16))
-    args = (_cu(c["q"]), c["albums"], _cu(c["W"]), _cu(c["b"]), _cu(c["pm"]), _cu(c["qm"]))
+    bf = cu(c["pool"].to(BF16))
+    args = (cu(c["q"]), c["albums"], cu(c["W"]), cu(c["b"]), cu(c["pm"]), cu(c["qm"]))
     with torch.no_grad():
         got = Fn.attention_3d_pooled_raw(bf, *args, simiMatrix=3, add_tanh=True)
         want = Fn.attention_3d_pooled_raw(bf.float(), *args, simiMatrix=3, add_tanh=True)
@@ -293,12 +256,12 @@ def test_a_padded_width_stays_bf16_and_exact():
 def test_training_over_a_bf16_leaf_still_widens():
     from fvta_memexqa_amd import functional as Fn
     c = _case(("mix", 2, True, True))
-    leaf = _cu(c["bf"]).requires_grad_()
-    ha, a = Fn.attention_3d_pooled_raw(leaf, _cu(c["q"]), c["albums"], _cu(c["W"]), _cu(c["b"]), _cu(c["pm"]), _cu(c["qm"]),
+    leaf = cu(c["bf"]).requires_grad_()
+    ha, a = Fn.attention_3d_pooled_raw(leaf, cu(c["q"]), c["albums"], cu(c["W"]), cu(c["b"]), cu(c["pm"]), cu(c["qm"]),
                                        simiMatrix=2, add_tanh=True, differentiable=True)
     ha.sum().backward()
     assert leaf.grad is not None and leaf.grad.dtype == BF16 and tuple(leaf.grad.shape) == tuple(leaf.shape)
     assert bool(torch.isfinite(leaf.grad.float()).all()) and float(leaf.grad.float().abs().max()) > 0
     with torch.no_grad():                                                      # the forward it took: the widened rows'
-        _same((ha.detach(),), (Fn.attention_3d_pooled_raw(leaf.detach().float(), _cu(c["q"]), c["albums"], _cu(c["W"]), _cu(c["b"]),
-                                                          _cu(c["pm"]), _cu(c["qm"]), simiMatrix=2, add_tanh=True)[0],), "forward")
+        _same((ha.detach(),), (Fn.attention_3d_pooled_raw(leaf.detach().float(), cu(c["q"]), c["albums"], cu(c["W"]), cu(c["b"]),
+                                                          cu(c["pm"]), cu(c["qm"]), simiMatrix=2, add_tanh=True)[0],), "forward")

@@ -5,89 +5,39 @@ attention_3d), at the tolerances of tests/_attn_shared_tw_ref.TOL: h_a rtol 1e-4
 2e-5, scale rtol 1e-4 / atol 1e-5.  tests/test_attn_pooled_tw_host.py holds every case to these tolerances on the CPU
 (the kernels' factorisation evaluated in fp32), so a failure here is the kernels'.  Every index given to a GPU call is
 valid."""
-import numpy as np
 import pytest
 import torch
 
 from tests import _attn_pooled_ref as R
 from tests import _attn_pooled_tw_ref as PT
+from tests._album_attn_gpu import album_energy, case, check_forward, close, cu, handle, infer, modules, warp_args
 
 pytestmark = pytest.mark.gpu
 
-_REF = {}
 FP32 = dict(rtol=2e-5, atol=2e-5)      # two fp32 routes under the band's scales (|scale| <= 7): tests/test_gpu_attn_shared_tw.py's
-
-
-def _close(a, b, rtol=1e-4, atol=1e-5, msg=""):
-    a = a.detach().cpu().double().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, np.float64)
-    b = b.detach().cpu().double().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float64)
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
-
-
-def _cu(t):
-    return None if t is None else t.cuda().contiguous()
 
 
 def _case(name):
     """the case and its fp64 reference, computed once per session and never written to"""
-    if name not in _REF:
-        c = PT.build_case(name)
-        _REF[name] = (c, PT.reference(c))
-    return _REF[name]
+    return case(PT, name)
 
 
 def _op(c, NQ=None, M=None):
-    from fvta_memexqa_amd import ops
-    return ops.PooledWarpedFocalAttention(c["P"], c["NQ"] if NQ is None else NQ, c["M"] if M is None else M, c["K"], c["JX"],
-                                          c["JQ"], c["w"], c["simi"], c["tanh"], c["warp_type"], c["window_t"])
+    return handle(c, "pooled", True, NQ=NQ, M=M)
 
 
-def _warp_args(c):
-    return _cu(c["WH_b"]), _cu(c["WC_W"].reshape(-1)), _cu(c["WC_b"])
+def _energy(c, op=None):
+    return album_energy(c, "pooled", op)
 
 
-def _energy(c, op=None, pool=None):
-    return (op or _op(c)).album_energy(_cu(c["pool"] if pool is None else pool), _cu(c["WH_W"]), _cu(c["WC_W"].reshape(-1)))
-
-
-def _run(c, rows=None, albums=None, pool=None, pm=None, energy=None, want_logits=True, sentinels=False):
+def _run(c, **kw):
     """ops.PooledWarpedFocalAttention on case c -> (h_a, a_logits, scale); rows: a subset of the questions (an index list);
     albums / pool / pm: in place of the case's own; sentinels: the outputs hold NaN before the call"""
-    from fvta_memexqa_amd import ops
-    q, qm, lq = c["q"], c["qm"], c["lq"]
-    al = c["albums"] if albums is None else albums
-    pool = c["pool"] if pool is None else pool
-    pm = c["pm"] if pm is None else pm
-    if rows is not None:
-        q, al, lq = q[rows], al[rows], lq[rows]
-        qm = None if qm is None else qm[rows]
-    op = _op(c, q.shape[0], al.shape[1])
-    if energy is None:
-        energy = _energy(c, op, pool)
-    idx = ops.check_album_lists(al, c["P"], c["pm"] is not None)
-    args = (_cu(pool), _cu(ops.as_mask_u8(pm)), energy, _cu(q), _cu(ops.as_mask_u8(qm)), _cu(lq), idx.cuda(),
-            None if c["W"] is None else _cu(c["W"].reshape(-1)), _cu(c["b"])) + _warp_args(c)
-    if not sentinels:
-        return op.forward(*args, want_logits=want_logits, want_scale=True)
-    # the C call itself, on outputs that hold NaN: whatever it leaves unwritten stays NaN
-    import ctypes
-    from fvta_memexqa_amd import _lib
-    NQ, T = q.shape[0], al.shape[1] * c["JX"]
-    outs = [torch.full(shape, float("nan"), device="cuda") for shape in ((NQ, c["w"]), (NQ, c["K"], T, c["JQ"]), (NQ, T))]
-    _lib.check(op.lib.fvta_attn_pool_fwd_tw(ctypes.byref(op.desc), *[_lib.ptr(t) for t in args], *[_lib.ptr(t) for t in outs],
-                                            _lib.ptr(op.work), _lib.stream_ptr()), "fvta_attn_pool_fwd_tw")
-    torch.cuda.synchronize()
-    return tuple(outs)
+    return infer(c, "pooled", True, **kw)
 
 
 def _check(name, got, ref):
-    (ha, a, s), (ref_ha, ref_a, ref_s) = got, ref
-    for g, r, what in ((ha, ref_ha, "h_a"), (a, ref_a, "a_logits"), (s, ref_s, "scale")):
-        assert bool(torch.isfinite(g).all()), what                              # no sentinel left, nothing unwritten
-        print("%s %s: worst |err| / (atol + rtol |ref|) = %.3f" % (name, what, PT.within(g.cpu(), r, what)[1]))
-    _close(s, ref_s, rtol=1e-4, atol=1e-5, msg="scale")
-    _close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
-    _close(ha, ref_ha, rtol=1e-4, atol=1e-5, msg="h_a")
+    check_forward(name, got, ref, PT.within)
 
 
 # ------------------------------------------------------------------ against the fp64 definition
@@ -115,12 +65,12 @@ def test_energy_is_the_shared_call_s_bit_for_bit():
         c, _ = _case(name)
         e = _energy(c)
         assert tuple(e.shape) == (c["P"], c["JX"])
-        _close(e, PT.energy(c), rtol=1e-4, atol=1e-5, msg="energy of %s" % name)
+        close(e, PT.energy(c), rtol=1e-4, atol=1e-5, msg="energy of %s" % name)
         shared = ops.SharedWarpedFocalAttention(c["P"], 1, c["K"], c["JX"], 1, c["w"], 1, False, 1)
-        assert torch.equal(e, shared.album_energy(_cu(c["pool"]), _cu(c["WH_W"]), _cu(c["WC_W"].reshape(-1))))
+        assert torch.equal(e, shared.album_energy(cu(c["pool"]), cu(c["WH_W"]), cu(c["WC_W"].reshape(-1))))
         assert torch.equal(e, _energy(c, _op(c, 1, 1)))                         # NQ and M do not enter
         with torch.no_grad():
-            assert torch.equal(e, Fn.album_energy(_cu(c["pool"]), _cu(c["WH_W"]), _cu(c["WC_W"])))      # a 4-D pool
+            assert torch.equal(e, Fn.album_energy(cu(c["pool"]), cu(c["WH_W"]), cu(c["WC_W"])))      # a 4-D pool
 
 
 # ------------------------------------------------------------------ M = 1 is the shared call under the warp
@@ -129,17 +79,17 @@ def test_one_slot_is_the_shared_call_bit_for_bit(simi, masked):
     from tests import _attn_shared_tw_ref as TW
     from fvta_memexqa_amd import ops
     c = TW.build_case("mix-simi%d-%s" % (simi, "masked" if masked else "open"))
-    rows = (_cu(c["h"]), _cu(ops.as_mask_u8(c["hm"])))
-    Wb = (None if c["W"] is None else _cu(c["W"].reshape(-1)), _cu(c["b"]))
-    wargs = (_cu(c["WH_b"]), _cu(c["WC_W"].reshape(-1)), _cu(c["WC_b"]))
+    rows = (cu(c["h"]), cu(ops.as_mask_u8(c["hm"])))
+    Wb = (None if c["W"] is None else cu(c["W"].reshape(-1)), cu(c["b"]))
+    wargs = (cu(c["WH_b"]), cu(c["WC_W"].reshape(-1)), cu(c["WC_b"]))
     shared = ops.SharedWarpedFocalAttention(c["A"], c["NQ"], c["K"], c["T"], c["JQ"], c["w"], simi, c["tanh"], 5, c["window_t"])
-    e = shared.album_energy(rows[0], _cu(c["WH_W"]), wargs[1])
-    ha_s, a_s, s_s = shared.forward(*rows, e, _cu(c["q"]), _cu(ops.as_mask_u8(c["qm"])), _cu(c["lq"]),
+    e = shared.album_energy(rows[0], cu(c["WH_W"]), wargs[1])
+    ha_s, a_s, s_s = shared.forward(*rows, e, cu(c["q"]), cu(ops.as_mask_u8(c["qm"])), cu(c["lq"]),
                                     ops.check_album_index(c["album"], c["A"]).cuda(), *Wb, *wargs, want_logits=True, want_scale=True)
     pooled = ops.PooledWarpedFocalAttention(c["A"], c["NQ"], 1, c["K"], c["T"], c["JQ"], c["w"], simi, c["tanh"], 5, c["window_t"])
     assert pooled.plan() == shared_plan(c, simi)
-    e_p = pooled.album_energy(rows[0], _cu(c["WH_W"]), wargs[1])
-    ha_p, a_p, s_p = pooled.forward(*rows, e_p, _cu(c["q"]), _cu(ops.as_mask_u8(c["qm"])), _cu(c["lq"]),
+    e_p = pooled.album_energy(rows[0], cu(c["WH_W"]), wargs[1])
+    ha_p, a_p, s_p = pooled.forward(*rows, e_p, cu(c["q"]), cu(ops.as_mask_u8(c["qm"])), cu(c["lq"]),
                                     ops.check_album_lists(c["album"][:, None], c["A"], masked).cuda(), *Wb, *wargs,
                                     want_logits=True, want_scale=True)
     assert torch.equal(e_p, e) and torch.equal(s_p, s_s) and torch.equal(a_p, a_s) and torch.equal(ha_p, ha_s)
@@ -160,13 +110,13 @@ def test_logits_and_scale_are_the_expanded_shared_call_s_bits(name):
     h, m = R.expand(c)
     NQ, T = c["NQ"], c["T"]
     shared = ops.SharedWarpedFocalAttention(NQ, NQ, c["K"], T, c["JQ"], c["w"], c["simi"], c["tanh"], c["warp_type"], c["window_t"])
-    e = shared.album_energy(_cu(h), _cu(c["WH_W"]), _cu(c["WC_W"].reshape(-1)))
-    ha_s, a_s, s_s = shared.forward(_cu(h), _cu(ops.as_mask_u8(m)), e, _cu(c["q"]), _cu(ops.as_mask_u8(c["qm"])), _cu(c["lq"]),
-                                    torch.arange(NQ, dtype=torch.int32).cuda(), None if c["W"] is None else _cu(c["W"].reshape(-1)),
-                                    _cu(c["b"]), *_warp_args(c), want_logits=True, want_scale=True)
+    e = shared.album_energy(cu(h), cu(c["WH_W"]), cu(c["WC_W"].reshape(-1)))
+    ha_s, a_s, s_s = shared.forward(cu(h), cu(ops.as_mask_u8(m)), e, cu(c["q"]), cu(ops.as_mask_u8(c["qm"])), cu(c["lq"]),
+                                    torch.arange(NQ, dtype=torch.int32).cuda(), None if c["W"] is None else cu(c["W"].reshape(-1)),
+                                    cu(c["b"]), *warp_args(c), want_logits=True, want_scale=True)
     ha, a, s = _run(c)
     assert torch.equal(s, s_s) and torch.equal(a, a_s)
-    _close(ha, ha_s, msg="h_a against the shared call on the expanded contexts", **FP32)
+    close(ha, ha_s, msg="h_a against the shared call on the expanded contexts", **FP32)
 
 
 # ------------------------------------------------------------------ the per-question route
@@ -176,17 +126,17 @@ def test_same_result_as_the_per_question_route(name):
     from fvta_memexqa_amd import ops
     c, _ = _case(name)
     h, m = R.expand(c)                                                          # [NQ,K,T,w]: what the pooled call never builds
-    rows = _cu(h)
+    rows = cu(h)
     tw = ops.TimeWarp(c["NQ"], c["K"], c["T"], c["w"], c["warp_type"], c["window_t"])
     warped = torch.empty_like(rows)
-    tw.forward(rows, _cu(c["lq"]), _cu(c["WH_W"]), *_warp_args(c), warped)
+    tw.forward(rows, cu(c["lq"]), cu(c["WH_W"]), *warp_args(c), warped)
     per_q = ops.FocalAttention(c["NQ"], c["K"], c["T"], c["JQ"], c["w"], c["simi"], c["tanh"])
-    ref_ha, ref_a = per_q.forward(warped, _cu(c["q"]), _cu(ops.as_mask_u8(m)), _cu(ops.as_mask_u8(c["qm"])),
-                                  _cu(c["W"].reshape(-1)), _cu(c["b"]), want_logits=True)
+    ref_ha, ref_a = per_q.forward(warped, cu(c["q"]), cu(ops.as_mask_u8(m)), cu(ops.as_mask_u8(c["qm"])),
+                                  cu(c["W"].reshape(-1)), cu(c["b"]), want_logits=True)
     ha, a, s = _run(c)
-    _close(s, tw.scale, rtol=2e-4, atol=2e-5, msg="scale")
-    _close(a, ref_a, rtol=2e-4, atol=4e-5, msg="a_logits")
-    _close(ha, ref_ha, rtol=2e-4, atol=2e-5, msg="h_a")
+    close(s, tw.scale, rtol=2e-4, atol=2e-5, msg="scale")
+    close(a, ref_a, rtol=2e-4, atol=4e-5, msg="a_logits")
+    close(ha, ref_ha, rtol=2e-4, atol=2e-5, msg="h_a")
 
 
 # ------------------------------------------------------------------ placement changes no bit
@@ -227,38 +177,26 @@ def test_the_count_runs_over_the_whole_list():
         cnt = PT.TW._count(c["T"], c["warp_type"], c["window_t"], torch.float64)
         JX = c["JX"]
         moved = torch.cat([(s / cnt)[:, m * JX:(m + 1) * JX] for m in order], 1) * cnt
-        _close(sp, moved, rtol=1e-5, atol=1e-6, msg="scale after permuting the slots")
-        _close(sp, PT.scale_of(cp), rtol=1e-4, atol=1e-5)
+        close(sp, moved, rtol=1e-5, atol=1e-6, msg="scale after permuting the slots")
+        close(sp, PT.scale_of(cp), rtol=1e-4, atol=1e-5)
 
 
 # ------------------------------------------------------------------ the Python surface
-def _modules(c):
-    from fvta_memexqa_amd import nn
-    att = nn.FocalAttention3D(c["w"], simiMatrix=c["simi"], add_tanh=c["tanh"])
-    tw = nn.TimeWarp(c["w"], warp_type=c["warp_type"], window_t=c["window_t"])
-    with torch.no_grad():
-        att.p("att_logits/W").copy_(c["W"])
-        att.p("att_logits/b").copy_(c["b"])
-        for name, key in (("WH/W", "WH_W"), ("WH/b", "WH_b"), ("WC/W", "WC_W"), ("WC/b", "WC_b")):
-            tw.p(name).copy_(c[key])
-    return att, tw
-
-
 def test_functional_nn_and_album_pool_give_the_ops_result():
     from fvta_memexqa_amd import functional as Fn, nn
     c, ref = _case("mix-simi2-masked")
     ha_ops, a_ops, s_ops = _run(c)
-    pool, q, lq, pm, qm = _cu(c["pool"]), _cu(c["q"]), _cu(c["lq"]), _cu(c["pm"]), _cu(c["qm"])
-    wargs = (_cu(c["WH_W"]), _cu(c["WH_b"]), _cu(c["WC_W"]), _cu(c["WC_b"]))
+    pool, q, lq, pm, qm = cu(c["pool"]), cu(c["q"]), cu(c["lq"]), cu(c["pm"]), cu(c["qm"])
+    wargs = (cu(c["WH_W"]), cu(c["WH_b"]), cu(c["WC_W"]), cu(c["WC_b"]))
     kw = dict(pool_mask=pm, hq_mask=qm, simiMatrix=c["simi"], add_tanh=c["tanh"], warp_type=c["warp_type"], window_t=c["window_t"])
     with torch.no_grad():
-        ha, a, s = Fn.attention_3d_pooled_warped_raw(pool, q, c["albums"], lq, _cu(c["W"]), _cu(c["b"]), *wargs, **kw)
+        ha, a, s = Fn.attention_3d_pooled_warped_raw(pool, q, c["albums"], lq, cu(c["W"]), cu(c["b"]), *wargs, **kw)
         e = Fn.album_energy(pool, wargs[0], wargs[2])
-        ha2, a2, s2 = Fn.attention_3d_pooled_warped_raw(pool, q, c["albums"].tolist(), lq, _cu(c["W"]), _cu(c["b"]), *wargs,
+        ha2, a2, s2 = Fn.attention_3d_pooled_warped_raw(pool, q, c["albums"].tolist(), lq, cu(c["W"]), cu(c["b"]), *wargs,
                                                         energy=e, **kw)
     for got in ((ha, a, s), (ha2, a2, s2)):
         assert torch.equal(got[0], ha_ops) and torch.equal(got[1], a_ops) and torch.equal(got[2], s_ops)
-    att, tw = _modules(c)
+    att, tw = modules(c)
     with torch.no_grad():
         ha_n, a_n = att.forward_pooled(pool, q, c["albums"], pm, qm, time_warp=tw, lq=lq)
         mem = nn.AlbumPool(pool, pm)
@@ -269,7 +207,7 @@ def test_functional_nn_and_album_pool_give_the_ops_result():
     assert torch.equal(ha_n, ha_ops) and torch.equal(a_n, a_ops)
     assert torch.equal(ha_m, ha_ops) and torch.equal(a_m, a_ops) and torch.equal(ha_m2, ha_ops)
     assert torch.equal(ha_plain, ha_unwarped) and not torch.equal(ha_plain, ha_ops)
-    _close(ha_m, ref[0], msg="AlbumPool.attend against the fp64 definition")
+    close(ha_m, ref[0], msg="AlbumPool.attend against the fp64 definition")
 
 
 def test_a_padded_width_goes_through():
@@ -279,9 +217,9 @@ def test_a_padded_width_goes_through():
     c = PT.TW.add_warp(dict(c, tanh=True), 77, 5)
     ref = PT.reference(c)
     with torch.no_grad():
-        got = Fn.attention_3d_pooled_warped_raw(_cu(c["pool"]), _cu(c["q"]), c["albums"], _cu(c["lq"]), _cu(c["W"]), _cu(c["b"]),
-                                                _cu(c["WH_W"]), _cu(c["WH_b"]), _cu(c["WC_W"]), _cu(c["WC_b"]), _cu(c["pm"]),
-                                                _cu(c["qm"]), simiMatrix=2, add_tanh=True, warp_type=5, window_t=c["window_t"])
+        got = Fn.attention_3d_pooled_warped_raw(cu(c["pool"]), cu(c["q"]), c["albums"], cu(c["lq"]), cu(c["W"]), cu(c["b"]),
+                                                cu(c["WH_W"]), cu(c["WH_b"]), cu(c["WC_W"]), cu(c["WC_b"]), cu(c["pm"]),
+                                                cu(c["qm"]), simiMatrix=2, add_tanh=True, warp_type=5, window_t=c["window_t"])
     assert tuple(got[0].shape) == (c["NQ"], 40) and tuple(got[2].shape) == (c["NQ"], c["T"])
     _check("w40", got, ref)
 
@@ -289,8 +227,8 @@ def test_a_padded_width_goes_through():
 def test_album_pool_never_serves_a_stale_energy():
     from fvta_memexqa_amd import nn
     c, _ = _case("mix-simi2-masked")
-    att, tw = _modules(c)
-    pool, q, lq, pm, qm = _cu(c["pool"]), _cu(c["q"]), _cu(c["lq"]), _cu(c["pm"]), _cu(c["qm"])
+    att, tw = modules(c)
+    pool, q, lq, pm, qm = cu(c["pool"]), cu(c["q"]), cu(c["lq"]), cu(c["pm"]), cu(c["qm"])
     mem = nn.AlbumPool(pool, pm)
     with torch.no_grad():
         ha0, _ = mem.attend(att, q, qm, c["albums"], time_warp=tw, lq=lq)
@@ -300,14 +238,14 @@ def test_album_pool_never_serves_a_stale_energy():
         ha1, _ = mem.attend(att, q, qm, c["albums"], time_warp=tw, lq=lq)
         assert mem.energy(tw) is not e0                                        # ... is seen by the next attend
         c15 = dict(c, WC_W=c["WC_W"] * 1.5)
-        _close(ha1, PT.reference(c15)[0], msg="after the in-place update")
+        close(ha1, PT.reference(c15)[0], msg="after the in-place update")
         assert not torch.equal(ha1, ha0)
         sd = {k: v.clone() for k, v in tw.state_dict().items()}
         sd["WH/W"] = sd["WH/W"] * 0.5
         tw.load_state_dict(sd)                                                 # load_state_dict writes in place as well
         ha2, _ = mem.attend(att, q, qm, c["albums"], time_warp=tw, lq=lq)
-        _close(ha2, PT.reference(dict(c15, WH_W=c["WH_W"] * 0.5))[0], msg="after load_state_dict")
-        _, tw_b = _modules(c)                                                  # another module, the first weights again
+        close(ha2, PT.reference(dict(c15, WH_W=c["WH_W"] * 0.5))[0], msg="after load_state_dict")
+        _, tw_b = modules(c)                                                  # another module, the first weights again
         ha3, _ = mem.attend(att, q, qm, c["albums"], time_warp=tw_b, lq=lq)
         assert torch.equal(ha3, ha0)
 
@@ -315,13 +253,13 @@ def test_album_pool_never_serves_a_stale_energy():
 def test_refusals():
     from fvta_memexqa_amd import _lib, functional as Fn, ops
     c, _ = _case("mix-simi2-masked")
-    att, tw = _modules(c)
-    pool, q, lq, pm, qm = _cu(c["pool"]), _cu(c["q"]), _cu(c["lq"]), _cu(c["pm"]), _cu(c["qm"])
+    att, tw = modules(c)
+    pool, q, lq, pm, qm = cu(c["pool"]), cu(c["q"]), cu(c["lq"]), cu(c["pm"]), cu(c["qm"])
     with pytest.raises(RuntimeError, match="forward-only.*per-question time_warp"):  # gradient mode on, the parameters require grad
         att.forward_pooled(pool, q, c["albums"], pm, qm, time_warp=tw, lq=lq)
     with pytest.raises(RuntimeError, match="forward-only"):
-        Fn.attention_3d_pooled_warped_raw(pool, q.clone().requires_grad_(), c["albums"], lq, _cu(c["W"]), _cu(c["b"]),
-                                          _cu(c["WH_W"]), _cu(c["WH_b"]), _cu(c["WC_W"]), _cu(c["WC_b"]), pm, qm, simiMatrix=2,
+        Fn.attention_3d_pooled_warped_raw(pool, q.clone().requires_grad_(), c["albums"], lq, cu(c["W"]), cu(c["b"]),
+                                          cu(c["WH_W"]), cu(c["WH_b"]), cu(c["WC_W"]), cu(c["WC_b"]), pm, qm, simiMatrix=2,
                                           warp_type=5)
     with pytest.raises(_lib.FvtaError, match="time warping type not implemented"):
         ops.PooledWarpedFocalAttention(2, 3, 2, 2, 9, 5, 64, 2, True, 9)
@@ -352,5 +290,5 @@ def test_from_context_agrees_with_the_per_question_time_warp_and_forward(attn_se
     print("from_context under the warp against TimeWarp + forward(): max |h_a diff| %.3g, max |a_logits diff| %.3g"
           % (float((ha_p - ha_f).abs().max()), float((a_p - a_f).abs().max())))
     # each route's own bound against fp64, added (tests/test_gpu_attn_shared_tw.py's end-to-end test)
-    _close(ha_p, ha_f, rtol=2e-4, atol=2e-5, msg="h_a: the pool cut from the context against TimeWarp + forward()")
-    _close(a_p, a_f, rtol=2e-4, atol=4e-5, msg="a_logits")
+    close(ha_p, ha_f, rtol=2e-4, atol=2e-5, msg="h_a: the pool cut from the context against TimeWarp + forward()")
+    close(a_p, a_f, rtol=2e-4, atol=4e-5, msg="a_logits")

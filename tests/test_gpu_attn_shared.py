@@ -11,66 +11,42 @@ sqrt(64 / w), partly valid masks), each case asserting its regime through the pl
 A = 1500 / NQ = 1284 (two albums per plan thread, 21 ordered batches, strided loops, ngmax clamped), `heavy` [150, 0, 50]
 questions (19 groups of one album), `chunks` [2] x 120 at T = 200 (67 rows per split of the weighted sum: 64 + 3), and the
 backward's `tiles-w64` / `-w512` / `-w2048` (T = 260 / 220 / 360), `k17`, `k64`."""
-import numpy as np
 import pytest
 import torch
 
 from tests import _attn_shared_ref as R
+from tests._album_attn_gpu import TrainRun, case, close, cu, infer
 
 pytestmark = pytest.mark.gpu
-
-_REF = {}
-
-
-def _close(a, b, rtol=1e-4, atol=1e-5, msg=""):
-    a = a.detach().cpu().double().numpy() if isinstance(a, torch.Tensor) else np.asarray(a, np.float64)
-    b = b.detach().cpu().double().numpy() if isinstance(b, torch.Tensor) else np.asarray(b, np.float64)
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
-
-
-def _cu(t):
-    return None if t is None else t.cuda().contiguous()
 
 
 def _case(name, simi, tanh, masked):
     """the case and its fp64 reference, computed once per session and never written to"""
-    key = (name, simi, tanh, masked)
-    if key not in _REF:
-        c = R.build_case(name, simi, masked)
-        _REF[key] = (c, R.reference(c, tanh))
-    return _REF[key]
+    return case(R, (name, simi, tanh, masked), lambda key: R.build_case(name, simi, masked), lambda c: R.reference(c, tanh))
 
 
-def _run(c, tanh, want_logits=True, rows=None):
+def _run(c, tanh, **kw):
     """ops.SharedFocalAttention on case c; rows: a subset of the questions (an index list), else all of them"""
-    from fvta_memexqa_amd import ops
-    q, qm, al = c["q"], c["qm"], c["album"]
-    if rows is not None:
-        q, al = q[rows], al[rows]
-        qm = None if qm is None else qm[rows]
-    op = ops.SharedFocalAttention(c["A"], q.shape[0], c["K"], c["T"], c["JQ"], c["w"], c["simi"], tanh)
-    idx = ops.check_album_index(al, c["A"])
-    return op.forward(_cu(c["h"]), _cu(ops.as_mask_u8(c["hm"])), _cu(q), _cu(ops.as_mask_u8(qm)), idx.cuda(),
-                      None if c["W"] is None else _cu(c["W"].reshape(-1)), _cu(c["b"]), want_logits=want_logits)
+    return infer(c, "shared", tanh=tanh, **kw)
 
 
 def _expanded(c, tanh, want_logits=False):
     """today's route: index_select of the rows to [NQ,...], then the per-question kernel"""
     from fvta_memexqa_amd import ops
     al = c["album"].cuda()
-    h = _cu(c["h"]).index_select(0, al)
-    hm = None if c["hm"] is None else _cu(ops.as_mask_u8(c["hm"])).index_select(0, al)
+    h = cu(c["h"]).index_select(0, al)
+    hm = None if c["hm"] is None else cu(ops.as_mask_u8(c["hm"])).index_select(0, al)
     op = ops.FocalAttention(c["NQ"], c["K"], c["T"], c["JQ"], c["w"], c["simi"], tanh)
-    return op.forward(h, _cu(c["q"]), hm, _cu(ops.as_mask_u8(c["qm"])), None if c["W"] is None else _cu(c["W"].reshape(-1)),
-                      _cu(c["b"]), want_logits=want_logits)
+    return op.forward(h, cu(c["q"]), hm, cu(ops.as_mask_u8(c["qm"])), None if c["W"] is None else cu(c["W"].reshape(-1)),
+                      cu(c["b"]), want_logits=want_logits)
 
 
 @pytest.mark.parametrize("name,simi,tanh,masked", R.CASES, ids=R.CASE_IDS)
 def test_matches_the_fp64_reference(name, simi, tanh, masked):
     c, (ref_ha, ref_a) = _case(name, simi, tanh, masked)
     ha, a = _run(c, tanh)
-    _close(ha, ref_ha, msg="h_a")
-    _close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
+    close(ha, ref_ha, msg="h_a")
+    close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
 
 
 def test_plan_is_what_the_shapes_assume():
@@ -90,7 +66,7 @@ def test_same_result_as_the_per_question_kernel(name, simi, tanh, masked, attn_s
     attn_select.exact()
     ref_ha, _ = _expanded(c, tanh)
     ha, _ = _run(c, tanh, want_logits=False)
-    _close(ha, ref_ha, rtol=2e-5, atol=2e-6, msg="h_a against the per-question exact kernel")
+    close(ha, ref_ha, rtol=2e-5, atol=2e-6, msg="h_a against the per-question exact kernel")
 
 
 def test_a_question_does_not_depend_on_its_company():
@@ -104,8 +80,8 @@ def test_a_question_does_not_depend_on_its_company():
     assert torch.equal(ha_all, again_ha) and torch.equal(a_all, again_a)       # the same call twice: the same bits
     i = int(members[G])
     ha_one, a_one = _run(c, True, rows=[i])
-    _close(ha_one[0], ha_all[i], rtol=2e-5, atol=2e-6, msg="alone against in company")
-    _close(a_one[0], a_all[i], rtol=2e-5, atol=2e-6)
+    close(ha_one[0], ha_all[i], rtol=2e-5, atol=2e-6, msg="alone against in company")
+    close(a_one[0], a_all[i], rtol=2e-5, atol=2e-6)
     ha_nol, none = _run(c, True, want_logits=False)
     assert none is None and torch.equal(ha_nol, ha_all)                        # want_logits changes no bit of h_a
 
@@ -114,36 +90,24 @@ def test_a_question_does_not_depend_on_its_company():
 def _loop_case(name):
     """a LOOP_SPECS case (the training recipe and, where the backward runs it too, its pinned seed) and its fp64 reference,
     evaluated in blocks of questions; once per session, never written to"""
-    if name not in _REF:
-        from tests import _attn_shared_bwd_ref as B
-        c = R.loop_case(name, R.CHUNKS_SEED) if name in R.FORWARD_ONLY else B.build_case(name)
-        _REF[name] = (c, R.reference(c, c["tanh"], block=100))
-    return _REF[name]
-
-
-def _loop_op(c):
-    """a fresh handle on case c and its device arguments; the regime the case is named for is asserted here, through the
-    plans' words, before anything is launched"""
-    from fvta_memexqa_amd import ops
-    op = ops.SharedFocalAttention(c["A"], c["NQ"], c["K"], c["T"], c["JQ"], c["w"], c["simi"], c["tanh"])
-    args = (_cu(c["h"]), _cu(ops.as_mask_u8(c["hm"])), _cu(c["q"]), _cu(ops.as_mask_u8(c["qm"])),
-            ops.check_album_index(c["album"], c["A"]).cuda(), _cu(c["W"].reshape(-1)), _cu(c["b"]))
-    return op, args
+    from tests import _attn_shared_bwd_ref as B
+    return case(R, name, lambda n: R.loop_case(n, R.CHUNKS_SEED) if n in R.FORWARD_ONLY else B.build_case(n),
+                lambda c: R.reference(c, c["tanh"], block=100))
 
 
 @pytest.mark.parametrize("name", R.LOOP_IDS)
 def test_loop_cases_match_the_fp64_reference(name):
     c, (ref_ha, ref_a) = _loop_case(name)
-    op, args = _loop_op(c)
-    R.loop_regime(name, c, op.plan(), None if name in R.FORWARD_ONLY else op.bwd_plan())
-    ha, a = op.forward(*args, want_logits=True)
+    run = TrainRun(c, "shared")                                  # the regime the case is named for: asserted before any launch
+    R.loop_regime(name, c, run.op.plan(), None if name in R.FORWARD_ONLY else run.op.bwd_plan())
+    ha, a = run.forward()
     live = ref_a > -1e29
     print("%s h_a: max |got - ref| %.3g, max |ref| %.3g" % (name, float((ha.cpu().double() - ref_ha).abs().max()),
                                                             float(ref_ha.abs().max())))
     print("%s a_logits: max |got - ref| over valid entries %.3g" % (name, float((a.cpu().double() - ref_a)[live].abs().max())))
-    _close(ha, ref_ha, msg="h_a")
-    _close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
-    ha_t, a_t = op.forward_train(*args, want_logits=True)        # the ordered plan: other places, the same bits
+    close(ha, ref_ha, msg="h_a")
+    close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
+    ha_t, a_t = run.forward_train()                              # the ordered plan: other places, the same bits
     assert torch.equal(ha_t, ha) and torch.equal(a_t, a)
 
 
@@ -154,8 +118,7 @@ def test_loop_cases_three_forward_calls_are_bitwise_equal(name):
     c, _ = _loop_case(name)
     outs = []
     for _ in range(3):
-        op, args = _loop_op(c)                                   # a fresh handle: workspace and plan anew
-        outs.append(op.forward(*args, want_logits=True))
+        outs.append(TrainRun(c, "shared").forward())             # a fresh handle: workspace and plan anew
     for ha, a in outs[1:]:
         assert torch.equal(ha, outs[0][0]) and torch.equal(a, outs[0][1])
 
@@ -171,16 +134,16 @@ def test_many_a_question_does_not_depend_on_its_company():
         assert members.numel() == size
         i = int(members[size // 2])
         ha_one, a_one = _run(c, c["tanh"], rows=[i])
-        _close(ha_one[0], ha_all[i], rtol=2e-5, atol=2e-6, msg="alone against in company, album of %d" % size)
-        _close(a_one[0], a_all[i], rtol=2e-5, atol=2e-6)
+        close(ha_one[0], ha_all[i], rtol=2e-5, atol=2e-6, msg="alone against in company, album of %d" % size)
+        close(a_one[0], a_all[i], rtol=2e-5, atol=2e-6)
 
 
 def test_functional_and_nn_surface():
     from fvta_memexqa_amd import functional as Fn, nn
     c, (ref_ha, ref_a) = _case("rows4", 1, False, True)                       # w = 256, simiMatrix 1, no tanh
     ha_ops, a_ops = _run(c, False)
-    h, q, W, b = _cu(c["h"]), _cu(c["q"]), _cu(c["W"]), _cu(c["b"])
-    hm, qm = _cu(c["hm"]), _cu(c["qm"])
+    h, q, W, b = cu(c["h"]), cu(c["q"]), cu(c["W"]), cu(c["b"])
+    hm, qm = cu(c["hm"]), cu(c["qm"])
     with torch.no_grad():
         ha, a = Fn.attention_3d_shared_raw(h, q, c["album"], W, b, hm, qm, simiMatrix=1, add_tanh=False)
     assert torch.equal(ha, ha_ops) and torch.equal(a, a_ops)
@@ -199,9 +162,9 @@ def test_functional_and_nn_surface():
         al = c["album"].cuda()
         ha_f, a_f = att.forward(h.index_select(0, al), q, hm.index_select(0, al), qm)
         ha_s, a_s = att.forward_shared(h, q, c["album"], hm, qm)
-    _close(ha_s, ha_f, msg="forward_shared against forward")
-    _close(a_s, a_f, rtol=1e-4, atol=2e-5)
-    _close(ha_s, ref_ha)
+    close(ha_s, ha_f, msg="forward_shared against forward")
+    close(a_s, a_f, rtol=1e-4, atol=2e-5)
+    close(ha_s, ref_ha)
     with pytest.raises(RuntimeError):                                          # the parameters require grad
         att.forward_shared(h, q, c["album"], hm, qm)
 
@@ -209,7 +172,7 @@ def test_functional_and_nn_surface():
 def test_album_memory_validates_before_any_library_call(monkeypatch):
     from fvta_memexqa_amd import nn, ops
     c, _ = _case("single", 1, False, True)
-    mem = nn.AlbumMemory(_cu(c["h"]), _cu(c["hm"]))
+    mem = nn.AlbumMemory(cu(c["h"]), cu(c["hm"]))
     assert len(mem) == c["A"] and mem.hall.is_contiguous() and mem.hall.dtype == torch.float32
     assert not isinstance(mem, torch.nn.Module)                                # no parameters, no encoder
     att = nn.FocalAttention3D(c["w"], simiMatrix=1)
@@ -221,9 +184,9 @@ def test_album_memory_validates_before_any_library_call(monkeypatch):
     with torch.no_grad():
         for bad in (torch.tensor([c["A"]]), torch.tensor([-1]), torch.tensor([0.0]), torch.tensor([[0]])):
             with pytest.raises(ValueError):
-                mem.attend(att, _cu(c["q"]), _cu(c["qm"]), bad)
+                mem.attend(att, cu(c["q"]), cu(c["qm"]), bad)
         with pytest.raises(ValueError):
-            mem.attend(att, _cu(c["q"]), _cu(c["qm"]), torch.tensor([0, 0]))   # two indices for one question
+            mem.attend(att, cu(c["q"]), cu(c["qm"]), torch.tensor([0, 0]))   # two indices for one question
 
 
 def test_end_to_end_many_questions_over_encoded_albums():
@@ -267,8 +230,8 @@ def test_end_to_end_many_questions_over_encoded_albums():
         g1_each, _ = att(hall.index_select(0, al), hq, hall_mask.index_select(0, al), qmask)
         logits_s, yp_s = head(g1_shared)
         logits_e, yp_e = head(g1_each)
-    _close(logits_s, logits_e, msg="shared against per-question")
-    _close(logits_s, ref_logits, msg="shared against the fp64 oracle")
+    close(logits_s, logits_e, msg="shared against per-question")
+    close(logits_s, ref_logits, msg="shared against the fp64 oracle")
     clear = margin > c["margin"]
     assert torch.equal(yp_s.argmax(-1).cpu()[clear], ref_yp.argmax(-1)[clear])
     assert torch.equal(yp_s.argmax(-1), yp_e.argmax(-1))

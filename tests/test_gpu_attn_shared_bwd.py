@@ -10,72 +10,25 @@ each asserting its regime through the two plans' words): `many` A = 1500 / NQ = 
 `tiles-w64` / `-w512` / `-w2048` with two row tiles per workgroup (T = 260 / 220 / 360), `k17`, `k64`, `splits9` (nine T
 splits of the question pass: the fold's eight-in-flight slot sum and its remainder).  The pinned seeds keep every arg-max clear in fp64 (tests/test_attn_shared_bwd_host.py); the
 first test also holds the GPU's own logits to a quarter of the case's smallest gap."""
-import numpy as np
 import pytest
 import torch
 
 from tests import _attn_shared_bwd_ref as B
 from tests import _attn_shared_ref as R
+from tests._album_attn_gpu import TrainRun, case, close_scaled, cu
 
 pytestmark = pytest.mark.gpu
-
-_REF = {}
-
-
-def _close(a, b, rtol=1e-4, atol=1e-5, msg=""):
-    a = a.detach().cpu().double().numpy()
-    b = b.detach().cpu().double().numpy()
-    scale = max(1.0, float(np.abs(b).max()))
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol * scale, err_msg=msg)
-
-
-def _cu(t):
-    return None if t is None else t.cuda().contiguous()
 
 
 def _case(name):
     """the case and its fp64 reference, computed once per session and never written to"""
-    if name not in _REF:
-        c = B.build_case(name)
-        _REF[name] = (c, B.reference(c))
-    return _REF[name]
-
-
-class _Run:
-    """ops.SharedFocalAttention on case c (rows: a subset of the questions), its device tensors kept for backward()"""
-
-    def __init__(self, c, rows=None):
-        from fvta_memexqa_amd import ops
-        q, qm, al, g = c["q"], c["qm"], c["album"], c["gout"]
-        if rows is not None:
-            q, al, g = q[rows], al[rows], g[rows]
-            qm = None if qm is None else qm[rows]
-        self.c, self.NQ = c, q.shape[0]
-        self.op = ops.SharedFocalAttention(c["A"], self.NQ, c["K"], c["T"], c["JQ"], c["w"], c["simi"], c["tanh"])
-        self.args = (_cu(c["h"]), _cu(ops.as_mask_u8(c["hm"])), _cu(q), _cu(ops.as_mask_u8(qm)),
-                     ops.check_album_index(al, c["A"]).cuda(), _cu(c["W"].reshape(-1)), _cu(c["b"]))
-        self.g = _cu(g)
-
-    def forward_train(self, want_logits=True):
-        return self.op.forward_train(*self.args, want_logits=want_logits)
-
-    def forward(self, want_logits=True):
-        return self.op.forward(*self.args, want_logits=want_logits)
-
-    def backward(self, dW=None, db=None, fill=7.0):
-        c = self.c
-        dh = torch.full((c["A"], c["K"], c["T"], c["w"]), fill, device="cuda")
-        dq = torch.full((self.NQ, c["JQ"], c["w"]), fill, device="cuda")
-        dW = torch.zeros_like(self.args[5]) if dW is None else dW
-        db = torch.zeros(1, device="cuda") if db is None else db
-        self.op.backward(*self.args, self.g, dh, dq, dW, db)
-        return dh, dq, dW, db
+    return case(B, name)
 
 
 @pytest.mark.parametrize("name", B.CASE_IDS)
 def test_gradients_match_fp64_autograd(name):
     c, ref = _case(name)
-    run = _Run(c)
+    run = TrainRun(c, "shared")
     R.loop_regime(name, c, run.op.plan(), run.op.bwd_plan())    # a LOOP_SPECS case reaches its loop, before any launch
     ha, a = run.forward_train()
     # the arg-max the backward routes through is the reference's: the GPU's logits are within a quarter of the smallest gap
@@ -84,23 +37,23 @@ def test_gradients_match_fp64_autograd(name):
     err = float((a.cpu().double() - ref["a_logits"])[v].abs().max())
     print("%s: max |a_logits - fp64| over valid entries %.3g, smallest gap %.3g" % (name, err, min(jgap, tgap)))
     assert err < min(jgap, tgap) / 4, (err, jgap, tgap)
-    _close(ha, ref["h_a"], msg="h_a")
+    close_scaled(ha, ref["h_a"], msg="h_a")
     dh, dq, dW, db = run.backward()                              # d_hinfo / d_hq prefilled with 7.0: overwritten
     for got, key in ((dh, "dh"), (dq, "dq"), (dW, "dW"), (db, "db")):
         print("%s %s: max |got - ref| %.3g, max |ref| %.3g" % (name, key, float((got.cpu().double() - ref[key]).abs().max()),
                                                                float(ref[key].abs().max())))
-    _close(dh, ref["dh"], msg="d_hinfo")
-    _close(dq, ref["dq"], msg="d_hq")
-    _close(dW, ref["dW"], msg="dW")
-    _close(db, ref["db"], msg="db")
+    close_scaled(dh, ref["dh"], msg="d_hinfo")
+    close_scaled(dq, ref["dq"], msg="d_hq")
+    close_scaled(dW, ref["dW"], msg="dW")
+    close_scaled(db, ref["db"], msg="db")
     empty = torch.bincount(c["album"], minlength=c["A"]) == 0
     if bool(empty.any()):                                        # albums without a question: exactly zero, not the 7.0
         assert float(dh.cpu()[empty].abs().max()) == 0.0
-    dh2, dq2, dW2, db2 = run.backward(dW=dW, db=db, fill=-3.0)   # a second call: dW / db accumulate, the others do not
-    _close(dW2, 2 * ref["dW"], atol=2e-5, msg="dW accumulates")
-    _close(db2, 2 * ref["db"], atol=2e-5, msg="db accumulates")
-    _close(dh2, ref["dh"], msg="d_hinfo overwritten")
-    _close(dq2, ref["dq"], msg="d_hq overwritten")
+    dh2, dq2, dW2, db2 = run.backward(acc=(dW, db), fill=-3.0)   # a second call: dW / db accumulate, the others do not
+    close_scaled(dW2, 2 * ref["dW"], atol=2e-5, msg="dW accumulates")
+    close_scaled(db2, 2 * ref["db"], atol=2e-5, msg="db accumulates")
+    close_scaled(dh2, ref["dh"], msg="d_hinfo overwritten")
+    close_scaled(dq2, ref["dq"], msg="d_hq overwritten")
 
 
 def test_same_result_as_the_per_question_route(attn_select):
@@ -112,7 +65,7 @@ def test_same_result_as_the_per_question_route(attn_select):
     that album's masked rows hold exactly that term and are compared like all others."""
     from fvta_memexqa_amd import ops
     c = B.build_case(B.MIX_MASKED, parity=False)
-    run = _Run(c)
+    run = TrainRun(c, "shared")
     run.forward_train(want_logits=False)
     dh, dq, dW, db = run.backward()
     attn_select.exact()
@@ -125,10 +78,10 @@ def test_same_result_as_the_per_question_route(attn_select):
     dWe, dbe = torch.zeros_like(W), torch.zeros(1, device="cuda")
     op.backward(he, q, hme, qm, W, b, run.g, dhe, dqe, dWe, dbe, 0)
     dh_ref = torch.zeros_like(h).index_add_(0, al64, dhe)
-    _close(dh, dh_ref, msg="d_hinfo against index_add_ of the per-question gradient")
-    _close(dq, dqe, msg="d_hq")
-    _close(dW, dWe, msg="dW")
-    _close(db, dbe, msg="db")
+    close_scaled(dh, dh_ref, msg="d_hinfo against index_add_ of the per-question gradient")
+    close_scaled(dq, dqe, msg="d_hq")
+    close_scaled(dW, dWe, msg="dW")
+    close_scaled(db, dbe, msg="db")
     cnt = torch.bincount(c["album"], minlength=c["A"])
     empty = int((cnt == 0).nonzero()[0])
     assert float(dh[empty].abs().max()) == 0.0                   # the album without a question: exactly zero
@@ -149,7 +102,7 @@ def test_same_result_as_the_per_question_route(attn_select):
 @pytest.mark.parametrize("name", ["mix-simi2-masked", "cols-jq33-w128", "rows-T333", "wide2048"])
 def test_forward_train_has_the_bits_of_the_inference_forward(name):
     c, _ = _case(name)
-    run = _Run(c)
+    run = TrainRun(c, "shared")
     ha_t, a_t = run.forward_train()
     ha_i, a_i = run.forward()
     assert torch.equal(ha_t, ha_i) and torch.equal(a_t, a_i)
@@ -164,7 +117,7 @@ def test_three_backward_calls_are_bitwise_equal(name):
     c, _ = _case(name)
     outs = []
     for _ in range(3):
-        run = _Run(c)                                            # a fresh handle: plan, saved and workspace anew
+        run = TrainRun(c, "shared")                              # a fresh handle: plan, saved and workspace anew
         run.forward_train(want_logits=False)
         outs.append(run.backward())
     for other in outs[1:]:
@@ -178,14 +131,14 @@ def test_a_questions_gradient_does_not_depend_on_its_company():
     big = int(torch.bincount(c["album"], minlength=c["A"]).argmax())          # the album with 2G+1 questions
     members = torch.nonzero(c["album"] == big).reshape(-1)
     assert members.numel() == 2 * G + 1
-    run = _Run(c)
+    run = TrainRun(c, "shared")
     run.forward_train(want_logits=False)
     _, dq_all, _, _ = run.backward()
     i = int(members[G])
-    one = _Run(c, rows=[i])
+    one = TrainRun(c, "shared", rows=[i])
     one.forward_train(want_logits=False)
     dh_one, dq_one, _, _ = one.backward()
-    _close(dq_one[0], dq_all[i], msg="d_hq alone against in company")
+    close_scaled(dq_one[0], dq_all[i], msg="d_hq alone against in company")
     others = [a for a in range(c["A"]) if a != big]
     assert float(dh_one[others].abs().max()) == 0.0                            # and it reaches its own album only
 
@@ -193,17 +146,17 @@ def test_a_questions_gradient_does_not_depend_on_its_company():
 def test_functional_and_nn_surface():
     from fvta_memexqa_amd import functional as Fn, nn
     c, ref = _case("rows-TRb+1")                                               # w = 256
-    h, q, W, b = (_cu(c[k]).requires_grad_() for k in ("h", "q", "W", "b"))
-    hm, qm, g = _cu(c["hm"]), _cu(c["qm"]), _cu(c["gout"])
+    h, q, W, b = (cu(c[k]).requires_grad_() for k in ("h", "q", "W", "b"))
+    hm, qm, g = cu(c["hm"]), cu(c["qm"]), cu(c["gout"])
     ha, a = Fn.attention_3d_shared_raw(h, q, c["album"], W, b, hm, qm, simiMatrix=c["simi"], add_tanh=c["tanh"],
                                        differentiable=True)
     assert ha.requires_grad and not a.requires_grad
     (ha * g).sum().backward()
-    _close(ha, ref["h_a"])
-    _close(h.grad, ref["dh"], msg="functional d_hinfo")
-    _close(q.grad, ref["dq"], msg="functional d_hq")
-    _close(W.grad.reshape(-1), ref["dW"], msg="functional dW")
-    _close(b.grad, ref["db"], msg="functional db")
+    close_scaled(ha, ref["h_a"])
+    close_scaled(h.grad, ref["dh"], msg="functional d_hinfo")
+    close_scaled(q.grad, ref["dq"], msg="functional d_hq")
+    close_scaled(W.grad.reshape(-1), ref["dW"], msg="functional dW")
+    close_scaled(b.grad, ref["db"], msg="functional db")
     with pytest.raises(RuntimeError, match="attention_3d"):                    # the default still refuses under gradient mode
         Fn.attention_3d_shared_raw(h, q, c["album"], W, b, hm, qm, simiMatrix=c["simi"], add_tanh=c["tanh"])
     with pytest.raises(NotImplementedError):
@@ -211,16 +164,16 @@ def test_functional_and_nn_surface():
 
     att = nn.FocalAttention3D(c["w"], simiMatrix=c["simi"], add_tanh=c["tanh"])
     with torch.no_grad():
-        att.p("att_logits/W").copy_(_cu(c["W"]))
-        att.p("att_logits/b").copy_(_cu(c["b"]))
-    h2, q2 = _cu(c["h"]).requires_grad_(), _cu(c["q"]).requires_grad_()
+        att.p("att_logits/W").copy_(cu(c["W"]))
+        att.p("att_logits/b").copy_(cu(c["b"]))
+    h2, q2 = cu(c["h"]).requires_grad_(), cu(c["q"]).requires_grad_()
     ha2, a2 = att.forward_shared(h2, q2, c["album"], hm, qm, differentiable=True)
     assert not a2.requires_grad
     (ha2 * g).sum().backward()
-    _close(h2.grad, ref["dh"], msg="nn d_hinfo")
-    _close(q2.grad, ref["dq"], msg="nn d_hq")
-    _close(att.p("att_logits/W").grad.reshape(-1), ref["dW"], msg="nn dW")
-    _close(att.p("att_logits/b").grad, ref["db"], msg="nn db")
+    close_scaled(h2.grad, ref["dh"], msg="nn d_hinfo")
+    close_scaled(q2.grad, ref["dq"], msg="nn d_hq")
+    close_scaled(att.p("att_logits/W").grad.reshape(-1), ref["dW"], msg="nn dW")
+    close_scaled(att.p("att_logits/b").grad, ref["db"], msg="nn db")
     with pytest.raises(RuntimeError):
         att.forward_shared(h2, q2, c["album"], hm, qm)
     with pytest.raises(NotImplementedError):
@@ -231,15 +184,15 @@ def test_functional_and_nn_surface():
     try:
         with torch.no_grad():
             al = c["album"].cuda()
-            ha_each, _ = Fn.attention_3d(_cu(c["h"]).index_select(0, al), _cu(c["q"]), hm.index_select(0, al), qm,
+            ha_each, _ = Fn.attention_3d(cu(c["h"]).index_select(0, al), cu(c["q"]), hm.index_select(0, al), qm,
                                          simiMatrix=c["simi"], add_tanh=c["tanh"], scope="att")
         names = set(Fn.variables)
-        h3 = _cu(c["h"]).requires_grad_()
-        ha3, a3 = Fn.attention_3d_shared(h3, _cu(c["q"]), c["album"], hm, qm, simiMatrix=c["simi"], add_tanh=c["tanh"],
+        h3 = cu(c["h"]).requires_grad_()
+        ha3, a3 = Fn.attention_3d_shared(h3, cu(c["q"]), c["album"], hm, qm, simiMatrix=c["simi"], add_tanh=c["tanh"],
                                          scope="att")
         assert set(Fn.variables) == names and any(n.endswith("att_logits/W") for n in names)
         assert ha3.requires_grad and not a3.requires_grad
-        _close(ha3, ha_each, msg="attention_3d_shared against attention_3d on gathered rows")
+        close_scaled(ha3, ha_each, msg="attention_3d_shared against attention_3d on gathered rows")
         ha3.sum().backward()
         assert h3.grad is not None and float(h3.grad.abs().max()) > 0
     finally:
@@ -251,16 +204,16 @@ def test_unpadded_width_goes_through_channel_padding():
     c = B.odd_width_case()                                                     # w = 100 -> the 128-wide kernels
     ref = B.reference(c)
     assert B.qualifies(c, ref["a_logits"])
-    h, q, W, b = (_cu(c[k]).requires_grad_() for k in ("h", "q", "W", "b"))
-    ha, a = Fn.attention_3d_shared_raw(h, q, c["album"], W, b, _cu(c["hm"]), _cu(c["qm"]), simiMatrix=c["simi"],
+    h, q, W, b = (cu(c[k]).requires_grad_() for k in ("h", "q", "W", "b"))
+    ha, a = Fn.attention_3d_shared_raw(h, q, c["album"], W, b, cu(c["hm"]), cu(c["qm"]), simiMatrix=c["simi"],
                                        add_tanh=c["tanh"], differentiable=True)
     assert tuple(ha.shape) == (c["NQ"], 100)
-    (ha * _cu(c["gout"])).sum().backward()
-    _close(ha, ref["h_a"])
-    _close(h.grad, ref["dh"], msg="d_hinfo")
-    _close(q.grad, ref["dq"], msg="d_hq")
-    _close(W.grad.reshape(-1), ref["dW"], msg="dW")
-    _close(b.grad, ref["db"], msg="db")
+    (ha * cu(c["gout"])).sum().backward()
+    close_scaled(ha, ref["h_a"])
+    close_scaled(h.grad, ref["dh"], msg="d_hinfo")
+    close_scaled(q.grad, ref["dq"], msg="d_hq")
+    close_scaled(W.grad.reshape(-1), ref["dW"], msg="dW")
+    close_scaled(b.grad, ref["db"], msg="db")
 
 
 def test_end_to_end_training_over_albums_encoded_once():
@@ -317,5 +270,5 @@ def test_end_to_end_training_over_albums_encoded_once():
     each, shared = step(False), step(True)
     assert set(each) == set(shared) and len(each) >= 2 + 2 * len(encs) + 6
     for key in each:
-        _close(shared[key], each[key], msg=key)
+        close_scaled(shared[key], each[key], msg=key)
     assert float(each["0/" + next(n for n, _ in encs[0].named_parameters())].abs().max()) > 0

@@ -1,7 +1,7 @@
 """GPU parity of the shared-context focal attention under the time warp (fvta_attn_shared_energy / fvta_attn_shared_fwd_tw,
 ops.SharedWarpedFocalAttention, functional.attention_3d_shared_warped_raw, nn.FocalAttention3D.forward_shared(time_warp=),
 nn.AlbumMemory.attend(time_warp=)) against the fp64 definition of tests/_attn_shared_tw_ref.py -- gather, time_warp_closed,
-attention_3d -- at the tolerances of tests/test_gpu_attn_shared.py, compared with that file's _close:
+attention_3d -- at the tolerances of tests/test_gpu_attn_shared.py, compared with tests/_album_attn_gpu.py's close:
 h_a 1e-4 / 1e-5, a_logits 1e-4 / 2e-5, scale 1e-4 / 1e-5.
 
 Conditioning: warp types 1, 3 and 4 multiply the rows by counts up to T, so the fp32 rounding of the warped rows' logits
@@ -21,59 +21,27 @@ import torch
 
 from tests import _attn_shared_ref as R
 from tests import _attn_shared_tw_ref as TW
-from tests.test_gpu_attn_shared import _close, _cu
+from tests._album_attn_gpu import album_energy, case, check_forward, close, cu, handle, infer, modules, warp_args
 
 pytestmark = pytest.mark.gpu
-
-_REF = {}
 
 
 def _case(name):
     """the case and its fp64 reference, computed once per session and never written to"""
-    if name not in _REF:
-        c = TW.build_case(name)
-        _REF[name] = (c, TW.reference(c, block=100))
-    return _REF[name]
-
-
-def _op(c, NQ=None):
-    from fvta_memexqa_amd import ops
-    return ops.SharedWarpedFocalAttention(c["A"], c["NQ"] if NQ is None else NQ, c["K"], c["T"], c["JQ"], c["w"], c["simi"],
-                                          c["tanh"], c["warp_type"], c["window_t"])
-
-
-def _warp_args(c):
-    return _cu(c["WH_b"]), _cu(c["WC_W"].reshape(-1)), _cu(c["WC_b"])
+    return case(TW, name, reference=lambda c: TW.reference(c, block=100))
 
 
 def _energy(c, op=None):
-    return (op or _op(c)).album_energy(_cu(c["h"]), _cu(c["WH_W"]), _cu(c["WC_W"].reshape(-1)))
+    return album_energy(c, "shared", op)
 
 
-def _run(c, rows=None, energy=None, want_logits=True):
+def _run(c, **kw):
     """ops.SharedWarpedFocalAttention on case c -> (h_a, a_logits, scale); rows: a subset of the questions (an index list)"""
-    from fvta_memexqa_amd import ops
-    q, qm, al, lq = c["q"], c["qm"], c["album"], c["lq"]
-    if rows is not None:
-        q, al, lq = q[rows], al[rows], lq[rows]
-        qm = None if qm is None else qm[rows]
-    op = _op(c, q.shape[0])
-    if energy is None:
-        energy = _energy(c, op)
-    idx = ops.check_album_index(al, c["A"])
-    return op.forward(_cu(c["h"]), _cu(ops.as_mask_u8(c["hm"])), energy, _cu(q), _cu(ops.as_mask_u8(qm)), _cu(lq), idx.cuda(),
-                      None if c["W"] is None else _cu(c["W"].reshape(-1)), _cu(c["b"]), *_warp_args(c),
-                      want_logits=want_logits, want_scale=True)
+    return infer(c, "shared", True, **kw)
 
 
 def _check(name, got, ref):
-    (ha, a, s), (ref_ha, ref_a, ref_s) = got, ref
-    for g, r, what in ((ha, ref_ha, "h_a"), (a, ref_a, "a_logits"), (s, ref_s, "scale")):
-        assert bool(torch.isfinite(g).all()), what
-        print("%s %s: worst |err| / (atol + rtol |ref|) = %.3f" % (name, what, TW.within(g.cpu(), r, what)[1]))
-    _close(s, ref_s, rtol=1e-4, atol=1e-5, msg="scale")
-    _close(a, ref_a, rtol=1e-4, atol=2e-5, msg="a_logits")
-    _close(ha, ref_ha, rtol=1e-4, atol=1e-5, msg="h_a")
+    check_forward(name, got, ref, TW.within)
 
 
 @pytest.mark.parametrize("name", TW.NAMES + TW.EXTRA)
@@ -89,12 +57,12 @@ def test_matches_the_fp64_definition(name):
 def test_energy_matches_and_is_the_album_s_alone():
     c, _ = _case("mix-simi2-masked")
     e = _energy(c)
-    _close(e, TW.energy(c), rtol=1e-4, atol=1e-5, msg="energy")
-    assert torch.equal(e, _energy(c, _op(c, 1)))                                # NQ does not enter
+    close(e, TW.energy(c), rtol=1e-4, atol=1e-5, msg="energy")
+    assert torch.equal(e, _energy(c, handle(c, "shared", True, NQ=1)))                                # NQ does not enter
     c9, _ = _case("k9")
-    _close(_energy(c9), TW.energy(c9), rtol=1e-4, atol=1e-5, msg="energy, K = 9")
+    close(_energy(c9), TW.energy(c9), rtol=1e-4, atol=1e-5, msg="energy, K = 9")
     cw, _ = _case("wide2048")
-    _close(_energy(cw), TW.energy(cw), rtol=1e-4, atol=1e-5, msg="energy, w = 2048")
+    close(_energy(cw), TW.energy(cw), rtol=1e-4, atol=1e-5, msg="energy, w = 2048")
 
 
 def test_three_calls_are_bitwise_equal():
@@ -118,8 +86,8 @@ def test_a_question_does_not_depend_on_its_company():
     ha_one, a_one, s_one = _run(c, rows=[i])
     # 2e-5, relative and absolute: another NQ is another split of T in the weighted sum, so another order of the same fp32
     # sum; the unwarped test's absolute 2e-6 times the largest |scale| of the band (2 * 3 + 1 = 7), rounded up
-    _close(ha_one[0], ha_all[i], rtol=2e-5, atol=2e-5, msg="alone against in company")
-    _close(a_one[0], a_all[i], rtol=2e-5, atol=2e-5)
+    close(ha_one[0], ha_all[i], rtol=2e-5, atol=2e-5, msg="alone against in company")
+    close(a_one[0], a_all[i], rtol=2e-5, atol=2e-5)
     assert torch.equal(s_one[0], s_all[i])
 
 
@@ -130,8 +98,8 @@ def test_one_energy_serves_two_question_sets():
     first, second = list(range(0, c["NQ"], 2)), list(range(1, c["NQ"], 2))
     for rows in (first, second):
         ha, a, s = _run(c, rows=rows, energy=e)
-        _close(ha, ha_all[rows], rtol=2e-5, atol=2e-5, msg="h_a of a question set against the whole call")
-        _close(a, a_all[rows], rtol=2e-5, atol=2e-5)
+        close(ha, ha_all[rows], rtol=2e-5, atol=2e-5, msg="h_a of a question set against the whole call")
+        close(a, a_all[rows], rtol=2e-5, atol=2e-5)
         assert torch.equal(s, s_all[rows])
 
 
@@ -140,48 +108,36 @@ def test_same_result_as_the_per_question_route():
     from fvta_memexqa_amd import ops
     c, _ = _case("mix-simi2-masked")
     al = c["album"].cuda()
-    rows = _cu(c["h"]).index_select(0, al)
-    hm = _cu(ops.as_mask_u8(c["hm"])).index_select(0, al)
+    rows = cu(c["h"]).index_select(0, al)
+    hm = cu(ops.as_mask_u8(c["hm"])).index_select(0, al)
     tw = ops.TimeWarp(c["NQ"], c["K"], c["T"], c["w"], c["warp_type"], c["window_t"])
     warped = torch.empty_like(rows)
-    tw.forward(rows, _cu(c["lq"]), _cu(c["WH_W"]), *_warp_args(c), warped)
+    tw.forward(rows, cu(c["lq"]), cu(c["WH_W"]), *warp_args(c), warped)
     per_q = ops.FocalAttention(c["NQ"], c["K"], c["T"], c["JQ"], c["w"], c["simi"], c["tanh"])
-    ref_ha, ref_a = per_q.forward(warped, _cu(c["q"]), hm, _cu(ops.as_mask_u8(c["qm"])), _cu(c["W"].reshape(-1)), _cu(c["b"]),
+    ref_ha, ref_a = per_q.forward(warped, cu(c["q"]), hm, cu(ops.as_mask_u8(c["qm"])), cu(c["W"].reshape(-1)), cu(c["b"]),
                                   want_logits=True)
     ha, a, s = _run(c)
-    _close(s, tw.scale, rtol=2e-4, atol=4e-5, msg="scale")
-    _close(a, ref_a, rtol=2e-4, atol=4e-5, msg="a_logits")
-    _close(ha, ref_ha, rtol=2e-4, atol=4e-5, msg="h_a")
+    close(s, tw.scale, rtol=2e-4, atol=4e-5, msg="scale")
+    close(a, ref_a, rtol=2e-4, atol=4e-5, msg="a_logits")
+    close(ha, ref_ha, rtol=2e-4, atol=4e-5, msg="h_a")
 
 
 # ------------------------------------------------------------------ the Python surface
-def _modules(c):
-    from fvta_memexqa_amd import nn
-    att = nn.FocalAttention3D(c["w"], simiMatrix=c["simi"], add_tanh=c["tanh"])
-    tw = nn.TimeWarp(c["w"], warp_type=c["warp_type"], window_t=c["window_t"])
-    with torch.no_grad():
-        att.p("att_logits/W").copy_(c["W"])
-        att.p("att_logits/b").copy_(c["b"])
-        for name, key in (("WH/W", "WH_W"), ("WH/b", "WH_b"), ("WC/W", "WC_W"), ("WC/b", "WC_b")):
-            tw.p(name).copy_(c[key])
-    return att, tw
-
-
 def test_functional_nn_and_album_memory_give_the_ops_result():
     from fvta_memexqa_amd import functional as Fn, nn
     c, ref = _case("mix-simi2-masked")
     ha_ops, a_ops, s_ops = _run(c)
-    h, q, lq, hm, qm = _cu(c["h"]), _cu(c["q"]), _cu(c["lq"]), _cu(c["hm"]), _cu(c["qm"])
-    wargs = (_cu(c["WH_W"]), _cu(c["WH_b"]), _cu(c["WC_W"]), _cu(c["WC_b"]))
+    h, q, lq, hm, qm = cu(c["h"]), cu(c["q"]), cu(c["lq"]), cu(c["hm"]), cu(c["qm"])
+    wargs = (cu(c["WH_W"]), cu(c["WH_b"]), cu(c["WC_W"]), cu(c["WC_b"]))
     kw = dict(simiMatrix=c["simi"], add_tanh=c["tanh"], warp_type=c["warp_type"], window_t=c["window_t"])
     with torch.no_grad():
-        ha, a, s = Fn.attention_3d_shared_warped_raw(h, q, c["album"], lq, _cu(c["W"]), _cu(c["b"]), *wargs, hm, qm, **kw)
+        ha, a, s = Fn.attention_3d_shared_warped_raw(h, q, c["album"], lq, cu(c["W"]), cu(c["b"]), *wargs, hm, qm, **kw)
         e = Fn.album_energy(h, wargs[0], wargs[2])
-        ha2, a2, s2 = Fn.attention_3d_shared_warped_raw(h, q, c["album"], lq, _cu(c["W"]), _cu(c["b"]), *wargs, hm, qm,
+        ha2, a2, s2 = Fn.attention_3d_shared_warped_raw(h, q, c["album"], lq, cu(c["W"]), cu(c["b"]), *wargs, hm, qm,
                                                         energy=e, **kw)
     for got in ((ha, a, s), (ha2, a2, s2)):
         assert torch.equal(got[0], ha_ops) and torch.equal(got[1], a_ops) and torch.equal(got[2], s_ops)
-    att, tw = _modules(c)
+    att, tw = modules(c)
     with torch.no_grad():
         ha_n, a_n = att.forward_shared(h, q, c["album"], hm, qm, time_warp=tw, lq=lq)
         mem = nn.AlbumMemory(h, hm)
@@ -192,7 +148,7 @@ def test_functional_nn_and_album_memory_give_the_ops_result():
     assert torch.equal(ha_n, ha_ops) and torch.equal(a_n, a_ops)
     assert torch.equal(ha_m, ha_ops) and torch.equal(a_m, a_ops) and torch.equal(ha_m2, ha_ops)
     assert torch.equal(ha_plain, ha_unwarped) and not torch.equal(ha_plain, ha_ops)
-    _close(ha_m, ref[0], msg="AlbumMemory.attend against the fp64 definition")
+    close(ha_m, ref[0], msg="AlbumMemory.attend against the fp64 definition")
 
 
 def test_a_padded_width_goes_through():
@@ -201,9 +157,9 @@ def test_a_padded_width_goes_through():
     c = TW.add_warp(dict(R.make_case([3, 2], 2, 9, 5, 40, 2, True, 77), tanh=True), 77, 5)
     ref_ha, ref_a, ref_s = TW.reference(c)
     with torch.no_grad():
-        ha, a, s = Fn.attention_3d_shared_warped_raw(_cu(c["h"]), _cu(c["q"]), c["album"], _cu(c["lq"]), _cu(c["W"]), _cu(c["b"]),
-                                                     _cu(c["WH_W"]), _cu(c["WH_b"]), _cu(c["WC_W"]), _cu(c["WC_b"]), _cu(c["hm"]),
-                                                     _cu(c["qm"]), simiMatrix=2, add_tanh=True, warp_type=5, window_t=c["window_t"])
+        ha, a, s = Fn.attention_3d_shared_warped_raw(cu(c["h"]), cu(c["q"]), c["album"], cu(c["lq"]), cu(c["W"]), cu(c["b"]),
+                                                     cu(c["WH_W"]), cu(c["WH_b"]), cu(c["WC_W"]), cu(c["WC_b"]), cu(c["hm"]),
+                                                     cu(c["qm"]), simiMatrix=2, add_tanh=True, warp_type=5, window_t=c["window_t"])
     assert ha.shape == (5, 40)
     _check("w40", (ha, a, s), (ref_ha, ref_a, ref_s))
 
@@ -211,8 +167,8 @@ def test_a_padded_width_goes_through():
 def test_album_memory_never_serves_a_stale_energy():
     from fvta_memexqa_amd import nn
     c, _ = _case("mix-simi2-masked")
-    att, tw = _modules(c)
-    h, q, lq, hm, qm = _cu(c["h"]), _cu(c["q"]), _cu(c["lq"]), _cu(c["hm"]), _cu(c["qm"])
+    att, tw = modules(c)
+    h, q, lq, hm, qm = cu(c["h"]), cu(c["q"]), cu(c["lq"]), cu(c["hm"]), cu(c["qm"])
     mem = nn.AlbumMemory(h, hm)
     with torch.no_grad():
         ha0, _ = mem.attend(att, q, qm, c["album"], time_warp=tw, lq=lq)
@@ -222,14 +178,14 @@ def test_album_memory_never_serves_a_stale_energy():
         ha1, _ = mem.attend(att, q, qm, c["album"], time_warp=tw, lq=lq)
         assert mem.energy(tw) is not e0                                        # ... is seen by the next attend
         c15 = dict(c, WH_W=c["WH_W"] * 1.5)
-        _close(ha1, TW.reference(c15)[0], msg="after the in-place update")
+        close(ha1, TW.reference(c15)[0], msg="after the in-place update")
         assert not torch.equal(ha1, ha0)
         sd = {k: v.clone() for k, v in tw.state_dict().items()}
         sd["WC/W"] = sd["WC/W"] * 0.5
         tw.load_state_dict(sd)                                                 # load_state_dict writes in place as well
         ha2, _ = mem.attend(att, q, qm, c["album"], time_warp=tw, lq=lq)
-        _close(ha2, TW.reference(dict(c15, WC_W=c["WC_W"] * 0.5))[0], msg="after load_state_dict")
-        _, tw_b = _modules(c)                                                  # another module, the first weights again
+        close(ha2, TW.reference(dict(c15, WC_W=c["WC_W"] * 0.5))[0], msg="after load_state_dict")
+        _, tw_b = modules(c)                                                  # another module, the first weights again
         ha3, _ = mem.attend(att, q, qm, c["album"], time_warp=tw_b, lq=lq)
         assert torch.equal(ha3, ha0)
 
@@ -237,13 +193,13 @@ def test_album_memory_never_serves_a_stale_energy():
 def test_refusals():
     from fvta_memexqa_amd import _lib, functional as Fn, nn, ops
     c, _ = _case("mix-simi2-masked")
-    att, tw = _modules(c)
-    h, q, lq, hm, qm = _cu(c["h"]), _cu(c["q"]), _cu(c["lq"]), _cu(c["hm"]), _cu(c["qm"])
+    att, tw = modules(c)
+    h, q, lq, hm, qm = cu(c["h"]), cu(c["q"]), cu(c["lq"]), cu(c["hm"]), cu(c["qm"])
     with pytest.raises(RuntimeError, match="forward-only"):                    # gradient mode on, the parameters require grad
         att.forward_shared(h, q, c["album"], hm, qm, time_warp=tw, lq=lq)
     with pytest.raises(RuntimeError, match="forward-only"):
-        Fn.attention_3d_shared_warped_raw(h, q.clone().requires_grad_(), c["album"], lq, _cu(c["W"]), _cu(c["b"]), _cu(c["WH_W"]),
-                                          _cu(c["WH_b"]), _cu(c["WC_W"]), _cu(c["WC_b"]), hm, qm, simiMatrix=2, warp_type=5)
+        Fn.attention_3d_shared_warped_raw(h, q.clone().requires_grad_(), c["album"], lq, cu(c["W"]), cu(c["b"]), cu(c["WH_W"]),
+                                          cu(c["WH_b"]), cu(c["WC_W"]), cu(c["WC_b"]), hm, qm, simiMatrix=2, warp_type=5)
     with pytest.raises(_lib.FvtaError, match="time warping type not implemented"):
         ops.SharedWarpedFocalAttention(2, 3, 2, 9, 5, 64, 2, True, 9)
     with pytest.raises(Exception, match="time warping type not implemented"):
@@ -255,8 +211,8 @@ def test_refusals():
 def test_lq_errors_are_raised_before_any_library_call(monkeypatch):
     from fvta_memexqa_amd import nn, ops
     c, _ = _case("mix-simi2-masked")
-    att, tw = _modules(c)
-    h, q, lq, hm, qm = _cu(c["h"]), _cu(c["q"]), _cu(c["lq"]), _cu(c["hm"]), _cu(c["qm"])
+    att, tw = modules(c)
+    h, q, lq, hm, qm = cu(c["h"]), cu(c["q"]), cu(c["lq"]), cu(c["hm"]), cu(c["qm"])
     mem = nn.AlbumMemory(h, hm)
 
     def boom(*a, **k):
@@ -322,7 +278,7 @@ def test_end_to_end_many_questions_under_the_time_warp():
         g1_each, a_each = att(warped, hq, hall_mask.index_select(0, al), qmask)
         assert bool((scale < 0).any()) and bool((scale > 0).any())
         # 2e-4 of the largest magnitude: each route's own 1e-4 against fp64 (BASELINE.json north_star), added
-        _close(g1_shared, g1_each, rtol=2e-4, atol=2e-4 * float(g1_each.abs().max()), msg="g1")
-        _close(a_shared, a_each, rtol=2e-4, atol=4e-5, msg="a_logits")
+        close(g1_shared, g1_each, rtol=2e-4, atol=2e-4 * float(g1_each.abs().max()), msg="g1")
+        close(a_shared, a_each, rtol=2e-4, atol=4e-5, msg="a_logits")
         logits_s, logits_e = head(g1_shared), head(g1_each)
-    _close(logits_s, logits_e, rtol=2e-4, atol=2e-4 * float(logits_e.abs().max()), msg="shared-warped against per-question")
+    close(logits_s, logits_e, rtol=2e-4, atol=2e-4 * float(logits_e.abs().max()), msg="shared-warped against per-question")

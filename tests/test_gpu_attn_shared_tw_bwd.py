@@ -17,104 +17,32 @@ d_lq 0.02, dW 0.03, db 0.03, dWH_W 0.01, dWH_b 0.02, dWC_W 0.15, dWC_b 0.11.  db
 plain sum of dx it cancels from summands of order 1 to a few 1e-3 (0 without tanh) and kept 4e-6 to 1.1e-5 of fp32 noise --
 1.08 and 1.05 of its tolerance at cols-jq1-w512 and cols-jq64-w512, and up to 0.69 on the per-question route on the same
 inputs.  The kernels sum -damax x^2 instead (tests/test_attn_shared_tw_bwd_host.py holds the identity)."""
-import numpy as np
 import pytest
 import torch
 
 from tests import _attn_shared_ref as R
 from tests import _attn_shared_tw_bwd_ref as TB
+from tests._album_attn_gpu import TrainRun, case, check_grads, close_scaled, cu, modules, output_names, tol_of, want_of
 
 pytestmark = pytest.mark.gpu
 
-_REF = {}
-NAMES = ("d_hinfo", "d_hq", "d_lq", "dW", "db", "dWH_W", "dWH_b", "dWC_W", "dWC_b")       # backward()'s outputs, in order
+NAMES = output_names("shared", True)                             # backward()'s nine outputs, in order
 OVERWRITTEN, ACCUMULATED = NAMES[:3], NAMES[3:]
-
-
-def _close(a, b, rtol=1e-4, atol=1e-5, msg=""):
-    a = a.detach().cpu().double().numpy()
-    b = b.detach().cpu().double().numpy()
-    scale = max(1.0, float(np.abs(b).max()))
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol * scale, err_msg=msg)
-
-
-def _cu(t):
-    return None if t is None else t.cuda().contiguous()
 
 
 def _case(name):
     """the case and its fp64 reference, computed once per session and never written to"""
-    if name not in _REF:
-        c = TB.build_case(name)
-        _REF[name] = (c, TB.reference(c))
-    return _REF[name]
-
-
-def _ref_of(ref, name):
-    return ref[{"d_hinfo": "dh", "d_hq": "dq", "d_lq": "dlq"}.get(name, name)]
+    return case(TB, name)
 
 
 def _check_grads(name, got, ref, what=""):
-    for n, g in zip(NAMES, got):
-        want = _ref_of(ref, n)
-        key = {"d_hinfo": "dh", "d_hq": "dq", "d_lq": "dlq"}.get(n, n)
-        if n == "dWH_W":
-            want = want[:g.shape[0]]
-        print("%s %s%s: worst |err| / (atol max(1, max|ref|) + rtol |ref|) = %.3f, max |ref| %.3g"
-              % (name, what, n, TB.within(g, want, key)[1], float(want.abs().max())))
-    for n, g in zip(NAMES, got):
-        want = _ref_of(ref, n)
-        key = {"d_hinfo": "dh", "d_hq": "dq", "d_lq": "dlq"}.get(n, n)
-        rtol, atol = TB.TOL[key]
-        _close(g, want[:g.shape[0]] if n == "dWH_W" else want, rtol=rtol, atol=atol, msg=what + n)
-
-
-class _Run:
-    """ops.SharedWarpedFocalAttention on case c (rows: a subset of the questions), its device tensors kept for backward()"""
-
-    def __init__(self, c, rows=None):
-        from fvta_memexqa_amd import ops
-        q, qm, al, g, lq = c["q"], c["qm"], c["album"], c["gout"], c["lq"]
-        if rows is not None:
-            q, al, g, lq = q[rows], al[rows], g[rows], lq[rows]
-            qm = None if qm is None else qm[rows]
-        self.c, self.NQ, w = c, q.shape[0], c["w"]
-        self.op = ops.SharedWarpedFocalAttention(c["A"], self.NQ, c["K"], c["T"], c["JQ"], w, c["simi"], c["tanh"], c["warp_type"],
-                                                 c["window_t"])
-        self.h, self.hm, self.q, self.qm = _cu(c["h"]), _cu(ops.as_mask_u8(c["hm"])), _cu(q), _cu(ops.as_mask_u8(qm))
-        self.lq, self.al = _cu(lq), ops.check_album_index(al, c["A"]).cuda()
-        self.W, self.b = _cu(c["W"].reshape(-1)), _cu(c["b"])
-        self.WH, self.WHb, self.WC, self.WCb = _cu(c["WH_W"]), _cu(c["WH_b"]), _cu(c["WC_W"].reshape(-1)), _cu(c["WC_b"])
-        self.g = _cu(g)
-        self.energy = self.op.album_energy(self.h, self.WH, self.WC)
-
-    def _fwd_args(self):
-        return (self.h, self.hm, self.energy, self.q, self.qm, self.lq, self.al, self.W, self.b, self.WHb, self.WC, self.WCb)
-
-    def forward_train(self, want_logits=True):
-        return self.op.forward_train(*self._fwd_args(), want_logits=want_logits, want_scale=True)
-
-    def forward(self, want_logits=True):
-        return self.op.forward(*self._fwd_args(), want_logits=want_logits, want_scale=True)
-
-    def backward(self, acc=None, fill=7.0):
-        """-> the nine outputs; d_hinfo, d_hq, d_lq prefilled with `fill`; acc: the six accumulated ones of an earlier call"""
-        c, w = self.c, self.c["w"]
-        dh = torch.full((c["A"], c["K"], c["T"], w), fill, device="cuda")
-        dq = torch.full((self.NQ, c["JQ"], w), fill, device="cuda")
-        dlq = torch.full((self.NQ, w), fill, device="cuda")
-        if acc is None:
-            acc = (torch.zeros_like(self.W), torch.zeros(1, device="cuda"), torch.zeros(w, w, device="cuda"),
-                   torch.zeros(w, device="cuda"), torch.zeros(w, device="cuda"), torch.zeros(1, device="cuda"))
-        self.op.backward(self.h, self.hm, self.q, self.qm, self.lq, self.al, self.W, self.b, self.WH, self.WHb, self.WC, self.WCb,
-                         self.g, dh, dq, dlq, *acc)
-        return (dh, dq, dlq) + tuple(acc)
+    check_grads(name, got, ref, NAMES, TB.TOL, TB.within, what)
 
 
 @pytest.mark.parametrize("name", TB.CASE_IDS)
 def test_gradients_match_fp64_autograd(name):
     c, ref = _case(name)
-    run = _Run(c)
+    run = TrainRun(c, "shared", True)
     from fvta_memexqa_amd import ops
     plan = ops.SharedFocalAttention(c["A"], c["NQ"], c["K"], c["T"], c["JQ"], c["w"], c["simi"], c["tanh"]).plan()
     R.loop_regime(name, c, plan, run.op.bwd_plan())              # a LOOP_SPECS case reaches its loop, before any launch
@@ -125,8 +53,8 @@ def test_gradients_match_fp64_autograd(name):
     err = float((a.cpu().double() - ref["a_logits"])[v].abs().max())
     print("%s: max |a_logits - fp64| over valid entries %.3g, smallest gap %.3g" % (name, err, min(jgap, tgap)))
     assert err < min(jgap, tgap) / 4, (err, jgap, tgap)
-    _close(ha, ref["h_a"], msg="h_a")
-    _close(s, ref["scale"], msg="scale")
+    close_scaled(ha, ref["h_a"], msg="h_a")
+    close_scaled(s, ref["scale"], msg="scale")
     got = run.backward()                                         # d_hinfo / d_hq / d_lq prefilled with 7.0: overwritten
     _check_grads(name, got, ref)
     empty = torch.bincount(c["album"], minlength=c["A"]) == 0
@@ -134,13 +62,11 @@ def test_gradients_match_fp64_autograd(name):
         assert float(got[0].cpu()[empty].abs().max()) == 0.0
     again = run.backward(acc=got[3:], fill=-3.0)                 # a second call: the parameter gradients accumulate ...
     for n, g in zip(ACCUMULATED, again[3:]):
-        key = n
-        rtol, atol = TB.TOL[key]
-        want = _ref_of(ref, n)
-        _close(g, 2 * (want[:g.shape[0]] if n == "dWH_W" else want), rtol=rtol, atol=2 * atol, msg=n + " accumulates")
+        rtol, atol = tol_of(TB.TOL, n)
+        close_scaled(g, 2 * want_of(ref, n, g), rtol=rtol, atol=2 * atol, msg=n + " accumulates")
     for n, g in zip(OVERWRITTEN, again[:3]):                     # ... the others do not
-        rtol, atol = TB.TOL[{"d_hinfo": "dh", "d_hq": "dq", "d_lq": "dlq"}[n]]
-        _close(g, _ref_of(ref, n), rtol=rtol, atol=atol, msg=n + " overwritten")
+        rtol, atol = tol_of(TB.TOL, n)
+        close_scaled(g, want_of(ref, n, g), rtol=rtol, atol=atol, msg=n + " overwritten")
 
 
 def test_same_result_as_the_per_question_route(attn_select):
@@ -150,12 +76,12 @@ def test_same_result_as_the_per_question_route(attn_select):
     gradient.  The project's tolerances apply."""
     from fvta_memexqa_amd import ops
     c = TB.build_case(TB.MIX_MASKED, parity=False)
-    run = _Run(c)
+    run = TrainRun(c, "shared", True)
     run.forward_train(want_logits=False)
     got = run.backward()
     attn_select.exact()
     al64 = run.al.long()
-    he, hme = run.h.index_select(0, al64), run.hm.index_select(0, al64)
+    he, hme = run.rows.index_select(0, al64), run.mask.index_select(0, al64)
     tw = ops.TimeWarp(c["NQ"], c["K"], c["T"], c["w"], c["warp_type"], c["window_t"])
     warped = torch.empty_like(he)
     tw.forward(he, run.lq, run.WH, run.WHb, run.WC, run.WCb, warped)
@@ -167,7 +93,7 @@ def test_same_result_as_the_per_question_route(attn_select):
     dhe, dlqe = torch.empty_like(he), torch.zeros_like(run.lq)
     dWH, dWHb, dWC, dWCb = torch.zeros_like(run.WH), torch.zeros_like(run.WHb), torch.zeros_like(run.WC), torch.zeros_like(run.WCb)
     tw.backward(he, run.lq, run.WH, run.WHb, run.WC, run.WCb, dwarp, dhe, dlqe, dWH, dWHb, dWC, dWCb)
-    dh_ref = torch.zeros_like(run.h).index_add_(0, al64, dhe)
+    dh_ref = torch.zeros_like(run.rows).index_add_(0, al64, dhe)
     want = dict(dh=dh_ref, dq=dqe, dlq=dlqe, dW=dWe, db=dbe, dWH_W=dWH, dWH_b=dWHb, dWC_W=dWC, dWC_b=dWCb)
     _check_grads("per-question", got, {k: v.cpu().double() for k, v in want.items()}, what="against the expanded route: ")
     cnt = torch.bincount(c["album"], minlength=c["A"])
@@ -181,7 +107,7 @@ def test_same_result_as_the_per_question_route(attn_select):
 @pytest.mark.parametrize("name", ["mix-simi2-masked", "cols-jq33-w128", "rows-T333", "wide2048", "short-T9-warp3"])
 def test_forward_train_has_the_bits_of_the_inference_forward(name):
     c, _ = _case(name)
-    run = _Run(c)
+    run = TrainRun(c, "shared", True)
     ha_t, a_t, s_t = run.forward_train()
     ha_i, a_i, s_i = run.forward()
     assert torch.equal(ha_t, ha_i) and torch.equal(a_t, a_i) and torch.equal(s_t, s_i)
@@ -195,7 +121,7 @@ def test_two_backward_calls_are_bitwise_equal(name):
     c, _ = _case(name)
     outs = []
     for _ in range(2):
-        run = _Run(c)                                            # a fresh handle: plan, saved and workspace anew
+        run = TrainRun(c, "shared", True)                        # a fresh handle: plan, saved and workspace anew
         run.forward_train(want_logits=False)
         outs.append(run.backward())
     assert len(outs[0]) == 9
@@ -214,32 +140,20 @@ def test_a_questions_gradient_does_not_depend_on_its_company():
     big = int(torch.bincount(c["album"], minlength=c["A"]).argmax())          # the album with 2G+1 questions
     members = torch.nonzero(c["album"] == big).reshape(-1)                     # ascending: groups of G, G and 1
     assert members.numel() == 2 * G + 1
-    run = _Run(c)
+    run = TrainRun(c, "shared", True)
     run.forward_train(want_logits=False)
     got_all = run.backward()
     others = [a for a in range(c["A"]) if a != big]
     for i, same_count in ((int(members[2 * G]), True), (int(members[G]), False)):
-        one = _Run(c, rows=[i])
+        one = TrainRun(c, "shared", True, rows=[i])
         one.forward_train(want_logits=False)
         got_one = one.backward()
         assert torch.equal(got_one[2][0], got_all[2][i]), "d_lq alone against in company"
         if same_count:
             assert torch.equal(got_one[1][0], got_all[1][i]), "d_hq alone against in company"
         else:
-            _close(got_one[1][0], got_all[1][i], msg="d_hq alone against in company, another group count")
+            close_scaled(got_one[1][0], got_all[1][i], msg="d_hq alone against in company, another group count")
         assert float(got_one[0][others].abs().max()) == 0.0                    # and it reaches its own album only
-
-
-def _modules(c):
-    from fvta_memexqa_amd import nn
-    att = nn.FocalAttention3D(c["w"], simiMatrix=c["simi"], add_tanh=c["tanh"])
-    tw = nn.TimeWarp(c["w"], warp_type=c["warp_type"], window_t=c["window_t"])
-    with torch.no_grad():
-        att.p("att_logits/W").copy_(c["W"])
-        att.p("att_logits/b").copy_(c["b"])
-        for name, key in (("WH/W", "WH_W"), ("WH/b", "WH_b"), ("WC/W", "WC_W"), ("WC/b", "WC_b")):
-            tw.p(name).copy_(c[key])
-    return att, tw
 
 
 def _module_grads(att, tw):
@@ -251,14 +165,14 @@ def test_functional_and_nn_surface():
     from fvta_memexqa_amd import functional as Fn, nn
     c, ref = _case("rows-TRb+1")                                               # w = 256
     keys = ("h", "q", "lq", "W", "b", "WH_W", "WH_b", "WC_W", "WC_b")
-    t = {k: _cu(c[k]).requires_grad_() for k in keys}
-    hm, qm, g = _cu(c["hm"]), _cu(c["qm"]), _cu(c["gout"])
+    t = {k: cu(c[k]).requires_grad_() for k in keys}
+    hm, qm, g = cu(c["hm"]), cu(c["qm"]), cu(c["gout"])
     kw = dict(simiMatrix=c["simi"], add_tanh=c["tanh"], warp_type=c["warp_type"], window_t=c["window_t"])
     args = lambda d: (d["h"], d["q"], c["album"], d["lq"], d["W"], d["b"], d["WH_W"], d["WH_b"], d["WC_W"], d["WC_b"], hm, qm)
     ha, a, s = Fn.attention_3d_shared_warped_raw(*args(t), differentiable=True, **kw)
     assert ha.requires_grad and not a.requires_grad and not s.requires_grad
     (ha * g).sum().backward()
-    _close(ha, ref["h_a"])
+    close_scaled(ha, ref["h_a"])
     grads = [t[k].grad for k in ("h", "q", "lq", "W", "b", "WH_W", "WH_b", "WC_W", "WC_b")]
     assert tuple(grads[5].shape) == (2 * c["w"], c["w"]) and float(grads[5][c["w"]:].abs().max()) == 0.0
     grads[3], grads[7] = grads[3].reshape(-1), grads[7].reshape(-1)
@@ -266,7 +180,7 @@ def test_functional_and_nn_surface():
     # a held energy and energy=None: the same bits, forward and backward
     with torch.no_grad():
         e = Fn.album_energy(t["h"], t["WH_W"], t["WC_W"])
-    t2 = {k: _cu(c[k]).requires_grad_() for k in keys}
+    t2 = {k: cu(c[k]).requires_grad_() for k in keys}
     ha2, a2, s2 = Fn.attention_3d_shared_warped_raw(*args(t2), energy=e, differentiable=True, **kw)
     (ha2 * g).sum().backward()
     assert torch.equal(ha2, ha) and torch.equal(a2, a) and torch.equal(s2, s)
@@ -279,24 +193,24 @@ def test_functional_and_nn_surface():
                                           t["WC_b"], hm, qm, simiMatrix=4, warp_type=5, differentiable=True)
 
     # nn: forward_shared_warped against the per-question nn path, at the end-to-end 2e-4 of tests/test_gpu_attn_shared_tw.py
-    att, tw = _modules(c)
-    h1, q1, lq1 = (_cu(c[k]).requires_grad_() for k in ("h", "q", "lq"))
+    att, tw = modules(c)
+    h1, q1, lq1 = (cu(c[k]).requires_grad_() for k in ("h", "q", "lq"))
     ha_s, a_s = att.forward_shared_warped(h1, q1, c["album"], lq1, tw, hm, qm)
     assert ha_s.requires_grad and not a_s.requires_grad
     (ha_s * g).sum().backward()
     shared = [h1.grad, q1.grad, lq1.grad] + [x.clone() for x in _module_grads(att, tw)]
     att.zero_grad(set_to_none=True)
     tw.zero_grad(set_to_none=True)
-    h2, q2, lq2 = (_cu(c[k]).requires_grad_() for k in ("h", "q", "lq"))
+    h2, q2, lq2 = (cu(c[k]).requires_grad_() for k in ("h", "q", "lq"))
     al = c["album"].cuda()
     warped, _ = tw(h2.index_select(0, al), lq2)[:2]
     ha_e, _ = att(warped, q2, hm.index_select(0, al), qm)
     (ha_e * g).sum().backward()
     each = [h2.grad, q2.grad, lq2.grad] + _module_grads(att, tw)
-    _close(ha_s, ha_e, rtol=2e-4, atol=2e-4, msg="nn h_a")
+    close_scaled(ha_s, ha_e, rtol=2e-4, atol=2e-4, msg="nn h_a")
     for n, x, y in zip(NAMES, shared, each):
         assert x is not None and y is not None, n
-        _close(x.reshape(y.shape), y, rtol=2e-4, atol=2e-4, msg="nn " + n)
+        close_scaled(x.reshape(y.shape), y, rtol=2e-4, atol=2e-4, msg="nn " + n)
     with pytest.raises(NotImplementedError, match="forward_shared_warped"):    # the inference call's refusal names the new one
         att.forward_shared(h2, q2, c["album"], hm, qm, differentiable=True, time_warp=tw, lq=lq2)
     with pytest.raises(NotImplementedError):
@@ -309,14 +223,14 @@ def test_unpadded_width_goes_through_channel_padding():
     ref = TB.reference(c)
     assert TB.qualifies(c, ref["a_logits"])
     keys = ("h", "q", "lq", "W", "b", "WH_W", "WH_b", "WC_W", "WC_b")
-    t = {k: _cu(c[k]).requires_grad_() for k in keys}
+    t = {k: cu(c[k]).requires_grad_() for k in keys}
     ha, a, s = Fn.attention_3d_shared_warped_raw(t["h"], t["q"], c["album"], t["lq"], t["W"], t["b"], t["WH_W"], t["WH_b"], t["WC_W"],
-                                                 t["WC_b"], _cu(c["hm"]), _cu(c["qm"]), simiMatrix=c["simi"], add_tanh=c["tanh"],
+                                                 t["WC_b"], cu(c["hm"]), cu(c["qm"]), simiMatrix=c["simi"], add_tanh=c["tanh"],
                                                  warp_type=c["warp_type"], window_t=c["window_t"], differentiable=True)
     assert tuple(ha.shape) == (c["NQ"], 100)
-    (ha * _cu(c["gout"])).sum().backward()
-    _close(ha, ref["h_a"])
-    _close(s, ref["scale"])
+    (ha * cu(c["gout"])).sum().backward()
+    close_scaled(ha, ref["h_a"])
+    close_scaled(s, ref["scale"])
     grads = [t[k].grad for k in ("h", "q", "lq")] + [t["W"].grad.reshape(-1), t["b"].grad, t["WH_W"].grad, t["WH_b"].grad,
                                                      t["WC_W"].grad.reshape(-1), t["WC_b"].grad]
     assert tuple(grads[5].shape) == (200, 100) and float(grads[5][100:].abs().max()) == 0.0

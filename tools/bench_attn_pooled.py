@@ -17,68 +17,27 @@ Usage: python tools/bench_attn_pooled.py [--case USERS QPU w]... [--iters 10] [-
         K = 6, JX = 300, M = 4, JQ = 30, simiMatrix 2 throughout)
 Under a kernel trace run one child directly:
        <tracer> -- python tools/bench_attn_pooled.py --child --case 8 8 512 --iters 1 --warmup 0"""
-import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _album_bench as ab
+
 K, JX, M, JQ, SIMI, OWNED = 6, 300, 4, 30, 2, 8
-ap = argparse.ArgumentParser()
-ap.add_argument("--case", type=int, nargs=3, action="append", metavar=("USERS", "QPU", "w"))
-ap.add_argument("--iters", type=int, default=10)
-ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--limit", type=float, default=240.0)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_pooled_bench.jsonl"))
-ap.add_argument("--child", action="store_true")
-args = ap.parse_args()
-cases = args.case or [[U, qpu, w] for w in (512, 1024) for U, qpu in ((8, 8), (8, 32), (64, 1))]
-
+args = ab.parse(("USERS", "QPU", "w"), [[U, qpu, w] for w in (512, 1024) for U, qpu in ((8, 8), (8, 32), (64, 1))], 240.0,
+                "attn_pooled_bench.jsonl")
 if not args.child:
-    for case in cases:
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--case"] + [str(v) for v in case] + \
-              ["--iters", str(args.iters), "--warmup", str(args.warmup)]
-        try:
-            p = subprocess.run(cmd, timeout=args.limit, stdout=subprocess.PIPE, text=True)
-            rc, line = p.returncode, p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
-        except subprocess.TimeoutExpired:
-            rc, line = 124, ""
-        if rc != 0:
-            print(json.dumps(dict(case=case, failed=rc)), flush=True)
-            sys.exit(rc)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
-    sys.exit(0)
+    sys.exit(ab.run_parent(__file__, args))
 
-sys.path.insert(0, ROOT)
+sys.path.insert(0, ab.ROOT)
 import torch  # noqa: E402
 from fvta_memexqa_amd import ops  # noqa: E402
 
 ops.require_gpu()                       # raises without a GPU: there is nothing to time on a CPU
-U, QPU, w = cases[0]
+U, QPU, w = args.cases[0]
 P, NQ, T = U * OWNED, U * QPU, M * JX
-g = torch.Generator().manual_seed(U * 1000 + QPU + w)
-pool = (torch.randn(P, K, JX, w, generator=g) * 0.5).cuda()
-hq = (torch.randn(NQ, JQ, w, generator=g) * 0.5).cuda()
-W = (torch.randn(2 * w, generator=g) * 0.1).cuda()
-b = (torch.randn(1, generator=g) * 0.1).cuda()
-pmask = torch.ones(P, K, JX, dtype=torch.uint8, device="cuda")
-qmask = torch.ones(NQ, JQ, dtype=torch.uint8, device="cuda")
-user = torch.arange(U).repeat_interleave(QPU)[torch.randperm(NQ, generator=g)]
-lists_host = torch.stack([int(u) * OWNED + torch.randperm(OWNED, generator=g)[:M] for u in user])      # [NQ,M]
+(pool, hq, W, b), pmask, qmask, lists_host = ab.pooled_inputs(("pool", "hq", "W_flat", "b"), (U, QPU, w), K, JX, M, JQ, OWNED)
 lists = ops.check_album_lists(lists_host, P, True).cuda()
 lists64 = lists.long()
-
-
-def gather():
-    """[NQ,K,M*JX,w] rows and [NQ,K,M*JX] mask of the listed albums: the per-question route's context"""
-    rows = pool.index_select(0, lists64.reshape(-1)).reshape(NQ, M, K, JX, w).permute(0, 2, 1, 3, 4).reshape(NQ, K, T, w)
-    mask = pmask.index_select(0, lists64.reshape(-1)).reshape(NQ, M, K, JX).permute(0, 2, 1, 3).reshape(NQ, K, T)
-    return rows.contiguous(), mask.contiguous()
-
 
 # (c): one context per distinct list, built beforehand
 distinct, which = torch.unique(lists_host, dim=0, return_inverse=True)
@@ -94,7 +53,7 @@ shared = ops.SharedFocalAttention(D, NQ, K, T, JQ, w, SIMI, False)
 
 
 def expand():
-    rows, mask = gather()
+    rows, mask = ab.gather_lists(pool, pmask, lists64)
     return per_q.forward(rows, hq, mask, qmask, W, b)[0]
 
 
@@ -109,18 +68,8 @@ rec = dict(users=U, questions_per_user=QPU, owned=OWNED, P=P, NQ=NQ, M=M, K=K, J
            distinct_context_bytes=D * M * row_bytes)
 out = {}
 for name, fn in routes.items():
-    for _ in range(args.warmup):
-        fn()
-    ts = []
-    for _ in range(args.iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out[name] = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    rec.update({name + "_ms_median": round(statistics.median(ts), 3), name + "_ms_min": round(min(ts), 3),
-                name + "_ms_max": round(max(ts), 3)})
+    out[name], ts = ab.time_route(fn, args.iters, args.warmup)
+    ab.record_ms(rec, name, ts)
 rec["max_abs_diff_pooled_vs_expand"] = float((out["pooled"] - out["expand"]).abs().max())
 rec["max_abs_diff_pooled_vs_shared"] = float((out["pooled"] - out["shared"]).abs().max())
 rec["h_a_sum"] = float(out["pooled"].double().sum())

@@ -16,64 +16,27 @@ Usage: python tools/bench_attn_pooled_bf16.py [--case USERS QPU w]... [--iters 1
         K = 6, JX = 300, M = 4, JQ = 30, simiMatrix 2 throughout)
 Under a kernel trace run one child directly:
        <tracer> -- python tools/bench_attn_pooled_bf16.py --child --case 8 8 512 --iters 1 --warmup 0"""
-import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _album_bench as ab
+
 K, JX, M, JQ, SIMI, OWNED, WARP, WINDOW = 6, 300, 4, 30, 2, 8, 5, 3.0
-ap = argparse.ArgumentParser()
-ap.add_argument("--case", type=int, nargs=3, action="append", metavar=("USERS", "QPU", "w"))
-ap.add_argument("--iters", type=int, default=10)
-ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--limit", type=float, default=240.0)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_pooled_bf16_bench.jsonl"))
-ap.add_argument("--child", action="store_true")
-args = ap.parse_args()
-cases = args.case or [[U, qpu, w] for w in (512, 1024) for U, qpu in ((8, 8), (8, 32), (64, 1))]
-
+args = ab.parse(("USERS", "QPU", "w"), [[U, qpu, w] for w in (512, 1024) for U, qpu in ((8, 8), (8, 32), (64, 1))], 240.0,
+                "attn_pooled_bf16_bench.jsonl")
 if not args.child:
-    for case in cases:
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--case"] + [str(v) for v in case] + \
-              ["--iters", str(args.iters), "--warmup", str(args.warmup)]
-        try:
-            p = subprocess.run(cmd, timeout=args.limit, stdout=subprocess.PIPE, text=True)
-            rc, line = p.returncode, p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
-        except subprocess.TimeoutExpired:
-            rc, line = 124, ""
-        if rc != 0:
-            print(json.dumps(dict(case=case, failed=rc)), flush=True)
-            sys.exit(rc)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
-    sys.exit(0)
+    sys.exit(ab.run_parent(__file__, args))
 
-sys.path.insert(0, ROOT)
+sys.path.insert(0, ab.ROOT)
 import torch  # noqa: E402
 from fvta_memexqa_amd import ops  # noqa: E402
 
 ops.require_gpu()                       # raises without a GPU: there is nothing to time on a CPU
-U, QPU, w = cases[0]
+U, QPU, w = args.cases[0]
 P, NQ, T = U * OWNED, U * QPU, M * JX
-g = torch.Generator().manual_seed(U * 1000 + QPU + w)
-pool16 = (torch.randn(P, K, JX, w, generator=g) * 0.5).to(torch.bfloat16).cuda()
+(pool16, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b), pmask, qmask, lists_host = ab.pooled_inputs(
+    ("pool_bf16", "hq", "lq", "W_flat", "b", "WH_W", "WH_b", "WC_W", "WC_b"), (U, QPU, w), K, JX, M, JQ, OWNED)
 pool32 = pool16.float()                 # the same values: what a holder that insists on fp32 keeps
-hq = (torch.randn(NQ, JQ, w, generator=g) * 0.5).cuda()
-lq = (torch.randn(NQ, w, generator=g) * 0.5).cuda()
-W = (torch.randn(2 * w, generator=g) * 0.1).cuda()
-b = (torch.randn(1, generator=g) * 0.1).cuda()
-WH_W = (torch.randn(2 * w, w, generator=g) * (0.3 / w ** 0.5)).cuda()
-WH_b = (torch.randn(w, generator=g) * 0.1).cuda()
-WC_W = (torch.randn(w, generator=g) * (0.5 / w ** 0.5)).cuda()
-WC_b = (torch.randn(1, generator=g) * 0.1).cuda()
-pmask = torch.ones(P, K, JX, dtype=torch.uint8, device="cuda")
-qmask = torch.ones(NQ, JQ, dtype=torch.uint8, device="cuda")
-user = torch.arange(U).repeat_interleave(QPU)[torch.randperm(NQ, generator=g)]
-lists_host = torch.stack([int(u) * OWNED + torch.randperm(OWNED, generator=g)[:M] for u in user])      # [NQ,M]
 lists = ops.check_album_lists(lists_host, P, True).cuda()
 
 pooled = ops.PooledFocalAttention(P, NQ, M, K, JX, JQ, w, SIMI, False)
@@ -99,18 +62,8 @@ rec = dict(users=U, questions_per_user=QPU, owned=OWNED, P=P, NQ=NQ, M=M, K=K, J
            pool_bytes_fp32=pool32.numel() * pool32.element_size(), pool_bytes_bf16=pool16.numel() * pool16.element_size())
 out = {}
 for name, fn in routes.items():
-    for _ in range(args.warmup):
-        fn()
-    ts = []
-    for _ in range(args.iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out[name] = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    rec.update({name + "_ms_median": round(statistics.median(ts), 3), name + "_ms_min": round(min(ts), 3),
-                name + "_ms_max": round(max(ts), 3)})
+    out[name], ts = ab.time_route(fn, args.iters, args.warmup)
+    ab.record_ms(rec, name, ts)
 rec["same_bits"] = bool(torch.equal(out["fp32"], out["bf16"]) and torch.equal(out["fp32_tw"], out["bf16_tw"])
                         and torch.equal(out["fp32_energy"], out["bf16_energy"]))
 rec["h_a_sum"] = float(out["bf16"].double().sum())

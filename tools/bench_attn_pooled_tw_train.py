@@ -23,68 +23,29 @@ Usage: python tools/bench_attn_pooled_tw_train.py [--case USERS QPU w]... [--ite
         K = 6, JX = 300, M = 4, JQ = 30, simiMatrix 2, warp type 5, window 3 throughout)
 Under a kernel trace run one child directly:
        <tracer> -- python tools/bench_attn_pooled_tw_train.py --child --case 8 8 512 --iters 1 --warmup 0 --only pooled"""
-import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _album_bench as ab
+
 K, JX, M, JQ, SIMI, OWNED, WARP, WINDOW = 6, 300, 4, 30, 2, 8, 5, 3.0
-ap = argparse.ArgumentParser()
-ap.add_argument("--case", type=int, nargs=3, action="append", metavar=("USERS", "QPU", "w"))
-ap.add_argument("--iters", type=int, default=10)
-ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--limit", type=float, default=300.0)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_pooled_tw_train_bench.jsonl"))
-ap.add_argument("--only", choices=("pooled_energy", "pooled", "expand"), help="child: run one route only (kernel traces)")
-ap.add_argument("--child", action="store_true")
-args = ap.parse_args()
-cases = args.case or [[U, qpu, w] for w in (512, 1024) for U, qpu in ((8, 8), (8, 32), (64, 1))]
-
+args = ab.parse(("USERS", "QPU", "w"), [[U, qpu, w] for w in (512, 1024) for U, qpu in ((8, 8), (8, 32), (64, 1))], 300.0,
+                "attn_pooled_tw_train_bench.jsonl", only=("pooled_energy", "pooled", "expand"))
 if not args.child:
-    for case in cases:
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--case"] + [str(v) for v in case] + \
-              ["--iters", str(args.iters), "--warmup", str(args.warmup)]
-        try:
-            p = subprocess.run(cmd, timeout=args.limit, stdout=subprocess.PIPE, text=True)
-            rc, line = p.returncode, p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
-        except subprocess.TimeoutExpired:
-            rc, line = 124, ""
-        if rc != 0:
-            print(json.dumps(dict(case=case, failed=rc)), flush=True)
-            sys.exit(rc)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
-    sys.exit(0)
+    sys.exit(ab.run_parent(__file__, args))
 
-sys.path.insert(0, ROOT)
+sys.path.insert(0, ab.ROOT)
 import torch  # noqa: E402
 from fvta_memexqa_amd import autograd, ops  # noqa: E402
 
 ops.require_gpu()                       # raises without a GPU: there is nothing to time on a CPU
-U, QPU, w = cases[0]
+U, QPU, w = args.cases[0]
 P, NQ, T = U * OWNED, U * QPU, M * JX
-g = torch.Generator().manual_seed(U * 1000 + QPU + w)
-pool = (torch.randn(P, K, JX, w, generator=g) * 0.5).cuda()
-hq = (torch.randn(NQ, JQ, w, generator=g) * 0.5).cuda()
-lq = (torch.randn(NQ, w, generator=g) * 0.5).cuda()
-# logits of order 1 at every width under a band of 2 * 3 + 1 = 7 positions (tests/_attn_pool_tw_bwd_ref.py's recipe)
-W = (torch.randn(2 * w, generator=g) * 0.1 * (64.0 / w) ** 0.5 / 49.0).cuda()
-b = (torch.randn(1, generator=g) * 0.1).cuda()
-WH_W = (torch.randn(2 * w, w, generator=g) * (0.3 / w ** 0.5)).cuda()
-WH_b = (torch.randn(w, generator=g) * 0.1).cuda()
-WC_W = (torch.randn(w, generator=g) * (0.5 / w ** 0.5)).cuda()
-WC_b = (torch.randn(1, generator=g) * 0.1).cuda()
-gout = torch.randn(NQ, w, generator=g).cuda()
-pmask = torch.ones(P, K, JX, dtype=torch.uint8, device="cuda")
-qmask = torch.ones(NQ, JQ, dtype=torch.uint8, device="cuda")
-user = torch.arange(U).repeat_interleave(QPU)[torch.randperm(NQ, generator=g)]
-lists_host = torch.stack([int(u) * OWNED + torch.randperm(OWNED, generator=g)[:M] for u in user])      # [NQ,M]
+# W_band: logits of order 1 at every width under the warp's band (tests/_attn_pool_tw_bwd_ref.py's recipe)
+(pool, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b, gout), pmask, qmask, lists_host = ab.pooled_inputs(
+    ("pool", "hq", "lq", "W_band", "b", "WH_W", "WH_b", "WC_W", "WC_b", "gout"), (U, QPU, w), K, JX, M, JQ, OWNED)
 lists = ops.check_album_lists(lists_host, P, True).cuda()
-refs64 = lists.long().reshape(-1)
+lists64 = lists.long()
 
 pooled = ops.PooledWarpedFocalAttention(P, NQ, M, K, JX, JQ, w, SIMI, False, WARP, WINDOW)
 energy = pooled.album_energy(pool, WH_W, WC_W)      # held: it belongs to the pool and the warp's weights
@@ -106,8 +67,7 @@ def route_pooled_energy():
 def route_expand():
     leaves = [t.detach().requires_grad_() for t in (pool, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b)]
     p_, q, l, W_, b_, WH_, WHb_, WC_, WCb_ = leaves
-    rows = p_.index_select(0, refs64).reshape(NQ, M, K, JX, w).permute(0, 2, 1, 3, 4).reshape(NQ, K, T, w).contiguous()
-    mask = pmask.index_select(0, refs64).reshape(NQ, M, K, JX).permute(0, 2, 1, 3).reshape(NQ, K, T).contiguous()
+    rows, mask = ab.gather_lists(p_, pmask, lists64)
     warped, _ = autograd.time_warp(rows, l, WH_, WHb_, WC_, WCb_, WARP, WINDOW)
     h_a, _ = autograd.focal_attention(warped, q, W_, b_, mask, qmask, SIMI, False)
     h_a.backward(gout)
@@ -121,32 +81,8 @@ row_bytes = K * JX * w * 4
 rec = dict(users=U, questions_per_user=QPU, owned=OWNED, P=P, NQ=NQ, M=M, K=K, JX=JX, T=T, JQ=JQ, w=w, simi=SIMI,
            warp_type=WARP, window_t=WINDOW, iters=args.iters, plan=pooled.plan(), bwd_plan=pooled.bwd_plan(),
            pool_bytes=P * row_bytes, expanded_bytes=NQ * M * row_bytes)
-out, ts = {}, {name: [] for name in routes}
-for name, fn in routes.items():         # peak memory of one call of each route, on a warm allocator
-    fn()
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    out[name] = fn()
-    torch.cuda.synchronize()
-    rec[name + "_peak_bytes"] = int(torch.cuda.max_memory_allocated())
-    out[name] = tuple(t.clone() for t in out[name])
-for it in range(args.warmup + args.iters):
-    for name, fn in routes.items():     # alternating: a, a', b, a, a', b, ...
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        res = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        del res
-        if it >= args.warmup:
-            ts[name].append(e0.elapsed_time(e1))
-for name, t in ts.items():
-    rec.update({name + "_ms_median": round(statistics.median(t), 3), name + "_ms_min": round(min(t), 3),
-                name + "_ms_max": round(max(t), 3)})
+out = ab.peak_bytes(routes, rec)
+ab.time_alternating(routes, rec, args.iters, args.warmup)       # a, a', b, a, a', b, ...
 if "pooled" in out and "expand" in out:
-    for i, key in enumerate(("d_pool", "d_hq", "d_lq", "dW", "db", "dWH_W", "dWH_b", "dWC_W", "dWC_b")):
-        x, y = out["pooled"][i], out["expand"][i]
-        rec["max_abs_diff_" + key] = float((x.reshape(-1) - y.reshape(-1)).abs().max())
-        rec["max_abs_" + key] = float(y.abs().max())
+    ab.grad_diffs(rec, ("d_pool", "d_hq", "d_lq", "dW", "db", "dWH_W", "dWH_b", "dWC_W", "dWC_b"), out["pooled"], out["expand"])
 print(json.dumps(rec), flush=True)

@@ -13,57 +13,24 @@ Usage: python tools/bench_attn_shared.py [--case A QPA w]... [--iters 10] [--war
         K = 6, T = 1200, JQ = 30, simiMatrix 2 throughout)
 Under a kernel trace run one child directly:
        <tracer> -- python tools/bench_attn_shared.py --child --case 8 8 1024 --iters 1 --warmup 0"""
-import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _album_bench as ab
+
 K, T, JQ, SIMI = 6, 1200, 30, 2
-ap = argparse.ArgumentParser()
-ap.add_argument("--case", type=int, nargs=3, action="append", metavar=("A", "QPA", "w"))
-ap.add_argument("--iters", type=int, default=10)
-ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--limit", type=float, default=240.0)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_shared_bench.jsonl"))
-ap.add_argument("--child", action="store_true")
-args = ap.parse_args()
-cases = args.case or [[A, qpa, w] for w in (1024, 512) for A, qpa in ((8, 8), (64, 1), (2, 32))]
-
+args = ab.parse(("A", "QPA", "w"), [[A, qpa, w] for w in (1024, 512) for A, qpa in ((8, 8), (64, 1), (2, 32))], 240.0,
+                "attn_shared_bench.jsonl")
 if not args.child:
-    for case in cases:
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--case"] + [str(v) for v in case] + \
-              ["--iters", str(args.iters), "--warmup", str(args.warmup)]
-        try:
-            p = subprocess.run(cmd, timeout=args.limit, stdout=subprocess.PIPE, text=True)
-            rc, line = p.returncode, p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
-        except subprocess.TimeoutExpired:
-            rc, line = 124, ""
-        if rc != 0:
-            print(json.dumps(dict(case=case, failed=rc)), flush=True)
-            sys.exit(rc)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
-    sys.exit(0)
+    sys.exit(ab.run_parent(__file__, args))
 
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
+sys.path.insert(0, ab.ROOT)
 from fvta_memexqa_amd import ops  # noqa: E402
 
 ops.require_gpu()                       # raises without a GPU: there is nothing to time on a CPU
-A, QPA, w = cases[0]
+A, QPA, w = args.cases[0]
 NQ = A * QPA
-g = torch.Generator().manual_seed(A * 1000 + QPA + w)
-hall = (torch.randn(A, K, T, w, generator=g) * 0.5).cuda()
-hq = (torch.randn(NQ, JQ, w, generator=g) * 0.5).cuda()
-W = (torch.randn(2 * w, generator=g) * 0.1).cuda()
-b = (torch.randn(1, generator=g) * 0.1).cuda()
-hmask = torch.ones(A, K, T, dtype=torch.uint8, device="cuda")
-qmask = torch.ones(NQ, JQ, dtype=torch.uint8, device="cuda")
-album_host = torch.arange(A).repeat_interleave(QPA)[torch.randperm(NQ, generator=g)]
+(hall, hq, W, b), hmask, qmask, album_host = ab.shared_inputs(("hall", "hq", "W_flat", "b"), (A, QPA, w), K, T, JQ)
 album = ops.check_album_index(album_host, A).cuda()
 album64 = album.long()
 
@@ -78,18 +45,8 @@ routes = {
 rec = dict(A=A, questions_per_album=QPA, NQ=NQ, K=K, T=T, JQ=JQ, w=w, simi=SIMI, iters=args.iters, plan=shared.plan())
 out = {}
 for name, fn in routes.items():
-    for _ in range(args.warmup):
-        fn()
-    ts = []
-    for _ in range(args.iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out[name] = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    rec.update({name + "_ms_median": round(statistics.median(ts), 3), name + "_ms_min": round(min(ts), 3),
-                name + "_ms_max": round(max(ts), 3)})
+    out[name], ts = ab.time_route(fn, args.iters, args.warmup)
+    ab.record_ms(rec, name, ts)
 rec["max_abs_diff_shared_vs_per_q"] = float((out["shared"] - out["per_q"]).abs().max())
 rec["h_a_sum"] = float(out["shared"].double().sum())
 print(json.dumps(rec), flush=True)

@@ -16,59 +16,25 @@ Usage: python tools/bench_attn_shared_train.py [--case A QPA w]... [--iters 10] 
         w = 512; K = 6, T = 1200, JQ = 30, simiMatrix 2 throughout)
 Under a kernel trace run one child directly:
        <tracer> -- python tools/bench_attn_shared_train.py --child --case 8 8 1024 --iters 1 --warmup 0 --only shared"""
-import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _album_bench as ab
+
 K, T, JQ, SIMI = 6, 1200, 30, 2
-ap = argparse.ArgumentParser()
-ap.add_argument("--case", type=int, nargs=3, action="append", metavar=("A", "QPA", "w"))
-ap.add_argument("--iters", type=int, default=10)
-ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--limit", type=float, default=300.0)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_shared_train_bench.jsonl"))
-ap.add_argument("--only", choices=("shared", "expand"), help="child: run one route only (kernel traces)")
-ap.add_argument("--child", action="store_true")
-args = ap.parse_args()
-cases = args.case or [[8, 8, 1024], [2, 32, 1024], [16, 4, 1024], [64, 1, 1024], [8, 8, 512], [2, 32, 512]]
-
+args = ab.parse(("A", "QPA", "w"), [[8, 8, 1024], [2, 32, 1024], [16, 4, 1024], [64, 1, 1024], [8, 8, 512], [2, 32, 512]], 300.0,
+                "attn_shared_train_bench.jsonl", only=("shared", "expand"))
 if not args.child:
-    for case in cases:
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--case"] + [str(v) for v in case] + \
-              ["--iters", str(args.iters), "--warmup", str(args.warmup)]
-        try:
-            p = subprocess.run(cmd, timeout=args.limit, stdout=subprocess.PIPE, text=True)
-            rc, line = p.returncode, p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
-        except subprocess.TimeoutExpired:
-            rc, line = 124, ""
-        if rc != 0:
-            print(json.dumps(dict(case=case, failed=rc)), flush=True)
-            sys.exit(rc)
-        print(line, flush=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
-    sys.exit(0)
+    sys.exit(ab.run_parent(__file__, args))
 
-sys.path.insert(0, ROOT)
+sys.path.insert(0, ab.ROOT)
 import torch  # noqa: E402
 from fvta_memexqa_amd import ops  # noqa: E402
 
 ops.require_gpu()                       # raises without a GPU: there is nothing to time on a CPU
-A, QPA, w = cases[0]
+A, QPA, w = args.cases[0]
 NQ = A * QPA
-g = torch.Generator().manual_seed(A * 1000 + QPA + w)
-hall = (torch.randn(A, K, T, w, generator=g) * 0.5).cuda()
-hq = (torch.randn(NQ, JQ, w, generator=g) * 0.5).cuda()
-W = (torch.randn(2 * w, generator=g) * 0.1 * (64.0 / w) ** 0.5).cuda()     # logits of order 1 at every width
-b = (torch.randn(1, generator=g) * 0.1).cuda()
-gout = torch.randn(NQ, w, generator=g).cuda()
-hmask = torch.ones(A, K, T, dtype=torch.uint8, device="cuda")
-qmask = torch.ones(NQ, JQ, dtype=torch.uint8, device="cuda")
-album_host = torch.arange(A).repeat_interleave(QPA)[torch.randperm(NQ, generator=g)]
+(hall, hq, W, b, gout), hmask, qmask, album_host = ab.shared_inputs(("hall", "hq", "W", "b", "gout"), (A, QPA, w), K, T, JQ)
 album = ops.check_album_index(album_host, A).cuda()
 album64 = album.long()
 
@@ -99,32 +65,8 @@ if args.only:
     routes = {args.only: routes[args.only]}
 rec = dict(A=A, questions_per_album=QPA, NQ=NQ, K=K, T=T, JQ=JQ, w=w, simi=SIMI, iters=args.iters, plan=shared.plan(),
            bwd_plan=shared.bwd_plan())
-out, ts = {}, {name: [] for name in routes}
-for name, fn in routes.items():         # peak memory of one call of each route, on a warm allocator
-    fn()
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    torch.cuda.reset_peak_memory_stats()
-    out[name] = fn()
-    torch.cuda.synchronize()
-    rec[name + "_peak_bytes"] = int(torch.cuda.max_memory_allocated())
-    out[name] = tuple(t.clone() for t in out[name])
-for it in range(args.warmup + args.iters):
-    for name, fn in routes.items():     # alternating: a, b, a, b, ...
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        res = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        del res
-        if it >= args.warmup:
-            ts[name].append(e0.elapsed_time(e1))
-for name, t in ts.items():
-    rec.update({name + "_ms_median": round(statistics.median(t), 3), name + "_ms_min": round(min(t), 3),
-                name + "_ms_max": round(max(t), 3)})
+out = ab.peak_bytes(routes, rec)
+ab.time_alternating(routes, rec, args.iters, args.warmup)       # a, b, a, b, ...
 if len(out) == 2:
-    for i, key in enumerate(("d_hinfo", "d_hq", "dW", "db")):
-        x, y = out["shared"][i], out["expand"][i]
-        rec["max_abs_diff_" + key] = float((x - y).abs().max())
-        rec["max_abs_" + key] = float(y.abs().max())
+    ab.grad_diffs(rec, ("d_hinfo", "d_hq", "dW", "db"), out["shared"], out["expand"])
 print(json.dumps(rec), flush=True)

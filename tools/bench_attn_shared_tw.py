@@ -23,24 +23,13 @@ Usage: python tools/bench_attn_shared_tw.py [--case A QPA w]... [--iters 10] [--
         warp type 5, window 3.0 throughout: tools/bench_attn_shared.py's shape)
 Under a kernel trace run one child directly:
        <tracer> -- python tools/bench_attn_shared_tw.py --child --case 8 8 512 --iters 1 --warmup 0"""
-import argparse
 import json
-import os
-import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import _album_bench as ab
+
 K, T, JQ, SIMI, WARP, WINDOW = 6, 1200, 30, 2, 5, 3.0
-ap = argparse.ArgumentParser()
-ap.add_argument("--case", type=int, nargs=3, action="append", metavar=("A", "QPA", "w"))
-ap.add_argument("--iters", type=int, default=10)
-ap.add_argument("--warmup", type=int, default=3)
-ap.add_argument("--limit", type=float, default=240.0)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attn_shared_tw_bench.jsonl"))
-ap.add_argument("--child", action="store_true")
-args = ap.parse_args()
-cases = args.case or [[8, 8, 512], [64, 1, 512]]
+args = ab.parse(("A", "QPA", "w"), [[8, 8, 512], [64, 1, 512]], 240.0, "attn_shared_tw_bench.jsonl")
 
 
 def algorithmic_bytes(A, QPA, w, G):
@@ -54,43 +43,17 @@ def algorithmic_bytes(A, QPA, w, G):
 
 
 if not args.child:
-    for case in cases:
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--case"] + [str(v) for v in case] + \
-              ["--iters", str(args.iters), "--warmup", str(args.warmup)]
-        try:
-            p = subprocess.run(cmd, timeout=args.limit, stdout=subprocess.PIPE, text=True)
-            rc, line = p.returncode, p.stdout.strip().splitlines()[-1] if p.stdout.strip() else ""
-        except subprocess.TimeoutExpired:
-            rc, line = 124, ""
-        if rc != 0:
-            print(json.dumps(dict(case=case, failed=rc)), flush=True)
-            sys.exit(rc)
-        print(line, flush=True)
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "a") as f:
-            f.write(line + "\n")
-    sys.exit(0)
+    sys.exit(ab.run_parent(__file__, args))
 
-sys.path.insert(0, ROOT)
+sys.path.insert(0, ab.ROOT)
 import torch  # noqa: E402
 from fvta_memexqa_amd import ops  # noqa: E402
 
 ops.require_gpu()                       # raises without a GPU: there is nothing to time on a CPU
-A, QPA, w = cases[0]
+A, QPA, w = args.cases[0]
 NQ = A * QPA
-g = torch.Generator().manual_seed(A * 1000 + QPA + w)
-hall = (torch.randn(A, K, T, w, generator=g) * 0.5).cuda()
-hq = (torch.randn(NQ, JQ, w, generator=g) * 0.5).cuda()
-lq = (torch.randn(NQ, w, generator=g) * 0.5).cuda()
-W = (torch.randn(2 * w, generator=g) * 0.1 * (64.0 / w) ** 0.5).cuda()
-b = (torch.randn(1, generator=g) * 0.1).cuda()
-WH_W = (torch.randn(2 * w, w, generator=g) * (0.3 / w ** 0.5)).cuda()
-WH_b = (torch.randn(w, generator=g) * 0.1).cuda()
-WC_W = (torch.randn(w, generator=g) * (0.5 / w ** 0.5)).cuda()
-WC_b = (torch.randn(1, generator=g) * 0.1).cuda()
-hmask = torch.ones(A, K, T, dtype=torch.uint8, device="cuda")
-qmask = torch.ones(NQ, JQ, dtype=torch.uint8, device="cuda")
-album_host = torch.arange(A).repeat_interleave(QPA)[torch.randperm(NQ, generator=g)]
+(hall, hq, lq, W, b, WH_W, WH_b, WC_W, WC_b), hmask, qmask, album_host = ab.shared_inputs(
+    ("hall", "hq", "lq", "W", "b", "WH_W", "WH_b", "WC_W", "WC_b"), (A, QPA, w), K, T, JQ)
 album = ops.check_album_index(album_host, A).cuda()
 album64 = album.long()
 
@@ -119,20 +82,9 @@ rec = dict(A=A, questions_per_album=QPA, NQ=NQ, K=K, T=T, JQ=JQ, w=w, simi=SIMI,
 nbytes = algorithmic_bytes(A, QPA, w, plan["G"])
 out = {}
 for name, fn in routes.items():
-    for _ in range(args.warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out[name] = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    med = statistics.median(ts)
-    rec.update({name + "_ms_median": round(med, 3), name + "_ms_min": round(min(ts), 3), name + "_ms_max": round(max(ts), 3),
-                name + "_algorithmic_bytes": nbytes[name], name + "_algorithmic_GBps": round(nbytes[name] / med / 1e6, 1)})
+    out[name], ts = ab.time_route(fn, args.iters, args.warmup)
+    med = ab.record_ms(rec, name, ts)
+    rec.update({name + "_algorithmic_bytes": nbytes[name], name + "_algorithmic_GBps": round(nbytes[name] / med / 1e6, 1)})
 top = float(out["expand"].abs().max())
 rec["max_abs_diff_shared_vs_expand_over_max_abs"] = float((out["shared_held"] - out["expand"]).abs().max()) / top
 rec["held_equals_recomputed"] = bool(torch.equal(out["shared_held"], out["shared_energy"]))

@@ -45,20 +45,27 @@ def test_token_embed_forward_backward(B, J, W, cd, cw, wd, VW, VF, VC):
     g = torch.Generator().manual_seed(5)
     gout = torch.randn(B, J, cw + wd, generator=g)
     (ref * gout.double()).sum().backward()
-    # rows land in an arena with a stride wider than the row (as the padded encoder input has)
+    # rows land in an arena with a stride wider than the row (as the padded encoder input has), in shuffled slots; the
+    # 4-float lead and every slot's 8 pad columns keep their sentinel, bit for bit
     stride = cw + wd + 8
     ntok = B * J
     op = ops.TokenEmbed(ntok, W, cd, cw, wd, VW, VW + VF, VC)
     cu = lambda t: t.cuda().contiguous()
-    tok_off = cu(torch.arange(ntok, dtype=torch.int64) * stride + 4)
-    x = torch.zeros(ntok * stride + 4, device="cuda")
+    slot = cu(torch.randperm(ntok, generator=g))
+    tok_off = slot * stride + 4
+    sentinel = -7777.25
+    x = torch.full((ntok * stride + 4,), sentinel, device="cuda")
     filt = cu(p["filt"].reshape(5, cd, cw))
     args = (cu(ids.reshape(-1)), cu(ch.reshape(-1, W)), tok_off)
     op.forward(*args, cu(p["word_emb"]), cu(p["fixed"]), cu(p["char_emb"]), filt, cu(p["bias"]), x)
-    got = x[4:].view(ntok, stride)[:, :cw + wd]
+    slots = x[4:].view(ntok, stride)
+    got = slots[slot, :cw + wd]
     _close(got, ref.reshape(ntok, -1), msg="x")
+    untouched = torch.full((1,), sentinel, device="cuda").view(torch.int32)
+    assert bool((x[:4].view(torch.int32) == untouched).all()), "the arena's lead was written"
+    assert bool((slots[:, cw + wd:].contiguous().view(torch.int32) == untouched).all()), "a slot's pad columns were written"
     dx = torch.zeros_like(x)
-    dx[4:].view(ntok, stride)[:, :cw + wd] = cu(gout.reshape(ntok, -1))
+    dx[4:].view(ntok, stride)[slot, :cw + wd] = cu(gout.reshape(ntok, -1))
     dwe, dce = torch.zeros(VW, wd, device="cuda"), torch.zeros(VC, cd, device="cuda")
     dfl, dbi = torch.zeros(5, cd, cw, device="cuda"), torch.zeros(cw, device="cuda")
     op.backward(*args, cu(p["char_emb"]), filt, dx, dwe, dce, dfl, dbi)
